@@ -16,9 +16,14 @@ Contract (DESIGN.md "Measurement"):
   * cpu_baseline: the REFERENCE itself (oracle/_ref/ref_driver, built from /root/reference by oracle/Makefile; else the C
     restatement oracle/liboracle.so) on one host core, one full run of the same workload, and `all_cores`: one
     independent run per host core at the same time (both legs after every GPU figure, alone).
-  * OUTPUT: the LAST stdout line is ONE compact JSON record (< 6 KB: `compact_record`); the full record (per-step lists,
-    every kernel class, the sweeps' details, notes) goes to gpurun_out/bench_full_<workload>.json (`--full-out`), never to
-    stdout.  Round 4's 18.9-KB line was not parsed by the driver; tests/test_bench_line.py holds the size.
+  * PLAIN RUN vs `--full`: a plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and prints the line;
+    its roofline block comes from the timed steps' own HIP events and the committed profiles/.  Every figure that takes runs
+    of its own -- R runs per GPU in step, the general functor, the concurrent sweeps, the other configurations, the live PMC
+    passes, the CPU baseline -- and the full record file are taken only with `--full`.
+  * OUTPUT: the LAST stdout line is ONE compact JSON record (< 6 KB: `compact_record`); with `--full` the full record (per-step
+    lists, every kernel class, the sweeps' details, notes) goes to bench_out/bench_full_<workload>.json (`--full-out`), never
+    to stdout.  Round 4's 18.9-KB line was not parsed by the driver; tests/test_bench_line.py holds the size.
+  * `--dump-outputs DIR`: what the timed path handed its caller in the last timed step, as DIR/<name>.npy (`dump_outputs`).
 """
 import argparse
 import ctypes as C
@@ -37,6 +42,7 @@ BYTES_PER_EVAL = 258.0
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8.0 TB/s spec
 GENERAL_PMC_FILES = ("r06_general_pmc.json",)      # PMC passes of the general-functor run (tools/collect_pmc.sh with PC_ABLATE=1)
 COMPACT_LIMIT = 6000        # bytes of the last stdout line (the driver parsed 6.5 KB and 13 KB, not 18.9 KB)
+DUMP_LIMIT = 60_000_000     # bytes of the arrays of --dump-outputs together (under 64 MB with the files' headers)
 # BASELINE.json configs through this harness: kind, nDims, nDerived, nlive, num_repeats, clustering, box, analytic logZ
 WORKLOADS = {
     "c2": dict(kind="gaussian", D=20, nDer=2, nlive=2000, nr=40, clustering=0, box=None, truth=0.0, ref_evals_per_dead=173.9,
@@ -361,6 +367,38 @@ def compact_record(full, full_path=None):
     return out
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------------------------------------------
+RUN_SCALARS = ("logZ", "varlogZ", "ndead", "nlike", "niter", "nlike_failed", "ncluster", "ncluster_dead", "nTotal", "batch")
+MERGED_SCALARS = ("logZ", "varlogZ", "logZ_replay", "varlogZ_replay", "n_runs", "records", "nlike", "ndead_all", "evidence_rule")
+
+
+def dump_outputs(dest, run, merged, limit=DUMP_LIMIT):
+    """DIR/<name>.npy, float64: the last timed step's run as pchip_run hands it back (dead points, their weights and entry contours, the
+    final live set, the evidences and the posterior moments) and the merged result of the exchange step (rank 0's view).  `*_scalars`
+    hold the numbers named in RUN_SCALARS / MERGED_SCALARS, in that order.  If the arrays would pass `limit` bytes together, every array
+    longer than 4096 rows keeps the same fixed, seeded sample of its rows (the same rows for every array of that length), so that two
+    builds given the same arguments write the same rows.  Returns {name: shape written}."""
+    arrs = {"run_" + k: run[k] for k in ("dead", "logweights", "entry", "live", "logZp", "varlogZp", "post_mean", "post_var")}
+    arrs["run_scalars"] = [run[k] for k in RUN_SCALARS]
+    if merged is not None:
+        arrs.update({"merged_" + k: merged[k] for k in ("logweights", "nlive", "post_mean", "post_var")})
+        arrs["merged_scalars"] = [merged[k] for k in MERGED_SCALARS]
+    arrs = {k: np.asarray(v, dtype=np.float64) for k, v in arrs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    small = sum(a.nbytes for a in arrs.values() if a.ndim == 0 or a.shape[0] <= 4096)
+    if total > limit:
+        frac = (limit - small) / float(total - small)
+        for k, a in arrs.items():
+            n = a.shape[0] if a.ndim else 0
+            if n > 4096:
+                rows = np.sort(np.random.default_rng(20240).choice(n, max(1, int(n * frac)), replace=False))
+                arrs[k] = a[rows]
+    os.makedirs(dest, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(dest, k + ".npy"), np.ascontiguousarray(a))
+    return {k: a.shape for k, a in arrs.items()}
+
+
 # ---- ranks ----------------------------------------------------------------------------------------------------------------
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -386,7 +424,12 @@ def parse_args(argv=None):
                          "as `other_configs`; '' = skip")
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed profiles/ instead of two profiled runs now")
     ap.add_argument("--no-extras", action="store_true", help="skip the figures after the timed region (general functor, concurrent sweep)")
-    ap.add_argument("--full-out", default=None, help="where the full record goes (default gpurun_out/bench_full_<workload>.json; '' = nowhere)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: R runs per GPU in step, general functor, concurrent sweeps, other configurations, "
+                         "live PMC passes, CPU baseline, the full record file (a plain run only times the steps)")
+    ap.add_argument("--full-out", default=None, help="where the full record goes (default with --full: bench_out/bench_full_<workload>.json; '' = nowhere)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: the last step's run and merged result as DIR/<name>.npy (float64, < 64 MB in all)")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"), help="process-group backend of the ranks (gloo: the launcher test on CPU)")
     ap.add_argument("--bootstrap-only", action="store_true", help="start the ranks, form the process group, reduce one number over it, print and stop "
                                                                    "(before the library's communicator): tests/test_bench_line.py")
@@ -411,7 +454,8 @@ def bootstrap(args):
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        # (the ranks are children: this process may have opened the GPU above, and such a process is not replaced by exec)
+        raise SystemExit(subprocess.call(cmd))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -475,7 +519,7 @@ class Bench:
         self.wl = WORKLOADS[args.workload]
         self.nlive = args.nlive if args.nlive > 0 else self.wl["nlive"]
         self.s, self.L, self.P, self.keep = self.problem(self.wl, self.nlive, args.batch)
-        self.extras = rank == 0 and world == 1 and not args.no_extras and args.steps > 0
+        self.extras = args.full and rank == 0 and world == 1 and not args.no_extras and args.steps > 0
 
     def cls_bit(self, name):
         return 1 << (self.api.KERNEL_CLASSES.index(name) + 1)
@@ -553,13 +597,15 @@ class Bench:
         self.sync()
         dt = time.perf_counter() - t0
         tmax, (nlike, nfailed) = self.reduce(dt, [float(sum(r["nlike"] for r in runs)), float(sum(r["nlike_failed"] for r in runs))])
+        if args.dump_outputs and self.rank == 0 and last is not None:
+            dump_outputs(args.dump_outputs, last, merged)
         last = None
         return dict(runs=runs, step_ms=step_ms, merged=merged, merge_ms=merge_ms, dt=dt, tmax=tmax, nlike=nlike, nfailed=nfailed)
 
     # ---- R runs of every GPU in step + the exchange of all N R runs (its own barrier-bracketed region; never part of `value`)
     def in_step_multi(self):
         args = self.args
-        if not (args.runs_per_gpu > 1 and args.steps > 0 and not args.no_extras and args.workload != "c5"):
+        if not (args.full and args.runs_per_gpu > 1 and args.steps > 0 and not args.no_extras and args.workload != "c5"):
             return None
         from polychordlite_amd.repeats import run_repeats
         R, api = args.runs_per_gpu, self.api
@@ -898,7 +944,7 @@ def main():
                 "rounds": int(runs[-1]["nrounds"]), "batches": int(runs[-1]["nbatches"]),
                 "paths": {k: v for k, v in runs[-1]["path"].items() if v},
                 "reference_cpu_evals_per_s_survey_container": 357e3}
-        cb = b.leg("cpu_baseline", lambda: CpuBaseline(wl, nlive).finish(), None) if world == 1 and not args.no_cpu else None      # (both legs now, alone: every GPU figure has been taken)
+        cb = b.leg("cpu_baseline", lambda: CpuBaseline(wl, nlive).finish(), None) if args.full and world == 1 and not args.no_cpu else None      # (both legs now, alone: every GPU figure has been taken)
         if cb:
             full["cpu_baseline"] = cb
             # wall clock of one run of the reference / of the engine: what a user waits for (the evals/s ratio also counts the
@@ -910,7 +956,7 @@ def main():
         if b.leg_errors:
             full["leg_errors"] = dict(b.leg_errors)
         full_path = None
-        dest = args.full_out if args.full_out is not None else os.path.join("gpurun_out", "bench_full_%s.json" % args.workload)
+        dest = args.full_out if args.full_out is not None else (os.path.join("bench_out", "bench_full_%s.json" % args.workload) if args.full else "")
         if dest:
             try:
                 os.makedirs(os.path.dirname(os.path.join(ROOT, dest)) or ".", exist_ok=True)

@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,7 +103,7 @@ def test_two_ranks_through_the_whole_harness_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--nlive", "400",
-                        "--runs-per-gpu", "3", "--no-cpu", "--full-out", ""], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+                        "--runs-per-gpu", "3", "--no-cpu", "--full-out", "", "--full"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]
     early, j = lines[0], lines[-1]
@@ -173,6 +174,38 @@ def test_the_latency_block_from_the_committed_cycles():
     kern = [{"kernel": "k_slice", "avg_launch_us": 70.0}]
     lat = bench.latency_model(runs, kern)
     assert lat["model_min"] > 0 and 0.3 < lat["frac_of_model"] < 1.0 and lat["measured_source"].startswith("profiles/r0")
+
+
+def test_full_is_off_by_default():
+    """a plain run takes no figure beside the headline; --full asks for them"""
+    a = bench.parse_args(["--steps", "3"])
+    assert not a.full and a.dump_outputs is None and a.steps == 3
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full
+
+
+def test_dump_outputs_are_float64_bounded_and_the_same_every_time(tmp_path):
+    rng = np.random.default_rng(0)
+    nd, nT = 100_000, 44
+    run = dict(dead=rng.random((nd, nT)), logweights=rng.random(nd), entry=rng.random(nd), live=rng.random((2000, nT)), logZp=np.zeros(1),
+               varlogZp=np.zeros(1), post_mean=rng.random(22), post_var=rng.random(22), **{k: 1 for k in bench.RUN_SCALARS})
+    run["dead"][:, 0] = run["logweights"]
+    merged = dict(logweights=rng.random(nd - 10), nlive=np.arange(nd - 10, dtype=np.int32), post_mean=rng.random(22), post_var=rng.random(22),
+                  **{k: 2 for k in bench.MERGED_SCALARS})
+    whole = bench.dump_outputs(str(tmp_path / "all"), run, merged)
+    assert whole["run_dead"] == (nd, nT) and whole["merged_nlive"] == (nd - 10,)
+    assert np.array_equal(np.load(tmp_path / "all" / "run_dead.npy"), run["dead"])
+    limit = 10_000_000
+    a = bench.dump_outputs(str(tmp_path / "a"), run, merged, limit=limit)
+    b = bench.dump_outputs(str(tmp_path / "b"), run, merged, limit=limit)
+    assert a == b and a["run_dead"][0] < nd and a["run_live"] == (2000, nT)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(k + ".npy" for k in a)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < limit + 128 * len(names)
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float64 and np.array_equal(x, y), n
+    # a sample keeps the same rows of every array of one length: the dead points kept carry their own weights
+    assert np.array_equal(np.load(tmp_path / "a" / "run_dead.npy")[:, 0], np.load(tmp_path / "a" / "run_logweights.npy"))
 
 
 def test_a_leg_that_fails_is_written_down_not_raised():

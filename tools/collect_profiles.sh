@@ -24,7 +24,7 @@ timeout 400 env PC_ABLATE=1 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-f
 python tools/pmc_summary.py "$out/gfetch" "$out/gwrite" "profiles/${tag}_general_pmc.json" "PC_ABLATE=1 rocprofv3 --pmc <COUNTER> --kernel-trace --output-format csv -- $BENCH (one pass per counter; the general-functor path)"
 cp "profiles/${tag}_general_pmc.json" "profiles/${tag}_general_kernel_stats.csv" gpurun_out/
 # the bench line itself (same command plus the CPU baseline and the concurrent-runs capacity figure), with the PMC file in place
-timeout 600 python bench.py --steps 20 --warmup 5 --full-out "gpurun_out/${tag}_bench_full.json" > "profiles/${tag}_bench.json" 2> "$out/bench.log"      # (the compact record the driver parses; the full one beside it)
+timeout 600 python bench.py --full --steps 20 --warmup 5 --full-out "$(dirname "$out")/${tag}_bench_full.json" > "profiles/${tag}_bench.json" 2> "$out/bench.log"      # (the compact record the driver parses; the full one beside it)
 [ -s "profiles/${tag}_bench.json" ] || { rm -f "profiles/${tag}_bench.json"; echo "collect_profiles.sh: bench.py printed no line:" >&2; tail -5 "$out/bench.log" >&2; }
 cp "profiles/${tag}_bench.json" gpurun_out/ 2>/dev/null; cp "gpurun_out/${tag}_bench_full.json" profiles/ 2>/dev/null
 head -5 "profiles/${tag}_kernel_stats.csv"

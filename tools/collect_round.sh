@@ -25,6 +25,7 @@ bash tools/collect_slice_dbg.sh $tag > /dev/null 2>> gpurun_out/${tag}_collect_c
 bash tools/collect_issue_profile.sh $tag > /dev/null 2>> gpurun_out/${tag}_collect_c2.log     # instruction counters of the metric configuration's kernels, single-wave issue intervals
 # the other BASELINE configurations through the same harness: their own line each (with the CPU baseline, the live PMC pass and -- c3, c4:
 # what north_star shards -- sixteen runs in step + the exchange as roofline.in_step_multi)
-for w in c3 c4 c5; do timeout 900 python bench.py --workload $w --steps 3 --warmup 1 --concurrent "" --full-out gpurun_out/${tag}_bench_${w}_full.json > gpurun_out/${tag}_bench_$w.json 2> /dev/null; done
+dst=$(dirname "$out")                   # (where every summary of this script lands)
+for w in c3 c4 c5; do timeout 900 python bench.py --full --workload $w --steps 3 --warmup 1 --concurrent "" --full-out "$dst/${tag}_bench_${w}_full.json" > "$dst/${tag}_bench_$w.json" 2> /dev/null; done
 find gpurun_out -maxdepth 1 -name "${tag}_*" -size 0 -print -delete | sed "s/^/collect_round.sh: EMPTY (removed): /"      # (nothing empty is carried into profiles/)
 ls gpurun_out | grep "^$tag" 
