@@ -14,7 +14,7 @@ module polychord_hip
     private
     public :: polychord_c_interface, polychord_hip_gaussian, polychord_hip_rastrigin, polychord_hip_twin_gaussian, &
               polychord_hip_uniform_prior, polychord_hip_set_gaussian, polychord_hip_set_uniform_prior, &
-              polychord_hip_set_option, run_polychord_hip
+              polychord_hip_set_option, polychord_hip_set_sub_clustering, run_polychord_hip
 
     interface
         subroutine polychord_c_interface(loglike, prior, dumper, nlive, num_repeats, nprior, nfail, do_clustering, &
@@ -73,6 +73,13 @@ module polychord_hip
             import :: c_char, c_double
             character(kind=c_char) :: name(*)
             real(c_double), value :: value
+        end subroutine
+        !> sub-dimension clustering of the next polychord_c_interface calls (the reference's settings%sub_clustering_dimensions):
+        !! n 0-based hypercube indices, clustered on first at every update; n = 0 clears it
+        subroutine polychord_hip_set_sub_clustering(n, dims) bind(c, name="polychord_hip_set_sub_clustering")
+            import :: c_int
+            integer(c_int), value :: n
+            integer(c_int) :: dims(*)
         end subroutine
     end interface
 

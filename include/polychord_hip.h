@@ -95,6 +95,13 @@ double polychord_hip_inv_normal_cdf(double p);
  * "inject_fault" (tests: the next run fails once -- 1: a device allocation, 2: cluster capacity at the next split,
  * 3: growth of the phantom array) */
 void polychord_hip_set_option(const char *name, double value);
+/* sub-dimension clustering of the next polychord_c_interface calls (sticky, like the options above): n 0-based hypercube
+ * indices (pchip_settings.sub_cluster_dims); n = 0 clears it.  polychord_c_interface_ini sets the ini file's markers for
+ * its own call and restores this setting afterwards. */
+void polychord_hip_set_sub_clustering(int n, const int *dims);
+/* the sub-clustering list of an ini file (parameters whose name holds a `*`, ini.f90:389-393; priors.f90:740-741): the
+ * 0-based hypercube indices in parameter order, at most `cap` of them written to dims; returns how many there are */
+int polychord_hip_ini_sub_clustering(const char *inifile, int *dims, int cap);
 /* message of the fatal condition that ended the last polychord_c_interface call in "halt_returns" mode, else NULL */
 const char *polychord_hip_last_error(void);
 void pchip_inject_fault(int kind);
@@ -164,6 +171,11 @@ typedef struct {
     int device_records; /* 1: the run also leaves the records of its points that entered the live set ON THE DEVICE (pchip_result.d_records:
                            what the exchange step of repeat-sharded runs sends; pchip_run_repeats sets it itself).  The dead points of a run
                            are made on the device; without this the merge uploads them again from the host arrays of the result */
+    /* sub-dimension clustering (the ini file's `*` parameter marker; settings%sub_clustering_dimensions, nested_sampling.F90:352-367):
+       with do_clustering, every update first clusters on these n_sub_cluster cube coordinates, then on all of them.  0-based hypercube
+       indices, distances summed in this order (calculate.f90:94-109); an index out of range or given twice fails the run (code 1).
+       0 / NULL: plain clustering.  polychord_hip_set_sub_clustering for polychord_c_interface callers. */
+    int n_sub_cluster; const int *sub_cluster_dims;
 } pchip_settings;
 
 typedef struct {
@@ -226,6 +238,8 @@ enum { PCHIP_PATH_CONSUME_PAR = 0,      /* one cluster: the parallel contraction
        PCHIP_PATH_DEFER_UPDATE = 15,    /* 1: the contraction runs past update triggers */
        PCHIP_PATH_CONSUME_CL_SERIAL = 16,   /* several clusters: k_consume_cl, one wavefront deciding chain after chain (settings.ablate bit 10, or an LDS
                                                block the parallel kernel's tables push over the limit) */
+       PCHIP_PATH_SUBCLUSTER_PASSES = 17,   /* clustering passes on the sub-clustering coordinates (settings.n_sub_cluster > 0: one per update) */
+       PCHIP_PATH_SUBCLUSTER_SPLITS = 18,   /* clusters those passes split */
        PCHIP_PATH_COUNT = 24 };
 
 /* snapshot handed to the update hook: what the reference's file writers see at every update
@@ -270,7 +284,7 @@ typedef struct {
  * bindings rely on).  A binding that mirrors them (ctypes, ISO_C_BINDING, cgo ...) checks itself against the library it loaded:
  * pchip_abi_version() == PCHIP_ABI_VERSION of the header it was written against, and pchip_sizeof("settings" | "result" | "merged" |
  * "like" | "prior" | "update") == the size of its own mirror (0 for an unknown name). */
-#define PCHIP_ABI_VERSION 7
+#define PCHIP_ABI_VERSION 8
 int  pchip_abi_version(void);
 unsigned long pchip_sizeof(const char *struct_name);
 void pchip_settings_default(pchip_settings *s, int nDims, int nDerived);

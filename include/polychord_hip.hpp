@@ -33,6 +33,9 @@ struct Settings {
     std::vector<double> loglikes;
     std::vector<int> nlives;
     int seed = -1;
+    // sub-dimension clustering (an engine extension to the reference's C++ Settings; its Fortran setting of this name): 0-based
+    // cube coordinates clustered on first at every update, then all of them.  Empty: plain clustering.
+    std::vector<int> sub_clustering_dimensions;
     Settings(int _nDims = 0, int _nDerived = 0)
         : nDims(_nDims), nDerived(_nDerived), num_repeats(_nDims * 5), grade_frac{1.0}, grade_dims{_nDims} {}
 };
@@ -45,6 +48,12 @@ inline void run_polychord(double (*loglikelihood)(double *, int, double *, int),
                           void (*dumper)(int, int, int, double *, double *, double *, double, double), Settings s)
 {
     int comm = 0;
+    // the list travels through the library's sticky setting for this call only (cleared again however the call ends)
+    struct SubClustering {
+        bool on;
+        explicit SubClustering(const std::vector<int> &d) : on(!d.empty()) { if (on) polychord_hip_set_sub_clustering((int)d.size(), d.data()); }
+        ~SubClustering() { if (on) polychord_hip_set_sub_clustering(0, nullptr); }
+    } sub(s.sub_clustering_dimensions);
     polychord_c_interface(loglikelihood, prior, dumper, s.nlive, s.num_repeats, s.nprior, s.nfail, s.do_clustering, s.feedback,
                           s.precision_criterion, s.logzero, s.max_ndead, s.boost_posterior, s.posteriors, s.equals,
                           s.cluster_posteriors, s.write_resume, s.write_paramnames, s.read_resume, s.write_stats, s.write_live,

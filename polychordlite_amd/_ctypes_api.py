@@ -33,7 +33,8 @@ class Settings(C.Structure):
                 ("force_general", C.c_int), ("ablate", C.c_int),
                 ("resume_write", C.c_char_p), ("sequential_rng", C.c_int), ("resume_read", C.c_char_p),
                 ("nGrade", C.c_int), ("grade_dims", C.POINTER(C.c_int)), ("grade_repeats", C.POINTER(C.c_int)),
-                ("epoch_discard", C.c_int), ("device_records", C.c_int)]
+                ("epoch_discard", C.c_int), ("device_records", C.c_int),
+                ("n_sub_cluster", C.c_int), ("sub_cluster_dims", C.POINTER(C.c_int))]
 
 
 class Like(C.Structure):
@@ -65,7 +66,7 @@ class Result(C.Structure):
 # pchip_result.path[]: launches per kernel variant (include/polychord_hip.h PCHIP_PATH_*)
 PATH_NAMES = ("consume_par", "consume_cl", "consume_general", "consume_fast", "killoff_par", "killoff_cl", "killoff_general",
               "killoff_fast", "update_fused", "update_steps", "slice_wave", "slice_lane", "nn_lists", "nn_fallbacks", "pool_mode",
-              "defer_update", "consume_cl_serial")
+              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits")
 
 
 _lib = None
@@ -95,6 +96,10 @@ def load():
     lib.polychord_hip_set_uniform_prior.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.polychord_hip_set_corr_gaussian.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double]
     lib.polychord_hip_set_option.argtypes = [C.c_char_p, C.c_double]
+    lib.polychord_hip_set_sub_clustering.argtypes = [C.c_int, C.POINTER(C.c_int)]
+    lib.polychord_hip_set_sub_clustering.restype = None
+    lib.polychord_hip_ini_sub_clustering.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.c_int]
+    lib.polychord_hip_ini_sub_clustering.restype = C.c_int
     # this mirror against the library that was loaded (the structs grow at their end: include/polychord_hip.h PCHIP_ABI_VERSION)
     lib.pchip_sizeof.argtypes = [C.c_char_p]
     lib.pchip_sizeof.restype = C.c_ulong
@@ -139,6 +144,14 @@ def set_grades(settings, dims, repeats):
     settings.grade_dims = gd.ctypes.data_as(C.POINTER(C.c_int))
     settings.grade_repeats = gr.ctypes.data_as(C.POINTER(C.c_int))
     return gd, gr
+
+
+def set_sub_clustering(settings, dims):
+    """sub-dimension clustering on the 0-based cube coordinates `dims` (in this order); returns the array to keep alive"""
+    sd = np.array(list(dims), dtype=np.int32)
+    settings.n_sub_cluster = len(sd)
+    settings.sub_cluster_dims = sd.ctypes.data_as(C.POINTER(C.c_int)) if len(sd) else None
+    return sd
 
 
 class _Owner:

@@ -28,6 +28,7 @@ struct Builtins {
     int cg_D = 0; std::vector<double> cg_invcov, cg_mean; double cg_logdet = 0.0;
     int up_D = 0; std::vector<double> up_lo, up_hi;
     int batch = 0, device = -1, epoch_discard = 0;
+    std::vector<int> sub_dims;                        // polychord_hip_set_sub_clustering: 0-based cube coordinates of the sub-dimension pass
     bool halt_returns = false;                        // fatal conditions return to the caller instead of `stop 1` (language bindings)
     std::string last_error;
 } G;
@@ -470,6 +471,11 @@ void polychord_hip_set_option(const char *name, double value)
     else std::fprintf(stderr, "polychord_hip: unknown option %s\n", name);
 }
 
+void polychord_hip_set_sub_clustering(int n, const int *dims)
+{
+    if (n > 0 && dims) G.sub_dims.assign(dims, dims + n); else G.sub_dims.clear();      // (checked by the run that uses it)
+}
+
 int pchip_abi_version(void) { return PCHIP_ABI_VERSION; }
 unsigned long pchip_sizeof(const char *n)
 {
@@ -677,6 +683,8 @@ static void c_interface_impl(
     s.compression_factor = compression_factor; s.n_nlives = n_nlives; s.loglikes = loglikes; s.nlives = nlives;
     s.seed = seed >= 0 ? seed : (int)(std::chrono::system_clock::now().time_since_epoch().count() & 0x7fffffff); // random_utils.F90:62-79
     s.batch = G.batch; s.device = G.device; s.epoch_discard = G.epoch_discard;
+    const std::vector<int> sub_dims = G.sub_dims;
+    s.n_sub_cluster = (int)sub_dims.size(); s.sub_cluster_dims = sub_dims.empty() ? nullptr : sub_dims.data();
     // tests: the engine's sequential-stream mode through the reference's entry point (draw order of the reference binary;
     // with the RNG shim of oracle/ the two programs then write the same files)
     if (const char *e = std::getenv("PC_SEQUENTIAL_RNG")) s.sequential_rng = std::atoi(e) != 0;
@@ -728,6 +736,11 @@ static void c_interface_impl(
         std::printf("\nPolyChord interface on polychord_hip (MI355X engine)\n");
         std::printf("nlive      : %8d\nnDims      : %8d\nnDerived   : %8d\n", nlive, nDims, nDerived);
         if (do_clustering) std::printf("Doing Clustering\n");
+        if (!sub_dims.empty()) {          // feedback.f90:48-55 (1-based like the reference's list); an empty list prints nothing
+            std::printf("Sub clustering on %4d dimension%s\n", (int)sub_dims.size(), sub_dims.size() == 1 ? "" : "s");
+            for (int d : sub_dims) std::printf("%12d", d + 1);
+            std::printf("\n");
+        }
         if (do_clustering && s.batch != 1)
             std::printf("chains in flight when the list of clusters changes: %s\n",
                         s.epoch_discard ? "all discarded (epoch_discard = 1: the reference farm's rule, nested_sampling.F90:313)"
@@ -775,3 +788,11 @@ static void c_interface_impl(
 }
 
 }  // extern "C"
+
+// polychord_c_interface_ini (pc_ini.hip): the ini file's list for its own call, the caller's setting back afterwards
+std::vector<int> pc_exchange_sub_clustering(const std::vector<int> &dims)
+{
+    std::vector<int> old = G.sub_dims;
+    G.sub_dims = dims;
+    return old;
+}

@@ -6,6 +6,8 @@
 //   k_similarity   S_ab = r_a + r_b - 2 x_a.x_b over the cube coordinates (calculate.f90:94-109),
 //                  one thread per pair, products and sums kept un-fused in dimension order so that the
 //                  neighbour ORDER equals the reference's;
+//   k_similarity_sub (and _b_sub, _b_many_sub)   the same over a list of cube coordinates, in list order: the sub-dimension
+//                  pass (settings%sub_clustering_dimensions, nested_sampling.F90:352-367);
 //   k_knn_sort     compute_knn for every row of a (sub)set at once: the insertion rule of
 //                  clustering.f90:156-172 (first slot with a strictly larger distance) is a stable sort
 //                  by (distance, index); one workgroup sorts one row in LDS (bitonic), which also makes
@@ -36,9 +38,34 @@ __device__ __forceinline__ void similarity_body(const PcState &S, const int *pts
     }
 }
 
+// The same over the cube coordinates dims[0..nd) in that order: the sub-dimension pass of an update (nested_sampling.F90:352-367 clusters
+// on RTI%live(sub_dimensions, :) first; calculate.f90:94-109 then sums over the list's rows in list order).  A body of its own, not a
+// runtime branch in similarity_body: the full-space kernels stay the code they were.  The list is a few entries of a device array the
+// run owns (uniform over the grid: scalar loads); a pass is as many launches as a full one.
+__device__ __forceinline__ void similarity_sub_body(const PcState &S, const int *dims, int nd, const int *pts, int n, double *Sm, int ybase, int ystride)
+{
+    const int a = blockIdx.x;
+    const double *xa = S.live + (size_t)pts[a] * S.nT;
+    double ra = 0.0;
+    for (int k = 0; k < nd; ++k) { const double v = xa[dims[k]]; ra = __dadd_rn(ra, __dmul_rn(v, v)); }
+    for (int b = ybase + threadIdx.x; b < n; b += ystride) {
+        const double *xb = S.live + (size_t)pts[b] * S.nT;
+        double rb = 0.0, s = 0.0;
+        for (int k = 0; k < nd; ++k) {
+            const int d = dims[k];
+            rb = __dadd_rn(rb, __dmul_rn(xb[d], xb[d])); s = __dadd_rn(s, __dmul_rn(xa[d], xb[d]));
+        }
+        Sm[(size_t)a * n + b] = __dadd_rn(__dadd_rn(ra, rb), -__dmul_rn(2.0, s));
+    }
+}
+
 __global__ __launch_bounds__(256) void k_similarity(PcState S, const int *pts, int n, double *Sm)
 {
     similarity_body(S, pts, n, Sm, blockIdx.y * 256, gridDim.y * 256);
+}
+__global__ __launch_bounds__(256) void k_similarity_sub(PcState S, const int *dims, int nd, const int *pts, int n, double *Sm)
+{
+    similarity_sub_body(S, dims, nd, pts, n, Sm, blockIdx.y * 256, gridDim.y * 256);
 }
 // One descriptor per cluster that is looked at in an update: {cluster, points, offset of its n x n blocks, offset of its labels}.
 // The first pass of do_clustering (clustering.f90:253-324) over ALL clusters of an update is three launches with the cluster
@@ -50,6 +77,12 @@ __global__ __launch_bounds__(256) void k_similarity_b(PcState S, const ClusDesc 
     const ClusDesc d = desc[blockIdx.y];
     if ((int)blockIdx.x >= d.n) return;
     similarity_body(S, S.cl_list + (size_t)d.c * S.Ncap, d.n, Sm + d.off2, 0, 256);
+}
+__global__ __launch_bounds__(256) void k_similarity_b_sub(PcState S, const int *dims, int nd, const ClusDesc *desc, double *Sm)
+{
+    const ClusDesc d = desc[blockIdx.y];
+    if ((int)blockIdx.x >= d.n) return;
+    similarity_sub_body(S, dims, nd, S.cl_list + (size_t)d.c * S.Ncap, d.n, Sm + d.off2, 0, 256);
 }
 
 // rows of the sub-matrix S(gidx, gidx) sorted by (distance, local index): knn[a*m + r] = r-th neighbour
@@ -375,6 +408,17 @@ __global__ __launch_bounds__(256) void k_similarity_b_many(const PcManyRec *__re
     if ((int)blockIdx.x >= d.n) return;
     similarity_body(r.S, r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[1] + d.off2, 0, 256);
 }
+// ... launched instead when a run of the launch makes its sub-dimension pass (p[5] its coordinates, ia[3] how many; a run with ia[3] = 0
+// in the same launch makes its full pass here, by the full-space body)
+__global__ __launch_bounds__(256) void k_similarity_b_many_sub(const PcManyRec *__restrict__ R)
+{
+    const PcManyView r = pc_many_view(R, blockIdx.z);
+    if ((int)blockIdx.y >= r.ia[1]) return;
+    const ClusDesc d = ((const ClusDesc *)r.p[0])[blockIdx.y];
+    if ((int)blockIdx.x >= d.n) return;
+    if (r.ia[3] > 0) similarity_sub_body(r.S, (const int *)r.p[5], r.ia[3], r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[1] + d.off2, 0, 256);
+    else similarity_body(r.S, r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[1] + d.off2, 0, 256);
+}
 __global__ __launch_bounds__(256) void k_knn_sort_b_many(const PcManyRec *__restrict__ R)
 {
     const PcManyView r = pc_many_view(R, blockIdx.z);
@@ -483,9 +527,11 @@ void pc_launch_shift_mats(const PcState *S, int p, int nc, hipStream_t st)
     if (p < nc - 1) hipLaunchKernelGGL(k_shift_mats, dim3(1), dim3(256), 0, st, *S, p, nc);
 }
 
-void pc_launch_similarity(const PcState *S, const int *pts, int n, double *Sm, hipStream_t st)
+// (dims / nd: the sub-dimension pass's coordinates, nd = 0 the full space -- in this and the batched launchers below)
+void pc_launch_similarity(const PcState *S, const int *pts, int n, double *Sm, const int *dims, int nd, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_similarity, dim3(n, (n + 1023) / 1024), dim3(256), 0, st, *S, pts, n, Sm);
+    if (nd > 0) hipLaunchKernelGGL(k_similarity_sub, dim3(n, (n + 1023) / 1024), dim3(256), 0, st, *S, dims, nd, pts, n, Sm);
+    else hipLaunchKernelGGL(k_similarity, dim3(n, (n + 1023) / 1024), dim3(256), 0, st, *S, pts, n, Sm);
 }
 
 int pc_launch_knn_cluster(const double *Sm, int nroot, const int *gidx, int m, int *knn, int *labels, int *out, hipStream_t st)
@@ -503,7 +549,8 @@ int pc_launch_knn_cluster(const double *Sm, int nroot, const int *gidx, int m, i
 }
 
 // first pass over `nd` clusters at once (descriptors on the device, host copy for the grid): out[k] = clusters found in the k-th
-int pc_launch_knn_cluster_batch(const PcState *S, const int *h_desc, const int *d_desc, int nd, double *Sm, int *knn, int *labels, int *out, hipStream_t st)
+int pc_launch_knn_cluster_batch(const PcState *S, const int *h_desc, const int *d_desc, int nd, double *Sm, int *knn, int *labels, int *out,
+                                const int *dims, int ndims, hipStream_t st)
 {
     if (nd <= 0) return 0;
     int nmax = 0;
@@ -515,14 +562,16 @@ int pc_launch_knn_cluster_batch(const PcState *S, const int *h_desc, const int *
     pc_need_dyn_lds((const void *)k_knn_sort_b, sh);
     pc_need_dyn_lds((const void *)k_nn_cluster_b, sh2);
     const ClusDesc *dd = (const ClusDesc *)d_desc;
-    hipLaunchKernelGGL(k_similarity_b, dim3(nmax, nd), dim3(256), 0, st, *S, dd, Sm);
+    if (ndims > 0) hipLaunchKernelGGL(k_similarity_b_sub, dim3(nmax, nd), dim3(256), 0, st, *S, dims, ndims, dd, Sm);
+    else hipLaunchKernelGGL(k_similarity_b, dim3(nmax, nd), dim3(256), 0, st, *S, dd, Sm);
     hipLaunchKernelGGL(k_knn_sort_b, dim3(nmax, nd), dim3(256), sh, st, (const double *)Sm, dd, knn);
     hipLaunchKernelGGL(k_nn_cluster_b, dim3(nd), dim3(1024), sh2, st, (const int *)knn, dd, labels, out);
     return 0;
 }
 
 // the same with the largest cluster given (no host copy of the descriptors at hand: a record of the runs in step launched on its own)
-int pc_launch_knn_cluster_batch_dev(const PcState *S, const int *d_desc, int nd, int nmax, double *Sm, int *knn, int *labels, int *out, hipStream_t st)
+int pc_launch_knn_cluster_batch_dev(const PcState *S, const int *d_desc, int nd, int nmax, double *Sm, int *knn, int *labels, int *out,
+                                    const int *dims, int ndims, hipStream_t st)
 {
     if (nd <= 0) return 0;
     int npow2 = 2;
@@ -532,12 +581,13 @@ int pc_launch_knn_cluster_batch_dev(const PcState *S, const int *d_desc, int nd,
     pc_need_dyn_lds((const void *)k_knn_sort_b, sh);
     pc_need_dyn_lds((const void *)k_nn_cluster_b, sh2);
     const ClusDesc *dd = (const ClusDesc *)d_desc;
-    hipLaunchKernelGGL(k_similarity_b, dim3(nmax, nd), dim3(256), 0, st, *S, dd, Sm);
+    if (ndims > 0) hipLaunchKernelGGL(k_similarity_b_sub, dim3(nmax, nd), dim3(256), 0, st, *S, dims, ndims, dd, Sm);
+    else hipLaunchKernelGGL(k_similarity_b, dim3(nmax, nd), dim3(256), 0, st, *S, dd, Sm);
     hipLaunchKernelGGL(k_knn_sort_b, dim3(nmax, nd), dim3(256), sh, st, (const double *)Sm, dd, knn);
     hipLaunchKernelGGL(k_nn_cluster_b, dim3(nd), dim3(1024), sh2, st, (const int *)knn, dd, labels, out);
     return 0;
 }
-int pc_launch_knn_cluster_batch_many(const PcState *S, const PcManyRec *dR, int R, int nd_max, int nmax, hipStream_t st)
+int pc_launch_knn_cluster_batch_many(const PcState *S, const PcManyRec *dR, int R, int nd_max, int nmax, int any_sub, hipStream_t st)
 {
     (void)S;
     if (nd_max <= 0) return 0;
@@ -547,7 +597,8 @@ int pc_launch_knn_cluster_batch_many(const PcState *S, const PcManyRec *dR, int 
     if (sh > 160 * 1024 || sh2 > 150 * 1024) return 1;
     pc_need_dyn_lds((const void *)k_knn_sort_b_many, sh);
     pc_need_dyn_lds((const void *)k_nn_cluster_b_many, sh2);
-    hipLaunchKernelGGL(k_similarity_b_many, dim3(nmax, nd_max, R), dim3(256), 0, st, dR);
+    if (any_sub) hipLaunchKernelGGL(k_similarity_b_many_sub, dim3(nmax, nd_max, R), dim3(256), 0, st, dR);
+    else hipLaunchKernelGGL(k_similarity_b_many, dim3(nmax, nd_max, R), dim3(256), 0, st, dR);
     hipLaunchKernelGGL(k_knn_sort_b_many, dim3(nmax, nd_max, R), dim3(256), sh, st, dR);
     hipLaunchKernelGGL(k_nn_cluster_b_many, dim3(nd_max, R), dim3(1024), sh2, st, dR);
     return 0;

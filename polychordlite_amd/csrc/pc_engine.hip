@@ -48,8 +48,8 @@ int pc_launch_nhats_many(const PcState *, const PcManyRec *, int, int, hipStream
 int pc_launch_nn_lists_many(const PcState *, const PcManyRec *, int, int, int, hipStream_t);
 int pc_launch_consume_cl_many(const PcState *, const PcManyRec *, int, int, hipStream_t);
 int pc_launch_reset_thresholds_many(const PcState *, const PcManyRec *, int, hipStream_t);
-int pc_launch_knn_cluster_batch_many(const PcState *, const PcManyRec *, int, int, int, hipStream_t);
-int pc_launch_knn_cluster_batch_dev(const PcState *, const int *, int, int, double *, int *, int *, int *, hipStream_t);
+int pc_launch_knn_cluster_batch_many(const PcState *, const PcManyRec *, int, int, int, int, hipStream_t);
+int pc_launch_knn_cluster_batch_dev(const PcState *, const int *, int, int, double *, int *, int *, int *, const int *, int, hipStream_t);
 int pc_launch_knn_cluster_sub(const int *, int, int, const double *, const int *, int *, int *, int *, hipStream_t);
 int pc_launch_knn_cluster_sub_many(const PcManyRec *, int, int, int, hipStream_t);
 int pc_launch_slice_t(const PcState *, unsigned, int, hipStream_t);
@@ -84,9 +84,9 @@ void pc_launch_clean(const PcState *, int, unsigned char *, int *, int *, double
                      unsigned long long *, int *, hipStream_t);
 void pc_launch_reset_thresholds(const PcState *, hipStream_t);
 int pc_cov_nchunk(const PcState *, int);
-void pc_launch_similarity(const PcState *, const int *, int, double *, hipStream_t);
+void pc_launch_similarity(const PcState *, const int *, int, double *, const int *, int, hipStream_t);
 int pc_launch_knn_cluster(const double *, int, const int *, int, int *, int *, int *, hipStream_t);
-int pc_launch_knn_cluster_batch(const PcState *, const int *, const int *, int, double *, int *, int *, int *, hipStream_t);
+int pc_launch_knn_cluster_batch(const PcState *, const int *, const int *, int, double *, int *, int *, int *, const int *, int, hipStream_t);
 void pc_launch_rebuild(const PcState *, int, hipStream_t);
 void pc_launch_ph_rehome(const PcState *, int, int, const unsigned *, int, int *, hipStream_t);
 void pc_launch_slice_tick(const PcState *, unsigned, int, void *, double *, int *, double *, const double *, const double *,
@@ -615,7 +615,7 @@ struct Cohort {
         case CK_NN: pc_launch_nn_lists(&r.S, r.ia[1], 1, st); break;      // (the run's CK_SORT of this round has been launched: kinds go in order)
         case CK_RESET: pc_launch_reset_thresholds(&r.S, st); break;
         case CK_CLUSG: (void)pc_launch_knn_cluster_sub((const int *)r.p[0], r.ia[1], r.ia[2], (const double *)r.p[1], (const int *)r.p[2], (int *)r.p[3], (int *)r.p[4], (int *)r.p[5], st); break;
-        case CK_CLUS1: (void)pc_launch_knn_cluster_batch_dev(&r.S, (const int *)r.p[0], r.ia[1], r.ia[2], (double *)r.p[1], (int *)r.p[2], (int *)r.p[3], (int *)r.p[4], st); break;
+        case CK_CLUS1: (void)pc_launch_knn_cluster_batch_dev(&r.S, (const int *)r.p[0], r.ia[1], r.ia[2], (double *)r.p[1], (int *)r.p[2], (int *)r.p[3], (int *)r.p[4], (const int *)r.p[5], r.ia[3], st); break;
         case CK_CONSUME_CL: (void)pc_launch_consume_cl(&r.S, r.a[0] ? 65 : 2, st); break;
         case CK_SORT: (void)pc_launch_sort_live(&r.S, st); break;
         case CK_CONSUME: (void)pc_launch_consume_par(&r.S, st); break;
@@ -706,7 +706,7 @@ struct Cohort {
             case CK_CONSUME_CL: rc = pc_launch_consume_cl_many(&f.S, d, cnt, (int)f.a[0], q); break;
             case CK_RESET: rc = pc_launch_reset_thresholds_many(&f.S, d, cnt, q); break;
             case CK_CLUSG: { int nbm = 0, nmx = 0; for (size_t x = i; x < j; ++x) { nbm = std::max(nbm, ord[x]->ia[1]); nmx = std::max(nmx, ord[x]->ia[2]); } rc = pc_launch_knn_cluster_sub_many(d, cnt, nbm, nmx, q); } break;
-            case CK_CLUS1: { int ndm = 0, nmx = 0; for (size_t x = i; x < j; ++x) { ndm = std::max(ndm, ord[x]->ia[1]); nmx = std::max(nmx, ord[x]->ia[2]); } rc = pc_launch_knn_cluster_batch_many(&f.S, d, cnt, ndm, nmx, q); } break;
+            case CK_CLUS1: { int ndm = 0, nmx = 0, sub = 0; for (size_t x = i; x < j; ++x) { ndm = std::max(ndm, ord[x]->ia[1]); nmx = std::max(nmx, ord[x]->ia[2]); sub |= ord[x]->ia[3] > 0; } rc = pc_launch_knn_cluster_batch_many(&f.S, d, cnt, ndm, nmx, sub, q); } break;
             case CK_SORT: rc = pc_launch_sort_live_many(&f.S, d, cnt, q); break;
             case CK_CONSUME: rc = pc_launch_consume_par_many(&f.S, d, cnt, q); break;
             case CK_FINAL: rc = pc_launch_final_par_many(d, cnt, q); break;
@@ -870,6 +870,15 @@ struct Engine {
             S.g_col0[g] = col; S.g_e0[g] = (int)S.n_dev;
             col += S.g_nr[g]; S.nb_total += S.g_nb[g]; S.n_dev += (unsigned)S.g_nb[g] * Dg * Dg;
         }
+        // sub-dimension clustering: the list is checked whether or not the run clusters (a bad list is a bad setting either way)
+        sub_dims.clear();
+        if (c.n_sub_cluster < 0 || (c.n_sub_cluster > 0 && !c.sub_cluster_dims)) engine_fail(PC_RC_SETTINGS, "n_sub_cluster = %d without a list of coordinates", c.n_sub_cluster);
+        for (int k = 0; k < c.n_sub_cluster; ++k) {
+            const int d = c.sub_cluster_dims[k];
+            if (d < 0 || d >= D) engine_fail(PC_RC_SETTINGS, "sub-clustering coordinate %d out of range (nDims = %d; the indices are 0-based)", d, D);
+            if (std::find(sub_dims.begin(), sub_dims.end(), d) != sub_dims.end()) engine_fail(PC_RC_SETTINGS, "sub-clustering coordinate %d given twice", d);
+            sub_dims.push_back(d);
+        }
         S.ch_nlike_g = nullptr;
         std::memset(nlike_g, 0, sizeof(nlike_g));
         S.p0 = D; S.d0 = 2 * D; S.b0 = 2 * D + nDer; S.l0 = S.b0 + 1;
@@ -969,6 +978,7 @@ struct Engine {
         if (c.do_clustering) {      // candidate lists of the nearest-cluster search (k_nn_lists)
             S.nn_list = dalloc<int>((size_t)B * nr * PC_NN_K); S.nn_slot_owner = dalloc<int>(Ncap); S.nn_chain_slot = dalloc<int>(B);
             S.nn_pts = dalloc<double>((size_t)(Ncap + B) * D); S.nn_code = dalloc<int>((size_t)2 * Ncap + B + 64);      // (codes of the candidates, then the ranks of the live points and their number: k_sort_live)
+            if (!sub_dims.empty()) { c_subdims = dalloc<int>(sub_dims.size()); upload(c_subdims, sub_dims.data(), sizeof(int) * sub_dims.size()); }
         }
         S.nhat = dalloc<double>((size_t)B * nr * D); S.nhat_w = dalloc<double>((size_t)B * nr);
         static const bool ms_off = std::getenv("PC_MS_PRE_OFF") != nullptr;
@@ -1512,7 +1522,22 @@ struct Engine {
             h_ctl->nphantom = total;
             if (seq_post) seq_consume((unsigned long long)(nph - total));
         }
-        if (cfg.do_clustering) do_clustering(cn);
+        if (cfg.do_clustering) {
+            // nested_sampling.F90:352-367: the sub-dimension pass first, then the full one over every cluster there is after it (the sizes
+            // fetched again when the first pass split); the chains in the nursery follow the list through both (cmap_total)
+            if (sub_dims.empty()) do_clustering(cn);
+            else {
+                const int nold = h_ctl->ncluster;
+                std::vector<int> map1, map2;
+                path[PCHIP_PATH_SUBCLUSTER_PASSES]++;
+                const long s0 = nsplits;
+                bool found = do_clustering(cn, c_subdims, (int)sub_dims.size(), &map1);
+                if (found) { path[PCHIP_PATH_SUBCLUSTER_SPLITS] += nsplits - s0; cn.clear(); }      // (the full pass asks for the sizes again)
+                found = do_clustering(cn, nullptr, 0, &map2) || found;
+                for (int &m : map1) m = m >= 0 ? map2[(size_t)m] : -1;        // the update's cluster j -> its place after both passes
+                if (found && !cfg.epoch_discard) remap_nursery(map1, nold);
+            }
+        }
         hipEvent_t e1 = kt.begin(KT_COV);
         covmats(total, h_ctl->ncluster);
         kt.end(KT_COV, e1);
@@ -1684,6 +1709,7 @@ struct Engine {
     // goes through the per-cluster path with its recursion and add_cluster, in the reference's order
     int *c_desc = nullptr, *c_bout = nullptr; int c_desc_cap = 0;
     int *c_map = nullptr; int c_map_cap = 0;
+    std::vector<int> sub_dims; int *c_subdims = nullptr;     // sub-dimension clustering: the run's coordinates (settings.sub_cluster_dims), on the device
     int *c_gdesc = nullptr, *c_gpool = nullptr, *c_glab = nullptr, *c_gout = nullptr; int c_g_cap = 0;
     // NN_clustering's recursion (clustering.f90:80-95) level by level.  The reference re-clusters every cluster it finds, alone, until one
     // pass over it finds a single cluster; the labels it returns are the final parts numbered by first appearance (relabel after every
@@ -1751,7 +1777,9 @@ struct Engine {
         }
         return true;
     }
-    bool do_clustering(std::vector<int> cn = std::vector<int>())
+    // dims / nd: the coordinates of the sub-dimension pass (nd = 0: all).  cmap_out: the pass leaves the map of the list's clusters
+    // through it there and does not move the nursery's chains itself (two passes in one update: the caller composes the two maps)
+    bool do_clustering(std::vector<int> cn = std::vector<int>(), const int *dims = nullptr, int nd_sub = 0, std::vector<int> *cmap_out = nullptr)
     {
         ensure_cluster_scratch();
         bool found = false;
@@ -1775,8 +1803,8 @@ struct Engine {
                 int nmax1 = 0;
                 for (int k = 0; k < nd; ++k) nmax1 = std::max(nmax1, desc[4 * k + 1]);
                 // (in step with other runs: the first pass of all runs that update in this round in three launches)
-                if (co) co->rec(CK_CLUS1, S, {c_desc, c_Sm, c_knn, c_lab, c_bout}, {}, {0, nd, nmax1});
-                else if (pc_launch_knn_cluster_batch(&S, desc.data(), c_desc, nd, c_Sm, c_knn, c_lab, c_bout, st)) engine_fail(PC_RC_LDS, "a cluster too large for the LDS kNN sort");
+                if (co) co->rec(CK_CLUS1, S, {c_desc, c_Sm, c_knn, c_lab, c_bout, (void *)dims}, {}, {0, nd, nmax1, nd_sub});
+                else if (pc_launch_knn_cluster_batch(&S, desc.data(), c_desc, nd, c_Sm, c_knn, c_lab, c_bout, dims, nd_sub, st)) engine_fail(PC_RC_LDS, "a cluster too large for the LDS kNN sort");
                 std::vector<int> out, lab0;
                 fetch(out, (const int *)c_bout, (size_t)nd);
                 fetch(lab0, (const int *)c_lab, (size_t)o1);       // (the first pass' labels of every cluster: a few KB, the same wait)
@@ -1801,7 +1829,7 @@ struct Engine {
             } else if (n > 2 && verdict[j] > 1) {
                 direct_op();
                 HIPCHK(hipMemcpyAsync(c_pts, S.cl_list + (size_t)ic * S.Ncap, sizeof(int) * n, hipMemcpyDeviceToDevice, st));
-                pc_launch_similarity(&S, c_pts, n, c_Sm, st);
+                pc_launch_similarity(&S, c_pts, n, c_Sm, dims, nd_sub, st);
                 std::vector<int> gidx(n), labels;
                 for (int i = 0; i < n; ++i) gidx[i] = i;
                 const int num = nn_clustering(n, gidx, labels);
@@ -1811,17 +1839,21 @@ struct Engine {
         }
         if (found) {
             if (cfg.epoch_discard) h_ctl->admin_epoch++;         // nested_sampling.F90:331-333 as written: every chain in flight is lost
-            else if (h_ctl->i_nursery > 0) {
-                // the engine's rule: the chains seeded in clusters this update left alone stay in the nursery, under their new numbers
-                if (c_map_cap < nold) { dfree(c_map); c_map_cap = std::max(2 * nold, 64); c_map = dalloc<int>(c_map_cap); }
-                send_raw(c_map, cmap.data(), sizeof(int) * (size_t)nold);
-                direct_op();
-                pc_launch_remap_chains(&S, c_map, nold, h_ctl->i_nursery, st);
-            }
+            else if (!cmap_out) remap_nursery(cmap, nold);
             h_ctl->status = PC_ST_RUNNING;
             send_raw(S.ctl, h_ctl, sizeof(PcCtl));
         }
+        if (cmap_out) cmap_out->swap(cmap);
         return found;
+    }
+    // the engine's rule (epoch_discard = 0): the chains seeded in clusters the update left alone stay in the nursery, under their new numbers
+    void remap_nursery(const std::vector<int> &cmap, int nold)
+    {
+        if (h_ctl->i_nursery <= 0) return;
+        if (c_map_cap < nold) { dfree(c_map); c_map_cap = std::max(2 * nold, 64); c_map = dalloc<int>(c_map_cap); }
+        send_raw(c_map, cmap.data(), sizeof(int) * (size_t)nold);
+        direct_op();
+        pc_launch_remap_chains(&S, c_map, nold, h_ctl->i_nursery, st);
     }
 
     void covmats(int nph, int nc)
@@ -2812,7 +2844,7 @@ struct Engine {
         dfree(d_x0s); dfree(d_prop); dfree(d_ans); dfree(d_decks);
         if (hp_prop) { hfree(hp_prop); hp_prop = nullptr; } if (hp_ans) { hfree(hp_ans); hp_ans = nullptr; } if (hp_need) { hfree(hp_need); hp_need = nullptr; }
         dfree(upd_part); dfree(upd_shift); upd_part_cap = 0;
-        dfree(c_gdesc); dfree(c_gpool); dfree(c_glab); dfree(c_gout); c_g_cap = 0; dfree(c_map); c_map_cap = 0; dfree(c_desc); dfree(c_bout); dfree(c_Sm); dfree(c_pts); dfree(c_gidx); dfree(c_knn); dfree(c_lab); dfree(c_out); dfree(c_cnt); dfree(c_olduid); c_cap = 0; c_desc_cap = 0;   // (the clustering scratch used to stay behind: 12 MB per clustered run)
+        dfree(c_gdesc); dfree(c_gpool); dfree(c_glab); dfree(c_gout); c_g_cap = 0; dfree(c_map); c_map_cap = 0; dfree(c_subdims); dfree(c_desc); dfree(c_bout); dfree(c_Sm); dfree(c_pts); dfree(c_gidx); dfree(c_knn); dfree(c_lab); dfree(c_out); dfree(c_cnt); dfree(c_olduid); c_cap = 0; c_desc_cap = 0;   // (the clustering scratch used to stay behind: 12 MB per clustered run)
         for (void *h : staged_up) hfree(h);
         staged_up.clear();
         for (const Fetch &f : fetching) hfree(f.h);

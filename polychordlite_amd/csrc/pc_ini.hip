@@ -23,7 +23,7 @@ std::string trim(const std::string &s)
     return a == std::string::npos ? "" : s.substr(a, b - a + 1);
 }
 
-struct Param { std::string name, latex; int speed = 1; std::string prior; int block = 1; std::vector<double> pp; };
+struct Param { std::string name, latex; int speed = 1; std::string prior; int block = 1; std::vector<double> pp; bool sub_cluster = false; };
 
 struct Ini {
     std::vector<std::pair<std::string, std::string>> kv;
@@ -70,7 +70,9 @@ Ini read_ini(const std::string &file)
                 if (parts.size() < 6) halt_program("ini error: malformed parameter line: " + line);
                 Param p; p.name = parts[0]; p.latex = parts[1]; p.speed = std::atoi(parts[2].c_str()); p.prior = parts[3];
                 p.block = std::atoi(parts[4].c_str());
-                if (!p.name.empty() && p.name.back() == '*') p.name.pop_back();       // sub-clustering marker
+                // sub-clustering marker (ini.f90:389-393): the name cut at its FIRST `*`, the parameter flagged
+                const size_t star = p.name.find('*');
+                if (star != std::string::npos) { p.name = trim(p.name.substr(0, star)); p.sub_cluster = true; }
                 std::stringstream ss(parts[5]); double v; while (ss >> v) p.pp.push_back(v);
                 ini.params.push_back(p);
             } else {
@@ -160,7 +162,45 @@ void ini_prior(double *cube_h, double *theta, int nDims)
     }
 }
 
+// hypercube index of every parameter (priors.f90:708-737): the speeds relabelled 1, 2, 3.. in increasing order, the cube lists the
+// parameters grade by grade, file order within a grade; grade_dims = parameters per grade
+std::vector<int> hypercube_indices(const std::vector<Param> &params, std::vector<int> *grade_dims = nullptr)
+{
+    const int nDims = (int)params.size();
+    std::vector<int> distinct, hyper((size_t)nDims, 0);
+    for (auto &p : params) distinct.push_back(p.speed);
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    int h = 0;
+    for (size_t g = 0; g < distinct.size(); ++g) {
+        int cnt = 0;
+        for (int i = 0; i < nDims; ++i) if (params[i].speed == distinct[g]) { hyper[i] = h++; cnt++; }
+        if (grade_dims) grade_dims->push_back(cnt);
+    }
+    return hyper;
+}
+
+// settings%sub_clustering_dimensions = pack(hypercube_indices, sub_cluster) (priors.f90:740-741): the marked parameters' cube
+// coordinates in PARAMETER order (not sorted), 0-based here
+std::vector<int> sub_clustering_dims(const std::vector<Param> &params, const std::vector<int> &hyper)
+{
+    std::vector<int> out;
+    for (size_t i = 0; i < params.size(); ++i) if (params[i].sub_cluster) out.push_back(hyper[i]);
+    return out;
+}
+
 }  // namespace
+
+std::vector<int> pc_exchange_sub_clustering(const std::vector<int> &dims);      // (pc_abi.hip)
+
+// the sub-clustering list of an ini file (tests; tools): the count, and the first `cap` entries in dims
+extern "C" int polychord_hip_ini_sub_clustering(const char *inifile, int *dims, int cap)
+{
+    const Ini ini = read_ini(inifile ? inifile : "");
+    const std::vector<int> sub = sub_clustering_dims(ini.params, hypercube_indices(ini.params));
+    for (int k = 0; k < (int)sub.size() && k < cap; ++k) dims[k] = sub[k];
+    return (int)sub.size();
+}
 
 // AS241 / PPND16 on the host (utils.F90:806-966), the inverse normal CDF every Gaussian prior uses
 extern "C" double polychord_hip_inv_normal_cdf(double p) { return inv_normal_cdf_host(p); }
@@ -202,20 +242,8 @@ extern "C" void polychord_c_interface_ini(polychord_loglike_fn loglikelihood, vo
     // uniform-only priors run on the device (when the likelihood is a built-in); anything else is a host prior
     // grades from the speed column (priors.f90:708-737): speeds relabelled 1,2,3.. in increasing order, the hypercube
     // lists the parameters grade by grade (file order within a grade), grade_dims = parameters per grade
-    std::vector<int> speeds(nDims), grade_dims;
-    {
-        std::vector<int> distinct;
-        for (auto &p : ini.params) distinct.push_back(p.speed);
-        std::sort(distinct.begin(), distinct.end());
-        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-        g_hyper.assign(nDims, 0);
-        int h = 0;
-        for (size_t g = 0; g < distinct.size(); ++g) {
-            int cnt = 0;
-            for (int i = 0; i < nDims; ++i) if (ini.params[i].speed == distinct[g]) { g_hyper[i] = h++; cnt++; }
-            grade_dims.push_back(cnt);
-        }
-    }
+    std::vector<int> grade_dims;
+    g_hyper = hypercube_indices(ini.params, &grade_dims);
     bool identity = true;
     for (int i = 0; i < nDims; ++i) identity = identity && g_hyper[i] == i;
     bool all_uniform = identity;               // the device prior maps cube coordinate i to parameter i
@@ -250,6 +278,8 @@ extern "C" void polychord_c_interface_ini(polychord_loglike_fn loglikelihood, vo
         f = std::fopen((base + "/" + root + ".properties.ini").c_str(), "w");      // read_write.F90:996-1014
         if (f) { std::fprintf(f, "sampler=nested\nlabel=%s\n", root.c_str()); std::fclose(f); }
     }
+    // the markers of this file for this call; the caller's own setting (polychord_hip_set_sub_clustering) back afterwards, whatever happens
+    struct SubGuard { std::vector<int> old; ~SubGuard() { pc_exchange_sub_clustering(old); } } sub_guard{pc_exchange_sub_clustering(sub_clustering_dims(ini.params, g_hyper))};
     polychord_c_interface(loglikelihood, prior, nullptr, ini.integer_required("nlive"), ini.integer_required("num_repeats"),
                           ini.integer("nprior", -1), ini.integer("nfail", -1), ini.logical("do_clustering", false), ini.integer("feedback", 1),
                           ini.dbl("precision_criterion", 1e-3), ini.dbl("logzero", -1e30), ini.integer("max_ndead", -1),

@@ -120,9 +120,37 @@ class _BatchEvaluator:
         self._cb = None
 
 
-def _engine_run(loglikelihood, prior, *args):
+class _SubClustering:
+    """sub-dimension clustering for the length of one call: the library's sticky setting (polychord_hip_set_sub_clustering)
+    set before it and cleared after it, however it ends -- the call format of `_pypolychord.run` stays the reference's"""
+
+    def __init__(self, dims):
+        self.dims = [int(d) for d in (dims or [])]
+        self.lib = None
+
+    def __enter__(self):
+        if self.dims:
+            import ctypes as C
+            from .. import _ctypes_api as api
+            self.lib = api.load()
+            self.lib.polychord_hip_set_sub_clustering(len(self.dims), (C.c_int * len(self.dims))(*self.dims))
+        return self
+
+    def __exit__(self, *exc):
+        if self.lib is not None:
+            self.lib.polychord_hip_set_sub_clustering(0, None)
+        return False
+
+
+def _engine_run(loglikelihood, prior, *args, sub_clustering_dimensions=()):
     """_pypolychord.run(wrapped loglikelihood, wrapped prior, *args) on rank 0; every rank leaves together (a failure on
-    rank 0 is re-raised there after the others have been released).  args[1], args[2] = nDims, nDerived; args[10] = logzero."""
+    rank 0 is re-raised there after the others have been released).  args[1], args[2] = nDims, nDerived; args[10] = logzero.
+    sub_clustering_dimensions: 0-based hypercube indices of the sub-dimension pass (empty: plain clustering)."""
+    with _SubClustering(sub_clustering_dimensions):
+        return _engine_run_call(loglikelihood, prior, *args)
+
+
+def _engine_run_call(loglikelihood, prior, *args):
     wl, wp = _wrap(loglikelihood, prior)
     comm = _mpi_comm()
     batch = _BatchEvaluator(loglikelihood, prior, args[1], args[2], comm, args[10])
@@ -307,7 +335,8 @@ def run_polychord(loglikelihood, nDims, nDerived, settings, prior=default_prior,
                      settings.cluster_posteriors, settings.write_resume, settings.write_paramnames, settings.read_resume,
                      settings.write_stats, settings.write_live, settings.write_dead, settings.write_prior, settings.maximise,
                      settings.compression_factor, settings.synchronous, settings.base_dir, settings.file_root,
-                     settings.grade_frac, settings.grade_dims, settings.nlives, settings.seed)
+                     settings.grade_frac, settings.grade_dims, settings.nlives, settings.seed,
+                     sub_clustering_dimensions=getattr(settings, "sub_clustering_dimensions", []))
     return _Output(settings.base_dir, settings.file_root)
 
 
@@ -322,6 +351,7 @@ def run(loglikelihood, nDims, **kwargs):
         "write_dead": True, "write_prior": True, "maximise": False, "compression_factor": np.exp(-1), "synchronous": True,
         "base_dir": "chains", "file_root": "test", "cluster_dir": "clusters", "grade_dims": [nDims], "nlives": {},
         "seed": -1, "cube_samples": None,
+        "sub_clustering_dimensions": [],      # engine extension: 0-based parameter indices clustered on first (the ini `*` marker)
     }
     default_kwargs["grade_frac"] = ([1.0] * len(default_kwargs["grade_dims"]) if "grade_dims" not in kwargs
                                     else [1.0] * len(kwargs["grade_dims"]))
@@ -350,7 +380,8 @@ def run(loglikelihood, nDims, **kwargs):
                      kwargs["write_paramnames"], kwargs["read_resume"], kwargs["write_stats"], kwargs["write_live"],
                      kwargs["write_dead"], kwargs["write_prior"], kwargs["maximise"], kwargs["compression_factor"],
                      kwargs["synchronous"], kwargs["base_dir"], kwargs["file_root"], kwargs["grade_frac"],
-                     kwargs["grade_dims"], kwargs["nlives"], kwargs["seed"])
+                     kwargs["grade_dims"], kwargs["nlives"], kwargs["seed"],
+                     sub_clustering_dimensions=kwargs["sub_clustering_dimensions"])
     try:
         import anesthetic
     except ImportError:

@@ -28,6 +28,9 @@ class PolyChordSettings:
         self.grade_frac = list(kwargs.pop("grade_frac", [1.0] * len(self.grade_dims)))
         self.nlives = kwargs.pop("nlives", {})
         self.cube_samples = kwargs.pop("cube_samples", None)
+        # engine extension: 0-based parameter (= hypercube) indices clustered on first at every update, then all of them
+        # (the reference's Fortran settings%sub_clustering_dimensions, set there by `*` markers in an ini file)
+        self.sub_clustering_dimensions = [int(d) for d in kwargs.pop("sub_clustering_dimensions", [])]
         if kwargs:
             raise TypeError("Unexpected **kwargs in Contours constructor: %r" % kwargs)
         if sum(self.grade_dims) != nDims:
