@@ -1958,40 +1958,59 @@ __global__ __launch_bounds__(256) void k_init_state(PcState S, double logzero)
 }
 
 // ------------------------------------------------------------------------------------------
-// posterior moments of theta from the dead points: weights exp(logw + logL - max), fixed-order sums
+// posterior moments of theta from the dead points: weights exp(logw + logL - max), fixed-order sums about a pivot (the row of
+// the largest weight, lowest index on ties), so that the variance of a narrow posterior far from zero keeps its digits
 // ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void post_argmax(double &m, int &im, double om, int oi)
+{
+    if (om > m || (om == m && oi < im)) { m = om; im = oi; }
+}
+// pmax[b] = largest posterior log-weight of block b's rows, pmax[grid + b] = its row (as a double; -1: none)
 __global__ __launch_bounds__(256) void k_post_max(PcState S, int nd, double *pmax)
 {
     __shared__ double red[256];
+    __shared__ int redi[256];
     if (nd < 0) nd = S.ctl->ndead;                      // (enqueued behind the kill-off, before the host knows the count)
     double m = -PC_HUGE;
+    int im = 0x7fffffff;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nd; i += gridDim.x * 256) {
         const double lw = S.dead_logw[i];
-        if (lw > S.logzero) m = fmax(m, lw + S.dead[(size_t)i * S.nT + S.l0]);
+        if (lw > S.logzero) post_argmax(m, im, lw + S.dead[(size_t)i * S.nT + S.l0], i);
     }
-    red[threadIdx.x] = m;
+    red[threadIdx.x] = m; redi[threadIdx.x] = im;
     __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) { if (threadIdx.x < off) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + off]); __syncthreads(); }
-    if (threadIdx.x == 0) pmax[blockIdx.x] = red[0];
+    for (int off = 128; off > 0; off >>= 1) {
+        if (threadIdx.x < off) { double a = red[threadIdx.x]; int ia = redi[threadIdx.x]; post_argmax(a, ia, red[threadIdx.x + off], redi[threadIdx.x + off]); red[threadIdx.x] = a; redi[threadIdx.x] = ia; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { pmax[blockIdx.x] = red[0]; pmax[gridDim.x + blockIdx.x] = redi[0] == 0x7fffffff ? -1.0 : (double)redi[0]; }
 }
 
-__global__ __launch_bounds__(256) void k_post_moments(PcState S, int nd, const double *pmax, double *part /* [grid][2D+1] */)
+__global__ __launch_bounds__(256) void k_post_moments(PcState S, int nd, const double *pmax, double *part /* [grid][3D+1] */)
 {
-    // thread = (row group g, coordinate d); group g takes rows blockIdx*G+g, +gridDim*G, ... in order
+    // thread = (row group g, coordinate d); group g takes rows blockIdx*G+g, +gridDim*G, ... in order.
+    // part[b] = sum w (x - p) [D], sum w (x - p)^2 [D], sum w, p [D]
     __shared__ double red[256];
     __shared__ double red2[256];
+    __shared__ int redi[256];
     const int tid = threadIdx.x, D = S.D + S.nDer;          // theta then phi, contiguous from p0
-    const int DPc = cov_dpc(D), G = 256 / DPc, g = tid / DPc;
+    const int DPc = cov_dpc(D), G = 256 / DPc, g = tid / DPc, pw = 3 * D + 1;
     if (nd < 0) nd = S.ctl->ndead;
     double m = -PC_HUGE;
-    for (int b = tid; b < (int)gridDim.x; b += 256) m = fmax(m, pmax[b]);
-    red[tid] = m;
+    int im = 0x7fffffff;
+    for (int b = tid; b < (int)gridDim.x; b += 256) { const double ib = pmax[gridDim.x + b]; if (ib >= 0.0) post_argmax(m, im, pmax[b], (int)ib); }
+    red[tid] = m; redi[tid] = im;
     __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) { if (tid < off) red[tid] = fmax(red[tid], red[tid + off]); __syncthreads(); }
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) { double a = red[tid]; int ia = redi[tid]; post_argmax(a, ia, red[tid + off], redi[tid + off]); red[tid] = a; redi[tid] = ia; }
+        __syncthreads();
+    }
     m = red[0];
+    const double *prow = (redi[0] < nd) ? S.dead + (size_t)redi[0] * S.nT + S.p0 : nullptr;
     __syncthreads();
     for (int d0 = 0; d0 < D; d0 += DPc) {
         const int d = d0 + tid % DPc;
+        const double p = (d < D && prow) ? prow[d] : 0.0;
         double s1 = 0.0, s2 = 0.0, sw = 0.0;
         for (int i = blockIdx.x * G + g; i < nd; i += gridDim.x * G) {
             const double lw = S.dead_logw[i];
@@ -1999,20 +2018,20 @@ __global__ __launch_bounds__(256) void k_post_moments(PcState S, int nd, const d
             const double *row = S.dead + (size_t)i * S.nT;
             const double wgt = exp(lw + row[S.l0] - m);
             sw += wgt;
-            if (d < D) { const double th = row[S.p0 + d]; s1 += wgt * th; s2 += wgt * th * th; }
+            if (d < D) { const double th = row[S.p0 + d] - p; s1 += wgt * th; s2 += wgt * th * th; }
         }
         red[tid] = s1; red2[tid] = s2;
         __syncthreads();
         if (tid < DPc && d < D) {
             double a = 0.0, b2 = 0.0;
             for (int gg = 0; gg < G; ++gg) { a += red[gg * DPc + tid]; b2 += red2[gg * DPc + tid]; }
-            part[(size_t)blockIdx.x * (2 * D + 1) + d] = a; part[(size_t)blockIdx.x * (2 * D + 1) + D + d] = b2;
+            part[(size_t)blockIdx.x * pw + d] = a; part[(size_t)blockIdx.x * pw + D + d] = b2; part[(size_t)blockIdx.x * pw + 2 * D + 1 + d] = p;
         }
         __syncthreads();
         if (d0 == 0) {
             red[tid] = (tid % DPc == 0) ? sw : 0.0;
             __syncthreads();
-            if (tid == 0) { double a = 0.0; for (int gg = 0; gg < G; ++gg) a += red[gg * DPc]; part[(size_t)blockIdx.x * (2 * D + 1) + 2 * D] = a; }
+            if (tid == 0) { double a = 0.0; for (int gg = 0; gg < G; ++gg) a += red[gg * DPc]; part[(size_t)blockIdx.x * pw + 2 * D] = a; }
             __syncthreads();
         }
     }

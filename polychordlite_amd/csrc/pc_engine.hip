@@ -2702,12 +2702,12 @@ struct Engine {
         // what the results need from the device is requested here, behind the kill-off and before the host waits for it: the
         // posterior moments of theta over the dead points (device reduction, fixed order; the kernels take the count from the
         // control block) and the evidences of the retired clusters -- one wait instead of four
-        es.pmD = S.D + S.nDer; es.pm_nb = pc_post_blocks(); es.pm_pw = 2 * es.pmD + 1;   // theta and phi columns are contiguous in a row
+        es.pmD = S.D + S.nDer; es.pm_nb = pc_post_blocks(); es.pm_pw = 3 * es.pmD + 1;   // theta and phi columns are contiguous in a row
         es.ncd_max = std::min(h_ctl->ncluster_dead + h_ctl->ncluster, S.maxc_dead);
         // (the partial sums go straight into pinned host memory, which the device addresses like its own: 180 KB over the
         //  link instead of a D2H copy request behind the kernel -- that request stalled its caller for 5-6 ms once per process,
         //  in the second or third run)
-        es.d_pmax = dalloc<double>(es.pm_nb); es.h_part = halloc<double>((size_t)es.pm_nb * es.pm_pw);
+        es.d_pmax = dalloc<double>(2 * (size_t)es.pm_nb); es.h_part = halloc<double>((size_t)es.pm_nb * es.pm_pw);
         es.h_zp = halloc<double>(2 * (size_t)std::max(1, es.ncd_max));
         pc_launch_post_moments(&S, -1, es.d_pmax, es.h_part, st);
         if (es.ncd_max > 0) {
@@ -2784,7 +2784,8 @@ struct Engine {
         if (ncd > ncd_max) engine_fail(PC_RC_DEVICE, "more retired clusters (%d) than the final stage could have left (%d)", ncd, ncd_max);
         for (int i = 0; i < ncd; ++i) { const double zp = h_zp[i], zp2 = h_zp[ncd_max + i]; out->logZp[i] = 2 * zp - 0.5 * zp2; out->varlogZp[i] = zp2 - 2 * zp; }
         hfree(h_zp);
-        // posterior moments of theta from the dead points (requested above)
+        // posterior moments of theta from the dead points (requested above): sums about the pivot row p (k_post_moments),
+        // mean = p + S1 / W, variance = S2 / W - (S1 / W)^2
         const int D = pmD, nb = pm_nb, pw = pm_pw;
         out->post_mean = (double *)std::calloc(D, sizeof(double)); out->post_var = (double *)std::calloc(D, sizeof(double));
         double sw = 0.0;
@@ -2792,7 +2793,11 @@ struct Engine {
             sw += h_part[(size_t)b * pw + 2 * D];
             for (int d = 0; d < D; ++d) { out->post_mean[d] += h_part[(size_t)b * pw + d]; out->post_var[d] += h_part[(size_t)b * pw + D + d]; }
         }
-        for (int d = 0; d < D; ++d) { out->post_mean[d] /= sw; out->post_var[d] = out->post_var[d] / sw - out->post_mean[d] * out->post_mean[d]; }
+        for (int d = 0; d < D; ++d) {
+            const double dm = out->post_mean[d] / sw;
+            out->post_mean[d] = h_part[2 * D + 1 + d] + dm;
+            out->post_var[d] = std::max(0.0, out->post_var[d] / sw - dm * dm);
+        }
         dfree(d_pmax); hfree(h_part);
         // settings.device_records: the lived records picked here, on the device that made them (what the exchange step of repeat-sharded
         // runs sends); their count comes back with the wait below

@@ -11,12 +11,16 @@
 //
 // Nothing here is a sort: every run's deaths already ascend in logL, so
 //   * rank of a record in the union = its own index + binary searches in the other runs' logL columns (R-way merge path);
-//   * live points of run q just before its k-th death, G_q[k] = #{entry contour < L_k} - k, from a histogram of where
-//     each point's entry contour sits in the run's own death sequence (an entry contour IS the logL of a later death of
-//     the same run, or logzero for the initial points) + one prefix sum;
+//   * live points of run q just before its k-th death, G_q[k] = #{points born before death k} - k, from a histogram of
+//     where each point's entry contour sits in the run's own death sequence (an entry contour IS the logL of an earlier
+//     death of the same run, or logzero for the initial points) + one prefix sum.  Ties: at a contour
+//     shared by m tied deaths of a run, the t-th point entering at that contour is born after the t-th tied death
+//     (t from 0), all points with t >= m - 1 after the last one;
 //   * n_i = sum_q G_q[rank of record i among run q's deaths];
 //   * the recursion over the merged sequence = two device-wide inclusive scans (plain sums of log n/(n+1), log n/(n+2);
-//     log-sum-exp pairs for <Z X>/X) + two log-sum-exp reductions, all with a fixed chunking (bit-reproducible).
+//     log-sum-exp pairs for <Z X>/X) + two log-sum-exp reductions, all with a fixed chunking (bit-reproducible);
+//   * posterior moments about a pivot known before the sums (the theta / phi of the record with the largest posterior weight,
+//     lowest merged position on ties): sum w (x - p), sum w (x - p)^2, so a narrow posterior far from zero keeps its variance.
 #include "pc_state.h"
 #include "pc_keys.h"
 #include "../../include/polychord_hip.h"
@@ -147,7 +151,7 @@ struct MergeDev {
     int *G;                      // [n + R] per run len+1 entries at off[q] + q: histogram, then live points before death k
     long long *perm;             // [n] merged position -> record
     double *Ls;                  // [n] merged logL
-    int *nl;                     // [n] live points just before each merged death
+    int *nl;                     // [n] live points just before each merged death (before k_merge_rank: the tie counters of k_merge_hist)
 };
 
 __device__ __forceinline__ int run_of(const MergeDev &M, long long g)
@@ -172,10 +176,12 @@ __device__ __forceinline__ long long upper_bound_d(const double *a, long long le
 __global__ void k_merge_extract(MergeDev M)
 {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < M.n) M.L[g] = M.rows[(size_t)g * M.nT + M.l0];
+    if (g < M.n) { M.L[g] = M.rows[(size_t)g * M.nT + M.l0]; M.nl[g] = 0; }
     if (g < M.n + M.R) M.G[g] = 0;
 }
-// where does each point's entry contour sit in its run's death sequence?
+// where does each point's entry contour sit in its run's death sequence?  A contour that is the logL of m tied deaths
+// [lo, lo + m): the t-th point entering there (t from a counter per tie group) is born after death lo + min(t, m - 1).  Which
+// point draws which t does not matter: they all share the contour, so the histogram is the same whatever the order.
 __global__ void k_merge_hist(MergeDev M)
 {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -184,7 +190,11 @@ __global__ void k_merge_hist(MergeDev M)
     const long long o = M.off[q], len = M.off[q + 1] - o;
     const double e = M.entry[g];
     long long pos = lower_bound_d(M.L + o, len, e);
-    if (pos < len && M.L[o + pos] == e) pos++;       // alive from the death AFTER the one whose logL is its entry contour
+    if (pos < len && M.L[o + pos] == e) {
+        const long long m = upper_bound_d(M.L + o, len, e) - pos;
+        const long long t = atomicAdd(&M.nl[o + pos], 1);
+        pos += 1 + (t < m - 1 ? t : m - 1);
+    }
     atomicAdd(&M.G[o + q + pos], 1);
 }
 // inclusive prefix of the histogram minus the deaths so far = live points before death k; one workgroup per run
@@ -231,36 +241,48 @@ __global__ void k_merge_rank(MergeDev M)
     }
     M.perm[rank] = g; M.Ls[rank] = x; M.nl[rank] = nlive < 1 ? 1 : nlive;
 }
+// log n/(n+1) and log n/(n+2) as -log1p(1/n), -log1p(2/n): exact to the term's own rounding.  (log n - log(n+1) of two ~11.5 numbers
+// carried an absolute error of ~1e-15 a term, the same one at every death of a constant live count: 4 M deaths at n = 1e5 put
+// 1.3e-9 into log Z)
+__device__ __forceinline__ double dl1(double v) { return -log1p(1.0 / v); }
+__device__ __forceinline__ double dl2(double v) { return -log1p(2.0 / v); }
 __global__ void k_merge_dx(const int *nl, long long n, P2 *X)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double v = (double)nl[i], l0 = log(v);
-    X[i] = P2{l0 - log(v + 1.0), l0 - log(v + 2.0)};
+    const double v = (double)nl[i];
+    X[i] = P2{dl1(v), dl2(v)};
 }
 // X: (logX, logXX) AFTER each death.  T: terms of <Z X> / X (run_time_info.f90:262-271 with the decay factored out)
 __global__ void k_merge_t(const int *nl, const double *Ls, const P2 *X, long long n, P2 *T)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double v = (double)nl[i], l0 = log(v), l1 = log(v + 1.0), l2 = log(v + 2.0);
-    const double XXm = X[i].b - (l0 - l2);
-    T[i] = P2{XXm + Ls[i] + l0 - l1 - l2 - X[i].a, 1.0};
+    const double v = (double)nl[i], l2 = log(v + 2.0);
+    const double XXm = X[i].b - dl2(v);
+    T[i] = P2{XXm + Ls[i] + dl1(v) - l2 - X[i].a, 1.0};
 }
 // per merged death: log weight, the two evidence terms; per chunk of 1024 deaths: (max, sum) partials of both sums
 // and the largest posterior log-weight
+// (value, merged position) of the largest posterior log-weight: the larger value, the lower position on ties
+__device__ __forceinline__ void argmax_comb(double &pm, long long &pi, double om, long long oi)
+{
+    if (om > pm || (om == pm && oi < pi)) { pm = om; pi = oi; }
+}
 __global__ __launch_bounds__(1024) void k_merge_terms(const int *nl, const double *Ls, const P2 *X, const P2 *T, long long n,
-                                                      double *logw, P2 *partA, P2 *partB, double *partM)
+                                                      double *logw, P2 *partA, P2 *partB, double *partM, long long *partI)
 {
     __shared__ P2 sa[16], sb[16];
     __shared__ double sm[16];
+    __shared__ long long si[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const long long i = (long long)blockIdx.x * 1024 + tid;
     P2 a = OpLse::id(), b = OpLse::id();
     double pm = NEGBIG;
+    long long pi = i < n ? i : n;
     if (i < n) {
-        const double v = (double)nl[i], l0 = log(v), l1 = log(v + 1.0), l2 = log(v + 2.0), L = Ls[i];
-        const double Xm = X[i].a - (l0 - l1), XXm = X[i].b - (l0 - l2);
+        const double v = (double)nl[i], l1 = log(v + 1.0), l2 = log(v + 2.0), L = Ls[i];
+        const double Xm = X[i].a - dl1(v), XXm = X[i].b - dl2(v);
         const double ZXm = i ? lsv(T[i - 1]) + X[i - 1].a : NEGBIG;
         const double log2v = 0.6931471805599453;
         a = P2{Xm + L - l1, 1.0};
@@ -271,19 +293,20 @@ __global__ __launch_bounds__(1024) void k_merge_terms(const int *nl, const doubl
     for (int s = 32; s > 0; s >>= 1) {
         const P2 oa = P2{__shfl_xor(a.a, s), __shfl_xor(a.b, s)}, ob = P2{__shfl_xor(b.a, s), __shfl_xor(b.b, s)};
         a = OpLse::comb(a, oa); b = OpLse::comb(b, ob);
-        pm = fmax(pm, __shfl_xor(pm, s));
+        argmax_comb(pm, pi, __shfl_xor(pm, s), __shfl_xor(pi, s));
     }
-    if (lane == 0) { sa[wv] = a; sb[wv] = b; sm[wv] = pm; }
+    if (lane == 0) { sa[wv] = a; sb[wv] = b; sm[wv] = pm; si[wv] = pi; }
     __syncthreads();
     if (tid == 0) {
-        for (int x = 1; x < 16; ++x) { a = OpLse::comb(a, sa[x]); b = OpLse::comb(b, sb[x]); pm = fmax(pm, sm[x]); }
-        partA[blockIdx.x] = a; partB[blockIdx.x] = b; partM[blockIdx.x] = pm;
+        for (int x = 1; x < 16; ++x) { a = OpLse::comb(a, sa[x]); b = OpLse::comb(b, sb[x]); argmax_comb(pm, pi, sm[x], si[x]); }
+        partA[blockIdx.x] = a; partB[blockIdx.x] = b; partM[blockIdx.x] = pm; partI[blockIdx.x] = pi;
     }
 }
-// weighted moments of theta and phi: thread = column, a workgroup walks a chunk of merged deaths (rows are read whole,
-// coalesced across the columns); part[b][2 nP + 1] = sum w x, sum w x^2, sum w
+// weighted moments of theta and phi about the pivot row (merged position ipiv): thread = column, a workgroup walks a chunk of merged
+// deaths (rows are read whole, coalesced across the columns); part[b][2 nP + 1] = sum w (x - p), sum w (x - p)^2, sum w; block 0 also
+// writes the pivot p behind all blocks' partials (part[nblocks (2 nP + 1) + c])
 #define MM_CHUNK 512
-__global__ __launch_bounds__(256) void k_merge_moments(MergeDev M, const double *logw, double wmax, int p0, int nP, double *part)
+__global__ __launch_bounds__(256) void k_merge_moments(MergeDev M, const double *logw, double wmax, long long ipiv, int p0, int nP, double *part)
 {
     __shared__ double sw[MM_CHUNK];
     __shared__ long long sg[MM_CHUNK];
@@ -292,11 +315,14 @@ __global__ __launch_bounds__(256) void k_merge_moments(MergeDev M, const double 
     const int m = (int)((M.n - i0) < MM_CHUNK ? (M.n - i0) : MM_CHUNK);
     for (int k = tid; k < m; k += 256) { sw[k] = exp(logw[i0 + k] + M.Ls[i0 + k] - wmax); sg[k] = M.perm[i0 + k]; }
     __syncthreads();
+    const double *prow = M.rows + (size_t)M.perm[ipiv] * M.nT + p0;
     double *out = part + (size_t)blockIdx.x * (2 * nP + 1);
     for (int c = tid; c < nP; c += 256) {
+        const double p = prow[c];
         double s1 = 0.0, s2 = 0.0;
-        for (int k = 0; k < m; ++k) { const double x = M.rows[(size_t)sg[k] * M.nT + p0 + c]; s1 += sw[k] * x; s2 += sw[k] * x * x; }
+        for (int k = 0; k < m; ++k) { const double x = M.rows[(size_t)sg[k] * M.nT + p0 + c] - p; s1 += sw[k] * x; s2 += sw[k] * x * x; }
         out[c] = s1; out[nP + c] = s2;
+        if (blockIdx.x == 0) part[(size_t)gridDim.x * (2 * nP + 1) + c] = p;
     }
     if (tid == 0) { double s = 0.0; for (int k = 0; k < m; ++k) s += sw[k]; out[2 * nP] = s; }
 }
@@ -394,17 +420,19 @@ __global__ __launch_bounds__(64) void k_unpad(const double *recv, long long nmax
 // it -- its cluster's volume over the cluster's live count, run_time_info.f90:211-296 -- over the number of runs; per chunk of 1024 the
 // largest posterior log-weight
 __global__ __launch_bounds__(1024) void k_merge_ownw(const long long *perm, const double *ownw, const double *Ls, long long n, double logR,
-                                                     double *logw, double *partM)
+                                                     double *logw, double *partM, long long *partI)
 {
     __shared__ double sm[16];
+    __shared__ long long si[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const long long i = (long long)blockIdx.x * 1024 + tid;
     double pm = NEGBIG;
+    long long pi = i < n ? i : n;
     if (i < n) { const double w = ownw[perm[i]] - logR; logw[i] = w; pm = w + Ls[i]; }
-    for (int s = 32; s > 0; s >>= 1) pm = fmax(pm, __shfl_xor(pm, s));
-    if (lane == 0) sm[wv] = pm;
+    for (int s = 32; s > 0; s >>= 1) argmax_comb(pm, pi, __shfl_xor(pm, s), __shfl_xor(pi, s));
+    if (lane == 0) { sm[wv] = pm; si[wv] = pi; }
     __syncthreads();
-    if (tid == 0) { for (int x = 1; x < 16; ++x) pm = fmax(pm, sm[x]); partM[blockIdx.x] = pm; }
+    if (tid == 0) { for (int x = 1; x < 16; ++x) argmax_comb(pm, pi, sm[x], si[x]); partM[blockIdx.x] = pm; partI[blockIdx.x] = pi; }
 }
 
 // ---- RCCL, resolved at run time: the engine has no link-time dependency on a collective library (a single-GPU user needs
@@ -637,8 +665,9 @@ int pchip_merge_records_ex(int nDims, int nDerived, int nruns, const long *count
     long long *d_off = B.get<long long>(nruns + 1);
     M.L = B.get<double>(n); M.G = B.get<int>(n + nruns); M.perm = B.get<long long>(n); M.Ls = B.get<double>(n); M.nl = B.get<int>(n);
     P2 *X = B.get<P2>(n), *T = B.get<P2>(n), *tot = B.get<P2>(nbs + 1), *pA = B.get<P2>(nbt), *pB = B.get<P2>(nbt);
-    double *pM = B.get<double>(nbt), *d_logw = B.get<double>(n), *pmom = B.get<double>((size_t)nbm * (2 * nP + 1));
-    if (!d_off || !M.L || !M.G || !M.perm || !M.Ls || !M.nl || !X || !T || !tot || !pA || !pB || !pM || !d_logw || !pmom) return fail("out of device memory");
+    double *pM = B.get<double>(nbt), *d_logw = B.get<double>(n), *pmom = B.get<double>((size_t)nbm * (2 * nP + 1) + nP);
+    long long *pI = B.get<long long>(nbt);
+    if (!d_off || !M.L || !M.G || !M.perm || !M.Ls || !M.nl || !X || !T || !tot || !pA || !pB || !pM || !pI || !d_logw || !pmom) return fail("out of device memory");
     M.off = d_off;
     if (hipMemcpy(d_off, off.data(), sizeof(long long) * (nruns + 1), hipMemcpyHostToDevice) != hipSuccess) return fail("upload");
     const int nb256 = (int)((n + nruns + 255) / 256);
@@ -650,36 +679,51 @@ int pchip_merge_records_ex(int nDims, int nDerived, int nruns, const long *count
     device_scan<OpAdd>(X, n, tot, st);
     hipLaunchKernelGGL(k_merge_t, dim3(nb256), dim3(256), 0, st, (const int *)M.nl, (const double *)M.Ls, (const P2 *)X, n, T);
     device_scan<OpLse>(T, n, tot, st);
-    hipLaunchKernelGGL(k_merge_terms, dim3(nbt), dim3(1024), 0, st, (const int *)M.nl, (const double *)M.Ls, (const P2 *)X, (const P2 *)T, n, d_logw, pA, pB, pM);
-    PinBuf<P2> hA(nbt), hB(nbt); PinBuf<double> hM(nbt);
-    if (!hA.p || !hB.p || !hM.p) return fail("out of pinned memory");
+    hipLaunchKernelGGL(k_merge_terms, dim3(nbt), dim3(1024), 0, st, (const int *)M.nl, (const double *)M.Ls, (const P2 *)X, (const P2 *)T, n, d_logw, pA, pB, pM, pI);
+    PinBuf<P2> hA(nbt), hB(nbt); PinBuf<double> hM(nbt); PinBuf<long long> hI(nbt);
+    if (!hA.p || !hB.p || !hM.p || !hI.p) return fail("out of pinned memory");
     if (hipMemcpy(hA.data(), pA, sizeof(P2) * nbt, hipMemcpyDeviceToHost) != hipSuccess) return fail("evidence kernels");
     (void)hipMemcpy(hB.data(), pB, sizeof(P2) * nbt, hipMemcpyDeviceToHost); (void)hipMemcpy(hM.data(), pM, sizeof(double) * nbt, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(hI.data(), pI, sizeof(long long) * nbt, hipMemcpyDeviceToHost);
     auto comb = [](P2 x, P2 y) { const double e = std::exp(-std::fabs(x.a - y.a)); return P2{std::max(x.a, y.a), x.a >= y.a ? x.b + y.b * e : x.b * e + y.b}; };
-    P2 a = hA[0], b = hB[0]; double wmax = hM[0];
-    for (int k = 1; k < nbt; ++k) { a = comb(a, hA[k]); b = comb(b, hB[k]); wmax = std::max(wmax, hM[k]); }
+    // the largest posterior log-weight and its merged position (the pivot of the moments), lowest position on ties
+    auto argmax = [&](double &wm, long long &ip) {
+        wm = hM[0]; ip = hI[0];
+        for (int k = 1; k < nbt; ++k) if (hM[k] > wm || (hM[k] == wm && hI[k] < ip)) { wm = hM[k]; ip = hI[k]; }
+        if (ip < 0 || ip >= n) ip = 0;
+    };
+    P2 a = hA[0], b = hB[0]; double wmax; long long ipiv;
+    for (int k = 1; k < nbt; ++k) { a = comb(a, hA[k]); b = comb(b, hB[k]); }
+    argmax(wmax, ipiv);
     const double lZ = a.a + std::log(a.b), lZ2 = b.a + std::log(b.b);       // log <Z>, log <Z^2>
     out->logZ = 2.0 * lZ - 0.5 * lZ2; out->varlogZ = lZ2 - 2.0 * lZ;       // run_time_info.f90:652-678
     out->logZ_replay = out->logZ; out->varlogZ_replay = out->varlogZ; out->evidence_rule = 0; out->nclustered = nclustered;
     if (own_rule) {
         runs_combined_evidence(run_logZ, run_varlogZ, nruns, &out->logZ, &out->varlogZ);
         out->evidence_rule = 1;
-        hipLaunchKernelGGL(k_merge_ownw, dim3(nbt), dim3(1024), 0, st, (const long long *)M.perm, d_ownw, (const double *)M.Ls, n, std::log((double)nruns), d_logw, pM);
+        hipLaunchKernelGGL(k_merge_ownw, dim3(nbt), dim3(1024), 0, st, (const long long *)M.perm, d_ownw, (const double *)M.Ls, n, std::log((double)nruns), d_logw, pM, pI);
         if (hipMemcpy(hM.data(), pM, sizeof(double) * nbt, hipMemcpyDeviceToHost) != hipSuccess) return fail("weight kernel");
-        wmax = hM[0];
-        for (int k = 1; k < nbt; ++k) wmax = std::max(wmax, hM[k]);
+        (void)hipMemcpy(hI.data(), pI, sizeof(long long) * nbt, hipMemcpyDeviceToHost);
+        argmax(wmax, ipiv);
     }
-    hipLaunchKernelGGL(k_merge_moments, dim3(nbm), dim3(256), 0, st, M, (const double *)d_logw, wmax, p0, nP, pmom);
-    PinBuf<double> hm((size_t)nbm * (2 * nP + 1));
+    hipLaunchKernelGGL(k_merge_moments, dim3(nbm), dim3(256), 0, st, M, (const double *)d_logw, wmax, ipiv, p0, nP, pmom);
+    PinBuf<double> hm((size_t)nbm * (2 * nP + 1) + nP);
     if (!hm.p) return fail("out of pinned memory");
     if (hipMemcpy(hm.data(), pmom, sizeof(double) * hm.size(), hipMemcpyDeviceToHost) != hipSuccess) return fail("moment kernel");
+    // mean = p + S1 / W, variance = S2 / W - (S1 / W)^2 with S1, S2 about the pivot p: the square subtracted is of the order of the
+    // variance itself, not of the mean (E[x^2] - mean^2 lost every digit of a narrow posterior far from zero).  Blocks in order.
     double sw = 0.0;
+    const double *piv = hm.data() + (size_t)nbm * (2 * nP + 1);
     for (int k = 0; k < nbm; ++k) {
         const double *p = hm.data() + (size_t)k * (2 * nP + 1);
         sw += p[2 * nP];
         for (int c = 0; c < nP; ++c) { out->post_mean[c] += p[c]; out->post_var[c] += p[nP + c]; }
     }
-    for (int c = 0; c < nP; ++c) { out->post_mean[c] /= sw; out->post_var[c] = out->post_var[c] / sw - out->post_mean[c] * out->post_mean[c]; }
+    for (int c = 0; c < nP; ++c) {
+        const double d = out->post_mean[c] / sw;
+        out->post_mean[c] = piv[c] + d;
+        out->post_var[c] = std::max(0.0, out->post_var[c] / sw - d * d);
+    }
     // (pinned blocks of the cache: a blocking copy into pageable memory has the driver pin the pages for the copy, and when the caller
     //  gives the arrays back -- megabytes: unmapped at once -- the kernel driver takes the process's queues off the device and puts
     //  them back some 20 ms later: the next call's first wait for the device, if it came at once, sat behind that)
