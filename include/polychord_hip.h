@@ -49,7 +49,7 @@ void polychord_c_interface_ini(polychord_loglike_fn loglikelihood, void (*setup_
 /* ===== Part 2: engine surface =============================================================== */
 
 enum { PCHIP_LIKE_CALLBACK = 0, PCHIP_LIKE_GAUSSIAN = 1, PCHIP_LIKE_RASTRIGIN = 2,
-       PCHIP_LIKE_TWIN_GAUSSIAN = 3, PCHIP_LIKE_CORR_GAUSSIAN = 4 };
+       PCHIP_LIKE_TWIN_GAUSSIAN = 3, PCHIP_LIKE_CORR_GAUSSIAN = 4, PCHIP_LIKE_SOURCE = 5 };
 
 /* Built-in likelihoods that run fused on the device.  These are ordinary host functions with the
  * reference's callback signature (they evaluate the same formula on the host); when one of them
@@ -149,7 +149,8 @@ typedef struct {
                            fused sampling kernel with ONE wavefront a workgroup (a chain) instead of four chains and their four helper wavefronts
                            (deck shuffle and whitening next to the seed choice instead of in front of it): the same numbers; bit 14 = with the helper, the closed
                            form's s.M.s of a direction reduced by the chain at the head of its slice instead of taken from the table the helper made with the
-                           whitening (the same bits: the table's sums follow the wave butterfly's order) */
+                           whitening (the same bits: the table's sums follow the wave butterfly's order); bit 15 = the sampling kernels of the built-in
+                           likelihoods launched from a module compiled at run time (pchip_source_create's path, PCHIP_PATH_SOURCE_KERNELS): the same numbers */
     const char *resume_write;  /* path of a .resume file (reference grammar, read_write.F90:219-288) rewritten at every
                                   update and at the end; NULL = off */
     int sequential_rng; /* tests: ONE Philox stream consumed in the reference's program order (forces batch = 1 and the
@@ -185,6 +186,7 @@ typedef struct {
     const double *mean;            /* host, D */
     double logdetcov;
     polychord_loglike_fn fn;       /* callback kind */
+    int source;                    /* PCHIP_LIKE_SOURCE: handle from pchip_source_create (ABI 9) */
 } pchip_like;
 
 typedef struct {
@@ -240,6 +242,7 @@ enum { PCHIP_PATH_CONSUME_PAR = 0,      /* one cluster: the parallel contraction
                                                block the parallel kernel's tables push over the limit) */
        PCHIP_PATH_SUBCLUSTER_PASSES = 17,   /* clustering passes on the sub-clustering coordinates (settings.n_sub_cluster > 0: one per update) */
        PCHIP_PATH_SUBCLUSTER_SPLITS = 18,   /* clusters those passes split */
+       PCHIP_PATH_SOURCE_KERNELS = 19,      /* launches of run-time compiled sampling kernels (PCHIP_LIKE_SOURCE, settings.ablate bit 15) */
        PCHIP_PATH_COUNT = 24 };
 
 /* snapshot handed to the update hook: what the reference's file writers see at every update
@@ -284,8 +287,18 @@ typedef struct {
  * bindings rely on).  A binding that mirrors them (ctypes, ISO_C_BINDING, cgo ...) checks itself against the library it loaded:
  * pchip_abi_version() == PCHIP_ABI_VERSION of the header it was written against, and pchip_sizeof("settings" | "result" | "merged" |
  * "like" | "prior" | "update") == the size of its own mirror (0 for an unknown name). */
-#define PCHIP_ABI_VERSION 8
+#define PCHIP_ABI_VERSION 9
 int  pchip_abi_version(void);
+/* A likelihood written as HIP device source, compiled at run time for the device a run is on and evaluated inside the sampling kernels
+ * (pchip_like.kind = PCHIP_LIKE_SOURCE, .source = the handle).  The source defines
+ *     __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
+ * a pure, deterministic function; it writes phi[0 .. nDerived) (nDerived <= PCHIP_SOURCE_MAX_DERIVED); a logL at or below logzero marks
+ * an invalid point.  `data` (ndata doubles, copied here) is uploaded to the device by every run.  `options`: extra compiler options
+ * separated by blanks (-D...), or NULL.  pchip_source_create compiles the user's functions at once: it returns the handle (> 0), or -1
+ * with the compiler's log in polychord_hip_last_error().  Needs libhiprtc at run time (dlopen'ed). */
+#define PCHIP_SOURCE_MAX_DERIVED 32
+int  pchip_source_create(const char *source, const char *options, const double *data, long ndata);
+void pchip_source_destroy(int handle);
 unsigned long pchip_sizeof(const char *struct_name);
 void pchip_settings_default(pchip_settings *s, int nDims, int nDerived);
 int  pchip_device_count(void);

@@ -16,10 +16,10 @@ PRIOR_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_i
 DUMPER_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.POINTER(C.c_double), C.c_double, C.c_double)
 
-LIKE_CALLBACK, LIKE_GAUSSIAN, LIKE_RASTRIGIN, LIKE_TWIN_GAUSSIAN, LIKE_CORR_GAUSSIAN = range(5)
+LIKE_CALLBACK, LIKE_GAUSSIAN, LIKE_RASTRIGIN, LIKE_TWIN_GAUSSIAN, LIKE_CORR_GAUSSIAN, LIKE_SOURCE = range(6)
 KERNEL_CLASSES = ("k_nhats", "k_slice", "k_consume", "k_apply", "k_clean", "k_covmats", "k_bases_side")
 LIKE_KINDS = {"gaussian": LIKE_GAUSSIAN, "rastrigin": LIKE_RASTRIGIN, "twin_gaussian": LIKE_TWIN_GAUSSIAN,
-              "corr_gaussian": LIKE_CORR_GAUSSIAN}
+              "corr_gaussian": LIKE_CORR_GAUSSIAN, "source": LIKE_SOURCE}
 
 
 class Settings(C.Structure):
@@ -39,7 +39,8 @@ class Settings(C.Structure):
 
 class Like(C.Structure):
     _fields_ = [("kind", C.c_int), ("mu", C.c_double), ("sigma", C.c_double), ("invcov", C.POINTER(C.c_double)),
-                ("mean", C.POINTER(C.c_double)), ("logdetcov", C.c_double), ("fn", C.c_void_p)]
+                ("mean", C.POINTER(C.c_double)), ("logdetcov", C.c_double), ("fn", C.c_void_p),
+                ("source", C.c_int)]
 
 
 class Prior(C.Structure):
@@ -66,7 +67,7 @@ class Result(C.Structure):
 # pchip_result.path[]: launches per kernel variant (include/polychord_hip.h PCHIP_PATH_*)
 PATH_NAMES = ("consume_par", "consume_cl", "consume_general", "consume_fast", "killoff_par", "killoff_cl", "killoff_general",
               "killoff_fast", "update_fused", "update_steps", "slice_wave", "slice_lane", "nn_lists", "nn_fallbacks", "pool_mode",
-              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits")
+              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits", "source_kernels")
 
 
 _lib = None
@@ -100,6 +101,17 @@ def load():
     lib.polychord_hip_set_sub_clustering.restype = None
     lib.polychord_hip_ini_sub_clustering.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.c_int]
     lib.polychord_hip_ini_sub_clustering.restype = C.c_int
+    lib.pchip_source_create.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long]
+    lib.pchip_source_create.restype = C.c_int
+    lib.pchip_source_destroy.argtypes = [C.c_int]
+    lib.pchip_source_destroy.restype = None
+    lib.pchip_rtc_embedded_source.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
+    lib.pchip_rtc_embedded_source.restype = C.c_char_p
+    lib.pchip_rtc_compile_check.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_double)]
+    lib.pchip_rtc_compile_check.restype = C.c_int
+    lib.pchip_rtc_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_double)]
+    lib.pchip_rtc_stats.restype = None
+    lib.polychord_hip_last_error.restype = C.c_char_p
     # this mirror against the library that was loaded (the structs grow at their end: include/polychord_hip.h PCHIP_ABI_VERSION)
     lib.pchip_sizeof.argtypes = [C.c_char_p]
     lib.pchip_sizeof.restype = C.c_ulong
@@ -115,11 +127,25 @@ def dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, invcov=None, mean=None, logdet=0.0):
-    """(Like, Prior, keepalive) for a built-in device likelihood and a uniform box prior."""
+def source_create(source, options=(), data=None):
+    """handle of a likelihood written as HIP device source (pchip_source_create); RuntimeError with the compiler's log if it does not compile"""
+    lib = load()
+    d = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
+    opts = " ".join(options) if not isinstance(options, str) else options
+    h = lib.pchip_source_create(source.encode(), opts.encode(), dptr(d) if d is not None and d.size else None,
+                                0 if d is None else int(d.size))
+    if h <= 0:
+        log = lib.polychord_hip_last_error()
+        raise RuntimeError("device source does not compile:\n" + (log.decode(errors="replace") if log else "(no log)"))
+    return h
+
+
+def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, invcov=None, mean=None, logdet=0.0, source=0):
+    """(Like, Prior, keepalive) for a built-in device likelihood, or a device source ("source", source=handle), and a uniform box prior."""
     keep = []
     L = Like()
     L.kind = LIKE_KINDS[kind]
+    L.source = source
     L.mu, L.sigma, L.logdetcov = mu, sigma, logdet
     if invcov is not None:
         ic = np.ascontiguousarray(invcov, dtype=np.float64)

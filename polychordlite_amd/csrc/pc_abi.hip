@@ -477,6 +477,8 @@ void polychord_hip_set_sub_clustering(int n, const int *dims)
 }
 
 int pchip_abi_version(void) { return PCHIP_ABI_VERSION; }
+// (pc_rtc.hip: pchip_source_create's compiler log; NULL clears)
+extern "C" void pc_abi_set_last_error(const char *msg) { if (msg) G.last_error = msg; else G.last_error.clear(); }
 unsigned long pchip_sizeof(const char *n)
 {
     if (!n) return 0;

@@ -7,15 +7,21 @@
 //   utils.F90:806-966 (AS241), utils.F90:362-439 (log-space sums),
 //   likelihoods/examples/{gaussian,rastrigin,twin_gaussian,random_gaussian}.f90, priors.f90:40-55.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#else                            // compiled at run time by hiprtc (pc_rtc.hip): no system headers
+using __hip_internal::uint32_t; using __hip_internal::uint64_t; using __hip_internal::int32_t; using __hip_internal::int64_t;
+typedef unsigned long uintptr_t;
+#endif
 
 #define PC_WAVE 64
 #define PC_SLICE_STRIDE 128
 enum { PC_DOM_LIVEGEN = 0, PC_DOM_SEED = 1, PC_DOM_NHAT = 2, PC_DOM_SHUFFLE = 3, PC_DOM_SLICE = 4,
        PC_DOM_PHANTOM = 5, PC_DOM_POST = 6, PC_DOM_SEQ = 0xFFFF };
 enum { PC_LIKE_CALLBACK = 0, PC_LIKE_GAUSSIAN = 1, PC_LIKE_RASTRIGIN = 2, PC_LIKE_TWIN_GAUSSIAN = 3,
-       PC_LIKE_CORR_GAUSSIAN = 4 };
+       PC_LIKE_CORR_GAUSSIAN = 4, PC_LIKE_SOURCE = 5 };
+#define PC_SRC_MAX_DERIVED 32    /* PC_LIKE_SOURCE: derived parameters a user function may write (pc_rtc.hip refuses more) */
 
 #define PC_HUGE 1.7976931348623157e308
 #define PC_LOG_TWO_PI 1.8378770664093453

@@ -36,6 +36,9 @@ extern "C" void *pc_cache_dev_alloc(size_t bytes);
 extern "C" void pc_cache_dev_free(void *p);
 extern "C" {
 int pc_launch_generate_live(const PcState *, int, int, double *, double *, hipStream_t);
+int pc_rtc_wanted(const PcState *);
+const char *pc_rtc_error(void);
+int pc_rtc_source_data(int, const double **, long long *);
 int pc_launch_nhats(const PcState *, unsigned, int, hipStream_t);
 int pc_nhats_splittable(const PcState *);
 int pc_launch_nhats_part(const PcState *, unsigned, int, int, hipStream_t, int);
@@ -799,7 +802,7 @@ struct Engine {
     double *psum = nullptr, *mean = nullptr, *pcov = nullptr; int *pcnt = nullptr, *count = nullptr;
     size_t cov_chunks_cap = 0;
     double *upd_part = nullptr, *upd_shift = nullptr; size_t upd_part_cap = 0;   // fused update (pc_update.hip)
-    double *d_lo = nullptr, *d_hi = nullptr, *d_invcovT = nullptr, *d_mean = nullptr;
+    double *d_lo = nullptr, *d_hi = nullptr, *d_invcovT = nullptr, *d_mean = nullptr, *d_src = nullptr;
     double *d_dynL = nullptr; int *d_dynN = nullptr; double *d_logn = nullptr;
     // clustering scratch (allocated on first use)
     double *c_Sm = nullptr; int *c_pts = nullptr, *c_gidx = nullptr, *c_knn = nullptr, *c_lab = nullptr, *c_out = nullptr, *c_cnt = nullptr;
@@ -924,6 +927,15 @@ struct Engine {
         S.like.inv_sigma = like.sigma > 0 ? 1.0 / like.sigma : 1.0;
         S.like.log_vn = 0.5 * D * std::log(3.14159265358979323846) - std::lgamma(1.0 + D / 2.0);
         S.like.invcov = nullptr; S.like.mean = nullptr;
+        S.src_id = 0; S.src_pad = 0; S.src_data = nullptr; S.src_ndata = 0;
+        if (like.kind == PC_LIKE_SOURCE) {         // a user's device source (pc_rtc.hip): its data block goes up with the run
+            const double *h = nullptr; long long n = 0;
+            if (pc_rtc_source_data(like.source, &h, &n)) engine_fail(PC_RC_SETTINGS, "device source handle %d does not exist", like.source);
+            if (nDer > PC_SRC_MAX_DERIVED) engine_fail(PC_RC_SETTINGS, "a device source likelihood writes at most %d derived parameters, not %d", PC_SRC_MAX_DERIVED, nDer);
+            if (prior.kind != 1) engine_fail(PC_RC_SETTINGS, "a device source likelihood needs a device prior (the uniform box), not a host-callback prior");
+            S.src_id = like.source;
+            if (n > 0) { d_src = dalloc<double>((size_t)n); upload(d_src, h, sizeof(double) * (size_t)n); S.src_data = d_src; S.src_ndata = n; }
+        }
         if (like.kind == PC_LIKE_CORR_GAUSSIAN) {
             std::vector<double> T((size_t)D * D);
             for (int a = 0; a < D; ++a) for (int b = 0; b < D; ++b) T[(size_t)b * D + a] = like.invcov[(size_t)a * D + b];
@@ -1988,7 +2000,11 @@ struct Engine {
         long long nlike = 0;
         bool direct = true;
         while (have < nprior) {
-            if (pc_launch_generate_live(&S, attempt0, nprior, rows, rl, st)) engine_fail(PC_RC_NDIMS, "nDims > 256 unsupported");
+            if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
+            if (pc_launch_generate_live(&S, attempt0, nprior, rows, rl, st)) {
+                if (pc_rtc_wanted(&S) && pc_rtc_error()) engine_fail(PC_RC_SETTINGS, "%.480s", pc_rtc_error());
+                engine_fail(PC_RC_NDIMS, "nDims > 256 unsupported");
+            }
             HIPCHK(hipMemcpyAsync(hl.data(), rl, sizeof(double) * nprior, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             int nvalid = 0;
@@ -2014,6 +2030,7 @@ struct Engine {
             int a = last_attempt + 1;
             for (; S.ngrade <= 1; ++a) {
                 double l1 = 0.0;
+                if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
                 (void)pc_launch_generate_live(&S, a, 1, rows, rl, st);
                 HIPCHK(hipMemcpyAsync(&l1, rl, sizeof(double), hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
@@ -2389,10 +2406,14 @@ struct Engine {
             else if (co && !callback_mode && !spec && cohort_general_ok() && (fused_slice || !splittable)) {
                 // in step with other runs, any device likelihood / several clusters: the one-run kernel with the run in the grid
                 path[PCHIP_PATH_SLICE_WAVE]++;
+                if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
                 co->rec(CK_SLICE_G, S, {}, {(long long)B, fused_slice ? 1LL : 0LL}, {(int)batch, 0, 0, fused_slice ? bases_seq : 0});
                 if (fused_slice && co->st2 && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
             }
-            else if ((path[PCHIP_PATH_SLICE_WAVE]++, co ? (co->flush(), co->wait_next(), 0) : 0) || (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st))) { std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false; }
+            else if ((path[PCHIP_PATH_SLICE_WAVE]++, path[PCHIP_PATH_SOURCE_KERNELS] += pc_rtc_wanted(&S) ? 1 : 0, co ? (co->flush(), co->wait_next(), 0) : 0) || (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st))) {
+                if (pc_rtc_wanted(&S) && pc_rtc_error()) { std::fprintf(stderr, "polychord_hip: %s\n", pc_rtc_error()); r_rc = 1; return false; }
+                std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false;
+            }
             S.spec_guard = 0;
             kt.end(KT_SLICE, e1);
             if (split && !spec) side_prefetch(batch);      // (speculative: only once the device is known to have taken the nursery)
@@ -2840,7 +2861,7 @@ struct Engine {
                           &S.lse_ref, &S.lse_sum, &S.death_thr, &S.chol, &S.cov, &S.logZp_dead, &S.logZp2_dead, &S.phantom,
                           &S.ph_logL, &S.dead, &S.dead_logw, &S.dead_postX, &S.dead_postZ, &S.babies, &S.baby_logL, &S.baby_logL_T,
                           &S.ch_contour, &S.nhat, &S.nhat_w, &S.nhat_raw, &S.nhat_Ms, &S.ch_My, &S.live_entry, &S.dead_entry, &ph2, &phL2, &psum, &mean,
-                          &pcov, &d_lo, &d_hi, &d_invcovT, &d_mean, &d_dynL };
+                          &pcov, &d_lo, &d_hi, &d_invcovT, &d_mean, &d_dynL, &d_src };
         for (auto p : dd) dfree(*p);
         int **ii[] = { &S.live_cluster, &S.live_pos, &S.cl_list, &S.cl_n, &S.imin_slot, &S.ch_cluster, &S.ch_epoch, &S.ch_nlike,
                        &S.ch_seed_slot, &S.slot_src, &S.slot_step, &S.slot_dead, &S.sort_slot, &blk, &d_total, &pcnt, &count, &d_dynN };
@@ -3347,6 +3368,10 @@ int pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const pc
                        int nchains, const double *seeds, const double *chol, double contour, double *babies_out,
                        double *nhats_out, int *nlike_out)
 {
+    if (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & (1 << 15))) {
+        std::fprintf(stderr, "polychord_hip: pchip_slice_chains does not take a device source likelihood (or settings.ablate bit 15)\n");
+        return 1;
+    }
     pchip_settings c = *s;
     c.nlive = nchains; c.nprior = nchains; c.batch = nchains; c.do_clustering = 0;
     Engine E;

@@ -1,0 +1,350 @@
+// pc_rtc.hip -- user likelihoods written as HIP device source, fused into the sampling kernels at run time.
+//
+// A source (pchip_source_create) is a string that defines
+//     __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
+// The library compiles it with hiprtc, together with the exact text of its own sampling kernels (pc_dev.h, pc_state.h, pc_sample.hip and
+// the bodies it includes, embedded when the library is built: pc_rtc_sources.inc), for the device a run is on.  The launchers of
+// pc_sample.hip choose a kernel variant and its launch shape as they do for the built-ins, and hand the variant's name to pc_rtc_launch,
+// which instantiates it (hiprtcAddNameExpression), loads the code object once per device and launches it with the same arguments and
+// the same dynamic LDS.  settings.ablate bit 15 sends the built-in kinds the same way (a module without a user source): the test that
+// this path is the static kernel.
+//
+// libhiprtc is opened with dlopen: without it the library loads and the built-ins run; a source run then fails with a message.
+#include "pc_state.h"
+#include "../../include/polychord_hip.h"
+#include <hip/hiprtc.h>          // types only: the library is dlopen'ed
+#include <dlfcn.h>
+#include <cstdio>
+#include <cstring>
+#include <cstdlib>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <sstream>
+#include <string>
+#include <tuple>
+#include <chrono>
+#include <vector>
+
+#include "pc_rtc_sources.inc"    // generated (Makefile): pc_rtc_src_name[], pc_rtc_src_text[], pc_rtc_nsrc
+
+namespace {
+
+struct Hiprtc {
+    void *h = nullptr; bool tried = false; std::string why;
+    hiprtcResult (*CreateProgram)(hiprtcProgram *, const char *, const char *, int, const char **, const char **) = nullptr;
+    hiprtcResult (*DestroyProgram)(hiprtcProgram *) = nullptr;
+    hiprtcResult (*AddNameExpression)(hiprtcProgram, const char *) = nullptr;
+    hiprtcResult (*CompileProgram)(hiprtcProgram, int, const char *const *) = nullptr;
+    hiprtcResult (*GetLoweredName)(hiprtcProgram, const char *, const char **) = nullptr;
+    hiprtcResult (*GetProgramLogSize)(hiprtcProgram, size_t *) = nullptr;
+    hiprtcResult (*GetProgramLog)(hiprtcProgram, char *) = nullptr;
+    hiprtcResult (*GetCodeSize)(hiprtcProgram, size_t *) = nullptr;
+    hiprtcResult (*GetCode)(hiprtcProgram, char *) = nullptr;
+    bool load()
+    {   // (under the registry's compile mutex)
+        if (tried) return h != nullptr;
+        tried = true;
+        const char *env = std::getenv("PCHIP_HIPRTC_LIB");
+        const char *names[] = { env, "libhiprtc.so", "libhiprtc.so.7", "libhiprtc.so.6", "/opt/rocm/lib/libhiprtc.so" };
+        for (const char *n : names) {
+            if (!n || !*n) continue;
+            if ((h = dlopen(n, RTLD_NOW | RTLD_LOCAL))) break;
+        }
+        if (!h) { why = "libhiprtc could not be loaded (set PCHIP_HIPRTC_LIB to its path)"; return false; }
+#define PC_SYM(f) f = (decltype(f))dlsym(h, "hiprtc" #f); if (!f) { why = "libhiprtc lacks hiprtc" #f; h = nullptr; return false; }
+        PC_SYM(CreateProgram) PC_SYM(DestroyProgram) PC_SYM(AddNameExpression) PC_SYM(CompileProgram) PC_SYM(GetLoweredName)
+        PC_SYM(GetProgramLogSize) PC_SYM(GetProgramLog) PC_SYM(GetCodeSize) PC_SYM(GetCode)
+#undef PC_SYM
+        return true;
+    }
+};
+
+struct Source {
+    std::string text;                      // the user's source, behind the #define lines of its options
+    std::vector<double> data;
+};
+
+// a code object of one kernel variant for one architecture: compiled once, loaded on every device of that architecture
+struct Code {
+    std::mutex m;                          // held by the thread that compiles it; the others wait for the result
+    bool done = false;
+    std::vector<char> code; std::string lowered, err;
+};
+
+struct Registry {
+    std::mutex m;                          // the maps below; never held across a compilation or a module load
+    std::mutex cm;                         // hiprtc itself: one compilation at a time
+    Hiprtc rtc;
+    std::map<int, std::shared_ptr<Source>> src;
+    int next = 1;
+    std::map<std::tuple<int, std::string, std::string>, std::shared_ptr<Code>> code;   // (source, arch, kernel name)
+    // (source, device, kernel name) -> function; modules stay loaded for the life of the process (a run may hold the function)
+    std::map<std::tuple<int, int, std::string>, hipFunction_t> fn;
+    std::map<int, std::string> arch;       // device -> gcnArchName
+    double compile_s = 0.0; long compiles = 0;
+};
+Registry &reg() { static Registry *r = new Registry; return *r; }
+
+thread_local std::string t_err;            // why the last pc_rtc_launch of this thread failed (the engine words the run's error from it)
+
+const char *const USER_NAME = "pchip_user_source.h";
+
+// the user's options: -DNAME[=VALUE] and -UNAME only, turned into #define / #undef lines in front of the user's text (and nowhere else:
+// the library's kernels keep their own compilation).  Anything else: "" and the offending option in *bad.
+std::string options_to_defines(const char *o, std::string *bad)
+{
+    std::string out;
+    if (!o) return out;
+    std::istringstream is(o);
+    std::string w;
+    while (is >> w) {
+        if (w.size() > 2 && w.compare(0, 2, "-D") == 0) {
+            const std::string d = w.substr(2);
+            const size_t eq = d.find('=');
+            out += "#define " + (eq == std::string::npos ? d + " 1" : d.substr(0, eq) + " " + d.substr(eq + 1)) + "\n";
+        } else if (w.size() > 2 && w.compare(0, 2, "-U") == 0) out += "#undef " + w.substr(2) + "\n";
+        else { *bad = w; return ""; }
+    }
+    return out;
+}
+
+// one hiprtc program: the user's source (as the header pchip_user_source.h, when there is one), the embedded kernel sources and `unit`;
+// the names in `exprs` are instantiated and their lowered names returned.  0: ok (code filled); else the log in `log`.
+int compile(const Source *s, const std::string &unit, const std::vector<std::string> &exprs, const std::string &arch,
+            std::vector<char> &code, std::vector<std::string> &lowered, std::string &log)
+{
+    Hiprtc &R = reg().rtc;
+    std::lock_guard<std::mutex> g(reg().cm);
+    if (!R.load()) { log = R.why; return 1; }
+    std::vector<const char *> hdr, names;
+    for (int i = 0; i < pc_rtc_nsrc; ++i) { hdr.push_back(pc_rtc_src_text[i]); names.push_back(pc_rtc_src_name[i]); }
+    if (s) { hdr.push_back(s->text.c_str()); names.push_back(USER_NAME); }
+    hiprtcProgram p;
+    if (R.CreateProgram(&p, unit.c_str(), "pchip_rtc_unit.hip", (int)hdr.size(), hdr.data(), names.data()) != HIPRTC_SUCCESS) {
+        log = "hiprtcCreateProgram failed"; return 1;
+    }
+    for (const auto &e : exprs) R.AddNameExpression(p, e.c_str());
+    // the options of the library's own kernels (Makefile CXXFLAGS: -O3 -std=c++17) and the device's architecture as reported
+    const std::vector<std::string> opt = { "--offload-arch=" + arch, "-O3", "-std=c++17", "-Wno-unused-value" };
+    std::vector<const char *> o;
+    for (const auto &x : opt) o.push_back(x.c_str());
+    const hiprtcResult rc = R.CompileProgram(p, (int)o.size(), o.data());
+    size_t n = 0;
+    R.GetProgramLogSize(p, &n);
+    log.assign(n, '\0');
+    if (n) { R.GetProgramLog(p, &log[0]); log.resize(std::strlen(log.c_str())); }
+    if (rc != HIPRTC_SUCCESS) { R.DestroyProgram(&p); if (log.empty()) log = "hiprtc: compilation failed"; return 1; }
+    lowered.clear();
+    for (const auto &e : exprs) {
+        const char *ln = nullptr;
+        if (R.GetLoweredName(p, e.c_str(), &ln) != HIPRTC_SUCCESS || !ln) { R.DestroyProgram(&p); log = "hiprtc: no kernel " + e; return 1; }
+        lowered.push_back(ln);
+    }
+    R.GetCodeSize(p, &n);
+    code.resize(n);
+    R.GetCode(p, code.data());
+    R.DestroyProgram(&p);
+    return 0;
+}
+
+// the translation unit of the sampling kernels: the library's kernels (pc_sample.hip declares pchip_loglikelihood under PCHIP_USER_SOURCE),
+// then the user's text -- its macros and pragmas reach nothing of the library's
+std::string kernel_unit(const Source *s)
+{
+    return s ? std::string("#define PCHIP_USER_SOURCE 1\n#include \"pc_sample.hip\"\n#include \"") + USER_NAME + "\"\n"
+             : std::string("#include \"pc_sample.hip\"\n");
+}
+
+// the quick compile of pchip_source_create: the user's functions alone behind the same declaration, called from a small kernel
+const char *const PROBE_UNIT =
+    "__device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
+    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, double *out)\n"
+    "{ out[0] = pchip_loglikelihood(th, phi, nDims, nDerived, data, ndata); }\n"
+    "#include \"pchip_user_source.h\"\n";
+
+std::string strip_parens(const char *expr)
+{
+    std::string e(expr);
+    while (e.size() >= 2 && e.front() == '(' && e.back() == ')') e = e.substr(1, e.size() - 2);
+    return e;
+}
+
+hipFunction_t get_function(int id, const std::string &expr, std::string &err)
+{
+    Registry &G = reg();
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { err = "no HIP device"; return nullptr; }
+    const auto key = std::make_tuple(id, dev, expr);
+    std::shared_ptr<Source> s;
+    std::string arch;
+    {
+        std::lock_guard<std::mutex> g(G.m);
+        auto it = G.fn.find(key);
+        if (it != G.fn.end()) return it->second;
+        if (id != 0) {
+            auto si = G.src.find(id);
+            if (si == G.src.end()) { err = "device source handle " + std::to_string(id) + " does not exist"; return nullptr; }
+            s = si->second;
+        }
+        auto ai = G.arch.find(dev);
+        if (ai == G.arch.end()) {
+            hipDeviceProp_t pr;
+            if (hipGetDeviceProperties(&pr, dev) != hipSuccess) { err = "hipGetDeviceProperties failed"; return nullptr; }
+            ai = G.arch.emplace(dev, std::string(pr.gcnArchName)).first;
+        }
+        arch = ai->second;
+    }
+    std::shared_ptr<Code> c;
+    {
+        std::lock_guard<std::mutex> g(G.m);
+        auto &slot = G.code[std::make_tuple(id, arch, expr)];
+        if (!slot) slot = std::make_shared<Code>();
+        c = slot;
+    }
+    {
+        std::lock_guard<std::mutex> g(c->m);      // (the first thread compiles; others asking for the same code wait here, nobody else does)
+        if (!c->done) {
+            std::vector<std::string> lowered; std::string log;
+            const auto t0 = std::chrono::steady_clock::now();
+            if (compile(s.get(), kernel_unit(s.get()), { expr }, arch, c->code, lowered, log)) c->err = "run-time compilation of " + expr + " failed:\n" + log;
+            else c->lowered = lowered[0];
+            c->done = true;
+            std::lock_guard<std::mutex> g2(G.m);
+            G.compile_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); G.compiles++;
+        }
+    }
+    if (!c->err.empty()) { err = c->err; return nullptr; }
+    hipModule_t mod;
+    if (hipModuleLoadData(&mod, c->code.data()) != hipSuccess) { (void)hipGetLastError(); err = "hipModuleLoadData failed for " + expr; return nullptr; }
+    hipFunction_t f;
+    if (hipModuleGetFunction(&f, mod, c->lowered.c_str()) != hipSuccess) { (void)hipGetLastError(); err = "hipModuleGetFunction failed for " + expr; return nullptr; }
+    std::lock_guard<std::mutex> g(G.m);
+    auto ins = G.fn.emplace(key, f);
+    if (!ins.second) (void)hipModuleUnload(mod);   // another thread of this device loaded it meanwhile: keep one
+    return ins.first->second;
+}
+
+}  // namespace
+
+extern "C" {
+
+// launched by PC_LAUNCH (pc_sample.hip) with the variant, grid, block, dynamic LDS and arguments the launcher chose for the static kernel
+int pc_rtc_launch(const PcState *S, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t st, void **args)
+{
+    t_err.clear();
+    const std::string e = strip_parens(expr);
+    hipFunction_t f = get_function(S->like.kind == PC_LIKE_SOURCE ? S->src_id : 0, e, t_err);
+    if (!f) return 1;
+    // (module functions have no dynamic-LDS attribute to raise: the launch is checked against the device's limit per workgroup)
+    int dev = 0, lim = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && sh > (size_t)lim) {
+        t_err = e + ": " + std::to_string(sh) + " bytes of LDS, the device has " + std::to_string(lim); return 1;
+    }
+    if (hipModuleLaunchKernel(f, grid.x, grid.y, grid.z, block.x, block.y, block.z, (unsigned)sh, st, args, nullptr) != hipSuccess) {
+        t_err = std::string("hipModuleLaunchKernel failed for ") + e + ": " + hipGetErrorString(hipGetLastError()); return 1;
+    }
+    return 0;
+}
+const char *pc_rtc_error(void) { return t_err.empty() ? nullptr : t_err.c_str(); }
+
+// a source exists (and its data block, for the engine's upload)
+int pc_rtc_source_data(int id, const double **data, long long *n)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    auto it = G.src.find(id);
+    if (it == G.src.end()) return 1;
+    *data = it->second->data.empty() ? nullptr : it->second->data.data();
+    *n = (long long)it->second->data.size();
+    return 0;
+}
+
+// pchip_source_create: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
+// Returns the handle (> 0), or -1 with the compiler's log in `log`.
+int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, std::string *log)
+{
+    if (!source) { *log = "pchip_source_create: no source"; return -1; }
+    if (ndata < 0 || (ndata > 0 && !data)) { *log = "pchip_source_create: ndata > 0 needs a data block"; return -1; }
+    std::string bad;
+    const std::string defs = options_to_defines(options, &bad);
+    if (!bad.empty()) { *log = "pchip_source_create: option " + bad + " -- only -DNAME[=VALUE] and -UNAME are passed on"; return -1; }
+    auto s = std::make_shared<Source>();
+    s->text = defs + "#line 1\n" + source;
+    if (ndata > 0) s->data.assign(data, data + ndata);
+    std::string arch = "gfx950";
+    int dev = 0, ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&dev) == hipSuccess) {
+        hipDeviceProp_t pr;
+        if (hipGetDeviceProperties(&pr, dev) == hipSuccess) arch = pr.gcnArchName;
+    }
+    (void)hipGetLastError();
+    std::vector<char> code; std::vector<std::string> lowered;
+    if (compile(s.get(), PROBE_UNIT, { "pchip_probe" }, arch, code, lowered, *log)) return -1;
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    const int id = G.next++;
+    G.src[id] = s;
+    return id;
+}
+
+}  // extern "C"
+
+// ---- C engine API ---------------------------------------------------------------------------------------------------------------------
+extern "C" void pc_abi_set_last_error(const char *msg);
+
+extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata)
+{
+    std::string log;
+    const int id = pc_rtc_source_create(source, options, data, ndata, &log);
+    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
+    return id;
+}
+
+extern "C" void pchip_source_destroy(int handle)
+{   // (compiled modules stay loaded: a run on another thread may still launch them)
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    G.src.erase(handle);
+}
+
+// the embedded text of kernel source `i` (its file name in *name), or NULL past the last: tests compare it with the files
+extern "C" const char *pchip_rtc_embedded_source(int i, const char **name)
+{
+    if (i < 0 || i >= pc_rtc_nsrc) return nullptr;
+    if (name) *name = pc_rtc_src_name[i];
+    return pc_rtc_src_text[i];
+}
+
+// compiles, for architecture `arch`, the sampling kernels named in `names` (';'-separated name expressions) with source `handle` (0: the
+// built-ins alone) -- what a run on such a device would compile, without a device.  0: ok; else the log in log[cap].
+extern "C" int pchip_rtc_compile_check(int handle, const char *arch, const char *names, char *log, int cap, double *seconds)
+{
+    std::shared_ptr<Source> s;
+    {
+        Registry &G = reg();
+        std::lock_guard<std::mutex> g(G.m);
+        if (handle) { auto it = G.src.find(handle); if (it == G.src.end()) { if (log && cap > 0) std::snprintf(log, cap, "no source %d", handle); return 1; } s = it->second; }
+    }
+    std::vector<std::string> exprs;
+    std::string all(names ? names : ""), e;
+    std::istringstream is(all);
+    while (std::getline(is, e, ';')) if (!e.empty()) exprs.push_back(e);
+    std::vector<char> code; std::vector<std::string> lowered; std::string lg;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc;
+    rc = compile(s.get(), kernel_unit(s.get()), exprs, arch ? arch : "gfx950", code, lowered, lg);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (log && cap > 0) std::snprintf(log, cap, "%s", rc ? lg.c_str() : "");
+    return rc ? 1 : (code.empty() ? 1 : 0);
+}
+
+// run-time compilations so far and the seconds they took (measurement)
+extern "C" void pchip_rtc_stats(long *compiles, double *seconds)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    if (compiles) *compiles = G.compiles;
+    if (seconds) *seconds = G.compile_s;
+}

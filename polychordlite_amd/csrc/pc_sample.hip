@@ -14,7 +14,9 @@
 //                SliceSampling / slice_sample (chordal_sampling.f90:7-92, 163-273) and
 //                calculate_point (calculate.f90:6-50); likelihood sums are DPP butterflies.
 #include "pc_state.h"
+#ifndef __HIPCC_RTC__
 #include <cstdlib>
+#endif
 
 // ------------------------------------------------------------------------------------------
 // likelihood on a wave: lane owns DPL coordinates (dim = lane + 64*k)
@@ -25,6 +27,11 @@ struct LaneDims {
     double mean[DPL];            // corr gaussian mean / twin gaussian means are derived
     bool on[DPL];
 };
+
+#ifdef PCHIP_USER_SOURCE
+// the user's function (pc_rtc.hip): its text follows the library's in the run-time unit, so that none of its macros reach these kernels
+__device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
+#endif
 
 template <int DPL, int NROWS>
 __device__ __forceinline__ double wsum(double v) { return (DPL > 1) ? wave_sum<4>(v) : wave_sum<NROWS>(v); }
@@ -63,6 +70,16 @@ __device__ __forceinline__ double like_eval(const PcState &S, const double (&th)
             }
         s1 = wsum<DPL, NROWS>(s1); s2 = wsum<DPL, NROWS>(s2);
         return pc_logaddexp(L.norm - s1 / 2.0, L.norm - s2 / 2.0) - 0.6931471805599453;
+#ifdef PCHIP_USER_SOURCE
+    } else if (kind == PC_LIKE_SOURCE) {          // the user's function (pc_rtc.hip): every lane evaluates it on the same LDS copy of theta,
+#pragma unroll                                    // so the result is wave-uniform without a broadcast
+        for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
+        __syncthreads();                          // one wave per workgroup: cheap
+        double phi[PC_SRC_MAX_DERIVED];
+        const double l = pchip_loglikelihood(ybuf, phi, D, S.nDer, S.src_data, (long)S.src_ndata);
+        __syncthreads();
+        return l;
+#endif
     } else {                                      // random_gaussian.f90:17-30, utils.F90:1028-1048
 #pragma unroll
         for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k] - ld.mean[k];
@@ -104,6 +121,22 @@ __device__ __forceinline__ void like_phi(const PcState &S, const double (&th)[DP
     }
 }
 
+#ifdef PCHIP_USER_SOURCE
+// all nDerived values of an accepted point of a source likelihood (the user's function once more; lane 0 writes them to out)
+template <int DPL>
+__device__ __forceinline__ void like_phi_source(const PcState &S, const double (&th)[DPL], const LaneDims<DPL> &ld, int lane, double *ybuf,
+                                                double *out)
+{
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
+    __syncthreads();
+    double phi[PC_SRC_MAX_DERIVED];
+    (void)pchip_loglikelihood(ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+    if (lane == 0) for (int e = 0; e < S.nDer; ++e) out[e] = phi[e];
+    __syncthreads();
+}
+#endif
+
 // ------------------------------------------------------------------------------------------
 // initial live points: GenerateLivePoints, linear mode (generate.F90:150-183)
 // one wave per attempt; attempts are the oracle's PC_DOM_LIVEGEN streams.
@@ -134,13 +167,18 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
     double phi0, phi1;
     like_phi<DPL, 4>(S, th, ld, lane, phi0, phi1);
     double *row = rows + (size_t)a * nT;
+#ifdef PCHIP_USER_SOURCE
+    if (S.like.kind == PC_LIKE_SOURCE && S.nDer > 0) like_phi_source<DPL>(S, th, ld, lane, ybuf, row + S.d0);
+#endif
 #pragma unroll
     for (int k = 0; k < DPL; ++k)
         if (ld.on[k]) { row[lane + 64 * k] = cube[k]; row[S.p0 + lane + 64 * k] = th[k]; }
     if (lane == 0) {
-        if (S.nDer >= 1) row[S.d0] = phi0;
-        if (S.nDer >= 2) row[S.d0 + 1] = phi1;
-        for (int e = 2; e < S.nDer; ++e) row[S.d0 + e] = 0.0;
+        if (S.like.kind != PC_LIKE_SOURCE) {
+            if (S.nDer >= 1) row[S.d0] = phi0;
+            if (S.nDer >= 2) row[S.d0 + 1] = phi1;
+            for (int e = 2; e < S.nDer; ++e) row[S.d0 + e] = 0.0;
+        }
         row[S.b0] = S.logzero;                   // generate.F90:163
         row[S.l0] = logL;
         rows_logL[a] = logL;
@@ -1173,6 +1211,17 @@ __device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS> &C, const double 
             thA[k] = C.ld.lo[k] + C.ld.span[k] * cA; thB[k] = C.ld.lo[k] + C.ld.span[k] * cB;
         }
         const bool oa = __ballot(outA) != 0ull, ob = __ballot(outB) != 0ull;
+#ifdef PCHIP_USER_SOURCE
+        if (kind == PC_LIKE_SOURCE) {
+            // the user's function only ever sees points inside the prior box (calculate.f90:36-38 tests the cube first); oa / ob are
+            // wave-uniform ballots, so the barriers inside like_eval stay uniform
+            lA = oa ? C.S.logzero : like_eval<DPL, NROWS, KIND>(C.S, thA, C.ld, C.lane, C.ybuf);
+            lB = ob ? C.S.logzero : like_eval<DPL, NROWS, KIND>(C.S, thB, C.ld, C.lane, C.ybuf);
+            if (!oa && lA > C.S.logzero) C.nlike++;
+            if (!ob && lB > C.S.logzero) C.nlike++;
+            return;
+        }
+#endif
         lA = like_eval<DPL, NROWS, KIND>(C.S, thA, C.ld, C.lane, C.ybuf);
         lB = like_eval<DPL, NROWS, KIND>(C.S, thB, C.ld, C.lane, C.ybuf);
         if (oa) lA = C.S.logzero; else if (lA > C.S.logzero) C.nlike++;     // calculate.f90:36-38
@@ -1250,13 +1299,26 @@ __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB) void k_slice_many(const PcM
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
+#ifndef __HIPCC_RTC__         // (hiprtc, pc_rtc.hip: the kernels above, not the host code below)
+// The sampling kernels of a source likelihood (PC_LIKE_SOURCE), and of every kind under settings.ablate bit 15, come from a module that
+// pc_rtc.hip compiles at run time from this very text: the launchers below choose the variant and its launch shape once, PC_LAUNCH sends
+// it to the static kernel or, by its name, to the module's.
+extern "C" int pc_rtc_launch(const PcState *S, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t st, void **args);
+extern "C" int pc_rtc_wanted(const PcState *S) { return S->like.kind == PC_LIKE_SOURCE || (S->ablate & (1 << 15)) != 0; }
+template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, dim3 g, dim3 b, size_t sh, hipStream_t st, A... a)
+{
+    void *args[] = { (void *)&a... };
+    return pc_rtc_launch(S, expr, g, b, sh, st, args);
+}
+#define PC_LAUNCH(K, G, B, SH, ST, ...) do { if (pc_rtc_wanted(S)) { if (pc_rtc_go(S, #K, G, B, SH, ST, __VA_ARGS__)) return 1; } \
+                                             else hipLaunchKernelGGL(K, G, B, SH, ST, __VA_ARGS__); } while (0)
 extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL,
                                        hipStream_t st)
 {
     const size_t sh = sizeof(double) * S->D;
-    if (S->D <= 64) hipLaunchKernelGGL((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
-    else if (S->D <= 128) hipLaunchKernelGGL((k_generate_live<2>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
-    else if (S->D <= 256) hipLaunchKernelGGL((k_generate_live<4>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
+    if (S->D <= 64) PC_LAUNCH((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
+    else if (S->D <= 128) PC_LAUNCH((k_generate_live<2>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
+    else if (S->D <= 256) PC_LAUNCH((k_generate_live<4>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
     else return 1;
     return 0;
 }
@@ -1387,18 +1449,18 @@ extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchai
 #define PC_SLICE_FUSED_L(NROWS, FW, LN) { \
         if ((LN == 3 || LN == 5) && help) { \
         if (sh4 > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 4, FW, LN>, sh4); \
-        hipLaunchKernelGGL((k_slice<1, NROWS, false, 4, FW, LN>), dim3(nchains / 4), dim3(512), sh4, st, *S, batch, phi_lds, 0); } else { \
+        PC_LAUNCH((k_slice<1, NROWS, false, 4, FW, LN>), dim3(nchains / 4), dim3(512), sh4, st, *S, batch, phi_lds, 0); } else { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW, LN>, sh); \
-        hipLaunchKernelGGL((k_slice<1, NROWS, false, 1, FW, LN>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } }
+        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW, LN>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } }
 #define PC_SLICE_FUSED(NROWS, FW) { \
         if (leanf == 3) PC_SLICE_FUSED_L(NROWS, FW, 3) else if (leanf == 4) PC_SLICE_FUSED_L(NROWS, FW, 4) else if (leanf == 5) PC_SLICE_FUSED_L(NROWS, FW, 5) else \
         if (lean) { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW, 1>, sh); \
         if (help) { if (sh4 > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 4, FW, 1>, sh4); \
-        hipLaunchKernelGGL((k_slice<1, NROWS, false, 4, FW, 1>), dim3(nchains / 4), dim3(512), sh4, st, *S, batch, phi_lds, 0); } else \
-        hipLaunchKernelGGL((k_slice<1, NROWS, false, 1, FW, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } else { \
+        PC_LAUNCH((k_slice<1, NROWS, false, 4, FW, 1>), dim3(nchains / 4), dim3(512), sh4, st, *S, batch, phi_lds, 0); } else \
+        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } else { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW>, sh); \
-        hipLaunchKernelGGL((k_slice<1, NROWS, false, 1, FW>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } }
+        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } }
     if (D <= 8) PC_SLICE_FUSED(1, 8)
     else if (D <= 16) PC_SLICE_FUSED(1, 16)
     else PC_SLICE_FUSED(2, 24)
@@ -1424,7 +1486,7 @@ extern "C" int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R
         const int leanf = slice_lean_functor(S) == 5 ? 0 : slice_lean_functor(S);
 #define PC_SLICE_FUSED_ML(NROWS, FW, LN) { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice_many<1, NROWS, false, 1, FW, LN>, sh); \
-        hipLaunchKernelGGL((k_slice_many<1, NROWS, false, 1, FW, LN>), dim3(nchains, R), dim3(64), sh, st, dR, phi_lds, 0); }
+        PC_LAUNCH((k_slice_many<1, NROWS, false, 1, FW, LN>), dim3(nchains, R), dim3(64), sh, st, dR, phi_lds, 0); }
 #define PC_SLICE_FUSED_M(NROWS, FW) { if (leanf == 3) PC_SLICE_FUSED_ML(NROWS, FW, 3) else if (leanf == 4) PC_SLICE_FUSED_ML(NROWS, FW, 4) else PC_SLICE_FUSED_ML(NROWS, FW, 0) }
         if (D <= 8) PC_SLICE_FUSED_M(1, 8)
         else if (D <= 16) PC_SLICE_FUSED_M(1, 16)
@@ -1438,7 +1500,7 @@ extern "C" int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R
     const int leanf = slice_lean_functor(S) == 5 ? 0 : slice_lean_functor(S);
 #define PC_SLICE_ML(DPL, NROWS, LN) { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice_many<DPL, NROWS, false, 1, 0, LN>, sh); \
-        hipLaunchKernelGGL((k_slice_many<DPL, NROWS, false, 1, 0, LN>), dim3(nchains, R), dim3(64), sh, st, dR, phi_lds, 0); }
+        PC_LAUNCH((k_slice_many<DPL, NROWS, false, 1, 0, LN>), dim3(nchains, R), dim3(64), sh, st, dR, phi_lds, 0); }
 #define PC_SLICE_M(DPL, NROWS) { if (leanf == 3) PC_SLICE_ML(DPL, NROWS, 3) else if (leanf == 4) PC_SLICE_ML(DPL, NROWS, 4) else PC_SLICE_ML(DPL, NROWS, 0) }
     if (D <= 16) PC_SLICE_M(1, 1)
     else if (D <= 32) PC_SLICE_M(1, 2)
@@ -1476,7 +1538,7 @@ extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hi
     if (mat_lds && D > 64 && D <= 128 && nchains % 4 == 0 && S->ngrade <= 1 && !S->seq_mode && !wpb_off && 4 * sh + mb <= 150 * 1024) {
         const size_t sh4 = 4 * sh + mb;
         if (sh4 > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<2, 4, false, 4>, sh4);
-        hipLaunchKernelGGL((k_slice<2, 4, false, 4>), dim3(nchains / 4), dim3(256), sh4, st, *S, batch, phi_lds, mat_lds);
+        PC_LAUNCH((k_slice<2, 4, false, 4>), dim3(nchains / 4), dim3(256), sh4, st, *S, batch, phi_lds, mat_lds);
         return 0;
     }
     if (mat_lds) sh += mb;
@@ -1485,16 +1547,16 @@ extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hi
         S->ngrade <= 1 && !S->seq_mode && !mat_lds) {
         // BASELINE configs[4]'s shape: the kernel without its other variants (LEAN = 2)
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<2, 4, false, 1, 0, 2>, sh);
-        hipLaunchKernelGGL((k_slice<2, 4, false, 1, 0, 2>), dim3(nchains), dim3(64), sh, st, *S, batch, 0, 0);
+        PC_LAUNCH((k_slice<2, 4, false, 1, 0, 2>), dim3(nchains), dim3(64), sh, st, *S, batch, 0, 0);
         return 0;
     }
 #define PC_SLICE_LAUNCH1(DPL, NROWS, GR) { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, GR>, sh); \
-        hipLaunchKernelGGL((k_slice<DPL, NROWS, GR>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, mat_lds); }
+        PC_LAUNCH((k_slice<DPL, NROWS, GR>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, mat_lds); }
     const int leanf = (D <= 64 && !mat_lds) ? slice_lean_functor(S) : 0;
 #define PC_SLICE_LAUNCHL(DPL, NROWS, LN) { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, false, 1, 0, LN>, sh); \
-        hipLaunchKernelGGL((k_slice<DPL, NROWS, false, 1, 0, LN>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, mat_lds); }
+        PC_LAUNCH((k_slice<DPL, NROWS, false, 1, 0, LN>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, mat_lds); }
 #define PC_SLICE_LAUNCH(DPL, NROWS) { if (DPL == 1 && leanf == 3) PC_SLICE_LAUNCHL(1, NROWS, 3) else if (DPL == 1 && leanf == 4) PC_SLICE_LAUNCHL(1, NROWS, 4) else if (DPL == 1 && leanf == 5) PC_SLICE_LAUNCHL(1, NROWS, 5) else \
         if (S->ngrade > 1 || S->seq_mode) PC_SLICE_LAUNCH1(DPL, NROWS, true) else PC_SLICE_LAUNCH1(DPL, NROWS, false) }
     if (D <= 16) PC_SLICE_LAUNCH(1, 1)
@@ -1508,3 +1570,4 @@ extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hi
 #undef PC_SLICE_LAUNCH1
     return 0;
 }
+#endif  // __HIPCC_RTC__

@@ -544,12 +544,17 @@
 #pragma unroll
             for (int k = 0; k < DPL; ++k) if (ld.on[k]) tb_row[64 * k] = th[k];
         } else if (!lean2 && nDer > 0) {
+#ifdef PCHIP_USER_SOURCE
+            if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) like_phi_source<DPL>(S, th, ld, lane, ybuf, row + o_d0); else
+#endif
+            {
             double phi0, phi1;
             like_phi<DPL, NROWS, KINDV>(S, th, ld, lane, phi0, phi1);
             if (lane == 0) {
                 row[o_d0] = phi0;
                 if (nDer >= 2) row[o_d0 + 1] = phi1;
                 for (int e = 2; e < nDer; ++e) row[o_d0 + e] = 0.0;
+            }
             }
         }
         if (lane == 0) {
@@ -588,6 +593,14 @@
             if (s >= nr) continue;
             double *row = S.babies + ((size_t)chain * nr + s) * nT;
             const double *tt = tbuf + (size_t)s * (D + 1);
+#ifdef PCHIP_USER_SOURCE
+            if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) {   // the user's function, lane = baby
+                double phi[PC_SRC_MAX_DERIVED];
+                (void)pchip_loglikelihood(tt, phi, D, S.nDer, S.src_data, (long)S.src_ndata);
+                for (int e = 0; e < S.nDer; ++e) row[S.d0 + e] = phi[e];
+                continue;
+            }
+#endif
             double phi0 = 0.0, phi1 = 0.0;
             if (lean || LEAN == 5 || (LEAN == 0 && S.like.kind == PC_LIKE_GAUSSIAN)) {
                 double r2 = 0.0;

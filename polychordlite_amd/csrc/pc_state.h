@@ -174,6 +174,10 @@ struct PcState {
     // they are done and stamp it with notify_seq, so the host learns the outcome of a round by watching memory instead
     // of a copy + stream synchronisation (and goes on enqueueing while the row-copy kernels of the round still run)
     PcCtl *ctl_host; unsigned notify_seq;
+    // PC_LIKE_SOURCE / settings.ablate bit 15: the sampling kernels come from a module compiled at run time (pc_rtc.hip) for source
+    // handle src_id (0: no user source, the built-ins only)
+    int src_id, src_pad;
+    const double *src_data; long long src_ndata;   // the user's read-only data block (device)
 };
 
 // One run's share of a launch made for several runs at once (pchip_run_repeats: the runs of a device go round by round together,
@@ -198,7 +202,7 @@ template <class T, class B> __device__ __forceinline__ T *pc_as_global(T *p, con
     return (T *)(gchar *)(uintptr_t)p;
 }
 // the state of run blockIdx.y with every pointer member global (a member added to PcState must be added here: the size is checked)
-static_assert(sizeof(PcState) == 944, "PcState changed: add the new pointer members to pc_many_state, then update this size");
+static_assert(sizeof(PcState) == 968, "PcState changed: add the new pointer members to pc_many_state, then update this size");
 __device__ __forceinline__ PcState pc_many_state(const PcManyRec *R, int run)
 {
     PcState S = R[run].S;
@@ -211,7 +215,7 @@ __device__ __forceinline__ PcState pc_many_state(const PcManyRec *R, int run)
     G(babies); G(baby_logL); G(baby_logL_T); G(ch_cluster); G(ch_epoch); G(ch_nlike); G(ch_seed_slot); G(ch_contour);
     G(nhat); G(nhat_w); G(nhat_raw); G(nhat_Ms); G(ch_My); G(plan); G(sort_slot); G(sort_key);
     G(slot_src); G(slot_dead); G(slot_step); G(ch_nlike_g); G(logn); G(nn_list); G(nn_slot_owner); G(nn_chain_slot);
-    G(nn_pts); G(nn_code); G(ctl); G(ctl_host);
+    G(nn_pts); G(nn_code); G(ctl); G(ctl_host); G(src_data);
 #undef G
     return S;
 }
@@ -287,6 +291,7 @@ __device__ __forceinline__ double pc_seq_uniform(const PcState &S, unsigned long
 // only ever has to grow.  Launch helpers are called from several host threads (the scheduler groups of pchip_run_repeats, runs on several
 // devices): a guard that is a plain function-local static races (one thread lowers the limit between another's check and its launch, and a
 // mark set for one device hides the need on the next).  One mutex, one high-water mark per (kernel, device); never lowered.
+#ifndef __HIPCC_RTC__
 #include <mutex>
 #include <map>
 #include <utility>
@@ -305,5 +310,6 @@ inline void pc_need_dyn_lds(const void *kernel, size_t bytes)
     if (bytes > m) { (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); m = bytes; }
     mine = m;
 }
+#endif
 
 
