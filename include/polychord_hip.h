@@ -140,12 +140,8 @@ typedef struct {
                            contraction of clustered runs ends its launch at a cluster's death (the host relaunches for the rest of the nursery) instead
                            of sorting the live set itself and going on; bit 9 = the kill-off of a run that ends with several clusters by the general
                            contraction kernel instead of the one-wave kernel k_killoff_cl (the same bits); bit 10 = several clusters: the contraction whose ONE
-                           wavefront decides chain after chain (k_consume_cl) instead of the one with parallel decisions (k_consume_clp): the same run; bit 11 = k_consume_clp with
-                           update_evidence and the live evidence as sums over all of a pass's deaths (a walk per cluster, pair sums, prefix sums: phase C' of
-                           pc_consume_clp_body.inc) instead of death after death on two wavefronts -- the same run to rounding in <Z^2>; an experiment that is
-                           NOT the default: its walks are as long as the largest cluster's events, and at the BASELINE shapes that is no shorter; bit 12 = runs in step
-                           (and bit 7): the deviates of a basis made in the registers of the Gram-Schmidt kernel (k_bases_own) instead of
-                           passing through HBM from a kernel of their own -- the same bases bit for bit, a third of the round's bytes less, NOT faster; bit 13 = the
+                           wavefront decides chain after chain (k_consume_cl) instead of the one with parallel decisions (k_consume_clp): the same run; bits 11, 12 = retired,
+                           no effect (experiments that were removed, CHANGELOG.md); bit 13 = the
                            fused sampling kernel with ONE wavefront a workgroup (a chain) instead of four chains and their four helper wavefronts
                            (deck shuffle and whitening next to the seed choice instead of in front of it): the same numbers; bit 14 = with the helper, the closed
                            form's s.M.s of a direction reduced by the chain at the head of its slice instead of taken from the table the helper made with the

@@ -57,7 +57,7 @@
     __shared__ double out_d[8];
     __shared__ double ref_d[8];        // launch-wide references: Lhi, lxm0
     __shared__ int lp_prog, lp_done, lp_stop, lp_lists;      // chains >= lp_prog are decided; the decisions are done; first chain that must not be consumed (-2: none); chains >= lp_lists are in the lists
-    __shared__ int pa_Tp, pa_K, pa_end, pa_hard, pa_jupd, pa_flag;       // steps decided, acceptances among them, the code of the step that ends the pass, first step with a baby no list resolves, the death that triggers the update
+    __shared__ int pa_Tp, pa_K, pa_end, pa_hard, pa_jupd;       // steps decided, acceptances among them, the code of the step that ends the pass, first step with a baby no list resolves, the death that triggers the update
     __shared__ double pa_sum0, pa_sum_end;
     __shared__ long long pa_scan[3 * (CLP_NT / 64)];
     __shared__ long long out_l[4];
@@ -254,7 +254,7 @@
 #pragma unroll
               for (int u = 0; u < 4; ++u) if (e0 + u * CLP_NT < nc * nc) xlinM[at[u]] = exp(v[u] - 2.0 * lxm0); } }
     }
-    if (tid == 0) { lp_prog = T; lp_done = 0; lp_stop = -2; lp_lists = T; pa_hard = 0x7fffffff; pa_end = 0x7fffffff; pa_jupd = 0x7fffffff; pa_flag = 0; }
+    if (tid == 0) { lp_prog = T; lp_done = 0; lp_stop = -2; lp_lists = T; pa_hard = 0x7fffffff; pa_end = 0x7fffffff; pa_jupd = 0x7fffffff; }
     const int curC_init = cl_uni((sSlotOf[0] != 0xFFFFu && sSort[0].L < PC_HUGE) ? sS[sSlotOf[0] != 0xFFFFu ? sSlotOf[0] : 0].c : 0);
     __syncthreads();
     const long long cyc0 = clock64();
@@ -479,7 +479,6 @@
         if (lane == 0) pa_sum0 = s0;
     }
     __syncthreads();
-    unsigned short *rkD = link, *rkA = idxOf;                              // (the pointer jumping and phase A are over)
     unsigned short *dstart = (unsigned short *)kmin;                       // [CL_MAXC + 1] where a cluster's deaths begin, the deaths taken cluster by cluster (kmin's LDS: unused between staging and write back)
     int my_r[(1024 + CLP_NT - 1) / CLP_NT]; double my_rat[(1024 + CLP_NT - 1) / CLP_NT];
 #pragma unroll
@@ -493,7 +492,6 @@
             for (int c2 = 0; c2 < c; ++c2) { const unsigned a = ctot[c2 * CL_MAXC + cd], b = ctot[c2 * CL_MAXC + ca]; Dd += (int)(a & 255u); Ad += (int)(a >> 8); Da += (int)(b & 255u); Aa += (int)(b >> 8); }
             const int nd = clN0[cd] + Ad - Dd, na = clN0[ca] + Aa - Da;
             my_r[u] = Dd;                                                  // my place among my cluster's deaths
-            rkD[j] = (unsigned short)Dd; rkA[j] = (unsigned short)Aa;      // ... and among the additions to the newcomer's cluster (phase C' lays the events out by them)
             sEvt[wj].b = (unsigned)nd | ((unsigned)na << 16);
             my_rat[u] = (double)nd * srcp[nd + 1];
             if (nd - 1 == 0 && cd != ca) {                                 // a cluster died (delete_cluster)
@@ -788,311 +786,6 @@
     __syncthreads();
     CLP_MARK(4);
 
-    // ------------------------------------------------------------------ phase C': update_evidence and the live evidence of ALL the pass's deaths at once
-    // k_consume_cl's waves 1 and 2 make them death after death, ~1000 cycles each on a chain of dependent instructions: a third of this kernel's time
-    // when everything in front of them was parallel.  In linear space about the launch's references (section 5e) both are sums:
-    //   * a cluster's volume X_p, F_p = prod n/(n+1), G_p = prod n/(n+2), its log volume and its own accumulators <Z_p>, <Z_p^2>, <Z_p X_p> change at ITS
-    //     deaths only: a thread a cluster walks them in their order -- the serial kernel's statements in its order, the same bits (log weights included);
-    //   * <Z> is the running sum of X_d L / (n+1) over the deaths (one wavefront, in their order: the same bits);
-    //   * Y_q = <Z X_q> / F_q moves by xlin[d][q] F_d c1 kZX_q at a death in another cluster (F_q cancels) and by XXs c2 kZX_q / (F_q rat) at its own: a SUM over
-    //     the deaths, so <Z X_d> in front of death j is (Y_d0 + sum_{i<j} ...) F_d -- the pair sum below -- and <Z^2> the sum of 2 (<Z X_d> c1 k2a + <X^2>.. k2b);
-    //   * the live evidence sum_p X_p <L>_p changes in two clusters a death: a thread a cluster walks ITS deaths and additions (the log-sum-exp bookkeeping of
-    //     utils.F90 with its reference switches: the same bits per cluster) and leaves what each moved the sum by; more_samples_needed is a prefix sum away.
-    // Not here (the serial waves below take the pass): a newcomer more than 600 nats above every cluster's reference (all clusters re-based: the first launches
-    // of a steep likelihood), tables that do not fit (more chains than half the live set), settings.ablate bit 11.
-    const int Kc = out_i[14];
-    double *T1 = (double *)(smem + Y.sorted), *T2 = T1 + S.B, *T3 = T2 + S.B;       // [Kc] a_j = F_d c1, s_j = XXs c2 / (F_d rat), tXX_j (the sorted snapshot's LDS: the commit was its last reader)
-    unsigned *ordR = (unsigned *)(T3 + S.B);                                        // [Kc][3] the deaths cluster by cluster: exp(L - Lhi) (two words), n | chain << 16
-    unsigned short *dList = sU, *evList = ctot, *dStart = (unsigned short *)kmin, *evStart = dStart + (CL_MAXC + 2);
-    double *cstZX0 = (double *)sOwn, *cstKZX = cstZX0 + CL_MAXC, *cstK2A = cstKZX + CL_MAXC, *cstF = cstK2A + CL_MAXC;      // per cluster (the own-accumulator records' LDS: held in registers meanwhile)
-    int *cntD = (int *)(cstF + CL_MAXC), *cntA = cntD + CL_MAXC;
-    double *termF = (double *)cntD;                                                 // [CL_MAXC] a cluster's term of the live sum when the pass is over (the counters' LDS, behind C1)
-    // (what the addition of a chain's last baby moved the live sum by goes to sCand[rank].L -- the candidates' logL, which nothing reads any more --, what the
-    //  death did to sEvt[].eL: two writers a death, each with a word of its own)
-    ClOwn own_keep{}; bool parC = false;
-    double pc_Xp = 0.0, pc_Flog = 0.0, pc_Glog = 0.0, pc_lref = 0.0, pc_lsum = 0.0; int pc_deaths = 0;       // thread c < nc: cluster c's state when the pass is over
-    {
-        if (tid == 0) pa_flag = (!(S.ablate & 2048) || Kc == 0 || 36 * (size_t)S.B > 18 * (size_t)(NS + 1) || S.B > Ncap || nc > CL_MAXC) ? 1 : 0;
-        __syncthreads();
-        // the reference of the live sums: the largest of the clusters' log-sum-exp references; a newcomer far above it means re-basing (serial waves)
-        double R0 = -PC_HUGE;
-        for (int q = lane; q < nc; q += 64) if (clN0[q] > 0) R0 = fmax(R0, S.lse_ref[q]);
-        R0 = wave_max(R0);
-        for (int j = tid; j < Kc; j += CLP_NT) if (sCh[T - 1 - (int)stepOf[j]].last - R0 > 600.0) pa_flag = 1;
-        if (tid < CL_MAXC) own_keep = sOwn[tid < nc ? tid : 0];
-        __syncthreads();
-        parC = pa_flag == 0;
-        if (parC) {
-            const double logZ0 = ctl->logZ, logZ20 = ctl->logZ2;
-            const double rZ = fmax(logZ0, lxm0 + Lhi), kZ = exp(lxm0 + Lhi - rZ);
-            // ---- C1: per-cluster constants, the deaths (and the deaths + additions) cluster by cluster
-            if (tid < CL_MAXC) {
-                const bool in = tid < nc;
-                const double zx0 = in ? S.logZXp[tid] : NEGBIG;
-                const double rzx = fmax(zx0, 2.0 * lxm0 + Lhi);
-                cstZX0[tid] = in ? exp(zx0 - rzx) : 0.0; cstKZX[tid] = exp(2.0 * lxm0 + Lhi - rzx); cstK2A[tid] = rzx;      // (k2a needs rZ2: below)
-                cntD[tid] = 0; cntA[tid] = 0;
-            }
-            __syncthreads();
-            double rZXmax = -PC_HUGE;
-            for (int q = lane; q < nc; q += 64) rZXmax = fmax(rZXmax, cstK2A[q]);
-            rZXmax = wave_max(rZXmax);
-            const double rZ2 = fmax(logZ20, fmax(rZXmax + Lhi, 2.0 * lxm0 + 2.0 * Lhi)), k2b = exp(2.0 * lxm0 + 2.0 * Lhi - rZ2);
-            int my_pd[(1024 + CLP_NT - 1) / CLP_NT], my_pe[(1024 + CLP_NT - 1) / CLP_NT], my_pa[(1024 + CLP_NT - 1) / CLP_NT];
-#pragma unroll
-            for (int u = 0; u < (1024 + CLP_NT - 1) / CLP_NT; ++u) {
-                const int j = tid + u * CLP_NT;
-                if (j < Kc) { const unsigned me = cdca[j]; atomicAdd(&cntD[me & 255u], 1); atomicAdd(&cntA[(me >> 8) & 127u], 1); }
-            }
-            __syncthreads();
-            const double rzx_mine = tid < CL_MAXC ? cstK2A[tid] : 0.0;
-            __syncthreads();
-            if (tid < CL_MAXC) cstK2A[tid] = exp(rzx_mine + Lhi - rZ2);
-            if (wv == 0) {
-                int d0 = cntD[2 * lane], d1 = cntD[2 * lane + 1], e0 = d0 + cntA[2 * lane], e1 = d1 + cntA[2 * lane + 1];
-                int id = d0 + d1, ie = e0 + e1;
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) { const int o = __shfl_up(id, dd), o2 = __shfl_up(ie, dd); if (lane >= dd) { id += o; ie += o2; } }
-                dStart[2 * lane] = (unsigned short)(id - d0 - d1); dStart[2 * lane + 1] = (unsigned short)(id - d1);
-                evStart[2 * lane] = (unsigned short)(ie - e0 - e1); evStart[2 * lane + 1] = (unsigned short)(ie - e1);
-                if (lane == 63) { dStart[CL_MAXC] = (unsigned short)id; evStart[CL_MAXC] = (unsigned short)ie; }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < (1024 + CLP_NT - 1) / CLP_NT; ++u) {
-                const int j = tid + u * CLP_NT;
-                if (j < Kc) {
-                    const unsigned me = cdca[j]; const int cd = (int)(me & 255u), ca = (int)((me >> 8) & 127u);
-                    const int wj = T - 1 - (int)stepOf[j];
-                    const ClEvt ev = sEvt[wj];
-                    const int nd = (int)(ev.b & 0xFFFFu), na = (int)(ev.b >> 16);
-                    const int Dd = rkD[j], Aa = rkA[j], Ad = nd - clN0[cd] + Dd, Da = clN0[ca] + Aa - na;
-                    const int pd = (int)dStart[cd] + Dd;
-                    dList[pd] = (unsigned short)j;
-                    ordR[3 * pd] = (unsigned)__double2loint(ev.eL); ordR[3 * pd + 1] = (unsigned)__double2hiint(ev.eL); ordR[3 * pd + 2] = (unsigned)nd | ((unsigned)wj << 16);
-                    evList[(int)evStart[cd] + Dd + Ad] = (unsigned short)j;
-                    evList[(int)evStart[ca] + Da + Aa] = (unsigned short)(j | 0x8000);
-                }
-            }
-            __syncthreads();
-            // ---- C2: the walks.  Threads 0 .. nc-1: a cluster's deaths (update_evidence's per-cluster half); threads 128 .. 128+nc-1: its deaths and additions (the live sum)
-            const double *xlinM = S.XpXq + (size_t)maxc * maxc;
-            const long long wk_t0 = clock64();
-            if (tid < nc) {
-                const int c = tid, p0 = dStart[c], p1 = dStart[c + 1];
-                double XL = clX0[c], F = 1.0, G = 1.0, Xp = S.logXp[c], Flog = 0.0, Glog = 0.0;
-                const double xdiag = xlinM[(size_t)c * maxc + c];
-                ClOwn o = own_keep;
-                // (the next death's record and tables are on their way while this one is worked in)
-                unsigned n_lo = 0, n_hi = 0, n_nw = 0; int n_j = 0; double n_r1 = 0, n_r2 = 0, n_l0 = 0, n_l1 = 0, n_l2 = 0;
-                auto fetch = [&](int p) {
-                    n_lo = ordR[3 * p]; n_hi = ordR[3 * p + 1]; n_nw = ordR[3 * p + 2]; n_j = dList[p];
-                    const int nd = (int)(n_nw & 0xFFFFu);
-                    n_r1 = srcp[nd + 1]; n_r2 = srcp[nd + 2]; n_l0 = slogn[nd]; n_l1 = slogn[nd + 1]; n_l2 = slogn[nd + 2];
-                };
-                if (p0 < p1) fetch(p0);
-                for (int p = p0; p < p1; ++p) {
-                    const double eL = __hiloint2double((int)n_hi, (int)n_lo); const int nd = (int)(n_nw & 0xFFFFu), w = (int)(n_nw >> 16), j = n_j;
-                    const double r1 = n_r1, r2 = n_r2, l0 = n_l0, l1 = n_l1, l2 = n_l2;
-                    if (p + 1 < p1) fetch(p + 1);
-                    const double rat = (double)nd * r1, c1 = eL * r1, c2 = eL * rat * r2;
-                    const double XXs = xdiag * G;                               // <X_c^2> now, about X_max^2
-                    const double logweight = Xp - l1;
-                    const double tZ = XL * c1;
-                    const double tXX = XXs * (eL * c1 * r2);
-                    T1[j] = F * c1; T2[j] = XXs * c2 / (F * rat); T3[j] = tXX;
-                    sHead[w].logw = logweight; sHead[w].zl = tZ;                // (zl: the term; the running sum takes its place below)
-                    const double zp_n = o.zp + tZ * o.kzp;
-                    const double zp2_n = o.zp2 + 2.0 * (o.zpx * c1 * o.kp2a + tXX * o.kp2b);
-                    const double zpx_n = o.zpx * rat + XXs * c2 * o.kzpx;
-                    o.zp = zp_n; o.zp2 = zp2_n; o.zpx = zpx_n; o.touched = 1;
-                    Xp += l0 - l1; Flog += l0 - l1; Glog += l0 - l2; XL *= rat; F *= rat; G *= (double)nd * r2;
-                }
-                own_keep = o; pc_Xp = Xp; pc_Flog = Flog; pc_Glog = Glog; pc_deaths = p1 - p0;
-                cstF[c] = F;
-            } else if (tid >= CL_MAXC && tid < CL_MAXC + nc) {
-                const int c = tid - CL_MAXC, p0 = evStart[c], p1 = evStart[c + 1];
-                int n = clN0[c];
-                double lref = S.lse_ref[c], lsum = S.lse_sum[c], XL = clX0[c];
-                double Eq = n > 0 ? exp(lref - R0) : 0.0, kd = exp(Lhi - lref), rn = srcp[n];
-                double term = n > 0 ? (lsum * rn) * XL * Eq : 0.0;
-                int n_e = 0, n_w = 0;
-                auto fetch = [&](int p) { n_e = evList[p]; n_w = T - 1 - (int)stepOf[n_e & 0x7FFF]; };
-                if (p0 < p1) fetch(p0);
-                for (int p = p0; p < p1; ++p) {
-                    const int e = n_e, w = n_w, j = e & 0x7FFF;
-                    if (p + 1 < p1) fetch(p + 1);
-                    const unsigned b = sEvt[w].b;
-                    if (!(e & 0x8000)) {
-                        // delete_outermost_point: the cluster's volume, count and log-sum-exp
-                        const int nd = (int)(b & 0xFFFFu);
-                        const double eL = sEvt[w].eL;
-                        const double rat = (double)nd * srcp[nd + 1];
-                        const double e_del = eL * kd;                           // exp(L - lse_ref[c])
-                        XL *= rat; n = nd - 1; lsum -= e_del; rn = srcp[n > 0 ? n : 0];
-                        const double tn = n > 0 ? (lsum * rn) * XL * Eq : 0.0;
-                        sEvt[w].eL = tn - term; term = tn;                      // (what the death moved the live sum by takes the exponential's place)
-                    } else {
-                        // add_point: the receiving cluster's log-sum-exp (utils.F90 logsumexp bookkeeping)
-                        const int na = (int)(b >> 16);
-                        const ClChain ch = sCh[w];
-                        const double Llast = ch.last, me_e = sCand[ch.rank & 0xFFFF].e;
-                        double nref = lref, nsum, nEq = Eq, nkd = kd;
-                        if (na == 0 || Llast > lref) {                          // the cluster's reference moves to the newcomer
-                            nsum = (na == 0) ? 1.0 : lsum * exp(lref - Llast) + 1.0;
-                            nref = Llast;
-                            nEq = exp(nref - R0); nkd = exp(Lhi - nref);
-                        } else {
-                            const bool plain = fabs(Llast - Lhi) < 600.0 && fabs(Lhi - lref) < 600.0;
-                            nsum = lsum + (plain ? me_e * nkd : exp(Llast - lref));
-                        }
-                        n = na + 1; lref = nref; lsum = nsum; Eq = nEq; kd = nkd; rn = srcp[n];
-                        const double tn = (lsum * rn) * XL * Eq;
-                        sCand[ch.rank & 0xFFFF].L = tn - term; term = tn;
-                    }
-                }
-                pc_lref = lref; pc_lsum = lsum;
-                termF[c] = term;                                                // (the cluster's term when the pass is over: the estimate that leaves the kernel)
-            }
-            if (tid == 0) ctl->wave_cyc[0] += clock64() - wk_t0;              // (developer counters in this mode: [0] / [1] the deaths' / the events' walks -- a wavefront as long as its longest cluster)
-            if (tid == CL_MAXC) ctl->wave_cyc[1] += clock64() - wk_t0;
-            __syncthreads();
-            // ---- C3: <Z> behind every death, in the order of the deaths (one wavefront); the live sum behind every death (prefix sum); the pair sums
-            if (wv == 0) {
-                double zl = exp(logZ0 - rZ);
-                for (int j0 = 0; j0 < Kc; j0 += 64) {
-                    const int j = j0 + lane; const int wj = j < Kc ? T - 1 - (int)stepOf[j] : 0;
-                    const double tz = j < Kc ? sHead[wj].zl : 0.0;
-                    double mine = 0.0;
-                    const int nn = Kc - j0 < 64 ? Kc - j0 : 64;
-                    for (int l = 0; l < nn; ++l) { const double t = readlane_f64(tz, l); zl += t * kZ; mine = (lane == l) ? zl : mine; }
-                    if (j < Kc) sHead[wj].zl = mine;
-                }
-                if (lane == 0) { out_d[0] = cl_log(rZ, zl, S.logzero); out_d[4] = rZ; out_d[5] = zl; }
-            }
-            // (the pair sums: what the deaths before j added to Y of j's cluster.  A wavefront takes 64 deaths (lane = death j) and walks the deaths i in front
-            //  of them: the matrix row of i's cluster sits across the wave's lanes -- asked for four deaths ahead, four buffers of fixed roles -- and lane j
-            //  takes the entry of ITS cluster by a cross-lane read; a_i, s_i and i's cluster come 64 at a time by v_readlane.  No load depends on a load)
-            double z2 = 0.0;
-            auto row_of = [&](double (&r)[J], int c) {
-#pragma unroll
-                for (int jj = 0; jj < J; ++jj) { const int q = lane + 64 * jj; r[jj] = (q < nc) ? xlinM[(size_t)c * maxc + q] : 0.0; }
-            };
-            auto entry = [&](const double (&r)[J], int c) -> double {       // the row's entry for cluster c, c different from lane to lane
-                const double lo = __shfl(r[0], c & 63);
-                if (J == 1) return lo;
-                const double hi = __shfl(r[J - 1], c & 63);
-                return c < 64 ? lo : hi;
-            };
-            for (int c = wv; c * 64 < Kc; c += CLP_NT / 64) {
-                const int j = c * 64 + lane; const bool inj = j < Kc;
-                const int dj = inj ? (int)(cdca[j] & 255u) : 0;
-                double Sj = 0.0;
-                const int iend = (c * 64 + 64 < Kc) ? c * 64 + 64 : Kc;      // (deaths in front of the group's last one)
-                double rA[J], rB[J], rC[J], rD[J];
-                auto cl_at = [&](int i) -> int { return (int)(cdca[i < Kc ? i : Kc - 1] & 255u); };
-                row_of(rA, cl_at(0)); row_of(rB, cl_at(1)); row_of(rC, cl_at(2)); row_of(rD, cl_at(3));
-                for (int i0 = 0; i0 < iend; i0 += 64) {
-                    const int iq = i0 + lane < Kc ? i0 + lane : Kc - 1;
-                    const int v_d = (int)(cdca[iq] & 255u), v_d4 = cl_at(i0 + lane + 4); const double v_a = T1[iq], v_s = T2[iq];
-                    const int n = iend - i0 < 64 ? iend - i0 : 64;
-                    auto step = [&](int l, double (&row)[J]) __attribute__((always_inline)) {
-                        const int i = i0 + l;
-                        const int di = __builtin_amdgcn_readlane(v_d, l);
-                        const double ai = readlane_f64(v_a, l), si = readlane_f64(v_s, l);
-                        const double x = entry(row, dj);
-                        const double add = (di == dj) ? si : x * ai;
-                        Sj += (inj && i < j) ? add : 0.0;
-                        row_of(row, __builtin_amdgcn_readlane(v_d4, l));      // this buffer's next turn: the death four ahead
-                    };
-                    for (int l = 0; l < n; l += 4) {
-                        step(l, rA);
-                        if (l + 1 < n) step(l + 1, rB);
-                        if (l + 2 < n) step(l + 2, rC);
-                        if (l + 3 < n) step(l + 3, rD);
-                    }
-                }
-                if (inj) {
-                    const double Yd = cstZX0[dj] + cstKZX[dj] * Sj;             // <Z X_d> / F_d in front of death j
-                    z2 += 2.0 * (Yd * T1[j] * cstK2A[dj] + T3[j] * k2b);        // <Z^2> += 2 <Z X_d> c1 k2a + 2 <X_d^2> L^2 / ((n+1)(n+2)) k2b   (<Z X_d> c1 = Y_d F_d c1 = Y_d a_j)
-                }
-            }
-            // <Z X_q> when the pass is over, every cluster (lane = cluster: the row's entries are where they are needed): Y_q F_q
-            double zxq[J];
-#pragma unroll
-            for (int jj = 0; jj < J; ++jj) zxq[jj] = 0.0;
-            if (wv == CLP_NT / 64 - 1) {
-                double rA[J], rB[J], rC[J], rD[J];
-                auto cl_at = [&](int i) -> int { return (int)(cdca[i < Kc ? i : Kc - 1] & 255u); };
-                row_of(rA, cl_at(0)); row_of(rB, cl_at(1)); row_of(rC, cl_at(2)); row_of(rD, cl_at(3));
-                for (int i0 = 0; i0 < Kc; i0 += 64) {
-                    const int iq = i0 + lane < Kc ? i0 + lane : Kc - 1;
-                    const int v_d = (int)(cdca[iq] & 255u), v_d4 = cl_at(i0 + lane + 4); const double v_a = T1[iq], v_s = T2[iq];
-                    const int n = Kc - i0 < 64 ? Kc - i0 : 64;
-                    auto step = [&](int l, double (&row)[J]) __attribute__((always_inline)) {
-                        const int di = __builtin_amdgcn_readlane(v_d, l);
-                        const double ai = readlane_f64(v_a, l), si = readlane_f64(v_s, l);
-#pragma unroll
-                        for (int jj = 0; jj < J; ++jj) zxq[jj] += (lane + 64 * jj == di) ? si : row[jj] * ai;
-                        row_of(row, __builtin_amdgcn_readlane(v_d4, l));
-                    };
-                    for (int l = 0; l < n; l += 4) {
-                        step(l, rA);
-                        if (l + 1 < n) step(l + 1, rB);
-                        if (l + 2 < n) step(l + 2, rC);
-                        if (l + 3 < n) step(l + 3, rD);
-                    }
-                }
-            }
-            {   // block sum of z2
-#pragma unroll
-                for (int dd = 32; dd > 0; dd >>= 1) z2 += __shfl_xor(z2, dd);
-                if (lane == 0) ((double *)pa_scan)[wv] = z2;
-            }
-            __syncthreads();
-            if (wv == CLP_NT / 64 - 1) {
-#pragma unroll
-                for (int jj = 0; jj < J; ++jj) {
-                    const int q = lane + 64 * jj;
-                    if (q < nc) { const double Yq = cstZX0[q] + cstKZX[q] * zxq[jj]; cstZX0[q] = Yq * cstF[q]; }      // (linear, about rZX[q]: written back behind the barrier below; the pair sums have read cstZX0)
-                }
-            }
-            if (tid == 0) {
-                double tot = 0.0;
-                for (int q = 0; q < CLP_NT / 64; ++q) tot += ((double *)pa_scan)[q];
-                out_d[1] = cl_log(rZ2, exp(logZ20 - rZ2) + tot, S.logzero);
-            }
-            // more_samples_needed (nested_sampling.F90:514-543) behind every death: the live sum by a prefix sum over what the deaths and additions moved it by
-            if (wv == 1) {
-                double acc0 = 0.0;
-                { double b = 0.0; for (int q = lane; q < nc; q += 64) { const int n = clN0[q]; b += n > 0 ? (S.lse_sum[q] * srcp[n]) * exp(S.logXp[q] - lxm0) * exp(S.lse_ref[q] - R0) : 0.0; } acc0 = wave_sum<4>(b); }
-                const double E0 = exp(S.log_prec + rZ - lxm0 - R0);
-                const bool use_prec = S.use_prec != 0;
-                int stop_w = -2;
-                if (use_prec && (!(acc0 > 0.0) || acc0 < exp(logZ0 - rZ) * E0)) stop_w = T - 1;
-                double carry = acc0;
-                for (int j0 = 0; j0 < Kc && stop_w == -2; j0 += 64) {
-                    const int j = j0 + lane; const int wj = j < Kc ? T - 1 - (int)stepOf[j] : 0;
-                    double v = j < Kc ? sEvt[wj].eL + sCand[sCh[wj].rank & 0xFFFF].L : 0.0;
-#pragma unroll
-                    for (int dd = 1; dd < 64; dd <<= 1) { const double o = __shfl_up(v, dd); if (lane >= dd) v += o; }
-                    const double acc = carry + v;
-                    const bool hit = j < Kc && use_prec && (!(acc > 0.0) || acc < sHead[wj].zl * E0);
-                    const unsigned long long hm = __ballot(hit);
-                    if (hm) stop_w = __builtin_amdgcn_readlane(wj, __ffsll((long long)hm) - 1) - 1;
-                    carry = readlane_f64(acc, 63);
-                }
-                if (lane == 0 && stop_w != -2) cl_lst(&lp_stop, stop_w);
-            }
-            if (wv == 2) {
-                double b = 0.0;
-                for (int q = lane; q < nc; q += 64) b += termF[q];
-                const double acc = wave_sum<4>(b);
-                if (lane == 0) { const double v = acc > 0.0 ? log(acc) + lxm0 + R0 : S.logzero; out_d[3] = (v > S.logzero + 800.0) ? v : pc_logaddexp(S.logzero, v); }
-            }
-            __syncthreads();
-        }
-    }
     // ------------------------------------------------------------------ phase C: update_evidence, the live evidence, the lists (waves 1, 2, 3 of k_consume_cl)
     auto cl_wait = [&](int w) -> bool { return lp_prog <= w; };       // (every decision is in place: a chain is either consumed or not)
 #define CL_MEET() \
@@ -1141,10 +834,6 @@
             }
             for (int q = lane; q < nc; q += 64) { S.cl_n[q] = clN0[q] + clAdd[q]; S.death_thr[q] = clThr[q]; }
         }
-    } else if (wv == 1 && parC) {
-        CL_MEET();
-    } else if (wv == 2 && parC) {
-        CL_MEET();
     } else if (wv == 1) {
         // ================================================================ wave 1: update_evidence
         const double logZ0 = ctl->logZ, logZ20 = ctl->logZ2;
@@ -1442,18 +1131,6 @@
 #undef CL_MEET
     __syncthreads();
     CLP_MARK(5);
-    if (parC) {
-        // what phase C' holds per cluster: thread c the evidence side, thread CL_MAXC + c the live sum's
-        double zx_end = 0.0, rzx = 0.0;
-        if (tid < nc) { zx_end = cstZX0[tid]; rzx = fmax(S.logZXp[tid], 2.0 * lxm0 + Lhi); }
-        __syncthreads();                                            // (the per-cluster constants have been read: their LDS is the own-accumulator records' again)
-        if (tid < nc) {
-            S.logXp[tid] = pc_Xp; S.logZXp[tid] = cl_log(rzx, zx_end, S.logzero); Fbuf[tid] = pc_Flog; Gbuf[tid] = pc_Glog;
-        }
-        if (tid < CL_MAXC) sOwn[tid] = own_keep;
-        if (tid >= CL_MAXC && tid < CL_MAXC + nc) { S.lse_ref[tid - CL_MAXC] = pc_lref; S.lse_sum[tid - CL_MAXC] = pc_lsum; }
-        __syncthreads();
-    }
     // ------------------------------------------------------------------ write back (all waves)
     int status = out_i[0];
     const int i_nursery = out_i[2], need_drop = out_i[7], seg_hi = out_i[8], hard_end = out_i[12];

@@ -1058,7 +1058,7 @@ struct Engine {
     }
 
     // ---- waiting for the device.  A run on its own synchronises its stream; a run in step, inside a fiber, yields to the driver,
-    //      which launches what all runs have written down, waits once for all of them and resumes them (pc_run_cohort)
+    //      which launches what all runs have written down, waits once for all of them and resumes them (pc_run_many)
     void sync_point()
     {
         if (fib) {
@@ -1180,7 +1180,7 @@ struct Engine {
         const int hi_before = c.i_nursery > 0 ? c.i_nursery - 1 : B - 1;       // the segment starts where the last one stopped
         c.status = (int)(got[0] & 0xFF); c.error = (int)((got[0] >> 8) & 0xFF); c.cluster_deleted = (int)((got[0] >> 16) & 1);
         c.upd_pending = (int)((got[0] >> 17) & 1); c.upd_marks = (int)((got[0] >> 18) & 0x3FFF);
-        c.i_nursery = (int)((unsigned)got[1] & 0xFFFFu); c.upd_in = (int)(((unsigned)got[1] >> 16) & 0xFFFFu); c.ndead = (int)(unsigned)got[2]; c.nphantom = (int)(unsigned)got[3];
+        c.i_nursery = (int)((unsigned)got[1] & 0xFFFFu); c.ndead = (int)(unsigned)got[2]; c.nphantom = (int)(unsigned)got[3];
         c.ncluster = (int)(got[4] & 0xFFFF);
         {   // the low 16 bits of a counter that only grows
             int cand = (c.ncluster_dead & ~0xFFFF) | (int)((got[4] >> 16) & 0xFFFF);
@@ -1242,7 +1242,6 @@ struct Engine {
     double *babies_own = nullptr;
     // the phantom array is full: the phantoms that are still wanted move to the front of the alternate buffers.  In step with other
     // runs the clean is launched for all of them at once and waited for once (compact_wanted / compact_record / compact_finish)
-    bool compact_worth_it() const { return S.pool && h_ctl->status == PC_ST_RUNNING && h_ctl->i_nursery == 0 && 2 * pool_cursor > (long long)S.Pcap; }      // (next to a run that has to: pc_run_cohort)
     bool compact_wanted() const { return S.pool && h_ctl->status == PC_ST_RUNNING && h_ctl->i_nursery == 0 && pool_cursor + (long long)B * S.nr > S.Pcap; }
     void compact_record() { co->rec(CK_COMPACT, S, {keep, blk, d_total, ph2, phL2, phC2, phU2}, {}, {0, (int)pool_cursor, ((int)pool_cursor + 255) / 256}); }
     void compact_finish(int total)
@@ -2343,17 +2342,15 @@ struct Engine {
         return -1;
     }
 
-    // The sampling of one nursery: pool rows, the bases (drawn ahead on the side stream, or now), k_slice, the bases of the
-    // nurseries to come.  spec: enqueued BEHIND the previous nursery's contraction before the host has seen its outcome; the
-    // kernel starts by asking the device whether that nursery was consumed whole with neither an update nor the end of the
-    // run in its way (PcCtl::spec_ok, left by k_consume_par) and returns at once if not.
     // what the cohort's launches for any device likelihood take (else the run launches for itself in between)
     bool cohort_general_ok() const
     {
         static const bool off = std::getenv("PC_COHORT_GENERAL") && std::atoi(std::getenv("PC_COHORT_GENERAL")) == 0;
         return !off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK;
     }
-    bool enqueue_nursery(bool spec)
+    // The sampling of one nursery: pool rows, the bases (drawn ahead on the side stream, or now), k_slice, the bases of the
+    // nurseries to come.
+    bool enqueue_nursery()
     {
         unsigned &batch = r_batch; int &nursery_left = r_nursery_left;
         if (S.pool) {
@@ -2364,7 +2361,7 @@ struct Engine {
         {
             // (between the stamp of the last round and the launch of k_slice the device idles: nothing that can wait
             //  is done in between -- capacity checks precede the contraction, not the sampling)
-            hipEvent_t e0 = spec ? nullptr : kt.begin(KT_NHATS);
+            hipEvent_t e0 = kt.begin(KT_NHATS);
             // (a run that has the chip to itself: next to other runs the side stream takes from them what it gives)
             // (next to other runs of this device the bases are drawn in line, in front of the sampling kernel: their side streams
             //  would take from each other what they give -- but the split itself, and with it the fused sampling kernel, stays)
@@ -2392,18 +2389,17 @@ struct Engine {
             else if (co && !callback_mode && cohort_general_ok() && S.D >= 25 && S.D <= 64) co->rec(CK_NHATS_G, S, {}, {(long long)B}, {(int)batch});
             else if ((co ? (co->flush(), 0) : 0) || pc_launch_nhats(&S, batch, B, st)) { std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false; }
             kt.end(KT_NHATS, e0);
-            hipEvent_t e1 = spec ? nullptr : kt.begin(KT_SLICE);
-            S.spec_guard = spec ? 1 : 0;                                         // (the kernel looks at the contraction's verdict first)
+            hipEvent_t e1 = kt.begin(KT_SLICE);
             if (callback_mode) { if (co) co->flush(); slice_callback(batch); if (stop.load(std::memory_order_relaxed)) { r_rc = 5; return false; } }
             // next to other runs of this device (or settings.ablate bit 6): the lane = chain kernel (pc_slice_t.hip), the same
             // numbers from 1/60 of the wavefronts
-            else if (fused_slice && !spec && (multi || (cfg.ablate & 64)) && pc_slice_t_ok(&S, h_ctl->ncluster)) {
+            else if (fused_slice && (multi || (cfg.ablate & 64)) && pc_slice_t_ok(&S, h_ctl->ncluster)) {
                 path[PCHIP_PATH_SLICE_LANE]++;
                 if (co) co->rec(CK_SLICE, S, {}, {(long long)B}, {(int)batch, 0, 0, bases_seq}); else (void)pc_launch_slice_t(&S, batch, B, st);
-                // in step with other runs: the bases of the next nurseries on the runs' second stream, next to this round's kernels
+                // in step with other runs: the bases of the next nursery on the runs' second stream, next to this round's kernels
                 if (co && co->st2 && splittable && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
             }
-            else if (co && !callback_mode && !spec && cohort_general_ok() && (fused_slice || !splittable)) {
+            else if (co && !callback_mode && cohort_general_ok() && (fused_slice || !splittable)) {
                 // in step with other runs, any device likelihood / several clusters: the one-run kernel with the run in the grid
                 path[PCHIP_PATH_SLICE_WAVE]++;
                 if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
@@ -2414,9 +2410,8 @@ struct Engine {
                 if (pc_rtc_wanted(&S) && pc_rtc_error()) { std::fprintf(stderr, "polychord_hip: %s\n", pc_rtc_error()); r_rc = 1; return false; }
                 std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false;
             }
-            S.spec_guard = 0;
             kt.end(KT_SLICE, e1);
-            if (split && !spec) side_prefetch(batch);      // (speculative: only once the device is known to have taken the nursery)
+            if (split) side_prefetch(batch);
             if (S.ngrade > 1) HIPCHK(hipMemcpyAsync(h_nlike_g.data(), S.ch_nlike_g, sizeof(int) * h_nlike_g.size(), hipMemcpyDeviceToHost, st));
             batch++; tm.batches++;
             S.nn_valid = 0; nursery_left = B;
@@ -2424,22 +2419,16 @@ struct Engine {
         return true;
     }
 
-    // in step with other runs: the bases of the nurseries after `cur` that are not drawn yet (two ahead with a ring of three) written down for
-    // the cohort's second stream
+    // in step with other runs: the bases of the nursery after `cur`, if they are not drawn yet, written down for the cohort's second
+    // stream (one ahead: two ahead were slower in step, CHANGELOG.md)
     void bases_ahead(unsigned cur)
     {
-        // (two ahead -- PC_COHORT_AHEAD=2 -- takes the wait for the bases out of a round without an update, but the bases kernels then run
-        //  next to k_slice_t: in a process of the engine's own sixteen runs take as long as with one ahead and 32 / 64 runs 2 % less, in
-        //  bench.py's process (the HIP runtime PyTorch brings) 8-10 % MORE: one ahead)
-        static const unsigned ahead_env = std::getenv("PC_COHORT_AHEAD") ? (unsigned)std::max(1, std::min(2, std::atoi(std::getenv("PC_COHORT_AHEAD")))) : 1u;
-        const unsigned ahead = raw_depth >= 3 ? ahead_env : 1u;
-        for (unsigned x = cur + 1; x <= cur + ahead; ++x) {
-            RawSlot &rn = ring[x % raw_depth];
-            if (rn.valid && rn.batch == x && rn.B == B) continue;
-            PcState S1 = S; S1.nhat_raw = raw_buf[x % raw_depth];
-            co->rec(CK_BASES_NEXT, S1, {}, {(long long)B}, {(int)x});
-            rn.valid = true; rn.batch = x; rn.B = B; rn.waited = true; rn.co_seq = co->seq_for_next();
-        }
+        const unsigned x = cur + 1;
+        RawSlot &rn = ring[x % raw_depth];
+        if (rn.valid && rn.batch == x && rn.B == B) return;
+        PcState S1 = S; S1.nhat_raw = raw_buf[x % raw_depth];
+        co->rec(CK_BASES_NEXT, S1, {}, {(long long)B}, {(int)x});
+        rn.valid = true; rn.batch = x; rn.B = B; rn.waited = true; rn.co_seq = co->seq_for_next();
     }
 
     void ensure_side()
@@ -2500,34 +2489,18 @@ struct Engine {
     }
     }
 
-    // a speculative nursery the device declined: the host's bookkeeping of it is taken back (its bases stay where they are,
-    // drawn and waited for: the real launch finds them)
-    bool spec_pending = false, spec_hit = false;
-    long spec_tried = 0, spec_declined = 0;
-    int spec_upd_in = 0; double spec_lived = 0.0;      // lived deaths until the next update after the round just seen; lived deaths a nursery yields (estimate)
-    void spec_undo()
-    {
-        r_batch--; tm.batches--;
-        if (S.pool) pool_cursor -= (long long)B * S.nr;
-        RawSlot &rs = ring[r_batch % raw_depth];
-        rs.valid = true; rs.batch = r_batch; rs.B = B; rs.waited = true;
-    }
-
     // enqueue one round (sampling when the nursery is empty, contraction, row copies); false: the loop is over (r_rc says how)
     bool round_enqueue()
     {
         unsigned &batch = r_batch; bool &sort_valid = r_sort_valid; int &nursery_left = r_nursery_left;
         const bool par_ok = r_par_ok, static_ok = r_static_ok; const int wide = 0;
         {
-            if (h_ctl->status == PC_ST_DONE) { if (spec_pending) { spec_pending = false; spec_undo(); } return false; }
+            if (h_ctl->status == PC_ST_DONE) return false;
             if (h_ctl->status == PC_ST_ERROR) { std::fprintf(stderr, "polychord_hip: device error %d\n", h_ctl->error); r_rc = 2; return false; }
             bool fresh_nursery = false;
             if (h_ctl->i_nursery == 0) {
                 fresh_nursery = true;
-                const bool have = spec_pending;                 // (still pending here = the device took it: round_finish undid the others)
-                spec_pending = false;
-                if (have) side_prefetch(batch - 1);
-                else { const auto n0 = std::chrono::steady_clock::now(); if (r_static_ok && cfg.force_general == 0 && !(cfg.ablate & 32)) presort_live(); const bool okn = enqueue_nursery(false); g_dbg_nursery_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - n0).count(); if (!okn) return false; }
+                const auto n0 = std::chrono::steady_clock::now(); if (r_static_ok && cfg.force_general == 0 && !(cfg.ablate & 32)) presort_live(); const bool okn = enqueue_nursery(); g_dbg_nursery_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - n0).count(); if (!okn) return false;
             }
             if (fresh_nursery) { const auto n0 = std::chrono::steady_clock::now(); ensure_capacity(); g_dbg_capacity_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - n0).count(); }
             hipEvent_t e2 = kt.begin(KT_CONSUME);
@@ -2591,31 +2564,6 @@ struct Engine {
             if (st_side) { RawSlot &rs = ring[batch % raw_depth]; if (rs.valid && rs.batch == batch && !rs.waited) { HIPCHK(hipStreamWaitEvent(st, rs.ready, 0)); rs.waited = true; } }
             r_fresh = fresh_nursery;
             ready_spins = 0;
-            // PC_SPEC=1 (experiment, off by default): the next nursery's sampling enqueued behind this round's kernels before the
-            // host knows how the round ends; k_slice asks the device first (PcCtl::spec_ok) and returns at once when an update or
-            // the end of the run is in the way.  48 of the 79 rounds of the metric configuration end with an empty nursery and no
-            // update, and in those the device goes from the row copies straight into k_slice -- but the run is no shorter for it
-            // (14.75 ms against 14.65, A/B in one call, identical results): the 31 declined launches and the second trip through
-            // the launch path cost what the 48 saved host round trips give.
-            // Round 4: the launch is enqueued ahead only when the update is far enough away.  The contraction reports how many deaths
-            // that enter the live set are left until the next trigger (PcCtl::upd_in, as the state stood after the LAST launch); a nursery
-            // yields at most spec_lived of them (a running estimate from the rounds seen so far, B before any was seen), so the sampling
-            // of the nursery after this one is enqueued now if this nursery AND a tenth more cannot reach the trigger.  A wrong guess
-            // costs a declined launch, never a result: the device's guard decides.  PC_SPEC=0: never; PC_SPEC=1: always (the experiment).
-            // Measured (round 4, metric configuration): 40 of 79 nurseries enqueued ahead, none declined -- and the run is no shorter
-            // (12.81 against 12.83 ms, three A/B pairs): the 13-18 us between the row copies and the next k_slice are the queue's, not the
-            // host's.  So: off unless asked for (PC_SPEC=2 = by the estimate).
-            static const int spec_mode = std::getenv("PC_SPEC") ? std::atoi(std::getenv("PC_SPEC")) : 0;
-            const bool spec_off = spec_mode == 0 || (spec_mode == 2 && !(spec_upd_in > 0 && (double)spec_upd_in > 1.1 * spec_lived + 8.0));
-            if (!spec_off && S.pool && par_ok && h_ctl->ncluster == 1 && !callback_mode && st_side && pc_slice_fusable(&S) != 0 &&
-                g_active_dev[dev & 63].load(std::memory_order_relaxed) == 1 &&
-                pool_cursor + (long long)B * S.nr <= S.Pcap && (long long)h_ctl->ndead + 2LL * B + S.Ncap + 16 <= S.Dcap) {
-                RawSlot &rs = ring[batch % raw_depth];
-                if (rs.valid && rs.batch == batch && rs.B == B && rs.waited) {
-                    if (!enqueue_nursery(true)) return false;
-                    spec_pending = true; spec_hit = false; spec_tried++;
-                }
-            }
         }
         return true;
     }
@@ -2632,26 +2580,12 @@ struct Engine {
     {
         unsigned &batch = r_batch; int &nursery_left = r_nursery_left; const bool fresh_nursery = r_fresh;
         (void)batch;
-        if (spec_pending) {
-            spec_hit = h_ctl->status == PC_ST_RUNNING && !h_ctl->upd_pending && h_ctl->i_nursery == 0 && h_ctl->error == 0;   // what the device's guard saw
-            if (!spec_hit) { spec_pending = false; spec_undo(); spec_declined++; }      // (before the update looks at the pool's cursor)
-        }
         {
             // A run whose last death exhausts a nursery AND triggers an update learns that it is over only from the next
             // launch (the kernels test more_samples_needed before a death, nested_sampling.F90:237): the nursery
             // generated in between was never touched and does not count.
             if (fresh_nursery && h_ctl->status == PC_ST_DONE && h_ctl->i_nursery == B) tm.batches--;
             nursery_left = h_ctl->i_nursery;
-            {   // what the contraction said about the next update (round_enqueue decides by it whether to enqueue ahead)
-                const int now = h_ctl->upd_in;
-                const bool updated = h_ctl->status == PC_ST_UPDATE || h_ctl->upd_pending;
-                if (spec_lived <= 0.0) spec_lived = (double)B;
-                if (!updated && fresh_nursery && h_ctl->i_nursery == 0 && spec_upd_in > now && now > 0) {
-                    const double lived = (double)(spec_upd_in - now);
-                    spec_lived = spec_lived >= (double)B ? lived : 0.75 * spec_lived + 0.25 * lived;
-                }
-                spec_upd_in = now;
-            }
             tally_grades();
             tm.rounds++;
             // dead rows leave for the host at every update (a copy per round, ~350 KB, next to the one-CU contraction cost it
@@ -2776,7 +2710,6 @@ struct Engine {
         for (int k = 0; k < KT_N; ++k) { out->k_time_s[k] = kt.total_ms[k] * 1e-3; out->k_launches[k] = kt.launches[k]; }
         // developer counters (PC_DEBUG=2|3|4); the feedback setting keeps the reference's meaning (feedback.f90)
         static const int dbg_lvl = std::getenv("PC_DEBUG") ? std::atoi(std::getenv("PC_DEBUG")) : 0;
-        if (dbg_lvl == 6) std::fprintf(stderr, "polychord_hip dbg spec: %ld nurseries enqueued ahead, %ld of them declined by the device (%ld rounds); a nursery yields ~%.0f lived deaths\n", spec_tried, spec_declined, tm.rounds, spec_lived);
         if (dbg_lvl >= 3) std::fprintf(stderr, "polychord_hip dbg general: term %lld identify %lld kill+add %lld tail %lld cycles; %lld chains identified from the candidate lists, %lld of them fell back to the full search\n", h_ctl->gen_cyc[0], h_ctl->gen_cyc[1], h_ctl->gen_cyc[2], h_ctl->gen_cyc[3], h_ctl->nn_walks, h_ctl->nn_fallbacks);
         if (dbg_lvl == 4) std::fprintf(stderr, "polychord_hip dbg par: stage+search %lld rank-sort %lld accept %lld merge+slots %lld evidence %lld triggers %lld publish %lld cycles\n", h_ctl->dbg[0], h_ctl->dbg[1], h_ctl->dbg[2], h_ctl->dbg[3], h_ctl->dbg[4], h_ctl->dbg[5], h_ctl->dbg[6]);
         if (dbg_lvl == 4) std::fprintf(stderr, "polychord_hip dbg par: %lld evidence scans as pairs (terms beyond one scale)\n", h_ctl->dbg[7]);
@@ -2992,17 +2925,11 @@ int pchip_run_hooks(const pchip_settings *s, const pchip_like *like, const pchip
     return rc;
 }
 
-// Several runs of one problem on ONE device, driven by the calling thread: every run is an engine of its own (own stream, own
-// state), and the thread goes round them -- enqueue a round, look whether a stamp has arrived, finish that round, enqueue the
-// next -- so that the kernels of up to `max_in_flight` runs are in the device's queues at any time.  (One host thread per
-// run, as before, spent its time in the HIP runtime's locks: 533 launches per run from sixteen threads at once gave 1.5 x the
-// throughput of one run; a single run keeps one wavefront per SIMD busy and the contraction kernel one CU.)
+// The runs of `seeds` on `device`, driven by the calling thread, up to max_in_flight of them in step on one stream (Cohort): every
+// phase of the round is gone through for all of them before anything is launched, then each kernel of the phase once for all.
 // Built-in device likelihoods only: a host callback belongs to its caller's thread.  Returns 0 or the first failing run's code.
-// The runs of `seeds` on `device`, up to max_in_flight of them in step on one stream (Cohort): every phase of the round is gone
-// through for all of them before anything is launched, then each kernel of the phase once for all.  PC_COHORT=0: the older
-// scheduler below (one stream per run, kernels launched run by run).
-static int pc_run_cohort(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds, int device,
-                         int max_in_flight, pchip_result *results)
+int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds, int device,
+                int max_in_flight, pchip_result *results)
 {
     static const bool prof = std::getenv("PC_DEBUG") && std::atoi(std::getenv("PC_DEBUG")) == 5;
     for (int k = 0; k < nseeds; ++k) std::memset(&results[k], 0, sizeof(pchip_result));
@@ -3015,13 +2942,8 @@ static int pc_run_cohort(const pchip_settings *s, const pchip_like *like, const 
     for (int base = 0; base < nseeds && !worst; base += done_here) {
         int n = std::min(W, nseeds - base);
         const auto Tpre = std::chrono::steady_clock::now();
-        Cohort co; bool own_streams = false;
+        Cohort co;
         static const bool side_off = std::getenv("PC_COHORT_SIDE") && std::atoi(std::getenv("PC_COHORT_SIDE")) == 0;
-        static const bool prio_off = !(std::getenv("PC_COHORT_PRIO") && std::atoi(std::getenv("PC_COHORT_PRIO")) == 1);      // (tried: 79 ms against 70 for sixteen runs -- off)
-        // (the round's own kernels first, the bases of the next round in what they leave: stream priorities)
-        int plo = 0, phi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&plo, &phi);      // (least, greatest: numerically lower = more urgent)
-        const auto Tp1 = std::chrono::steady_clock::now();
         // (a main stream whose hardware queue is known already, if the pool has one: the side stream is then picked without a test --
         //  a test is a millisecond, several once PyTorch lives in the process, and the pool's first stream was a different one of
         //  the engines' copy streams at every call)
@@ -3032,7 +2954,7 @@ static int pc_run_cohort(const pchip_settings *s, const pchip_like *like, const 
         int cls_main = -1, cls_side = -1;
         bool cohort_loaded = false;
         CohortLease lease(devq);
-        if (prio_off || plo == phi) {
+        {
             hipStream_t want, want2;
             { std::lock_guard<std::mutex> g(last_m); want = last_st[devq]; want2 = last_st2[devq]; }
             std::lock_guard<std::mutex> gq(cstreams().m);             // (one group at a time picks: what it takes the next one avoids)
@@ -3044,7 +2966,7 @@ static int pc_run_cohort(const pchip_settings *s, const pchip_like *like, const 
             if (want) co.st = hpool().take_stream_if([&](hipStream_t x) { return x == want && (busy.empty() || free_cls(x)); });
             if (!co.st) co.st = hpool().take_stream_if([&](hipStream_t x) { return busy.empty() ? sclasses().known(x) >= 0 : free_cls(x); });
             if (!co.st) co.st = busy.empty() ? hpool().get_stream() : stream_avoiding(busy, loaded);
-            const auto Tp2 = std::chrono::steady_clock::now();
+            const auto Tp1 = std::chrono::steady_clock::now();
             if (!busy.empty() || !side_off) cls_main = loaded ? sclasses().known(co.st) : sclasses().classify(co.st);
             if (!side_off) {
                 if (cls_main >= 0) busy.push_back(cls_main);
@@ -3055,11 +2977,11 @@ static int pc_run_cohort(const pchip_settings *s, const pchip_like *like, const 
             cohort_loaded = loaded;
             cstreams().take(devq, cls_main, true); cstreams().take(devq, cls_side); lease.hold(cls_main, cls_side);
             { std::lock_guard<std::mutex> g(last_m); last_st[devq] = co.st; last_st2[devq] = co.st2; }
-            if (prof) std::fprintf(stderr, "polychord_hip dbg cohort: priority range %.2f ms, main stream %.2f ms, side stream %.2f ms\n", std::chrono::duration<double>(Tp1 - Tpre).count() * 1e3, std::chrono::duration<double>(Tp2 - Tp1).count() * 1e3, std::chrono::duration<double>(std::chrono::steady_clock::now() - Tp2).count() * 1e3); }
-        else { HIPCHK(hipStreamCreateWithPriority(&co.st, hipStreamNonBlocking, phi)); if (!side_off) HIPCHK(hipStreamCreateWithPriority(&co.st2, hipStreamNonBlocking, plo)); own_streams = true; }
+            if (prof) std::fprintf(stderr, "polychord_hip dbg cohort: main stream %.2f ms, side stream %.2f ms\n", std::chrono::duration<double>(Tp1 - Tpre).count() * 1e3, std::chrono::duration<double>(std::chrono::steady_clock::now() - Tp1).count() * 1e3);
+        }
         if (co.st2) { co.ev_up = hpool().get_sync_event(); co.ev_next = hpool().get_sync_event(); }
         static const bool stc_off = std::getenv("PC_COHORT_COPY_STREAMS") && std::atoi(std::getenv("PC_COHORT_COPY_STREAMS")) == 0;
-        if (!stc_off && !own_streams) { co.stc[0] = stream_beside({co.st, co.st2}, cohort_loaded); co.stc[1] = stream_beside({co.st, co.st2, co.stc[0]}, cohort_loaded); }
+        if (!stc_off) { co.stc[0] = stream_beside({co.st, co.st2}, cohort_loaded); co.stc[1] = stream_beside({co.st, co.st2, co.stc[0]}, cohort_loaded); }
         std::vector<Engine *> E((size_t)n, nullptr);
         std::vector<char> live((size_t)n, 0), enq((size_t)n, 0);
         const auto T0 = std::chrono::steady_clock::now();
@@ -3129,14 +3051,13 @@ static int pc_run_cohort(const pchip_settings *s, const pchip_like *like, const 
                     // that are more than half full along -- the runs fill theirs at slightly different rates, and a pass a round
                     // later is another wait of the whole cohort -- kept the passes at three a call, and changed the last bits of
                     // some runs: the update's partial sums are grouped by the array's extent, so a run must compact exactly
-                    // when it would alone.  tools/dev/fuzz_in_step.py found it; PC_COHORT_COMPACT_ALIGN=1 brings it back)
+                    // when it would alone.  tools/dev/fuzz_in_step.py found it)
                     int nc = 0;
                     for (int k = 0; k < n; ++k) if (live[k] && E[k]->compact_wanted()) nc++;
                     if (nc) {
                         const auto c0 = nowc();
-                        static const bool align_off = !(std::getenv("PC_COHORT_COMPACT_ALIGN") && std::atoi(std::getenv("PC_COHORT_COMPACT_ALIGN")) == 1);
                         std::vector<char> cmp((size_t)n, 0);
-                        for (int k = 0; k < n; ++k) if (live[k] && (E[k]->compact_wanted() || (!align_off && E[k]->compact_worth_it()))) { cmp[k] = 1; E[k]->compact_record(); }
+                        for (int k = 0; k < n; ++k) if (live[k] && E[k]->compact_wanted()) { cmp[k] = 1; E[k]->compact_record(); }
                         co.flush();
                         if ((size_t)n > totals_cap) { if (h_totals) hfree(h_totals); h_totals = halloc<int>((size_t)n); totals_cap = (size_t)n; }
                         for (int k = 0; k < n; ++k) if (cmp[k]) HIPCHK(hipMemcpyAsync(&h_totals[k], E[k]->d_total, sizeof(int), hipMemcpyDeviceToHost, co.st));
@@ -3285,72 +3206,11 @@ static int pc_run_cohort(const pchip_settings *s, const pchip_like *like, const 
         if (h_totals) hfree(h_totals);
         (void)hipStreamSynchronize(co.st);
         lease.release();
-        if (own_streams) (void)hipStreamDestroy(co.st); else hpool().put_stream(co.st);
-        if (co.st2) { (void)hipStreamSynchronize(co.st2); if (own_streams) (void)hipStreamDestroy(co.st2); else hpool().put_stream(co.st2); hpool().put_sync_event(co.ev_up); hpool().put_sync_event(co.ev_next); }
+        hpool().put_stream(co.st);
+        if (co.st2) { (void)hipStreamSynchronize(co.st2); hpool().put_stream(co.st2); hpool().put_sync_event(co.ev_up); hpool().put_sync_event(co.ev_next); }
         for (int q = 0; q < 2; ++q) if (co.stc[q]) { (void)hipStreamSynchronize(co.stc[q]); hpool().put_stream(co.stc[q]); co.stc[q] = nullptr; }
         done_here = n;
     }
-    return worst;
-}
-
-int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds, int device,
-                int max_in_flight, pchip_result *results)
-{
-    {
-        static const bool cohort_off = std::getenv("PC_COHORT") && std::atoi(std::getenv("PC_COHORT")) == 0;
-        if (!cohort_off) return pc_run_cohort(s, like, prior, nseeds, seeds, device, max_in_flight, results);
-    }
-    struct Job { Engine *E = nullptr; int k = -1; bool waiting = false; };
-    std::vector<Job> jobs((size_t)std::max(1, std::min(max_in_flight, nseeds)));
-    int next = 0, active = 0, worst = 0;
-    for (int k = 0; k < nseeds; ++k) std::memset(&results[k], 0, sizeof(pchip_result));
-    auto finish = [&](Job &j, int rc) {
-        if (rc != 0) { pchip_result_free(&results[j.k]); if (!worst) worst = rc; }
-        j.E->destroy(); delete j.E; j.E = nullptr; j.waiting = false; active--;
-    };
-    // one step of a job; exceptions of the engine end that job only
-    auto guarded = [&](Job &j, auto &&fn) {
-        try { fn(); }
-        catch (const EngineError &e) { std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str()); (void)hipGetLastError(); finish(j, e.code); }
-        catch (const std::bad_alloc &) { std::fprintf(stderr, "polychord_hip: out of host memory\n"); finish(j, PC_RC_MEMORY); }
-    };
-    static const bool prof = std::getenv("PC_DEBUG") && std::atoi(std::getenv("PC_DEBUG")) == 5;
-    double t_begin = 0, t_enq = 0, t_fin = 0, t_end = 0; long n_enq = 0, n_poll = 0;
-    const auto T0 = std::chrono::steady_clock::now();
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    while (next < nseeds || active > 0) {
-        for (Job &j : jobs) {
-            if (!j.E) {
-                if (next >= nseeds || worst) continue;
-                j.k = next++; j.E = new Engine; active++;
-                guarded(j, [&] {
-                    pchip_settings c = *s; c.seed = seeds[j.k]; c.device = device;
-                    j.E->setup(c, *like, *prior);
-                    const auto a0 = now();
-                    const int rc = j.E->begin();
-                    t_begin += secs(a0, now());
-                    if (rc >= 0) { finish(j, rc ? rc : PC_RC_DEVICE); return; }
-                    if (!j.E->round_enqueue()) { const int r = j.E->r_rc ? j.E->r_rc : j.E->end(&results[j.k]); finish(j, r); return; }
-                    j.waiting = true;
-                });
-            } else if (j.waiting) {
-                guarded(j, [&] {
-                    n_poll++;
-                    if (!j.E->round_ready()) return;
-                    const auto a0 = now();
-                    const bool go = j.E->round_finish();
-                    const auto a1 = now(); t_fin += secs(a0, a1);
-                    const bool go2 = go && j.E->round_enqueue();
-                    const auto a2 = now(); t_enq += secs(a1, a2); n_enq++;
-                    if (!go2) { const int r = j.E->r_rc ? j.E->r_rc : j.E->end(&results[j.k]); t_end += secs(a2, now()); finish(j, r); }
-                });
-            }
-        }
-        if (worst && active == 0) break;
-    }
-    if (prof) std::fprintf(stderr, "polychord_hip dbg many: %d runs, wall %.2f ms; begin %.2f, finish(+updates) %.2f, enqueue %.2f (%ld rounds), end %.2f ms; %ld polls\n",
-                           nseeds, secs(T0, now()) * 1e3, t_begin * 1e3, t_fin * 1e3, t_enq * 1e3, n_enq, t_end * 1e3, n_poll);
     return worst;
 }
 

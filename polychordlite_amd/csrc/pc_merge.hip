@@ -786,7 +786,7 @@ int pchip_run_repeats_ex(const pchip_settings *s, const pchip_like *like, const 
     const int per_dev = std::max(1, max_in_flight);
     std::atomic<int> next{0}, worst{0};
     const auto t0 = clk::now();
-    const bool device_like = like->kind != PCHIP_LIKE_CALLBACK && prior->kind == 1 && !std::getenv("PC_REPEATS_THREADS");
+    const bool device_like = like->kind != PCHIP_LIKE_CALLBACK && prior->kind == 1;
     // (the runs leave their lived records on the device for the merge below: no second trip over the host link)
     pchip_settings s_loc = *s;
     // (set here, freed here: a caller that did not ask for the device block must not find its results pinning ndead x (nTotal + 2) doubles

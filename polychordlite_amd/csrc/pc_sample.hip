@@ -1445,7 +1445,7 @@ extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchai
     static const bool helper_off = std::getenv("PC_SLICE_HELPER_OFF") != nullptr;
     const size_t pw4 = ((size_t)D + S->nr + ((phi_lds || lean) ? (size_t)S->nr * (D + 1) : 0) + (size_t)FWv * D + (size_t)S->nr * (D + 2) + (size_t)((S->nr + 3) / 4) * 128 + (size_t)S->nr + 1) & ~(size_t)1;
     const size_t sh4 = 4 * sizeof(double) * pw4 + 16;
-    const bool help = !helper_off && !(S->ablate & 8192) && S->nr <= 64 && (nchains & 3) == 0 && sh4 <= 150 * 1024 && !S->spec_guard;
+    const bool help = !helper_off && !(S->ablate & 8192) && S->nr <= 64 && (nchains & 3) == 0 && sh4 <= 150 * 1024;
 #define PC_SLICE_FUSED_L(NROWS, FW, LN) { \
         if ((LN == 3 || LN == 5) && help) { \
         if (sh4 > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 4, FW, LN>, sh4); \

@@ -47,8 +47,6 @@ struct PcCtl {                   // written by the consume kernel, read by the h
     int upd_keep_thr, upd_pad;          // deaths after the mark: death_thr stays the last death's logL
     double upd_thr;                     // logL of the death that triggered the mark (clean_phantoms' threshold)
     int chol_suspect, chol_pad;         // the blocked factorisation met a pivot it does not trust: the reference-order kernel behind it decides
-    int spec_ok, upd_in;                // upd_in: lived deaths until the next update trigger, as the state stands after this launch (0 = not known); spec_ok: parallel contraction: number of the nursery that may be sampled at once (this one was consumed whole, no
-                                        // update is due, the run goes on), or -1: what a speculatively enqueued k_slice asks first
     long long wave_cyc[4];              // developer counters of k_consume_clp: cycles waves 1, 2, 3 spend in their loops over a pass's deaths, the phantom waves in theirs
 };
 
@@ -163,12 +161,11 @@ struct PcState {
                                  // along the chord; bits 1 / 2 / 3 = no pool mode / no deferred update / no fused update (the same numbers
                                  // by the older kernels: tests/test_gpu_parity.py); bit 4 = the parallel contraction's evidence prefixes by pair
                                  // scans only (no linear-space path); bit 5 = several clusters: the general contraction kernel for every launch (not
-                                 // the one-wave kernel of pc_clus.hip); bit 30 = trace of Cholesky fallbacks
+                                 // the one-wave kernel of pc_clus.hip); bits 11, 12 = retired, no effect; bit 30 = trace of Cholesky fallbacks
     int seq_mode;                // tests: ONE running Philox stream consumed in the reference's program order
                                  // (B = 1 only; PcCtl::seq is the position), cf. oracle `sequential` mode
     int epoch_discard;           // 1: nested_sampling.F90:313 as written (a change of the cluster list loses every chain in flight); 0: only the ended cluster's
     int seed_override;           // test hook: chain c starts from slot c instead of a random seed
-    int spec_guard;              // k_slice: enqueued ahead of the host's decision -- return unless ctl->spec_ok names this nursery
     PcCtl *ctl;
     // host notification: the contraction kernels copy the control block into a pinned, device-visible host mirror when
     // they are done and stamp it with notify_seq, so the host learns the outcome of a round by watching memory instead
@@ -249,7 +246,7 @@ __device__ __forceinline__ void pc_publish_ctl(const PcState &S)
         const PcCtl *c = S.ctl;
         pc_note_sh[0] = (unsigned)c->status | ((unsigned)c->error << 8) | ((unsigned)(c->cluster_deleted != 0) << 16) |
                         ((unsigned)(c->upd_pending != 0) << 17) | ((unsigned)(c->upd_marks > 0x3FFF ? 0x3FFF : c->upd_marks) << 18);   // (a launch consumes <= 1024 chains: <= 1024 marks)
-        pc_note_sh[1] = ((unsigned)c->i_nursery & 0xFFFFu) | ((unsigned)(c->upd_in < 0 ? 0 : (c->upd_in > 0xFFFF ? 0xFFFF : c->upd_in)) << 16);   // (a nursery holds <= 65535 chains: Engine::setup refuses a larger batch)
+        pc_note_sh[1] = (unsigned)c->i_nursery & 0xFFFFu;   // (a nursery holds <= 65535 chains: Engine::setup refuses a larger batch)
         pc_note_sh[2] = (unsigned)c->ndead; pc_note_sh[3] = (unsigned)c->nphantom;
         pc_note_sh[4] = (unsigned)c->ncluster | ((unsigned)(c->ncluster_dead & 0xFFFF) << 16);   // (ncluster <= 16384: Engine::grow_clusters; the full dead count comes with the block)
     }

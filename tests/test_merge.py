@@ -639,10 +639,10 @@ def test_runs_in_step_at_every_width(engine, D):
 
 
 @pytest.mark.gpu
-def test_bases_with_their_own_deviates_are_the_same_bases(engine):
-    """settings.ablate bit 12: runs in step whose Gram-Schmidt kernel makes its own deviates (k_bases_own: Philox and AS241 in the
-    registers the vectors live in, the tail arguments of a wavefront finished together) -- every run bit for bit the run it is alone,
-    whose bases come from k_nhats; nDims even and odd (an odd nDims puts every other vector on the second half of a Philox call)."""
+def test_bases_of_runs_in_step_are_the_bases_of_runs_alone(engine):
+    """runs in step, whose bases come from the deviates kernel and the Gram-Schmidt kernel behind it (k_deviates_t + k_bases_packed) --
+    every run bit for bit the run it is alone, whose bases come from k_nhats; nDims even and odd (an odd nDims puts every other vector
+    on the second half of a Philox call)."""
     from polychordlite_amd.repeats import run_repeats
     api = engine
     lib = api.load()
@@ -654,7 +654,7 @@ def test_bases_with_their_own_deviates_are_the_same_bases(engine):
             return s
         seeds = [700 + D + j for j in range(4)]
         singles = [api.run(settings(sd, 0), L, P) for sd in seeds]
-        merged, runs = run_repeats(settings(0, 4096), L, P, seeds, max_in_flight=len(seeds))
+        merged, runs = run_repeats(settings(0, 0), L, P, seeds, max_in_flight=len(seeds))
         for one, r in zip(singles, runs):
             assert r["path"]["slice_lane"] > 0 and one["path"]["slice_lane"] == 0
             for k in ("ndead", "nlike", "niter", "nupdates", "nbatches"):
