@@ -28,6 +28,7 @@ int main(int argc, char **argv)
     s.base_dir = argc > 1 ? argv[1] : "chains"; s.file_root = "cpp_device";
     polychord_hip_set_gaussian(0.5, 0.1);
     run_polychord(polychord_hip_gaussian, polychord_hip_uniform_prior, my_dumper, s);     // fused on the GPU
+    // (any of the reference's prior types the same way: polychord_hip_set_table_prior(nDims, entries, nullptr), then polychord_hip_table_prior)
     const int dumps_device = g_dumps;
     s.file_root = "cpp_host";
     run_polychord(my_gaussian, my_dumper, s);                                               // host callback, default prior

@@ -1,5 +1,6 @@
 !> Fortran driver in the style of src/drivers/polychord_examples.f90: the 20-D Gaussian of ini/gaussian.ini on the
 !! MI355X engine, once with the device likelihood and once with a likelihood written in Fortran (host callback).
+!! (Another prior type on the device: fill pchip_prior_entry(nDims), polychord_hip_set_table_prior, pass polychord_hip_table_prior.)
 program example_gaussian
     use iso_c_binding
     use polychord_hip

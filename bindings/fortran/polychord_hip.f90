@@ -14,7 +14,15 @@ module polychord_hip
     private
     public :: polychord_c_interface, polychord_hip_gaussian, polychord_hip_rastrigin, polychord_hip_twin_gaussian, &
               polychord_hip_uniform_prior, polychord_hip_set_gaussian, polychord_hip_set_uniform_prior, &
+              polychord_hip_table_prior, polychord_hip_set_table_prior, pchip_prior_entry, &
               polychord_hip_set_option, polychord_hip_set_sub_clustering, run_polychord_hip
+
+    !> one parameter of a prior table (pchip_prior_entry of polychord_hip.h): the reference's type number 1 .. 10 (priors.f90:5-15),
+    !! the prior block, the number of prior parameters and the parameters in the ini file's order
+    type, bind(c) :: pchip_prior_entry
+        integer(c_int) :: ptype, pblock, npar
+        real(c_double) :: par(3)
+    end type
 
     interface
         subroutine polychord_c_interface(loglike, prior, dumper, nlive, num_repeats, nprior, nfail, do_clustering, &
@@ -60,6 +68,21 @@ module polychord_hip
             real(c_double) :: cube(*), theta(*)
             integer(c_int), value :: nDims
         end subroutine
+        !> the reference's prior types as a table evaluated inside the sampling kernels (polychord_hip.h): pass it as `prior`
+        subroutine polychord_hip_table_prior(cube, theta, nDims) bind(c, name="polychord_hip_table_prior")
+            import :: c_double, c_int
+            real(c_double) :: cube(*), theta(*)
+            integer(c_int), value :: nDims
+        end subroutine
+        !> entries(nDims) in parameter order, hyper(nDims) = 0-based hypercube index of every parameter (c_null_ptr: identity);
+        !! 0, or non-zero with the message in polychord_hip_last_error()
+        function polychord_hip_set_table_prior(nDims, entries, hyper) result(rc) bind(c, name="polychord_hip_set_table_prior")
+            import :: c_int, c_ptr, pchip_prior_entry
+            integer(c_int), value :: nDims
+            type(pchip_prior_entry) :: entries(*)
+            type(c_ptr), value :: hyper
+            integer(c_int) :: rc
+        end function
         subroutine polychord_hip_set_gaussian(mu, sigma) bind(c, name="polychord_hip_set_gaussian")
             import :: c_double
             real(c_double), value :: mu, sigma

@@ -67,6 +67,24 @@ void polychord_hip_set_corr_gaussian(int nDims, const double *invcov_rowmajor, c
 /* uniform box prior evaluated on the device; pass polychord_hip_uniform_prior as `prior` */
 void polychord_hip_uniform_prior(double *cube, double *theta, int nDims);
 void polychord_hip_set_uniform_prior(int nDims, const double *lo, const double *hi);
+/* The reference's prior types as a table, evaluated INSIDE the sampling kernels when the likelihood is a device likelihood: one entry
+ * per PARAMETER -- the type number of priors.f90:5-15, the prior block, the prior parameters in the ini file's order -- and the
+ * hypercube index of every parameter (priors.f90:708-737; NULL = identity).  sorted_ blocks are consecutive parameters of one type
+ * and block (priors.f90:245-262).  The adaptive types (11-15) are not supported. */
+enum { PCHIP_PT_UNIFORM = 1, PCHIP_PT_LOG_UNIFORM = 2, PCHIP_PT_POWER_UNIFORM = 3, PCHIP_PT_GAUSSIAN = 4, PCHIP_PT_HALF_GAUSSIAN = 5,
+       PCHIP_PT_EXPONENTIAL = 6, PCHIP_PT_SORTED_UNIFORM = 7, PCHIP_PT_SORTED_GAUSSIAN = 8, PCHIP_PT_SORTED_HALF_GAUSSIAN = 9,
+       PCHIP_PT_SORTED_EXPONENTIAL = 10 };
+typedef struct {
+    int type;                      /* PCHIP_PT_* */
+    int block;                     /* prior block (the ini file's fifth column); only tells sorted_ blocks of one type apart */
+    int npar;                      /* prior parameters given (uniform, log_uniform, gaussian, half_gaussian: 2; exponential: 1; power_uniform: 3) */
+    double par[3];
+} pchip_prior_entry;
+/* polychord_hip_table_prior is a real host function (the maximiser, write_prior, tests and a reference-side caller evaluate it); passed
+ * as `prior` to polychord_c_interface with a built-in likelihood the engine recognises the pointer and evaluates the table on the
+ * device.  polychord_hip_set_table_prior checks the table: 0, or non-zero with the message in polychord_hip_last_error(). */
+void polychord_hip_table_prior(double *cube, double *theta, int nDims);
+int  polychord_hip_set_table_prior(int nDims, const pchip_prior_entry *entries, const int *hyper);
 /* Batched host evaluation.  In host-callback mode the engine parks the proposals of all chains of a nursery and hands them
  * to the host together; with a batch callback registered it makes ONE call per round instead of one loglikelihood call
  * per proposal: prior + likelihood for n hypercube points (row-major, host memory; logL[i] <= logzero marks an invalid
@@ -93,7 +111,8 @@ double polychord_hip_inv_normal_cdf(double p);
  * and so does this library by default -- returns to the caller instead, with the message kept for
  * polychord_hip_last_error(): what a language binding needs to raise an exception rather than lose its interpreter),
  * "inject_fault" (tests: the next run fails once -- 1: a device allocation, 2: cluster capacity at the next split,
- * 3: growth of the phantom array) */
+ * 3: growth of the phantom array), "device_prior" (default 1; 0: polychord_c_interface_ini and polychord_hip_table_prior evaluate
+ * their prior table on the host as before -- a built-in likelihood then runs as a host callback too) */
 void polychord_hip_set_option(const char *name, double value);
 /* sub-dimension clustering of the next polychord_c_interface calls (sticky, like the options above): n 0-based hypercube
  * indices (pchip_settings.sub_cluster_dims); n = 0 clears it.  polychord_c_interface_ini sets the ini file's markers for
@@ -185,10 +204,16 @@ typedef struct {
     int source;                    /* PCHIP_LIKE_SOURCE: handle from pchip_source_create (ABI 9) */
 } pchip_like;
 
+enum { PCHIP_PRIOR_CALLBACK = 0, PCHIP_PRIOR_BOX = 1, PCHIP_PRIOR_TABLE = 2 };
 typedef struct {
-    int kind;                      /* 0 callback, 1 uniform box */
+    int kind;                      /* PCHIP_PRIOR_*: 0 callback, 1 uniform box, 2 table */
     const double *lo, *hi;         /* host, D each; NULL => [0,1] */
     polychord_prior_fn fn;
+    /* kind == PCHIP_PRIOR_TABLE only (never read otherwise): nDims entries in parameter order, and the hypercube index of every
+       parameter (NULL = identity).  With a device likelihood the table is evaluated in the sampling kernels (PCHIP_PATH_DEVICE_PRIOR);
+       with a callback likelihood it serves as the host prior.  A table that is a box (all uniform, identity order) runs as kind 1. */
+    const pchip_prior_entry *table;
+    const int *hyper;
 } pchip_prior;
 
 typedef struct {
@@ -239,6 +264,7 @@ enum { PCHIP_PATH_CONSUME_PAR = 0,      /* one cluster: the parallel contraction
        PCHIP_PATH_SUBCLUSTER_PASSES = 17,   /* clustering passes on the sub-clustering coordinates (settings.n_sub_cluster > 0: one per update) */
        PCHIP_PATH_SUBCLUSTER_SPLITS = 18,   /* clusters those passes split */
        PCHIP_PATH_SOURCE_KERNELS = 19,      /* launches of run-time compiled sampling kernels (PCHIP_LIKE_SOURCE, settings.ablate bit 15) */
+       PCHIP_PATH_DEVICE_PRIOR = 20,        /* sampling launches (live points, nurseries) that evaluated a prior table on the device */
        PCHIP_PATH_COUNT = 24 };
 
 /* snapshot handed to the update hook: what the reference's file writers see at every update
@@ -283,6 +309,8 @@ typedef struct {
  * bindings rely on).  A binding that mirrors them (ctypes, ISO_C_BINDING, cgo ...) checks itself against the library it loaded:
  * pchip_abi_version() == PCHIP_ABI_VERSION of the header it was written against, and pchip_sizeof("settings" | "result" | "merged" |
  * "like" | "prior" | "update") == the size of its own mirror (0 for an unknown name). */
+/* (still 9 with pchip_prior's two trailing members and PCHIP_PRIOR_TABLE: they are read only when kind == 2, which no earlier caller
+ *  sets; pchip_sizeof("prior") tells a mirror of the older layout apart) */
 #define PCHIP_ABI_VERSION 9
 int  pchip_abi_version(void);
 /* A likelihood written as HIP device source, compiled at run time for the device a run is on and evaluated inside the sampling kernels
@@ -406,6 +434,10 @@ const char *pchip_comm_library(void);   /* the RCCL that was resolved (path or s
 int  pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior,
                         unsigned batch, int nchains, const double *seeds, const double *chol,
                         double contour, double *babies_out, double *nhats_out, int *nlike_out);
+/* kernel-level: the DEVICE transform of a prior table (prior->kind == PCHIP_PRIOR_TABLE) at n hypercube points, cube [n][nDims] in,
+ * theta [n][nDims] out (host memory) -- parity tests against polychord_hip_table_prior.  0, 1 (a bad table, message in
+ * polychord_hip_last_error()), 2 (no device), 3 (nDims > 256). */
+int  pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const double *cube, double *theta, int device);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,8 @@
 //     double loglike(double *theta, int nDims, double *phi, int nDerived);
 //     int main() { Settings s(20, 2); s.nlive = 2000; s.num_repeats = 40; s.write_stats = true; run_polychord(loglike, s); }
 //
-// Passing polychord_hip_gaussian / _rastrigin / _twin_gaussian / _corr_gaussian (and polychord_hip_uniform_prior) as the
+// Passing polychord_hip_gaussian / _rastrigin / _twin_gaussian / _corr_gaussian (and polychord_hip_uniform_prior, or
+// polychord_hip_table_prior after polychord_hip_set_table_prior: the reference's prior types, both declared in polychord_hip.h) as the
 // callbacks makes the engine evaluate them inside the sampling kernel.  There is no MPI in this engine: the MPI_Comm
 // overloads of the reference have no counterpart; one process drives one GPU.
 #pragma once

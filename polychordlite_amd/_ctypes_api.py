@@ -43,8 +43,21 @@ class Like(C.Structure):
                 ("source", C.c_int)]
 
 
+class PriorEntry(C.Structure):
+    """pchip_prior_entry: one parameter of a prior table (type number of PRIOR_TYPES, prior block, prior parameters)"""
+    _fields_ = [("type", C.c_int), ("block", C.c_int), ("npar", C.c_int), ("par", C.c_double * 3)]
+
+
 class Prior(C.Structure):
-    _fields_ = [("kind", C.c_int), ("lo", C.POINTER(C.c_double)), ("hi", C.POINTER(C.c_double)), ("fn", C.c_void_p)]
+    _fields_ = [("kind", C.c_int), ("lo", C.POINTER(C.c_double)), ("hi", C.POINTER(C.c_double)), ("fn", C.c_void_p),
+                ("table", C.POINTER(PriorEntry)), ("hyper", C.POINTER(C.c_int))]
+
+
+# pchip_prior.kind
+PRIOR_CALLBACK, PRIOR_BOX, PRIOR_TABLE = 0, 1, 2
+# the reference's prior type numbers (priors.f90:5-15) a table takes
+PRIOR_TYPES = {"uniform": 1, "log_uniform": 2, "power_uniform": 3, "gaussian": 4, "half_gaussian": 5, "exponential": 6,
+               "sorted_uniform": 7, "sorted_gaussian": 8, "sorted_half_gaussian": 9, "sorted_exponential": 10}
 
 
 class Result(C.Structure):
@@ -67,7 +80,7 @@ class Result(C.Structure):
 # pchip_result.path[]: launches per kernel variant (include/polychord_hip.h PCHIP_PATH_*)
 PATH_NAMES = ("consume_par", "consume_cl", "consume_general", "consume_fast", "killoff_par", "killoff_cl", "killoff_general",
               "killoff_fast", "update_fused", "update_steps", "slice_wave", "slice_lane", "nn_lists", "nn_fallbacks", "pool_mode",
-              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits", "source_kernels")
+              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits", "source_kernels", "device_prior")
 
 
 _lib = None
@@ -112,6 +125,12 @@ def load():
     lib.pchip_rtc_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_double)]
     lib.pchip_rtc_stats.restype = None
     lib.polychord_hip_last_error.restype = C.c_char_p
+    lib.polychord_hip_set_table_prior.argtypes = [C.c_int, C.POINTER(PriorEntry), C.POINTER(C.c_int)]
+    lib.polychord_hip_set_table_prior.restype = C.c_int
+    lib.polychord_hip_table_prior.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+    lib.polychord_hip_table_prior.restype = None
+    lib.pchip_prior_transform.argtypes = [C.POINTER(Prior), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+    lib.pchip_prior_transform.restype = C.c_int
     # this mirror against the library that was loaded (the structs grow at their end: include/polychord_hip.h PCHIP_ABI_VERSION)
     lib.pchip_sizeof.argtypes = [C.c_char_p]
     lib.pchip_sizeof.restype = C.c_ulong
@@ -140,8 +159,61 @@ def source_create(source, options=(), data=None):
     return h
 
 
-def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, invcov=None, mean=None, logdet=0.0, source=0):
-    """(Like, Prior, keepalive) for a built-in device likelihood, or a device source ("source", source=handle), and a uniform box prior."""
+def prior_table(entries, hyper=None):
+    """(PriorEntry array, hypercube-order array or None) of a prior table: entries = one (type, block, params) or (type, params) per
+    PARAMETER, type a name of PRIOR_TYPES or its number; hyper = hypercube index of every parameter (None: identity)"""
+    arr = (PriorEntry * len(entries))()
+    for i, e in enumerate(entries):
+        t, block, pars = (e[0], 1, e[1]) if len(e) == 2 else e
+        pars = [float(v) for v in np.atleast_1d(pars)]
+        arr[i].type = PRIOR_TYPES[t] if isinstance(t, str) else int(t)
+        arr[i].block, arr[i].npar = int(block), len(pars)
+        for k, v in enumerate(pars[:3]):
+            arr[i].par[k] = v
+    hy = None if hyper is None else np.ascontiguousarray(hyper, dtype=np.int32)
+    return arr, hy
+
+
+def set_table_prior(entries, hyper=None):
+    """polychord_hip_set_table_prior: the table behind polychord_hip_table_prior; ValueError with the library's message if it is refused"""
+    lib = load()
+    arr, hy = prior_table(entries, hyper)
+    if lib.polychord_hip_set_table_prior(len(arr), arr, hy.ctypes.data_as(C.POINTER(C.c_int)) if hy is not None else None) != 0:
+        msg = lib.polychord_hip_last_error()
+        raise ValueError(msg.decode(errors="replace") if msg else "prior table refused")
+
+
+def table_prior(cube):
+    """polychord_hip_table_prior (the HOST function) at one hypercube point"""
+    lib = load()
+    c = np.ascontiguousarray(cube, dtype=np.float64)
+    th = np.empty_like(c)
+    lib.polychord_hip_table_prior(dptr(c), dptr(th), int(c.size))
+    return th
+
+
+def prior_transform(entries, cubes, hyper=None, device=-1):
+    """pchip_prior_transform: the DEVICE transform of a table at the rows of `cubes` ([n][nDims]); theta rows"""
+    lib = load()
+    c = np.ascontiguousarray(np.atleast_2d(cubes), dtype=np.float64)
+    th = np.empty_like(c)
+    arr, hy = prior_table(entries, hyper)
+    P = Prior()
+    P.kind, P.table = PRIOR_TABLE, arr
+    if hy is not None:
+        P.hyper = hy.ctypes.data_as(C.POINTER(C.c_int))
+    rc = lib.pchip_prior_transform(C.byref(P), c.shape[1], c.shape[0], dptr(c), dptr(th), device)
+    if rc != 0:
+        msg = lib.polychord_hip_last_error()
+        raise RuntimeError(f"pchip_prior_transform failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
+    return th
+
+
+def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, invcov=None, mean=None, logdet=0.0, source=0,
+                 prior_table=None, hyper=None):
+    """(Like, Prior, keepalive) for a built-in device likelihood, or a device source ("source", source=handle), and a uniform box prior
+    -- or, with prior_table = [(type, block, params) | (type, params), ...] (and hyper, the parameters' hypercube indices), a prior table
+    evaluated inside the sampling kernels (pchip_prior.kind = 2)."""
     keep = []
     L = Like()
     L.kind = LIKE_KINDS[kind]
@@ -154,6 +226,13 @@ def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, i
         L.invcov, L.mean = dptr(ic), dptr(mn)
     P = Prior()
     P.kind = 1
+    if prior_table is not None:
+        arr, hy = globals()["prior_table"](prior_table, hyper)
+        keep += [arr, hy]
+        P.kind, P.table = PRIOR_TABLE, arr
+        if hy is not None:
+            P.hyper = hy.ctypes.data_as(C.POINTER(C.c_int))
+        return L, P, keep
     if lo is not None:
         lo_a = np.ascontiguousarray(np.broadcast_to(lo, (nDims,)), dtype=np.float64)
         hi_a = np.ascontiguousarray(np.broadcast_to(hi, (nDims,)), dtype=np.float64)

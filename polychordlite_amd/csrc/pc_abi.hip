@@ -8,6 +8,7 @@
 // Fatal conditions follow abort.F90:19-29: message on stderr, exit status 1.
 #include "../../include/polychord_hip.h"
 #include "pc_resume.h"
+#include "pc_prior_table.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +28,8 @@ struct Builtins {
     double g_mu = 0.5, g_sigma = 0.1;                 // likelihoods/examples/gaussian.f90:25-26
     int cg_D = 0; std::vector<double> cg_invcov, cg_mean; double cg_logdet = 0.0;
     int up_D = 0; std::vector<double> up_lo, up_hi;
+    PcPriorTable table;                               // polychord_hip_set_table_prior (D = 0: none)
+    bool device_prior = true;                         // option "device_prior": a table goes to the device when the likelihood is there
     int batch = 0, device = -1, epoch_discard = 0;
     std::vector<int> sub_dims;                        // polychord_hip_set_sub_clustering: 0-based cube coordinates of the sub-dimension pass
     bool halt_returns = false;                        // fatal conditions return to the caller instead of `stop 1` (language bindings)
@@ -458,6 +461,22 @@ void polychord_hip_set_uniform_prior(int D, const double *lo, const double *hi)
 {
     G.up_D = D; G.up_lo.assign(lo, lo + D); G.up_hi.assign(hi, hi + D);
 }
+// the prior table as a host function: what the maximiser, write_prior, the tests' oracle and a reference-side caller evaluate
+// (pc_prior_table.h: the one host implementation; polychord_hip_ini_prior goes through it too)
+void polychord_hip_table_prior(double *cube, double *theta, int D)
+{
+    if (G.table.D != D) halt_program("polychord_hip: polychord_hip_set_table_prior was not called for this nDims");
+    pc_prior_table_eval(G.table, cube, theta);
+}
+int polychord_hip_set_table_prior(int D, const pchip_prior_entry *entries, const int *hyper)
+{
+    PcPriorTable T;
+    const std::string err = pc_prior_table_build(D, entries, hyper, T);
+    if (!err.empty()) { G.last_error = err; return 1; }
+    G.table = T;
+    G.last_error.clear();
+    return 0;
+}
 void polychord_hip_set_option(const char *name, double value)
 {
     if (!std::strcmp(name, "batch")) G.batch = (int)value;
@@ -468,6 +487,7 @@ void polychord_hip_set_option(const char *name, double value)
     else if (!std::strcmp(name, "trim_cache")) pchip_trim_cache();
     else if (!std::strcmp(name, "halt_returns")) G.halt_returns = value != 0.0;
     else if (!std::strcmp(name, "epoch_discard")) G.epoch_discard = value != 0.0 ? 1 : 0;
+    else if (!std::strcmp(name, "device_prior")) G.device_prior = value != 0.0;
     else std::fprintf(stderr, "polychord_hip: unknown option %s\n", name);
 }
 
@@ -704,7 +724,12 @@ static void c_interface_impl(
     if (prior == polychord_hip_uniform_prior) {
         P.kind = 1;
         if (G.up_D == nDims) { P.lo = G.up_lo.data(); P.hi = G.up_hi.data(); }
+    } else if (prior == polychord_hip_table_prior && G.device_prior && L.kind != PCHIP_LIKE_CALLBACK) {
+        // a prior table with a built-in likelihood: both on the device (a table that is a box runs as the box: Engine::setup)
+        if (G.table.D != nDims) halt_program("polychord_hip: polychord_hip_set_table_prior was not called for this nDims");
+        P.kind = PCHIP_PRIOR_TABLE; P.table = G.table.e.data(); P.hyper = G.table.hyper.data(); P.fn = prior;
     } else { P.kind = 0; P.fn = prior; }
+    const bool table_on_device = P.kind == PCHIP_PRIOR_TABLE && !G.table.is_box;
     const std::string base = base_dir ? base_dir : "chains", root = file_root ? file_root : "test";
     if (write_stats_f || write_dead || write_live || posteriors || equals || write_prior || write_resume) {
         struct stat sb;
@@ -747,6 +772,7 @@ static void c_interface_impl(
             std::printf("chains in flight when the list of clusters changes: %s\n",
                         s.epoch_discard ? "all discarded (epoch_discard = 1: the reference farm's rule, nested_sampling.F90:313)"
                                         : "only those seeded in the cluster that ended are lost (epoch_discard = 0, this engine's default; option \"epoch_discard\" = 1: the reference farm's rule)");
+        if (table_on_device) std::printf("prior table evaluated on the device, inside the sampling kernels (option \"device_prior\" = 0: on the host)\n");
         if (write_resume || read_resume) std::printf("Resume file: %s/%s.resume\n", base.c_str(), root.c_str());
         std::printf("\nnum_repeats:");
         if (g_reps.size()) for (int v : g_reps) std::printf("%8d", v); else std::printf("%8d", num_repeats);

@@ -7,6 +7,7 @@
 // + [K2 consume | K3 apply] + (on an update) [clean phantoms | covariance + Cholesky].
 #include "pc_state.h"
 #include "pc_resume.h"
+#include "pc_prior_table.h"
 #include "../../include/polychord_hip.h"
 #include <cstdio>
 #include <cstdlib>
@@ -43,6 +44,8 @@ int pc_launch_nhats(const PcState *, unsigned, int, hipStream_t);
 int pc_nhats_splittable(const PcState *);
 int pc_launch_nhats_part(const PcState *, unsigned, int, int, hipStream_t, int);
 int pc_launch_slice(const PcState *, unsigned, int, hipStream_t);
+int pc_launch_prior_transform(const PcState *, int, const double *, double *, hipStream_t);
+void pc_abi_set_last_error(const char *);
 int pc_slice_fusable(const PcState *);
 int pc_launch_slice_fused(const PcState *, unsigned, int, hipStream_t);
 int pc_slice_t_ok(const PcState *, int);
@@ -802,6 +805,7 @@ struct Engine {
     double *psum = nullptr, *mean = nullptr, *pcov = nullptr; int *pcnt = nullptr, *count = nullptr;
     size_t cov_chunks_cap = 0;
     double *upd_part = nullptr, *upd_shift = nullptr; size_t upd_part_cap = 0;   // fused update (pc_update.hip)
+    PcPriorTable ptab; bool have_ptab = false;      // prior.kind == PCHIP_PRIOR_TABLE: checked copy (the host function of callback mode; what went to the device)
     double *d_lo = nullptr, *d_hi = nullptr, *d_invcovT = nullptr, *d_mean = nullptr, *d_src = nullptr;
     double *d_dynL = nullptr; int *d_dynN = nullptr; double *d_logn = nullptr;
     // clustering scratch (allocated on first use)
@@ -897,7 +901,7 @@ struct Engine {
         // are spent on spawns that fail -- cheap for a compiled likelihood (then the round trips per nursery dominate and
         // many chains per nursery pay: nlive / 2), dear for an expensive one (nlive / 4, at most 64).  Which one this is
         // is measured while the live points are generated; buffers are sized for the larger choice.
-        cb_auto_batch = c.batch <= 0 && !c.sequential_rng && (like.kind == PC_LIKE_CALLBACK || prior.kind != 1);
+        cb_auto_batch = c.batch <= 0 && !c.sequential_rng && (like.kind == PC_LIKE_CALLBACK || (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE));
         if (cb_auto_batch) B_small = std::max(1, std::min(64, c.nlive / 4));
         S.B = B;
         S.maxc = c.do_clustering ? std::max(2, g_cap_clusters.load()) : 4;
@@ -932,7 +936,7 @@ struct Engine {
             const double *h = nullptr; long long n = 0;
             if (pc_rtc_source_data(like.source, &h, &n)) engine_fail(PC_RC_SETTINGS, "device source handle %d does not exist", like.source);
             if (nDer > PC_SRC_MAX_DERIVED) engine_fail(PC_RC_SETTINGS, "a device source likelihood writes at most %d derived parameters, not %d", PC_SRC_MAX_DERIVED, nDer);
-            if (prior.kind != 1) engine_fail(PC_RC_SETTINGS, "a device source likelihood needs a device prior (the uniform box), not a host-callback prior");
+            if (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE) engine_fail(PC_RC_SETTINGS, "a device source likelihood needs a device prior (the uniform box), not a host-callback prior");
             S.src_id = like.source;
             if (n > 0) { d_src = dalloc<double>((size_t)n); upload(d_src, h, sizeof(double) * (size_t)n); S.src_data = d_src; S.src_ndata = n; }
         }
@@ -944,17 +948,42 @@ struct Engine {
             upload(d_mean, like.mean, sizeof(double) * D);
             S.like.invcov = d_invcovT; S.like.mean = d_mean;
         }
-        callback_mode = (like.kind == PC_LIKE_CALLBACK) || (prior.kind != 1);
+        // A prior table: checked once.  With a callback likelihood it serves as the host prior function; with a device likelihood
+        // it goes up once -- S.prior.lo carries the per-parameter doubles, S.prior.hi the per-parameter integers, S.src_pad the mask of
+        // the types present (pc_table_theta, pc_sample.hip: PcState keeps its size and every kernel of a box run its arguments) --
+        // unless it IS a box (all uniform, identity order): then the run is the box run, bit for bit.
+        have_ptab = false;
+        int prior_kind = prior.kind;
+        std::vector<double> box_lo, box_hi;
+        const double *p_lo = prior.lo, *p_hi = prior.hi;
+        if (prior.kind == PCHIP_PRIOR_TABLE) {
+            const std::string err = pc_prior_table_build(D, prior.table, prior.hyper, ptab);
+            if (!err.empty()) { pc_abi_set_last_error(err.c_str()); engine_fail(PC_RC_SETTINGS, "%s", err.c_str()); }
+            have_ptab = true;
+            if (ptab.is_box && like.kind != PC_LIKE_CALLBACK) {
+                box_lo.resize(D); box_hi.resize(D);
+                for (int i = 0; i < D; ++i) { box_lo[i] = ptab.e[i].par[0]; box_hi[i] = ptab.e[i].par[1]; }
+                prior_kind = 1; p_lo = box_lo.data(); p_hi = box_hi.data();
+            }
+        } else if (prior.kind != 0 && prior.kind != 1) engine_fail(PC_RC_SETTINGS, "prior.kind = %d: 0 (callback), 1 (uniform box) or 2 (table)", prior.kind);
+        callback_mode = (like.kind == PC_LIKE_CALLBACK) || (prior_kind != 1 && prior_kind != PCHIP_PRIOR_TABLE);
         if (callback_mode) {
-            cb_like = like.fn; cb_prior = prior.fn;
+            cb_like = like.fn; cb_prior = prior.kind == PCHIP_PRIOR_TABLE ? nullptr : prior.fn;      // (a table is its own host function: host_eval)
             if (!cb_like) engine_fail(PC_RC_SETTINGS, "callback mode needs a loglikelihood function pointer");
         }
-        S.prior.kind = prior.kind; S.prior.lo = nullptr; S.prior.hi = nullptr;
-        if (prior.kind == 1 && prior.lo && prior.hi) {
+        S.prior.kind = callback_mode ? (prior_kind == PCHIP_PRIOR_TABLE ? 0 : prior_kind) : prior_kind; S.prior.lo = nullptr; S.prior.hi = nullptr;
+        if (prior_kind == 1 && p_lo && p_hi) {
             d_lo = dalloc<double>(D); d_hi = dalloc<double>(D);
-            upload(d_lo, prior.lo, sizeof(double) * D);
-            upload(d_hi, prior.hi, sizeof(double) * D);
+            upload(d_lo, p_lo, sizeof(double) * D);
+            upload(d_hi, p_hi, sizeof(double) * D);
             S.prior.lo = d_lo; S.prior.hi = d_hi;
+        }
+        if (S.prior.kind == PCHIP_PRIOR_TABLE) {
+            const std::vector<double> tp = ptab.dev_par(); const std::vector<int> ti = ptab.dev_int();
+            d_lo = dalloc<double>(tp.size()); d_hi = dalloc<double>((ti.size() + 1) / 2);
+            upload(d_lo, tp.data(), sizeof(double) * tp.size());
+            upload(d_hi, ti.data(), sizeof(int) * ti.size());
+            S.prior.lo = d_lo; S.prior.hi = d_hi; S.src_pad = (int)ptab.mask;
         }
         // state arrays
         const int Ncap = S.Ncap, maxc = S.maxc, nT = S.nT, nr = S.nr;
@@ -994,7 +1023,7 @@ struct Engine {
         }
         S.nhat = dalloc<double>((size_t)B * nr * D); S.nhat_w = dalloc<double>((size_t)B * nr);
         static const bool ms_off = std::getenv("PC_MS_PRE_OFF") != nullptr;
-        const bool ms_pre = S.like.kind == PC_LIKE_CORR_GAUSSIAN && D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !(S.ablate & 1) && !ms_off;
+        const bool ms_pre = S.like.kind == PC_LIKE_CORR_GAUSSIAN && D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !(S.ablate & 1) && !ms_off && S.prior.kind != PCHIP_PRIOR_TABLE;
         S.nhat_Ms = ms_pre ? dalloc<double>((size_t)B * nr * D) : nullptr;
         S.ch_My = ms_pre ? dalloc<double>((size_t)B * D) : nullptr;
         static const bool split_off = std::getenv("PC_NHATS_SPLIT_OFF") != nullptr;
@@ -1888,6 +1917,7 @@ struct Engine {
     {
         const int D = S.D;
         if (cb_prior) cb_prior(const_cast<double *>(cube), theta, D);
+        else if (have_ptab) pc_prior_table_eval(ptab, cube, theta);
         else {
             if ((int)h_lo.size() != D) {
                 h_lo.assign(D, 0.0); h_hi.assign(D, 1.0);
@@ -2000,6 +2030,7 @@ struct Engine {
         bool direct = true;
         while (have < nprior) {
             if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
+            if (S.prior.kind == PCHIP_PRIOR_TABLE) path[PCHIP_PATH_DEVICE_PRIOR]++;
             if (pc_launch_generate_live(&S, attempt0, nprior, rows, rl, st)) {
                 if (pc_rtc_wanted(&S) && pc_rtc_error()) engine_fail(PC_RC_SETTINGS, "%.480s", pc_rtc_error());
                 engine_fail(PC_RC_NDIMS, "nDims > 256 unsupported");
@@ -2030,6 +2061,7 @@ struct Engine {
             for (; S.ngrade <= 1; ++a) {
                 double l1 = 0.0;
                 if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
+                if (S.prior.kind == PCHIP_PRIOR_TABLE) path[PCHIP_PATH_DEVICE_PRIOR]++;
                 (void)pc_launch_generate_live(&S, a, 1, rows, rl, st);
                 HIPCHK(hipMemcpyAsync(&l1, rl, sizeof(double), hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
@@ -2346,7 +2378,7 @@ struct Engine {
     bool cohort_general_ok() const
     {
         static const bool off = std::getenv("PC_COHORT_GENERAL") && std::atoi(std::getenv("PC_COHORT_GENERAL")) == 0;
-        return !off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK;
+        return !off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK && S.prior.kind != PCHIP_PRIOR_TABLE;
     }
     // The sampling of one nursery: pool rows, the bases (drawn ahead on the side stream, or now), k_slice, the bases of the
     // nurseries to come.
@@ -2406,7 +2438,7 @@ struct Engine {
                 co->rec(CK_SLICE_G, S, {}, {(long long)B, fused_slice ? 1LL : 0LL}, {(int)batch, 0, 0, fused_slice ? bases_seq : 0});
                 if (fused_slice && co->st2 && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
             }
-            else if ((path[PCHIP_PATH_SLICE_WAVE]++, path[PCHIP_PATH_SOURCE_KERNELS] += pc_rtc_wanted(&S) ? 1 : 0, co ? (co->flush(), co->wait_next(), 0) : 0) || (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st))) {
+            else if ((path[PCHIP_PATH_SLICE_WAVE]++, path[PCHIP_PATH_SOURCE_KERNELS] += pc_rtc_wanted(&S) ? 1 : 0, path[PCHIP_PATH_DEVICE_PRIOR] += S.prior.kind == PCHIP_PRIOR_TABLE ? 1 : 0, co ? (co->flush(), co->wait_next(), 0) : 0) || (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st))) {
                 if (pc_rtc_wanted(&S) && pc_rtc_error()) { std::fprintf(stderr, "polychord_hip: %s\n", pc_rtc_error()); r_rc = 1; return false; }
                 std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false;
             }
@@ -3262,6 +3294,37 @@ int pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const pc
         rc = e.code;
     }
     E.destroy();
+    return rc;
+}
+
+// kernel-level entry for the parity tests: the device transform of a prior table at n hypercube points
+int pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const double *cube, double *theta, int device)
+{
+    if (!prior || prior->kind != PCHIP_PRIOR_TABLE || n < 1 || !cube || !theta) { pc_abi_set_last_error("pchip_prior_transform: a prior table (kind 2) and n >= 1 points"); return 1; }
+    PcPriorTable T;
+    const std::string err = pc_prior_table_build(nDims, prior->table, prior->hyper, T);
+    if (!err.empty()) { pc_abi_set_last_error(err.c_str()); return 1; }
+    if (nDims > 256) return 3;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
+    if (hipSetDevice(device >= 0 ? device % ndev : 0) != hipSuccess) return 2;
+    const std::vector<double> tp = T.dev_par(); const std::vector<int> ti = T.dev_int();
+    double *d_tp = nullptr, *d_c = nullptr, *d_t = nullptr; int *d_ti = nullptr;
+    const size_t nb = sizeof(double) * (size_t)n * nDims;
+    int rc = 2;
+    if (hipMalloc(&d_tp, sizeof(double) * tp.size()) == hipSuccess && hipMalloc(&d_ti, sizeof(int) * ti.size()) == hipSuccess &&
+        hipMalloc(&d_c, nb) == hipSuccess && hipMalloc(&d_t, nb) == hipSuccess &&
+        hipMemcpy(d_tp, tp.data(), sizeof(double) * tp.size(), hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_ti, ti.data(), sizeof(int) * ti.size(), hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_c, cube, nb, hipMemcpyHostToDevice) == hipSuccess) {
+        PcState S;
+        std::memset(&S, 0, sizeof(S));
+        S.D = nDims; S.prior.kind = PCHIP_PRIOR_TABLE; S.prior.lo = d_tp; S.prior.hi = (const double *)d_ti; S.src_pad = (int)T.mask;
+        if (pc_launch_prior_transform(&S, n, d_c, d_t, nullptr) == 0 && hipDeviceSynchronize() == hipSuccess &&
+            hipMemcpy(theta, d_t, nb, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    }
+    if (rc) (void)hipGetLastError();
+    (void)hipFree(d_tp); (void)hipFree(d_ti); (void)hipFree(d_c); (void)hipFree(d_t);
     return rc;
 }
 

@@ -28,6 +28,99 @@ struct LaneDims {
     bool on[DPL];
 };
 
+// ------------------------------------------------------------------------------------------
+// prior table (PcPrior::kind == 2, the reference's prior types: priors.f90:40-290, hypercube_to_physical :494-556) on a wave, lane =
+// PARAMETER.  S.prior.lo carries the doubles [3][D] -- per base type: uniform lo, hi - lo; log_uniform lo, hi / lo; power_uniform
+// a = lo^(1/p), |a - hi^(1/p)|, p; gaussian / half_gaussian mu, sigma; exponential the rate -- S.prior.hi the integers [4][D] (base type
+// 1 .. 6, 1-based position in the sorted_ block and the block's length or 0, 0, hypercube index), S.src_pad the wave-uniform mask:
+// bit t = base type t is present, bit 16 = a sorted_ block, bit 17 = the hypercube order is no identity.  Read ONCE at the head of a chain.
+// ------------------------------------------------------------------------------------------
+#define PC_PT_SORTED (1u << 16)
+#define PC_PT_PERMUTED (1u << 17)
+template <int DPL>
+struct LaneTable {
+    int type[DPL], pos[DPL], len[DPL], hyp[DPL];
+    double p0[DPL], p1[DPL], p2[DPL];
+    unsigned mask;
+};
+template <int DPL>
+__device__ __forceinline__ void pc_table_load(const PcState &S, int lane, LaneTable<DPL> &lt)
+{
+    const int D = S.D;
+    const double *tp = S.prior.lo;
+    const int *ti = (const int *)S.prior.hi;
+    lt.mask = (unsigned)S.src_pad;
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) {
+        const int dim = lane + 64 * k;
+        const bool on = dim < D;
+        lt.type[k] = on ? ti[dim] : 0; lt.pos[k] = on ? ti[D + dim] : 0; lt.len[k] = on ? ti[2 * D + dim] : 0; lt.hyp[k] = on ? ti[3 * D + dim] : 0;
+        lt.p0[k] = on ? tp[dim] : 0.0; lt.p1[k] = on ? tp[D + dim] : 0.0; lt.p2[k] = on ? tp[2 * D + dim] : 0.0;
+    }
+}
+// cube (hypercube order) -> theta (parameter order).  ybuf: the wave's LDS scratch of >= D doubles (one wave per workgroup: the barriers
+// are cheap and every lane reaches them -- the mask is a kernel argument).  A wave pays each type PRESENT in the run once per call:
+//   * y = cube[hyper[dim]]: a gather through LDS unless the order is the identity;
+//   * sorted_ blocks (priors.f90:245-262): every member forms x_j^(1/j) (one pow a lane), then the running product from the block's LAST member down to
+//     its own, in the reference's order of multiplication (y_n = x_n^(1/n), y_k = y_{k+1} x_k^(1/k)): a short serial chain a lane over
+//     LDS, all members in parallel; a block may lie across the lane-63 / lane-0 boundary;
+//   * the separable transform of the lane's type; the types that are absent from the run are skipped by a scalar branch.
+template <int DPL>
+__device__ __forceinline__ void pc_table_theta(const LaneTable<DPL> &lt, const double (&cube)[DPL], double (&th)[DPL], int lane, double *ybuf)
+{
+    double y[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) y[k] = cube[k];
+    if (lt.mask & PC_PT_PERMUTED) {
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) if (lt.type[k]) ybuf[lane + 64 * k] = cube[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) if (lt.type[k]) y[k] = ybuf[lt.hyp[k]];
+        __syncthreads();
+    }
+    if (lt.mask & PC_PT_SORTED) {
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) {
+            if (lt.len[k] > 0) {
+                const int j = lt.pos[k];
+                double t = pow(y[k], 1.0 / (double)j);
+                // (within 2^-33 of 1 the root is formed exactly, as on the host -- pc_sorted_root, pc_prior_table.h: the last bit of pow
+                //  would decide there whether the block's largest member meets the p >= 1 guard of AS241)
+                if (y[k] < 1.0 && y[k] > 1.0 - 0x1p-33 && j <= 256) {
+                    const int kk = (int)((1.0 - y[k]) * 0x1p53);
+                    t = 1.0 - (double)((2 * kk + j) / (2 * j)) * 0x1p-53;
+                }
+                y[k] = t;
+            }
+            if (lt.type[k]) ybuf[lane + 64 * k] = y[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < DPL; ++k)
+            if (lt.len[k] > 0) {
+                const int dim = lane + 64 * k, last = dim - lt.pos[k] + lt.len[k];
+                double r = ybuf[last];
+                for (int i = last - 1; i >= dim; --i) r = r * ybuf[i];
+                y[k] = r;
+            }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) {
+        const int t = lt.type[k];
+        double v = 0.0;
+        if (lt.mask & (1u << 1)) { if (t == 1) v = lt.p0[k] + lt.p1[k] * y[k]; }                          // priors.f90:40-55
+        if (lt.mask & (1u << 2)) { if (t == 2) v = lt.p0[k] * pow(lt.p1[k], y[k]); }                      // :114-128
+        if (lt.mask & (1u << 3)) { if (t == 3) v = pow(lt.p0[k] - y[k] * lt.p1[k], lt.p2[k]); }           // :151-167
+        if (lt.mask & ((1u << 4) | (1u << 5))) {                                                          // :73-88, :172-187
+            if (t == 4 || t == 5) v = lt.p0[k] + lt.p1[k] * pc_inv_normal_cdf(t == 4 ? y[k] : 0.5 + 0.5 * y[k]);
+        }
+        if (lt.mask & (1u << 6)) { if (t == 6) v = -log(1.0 - y[k]) / lt.p0[k]; }                         // :192-204
+        th[k] = v;
+    }
+}
+
 #ifdef PCHIP_USER_SOURCE
 // the user's function (pc_rtc.hip): its text follows the library's in the run-time unit, so that none of its macros reach these kernels
 __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
@@ -141,7 +234,8 @@ __device__ __forceinline__ void like_phi_source(const PcState &S, const double (
 // initial live points: GenerateLivePoints, linear mode (generate.F90:150-183)
 // one wave per attempt; attempts are the oracle's PC_DOM_LIVEGEN streams.
 // ------------------------------------------------------------------------------------------
-template <int DPL>
+// PT = 1: the prior is a table (pc_table_theta); PT = 0, the default, is the uniform box
+template <int DPL, int PT = 0>
 __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, double *rows /* [n][nT] */,
                                                      double *rows_logL)
 {
@@ -155,13 +249,18 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
     for (int k = 0; k < DPL; ++k) {
         const int dim = lane + 64 * k;
         ld.on[k] = dim < D;
-        const double lo = (ld.on[k] && S.prior.lo) ? S.prior.lo[dim] : 0.0;
-        const double hi = (ld.on[k] && S.prior.hi) ? S.prior.hi[dim] : 1.0;
+        const double lo = (PT == 0 && ld.on[k] && S.prior.lo) ? S.prior.lo[dim] : 0.0;
+        const double hi = (PT == 0 && ld.on[k] && S.prior.hi) ? S.prior.hi[dim] : 1.0;
         ld.lo[k] = lo; ld.span[k] = hi - lo;
         ld.mean[k] = (ld.on[k] && S.like.mean) ? S.like.mean[dim] : 0.0;
         cube[k] = !ld.on[k] ? 0.5 : (S.seq_mode ? pc_seq_uniform(S, (unsigned long long)attempt * D + dim)
                                                  : pc_uniform(S.k0, S.k1, PC_DOM_LIVEGEN, 0u, (uint32_t)attempt, (uint32_t)dim));
         th[k] = ld.lo[k] + ld.span[k] * cube[k];
+    }
+    if constexpr (PT != 0) {
+        LaneTable<DPL> lt;
+        pc_table_load<DPL>(S, lane, lt);
+        pc_table_theta<DPL>(lt, cube, th, lane, ybuf);
     }
     const double logL = like_eval<DPL, 4>(S, th, ld, lane, ybuf);
     double phi0, phi1;
@@ -183,6 +282,24 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
         row[S.l0] = logL;
         rows_logL[a] = logL;
     }
+}
+
+// the device transform of a prior table alone (pchip_prior_transform: parity tests against the host function): one wave a point
+template <int DPL>
+__global__ __launch_bounds__(64) void k_prior_transform(PcState S, const double *cubes /* [n][D] */, double *thetas /* [n][D] */)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double *ybuf = (double *)smem;
+    const int lane = threadIdx.x, D = S.D;
+    const size_t base = (size_t)blockIdx.x * D;
+    LaneTable<DPL> lt;
+    pc_table_load<DPL>(S, lane, lt);
+    double cube[DPL], th[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) cube[k] = (lane + 64 * k < D) ? cubes[base + lane + 64 * k] : 0.5;
+    pc_table_theta<DPL>(lt, cube, th, lane, ybuf);
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) if (lane + 64 * k < D) thetas[base + lane + 64 * k] = th[k];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1120,7 +1237,7 @@ __global__ __launch_bounds__(256) void k_whiten(PcState S, unsigned batch)
 // ------------------------------------------------------------------------------------------
 // K1: one slice-sampling chain per wavefront
 // ------------------------------------------------------------------------------------------
-template <int DPL, int NROWS>
+template <int DPL, int NROWS, int PT = 0>
 struct ChainCtx {
     const PcState &S;
     const LaneDims<DPL> &ld;
@@ -1136,10 +1253,23 @@ struct ChainCtx {
     bool quad;
     double qa, qb, qc, qnorm;
 };
+// PT = 1: the same with the chain's prior table behind it (a non-linear prior has no closed form along the chord: quad stays false).
+// A specialisation, so that the box's context -- and with it every kernel of a box run -- is what it was.
+template <int DPL, int NROWS>
+struct ChainCtx<DPL, NROWS, 1> {
+    const PcState &S;
+    const LaneDims<DPL> &ld;
+    int lane;
+    double *ybuf;
+    int nlike;
+    bool quad;
+    double qa, qb, qc, qnorm;
+    LaneTable<DPL> tb;
+};
 
 // calculate_point (calculate.f90:6-50) at x0 + t*nh; leaves cube/theta of the trial in registers
-template <int DPL, int NROWS, int KIND = -1>
-__device__ __forceinline__ double eval_at(ChainCtx<DPL, NROWS> &C, const double (&x0)[DPL], const double (&nh)[DPL],
+template <int DPL, int NROWS, int KIND = -1, int PT = 0>
+__device__ __forceinline__ double eval_at(ChainCtx<DPL, NROWS, PT> &C, const double (&x0)[DPL], const double (&nh)[DPL],
                                           double t, double (&cube)[DPL], double (&th)[DPL])
 {
     bool outside = false;
@@ -1168,8 +1298,11 @@ __device__ __forceinline__ double eval_at(ChainCtx<DPL, NROWS> &C, const double 
         for (int k = 0; k < DPL; ++k) th[k] = 0.0;
         return C.S.logzero;
     }
+    if constexpr (PT != 0) pc_table_theta<DPL>(C.tb, cube, th, C.lane, C.ybuf);
+    else {
 #pragma unroll
     for (int k = 0; k < DPL; ++k) th[k] = C.ld.lo[k] + C.ld.span[k] * cube[k];
+    }
     const double logL = like_eval<DPL, NROWS, KIND>(C.S, th, C.ld, C.lane, C.ybuf);
     if (logL > C.S.logzero) C.nlike++;
     return logL;
@@ -1178,12 +1311,36 @@ __device__ __forceinline__ double eval_at(ChainCtx<DPL, NROWS> &C, const double 
 // Two independent trial points at once (the two ends of the initial bracket): the per-point work is a
 // dependent chain (FMA -> compare -> reduction), so the second evaluation rides in the shadow of the first.
 // Straight-line code: both likelihoods are computed unconditionally and masked afterwards.
-template <int DPL, int NROWS, int KIND = -1>
-__device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS> &C, const double (&x0)[DPL], const double (&nh)[DPL],
+template <int DPL, int NROWS, int KIND = -1, int PT = 0>
+__device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS, PT> &C, const double (&x0)[DPL], const double (&nh)[DPL],
                                           double tA, double tB, double &lA, double &lB)
 {
     const PcLike &L = C.S.like;
     const int kind = KIND >= 0 ? KIND : L.kind;
+    if constexpr (PT != 0) {
+        // a prior table: the outside-the-cube test first (calculate.f90:36-38; wave-uniform ballots), then the transform and the
+        // likelihood of the points that are inside -- any kind through like_eval
+        bool outA = false, outB = false;
+        double cA[DPL], cB[DPL], thA[DPL], thB[DPL];
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) {
+            cA[k] = x0[k] + tA * nh[k]; cB[k] = x0[k] + tB * nh[k];
+            if (C.ld.on[k]) { outA |= (cA[k] < 0.0) | (cA[k] > 1.0); outB |= (cB[k] < 0.0) | (cB[k] > 1.0); }
+        }
+        const bool oa = __ballot(outA) != 0ull, ob = __ballot(outB) != 0ull;
+        lA = C.S.logzero; lB = C.S.logzero;
+        if (!oa) {
+            pc_table_theta<DPL>(C.tb, cA, thA, C.lane, C.ybuf);
+            lA = like_eval<DPL, NROWS, KIND>(C.S, thA, C.ld, C.lane, C.ybuf);
+            if (lA > C.S.logzero) C.nlike++;
+        }
+        if (!ob) {
+            pc_table_theta<DPL>(C.tb, cB, thB, C.lane, C.ybuf);
+            lB = like_eval<DPL, NROWS, KIND>(C.S, thB, C.ld, C.lane, C.ybuf);
+            if (lB > C.S.logzero) C.nlike++;
+        }
+        return;
+    }
     if (C.quad) {
         bool oA = false, oB = false;
 #pragma unroll
@@ -1277,7 +1434,8 @@ __device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS> &C, const double 
 #else
 #define PC_SLICE_ATTR
 #endif
-template <int DPL, int NROWS, bool SPECIAL, int WPB = 1, int FW = 0, int LEAN = 0>
+// PT = 1: the prior is a table (pc_table_theta) -- the general variants only (LEAN = 0, WPB = 1): no closed form along the chord
+template <int DPL, int NROWS, bool SPECIAL, int WPB = 1, int FW = 0, int LEAN = 0, int PT = 0>
 __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB * ((FW > 0 && (LEAN == 1 || LEAN == 3 || LEAN == 5) && WPB == 4) ? 2 : 1)) void k_slice(PcState S, unsigned batch, int phi_lds, int mat_lds)
 {
 #include "pc_slice_body.inc"
@@ -1293,6 +1451,7 @@ __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB) void k_slice_many(const PcM
     //  kernel, the same statements, and a run in step was no longer bit for bit the run alone)
     const PcState S = R[blockIdx.y].S;
     const unsigned batch = (unsigned)R[blockIdx.y].ia[0];
+    constexpr int PT = 0;                         // (runs in step take the box only)
 #include "pc_slice_body.inc"
 }
 
@@ -1316,6 +1475,13 @@ extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, do
                                        hipStream_t st)
 {
     const size_t sh = sizeof(double) * S->D;
+    if (S->prior.kind == 2) {                   // a prior table
+        if (S->D <= 64) PC_LAUNCH((k_generate_live<1, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
+        else if (S->D <= 128) PC_LAUNCH((k_generate_live<2, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
+        else if (S->D <= 256) PC_LAUNCH((k_generate_live<4, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
+        else return 1;
+        return 0;
+    }
     if (S->D <= 64) PC_LAUNCH((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
     else if (S->D <= 128) PC_LAUNCH((k_generate_live<2>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
     else if (S->D <= 256) PC_LAUNCH((k_generate_live<4>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
@@ -1423,7 +1589,7 @@ extern "C" int pc_slice_fusable(const PcState *S)
 static int slice_lean_functor(const PcState *S)
 {
     static const bool off = std::getenv("PC_SLICE_LEAN_OFF") != nullptr;
-    if (off || S->ngrade > 1 || S->seq_mode) return 0;
+    if (off || S->ngrade > 1 || S->seq_mode || S->prior.kind == 2) return 0;      // (a prior table: the general variants)
     return S->like.kind == PC_LIKE_RASTRIGIN ? 3 : (S->like.kind == PC_LIKE_TWIN_GAUSSIAN ? 4 : ((S->like.kind == PC_LIKE_GAUSSIAN && (S->ablate & 1)) ? 5 : 0));
 }
 
@@ -1437,7 +1603,8 @@ extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchai
     const size_t sh = sh0 + (phi_lds ? tb : 0) + sizeof(double) * ((size_t)FWv * D + (size_t)S->nr * (D + 2));   // + L, directions, widths
     if (sh > 150 * 1024) return 1;
     static const bool lean_off = std::getenv("PC_SLICE_LEAN_OFF") != nullptr;
-    const bool lean = !lean_off && S->like.kind == PC_LIKE_GAUSSIAN && !(S->ablate & 1) && phi_lds && S->nr <= 64 && !S->seq_mode && S->ngrade <= 1;
+    const bool table = S->prior.kind == 2;
+    const bool lean = !lean_off && !table && S->like.kind == PC_LIKE_GAUSSIAN && !(S->ablate & 1) && phi_lds && S->nr <= 64 && !S->seq_mode && S->ngrade <= 1;
     const int leanf = slice_lean_functor(S);
     // (a helper wavefront per chain for the lean variants whose deck lives in registers: pc_slice_body.inc; settings.ablate bit 13 / PC_SLICE_HELPER_OFF: without)
     // four chains a workgroup with their four helper wavefronts (pc_slice_body.inc): the lean variants whose deck lives in registers, nurseries of a
@@ -1458,7 +1625,9 @@ extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchai
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW, 1>, sh); \
         if (help) { if (sh4 > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 4, FW, 1>, sh4); \
         PC_LAUNCH((k_slice<1, NROWS, false, 4, FW, 1>), dim3(nchains / 4), dim3(512), sh4, st, *S, batch, phi_lds, 0); } else \
-        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } else { \
+        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } else if (table) { \
+        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW, 0, 1>, sh); \
+        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW, 0, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } else { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW>, sh); \
         PC_LAUNCH((k_slice<1, NROWS, false, 1, FW>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } }
     if (D <= 8) PC_SLICE_FUSED(1, 8)
@@ -1475,6 +1644,7 @@ extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchai
 extern "C" int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st)
 {
     const int D = S->D;
+    if (S->prior.kind == 2) return 1;           // (a prior table: the one-run launchers)
     const size_t sh0 = sizeof(double) * ((size_t)D + S->nr) + 16;
     const size_t tb = sizeof(double) * (size_t)S->nr * (D + 1);
     const int phi_lds = (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
@@ -1531,7 +1701,8 @@ extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hi
     const int phi_lds = (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
     size_t sh = sh0 + (phi_lds ? tb : 0);
     const size_t mb = sizeof(double) * (size_t)S->D * S->D;
-    const int mat_lds = (S->like.kind == PC_LIKE_CORR_GAUSSIAN && S->nhat_Ms == nullptr && sh + mb <= 150 * 1024) ? 1 : 0;
+    const bool table = S->prior.kind == 2;      // (a prior table: every likelihood through like_eval, no matrix in LDS)
+    const int mat_lds = (!table && S->like.kind == PC_LIKE_CORR_GAUSSIAN && S->nhat_Ms == nullptr && sh + mb <= 150 * 1024) ? 1 : 0;
     const int D = S->D;
     // four chains per workgroup around one LDS copy of the inverse covariance (65 <= nDims <= 128)
     static const bool wpb_off = std::getenv("PC_SLICE_WPB_OFF") != nullptr;
@@ -1543,7 +1714,7 @@ extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hi
     }
     if (mat_lds) sh += mb;
     static const bool lean2_off = std::getenv("PC_SLICE_LEAN_OFF") != nullptr;
-    if (!lean2_off && S->like.kind == PC_LIKE_CORR_GAUSSIAN && S->nhat_Ms != nullptr && !(S->ablate & 1) && S->nDer == 0 && S->nr > 64 && D > 64 && D <= 128 &&
+    if (!lean2_off && !table && S->like.kind == PC_LIKE_CORR_GAUSSIAN && S->nhat_Ms != nullptr && !(S->ablate & 1) && S->nDer == 0 && S->nr > 64 && D > 64 && D <= 128 &&
         S->ngrade <= 1 && !S->seq_mode && !mat_lds) {
         // BASELINE configs[4]'s shape: the kernel without its other variants (LEAN = 2)
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<2, 4, false, 1, 0, 2>, sh);
@@ -1554,10 +1725,14 @@ extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hi
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, GR>, sh); \
         PC_LAUNCH((k_slice<DPL, NROWS, GR>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, mat_lds); }
     const int leanf = (D <= 64 && !mat_lds) ? slice_lean_functor(S) : 0;
+#define PC_SLICE_LAUNCHT(DPL, NROWS, GR) { \
+        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, GR, 1, 0, 0, 1>, sh); \
+        PC_LAUNCH((k_slice<DPL, NROWS, GR, 1, 0, 0, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); }
 #define PC_SLICE_LAUNCHL(DPL, NROWS, LN) { \
         if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, false, 1, 0, LN>, sh); \
         PC_LAUNCH((k_slice<DPL, NROWS, false, 1, 0, LN>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, mat_lds); }
 #define PC_SLICE_LAUNCH(DPL, NROWS) { if (DPL == 1 && leanf == 3) PC_SLICE_LAUNCHL(1, NROWS, 3) else if (DPL == 1 && leanf == 4) PC_SLICE_LAUNCHL(1, NROWS, 4) else if (DPL == 1 && leanf == 5) PC_SLICE_LAUNCHL(1, NROWS, 5) else \
+        if (table) { if (S->ngrade > 1 || S->seq_mode) PC_SLICE_LAUNCHT(DPL, NROWS, true) else PC_SLICE_LAUNCHT(DPL, NROWS, false) } else \
         if (S->ngrade > 1 || S->seq_mode) PC_SLICE_LAUNCH1(DPL, NROWS, true) else PC_SLICE_LAUNCH1(DPL, NROWS, false) }
     if (D <= 16) PC_SLICE_LAUNCH(1, 1)
     else if (D <= 32) PC_SLICE_LAUNCH(1, 2)
@@ -1566,8 +1741,21 @@ extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hi
     else if (D <= 256) PC_SLICE_LAUNCH(4, 4)
     else return 1;
 #undef PC_SLICE_LAUNCH
+#undef PC_SLICE_LAUNCHT
 #undef PC_SLICE_LAUNCHL
 #undef PC_SLICE_LAUNCH1
+    return 0;
+}
+
+// pchip_prior_transform: the device transform of the table in S->prior at n points (device pointers)
+extern "C" int pc_launch_prior_transform(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st)
+{
+    if (S->prior.kind != 2 || n < 1) return 1;
+    const size_t sh = sizeof(double) * S->D;
+    if (S->D <= 64) hipLaunchKernelGGL((k_prior_transform<1>), dim3(n), dim3(64), sh, st, *S, cubes, thetas);
+    else if (S->D <= 128) hipLaunchKernelGGL((k_prior_transform<2>), dim3(n), dim3(64), sh, st, *S, cubes, thetas);
+    else if (S->D <= 256) hipLaunchKernelGGL((k_prior_transform<4>), dim3(n), dim3(64), sh, st, *S, cubes, thetas);
+    else return 1;
     return 0;
 }
 #endif  // __HIPCC_RTC__

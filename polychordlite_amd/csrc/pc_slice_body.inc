@@ -191,8 +191,8 @@
         for (int k = 0; k < DPL; ++k) {
             const int dim = lane + 64 * k;
             ld.on[k] = dim < D;
-            const double lo = (ld.on[k] && S.prior.lo) ? S.prior.lo[dim] : 0.0;
-            const double hi = (ld.on[k] && S.prior.hi) ? S.prior.hi[dim] : 1.0;
+            const double lo = (PT == 0 && ld.on[k] && S.prior.lo) ? S.prior.lo[dim] : 0.0;
+            const double hi = (PT == 0 && ld.on[k] && S.prior.hi) ? S.prior.hi[dim] : 1.0;
             ld.lo[k] = lo; ld.span[k] = hi - lo;
             ld.mean[k] = (ld.on[k] && S.like.mean) ? S.like.mean[dim] : 0.0;
             x0[k] = ld.on[k] ? seed[dim] : 0.5;
@@ -203,9 +203,12 @@
 #if defined(SLICE_DBG) && SLICE_DBG == 2
     const long long kp2 = clock64();
 #endif
-    ChainCtx<DPL, NROWS> C{S, ld, lane, ybuf, 0, false, 0.0, 0.0, 0.0, 0.0};
-    const bool corr = lean2 || (!lean && !leanf && S.like.kind == PC_LIKE_CORR_GAUSSIAN);
-    C.quad = !leanf && (lean_any || ((corr || S.like.kind == PC_LIKE_GAUSSIAN) && !(S.ablate & 1)));
+    // PT: the chain's prior table, its constants read once (pc_table_load); every trial is then cube -> theta by pc_table_theta and a
+    // likelihood call -- no closed form along the chord, no carried products of the correlated Gaussian
+    ChainCtx<DPL, NROWS, PT> C{S, ld, lane, ybuf, 0, false, 0.0, 0.0, 0.0, 0.0};
+    if constexpr (PT != 0) pc_table_load<DPL>(S, lane, C.tb);
+    const bool corr = PT == 0 && (lean2 || (!lean && !leanf && S.like.kind == PC_LIKE_CORR_GAUSSIAN));
+    C.quad = PT == 0 && !leanf && (lean_any || ((corr || S.like.kind == PC_LIKE_GAUSSIAN) && !(S.ablate & 1)));
     C.qnorm = corr ? -((double)D * PC_LOG_TWO_PI + S.like.logdetcov) / 2.0 : S.like.norm;
     // correlated Gaussian: y = theta - mean and M.y travel with the chain (updated, not recomputed, at every
     // accepted point); the matrix is read from LDS when it fits

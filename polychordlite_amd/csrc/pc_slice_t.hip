@@ -707,7 +707,7 @@ namespace {
 extern "C" int pc_slice_t_ok(const PcState *S, int ncluster)
 {
     static const bool off = std::getenv("PC_SLICE_T_OFF") != nullptr;
-    if (off || ncluster != 1) return 0;
+    if (off || ncluster != 1 || S->prior.kind == 2) return 0;      // (a prior table: k_slice's general variants)
     if (S->D > 24 || S->ngrade > 1 || S->seq_mode || S->nhat_raw == nullptr || S->nr > 255) return 0;
     if (S->like.kind != PC_LIKE_GAUSSIAN || (S->ablate & 1)) return 0;
     const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16, tb = sizeof(double) * (size_t)S->nr * (S->D + 1);

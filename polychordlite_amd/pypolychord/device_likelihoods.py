@@ -90,3 +90,25 @@ class UniformPrior:
     def __call__(self, cube):
         cube = np.asarray(cube, dtype=np.float64)
         return np.broadcast_to(self.lo, cube.shape) + (np.broadcast_to(self.hi, cube.shape) - np.broadcast_to(self.lo, cube.shape)) * cube
+
+
+class TablePrior:
+    """The reference's prior types (priors.f90: uniform, log_uniform, power_uniform, gaussian, half_gaussian, exponential and the
+    sorted_ forms of uniform / gaussian / half_gaussian / exponential) as a table, one entry per parameter: (type, params) or
+    (type, block, params), e.g. [("gaussian", [0.5, 1.0])] * 4 + [("sorted_uniform", 1, [0, 1])] * 2.  `hyper`: the hypercube index
+    of every parameter (None: identity).  Evaluated inside the sampling kernels when the likelihood is a built-in; called like a
+    function it is the library's host function (polychord_hip_table_prior).  ValueError if the library refuses the table."""
+    symbol = "polychord_hip_table_prior"
+
+    def __init__(self, entries, hyper=None):
+        self.entries, self.hyper = list(entries), hyper
+
+    def configure(self, nDims):
+        if nDims != len(self.entries):
+            raise ValueError(f"TablePrior has {len(self.entries)} entries, the run {nDims} parameters")
+        api.set_table_prior(self.entries, self.hyper)
+
+    def __call__(self, cube):
+        cube = np.ascontiguousarray(cube, dtype=np.float64)
+        self.configure(cube.size)
+        return api.table_prior(cube)

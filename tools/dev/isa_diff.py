@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 instruction text of the kernels two builds of an object file have in common.
+
+    python3 tools/dev/isa_diff.py OLD.o NEW.o [--arch gfx950] [--drop-trailing-zero NAME ...]
+
+Unbundles the device code object of both files, disassembles them, and compares kernel by kernel (demangled names) the instruction
+text with addresses and encodings removed.  A template that gained a defaulted trailing parameter keeps its instruction stream but not
+its name: `--drop-trailing-zero k_slice` compares NEW's `k_slice<..., 0>` with OLD's `k_slice<...>`.  Prints one line per kernel that
+differs or exists on one side only, then a summary; exit status 1 if a common kernel differs.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
+
+
+def disassemble(obj, arch, tmp):
+    stem = os.path.join(tmp, os.path.basename(obj) + "." + str(len(os.listdir(tmp))))
+    fat, co = stem + ".fatbin", stem + ".co"
+    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj, os.devnull])
+    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--unbundle", "--input=" + fat, "--output=" + co,
+                           "--targets=hipv4-amdgcn-amd-amdhsa--" + arch])
+    text = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", "--demangle", co], text=True)
+    funcs, name = {}, None
+    for line in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
+        if m:
+            name = m.group(1)
+            funcs[name] = []
+            continue
+        if name is None or not line.startswith("\t"):
+            continue
+        ins = line.split("//")[0].strip()
+        ins = re.sub(r"<[^>]*>", "<sym>", ins)          # branch targets are printed as <symbol+offset>
+        if ins and ins != "...":
+            funcs[name].append(ins)
+    return funcs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("old"); ap.add_argument("new")
+    ap.add_argument("--arch", default="gfx950")
+    ap.add_argument("--drop-trailing-zero", nargs="*", default=[])
+    ap.add_argument("--show", type=int, default=0, help="print up to this many lines of the diff of every kernel that differs")
+    a = ap.parse_args()
+    with tempfile.TemporaryDirectory() as tmp:
+        old, new = disassemble(a.old, a.arch, tmp), disassemble(a.new, a.arch, tmp)
+    renamed = {}
+    for n, body in new.items():
+        k = n
+        for t in a.drop_trailing_zero:
+            m = re.match(r"^(.*\b" + re.escape(t) + r"<.*), 0>(\(.*)$", n)
+            if m and (m.group(1) + ">" + m.group(2)) in old:
+                k = m.group(1) + ">" + m.group(2)
+        renamed[k] = body
+    same = diff = 0
+    for n in sorted(old):
+        if n not in renamed:
+            print("only in OLD:", n)
+            continue
+        if old[n] == renamed[n]:
+            same += 1
+        else:
+            diff += 1
+            first = next((i for i, (x, y) in enumerate(zip(old[n], renamed[n])) if x != y), min(len(old[n]), len(renamed[n])))
+            print("DIFFERS: %s (%d / %d instructions, first difference at %d)" % (n, len(old[n]), len(renamed[n]), first))
+            if a.show:
+                import difflib
+                for l in list(difflib.unified_diff(old[n], renamed[n], "OLD", "NEW", n=1, lineterm=""))[:a.show]:
+                    print("    " + l)
+    only_new = [n for n in sorted(renamed) if n not in old]
+    for n in only_new:
+        print("only in NEW:", n)
+    print("%d kernels / functions identical, %d differ, %d only in NEW" % (same, diff, len(only_new)))
+    return 1 if diff else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
