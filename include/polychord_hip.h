@@ -265,6 +265,7 @@ enum { PCHIP_PATH_CONSUME_PAR = 0,      /* one cluster: the parallel contraction
        PCHIP_PATH_SUBCLUSTER_SPLITS = 18,   /* clusters those passes split */
        PCHIP_PATH_SOURCE_KERNELS = 19,      /* launches of run-time compiled sampling kernels (PCHIP_LIKE_SOURCE, settings.ablate bit 15) */
        PCHIP_PATH_DEVICE_PRIOR = 20,        /* sampling launches (live points, nurseries) that evaluated a prior table on the device */
+       PCHIP_PATH_SOURCE_TERMS = 21,        /* ... of those of slot 19, the launches whose kernels took the terms form of a source (pchip_source_create_terms) */
        PCHIP_PATH_COUNT = 24 };
 
 /* snapshot handed to the update hook: what the reference's file writers see at every update
@@ -323,6 +324,26 @@ int  pchip_abi_version(void);
 #define PCHIP_SOURCE_MAX_DERIVED 32
 int  pchip_source_create(const char *source, const char *options, const double *data, long ndata);
 void pchip_source_destroy(int handle);
+/* The terms form of a device source, for a likelihood that is a SUM OVER DATA (a chi-square, a fit, a product of per-event densities).
+ * Instead of pchip_loglikelihood the source defines
+ *     __device__ double pchip_logl_term(const double *theta, int nDims, const double *data, long ndata, long i);
+ *     __device__ double pchip_logl_finish(double sum, const double *theta, double *phi, int nDims, int nDerived,
+ *                                         const double *data, long ndata);
+ * term(i), 0 <= i < nterms, is called by ONE lane of the wavefront per i (lanes take consecutive i: lay records out as a structure of
+ * arrays and the loads coalesce); finish gets the finished sum, returns logL and writes all nDerived derived parameters -- cheap, no
+ * loop over the data.  The sum has one defined order: lane l adds term(l), term(l + 64), ... in turn to 0.0 (plain IEEE adds of the
+ * returned values, never fused with arithmetic inside the term), and the 64 partial sums are added in a balanced pairwise tree over
+ * the lanes in lane order ((s0 + s1) + (s2 + s3) ... within rows of sixteen lanes, then (r0 + r1) + (r2 + r3)).  Contract: term is
+ * pure, may read theta and data, must not synchronise; finish is pure and must not assume which lane calls it nor that all lanes see
+ * the same theta (the derived parameters of a chain's points are written lane = point, from the sum kept when each was accepted: the
+ * data are never walked a second time).  One sum per evaluation.  Same options rule, data block, handle space and
+ * pchip_source_destroy as pchip_source_create; nterms >= 1.  pchip_like.kind stays PCHIP_LIKE_SOURCE: the handle knows its form;
+ * pchip_result.path[PCHIP_PATH_SOURCE_TERMS] counts the launches that took it. */
+int  pchip_source_create_terms(const char *source, const char *options, const double *data, long ndata, long nterms);
+/* A source likelihood (either form) at n points, thetas[n][nDims] -> logL[n], phi[n][nDerived] (host arrays; phi may be NULL when
+ * nDerived is 0): one wavefront a point, through the evaluation code of the sampling kernels.  For tests, and for users checking their
+ * source against a host version.  0, or 1 with a message in polychord_hip_last_error(), 2 no device / HIP error, 3 nDims > 256. */
+int  pchip_source_eval(int handle, const double *thetas, long n, int nDims, int nDerived, double *logL, double *phi);
 unsigned long pchip_sizeof(const char *struct_name);
 void pchip_settings_default(pchip_settings *s, int nDims, int nDerived);
 int  pchip_device_count(void);

@@ -80,7 +80,7 @@ class Result(C.Structure):
 # pchip_result.path[]: launches per kernel variant (include/polychord_hip.h PCHIP_PATH_*)
 PATH_NAMES = ("consume_par", "consume_cl", "consume_general", "consume_fast", "killoff_par", "killoff_cl", "killoff_general",
               "killoff_fast", "update_fused", "update_steps", "slice_wave", "slice_lane", "nn_lists", "nn_fallbacks", "pool_mode",
-              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits", "source_kernels", "device_prior")
+              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits", "source_kernels", "device_prior", "source_terms")
 
 
 _lib = None
@@ -116,6 +116,10 @@ def load():
     lib.polychord_hip_ini_sub_clustering.restype = C.c_int
     lib.pchip_source_create.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long]
     lib.pchip_source_create.restype = C.c_int
+    lib.pchip_source_create_terms.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long]
+    lib.pchip_source_create_terms.restype = C.c_int
+    lib.pchip_source_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_long, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.pchip_source_eval.restype = C.c_int
     lib.pchip_source_destroy.argtypes = [C.c_int]
     lib.pchip_source_destroy.restype = None
     lib.pchip_rtc_embedded_source.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
@@ -146,17 +150,31 @@ def dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def source_create(source, options=(), data=None):
-    """handle of a likelihood written as HIP device source (pchip_source_create); RuntimeError with the compiler's log if it does not compile"""
+def source_create(source, options=(), data=None, nterms=None):
+    """handle of a likelihood written as HIP device source (pchip_source_create); RuntimeError with the compiler's log if it does not compile.
+    nterms given: the terms form (pchip_source_create_terms) -- the source defines pchip_logl_term and pchip_logl_finish, the sum has nterms terms"""
     lib = load()
     d = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
     opts = " ".join(options) if not isinstance(options, str) else options
-    h = lib.pchip_source_create(source.encode(), opts.encode(), dptr(d) if d is not None and d.size else None,
-                                0 if d is None else int(d.size))
+    args = (source.encode(), opts.encode(), dptr(d) if d is not None and d.size else None, 0 if d is None else int(d.size))
+    h = lib.pchip_source_create(*args) if nterms is None else lib.pchip_source_create_terms(*args, int(nterms))
     if h <= 0:
         log = lib.polychord_hip_last_error()
         raise RuntimeError("device source does not compile:\n" + (log.decode(errors="replace") if log else "(no log)"))
     return h
+
+
+def source_eval(handle, thetas, nDerived=0):
+    """pchip_source_eval: a source likelihood (either form) at the rows of `thetas` ([n][nDims]), on the device; (logL [n], phi [n][nDerived])"""
+    lib = load()
+    t = np.ascontiguousarray(np.atleast_2d(thetas), dtype=np.float64)
+    logL = np.empty(t.shape[0])
+    phi = np.empty((t.shape[0], nDerived))
+    rc = lib.pchip_source_eval(handle, dptr(t), t.shape[0], t.shape[1], nDerived, dptr(logL), dptr(phi) if nDerived > 0 else None)
+    if rc != 0:
+        msg = lib.polychord_hip_last_error()
+        raise RuntimeError(f"pchip_source_eval failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
+    return logL, phi
 
 
 def prior_table(entries, hyper=None):

@@ -40,6 +40,8 @@ int pc_launch_generate_live(const PcState *, int, int, double *, double *, hipSt
 int pc_rtc_wanted(const PcState *);
 const char *pc_rtc_error(void);
 int pc_rtc_source_data(int, const double **, long long *);
+long pc_rtc_source_terms(int);
+int pc_launch_source_eval(const PcState *, int, const double *, double *, double *, hipStream_t);
 int pc_launch_nhats(const PcState *, unsigned, int, hipStream_t);
 int pc_nhats_splittable(const PcState *);
 int pc_launch_nhats_part(const PcState *, unsigned, int, int, hipStream_t, int);
@@ -812,6 +814,7 @@ struct Engine {
     double *c_Sm = nullptr; int *c_pts = nullptr, *c_gidx = nullptr, *c_knn = nullptr, *c_lab = nullptr, *c_out = nullptr, *c_cnt = nullptr;
     unsigned *c_olduid = nullptr; int c_cap = 0;
     long nsplits = 0; int ncluster_peak = 1;
+    bool src_terms = false;                    // a source likelihood in the terms form (pchip_source_create_terms)
     long path[PCHIP_PATH_COUNT] = {};          // launches per kernel variant (pchip_result.path): counted where the choice is made
     Timing tm;
     KTimer kt;
@@ -938,6 +941,7 @@ struct Engine {
             if (nDer > PC_SRC_MAX_DERIVED) engine_fail(PC_RC_SETTINGS, "a device source likelihood writes at most %d derived parameters, not %d", PC_SRC_MAX_DERIVED, nDer);
             if (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE) engine_fail(PC_RC_SETTINGS, "a device source likelihood needs a device prior (the uniform box), not a host-callback prior");
             S.src_id = like.source;
+            src_terms = pc_rtc_source_terms(like.source) > 0;
             if (n > 0) { d_src = dalloc<double>((size_t)n); upload(d_src, h, sizeof(double) * (size_t)n); S.src_data = d_src; S.src_ndata = n; }
         }
         if (like.kind == PC_LIKE_CORR_GAUSSIAN) {
@@ -2030,6 +2034,7 @@ struct Engine {
         bool direct = true;
         while (have < nprior) {
             if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
+            if (src_terms) path[PCHIP_PATH_SOURCE_TERMS]++;
             if (S.prior.kind == PCHIP_PRIOR_TABLE) path[PCHIP_PATH_DEVICE_PRIOR]++;
             if (pc_launch_generate_live(&S, attempt0, nprior, rows, rl, st)) {
                 if (pc_rtc_wanted(&S) && pc_rtc_error()) engine_fail(PC_RC_SETTINGS, "%.480s", pc_rtc_error());
@@ -2061,6 +2066,7 @@ struct Engine {
             for (; S.ngrade <= 1; ++a) {
                 double l1 = 0.0;
                 if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
+                if (src_terms) path[PCHIP_PATH_SOURCE_TERMS]++;
                 if (S.prior.kind == PCHIP_PRIOR_TABLE) path[PCHIP_PATH_DEVICE_PRIOR]++;
                 (void)pc_launch_generate_live(&S, a, 1, rows, rl, st);
                 HIPCHK(hipMemcpyAsync(&l1, rl, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2438,7 +2444,7 @@ struct Engine {
                 co->rec(CK_SLICE_G, S, {}, {(long long)B, fused_slice ? 1LL : 0LL}, {(int)batch, 0, 0, fused_slice ? bases_seq : 0});
                 if (fused_slice && co->st2 && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
             }
-            else if ((path[PCHIP_PATH_SLICE_WAVE]++, path[PCHIP_PATH_SOURCE_KERNELS] += pc_rtc_wanted(&S) ? 1 : 0, path[PCHIP_PATH_DEVICE_PRIOR] += S.prior.kind == PCHIP_PRIOR_TABLE ? 1 : 0, co ? (co->flush(), co->wait_next(), 0) : 0) || (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st))) {
+            else if ((path[PCHIP_PATH_SLICE_WAVE]++, path[PCHIP_PATH_SOURCE_KERNELS] += pc_rtc_wanted(&S) ? 1 : 0, path[PCHIP_PATH_SOURCE_TERMS] += src_terms ? 1 : 0, path[PCHIP_PATH_DEVICE_PRIOR] += S.prior.kind == PCHIP_PRIOR_TABLE ? 1 : 0, co ? (co->flush(), co->wait_next(), 0) : 0) || (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st))) {
                 if (pc_rtc_wanted(&S) && pc_rtc_error()) { std::fprintf(stderr, "polychord_hip: %s\n", pc_rtc_error()); r_rc = 1; return false; }
                 std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false;
             }
@@ -3325,6 +3331,37 @@ int pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const doub
     }
     if (rc) (void)hipGetLastError();
     (void)hipFree(d_tp); (void)hipFree(d_ti); (void)hipFree(d_c); (void)hipFree(d_t);
+    return rc;
+}
+
+// a source likelihood alone at n points (either form of source): the handle's run-time module, k_source_eval, one wavefront a point
+int pchip_source_eval(int handle, const double *thetas, long n, int nDims, int nDerived, double *logL, double *phi)
+{
+    const double *h = nullptr; long long nd = 0;
+    if (pc_rtc_source_data(handle, &h, &nd)) { pc_abi_set_last_error(("pchip_source_eval: device source handle " + std::to_string(handle) + " does not exist").c_str()); return 1; }
+    if (!thetas || !logL || n < 1 || n > 0x7fffffffL || nDims < 1 || nDerived < 0 || (nDerived > 0 && !phi)) {
+        pc_abi_set_last_error("pchip_source_eval: n >= 1 points, nDims >= 1, arrays for theta, logL and (nDerived > 0) phi"); return 1;
+    }
+    if (nDerived > PC_SRC_MAX_DERIVED) { pc_abi_set_last_error(("pchip_source_eval: a device source likelihood writes at most " + std::to_string(PC_SRC_MAX_DERIVED) + " derived parameters").c_str()); return 1; }
+    if (nDims > 256) return 3;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
+    double *d_src = nullptr, *d_t = nullptr, *d_l = nullptr, *d_p = nullptr;
+    const size_t nt = sizeof(double) * (size_t)n * nDims, np = sizeof(double) * (size_t)n * (nDerived > 0 ? nDerived : 1);
+    int rc = 2;
+    pc_abi_set_last_error(nullptr);
+    if ((nd == 0 || (hipMalloc(&d_src, sizeof(double) * (size_t)nd) == hipSuccess && hipMemcpy(d_src, h, sizeof(double) * (size_t)nd, hipMemcpyHostToDevice) == hipSuccess)) &&
+        hipMalloc(&d_t, nt) == hipSuccess && hipMalloc(&d_l, sizeof(double) * (size_t)n) == hipSuccess && hipMalloc(&d_p, np) == hipSuccess &&
+        hipMemcpy(d_t, thetas, nt, hipMemcpyHostToDevice) == hipSuccess) {
+        PcState S;
+        std::memset(&S, 0, sizeof(S));
+        S.D = nDims; S.nDer = nDerived; S.like.kind = PC_LIKE_SOURCE; S.src_id = handle; S.src_data = d_src; S.src_ndata = nd;
+        if (pc_launch_source_eval(&S, (int)n, d_t, d_l, d_p, nullptr)) { rc = 1; pc_abi_set_last_error(pc_rtc_error() ? pc_rtc_error() : "pchip_source_eval: the launch failed"); }
+        else if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(logL, d_l, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
+                 (nDerived == 0 || hipMemcpy(phi, d_p, np, hipMemcpyDeviceToHost) == hipSuccess)) rc = 0;
+    }
+    if (rc == 2) (void)hipGetLastError();
+    (void)hipFree(d_src); (void)hipFree(d_t); (void)hipFree(d_l); (void)hipFree(d_p);
     return rc;
 }
 

@@ -6,7 +6,12 @@
 // the bodies it includes, embedded when the library is built: pc_rtc_sources.inc), for the device a run is on.  The launchers of
 // pc_sample.hip choose a kernel variant and its launch shape as they do for the built-ins, and hand the variant's name to pc_rtc_launch,
 // which instantiates it (hiprtcAddNameExpression), loads the code object once per device and launches it with the same arguments and
-// the same dynamic LDS.  settings.ablate bit 15 sends the built-in kinds the same way (a module without a user source): the test that
+// the same dynamic LDS.
+//
+// The terms form (pchip_source_create_terms): the source defines pchip_logl_term (the i-th term of a sum over the data, one lane per i) and
+// pchip_logl_finish (logL and the derived parameters from the finished sum) instead.  The form and the number of terms reach the kernels
+// as #defines in front of the library's text in that handle's unit (PCHIP_USER_TERMS, PCHIP_SRC_NTERMS): pc_sample.hip's wave-cooperative
+// evaluation is compiled in their place only.  settings.ablate bit 15 sends the built-in kinds the same way (a module without a user source): the test that
 // this path is the static kernel.
 //
 // libhiprtc is opened with dlopen: without it the library loads and the built-ins run; a source run then fails with a message.
@@ -63,6 +68,7 @@ struct Hiprtc {
 struct Source {
     std::string text;                      // the user's source, behind the #define lines of its options
     std::vector<double> data;
+    long nterms = 0;                       // > 0: the terms form (pchip_logl_term / pchip_logl_finish), the sum's length
 };
 
 // a code object of one kernel variant for one architecture: compiled once, loaded on every device of that architecture
@@ -149,9 +155,11 @@ int compile(const Source *s, const std::string &unit, const std::vector<std::str
 }
 
 // the translation unit of the sampling kernels: the library's kernels (pc_sample.hip declares pchip_loglikelihood under PCHIP_USER_SOURCE),
-// then the user's text -- its macros and pragmas reach nothing of the library's
+// then the user's text -- its macros and pragmas reach nothing of the library's.  A terms handle: its form and its loop bound in front.
 std::string kernel_unit(const Source *s)
 {
+    if (s && s->nterms > 0)
+        return "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
     return s ? std::string("#define PCHIP_USER_SOURCE 1\n#include \"pc_sample.hip\"\n#include \"") + USER_NAME + "\"\n"
              : std::string("#include \"pc_sample.hip\"\n");
 }
@@ -161,6 +169,13 @@ const char *const PROBE_UNIT =
     "__device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
     "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, double *out)\n"
     "{ out[0] = pchip_loglikelihood(th, phi, nDims, nDerived, data, ndata); }\n"
+    "#include \"pchip_user_source.h\"\n";
+// ... and of pchip_source_create_terms: both functions of the terms form (a source that lacks one fails at the link of this unit, by name)
+const char *const PROBE_UNIT_TERMS =
+    "__device__ double pchip_logl_term(const double *theta, int nDims, const double *data, long ndata, long i);\n"
+    "__device__ double pchip_logl_finish(double sum, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
+    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
+    "{ out[0] = pchip_logl_finish(pchip_logl_term(th, nDims, data, ndata, i), th, phi, nDims, nDerived, data, ndata); }\n"
     "#include \"pchip_user_source.h\"\n";
 
 std::string strip_parens(const char *expr)
@@ -261,9 +276,18 @@ int pc_rtc_source_data(int id, const double **data, long long *n)
     return 0;
 }
 
-// pchip_source_create: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
-// Returns the handle (> 0), or -1 with the compiler's log in `log`.
-int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, std::string *log)
+// the number of terms of a terms-form handle; 0: the plain form, or no such handle
+long pc_rtc_source_terms(int id)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    auto it = G.src.find(id);
+    return it == G.src.end() ? 0 : it->second->nterms;
+}
+
+// pchip_source_create[_terms]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
+// nterms > 0: the terms form.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
+int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, std::string *log)
 {
     if (!source) { *log = "pchip_source_create: no source"; return -1; }
     if (ndata < 0 || (ndata > 0 && !data)) { *log = "pchip_source_create: ndata > 0 needs a data block"; return -1; }
@@ -273,6 +297,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     auto s = std::make_shared<Source>();
     s->text = defs + "#line 1\n" + source;
     if (ndata > 0) s->data.assign(data, data + ndata);
+    s->nterms = nterms;
     std::string arch = "gfx950";
     int dev = 0, ndev = 0;
     if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&dev) == hipSuccess) {
@@ -281,7 +306,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     }
     (void)hipGetLastError();
     std::vector<char> code; std::vector<std::string> lowered;
-    if (compile(s.get(), PROBE_UNIT, { "pchip_probe" }, arch, code, lowered, *log)) return -1;
+    if (compile(s.get(), nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT, { "pchip_probe" }, arch, code, lowered, *log)) return -1;
     Registry &G = reg();
     std::lock_guard<std::mutex> g(G.m);
     const int id = G.next++;
@@ -297,7 +322,17 @@ extern "C" void pc_abi_set_last_error(const char *msg);
 extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata)
 {
     std::string log;
-    const int id = pc_rtc_source_create(source, options, data, ndata, &log);
+    const int id = pc_rtc_source_create(source, options, data, ndata, 0, &log);
+    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
+    return id;
+}
+
+extern "C" int pchip_source_create_terms(const char *source, const char *options, const double *data, long ndata, long nterms)
+{
+    std::string log;
+    int id = -1;
+    if (nterms < 1) log = "pchip_source_create_terms: nterms = " + std::to_string(nterms) + " -- the sum needs at least one term (nterms >= 1)";
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, &log);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }

@@ -129,6 +129,97 @@ __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDim
 template <int DPL, int NROWS>
 __device__ __forceinline__ double wsum(double v) { return (DPL > 1) ? wave_sum<4>(v) : wave_sum<NROWS>(v); }
 
+#ifdef PCHIP_USER_TERMS
+// The terms form of a user source (pchip_source_create_terms; pc_rtc.hip defines PCHIP_USER_TERMS and PCHIP_SRC_NTERMS in front of this
+// text in such a handle's unit): the likelihood is finish(sum of PCHIP_SRC_NTERMS terms), and the wavefront SHARES the loop over the
+// terms instead of every lane running all of it.  The sum has one defined order (the parity tests rest on it):
+//   lane l:  s_l = 0;  for (i = l; i < nterms; i += 64) s_l = s_l + term(i)       -- a plain IEEE add of the returned value
+//   wave:    wave_sum<4> of the 64 partials: a balanced pairwise tree over the lanes in lane order within each row of sixteen,
+//            then (r0 + r1) + (r2 + r3); a lane without a term contributes 0.0 and takes part in the reduction
+// The term's value passes an empty asm before it is added: hipcc contracts by default (-ffp-contract=fast, on whatever the optimiser
+// has made of the code), and the add must not fuse with a multiply at the end of the user's inlined term.
+// Lane-consecutive i: a data block laid out as a structure of arrays is read with coalesced loads.  No LDS traffic and no barrier in
+// the loop (theta is read from the LDS copy behind the one barrier a source evaluation always had).
+__device__ double pchip_logl_term(const double *theta, int nDims, const double *data, long ndata, long i);
+__device__ double pchip_logl_finish(double sum, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
+
+// (four terms a step where the lane has them -- their loads are in flight together, a lane's wait for the data is what a short term
+//  costs --, the adds one after the other in the order of i)
+__device__ __forceinline__ double pc_terms_sum(const PcState &S, const double *theta, int lane)
+{
+    constexpr long N = (long)(PCHIP_SRC_NTERMS);
+    double s = 0.0;
+    long i = lane;
+    for (; i + 192 < N; i += 256) {
+        double t[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) t[u] = pchip_logl_term(theta, S.D, S.src_data, (long)S.src_ndata, i + 64 * u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { asm volatile("" : "+v"(t[u])); s = s + t[u]; }
+    }
+    for (; i < N; i += 64) {
+        double t = pchip_logl_term(theta, S.D, S.src_data, (long)S.src_ndata, i);
+        asm volatile("" : "+v"(t));
+        s = s + t;
+    }
+    return wave_sum<4>(s);
+}
+// two points in ONE pass over the data, an accumulator each: every sum in the order above, so its bits do not depend on whether the point
+// was evaluated alone or in a pair
+__device__ __forceinline__ void pc_terms_sum2(const PcState &S, const double *thA, const double *thB, int lane, double &sA, double &sB)
+{
+    constexpr long N = (long)(PCHIP_SRC_NTERMS);
+    double a = 0.0, b = 0.0;
+    long i = lane;
+    for (; i + 64 < N; i += 128) {
+        double tA[2], tB[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            tA[u] = pchip_logl_term(thA, S.D, S.src_data, (long)S.src_ndata, i + 64 * u);
+            tB[u] = pchip_logl_term(thB, S.D, S.src_data, (long)S.src_ndata, i + 64 * u);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) { asm volatile("" : "+v"(tA[u])); asm volatile("" : "+v"(tB[u])); a = a + tA[u]; b = b + tB[u]; }
+    }
+    for (; i < N; i += 64) {
+        double tA = pchip_logl_term(thA, S.D, S.src_data, (long)S.src_ndata, i);
+        double tB = pchip_logl_term(thB, S.D, S.src_data, (long)S.src_ndata, i);
+        asm volatile("" : "+v"(tA));
+        asm volatile("" : "+v"(tB));
+        a = a + tA; b = b + tB;
+    }
+    sA = wave_sum<4>(a); sB = wave_sum<4>(b);
+}
+// logL of theta (uniform over the wave) and, in `sum`, the finished sum it came from: whoever accepts the point keeps it, and the
+// derived parameters are finish(sum, theta) again -- never a second walk over the data
+template <int DPL>
+__device__ __forceinline__ double like_eval_terms(const PcState &S, const double (&th)[DPL], const LaneDims<DPL> &ld, int lane, double *ybuf,
+                                                  double &sum)
+{
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
+    __syncthreads();                              // one wave per workgroup: cheap
+    sum = pc_terms_sum(S, ybuf, lane);
+    double phi[PC_SRC_MAX_DERIVED];
+    const double l = pchip_logl_finish(sum, ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+    __syncthreads();
+    return l;
+}
+// all nDerived values of an accepted point from its sum (lane 0 writes them to out)
+template <int DPL>
+__device__ __forceinline__ void like_phi_terms(const PcState &S, const double (&th)[DPL], const LaneDims<DPL> &ld, int lane, double *ybuf,
+                                               double sum, double *out)
+{
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
+    __syncthreads();
+    double phi[PC_SRC_MAX_DERIVED];
+    (void)pchip_logl_finish(sum, ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+    if (lane == 0) for (int e = 0; e < S.nDer; ++e) out[e] = phi[e];
+    __syncthreads();
+}
+#endif
+
 // returns logL of theta (uniform over the wave).  ybuf: per-wave LDS scratch of >= D doubles.
 // (KIND >= 0: the likelihood is known when the kernel is compiled -- k_slice's LEAN variants -- and the other branches are not there)
 template <int DPL, int NROWS, int KIND = -1>
@@ -163,7 +254,11 @@ __device__ __forceinline__ double like_eval(const PcState &S, const double (&th)
             }
         s1 = wsum<DPL, NROWS>(s1); s2 = wsum<DPL, NROWS>(s2);
         return pc_logaddexp(L.norm - s1 / 2.0, L.norm - s2 / 2.0) - 0.6931471805599453;
-#ifdef PCHIP_USER_SOURCE
+#ifdef PCHIP_USER_TERMS
+    } else if (kind == PC_LIKE_SOURCE) {          // the terms form: the wave shares the loop over the terms (like_eval_terms)
+        double sum;
+        return like_eval_terms<DPL>(S, th, ld, lane, ybuf, sum);
+#elif defined(PCHIP_USER_SOURCE)
     } else if (kind == PC_LIKE_SOURCE) {          // the user's function (pc_rtc.hip): every lane evaluates it on the same LDS copy of theta,
 #pragma unroll                                    // so the result is wave-uniform without a broadcast
         for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
@@ -262,11 +357,18 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
         pc_table_load<DPL>(S, lane, lt);
         pc_table_theta<DPL>(lt, cube, th, lane, ybuf);
     }
+#ifdef PCHIP_USER_TERMS
+    double tsum = 0.0;
+    const double logL = S.like.kind == PC_LIKE_SOURCE ? like_eval_terms<DPL>(S, th, ld, lane, ybuf, tsum) : like_eval<DPL, 4>(S, th, ld, lane, ybuf);
+#else
     const double logL = like_eval<DPL, 4>(S, th, ld, lane, ybuf);
+#endif
     double phi0, phi1;
     like_phi<DPL, 4>(S, th, ld, lane, phi0, phi1);
     double *row = rows + (size_t)a * nT;
-#ifdef PCHIP_USER_SOURCE
+#ifdef PCHIP_USER_TERMS
+    if (S.like.kind == PC_LIKE_SOURCE && S.nDer > 0) like_phi_terms<DPL>(S, th, ld, lane, ybuf, tsum, row + S.d0);
+#elif defined(PCHIP_USER_SOURCE)
     if (S.like.kind == PC_LIKE_SOURCE && S.nDer > 0) like_phi_source<DPL>(S, th, ld, lane, ybuf, row + S.d0);
 #endif
 #pragma unroll
@@ -301,6 +403,37 @@ __global__ __launch_bounds__(64) void k_prior_transform(PcState S, const double 
 #pragma unroll
     for (int k = 0; k < DPL; ++k) if (lane + 64 * k < D) thetas[base + lane + 64 * k] = th[k];
 }
+
+#ifdef PCHIP_USER_SOURCE
+// a source likelihood alone (pchip_source_eval: tests, and users checking their source): one wave a point, through the evaluation code of
+// the sampling kernels -- like_eval and the derived parameters as k_generate_live writes them -- for both forms of source
+template <int DPL>
+__global__ __launch_bounds__(64) void k_source_eval(PcState S, const double *thetas /* [n][D] */, double *logL /* [n] */, double *phi /* [n][nDer] */)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double *ybuf = (double *)smem;
+    const int lane = threadIdx.x, D = S.D;
+    const size_t base = (size_t)blockIdx.x * D;
+    LaneDims<DPL> ld;
+    double th[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) {
+        ld.on[k] = lane + 64 * k < D;
+        ld.lo[k] = 0.0; ld.span[k] = 1.0; ld.mean[k] = 0.0;
+        th[k] = ld.on[k] ? thetas[base + lane + 64 * k] : 0.0;
+    }
+    double *out = phi + (size_t)blockIdx.x * S.nDer;
+#ifdef PCHIP_USER_TERMS
+    double sum;
+    const double l = like_eval_terms<DPL>(S, th, ld, lane, ybuf, sum);
+    if (S.nDer > 0) like_phi_terms<DPL>(S, th, ld, lane, ybuf, sum, out);
+#else
+    const double l = like_eval<DPL, 4>(S, th, ld, lane, ybuf);
+    if (S.nDer > 0) like_phi_source<DPL>(S, th, ld, lane, ybuf, out);
+#endif
+    if (lane == 0) logL[blockIdx.x] = l;
+}
+#endif
 
 // ------------------------------------------------------------------------------------------
 // K0: seed choice + random orthonormal bases + whitening
@@ -1252,6 +1385,10 @@ struct ChainCtx {
     // one evaluation (calculate.f90:44).
     bool quad;
     double qa, qb, qc, qnorm;
+#ifdef PCHIP_USER_TERMS
+    double tsum;        // the terms form: the sum of the last point eval_at evaluated -- the accepted point's, when a slice ends
+    double *ybuf2;      // ... and LDS for a second theta (eval_pair: both bracket ends in one pass over the data)
+#endif
 };
 // PT = 1: the same with the chain's prior table behind it (a non-linear prior has no closed form along the chord: quad stays false).
 // A specialisation, so that the box's context -- and with it every kernel of a box run -- is what it was.
@@ -1265,7 +1402,38 @@ struct ChainCtx<DPL, NROWS, 1> {
     bool quad;
     double qa, qb, qc, qnorm;
     LaneTable<DPL> tb;
+#ifdef PCHIP_USER_TERMS
+    double tsum;
+    double *ybuf2;
+#endif
 };
+
+#ifdef PCHIP_USER_TERMS
+// the two ends of a bracket (thA / thB: theta of the ends that are inside the cube, inA / inB wave-uniform): both in one pass over the
+// data when both are inside, each counted as calculate.f90:44 counts it
+template <int DPL, int NROWS, int PT>
+__device__ __forceinline__ void like_pair_terms(ChainCtx<DPL, NROWS, PT> &C, const double (&thA)[DPL], const double (&thB)[DPL], bool inA, bool inB,
+                                                double &lA, double &lB)
+{
+    const PcState &S = C.S;
+    lA = S.logzero; lB = S.logzero;
+    double sum;
+    if (inA && inB) {
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) if (C.ld.on[k]) { C.ybuf[C.lane + 64 * k] = thA[k]; C.ybuf2[C.lane + 64 * k] = thB[k]; }
+        __syncthreads();
+        double sA, sB;
+        pc_terms_sum2(S, C.ybuf, C.ybuf2, C.lane, sA, sB);
+        double phi[PC_SRC_MAX_DERIVED];
+        lA = pchip_logl_finish(sA, C.ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+        lB = pchip_logl_finish(sB, C.ybuf2, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+        __syncthreads();
+    } else if (inA) lA = like_eval_terms<DPL>(S, thA, C.ld, C.lane, C.ybuf, sum);
+    else if (inB) lB = like_eval_terms<DPL>(S, thB, C.ld, C.lane, C.ybuf, sum);
+    if (inA && lA > S.logzero) C.nlike++;
+    if (inB && lB > S.logzero) C.nlike++;
+}
+#endif
 
 // calculate_point (calculate.f90:6-50) at x0 + t*nh; leaves cube/theta of the trial in registers
 template <int DPL, int NROWS, int KIND = -1, int PT = 0>
@@ -1303,7 +1471,12 @@ __device__ __forceinline__ double eval_at(ChainCtx<DPL, NROWS, PT> &C, const dou
 #pragma unroll
     for (int k = 0; k < DPL; ++k) th[k] = C.ld.lo[k] + C.ld.span[k] * cube[k];
     }
+#ifdef PCHIP_USER_TERMS     // (the sum stays with the chain: the derived parameters of the point a slice accepts are finish(sum))
+    const double logL = (KIND < 0 && C.S.like.kind == PC_LIKE_SOURCE) ? like_eval_terms<DPL>(C.S, th, C.ld, C.lane, C.ybuf, C.tsum)
+                                                                      : like_eval<DPL, NROWS, KIND>(C.S, th, C.ld, C.lane, C.ybuf);
+#else
     const double logL = like_eval<DPL, NROWS, KIND>(C.S, th, C.ld, C.lane, C.ybuf);
+#endif
     if (logL > C.S.logzero) C.nlike++;
     return logL;
 }
@@ -1328,6 +1501,14 @@ __device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS, PT> &C, const dou
             if (C.ld.on[k]) { outA |= (cA[k] < 0.0) | (cA[k] > 1.0); outB |= (cB[k] < 0.0) | (cB[k] > 1.0); }
         }
         const bool oa = __ballot(outA) != 0ull, ob = __ballot(outB) != 0ull;
+#ifdef PCHIP_USER_TERMS
+        if (kind == PC_LIKE_SOURCE) {
+            if (!oa) pc_table_theta<DPL>(C.tb, cA, thA, C.lane, C.ybuf);
+            if (!ob) pc_table_theta<DPL>(C.tb, cB, thB, C.lane, C.ybuf);
+            like_pair_terms<DPL, NROWS, PT>(C, thA, thB, !oa, !ob, lA, lB);
+            return;
+        }
+#endif
         lA = C.S.logzero; lB = C.S.logzero;
         if (!oa) {
             pc_table_theta<DPL>(C.tb, cA, thA, C.lane, C.ybuf);
@@ -1368,7 +1549,9 @@ __device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS, PT> &C, const dou
             thA[k] = C.ld.lo[k] + C.ld.span[k] * cA; thB[k] = C.ld.lo[k] + C.ld.span[k] * cB;
         }
         const bool oa = __ballot(outA) != 0ull, ob = __ballot(outB) != 0ull;
-#ifdef PCHIP_USER_SOURCE
+#ifdef PCHIP_USER_TERMS
+        if (kind == PC_LIKE_SOURCE) { like_pair_terms<DPL, NROWS, PT>(C, thA, thB, !oa, !ob, lA, lB); return; }
+#elif defined(PCHIP_USER_SOURCE)
         if (kind == PC_LIKE_SOURCE) {
             // the user's function only ever sees points inside the prior box (calculate.f90:36-38 tests the cube first); oa / ob are
             // wave-uniform ballots, so the barriers inside like_eval stay uniform
@@ -1471,6 +1654,12 @@ template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, d
 }
 #define PC_LAUNCH(K, G, B, SH, ST, ...) do { if (pc_rtc_wanted(S)) { if (pc_rtc_go(S, #K, G, B, SH, ST, __VA_ARGS__)) return 1; } \
                                              else hipLaunchKernelGGL(K, G, B, SH, ST, __VA_ARGS__); } while (0)
+// the terms form of a source evaluates the two ends of a bracket in one pass over the data: LDS for the second theta behind the chain's block
+extern "C" long pc_rtc_source_terms(int id);
+static size_t pc_terms_lds(const PcState *S)
+{
+    return (S->like.kind == PC_LIKE_SOURCE && pc_rtc_source_terms(S->src_id) > 0) ? sizeof(double) * (size_t)S->D : 0;
+}
 extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL,
                                        hipStream_t st)
 {
@@ -1600,7 +1789,7 @@ extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchai
     const size_t tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
     const int phi_lds = (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
     const int D = S->D, FWv = D <= 8 ? 8 : (D <= 16 ? 16 : 24);
-    const size_t sh = sh0 + (phi_lds ? tb : 0) + sizeof(double) * ((size_t)FWv * D + (size_t)S->nr * (D + 2));   // + L, directions, widths
+    const size_t sh = sh0 + (phi_lds ? tb : 0) + sizeof(double) * ((size_t)FWv * D + (size_t)S->nr * (D + 2)) + pc_terms_lds(S);   // + L, directions, widths
     if (sh > 150 * 1024) return 1;
     static const bool lean_off = std::getenv("PC_SLICE_LEAN_OFF") != nullptr;
     const bool table = S->prior.kind == 2;
@@ -1699,7 +1888,7 @@ extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hi
     const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16;     // ybuf + two int decks
     const size_t tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
     const int phi_lds = (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
-    size_t sh = sh0 + (phi_lds ? tb : 0);
+    size_t sh = sh0 + (phi_lds ? tb : 0) + pc_terms_lds(S);
     const size_t mb = sizeof(double) * (size_t)S->D * S->D;
     const bool table = S->prior.kind == 2;      // (a prior table: every likelihood through like_eval, no matrix in LDS)
     const int mat_lds = (!table && S->like.kind == PC_LIKE_CORR_GAUSSIAN && S->nhat_Ms == nullptr && sh + mb <= 150 * 1024) ? 1 : 0;
@@ -1757,5 +1946,16 @@ extern "C" int pc_launch_prior_transform(const PcState *S, int n, const double *
     else if (S->D <= 256) hipLaunchKernelGGL((k_prior_transform<4>), dim3(n), dim3(64), sh, st, *S, cubes, thetas);
     else return 1;
     return 0;
+}
+
+// pchip_source_eval: a source likelihood at n points (device pointers), by the handle's run-time module -- there is no static kernel
+extern "C" int pc_launch_source_eval(const PcState *S, int n, const double *thetas, double *logL, double *phi, hipStream_t st)
+{
+    if (S->like.kind != PC_LIKE_SOURCE || n < 1) return 1;
+    const size_t sh = sizeof(double) * S->D;
+    if (S->D <= 64) return pc_rtc_go(S, "k_source_eval<1>", dim3(n), dim3(64), sh, st, *S, thetas, logL, phi);
+    if (S->D <= 128) return pc_rtc_go(S, "k_source_eval<2>", dim3(n), dim3(64), sh, st, *S, thetas, logL, phi);
+    if (S->D <= 256) return pc_rtc_go(S, "k_source_eval<4>", dim3(n), dim3(64), sh, st, *S, thetas, logL, phi);
+    return 1;
 }
 #endif  // __HIPCC_RTC__

@@ -207,6 +207,11 @@
     // likelihood call -- no closed form along the chord, no carried products of the correlated Gaussian
     ChainCtx<DPL, NROWS, PT> C{S, ld, lane, ybuf, 0, false, 0.0, 0.0, 0.0, 0.0};
     if constexpr (PT != 0) pc_table_load<DPL>(S, lane, C.tb);
+#ifdef PCHIP_USER_TERMS
+    // the terms form of a source: the second theta of eval_pair behind the chain's block, where the launchers add nDims doubles for it
+    // (pc_terms_lds); the sum of every baby in the spare double of its tbuf row (the rows are D + 1 apart)
+    C.tsum = 0.0; C.ybuf2 = (double *)smem + (size_t)WPB * per_wave;
+#endif
     const bool corr = PT == 0 && (lean2 || (!lean && !leanf && S.like.kind == PC_LIKE_CORR_GAUSSIAN));
     C.quad = PT == 0 && !leanf && (lean_any || ((corr || S.like.kind == PC_LIKE_GAUSSIAN) && !(S.ablate & 1)));
     C.qnorm = corr ? -((double)D * PC_LOG_TWO_PI + S.like.logdetcov) / 2.0 : S.like.norm;
@@ -507,6 +512,10 @@
             else ok = true;
         }
         if (!ok) lnew = logzero;                    // "Non deterministic loglikelihood"
+#ifdef PCHIP_USER_TERMS
+        // (no point in 101 trials: the row gets the last trial's theta -- zeros if that was outside the cube --, the sum of that theta goes with it)
+        if (!ok && LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) (void)like_eval_terms<DPL>(S, th, ld, lane, ybuf, C.tsum);
+#endif
         if (corr) {                                 // the next start point: y and M.y move along the chord
             C.qa = C.qa + t_last * (2.0 * C.qb + t_last * C.qc);
 #pragma unroll
@@ -544,8 +553,13 @@
         if (phi_lds) {
 #pragma unroll
             for (int k = 0; k < DPL; ++k) if (ld.on[k]) tb_row[64 * k] = th[k];
+#ifdef PCHIP_USER_TERMS
+            if (LEAN == 0 && lane == 0) tb_row[D] = C.tsum;     // (lane 0: tb_row is the row's start)
+#endif
         } else if (!lean2 && nDer > 0) {
-#ifdef PCHIP_USER_SOURCE
+#ifdef PCHIP_USER_TERMS
+            if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) like_phi_terms<DPL>(S, th, ld, lane, ybuf, C.tsum, row + o_d0); else
+#elif defined(PCHIP_USER_SOURCE)
             if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) like_phi_source<DPL>(S, th, ld, lane, ybuf, row + o_d0); else
 #endif
             {
@@ -594,7 +608,14 @@
             if (s >= nr) continue;
             double *row = S.babies + ((size_t)chain * nr + s) * nT;
             const double *tt = tbuf + (size_t)s * (D + 1);
-#ifdef PCHIP_USER_SOURCE
+#ifdef PCHIP_USER_TERMS
+            if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) {   // finish(sum, theta) of the baby's kept sum, lane = baby: no walk over the data
+                double phi[PC_SRC_MAX_DERIVED];
+                (void)pchip_logl_finish(tt[D], tt, phi, D, S.nDer, S.src_data, (long)S.src_ndata);
+                for (int e = 0; e < S.nDer; ++e) row[S.d0 + e] = phi[e];
+                continue;
+            }
+#elif defined(PCHIP_USER_SOURCE)
             if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) {   // the user's function, lane = baby
                 double phi[PC_SRC_MAX_DERIVED];
                 (void)pchip_loglikelihood(tt, phi, D, S.nDer, S.src_data, (long)S.src_ndata);
