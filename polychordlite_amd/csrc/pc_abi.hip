@@ -7,6 +7,7 @@
 //   <root>_phys_live.txt / -birth (:621-676), <root>.paramnames is written by the Python layer.
 // Fatal conditions follow abort.F90:19-29: message on stderr, exit status 1.
 #include "../../include/polychord_hip.h"
+#include "pc_launch.h"
 #include "pc_resume.h"
 #include "pc_prior_table.h"
 #include <cstdio>

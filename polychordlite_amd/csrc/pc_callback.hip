@@ -10,6 +10,7 @@
 // (calculate.f90:36-38).  Everything downstream (contraction, phantoms, covariance, clustering) is
 // unchanged.
 #include "pc_state.h"
+#include "pc_launch.h"
 
 enum { CB_NEW_SLICE = 0, CB_WAIT_R0, CB_WAIT_L0, CB_STEP_R, CB_WAIT_R, CB_STEP_L, CB_WAIT_L, CB_SHRINK, CB_WAIT_S, CB_DONE };
 

@@ -35,6 +35,7 @@
 // and the two must produce the same run (tests/test_gpu_parity.py).  A cluster that dies ends the loop: the deletion
 // (delete_cluster, run_time_info.f90:507-598) is done by the workgroup on the way out.
 #include "pc_state.h"
+#include "pc_launch.h"
 #include "pc_keys.h"
 #include <cstdlib>
 

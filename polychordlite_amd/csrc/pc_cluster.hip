@@ -22,6 +22,7 @@
 // The recursion over found clusters (clustering.f90:80-95) and the O(ncluster) evidence split
 // (run_time_info.f90:458-503) are driven from the host (pc_engine.hip); they touch a few integers.
 #include "pc_state.h"
+#include "pc_launch.h"
 #include <cstdlib>
 
 __device__ __forceinline__ void similarity_body(const PcState &S, const int *pts /* slots in list order */, int n, double *Sm, int ybase, int ystride)

@@ -12,6 +12,7 @@
 //               threshold test + deterministic stream compaction, calculate_covmats (:601-641) as a
 //               two-pass mean / centred SYRK with fixed-order reduction, calc_cholesky (utils.F90:621-649).
 #include "pc_state.h"
+#include "pc_launch.h"
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>

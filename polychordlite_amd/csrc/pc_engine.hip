@@ -8,7 +8,7 @@
 #include "pc_state.h"
 #include "pc_resume.h"
 #include "pc_prior_table.h"
-#include "../../include/polychord_hip.h"
+#include "pc_launch.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,85 +30,6 @@
 #include <array>
 #include <sys/mman.h>
 #include <unistd.h>
-
-extern "C" size_t pc_records_block_bytes(long long cap, int nT);
-extern "C" int pc_pack_lived_device(const double *, const double *, const double *, long long, int, double, double *, long long, long long *, hipStream_t);
-extern "C" void *pc_cache_dev_alloc(size_t bytes);
-extern "C" void pc_cache_dev_free(void *p);
-extern "C" {
-int pc_launch_generate_live(const PcState *, int, int, double *, double *, hipStream_t);
-int pc_rtc_wanted(const PcState *);
-const char *pc_rtc_error(void);
-int pc_rtc_source_data(int, const double **, long long *);
-long pc_rtc_source_terms(int);
-int pc_launch_source_eval(const PcState *, int, const double *, double *, double *, hipStream_t);
-int pc_launch_nhats(const PcState *, unsigned, int, hipStream_t);
-int pc_nhats_splittable(const PcState *);
-int pc_launch_nhats_part(const PcState *, unsigned, int, int, hipStream_t, int);
-int pc_launch_slice(const PcState *, unsigned, int, hipStream_t);
-int pc_launch_prior_transform(const PcState *, int, const double *, double *, hipStream_t);
-void pc_abi_set_last_error(const char *);
-int pc_slice_fusable(const PcState *);
-int pc_launch_slice_fused(const PcState *, unsigned, int, hipStream_t);
-int pc_slice_t_ok(const PcState *, int);
-int pc_launch_slice_many(const PcState *, const PcManyRec *, int, int, int, hipStream_t);
-int pc_launch_nhats_many(const PcState *, const PcManyRec *, int, int, hipStream_t);
-int pc_launch_nn_lists_many(const PcState *, const PcManyRec *, int, int, int, hipStream_t);
-int pc_launch_consume_cl_many(const PcState *, const PcManyRec *, int, int, hipStream_t);
-int pc_launch_reset_thresholds_many(const PcState *, const PcManyRec *, int, hipStream_t);
-int pc_launch_knn_cluster_batch_many(const PcState *, const PcManyRec *, int, int, int, int, hipStream_t);
-int pc_launch_knn_cluster_batch_dev(const PcState *, const int *, int, int, double *, int *, int *, int *, const int *, int, hipStream_t);
-int pc_launch_knn_cluster_sub(const int *, int, int, const double *, const int *, int *, int *, int *, hipStream_t);
-int pc_launch_knn_cluster_sub_many(const PcManyRec *, int, int, int, hipStream_t);
-int pc_launch_slice_t(const PcState *, unsigned, int, hipStream_t);
-int pc_bases_t_ok(const PcState *);
-int pc_launch_slice_t_many(const PcState *, const PcManyRec *, int, unsigned, int, hipStream_t);
-int pc_launch_bases_t_many(const PcState *, const PcManyRec *, int, unsigned, int, hipStream_t);
-int pc_update_fused_grid(const PcState *, int, int);
-int pc_launch_clean_many(const PcManyRec *, int, int, hipStream_t);
-int pc_launch_final_par_many(const PcManyRec *, int, hipStream_t);
-int pc_launch_sort_live_many(const PcState *, const PcManyRec *, int, hipStream_t);
-int pc_launch_consume_par_many(const PcState *, const PcManyRec *, int, hipStream_t);
-int pc_launch_apply_many(const PcState *, const PcManyRec *, int, unsigned, int, hipStream_t);
-int pc_launch_update_fused_many(const PcState *, const PcManyRec *, int, int, int, int, hipStream_t);
-int pc_launch_consume(const PcState *, int, int, hipStream_t);
-void pc_launch_nn_lists(const PcState *, int, int, hipStream_t);
-void pc_launch_shift_mats(const PcState *, int, int, hipStream_t);
-void pc_launch_remap_chains(const PcState *, const int *, int, int, hipStream_t);
-int pc_launch_consume_fast(const PcState *, int, hipStream_t);
-int pc_fast_fits(const PcState *);
-int pc_par_fits(const PcState *);
-int pc_launch_sort_live(const PcState *, hipStream_t);
-int pc_launch_consume_par(const PcState *, hipStream_t);
-int pc_launch_final_par(const PcState *, hipStream_t);
-int pc_consume_cl_fits(const PcState *, int);
-int pc_consume_clp_fits(const PcState *, int);
-int pc_launch_consume_cl(const PcState *, int, hipStream_t);
-int pc_launch_killoff_cl(const PcState *, int, hipStream_t);
-void pc_launch_ph_prepare(const PcState *, hipStream_t);
-void pc_launch_apply(const PcState *, unsigned, int, hipStream_t);
-void pc_launch_install_live(const PcState *, const double *, int, hipStream_t);
-void pc_launch_clean(const PcState *, int, unsigned char *, int *, int *, double *, double *, unsigned *,
-                     unsigned long long *, int *, hipStream_t);
-void pc_launch_reset_thresholds(const PcState *, hipStream_t);
-int pc_cov_nchunk(const PcState *, int);
-void pc_launch_similarity(const PcState *, const int *, int, double *, const int *, int, hipStream_t);
-int pc_launch_knn_cluster(const double *, int, const int *, int, int *, int *, int *, hipStream_t);
-int pc_launch_knn_cluster_batch(const PcState *, const int *, const int *, int, double *, int *, int *, int *, const int *, int, hipStream_t);
-void pc_launch_rebuild(const PcState *, int, hipStream_t);
-void pc_launch_ph_rehome(const PcState *, int, int, const unsigned *, int, int *, hipStream_t);
-void pc_launch_slice_tick(const PcState *, unsigned, int, void *, double *, int *, double *, const double *, const double *,
-                          const double *, int, double *, int *, hipStream_t);
-size_t pc_chain_state_size(void);
-void pc_launch_init_state(const PcState *, double, hipStream_t);
-int pc_post_blocks(void);
-void pc_launch_post_moments(const PcState *, int, double *, double *, hipStream_t);
-int pc_launch_covmats(const PcState *, int, int, double *, int *, double *, int *, double *, hipStream_t);
-int pc_update_fused_ok(const PcState *, int);
-int pc_update_fused_blocks(const PcState *, int);
-int pc_update_fused_entries(const PcState *);
-void pc_launch_update_fused(const PcState *, int, unsigned char *, int *, int *, double *, double *, unsigned *, unsigned long long *, double *, double *, int, hipStream_t);
-}
 
 // Fatal conditions unwind to the C ABI entry points (pchip_run_hooks, pchip_slice_chains), which release the run's
 // resources, print the message and return the code: the reference's convention is message + `stop 1`
@@ -2444,9 +2365,17 @@ struct Engine {
                 co->rec(CK_SLICE_G, S, {}, {(long long)B, fused_slice ? 1LL : 0LL}, {(int)batch, 0, 0, fused_slice ? bases_seq : 0});
                 if (fused_slice && co->st2 && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
             }
-            else if ((path[PCHIP_PATH_SLICE_WAVE]++, path[PCHIP_PATH_SOURCE_KERNELS] += pc_rtc_wanted(&S) ? 1 : 0, path[PCHIP_PATH_SOURCE_TERMS] += src_terms ? 1 : 0, path[PCHIP_PATH_DEVICE_PRIOR] += S.prior.kind == PCHIP_PRIOR_TABLE ? 1 : 0, co ? (co->flush(), co->wait_next(), 0) : 0) || (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st))) {
-                if (pc_rtc_wanted(&S) && pc_rtc_error()) { std::fprintf(stderr, "polychord_hip: %s\n", pc_rtc_error()); r_rc = 1; return false; }
-                std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false;
+            else {
+                // a launch of this run alone: lane = coordinate
+                path[PCHIP_PATH_SLICE_WAVE]++;
+                if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
+                if (src_terms) path[PCHIP_PATH_SOURCE_TERMS]++;
+                if (S.prior.kind == PCHIP_PRIOR_TABLE) path[PCHIP_PATH_DEVICE_PRIOR]++;
+                if (co) { co->flush(); co->wait_next(); }
+                if (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st)) {
+                    if (pc_rtc_wanted(&S) && pc_rtc_error()) { std::fprintf(stderr, "polychord_hip: %s\n", pc_rtc_error()); r_rc = 1; return false; }
+                    std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false;
+                }
             }
             kt.end(KT_SLICE, e1);
             if (split) side_prefetch(batch);

@@ -26,6 +26,7 @@
 //
 // Exact ties in logL are broken by (sorted snapshot first, then lane order) instead of list position.
 #include "pc_state.h"
+#include "pc_launch.h"
 
 #include "pc_keys.h"
 

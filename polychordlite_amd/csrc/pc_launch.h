@@ -1,0 +1,153 @@
+// pc_launch.h -- the host functions one .hip file of the engine defines and another calls, declared once.
+//
+// All of them have C linkage (tools and tests reach some by name), so a call through a stale hand-written prototype would link
+// without a word: every file that defines or calls one includes this header, and the compiler compares each definition with it.
+// Grouped by the file that defines them.  Launchers enqueue on stream `st` and do not wait.
+#pragma once
+#include "pc_state.h"
+#include "../../include/polychord_hip.h"
+#include <cstddef>
+
+// k_slice keeps the theta rows of a chain's babies in LDS (its run-time flag phi_lds: derived parameters at the end of the chain, summed
+// in that order) when they fit under 48 KB next to the chain's block; pc_slice_t_ok takes only states where it does
+// (pc_slice_plan's rule, asked by pc_slice_t_ok in another file: inline here, the one definition in this header, so that the library's
+//  exported pc_* names stay what they were)
+static inline int pc_slice_phi_lds(const PcState *S)
+{
+    const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16, tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
+    return (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
+}
+
+extern "C" {
+
+// ---- pc_abi.hip --------------------------------------------------------------------------------------------
+// the text behind pchip_last_error (NULL clears)
+void pc_abi_set_last_error(const char *msg);
+// ---- pc_callback.hip ---------------------------------------------------------------------------------------
+void pc_launch_slice_tick(const PcState *S, unsigned batch, int nchains, void *cs, double *x0s, int *decks, double *prop, const double *ev_logL,
+                          const double *ev_theta, const double *ev_phi, int first, double *prop_host, int *need_host, hipStream_t st);
+size_t pc_chain_state_size(void);
+// ---- pc_clus.hip -------------------------------------------------------------------------------------------
+// 0: launched; 1: not this way (the caller takes the general kernel)
+int pc_launch_killoff_cl(const PcState *S, int nc, hipStream_t st);
+int pc_consume_cl_fits(const PcState *S, int nc);
+// the kernel with parallel decisions: the same envelope, its own (larger) LDS block
+int pc_consume_clp_fits(const PcState *S, int nc);
+int pc_launch_consume_cl_many(const PcState *S, const PcManyRec *dR, int R, int wide, hipStream_t st);
+int pc_launch_consume_cl(const PcState *S, int nc, hipStream_t st);
+// ---- pc_cluster.hip ----------------------------------------------------------------------------------------
+int pc_launch_knn_cluster_sub(const int *d_desc, int nb, int mmax, const double *Sm, const int *pool, int *knn, int *labels, int *out, hipStream_t st);
+int pc_launch_knn_cluster_sub_many(const PcManyRec *dR, int R, int nb_max, int mmax, hipStream_t st);
+void pc_launch_remap_chains(const PcState *S, const int *map, int nold, int n, hipStream_t st);
+void pc_launch_shift_mats(const PcState *S, int p, int nc, hipStream_t st);
+// (dims / nd: the sub-dimension pass's coordinates, nd = 0 the full space -- in this and the batched launchers below)
+void pc_launch_similarity(const PcState *S, const int *pts, int n, double *Sm, const int *dims, int nd, hipStream_t st);
+int pc_launch_knn_cluster(const double *Sm, int nroot, const int *gidx, int m, int *knn, int *labels, int *out, hipStream_t st);
+int pc_launch_knn_cluster_batch(const PcState *S, const int *h_desc, const int *d_desc, int nd, double *Sm, int *knn, int *labels, int *out, const int *dims, int ndims, hipStream_t st);
+int pc_launch_knn_cluster_batch_dev(const PcState *S, const int *d_desc, int nd, int nmax, double *Sm, int *knn, int *labels, int *out, const int *dims, int ndims, hipStream_t st);
+int pc_launch_knn_cluster_batch_many(const PcState *S, const PcManyRec *dR, int R, int nd_max, int nmax, int any_sub, hipStream_t st);
+void pc_launch_rebuild(const PcState *S, int nc, hipStream_t st);
+void pc_launch_ph_rehome(const PcState *S, int nph, int nc, const unsigned *old_uids, int nold_uids, int *counts, hipStream_t st);
+// ---- pc_contract.hip ---------------------------------------------------------------------------------------
+// use_rank: k_sort_live has run on this state in front of this launch
+void pc_launch_nn_lists(const PcState *S, int nleft, int use_rank, hipStream_t st);
+int pc_launch_nn_lists_many(const PcState *S, const PcManyRec *dR, int R, int nleft_max, int use_rank, hipStream_t st);
+int pc_launch_consume(const PcState *S, int final_mode, int wide, hipStream_t st);
+void pc_launch_apply(const PcState *S, unsigned batch, int nchains, hipStream_t st);
+int pc_launch_apply_many(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st);
+// ... for R runs at once: every run its own row count (PcManyRec::ia[1], blocks ia[2])
+int pc_launch_clean_many(const PcManyRec *dR, int R, int nblk_max, hipStream_t st);
+void pc_launch_install_live(const PcState *S, const double *rows, int n, hipStream_t st);
+// phantom clean: returns nothing; *d_total (device int) receives the surviving count
+void pc_launch_clean(const PcState *S, int nph, unsigned char *keep, int *blk, int *d_total, double *ph2, double *phL2, unsigned *phC2, unsigned long long *phU2, int *dst_index, hipStream_t st);
+void pc_launch_reset_thresholds(const PcState *S, hipStream_t st);
+int pc_launch_reset_thresholds_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st);
+int pc_cov_nchunk(const PcState *S, int nph);
+int pc_launch_covmats(const PcState *S, int nph, int nc, double *psum, int *pcnt, double *mean, int *count, double *pcov, hipStream_t st);
+// pieces of the general update path used by the fused update of pc_update.hip
+void pc_launch_scan_blocks(int *blk, int nblk, int *total, int *total2, hipStream_t st);
+void pc_launch_chol_only(const PcState *S, const double *ncov, const int *count, hipStream_t st);
+void pc_launch_init_state(const PcState *S, double logzero, hipStream_t st);
+int pc_post_blocks(void);
+void pc_launch_post_moments(const PcState *S, int nd, double *pmax, double *part, hipStream_t st);
+// ---- pc_engine.hip -----------------------------------------------------------------------------------------
+// called before several scheduler groups start on a device, while it is idle: the pool gets at least `want` streams
+void pc_prepare_streams(int dev, int want);
+// scratch blocks kept between calls (the driver works frees off for 10 ... 30 ms)
+void *pc_cache_dev_alloc(size_t bytes);
+void pc_cache_dev_free(void *p);
+void *pc_cache_host_alloc(size_t bytes);
+void pc_cache_host_free(void *p);
+// several runs of one problem in step on a device.  Returns 0 or the first failing run's code.
+int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds, int device, int max_in_flight, pchip_result *results);
+// ---- pc_fast.hip -------------------------------------------------------------------------------------------
+// _fits: 1 where the kernel's LDS block fits; launchers: 0: launched; 1: not this way
+int pc_fast_fits(const PcState *S);
+int pc_launch_sort_live(const PcState *S, hipStream_t st);
+int pc_launch_sort_live_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st);
+int pc_launch_consume_fast(const PcState *S, int final_mode, hipStream_t st);
+void pc_launch_ph_prepare(const PcState *S, hipStream_t st);
+// ---- pc_merge.hip ------------------------------------------------------------------------------------------
+// the lived records of a run packed on its device into `block`: rows [cap][nT] | entry [cap] | own log weight [cap] | scratch
+size_t pc_records_block_bytes(long long cap, int nT);
+int pc_pack_lived_device(const double *dead, const double *logw, const double *entry, long long nd, int nT, double logzero, double *block, long long cap, long long *h_count, hipStream_t st);
+// ---- pc_par.hip --------------------------------------------------------------------------------------------
+// _fits: 1 where the kernel's LDS block fits; launchers: 0: launched; 1: not this way
+int pc_par_fits(const PcState *S);
+int pc_launch_consume_par(const PcState *S, hipStream_t st);
+// the same launch for R runs of one shape at once (blockIdx.y = run; dR: device array of their records)
+int pc_launch_consume_par_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st);
+int pc_launch_final_par(const PcState *S, hipStream_t st);
+int pc_launch_final_par_many(const PcManyRec *dR, int R, hipStream_t st);
+// ---- pc_rtc.hip --------------------------------------------------------------------------------------------
+// launched by PC_LAUNCH (pc_sample.hip) with the variant, grid, block, dynamic LDS and arguments the launcher chose for the static kernel.
+// 0: launched; 1: no such kernel (pc_rtc_error has the text)
+int pc_rtc_launch(const PcState *S, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t st, void **args);
+const char *pc_rtc_error(void);
+// 0: a source exists (and its data block, for the engine's upload)
+int pc_rtc_source_data(int id, const double **data, long long *n);
+// the number of terms of a terms-form handle; 0: the plain form, or no such handle
+long pc_rtc_source_terms(int id);
+// ---- pc_sample.hip -----------------------------------------------------------------------------------------
+// Launchers: 0: launched; 1: not this way (no kernel for this shape, or the run-time module failed: pc_rtc_error).
+// the sampling kernels come from the run-time module (a source likelihood, settings.ablate bit 15)
+int pc_rtc_wanted(const PcState *S);
+int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL, hipStream_t st);
+// the split launch (see k_nhats): part 1 = bases, part 2 = seeds + whitening; 1 where it exists (else only the whole kernel: pc_launch_nhats)
+int pc_nhats_splittable(const PcState *S);
+int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchains, int part, hipStream_t st, int packed);
+int pc_launch_nhats(const PcState *S, unsigned batch, int nchains, hipStream_t st);
+// 1: k_slice can do seeds + whitening itself (pc_launch_slice_fused; pc_launch_slice_many with fused = 1)
+int pc_slice_fusable(const PcState *S);
+int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchains, hipStream_t st);
+// R runs of a device in step (grid.y = run, every run the same shape).  1: a shape only the one-run launchers take
+int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st);
+// ... and their directions for the shapes that do not split: 24 < nDims <= 64
+int pc_launch_nhats_many(const PcState *S, const PcManyRec *dR, int R, int nchains, hipStream_t st);
+int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t st);
+// pchip_prior_transform: the device transform of the table in S->prior at n points (device pointers)
+int pc_launch_prior_transform(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st);
+// pchip_source_eval: a source likelihood at n points (device pointers), by the handle's run-time module
+int pc_launch_source_eval(const PcState *S, int n, const double *thetas, double *logL, double *phi, hipStream_t st);
+// ---- pc_slice_t.hip ----------------------------------------------------------------------------------------
+// lane = chain / lane = basis.  _ok: 1 where the kernels take the state; launchers: 0: launched; 1: not this way
+int pc_bases_t_ok(const PcState *S);
+int pc_launch_bases_t(const PcState *S, unsigned batch, int nchains, hipStream_t st);
+int pc_launch_bases_t_many(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st);
+int pc_slice_t_ok(const PcState *S, int ncluster);
+int pc_launch_slice_t(const PcState *S, unsigned batch, int nchains, hipStream_t st);
+int pc_launch_slice_t_many(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st);
+// ---- pc_update.hip -----------------------------------------------------------------------------------------
+// the fused update: _ok 1 where it exists (one cluster, nDims <= 128)
+int pc_update_fused_ok(const PcState *S, int nc);
+int pc_update_fused_blocks(const PcState *S, int nph);
+int pc_update_fused_entries(const PcState *S);
+// nph >= 1.  keep [nph], blk [blocks], part [pc_update_fused_blocks * pc_update_fused_entries] doubles, shift [D]; deferred: see k_upd_flag
+void pc_launch_update_fused(const PcState *S, int nph, unsigned char *keep, int *blk, int *d_total, double *ph2, double *phL2, unsigned *phC2,
+                            unsigned long long *phU2, double *part, double *shift, int deferred, hipStream_t st);
+int pc_update_fused_grid(const PcState *S, int nph, int deferred);
+// ... for R runs, all of them the same number G of gathering workgroups (pc_update_fused_grid) and nblk_max >= their blocks.
+// 1: not this way (the caller launches them one by one)
+int pc_launch_update_fused_many(const PcState *S, const PcManyRec *dR, int R, int nblk_max, int G, int deferred, hipStream_t st);
+
+}   // extern "C"

@@ -22,6 +22,7 @@
 //   * posterior moments about a pivot known before the sums (the theta / phi of the record with the largest posterior weight,
 //     lowest merged position on ties): sum w (x - p), sum w (x - p)^2, so a narrow posterior far from zero keeps its variance.
 #include "pc_state.h"
+#include "pc_launch.h"
 #include "pc_keys.h"
 #include "../../include/polychord_hip.h"
 #include <cstdio>
@@ -36,9 +37,6 @@
 #include <mutex>
 #include <dlfcn.h>
 #include <rccl/rccl.h>          // types and enums only: the library is dlopen'ed (no link-time dependency on RCCL)
-
-extern "C" int pc_run_many(const pchip_settings *, const pchip_like *, const pchip_prior *, int, const int *, int, int, pchip_result *);
-extern "C" void pc_prepare_streams(int dev, int want);
 
 namespace {
 
@@ -475,10 +473,6 @@ struct Rccl {
 Rccl &rccl() { static Rccl *r = new Rccl; return *r; }
 
 // (device scratch and the merged rows come from the engine's block caches, pc_engine.hip)
-extern "C" void *pc_cache_dev_alloc(size_t bytes);
-extern "C" void pc_cache_dev_free(void *p);
-extern "C" void *pc_cache_host_alloc(size_t bytes);
-extern "C" void pc_cache_host_free(void *p);
 // host side of a blocking copy: a pinned block of the cache (see pchip_merge_records on why not a vector)
 template <class T> struct PinBuf {
     T *p; size_t n;

@@ -23,6 +23,7 @@
 // One workgroup of 1024 threads, thread = nursery step (B <= 1024).  Ties in logL: snapshot points
 // before candidates, earlier steps count as larger (what the strict `>` of run_time_info.f90:733 needs).
 #include "pc_state.h"
+#include "pc_launch.h"
 #include "pc_keys.h"
 
 typedef unsigned long long u64;

@@ -16,6 +16,7 @@
 //
 // libhiprtc is opened with dlopen: without it the library loads and the built-ins run; a source run then fails with a message.
 #include "pc_state.h"
+#include "pc_launch.h"
 #include "../../include/polychord_hip.h"
 #include <hip/hiprtc.h>          // types only: the library is dlopen'ed
 #include <dlfcn.h>
@@ -317,7 +318,6 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
 }  // extern "C"
 
 // ---- C engine API ---------------------------------------------------------------------------------------------------------------------
-extern "C" void pc_abi_set_last_error(const char *msg);
 
 extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata)
 {

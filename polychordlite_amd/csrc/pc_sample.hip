@@ -1642,10 +1642,11 @@ __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB) void k_slice_many(const PcM
 // launchers
 // ------------------------------------------------------------------------------------------
 #ifndef __HIPCC_RTC__         // (hiprtc, pc_rtc.hip: the kernels above, not the host code below)
+#include "pc_launch.h"
+#include <cstdio>
 // The sampling kernels of a source likelihood (PC_LIKE_SOURCE), and of every kind under settings.ablate bit 15, come from a module that
 // pc_rtc.hip compiles at run time from this very text: the launchers below choose the variant and its launch shape once, PC_LAUNCH sends
 // it to the static kernel or, by its name, to the module's.
-extern "C" int pc_rtc_launch(const PcState *S, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t st, void **args);
 extern "C" int pc_rtc_wanted(const PcState *S) { return S->like.kind == PC_LIKE_SOURCE || (S->ablate & (1 << 15)) != 0; }
 template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, dim3 g, dim3 b, size_t sh, hipStream_t st, A... a)
 {
@@ -1655,27 +1656,26 @@ template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, d
 #define PC_LAUNCH(K, G, B, SH, ST, ...) do { if (pc_rtc_wanted(S)) { if (pc_rtc_go(S, #K, G, B, SH, ST, __VA_ARGS__)) return 1; } \
                                              else hipLaunchKernelGGL(K, G, B, SH, ST, __VA_ARGS__); } while (0)
 // the terms form of a source evaluates the two ends of a bracket in one pass over the data: LDS for the second theta behind the chain's block
-extern "C" long pc_rtc_source_terms(int id);
 static size_t pc_terms_lds(const PcState *S)
 {
     return (S->like.kind == PC_LIKE_SOURCE && pc_rtc_source_terms(S->src_id) > 0) ? sizeof(double) * (size_t)S->D : 0;
 }
+// lane = coordinate: the coordinates a lane holds (template DPL) at nDims <= 64, 128, 256; 0 beyond (the launchers return 1)
+static int pc_dpl(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : (D <= 256 ? 4 : 0)); }
 extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL,
                                        hipStream_t st)
 {
     const size_t sh = sizeof(double) * S->D;
-    if (S->prior.kind == 2) {                   // a prior table
-        if (S->D <= 64) PC_LAUNCH((k_generate_live<1, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
-        else if (S->D <= 128) PC_LAUNCH((k_generate_live<2, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
-        else if (S->D <= 256) PC_LAUNCH((k_generate_live<4, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
-        else return 1;
-        return 0;
+    const bool table = S->prior.kind == 2;          // a prior table
+    switch (pc_dpl(S->D) + (table ? 8 : 0)) {
+    case 1: PC_LAUNCH((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
+    case 2: PC_LAUNCH((k_generate_live<2>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
+    case 4: PC_LAUNCH((k_generate_live<4>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
+    case 9: PC_LAUNCH((k_generate_live<1, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
+    case 10: PC_LAUNCH((k_generate_live<2, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
+    case 12: PC_LAUNCH((k_generate_live<4, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
     }
-    if (S->D <= 64) PC_LAUNCH((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
-    else if (S->D <= 128) PC_LAUNCH((k_generate_live<2>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
-    else if (S->D <= 256) PC_LAUNCH((k_generate_live<4>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL);
-    else return 1;
-    return 0;
+    return 1;
 }
 
 // the split launch (see k_nhats): part 1 = bases, part 2 = seeds + whitening; returns 1 where only the whole kernel exists
@@ -1686,9 +1686,10 @@ extern "C" int pc_nhats_splittable(const PcState *S)
     if (S->D > 24 && S->D <= 64) return S->ngrade <= 1 && !S->seq_mode && S->nhat_raw != nullptr && (!e || std::atoi(e) <= 25);      // k_nhats_q<8 / 16, 1 / 2> (round 5)
     return S->D <= 24 && S->D < (e ? std::atoi(e) : 25) && !S->seq_mode && S->nhat_raw != nullptr;
 }
-// (two tile buffers up to nDims 112; beyond that one, with a barrier more per tile: 160 KB of LDS)
+// dynamic LDS of k_nhats_q<HV> (HV = 8, 16): pivot buffer + Cholesky tile (HV rows of 4 (HV + 2) doubles) ...
+static size_t pc_nhats_q_lds(int HV) { return sizeof(double) * (size_t)(2 + HV) * 4 * (HV + 2); }
+// ... and of k_nhats_q<32>: basis + sixteen rows of L (two tile buffers up to nDims 112; beyond that one, with a barrier more per tile: 160 KB of LDS)
 static size_t pc_nhats_q32_lds(int D) { const int NR = ((D + 15) / 16) * 16; return sizeof(double) * (2 * 4 * 34 + (size_t)(NR + (NR <= 112 ? 32 : 16)) * 129); }
-extern "C" int pc_launch_bases_t(const PcState *S, unsigned batch, int nchains, hipStream_t st);
 extern "C" int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchains, int part, hipStream_t st, int packed)
 {
     if (!pc_nhats_splittable(S)) return 1;
@@ -1717,9 +1718,8 @@ extern "C" int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchain
     if (D > 24) {
         // nDims 25 ... 64: the four-threads-per-vector kernel in two halves -- deviates + Gram-Schmidt (nothing the contraction changes:
         // drawn ahead on the side stream), then seeds + whitening in front of k_slice
-        auto lds_q = [](int HV) { return sizeof(double) * (size_t)(2 + HV) * 4 * (HV + 2); };
-        if (D <= 32) { if (part == 1) hipLaunchKernelGGL((k_nhats_q<8, 1>), grid, dim3(128), lds_q(8), st, *S, batch); else hipLaunchKernelGGL((k_nhats_q<8, 2>), grid, dim3(128), lds_q(8), st, *S, batch); }
-        else { if (part == 1) hipLaunchKernelGGL((k_nhats_q<16, 1>), grid, dim3(256), lds_q(16), st, *S, batch); else hipLaunchKernelGGL((k_nhats_q<16, 2>), grid, dim3(256), lds_q(16), st, *S, batch); }
+        if (D <= 32) { if (part == 1) hipLaunchKernelGGL((k_nhats_q<8, 1>), grid, dim3(128), pc_nhats_q_lds(8), st, *S, batch); else hipLaunchKernelGGL((k_nhats_q<8, 2>), grid, dim3(128), pc_nhats_q_lds(8), st, *S, batch); }
+        else { if (part == 1) hipLaunchKernelGGL((k_nhats_q<16, 1>), grid, dim3(256), pc_nhats_q_lds(16), st, *S, batch); else hipLaunchKernelGGL((k_nhats_q<16, 2>), grid, dim3(256), pc_nhats_q_lds(16), st, *S, batch); }
         return 0;
     }
     const size_t sh = sizeof(double) * ((size_t)(D + 8) * (D + 8) + 2 * 128) + 16;
@@ -1744,10 +1744,8 @@ extern "C" int pc_launch_nhats(const PcState *S, unsigned batch, int nchains, hi
     static int quad_min = -1;                       // smallest nDims that takes the four-threads-per-vector kernel
     if (quad_min < 0) { const char *e = std::getenv("PC_NHATS_QUAD_MIN"); quad_min = e ? std::atoi(e) : 25; }   // measured: 20-D 52 vs 39 us (old kernel better), 28-D 43 vs 47, 40-D 95 vs 133, 64-D 129 vs 240
     if (D >= quad_min) {
-        // dynamic LDS: pivot buffer + Cholesky tile (HV rows of 4 (HV + 2) doubles), or basis + sixteen rows of L (HV = 32)
-        auto lds_q = [](int HV) { return sizeof(double) * (size_t)(2 + HV) * 4 * (HV + 2); };
-        if (D <= 32) hipLaunchKernelGGL((k_nhats_q<8>), grid, dim3(128), lds_q(8), st, *S, batch);
-        else if (D <= 64) hipLaunchKernelGGL((k_nhats_q<16>), grid, dim3(256), lds_q(16), st, *S, batch);
+        if (D <= 32) hipLaunchKernelGGL((k_nhats_q<8>), grid, dim3(128), pc_nhats_q_lds(8), st, *S, batch);
+        else if (D <= 64) hipLaunchKernelGGL((k_nhats_q<16>), grid, dim3(256), pc_nhats_q_lds(16), st, *S, batch);
         else if (D <= 128) {
             const size_t shq = pc_nhats_q32_lds(D);
             pc_need_dyn_lds((const void *)k_nhats_q<32>, shq);
@@ -1768,194 +1766,167 @@ extern "C" int pc_launch_nhats(const PcState *S, unsigned batch, int nchains, hi
     return 0;
 }
 
+// ... and for several runs of a device in step (grid.z = run) the shapes that do not split: 24 < nDims <= 64
+extern "C" int pc_launch_nhats_many(const PcState *S, const PcManyRec *dR, int R, int nchains, hipStream_t st)
+{
+    const int D = S->D, nb = S->nb_total;
+    if (D < 25 || D > 64 || S->seq_mode || std::getenv("PC_NHATS_QUAD_MIN")) return 1;
+    dim3 grid(nb, nchains, R);
+    if (D <= 32) hipLaunchKernelGGL((k_nhats_q_many<8>), grid, dim3(128), pc_nhats_q_lds(8), st, dR);
+    else hipLaunchKernelGGL((k_nhats_q_many<16>), grid, dim3(256), pc_nhats_q_lds(16), st, dR);
+    return 0;
+}
+
 extern "C" int pc_slice_fusable(const PcState *S)
 {   // the slice kernel can do seeds + whitening itself: raw bases in HBM (split launch), one grade, nDims <= 24
     static const bool off = std::getenv("PC_SLICE_FUSED_OFF") != nullptr;
     return !off && S->D <= 24 && pc_nhats_splittable(S) && S->ngrade <= 1 && S->like.kind != PC_LIKE_CORR_GAUSSIAN && S->nr <= 1024;
 }
 
-// the functor variants of k_slice (LEAN = 3 Rastrigin, 4 twin Gaussian, 5 the Gaussian when settings.ablate bit 0 asks for it as a functor): one grade, keyed draws
-static int slice_lean_functor(const PcState *S)
-{
-    static const bool off = std::getenv("PC_SLICE_LEAN_OFF") != nullptr;
-    if (off || S->ngrade > 1 || S->seq_mode || S->prior.kind == 2) return 0;      // (a prior table: the general variants)
-    return S->like.kind == PC_LIKE_RASTRIGIN ? 3 : (S->like.kind == PC_LIKE_TWIN_GAUSSIAN ? 4 : ((S->like.kind == PC_LIKE_GAUSSIAN && (S->ablate & 1)) ? 5 : 0));
-}
+// ------------------------------------------------------------------------------------------
+// The launch of k_slice / k_slice_many: pc_slice_plan chooses the variant and the launch shape (every rule in one place),
+// PC_SLICE_VARIANTS lists the variants that exist, pc_slice_launch sends a plan to its row.  A new variant: a rule in the
+// plan and a row in the table.
+// ------------------------------------------------------------------------------------------
+struct PcSlicePlan {
+    bool ok, many;                                // ok = false: no such launch (the launchers return 1);  many: k_slice_many, grid.y = run
+    int dpl, nrows; bool special; int wpb, fw, lean, pt;      // the template arguments (see k_slice)
+    dim3 grid, block; size_t lds;
+    int phi_lds, mat_lds;                         // the kernels' run-time flags: theta rows of the babies / the inverse covariance in LDS
+};
 
-extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchains, hipStream_t st)
+// The plan for a nursery of nchains chains: `fused` = seed choice and whitening inside the kernel (FW > 0, pc_slice_fusable), else the
+// plain kernel behind k_nhats*;  R = 0: a run on its own (k_slice), R > 0: R runs of a device in step (k_slice_many: every run the same
+// shape -- nDims, num_repeats, chains, likelihood kind).
+static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R)
 {
-    if (!pc_slice_fusable(S)) return 1;
-    const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16;
-    const size_t tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
-    const int phi_lds = (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
-    const int D = S->D, FWv = D <= 8 ? 8 : (D <= 16 ? 16 : 24);
-    const size_t sh = sh0 + (phi_lds ? tb : 0) + sizeof(double) * ((size_t)FWv * D + (size_t)S->nr * (D + 2)) + pc_terms_lds(S);   // + L, directions, widths
-    if (sh > 150 * 1024) return 1;
-    static const bool lean_off = std::getenv("PC_SLICE_LEAN_OFF") != nullptr;
-    const bool table = S->prior.kind == 2;
-    const bool lean = !lean_off && !table && S->like.kind == PC_LIKE_GAUSSIAN && !(S->ablate & 1) && phi_lds && S->nr <= 64 && !S->seq_mode && S->ngrade <= 1;
-    const int leanf = slice_lean_functor(S);
-    // (a helper wavefront per chain for the lean variants whose deck lives in registers: pc_slice_body.inc; settings.ablate bit 13 / PC_SLICE_HELPER_OFF: without)
-    // four chains a workgroup with their four helper wavefronts (pc_slice_body.inc): the lean variants whose deck lives in registers, nurseries of a
-    // multiple of four chains; settings.ablate bit 13 / PC_SLICE_HELPER_OFF: one wavefront a workgroup as before (the same numbers)
-    static const bool helper_off = std::getenv("PC_SLICE_HELPER_OFF") != nullptr;
-    const size_t pw4 = ((size_t)D + S->nr + ((phi_lds || lean) ? (size_t)S->nr * (D + 1) : 0) + (size_t)FWv * D + (size_t)S->nr * (D + 2) + (size_t)((S->nr + 3) / 4) * 128 + (size_t)S->nr + 1) & ~(size_t)1;
-    const size_t sh4 = 4 * sizeof(double) * pw4 + 16;
-    const bool help = !helper_off && !(S->ablate & 8192) && S->nr <= 64 && (nchains & 3) == 0 && sh4 <= 150 * 1024;
-#define PC_SLICE_FUSED_L(NROWS, FW, LN) { \
-        if ((LN == 3 || LN == 5) && help) { \
-        if (sh4 > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 4, FW, LN>, sh4); \
-        PC_LAUNCH((k_slice<1, NROWS, false, 4, FW, LN>), dim3(nchains / 4), dim3(512), sh4, st, *S, batch, phi_lds, 0); } else { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW, LN>, sh); \
-        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW, LN>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } }
-#define PC_SLICE_FUSED(NROWS, FW) { \
-        if (leanf == 3) PC_SLICE_FUSED_L(NROWS, FW, 3) else if (leanf == 4) PC_SLICE_FUSED_L(NROWS, FW, 4) else if (leanf == 5) PC_SLICE_FUSED_L(NROWS, FW, 5) else \
-        if (lean) { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW, 1>, sh); \
-        if (help) { if (sh4 > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 4, FW, 1>, sh4); \
-        PC_LAUNCH((k_slice<1, NROWS, false, 4, FW, 1>), dim3(nchains / 4), dim3(512), sh4, st, *S, batch, phi_lds, 0); } else \
-        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } else if (table) { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW, 0, 1>, sh); \
-        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW, 0, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } else { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<1, NROWS, false, 1, FW>, sh); \
-        PC_LAUNCH((k_slice<1, NROWS, false, 1, FW>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); } }
-    if (D <= 8) PC_SLICE_FUSED(1, 8)
-    else if (D <= 16) PC_SLICE_FUSED(1, 16)
-    else PC_SLICE_FUSED(2, 24)
-#undef PC_SLICE_FUSED
-#undef PC_SLICE_FUSED_L
-    return 0;
-}
-
-// Several runs of a device in step: the sampling kernel of any device likelihood launched once for all of them (grid.y = run; every
-// run the same shape: nDims, num_repeats, chains, likelihood kind).  fused: k_slice with the seed choice and the whitening inside
-// (pc_launch_slice_fused); else the plain kernel behind k_nhats*.  1: a shape only the one-run launchers take.
-extern "C" int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st)
-{
-    const int D = S->D;
-    if (S->prior.kind == 2) return 1;           // (a prior table: the one-run launchers)
-    const size_t sh0 = sizeof(double) * ((size_t)D + S->nr) + 16;
-    const size_t tb = sizeof(double) * (size_t)S->nr * (D + 1);
-    const int phi_lds = (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
+    static const bool lean_off = std::getenv("PC_SLICE_LEAN_OFF") != nullptr, helper_off = std::getenv("PC_SLICE_HELPER_OFF") != nullptr,
+                      wpb_off = std::getenv("PC_SLICE_WPB_OFF") != nullptr;
+    PcSlicePlan p{};
+    const int D = S->D, nr = S->nr;
+    const bool table = S->prior.kind == 2;                      // a prior table: every likelihood through like_eval, no matrix in LDS
+    const bool special = S->ngrade > 1 || S->seq_mode;          // the two rare modes (pc_slice_fusable excludes both)
+    const bool corr = S->like.kind == PC_LIKE_CORR_GAUSSIAN;
+    if (D > 256 || (fused && !pc_slice_fusable(S))) return p;
+    if (R && (table || (!fused && (corr || special || D > 64)))) return p;      // shapes only the one-run launchers take
+    p.many = R > 0;
+    p.dpl = pc_dpl(D);
+    p.nrows = D <= 16 ? 1 : ((D <= 32 || fused) ? 2 : 4);
+    p.special = special; p.wpb = 1; p.pt = table ? 1 : 0;
+    p.fw = !fused ? 0 : (D <= 8 ? 8 : (D <= 16 ? 16 : 24));
+    p.grid = R ? dim3(nchains, R) : dim3(nchains); p.block = dim3(64);
+    // a chain's LDS: ybuf + two int decks; theta of every baby (derived parameters at the end of the chain) when it fits
+    p.phi_lds = pc_slice_phi_lds(S);
+    const size_t tb = sizeof(double) * (size_t)nr * (D + 1);
+    size_t sh = sizeof(double) * ((size_t)D + nr) + 16 + (p.phi_lds ? tb : 0);
+    if (fused) sh += sizeof(double) * ((size_t)p.fw * D + (size_t)nr * (D + 2));     // + L, directions, widths
+    if (!R) sh += pc_terms_lds(S);                              // (runs in step take no source: pchip_run_repeats refuses the handle)
+    if (fused && sh > 150 * 1024) return p;
+    // the functor variants (LEAN = 3 Rastrigin, 4 twin Gaussian, 5 the Gaussian when settings.ablate bit 0 asks for it as a functor): one grade,
+    // keyed draws, the box (a prior table: the general variants); runs in step take the Gaussian functor as the general kernel
+    int leanf = 0;
+    if (!lean_off && !special && !table)
+        leanf = S->like.kind == PC_LIKE_RASTRIGIN ? 3 : (S->like.kind == PC_LIKE_TWIN_GAUSSIAN ? 4 : ((S->like.kind == PC_LIKE_GAUSSIAN && (S->ablate & 1) && !R) ? 5 : 0));
     if (fused) {
-        if (!pc_slice_fusable(S)) return 1;
-        const int FWv = D <= 8 ? 8 : (D <= 16 ? 16 : 24);
-        const size_t sh = sh0 + (phi_lds ? tb : 0) + sizeof(double) * ((size_t)FWv * D + (size_t)S->nr * (D + 2));
-        if (sh > 150 * 1024) return 1;
-        const int leanf = slice_lean_functor(S) == 5 ? 0 : slice_lean_functor(S);
-#define PC_SLICE_FUSED_ML(NROWS, FW, LN) { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice_many<1, NROWS, false, 1, FW, LN>, sh); \
-        PC_LAUNCH((k_slice_many<1, NROWS, false, 1, FW, LN>), dim3(nchains, R), dim3(64), sh, st, dR, phi_lds, 0); }
-#define PC_SLICE_FUSED_M(NROWS, FW) { if (leanf == 3) PC_SLICE_FUSED_ML(NROWS, FW, 3) else if (leanf == 4) PC_SLICE_FUSED_ML(NROWS, FW, 4) else PC_SLICE_FUSED_ML(NROWS, FW, 0) }
-        if (D <= 8) PC_SLICE_FUSED_M(1, 8)
-        else if (D <= 16) PC_SLICE_FUSED_M(1, 16)
-        else PC_SLICE_FUSED_M(2, 24)
-#undef PC_SLICE_FUSED_M
-#undef PC_SLICE_FUSED_ML
-        return 0;
+        // LEAN = 1: the Gaussian in closed form along the chord, its deck in registers (one-run launches)
+        const bool lean = !R && !lean_off && !table && S->like.kind == PC_LIKE_GAUSSIAN && !(S->ablate & 1) && p.phi_lds && nr <= 64 && !special;
+        p.lean = leanf ? leanf : (lean ? 1 : 0);
+        // four chains a workgroup with their four helper wavefronts (pc_slice_body.inc): the lean variants whose deck lives in registers (1, 3, 5),
+        // nurseries of a multiple of four chains; settings.ablate bit 13 / PC_SLICE_HELPER_OFF: one wavefront a workgroup as before (the same numbers)
+        const size_t pw4 = ((size_t)D + nr + (p.phi_lds ? (size_t)nr * (D + 1) : 0) + (size_t)p.fw * D + (size_t)nr * (D + 2) + (size_t)((nr + 3) / 4) * 128 + (size_t)nr + 1) & ~(size_t)1;
+        const size_t sh4 = 4 * sizeof(double) * pw4 + 16;
+        if (!R && (p.lean == 1 || p.lean == 3 || p.lean == 5) && !helper_off && !(S->ablate & 8192) && nr <= 64 && (nchains & 3) == 0 && sh4 <= 150 * 1024) {
+            p.wpb = 4; p.grid = dim3(nchains / 4); p.block = dim3(512); sh = sh4;
+        }
+    } else {
+        // the inverse covariance of the correlated Gaussian in LDS when it fits (and its products are not in HBM: nhat_Ms)
+        const size_t mb = sizeof(double) * (size_t)D * D;
+        p.mat_lds = (!table && corr && S->nhat_Ms == nullptr && sh + mb <= 150 * 1024) ? 1 : 0;
+        if (p.mat_lds && D > 64 && D <= 128 && nchains % 4 == 0 && !special && !wpb_off && 4 * sh + mb <= 150 * 1024) {
+            // four chains per workgroup around one LDS copy of the inverse covariance (65 <= nDims <= 128)
+            p.wpb = 4; p.grid = dim3(nchains / 4); p.block = dim3(256); sh = 4 * sh + mb;
+        } else {
+            if (p.mat_lds) sh += mb;
+            // BASELINE configs[4]'s shape: the kernel without its other variants (LEAN = 2)
+            if (!lean_off && !table && corr && S->nhat_Ms != nullptr && !(S->ablate & 1) && S->nDer == 0 && nr > 64 && D > 64 && D <= 128 && !special) p.lean = 2;
+            else if (D <= 64) p.lean = leanf;
+        }
     }
-    if (S->like.kind == PC_LIKE_CORR_GAUSSIAN || S->ngrade > 1 || S->seq_mode || D > 64) return 1;
-    const size_t sh = sh0 + (phi_lds ? tb : 0);
-    const int leanf = slice_lean_functor(S) == 5 ? 0 : slice_lean_functor(S);
-#define PC_SLICE_ML(DPL, NROWS, LN) { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice_many<DPL, NROWS, false, 1, 0, LN>, sh); \
-        PC_LAUNCH((k_slice_many<DPL, NROWS, false, 1, 0, LN>), dim3(nchains, R), dim3(64), sh, st, dR, phi_lds, 0); }
-#define PC_SLICE_M(DPL, NROWS) { if (leanf == 3) PC_SLICE_ML(DPL, NROWS, 3) else if (leanf == 4) PC_SLICE_ML(DPL, NROWS, 4) else PC_SLICE_ML(DPL, NROWS, 0) }
-    if (D <= 16) PC_SLICE_M(1, 1)
-    else if (D <= 32) PC_SLICE_M(1, 2)
-    else PC_SLICE_M(1, 4)
-#undef PC_SLICE_M
-#undef PC_SLICE_ML
-    return 0;
+    p.lds = sh; p.ok = true;
+    return p;
 }
 
-// ... and the directions (bases, seeds, whitening in one kernel: pc_launch_nhats) for the shapes that do not split: 24 < nDims <= 64
-extern "C" int pc_launch_nhats_many(const PcState *S, const PcManyRec *dR, int R, int nchains, hipStream_t st)
+// the instantiations of k_slice: DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT  (a prior table: the rows k_slice<DPL, NROWS, GR, 1, 0, 0, 1> and, fused,
+// k_slice<1, NROWS, false, 1, FW, 0, 1>)
+#define PC_SLICE_VARIANTS(X) \
+    /* behind k_nhats*: nDims <= 16, 32, 64, 128, 256; general (box / table prior, without / with the rare modes) and functors */ \
+    X(1, 1, false, 1, 0, 0, 0) X(1, 1, true, 1, 0, 0, 0) X(1, 1, false, 1, 0, 0, 1) X(1, 1, true, 1, 0, 0, 1) X(1, 1, false, 1, 0, 3, 0) X(1, 1, false, 1, 0, 4, 0) X(1, 1, false, 1, 0, 5, 0) \
+    X(1, 2, false, 1, 0, 0, 0) X(1, 2, true, 1, 0, 0, 0) X(1, 2, false, 1, 0, 0, 1) X(1, 2, true, 1, 0, 0, 1) X(1, 2, false, 1, 0, 3, 0) X(1, 2, false, 1, 0, 4, 0) X(1, 2, false, 1, 0, 5, 0) \
+    X(1, 4, false, 1, 0, 0, 0) X(1, 4, true, 1, 0, 0, 0) X(1, 4, false, 1, 0, 0, 1) X(1, 4, true, 1, 0, 0, 1) X(1, 4, false, 1, 0, 3, 0) X(1, 4, false, 1, 0, 4, 0) X(1, 4, false, 1, 0, 5, 0) \
+    X(2, 4, false, 1, 0, 0, 0) X(2, 4, true, 1, 0, 0, 0) X(2, 4, false, 1, 0, 0, 1) X(2, 4, true, 1, 0, 0, 1) \
+    X(4, 4, false, 1, 0, 0, 0) X(4, 4, true, 1, 0, 0, 0) X(4, 4, false, 1, 0, 0, 1) X(4, 4, true, 1, 0, 0, 1) \
+    /* the correlated Gaussian, 65 <= nDims <= 128: four chains around one matrix in LDS; its products from HBM (LEAN = 2) */ \
+    X(2, 4, false, 4, 0, 0, 0) X(2, 4, false, 1, 0, 2, 0) \
+    /* fused, nDims <= 8, 16, 24: general (box / table), then LEAN = 1, 3, 4, 5 with one chain and with four chains + helpers a workgroup */ \
+    /* (WPB = 4 with LEAN = 4 is compiled and never chosen: the twin Gaussian's functor has no helper wavefront) */ \
+    X(1, 1, false, 1, 8, 0, 0) X(1, 1, false, 1, 8, 0, 1) X(1, 1, false, 1, 8, 1, 0) X(1, 1, false, 4, 8, 1, 0) X(1, 1, false, 1, 8, 3, 0) X(1, 1, false, 4, 8, 3, 0) X(1, 1, false, 1, 8, 4, 0) X(1, 1, false, 4, 8, 4, 0) X(1, 1, false, 1, 8, 5, 0) X(1, 1, false, 4, 8, 5, 0) \
+    X(1, 1, false, 1, 16, 0, 0) X(1, 1, false, 1, 16, 0, 1) X(1, 1, false, 1, 16, 1, 0) X(1, 1, false, 4, 16, 1, 0) X(1, 1, false, 1, 16, 3, 0) X(1, 1, false, 4, 16, 3, 0) X(1, 1, false, 1, 16, 4, 0) X(1, 1, false, 4, 16, 4, 0) X(1, 1, false, 1, 16, 5, 0) X(1, 1, false, 4, 16, 5, 0) \
+    X(1, 2, false, 1, 24, 0, 0) X(1, 2, false, 1, 24, 0, 1) X(1, 2, false, 1, 24, 1, 0) X(1, 2, false, 4, 24, 1, 0) X(1, 2, false, 1, 24, 3, 0) X(1, 2, false, 4, 24, 3, 0) X(1, 2, false, 1, 24, 4, 0) X(1, 2, false, 4, 24, 4, 0) X(1, 2, false, 1, 24, 5, 0) X(1, 2, false, 4, 24, 5, 0)
+// ... and of k_slice_many (no PT: runs in step take the box only): DPL, NROWS, SPECIAL, WPB, FW, LEAN
+#define PC_SLICE_MANY_VARIANTS(X) \
+    X(1, 1, false, 1, 0, 0) X(1, 1, false, 1, 0, 3) X(1, 1, false, 1, 0, 4) X(1, 2, false, 1, 0, 0) X(1, 2, false, 1, 0, 3) X(1, 2, false, 1, 0, 4) X(1, 4, false, 1, 0, 0) X(1, 4, false, 1, 0, 3) X(1, 4, false, 1, 0, 4) \
+    X(1, 1, false, 1, 8, 0) X(1, 1, false, 1, 8, 3) X(1, 1, false, 1, 8, 4) X(1, 1, false, 1, 16, 0) X(1, 1, false, 1, 16, 3) X(1, 1, false, 1, 16, 4) X(1, 2, false, 1, 24, 0) X(1, 2, false, 1, 24, 3) X(1, 2, false, 1, 24, 4)
+
+// 0: launched; 1: no such launch, the run-time module failed (pc_rtc_error), or the plan names a variant that is not in the table (a programming error)
+static int pc_slice_launch(const PcState *S, const PcSlicePlan &p, const PcManyRec *dR, unsigned batch, hipStream_t st)
 {
-    const int D = S->D, nb = S->nb_total;
-    if (D < 25 || D > 64 || S->seq_mode || std::getenv("PC_NHATS_QUAD_MIN")) return 1;
-    dim3 grid(nb, nchains, R);
-    auto lds_q = [](int HV) { return sizeof(double) * (size_t)(2 + HV) * 4 * (HV + 2); };
-    if (D <= 32) hipLaunchKernelGGL((k_nhats_q_many<8>), grid, dim3(128), lds_q(8), st, dR);
-    else hipLaunchKernelGGL((k_nhats_q_many<16>), grid, dim3(256), lds_q(16), st, dR);
-    return 0;
+    if (!p.ok) return 1;
+#define PC_ROW(DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT) \
+    if (!p.many && p.dpl == DPL && p.nrows == NROWS && p.special == SPECIAL && p.wpb == WPB && p.fw == FW && p.lean == LEAN && p.pt == PT) { \
+        if (p.lds > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT>, p.lds); \
+        PC_LAUNCH((k_slice<DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT>), p.grid, p.block, p.lds, st, *S, batch, p.phi_lds, p.mat_lds); \
+        return 0; }
+    PC_SLICE_VARIANTS(PC_ROW)
+#undef PC_ROW
+#define PC_ROW(DPL, NROWS, SPECIAL, WPB, FW, LEAN) \
+    if (p.many && p.dpl == DPL && p.nrows == NROWS && p.special == SPECIAL && p.wpb == WPB && p.fw == FW && p.lean == LEAN && p.pt == 0) { \
+        if (p.lds > 48 * 1024) pc_need_dyn_lds((const void *)k_slice_many<DPL, NROWS, SPECIAL, WPB, FW, LEAN>, p.lds); \
+        PC_LAUNCH((k_slice_many<DPL, NROWS, SPECIAL, WPB, FW, LEAN>), p.grid, p.block, p.lds, st, dR, p.phi_lds, p.mat_lds); \
+        return 0; }
+    PC_SLICE_MANY_VARIANTS(PC_ROW)
+#undef PC_ROW
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "pc_slice_launch: no %s<%d, %d, %d, %d, %d, %d, %d> in the variant table", p.many ? "k_slice_many" : "k_slice",
+                  p.dpl, p.nrows, (int)p.special, p.wpb, p.fw, p.lean, p.pt);
+    pc_abi_set_last_error(msg);
+    return 1;
 }
 
-extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t st)
-{
-    // theta of every baby stays in LDS (derived parameters at the end of the chain) when it fits; so does the
-    // inverse covariance of the correlated Gaussian
-    const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16;     // ybuf + two int decks
-    const size_t tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
-    const int phi_lds = (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
-    size_t sh = sh0 + (phi_lds ? tb : 0) + pc_terms_lds(S);
-    const size_t mb = sizeof(double) * (size_t)S->D * S->D;
-    const bool table = S->prior.kind == 2;      // (a prior table: every likelihood through like_eval, no matrix in LDS)
-    const int mat_lds = (!table && S->like.kind == PC_LIKE_CORR_GAUSSIAN && S->nhat_Ms == nullptr && sh + mb <= 150 * 1024) ? 1 : 0;
-    const int D = S->D;
-    // four chains per workgroup around one LDS copy of the inverse covariance (65 <= nDims <= 128)
-    static const bool wpb_off = std::getenv("PC_SLICE_WPB_OFF") != nullptr;
-    if (mat_lds && D > 64 && D <= 128 && nchains % 4 == 0 && S->ngrade <= 1 && !S->seq_mode && !wpb_off && 4 * sh + mb <= 150 * 1024) {
-        const size_t sh4 = 4 * sh + mb;
-        if (sh4 > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<2, 4, false, 4>, sh4);
-        PC_LAUNCH((k_slice<2, 4, false, 4>), dim3(nchains / 4), dim3(256), sh4, st, *S, batch, phi_lds, mat_lds);
-        return 0;
-    }
-    if (mat_lds) sh += mb;
-    static const bool lean2_off = std::getenv("PC_SLICE_LEAN_OFF") != nullptr;
-    if (!lean2_off && !table && S->like.kind == PC_LIKE_CORR_GAUSSIAN && S->nhat_Ms != nullptr && !(S->ablate & 1) && S->nDer == 0 && S->nr > 64 && D > 64 && D <= 128 &&
-        S->ngrade <= 1 && !S->seq_mode && !mat_lds) {
-        // BASELINE configs[4]'s shape: the kernel without its other variants (LEAN = 2)
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<2, 4, false, 1, 0, 2>, sh);
-        PC_LAUNCH((k_slice<2, 4, false, 1, 0, 2>), dim3(nchains), dim3(64), sh, st, *S, batch, 0, 0);
-        return 0;
-    }
-#define PC_SLICE_LAUNCH1(DPL, NROWS, GR) { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, GR>, sh); \
-        PC_LAUNCH((k_slice<DPL, NROWS, GR>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, mat_lds); }
-    const int leanf = (D <= 64 && !mat_lds) ? slice_lean_functor(S) : 0;
-#define PC_SLICE_LAUNCHT(DPL, NROWS, GR) { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, GR, 1, 0, 0, 1>, sh); \
-        PC_LAUNCH((k_slice<DPL, NROWS, GR, 1, 0, 0, 1>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, 0); }
-#define PC_SLICE_LAUNCHL(DPL, NROWS, LN) { \
-        if (sh > 48 * 1024) pc_need_dyn_lds((const void *)k_slice<DPL, NROWS, false, 1, 0, LN>, sh); \
-        PC_LAUNCH((k_slice<DPL, NROWS, false, 1, 0, LN>), dim3(nchains), dim3(64), sh, st, *S, batch, phi_lds, mat_lds); }
-#define PC_SLICE_LAUNCH(DPL, NROWS) { if (DPL == 1 && leanf == 3) PC_SLICE_LAUNCHL(1, NROWS, 3) else if (DPL == 1 && leanf == 4) PC_SLICE_LAUNCHL(1, NROWS, 4) else if (DPL == 1 && leanf == 5) PC_SLICE_LAUNCHL(1, NROWS, 5) else \
-        if (table) { if (S->ngrade > 1 || S->seq_mode) PC_SLICE_LAUNCHT(DPL, NROWS, true) else PC_SLICE_LAUNCHT(DPL, NROWS, false) } else \
-        if (S->ngrade > 1 || S->seq_mode) PC_SLICE_LAUNCH1(DPL, NROWS, true) else PC_SLICE_LAUNCH1(DPL, NROWS, false) }
-    if (D <= 16) PC_SLICE_LAUNCH(1, 1)
-    else if (D <= 32) PC_SLICE_LAUNCH(1, 2)
-    else if (D <= 64) PC_SLICE_LAUNCH(1, 4)
-    else if (D <= 128) PC_SLICE_LAUNCH(2, 4)
-    else if (D <= 256) PC_SLICE_LAUNCH(4, 4)
-    else return 1;
-#undef PC_SLICE_LAUNCH
-#undef PC_SLICE_LAUNCHT
-#undef PC_SLICE_LAUNCHL
-#undef PC_SLICE_LAUNCH1
-    return 0;
-}
+extern "C" int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t st) { return pc_slice_launch(S, pc_slice_plan(S, nchains, 0, 0), nullptr, batch, st); }
+extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchains, hipStream_t st) { return pc_slice_launch(S, pc_slice_plan(S, nchains, 1, 0), nullptr, batch, st); }
+// Several runs of a device in step: the sampling kernel of any device likelihood launched once for all of them (grid.y = run).
+// 1: a shape only the one-run launchers take.
+extern "C" int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st) { return pc_slice_launch(S, pc_slice_plan(S, nchains, fused, R), dR, 0u, st); }
 
 // pchip_prior_transform: the device transform of the table in S->prior at n points (device pointers)
 extern "C" int pc_launch_prior_transform(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st)
 {
     if (S->prior.kind != 2 || n < 1) return 1;
     const size_t sh = sizeof(double) * S->D;
-    if (S->D <= 64) hipLaunchKernelGGL((k_prior_transform<1>), dim3(n), dim3(64), sh, st, *S, cubes, thetas);
-    else if (S->D <= 128) hipLaunchKernelGGL((k_prior_transform<2>), dim3(n), dim3(64), sh, st, *S, cubes, thetas);
-    else if (S->D <= 256) hipLaunchKernelGGL((k_prior_transform<4>), dim3(n), dim3(64), sh, st, *S, cubes, thetas);
-    else return 1;
-    return 0;
+    switch (pc_dpl(S->D)) {
+    case 1: hipLaunchKernelGGL((k_prior_transform<1>), dim3(n), dim3(64), sh, st, *S, cubes, thetas); return 0;
+    case 2: hipLaunchKernelGGL((k_prior_transform<2>), dim3(n), dim3(64), sh, st, *S, cubes, thetas); return 0;
+    case 4: hipLaunchKernelGGL((k_prior_transform<4>), dim3(n), dim3(64), sh, st, *S, cubes, thetas); return 0;
+    }
+    return 1;
 }
 
 // pchip_source_eval: a source likelihood at n points (device pointers), by the handle's run-time module -- there is no static kernel
 extern "C" int pc_launch_source_eval(const PcState *S, int n, const double *thetas, double *logL, double *phi, hipStream_t st)
 {
-    if (S->like.kind != PC_LIKE_SOURCE || n < 1) return 1;
-    const size_t sh = sizeof(double) * S->D;
-    if (S->D <= 64) return pc_rtc_go(S, "k_source_eval<1>", dim3(n), dim3(64), sh, st, *S, thetas, logL, phi);
-    if (S->D <= 128) return pc_rtc_go(S, "k_source_eval<2>", dim3(n), dim3(64), sh, st, *S, thetas, logL, phi);
-    if (S->D <= 256) return pc_rtc_go(S, "k_source_eval<4>", dim3(n), dim3(64), sh, st, *S, thetas, logL, phi);
-    return 1;
+    const int dpl = pc_dpl(S->D);
+    if (S->like.kind != PC_LIKE_SOURCE || n < 1 || !dpl) return 1;
+    const char *name = dpl == 1 ? "k_source_eval<1>" : (dpl == 2 ? "k_source_eval<2>" : "k_source_eval<4>");
+    return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D, st, *S, thetas, logL, phi);
 }
 #endif  // __HIPCC_RTC__

@@ -21,6 +21,7 @@
 // Gaussian in closed form along the chord, ONE cluster at launch, num_repeats <= 255, derived parameters from the
 // per-baby theta rows (the order k_slice uses whenever those rows fit its LDS).
 #include "pc_state.h"
+#include "pc_launch.h"
 #include <cstdlib>
 
 namespace {
@@ -482,12 +483,20 @@ __global__ __launch_bounds__(HELP ? 192 : 64) void k_slice_t_many(const PcManyRe
 
 static int deck_stride(int nr) { int q = (nr + 3) / 4; if ((q & 1) == 0) q++; return 4 * q; }   // bytes, an odd number of words: lanes on different banks
 
+// a wave's LDS: factor, box, 64 decks, 64 records
+static size_t slice_t_lds(const PcState *S)
+{
+    const int FW = S->D <= 8 ? 8 : (S->D <= 16 ? 16 : 24);
+    return sizeof(double) * ((size_t)S->D * S->D + 2 * FW) + (size_t)64 * deck_stride(S->nr) + sizeof(double) * 64 * (size_t)(S->nT | 1);
+}
+
+// dR: R runs of a device in step (k_slice_t_many, blockIdx.y = run), else one run (k_slice_t).  The choice first -- the unit box, the
+// helping wavefronts, the LDS --, then one launch site per kernel.
 template <int DT>
 static void launch_t(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st)
 {
-    constexpr int FW = DT <= 8 ? 8 : (DT <= 16 ? 16 : 24);
     const int nrp = deck_stride(S->nr), grid = (nchains + 63) / 64;
-    const size_t sh = sizeof(double) * ((size_t)DT * DT + 2 * FW) + (size_t)64 * nrp + sizeof(double) * 64 * (size_t)(S->nT | 1);
+    const size_t sh = slice_t_lds(S);                             // (long decks and wide records: pc_slice_t_ok keeps it under 64 KB)
     const size_t shh = sh + sizeof(double) * (size_t)64 * (DT + 1 + 9);      // + the buffer of the next slice's direction and uniforms
     const bool unit = S->prior.lo == nullptr && S->prior.hi == nullptr;
     static const bool help_off = std::getenv("PC_SLICE_T_HELP_OFF") != nullptr;
@@ -496,21 +505,21 @@ static void launch_t(const PcState *S, const PcManyRec *dR, int R, unsigned batc
     //  own wavefronts share SIMDs with the helpers of their neighbours, and forty-eight runs were no faster than without: 132 ms against 130)
     static const long long help_env = std::getenv("PC_SLICE_T_HELP_MAX") ? std::atoll(std::getenv("PC_SLICE_T_HELP_MAX")) : -1;
     const long long help_max = help_env >= 0 ? help_env : 256LL * std::max<long long>(1, std::min<long long>(2, (long long)(156 * 1024) / (long long)shh));
-    if (dR && !help_off && shh <= 64 * 1024 && (long long)grid * R <= help_max) {      // runs in step: a second wavefront per 64 chains works a slice ahead
-        if (shh > 48 * 1024) { if (unit) pc_need_dyn_lds((const void *)k_slice_t_many<DT, true, true>, shh); else pc_need_dyn_lds((const void *)k_slice_t_many<DT, false, true>, shh); }
-        if (unit) hipLaunchKernelGGL((k_slice_t_many<DT, true, true>), dim3(grid, R), dim3(192), shh, st, dR, nchains, nrp);
-        else hipLaunchKernelGGL((k_slice_t_many<DT, false, true>), dim3(grid, R), dim3(192), shh, st, dR, nchains, nrp);
-        return;
-    }
-    if (sh > 48 * 1024) {                                         // (long decks and wide records: pc_slice_t_ok keeps it under 64 KB)
-        if (dR) { if (unit) pc_need_dyn_lds((const void *)k_slice_t_many<DT, true, false>, sh); else pc_need_dyn_lds((const void *)k_slice_t_many<DT, false, false>, sh); }
-        else { if (unit) pc_need_dyn_lds((const void *)k_slice_t<DT, true>, sh); else pc_need_dyn_lds((const void *)k_slice_t<DT, false>, sh); }
-    }
-    if (dR) {
-        if (unit) hipLaunchKernelGGL((k_slice_t_many<DT, true, false>), dim3(grid, R), dim3(64), sh, st, dR, nchains, nrp);
-        else hipLaunchKernelGGL((k_slice_t_many<DT, false, false>), dim3(grid, R), dim3(64), sh, st, dR, nchains, nrp);
-    } else if (unit) hipLaunchKernelGGL((k_slice_t<DT, true>), dim3(grid), dim3(64), sh, st, *S, batch, nchains, nrp);
-    else hipLaunchKernelGGL((k_slice_t<DT, false>), dim3(grid), dim3(64), sh, st, *S, batch, nchains, nrp);
+    // runs in step: a second wavefront per 64 chains works a slice ahead
+    const bool help = dR && !help_off && shh <= 64 * 1024 && (long long)grid * R <= help_max;
+    const size_t lds = help ? shh : sh;
+#define PC_T_MANY(UNIT, HELP) { \
+        if (lds > 48 * 1024) pc_need_dyn_lds((const void *)k_slice_t_many<DT, UNIT, HELP>, lds); \
+        hipLaunchKernelGGL((k_slice_t_many<DT, UNIT, HELP>), dim3(grid, R), dim3(HELP ? 192 : 64), lds, st, dR, nchains, nrp); }
+#define PC_T_ONE(UNIT) { \
+        if (lds > 48 * 1024) pc_need_dyn_lds((const void *)k_slice_t<DT, UNIT>, lds); \
+        hipLaunchKernelGGL((k_slice_t<DT, UNIT>), dim3(grid), dim3(64), lds, st, *S, batch, nchains, nrp); }
+    // (the kernels lie in the code object in the order of these lines)
+    if (help) { if (unit) PC_T_MANY(true, true) else PC_T_MANY(false, true) }
+    else if (dR) { if (unit) PC_T_MANY(true, false) else PC_T_MANY(false, false) }
+    else { if (unit) PC_T_ONE(true) else PC_T_ONE(false) }
+#undef PC_T_ONE
+#undef PC_T_MANY
 }
 
 }   // namespace
@@ -700,22 +709,15 @@ extern "C" int pc_bases_t_ok(const PcState *S) { return bases_t_takes(S) ? 1 : 0
 extern "C" int pc_launch_bases_t(const PcState *S, unsigned batch, int nchains, hipStream_t st) { return bases_t_dispatch(S, nullptr, 0, batch, nchains, st); }
 extern "C" int pc_launch_bases_t_many(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st) { return bases_t_dispatch(S, dR, R, batch, nchains, st); }
 
-namespace {
-}   // namespace
-
-// what k_slice_t takes; phi_lds_fits = the condition under which k_slice keeps the babies' theta rows in LDS (pc_launch_slice_fused)
+// what k_slice_t takes
 extern "C" int pc_slice_t_ok(const PcState *S, int ncluster)
 {
     static const bool off = std::getenv("PC_SLICE_T_OFF") != nullptr;
     if (off || ncluster != 1 || S->prior.kind == 2) return 0;      // (a prior table: k_slice's general variants)
     if (S->D > 24 || S->ngrade > 1 || S->seq_mode || S->nhat_raw == nullptr || S->nr > 255) return 0;
     if (S->like.kind != PC_LIKE_GAUSSIAN || (S->ablate & 1)) return 0;
-    const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16, tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
-    if (S->nDer > 0 && sh0 + tb > 48 * 1024) return 0;      // (k_slice would take the derived parameters' other summation order)
-    const int FW = S->D <= 8 ? 8 : (S->D <= 16 ? 16 : 24);
-    const size_t sh = sizeof(double) * ((size_t)S->D * S->D + 2 * FW) + (size_t)64 * deck_stride(S->nr) + sizeof(double) * 64 * (size_t)(S->nT | 1);
-    if (sh > 64 * 1024) return 0;                           // (the wave's LDS: factor, box, 64 decks, 64 records)
-    return 1;
+    if (S->nDer > 0 && !pc_slice_phi_lds(S)) return 0;      // (k_slice would take the derived parameters' other summation order)
+    return slice_t_lds(S) <= 64 * 1024;
 }
 
 static int slice_t_dispatch(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st)

@@ -19,6 +19,7 @@
 // mean (the cube centre at first), which the new mean is within a fraction of a standard deviation of, so the
 // subtraction cov = M2/n - delta delta^T loses a digit at most, not the six it would lose about the origin.
 #include "pc_state.h"
+#include "pc_launch.h"
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -606,9 +607,6 @@ __global__ __launch_bounds__(1024) void k_upd_final_w(PcState S, int nb, const d
     if (tid == 0) { count[0] = (int)n; if (!(def && S.ctl->upd_keep_thr)) S.death_thr[0] = -PC_HUGE; if (def) S.ctl->upd_pending = 0; }
 }
 
-extern "C" int pc_update_fused_entries(const PcState *S);
-extern "C" void pc_launch_scan_blocks(int *blk, int nblk, int *total, int *total2, hipStream_t st);
-extern "C" void pc_launch_chol_only(const PcState *S, const double *ncov, const int *count, hipStream_t st);
 static int upd_grid(const PcState *S, int nph, int deferred)
 {
     const int nblk = (nph + UPD_ROWS - 1) / UPD_ROWS, nlb = (S->Ncap + UPD_ROWS - 1) / UPD_ROWS, ndb = deferred ? (S->B + UPD_ROWS - 1) / UPD_ROWS : 0;
