@@ -165,7 +165,10 @@ typedef struct {
                            (deck shuffle and whitening next to the seed choice instead of in front of it): the same numbers; bit 14 = with the helper, the closed
                            form's s.M.s of a direction reduced by the chain at the head of its slice instead of taken from the table the helper made with the
                            whitening (the same bits: the table's sums follow the wave butterfly's order); bit 15 = the sampling kernels of the built-in
-                           likelihoods launched from a module compiled at run time (pchip_source_create's path, PCHIP_PATH_SOURCE_KERNELS): the same numbers */
+                           likelihoods launched from a module compiled at run time (pchip_source_create's path, PCHIP_PATH_SOURCE_KERNELS): the same numbers; bit 16 = the
+                           one-cluster update as a chain of two launches whose last-arriving workgroups go on with the next stage (pc_update.hip)
+                           instead of five launches (flag, index, gather, fold, final): the same rows in the same order and the same groups of
+                           sums, the same bits; slower at the metric configuration, kept as the independent second way the tests compare with */
     const char *resume_write;  /* path of a .resume file (reference grammar, read_write.F90:219-288) rewritten at every
                                   update and at the end; NULL = off */
     int sequential_rng; /* tests: ONE Philox stream consumed in the reference's program order (forces batch = 1 and the

@@ -971,7 +971,7 @@ struct Engine {
         for (int r = 1; r < raw_depth; ++r) raw_buf[r] = ((D <= 24 || split_q || split_m) && S.nhat_raw) ? dalloc<double>(raw_n) : nullptr;
         S.plan = dalloc<PcPlan>(B); S.slot_src = dalloc<int>(Ncap); S.slot_step = dalloc<int>(Ncap); S.slot_dead = dalloc<int>(Ncap); HIPCHK(hipMemsetAsync(S.slot_dead, 0xFF, sizeof(int) * Ncap, st)); S.defer_update = 0; S.sort_slot = dalloc<int>(Ncap + 64); S.sort_key = dalloc<unsigned long long>(Ncap + 64);
         S.ctl = dalloc<PcCtl>(1);
-        d_total = dalloc<int>(1);
+        d_total = dalloc<int>(PC_UPD_CTR_INTS); HIPCHK(hipMemsetAsync(d_total, 0, sizeof(int) * PC_UPD_CTR_INTS, st));      // (the count, and the update chain's tickets: dalloc recycles memory as it is)
         if (callback_mode) {
             d_cs = (void *)dalloc<char>(pc_chain_state_size() * B); d_x0s = dalloc<double>((size_t)B * D); d_prop = dalloc<double>((size_t)B * D);
             const size_t nans = (size_t)B * (1 + D + std::max(1, nDer));
@@ -1431,7 +1431,7 @@ struct Engine {
         const int nph = S.pool ? (int)pool_cursor : h_ctl->nphantom;
         static const bool fused_off = std::getenv("PC_UPDATE_FUSED_OFF") != nullptr;
         if (!fused_off && !(cfg.ablate & 8) && nph > 0 && !cfg.do_clustering && cfg.boost_posterior == 0.0 && pc_update_fused_ok(&S, h_ctl->ncluster)) {
-            // one cluster, nDims < 32: clean + covariance + Cholesky in three launches (pc_update.hip)
+            // one cluster: clean + covariance + Cholesky in five launches (pc_update.hip; settings.ablate bit 16: as a chain of two)
             const size_t need = (size_t)pc_update_fused_blocks(&S, nph) * pc_update_fused_entries(&S);
             if (need > upd_part_cap) { dfree(upd_part); upd_part_cap = 2 * need; upd_part = dalloc<double>(upd_part_cap); }
             if (!upd_shift) {

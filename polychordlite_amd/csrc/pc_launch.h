@@ -142,7 +142,10 @@ int pc_launch_slice_t_many(const PcState *S, const PcManyRec *dR, int R, unsigne
 int pc_update_fused_ok(const PcState *S, int nc);
 int pc_update_fused_blocks(const PcState *S, int nph);
 int pc_update_fused_entries(const PcState *S);
-// nph >= 1.  keep [nph], blk [blocks], part [pc_update_fused_blocks * pc_update_fused_entries] doubles, shift [D]; deferred: see k_upd_flag
+// nph >= 1.  keep [nph], blk [blocks], part [pc_update_fused_blocks * pc_update_fused_entries] doubles, shift [D]; deferred: see k_upd_flag.
+// d_total [PC_UPD_CTR_INTS]: the survivor count and, behind it, the ticket counters of the two-launch chain (settings.ablate bit 16) -- zero
+// when first handed in (the chain leaves them zero)
+#define PC_UPD_CTR_INTS 2048
 void pc_launch_update_fused(const PcState *S, int nph, unsigned char *keep, int *blk, int *d_total, double *ph2, double *phL2, unsigned *phC2,
                             unsigned long long *phU2, double *part, double *shift, int deferred, hipStream_t st);
 int pc_update_fused_grid(const PcState *S, int nph, int deferred);

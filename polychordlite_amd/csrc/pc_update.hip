@@ -1,4 +1,4 @@
-// pc_update.hip -- the update step (nested_sampling.F90:323-368 minus files and clustering) as FOUR short kernels for the
+// pc_update.hip -- the update step (nested_sampling.F90:323-368 minus files and clustering) as FIVE short kernels for the
 // common case: one cluster, nDims < 32.
 //
 //   clean_phantoms (run_time_info.f90:820-877): phantoms below the last death are dropped, the others are compacted;
@@ -9,12 +9,22 @@
 // k_cov_mean_partial / k_fold_partials / k_cov_partial / k_fold_partials / k_cov_final_chol) is nine launches of 4 - 25 us
 // with the host's launch rate between them: ~140 us per update, 31 updates per run at the metric configuration = a fifth
 // of the run.  Here:
-//   k_upd_flag   which phantoms survive, survivors per block of 256 rows
-//   k_upd_gather persistent workgroups: compaction of the survivors into the alternate buffer (offsets from k_scan_blocks;
-//                pool mode: none) and -- in the same pass -- first and second moments of the rows' cube coordinates about a
-//                SHIFT; the live points likewise
-//   k_upd_fold   the blocks' moments added in groups of sixteen
-//   k_upd_final  the groups' moments added, mean / covariance / Cholesky factor, new shift, thresholds reset
+//   k_upd_flag        which phantoms survive, survivors per block of 256 rows
+//   k_upd_index_self  pool mode: the rows that count, by index, in row order (k_upd_scan + k_upd_index beyond 4096 blocks)
+//   k_upd_gather      persistent workgroups: compaction of the survivors into the alternate buffer (offsets from k_scan_blocks;
+//                     pool mode: none) and -- in the same pass -- first and second moments of the rows' cube coordinates about a
+//                     SHIFT; the live points likewise
+//   k_upd_fold        the blocks' moments added in groups of sixteen
+//   k_upd_final       the groups' moments added, mean / covariance / Cholesky factor, new shift, thresholds reset
+// A stage needs all of the stage before it, and three of the five are a memory round trip each.  The same stages as a chain of TWO
+// launches in which no workgroup waits for another exist under settings.ablate bit 16 (a run on its own, pool mode):
+//   k_upd_flag_scan   flag; the workgroup that finishes LAST (a ticket, upd_ticket_last) turns the counts into offsets
+//   k_upd_chain       a gathering workgroup finds the rows of its chunks itself (offsets in LDS, binary search, keep bytes, ballot);
+//                     the last to finish of a group of sixteen folds the group, the last of the groups makes the factor
+// -- the same rows in the same tile rows, the same flushes, the same groups: the same bits (tests/test_update_chain.py).  It is NOT the
+// default: measured at the metric configuration the chain's update is 71 us from its first kernel to the next k_slice against 61 us
+// for the five launches (profiles/update_chain.json) -- what the last arrivers do alone (two ticket round trips, two acquires, fold,
+// final: one workgroup on an otherwise idle chip) and the 5 us a workgroup spends finding its rows cost more than three boundaries.
 // One pass instead of two (mean, then centred products) needs the shift: the moments are taken about the PREVIOUS update's
 // mean (the cube centre at first), which the new mean is within a fraction of a standard deviation of, so the
 // subtraction cov = M2/n - delta delta^T loses a digit at most, not the six it would lose about the origin.
@@ -68,6 +78,9 @@ __device__ __forceinline__ void upd_stage_masked(const double *src0, unsigned lo
 // points that were alive then and have died since (their rows are in the dead array)
 // (a wavefront takes one block of the counts -- 256 rows, four consecutive rows per lane: 32-byte, 16-byte and 4-byte accesses in
 //  place of 8, 4 and 1 -- and a workgroup four of them; the survivors of a block are counted by ballots, no LDS)
+// a value another workgroup of the SAME launch reads behind a ticket (upd_ticket_last): stored write-through at agent scope, so that the
+// ticket needs no release fence (a release writes back the whole L2 of the XCD -- with the sampling kernel's rows still dirty there)
+template <typename T> __device__ __forceinline__ void upd_store_wt(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void upd_flag_body(const PcState &S, int nph, unsigned char *keep, int *blk_count, int def, int nblk)
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -112,10 +125,61 @@ __device__ __forceinline__ void upd_flag_body(const PcState &S, int nph, unsigne
     } else {
         for (int u = 0; u < 4; ++u) if (j0 + u < nph) { keep[j0 + u] = (unsigned char)((kb >> (8 * u)) & 0xFFu); if (wr) S.ph_cuid[j0 + u] = cu[u]; }
     }
-    if (lane == 0) blk_count[sb] = cnt;
+    if (lane == 0) upd_store_wt(blk_count + sb, cnt);        // (write-through: the chain's last arriver reads it in this launch)
 }
 __global__ __launch_bounds__(UPD_NT) void k_upd_flag(PcState S, int nph, unsigned char *keep, int *blk_count, int def, int nblk) { upd_flag_body(S, nph, keep, blk_count, def, nblk); }
 __global__ __launch_bounds__(UPD_NT) void k_upd_flag_many(const PcManyRec *R, int def) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x * 4 >= r.ia[2]) return; upd_flag_body(r.S, r.ia[1], (unsigned char *)r.p[0], (int *)r.p[1], def, r.ia[2]); }
+
+// ------------------------------------------------------------------------------------------------------------------
+// tickets: what lets one launch do the work of several without any workgroup waiting for another.  A workgroup that has written
+// its share -- write-through stores at agent scope (upd_store_wt; the XCDs' L2s are not coherent), drained by every wave -- draws a
+// ticket; the one that draws the last of n acquires at agent scope and goes on with the next stage: it only does more work, nobody
+// spins.  The counters live behind the survivor count (PC_UPD_CTR_INTS ints, zeroed in-stream when the engine allocates them); the
+// last arriver leaves a counter at zero for the next update.  True, for every thread, in the workgroup that drew the last ticket.
+__device__ __forceinline__ bool upd_ticket_last(int *ctr, int n, int *last_s)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int t = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = t == n - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        *last_s = last;
+    }
+    __syncthreads();
+    return *last_s != 0;
+}
+#define UPD_TICKET_FLAG 1                              // ctr[0] is the survivor count (d_total)
+#define UPD_TICKET_FINAL 2
+#define UPD_TICKET_GROUP 16                            // ... + g: the groups of UPD_FOLD records
+
+// launch A of the chain: k_upd_flag, and the workgroup that finishes last turns the counts of the nblk <= UPD_SELF_BLOCKS blocks
+// into exclusive offsets in place (sixteen consecutive counts a thread) and leaves their total
+#define UPD_SELF_BLOCKS 4096
+__global__ __launch_bounds__(UPD_NT) void k_upd_flag_scan(PcState S, int nph, unsigned char *keep, int *blk, int def, int nblk, int *ctr)
+{
+    __shared__ int last_s, wsum[4];
+    upd_flag_body(S, nph, keep, blk, def, nblk);
+    if (!upd_ticket_last(ctr + UPD_TICKET_FLAG, (int)gridDim.x, &last_s)) return;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i0 = 16 * tid;
+    int c[16], s = 0;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { c[u] = (i0 + u < nblk) ? blk[i0 + u] : 0; s += c[u]; }
+    int inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    int run = inc - s;
+    for (int x = 0; x < wv; ++x) run += wsum[x];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { if (i0 + u < nblk) blk[i0 + u] = run; run += c[u]; }
+    if (tid == UPD_NT - 1) ctr[0] = run;
+}
 
 
 // exclusive scan of the block counts in place, one workgroup, 4096 counts at a time (four per thread, coalesced)
@@ -166,7 +230,6 @@ __global__ __launch_bounds__(UPD_NT) void k_upd_index(int nph, const unsigned ch
 // the same without the scan launch in front, for index lists of up to UPD_SELF_BLOCKS blocks: a block's offset is the sum of
 // the counts of the blocks before it, which 256 threads add up from L2 in about a microsecond (at 3750 blocks: 7 M loads on the
 // whole chip) -- less than the one-workgroup scan kernel and the launch boundary behind it (4.7 + 3.5 us per update)
-#define UPD_SELF_BLOCKS 4096
 // (a workgroup of four wavefronts takes sixteen blocks of 256 rows, a wavefront four of them one after the other, four rows a lane:
 //  the counts before the workgroup's first block are added up once for sixteen blocks -- with 2500 blocks a run and sixteen runs
 //  in step the sums were the kernel's time.  Sixteen wavefronts a workgroup did the same at sixteen runs and took 457 us at
@@ -232,6 +295,134 @@ __device__ __forceinline__ void upd_stage_idx(const double *base, const int *rid
     }
 }
 
+// partial records folded in groups of sixteen (one batch of loads per thread), in block order
+#define UPD_FOLD 16
+__device__ __forceinline__ void upd_fold_body(const double *part, int nb, int E, double *part2, int g)
+{
+    for (int e = threadIdx.x; e < E; e += 256) {
+        double t[UPD_FOLD];
+#pragma unroll
+        for (int u = 0; u < UPD_FOLD; ++u) t[u] = (g * UPD_FOLD + u < nb) ? part[(size_t)(g * UPD_FOLD + u) * E + e] : 0.0;
+        double s = 0.0;
+#pragma unroll
+        for (int u = 0; u < UPD_FOLD; ++u) s += t[u];
+        upd_store_wt(part2 + (size_t)g * E + e, s);
+    }
+}
+__global__ __launch_bounds__(256) void k_upd_fold(const double *part, int nb, int E, double *part2) { upd_fold_body(part, nb, E, part2, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_upd_fold_many(const PcManyRec *R, int nb, int E) { double *part = pc_as_global((double *)R[blockIdx.y].p[7], R); upd_fold_body(part, nb, E, part + (size_t)nb * E, blockIdx.x); }
+
+
+// fold + mean + covariance + Cholesky; one workgroup of 256 threads (four wavefronts: what the fold and the D x D copies use)
+// (the groups' records: four interleaved sums per entry -- blocks h, h + 4, ... in that order, sixteen loads of each in flight -- combined
+//  (0 + 1) + (2 + 3))
+__device__ __forceinline__ void upd_final_fold(int nb, const double *part, int E, int nE, double *tot)
+{
+    for (int e = threadIdx.x; e < nE; e += 256) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k0 = 0; k0 < nb; k0 += 4 * 16) {
+            double t[4][16];
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
+#pragma unroll
+                for (int u = 0; u < 16; ++u) t[h][u] = (k0 + h + 4 * u < nb) ? part[(size_t)(k0 + h + 4 * u) * E + e] : 0.0;
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
+#pragma unroll
+                for (int u = 0; u < 16; ++u) s[h] += t[h][u];
+        }
+        tot[e] = (s[0] + s[1]) + (s[2] + s[3]);
+    }
+    __syncthreads();
+}
+// LDS of the final stage, in doubles: tot [544] | A [32 x 32] | L [32 x 32] | mu [32] | bad
+#define UPD_FINAL_LDS (544 + 1024 + 1024 + 32 + 1)
+// DMAX >= D: the bound of the factorisation's unrolled loops.  Rows and columns beyond D are zero and stay zero (0 - l 0), so the
+// statements need no guard of their own: per-element `if (k < D)` inside fully unrolled register loops is a scalar
+// compare-and-branch each (the fault k_nhats had)
+template <int DMAX>
+__device__ __forceinline__ void upd_final_stage(const PcState &S, double *lds, double *shift, int def)
+{
+    double *tot = lds, *A = tot + 544, *L = A + 1024, *mu = L + 1024;
+    int *bad = (int *)(mu + 32);
+    const int tid = threadIdx.x, D = S.D, npair = D * (D + 1) / 2;
+#ifdef UPD_DBG
+    const long long f0 = clock64();
+#endif
+    if (tid == 0) *bad = 0;
+    const double n = tot[npair + D];
+    if (tid < D) mu[tid] = tot[npair + tid] / n;               // delta = mean - shift
+    __syncthreads();
+    for (int p = tid; p < D * D; p += 256) {
+        const int a = p / D, b = p % D, lo = a < b ? a : b, hi = a < b ? b : a;
+        const int idx = lo * D - lo * (lo - 1) / 2 + (hi - lo);
+        const double c = tot[idx] / n - mu[lo] * mu[hi];       // population normalisation, run_time_info.f90:634
+        A[p] = c; L[p] = 0.0;
+        S.cov[p] = c;
+    }
+    __syncthreads();
+#ifdef UPD_DBG
+    const long long f1 = clock64();
+#endif
+    // calc_cholesky (utils.F90:621-649) by one wavefront, lane j = row j held in registers, right-looking: column i is
+    // scaled by 1/sqrt(a_ii), then every later column k loses l_ji l_ki -- the same products subtracted in the same order
+    // (ascending i) as the reference's dot products accumulate them; compile-time indices only (fully unrolled)
+    if (tid < 64) {
+        double a[DMAX];
+#pragma unroll
+        for (int k = 0; k < DMAX; ++k) a[k] = (tid < D && k < D) ? A[tid * D + k] : 0.0;
+        bool fail = false;
+#pragma unroll
+        for (int i = 0; i < DMAX; ++i) {
+            if (i < D && !fail) {
+                const double aii = readlane_f64(a[i], i);
+                if (aii <= 0.0) fail = true;
+                else {
+                    const double lii = sqrt(aii);
+                    const double lji = (tid == i) ? lii : a[i] / lii;
+                    if (tid >= i) a[i] = lji;
+#pragma unroll
+                    for (int k = i + 1; k < DMAX; ++k) { const double lki = readlane_f64(lji, k); if (tid > i) a[k] -= lji * lki; }
+                }
+            }
+        }
+        if (fail) { if (tid == 0) *bad = 1; }
+        else if (tid < D) {
+#pragma unroll
+            for (int k = 0; k < DMAX; ++k) if (k < D) L[tid * D + k] = (k <= tid) ? a[k] : 0.0;
+        }
+    }
+    __syncthreads();
+    if (*bad) {                                                // no Cholesky factor: scaled identity (utils.F90:633-638)
+        double tr = 0.0;
+        for (int k = 0; k < D; ++k) tr += A[k * D + k];
+        for (int p = tid; p < D * D; p += 256) L[p] = (p / D == p % D) ? sqrt(tr) : 0.0;
+        __syncthreads();
+    }
+    for (int p = tid; p < D * D; p += 256) S.chol[p] = L[p];
+    if (tid < D) shift[tid] += mu[tid];                        // the next update's moments are taken about this mean
+    // every survivor is above the last death (k_reset_thresholds) -- unless the launch went on dying after the mark:
+    // then the threshold of the next clean stays the logL of its last death
+    if (tid == 0) { if (!(def && S.ctl->upd_keep_thr)) S.death_thr[0] = -PC_HUGE; if (def) S.ctl->upd_pending = 0; }
+#ifdef UPD_DBG
+    if (tid == 0) { const long long f2 = clock64(); S.ctl->gen_cyc[2] += f1 - f0; S.ctl->gen_cyc[3] += f2 - f1; S.ctl->nn_walks += f0; }
+#endif
+}
+// NT: the gather's tile count when the stage runs inside it (0: any nDims < 32)
+template <int NT>
+__device__ __forceinline__ void upd_final_body(const PcState &S, int nb, const double *part, int E, double *lds, double *shift, int def)
+{
+    const int D = S.D;
+    upd_final_fold(nb, part, E, D * (D + 1) / 2 + D + 1, lds);
+    if (NT != 2 && D <= 8) upd_final_stage<8>(S, lds, shift, def);
+    else if (D <= 16) upd_final_stage<16>(S, lds, shift, def);
+    else if (NT != 1 && D <= 24) upd_final_stage<24>(S, lds, shift, def);
+    else if (NT != 1) upd_final_stage<32>(S, lds, shift, def);
+}
+__global__ __launch_bounds__(256) void k_upd_final(PcState S, int nb, const double *part, int E, double *shift, int def) { __shared__ double lds[UPD_FINAL_LDS]; upd_final_body<0>(S, nb, part, E, lds, shift, def); }
+__global__ __launch_bounds__(256) void k_upd_final_many(const PcManyRec *R, int nb, int E, int def, int G) { __shared__ double lds[UPD_FINAL_LDS]; const PcManyView r = pc_many_view(R, blockIdx.y); upd_final_body<0>(r.S, nb, (const double *)r.p[7] + (size_t)G * E, E, lds, (double *)r.p[8], def); }
+
+
 typedef double upd_v4d __attribute__((ext_vector_type(4)));
 // ------------------------------------------------------------------------------------------------------------------
 // k_upd_gather: ONE pass over the phantom array (and the live points, and for a deferred update the points that died after
@@ -283,12 +474,16 @@ __device__ __forceinline__ int updg_slot(int D, int ti, int tj, int li, int lk, 
     return (b < D) ? a * D - a * (a - 1) / 2 + (b - a) : (a < D ? npair + a : npair + D);
 }
 
-template <int NT, bool IDX>
+// CHAIN (pool mode, launch B of the chain): there is no index list -- blk_off holds the blocks' exclusive offsets (k_upd_flag_scan)
+// and a workgroup finds the rows of its chunks itself; nDims < 32: it also goes on to the fold and the final stage by ticket
+// (ctr: upd_ticket_last)
+template <int NT, bool IDX, bool CHAIN>
 __device__ __forceinline__ void upd_gather_body(const PcState &S, int nph, int nblk, const unsigned char *keep, const int *blk_off,
                                                 double *ph2, double *phL2, unsigned *phC2, unsigned long long *phU2,
                                                 const int *idx, const int *nidx_p,
-                                                const double *shift, double *part, int E, int def, int nlb, int ndb)
+                                                const double *shift, double *part, int E, int def, int nlb, int ndb, double *shift_out = nullptr, int *ctr = nullptr)
 {
+    static_assert(!CHAIN || IDX, "the chain is pool mode's");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr bool KS = NT <= 2;
     // row stride: odd (K split: the four row groups of an operand start in different banks) / 16 mod 32 doubles (pair split)
@@ -296,7 +491,7 @@ __device__ __forceinline__ void upd_gather_body(const PcState &S, int nph, int n
     constexpr int CAP = KS ? 128 : 64;                                  // tile rows; a flush when the next 64-row piece does not fit
     constexpr int NACC = KS ? NT * (NT + 1) / 2 : (NT * (NT + 1) / 2 + 3) / 4;
     __shared__ unsigned long long m64[4], mm64[4];
-    __shared__ long long dix[256];
+    __shared__ int dix[256];
     const int tmark = def ? S.ctl->upd_tmark : 0x7fffffff, nph0u = def ? S.ctl->upd_nph0 : 0x7fffffff, updT = def ? S.ctl->upd_T : 0;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4, D = S.D, nT = S.nT;
     constexpr bool pool = IDX;                                          // (pool mode always comes with the index list)
@@ -308,6 +503,9 @@ __device__ __forceinline__ void upd_gather_body(const PcState &S, int nph, int n
 #pragma unroll
     for (int t = 0; t < NACC; ++t) acc[t] = upd_v4d{0.0, 0.0, 0.0, 0.0};
     int nfill = 0;
+#ifdef UPD_DBG
+    const long long g0 = clock64();
+#endif
     auto flush = [&]() __attribute__((always_inline)) {
         __syncthreads();
         const int n16 = (nfill + 15) & ~15;
@@ -336,6 +534,43 @@ __device__ __forceinline__ void upd_gather_body(const PcState &S, int nph, int n
         // wave, no masks, no barriers but the flushes
         const int nidx = *nidx_p;
         const int gchunk = (int)gridDim.x - nlb - ndb;                      // the last nlb + ndb workgroups take a live / dead block each
+        if constexpr (CHAIN) {
+            // chunk c is the rows 64 c .. 64 c + 63 of "the rows that count, in row order" (what k_upd_index_self lists): the blocks
+            // that hold them are found in the offsets (LDS, binary search), their keep bytes read, the rows picked by ballot
+            __shared__ int off_s[UPD_SELF_BLOCKS + 1], ridx_s[2][64];
+            const bool mine = (int)blockIdx.x < gchunk && (int)blockIdx.x * 64 < nidx;
+            if (mine) {
+                for (int b = tid; b < nblk; b += 256) off_s[b] = blk_off[b];
+                if (tid == 0) off_s[nblk] = nidx;
+                __syncthreads();
+            }
+            const unsigned long long below = (1ull << lane) - 1ull;
+            int par = 0;
+            for (int c = blockIdx.x; mine && c * 64 < nidx; c += gchunk, par ^= 1) {
+                const int p0 = c * 64, have = min(64, nidx - p0), p1 = p0 + have;
+                if (nfill + have > CAP) flush();
+                int lo = 0, hi = nblk - 1;                                  // the last block whose offset is <= p0 holds row p0
+                while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (off_s[mid] <= p0) lo = mid; else hi = mid - 1; }
+                for (int sb = lo + wv; sb < nblk; sb += 4) {
+                    const int o = off_s[sb];
+                    if (o >= p1) break;
+                    if (off_s[sb + 1] == o) continue;
+                    const int j0 = sb * UPD_ROWS + 4 * lane;
+                    unsigned w = 0;
+                    if (j0 + 3 < nph) w = *(const unsigned *)(keep + j0);
+                    else for (int u = 0; u < 4; ++u) if (j0 + u < nph) w |= (unsigned)keep[j0 + u] << (8 * u);
+                    int pos = o;
+                    bool f[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) { f[u] = (w >> (8 * u + 1)) & 1u; pos += __popcll(__ballot(f[u]) & below); }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) if (f[u]) { if (pos >= p0 && pos < p1) ridx_s[par][pos - p0] = j0 + u; pos++; }
+                }
+                __syncthreads();                                            // (two lists in turn: a list is rewritten two barriers after it was read)
+                upd_stage_idx(S.phantom, ridx_s[par] + 16 * wv, min(16, have - 16 * wv), tile + (size_t)(nfill + 16 * wv) * TS, TS, sh, D, nT, lane);
+                nfill += have;
+            }
+        } else
         for (int c = blockIdx.x; (int)blockIdx.x < gchunk && c * 64 < nidx; c += gchunk) {
             const int have = min(64, nidx - c * 64);
             if (nfill + have > CAP) flush();
@@ -382,39 +617,35 @@ __device__ __forceinline__ void upd_gather_body(const PcState &S, int nph, int n
         } else {
             // ---- def: points alive at the mark that died later in the launch: the dead rows of the steps t >= tmark whose
             //      dying point was a snapshot point or the newcomer of a step before the mark; scattered in the dead array:
-            //      the four waves take them in turn, lane = coordinate
+            //      their indices are collected first, then loaded like the phantoms of the index list
             const PcCtl *ctl = S.ctl;
             const int T = ctl->upd_T, ts = ctl->upd_ts;
             const int t = tmark + (b - nblk - nlb) * 256 + tid;
-            long long di = -1;
+            int di = -1;
             if (t < ts) {
                 const PcPlan *pw = S.plan + (T - 1 - t);
                 const int src = pw->dead_src;
                 const bool existed = src >= 0 || (T - 1 - (-src - 1)) < tmark;
                 if (pw->dead_idx >= 0 && pw->logw > S.logzero && existed) di = pw->dead_idx;
             }
-            dix[tid] = di;
             const unsigned long long m = __ballot(di >= 0);
+            if (di >= 0) dix[wv * 64 + __popcll(m & ((1ull << lane) - 1ull))] = (int)di;      // the piece's rows, in step order
             if (lane == 0) m64[wv] = m;
             __syncthreads();
+            // (piece after piece, a wavefront sixteen rows of it, all their loads in flight: a row's tile row is its place in the
+            //  piece, a flush falls where it fell when the rows were loaded one after the other)
             for (int sub = 0; sub < 4; ++sub) {
-                unsigned long long mb = m64[sub];
-                const int cnt = __popcll(mb);
+                const int cnt = __popcll(m64[sub]);
                 if (cnt == 0) continue;
                 if (nfill + cnt > CAP) flush();
-                int row = 0;
-                while (mb) {
-                    const int bit = __ffsll((long long)mb) - 1; mb &= mb - 1;
-                    if ((row & 3) == wv) {
-                        const long long d = dix[sub * 64 + bit];
-                        for (int e = lane; e <= D; e += 64) tile[(size_t)(nfill + row) * TS + e] = e < D ? S.dead[(size_t)d * nT + e] - sh[e] : 1.0;
-                    }
-                    row++;
-                }
+                upd_stage_idx(S.dead, dix + sub * 64 + 16 * wv, min(16, cnt - 16 * wv), tile + (size_t)(nfill + 16 * wv) * TS, TS, sh, D, nT, lane);
                 nfill += cnt;
             }
         }
     }
+#ifdef UPD_DBG
+    const long long g1 = clock64();
+#endif
     flush();
     double *out = part + (size_t)blockIdx.x * E;
     if constexpr (KS) {
@@ -434,7 +665,7 @@ __device__ __forceinline__ void upd_gather_body(const PcState &S, int nph, int n
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int p = updg_slot(D, ti, tj, li, lk, r), idx = (lk + 4 * r) * 16 + li;
-                        if (p >= 0) out[p] = ((wres[(size_t)(0 * NACC + q) * 256 + idx] + wres[(size_t)(1 * NACC + q) * 256 + idx]) +
+                        if (p >= 0) upd_store_wt(out + p, (wres[(size_t)(0 * NACC + q) * 256 + idx] + wres[(size_t)(1 * NACC + q) * 256 + idx]) +
                                               (wres[(size_t)(2 * NACC + q) * 256 + idx] + wres[(size_t)(3 * NACC + q) * 256 + idx]));
                     }
         }
@@ -449,131 +680,44 @@ __device__ __forceinline__ void upd_gather_body(const PcState &S, int nph, int n
                     for (int r = 0; r < 4; ++r) { const int p = updg_slot(D, ti, tj, li, lk, r); if (p >= 0) out[p] = acc[q >> 2][r]; }
                 }
     }
+#ifdef UPD_DBG
+    // cycles of a workgroup by kind (0 index chunks, 1 live block, 2 dead-after-mark block) up to the last flush; 3: flush + write-out
+    if (IDX && tid == 0) {
+        const int gch = (int)gridDim.x - nlb - ndb, kind = (int)blockIdx.x < gch ? 0 : ((int)blockIdx.x < gch + nlb ? 1 : 2);
+        atomicAdd((unsigned long long *)&S.ctl->wave_cyc[kind], (unsigned long long)(g1 - g0));
+        atomicAdd((unsigned long long *)&S.ctl->wave_cyc[3], (unsigned long long)(clock64() - g1));
+    }
+#endif
+    if constexpr (CHAIN && KS) {
+        // the record is written: whoever completes a group of UPD_FOLD records adds them up (k_upd_fold's additions), whoever
+        // completes the groups makes the factor (k_upd_final's statements); the row tile serves as the final stage's LDS
+        static_assert(sizeof(double) * UPD_FINAL_LDS <= sizeof(double) * 4 * 3 * 256, "the final stage's LDS fits the row tile");
+        __shared__ int last_s;
+        const int G = gridDim.x, g = blockIdx.x / UPD_FOLD, ng = (G + UPD_FOLD - 1) / UPD_FOLD;
+        double *part2 = part + (size_t)G * E;
+        if (!upd_ticket_last(ctr + UPD_TICKET_GROUP + g, min(UPD_FOLD, G - g * UPD_FOLD), &last_s)) return;
+        upd_fold_body(part, G, E, part2, g);
+        if (!upd_ticket_last(ctr + UPD_TICKET_FINAL, ng, &last_s)) return;
+        upd_final_body<NT>(S, ng, part2, E, tile, shift_out, def);
+    }
 }
 template <int NT, bool IDX>
 __global__ __launch_bounds__(256) void k_upd_gather(PcState S, int nph, int nblk, const unsigned char *keep, const int *blk_off,
                                                     double *ph2, double *phL2, unsigned *phC2, unsigned long long *phU2,
                                                     const int *idx, const int *nidx_p,
                                                     const double *shift, double *part, int E, int def, int nlb, int ndb)
-{ upd_gather_body<NT, IDX>(S, nph, nblk, keep, blk_off, ph2, phL2, phC2, phU2, idx, nidx_p, shift, part, E, def, nlb, ndb); }
+{ upd_gather_body<NT, IDX, false>(S, nph, nblk, keep, blk_off, ph2, phL2, phC2, phU2, idx, nidx_p, shift, part, E, def, nlb, ndb); }
+// launch B of the chain (pool mode): locate + gather, and for nDims < 32 fold + final; blk_off: the offsets, ctr[0] their total
+template <int NT>
+__global__ __launch_bounds__(256) void k_upd_chain(PcState S, int nph, int nblk, const unsigned char *keep, const int *blk_off, double *shift, double *part, int E, int def, int nlb, int ndb, int *ctr)
+{ upd_gather_body<NT, true, true>(S, nph, nblk, keep, blk_off, nullptr, nullptr, nullptr, nullptr, nullptr, ctr, shift, part, E, def, nlb, ndb, shift, ctr); }
 template <int NT>
 __global__ __launch_bounds__(256) void k_upd_gather_many(const PcManyRec *R, int E, int def, int nlb, int ndb)
 {
     const PcManyView r = pc_many_view(R, blockIdx.y);
-    upd_gather_body<NT, true>(r.S, r.ia[1], r.ia[2], (const unsigned char *)r.p[0], (const int *)r.p[1], (double *)r.p[3], (double *)r.p[4], (unsigned *)r.p[5],
+    upd_gather_body<NT, true, false>(r.S, r.ia[1], r.ia[2], (const unsigned char *)r.p[0], (const int *)r.p[1], (double *)r.p[3], (double *)r.p[4], (unsigned *)r.p[5],
                               (unsigned long long *)r.p[6], (const int *)r.p[5], (const int *)r.p[2], (const double *)r.p[8], (double *)r.p[7], E, def, nlb, ndb);
 }
-
-
-// partial records folded in groups of sixteen (one batch of loads per thread), in block order
-#define UPD_FOLD 16
-__device__ __forceinline__ void upd_fold_body(const double *part, int nb, int E, double *part2)
-{
-    const int g = blockIdx.x;
-    for (int e = threadIdx.x; e < E; e += 256) {
-        double t[UPD_FOLD];
-#pragma unroll
-        for (int u = 0; u < UPD_FOLD; ++u) t[u] = (g * UPD_FOLD + u < nb) ? part[(size_t)(g * UPD_FOLD + u) * E + e] : 0.0;
-        double s = 0.0;
-#pragma unroll
-        for (int u = 0; u < UPD_FOLD; ++u) s += t[u];
-        part2[(size_t)g * E + e] = s;
-    }
-}
-__global__ __launch_bounds__(256) void k_upd_fold(const double *part, int nb, int E, double *part2) { upd_fold_body(part, nb, E, part2); }
-__global__ __launch_bounds__(256) void k_upd_fold_many(const PcManyRec *R, int nb, int E) { double *part = pc_as_global((double *)R[blockIdx.y].p[7], R); upd_fold_body(part, nb, E, part + (size_t)nb * E); }
-
-
-// fold + mean + covariance + Cholesky; one workgroup of 1024 threads
-__device__ __forceinline__ void upd_final_body(const PcState &S, int nb, const double *part, int E, double *shift, int def)
-{
-    __shared__ double acc[4][256];                 // E <= 256 * 2: entries beyond 256 take a second round
-    __shared__ double A[32 * 32], L[32 * 32], mu[32];
-    __shared__ int bad;
-    const int tid = threadIdx.x, D = S.D, npair = D * (D + 1) / 2, nE = npair + D + 1;
-    __shared__ double tot[544];
-    for (int e0 = 0; e0 < nE; e0 += 256) {
-        const int e = e0 + (tid & 255), h = tid >> 8;         // four threads per entry: blocks h, h+4, ... in that order
-        double s = 0.0;
-        if (e < nE) {
-            for (int k = h; k < nb; k += 4 * 16) {            // sixteen loads in flight, added in block order (no serial tail)
-                double t[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) t[u] = (k + 4 * u < nb) ? part[(size_t)(k + 4 * u) * E + e] : 0.0;
-#pragma unroll
-                for (int u = 0; u < 16; ++u) s += t[u];
-            }
-        }
-        acc[h][tid & 255] = s;
-        __syncthreads();
-        if (tid < 256 && e < nE) tot[e] = (acc[0][tid] + acc[1][tid]) + (acc[2][tid] + acc[3][tid]);
-        __syncthreads();
-    }
-#ifdef UPD_DBG
-    const long long f0 = clock64();
-#endif
-    if (tid == 0) bad = 0;
-    const double n = tot[npair + D];
-    if (tid < D) mu[tid] = tot[npair + tid] / n;               // delta = mean - shift
-    __syncthreads();
-    for (int p = tid; p < D * D; p += 1024) {
-        const int a = p / D, b = p % D, lo = a < b ? a : b, hi = a < b ? b : a;
-        const int idx = lo * D - lo * (lo - 1) / 2 + (hi - lo);
-        const double c = tot[idx] / n - mu[lo] * mu[hi];       // population normalisation, run_time_info.f90:634
-        A[p] = c; L[p] = 0.0;
-        S.cov[p] = c;
-    }
-    __syncthreads();
-#ifdef UPD_DBG
-    const long long f1 = clock64();
-#endif
-    // calc_cholesky (utils.F90:621-649) by one wavefront, lane j = row j held in registers, right-looking: column i is
-    // scaled by 1/sqrt(a_ii), then every later column k loses l_ji l_ki -- the same products subtracted in the same order
-    // (ascending i) as the reference's dot products accumulate them; compile-time indices only (fully unrolled)
-    if (tid < 64) {
-        double a[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) a[k] = (tid < D && k < D) ? A[tid * D + k] : 0.0;
-        bool fail = false;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            if (i < D && !fail) {
-                const double aii = readlane_f64(a[i], i);
-                if (aii <= 0.0) fail = true;
-                else {
-                    const double lii = sqrt(aii);
-                    const double lji = (tid == i) ? lii : a[i] / lii;
-                    if (tid >= i) a[i] = lji;
-#pragma unroll
-                    for (int k = i + 1; k < 32; ++k)
-                        if (k < D) { const double lki = readlane_f64(lji, k); if (tid > i) a[k] -= lji * lki; }
-                }
-            }
-        }
-        if (fail) { if (tid == 0) bad = 1; }
-        else if (tid < D) {
-#pragma unroll
-            for (int k = 0; k < 32; ++k) if (k < D) L[tid * D + k] = (k <= tid) ? a[k] : 0.0;
-        }
-    }
-    __syncthreads();
-    if (bad) {                                                 // no Cholesky factor: scaled identity (utils.F90:633-638)
-        double tr = 0.0;
-        for (int k = 0; k < D; ++k) tr += A[k * D + k];
-        for (int p = tid; p < D * D; p += 1024) L[p] = (p / D == p % D) ? sqrt(tr) : 0.0;
-        __syncthreads();
-    }
-    for (int p = tid; p < D * D; p += 1024) S.chol[p] = L[p];
-    if (tid < D) shift[tid] += mu[tid];                        // the next update's moments are taken about this mean
-    // every survivor is above the last death (k_reset_thresholds) -- unless the launch went on dying after the mark:
-    // then the threshold of the next clean stays the logL of its last death
-    if (tid == 0) { if (!(def && S.ctl->upd_keep_thr)) S.death_thr[0] = -PC_HUGE; if (def) S.ctl->upd_pending = 0; }
-#ifdef UPD_DBG
-    if (tid == 0) { const long long f2 = clock64(); S.ctl->gen_cyc[2] += f1 - f0; S.ctl->gen_cyc[3] += f2 - f1; S.ctl->nn_walks += f0; }
-#endif
-}
-__global__ __launch_bounds__(1024) void k_upd_final(PcState S, int nb, const double *part, int E, double *shift, int def) { upd_final_body(S, nb, part, E, shift, def); }
-__global__ __launch_bounds__(1024) void k_upd_final_many(const PcManyRec *R, int nb, int E, int def, int G) { const PcManyView r = pc_many_view(R, blockIdx.y); upd_final_body(r.S, nb, (const double *)r.p[7] + (size_t)G * E, E, (double *)r.p[8], def); }
 
 
 // records added up; delta = mean - shift; n cov = M2 - n delta delta^T for k_cov_final_chol (which divides by n, stores the
@@ -638,29 +782,44 @@ extern "C" void pc_launch_update_fused(const PcState *S, int nph, unsigned char 
     double *part2 = part + (size_t)G * E;
     size_t shw = sizeof(double) * ((size_t)CAPv * TSv + D);
     if (NTv <= 2 && shw < sizeof(double) * (size_t)(4 * 3 * 256)) shw = sizeof(double) * (size_t)(4 * 3 * 256);      // the waves' result tiles reuse the row tile
-    hipLaunchKernelGGL(k_upd_flag, dim3((nblk + 3) / 4), dim3(UPD_NT), 0, st, *S, nph, keep, blk, deferred, nblk);
-    if (!S->pool) pc_launch_scan_blocks(blk, nblk, d_total, &S->ctl->nphantom, st);
-    else if (nblk <= UPD_SELF_BLOCKS && !std::getenv("PC_UPD_SCAN_LAUNCH"))
-        hipLaunchKernelGGL(k_upd_index_self, dim3((nblk + 15) / 16), dim3(UPD_IDX_NT), 0, st, nph, (const unsigned char *)keep, (const int *)blk, nblk, (int *)phC2, d_total);
-    else {
-        hipLaunchKernelGGL(k_upd_scan, dim3(1), dim3(1024), 0, st, blk, nblk, d_total);
-        hipLaunchKernelGGL(k_upd_index, dim3(nblk), dim3(UPD_NT), 0, st, nph, (const unsigned char *)keep, (const int *)blk, (int *)phC2);
-    }
-    int devi = 0; (void)hipGetDevice(&devi); devi &= 63;
+    // settings.ablate bit 16: the chain (pool mode, up to UPD_SELF_BLOCKS blocks, tickets for every group): flag + offsets, then locate +
+    // gather (+ fold + final below 32 dimensions) -- the same bits, 10 us an update slower than the launches below (header comment)
+    if (S->pool && nblk <= UPD_SELF_BLOCKS && UPD_TICKET_GROUP + ng <= PC_UPD_CTR_INTS && (S->ablate & (1 << 16))) {
+        int *ctr = d_total;
+        hipLaunchKernelGGL(k_upd_flag_scan, dim3((nblk + 3) / 4), dim3(UPD_NT), 0, st, *S, nph, keep, blk, deferred, nblk, ctr);
+#define UPDC_LAUNCH(NT) { \
+        pc_need_dyn_lds((const void *)k_upd_chain<NT>, shw); \
+        hipLaunchKernelGGL((k_upd_chain<NT>), dim3(G), dim3(256), shw, st, *S, nph, nblk, (const unsigned char *)keep, (const int *)blk, shift, part, E, deferred, nlb, ndb, ctr); }
+        switch (NTv) { case 1: UPDC_LAUNCH(1) break; case 2: UPDC_LAUNCH(2) break; case 3: UPDC_LAUNCH(3) break; case 4: UPDC_LAUNCH(4) break;
+                       case 5: UPDC_LAUNCH(5) break; case 6: UPDC_LAUNCH(6) break; case 7: UPDC_LAUNCH(7) break; case 8: UPDC_LAUNCH(8) break;
+                       default: UPDC_LAUNCH(9) break; }
+#undef UPDC_LAUNCH
+        if (D < 32) return;
+    } else {
+        hipLaunchKernelGGL(k_upd_flag, dim3((nblk + 3) / 4), dim3(UPD_NT), 0, st, *S, nph, keep, blk, deferred, nblk);
+        if (!S->pool) pc_launch_scan_blocks(blk, nblk, d_total, &S->ctl->nphantom, st);
+        else if (nblk <= UPD_SELF_BLOCKS && !std::getenv("PC_UPD_SCAN_LAUNCH"))
+            hipLaunchKernelGGL(k_upd_index_self, dim3((nblk + 15) / 16), dim3(UPD_IDX_NT), 0, st, nph, (const unsigned char *)keep, (const int *)blk, nblk, (int *)phC2, d_total);
+        else {
+            hipLaunchKernelGGL(k_upd_scan, dim3(1), dim3(1024), 0, st, blk, nblk, d_total);
+            hipLaunchKernelGGL(k_upd_index, dim3(nblk), dim3(UPD_NT), 0, st, nph, (const unsigned char *)keep, (const int *)blk, (int *)phC2);
+        }
+        int devi = 0; (void)hipGetDevice(&devi); devi &= 63;
 #define UPDG_LAUNCH(NT) { \
-        pc_need_dyn_lds((const void *)k_upd_gather<NT, false>, shw); \
-                          pc_need_dyn_lds((const void *)k_upd_gather<NT, true>, shw); \
-        /* pool mode: the alternate id buffer is free between compactions and holds the index list, *d_total its length */ \
-        if (S->pool) hipLaunchKernelGGL((k_upd_gather<NT, true>), dim3(G), dim3(256), shw, st, *S, nph, nblk, (const unsigned char *)keep, (const int *)blk, \
-                           ph2, phL2, phC2, phU2, (const int *)phC2, (const int *)d_total, (const double *)shift, part, E, deferred, nlb, ndb); \
-        else hipLaunchKernelGGL((k_upd_gather<NT, false>), dim3(G), dim3(256), shw, st, *S, nph, nblk, (const unsigned char *)keep, (const int *)blk, \
-                           ph2, phL2, phC2, phU2, (const int *)nullptr, (const int *)nullptr, (const double *)shift, part, E, deferred, nlb, ndb); }
-    switch (NTv) { case 1: UPDG_LAUNCH(1) break; case 2: UPDG_LAUNCH(2) break; case 3: UPDG_LAUNCH(3) break; case 4: UPDG_LAUNCH(4) break;
-                   case 5: UPDG_LAUNCH(5) break; case 6: UPDG_LAUNCH(6) break; case 7: UPDG_LAUNCH(7) break; case 8: UPDG_LAUNCH(8) break;
-                   default: UPDG_LAUNCH(9) break; }
+            pc_need_dyn_lds((const void *)k_upd_gather<NT, false>, shw); \
+                              pc_need_dyn_lds((const void *)k_upd_gather<NT, true>, shw); \
+            /* pool mode: the alternate id buffer is free between compactions and holds the index list, *d_total its length */ \
+            if (S->pool) hipLaunchKernelGGL((k_upd_gather<NT, true>), dim3(G), dim3(256), shw, st, *S, nph, nblk, (const unsigned char *)keep, (const int *)blk, \
+                               ph2, phL2, phC2, phU2, (const int *)phC2, (const int *)d_total, (const double *)shift, part, E, deferred, nlb, ndb); \
+            else hipLaunchKernelGGL((k_upd_gather<NT, false>), dim3(G), dim3(256), shw, st, *S, nph, nblk, (const unsigned char *)keep, (const int *)blk, \
+                               ph2, phL2, phC2, phU2, (const int *)nullptr, (const int *)nullptr, (const double *)shift, part, E, deferred, nlb, ndb); }
+        switch (NTv) { case 1: UPDG_LAUNCH(1) break; case 2: UPDG_LAUNCH(2) break; case 3: UPDG_LAUNCH(3) break; case 4: UPDG_LAUNCH(4) break;
+                       case 5: UPDG_LAUNCH(5) break; case 6: UPDG_LAUNCH(6) break; case 7: UPDG_LAUNCH(7) break; case 8: UPDG_LAUNCH(8) break;
+                       default: UPDG_LAUNCH(9) break; }
 #undef UPDG_LAUNCH
+    }
     hipLaunchKernelGGL(k_upd_fold, dim3(ng), dim3(256), 0, st, (const double *)part, G, E, part2);
-    if (D < 32) { hipLaunchKernelGGL(k_upd_final, dim3(1), dim3(1024), 0, st, *S, ng, (const double *)part2, E, shift, deferred); return; }
+    if (D < 32) { hipLaunchKernelGGL(k_upd_final, dim3(1), dim3(256), 0, st, *S, ng, (const double *)part2, E, shift, deferred); return; }
     double *ncov = part2 + (size_t)ng * E;
     int *count = (int *)(ncov + (size_t)D * D);
     const size_t shf = sizeof(double) * (size_t)(D * (D + 1) / 2 + D + 1);
@@ -691,6 +850,6 @@ extern "C" int pc_launch_update_fused_many(const PcState *S, const PcManyRec *dR
     if (NTv == 1) UPDM_LAUNCH(1) else UPDM_LAUNCH(2)
 #undef UPDM_LAUNCH
     hipLaunchKernelGGL(k_upd_fold_many, dim3(ng, R), dim3(256), 0, st, dR, G, E);
-    hipLaunchKernelGGL(k_upd_final_many, dim3(1, R), dim3(1024), 0, st, dR, ng, E, deferred, G);
+    hipLaunchKernelGGL(k_upd_final_many, dim3(1, R), dim3(256), 0, st, dR, ng, E, deferred, G);
     return 0;
 }
