@@ -399,43 +399,43 @@ __global__ __launch_bounds__(256) void k_shift_mats(PcState S, int p, int nc)
     }
 }
 
-// the first pass for several runs in step: blockIdx.z = run, every run its own descriptors and scratch (PcManyRec::p: 0 descriptors,
-// 1 similarity blocks, 2 neighbour lists, 3 labels, 4 verdicts; ia[1] = clusters looked at)
+// the first pass for several runs in step: blockIdx.z = run, every run its own descriptors and scratch (PcManyRec::p under
+// PC_REC_DESC .. PC_REC_OUT; ia[PC_REC_I_ND] = clusters looked at)
 __global__ __launch_bounds__(256) void k_similarity_b_many(const PcManyRec *__restrict__ R)
 {
     const PcManyView r = pc_many_view(R, blockIdx.z);
-    if ((int)blockIdx.y >= r.ia[1]) return;
-    const ClusDesc d = ((const ClusDesc *)r.p[0])[blockIdx.y];
+    if ((int)blockIdx.y >= r.ia[PC_REC_I_ND]) return;
+    const ClusDesc d = ((const ClusDesc *)r.p[PC_REC_DESC])[blockIdx.y];
     if ((int)blockIdx.x >= d.n) return;
-    similarity_body(r.S, r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[1] + d.off2, 0, 256);
+    similarity_body(r.S, r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[PC_REC_SM] + d.off2, 0, 256);
 }
-// ... launched instead when a run of the launch makes its sub-dimension pass (p[5] its coordinates, ia[3] how many; a run with ia[3] = 0
+// ... launched instead when a run of the launch makes its sub-dimension pass (PC_REC_DIMS its coordinates, PC_REC_I_ND_SUB how many; a run with none
 // in the same launch makes its full pass here, by the full-space body)
 __global__ __launch_bounds__(256) void k_similarity_b_many_sub(const PcManyRec *__restrict__ R)
 {
     const PcManyView r = pc_many_view(R, blockIdx.z);
-    if ((int)blockIdx.y >= r.ia[1]) return;
-    const ClusDesc d = ((const ClusDesc *)r.p[0])[blockIdx.y];
+    if ((int)blockIdx.y >= r.ia[PC_REC_I_ND]) return;
+    const ClusDesc d = ((const ClusDesc *)r.p[PC_REC_DESC])[blockIdx.y];
     if ((int)blockIdx.x >= d.n) return;
-    if (r.ia[3] > 0) similarity_sub_body(r.S, (const int *)r.p[5], r.ia[3], r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[1] + d.off2, 0, 256);
-    else similarity_body(r.S, r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[1] + d.off2, 0, 256);
+    if (r.ia[PC_REC_I_ND_SUB] > 0) similarity_sub_body(r.S, (const int *)r.p[PC_REC_DIMS], r.ia[PC_REC_I_ND_SUB], r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[PC_REC_SM] + d.off2, 0, 256);
+    else similarity_body(r.S, r.S.cl_list + (size_t)d.c * r.S.Ncap, d.n, (double *)r.p[PC_REC_SM] + d.off2, 0, 256);
 }
 __global__ __launch_bounds__(256) void k_knn_sort_b_many(const PcManyRec *__restrict__ R)
 {
     const PcManyView r = pc_many_view(R, blockIdx.z);
-    if ((int)blockIdx.y >= r.ia[1]) return;
-    const ClusDesc d = ((const ClusDesc *)r.p[0])[blockIdx.y];
+    if ((int)blockIdx.y >= r.ia[PC_REC_I_ND]) return;
+    const ClusDesc d = ((const ClusDesc *)r.p[PC_REC_DESC])[blockIdx.y];
     if ((int)blockIdx.x >= d.n) return;
     int npow2 = 2;
     while (npow2 < d.n) npow2 <<= 1;
-    knn_sort_body((const double *)r.p[1] + d.off2, d.n, nullptr, d.n, npow2, (int *)r.p[2] + d.off2);
+    knn_sort_body((const double *)r.p[PC_REC_SM] + d.off2, d.n, nullptr, d.n, npow2, (int *)r.p[PC_REC_KNN] + d.off2);
 }
 __global__ __launch_bounds__(1024) void k_nn_cluster_b_many(const PcManyRec *__restrict__ R)
 {
     const PcManyView r = pc_many_view(R, blockIdx.y);
-    if ((int)blockIdx.x >= r.ia[1]) return;
-    const ClusDesc d = ((const ClusDesc *)r.p[0])[blockIdx.x];
-    nn_cluster_body((const int *)r.p[2] + d.off2, d.n, (int *)r.p[3] + d.off1, (int *)r.p[4] + blockIdx.x);
+    if ((int)blockIdx.x >= r.ia[PC_REC_I_ND]) return;
+    const ClusDesc d = ((const ClusDesc *)r.p[PC_REC_DESC])[blockIdx.x];
+    nn_cluster_body((const int *)r.p[PC_REC_KNN] + d.off2, d.n, (int *)r.p[PC_REC_LAB] + d.off1, (int *)r.p[PC_REC_OUT] + blockIdx.x);
 }
 
 // One level of NN_clustering's recursion for many parts at once (Engine::refine_partitions): part b = m points of a cluster, given by
@@ -456,23 +456,23 @@ __global__ __launch_bounds__(1024) void k_nn_cluster_sub(const SubDesc *desc, co
     const SubDesc d = desc[blockIdx.x];
     nn_cluster_body(knn + d.koff, d.m, labels + d.ioff, out + blockIdx.x);
 }
-// ... for several runs in step (PcManyRec::p: 0 descriptors, 1 similarity blocks, 2 pool, 3 neighbour lists, 4 labels, 5 verdicts; ia[1] parts)
+// ... for several runs in step (PcManyRec::p under PC_REC_G_DESC .. PC_REC_G_OUT; ia[PC_REC_I_NB] parts)
 __global__ __launch_bounds__(256) void k_knn_sort_sub_many(const PcManyRec *__restrict__ R)
 {
     const PcManyView r = pc_many_view(R, blockIdx.z);
-    if ((int)blockIdx.y >= r.ia[1]) return;
-    const SubDesc d = ((const SubDesc *)r.p[0])[blockIdx.y];
+    if ((int)blockIdx.y >= r.ia[PC_REC_I_NB]) return;
+    const SubDesc d = ((const SubDesc *)r.p[PC_REC_G_DESC])[blockIdx.y];
     if ((int)blockIdx.x >= d.m) return;
     int npow2 = 2;
     while (npow2 < d.m) npow2 <<= 1;
-    knn_sort_body((const double *)r.p[1] + d.off2, d.n, (const int *)r.p[2] + d.ioff, d.m, npow2, (int *)r.p[3] + d.koff);
+    knn_sort_body((const double *)r.p[PC_REC_G_SM] + d.off2, d.n, (const int *)r.p[PC_REC_G_POOL] + d.ioff, d.m, npow2, (int *)r.p[PC_REC_G_KNN] + d.koff);
 }
 __global__ __launch_bounds__(1024) void k_nn_cluster_sub_many(const PcManyRec *__restrict__ R)
 {
     const PcManyView r = pc_many_view(R, blockIdx.y);
-    if ((int)blockIdx.x >= r.ia[1]) return;
-    const SubDesc d = ((const SubDesc *)r.p[0])[blockIdx.x];
-    nn_cluster_body((const int *)r.p[3] + d.koff, d.m, (int *)r.p[4] + d.ioff, (int *)r.p[5] + blockIdx.x);
+    if ((int)blockIdx.x >= r.ia[PC_REC_I_NB]) return;
+    const SubDesc d = ((const SubDesc *)r.p[PC_REC_G_DESC])[blockIdx.x];
+    nn_cluster_body((const int *)r.p[PC_REC_G_KNN] + d.koff, d.m, (int *)r.p[PC_REC_G_LAB] + d.ioff, (int *)r.p[PC_REC_G_OUT] + blockIdx.x);
 }
 
 extern "C" {

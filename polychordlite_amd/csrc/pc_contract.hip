@@ -242,12 +242,12 @@ __device__ __forceinline__ void nn_lists_body(const PcState &S, int nleft, int t
     }
 }
 __global__ __launch_bounds__(256) void k_nn_lists(PcState S, int nleft, int tile_pts) { nn_lists_body(S, nleft, tile_pts); }
-// several runs in step (blockIdx.y = run): each run its own number of chains left in the nursery (PcManyRec::ia[1])
+// several runs in step (blockIdx.y = run): each run its own number of chains left in the nursery (PcManyRec::ia[PC_REC_I_NLEFT])
 __global__ __launch_bounds__(256) void k_nn_lists_many(const PcManyRec *__restrict__ R, int tile_pts)
 {
     const PcManyView r = pc_many_view(R, blockIdx.y);
-    if ((int)blockIdx.x >= r.ia[1]) return;
-    nn_lists_body(r.S, r.ia[1], tile_pts);
+    if ((int)blockIdx.x >= r.ia[PC_REC_I_NLEFT]) return;
+    nn_lists_body(r.S, r.ia[PC_REC_I_NLEFT], tile_pts);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -283,7 +283,7 @@ __device__ __forceinline__ void nn_gather_body(const PcState &S, int nleft, int 
     if (d == 0) S.nn_code[pos] = code;
 }
 __global__ __launch_bounds__(256) void k_nn_gather(PcState S, int nleft, int use_rank) { nn_gather_body(S, nleft, use_rank); }
-__global__ __launch_bounds__(256) void k_nn_gather_many(const PcManyRec *__restrict__ R, int use_rank) { const PcManyView r = pc_many_view(R, blockIdx.y); nn_gather_body(r.S, r.ia[1], use_rank); }
+__global__ __launch_bounds__(256) void k_nn_gather_many(const PcManyRec *__restrict__ R, int use_rank) { const PcManyView r = pc_many_view(R, blockIdx.y); nn_gather_body(r.S, r.ia[PC_REC_I_NLEFT], use_rank); }
 
 #define NND_SC 16                                   /* at most this many scanners per pair of babies */
 // Round 4: most of the candidates cannot die before the chain is looked at.  The deaths of a nursery take the snapshot's points in
@@ -487,8 +487,8 @@ template <int D> __global__ __launch_bounds__(256) void k_nn_lists_d(PcState S, 
 template <int D> __global__ __launch_bounds__(256) void k_nn_lists_d_many(const PcManyRec *__restrict__ R, int tile_pts, int use_rank)
 {
     const PcManyView r = pc_many_view(R, blockIdx.y);
-    if ((int)blockIdx.x >= r.ia[1]) return;
-    nn_lists_d_body<D>(r.S, r.ia[1], tile_pts, use_rank);
+    if ((int)blockIdx.x >= r.ia[PC_REC_I_NLEFT]) return;
+    nn_lists_d_body<D>(r.S, r.ia[PC_REC_I_NLEFT], tile_pts, use_rank);
 }
 static size_t nn_lists_d_lds(const PcState *S, int &tile)
 {
@@ -1342,7 +1342,7 @@ __device__ __forceinline__ void apply_dead_ph_body(const PcState &S, unsigned ba
     }
 }
 __global__ __launch_bounds__(64 * PC_APPLY_WAVES) void k_apply_dead_ph(PcState S, unsigned batch) { apply_dead_ph_body(S, batch); }
-__global__ __launch_bounds__(64 * PC_APPLY_WAVES) void k_apply_dead_ph_many(const PcManyRec *__restrict__ R) { apply_dead_ph_body(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[0]); }
+__global__ __launch_bounds__(64 * PC_APPLY_WAVES) void k_apply_dead_ph_many(const PcManyRec *__restrict__ R) { apply_dead_ph_body(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[PC_REC_I_BATCH]); }
 
 // pool mode: both of the above in ONE launch (a kernel boundary on the main stream costs 6 us, 79 times per run at the metric
 // configuration).  No row is copied to become a phantom, so a chain's workgroup only writes the side arrays of its region and,
@@ -1406,7 +1406,7 @@ __device__ __forceinline__ void apply_pool_body(const PcState &S, unsigned batch
     if (lane == 0) { S.slot_src[slot] = -1; S.slot_dead[slot] = -1; if (src >= 0) S.live_entry[slot] = S.plan[src].contour; }
 }
 __global__ __launch_bounds__(256) void k_apply_pool(PcState S, unsigned batch, int nchains) { apply_pool_body(S, batch, nchains); }
-__global__ __launch_bounds__(256) void k_apply_pool_many(const PcManyRec *R, int nchains) { apply_pool_body(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[0], nchains); }
+__global__ __launch_bounds__(256) void k_apply_pool_many(const PcManyRec *R, int nchains) { apply_pool_body(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[PC_REC_I_BATCH], nchains); }
 
 
 // new live rows: every slot now owned by a chain's last baby
@@ -1490,7 +1490,7 @@ __device__ __forceinline__ void clean_flag_body(const PcState &S, int nph, unsig
     if (threadIdx.x == 0) blk_count[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
 }
 __global__ __launch_bounds__(256) void k_clean_flag(PcState S, int nph, unsigned char *keep, int *blk_count) { clean_flag_body(S, nph, keep, blk_count); }
-__global__ __launch_bounds__(256) void k_clean_flag_many(const PcManyRec *R) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x >= r.ia[2]) return; clean_flag_body(r.S, r.ia[1], (unsigned char *)r.p[0], (int *)r.p[1]); }
+__global__ __launch_bounds__(256) void k_clean_flag_many(const PcManyRec *R) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x >= r.ia[PC_REC_I_BLOCKS]) return; clean_flag_body(r.S, r.ia[PC_REC_I_ROWS], (unsigned char *)r.p[PC_REC_KEEP], (int *)r.p[PC_REC_BLK]); }
 
 
 __device__ __forceinline__ void scan_blocks_body(int *blk_count, int nblk, int *total, int *total2)
@@ -1518,7 +1518,7 @@ __device__ __forceinline__ void scan_blocks_body(int *blk_count, int nblk, int *
     if (threadIdx.x == 0) { *total = carry; if (total2) *total2 = carry; }   // total2: the control block's phantom count
 }
 __global__ __launch_bounds__(256) void k_scan_blocks(int *blk_count, int nblk, int *total, int *total2) { scan_blocks_body(blk_count, nblk, total, total2); }
-__global__ __launch_bounds__(256) void k_scan_blocks_many(const PcManyRec *R) { const PcManyView r = pc_many_view(R, blockIdx.y); scan_blocks_body((int *)r.p[1], r.ia[2], (int *)r.p[2], &r.S.ctl->nphantom); }
+__global__ __launch_bounds__(256) void k_scan_blocks_many(const PcManyRec *R) { const PcManyView r = pc_many_view(R, blockIdx.y); scan_blocks_body((int *)r.p[PC_REC_BLK], r.ia[PC_REC_I_BLOCKS], (int *)r.p[PC_REC_TOTAL], &r.S.ctl->nphantom); }
 
 
 __device__ __forceinline__ void clean_scatter_body(const PcState &S, int nph, const unsigned char *keep, const int *blk_off,
@@ -1546,8 +1546,8 @@ __global__ __launch_bounds__(256) void k_clean_scatter(PcState S, int nph, const
 __global__ __launch_bounds__(256) void k_clean_scatter_many(const PcManyRec *R)
 {
     const PcManyView r = pc_many_view(R, blockIdx.y);
-    if ((int)blockIdx.x >= r.ia[2]) return;
-    clean_scatter_body(r.S, r.ia[1], (const unsigned char *)r.p[0], (const int *)r.p[1], (double *)r.p[3], (double *)r.p[4], (unsigned *)r.p[5], (unsigned long long *)r.p[6], nullptr);
+    if ((int)blockIdx.x >= r.ia[PC_REC_I_BLOCKS]) return;
+    clean_scatter_body(r.S, r.ia[PC_REC_I_ROWS], (const unsigned char *)r.p[PC_REC_KEEP], (const int *)r.p[PC_REC_BLK], (double *)r.p[PC_REC_PH2], (double *)r.p[PC_REC_PHL2], (unsigned *)r.p[PC_REC_PHC2], (unsigned long long *)r.p[PC_REC_PHU2], nullptr);
 }
 
 
@@ -2109,11 +2109,11 @@ extern "C" int pc_launch_apply_many(const PcState *S, const PcManyRec *dR, int R
         return 0;
     }
     static const int wpg = std::getenv("PC_APPLY_WAVES") ? std::max(1, std::min(4, std::atoi(std::getenv("PC_APPLY_WAVES")))) : 4;
-    hipLaunchKernelGGL(k_apply_pool_many, dim3((nchains + S->Ncap + wpg - 1) / wpg, R), dim3(64 * wpg), 0, st, dR, nchains);      // (the nursery's number: each run's own, PcManyRec::ia[0])
+    hipLaunchKernelGGL(k_apply_pool_many, dim3((nchains + S->Ncap + wpg - 1) / wpg, R), dim3(64 * wpg), 0, st, dR, nchains);      // (the nursery's number: each run's own, PcManyRec::ia[PC_REC_I_BATCH])
     return 0;
 }
 
-// the phantom clean for R runs at once (pool compaction of runs in step): every run its own row count (PcManyRec::ia[1], blocks ia[2])
+// the phantom clean for R runs at once (pool compaction of runs in step): every run its own row count (PcManyRec::ia[PC_REC_I_ROWS], blocks PC_REC_I_BLOCKS)
 extern "C" int pc_launch_clean_many(const PcManyRec *dR, int R, int nblk_max, hipStream_t st)
 {
     if (nblk_max < 1) return 1;

@@ -490,191 +490,13 @@ struct Fiber {
     void yield() { swapcontext(&ctx, &ret); }
 };
 
-enum { CK_COMPACT = 0, CK_RESET, CK_CLUS1, CK_CLUSG, CK_BASES, CK_NHATS_G, CK_SLICE, CK_SLICE_G, CK_BASES_NEXT, CK_SORT, CK_NN, CK_CONSUME, CK_CONSUME_CL, CK_APPLY, CK_UPDATE, CK_COV, CK_FINAL, CK_N };      // (in the order they are launched)
-// (_G: any device likelihood, the wavefront-per-chain kernels of a run on its own with the run in the grid; NN / CONSUME_CL: runs with several clusters)
-struct Cohort {
-    hipStream_t st = nullptr;
-    hipStream_t st2 = nullptr;          // the bases of the NEXT nursery, next to this one's sampling and contraction
-    hipEvent_t ev_up = nullptr, ev_next = nullptr; bool next_pending = false;
-    // bases drawn TWO nurseries ahead: a sampling launch waits for the launch that drew ITS bases (numbered), not for the second stream's
-    // latest -- with one event for the latest, sixteen runs' k_slice_t waited 140 us per round without an update for the 250 us of
-    // deviates + bases launched a round before
-    hipEvent_t ev_seq[4] = {nullptr, nullptr, nullptr, nullptr}; unsigned long long seq_launched = 0, seq_waited = 0; bool seq_open = false;
-    int seq_for_next() const { return (int)(seq_launched + 1); }      // (the number the bases written down now will be launched under)
-    struct Rec { int kind; PcState S; void *p[10]; long long a[4]; int ia[6]; };      // a: what the runs of one launch must share; ia: each run's own (PcManyRec::ia)
-    std::vector<Rec> pend;
-    static constexpr int RING = 4;
-    PcManyRec *h_stage[RING] = {}, *d_recs[RING] = {};
-    // a slot's records are read by the kernels launched from it: its events are recorded behind the LAST of them, on both streams
-    hipEvent_t ev[RING] = {}, ev2[RING] = {}; bool ev_used[RING] = {}, ev2_used[RING] = {};
-    size_t cap = 0; int ring = 0;
-    void slot_wait(int k)
-    {
-        if (ev_used[k]) { HIPCHK(hipEventSynchronize(ev[k])); ev_used[k] = false; }
-        if (ev2_used[k]) { HIPCHK(hipEventSynchronize(ev2[k])); ev2_used[k] = false; }
-    }
-    // the bases of this nursery were drawn on the second stream: whatever reads them on the main stream comes behind them
-    void wait_next() { if (next_pending) { HIPCHK(hipStreamWaitEvent(st, ev_next, 0)); next_pending = false; } }
-    long n_fused = 0, n_single = 0;
-    // the runs' copies to the host (dead rows, results) share two streams of the cohort, on hardware queues other than the two its
-    // kernels use: a copy stream per run came from the pool, on whatever queue -- and where copies are shader blits (the HIP runtime
-    // PyTorch ships: 48 us each) a round's kernels queued behind them
-    hipStream_t stc[2] = {nullptr, nullptr}; int n_stc = 0;
-    // copies to the host that belong behind what has been written down: made at the end of flush(), in the order they were asked for
-    std::vector<std::function<void()>> post;
-    // ... and copies to the device that what is written down reads: made at the start of flush()
-    std::vector<std::function<void()>> pre;
-    void rec(int kind, const PcState &S, std::initializer_list<void *> p, std::initializer_list<long long> a, std::initializer_list<int> ia)
-    {
-        pend.emplace_back();
-        Rec &r = pend.back();
-        r.kind = kind; r.S = S;
-        int i = 0; for (void *x : p) r.p[i++] = x; for (; i < 10; ++i) r.p[i] = nullptr;
-        i = 0; for (long long x : a) r.a[i++] = x; for (; i < 4; ++i) r.a[i] = 0;
-        i = 0; for (int x : ia) r.ia[i++] = x; for (; i < 6; ++i) r.ia[i] = 0;
-    }
-    static void single(const Rec &r, hipStream_t st)
-    {
-        switch (r.kind) {
-        case CK_COMPACT: pc_launch_clean(&r.S, r.ia[1], (unsigned char *)r.p[0], (int *)r.p[1], (int *)r.p[2], (double *)r.p[3], (double *)r.p[4], (unsigned *)r.p[5], (unsigned long long *)r.p[6], nullptr, st); break;
-        case CK_BASES: case CK_BASES_NEXT: (void)pc_launch_nhats_part(&r.S, (unsigned)r.ia[0], (int)r.a[0], 1, st, 1); break;
-        case CK_SLICE: (void)pc_launch_slice_t(&r.S, (unsigned)r.ia[0], (int)r.a[0], st); break;
-        case CK_NHATS_G: (void)pc_launch_nhats(&r.S, (unsigned)r.ia[0], (int)r.a[0], st); break;
-        case CK_SLICE_G: if (r.a[1]) (void)pc_launch_slice_fused(&r.S, (unsigned)r.ia[0], (int)r.a[0], st); else (void)pc_launch_slice(&r.S, (unsigned)r.ia[0], (int)r.a[0], st); break;
-        case CK_NN: pc_launch_nn_lists(&r.S, r.ia[1], 1, st); break;      // (the run's CK_SORT of this round has been launched: kinds go in order)
-        case CK_RESET: pc_launch_reset_thresholds(&r.S, st); break;
-        case CK_CLUSG: (void)pc_launch_knn_cluster_sub((const int *)r.p[0], r.ia[1], r.ia[2], (const double *)r.p[1], (const int *)r.p[2], (int *)r.p[3], (int *)r.p[4], (int *)r.p[5], st); break;
-        case CK_CLUS1: (void)pc_launch_knn_cluster_batch_dev(&r.S, (const int *)r.p[0], r.ia[1], r.ia[2], (double *)r.p[1], (int *)r.p[2], (int *)r.p[3], (int *)r.p[4], (const int *)r.p[5], r.ia[3], st); break;
-        case CK_CONSUME_CL: (void)pc_launch_consume_cl(&r.S, r.a[0] ? 65 : 2, st); break;
-        case CK_SORT: (void)pc_launch_sort_live(&r.S, st); break;
-        case CK_CONSUME: (void)pc_launch_consume_par(&r.S, st); break;
-        case CK_FINAL: (void)pc_launch_final_par(&r.S, st); break;
-        case CK_APPLY: pc_launch_apply(&r.S, (unsigned)r.ia[0], (int)r.a[0], st); break;
-        case CK_UPDATE: pc_launch_update_fused(&r.S, r.ia[1], (unsigned char *)r.p[0], (int *)r.p[1], (int *)r.p[2], (double *)r.p[3], (double *)r.p[4],
-                                               (unsigned *)r.p[5], (unsigned long long *)r.p[6], (double *)r.p[7], (double *)r.p[8], (int)r.a[1], st); break;
-        }
-    }
-    // ... the copies among them as (destination, source, bytes): one kernel for all of them (k_copy_batch), not a hipMemcpyAsync each
-    std::vector<std::array<uintptr_t, 3>> post_copies, pre_copies;
-    void run_post()
-    {
-        if (!post_copies.empty()) { std::vector<std::array<uintptr_t, 3>> c; c.swap(post_copies); pc_copy_many(c, st); }
-        if (post.empty()) return;
-        std::vector<std::function<void()>> p; p.swap(post); for (auto &f : p) f();
-    }
-    void run_pre()
-    {
-        if (!pre_copies.empty()) { std::vector<std::array<uintptr_t, 3>> c; c.swap(pre_copies); pc_copy_many(c, st); }
-        if (pre.empty()) return;
-        std::vector<std::function<void()>> p; p.swap(pre); for (auto &f : p) f();
-    }
-    void flush()
-    {
-        run_pre();
-        if (pend.empty()) { run_post(); return; }
-        const size_t n = pend.size();
-        if (n > cap) {
-            for (int k = 0; k < RING; ++k) {
-                slot_wait(k);      // (kernels of earlier flushes may still be reading the old records, on either stream)
-                // (from the block caches and the event pool: asking the driver -- and giving back to it at the end -- was 2 ms per call)
-                if (h_stage[k]) hfree(h_stage[k]);
-                if (d_recs[k]) dfree(d_recs[k]);
-                h_stage[k] = halloc<PcManyRec>(2 * n);
-                d_recs[k] = dalloc<PcManyRec>(2 * n);
-                if (!ev[k]) ev[k] = hpool().get_sync_event();
-                if (!ev2[k] && st2) ev2[k] = hpool().get_sync_event();
-            }
-            cap = 2 * n;
-        }
-        const int slot = ring++ % RING;
-        slot_wait(slot);
-        PcManyRec *hs = h_stage[slot], *dr = d_recs[slot];
-        // records in launch order: by kind, and inside a kind by the arguments all runs of a launch must share
-        std::vector<const Rec *> ord; ord.reserve(n);
-        for (const Rec &r : pend) ord.push_back(&r);
-        auto shape_less = [](const Rec *x, const Rec *y) {
-            if (x->kind != y->kind) return x->kind < y->kind;
-            const int c = std::memcmp(x->a, y->a, sizeof(x->a));
-            if (c != 0) return c < 0;
-            if (x->S.Ncap != y->S.Ncap) return x->S.Ncap < y->S.Ncap;
-            if (x->S.B != y->S.B) return x->S.B < y->S.B;
-            if (x->S.pool != y->S.pool) return x->S.pool < y->S.pool;
-            return (x->S.prior.lo == nullptr) < (y->S.prior.lo == nullptr);
-        };
-        std::stable_sort(ord.begin(), ord.end(), shape_less);
-        for (size_t i = 0; i < n; ++i) { hs[i].S = ord[i]->S; std::memcpy(hs[i].p, ord[i]->p, sizeof(ord[i]->p)); std::memcpy(hs[i].ia, ord[i]->ia, sizeof(ord[i]->ia)); }
-        HIPCHK(hipMemcpyAsync(dr, hs, sizeof(PcManyRec) * n, hipMemcpyHostToDevice, st));
-        bool up_marked = false, used_st2 = false;
-        for (size_t i = 0; i < n;) {
-            size_t j = i + 1;
-            while (j < n && !shape_less(ord[i], ord[j]) && !shape_less(ord[j], ord[i])) ++j;
-            const Rec &f = *ord[i];
-            const PcManyRec *d = dr + i;
-            const int cnt = (int)(j - i), k = f.kind;
-            hipStream_t q = st;
-            if (k == CK_BASES_NEXT && st2) {         // on the second stream, behind the upload of the records
-                if (!up_marked) { HIPCHK(hipEventRecord(ev_up, st)); up_marked = true; }
-                HIPCHK(hipStreamWaitEvent(st2, ev_up, 0));
-                q = st2; used_st2 = true;
-            }
-            if (k == CK_SLICE || k == CK_SLICE_G) {             // (its bases were drawn over there)
-                int need = 0; bool numbered = st2 != nullptr;
-                for (size_t x = i; x < j; ++x) { numbered = numbered && ord[x]->ia[3] > 0; need = std::max(need, ord[x]->ia[3]); }
-                if (numbered && (unsigned long long)need <= seq_launched) {
-                    if ((unsigned long long)need > seq_waited) { HIPCHK(hipStreamWaitEvent(st, ev_seq[need & 3], 0)); seq_waited = (unsigned long long)need; }
-                } else wait_next();
-            }
-            int rc = 1;
-            switch (k) {
-            case CK_COMPACT: { int nbm = 0; for (size_t x = i; x < j; ++x) nbm = std::max(nbm, ord[x]->ia[2]); rc = pc_launch_clean_many(d, cnt, nbm, q); } break;
-            case CK_BASES: case CK_BASES_NEXT: rc = pc_launch_bases_t_many(&f.S, d, cnt, 0u, (int)f.a[0], q); break;
-            case CK_SLICE: rc = pc_launch_slice_t_many(&f.S, d, cnt, 0u, (int)f.a[0], q); break;
-            case CK_NHATS_G: rc = pc_launch_nhats_many(&f.S, d, cnt, (int)f.a[0], q); break;
-            case CK_SLICE_G: rc = pc_launch_slice_many(&f.S, d, cnt, (int)f.a[0], (int)f.a[1], q); break;
-            case CK_NN: { int nl = 0; for (size_t x = i; x < j; ++x) nl = std::max(nl, ord[x]->ia[1]); rc = pc_launch_nn_lists_many(&f.S, d, cnt, nl, 1, q); } break;
-            case CK_CONSUME_CL: rc = pc_launch_consume_cl_many(&f.S, d, cnt, (int)f.a[0], q); break;
-            case CK_RESET: rc = pc_launch_reset_thresholds_many(&f.S, d, cnt, q); break;
-            case CK_CLUSG: { int nbm = 0, nmx = 0; for (size_t x = i; x < j; ++x) { nbm = std::max(nbm, ord[x]->ia[1]); nmx = std::max(nmx, ord[x]->ia[2]); } rc = pc_launch_knn_cluster_sub_many(d, cnt, nbm, nmx, q); } break;
-            case CK_CLUS1: { int ndm = 0, nmx = 0, sub = 0; for (size_t x = i; x < j; ++x) { ndm = std::max(ndm, ord[x]->ia[1]); nmx = std::max(nmx, ord[x]->ia[2]); sub |= ord[x]->ia[3] > 0; } rc = pc_launch_knn_cluster_batch_many(&f.S, d, cnt, ndm, nmx, sub, q); } break;
-            case CK_SORT: rc = pc_launch_sort_live_many(&f.S, d, cnt, q); break;
-            case CK_CONSUME: rc = pc_launch_consume_par_many(&f.S, d, cnt, q); break;
-            case CK_FINAL: rc = pc_launch_final_par_many(d, cnt, q); break;
-            case CK_APPLY: rc = pc_launch_apply_many(&f.S, d, cnt, 0u, (int)f.a[0], q); break;
-            case CK_UPDATE: { int nbm = 0; for (size_t x = i; x < j; ++x) nbm = std::max(nbm, ord[x]->ia[2]); rc = pc_launch_update_fused_many(&f.S, d, cnt, nbm, (int)f.a[0], (int)f.a[1], q); } break;
-            }
-            if (rc == 0) n_fused += cnt;
-            else for (size_t x = i; x < j; ++x) { single(*ord[x], q); n_single++; }
-            if (k == CK_BASES_NEXT && st2) {
-                HIPCHK(hipEventRecord(ev_next, st2)); next_pending = true;
-                if (!seq_open) { seq_launched++; seq_open = true; }
-                if (!ev_seq[seq_launched & 3]) ev_seq[seq_launched & 3] = hpool().get_sync_event();
-                HIPCHK(hipEventRecord(ev_seq[seq_launched & 3], st2));
-            }
-            i = j;
-        }
-        HIPCHK(hipEventRecord(ev[slot], st)); ev_used[slot] = true;
-        if (used_st2 && ev2[slot]) { HIPCHK(hipEventRecord(ev2[slot], st2)); ev2_used[slot] = true; }
-        pend.clear();
-        seq_open = false;
-        run_post();
-    }
-    void destroy()
-    {
-        for (int k = 0; k < 4; ++k) if (ev_seq[k]) { hpool().put_sync_event(ev_seq[k]); ev_seq[k] = nullptr; }
-        for (int k = 0; k < RING; ++k) {
-            if (ev_used[k]) (void)hipEventSynchronize(ev[k]);
-            if (ev2_used[k]) (void)hipEventSynchronize(ev2[k]);
-            if (ev[k]) hpool().put_sync_event(ev[k]);
-            if (ev2[k]) hpool().put_sync_event(ev2[k]);
-            ev2[k] = nullptr; ev2_used[k] = false;
-            if (h_stage[k]) hfree(h_stage[k]);
-            if (d_recs[k]) dfree(d_recs[k]);
-            ev[k] = nullptr; h_stage[k] = nullptr; d_recs[k] = nullptr; ev_used[k] = false;
-        }
-        cap = 0;
-    }
-};
+#include "pc_cohort.h"      // Cohort: the launches of the runs in step, written down and made once for all of them (the table of stages)
 
+// adds its lifetime to one of the counters below
+struct DbgSpan {
+    std::atomic<long long> &ns; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    ~DbgSpan() { ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
+};
 static std::atomic<long long> g_dbg_compact_ns{0}, g_dbg_nursery_ns{0}, g_dbg_capacity_ns{0}, g_dbg_endb_ns{0}, g_dbg_destroy_ns{0}, g_dbg_evwait_ns{0}, g_dbg_d1{0}, g_dbg_d2{0};      // (PC_DEBUG=5: where round_enqueue's time goes)
 struct Engine {
     Cohort *co = nullptr;               // not null: this run goes in step with others of its device, on their common stream
@@ -1033,6 +855,12 @@ struct Engine {
     }
     // something launched here and now, behind whatever the runs in step have written down so far
     void direct_op() { if (co) co->flush(); }
+    // a stage of the round: in step with other runs written down (0), alone launched now by the stage's one-run launch (its return code)
+    int stage(const Cohort::Rec &r)
+    {
+        if (co) { co->rec(r); return 0; }
+        return Cohort::stage(r.kind).one(r, st);
+    }
     // device -> host, through a pinned block, in stream order behind everything asked for so far; the values are there after fetch_wait()
     struct Fetch { void *h; void *dst; size_t bytes; };
     std::vector<Fetch> fetching;
@@ -1197,7 +1025,7 @@ struct Engine {
     // the phantom array is full: the phantoms that are still wanted move to the front of the alternate buffers.  In step with other
     // runs the clean is launched for all of them at once and waited for once (compact_wanted / compact_record / compact_finish)
     bool compact_wanted() const { return S.pool && h_ctl->status == PC_ST_RUNNING && h_ctl->i_nursery == 0 && pool_cursor + (long long)B * S.nr > S.Pcap; }
-    void compact_record() { co->rec(CK_COMPACT, S, {keep, blk, d_total, ph2, phL2, phC2, phU2}, {}, {0, (int)pool_cursor, ((int)pool_cursor + 255) / 256}); }
+    void compact_record() { co->rec(rec_compact(S, keep, blk, d_total, ph2, phL2, phC2, phU2, (int)pool_cursor)); }
     void compact_finish(int total)
     {
         std::swap(S.phantom, ph2); std::swap(S.ph_logL, phL2); std::swap(S.ph_cuid, phC2); std::swap(S.ph_uid, phU2);
@@ -1207,8 +1035,7 @@ struct Engine {
     }
     void pool_compact()
     {
-        const auto dbg_t0 = std::chrono::steady_clock::now();
-        struct DbgT { std::chrono::steady_clock::time_point t0; ~DbgT() { g_dbg_compact_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); } } dbg_t{dbg_t0};
+        DbgSpan dbg_t{g_dbg_compact_ns};
         if (co) co->flush();
         hipEvent_t e0 = kt.begin(KT_CLEAN);
         pc_launch_clean(&S, (int)pool_cursor, keep, blk, d_total, ph2, phL2, phC2, phU2, nullptr, st);
@@ -1442,8 +1269,7 @@ struct Engine {
             }
             path[PCHIP_PATH_UPDATE_FUSED]++;
             hipEvent_t e0 = kt.begin(KT_CLEAN);
-            if (co) co->rec(CK_UPDATE, S, {keep, blk, d_total, ph2, phL2, phC2, phU2, upd_part, upd_shift}, {(long long)pc_update_fused_grid(&S, nph, deferred ? 1 : 0), deferred ? 1LL : 0LL}, {0, nph, (nph + 255) / 256});
-            else pc_launch_update_fused(&S, nph, keep, blk, d_total, ph2, phL2, phC2, phU2, upd_part, upd_shift, deferred ? 1 : 0, st);
+            (void)stage(rec_update(S, keep, blk, d_total, ph2, phL2, phC2, phU2, upd_part, upd_shift, co ? pc_update_fused_grid(&S, nph, deferred ? 1 : 0) : 0, deferred, nph));
             kt.end(KT_CLEAN, e0);
             if (cfg.resume_write || dumper || on_update || seq_post) {
                 // (in step with other runs the update was only written down: the copy of its count comes behind its launch)
@@ -1462,8 +1288,9 @@ struct Engine {
         path[PCHIP_PATH_UPDATE_STEPS]++;
         hipEvent_t e0 = kt.begin(KT_CLEAN);
         // (in step with other runs: the clean of all runs that update in this round is one launch, like the pool compaction)
-        if (co && nph > 0) co->rec(CK_COMPACT, S, {keep, blk, d_total, ph2, phL2, phC2, phU2}, {}, {0, nph, (nph + 255) / 256});
-        else { direct_op(); pc_launch_clean(&S, nph, keep, blk, d_total, ph2, phL2, phC2, phU2, nullptr, st); }
+        // (... of no rows: nothing to write down, launched now behind what has been)
+        if (co && nph <= 0) { direct_op(); pc_launch_clean(&S, nph, keep, blk, d_total, ph2, phL2, phC2, phU2, nullptr, st); }
+        else (void)stage(rec_compact(S, keep, blk, d_total, ph2, phL2, phC2, phU2, nph));
         kt.end(KT_CLEAN, e0);
         if (cfg.boost_posterior != 0.0 && (cfg.posteriors || cfg.equals)) collect_phantom_posteriors(nph);
         if (hook_late) call_dumper();
@@ -1479,7 +1306,7 @@ struct Engine {
             if (ctl_late) fetch_raw(&ctl_in, S.ctl, sizeof(PcCtl));
         } else nph_stale = true;
         std::swap(S.phantom, ph2); std::swap(S.ph_logL, phL2); std::swap(S.ph_cuid, phC2); std::swap(S.ph_uid, phU2);
-        if (co) co->rec(CK_RESET, S, {}, {}, {}); else pc_launch_reset_thresholds(&S, st);
+        (void)stage(rec_reset(S));
         if (need_count) {
             fetch_wait();
             if (ctl_late) { const int st_keep = h_ctl->status; *h_ctl = ctl_in; h_ctl->status = st_keep; nph_stale = false; }
@@ -1720,7 +1547,8 @@ struct Engine {
             }
             send_pre(c_gdesc, gdesc.data(), sizeof(int) * gdesc.size());
             send_pre(c_gpool, pool.data(), sizeof(int) * pool.size());
-            if (co) co->rec(CK_CLUSG, S, {c_gdesc, c_Sm, c_gpool, c_knn, c_glab, c_gout}, {}, {0, nb, mmax});
+            // (not stage(): a run on its own fails where the launcher declines; in step the row's one-run launch is taken instead)
+            if (co) co->rec(rec_clusg(S, c_gdesc, c_Sm, c_gpool, c_knn, c_glab, c_gout, nb, mmax));
             else if (pc_launch_knn_cluster_sub(c_gdesc, nb, mmax, c_Sm, c_gpool, c_knn, c_glab, c_gout, st)) engine_fail(PC_RC_LDS, "cluster of %d points too large for the LDS kNN sort", mmax);
             std::vector<int> labs, nums;
             fetch(labs, (const int *)c_glab, pool.size()); fetch(nums, (const int *)c_gout, (size_t)nb);
@@ -1768,7 +1596,8 @@ struct Engine {
                 int nmax1 = 0;
                 for (int k = 0; k < nd; ++k) nmax1 = std::max(nmax1, desc[4 * k + 1]);
                 // (in step with other runs: the first pass of all runs that update in this round in three launches)
-                if (co) co->rec(CK_CLUS1, S, {c_desc, c_Sm, c_knn, c_lab, c_bout, (void *)dims}, {}, {0, nd, nmax1, nd_sub});
+                // (not stage(): a run on its own launches from the host's copy of the descriptors, pc_launch_knn_cluster_batch)
+                if (co) co->rec(rec_clus1(S, c_desc, c_Sm, c_knn, c_lab, c_bout, dims, nd, nmax1, nd_sub));
                 else if (pc_launch_knn_cluster_batch(&S, desc.data(), c_desc, nd, c_Sm, c_knn, c_lab, c_bout, dims, nd_sub, st)) engine_fail(PC_RC_LDS, "a cluster too large for the LDS kNN sort");
                 std::vector<int> out, lab0;
                 fetch(out, (const int *)c_bout, (size_t)nd);
@@ -2338,14 +2167,16 @@ struct Engine {
                 if (rs.valid && rs.batch == batch && rs.B == B) { if (!rs.waited) HIPCHK(hipStreamWaitEvent(st, rs.ready, 0)); bases_seq = rs.co_seq; }      // (in step with other runs: the wait for the launch that drew them, Cohort::flush)
                 else {
                     if (rs.valid) HIPCHK(hipStreamWaitEvent(st, rs.ready, 0));       // (a stale job may still be writing there)
-                    if (co && pc_bases_t_ok(&S)) co->rec(CK_BASES, S, {}, {(long long)B}, {(int)batch});
+                    // (not stage(): a run on its own passes its packed flag from `multi` and settings.ablate bit 7, the row's one-run launch 1)
+                    if (co && pc_bases_t_ok(&S)) co->rec(rec_bases(S, batch, B));
                     else (void)pc_launch_nhats_part(&S, batch, B, 1, st, (multi || (cfg.ablate & 128)) ? 1 : 0);
                 }
                 rs.valid = false;
                 fused_slice = !callback_mode && pc_slice_fusable(&S) != 0;       // seeds + whitening inside k_slice
                 if (!fused_slice) { if (co) { co->flush(); co->wait_next(); } (void)pc_launch_nhats_part(&S, batch, B, 2, st, 0); }
             }
-            else if (co && !callback_mode && cohort_general_ok() && S.D >= 25 && S.D <= 64) co->rec(CK_NHATS_G, S, {}, {(long long)B}, {(int)batch});
+            // (not stage(): CK_NHATS_G exists in step only, a run on its own reports a failing launch)
+            else if (co && !callback_mode && cohort_general_ok() && S.D >= 25 && S.D <= 64) co->rec(rec_nhats_g(S, batch, B));
             else if ((co ? (co->flush(), 0) : 0) || pc_launch_nhats(&S, batch, B, st)) { std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false; }
             kt.end(KT_NHATS, e0);
             hipEvent_t e1 = kt.begin(KT_SLICE);
@@ -2354,7 +2185,7 @@ struct Engine {
             // numbers from 1/60 of the wavefronts
             else if (fused_slice && (multi || (cfg.ablate & 64)) && pc_slice_t_ok(&S, h_ctl->ncluster)) {
                 path[PCHIP_PATH_SLICE_LANE]++;
-                if (co) co->rec(CK_SLICE, S, {}, {(long long)B}, {(int)batch, 0, 0, bases_seq}); else (void)pc_launch_slice_t(&S, batch, B, st);
+                (void)stage(rec_slice(S, batch, B, bases_seq));
                 // in step with other runs: the bases of the next nursery on the runs' second stream, next to this round's kernels
                 if (co && co->st2 && splittable && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
             }
@@ -2362,7 +2193,8 @@ struct Engine {
                 // in step with other runs, any device likelihood / several clusters: the one-run kernel with the run in the grid
                 path[PCHIP_PATH_SLICE_WAVE]++;
                 if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
-                co->rec(CK_SLICE_G, S, {}, {(long long)B, fused_slice ? 1LL : 0LL}, {(int)batch, 0, 0, fused_slice ? bases_seq : 0});
+                // (not stage(): no run on its own comes here -- its launch is the branch below, which counts other paths and reports a failure)
+                co->rec(rec_slice_g(S, batch, B, fused_slice, fused_slice ? bases_seq : 0));
                 if (fused_slice && co->st2 && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
             }
             else {
@@ -2394,7 +2226,7 @@ struct Engine {
         RawSlot &rn = ring[x % raw_depth];
         if (rn.valid && rn.batch == x && rn.B == B) return;
         PcState S1 = S; S1.nhat_raw = raw_buf[x % raw_depth];
-        co->rec(CK_BASES_NEXT, S1, {}, {(long long)B}, {(int)x});
+        co->rec(rec_bases_next(S1, x, B));      // (in step only)
         rn.valid = true; rn.batch = x; rn.B = B; rn.waited = true; rn.co_seq = co->seq_for_next();
     }
 
@@ -2467,9 +2299,11 @@ struct Engine {
             bool fresh_nursery = false;
             if (h_ctl->i_nursery == 0) {
                 fresh_nursery = true;
-                const auto n0 = std::chrono::steady_clock::now(); if (r_static_ok && cfg.force_general == 0 && !(cfg.ablate & 32)) presort_live(); const bool okn = enqueue_nursery(); g_dbg_nursery_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - n0).count(); if (!okn) return false;
+                DbgSpan dbg_t{g_dbg_nursery_ns};
+                if (r_static_ok && cfg.force_general == 0 && !(cfg.ablate & 32)) presort_live();
+                if (!enqueue_nursery()) return false;
             }
-            if (fresh_nursery) { const auto n0 = std::chrono::steady_clock::now(); ensure_capacity(); g_dbg_capacity_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - n0).count(); }
+            if (fresh_nursery) { DbgSpan dbg_t{g_dbg_capacity_ns}; ensure_capacity(); }
             hipEvent_t e2 = kt.begin(KT_CONSUME);
             int rc2;
             const bool use_fast = fast_ok && h_ctl->ncluster == 1;
@@ -2479,11 +2313,8 @@ struct Engine {
                 // the parallel contraction keeps the sorted order of the live set up to date itself
                 rc2 = 0; S.nn_valid = 0;                     // (the one-cluster kernels do not keep the list bookkeeping)
                 path[PCHIP_PATH_CONSUME_PAR]++;
-                if (co) { if (!sort_valid) { co->rec(CK_SORT, S, {}, {}, {}); sort_valid = true; } co->rec(CK_CONSUME, S, {}, {}, {}); }
-                else {
-                if (!sort_valid) { rc2 = pc_launch_sort_live(&S, st); sort_valid = true; }
-                rc2 = rc2 || pc_launch_consume_par(&S, st);      // also lays out the phantoms
-                }
+                if (!sort_valid) { rc2 = stage(rec_sort(S)); sort_valid = true; }
+                rc2 = rc2 || stage(rec_consume(S));      // also lays out the phantoms
             }
             else if (use_fast) { if (co) co->flush(); sort_valid = false; S.nn_valid = 0; path[PCHIP_PATH_CONSUME_FAST]++; rc2 = pc_launch_consume_fast(&S, 0, st); pc_launch_ph_prepare(&S, st); }
             else {
@@ -2499,10 +2330,12 @@ struct Engine {
                                     pc_consume_cl_fits(&S, h_ctl->ncluster);
                 if (co && use_cl && cohort_general_ok()) {
                     // in step with other runs: lists, sort and the one-wave contraction once for all runs with several clusters
-                    if (want_nn) { co->rec(CK_NN, S, {}, {}, {0, nursery_left}); S.nn_valid = 1; path[PCHIP_PATH_NN_LISTS]++; }
+                    // (not stage(), the three of them: a run on its own passes the lists whether the sort was made now and the contraction the
+                    //  number of clusters, the rows' one-run launches 1 and 65 or 2)
+                    if (want_nn) { co->rec(rec_nn(S, nursery_left)); S.nn_valid = 1; path[PCHIP_PATH_NN_LISTS]++; }
                     path[pc_consume_clp_fits(&S, h_ctl->ncluster) ? PCHIP_PATH_CONSUME_CL : PCHIP_PATH_CONSUME_CL_SERIAL]++;
-                    co->rec(CK_SORT, S, {}, {}, {});
-                    co->rec(CK_CONSUME_CL, S, {}, {h_ctl->ncluster > 64 ? 1LL : 0LL}, {});
+                    co->rec(rec_sort(S));
+                    co->rec(rec_consume_cl(S, h_ctl->ncluster > 64));
                     rc2 = 0;
                 } else {
                 if (co) co->flush();
@@ -2524,7 +2357,7 @@ struct Engine {
             if (rc2) { std::fprintf(stderr, "polychord_hip: nlive too large for the LDS-resident contraction\n"); r_rc = 4; return false; }
             kt.end(KT_CONSUME, e2);
             hipEvent_t e3 = kt.begin(KT_APPLY);
-            if (co) co->rec(CK_APPLY, S, {}, {(long long)B}, {(int)(batch - 1)}); else pc_launch_apply(&S, batch - 1, B, st);
+            (void)stage(rec_apply(S, batch - 1, B));
             kt.end(KT_APPLY, e3);
             // the main stream's wait for the next nursery's bases is enqueued now, behind this round's kernels (long
             // satisfied when the next k_slice gets there), not between the stamp and the next launch
@@ -2607,7 +2440,7 @@ struct Engine {
             // a finished run read back from its .resume file: nothing to kill
         } else if (par_ok && h_ctl->ncluster == 1) {
             path[PCHIP_PATH_KILLOFF_PAR]++;
-            if (co && sort_valid) { co->rec(CK_FINAL, S, {}, {}, {}); if (!fused_final) co->flush(); }      // (fused: the caller launches the kill-off of all runs that end now, then calls end_a2)
+            if (co && sort_valid) { co->rec(rec_final(S)); if (!fused_final) co->flush(); }      // (fused: the caller launches the kill-off of all runs that end now, then calls end_a2)
             else {
             if (!sort_valid) (void)pc_launch_sort_live(&S, st);
             (void)pc_launch_final_par(&S, st);

@@ -55,7 +55,7 @@ int pc_launch_nn_lists_many(const PcState *S, const PcManyRec *dR, int R, int nl
 int pc_launch_consume(const PcState *S, int final_mode, int wide, hipStream_t st);
 void pc_launch_apply(const PcState *S, unsigned batch, int nchains, hipStream_t st);
 int pc_launch_apply_many(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st);
-// ... for R runs at once: every run its own row count (PcManyRec::ia[1], blocks ia[2])
+// ... for R runs at once: every run its own row count (PcManyRec::ia[PC_REC_I_ROWS], blocks PC_REC_I_BLOCKS)
 int pc_launch_clean_many(const PcManyRec *dR, int R, int nblk_max, hipStream_t st);
 void pc_launch_install_live(const PcState *S, const double *rows, int n, hipStream_t st);
 // phantom clean: returns nothing; *d_total (device int) receives the surviving count

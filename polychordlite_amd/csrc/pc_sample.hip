@@ -986,7 +986,7 @@ __global__ __launch_bounds__(16 * HV) void k_nhats_q_many(const PcManyRec *__res
     // (pointers left generic here: with them made global -- pc_many_state -- the compiler fused other multiply-adds than in the one-run
     //  kernel, the same statements, and a run in step was no longer bit for bit the run alone)
     const PcState S = R[blockIdx.z].S;
-    const unsigned batch = (unsigned)R[blockIdx.z].ia[0];
+    const unsigned batch = (unsigned)R[blockIdx.z].ia[PC_REC_I_BATCH];
     {
 #pragma clang fp contract(on)
 #include "pc_nhats_q_body.inc"
@@ -1633,7 +1633,7 @@ __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB) void k_slice_many(const PcM
     // (pointers left generic here: with them made global -- pc_many_state -- the compiler fused other multiply-adds than in the one-run
     //  kernel, the same statements, and a run in step was no longer bit for bit the run alone)
     const PcState S = R[blockIdx.y].S;
-    const unsigned batch = (unsigned)R[blockIdx.y].ia[0];
+    const unsigned batch = (unsigned)R[blockIdx.y].ia[PC_REC_I_BATCH];
     constexpr int PT = 0;                         // (runs in step take the box only)
 #include "pc_slice_body.inc"
 }

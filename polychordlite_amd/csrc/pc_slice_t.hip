@@ -478,7 +478,7 @@ __device__ __forceinline__ void slice_t_body(const PcState &S, unsigned batch, i
 template <int DT, bool UNIT>
 __global__ __launch_bounds__(64) void k_slice_t(PcState S, unsigned batch, int nchains, int nrp) { slice_t_body<DT, UNIT, false>(S, batch, nchains, nrp); }
 template <int DT, bool UNIT, bool HELP>
-__global__ __launch_bounds__(HELP ? 192 : 64) void k_slice_t_many(const PcManyRec *R, int nchains, int nrp) { slice_t_body<DT, UNIT, HELP>(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[0], nchains, nrp); }
+__global__ __launch_bounds__(HELP ? 192 : 64) void k_slice_t_many(const PcManyRec *R, int nchains, int nrp) { slice_t_body<DT, UNIT, HELP>(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[PC_REC_I_BATCH], nchains, nrp); }
 
 
 static int deck_stride(int nr) { int q = (nr + 3) / 4; if ((q & 1) == 0) q++; return 4 * q; }   // bytes, an odd number of words: lanes on different banks
@@ -665,7 +665,7 @@ __device__ __forceinline__ void deviates_t_body(const PcState &S, unsigned batch
     for (int k = lane; k < qn; k += 64) S.nhat_raw[qA[wv][k]] = pc_inv_normal_tail(qU[wv][k]);
 }
 __global__ __launch_bounds__(256) void k_deviates_t(PcState S, unsigned batch, int nbases, int NC) { deviates_t_body(S, batch, nbases, NC); }
-__global__ __launch_bounds__(256) void k_deviates_t_many(const PcManyRec *R, int nbases, int NC) { deviates_t_body(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[0], nbases, NC); }
+__global__ __launch_bounds__(256) void k_deviates_t_many(const PcManyRec *R, int nbases, int NC) { deviates_t_body(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[PC_REC_I_BATCH], nbases, NC); }
 
 
 template <int DT>

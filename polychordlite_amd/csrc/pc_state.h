@@ -179,8 +179,23 @@ struct PcState {
 
 // One run's share of a launch made for several runs at once (pchip_run_repeats: the runs of a device go round by round together,
 // and each kernel of a round is launched ONCE for all of them, blockIdx.y = run): its state, and the buffers the one-run
-// kernel takes as arguments (update: 0 keep, 1 block counts, 2 total, 3-6 the alternate phantom arrays, 7 partial sums, 8 shift).
-struct PcManyRec { PcState S; void *p[10]; int ia[6]; int pad[2]; };      // ia: 0 the nursery's number, 1 phantom rows in use (update), 2 its blocks
+// kernel takes as arguments in p[] and ia[], under the PC_REC_* names below (one name per meaning of a slot, grouped by stage).
+struct PcManyRec { PcState S; void *p[10]; int ia[6]; int pad[2]; };
+// sampling, directions, apply: the nursery's number; the sampling launches also the number of the launch that drew their bases (0: in line)
+enum { PC_REC_I_BATCH = 0, PC_REC_I_BASES_SEQ = 3 };
+// update and clean: keep flags, block counts, total, the alternate phantom arrays (rows, logL, cluster ids, uids), and for the fused update
+// its partial sums and shift; phantom rows in use and their blocks of 256
+enum { PC_REC_KEEP = 0, PC_REC_BLK = 1, PC_REC_TOTAL = 2, PC_REC_PH2 = 3, PC_REC_PHL2 = 4, PC_REC_PHC2 = 5, PC_REC_PHU2 = 6, PC_REC_PART = 7, PC_REC_SHIFT = 8 };
+enum { PC_REC_I_ROWS = 1, PC_REC_I_BLOCKS = 2 };
+// candidate lists: chains left in the nursery
+enum { PC_REC_I_NLEFT = 1 };
+// clustering, first pass over whole clusters: descriptors, similarities, kNN lists, labels, verdicts, the sub-dimension pass's coordinates;
+// descriptors, the largest cluster, coordinates in `dims` (0: the full space)
+enum { PC_REC_DESC = 0, PC_REC_SM = 1, PC_REC_KNN = 2, PC_REC_LAB = 3, PC_REC_OUT = 4, PC_REC_DIMS = 5 };
+enum { PC_REC_I_ND = 1, PC_REC_I_NMAX = 2, PC_REC_I_ND_SUB = 3 };
+// clustering, the passes over parts of clusters: part descriptors, similarities, the parts' points, kNN lists, labels, verdicts; parts, the largest
+enum { PC_REC_G_DESC = 0, PC_REC_G_SM = 1, PC_REC_G_POOL = 2, PC_REC_G_KNN = 3, PC_REC_G_LAB = 4, PC_REC_G_OUT = 5 };
+enum { PC_REC_I_NB = 1, PC_REC_I_MMAX = 2 };
 
 #ifdef __HIPCC__
 // ---- kernels that take their state from a record in memory (the runs of a device in step, blockIdx.y = run) --------------------------

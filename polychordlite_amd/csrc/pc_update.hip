@@ -128,7 +128,7 @@ __device__ __forceinline__ void upd_flag_body(const PcState &S, int nph, unsigne
     if (lane == 0) upd_store_wt(blk_count + sb, cnt);        // (write-through: the chain's last arriver reads it in this launch)
 }
 __global__ __launch_bounds__(UPD_NT) void k_upd_flag(PcState S, int nph, unsigned char *keep, int *blk_count, int def, int nblk) { upd_flag_body(S, nph, keep, blk_count, def, nblk); }
-__global__ __launch_bounds__(UPD_NT) void k_upd_flag_many(const PcManyRec *R, int def) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x * 4 >= r.ia[2]) return; upd_flag_body(r.S, r.ia[1], (unsigned char *)r.p[0], (int *)r.p[1], def, r.ia[2]); }
+__global__ __launch_bounds__(UPD_NT) void k_upd_flag_many(const PcManyRec *R, int def) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x * 4 >= r.ia[PC_REC_I_BLOCKS]) return; upd_flag_body(r.S, r.ia[PC_REC_I_ROWS], (unsigned char *)r.p[PC_REC_KEEP], (int *)r.p[PC_REC_BLK], def, r.ia[PC_REC_I_BLOCKS]); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // tickets: what lets one launch do the work of several without any workgroup waiting for another.  A workgroup that has written
@@ -273,7 +273,7 @@ __device__ __forceinline__ void upd_index_self_body(int nph, const unsigned char
     }
 }
 __global__ __launch_bounds__(UPD_IDX_NT) void k_upd_index_self(int nph, const unsigned char *keep, const int *blk_count, int nblk, int *idx, int *total) { upd_index_self_body(nph, keep, blk_count, nblk, idx, total); }
-__global__ __launch_bounds__(UPD_IDX_NT) void k_upd_index_self_many(const PcManyRec *R) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x * 16 >= r.ia[2]) return; upd_index_self_body(r.ia[1], (const unsigned char *)r.p[0], (const int *)r.p[1], r.ia[2], (int *)r.p[5], (int *)r.p[2]); }
+__global__ __launch_bounds__(UPD_IDX_NT) void k_upd_index_self_many(const PcManyRec *R) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x * 16 >= r.ia[PC_REC_I_BLOCKS]) return; upd_index_self_body(r.ia[PC_REC_I_ROWS], (const unsigned char *)r.p[PC_REC_KEEP], (const int *)r.p[PC_REC_BLK], r.ia[PC_REC_I_BLOCKS], (int *)r.p[PC_REC_PHC2], (int *)r.p[PC_REC_TOTAL]); }
 
 
 // sixteen rows given by index, coordinates minus shift and a one, to consecutive tile rows; lane = element, the loads of
@@ -310,7 +310,7 @@ __device__ __forceinline__ void upd_fold_body(const double *part, int nb, int E,
     }
 }
 __global__ __launch_bounds__(256) void k_upd_fold(const double *part, int nb, int E, double *part2) { upd_fold_body(part, nb, E, part2, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_upd_fold_many(const PcManyRec *R, int nb, int E) { double *part = pc_as_global((double *)R[blockIdx.y].p[7], R); upd_fold_body(part, nb, E, part + (size_t)nb * E, blockIdx.x); }
+__global__ __launch_bounds__(256) void k_upd_fold_many(const PcManyRec *R, int nb, int E) { double *part = pc_as_global((double *)R[blockIdx.y].p[PC_REC_PART], R); upd_fold_body(part, nb, E, part + (size_t)nb * E, blockIdx.x); }
 
 
 // fold + mean + covariance + Cholesky; one workgroup of 256 threads (four wavefronts: what the fold and the D x D copies use)
@@ -420,7 +420,7 @@ __device__ __forceinline__ void upd_final_body(const PcState &S, int nb, const d
     else if (NT != 1) upd_final_stage<32>(S, lds, shift, def);
 }
 __global__ __launch_bounds__(256) void k_upd_final(PcState S, int nb, const double *part, int E, double *shift, int def) { __shared__ double lds[UPD_FINAL_LDS]; upd_final_body<0>(S, nb, part, E, lds, shift, def); }
-__global__ __launch_bounds__(256) void k_upd_final_many(const PcManyRec *R, int nb, int E, int def, int G) { __shared__ double lds[UPD_FINAL_LDS]; const PcManyView r = pc_many_view(R, blockIdx.y); upd_final_body<0>(r.S, nb, (const double *)r.p[7] + (size_t)G * E, E, lds, (double *)r.p[8], def); }
+__global__ __launch_bounds__(256) void k_upd_final_many(const PcManyRec *R, int nb, int E, int def, int G) { __shared__ double lds[UPD_FINAL_LDS]; const PcManyView r = pc_many_view(R, blockIdx.y); upd_final_body<0>(r.S, nb, (const double *)r.p[PC_REC_PART] + (size_t)G * E, E, lds, (double *)r.p[PC_REC_SHIFT], def); }
 
 
 typedef double upd_v4d __attribute__((ext_vector_type(4)));
@@ -715,8 +715,8 @@ template <int NT>
 __global__ __launch_bounds__(256) void k_upd_gather_many(const PcManyRec *R, int E, int def, int nlb, int ndb)
 {
     const PcManyView r = pc_many_view(R, blockIdx.y);
-    upd_gather_body<NT, true, false>(r.S, r.ia[1], r.ia[2], (const unsigned char *)r.p[0], (const int *)r.p[1], (double *)r.p[3], (double *)r.p[4], (unsigned *)r.p[5],
-                              (unsigned long long *)r.p[6], (const int *)r.p[5], (const int *)r.p[2], (const double *)r.p[8], (double *)r.p[7], E, def, nlb, ndb);
+    upd_gather_body<NT, true, false>(r.S, r.ia[PC_REC_I_ROWS], r.ia[PC_REC_I_BLOCKS], (const unsigned char *)r.p[PC_REC_KEEP], (const int *)r.p[PC_REC_BLK], (double *)r.p[PC_REC_PH2], (double *)r.p[PC_REC_PHL2], (unsigned *)r.p[PC_REC_PHC2],
+                              (unsigned long long *)r.p[PC_REC_PHU2], (const int *)r.p[PC_REC_PHC2], (const int *)r.p[PC_REC_TOTAL], (const double *)r.p[PC_REC_SHIFT], (double *)r.p[PC_REC_PART], E, def, nlb, ndb);
 }
 
 
@@ -830,7 +830,7 @@ extern "C" void pc_launch_update_fused(const PcState *S, int nph, unsigned char 
 
 extern "C" int pc_update_fused_grid(const PcState *S, int nph, int deferred) { return upd_grid(S, nph, deferred); }
 // the fused update for R runs of one shape at once (blockIdx.y = run); every run brings its own number of phantom rows
-// (PcManyRec::ia[1], its blocks in ia[2]); all of them the same number G of gathering workgroups (pc_update_fused_grid) and
+// (PcManyRec::ia[PC_REC_I_ROWS], its blocks in PC_REC_I_BLOCKS); all of them the same number G of gathering workgroups (pc_update_fused_grid) and
 // nblk_max >= their blocks.  1: not this way (the caller launches them one by one)
 extern "C" int pc_launch_update_fused_many(const PcState *S, const PcManyRec *dR, int R, int nblk_max, int G, int deferred, hipStream_t st)
 {
