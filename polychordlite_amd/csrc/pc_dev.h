@@ -178,20 +178,28 @@ __device__ __forceinline__ void pc_lds_barrier() { asm volatile("s_waitcnt lgkmc
 // Butterfly inside each row of 16 lanes with DPP (no LDS traffic), then the four row
 // results are combined through v_readlane.  Every lane ends with the bit-identical total
 // (IEEE add/min are commutative and each level combines the same two partial results).
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
-
 #define PC_DPP_XOR1 0xB1        /* quad_perm [1,0,3,2] */
 #define PC_DPP_XOR2 0x4E        /* quad_perm [2,3,0,1] */
 #define PC_DPP_HALF_MIRROR 0x141
 #define PC_DPP_MIRROR 0x140
+// (a control that reads a valid lane everywhere -- quad_perm, the two mirrors -- never shows `old`: with bound_ctrl the move needs no zeroed
+//  destination in front of it, a level of a butterfly is two moves and the operation instead of two zero moves, a wait state, two moves and
+//  the operation.  The shifts and broadcasts keep old = 0: their lanes without a source rely on it.)
+template <int CTRL>
+constexpr bool pc_dpp_full = CTRL < 0x100 || CTRL == PC_DPP_HALF_MIRROR || CTRL == PC_DPP_MIRROR;
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, pc_dpp_full<CTRL>); }
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v)
+{
+    const int lo = dpp_i32<CTRL>(__double2loint(v));
+    const int hi = dpp_i32<CTRL>(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+// the lanes where `p` holds.  With a comparison as its argument this is the comparison's own lane mask, and whatever is built from such
+// masks with & and | stays on the scalar unit down to the one compare with zero (__ballot(p) != 0 takes an int: the mask becomes a 0 / 1
+// per lane, is compared again on the vector unit, and only then reaches the scalar unit)
+__device__ __forceinline__ unsigned long long pc_lanes(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 __device__ __forceinline__ double readlane_f64(double v, int lane)
 {
@@ -208,18 +216,35 @@ __device__ __forceinline__ double row_sum(double v)
     v += dpp_f64<PC_DPP_MIRROR>(v);
     return v;
 }
+// two / three row sums level by level: each sum its own tree, operands and order as row_sum's, the levels of one between the levels
+// of the other so that no move waits on the add in front of it
+__device__ __forceinline__ void row_sum2(double &a, double &b)
+{
+    { const double ta = dpp_f64<PC_DPP_XOR1>(a), tb = dpp_f64<PC_DPP_XOR1>(b); a += ta; b += tb; }
+    { const double ta = dpp_f64<PC_DPP_XOR2>(a), tb = dpp_f64<PC_DPP_XOR2>(b); a += ta; b += tb; }
+    { const double ta = dpp_f64<PC_DPP_HALF_MIRROR>(a), tb = dpp_f64<PC_DPP_HALF_MIRROR>(b); a += ta; b += tb; }
+    { const double ta = dpp_f64<PC_DPP_MIRROR>(a), tb = dpp_f64<PC_DPP_MIRROR>(b); a += ta; b += tb; }
+}
+__device__ __forceinline__ void row_sum3(double &a, double &b, double &c)
+{
+    { const double ta = dpp_f64<PC_DPP_XOR1>(a), tb = dpp_f64<PC_DPP_XOR1>(b), tc = dpp_f64<PC_DPP_XOR1>(c); a += ta; b += tb; c += tc; }
+    { const double ta = dpp_f64<PC_DPP_XOR2>(a), tb = dpp_f64<PC_DPP_XOR2>(b), tc = dpp_f64<PC_DPP_XOR2>(c); a += ta; b += tb; c += tc; }
+    { const double ta = dpp_f64<PC_DPP_HALF_MIRROR>(a), tb = dpp_f64<PC_DPP_HALF_MIRROR>(b), tc = dpp_f64<PC_DPP_HALF_MIRROR>(c); a += ta; b += tb; c += tc; }
+    { const double ta = dpp_f64<PC_DPP_MIRROR>(a), tb = dpp_f64<PC_DPP_MIRROR>(b), tc = dpp_f64<PC_DPP_MIRROR>(c); a += ta; b += tb; c += tc; }
+}
 
 // sum over the whole wave; NROWS = number of 16-lane rows that can hold non-zero data
 template <int NROWS>
-__device__ __forceinline__ double wave_sum(double v)
+__device__ __forceinline__ double wave_sum_rows(double v)     // (v: the row sums, every lane of a row its row's)
 {
-    v = row_sum(v);
     if (NROWS == 1) return readlane_f64(v, 0);
     const double r0 = readlane_f64(v, 0), r1 = readlane_f64(v, 16);
     if (NROWS == 2) return r0 + r1;
     const double r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
     return (r0 + r1) + (r2 + r3);
 }
+template <int NROWS>
+__device__ __forceinline__ double wave_sum(double v) { return wave_sum_rows<NROWS>(row_sum(v)); }
 
 __device__ __forceinline__ double wave_max(double v)
 {

@@ -413,8 +413,10 @@ __global__ __launch_bounds__(64) void k_consume_fast(PcState S, int final_mode)
         ctl->ncluster = nc; ctl->ncluster_dead = nc_dead;
         ctl->nlike = nlike; ctl->niter = niter; ctl->nlike_failed = nlike_failed; ctl->logZ = logZ; ctl->logZ2 = logZ2; ctl->logX_last_update = lx_last;
         ctl->live_logZ = live_logZ_val;
+#ifndef PAR_NO_DBG      // (the developer builds that keep k_slice's own counters in PcCtl::dbg)
         ctl->dbg[0] += cy1 - cy0; ctl->dbg[1] += cyB; ctl->dbg[2] += cyCommon; ctl->dbg[3] += nCommon; ctl->dbg[4] += nFlush;
         ctl->dbg[5] += cyIns; ctl->dbg[6] += nIns; ctl->dbg[7] += cyRej;
+#endif
     }
 }
 

@@ -1442,14 +1442,15 @@ __device__ __forceinline__ double eval_at(ChainCtx<DPL, NROWS, PT> &C, const dou
 {
     bool outside = false;
     if (C.quad) {
+        unsigned long long om = 0ull;               // the lanes outside the cube, as a mask: one scalar compare decides
 #pragma unroll
         for (int k = 0; k < DPL; ++k) {
             cube[k] = x0[k] + t * nh[k];
-            if (C.ld.on[k]) outside |= (cube[k] < 0.0) | (cube[k] > 1.0);
+            om |= (pc_lanes(cube[k] < 0.0) | pc_lanes(cube[k] > 1.0)) & pc_lanes(C.ld.on[k]);
             th[k] = C.ld.lo[k] + C.ld.span[k] * cube[k];
         }
         double lg = C.qnorm - (C.qa + t * (2.0 * C.qb + t * C.qc)) / 2.0;
-        if (__ballot(outside) != 0ull) {
+        if (om != 0ull) {
 #pragma unroll
             for (int k = 0; k < DPL; ++k) th[k] = 0.0;
             lg = C.S.logzero;                   // calculate.f90:36-38
@@ -1523,16 +1524,18 @@ __device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS, PT> &C, const dou
         return;
     }
     if (C.quad) {
-        bool oA = false, oB = false;
+        unsigned long long oA = 0ull, oB = 0ull;     // the lanes outside the cube, as masks
 #pragma unroll
         for (int k = 0; k < DPL; ++k) {
             const double cA = x0[k] + tA * nh[k], cB = x0[k] + tB * nh[k];
-            if (C.ld.on[k]) { oA |= (cA < 0.0) | (cA > 1.0); oB |= (cB < 0.0) | (cB > 1.0); }
+            const unsigned long long on = pc_lanes(C.ld.on[k]);
+            oA |= (pc_lanes(cA < 0.0) | pc_lanes(cA > 1.0)) & on; oB |= (pc_lanes(cB < 0.0) | pc_lanes(cB > 1.0)) & on;
         }
         lA = C.qnorm - (C.qa + tA * (2.0 * C.qb + tA * C.qc)) / 2.0;
         lB = C.qnorm - (C.qa + tB * (2.0 * C.qb + tB * C.qc)) / 2.0;
-        if (__ballot(oA) != 0ull) lA = C.S.logzero; else if (lA > C.S.logzero) C.nlike++;     // calculate.f90:36-38
-        if (__ballot(oB) != 0ull) lB = C.S.logzero; else if (lB > C.S.logzero) C.nlike++;
+        // (calculate.f90:36-38; selects and a sum: no branch, no exec mask around one add)
+        lA = oA != 0ull ? C.S.logzero : lA; lB = oB != 0ull ? C.S.logzero : lB;
+        C.nlike += (int)(lA > C.S.logzero) + (int)(lB > C.S.logzero);
         return;
     }
     if (kind != PC_LIKE_RASTRIGIN && kind != PC_LIKE_TWIN_GAUSSIAN) {
@@ -1611,6 +1614,12 @@ __device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS, PT> &C, const dou
 // the directions never travel through HBM: a prologue whitens all of the chain's directions at once, lane = direction
 // (the loops of k_nhats, bit for bit: row sums in ascending b, the norm on four partial sums), into LDS, from where the
 // slices pick them up in deck order.  FW = unroll width >= nDims.
+// PC_STEP_SPEC: the candidates of each side that the stepping out of a closed-form slice evaluates in straight-line code before its loop
+// (pc_slice_body.inc; profiles/slice_stepping.json has the histogram it was chosen from).  0 = the loop alone, a developer build.
+#ifndef PC_STEP_SPEC
+#define PC_STEP_SPEC 1
+#endif
+constexpr int pc_step_spec = PC_STEP_SPEC;
 // PC_SLICE_WAVES (build-time experiment): cap the registers so that this many waves share a SIMD
 #ifdef PC_SLICE_WAVES
 #define PC_SLICE_ATTR __attribute__((amdgpu_waves_per_eu(PC_SLICE_WAVES, PC_SLICE_WAVES)))

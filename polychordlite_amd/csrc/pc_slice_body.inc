@@ -335,6 +335,9 @@
 
 #ifdef SLICE_DBG
     long long scy[6] = {0, 0, 0, 0, 0, 0}; long long nev = 0, ev2 = 0;
+#if SLICE_DBG == 3
+    long long hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
 #if SLICE_DBG == 2
     const long long kc1 = clock64();
 #endif
@@ -421,7 +424,6 @@
                     const double zB = (ld.span[k] * nh[k]) * S.like.inv_sigma;
                     if (ld.on[k]) { pa += zA * zA; pb += zA * zB; if (!(LEAN == 1 && have_qc)) pc += zB * zB; }
                 }
-                C.qa = wsum<DPL, NROWS>(pa);
             } else {
 #pragma unroll
                 for (int k = 0; k < DPL; ++k) sv[k] = ld.on[k] ? ld.span[k] * nh[k] : 0.0;
@@ -429,8 +431,16 @@
 #pragma unroll
                 for (int k = 0; k < DPL; ++k) { pb += sv[k] * My[k]; pc += sv[k] * Ms[k]; }
             }
-            C.qb = wsum<DPL, NROWS>(pb);
-            if (LEAN == 1 && have_qc) C.qc = qc_cur; else C.qc = wsum<DPL, NROWS>(pc);
+            // (the slice's wave sums side by side: each its own tree, a level of one between the levels of the others)
+            constexpr int NR_ = DPL > 1 ? 4 : NROWS;
+            if (!corr) {
+                if (LEAN == 1 && have_qc) { row_sum2(pa, pb); C.qc = qc_cur; }
+                else { row_sum3(pa, pb, pc); C.qc = wave_sum_rows<NR_>(pc); }
+                C.qa = wave_sum_rows<NR_>(pa); C.qb = wave_sum_rows<NR_>(pb);
+            } else {
+                row_sum2(pb, pc);
+                C.qb = wave_sum_rows<NR_>(pb); C.qc = wave_sum_rows<NR_>(pc);
+            }
         }
         // initial bracket (chordal_sampling.f90:213-219)
         const double u0 = next_u();
@@ -441,10 +451,65 @@
         const long long c2 = clock64();
 #endif
         // stepping out (:223-236)
-        int istep = 0;
-        while (lR >= contour && lR > logzero) { istep++; tR = w * istep; lR = eval_at<DPL, NROWS, KINDV>(C, x0, nh, tR, cube, th); }
-        istep = 0;
-        while (lL >= contour && lL > logzero) { istep++; tL = -(w * istep); lL = eval_at<DPL, NROWS, KINDV>(C, x0, nh, tL, cube, th); }
+        int istepR = 0, istepL = 0;
+        if (C.quad && !seq_mode) {
+            // The first pc_step_spec candidates of each side at once.  Where candidate j lies -- w j to the right, -(w j) to the left -- does
+            // not depend on any likelihood, and with the closed form along the chord one more candidate is a handful of operations: so they
+            // are computed in straight-line code, as the shrinkage's four trials below, and each side takes the first one that ends the
+            // reference's loop; the candidates behind it never happened (not counted).  A loop iteration is one dependent chain through the
+            // vector unit, the scalar unit and two or three taken branches; here the state moves by selects.  A side that none of the
+            // candidates ends goes on in the loop below with candidate pc_step_spec + 1 (its test fails at once for every other side).
+            bool goR = (lR >= contour) & (lR > logzero), goL = (lL >= contour) & (lL > logzero);
+            int cnt = 0;
+#if defined(SLICE_DBG) && SLICE_DBG == 3
+            int nR = 0, nL = 0;
+#endif
+#pragma unroll
+            for (int j = 1; j <= pc_step_spec; ++j) {
+                const double tr = w * j, tl = -(w * j);
+                unsigned long long oR = 0ull, oL = 0ull;
+#pragma unroll
+                for (int k = 0; k < DPL; ++k) {
+                    const double cR = x0[k] + tr * nh[k], cL = x0[k] + tl * nh[k];
+                    const unsigned long long on = pc_lanes(ld.on[k]);
+                    oR |= (pc_lanes(cR < 0.0) | pc_lanes(cR > 1.0)) & on; oL |= (pc_lanes(cL < 0.0) | pc_lanes(cL > 1.0)) & on;
+                }
+                const double gR = C.qnorm - (C.qa + tr * (2.0 * C.qb + tr * C.qc)) / 2.0;
+                const double gL = C.qnorm - (C.qa + tl * (2.0 * C.qb + tl * C.qc)) / 2.0;
+                const double lr = oR != 0ull ? logzero : gR, ll = oL != 0ull ? logzero : gL;     // calculate.f90:36-38
+                const bool evR = goR & (lr > logzero), evL = goL & (ll > logzero);                 // ... :44, the evaluations the loop would count
+                cnt += (int)evR + (int)evL;
+                tR = goR ? tr : tR; lR = goR ? lr : lR;
+                tL = goL ? tl : tL; lL = goL ? ll : lL;
+#if defined(SLICE_DBG) && SLICE_DBG == 3
+                nR += (int)goR; nL += (int)goL;
+#endif
+                goR = evR & (lr >= contour); goL = evL & (ll >= contour);
+            }
+            C.nlike += cnt;
+            istepR = istepL = pc_step_spec;
+#if defined(SLICE_DBG) && SLICE_DBG == 3
+            if (!goR) istepR = nR;
+            if (!goL) istepL = nL;
+#endif
+        }
+#if defined(SLICE_DBG) && SLICE_DBG == 3
+        const int spR = istepR, spL = istepL;
+#endif
+        while (lR >= contour && lR > logzero) { istepR++; tR = w * istepR; lR = eval_at<DPL, NROWS, KINDV>(C, x0, nh, tR, cube, th); }
+        while (lL >= contour && lL > logzero) { istepL++; tL = -(w * istepL); lL = eval_at<DPL, NROWS, KINDV>(C, x0, nh, tL, cube, th); }
+#if defined(SLICE_DBG) && SLICE_DBG == 3
+        // the histogram build: iterations of the reference's loop per side (right in the low word, left in the high one) and the slices whose
+        // loop went on behind the straight-line candidates
+        {
+            const bool fbR = istepR > spR, fbL = istepL > spL;
+#pragma unroll
+            for (int x = 0; x < 5; ++x) hist[x] += (long long)((istepR < 4 ? istepR : 4) == x) + ((long long)((istepL < 4 ? istepL : 4) == x) << 32);
+            hist[5] += 1ll + ((long long)(istepR > 0 && istepL > 0) << 32);
+            hist[6] += (long long)(fbR && !fbL) + ((long long)(fbL && !fbR) << 32);
+            hist[7] += (long long)(fbR && fbL);
+        }
+#endif
 #ifdef SLICE_DBG
         const long long c3 = clock64();
 #endif
@@ -473,15 +538,17 @@
                 tc[q] = t;
                 if (t > 0.0) tRc = t; else tLc = t;
                 tLb[q] = tLc; tRb[q] = tRc;                         // the bracket after rejecting trial q
-                bool outside = false;
+                unsigned long long om = 0ull;
 #pragma unroll
                 for (int k = 0; k < DPL; ++k) {
                     const double cb = x0[k] + t * nh[k];
-                    if (ld.on[k]) outside |= (cb < 0.0) | (cb > 1.0);
+                    om |= (pc_lanes(cb < 0.0) | pc_lanes(cb > 1.0)) & pc_lanes(ld.on[k]);
                 }
-                oc[q] = __ballot(outside) != 0ull;
+                oc[q] = om != 0ull;
                 lc[q] = C.qnorm - (C.qa + t * (2.0 * C.qb + t * C.qc)) / 2.0;
             }
+            // (a chain of ifs that leaves at the first accepted trial -- most slices accept the first or second: the same decisions as selects
+            //  over all four trials measured 3 us a launch slower, with scalar branches on the lane masks level: profiles/slice_stepping.json)
             int acc = -1;
 #pragma unroll
             for (int q = 0; q < NSP; ++q) {
@@ -588,6 +655,8 @@
     }
 #if defined(SLICE_DBG) && SLICE_DBG == 2
     const long long kc2 = clock64();
+#elif defined(SLICE_DBG) && SLICE_DBG == 3
+    if (lane == 0) for (int x = 0; x < 8; ++x) atomicAdd((unsigned long long *)&S.ctl->dbg[x], (unsigned long long)hist[x]);      // (every chain)
 #elif defined(SLICE_DBG)
     if (lane == 0 && chain == 0) { for (int x = 0; x < 5; ++x) S.ctl->dbg[x] += scy[x]; S.ctl->dbg[5] += nev; S.ctl->dbg[6] += scy[5]; S.ctl->dbg[7] += ev2; }
 #endif
