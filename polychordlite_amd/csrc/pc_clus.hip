@@ -402,8 +402,7 @@ __global__ __launch_bounds__(KO_NT) void k_killoff_cl(PcState S, int npow2, int 
 // 0: launched; 1: not this way (the caller takes the general kernel)
 extern "C" int pc_launch_killoff_cl(const PcState *S, int nc, hipStream_t st)
 {
-    static const bool off = std::getenv("PC_KILLOFF_GENERAL") != nullptr;
-    if (off || (S->ablate & 512) || nc < 2 || nc > KO_MAXC || S->seq_mode) return 1;
+    if ((S->ablate & PC_ABL_KILLOFF_GENERAL) || nc < 2 || nc > KO_MAXC || S->seq_mode) return 1;
     int npow2 = 64;
     while (npow2 < S->Ncap) npow2 <<= 1;
     const size_t sh = ko_layout(S->Ncap, npow2, nc).total;
@@ -419,11 +418,21 @@ extern "C" int pc_consume_cl_fits(const PcState *S, int nc)
     return cl_layout(S->Ncap, S->B, S->nr).total + 1024 <= (size_t)160 * 1024;
 }
 
-// the kernel with parallel decisions: the same envelope, its own (larger) LDS block, at most 127 clusters in a death's packed record
+// The kernel with parallel decisions: the same envelope and its own (larger) LDS block.  Its packed fields rely on four limits, stated here although each
+// follows from pc_consume_cl_fits and the LDS budget today -- a change to CL_MAXC, cl_layout or the budget then cannot overflow a field silently:
+//   nc <= 128      a cluster's index (0 .. 127) in 7 bits of a death's record (cdca: cd | ca << 8, bit 15 a flag; ClEvt::a: cd << 1 below predC + 1 at bit 8)
+//                  and cluster + 1 (1 .. 128) in the 8 bits of clp_tag -- 128 clusters, not 127: the indices stop at 127.  pc_consume_cl_fits: nc <= CL_MAXC
+//   B <= 1024      the chains of a launch in the per-thread arrays of the death links ((1024 + CLP_NT - 1) / CLP_NT entries).  pc_consume_cl_fits asks it
+//   T < 2047       a step of the launch (T <= B of them) in clp_tag's 11 bits of birth + 1 and below CLP_NEVER in its 13 bits of death: B <= 1024
+//   Ncap < 32768   a rank of the sorted snapshot in 15 bits (sU: bit 15 says "a candidate"; idxOf, sSlotOf: 0xFFFF says none).  ClSlot is 16 bytes a live
+//                  point, so cl_layout(...).total <= 160 KB alone keeps Ncap below 10240
+static_assert(CL_MAXC <= 128, "cdca and ClEvt::a hold a cluster's index in 7 bits, clp_tag cluster + 1 in 8");
+static_assert(CL_MAXC == 2 * 64, "two clusters per lane: the per-cluster registers are J = 1 or 2 wide");
+static_assert(sizeof(ClSlot) * 32768 > (size_t)160 * 1024, "the LDS budget no longer keeps Ncap below 32768: pc_consume_clp_fits must ask");
 extern "C" int pc_consume_clp_fits(const PcState *S, int nc)
 {
-    static const bool off = std::getenv("PC_CONSUME_CLP_OFF") != nullptr;
-    if (off || (S->ablate & 1024) || !pc_consume_cl_fits(S, nc)) return 0;
+    if ((S->ablate & PC_ABL_CONSUME_CL_SERIAL) || !pc_consume_cl_fits(S, nc)) return 0;
+    if (nc > 128 || S->B > 1024 || S->B >= (int)CLP_NEVER || S->Ncap >= 32768) return 0;      // (implied by the line above: see the table)
     int npow2 = 2;
     while (npow2 < S->Ncap) npow2 <<= 1;
     if ((size_t)npow2 * 16 + 1024 > (size_t)160 * 1024) return 0;      // (the in-kernel sort of the live set between passes)
@@ -433,38 +442,20 @@ extern "C" int pc_consume_clp_fits(const PcState *S, int nc)
 // (the runs of a launch: one shape -- live points, chains, repeats -- and one width J of the per-cluster registers)
 extern "C" int pc_launch_consume_cl_many(const PcState *S, const PcManyRec *dR, int R, int wide, hipStream_t st)
 {
-    if (pc_consume_clp_fits(S, 2)) {
-        const size_t shp = clp_layout(S->Ncap, S->B, S->nr).total;
-        if (!wide) { pc_need_dyn_lds((const void *)k_consume_clp_many<1>, shp); hipLaunchKernelGGL(k_consume_clp_many<1>, dim3(1, R), dim3(CLP_NT), shp, st, dR); }
-        else { pc_need_dyn_lds((const void *)k_consume_clp_many<2>, shp); hipLaunchKernelGGL(k_consume_clp_many<2>, dim3(1, R), dim3(CLP_NT), shp, st, dR); }
-        return 0;
-    }
-    const size_t sh = cl_layout(S->Ncap, S->B, S->nr).total;
-    if (!wide) {
-        pc_need_dyn_lds((const void *)k_consume_cl_many<1>, sh);
-        hipLaunchKernelGGL(k_consume_cl_many<1>, dim3(1, R), dim3(CL_NT), sh, st, dR);
-    } else {
-        pc_need_dyn_lds((const void *)k_consume_cl_many<2>, sh);
-        hipLaunchKernelGGL(k_consume_cl_many<2>, dim3(1, R), dim3(CL_NT), sh, st, dR);
-    }
+    const bool clp = pc_consume_clp_fits(S, 2);
+    void (*const k)(const PcManyRec *) = clp ? (wide ? k_consume_clp_many<2> : k_consume_clp_many<1>) : (wide ? k_consume_cl_many<2> : k_consume_cl_many<1>);
+    const size_t sh = clp ? clp_layout(S->Ncap, S->B, S->nr).total : cl_layout(S->Ncap, S->B, S->nr).total;
+    pc_need_dyn_lds((const void *)k, sh);
+    hipLaunchKernelGGL(k, dim3(1, R), dim3(clp ? CLP_NT : CL_NT), sh, st, dR);
     return 0;
 }
 
 extern "C" int pc_launch_consume_cl(const PcState *S, int nc, hipStream_t st)
 {
-    if (pc_consume_clp_fits(S, nc)) {
-        const size_t shp = clp_layout(S->Ncap, S->B, S->nr).total;
-        if (nc <= 64) { pc_need_dyn_lds((const void *)k_consume_clp<1>, shp); hipLaunchKernelGGL(k_consume_clp<1>, dim3(1), dim3(CLP_NT), shp, st, *S); }
-        else { pc_need_dyn_lds((const void *)k_consume_clp<2>, shp); hipLaunchKernelGGL(k_consume_clp<2>, dim3(1), dim3(CLP_NT), shp, st, *S); }
-        return 0;
-    }
-    const size_t sh = cl_layout(S->Ncap, S->B, S->nr).total;
-    if (nc <= 64) {
-        pc_need_dyn_lds((const void *)k_consume_cl<1>, sh);
-        hipLaunchKernelGGL(k_consume_cl<1>, dim3(1), dim3(CL_NT), sh, st, *S);
-    } else {
-        pc_need_dyn_lds((const void *)k_consume_cl<2>, sh);
-        hipLaunchKernelGGL(k_consume_cl<2>, dim3(1), dim3(CL_NT), sh, st, *S);
-    }
+    const bool clp = pc_consume_clp_fits(S, nc), wide = nc > 64;
+    void (*const k)(PcState) = clp ? (wide ? k_consume_clp<2> : k_consume_clp<1>) : (wide ? k_consume_cl<2> : k_consume_cl<1>);
+    const size_t sh = clp ? clp_layout(S->Ncap, S->B, S->nr).total : cl_layout(S->Ncap, S->B, S->nr).total;
+    pc_need_dyn_lds((const void *)k, sh);
+    hipLaunchKernelGGL(k, dim3(1), dim3(clp ? CLP_NT : CL_NT), sh, st, *S);
     return 0;
 }

@@ -859,7 +859,7 @@
     }
     // go round again?  (uniform: every thread holds the same values)
     const bool again = cluster_deleted && status == PC_ST_RUNNING && i_nursery > 0 && !S.epoch_discard && nc >= 2 && out_i[1] == PC_ERR_NONE &&
-                       ncd + nc + 2 <= S.maxc_dead && pass < 256 && !(S.ablate & 256);      // (settings.ablate bit 8: the launch ends at a cluster's death, as before round 5)
+                       ncd + nc + 2 <= S.maxc_dead && pass < 256 && !(S.ablate & PC_ABL_CL_END_AT_DEATH);      // (settings.ablate bit 8: the launch ends at a cluster's death, as before round 5)
     if (!again) break;
     redo_limit = CL_NO_LIMIT;
     __threadfence(); __syncthreads();                 // the state this pass wrote is what the next one stages

@@ -408,7 +408,7 @@
     // cluster can neither gain nor lose a point any more, the chains seeded in it are lost from the next step on (what the remap does to them), its
     // volume leaves the update trigger's sum behind the step of its death -- and the arrays are compacted when the pass is over, cluster after cluster
     // in the order they ended.  (The reference farm's rule, settings.epoch_discard = 1: the pass ends at the death, as before.)
-    const bool can_cont = !S.epoch_discard && !(S.ablate & 256) && ctl->ncluster_dead + nc + 2 <= S.maxc_dead;
+    const bool can_cont = !S.epoch_discard && !(S.ablate & PC_ABL_CL_END_AT_DEATH) && ctl->ncluster_dead + nc + 2 <= S.maxc_dead;
     auto qall = [&](int r) -> int { const int wd = r >> 6; return wd >= 16 ? 0 : sufW[wd + 1] + __popcll(accW[wd] >> (r & 63)); };
     // ---- B1: the order of deaths = the first K (+ 1) entries of the merge of the snapshot and the accepted candidates
     for (int t = tid; t < Tp; t += CLP_NT) {
@@ -1298,7 +1298,7 @@
     }
     // go round again?  (uniform: every thread holds the same values) -- behind a cluster's death, or in front of a baby that asks for the full search
     const bool again = ((cluster_deleted && need_drop) || hard_end) && status == PC_ST_RUNNING && i_nursery > 0 && !(S.epoch_discard && cluster_deleted) && nc >= 2 && out_i[1] == PC_ERR_NONE &&
-                       ncd + nc + 2 <= S.maxc_dead && pass < 1024 && (!(S.ablate & 256) || !cluster_deleted);
+                       ncd + nc + 2 <= S.maxc_dead && pass < 1024 && (!(S.ablate & PC_ABL_CL_END_AT_DEATH) || !cluster_deleted);
     if (!again) break;
     redo_limit = CL_NO_LIMIT; hard_cap = 0x7fffffff;
     __threadfence(); __syncthreads();                 // the state this pass wrote is what the next one stages

@@ -9,6 +9,7 @@
 #include "pc_resume.h"
 #include "pc_prior_table.h"
 #include "pc_launch.h"
+#include "pc_plan.h"       // which kernels a run, a nursery, a contraction and an update take; the developer switches of the environment (pc_env)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -154,9 +155,8 @@ BlockCache &hcache() { static BlockCache *c = new BlockCache(true, (size_t)12 <<
 // what the previous run left in it
 template <class T> T *dalloc(size_t n)
 {
-    static const bool poison = std::getenv("PC_POISON") != nullptr;
     T *p = (T *)dcache().get(sizeof(T) * (n ? n : 1));
-    if (poison) { (void)hipMemset((void *)p, 0x5A, sizeof(T) * (n ? n : 1)); (void)hipDeviceSynchronize(); }
+    if (pc_env().poison) { (void)hipMemset((void *)p, 0x5A, sizeof(T) * (n ? n : 1)); (void)hipDeviceSynchronize(); }
     return p;
 }
 static thread_local std::vector<void *> *tl_dfree_batch = nullptr;      // (Engine::destroy: the blocks are collected and given back together)
@@ -271,8 +271,7 @@ static bool streams_overlap_test(hipStream_t a, hipStream_t b)
     static std::atomic<bool> warmed{false};
     if (!warmed.exchange(true)) (void)both();                // (the kernel's first launch loads its code)
     const double two = std::min(both(), both());
-    static const bool dbg = std::getenv("PC_DEBUG") && std::atoi(std::getenv("PC_DEBUG")) == 5;
-    if (dbg) std::fprintf(stderr, "polychord_hip dbg streams %p %p: both %.1f us\n", (void *)a, (void *)b, two * 1e6);
+    if (pc_env().debug == 5) std::fprintf(stderr, "polychord_hip dbg streams %p %p: both %.1f us\n", (void *)a, (void *)b, two * 1e6);
     return two < 170e-6;                                    // side by side: ~120 us (one spin and the launches); in turn: ~225 us
 }
 // streams that take turns are streams of one hardware queue: every stream is put into its class once (one test against a
@@ -300,8 +299,7 @@ static StreamClasses &sclasses() { static StreamClasses *p = new StreamClasses; 
 static hipStream_t stream_avoiding(std::vector<int> avoid, bool known_only = false);
 static hipStream_t stream_beside(std::initializer_list<hipStream_t> others, bool known_only = false)
 {
-    static const bool off = std::getenv("PC_SIDE_PICK_OFF") != nullptr;
-    if (off) return hpool().get_stream();
+    if (pc_env().side_pick_off) return hpool().get_stream();
     std::vector<int> avoid;
     for (hipStream_t o : others) if (o) { const int c = known_only ? sclasses().known(o) : sclasses().classify(o); if (c >= 0) avoid.push_back(c); }
     return stream_avoiding(avoid, known_only);
@@ -321,7 +319,7 @@ static hipStream_t stream_avoiding(std::vector<int> avoid, bool known_only)
     hipStream_t pick = nullptr;
     for (int k = 0; k < 8 && !pick; ++k) {
         hipStream_t c = hpool().take_stream_if([&](hipStream_t x) { return sclasses().known(x) < 0; });
-        static const bool dbg = std::getenv("PC_DEBUG") && std::atoi(std::getenv("PC_DEBUG")) == 5;
+        const bool dbg = pc_env().debug == 5;
         const auto q0 = std::chrono::steady_clock::now();
         const bool made = !c;
         if (!c) { HIPCHK(hipStreamCreate(&c)); }
@@ -562,7 +560,6 @@ struct Engine {
     Timing tm;
     KTimer kt;
     int B = 0, dev = 0;
-    bool fast_ok = false;
     bool cb_auto_batch = false; int B_small = 1; double cb_eval_seconds = -1.0;   // host callbacks: chains per nursery chosen from the measured cost of a call
     long long nlike_g[PC_MAX_GRADE] = {0};      // RTI%nlike per grade (grade 1 includes the prior samples)
     std::vector<int> h_nlike_g;                 // [B][PC_MAX_GRADE] of the batch in the nursery
@@ -769,11 +766,10 @@ struct Engine {
             if (!sub_dims.empty()) { c_subdims = dalloc<int>(sub_dims.size()); upload(c_subdims, sub_dims.data(), sizeof(int) * sub_dims.size()); }
         }
         S.nhat = dalloc<double>((size_t)B * nr * D); S.nhat_w = dalloc<double>((size_t)B * nr);
-        static const bool ms_off = std::getenv("PC_MS_PRE_OFF") != nullptr;
-        const bool ms_pre = S.like.kind == PC_LIKE_CORR_GAUSSIAN && D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !(S.ablate & 1) && !ms_off && S.prior.kind != PCHIP_PRIOR_TABLE;
+        const bool ms_pre = S.like.kind == PC_LIKE_CORR_GAUSSIAN && D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !(S.ablate & PC_ABL_FUNCTOR) && !pc_env().ms_pre_off && S.prior.kind != PCHIP_PRIOR_TABLE;
         S.nhat_Ms = ms_pre ? dalloc<double>((size_t)B * nr * D) : nullptr;
         S.ch_My = ms_pre ? dalloc<double>((size_t)B * D) : nullptr;
-        static const bool split_off = std::getenv("PC_NHATS_SPLIT_OFF") != nullptr;
+        const bool split_off = pc_env().nhats_split_off;
         // 64 < nDims <= 128, one grade: k_nhats_q<32, 1> leaves a basis register-major, 32 x 512 doubles
         const bool split_q = D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !split_off && !callback_mode;
         // 24 < nDims <= 64, one grade (round 5): k_nhats_q<8 / 16, 1> leaves a basis thread by thread, 16 HV^2 doubles
@@ -787,8 +783,7 @@ struct Engine {
         // (nDims <= 24: three -- the bases of nursery b + 2 are drawn under nursery b's contraction.  With two, nursery b + 1's were drawn
         //  there and k_slice(b + 1) waited for them across streams: kernel 39 us + ~10 us for the event to cross, a path as long as
         //  contraction + row copies + the host's look at the stamp, which is why enqueueing k_slice ahead changed nothing)
-        static const int depth_env = std::getenv("PC_RAW_DEPTH") ? std::max(2, std::min(RAW_RING, std::atoi(std::getenv("PC_RAW_DEPTH")))) : 3;
-        raw_depth = split_q ? RAW_RING : depth_env;
+        raw_depth = split_q ? RAW_RING : std::min((int)RAW_RING, pc_env().raw_depth);
         raw_buf[0] = S.nhat_raw;
         for (int r = 1; r < raw_depth; ++r) raw_buf[r] = ((D <= 24 || split_q || split_m) && S.nhat_raw) ? dalloc<double>(raw_n) : nullptr;
         S.plan = dalloc<PcPlan>(B); S.slot_src = dalloc<int>(Ncap); S.slot_step = dalloc<int>(Ncap); S.slot_dead = dalloc<int>(Ncap); HIPCHK(hipMemsetAsync(S.slot_dead, 0xFF, sizeof(int) * Ncap, st)); S.defer_update = 0; S.sort_slot = dalloc<int>(Ncap + 64); S.sort_key = dalloc<unsigned long long>(Ncap + 64);
@@ -916,7 +911,7 @@ struct Engine {
         if (batch_copies()) co->pre_copies.push_back({(uintptr_t)dst, (uintptr_t)h, (uintptr_t)bytes});
         else co->pre.push_back([dst, h, bytes, q] { HIPCHK(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, q)); });
     }
-    static bool batch_copies() { static const bool off = std::getenv("PC_COPY_BATCH_OFF") != nullptr; return !off; }
+    static bool batch_copies() { return !pc_env().copy_batch_off; }
 
     void read_ctl()
     {
@@ -938,7 +933,7 @@ struct Engine {
     // has the round's contraction kernel reported?  (non-blocking; a stream that finished without a stamp is an error)
     bool round_ready()
     {
-        static const bool off = std::getenv("PC_NOTIFY_OFF") != nullptr;
+        const bool off = pc_env().notify_off;
         if (off || !S.ctl_host) { read_ctl(); return true; }
         const volatile unsigned long long *w = (const volatile unsigned long long *)h_note;
         unsigned long long got[PC_NOTE_WORDS];
@@ -1243,22 +1238,21 @@ struct Engine {
         HIPCHK(hipMemcpy(&S.ctl->seq, &h_ctl->seq, sizeof(unsigned long long), hipMemcpyHostToDevice));
     }
 
+    // what a sampling launch of this run alone is counted under besides its kernel (live points, nurseries)
+    PcLaunchTraits launch_traits() const { return PcLaunchTraits{pc_rtc_wanted(&S) != 0, src_terms, S.prior.kind == PCHIP_PRIOR_TABLE}; }
+    PcUpdateFacts update_facts(int nph) const { return PcUpdateFacts{nph > 0, pc_update_fused_ok(&S, h_ctl->ncluster) != 0, h_ctl->ncluster}; }
+
     void do_update(bool deferred = false)
     {
         tm.updates += deferred ? std::max(1, h_ctl->upd_marks) : 1;
         // the round loop only sees the compact notification; whoever looks at evidences, counters or cluster ids gets the block
         const bool seq_post = S.seq_mode && (cfg.posteriors || cfg.equals);
-        // (clustering alone: the block comes with the counts below, in the same wait)
-        const bool ctl_late = cfg.do_clustering && !(dumper || on_update || cfg.resume_write || cfg.boost_posterior != 0.0 || seq_post);
-        if (!ctl_late && (dumper || on_update || cfg.do_clustering || cfg.resume_write || cfg.boost_posterior != 0.0 || seq_post)) { const int st_keep = h_ctl->status; read_ctl(); h_ctl->status = st_keep; }
-        // (the reference makes update_posteriors -- clean_phantoms with it -- BEFORE it writes files and calls the dumper,
-        //  nested_sampling.F90:325-336: when phantoms can join the posterior (boost_posterior) the hook waits for this update's)
-        const bool hook_late = cfg.boost_posterior != 0.0 && (cfg.posteriors || cfg.equals);
-        if (!hook_late) call_dumper();
+        if (plan.ctl == PC_CTL_EARLY) { const int st_keep = h_ctl->status; read_ctl(); h_ctl->status = st_keep; }
+        if (!plan.hook_late) call_dumper();
         const int nph = S.pool ? (int)pool_cursor : h_ctl->nphantom;
-        static const bool fused_off = std::getenv("PC_UPDATE_FUSED_OFF") != nullptr;
-        if (!fused_off && !(cfg.ablate & 8) && nph > 0 && !cfg.do_clustering && cfg.boost_posterior == 0.0 && pc_update_fused_ok(&S, h_ctl->ncluster)) {
-            // one cluster: clean + covariance + Cholesky in five launches (pc_update.hip; settings.ablate bit 16: as a chain of two)
+        const PcUpdateChoice upd = pc_choose_update(plan, update_facts(nph));
+        pc_count(path, upd);
+        if (upd.kind == PC_UPDATE_FUSED) {
             const size_t need = (size_t)pc_update_fused_blocks(&S, nph) * pc_update_fused_entries(&S);
             if (need > upd_part_cap) { dfree(upd_part); upd_part_cap = 2 * need; upd_part = dalloc<double>(upd_part_cap); }
             if (!upd_shift) {
@@ -1267,11 +1261,10 @@ struct Engine {
                 HIPCHK(hipMemcpyAsync(upd_shift, half.data(), sizeof(double) * S.D, hipMemcpyHostToDevice, st));
                 HIPCHK(hipStreamSynchronize(st));
             }
-            path[PCHIP_PATH_UPDATE_FUSED]++;
             hipEvent_t e0 = kt.begin(KT_CLEAN);
             (void)stage(rec_update(S, keep, blk, d_total, ph2, phL2, phC2, phU2, upd_part, upd_shift, co ? pc_update_fused_grid(&S, nph, deferred ? 1 : 0) : 0, deferred, nph));
             kt.end(KT_CLEAN, e0);
-            if (cfg.resume_write || dumper || on_update || seq_post) {
+            if (upd.need_count) {
                 // (in step with other runs the update was only written down: the copy of its count comes behind its launch)
                 std::vector<int> tot;
                 fetch(tot, (const int *)d_total, 1);
@@ -1285,19 +1278,17 @@ struct Engine {
             return;
         }
         if (deferred) engine_fail(PC_RC_DEVICE, "deferred update without the fused update path");
-        path[PCHIP_PATH_UPDATE_STEPS]++;
         hipEvent_t e0 = kt.begin(KT_CLEAN);
         // (in step with other runs: the clean of all runs that update in this round is one launch, like the pool compaction)
         // (... of no rows: nothing to write down, launched now behind what has been)
         if (co && nph <= 0) { direct_op(); pc_launch_clean(&S, nph, keep, blk, d_total, ph2, phL2, phC2, phU2, nullptr, st); }
         else (void)stage(rec_compact(S, keep, blk, d_total, ph2, phL2, phC2, phU2, nph));
         kt.end(KT_CLEAN, e0);
-        if (cfg.boost_posterior != 0.0 && (cfg.posteriors || cfg.equals)) collect_phantom_posteriors(nph);
-        if (hook_late) call_dumper();
+        if (plan.hook_late) { collect_phantom_posteriors(nph); call_dumper(); }
         // The surviving count is written to the control block on the device.  Without clustering / resume files
         // nothing on the host needs it before the next round's read-back, so the update costs no extra sync: the
         // covariance grid is sized with the pre-clean count and the kernels clamp to the device value.
-        const bool need_count = cfg.do_clustering || cfg.resume_write || dumper || on_update || cfg.boost_posterior != 0.0 || seq_post;
+        const bool need_count = upd.need_count, ctl_late = upd.ctl == PC_CTL_LATE;
         int total = nph;
         std::vector<int> tot, cn;
         if (need_count) {
@@ -1590,7 +1581,7 @@ struct Engine {
             for (int c = 0; c < nold; ++c)
                 if (cn[c] > 2) { desc.push_back(c); desc.push_back(cn[c]); desc.push_back((int)o2); desc.push_back(o1); which.push_back(c); o1 += cn[c]; o2 += (long long)cn[c] * cn[c]; }
             const int nd = (int)which.size();
-            static const bool batch_off = std::getenv("PC_CLUSTER_BATCH_OFF") != nullptr;
+            const bool batch_off = pc_env().cluster_batch_off;
             if (nd > 0 && !batch_off && o2 <= (long long)c_cap * c_cap) {
                 send_pre(c_desc, desc.data(), sizeof(int) * desc.size());
                 int nmax1 = 0;
@@ -1732,7 +1723,7 @@ struct Engine {
         ndiscarded = (long)attempt - nprior;
         cb_eval_seconds = attempt ? t_eval / attempt : -1.0;
         call_dumper(2);
-        if (nprior > cfg.nlive) { path[PCHIP_PATH_CONSUME_GENERAL]++; pc_launch_consume(&S, 2, 0, st); read_ctl(); }
+        if (nprior > cfg.nlive) { pc_count(path, PcTrimLive{}); pc_launch_consume(&S, 2, 0, st); read_ctl(); }
     }
 
     // one nursery batch in callback mode: tick the chains until all of them are done
@@ -1783,9 +1774,7 @@ struct Engine {
         long long nlike = 0;
         bool direct = true;
         while (have < nprior) {
-            if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
-            if (src_terms) path[PCHIP_PATH_SOURCE_TERMS]++;
-            if (S.prior.kind == PCHIP_PRIOR_TABLE) path[PCHIP_PATH_DEVICE_PRIOR]++;
+            pc_count(path, launch_traits());
             if (pc_launch_generate_live(&S, attempt0, nprior, rows, rl, st)) {
                 if (pc_rtc_wanted(&S) && pc_rtc_error()) engine_fail(PC_RC_SETTINGS, "%.480s", pc_rtc_error());
                 engine_fail(PC_RC_NDIMS, "nDims > 256 unsupported");
@@ -1815,9 +1804,7 @@ struct Engine {
             int a = last_attempt + 1;
             for (; S.ngrade <= 1; ++a) {
                 double l1 = 0.0;
-                if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
-                if (src_terms) path[PCHIP_PATH_SOURCE_TERMS]++;
-                if (S.prior.kind == PCHIP_PRIOR_TABLE) path[PCHIP_PATH_DEVICE_PRIOR]++;
+                pc_count(path, launch_traits());
                 (void)pc_launch_generate_live(&S, a, 1, rows, rl, st);
                 HIPCHK(hipMemcpyAsync(&l1, rl, sizeof(double), hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
@@ -1829,7 +1816,7 @@ struct Engine {
         dfree(rows); dfree(rl);
         call_dumper(2);                // write_prior_file, nested_sampling.F90:197
         if (nprior > cfg.nlive) {      // nested_sampling.F90:201-205
-            path[PCHIP_PATH_CONSUME_GENERAL]++; pc_launch_consume(&S, 2, 0, st);
+            pc_count(path, PcTrimLive{}); pc_launch_consume(&S, 2, 0, st);
             read_ctl();
         }
     }
@@ -2054,7 +2041,8 @@ struct Engine {
     std::unique_ptr<ActiveRun> active_run;
     using clk = std::chrono::steady_clock;
     clk::time_point r_t0, r_t1, r_t2;
-    unsigned r_batch = 0; bool r_sort_valid = false, r_fresh = false, r_par_ok = false, r_static_ok = false; int r_nursery_left = 0;
+    unsigned r_batch = 0; bool r_sort_valid = false, r_fresh = false; int r_nursery_left = 0;
+    PcRunPlan plan{};                             // which kernels this run may take: made once, at the end of begin() (pc_plan.h)
     int r_rc = 0;                                 // outcome of the loop: 0, or the code run() returns
 
     int run(pchip_result *out)
@@ -2085,7 +2073,7 @@ struct Engine {
                 resumed = true;
                 int ntot = 0;
                 for (int v : rs.nlive) ntot += v;
-                if (ntot > cfg.nlive && rs.ncluster == 1) { path[PCHIP_PATH_CONSUME_GENERAL]++; pc_launch_consume(&S, 2, 0, st); read_ctl(); ntot = cfg.nlive; }   // nested_sampling.F90:201-205
+                if (ntot > cfg.nlive && rs.ncluster == 1) { pc_count(path, PcTrimLive{}); pc_launch_consume(&S, 2, 0, st); read_ctl(); ntot = cfg.nlive; }   // nested_sampling.F90:201-205
                 resume_static = (ntot == cfg.nlive);
                 resume_batch0 = (unsigned)rs.ndead;
             }
@@ -2097,25 +2085,8 @@ struct Engine {
         r_batch = resume_batch0;                      // fresh counter-RNG streams after a resume
         r_sort_valid = false;
         r_nursery_left = 0;
-        const int nprior0 = cfg.nprior <= 0 ? cfg.nlive : cfg.nprior;
-        // the one-cluster kernels assume a static number of live points; each has its own LDS budget
-        const bool static_ok = (cfg.n_nlives == 0) && (nprior0 >= cfg.nlive) && resume_static && cfg.force_general != 1;
-        fast_ok = static_ok && pc_fast_fits(&S);
-        const bool par_ok = static_ok && cfg.force_general == 0 && pc_par_fits(&S);
-        r_static_ok = static_ok; r_par_ok = par_ok;
-        // The parallel contraction may run past an update trigger and have the update made afterwards, for the state at
-        // the trigger (pc_update.hip): a nursery is then consumed in ONE launch instead of being cut where the reference
-        // updates.  Only when nothing on the host is tied to the moment of an update (files, dumper, resume) and the
-        // fused update applies.
-        static const bool defer_off = std::getenv("PC_DEFER_OFF") != nullptr;
-        // (ablate bits 1, 2, 3: no pool mode, no deferred update, no fused update -- the same numbers by other kernels: tests/)
-        S.defer_update = (!defer_off && !(cfg.ablate & 4) && par_ok && !cfg.do_clustering && cfg.boost_posterior == 0.0 && !dumper && !on_update && !cfg.resume_write &&
-                          !S.seq_mode && pc_update_fused_ok(&S, 1) && !std::getenv("PC_UPDATE_FUSED_OFF") && !(cfg.ablate & 8)) ? 1 : 0;
-        // Pool mode (same conditions, likelihood on the device): k_slice writes a nursery's babies into the phantom array itself,
-        // updates invalidate phantoms where they lie, and the array is compacted only when it is full -- the rows of a run
-        // are written once and read once (pc_state.h).  The host keeps the cursor: nothing it does not know moves it.
-        static const bool pool_off = std::getenv("PC_POOL_OFF") != nullptr;
-        S.pool = (S.defer_update && !callback_mode && !pool_off && !(cfg.ablate & 2)) ? 1 : 0;
+        make_plan();
+        S.defer_update = plan.defer ? 1 : 0; S.pool = plan.pool ? 1 : 0;
         if (S.pool) {
             pool_cursor = h_ctl->nphantom;
             babies_own = S.babies;
@@ -2130,14 +2101,44 @@ struct Engine {
         return -1;
     }
 
+    // the run's plan: the launchers' predicates whose inputs are fixed from here on are asked here
+    void make_plan()
+    {
+        const int nprior0 = cfg.nprior <= 0 ? cfg.nlive : cfg.nprior;
+        PcRunFacts f{};
+        f.ablate = cfg.ablate; f.force_general = cfg.force_general;
+        f.fixed_nlive = (cfg.n_nlives == 0) && (nprior0 >= cfg.nlive) && resume_static;
+        f.par_fits = pc_par_fits(&S) != 0; f.fast_fits = pc_fast_fits(&S) != 0; f.fused_fits_one = pc_update_fused_ok(&S, 1) != 0;
+        f.clustering = cfg.do_clustering != 0; f.boost = cfg.boost_posterior != 0.0;
+        f.dumper = dumper != nullptr; f.on_update = on_update != nullptr; f.resume_write = cfg.resume_write != nullptr;
+        f.seq_mode = S.seq_mode != 0; f.posteriors = cfg.posteriors || cfg.equals;
+        f.callback = callback_mode;
+        plan = pc_plan_run(f);
+    }
+    // another run is at work on this device, in step with this one or not
+    bool other_active() const { return g_active_dev[dev & 63].load(std::memory_order_relaxed) > 1; }
     // what the cohort's launches for any device likelihood take (else the run launches for itself in between)
     bool cohort_general_ok() const
     {
-        static const bool off = std::getenv("PC_COHORT_GENERAL") && std::atoi(std::getenv("PC_COHORT_GENERAL")) == 0;
-        return !off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK && S.prior.kind != PCHIP_PRIOR_TABLE;
+        return !pc_env().cohort_general_off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK && S.prior.kind != PCHIP_PRIOR_TABLE;
+    }
+    // what is known when a nursery is about to be sampled (the launchers' predicates: asked here, once a nursery)
+    PcNurseryFacts nursery_facts(unsigned batch) const
+    {
+        PcNurseryFacts f{};
+        f.in_step = co != nullptr; f.other_active = other_active(); f.callback = callback_mode; f.D = S.D;
+        f.ring = raw_buf[1] != nullptr;
+        const RawSlot &rs = ring[batch % raw_depth];
+        f.slot_ready = rs.valid && rs.batch == batch && rs.B == B;
+        f.second_stream = co && co->st2 && raw_depth >= 2;
+        f.splittable = pc_nhats_splittable(&S) != 0; f.fusable = pc_slice_fusable(&S) != 0; f.bases_t = pc_bases_t_ok(&S) != 0;
+        f.slice_t = pc_slice_t_ok(&S, h_ctl->ncluster) != 0;
+        f.cohort_general = cohort_general_ok();
+        f.traits = launch_traits();
+        return f;
     }
     // The sampling of one nursery: pool rows, the bases (drawn ahead on the side stream, or now), k_slice, the bases of the
-    // nurseries to come.
+    // nurseries to come.  Which of them: pc_choose_nursery.
     bool enqueue_nursery()
     {
         unsigned &batch = r_batch; int &nursery_left = r_nursery_left;
@@ -2150,67 +2151,53 @@ struct Engine {
             // (between the stamp of the last round and the launch of k_slice the device idles: nothing that can wait
             //  is done in between -- capacity checks precede the contraction, not the sampling)
             hipEvent_t e0 = kt.begin(KT_NHATS);
-            // (a run that has the chip to itself: next to other runs the side stream takes from them what it gives)
-            // (next to other runs of this device the bases are drawn in line, in front of the sampling kernel: their side streams
-            //  would take from each other what they give -- but the split itself, and with it the fused sampling kernel, stays)
-            const bool multi = co != nullptr || g_active_dev[dev & 63].load(std::memory_order_relaxed) > 1;
-            // (nDims 25 ... 64: the halves for a run on its own; runs in step take the whole kernel with the run in the grid, CK_NHATS_G)
-            const bool splittable = pc_nhats_splittable(&S) != 0 && raw_buf[1] && !(S.D > 24 && S.D <= 64 && multi);
-            const bool split = splittable && !multi;
-            bool fused_slice = false;
+            const PcNurseryChoice ch = pc_choose_nursery(plan, nursery_facts(batch));
+            pc_count(path, ch);
             int bases_seq = 0;                        // in step with other runs: the number of the launch that drew this nursery's bases (0: in line)
-            if (splittable) {
-                // the bases of this nursery were drawn on the side stream while earlier ones were sampled and consumed (or
-                // are drawn now)
+            switch (ch.bases) {
+            case PC_BASES_READY: case PC_BASES_PART1: case PC_BASES_PART1_STEP: {
                 RawSlot &rs = ring[batch % raw_depth];
                 S.nhat_raw = raw_buf[batch % raw_depth];
-                if (rs.valid && rs.batch == batch && rs.B == B) { if (!rs.waited) HIPCHK(hipStreamWaitEvent(st, rs.ready, 0)); bases_seq = rs.co_seq; }      // (in step with other runs: the wait for the launch that drew them, Cohort::flush)
+                if (ch.bases == PC_BASES_READY) { if (!rs.waited) HIPCHK(hipStreamWaitEvent(st, rs.ready, 0)); bases_seq = rs.co_seq; }      // (in step with other runs: the wait for the launch that drew them, Cohort::flush)
                 else {
                     if (rs.valid) HIPCHK(hipStreamWaitEvent(st, rs.ready, 0));       // (a stale job may still be writing there)
-                    // (not stage(): a run on its own passes its packed flag from `multi` and settings.ablate bit 7, the row's one-run launch 1)
-                    if (co && pc_bases_t_ok(&S)) co->rec(rec_bases(S, batch, B));
-                    else (void)pc_launch_nhats_part(&S, batch, B, 1, st, (multi || (cfg.ablate & 128)) ? 1 : 0);
+                    // (not stage(): a run on its own passes its packed flag, the row's one-run launch 1)
+                    if (ch.bases == PC_BASES_PART1_STEP) co->rec(rec_bases(S, batch, B));
+                    else (void)pc_launch_nhats_part(&S, batch, B, 1, st, ch.packed ? 1 : 0);
                 }
                 rs.valid = false;
-                fused_slice = !callback_mode && pc_slice_fusable(&S) != 0;       // seeds + whitening inside k_slice
-                if (!fused_slice) { if (co) { co->flush(); co->wait_next(); } (void)pc_launch_nhats_part(&S, batch, B, 2, st, 0); }
+                if (ch.part2) { if (co) { co->flush(); co->wait_next(); } (void)pc_launch_nhats_part(&S, batch, B, 2, st, 0); }
+                break;
             }
             // (not stage(): CK_NHATS_G exists in step only, a run on its own reports a failing launch)
-            else if (co && !callback_mode && cohort_general_ok() && S.D >= 25 && S.D <= 64) co->rec(rec_nhats_g(S, batch, B));
-            else if ((co ? (co->flush(), 0) : 0) || pc_launch_nhats(&S, batch, B, st)) { std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false; }
+            case PC_BASES_NHATS_G: co->rec(rec_nhats_g(S, batch, B)); break;
+            case PC_BASES_WHOLE:
+                if (co) co->flush();
+                if (pc_launch_nhats(&S, batch, B, st)) { std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false; }
+                break;
+            }
             kt.end(KT_NHATS, e0);
             hipEvent_t e1 = kt.begin(KT_SLICE);
-            if (callback_mode) { if (co) co->flush(); slice_callback(batch); if (stop.load(std::memory_order_relaxed)) { r_rc = 5; return false; } }
-            // next to other runs of this device (or settings.ablate bit 6): the lane = chain kernel (pc_slice_t.hip), the same
-            // numbers from 1/60 of the wavefronts
-            else if (fused_slice && (multi || (cfg.ablate & 64)) && pc_slice_t_ok(&S, h_ctl->ncluster)) {
-                path[PCHIP_PATH_SLICE_LANE]++;
-                (void)stage(rec_slice(S, batch, B, bases_seq));
-                // in step with other runs: the bases of the next nursery on the runs' second stream, next to this round's kernels
-                if (co && co->st2 && splittable && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
-            }
-            else if (co && !callback_mode && cohort_general_ok() && (fused_slice || !splittable)) {
-                // in step with other runs, any device likelihood / several clusters: the one-run kernel with the run in the grid
-                path[PCHIP_PATH_SLICE_WAVE]++;
-                if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
-                // (not stage(): no run on its own comes here -- its launch is the branch below, which counts other paths and reports a failure)
-                co->rec(rec_slice_g(S, batch, B, fused_slice, fused_slice ? bases_seq : 0));
-                if (fused_slice && co->st2 && raw_depth >= 2 && pc_bases_t_ok(&S)) bases_ahead(batch);
-            }
-            else {
-                // a launch of this run alone: lane = coordinate
-                path[PCHIP_PATH_SLICE_WAVE]++;
-                if (pc_rtc_wanted(&S)) path[PCHIP_PATH_SOURCE_KERNELS]++;
-                if (src_terms) path[PCHIP_PATH_SOURCE_TERMS]++;
-                if (S.prior.kind == PCHIP_PRIOR_TABLE) path[PCHIP_PATH_DEVICE_PRIOR]++;
+            switch (ch.sampler) {
+            case PC_SAMPLER_CALLBACK:
+                if (co) co->flush();
+                slice_callback(batch);
+                if (stop.load(std::memory_order_relaxed)) { r_rc = 5; return false; }
+                break;
+            case PC_SAMPLER_LANE: (void)stage(rec_slice(S, batch, B, bases_seq)); break;
+            // (not stage(): no run on its own comes here -- its launch is the case below, which counts other paths and reports a failure)
+            case PC_SAMPLER_WAVE_STEP: co->rec(rec_slice_g(S, batch, B, ch.fused, ch.fused ? bases_seq : 0)); break;
+            case PC_SAMPLER_WAVE:
                 if (co) { co->flush(); co->wait_next(); }
-                if (fused_slice ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st)) {
+                if (ch.fused ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st)) {
                     if (pc_rtc_wanted(&S) && pc_rtc_error()) { std::fprintf(stderr, "polychord_hip: %s\n", pc_rtc_error()); r_rc = 1; return false; }
                     std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false;
                 }
+                break;
             }
+            if (ch.ahead == PC_AHEAD_STEP) bases_ahead(batch);
             kt.end(KT_SLICE, e1);
-            if (split) side_prefetch(batch);
+            if (ch.ahead == PC_AHEAD_SIDE) side_prefetch(batch);
             if (S.ngrade > 1) HIPCHK(hipMemcpyAsync(h_nlike_g.data(), S.ch_nlike_g, sizeof(int) * h_nlike_g.size(), hipMemcpyDeviceToHost, st));
             batch++; tm.batches++;
             S.nn_valid = 0; nursery_left = B;
@@ -2243,9 +2230,8 @@ struct Engine {
     bool presorted = false;
     void presort_live()
     {
-        static const bool off = std::getenv("PC_PRESORT_OFF") != nullptr;
         presorted = false;
-        if (off || co || callback_mode || S.seq_mode || !S.nn_list || h_ctl->ncluster < 2 || g_active_dev[dev & 63].load(std::memory_order_relaxed) != 1) return;
+        if (pc_env().presort_off || co || other_active() || callback_mode || S.seq_mode || !S.nn_list || h_ctl->ncluster < 2) return;
         ensure_side();
         if (!ev_presort_a) { ev_presort_a = hpool().get_sync_event(); ev_presort_b = hpool().get_sync_event(); }
         HIPCHK(hipEventRecord(ev_presort_a, st)); HIPCHK(hipStreamWaitEvent(st_side, ev_presort_a, 0));      // (behind the row copies of the round before)
@@ -2263,8 +2249,7 @@ struct Engine {
         ensure_side();
         // (nDims > 64: the bases take longer than the contraction and the slice kernel is one wave per SIMD for
         //  half a millisecond: there they run next to it from the start)
-        static const bool side_free_env = std::getenv("PC_SIDE_FREE") != nullptr, side_ord_env = std::getenv("PC_SIDE_ORDERED") != nullptr;
-        const bool side_free = side_free_env || (S.D > 64 && !side_ord_env);
+        const bool side_free = pc_env().side_free || (S.D > 64 && !pc_env().side_ordered);
         // the buffer of this nursery is free again once its bases have been whitened (fused: once sampled)
         // (ordered: the side stream follows k_slice anyway -- one event between k_slice and the contraction, not two:
         //  every record on the main stream is a few microseconds before the next kernel starts)
@@ -2280,7 +2265,7 @@ struct Engine {
             if (rs.used) HIPCHK(hipStreamWaitEvent(st_side, rs.consumed, 0));
             PcState S1 = S; S1.nhat_raw = raw_buf[x % raw_depth];
             hipEvent_t es = kt.begin_on(KT_SIDE, st_side);
-            (void)pc_launch_nhats_part(&S1, x, B, 1, st_side, (cfg.ablate & 128) ? 1 : 0);
+            (void)pc_launch_nhats_part(&S1, x, B, 1, st_side, (cfg.ablate & PC_ABL_BASES_PACKED) ? 1 : 0);
             kt.end_on(KT_SIDE, es, st_side);
             HIPCHK(hipEventRecord(rs.ready, st_side));
             rs.valid = true; rs.batch = x; rs.B = B; rs.waited = false;
@@ -2288,11 +2273,21 @@ struct Engine {
     }
     }
 
+    // what is known when a round's contraction is about to be launched
+    PcContractFacts contract_facts(int nursery_left) const
+    {
+        PcContractFacts f{};
+        f.ncluster = h_ctl->ncluster; f.nursery_left = nursery_left;
+        f.in_step = co != nullptr; f.cohort_general = cohort_general_ok();
+        f.nn_lists = S.nn_list && !pc_env().nn_lists_off; f.nn_valid = S.nn_valid != 0;
+        f.cl_fits = f.ncluster > 1 && pc_consume_cl_fits(&S, f.ncluster) != 0;
+        f.clp_fits = f.cl_fits && pc_consume_clp_fits(&S, f.ncluster) != 0;
+        return f;
+    }
     // enqueue one round (sampling when the nursery is empty, contraction, row copies); false: the loop is over (r_rc says how)
     bool round_enqueue()
     {
         unsigned &batch = r_batch; bool &sort_valid = r_sort_valid; int &nursery_left = r_nursery_left;
-        const bool par_ok = r_par_ok, static_ok = r_static_ok; const int wide = 0;
         {
             if (h_ctl->status == PC_ST_DONE) return false;
             if (h_ctl->status == PC_ST_ERROR) { std::fprintf(stderr, "polychord_hip: device error %d\n", h_ctl->error); r_rc = 2; return false; }
@@ -2300,59 +2295,50 @@ struct Engine {
             if (h_ctl->i_nursery == 0) {
                 fresh_nursery = true;
                 DbgSpan dbg_t{g_dbg_nursery_ns};
-                if (r_static_ok && cfg.force_general == 0 && !(cfg.ablate & 32)) presort_live();
+                if (plan.cl_ok) presort_live();
                 if (!enqueue_nursery()) return false;
             }
             if (fresh_nursery) { DbgSpan dbg_t{g_dbg_capacity_ns}; ensure_capacity(); }
             hipEvent_t e2 = kt.begin(KT_CONSUME);
-            int rc2;
-            const bool use_fast = fast_ok && h_ctl->ncluster == 1;
+            int rc2 = 0;
+            const PcContractChoice ch = pc_choose_contract(plan, contract_facts(nursery_left));
+            pc_count(path, ch);
             launch_stamp();
-            if (presorted && (co || !(h_ctl->ncluster > 1) || use_fast)) { HIPCHK(hipStreamWaitEvent(st, ev_presort_b, 0)); presorted = false; }
-            if (par_ok && h_ctl->ncluster == 1) {
-                // the parallel contraction keeps the sorted order of the live set up to date itself
-                rc2 = 0; S.nn_valid = 0;                     // (the one-cluster kernels do not keep the list bookkeeping)
-                path[PCHIP_PATH_CONSUME_PAR]++;
+            if (presorted && (co || !(h_ctl->ncluster > 1))) { HIPCHK(hipStreamWaitEvent(st, ev_presort_b, 0)); presorted = false; }
+            switch (ch.kind) {
+            case PC_CONTRACT_PAR:
+                S.nn_valid = 0;                              // (the one-cluster kernels do not keep the list bookkeeping)
                 if (!sort_valid) { rc2 = stage(rec_sort(S)); sort_valid = true; }
                 rc2 = rc2 || stage(rec_consume(S));      // also lays out the phantoms
-            }
-            else if (use_fast) { if (co) co->flush(); sort_valid = false; S.nn_valid = 0; path[PCHIP_PATH_CONSUME_FAST]++; rc2 = pc_launch_consume_fast(&S, 0, st); pc_launch_ph_prepare(&S, st); }
-            else {
+                break;
+            case PC_CONTRACT_FAST:
+                if (co) co->flush();
+                sort_valid = false; S.nn_valid = 0;
+                rc2 = pc_launch_consume_fast(&S, 0, st); pc_launch_ph_prepare(&S, st);
+                break;
+            case PC_CONTRACT_CL_STEP:
+                // (not stage(), the three of them: a run on its own passes the lists whether the sort was made now and the contraction the
+                //  number of clusters, the rows' one-run launches 1 and 65 or 2)
                 sort_valid = false;
-                // several clusters: rank the possible nearest neighbours of every baby still in the nursery once, on
-                // the whole chip; the serial contraction then walks short lists instead of searching the live set
-                static const bool nn_off = std::getenv("PC_NN_LISTS_OFF") != nullptr;
-                const bool want_nn = h_ctl->ncluster > 1 && S.nn_list && !S.nn_valid && !nn_off && !S.seq_mode && nursery_left > 1;
-                // several clusters, static number of live points, lists in place: the one-wave contraction (pc_clus.hip); everything
-                // else -- and every launch when settings.ablate bit 5 is set -- goes to the general kernel, which is its arbiter
-                static const bool cl_off = std::getenv("PC_CONSUME_CL_OFF") != nullptr;
-                const bool use_cl = static_ok && cfg.force_general == 0 && !cl_off && !(cfg.ablate & 32) && (S.nn_valid || want_nn) && !S.seq_mode && h_ctl->ncluster > 1 &&
-                                    pc_consume_cl_fits(&S, h_ctl->ncluster);
-                if (co && use_cl && cohort_general_ok()) {
-                    // in step with other runs: lists, sort and the one-wave contraction once for all runs with several clusters
-                    // (not stage(), the three of them: a run on its own passes the lists whether the sort was made now and the contraction the
-                    //  number of clusters, the rows' one-run launches 1 and 65 or 2)
-                    if (want_nn) { co->rec(rec_nn(S, nursery_left)); S.nn_valid = 1; path[PCHIP_PATH_NN_LISTS]++; }
-                    path[pc_consume_clp_fits(&S, h_ctl->ncluster) ? PCHIP_PATH_CONSUME_CL : PCHIP_PATH_CONSUME_CL_SERIAL]++;
-                    co->rec(rec_sort(S));
-                    co->rec(rec_consume_cl(S, h_ctl->ncluster > 64));
-                    rc2 = 0;
-                } else {
+                if (ch.want_nn) { co->rec(rec_nn(S, nursery_left)); S.nn_valid = 1; }
+                co->rec(rec_sort(S));
+                co->rec(rec_consume_cl(S, h_ctl->ncluster > 64));
+                break;
+            case PC_CONTRACT_CL: case PC_CONTRACT_GENERAL: {
+                sort_valid = false;
                 if (co) co->flush();
                 bool sorted_now = false;
                 if (presorted) { HIPCHK(hipStreamWaitEvent(st, ev_presort_b, 0)); sorted_now = fresh_nursery; presorted = false; }      // (made beside k_slice: presort_live)
-                if (want_nn) {
+                if (ch.want_nn) {
                     // (the sorted order first: its ranks tell the lists' kernel which candidates cannot die before a chain is looked at)
                     if (!sorted_now) sorted_now = pc_launch_sort_live(&S, st) == 0;
                     pc_launch_nn_lists(&S, nursery_left, sorted_now ? 1 : 0, st);
-                    S.nn_valid = 1; path[PCHIP_PATH_NN_LISTS]++;
+                    S.nn_valid = 1;
                 }
-                path[use_cl ? (pc_consume_clp_fits(&S, h_ctl->ncluster) ? PCHIP_PATH_CONSUME_CL : PCHIP_PATH_CONSUME_CL_SERIAL) : PCHIP_PATH_CONSUME_GENERAL]++;
-                if (use_cl) {
-                    rc2 = (sorted_now ? 0 : pc_launch_sort_live(&S, st)) || pc_launch_consume_cl(&S, h_ctl->ncluster, st);
-                } else
-                rc2 = pc_launch_consume(&S, 0, (h_ctl->ncluster > 1) ? 1 : wide, st);
-                }
+                if (ch.kind == PC_CONTRACT_CL) rc2 = (sorted_now ? 0 : pc_launch_sort_live(&S, st)) || pc_launch_consume_cl(&S, h_ctl->ncluster, st);
+                else rc2 = pc_launch_consume(&S, 0, (h_ctl->ncluster > 1) ? 1 : 0, st);
+                break;
+            }
             }
             if (rc2) { std::fprintf(stderr, "polychord_hip: nlive too large for the LDS-resident contraction\n"); r_rc = 4; return false; }
             kt.end(KT_CONSUME, e2);
@@ -2372,8 +2358,7 @@ struct Engine {
     bool finish_may_wait() const
     {
         const bool upd = h_ctl->status == PC_ST_UPDATE || (h_ctl->upd_pending && h_ctl->status == PC_ST_RUNNING);
-        return upd && (cfg.do_clustering || dumper || on_update || cfg.resume_write || cfg.boost_posterior != 0.0 || S.seq_mode || h_ctl->ncluster > 1 ||
-                       !pc_update_fused_ok(&S, h_ctl->ncluster));
+        return upd && pc_choose_update(plan, update_facts(1)).may_wait;
     }
     // what the round did, once its stamp is in; false: the loop is over
     bool round_finish()
@@ -2418,11 +2403,10 @@ struct Engine {
     void end_a(bool fused_final = false)
     {
         if (co && !fused_final) co->flush();      // (fused: the caller has launched what was pending, and launches the kill-offs together)
-        const bool par_ok = r_par_ok; bool &sort_valid = r_sort_valid;
+        bool &sort_valid = r_sort_valid;
         es.t2 = clk::now();
         st_fin = st;
-        static const bool fin_off = std::getenv("PC_COHORT_FINAL_ASIDE") && std::atoi(std::getenv("PC_COHORT_FINAL_ASIDE")) == 0;
-        if (co && fused_final && !fin_off && st_copy && st_copy != st && h_ctl->ncluster > 1) {
+        if (co && fused_final && !pc_env().cohort_final_aside_off && st_copy && st_copy != st && h_ctl->ncluster > 1) {
             ev_fin = hpool().get_sync_event();
             HIPCHK(hipEventRecord(ev_fin, st));
             HIPCHK(hipStreamWaitEvent(st_copy, ev_fin, 0));
@@ -2438,7 +2422,7 @@ struct Engine {
         es.nc_end = h_ctl->ncluster;
         if (h_ctl->ncluster == 0) {
             // a finished run read back from its .resume file: nothing to kill
-        } else if (par_ok && h_ctl->ncluster == 1) {
+        } else if (plan.par_ok && h_ctl->ncluster == 1) {
             path[PCHIP_PATH_KILLOFF_PAR]++;
             if (co && sort_valid) { co->rec(rec_final(S)); if (!fused_final) co->flush(); }      // (fused: the caller launches the kill-off of all runs that end now, then calls end_a2)
             else {
@@ -2447,7 +2431,7 @@ struct Engine {
             }
         } else if (h_ctl->ncluster > 1 && pc_launch_killoff_cl(&S, h_ctl->ncluster, st) == 0) {      // (several clusters: the deaths in sorted order by one wavefront, pc_clus.hip)
             path[PCHIP_PATH_KILLOFF_CL]++;
-        } else if (fast_ok && h_ctl->ncluster == 1 && pc_launch_consume_fast(&S, 1, st) == 0) path[PCHIP_PATH_KILLOFF_FAST]++;
+        } else if (plan.fast_ok && h_ctl->ncluster == 1 && pc_launch_consume_fast(&S, 1, st) == 0) path[PCHIP_PATH_KILLOFF_FAST]++;
         else { path[PCHIP_PATH_KILLOFF_GENERAL]++; pc_launch_consume(&S, 1, (h_ctl->ncluster > 1 && !S.seq_mode) ? 1 : 0, st); }   // (the general kernel: four waves, a death's jobs side by side)
         if (!fused_final) end_a2();
     }
@@ -2509,7 +2493,7 @@ struct Engine {
         out->t_generate = tm.t_gen; out->t_loop = tm.t_loop; out->t_final = tm.t_final; out->t_total = tm.t_total;
         for (int k = 0; k < KT_N; ++k) { out->k_time_s[k] = kt.total_ms[k] * 1e-3; out->k_launches[k] = kt.launches[k]; }
         // developer counters (PC_DEBUG=2|3|4); the feedback setting keeps the reference's meaning (feedback.f90)
-        static const int dbg_lvl = std::getenv("PC_DEBUG") ? std::atoi(std::getenv("PC_DEBUG")) : 0;
+        const int dbg_lvl = pc_env().debug;
         if (dbg_lvl >= 3) std::fprintf(stderr, "polychord_hip dbg general: term %lld identify %lld kill+add %lld tail %lld cycles; %lld chains identified from the candidate lists, %lld of them fell back to the full search\n", h_ctl->gen_cyc[0], h_ctl->gen_cyc[1], h_ctl->gen_cyc[2], h_ctl->gen_cyc[3], h_ctl->nn_walks, h_ctl->nn_fallbacks);
         if (dbg_lvl == 4) std::fprintf(stderr, "polychord_hip dbg par: stage+search %lld rank-sort %lld accept %lld merge+slots %lld evidence %lld triggers %lld publish %lld cycles\n", h_ctl->dbg[0], h_ctl->dbg[1], h_ctl->dbg[2], h_ctl->dbg[3], h_ctl->dbg[4], h_ctl->dbg[5], h_ctl->dbg[6]);
         if (dbg_lvl == 4) std::fprintf(stderr, "polychord_hip dbg par: %lld evidence scans as pairs (terms beyond one scale)\n", h_ctl->dbg[7]);
@@ -2731,7 +2715,7 @@ int pchip_run_hooks(const pchip_settings *s, const pchip_like *like, const pchip
 int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds, int device,
                 int max_in_flight, pchip_result *results)
 {
-    static const bool prof = std::getenv("PC_DEBUG") && std::atoi(std::getenv("PC_DEBUG")) == 5;
+    const bool prof = pc_env().debug == 5;
     for (int k = 0; k < nseeds; ++k) std::memset(&results[k], 0, sizeof(pchip_result));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return PC_RC_DEVICE; }
@@ -2743,7 +2727,7 @@ int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_pri
         int n = std::min(W, nseeds - base);
         const auto Tpre = std::chrono::steady_clock::now();
         Cohort co;
-        static const bool side_off = std::getenv("PC_COHORT_SIDE") && std::atoi(std::getenv("PC_COHORT_SIDE")) == 0;
+        const bool side_off = pc_env().cohort_side_off;
         // (a main stream whose hardware queue is known already, if the pool has one: the side stream is then picked without a test --
         //  a test is a millisecond, several once PyTorch lives in the process, and the pool's first stream was a different one of
         //  the engines' copy streams at every call)
@@ -2780,13 +2764,13 @@ int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_pri
             if (prof) std::fprintf(stderr, "polychord_hip dbg cohort: main stream %.2f ms, side stream %.2f ms\n", std::chrono::duration<double>(Tp1 - Tpre).count() * 1e3, std::chrono::duration<double>(std::chrono::steady_clock::now() - Tp1).count() * 1e3);
         }
         if (co.st2) { co.ev_up = hpool().get_sync_event(); co.ev_next = hpool().get_sync_event(); }
-        static const bool stc_off = std::getenv("PC_COHORT_COPY_STREAMS") && std::atoi(std::getenv("PC_COHORT_COPY_STREAMS")) == 0;
+        const bool stc_off = pc_env().cohort_copy_streams_off;
         if (!stc_off) { co.stc[0] = stream_beside({co.st, co.st2}, cohort_loaded); co.stc[1] = stream_beside({co.st, co.st2, co.stc[0]}, cohort_loaded); }
         std::vector<Engine *> E((size_t)n, nullptr);
         std::vector<char> live((size_t)n, 0), enq((size_t)n, 0);
         const auto T0 = std::chrono::steady_clock::now();
         long rounds = 0; double t_begin = 0, t_end = 0, t_wait = 0, t_enq = 0, t_fin = 0, t_fl = 0, t_comp = 0, t_end_dev = 0, t_fwait = 0; long n_fwait = 0;
-        static const bool fibers_on = !(std::getenv("PC_COHORT_FIBERS") && std::atoi(std::getenv("PC_COHORT_FIBERS")) == 0);
+        const bool fibers_on = !pc_env().cohort_fibers_off;
         std::vector<Fiber> fibs;
         int *h_totals = nullptr; size_t totals_cap = 0;
         double t_setup_max = 0; int n_comp_pass = 0;
@@ -2819,7 +2803,7 @@ int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_pri
                 };
                 const auto b0 = nowc();
                 setup_one(0);
-                static const int setup_threads = std::getenv("PC_COHORT_SETUP_THREADS") ? std::max(1, std::atoi(std::getenv("PC_COHORT_SETUP_THREADS"))) : 1;
+                const int setup_threads = pc_env().cohort_setup_threads;
                 if (n > 1 && !failed) {
                     std::atomic<int> nextk{1};
                     auto worker = [&] { (void)hipSetDevice(devnow); for (int k; !failed && (k = nextk.fetch_add(1)) < n;) setup_one(k); };
@@ -3028,7 +3012,7 @@ int pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const pc
                        int nchains, const double *seeds, const double *chol, double contour, double *babies_out,
                        double *nhats_out, int *nlike_out)
 {
-    if (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & (1 << 15))) {
+    if (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & PC_ABL_RTC_BUILTINS)) {
         std::fprintf(stderr, "polychord_hip: pchip_slice_chains does not take a device source likelihood (or settings.ablate bit 15)\n");
         return 1;
     }

@@ -765,7 +765,7 @@ int pchip_run_repeats_ex(const pchip_settings *s, const pchip_like *like, const 
 {
     using clk = std::chrono::steady_clock;
     if (nseeds < 1) return 1;
-    if (like && (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & (1 << 15)))) {
+    if (like && (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & PC_ABL_RTC_BUILTINS))) {
         // (the runs in step would take k_slice_many from the run-time module: not yet pinned to the solo runs)
         std::fprintf(stderr, "polychord_hip: pchip_run_repeats does not take a device source likelihood (or settings.ablate bit 15) yet: run the seeds one by one with pchip_run\n");
         return 1;

@@ -486,7 +486,7 @@ __device__ __forceinline__ void consume_par_body(const PcState &S)
         lsM = fmax(Ladd, L); lsS = (dl <= 0.0) ? 1.0 - e : e - 1.0;
     }
     __shared__ double lsc[4 * PAR_W];
-    const bool lin_on = !(S.ablate & 16);             // (bit 4: pair scans only -- tests compare the two paths on the same run)
+    const bool lin_on = !(S.ablate & PC_ABL_PAIR_SCANS);             // (bit 4: pair scans only -- tests compare the two paths on the same run)
     __shared__ double ucv[4], uexp[4];
     __shared__ int ucq[4];
     bool lin1 = false;

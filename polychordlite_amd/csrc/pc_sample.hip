@@ -1656,7 +1656,7 @@ __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB) void k_slice_many(const PcM
 // The sampling kernels of a source likelihood (PC_LIKE_SOURCE), and of every kind under settings.ablate bit 15, come from a module that
 // pc_rtc.hip compiles at run time from this very text: the launchers below choose the variant and its launch shape once, PC_LAUNCH sends
 // it to the static kernel or, by its name, to the module's.
-extern "C" int pc_rtc_wanted(const PcState *S) { return S->like.kind == PC_LIKE_SOURCE || (S->ablate & (1 << 15)) != 0; }
+extern "C" int pc_rtc_wanted(const PcState *S) { return S->like.kind == PC_LIKE_SOURCE || (S->ablate & PC_ABL_RTC_BUILTINS) != 0; }
 template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, dim3 g, dim3 b, size_t sh, hipStream_t st, A... a)
 {
     void *args[] = { (void *)&a... };
@@ -1835,16 +1835,16 @@ static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R
     // keyed draws, the box (a prior table: the general variants); runs in step take the Gaussian functor as the general kernel
     int leanf = 0;
     if (!lean_off && !special && !table)
-        leanf = S->like.kind == PC_LIKE_RASTRIGIN ? 3 : (S->like.kind == PC_LIKE_TWIN_GAUSSIAN ? 4 : ((S->like.kind == PC_LIKE_GAUSSIAN && (S->ablate & 1) && !R) ? 5 : 0));
+        leanf = S->like.kind == PC_LIKE_RASTRIGIN ? 3 : (S->like.kind == PC_LIKE_TWIN_GAUSSIAN ? 4 : ((S->like.kind == PC_LIKE_GAUSSIAN && (S->ablate & PC_ABL_FUNCTOR) && !R) ? 5 : 0));
     if (fused) {
         // LEAN = 1: the Gaussian in closed form along the chord, its deck in registers (one-run launches)
-        const bool lean = !R && !lean_off && !table && S->like.kind == PC_LIKE_GAUSSIAN && !(S->ablate & 1) && p.phi_lds && nr <= 64 && !special;
+        const bool lean = !R && !lean_off && !table && S->like.kind == PC_LIKE_GAUSSIAN && !(S->ablate & PC_ABL_FUNCTOR) && p.phi_lds && nr <= 64 && !special;
         p.lean = leanf ? leanf : (lean ? 1 : 0);
         // four chains a workgroup with their four helper wavefronts (pc_slice_body.inc): the lean variants whose deck lives in registers (1, 3, 5),
         // nurseries of a multiple of four chains; settings.ablate bit 13 / PC_SLICE_HELPER_OFF: one wavefront a workgroup as before (the same numbers)
         const size_t pw4 = ((size_t)D + nr + (p.phi_lds ? (size_t)nr * (D + 1) : 0) + (size_t)p.fw * D + (size_t)nr * (D + 2) + (size_t)((nr + 3) / 4) * 128 + (size_t)nr + 1) & ~(size_t)1;
         const size_t sh4 = 4 * sizeof(double) * pw4 + 16;
-        if (!R && (p.lean == 1 || p.lean == 3 || p.lean == 5) && !helper_off && !(S->ablate & 8192) && nr <= 64 && (nchains & 3) == 0 && sh4 <= 150 * 1024) {
+        if (!R && (p.lean == 1 || p.lean == 3 || p.lean == 5) && !helper_off && !(S->ablate & PC_ABL_NO_HELPER) && nr <= 64 && (nchains & 3) == 0 && sh4 <= 150 * 1024) {
             p.wpb = 4; p.grid = dim3(nchains / 4); p.block = dim3(512); sh = sh4;
         }
     } else {
@@ -1857,7 +1857,7 @@ static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R
         } else {
             if (p.mat_lds) sh += mb;
             // BASELINE configs[4]'s shape: the kernel without its other variants (LEAN = 2)
-            if (!lean_off && !table && corr && S->nhat_Ms != nullptr && !(S->ablate & 1) && S->nDer == 0 && nr > 64 && D > 64 && D <= 128 && !special) p.lean = 2;
+            if (!lean_off && !table && corr && S->nhat_Ms != nullptr && !(S->ablate & PC_ABL_FUNCTOR) && S->nDer == 0 && nr > 64 && D > 64 && D <= 128 && !special) p.lean = 2;
             else if (D <= 64) p.lean = leanf;
         }
     }

@@ -213,7 +213,7 @@
     C.tsum = 0.0; C.ybuf2 = (double *)smem + (size_t)WPB * per_wave;
 #endif
     const bool corr = PT == 0 && (lean2 || (!lean && !leanf && S.like.kind == PC_LIKE_CORR_GAUSSIAN));
-    C.quad = PT == 0 && !leanf && (lean_any || ((corr || S.like.kind == PC_LIKE_GAUSSIAN) && !(S.ablate & 1)));
+    C.quad = PT == 0 && !leanf && (lean_any || ((corr || S.like.kind == PC_LIKE_GAUSSIAN) && !(S.ablate & PC_ABL_FUNCTOR)));
     C.qnorm = corr ? -((double)D * PC_LOG_TWO_PI + S.like.logdetcov) / 2.0 : S.like.norm;
     // correlated Gaussian: y = theta - mean and M.y travel with the chain (updated, not recomputed, at every
     // accepted point); the matrix is read from LDS when it fits
@@ -318,7 +318,7 @@
         const int v0 = deck_in_regs ? __builtin_amdgcn_readlane(deck, 0) : sdeck[0];
         nh_next[0] = (lane < D) ? nhs[(size_t)v0 * (D + 1) + lane] : 0.0;
         w_next = wsh[v0];
-        if constexpr (LEAN == 1) { if (helped && whitened && !(S.ablate & 16384)) { have_qc = true; qcT = wsh + nr + (size_t)((nr + 3) / 4) * 128; qc_next = qcT[v0]; } }
+        if constexpr (LEAN == 1) { if (helped && whitened && !(S.ablate & PC_ABL_QC_BY_CHAIN)) { have_qc = true; qcT = wsh + nr + (size_t)((nr + 3) / 4) * 128; qc_next = qcT[v0]; } }
     } else
     {   // prefetch the first direction
         const int v0 = deck_in_regs ? __builtin_amdgcn_readlane(deck, 0) : sdeck[0];

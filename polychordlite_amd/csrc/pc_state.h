@@ -11,6 +11,32 @@
 enum { PC_ST_RUNNING = 0, PC_ST_DONE = 1, PC_ST_UPDATE = 2, PC_ST_ERROR = 4 };
 enum { PC_ERR_NONE = 0, PC_ERR_PHANTOM_CAP = 1, PC_ERR_DEAD_CAP = 2, PC_ERR_CLUSTER_CAP = 3, PC_ERR_NOSLOT = 4 };
 
+// PcState::ablate / pchip_settings.ablate: developer and test switches, one bit each, 0 in production (include/polychord_hip.h is the users'
+// description).  Each takes ONE code path away so that the tests can compare it with the other on the same run:
+//   bit  name                       instead of the product                                                   read by
+//    0   PC_ABL_FUNCTOR             built-in quadratic likelihoods like any device functor (one reduction   pc_sample.hip, pc_slice_body.inc,
+//                                   per trial), not in closed form along the chord                           pc_slice_t.hip, pc_engine.hip
+//    1   PC_ABL_NO_POOL             no pool mode                                                             pc_plan.h
+//    2   PC_ABL_NO_DEFER            no deferred update                                                       pc_plan.h
+//    3   PC_ABL_NO_FUSED_UPDATE     no fused update (bits 1 - 3: the same numbers by the older kernels)      pc_plan.h
+//    4   PC_ABL_PAIR_SCANS          the parallel contraction's evidence prefixes by pair scans only          pc_par.hip
+//    5   PC_ABL_CONSUME_GENERAL     several clusters: the general contraction kernel for every launch        pc_plan.h
+//    6   PC_ABL_SLICE_LANE          a run on its own by the lane = chain sampling kernel of runs in step     pc_plan.h
+//    7   PC_ABL_BASES_PACKED        ... and by the lane-per-vector bases                                     pc_plan.h, pc_engine.hip
+//    8   PC_ABL_CL_END_AT_DEATH     the one-wave contraction ends its launch at a cluster's death            pc_consume_cl*_body.inc
+//    9   PC_ABL_KILLOFF_GENERAL     a clustered run's kill-off by the general kernel, not k_killoff_cl       pc_clus.hip
+//   10   PC_ABL_CONSUME_CL_SERIAL   several clusters: k_consume_cl (chain after chain), not k_consume_clp    pc_clus.hip
+//   11, 12                          retired, no effect (experiments that were removed, CHANGELOG.md)
+//   13   PC_ABL_NO_HELPER           the fused k_slice with one wavefront a workgroup, no helper wavefronts   pc_sample.hip
+//   14   PC_ABL_QC_BY_CHAIN         with the helper: s.M.s reduced by the chain, not taken from its table    pc_slice_body.inc
+//   15   PC_ABL_RTC_BUILTINS        the built-ins' sampling kernels from the run-time compiled module        pc_sample.hip, pc_merge.hip, pc_engine.hip
+//   16   PC_ABL_UPDATE_CHAIN        the one-cluster update as a chain of two launches, not five              pc_update.hip
+//   30   PC_ABL_TRACE_CHOL          trace of Cholesky fallbacks                                              pc_contract.hip
+enum { PC_ABL_FUNCTOR = 1 << 0, PC_ABL_NO_POOL = 1 << 1, PC_ABL_NO_DEFER = 1 << 2, PC_ABL_NO_FUSED_UPDATE = 1 << 3, PC_ABL_PAIR_SCANS = 1 << 4,
+       PC_ABL_CONSUME_GENERAL = 1 << 5, PC_ABL_SLICE_LANE = 1 << 6, PC_ABL_BASES_PACKED = 1 << 7, PC_ABL_CL_END_AT_DEATH = 1 << 8,
+       PC_ABL_KILLOFF_GENERAL = 1 << 9, PC_ABL_CONSUME_CL_SERIAL = 1 << 10, PC_ABL_RETIRED_11 = 1 << 11, PC_ABL_RETIRED_12 = 1 << 12,
+       PC_ABL_NO_HELPER = 1 << 13, PC_ABL_QC_BY_CHAIN = 1 << 14, PC_ABL_RTC_BUILTINS = 1 << 15, PC_ABL_UPDATE_CHAIN = 1 << 16, PC_ABL_TRACE_CHOL = 1 << 30 };
+
 #define PC_MASK_WORDS 16         /* phantom mask words per chain: num_repeats <= 1024 */
 
 struct PcCtl {                   // written by the consume kernel, read by the host after each round
@@ -156,12 +182,7 @@ struct PcState {
                                  //   then the last baby of every chain still in the nursery
     int *nn_code;                // [Ncap + B] their codes (slot, -(1 + chain), PC_NN_NONE for an empty slot)
     int nn_valid;                // set by the host for the launches after T0 of the same nursery
-    int ablate;                  // developer / bench switches (bit mask), 0 in production: bit 0 = the built-in quadratic-form
-                                 // likelihoods are evaluated like any device functor (one reduction per trial) instead of in closed form
-                                 // along the chord; bits 1 / 2 / 3 = no pool mode / no deferred update / no fused update (the same numbers
-                                 // by the older kernels: tests/test_gpu_parity.py); bit 4 = the parallel contraction's evidence prefixes by pair
-                                 // scans only (no linear-space path); bit 5 = several clusters: the general contraction kernel for every launch (not
-                                 // the one-wave kernel of pc_clus.hip); bits 11, 12 = retired, no effect; bit 30 = trace of Cholesky fallbacks
+    int ablate;                  // developer / bench switches (PC_ABL_* below), 0 in production
     int seq_mode;                // tests: ONE running Philox stream consumed in the reference's program order
                                  // (B = 1 only; PcCtl::seq is the position), cf. oracle `sequential` mode
     int epoch_discard;           // 1: nested_sampling.F90:313 as written (a change of the cluster list loses every chain in flight); 0: only the ended cluster's

@@ -784,7 +784,7 @@ extern "C" void pc_launch_update_fused(const PcState *S, int nph, unsigned char 
     if (NTv <= 2 && shw < sizeof(double) * (size_t)(4 * 3 * 256)) shw = sizeof(double) * (size_t)(4 * 3 * 256);      // the waves' result tiles reuse the row tile
     // settings.ablate bit 16: the chain (pool mode, up to UPD_SELF_BLOCKS blocks, tickets for every group): flag + offsets, then locate +
     // gather (+ fold + final below 32 dimensions) -- the same bits, 10 us an update slower than the launches below (header comment)
-    if (S->pool && nblk <= UPD_SELF_BLOCKS && UPD_TICKET_GROUP + ng <= PC_UPD_CTR_INTS && (S->ablate & (1 << 16))) {
+    if (S->pool && nblk <= UPD_SELF_BLOCKS && UPD_TICKET_GROUP + ng <= PC_UPD_CTR_INTS && (S->ablate & PC_ABL_UPDATE_CHAIN)) {
         int *ctr = d_total;
         hipLaunchKernelGGL(k_upd_flag_scan, dim3((nblk + 3) / 4), dim3(UPD_NT), 0, st, *S, nph, keep, blk, deferred, nblk, ctr);
 #define UPDC_LAUNCH(NT) { \
