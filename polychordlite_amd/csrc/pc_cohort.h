@@ -79,6 +79,8 @@ struct Cohort {
     void rec(const Rec &r) { pend.push_back(r); }
     // ... the copies among them as (destination, source, bytes): one kernel for all of them (k_copy_batch), not a hipMemcpyAsync each
     std::vector<std::array<uintptr_t, 3>> post_copies, pre_copies;
+    // everything written down and asked for is forgotten, nothing of it launched (the flush it waited for will not come)
+    void drop_pending() { pre.clear(); post.clear(); pend.clear(); pre_copies.clear(); post_copies.clear(); }
     void run_post()
     {
         if (!post_copies.empty()) { std::vector<std::array<uintptr_t, 3>> c; c.swap(post_copies); pc_copy_many(c, st); }

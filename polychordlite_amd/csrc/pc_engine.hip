@@ -14,6 +14,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <cstdarg>
+#include <cstdint>
+#include <new>
 #include <cmath>
 #include <vector>
 #include <memory>
@@ -441,52 +443,7 @@ static double h_uniform(uint32_t k0, uint32_t k1, uint32_t dom, uint32_t shi, ui
 //      ONE stream and go round by round together: what each engine would launch in a phase of the round it writes down here, and
 //      every kernel of the phase is launched ONCE for all of them (blockIdx.y = run, PcManyRec).  The same kernels' bodies on
 //      the same states: the numbers of a run do not know whether it ran alone.
-// ---- a run's host work that has to WAIT for the device in the middle (an update with clustering: counts down, verdicts back,
-//      splits) as a fiber of the thread that drives the runs in step: where a run on its own synchronises its stream, a run in step
-//      yields (Engine::sync_point); the driver goes through all the runs that have something to wait for, launches what they
-//      wrote down ONCE for all of them, waits ONCE, and resumes them.  The waits of sixteen runs' updates cost what one run's do,
-//      and the kernels between two waits are launched together.  (makecontext / swapcontext: no threads, no locks; an
-//      exception inside a fiber is caught at its foot and rethrown by the driver.)
-struct FiberCancelled {};      // thrown inside a suspended fiber that is resumed only to unwind (another run's update failed)
-struct Fiber {
-    ucontext_t ctx, ret;
-    void *stack = nullptr; size_t stack_sz = 0;      // usable part; one PROT_NONE page below it (stacks grow down): an overflow faults
-    void *map = nullptr; size_t map_sz = 0;          // instead of running into the heap
-    std::function<void()> fn;
-    bool started = false, done = false, cancel = false;
-    std::exception_ptr err;
-    // round_finish with clustering goes deep (update, kNN passes, add_cluster, the resume file's writer, HIP runtime calls): 8 MB of
-    // address space, committed as touched
-    void make_stack()
-    {
-        if (stack) return;
-        const size_t page = (size_t)sysconf(_SC_PAGESIZE), want = (size_t)8 << 20;
-        void *m = mmap(nullptr, want + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_STACK, -1, 0);
-        if (m == MAP_FAILED) throw std::bad_alloc();
-        (void)mprotect(m, page, PROT_NONE);
-        map = m; map_sz = want + page; stack = (char *)m + page; stack_sz = want;
-    }
-    void free_stack() { if (map) munmap(map, map_sz); map = stack = nullptr; map_sz = stack_sz = 0; }
-    static void foot(unsigned lo, unsigned hi)
-    {
-        Fiber *f = (Fiber *)(((uintptr_t)hi << 32) | (uintptr_t)lo);
-        try { f->fn(); } catch (...) { f->err = std::current_exception(); }
-        f->done = true;
-        swapcontext(&f->ctx, &f->ret);
-    }
-    void resume()
-    {
-        if (!started) {
-            getcontext(&ctx);
-            ctx.uc_stack.ss_sp = stack; ctx.uc_stack.ss_size = stack_sz; ctx.uc_link = nullptr;
-            const uintptr_t a = (uintptr_t)this;
-            makecontext(&ctx, (void (*)())foot, 2, (unsigned)(a & 0xFFFFFFFFu), (unsigned)(a >> 32));
-            started = true;
-        }
-        swapcontext(&ret, &ctx);
-    }
-    void yield() { swapcontext(&ctx, &ret); }
-};
+#include "pc_fiber.h"       // Fiber: a run's host work that has to wait for the device in the middle, as a fiber of the driving thread; pc_wait_stream
 
 #include "pc_cohort.h"      // Cohort: the launches of the runs in step, written down and made once for all of them (the table of stages)
 
@@ -844,9 +801,7 @@ struct Engine {
             return;
         }
         if (co) co->flush();
-        // (polling the stream wakes the host a few microseconds after the copy; the blocking wait sleeps on an interrupt)
-        for (int spins = 0; spins < 200000; ++spins) { const hipError_t q = hipStreamQuery(st); if (q != hipErrorNotReady) { HIPCHK(q); break; } __builtin_ia32_pause(); }
-        HIPCHK(hipStreamSynchronize(st));
+        pc_wait_stream(st);
     }
     // something launched here and now, behind whatever the runs in step have written down so far
     void direct_op() { if (co) co->flush(); }
@@ -2622,6 +2577,8 @@ struct Engine {
 
 }  // namespace
 
+#include "pc_step.h"        // pc_run_many: the driver of the runs in step, a group at a time, as named phases (StepGroup)
+
 extern "C" {
 
 void polychord_hip_request_stop(void) { std::lock_guard<std::mutex> g(g_run_mutex); for (auto *f : g_run_stop) f->store(1); }
@@ -2707,295 +2664,6 @@ int pchip_run_hooks(const pchip_settings *s, const pchip_like *like, const pchip
         out->t_results = std::chrono::duration<double>(t2 - t1).count() - out->t_total;
     }
     return rc;
-}
-
-// The runs of `seeds` on `device`, driven by the calling thread, up to max_in_flight of them in step on one stream (Cohort): every
-// phase of the round is gone through for all of them before anything is launched, then each kernel of the phase once for all.
-// Built-in device likelihoods only: a host callback belongs to its caller's thread.  Returns 0 or the first failing run's code.
-int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds, int device,
-                int max_in_flight, pchip_result *results)
-{
-    const bool prof = pc_env().debug == 5;
-    for (int k = 0; k < nseeds; ++k) std::memset(&results[k], 0, sizeof(pchip_result));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return PC_RC_DEVICE; }
-    (void)hipSetDevice(device >= 0 ? device % ndev : 0);
-    const int W = std::max(1, std::min(std::min(max_in_flight, nseeds), 64));
-    int worst = 0;
-    int done_here = 0;
-    for (int base = 0; base < nseeds && !worst; base += done_here) {
-        int n = std::min(W, nseeds - base);
-        const auto Tpre = std::chrono::steady_clock::now();
-        Cohort co;
-        const bool side_off = pc_env().cohort_side_off;
-        // (a main stream whose hardware queue is known already, if the pool has one: the side stream is then picked without a test --
-        //  a test is a millisecond, several once PyTorch lives in the process, and the pool's first stream was a different one of
-        //  the engines' copy streams at every call)
-        // (and the pair of the call before, if the pool still has it: whatever the runtime sets up for a stream at its first copy or
-        //  launch is then there -- a call's first wait was 10 ... 24 ms now and then while the pair changed from call to call)
-        static std::mutex last_m; static hipStream_t last_st[64] = {nullptr}, last_st2[64] = {nullptr};
-        int devq = 0; (void)hipGetDevice(&devq); devq &= 63;
-        int cls_main = -1, cls_side = -1;
-        bool cohort_loaded = false;
-        CohortLease lease(devq);
-        {
-            hipStream_t want, want2;
-            { std::lock_guard<std::mutex> g(last_m); want = last_st[devq]; want2 = last_st2[devq]; }
-            std::lock_guard<std::mutex> gq(cstreams().m);             // (one group at a time picks: what it takes the next one avoids)
-            std::vector<int> busy = cstreams().busy(devq);
-            const bool loaded = !busy.empty();                    // another group is at work on this device: no class tests now
-            // (more groups than hardware queues can keep apart: at least not on another group's MAIN stream's queue)
-            if (busy.size() >= 4) busy = cstreams().busy(devq, true);
-            auto free_cls = [&](hipStream_t x) { const int c = sclasses().known(x); return c >= 0 && std::find(busy.begin(), busy.end(), c) == busy.end(); };
-            if (want) co.st = hpool().take_stream_if([&](hipStream_t x) { return x == want && (busy.empty() || free_cls(x)); });
-            if (!co.st) co.st = hpool().take_stream_if([&](hipStream_t x) { return busy.empty() ? sclasses().known(x) >= 0 : free_cls(x); });
-            if (!co.st) co.st = busy.empty() ? hpool().get_stream() : stream_avoiding(busy, loaded);
-            const auto Tp1 = std::chrono::steady_clock::now();
-            if (!busy.empty() || !side_off) cls_main = loaded ? sclasses().known(co.st) : sclasses().classify(co.st);
-            if (!side_off) {
-                if (cls_main >= 0) busy.push_back(cls_main);
-                if (co.st == want && want2) co.st2 = hpool().take_stream_if([&](hipStream_t x) { return x == want2 && free_cls(x); });
-                if (!co.st2) co.st2 = stream_avoiding(busy, loaded);
-                cls_side = loaded ? sclasses().known(co.st2) : sclasses().classify(co.st2);
-            }
-            cohort_loaded = loaded;
-            cstreams().take(devq, cls_main, true); cstreams().take(devq, cls_side); lease.hold(cls_main, cls_side);
-            { std::lock_guard<std::mutex> g(last_m); last_st[devq] = co.st; last_st2[devq] = co.st2; }
-            if (prof) std::fprintf(stderr, "polychord_hip dbg cohort: main stream %.2f ms, side stream %.2f ms\n", std::chrono::duration<double>(Tp1 - Tpre).count() * 1e3, std::chrono::duration<double>(std::chrono::steady_clock::now() - Tp1).count() * 1e3);
-        }
-        if (co.st2) { co.ev_up = hpool().get_sync_event(); co.ev_next = hpool().get_sync_event(); }
-        const bool stc_off = pc_env().cohort_copy_streams_off;
-        if (!stc_off) { co.stc[0] = stream_beside({co.st, co.st2}, cohort_loaded); co.stc[1] = stream_beside({co.st, co.st2, co.stc[0]}, cohort_loaded); }
-        std::vector<Engine *> E((size_t)n, nullptr);
-        std::vector<char> live((size_t)n, 0), enq((size_t)n, 0);
-        const auto T0 = std::chrono::steady_clock::now();
-        long rounds = 0; double t_begin = 0, t_end = 0, t_wait = 0, t_enq = 0, t_fin = 0, t_fl = 0, t_comp = 0, t_end_dev = 0, t_fwait = 0; long n_fwait = 0;
-        const bool fibers_on = !pc_env().cohort_fibers_off;
-        std::vector<Fiber> fibs;
-        int *h_totals = nullptr; size_t totals_cap = 0;
-        double t_setup_max = 0; int n_comp_pass = 0;
-        struct EndBatch { std::vector<int> fin, rcs; hipEvent_t ev = nullptr, ev2 = nullptr; int dev = 0; std::thread th; };
-        std::vector<std::unique_ptr<EndBatch>> endings;
-        auto nowc = [] { return std::chrono::steady_clock::now(); };
-        auto secc = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-        auto close = [&](int k, int rc) {
-            if (rc != 0) { pchip_result_free(&results[base + k]); if (!worst) worst = rc; }
-            E[k]->destroy(); delete E[k]; E[k] = nullptr; live[k] = 0;
-        };
-        try {
-            {
-                // set-up and live points of the runs: the first one by itself (a run that does not fit, or fails, alone is the
-                // call's failure), then the others -- a tenth of a millisecond of host work each, 7 ms of sixty-four runs' 175.
-                // (Shared out among four threads it was TWICE as long -- 13 ms -- the runtime's calls queue for one another:
-                //  PC_COHORT_SETUP_THREADS, one by default)
-                std::vector<int> rc_begin((size_t)n, -1), err((size_t)n, 0);
-                std::vector<std::string> errmsg((size_t)n);
-                std::atomic<bool> failed{false};
-                int devnow = 0; (void)hipGetDevice(&devnow);
-                auto setup_one = [&](int k) {
-                    E[k] = new Engine; E[k]->co = &co;
-                    pchip_settings c = *s; c.seed = seeds[base + k]; c.device = device;
-                    const auto q0 = nowc();
-                    try { E[k]->setup(c, *like, *prior); rc_begin[k] = E[k]->begin(); }
-                    catch (const EngineError &e) { err[k] = e.code ? e.code : PC_RC_DEVICE; errmsg[k] = e.msg; failed = true; }
-                    catch (const std::bad_alloc &) { err[k] = PC_RC_MEMORY; errmsg[k] = "out of host memory"; failed = true; }
-                    if (k == 0) t_setup_max = secc(q0, nowc());
-                };
-                const auto b0 = nowc();
-                setup_one(0);
-                const int setup_threads = pc_env().cohort_setup_threads;
-                if (n > 1 && !failed) {
-                    std::atomic<int> nextk{1};
-                    auto worker = [&] { (void)hipSetDevice(devnow); for (int k; !failed && (k = nextk.fetch_add(1)) < n;) setup_one(k); };
-                    std::vector<std::thread> th;
-                    for (int t = 1; t < std::min(setup_threads, n - 1) && n >= 8; ++t) th.emplace_back(worker);
-                    worker();
-                    for (auto &t : th) t.join();
-                }
-                t_begin += secc(b0, nowc());
-                for (int k = 0; k < n; ++k) {
-                    if (!err[k] && E[k]) continue;
-                    if (err[k] && (err[k] != PC_RC_MEMORY || k == 0)) throw EngineError{err[k], errmsg[k]};
-                    // no memory for one more run of this size next to the k that are set up: those go in step, the others after them
-                    (void)hipGetLastError();
-                    for (int j = k; j < n; ++j) if (E[j]) { try { E[j]->destroy(); } catch (...) {} delete E[j]; E[j] = nullptr; }
-                    n = k;
-                    break;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const int rc = rc_begin[k];
-                    if (rc >= 0) { close(k, rc ? rc : PC_RC_DEVICE); continue; }
-                    live[k] = 1;
-                }
-            }
-            int nlive = 0;
-            for (int k = 0; k < n; ++k) nlive += live[k];
-            while (nlive > 0 && !worst) {
-                {   // phantom arrays that are full: compacted together, one wait for all.  (Only the full ones: taking the arrays
-                    // that are more than half full along -- the runs fill theirs at slightly different rates, and a pass a round
-                    // later is another wait of the whole cohort -- kept the passes at three a call, and changed the last bits of
-                    // some runs: the update's partial sums are grouped by the array's extent, so a run must compact exactly
-                    // when it would alone.  tools/dev/fuzz_in_step.py found it)
-                    int nc = 0;
-                    for (int k = 0; k < n; ++k) if (live[k] && E[k]->compact_wanted()) nc++;
-                    if (nc) {
-                        const auto c0 = nowc();
-                        std::vector<char> cmp((size_t)n, 0);
-                        for (int k = 0; k < n; ++k) if (live[k] && E[k]->compact_wanted()) { cmp[k] = 1; E[k]->compact_record(); }
-                        co.flush();
-                        if ((size_t)n > totals_cap) { if (h_totals) hfree(h_totals); h_totals = halloc<int>((size_t)n); totals_cap = (size_t)n; }
-                        for (int k = 0; k < n; ++k) if (cmp[k]) HIPCHK(hipMemcpyAsync(&h_totals[k], E[k]->d_total, sizeof(int), hipMemcpyDeviceToHost, co.st));
-                        HIPCHK(hipStreamSynchronize(co.st));
-                        for (int k = 0; k < n; ++k) if (cmp[k]) E[k]->compact_finish(h_totals[k]);
-                        t_comp += secc(c0, nowc()); n_comp_pass++;
-                    }
-                }
-                { const auto a0 = nowc(); for (int k = 0; k < n; ++k) enq[k] = (live[k] && E[k]->round_enqueue()) ? 1 : 0; const auto a1 = nowc(); t_enq += secc(a0, a1);
-                  co.flush(); t_fl += secc(a1, nowc()); }
-                { const auto w0 = nowc(); for (int k = 0; k < n; ++k) if (enq[k]) while (!E[k]->round_ready()) __builtin_ia32_pause(); t_wait += secc(w0, nowc()); }
-                { const auto a0 = nowc();
-                  // what the round did: a run whose update has to wait for the device in the middle (clustering, files, hooks) makes it as a
-                  // fiber of this thread; the others at once
-                  std::vector<int> wk;
-                  for (int k = 0; k < n; ++k) {
-                      if (!enq[k]) continue;
-                      if (fibers_on && E[k]->finish_may_wait()) wk.push_back(k);
-                      else if (!E[k]->round_finish()) enq[k] = 0;
-                  }
-                  if (!wk.empty()) {
-                      if (fibs.size() < wk.size()) fibs.resize(wk.size());
-                      std::vector<char> ok(wk.size(), 1);
-                      for (size_t a = 0; a < wk.size(); ++a) {
-                          Fiber &f = fibs[a];
-                          f.make_stack();
-                          f.started = false; f.done = false; f.cancel = false; f.err = nullptr;
-                          Engine *e = E[wk[a]]; char *okp = &ok[a];
-                          f.fn = [e, okp] { *okp = e->round_finish() ? 1 : 0; };
-                          e->fib = &f;
-                      }
-                      std::exception_ptr first_err;
-                      for (;;) {
-                          bool waiting = false;
-                          for (size_t a = 0; a < wk.size(); ++a) {
-                              Fiber &f = fibs[a];
-                              if (f.done) continue;
-                              f.resume();
-                              if (f.err && !first_err) first_err = f.err;
-                              if (!f.done) waiting = true;
-                          }
-                          if (first_err || !waiting) break;
-                          // one launch of what they all wrote down, one wait for all of them
-                          const auto w0 = nowc();
-                          co.flush();
-                          for (int spins = 0; spins < 200000; ++spins) { const hipError_t q = hipStreamQuery(co.st); if (q != hipErrorNotReady) { HIPCHK(q); break; } __builtin_ia32_pause(); }
-                          HIPCHK(hipStreamSynchronize(co.st));
-                          t_fwait += secc(w0, nowc()); n_fwait++;
-                      }
-                      if (first_err) {
-                          // the fibers still suspended hold locals, pinned blocks and copies written down for a flush that will not come: what
-                          // they wrote down is dropped, and each is resumed once more with the cancel flag -- its wait throws, its frames unwind
-                          co.pre.clear(); co.post.clear(); co.pend.clear(); co.pre_copies.clear(); co.post_copies.clear();
-                          for (size_t a = 0; a < wk.size(); ++a) {
-                              Fiber &f = fibs[a];
-                              if (f.started && !f.done) { f.cancel = true; f.resume(); }
-                          }
-                          co.pre.clear(); co.post.clear(); co.pend.clear(); co.pre_copies.clear(); co.post_copies.clear();
-                      }
-                      for (size_t a = 0; a < wk.size(); ++a) { E[wk[a]]->fib = nullptr; if (!ok[a]) enq[wk[a]] = 0; }
-                      if (first_err) std::rethrow_exception(first_err);
-                  }
-                  const auto a1 = nowc(); t_fin += secc(a0, a1);
-                  co.flush(); t_fl += secc(a1, nowc()); }
-                rounds++;
-                bool any_done = false;
-                for (int k = 0; k < n; ++k) any_done = any_done || (live[k] && !enq[k]);
-                if (any_done) {
-                    // the runs that are over end together: their kill-off in one launch, and what their results need asked of the
-                    // device behind it.  Nobody waits here: a thread takes the batch from there (two events, then the host's half
-                    // of the endings -- results, buffers given back, a third of a millisecond per run, shared out among a few
-                    // threads) while the runs that are left go on with their rounds
-                    const auto e0 = nowc();
-                    co.flush();
-                    for (int k = 0; k < n; ++k) if (live[k] && !enq[k] && !E[k]->r_rc) E[k]->end_a(true);
-                    co.flush();
-                    for (int k = 0; k < n; ++k) if (live[k] && !enq[k] && !E[k]->r_rc) E[k]->end_a2();
-                    endings.emplace_back(new EndBatch);
-                    EndBatch *eb = endings.back().get();
-                    for (int k = 0; k < n; ++k) if (live[k] && !enq[k]) eb->fin.push_back(k);
-                    eb->rcs.assign(eb->fin.size(), 0);
-                    eb->dev = E[eb->fin[0]]->dev;
-                    eb->ev = hpool().get_sync_event(); HIPCHK(hipEventRecord(eb->ev, co.st));
-                    if (co.st2) { eb->ev2 = hpool().get_sync_event(); HIPCHK(hipEventRecord(eb->ev2, co.st2)); }      // (bases drawn ahead for a run that is over: not into freed memory)
-                    for (int k : eb->fin) { live[k] = 0; nlive--; if (E[k]->r_rc && !worst) worst = E[k]->r_rc; }      // (a run that failed stops the others at once)
-                    eb->th = std::thread([&E, &results, base, eb] {
-                        (void)hipSetDevice(eb->dev);
-                        const auto w0 = std::chrono::steady_clock::now();
-                        const hipError_t w1 = hipEventSynchronize(eb->ev), w2 = eb->ev2 ? hipEventSynchronize(eb->ev2) : hipSuccess;
-                        g_dbg_evwait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - w0).count();
-                        auto finish_one = [&](size_t a) {
-                            const int k = eb->fin[a];
-                            int r = E[k]->r_rc;
-                            if (!r && (w1 != hipSuccess || w2 != hipSuccess)) r = PC_RC_DEVICE;
-                            const auto q0 = std::chrono::steady_clock::now();
-                            if (!r) {
-                                try { E[k]->end_wait_aside(); r = E[k]->end_b(&results[base + k]); }
-                                catch (const EngineError &e) { std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str()); r = e.code; }
-                                catch (const std::bad_alloc &) { r = PC_RC_MEMORY; }
-                            }
-                            const auto q1 = std::chrono::steady_clock::now();
-                            if (r != 0) pchip_result_free(&results[base + k]);
-                            try { E[k]->destroy(r == 0 && E[k]->st_side == nullptr); } catch (...) {}      // (end_b has waited for the copy stream, this thread for the cohort's two)
-                            delete E[k]; E[k] = nullptr; eb->rcs[a] = r;
-                            g_dbg_endb_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(q1 - q0).count();
-                            g_dbg_destroy_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - q1).count();
-                        };
-                        const size_t nth = std::min<size_t>(eb->fin.size(), 8);
-                        if (nth <= 1) { for (size_t a = 0; a < eb->fin.size(); ++a) finish_one(a); }
-                        else {
-                            std::atomic<size_t> nexta{0};
-                            auto worker = [&] { (void)hipSetDevice(eb->dev); for (size_t a; (a = nexta.fetch_add(1)) < eb->fin.size();) finish_one(a); };
-                            std::vector<std::thread> th;
-                            for (size_t t = 1; t < nth; ++t) th.emplace_back(worker);
-                            worker();
-                            for (auto &t : th) t.join();
-                        }
-                    });
-                    t_end_dev += secc(e0, nowc());
-                }
-            }
-        }
-        catch (const EngineError &e) { std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str()); (void)hipGetLastError(); if (!worst) worst = e.code; }
-        catch (const std::bad_alloc &) { std::fprintf(stderr, "polychord_hip: out of host memory\n"); if (!worst) worst = PC_RC_MEMORY; }
-        catch (const std::exception &e) { std::fprintf(stderr, "polychord_hip: %s\n", e.what()); if (!worst) worst = PC_RC_DEVICE; }      // (a thread that could not be started: nothing leaves through the C interface)
-        {   // the endings under way
-            const auto e0 = nowc();
-            for (auto &eb : endings) {
-                if (eb->th.joinable()) eb->th.join();
-                for (int r : eb->rcs) if (r != 0 && !worst) worst = r;
-                if (eb->ev) hpool().put_sync_event(eb->ev); if (eb->ev2) hpool().put_sync_event(eb->ev2);
-            }
-            t_end += secc(e0, nowc());
-        }
-        if (co.st2) (void)hipStreamSynchronize(co.st2);
-        for (int k = 0; k < n; ++k) if (E[k]) { pchip_result_free(&results[base + k]); try { E[k]->destroy(); } catch (...) {} delete E[k]; E[k] = nullptr; }
-        if (prof) { std::fprintf(stderr, "polychord_hip dbg cohort: of enqueue: nursery %.2f ms (compaction %.2f), capacity %.2f\n", g_dbg_nursery_ns.exchange(0) * 1e-6, g_dbg_compact_ns.exchange(0) * 1e-6, g_dbg_capacity_ns.exchange(0) * 1e-6);
-                    std::fprintf(stderr, "polychord_hip dbg cohort: %zu ending batches: events %.2f ms, results %.2f ms, teardown %.2f ms (summed over threads); the block caches hold %.2f GB of device and %.2f GB of pinned memory; teardown: device blocks %.2f, the rest %.2f ms\n", endings.size(), g_dbg_evwait_ns.exchange(0) * 1e-6, g_dbg_endb_ns.exchange(0) * 1e-6, g_dbg_destroy_ns.exchange(0) * 1e-6, dcache().cached / 1073741824.0, hcache().cached / 1073741824.0, g_dbg_d1.exchange(0) * 1e-6, g_dbg_d2.exchange(0) * 1e-6); }
-        if (prof) std::fprintf(stderr, "polychord_hip dbg cohort: the first run's set-up and live points %.2f ms\n", t_setup_max * 1e3);
-        if (prof) std::fprintf(stderr, "polychord_hip dbg cohort: trips to the driver: %lld device blocks (%.2f ms), %lld pinned blocks (%.2f ms), %lld streams (%.2f ms)\n", g_dbg_miss_n[0].exchange(0), g_dbg_miss_ns[0].exchange(0) * 1e-6, g_dbg_miss_n[1].exchange(0), g_dbg_miss_ns[1].exchange(0) * 1e-6, g_dbg_mk_stream_n.exchange(0), g_dbg_mk_stream_ns.exchange(0) * 1e-6);
-        if (prof) std::fprintf(stderr, "polychord_hip dbg cohort: %d runs, %ld rounds, streams %.2f ms, wall %.2f ms (setup + begin %.2f, compactions %.2f in %d passes, enqueue %.2f, finish %.2f, launches %.2f, waiting for the device %.2f, the endings' requests %.2f, waiting for the endings %.2f); %ld records launched together, %ld one by one\n", n, rounds, std::chrono::duration<double>(T0 - Tpre).count() * 1e3,
-                               std::chrono::duration<double>(std::chrono::steady_clock::now() - T0).count() * 1e3, t_begin * 1e3, t_comp * 1e3, n_comp_pass, t_enq * 1e3, t_fin * 1e3, t_fl * 1e3, t_wait * 1e3, t_end_dev * 1e3, t_end * 1e3, co.n_fused, co.n_single);
-        for (Fiber &f : fibs) f.free_stack();
-        if (prof) std::fprintf(stderr, "polychord_hip dbg cohort: of finish: %ld shared waits, %.2f ms\n", n_fwait, t_fwait * 1e3);
-        co.destroy();
-        if (h_totals) hfree(h_totals);
-        (void)hipStreamSynchronize(co.st);
-        lease.release();
-        hpool().put_stream(co.st);
-        if (co.st2) { (void)hipStreamSynchronize(co.st2); hpool().put_stream(co.st2); hpool().put_sync_event(co.ev_up); hpool().put_sync_event(co.ev_next); }
-        for (int q = 0; q < 2; ++q) if (co.stc[q]) { (void)hipStreamSynchronize(co.stc[q]); hpool().put_stream(co.stc[q]); co.stc[q] = nullptr; }
-        done_here = n;
-    }
-    return worst;
 }
 
 void pchip_result_free(pchip_result *r)

@@ -639,6 +639,33 @@ def test_runs_in_step_at_every_width(engine, D):
 
 
 @pytest.mark.gpu
+def test_more_seeds_than_fit_go_group_after_group(engine):
+    """more seeds than max_in_flight: a driving thread takes its runs a group at a time, the next group on the stream pair the one before
+    gave back -- every run bit for bit the run it is alone.  Unclustered: five seeds, two in flight (one thread: groups of 2, 2 and 1).
+    Clustered: twelve seeds, eight in flight (four scheduler threads side by side, each a group of two, then a group of one)."""
+    from polychordlite_amd.repeats import run_repeats
+    api = engine
+    lib = api.load()
+    for kind, box, nlive, nr, clus, seeds, mif in [("gaussian", None, 50, 4, 0, [700 + j for j in range(5)], 2),
+                                                   ("rastrigin", (-5.12, 5.12), 100, 6, 1, [720 + j for j in range(12)], 8)]:
+        L, P, keep = api.make_problem(kind, 2, 0, *box) if box else api.make_problem(kind, 2, 0)
+        def settings(seed):
+            s = api.Settings(); lib.pchip_settings_default(C.byref(s), 2, 0)
+            s.nlive, s.num_repeats, s.seed, s.do_clustering = nlive, nr, seed, clus
+            return s
+        singles = [api.run(settings(sd), L, P) for sd in seeds]
+        merged, runs = run_repeats(settings(0), L, P, seeds, max_in_flight=mif)
+        assert len(runs) == len(seeds) and merged["n_runs"] == len(seeds)
+        assert len({r["nrounds"] for r in singles}) > 1      # (they do not all end in the same round)
+        for one, r in zip(singles, runs):
+            for k in ("ndead", "nlike", "niter", "nupdates", "nbatches"):
+                assert one[k] == r[k], (kind, k, one[k], r[k])
+            assert one["logZ"] == r["logZ"] and one["logZerr"] == r["logZerr"]
+            assert np.array_equal(one["dead"], r["dead"], equal_nan=True) and np.array_equal(one["logweights"], r["logweights"]) and np.array_equal(one["live"], r["live"], equal_nan=True)
+            assert np.array_equal(one["post_mean"], r["post_mean"], equal_nan=True)
+
+
+@pytest.mark.gpu
 def test_bases_of_runs_in_step_are_the_bases_of_runs_alone(engine):
     """runs in step, whose bases come from the deviates kernel and the Gram-Schmidt kernel behind it (k_deviates_t + k_bases_packed) --
     every run bit for bit the run it is alone, whose bases come from k_nhats; nDims even and odd (an odd nDims puts every other vector
