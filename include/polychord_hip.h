@@ -207,9 +207,10 @@ typedef struct {
     int source;                    /* PCHIP_LIKE_SOURCE: handle from pchip_source_create (ABI 9) */
 } pchip_like;
 
-enum { PCHIP_PRIOR_CALLBACK = 0, PCHIP_PRIOR_BOX = 1, PCHIP_PRIOR_TABLE = 2 };
+enum { PCHIP_PRIOR_CALLBACK = 0, PCHIP_PRIOR_BOX = 1, PCHIP_PRIOR_TABLE = 2, PCHIP_PRIOR_SOURCE = 3 };
 typedef struct {
-    int kind;                      /* PCHIP_PRIOR_*: 0 callback, 1 uniform box, 2 table */
+    int kind;                      /* PCHIP_PRIOR_*: 0 callback, 1 uniform box, 2 table, 3 the source handle's own pchip_prior_param
+                                      (pchip_source_create_prior; the handle is pchip_like.source, nothing below is read) */
     const double *lo, *hi;         /* host, D each; NULL => [0,1] */
     polychord_prior_fn fn;
     /* kind == PCHIP_PRIOR_TABLE only (never read otherwise): nDims entries in parameter order, and the hypercube index of every
@@ -267,7 +268,7 @@ enum { PCHIP_PATH_CONSUME_PAR = 0,      /* one cluster: the parallel contraction
        PCHIP_PATH_SUBCLUSTER_PASSES = 17,   /* clustering passes on the sub-clustering coordinates (settings.n_sub_cluster > 0: one per update) */
        PCHIP_PATH_SUBCLUSTER_SPLITS = 18,   /* clusters those passes split */
        PCHIP_PATH_SOURCE_KERNELS = 19,      /* launches of run-time compiled sampling kernels (PCHIP_LIKE_SOURCE, settings.ablate bit 15) */
-       PCHIP_PATH_DEVICE_PRIOR = 20,        /* sampling launches (live points, nurseries) that evaluated a prior table on the device */
+       PCHIP_PATH_DEVICE_PRIOR = 20,        /* sampling launches (live points, nurseries) that evaluated a prior table or a source prior on the device */
        PCHIP_PATH_SOURCE_TERMS = 21,        /* ... of those of slot 19, the launches whose kernels took the terms form of a source (pchip_source_create_terms) */
        PCHIP_PATH_COUNT = 24 };
 
@@ -343,6 +344,22 @@ void pchip_source_destroy(int handle);
  * pchip_source_destroy as pchip_source_create; nterms >= 1.  pchip_like.kind stays PCHIP_LIKE_SOURCE: the handle knows its form;
  * pchip_result.path[PCHIP_PATH_SOURCE_TERMS] counts the launches that took it. */
 int  pchip_source_create_terms(const char *source, const char *options, const double *data, long ndata, long nterms);
+/* The user's PRIOR in the same source and the same handle as the likelihood (pchip_prior.kind = PCHIP_PRIOR_SOURCE with pchip_like.kind =
+ * PCHIP_LIKE_SOURCE, .source = the handle).  Besides the likelihood functions of its form -- nterms == 0: pchip_loglikelihood; nterms
+ * >= 1: pchip_logl_term and pchip_logl_finish -- the source defines
+ *     __device__ double pchip_prior_param(const double *cube, int i, int nDims, const double *data, long ndata);
+ * which returns theta[i].  It is called once per parameter, lane = parameter: `cube` is the whole hypercube point (nDims doubles,
+ * read-only, hypercube order = parameter order; the source may read any coordinate, so a dependent prior -- a Cholesky factor, a
+ * hyper-parameter, an ordered block -- loops in its lane), `data` the handle's data block, the one the likelihood sees.  Contract: pure,
+ * deterministic, must not synchronise; only ever called for points inside the unit cube; the likelihood receives exactly the values
+ * returned.  Same options rule, data block, handle space and pchip_source_destroy as pchip_source_create; a source that lacks one of
+ * its functions fails here, by name.  The handle also runs under prior.kind 1 and 2, as one without a prior does.  A prior source for a
+ * built-in or callback likelihood (a prior-only handle), pchip_run_repeats and the PolyChord-interface doors are not supported:
+ * the run fails with a message.  Launches are counted in path[PCHIP_PATH_DEVICE_PRIOR] and path[PCHIP_PATH_SOURCE_KERNELS]. */
+int  pchip_source_create_prior(const char *source, const char *options, const double *data, long ndata, long nterms);
+/* The prior of such a handle at n hypercube points, cubes[n][nDims] -> thetas[n][nDims] (host arrays): one wavefront a point, through
+ * the transform code of the sampling kernels.  Return codes as pchip_source_eval. */
+int  pchip_source_prior_eval(int handle, const double *cubes, long n, int nDims, double *thetas);
 /* A source likelihood (either form) at n points, thetas[n][nDims] -> logL[n], phi[n][nDerived] (host arrays; phi may be NULL when
  * nDerived is 0): one wavefront a point, through the evaluation code of the sampling kernels.  For tests, and for users checking their
  * source against a host version.  0, or 1 with a message in polychord_hip_last_error(), 2 no device / HIP error, 3 nDims > 256. */

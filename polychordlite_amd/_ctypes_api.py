@@ -54,7 +54,7 @@ class Prior(C.Structure):
 
 
 # pchip_prior.kind
-PRIOR_CALLBACK, PRIOR_BOX, PRIOR_TABLE = 0, 1, 2
+PRIOR_CALLBACK, PRIOR_BOX, PRIOR_TABLE, PRIOR_SOURCE = 0, 1, 2, 3
 # the reference's prior type numbers (priors.f90:5-15) a table takes
 PRIOR_TYPES = {"uniform": 1, "log_uniform": 2, "power_uniform": 3, "gaussian": 4, "half_gaussian": 5, "exponential": 6,
                "sorted_uniform": 7, "sorted_gaussian": 8, "sorted_half_gaussian": 9, "sorted_exponential": 10}
@@ -118,6 +118,10 @@ def load():
     lib.pchip_source_create.restype = C.c_int
     lib.pchip_source_create_terms.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long]
     lib.pchip_source_create_terms.restype = C.c_int
+    lib.pchip_source_create_prior.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long]
+    lib.pchip_source_create_prior.restype = C.c_int
+    lib.pchip_source_prior_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_long, C.c_int, C.POINTER(C.c_double)]
+    lib.pchip_source_prior_eval.restype = C.c_int
     lib.pchip_source_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_long, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.pchip_source_eval.restype = C.c_int
     lib.pchip_source_destroy.argtypes = [C.c_int]
@@ -150,14 +154,18 @@ def dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def source_create(source, options=(), data=None, nterms=None):
+def source_create(source, options=(), data=None, nterms=None, prior=False):
     """handle of a likelihood written as HIP device source (pchip_source_create); RuntimeError with the compiler's log if it does not compile.
-    nterms given: the terms form (pchip_source_create_terms) -- the source defines pchip_logl_term and pchip_logl_finish, the sum has nterms terms"""
+    nterms given: the terms form (pchip_source_create_terms) -- the source defines pchip_logl_term and pchip_logl_finish, the sum has nterms terms.
+    prior=True: the source defines pchip_prior_param as well (pchip_source_create_prior), for runs with prior.kind = PRIOR_SOURCE"""
     lib = load()
     d = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
     opts = " ".join(options) if not isinstance(options, str) else options
     args = (source.encode(), opts.encode(), dptr(d) if d is not None and d.size else None, 0 if d is None else int(d.size))
-    h = lib.pchip_source_create(*args) if nterms is None else lib.pchip_source_create_terms(*args, int(nterms))
+    if prior:
+        h = lib.pchip_source_create_prior(*args, 0 if nterms is None else int(nterms))
+    else:
+        h = lib.pchip_source_create(*args) if nterms is None else lib.pchip_source_create_terms(*args, int(nterms))
     if h <= 0:
         log = lib.polychord_hip_last_error()
         raise RuntimeError("device source does not compile:\n" + (log.decode(errors="replace") if log else "(no log)"))
@@ -175,6 +183,19 @@ def source_eval(handle, thetas, nDerived=0):
         msg = lib.polychord_hip_last_error()
         raise RuntimeError(f"pchip_source_eval failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
     return logL, phi
+
+
+def source_prior_eval(handle, cubes):
+    """pchip_source_prior_eval: the prior of a source handle (source_create(..., prior=True)) at the rows of `cubes` ([n][nDims]), on the
+    device; theta rows"""
+    lib = load()
+    c = np.ascontiguousarray(np.atleast_2d(cubes), dtype=np.float64)
+    th = np.empty_like(c)
+    rc = lib.pchip_source_prior_eval(handle, dptr(c), c.shape[0], c.shape[1], dptr(th))
+    if rc != 0:
+        msg = lib.polychord_hip_last_error()
+        raise RuntimeError(f"pchip_source_prior_eval failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
+    return th
 
 
 def prior_table(entries, hyper=None):
@@ -228,10 +249,11 @@ def prior_transform(entries, cubes, hyper=None, device=-1):
 
 
 def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, invcov=None, mean=None, logdet=0.0, source=0,
-                 prior_table=None, hyper=None):
+                 prior_table=None, hyper=None, prior_source=False):
     """(Like, Prior, keepalive) for a built-in device likelihood, or a device source ("source", source=handle), and a uniform box prior
     -- or, with prior_table = [(type, block, params) | (type, params), ...] (and hyper, the parameters' hypercube indices), a prior table
-    evaluated inside the sampling kernels (pchip_prior.kind = 2)."""
+    evaluated inside the sampling kernels (pchip_prior.kind = 2) -- or, with prior_source=True, the source handle's own pchip_prior_param
+    (pchip_prior.kind = 3; the handle from source_create(..., prior=True))."""
     keep = []
     L = Like()
     L.kind = LIKE_KINDS[kind]
@@ -244,6 +266,9 @@ def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, i
         L.invcov, L.mean = dptr(ic), dptr(mn)
     P = Prior()
     P.kind = 1
+    if prior_source:
+        P.kind = PRIOR_SOURCE
+        return L, P, keep
     if prior_table is not None:
         arr, hy = globals()["prior_table"](prior_table, hyper)
         keep += [arr, hy]

@@ -601,7 +601,7 @@ struct Engine {
         // are spent on spawns that fail -- cheap for a compiled likelihood (then the round trips per nursery dominate and
         // many chains per nursery pay: nlive / 2), dear for an expensive one (nlive / 4, at most 64).  Which one this is
         // is measured while the live points are generated; buffers are sized for the larger choice.
-        cb_auto_batch = c.batch <= 0 && !c.sequential_rng && (like.kind == PC_LIKE_CALLBACK || (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE));
+        cb_auto_batch = c.batch <= 0 && !c.sequential_rng && (like.kind == PC_LIKE_CALLBACK || (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE && prior.kind != PCHIP_PRIOR_SOURCE));
         if (cb_auto_batch) B_small = std::max(1, std::min(64, c.nlive / 4));
         S.B = B;
         S.maxc = c.do_clustering ? std::max(2, g_cap_clusters.load()) : 4;
@@ -636,11 +636,18 @@ struct Engine {
             const double *h = nullptr; long long n = 0;
             if (pc_rtc_source_data(like.source, &h, &n)) engine_fail(PC_RC_SETTINGS, "device source handle %d does not exist", like.source);
             if (nDer > PC_SRC_MAX_DERIVED) engine_fail(PC_RC_SETTINGS, "a device source likelihood writes at most %d derived parameters, not %d", PC_SRC_MAX_DERIVED, nDer);
-            if (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE) engine_fail(PC_RC_SETTINGS, "a device source likelihood needs a device prior (the uniform box), not a host-callback prior");
+            if (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE && prior.kind != PCHIP_PRIOR_SOURCE)
+                engine_fail(PC_RC_SETTINGS, "a device source likelihood needs a device prior (the uniform box, a table or its own source prior: prior.kind 1, 2 or 3), not a host-callback prior");
+            if (prior.kind == PCHIP_PRIOR_SOURCE && !pc_rtc_source_has_prior(like.source))
+                engine_fail(PC_RC_SETTINGS, "prior.kind = 3 (source prior): device source handle %d defines no pchip_prior_param -- make it with pchip_source_create_prior", like.source);
             S.src_id = like.source;
             src_terms = pc_rtc_source_terms(like.source) > 0;
             if (n > 0) { d_src = dalloc<double>((size_t)n); upload(d_src, h, sizeof(double) * (size_t)n); S.src_data = d_src; S.src_ndata = n; }
         }
+        // a source prior is the handle's own function, inside the sampling kernels: there is no host function for callback mode to call
+        if (prior.kind == PCHIP_PRIOR_SOURCE && like.kind != PC_LIKE_SOURCE)
+            engine_fail(PC_RC_SETTINGS, "prior.kind = 3 (source prior) needs a device source likelihood of the same handle (like.kind = %d is none): a prior-only source is not supported", like.kind);
+        if (prior.kind == PCHIP_PRIOR_SOURCE && c.feedback >= 1) { std::printf("prior source evaluated on the device, inside the sampling kernels (pchip_prior_param of source handle %d)\n", like.source); std::fflush(stdout); }
         if (like.kind == PC_LIKE_CORR_GAUSSIAN) {
             std::vector<double> T((size_t)D * D);
             for (int a = 0; a < D; ++a) for (int b = 0; b < D; ++b) T[(size_t)b * D + a] = like.invcov[(size_t)a * D + b];
@@ -666,8 +673,8 @@ struct Engine {
                 for (int i = 0; i < D; ++i) { box_lo[i] = ptab.e[i].par[0]; box_hi[i] = ptab.e[i].par[1]; }
                 prior_kind = 1; p_lo = box_lo.data(); p_hi = box_hi.data();
             }
-        } else if (prior.kind != 0 && prior.kind != 1) engine_fail(PC_RC_SETTINGS, "prior.kind = %d: 0 (callback), 1 (uniform box) or 2 (table)", prior.kind);
-        callback_mode = (like.kind == PC_LIKE_CALLBACK) || (prior_kind != 1 && prior_kind != PCHIP_PRIOR_TABLE);
+        } else if (prior.kind != 0 && prior.kind != 1 && prior.kind != PCHIP_PRIOR_SOURCE) engine_fail(PC_RC_SETTINGS, "prior.kind = %d: 0 (callback), 1 (uniform box), 2 (table) or 3 (source)", prior.kind);
+        callback_mode = (like.kind == PC_LIKE_CALLBACK) || (prior_kind != 1 && prior_kind != PCHIP_PRIOR_TABLE && prior_kind != PCHIP_PRIOR_SOURCE);
         if (callback_mode) {
             cb_like = like.fn; cb_prior = prior.kind == PCHIP_PRIOR_TABLE ? nullptr : prior.fn;      // (a table is its own host function: host_eval)
             if (!cb_like) engine_fail(PC_RC_SETTINGS, "callback mode needs a loglikelihood function pointer");
@@ -723,7 +730,7 @@ struct Engine {
             if (!sub_dims.empty()) { c_subdims = dalloc<int>(sub_dims.size()); upload(c_subdims, sub_dims.data(), sizeof(int) * sub_dims.size()); }
         }
         S.nhat = dalloc<double>((size_t)B * nr * D); S.nhat_w = dalloc<double>((size_t)B * nr);
-        const bool ms_pre = S.like.kind == PC_LIKE_CORR_GAUSSIAN && D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !(S.ablate & PC_ABL_FUNCTOR) && !pc_env().ms_pre_off && S.prior.kind != PCHIP_PRIOR_TABLE;
+        const bool ms_pre = S.like.kind == PC_LIKE_CORR_GAUSSIAN && D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !(S.ablate & PC_ABL_FUNCTOR) && !pc_env().ms_pre_off && S.prior.kind < PCHIP_PRIOR_TABLE;
         S.nhat_Ms = ms_pre ? dalloc<double>((size_t)B * nr * D) : nullptr;
         S.ch_My = ms_pre ? dalloc<double>((size_t)B * D) : nullptr;
         const bool split_off = pc_env().nhats_split_off;
@@ -1194,7 +1201,7 @@ struct Engine {
     }
 
     // what a sampling launch of this run alone is counted under besides its kernel (live points, nurseries)
-    PcLaunchTraits launch_traits() const { return PcLaunchTraits{pc_rtc_wanted(&S) != 0, src_terms, S.prior.kind == PCHIP_PRIOR_TABLE}; }
+    PcLaunchTraits launch_traits() const { return PcLaunchTraits{pc_rtc_wanted(&S) != 0, src_terms, S.prior.kind >= PCHIP_PRIOR_TABLE}; }
     PcUpdateFacts update_facts(int nph) const { return PcUpdateFacts{nph > 0, pc_update_fused_ok(&S, h_ctl->ncluster) != 0, h_ctl->ncluster}; }
 
     void do_update(bool deferred = false)
@@ -2075,7 +2082,7 @@ struct Engine {
     // what the cohort's launches for any device likelihood take (else the run launches for itself in between)
     bool cohort_general_ok() const
     {
-        return !pc_env().cohort_general_off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK && S.prior.kind != PCHIP_PRIOR_TABLE;
+        return !pc_env().cohort_general_off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK && S.prior.kind < PCHIP_PRIOR_TABLE;
     }
     // what is known when a nursery is about to be sampled (the launchers' predicates: asked here, once a nursery)
     PcNurseryFacts nursery_facts(unsigned batch) const
@@ -2745,6 +2752,33 @@ int pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const doub
     }
     if (rc) (void)hipGetLastError();
     (void)hipFree(d_tp); (void)hipFree(d_ti); (void)hipFree(d_c); (void)hipFree(d_t);
+    return rc;
+}
+
+// the prior of a source handle alone at n hypercube points: the handle's run-time module, k_prior_transform, one wavefront a point
+int pchip_source_prior_eval(int handle, const double *cubes, long n, int nDims, double *thetas)
+{
+    const double *h = nullptr; long long nd = 0;
+    if (pc_rtc_source_data(handle, &h, &nd)) { pc_abi_set_last_error(("pchip_source_prior_eval: device source handle " + std::to_string(handle) + " does not exist").c_str()); return 1; }
+    if (!pc_rtc_source_has_prior(handle)) { pc_abi_set_last_error(("pchip_source_prior_eval: device source handle " + std::to_string(handle) + " defines no pchip_prior_param (pchip_source_create_prior makes one that does)").c_str()); return 1; }
+    if (!cubes || !thetas || n < 1 || n > 0x7fffffffL || nDims < 1) { pc_abi_set_last_error("pchip_source_prior_eval: n >= 1 points, nDims >= 1, arrays for cube and theta"); return 1; }
+    if (nDims > 256) return 3;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
+    double *d_src = nullptr, *d_c = nullptr, *d_t = nullptr;
+    const size_t nb = sizeof(double) * (size_t)n * nDims;
+    int rc = 2;
+    pc_abi_set_last_error(nullptr);
+    if ((nd == 0 || (hipMalloc(&d_src, sizeof(double) * (size_t)nd) == hipSuccess && hipMemcpy(d_src, h, sizeof(double) * (size_t)nd, hipMemcpyHostToDevice) == hipSuccess)) &&
+        hipMalloc(&d_c, nb) == hipSuccess && hipMalloc(&d_t, nb) == hipSuccess && hipMemcpy(d_c, cubes, nb, hipMemcpyHostToDevice) == hipSuccess) {
+        PcState S;
+        std::memset(&S, 0, sizeof(S));
+        S.D = nDims; S.like.kind = PC_LIKE_SOURCE; S.prior.kind = PCHIP_PRIOR_SOURCE; S.src_id = handle; S.src_data = d_src; S.src_ndata = nd;
+        if (pc_launch_source_prior_eval(&S, (int)n, d_c, d_t, nullptr)) { rc = 1; pc_abi_set_last_error(pc_rtc_error() ? pc_rtc_error() : "pchip_source_prior_eval: the launch failed"); }
+        else if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(thetas, d_t, nb, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    }
+    if (rc == 2) (void)hipGetLastError();
+    (void)hipFree(d_src); (void)hipFree(d_c); (void)hipFree(d_t);
     return rc;
 }
 

@@ -108,6 +108,8 @@ const char *pc_rtc_error(void);
 int pc_rtc_source_data(int id, const double **data, long long *n);
 // the number of terms of a terms-form handle; 0: the plain form, or no such handle
 long pc_rtc_source_terms(int id);
+// 1: the handle's source defines pchip_prior_param as well (pchip_source_create_prior); 0: it does not, or no such handle
+int pc_rtc_source_has_prior(int id);
 // ---- pc_sample.hip -----------------------------------------------------------------------------------------
 // Launchers: 0: launched; 1: not this way (no kernel for this shape, or the run-time module failed: pc_rtc_error).
 // the sampling kernels come from the run-time module (a source likelihood, settings.ablate bit 15)
@@ -129,6 +131,8 @@ int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t s
 int pc_launch_prior_transform(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st);
 // pchip_source_eval: a source likelihood at n points (device pointers), by the handle's run-time module
 int pc_launch_source_eval(const PcState *S, int n, const double *thetas, double *logL, double *phi, hipStream_t st);
+// the prior of a source handle (prior.kind 3) at n points: k_prior_transform by name from the handle's module
+int pc_launch_source_prior_eval(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st);
 // ---- pc_slice_t.hip ----------------------------------------------------------------------------------------
 // lane = chain / lane = basis.  _ok: 1 where the kernels take the state; launchers: 0: launched; 1: not this way
 int pc_bases_t_ok(const PcState *S);

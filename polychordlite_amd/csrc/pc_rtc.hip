@@ -11,7 +11,13 @@
 // The terms form (pchip_source_create_terms): the source defines pchip_logl_term (the i-th term of a sum over the data, one lane per i) and
 // pchip_logl_finish (logL and the derived parameters from the finished sum) instead.  The form and the number of terms reach the kernels
 // as #defines in front of the library's text in that handle's unit (PCHIP_USER_TERMS, PCHIP_SRC_NTERMS): pc_sample.hip's wave-cooperative
-// evaluation is compiled in their place only.  settings.ablate bit 15 sends the built-in kinds the same way (a module without a user source): the test that
+// evaluation is compiled in their place only.
+//
+// A prior in the same source (pchip_source_create_prior): the text defines pchip_prior_param (theta[i] from the whole cube, one call per
+// parameter) next to the likelihood of either form; such a handle's unit gets PCHIP_USER_PRIOR in front, and a run with prior.kind =
+// PCHIP_PRIOR_SOURCE takes the table's kernel variants with that function behind the transform's one entry point (pc_sample.hip).
+//
+// settings.ablate bit 15 sends the built-in kinds the same way (a module without a user source): the test that
 // this path is the static kernel.
 //
 // libhiprtc is opened with dlopen: without it the library loads and the built-ins run; a source run then fails with a message.
@@ -70,6 +76,7 @@ struct Source {
     std::string text;                      // the user's source, behind the #define lines of its options
     std::vector<double> data;
     long nterms = 0;                       // > 0: the terms form (pchip_logl_term / pchip_logl_finish), the sum's length
+    bool has_prior = false;                // the source defines pchip_prior_param as well (pchip_source_create_prior)
 };
 
 // a code object of one kernel variant for one architecture: compiled once, loaded on every device of that architecture
@@ -156,12 +163,14 @@ int compile(const Source *s, const std::string &unit, const std::vector<std::str
 }
 
 // the translation unit of the sampling kernels: the library's kernels (pc_sample.hip declares pchip_loglikelihood under PCHIP_USER_SOURCE),
-// then the user's text -- its macros and pragmas reach nothing of the library's.  A terms handle: its form and its loop bound in front.
+// then the user's text -- its macros and pragmas reach nothing of the library's.  A terms handle: its form and its loop bound in front;
+// a handle with a prior (pchip_source_create_prior): PCHIP_USER_PRIOR in front.
 std::string kernel_unit(const Source *s)
 {
+    const std::string prior = s && s->has_prior ? "#define PCHIP_USER_PRIOR 1\n" : "";
     if (s && s->nterms > 0)
-        return "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
-    return s ? std::string("#define PCHIP_USER_SOURCE 1\n#include \"pc_sample.hip\"\n#include \"") + USER_NAME + "\"\n"
+        return prior + "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
+    return s ? prior + "#define PCHIP_USER_SOURCE 1\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n"
              : std::string("#include \"pc_sample.hip\"\n");
 }
 
@@ -178,6 +187,19 @@ const char *const PROBE_UNIT_TERMS =
     "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
     "{ out[0] = pchip_logl_finish(pchip_logl_term(th, nDims, data, ndata, i), th, phi, nDims, nDerived, data, ndata); }\n"
     "#include \"pchip_user_source.h\"\n";
+
+// ... and of pchip_source_create_prior: the probe of the handle's form, then pchip_prior_param behind its declaration, called as well
+const char *const PROBE_PRIOR_DECL =
+    "__device__ double pchip_prior_param(const double *cube, int i, int nDims, const double *data, long ndata);\n";
+const char *const PROBE_PRIOR_CALL = "out[0] += pchip_prior_param(th, 0, nDims, data, ndata); }\n";
+std::string probe_unit(long nterms, bool prior)
+{
+    std::string u = nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT;
+    if (!prior) return u;
+    const size_t close = u.rfind(" }\n");        // the end of pchip_probe's body: the call goes in front of it
+    u.replace(close, 3, std::string(" ") + PROBE_PRIOR_CALL);
+    return PROBE_PRIOR_DECL + u;
+}
 
 std::string strip_parens(const char *expr)
 {
@@ -286,9 +308,17 @@ long pc_rtc_source_terms(int id)
     return it == G.src.end() ? 0 : it->second->nterms;
 }
 
-// pchip_source_create[_terms]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
+int pc_rtc_source_has_prior(int id)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    auto it = G.src.find(id);
+    return it != G.src.end() && it->second->has_prior ? 1 : 0;
+}
+
+// pchip_source_create[_terms | _prior]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
 // nterms > 0: the terms form.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
-int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, std::string *log)
+int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, bool prior, std::string *log)
 {
     if (!source) { *log = "pchip_source_create: no source"; return -1; }
     if (ndata < 0 || (ndata > 0 && !data)) { *log = "pchip_source_create: ndata > 0 needs a data block"; return -1; }
@@ -298,7 +328,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     auto s = std::make_shared<Source>();
     s->text = defs + "#line 1\n" + source;
     if (ndata > 0) s->data.assign(data, data + ndata);
-    s->nterms = nterms;
+    s->nterms = nterms; s->has_prior = prior;
     std::string arch = "gfx950";
     int dev = 0, ndev = 0;
     if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&dev) == hipSuccess) {
@@ -307,7 +337,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     }
     (void)hipGetLastError();
     std::vector<char> code; std::vector<std::string> lowered;
-    if (compile(s.get(), nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT, { "pchip_probe" }, arch, code, lowered, *log)) return -1;
+    if (compile(s.get(), probe_unit(nterms, prior), { "pchip_probe" }, arch, code, lowered, *log)) return -1;
     Registry &G = reg();
     std::lock_guard<std::mutex> g(G.m);
     const int id = G.next++;
@@ -322,7 +352,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
 extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata)
 {
     std::string log;
-    const int id = pc_rtc_source_create(source, options, data, ndata, 0, &log);
+    const int id = pc_rtc_source_create(source, options, data, ndata, 0, false, &log);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }
@@ -332,7 +362,18 @@ extern "C" int pchip_source_create_terms(const char *source, const char *options
     std::string log;
     int id = -1;
     if (nterms < 1) log = "pchip_source_create_terms: nterms = " + std::to_string(nterms) + " -- the sum needs at least one term (nterms >= 1)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, &log);
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, false, &log);
+    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
+    return id;
+}
+
+// likelihood and prior in one source and one handle: nterms == 0 the plain form of likelihood, nterms >= 1 the terms form
+extern "C" int pchip_source_create_prior(const char *source, const char *options, const double *data, long ndata, long nterms)
+{
+    std::string log;
+    int id = -1;
+    if (nterms < 0) log = "pchip_source_create_prior: nterms = " + std::to_string(nterms) + " -- 0 (the plain form) or the number of terms (nterms >= 1)";
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, true, &log);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }

@@ -121,6 +121,53 @@ __device__ __forceinline__ void pc_table_theta(const LaneTable<DPL> &lt, const d
     }
 }
 
+// The one entry point of the transform: every kernel that turns a cube into theta behind a prior table goes through PC_PRIOR_LOAD (the
+// head of a chain) and PC_PRIOR_THETA (every trial).  Without a user prior they ARE pc_table_load and pc_table_theta, token for token.
+#ifdef PCHIP_USER_PRIOR
+// A user's prior written as device source (PcPrior::kind == 3, pchip_source_create_prior; pc_rtc.hip defines PCHIP_USER_PRIOR in front of
+// this text in such a handle's unit): theta[i] = pchip_prior_param(cube, i, ...), one call per parameter, lane = parameter.  The function
+// may read ANY coordinate of the cube (a dependent prior loops in its lane, as the sorted_ blocks above do), so the cube is staged in the
+// wave's LDS scratch first: write / barrier / read / barrier, the shape of the table's permuted gather.  Only ever called for points
+// inside the unit cube (calculate.f90:36-38 stays in front, where it is for a table).
+__device__ double pchip_prior_param(const double *cube, int i, int nDims, const double *data, long ndata);
+
+template <int DPL>
+__device__ __forceinline__ void pc_source_theta(const PcState &S, const double (&cube)[DPL], double (&th)[DPL], int lane, double *ybuf)
+{
+    const int D = S.D;
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) if (lane + 64 * k < D) ybuf[lane + 64 * k] = cube[k];
+    __syncthreads();                              // one wave per workgroup: cheap
+#pragma unroll
+    for (int k = 0; k < DPL; ++k)
+        th[k] = (lane + 64 * k < D) ? pchip_prior_param(ybuf, lane + 64 * k, D, S.src_data, (long)S.src_ndata) : 0.0;
+    __syncthreads();                              // ... before the likelihood re-uses ybuf for theta
+}
+// S.prior.kind is a kernel argument: the branch is wave-uniform, and a table (kind 2) run of such a handle takes pc_table_theta as ever.
+// A source prior has no table: S.prior.lo / .hi are null and nothing is loaded.
+template <int DPL>
+__device__ __forceinline__ void pc_prior_load(const PcState &S, int lane, LaneTable<DPL> &lt)
+{
+    if (S.prior.kind == 3) {
+        lt.mask = 0u;
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) { lt.type[k] = 0; lt.pos[k] = 0; lt.len[k] = 0; lt.hyp[k] = 0; lt.p0[k] = 0.0; lt.p1[k] = 0.0; lt.p2[k] = 0.0; }
+    } else pc_table_load<DPL>(S, lane, lt);
+}
+template <int DPL>
+__device__ __forceinline__ void pc_prior_theta(const PcState &S, const LaneTable<DPL> &lt, const double (&cube)[DPL], double (&th)[DPL], int lane,
+                                               double *ybuf)
+{
+    if (S.prior.kind == 3) pc_source_theta<DPL>(S, cube, th, lane, ybuf);
+    else pc_table_theta<DPL>(lt, cube, th, lane, ybuf);
+}
+#define PC_PRIOR_LOAD(DPL, S, lane, lt) pc_prior_load<DPL>(S, lane, lt)
+#define PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf) pc_prior_theta<DPL>(S, lt, cube, th, lane, ybuf)
+#else
+#define PC_PRIOR_LOAD(DPL, S, lane, lt) pc_table_load<DPL>(S, lane, lt)
+#define PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf) pc_table_theta<DPL>(lt, cube, th, lane, ybuf)
+#endif
+
 #ifdef PCHIP_USER_SOURCE
 // the user's function (pc_rtc.hip): its text follows the library's in the run-time unit, so that none of its macros reach these kernels
 __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
@@ -354,8 +401,8 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
     }
     if constexpr (PT != 0) {
         LaneTable<DPL> lt;
-        pc_table_load<DPL>(S, lane, lt);
-        pc_table_theta<DPL>(lt, cube, th, lane, ybuf);
+        PC_PRIOR_LOAD(DPL, S, lane, lt);
+        PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf);
     }
 #ifdef PCHIP_USER_TERMS
     double tsum = 0.0;
@@ -395,11 +442,11 @@ __global__ __launch_bounds__(64) void k_prior_transform(PcState S, const double 
     const int lane = threadIdx.x, D = S.D;
     const size_t base = (size_t)blockIdx.x * D;
     LaneTable<DPL> lt;
-    pc_table_load<DPL>(S, lane, lt);
+    PC_PRIOR_LOAD(DPL, S, lane, lt);
     double cube[DPL], th[DPL];
 #pragma unroll
     for (int k = 0; k < DPL; ++k) cube[k] = (lane + 64 * k < D) ? cubes[base + lane + 64 * k] : 0.5;
-    pc_table_theta<DPL>(lt, cube, th, lane, ybuf);
+    PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf);
 #pragma unroll
     for (int k = 0; k < DPL; ++k) if (lane + 64 * k < D) thetas[base + lane + 64 * k] = th[k];
 }
@@ -1467,7 +1514,7 @@ __device__ __forceinline__ double eval_at(ChainCtx<DPL, NROWS, PT> &C, const dou
         for (int k = 0; k < DPL; ++k) th[k] = 0.0;
         return C.S.logzero;
     }
-    if constexpr (PT != 0) pc_table_theta<DPL>(C.tb, cube, th, C.lane, C.ybuf);
+    if constexpr (PT != 0) PC_PRIOR_THETA(DPL, C.S, C.tb, cube, th, C.lane, C.ybuf);
     else {
 #pragma unroll
     for (int k = 0; k < DPL; ++k) th[k] = C.ld.lo[k] + C.ld.span[k] * cube[k];
@@ -1504,20 +1551,20 @@ __device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS, PT> &C, const dou
         const bool oa = __ballot(outA) != 0ull, ob = __ballot(outB) != 0ull;
 #ifdef PCHIP_USER_TERMS
         if (kind == PC_LIKE_SOURCE) {
-            if (!oa) pc_table_theta<DPL>(C.tb, cA, thA, C.lane, C.ybuf);
-            if (!ob) pc_table_theta<DPL>(C.tb, cB, thB, C.lane, C.ybuf);
+            if (!oa) PC_PRIOR_THETA(DPL, C.S, C.tb, cA, thA, C.lane, C.ybuf);
+            if (!ob) PC_PRIOR_THETA(DPL, C.S, C.tb, cB, thB, C.lane, C.ybuf);
             like_pair_terms<DPL, NROWS, PT>(C, thA, thB, !oa, !ob, lA, lB);
             return;
         }
 #endif
         lA = C.S.logzero; lB = C.S.logzero;
         if (!oa) {
-            pc_table_theta<DPL>(C.tb, cA, thA, C.lane, C.ybuf);
+            PC_PRIOR_THETA(DPL, C.S, C.tb, cA, thA, C.lane, C.ybuf);
             lA = like_eval<DPL, NROWS, KIND>(C.S, thA, C.ld, C.lane, C.ybuf);
             if (lA > C.S.logzero) C.nlike++;
         }
         if (!ob) {
-            pc_table_theta<DPL>(C.tb, cB, thB, C.lane, C.ybuf);
+            PC_PRIOR_THETA(DPL, C.S, C.tb, cB, thB, C.lane, C.ybuf);
             lB = like_eval<DPL, NROWS, KIND>(C.S, thB, C.ld, C.lane, C.ybuf);
             if (lB > C.S.logzero) C.nlike++;
         }
@@ -1675,7 +1722,7 @@ extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, do
                                        hipStream_t st)
 {
     const size_t sh = sizeof(double) * S->D;
-    const bool table = S->prior.kind == 2;          // a prior table
+    const bool table = S->prior.kind >= 2;          // a prior table, or a source prior (kind 3: the same variants, from its handle's module)
     switch (pc_dpl(S->D) + (table ? 8 : 0)) {
     case 1: PC_LAUNCH((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
     case 2: PC_LAUNCH((k_generate_live<2>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
@@ -1813,7 +1860,7 @@ static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R
                       wpb_off = std::getenv("PC_SLICE_WPB_OFF") != nullptr;
     PcSlicePlan p{};
     const int D = S->D, nr = S->nr;
-    const bool table = S->prior.kind == 2;                      // a prior table: every likelihood through like_eval, no matrix in LDS
+    const bool table = S->prior.kind >= 2;                      // a prior table or a source prior (kind 3): every likelihood through like_eval, no matrix in LDS
     const bool special = S->ngrade > 1 || S->seq_mode;          // the two rare modes (pc_slice_fusable excludes both)
     const bool corr = S->like.kind == PC_LIKE_CORR_GAUSSIAN;
     if (D > 256 || (fused && !pc_slice_fusable(S))) return p;
@@ -1937,5 +1984,14 @@ extern "C" int pc_launch_source_eval(const PcState *S, int n, const double *thet
     if (S->like.kind != PC_LIKE_SOURCE || n < 1 || !dpl) return 1;
     const char *name = dpl == 1 ? "k_source_eval<1>" : (dpl == 2 ? "k_source_eval<2>" : "k_source_eval<4>");
     return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D, st, *S, thetas, logL, phi);
+}
+
+// pchip_source_prior_eval: the prior of a source handle at n points (device pointers) -- k_prior_transform of the handle's run-time module
+extern "C" int pc_launch_source_prior_eval(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st)
+{
+    const int dpl = pc_dpl(S->D);
+    if (S->like.kind != PC_LIKE_SOURCE || S->prior.kind != 3 || n < 1 || !dpl) return 1;
+    const char *name = dpl == 1 ? "k_prior_transform<1>" : (dpl == 2 ? "k_prior_transform<2>" : "k_prior_transform<4>");
+    return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D, st, *S, cubes, thetas);
 }
 #endif  // __HIPCC_RTC__

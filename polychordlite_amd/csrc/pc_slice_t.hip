@@ -713,7 +713,7 @@ extern "C" int pc_launch_bases_t_many(const PcState *S, const PcManyRec *dR, int
 extern "C" int pc_slice_t_ok(const PcState *S, int ncluster)
 {
     static const bool off = std::getenv("PC_SLICE_T_OFF") != nullptr;
-    if (off || ncluster != 1 || S->prior.kind == 2) return 0;      // (a prior table: k_slice's general variants)
+    if (off || ncluster != 1 || S->prior.kind >= 2) return 0;      // (a prior table or a source prior: k_slice's general variants)
     if (S->D > 24 || S->ngrade > 1 || S->seq_mode || S->nhat_raw == nullptr || S->nr > 255) return 0;
     if (S->like.kind != PC_LIKE_GAUSSIAN || (S->ablate & PC_ABL_FUNCTOR)) return 0;
     if (S->nDer > 0 && !pc_slice_phi_lds(S)) return 0;      // (k_slice would take the derived parameters' other summation order)

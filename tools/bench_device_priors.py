@@ -7,7 +7,16 @@ pchip_run (which synchronises the device), the legs alternated REPS times, evalu
   b  device_prior    the table evaluated inside the sampling kernels (pchip_prior.kind = 2);
   c  box_functor     the ceiling: the uniform box with the likelihood as a general device functor (settings.ablate bit 0).
 
-Writes JSON to argv[1] (default: stdout):  python tools/bench_device_priors.py profiles/device_priors.json"""
+Writes JSON to argv[1] (default: stdout):  python tools/bench_device_priors.py profiles/device_priors.json
+
+--source: the same shape with the likelihood as a device source (pchip_source_create_prior: one handle for all three legs), the prior
+three ways -- what a prior written as device source costs next to the table and the box:
+
+  a  table           twenty `gaussian` priors as a table (pchip_prior.kind = 2);
+  b  prior_source    the same transform, mu + sigma normcdfinv(cube_i), as the handle's pchip_prior_param (pchip_prior.kind = 3);
+  c  box             the uniform box (pchip_prior.kind = 1).
+
+python tools/bench_device_priors.py --source profiles/prior_source.json"""
 import ctypes as C
 import json
 import os
@@ -40,6 +49,29 @@ def legs():
     return {"host_prior": (La, Pa, 0, ka), "device_prior": (Lb, Pb, 0, kb), "box_functor": (Lc, Pc, 1, kc)}
 
 
+SOURCE = r"""
+__device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata)
+{
+    double s = 0.0, m = 0.0;
+    for (int i = 0; i < nDims; ++i) { const double z = (theta[i] - 0.5) / 0.1; s += z * z; m += theta[i]; }
+    for (int e = 0; e < nDerived; ++e) phi[e] = (e == 0) ? s : m * (double)e;
+    return -s / 2.0 + 1.3836465597893728 * (double)nDims;
+}
+__device__ double pchip_prior_param(const double *cube, int i, int nDims, const double *data, long ndata)
+{
+    return data[0] + data[1] * normcdfinv(cube[i]);
+}
+"""
+
+
+def source_legs():
+    h = api.source_create(SOURCE, data=[0.5, 1.0], prior=True)
+    La, Pa, ka = api.make_problem("source", D, NDER, source=h, prior_table=TABLE)
+    Lb, Pb, kb = api.make_problem("source", D, NDER, source=h, prior_source=True)
+    Lc, Pc, kc = api.make_problem("source", D, NDER, source=h)
+    return {"table": (La, Pa, 0, ka), "prior_source": (Lb, Pb, 0, kb), "box": (Lc, Pc, 0, kc)}
+
+
 def one(L, P, ablate):
     t = time.perf_counter()
     g = api.run(settings(ablate), L, P)
@@ -49,7 +81,10 @@ def one(L, P, ablate):
 
 
 def main():
-    lg = legs()
+    source = "--source" in sys.argv
+    if source:
+        sys.argv.remove("--source")
+    lg = source_legs() if source else legs()
     out = dict(shape=dict(nDims=D, nDerived=NDER, nlive=NLIVE, num_repeats=NR, prior="gaussian 0.5 1.0"), reps=REPS, runs={k: [] for k in lg})
     for k, (L, P, ab, keep) in lg.items():          # warm-up: module loads, block caches
         one(L, P, ab)
@@ -61,8 +96,15 @@ def main():
         out[k] = dict(evals_per_s_median=statistics.median(v), evals_per_s_min=min(v), evals_per_s_max=max(v),
                       wall_s_median=statistics.median(r["wall_s"] for r in rs))
     med = {k: out[k]["evals_per_s_median"] for k in lg}
-    out["device_over_host"] = med["device_prior"] / med["host_prior"]
-    out["device_over_box_functor"] = med["device_prior"] / med["box_functor"]
+    if source:
+        out["likelihood"] = "device source (Gaussian 0.5, 0.1), the same handle in every leg"
+        out["prior_source_over_table"] = med["prior_source"] / med["table"]
+        out["prior_source_over_box"] = med["prior_source"] / med["box"]
+        for k in lg:
+            out[k]["ms_per_run_median"] = 1e3 * out[k]["wall_s_median"]
+    else:
+        out["device_over_host"] = med["device_prior"] / med["host_prior"]
+        out["device_over_box_functor"] = med["device_prior"] / med["box_functor"]
     txt = json.dumps(out, indent=1)
     if len(sys.argv) > 1:
         open(sys.argv[1], "w").write(txt + "\n")
