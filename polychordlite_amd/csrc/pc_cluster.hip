@@ -2,25 +2,30 @@
 //
 // Restates do_clustering / NN_clustering / compute_knn / do_clustering_k / relabel
 // (src/polychord/clustering.f90:15-324, utils.F90:713-749) and the data-parallel parts of
-// add_cluster (run_time_info.f90:303-505):
-//   k_similarity   S_ab = r_a + r_b - 2 x_a.x_b over the cube coordinates (calculate.f90:94-109),
+// add_cluster (run_time_info.f90:303-505).
+//
+// Four device bodies.  The kernels around them launch each for all clusters of an update at once (_b: the first pass, a descriptor per
+// cluster), for all open parts of a level of the recursion (_sub: a descriptor per part), and for several runs in step (_many:
+// blockIdx.z or .y = run):
+//   similarity_body   S_ab = r_a + r_b - 2 x_a.x_b over the cube coordinates (calculate.f90:94-109),
 //                  one thread per pair, products and sums kept un-fused in dimension order so that the
 //                  neighbour ORDER equals the reference's;
-//   k_similarity_sub (and _b_sub, _b_many_sub)   the same over a list of cube coordinates, in list order: the sub-dimension
+//   similarity_sub_body (k_similarity_b_sub, _b_many_sub)   the same over a list of cube coordinates, in list order: the sub-dimension
 //                  pass (settings%sub_clustering_dimensions, nested_sampling.F90:352-367);
-//   k_knn_sort     compute_knn for every row of a (sub)set at once: the insertion rule of
+//   knn_sort_body  compute_knn for every row of a (sub)set at once: the insertion rule of
 //                  clustering.f90:156-172 (first slot with a strictly larger distance) is a stable sort
 //                  by (distance, index); one workgroup sorts one row in LDS (bitonic), which also makes
 //                  the "double k and recompute" step of NN_clustering free;
-//   k_nn_cluster   one workgroup runs the n = 2..k loop of NN_clustering (:53-76): connected components
+//   nn_cluster_body   one workgroup runs the n = 2..k loop of NN_clustering (:53-76): connected components
 //                  of the "i in j's n-list or j in i's" graph by min-label hooking + pointer jumping in
-//                  LDS, relabel by first appearance, early exits;
+//                  LDS, relabel by first appearance, early exits.
+// And three kernels of their own:
 //   k_rebuild_lists / k_cluster_stats / k_ph_rehome   the array side of add_cluster: list order from
 //                  (cluster, position) labels, per-cluster contour + live log-sum-exp, and phantoms
 //                  re-homed to the cluster of their nearest live point (identify_cluster,
 //                  run_time_info.f90:444-453, 913-949).
-// The recursion over found clusters (clustering.f90:80-95) and the O(ncluster) evidence split
-// (run_time_info.f90:458-503) are driven from the host (pc_engine.hip); they touch a few integers.
+// The recursion over found clusters (clustering.f90:80-95), level by level, and the O(ncluster) evidence split
+// (run_time_info.f90:458-503) are driven from the host (pc_split.h); they touch a few integers.
 #include "pc_state.h"
 #include "pc_launch.h"
 #include <cstdlib>
@@ -60,18 +65,10 @@ __device__ __forceinline__ void similarity_sub_body(const PcState &S, const int 
     }
 }
 
-__global__ __launch_bounds__(256) void k_similarity(PcState S, const int *pts, int n, double *Sm)
-{
-    similarity_body(S, pts, n, Sm, blockIdx.y * 256, gridDim.y * 256);
-}
-__global__ __launch_bounds__(256) void k_similarity_sub(PcState S, const int *dims, int nd, const int *pts, int n, double *Sm)
-{
-    similarity_sub_body(S, dims, nd, pts, n, Sm, blockIdx.y * 256, gridDim.y * 256);
-}
 // One descriptor per cluster that is looked at in an update: {cluster, points, offset of its n x n blocks, offset of its labels}.
 // The first pass of do_clustering (clustering.f90:253-324) over ALL clusters of an update is three launches with the cluster
 // in blockIdx.y instead of three launches and two host round trips per cluster (70 clusters, 130 updates per run at
-// BASELINE configs[2]); only a cluster in which the pass finds a split goes through the per-cluster path, with its recursion.
+// BASELINE configs[2]); the parts of a cluster in which the pass finds a split are re-clustered by the _sub kernels below.
 struct ClusDesc { int c, n, off2, off1; };
 __global__ __launch_bounds__(256) void k_similarity_b(PcState S, const ClusDesc *desc, double *Sm)
 {
@@ -110,10 +107,6 @@ __device__ __forceinline__ void knn_sort_body(const double *Sm, int nroot, const
             __syncthreads();
         }
     for (int i = tid; i < m; i += 256) knn[(size_t)a * m + i] = ki[i];
-}
-__global__ __launch_bounds__(256) void k_knn_sort(const double *Sm, int nroot, const int *gidx, int m, int npow2, int *knn)
-{
-    knn_sort_body(Sm, nroot, gidx, m, npow2, knn);
 }
 __global__ __launch_bounds__(256) void k_knn_sort_b(const double *Sm, const ClusDesc *desc, int *knn)
 {
@@ -207,10 +200,6 @@ __device__ __forceinline__ void nn_cluster_body(const int *knn, int m, int *labe
         __syncthreads();
     }
     if (tid == 0) { out[0] = num; sh_num = num; }
-}
-__global__ __launch_bounds__(1024) void k_nn_cluster(const int *knn, int m, int *labels_out, int *out)
-{
-    nn_cluster_body(knn, m, labels_out, out);
 }
 __global__ __launch_bounds__(1024) void k_nn_cluster_b(const int *knn, const ClusDesc *desc, int *labels, int *out)
 {
@@ -438,7 +427,7 @@ __global__ __launch_bounds__(1024) void k_nn_cluster_b_many(const PcManyRec *__r
     nn_cluster_body((const int *)r.p[PC_REC_KNN] + d.off2, d.n, (int *)r.p[PC_REC_LAB] + d.off1, (int *)r.p[PC_REC_OUT] + blockIdx.x);
 }
 
-// One level of NN_clustering's recursion for many parts at once (Engine::refine_partitions): part b = m points of a cluster, given by
+// One level of NN_clustering's recursion for many parts at once (PartRefiner, pc_split.h): part b = m points of a cluster, given by
 // their positions in the cluster's point order (pool + ioff), clustered on the sub-matrix of the cluster's similarity block the first
 // pass left at Sm + off2 (n x n).  Descriptor: {off2, n, ioff, m, koff}: its neighbour lists go to knn + koff (m x m), its labels to
 // labels + ioff, the number of clusters found to out[b].
@@ -528,49 +517,8 @@ void pc_launch_shift_mats(const PcState *S, int p, int nc, hipStream_t st)
     if (p < nc - 1) hipLaunchKernelGGL(k_shift_mats, dim3(1), dim3(256), 0, st, *S, p, nc);
 }
 
-// (dims / nd: the sub-dimension pass's coordinates, nd = 0 the full space -- in this and the batched launchers below)
-void pc_launch_similarity(const PcState *S, const int *pts, int n, double *Sm, const int *dims, int nd, hipStream_t st)
-{
-    if (nd > 0) hipLaunchKernelGGL(k_similarity_sub, dim3(n, (n + 1023) / 1024), dim3(256), 0, st, *S, dims, nd, pts, n, Sm);
-    else hipLaunchKernelGGL(k_similarity, dim3(n, (n + 1023) / 1024), dim3(256), 0, st, *S, pts, n, Sm);
-}
-
-int pc_launch_knn_cluster(const double *Sm, int nroot, const int *gidx, int m, int *knn, int *labels, int *out, hipStream_t st)
-{
-    int npow2 = 2;
-    while (npow2 < m) npow2 <<= 1;
-    const size_t sh = (size_t)npow2 * 12;
-    const size_t sh2 = (size_t)m * 12 + 64;
-    if (sh > 160 * 1024 || sh2 > 150 * 1024) return 1;
-    pc_need_dyn_lds((const void *)k_knn_sort, sh);
-    pc_need_dyn_lds((const void *)k_nn_cluster, sh2);
-    hipLaunchKernelGGL(k_knn_sort, dim3(m), dim3(256), sh, st, Sm, nroot, gidx, m, npow2, knn);
-    hipLaunchKernelGGL(k_nn_cluster, dim3(1), dim3(1024), sh2, st, knn, m, labels, out);
-    return 0;
-}
-
-// first pass over `nd` clusters at once (descriptors on the device, host copy for the grid): out[k] = clusters found in the k-th
-int pc_launch_knn_cluster_batch(const PcState *S, const int *h_desc, const int *d_desc, int nd, double *Sm, int *knn, int *labels, int *out,
-                                const int *dims, int ndims, hipStream_t st)
-{
-    if (nd <= 0) return 0;
-    int nmax = 0;
-    for (int k = 0; k < nd; ++k) nmax = h_desc[4 * k + 1] > nmax ? h_desc[4 * k + 1] : nmax;
-    int npow2 = 2;
-    while (npow2 < nmax) npow2 <<= 1;
-    const size_t sh = (size_t)npow2 * 12, sh2 = (size_t)nmax * 12 + 64;
-    if (sh > 160 * 1024 || sh2 > 150 * 1024) return 1;
-    pc_need_dyn_lds((const void *)k_knn_sort_b, sh);
-    pc_need_dyn_lds((const void *)k_nn_cluster_b, sh2);
-    const ClusDesc *dd = (const ClusDesc *)d_desc;
-    if (ndims > 0) hipLaunchKernelGGL(k_similarity_b_sub, dim3(nmax, nd), dim3(256), 0, st, *S, dims, ndims, dd, Sm);
-    else hipLaunchKernelGGL(k_similarity_b, dim3(nmax, nd), dim3(256), 0, st, *S, dd, Sm);
-    hipLaunchKernelGGL(k_knn_sort_b, dim3(nmax, nd), dim3(256), sh, st, (const double *)Sm, dd, knn);
-    hipLaunchKernelGGL(k_nn_cluster_b, dim3(nd), dim3(1024), sh2, st, (const int *)knn, dd, labels, out);
-    return 0;
-}
-
-// the same with the largest cluster given (no host copy of the descriptors at hand: a record of the runs in step launched on its own)
+// first pass over `nd` clusters at once, the largest of nmax points (descriptors on the device): out[k] = clusters found in the k-th.
+// (dims / ndims: the sub-dimension pass's coordinates, ndims = 0 the full space -- in this and the launchers below)
 int pc_launch_knn_cluster_batch_dev(const PcState *S, const int *d_desc, int nd, int nmax, double *Sm, int *knn, int *labels, int *out,
                                     const int *dims, int ndims, hipStream_t st)
 {
@@ -587,6 +535,14 @@ int pc_launch_knn_cluster_batch_dev(const PcState *S, const int *d_desc, int nd,
     hipLaunchKernelGGL(k_knn_sort_b, dim3(nmax, nd), dim3(256), sh, st, (const double *)Sm, dd, knn);
     hipLaunchKernelGGL(k_nn_cluster_b, dim3(nd), dim3(1024), sh2, st, (const int *)knn, dd, labels, out);
     return 0;
+}
+// the same with the host's copy of the descriptors at hand: the largest cluster is found here
+int pc_launch_knn_cluster_batch(const PcState *S, const int *h_desc, const int *d_desc, int nd, double *Sm, int *knn, int *labels, int *out,
+                                const int *dims, int ndims, hipStream_t st)
+{
+    int nmax = 0;
+    for (int k = 0; k < nd; ++k) nmax = h_desc[4 * k + 1] > nmax ? h_desc[4 * k + 1] : nmax;
+    return pc_launch_knn_cluster_batch_dev(S, d_desc, nd, nmax, Sm, knn, labels, out, dims, ndims, st);
 }
 int pc_launch_knn_cluster_batch_many(const PcState *S, const PcManyRec *dR, int R, int nd_max, int nmax, int any_sub, hipStream_t st)
 {

@@ -447,6 +447,8 @@ static double h_uniform(uint32_t k0, uint32_t k1, uint32_t dom, uint32_t shi, ui
 
 #include "pc_cohort.h"      // Cohort: the launches of the runs in step, written down and made once for all of them (the table of stages)
 
+#include "pc_split.h"       // ClusterUpdate: the host's half of a clustering update -- first pass, recursion level by level, add_cluster
+
 // adds its lifetime to one of the counters below
 struct DbgSpan {
     std::atomic<long long> &ns; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -508,9 +510,9 @@ struct Engine {
     PcPriorTable ptab; bool have_ptab = false;      // prior.kind == PCHIP_PRIOR_TABLE: checked copy (the host function of callback mode; what went to the device)
     double *d_lo = nullptr, *d_hi = nullptr, *d_invcovT = nullptr, *d_mean = nullptr, *d_src = nullptr;
     double *d_dynL = nullptr; int *d_dynN = nullptr; double *d_logn = nullptr;
-    // clustering scratch (allocated on first use)
-    double *c_Sm = nullptr; int *c_pts = nullptr, *c_gidx = nullptr, *c_knn = nullptr, *c_lab = nullptr, *c_out = nullptr, *c_cnt = nullptr;
-    unsigned *c_olduid = nullptr; int c_cap = 0;
+    ClusterUpdate<Engine> clus{*this};         // the host's half of a clustering update and its scratch on the device (pc_split.h)
+    Engine() = default; Engine(const Engine &) = delete; Engine &operator=(const Engine &) = delete;     // (clus refers to this Engine)
+    std::vector<int> sub_dims; int *c_subdims = nullptr;     // sub-dimension clustering: the run's coordinates (settings.sub_cluster_dims), on the device
     long nsplits = 0; int ncluster_peak = 1;
     bool src_terms = false;                    // a source likelihood in the terms form (pchip_source_create_terms)
     long path[PCHIP_PATH_COUNT] = {};          // launches per kernel variant (pchip_result.path): counted where the choice is made
@@ -1064,7 +1066,7 @@ struct Engine {
             dfree(p); p = q;
         };
         grow_mat(S.chol); grow_mat(S.cov);
-        if (c_cnt) { dfree(c_cnt); dfree(c_olduid); c_cnt = dalloc<int>(mn); c_olduid = dalloc<unsigned>(mn); }
+        clus.regrow_counts(mn);
         dfree(psum); dfree(pcnt); dfree(pcov); dfree(mean); dfree(count); cov_chunks_cap = 0;   // sized with maxc: covmats() reallocates
         S.maxc = mn;
     }
@@ -1270,76 +1272,23 @@ struct Engine {
         if (cfg.do_clustering) {
             // nested_sampling.F90:352-367: the sub-dimension pass first, then the full one over every cluster there is after it (the sizes
             // fetched again when the first pass split); the chains in the nursery follow the list through both (cmap_total)
-            if (sub_dims.empty()) do_clustering(cn);
+            if (sub_dims.empty()) clus.do_clustering(cn);
             else {
                 const int nold = h_ctl->ncluster;
                 std::vector<int> map1, map2;
                 path[PCHIP_PATH_SUBCLUSTER_PASSES]++;
                 const long s0 = nsplits;
-                bool found = do_clustering(cn, c_subdims, (int)sub_dims.size(), &map1);
+                bool found = clus.do_clustering(cn, c_subdims, (int)sub_dims.size(), &map1);
                 if (found) { path[PCHIP_PATH_SUBCLUSTER_SPLITS] += nsplits - s0; cn.clear(); }      // (the full pass asks for the sizes again)
-                found = do_clustering(cn, nullptr, 0, &map2) || found;
-                for (int &m : map1) m = m >= 0 ? map2[(size_t)m] : -1;        // the update's cluster j -> its place after both passes
-                if (found && !cfg.epoch_discard) remap_nursery(map1, nold);
+                found = clus.do_clustering(cn, nullptr, 0, &map2) || found;
+                cluster_map_compose(map1, map2);                              // the update's cluster j -> its place after both passes
+                if (found && !cfg.epoch_discard) clus.remap_nursery(map1, nold);
             }
         }
         hipEvent_t e1 = kt.begin(KT_COV);
         covmats(total, h_ctl->ncluster);
         kt.end(KT_COV, e1);
         write_resume();                               // nested_sampling.F90:337
-    }
-
-    // ---- kNN clustering (clustering.f90:253-324); heavy parts on the device (pc_cluster.hip)
-    static int relabel_host(std::vector<int> &lab)
-    {   // utils.F90:713-749
-        std::vector<int> map; std::vector<int> out(lab.size());
-        for (size_t i = 0; i < lab.size(); ++i) {
-            int f = -1;
-            for (size_t k = 0; k < map.size(); ++k) if (map[k] == lab[i]) { f = (int)k; break; }
-            if (f < 0) { map.push_back(lab[i]); f = (int)map.size() - 1; }
-            out[i] = f + 1;
-        }
-        lab.swap(out);
-        return (int)map.size();
-    }
-
-    // NN_clustering on the subset `gidx` (indices into the root cluster's point order); recursion
-    // over the found clusters as in clustering.f90:80-95
-    int nn_clustering(int nroot, const std::vector<int> &gidx, std::vector<int> &labels)
-    {
-        const int m = (int)gidx.size();
-        labels.assign(m, 1);
-        if (m <= 1) return 1;
-        send_raw(c_gidx, gidx.data(), sizeof(int) * m);
-        direct_op();
-        if (pc_launch_knn_cluster(c_Sm, nroot, c_gidx, m, c_knn, c_lab, c_out, st)) engine_fail(PC_RC_LDS, "cluster of %d points too large for the LDS kNN sort", m);
-        std::vector<int> numv;
-        fetch_raw(labels.data(), c_lab, sizeof(int) * m);
-        fetch(numv, (const int *)c_out, 1);
-        fetch_wait();
-        int num = numv[0];
-        if (num > 1) {
-            int ic = 1;
-            while (ic <= num) {
-                std::vector<int> pts, sub;
-                for (int j = 0; j < m; ++j) if (labels[j] == ic) { pts.push_back(j); sub.push_back(gidx[j]); }
-                std::vector<int> sl;
-                const int nnew = nn_clustering(nroot, sub, sl);
-                for (size_t a = 0; a < pts.size(); ++a) labels[pts[a]] = num + sl[a];
-                if (nnew == 1) ic++;
-                num = relabel_host(labels);
-            }
-        }
-        return num;
-    }
-
-    void ensure_cluster_scratch()
-    {
-        if (c_cap >= S.Ncap) return;
-        c_cap = S.Ncap;
-        c_Sm = dalloc<double>((size_t)c_cap * c_cap); c_pts = dalloc<int>(c_cap); c_gidx = dalloc<int>(c_cap);
-        c_knn = dalloc<int>((size_t)c_cap * c_cap); c_lab = dalloc<int>(c_cap); c_out = dalloc<int>(4);
-        c_cnt = dalloc<int>(S.maxc); c_olduid = dalloc<unsigned>(S.maxc);
     }
 
     // (in stream order, through pinned blocks: a run in step shares the wait with the others)
@@ -1351,257 +1300,6 @@ struct Engine {
         return v;
     }
     template <class T> void ul(T *p, const std::vector<T> &v) { send_raw(p, v.data(), sizeof(T) * v.size()); }
-
-    // What the host's half of a split reads: the points' (cluster, position) labels and the clusters' volumes, evidences, thresholds,
-    // ids, cross-volume rows -- the first nc entries / rows; what lies behind them stays what it is on the device.  Asked for with the
-    // verdicts of the update's first clustering pass (do_clustering: the same wait), it serves every split of the update: a split
-    // leaves on the host exactly what it sends up, so the splits of an update cost one wait each (the phantoms' counts), not two.
-    struct ClusterMirror {
-        bool valid = false; int maxc = 0;
-        std::vector<int> lc, lp; std::vector<double> Xp, ZXp, Zp, Zp2, ZpXp, thr, XQ; std::vector<unsigned> uid;
-    } cmir;
-    void cmir_ask()
-    {
-        const int nc = h_ctl->ncluster, maxc = S.maxc, Ncap = S.Ncap;
-        cmir.lc.resize(Ncap); cmir.lp.resize(Ncap);
-        for (std::vector<double> *v : {&cmir.Xp, &cmir.ZXp, &cmir.Zp, &cmir.Zp2, &cmir.ZpXp, &cmir.thr}) v->resize(maxc);
-        cmir.XQ.resize((size_t)maxc * maxc); cmir.uid.resize(maxc);
-        fetch_raw(cmir.lc.data(), S.live_cluster, sizeof(int) * Ncap); fetch_raw(cmir.lp.data(), S.live_pos, sizeof(int) * Ncap);
-        fetch_raw(cmir.Xp.data(), S.logXp, sizeof(double) * nc); fetch_raw(cmir.ZXp.data(), S.logZXp, sizeof(double) * nc);
-        fetch_raw(cmir.Zp.data(), S.logZp, sizeof(double) * nc); fetch_raw(cmir.Zp2.data(), S.logZp2, sizeof(double) * nc);
-        fetch_raw(cmir.ZpXp.data(), S.logZpXp, sizeof(double) * nc); fetch_raw(cmir.thr.data(), S.death_thr, sizeof(double) * nc);
-        fetch_raw(cmir.XQ.data(), S.XpXq, sizeof(double) * (size_t)nc * maxc); fetch_raw(cmir.uid.data(), S.cl_uid, sizeof(unsigned) * nc);
-        cmir.maxc = maxc;
-    }
-
-    // add_cluster (run_time_info.f90:303-505): cluster p splits into nnew clusters appended at the end
-    void add_cluster(int p, const std::vector<int> &labels, int nnew)
-    {
-        const int nc = h_ctl->ncluster, nold = nc - 1, ncn = nc + nnew - 1, Ncap = S.Ncap;
-        if (g_inject_fault.load() == 2) { g_inject_fault = 0; engine_fail(PC_RC_LIMIT, "more than %d clusters (injected)", nc); }
-        if (ncn > S.maxc) { grow_clusters(ncn); cmir.valid = false; }
-        const int maxc = S.maxc;
-        nsplits++;
-        // everything the host's half of the split reads: there since the update's first pass, or asked for now in ONE wait (a run in step
-        // shares it with the others)
-        if (!cmir.valid || cmir.maxc != maxc) { cmir_ask(); fetch_wait(); cmir.valid = true; }
-        std::vector<int> &lc = cmir.lc, &lp = cmir.lp; std::vector<double> &Xp = cmir.Xp, &ZXp = cmir.ZXp, &Zp = cmir.Zp, &Zp2 = cmir.Zp2, &ZpXp = cmir.ZpXp, &thr = cmir.thr, &XQ = cmir.XQ;
-        std::vector<unsigned> &uid = cmir.uid;
-        auto uln = [&](auto *dst, const auto &v, size_t n) { send_raw(dst, v.data(), sizeof(v[0]) * n); };
-        // position of every split point inside its new cluster = rank among equal labels in list order
-        std::vector<int> posnew(labels.size()), cnt(nnew, 0);
-        for (size_t a = 0; a < labels.size(); ++a) posnew[a] = cnt[labels[a] - 1]++;
-        for (int s = 0; s < Ncap; ++s) {
-            const int c = lc[s];
-            if (c < 0) continue;
-            if (c == p) { const int a = lp[s]; lc[s] = nold + labels[a] - 1; lp[s] = posnew[a]; }
-            else if (c > p) lc[s] = c - 1;
-        }
-        ul(S.live_cluster, lc); ul(S.live_pos, lp);
-        // per-cluster state: old clusters keep their order at 0..nold-1 (old_save/old_target, :371-376)
-        std::vector<unsigned> olduid(uid.begin(), uid.begin() + nc);
-        send_raw(c_olduid, olduid.data(), sizeof(unsigned) * nc);
-        const double logXp = Xp[p], logXp2 = XQ[(size_t)p * maxc + p], logZp = Zp[p], logZp2 = Zp2[p], logZXp = ZXp[p], logZpXp = ZpXp[p];
-        std::vector<double> rowpq;
-        for (int q = 0; q < nc; ++q) if (q != p) rowpq.push_back(XQ[(size_t)p * maxc + q]);
-        auto shift = [&](std::vector<double> &v) { for (int c = p; c < nc - 1; ++c) v[c] = v[c + 1]; };
-        shift(Xp); shift(ZXp); shift(Zp); shift(Zp2); shift(ZpXp); shift(thr);
-        for (int c = p; c < nc - 1; ++c) uid[c] = uid[c + 1];
-        {
-            std::vector<double> t(XQ);
-            for (int a = 0, na = 0; a < nc; ++a) { if (a == p) continue; for (int b = 0, nb = 0; b < nc; ++b) { if (b == p) continue; XQ[(size_t)na * maxc + nb] = t[(size_t)a * maxc + b]; nb++; } na++; }
-        }
-        // (the Cholesky factors and covariances of the clusters behind p move up a block: one launch, not two copies per cluster)
-        direct_op();
-        pc_launch_shift_mats(&S, p, nc, st);
-        for (int k = 0; k < nnew; ++k) { uid[nold + k] = h_ctl->next_cluster_uid++; thr[nold + k] = -PC_HUGE; }
-        uln(S.cl_uid, uid, (size_t)ncn); uln(S.death_thr, thr, (size_t)ncn);
-        // lists, contours, live log-sum-exp of every cluster; then the phantoms find their new homes
-        direct_op();
-        pc_launch_rebuild(&S, ncn, st);
-        pc_launch_ph_rehome(&S, h_ctl->nphantom, ncn, c_olduid, nc, c_cnt, st);
-        std::vector<int> nph, nlv;
-        fetch(nph, (const int *)c_cnt, ncn); fetch(nlv, (const int *)S.cl_n, ncn);
-        fetch_wait();
-        // 5) evidences and volumes split in proportion to nlive + nphantom (:458-503)
-        std::vector<double> logni(nnew), logni1(nnew);
-        for (int k = 0; k < nnew; ++k) { logni[k] = std::log((double)(nlv[nold + k] + nph[nold + k]) + 0.0); logni1[k] = std::log((double)(nlv[nold + k] + nph[nold + k]) + 1.0); }
-        double mx = logni[0];
-        for (int k = 1; k < nnew; ++k) mx = std::max(mx, logni[k]);
-        double sm = 0.0;
-        for (int k = 0; k < nnew; ++k) sm += std::exp(logni[k] - mx);
-        const double logn = mx + std::log(sm);
-        const double logn1 = logn > 0.0 ? logn + std::log(std::exp(0.0 - logn) + 1.0) : 0.0 + std::log(std::exp(logn - 0.0) + 1.0);
-        for (int k = 0; k < nnew; ++k) { split_child.push_back(uid[nold + k]); split_parent.push_back(olduid[p]); split_logfrac.push_back(logni[k] - logn); }
-        for (int k = 0; k < nnew; ++k) {
-            const int c = nold + k;
-            Xp[c] = logXp + logni[k] - logn; ZXp[c] = logZXp + logni[k] - logn; Zp[c] = logZp + logni[k] - logn;
-            Zp2[c] = logZp2 + logni[k] + logni1[k] - logn - logn1; ZpXp[c] = logZpXp + logni[k] + logni1[k] - logn - logn1;
-            for (int q = 0; q < nold; ++q) { XQ[(size_t)c * maxc + q] = rowpq[q] + logni[k] - logn; XQ[(size_t)q * maxc + c] = XQ[(size_t)c * maxc + q]; }
-        }
-        for (int a = 0; a < nnew; ++a)
-            for (int b = 0; b < nnew; ++b)
-                XQ[(size_t)(nold + a) * maxc + nold + b] = (a == b) ? logXp2 + logni[a] + logni1[a] - logn - logn1
-                                                                     : logXp2 + logni[a] + logni[b] - logn - logn1;
-        uln(S.logXp, Xp, (size_t)ncn); uln(S.logZXp, ZXp, (size_t)ncn); uln(S.logZp, Zp, (size_t)ncn); uln(S.logZp2, Zp2, (size_t)ncn); uln(S.logZpXp, ZpXp, (size_t)ncn);
-        uln(S.XpXq, XQ, (size_t)ncn * maxc);
-        h_ctl->ncluster = ncn;
-        ncluster_peak = std::max(ncluster_peak, ncn);
-    }
-
-    // do_clustering (clustering.f90:253-324).  First pass: every cluster with more than two points at once (three launches, the
-    // counts down and the verdicts back: two host waits per update); a cluster in which the pass finds more than one group
-    // goes through the per-cluster path with its recursion and add_cluster, in the reference's order
-    int *c_desc = nullptr, *c_bout = nullptr; int c_desc_cap = 0;
-    int *c_map = nullptr; int c_map_cap = 0;
-    std::vector<int> sub_dims; int *c_subdims = nullptr;     // sub-dimension clustering: the run's coordinates (settings.sub_cluster_dims), on the device
-    int *c_gdesc = nullptr, *c_gpool = nullptr, *c_glab = nullptr, *c_gout = nullptr; int c_g_cap = 0;
-    // NN_clustering's recursion (clustering.f90:80-95) level by level.  The reference re-clusters every cluster it finds, alone, until one
-    // pass over it finds a single cluster; the labels it returns are the final parts numbered by first appearance (relabel after every
-    // step, utils.F90:713-749).  A part's own clustering depends on its points only, so the order in which the parts are looked at does
-    // not matter: all parts of all clusters of this update that are still open are clustered in ONE launch per level (and, in step
-    // with other runs, together with theirs), on the similarity blocks the first pass left behind -- two or three waits per update
-    // instead of one per part.  desc: the first pass' descriptors {cluster, n, off2, off1}; out: clusters it found; lab0: its labels.
-    bool refine_partitions(const std::vector<int> &desc, const std::vector<int> &which, const std::vector<int> &out, const std::vector<int> &lab0,
-                           std::vector<std::vector<int>> &final_labels, std::vector<int> &final_num)
-    {
-        struct Part { int k; std::vector<int> idx; };              // k: descriptor; idx: positions in the cluster's point order
-        const int nd = (int)which.size();
-        std::vector<std::vector<std::vector<int>>> done((size_t)nd);       // final parts of every split cluster
-        std::vector<Part> work;
-        auto split_by = [&](int k, const std::vector<int> &idx, const int *lab /* 1-based, one per entry of idx */, int num) {
-            std::vector<std::vector<int>> parts((size_t)num);
-            for (size_t a = 0; a < idx.size(); ++a) parts[(size_t)lab[a] - 1].push_back(idx[a]);
-            for (auto &pt : parts) { if (pt.size() > 1) work.push_back(Part{k, std::move(pt)}); else if (!pt.empty()) done[(size_t)k].push_back(std::move(pt)); }
-        };
-        for (int k = 0; k < nd; ++k) {
-            if (out[k] <= 1) continue;
-            const int n = desc[4 * k + 1], o1 = desc[4 * k + 3];
-            std::vector<int> all((size_t)n);
-            for (int i = 0; i < n; ++i) all[i] = i;
-            split_by(k, all, lab0.data() + o1, out[k]);
-        }
-        while (!work.empty()) {
-            std::vector<Part> cur; cur.swap(work);
-            const int nb = (int)cur.size();
-            std::vector<int> gdesc((size_t)5 * nb), pool;
-            int mmax = 0; long long koff = 0;
-            for (int b = 0; b < nb; ++b) {
-                const int k = cur[b].k, m = (int)cur[b].idx.size();
-                gdesc[5 * b + 0] = desc[4 * k + 2]; gdesc[5 * b + 1] = desc[4 * k + 1]; gdesc[5 * b + 2] = (int)pool.size(); gdesc[5 * b + 3] = m; gdesc[5 * b + 4] = (int)koff;
-                pool.insert(pool.end(), cur[b].idx.begin(), cur[b].idx.end());
-                mmax = std::max(mmax, m); koff += (long long)m * m;
-            }
-            if (koff > (long long)c_cap * c_cap) return false;           // (cannot happen: the parts of a cluster are disjoint)
-            if (c_g_cap < std::max(nb, (int)pool.size())) {
-                dfree(c_gdesc); dfree(c_gpool); dfree(c_glab); dfree(c_gout);
-                c_g_cap = std::max(2 * std::max(nb, (int)pool.size()), S.Ncap);
-                c_gdesc = dalloc<int>((size_t)5 * c_g_cap); c_gpool = dalloc<int>(c_g_cap); c_glab = dalloc<int>(c_g_cap); c_gout = dalloc<int>(c_g_cap);
-            }
-            send_pre(c_gdesc, gdesc.data(), sizeof(int) * gdesc.size());
-            send_pre(c_gpool, pool.data(), sizeof(int) * pool.size());
-            // (not stage(): a run on its own fails where the launcher declines; in step the row's one-run launch is taken instead)
-            if (co) co->rec(rec_clusg(S, c_gdesc, c_Sm, c_gpool, c_knn, c_glab, c_gout, nb, mmax));
-            else if (pc_launch_knn_cluster_sub(c_gdesc, nb, mmax, c_Sm, c_gpool, c_knn, c_glab, c_gout, st)) engine_fail(PC_RC_LDS, "cluster of %d points too large for the LDS kNN sort", mmax);
-            std::vector<int> labs, nums;
-            fetch(labs, (const int *)c_glab, pool.size()); fetch(nums, (const int *)c_gout, (size_t)nb);
-            fetch_wait();
-            for (int b = 0; b < nb; ++b) {
-                if (nums[b] > 1) split_by(cur[b].k, cur[b].idx, labs.data() + gdesc[5 * b + 2], nums[b]);
-                else done[(size_t)cur[b].k].push_back(std::move(cur[b].idx));
-            }
-        }
-        for (int k = 0; k < nd; ++k) {
-            if (out[k] <= 1) continue;
-            const int n = desc[4 * k + 1], j = which[k];
-            std::vector<int> part_of((size_t)n, -1), newlab(done[(size_t)k].size(), 0);
-            for (size_t q = 0; q < done[(size_t)k].size(); ++q) for (int i : done[(size_t)k][q]) part_of[(size_t)i] = (int)q;
-            int next = 0;
-            final_labels[(size_t)j].assign((size_t)n, 0);
-            for (int i = 0; i < n; ++i) { int &l = newlab[(size_t)part_of[(size_t)i]]; if (l == 0) l = ++next; final_labels[(size_t)j][(size_t)i] = l; }
-            final_num[(size_t)j] = next;
-        }
-        return true;
-    }
-    // dims / nd: the coordinates of the sub-dimension pass (nd = 0: all).  cmap_out: the pass leaves the map of the list's clusters
-    // through it there and does not move the nursery's chains itself (two passes in one update: the caller composes the two maps)
-    bool do_clustering(std::vector<int> cn = std::vector<int>(), const int *dims = nullptr, int nd_sub = 0, std::vector<int> *cmap_out = nullptr)
-    {
-        ensure_cluster_scratch();
-        bool found = false;
-        cmir.valid = false;                              // (the contraction has moved volumes and evidences since the last update)
-        struct MirrorEnds { ClusterMirror &m; ~MirrorEnds() { m.valid = false; } } mirror_ends{cmir};
-        const int nold = h_ctl->ncluster;
-        if (c_desc_cap < nold) { dfree(c_desc); dfree(c_bout); c_desc_cap = std::max(2 * nold, 64); c_desc = dalloc<int>((size_t)4 * c_desc_cap); c_bout = dalloc<int>(c_desc_cap); }
-        if ((int)cn.size() != nold) cn = dl(S.cl_n, (size_t)nold);
-        std::vector<int> desc, verdict(nold, 1);
-        std::vector<std::vector<int>> final_labels((size_t)nold); std::vector<int> final_num((size_t)nold, 1);
-        bool refined = false;
-        {
-            int o1 = 0; long long o2 = 0;
-            std::vector<int> which;
-            for (int c = 0; c < nold; ++c)
-                if (cn[c] > 2) { desc.push_back(c); desc.push_back(cn[c]); desc.push_back((int)o2); desc.push_back(o1); which.push_back(c); o1 += cn[c]; o2 += (long long)cn[c] * cn[c]; }
-            const int nd = (int)which.size();
-            const bool batch_off = pc_env().cluster_batch_off;
-            if (nd > 0 && !batch_off && o2 <= (long long)c_cap * c_cap) {
-                send_pre(c_desc, desc.data(), sizeof(int) * desc.size());
-                int nmax1 = 0;
-                for (int k = 0; k < nd; ++k) nmax1 = std::max(nmax1, desc[4 * k + 1]);
-                // (in step with other runs: the first pass of all runs that update in this round in three launches)
-                // (not stage(): a run on its own launches from the host's copy of the descriptors, pc_launch_knn_cluster_batch)
-                if (co) co->rec(rec_clus1(S, c_desc, c_Sm, c_knn, c_lab, c_bout, dims, nd, nmax1, nd_sub));
-                else if (pc_launch_knn_cluster_batch(&S, desc.data(), c_desc, nd, c_Sm, c_knn, c_lab, c_bout, dims, nd_sub, st)) engine_fail(PC_RC_LDS, "a cluster too large for the LDS kNN sort");
-                std::vector<int> out, lab0;
-                fetch(out, (const int *)c_bout, (size_t)nd);
-                fetch(lab0, (const int *)c_lab, (size_t)o1);       // (the first pass' labels of every cluster: a few KB, the same wait)
-                cmir_ask();                                        // (and what a split will read, should the pass find one)
-                fetch_wait();
-                cmir.valid = true;
-                for (int k = 0; k < nd; ++k) verdict[which[k]] = out[k];
-                refined = refine_partitions(desc, which, out, lab0, final_labels, final_num);
-            } else for (int c = 0; c < nold; ++c) verdict[c] = cn[c] > 2 ? 2 : 1;      // (no first pass: look at every cluster)
-        }
-        int ic = 0;
-        std::vector<int> cmap((size_t)nold);             // where the update's cluster j is in the list now; -1: it was split
-        for (int j = 0; j < nold; ++j) cmap[(size_t)j] = j;
-        auto split_at = [&](int p) { for (int &m : cmap) { if (m == p) m = -1; else if (m > p) m -= 1; } };
-        for (int j = 0; j < nold; ++j) {                 // j: the cluster's number when the update began; ic: its number now
-            if (ic >= h_ctl->ncluster) break;
-            const int n = cn[j];
-            if (refined && n > 2 && verdict[j] > 1) {
-                // (the recursion of clustering.f90:80-95 was made for all clusters and all runs level by level: refine_partitions)
-                if (final_num[j] > 1) { found = true; add_cluster(ic, final_labels[j], final_num[j]); split_at(ic); }
-                else ic++;
-            } else if (n > 2 && verdict[j] > 1) {
-                direct_op();
-                HIPCHK(hipMemcpyAsync(c_pts, S.cl_list + (size_t)ic * S.Ncap, sizeof(int) * n, hipMemcpyDeviceToDevice, st));
-                pc_launch_similarity(&S, c_pts, n, c_Sm, dims, nd_sub, st);
-                std::vector<int> gidx(n), labels;
-                for (int i = 0; i < n; ++i) gidx[i] = i;
-                const int num = nn_clustering(n, gidx, labels);
-                if (num > 1) { found = true; add_cluster(ic, labels, num); split_at(ic); }
-                else ic++;
-            } else ic++;
-        }
-        if (found) {
-            if (cfg.epoch_discard) h_ctl->admin_epoch++;         // nested_sampling.F90:331-333 as written: every chain in flight is lost
-            else if (!cmap_out) remap_nursery(cmap, nold);
-            h_ctl->status = PC_ST_RUNNING;
-            send_raw(S.ctl, h_ctl, sizeof(PcCtl));
-        }
-        if (cmap_out) cmap_out->swap(cmap);
-        return found;
-    }
-    // the engine's rule (epoch_discard = 0): the chains seeded in clusters the update left alone stay in the nursery, under their new numbers
-    void remap_nursery(const std::vector<int> &cmap, int nold)
-    {
-        if (h_ctl->i_nursery <= 0) return;
-        if (c_map_cap < nold) { dfree(c_map); c_map_cap = std::max(2 * nold, 64); c_map = dalloc<int>(c_map_cap); }
-        send_raw(c_map, cmap.data(), sizeof(int) * (size_t)nold);
-        direct_op();
-        pc_launch_remap_chains(&S, c_map, nold, h_ctl->i_nursery, st);
-    }
 
     void covmats(int nph, int nc)
     {
@@ -2549,7 +2247,7 @@ struct Engine {
         dfree(d_x0s); dfree(d_prop); dfree(d_ans); dfree(d_decks);
         if (hp_prop) { hfree(hp_prop); hp_prop = nullptr; } if (hp_ans) { hfree(hp_ans); hp_ans = nullptr; } if (hp_need) { hfree(hp_need); hp_need = nullptr; }
         dfree(upd_part); dfree(upd_shift); upd_part_cap = 0;
-        dfree(c_gdesc); dfree(c_gpool); dfree(c_glab); dfree(c_gout); c_g_cap = 0; dfree(c_map); c_map_cap = 0; dfree(c_subdims); dfree(c_desc); dfree(c_bout); dfree(c_Sm); dfree(c_pts); dfree(c_gidx); dfree(c_knn); dfree(c_lab); dfree(c_out); dfree(c_cnt); dfree(c_olduid); c_cap = 0; c_desc_cap = 0;   // (the clustering scratch used to stay behind: 12 MB per clustered run)
+        clus.release(); dfree(c_subdims);   // (the clustering scratch used to stay behind: 12 MB per clustered run)
         for (void *h : staged_up) hfree(h);
         staged_up.clear();
         for (const Fetch &f : fetching) hfree(f.h);

@@ -40,9 +40,7 @@ int pc_launch_knn_cluster_sub(const int *d_desc, int nb, int mmax, const double 
 int pc_launch_knn_cluster_sub_many(const PcManyRec *dR, int R, int nb_max, int mmax, hipStream_t st);
 void pc_launch_remap_chains(const PcState *S, const int *map, int nold, int n, hipStream_t st);
 void pc_launch_shift_mats(const PcState *S, int p, int nc, hipStream_t st);
-// (dims / nd: the sub-dimension pass's coordinates, nd = 0 the full space -- in this and the batched launchers below)
-void pc_launch_similarity(const PcState *S, const int *pts, int n, double *Sm, const int *dims, int nd, hipStream_t st);
-int pc_launch_knn_cluster(const double *Sm, int nroot, const int *gidx, int m, int *knn, int *labels, int *out, hipStream_t st);
+// (nd: descriptors, one per cluster; dims / ndims: the sub-dimension pass's coordinates, ndims = 0 the full space -- in the batched launchers below)
 int pc_launch_knn_cluster_batch(const PcState *S, const int *h_desc, const int *d_desc, int nd, double *Sm, int *knn, int *labels, int *out, const int *dims, int ndims, hipStream_t st);
 int pc_launch_knn_cluster_batch_dev(const PcState *S, const int *d_desc, int nd, int nmax, double *Sm, int *knn, int *labels, int *out, const int *dims, int ndims, hipStream_t st);
 int pc_launch_knn_cluster_batch_many(const PcState *S, const PcManyRec *dR, int R, int nd_max, int nmax, int any_sub, hipStream_t st);

@@ -32,7 +32,6 @@ struct PcEnv {
     const int raw_depth = std::max(2, num("PC_RAW_DEPTH", 3));              // ring of bases buffers (the engine caps it at its ring)
     const bool copy_batch_off = set("PC_COPY_BATCH_OFF");                   // an update's small copies as hipMemcpyAsync calls, not one k_copy_batch
     const bool notify_off = set("PC_NOTIFY_OFF");                           // the round's outcome by copy + wait, not by the stamped host mirror
-    const bool cluster_batch_off = set("PC_CLUSTER_BATCH_OFF");             // clustering's passes over parts of clusters one launch a part
     const bool presort_off = set("PC_PRESORT_OFF");                         // clustered run on its own: k_sort_live in line, not beside k_slice
     const bool side_free = set("PC_SIDE_FREE"), side_ordered = set("PC_SIDE_ORDERED");      // the side stream's bases beside / behind k_slice whatever nDims
     const bool nn_lists_off = set("PC_NN_LISTS_OFF");                       // no candidate lists: every launch of a clustered run by the general kernel
