@@ -479,6 +479,18 @@ int  pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const p
  * theta [n][nDims] out (host memory) -- parity tests against polychord_hip_table_prior.  0, 1 (a bad table, message in
  * polychord_hip_last_error()), 2 (no device), 3 (nDims > 256). */
 int  pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const double *cube, double *theta, int device);
+/* kernel-level: the covariance and the Cholesky factor an update makes (calculate_covmats + calc_cholesky behind clean_phantoms) of given
+ * rows, by the run's own launchers -- accuracy tests against a long double reference (tests/test_update_factors.py).  Of `s` nDims,
+ * ablate and device are read.  Host arrays in: live [nlive][nDims] cube coordinates with a 0-based cluster per row; phantom
+ * [nph][nDims] with a logL and a cluster per row, cluster -1 = the row holds no phantom; threshold [ncluster]: a phantom counts unless
+ * logL < threshold of its cluster; shift [nDims] or NULL (the cube centre).  path 1 = the fused update (one cluster, nDims <= 128,
+ * nph >= 1; settings.ablate bits 1 and 16 choose compacting mode and the chain), path 0 = the general steps (clean, covmats).
+ * Out: cov, chol [ncluster][nDims][nDims]; count [ncluster], the rows that were counted; shift_out [nDims] (may be NULL), the next
+ * update's shift (path 0: the shift as given); *chol_suspect (may be NULL), PcCtl::chol_suspect after the update.
+ * 0, 1 (bad arguments, message in polychord_hip_last_error()), 2 (no device), 3 (nDims > 256), else a pchip_run code. */
+int  pchip_update_factors(const pchip_settings *s, int ncluster, int nlive, const double *live, const int *live_cluster,
+                          int nph, const double *phantom, const double *ph_logL, const int *ph_cluster, const double *threshold,
+                          const double *shift, int path, double *cov, double *chol, int *count, double *shift_out, int *chol_suspect);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,9 @@ def load():
     lib.polychord_hip_table_prior.restype = None
     lib.pchip_prior_transform.argtypes = [C.POINTER(Prior), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
     lib.pchip_prior_transform.restype = C.c_int
+    pi = C.POINTER(C.c_int); pd = C.POINTER(C.c_double)
+    lib.pchip_update_factors.argtypes = [C.POINTER(Settings), C.c_int, C.c_int, pd, pi, C.c_int, pd, pd, pi, pd, pd, C.c_int, pd, pd, pi, pd, pi]
+    lib.pchip_update_factors.restype = C.c_int
     # this mirror against the library that was loaded (the structs grow at their end: include/polychord_hip.h PCHIP_ABI_VERSION)
     lib.pchip_sizeof.argtypes = [C.c_char_p]
     lib.pchip_sizeof.restype = C.c_ulong
@@ -246,6 +249,36 @@ def prior_transform(entries, cubes, hyper=None, device=-1):
         msg = lib.polychord_hip_last_error()
         raise RuntimeError(f"pchip_prior_transform failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
     return th
+
+
+def update_factors(live, live_cluster, phantom, ph_logL, ph_cluster, threshold, path, shift=None, ablate=0, device=-1):
+    """pchip_update_factors: covariance and Cholesky factor of an update of the given rows, by the run's own launchers (path 1: the fused
+    update, path 0: clean + covmats).  live [nlive][nDims] with a 0-based cluster per row; phantom [nph][nDims] with logL and cluster
+    per row (-1: the row holds no phantom); threshold per cluster; shift [nDims] or None (the cube centre).
+    dict: cov, chol [ncluster][nDims][nDims], count [ncluster], shift [nDims], chol_suspect"""
+    lib = load()
+    x = np.ascontiguousarray(np.atleast_2d(live), dtype=np.float64)
+    D = x.shape[1]
+    ph = np.ascontiguousarray(np.reshape(phantom, (-1, D)), dtype=np.float64)
+    lc = np.ascontiguousarray(live_cluster, dtype=np.int32)
+    pl = np.ascontiguousarray(ph_logL, dtype=np.float64)
+    pc = np.ascontiguousarray(ph_cluster, dtype=np.int32)
+    thr = np.ascontiguousarray(np.atleast_1d(threshold), dtype=np.float64)
+    nc = thr.size
+    assert lc.shape == (x.shape[0],) and pl.shape == (ph.shape[0],) and pc.shape == (ph.shape[0],)
+    sh = None if shift is None else np.ascontiguousarray(shift, dtype=np.float64)
+    assert sh is None or sh.shape == (D,)
+    s = Settings(); lib.pchip_settings_default(C.byref(s), D, 0)
+    s.ablate, s.device = ablate, device
+    cov = np.full((nc, D, D), np.nan); chol = np.full((nc, D, D), np.nan)
+    count = np.full(nc, -1, dtype=np.int32); sho = np.full(D, np.nan); sus = C.c_int(-1)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    rc = lib.pchip_update_factors(C.byref(s), nc, x.shape[0], dptr(x), ip(lc), ph.shape[0], dptr(ph), dptr(pl), ip(pc), dptr(thr),
+                                  dptr(sh) if sh is not None else None, path, dptr(cov), dptr(chol), ip(count), dptr(sho), C.byref(sus))
+    if rc != 0:
+        msg = lib.polychord_hip_last_error()
+        raise RuntimeError(f"pchip_update_factors failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
+    return dict(cov=cov, chol=chol, count=count, shift=sho, chol_suspect=sus.value)
 
 
 def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, invcov=None, mean=None, logdet=0.0, source=0,

@@ -2453,6 +2453,106 @@ int pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const doub
     return rc;
 }
 
+// kernel-level entry for the accuracy tests of the update (tests/test_update_factors.py): covariance and Cholesky factor of given live
+// and phantom rows by the launchers of Engine::do_update's non-deferred branch -- no hooks, no clustering, no resume file.
+//   path 1: pc_launch_update_fused (one cluster, nDims <= 128, nph >= 1; pool mode unless settings.ablate has PC_ABL_NO_POOL; the chain
+//           with PC_ABL_UPDATE_CHAIN), the moments about `shift` (NULL: the cube centre);
+//   path 0: pc_launch_clean, the buffers swapped, the thresholds reset, pc_launch_covmats -- with one cluster on the row count from
+//           before the clean (the kernels clamp to the device's count, as in a run nobody watches), with more on the count after it.
+int pchip_update_factors(const pchip_settings *s, int ncluster, int nlive, const double *live, const int *live_cluster,
+                         int nph, const double *phantom, const double *ph_logL, const int *ph_cluster, const double *threshold,
+                         const double *shift, int path, double *cov, double *chol, int *count, double *shift_out, int *chol_suspect)
+{
+    if (!s || s->nDims < 1 || ncluster < 1 || nlive < 1 || !live || !live_cluster || nph < 0 || (nph > 0 && (!phantom || !ph_logL || !ph_cluster)) ||
+        !threshold || !cov || !chol || !count || (path != 0 && path != 1)) {
+        pc_abi_set_last_error("pchip_update_factors: nDims >= 1, ncluster >= 1, nlive >= 1 rows with their clusters, nph >= 0 rows with logL and cluster, a threshold per cluster, path 0 or 1, arrays for cov, chol and the counts");
+        return 1;
+    }
+    if (s->nDims > 256) return 3;
+    if (path == 1 && (ncluster != 1 || s->nDims > 128 || nph < 1)) { pc_abi_set_last_error("pchip_update_factors: the fused update (path 1) takes one cluster, nDims <= 128 and at least one phantom row"); return 1; }
+    for (int i = 0; i < nlive; ++i) if (live_cluster[i] < 0 || live_cluster[i] >= ncluster) { pc_abi_set_last_error("pchip_update_factors: a live row's cluster is 0 ... ncluster - 1"); return 1; }
+    for (int j = 0; j < nph; ++j) if (ph_cluster[j] < -1 || ph_cluster[j] >= ncluster) { pc_abi_set_last_error("pchip_update_factors: a phantom row's cluster is -1 (no phantom) or 0 ... ncluster - 1"); return 1; }
+    pchip_settings c;
+    pchip_settings_default(&c, s->nDims, 0);
+    c.nlive = nlive; c.nprior = nlive; c.batch = 1; c.num_repeats = 1; c.do_clustering = 0; c.seed = 1; c.device = s->device; c.ablate = s->ablate;
+    pchip_like like; std::memset(&like, 0, sizeof(like)); like.kind = PC_LIKE_GAUSSIAN; like.mu = 0.5; like.sigma = 1.0;
+    pchip_prior prior; std::memset(&prior, 0, sizeof(prior)); prior.kind = 1;
+    Engine E;
+    int rc = 0;
+    try {
+        E.setup(c, like, prior);
+        PcState &S = E.S;
+        const int nT = S.nT, D = S.D, DD = D * D;
+        HIPCHK(hipStreamSynchronize(E.st));                      // (the set-up's own launch writes the per-cluster arrays and the control block)
+        if (ncluster > S.maxc) E.grow_clusters(ncluster);
+        if (nph > S.Pcap) E.grow_phantoms(nph);
+        std::vector<double> rows((size_t)nlive * nT, 0.0);
+        for (int i = 0; i < nlive; ++i) std::memcpy(rows.data() + (size_t)i * nT, live + (size_t)i * D, sizeof(double) * D);
+        HIPCHK(hipMemcpy(S.live, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(S.live_cluster, live_cluster, sizeof(int) * nlive, hipMemcpyHostToDevice));
+        if (nph > 0) {
+            rows.assign((size_t)nph * nT, 0.0);
+            std::vector<unsigned> cu(nph); std::vector<unsigned long long> uid(nph);
+            for (int j = 0; j < nph; ++j) {
+                std::memcpy(rows.data() + (size_t)j * nT, phantom + (size_t)j * D, sizeof(double) * D);
+                cu[j] = ph_cluster[j] < 0 ? PC_CUID_NONE : (unsigned)ph_cluster[j]; uid[j] = (unsigned long long)j;
+            }
+            HIPCHK(hipMemcpy(S.phantom, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.ph_logL, ph_logL, sizeof(double) * nph, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.ph_cuid, cu.data(), sizeof(unsigned) * nph, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.ph_uid, uid.data(), sizeof(unsigned long long) * nph, hipMemcpyHostToDevice));
+        }
+        std::vector<unsigned> cuid(ncluster);
+        for (int k = 0; k < ncluster; ++k) cuid[k] = (unsigned)k;
+        HIPCHK(hipMemcpy(S.cl_uid, cuid.data(), sizeof(unsigned) * ncluster, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(S.death_thr, threshold, sizeof(double) * ncluster, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(&S.ctl->ncluster, &ncluster, sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(&S.ctl->nphantom, &nph, sizeof(int), hipMemcpyHostToDevice));
+        E.h_ctl->ncluster = ncluster; E.h_ctl->nphantom = nph;
+        if (path == 1) {
+            S.pool = (s->ablate & PC_ABL_NO_POOL) ? 0 : 1;
+            const size_t need = (size_t)pc_update_fused_blocks(&S, nph) * pc_update_fused_entries(&S);
+            E.upd_part_cap = need; E.upd_part = dalloc<double>(need);
+            E.upd_shift = dalloc<double>(D);
+            std::vector<double> sh(D, 0.5);
+            if (shift) sh.assign(shift, shift + D);
+            HIPCHK(hipMemcpy(E.upd_shift, sh.data(), sizeof(double) * D, hipMemcpyHostToDevice));
+            pc_launch_update_fused(&S, nph, E.keep, E.blk, E.d_total, E.ph2, E.phL2, E.phC2, E.phU2, E.upd_part, E.upd_shift, 0, E.st);
+            HIPCHK(hipStreamSynchronize(E.st));
+            HIPCHK(hipGetLastError());
+            // the rows that were counted: the count entries of the groups' records (k_upd_fold), whole numbers in doubles
+            const int G = pc_update_fused_grid(&S, nph, 0), ng = (G + 15) / 16, Ee = pc_update_fused_entries(&S), npair = D * (D + 1) / 2;
+            std::vector<double> rec((size_t)ng * Ee);
+            HIPCHK(hipMemcpy(rec.data(), E.upd_part + (size_t)G * Ee, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
+            double n = 0.0;
+            for (int g = 0; g < ng; ++g) n += rec[(size_t)g * Ee + npair + D];
+            count[0] = (int)n;
+            if (shift_out) HIPCHK(hipMemcpy(shift_out, E.upd_shift, sizeof(double) * D, hipMemcpyDeviceToHost));
+        } else {
+            S.pool = 0;
+            pc_launch_clean(&S, nph, E.keep, E.blk, E.d_total, E.ph2, E.phL2, E.phC2, E.phU2, nullptr, E.st);
+            int total = nph;
+            if (ncluster > 1) { HIPCHK(hipMemcpyAsync(&total, E.d_total, sizeof(int), hipMemcpyDeviceToHost, E.st)); HIPCHK(hipStreamSynchronize(E.st)); }
+            std::swap(S.phantom, E.ph2); std::swap(S.ph_logL, E.phL2); std::swap(S.ph_cuid, E.phC2); std::swap(S.ph_uid, E.phU2);
+            pc_launch_reset_thresholds(&S, E.st);
+            E.covmats(total, ncluster);
+            HIPCHK(hipStreamSynchronize(E.st));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpy(count, E.count, sizeof(int) * ncluster, hipMemcpyDeviceToHost));
+            if (shift_out) for (int d = 0; d < D; ++d) shift_out[d] = shift ? shift[d] : 0.5;      // (the steps take no shift)
+        }
+        HIPCHK(hipMemcpy(cov, S.cov, sizeof(double) * (size_t)ncluster * DD, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(chol, S.chol, sizeof(double) * (size_t)ncluster * DD, hipMemcpyDeviceToHost));
+        if (chol_suspect) HIPCHK(hipMemcpy(chol_suspect, &S.ctl->chol_suspect, sizeof(int), hipMemcpyDeviceToHost));
+    } catch (const EngineError &e) {
+        std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str());
+        (void)hipGetLastError();
+        rc = e.code;
+    }
+    E.destroy();
+    return rc;
+}
+
 // the prior of a source handle alone at n hypercube points: the handle's run-time module, k_prior_transform, one wavefront a point
 int pchip_source_prior_eval(int handle, const double *cubes, long n, int nDims, double *thetas)
 {

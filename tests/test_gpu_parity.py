@@ -92,7 +92,9 @@ RUNS = [  # kind D nDer nlive nr B general clustering
     # degenerate sizes: two live points, one repeat, more chains per nursery than live points (one live point has no
     # covariance: the reference's directions are 0/0 there, and so are the oracle's and the engine's)
     # (fewer live points than nDims + 1 is left out: the covariance is singular in exact arithmetic, so whether the
-    #  Cholesky pivot comes out <= 0 -- the scaled-identity fallback of utils.F90:633-638 -- is decided by round-off)
+    #  Cholesky pivot comes out <= 0 -- the scaled-identity fallback of utils.F90:633-638 -- is decided by round-off;
+    #  tests/test_update_factors.py holds those live sets at the kernels instead: a pinned coordinate, one row, n <= nDims -- a factor
+    #  within its backward bound or the scaled identity, nothing else -- in the fused update and in the general steps)
     ("gaussian", 1, 0, 2, 1, 1, 0, 0), ("gaussian", 4, 0, 7, 5, 64, 0, 1),
 ]
 
