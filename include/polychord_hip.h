@@ -270,6 +270,8 @@ enum { PCHIP_PATH_CONSUME_PAR = 0,      /* one cluster: the parallel contraction
        PCHIP_PATH_SOURCE_KERNELS = 19,      /* launches of run-time compiled sampling kernels (PCHIP_LIKE_SOURCE, settings.ablate bit 15) */
        PCHIP_PATH_DEVICE_PRIOR = 20,        /* sampling launches (live points, nurseries) that evaluated a prior table or a source prior on the device */
        PCHIP_PATH_SOURCE_TERMS = 21,        /* ... of those of slot 19, the launches whose kernels took the terms form of a source (pchip_source_create_terms) */
+       PCHIP_PATH_SLICE_STEP = 22,          /* runs in step: nurseries whose sampling kernel was launched ONCE for several runs (whichever kernel: k_slice_many,
+                                               k_slice_t_many); 0 for a run on its own, a group of one, a shape each run launches for itself */
        PCHIP_PATH_COUNT = 24 };
 
 /* snapshot handed to the update hook: what the reference's file writers see at every update
@@ -355,7 +357,7 @@ int  pchip_source_create_terms(const char *source, const char *options, const do
  * returned.  Same options rule, data block, handle space and pchip_source_destroy as pchip_source_create; a source that lacks one of
  * its functions fails here, by name.  The handle also runs under prior.kind 1 and 2, as one without a prior does.  A prior source for a
  * built-in or callback likelihood (a prior-only handle), pchip_run_repeats and the PolyChord-interface doors are not supported:
- * the run fails with a message.  Launches are counted in path[PCHIP_PATH_DEVICE_PRIOR] and path[PCHIP_PATH_SOURCE_KERNELS]. */
+ * the run fails with a message (several seeds in step: pchip_run_in_step).  Launches are counted in path[PCHIP_PATH_DEVICE_PRIOR] and path[PCHIP_PATH_SOURCE_KERNELS]. */
 int  pchip_source_create_prior(const char *source, const char *options, const double *data, long ndata, long nterms);
 /* The prior of such a handle at n hypercube points, cubes[n][nDims] -> thetas[n][nDims] (host arrays): one wavefront a point, through
  * the transform code of the sampling kernels.  Return codes as pchip_source_eval. */
@@ -437,6 +439,17 @@ int  pchip_run_repeats(const pchip_settings *s, const pchip_like *like, const pc
    for sixteen runs of the metric configuration) */
 int  pchip_run_repeats_ex(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds,
                           int ndevices, const int *devices, int max_in_flight, int want_rows, pchip_result *results, pchip_merged *merged);
+/* The runs in step for any problem that is wholly on the device: a built-in or a source likelihood (plain or terms form), under the uniform
+ * box, a prior table or the handle's own source prior (prior.kind 1, 2, 3), and settings.ablate bit 15.  Arguments, results, merge and
+ * return codes of pchip_run_repeats_ex; the seeds are dealt to the devices and their scheduler groups in the same way, up to max_in_flight
+ * runs of a device go round by round together, and every kernel of a round is launched once for all of them.  Every run is bit for bit
+ * pchip_run of its seed.  path[PCHIP_PATH_SLICE_STEP] counts a run's nurseries whose sampling launch was shared; a shape without a shared
+ * launch (nDims > 64 behind the bases kernels, parameter grades, the sequential stream, the correlated Gaussian) still goes round by round
+ * with the others and launches its own k_slice.  A host callback likelihood or a host prior (kind 0) is refused with code 1 and a message,
+ * before any device call; prior.kind 3 with a handle that defines no prior fails as pchip_run does.  (pchip_run_repeats keeps refusing a
+ * source handle and runs a table one thread per run.) */
+int  pchip_run_in_step(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds,
+                       int ndevices, const int *devices, int max_in_flight, int want_rows, pchip_result *results, pchip_merged *merged);
 
 /* ---- between processes: one rank per GPU, RCCL inside the library (dlopen of librccl.so at first use, none at link time).
  * Replaces the reference's MPI exchange (mpi_utils.F90:376-463 throw_baby / catch_babies, nested_sampling.F90:262-301) for

@@ -80,7 +80,7 @@ class Result(C.Structure):
 # pchip_result.path[]: launches per kernel variant (include/polychord_hip.h PCHIP_PATH_*)
 PATH_NAMES = ("consume_par", "consume_cl", "consume_general", "consume_fast", "killoff_par", "killoff_cl", "killoff_general",
               "killoff_fast", "update_fused", "update_steps", "slice_wave", "slice_lane", "nn_lists", "nn_fallbacks", "pool_mode",
-              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits", "source_kernels", "device_prior", "source_terms")
+              "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits", "source_kernels", "device_prior", "source_terms", "slice_step")
 
 
 _lib = None

@@ -41,7 +41,10 @@ struct Cohort {
     // deviates + bases launched a round before
     hipEvent_t ev_seq[4] = {nullptr, nullptr, nullptr, nullptr}; unsigned long long seq_launched = 0, seq_waited = 0; bool seq_open = false;
     int seq_for_next() const { return (int)(seq_launched + 1); }      // (the number the bases written down now will be launched under)
-    struct Rec { int kind; PcState S; void *p[10]; long long a[4]; int ia[6]; };      // a: what the runs of one launch must share; p, ia: each run's own (PcManyRec)
+    // a: what the runs of one launch must share; p, ia: each run's own (PcManyRec); note: host only, where flush() tells the run what became of a
+    // sampling record (null: nobody asks)
+    struct Note { long shared = 0; int failed = 0; };      // shared: sampling records launched once for several runs; failed: ... that no launcher took
+    struct Rec { int kind; PcState S; void *p[10]; long long a[4]; int ia[6]; Note *note; };
     // a row of the table of stages.  `one`: the launch for one run (what a run on its own makes at this point, where Engine::stage is used);
     // `many`: for cnt runs whose records start at d, f the first of them, fold[t] the fold of ia[folds[t].slot] over them; both return the
     // launcher's code (0: launched)
@@ -124,7 +127,11 @@ struct Cohort {
             if (x->S.Ncap != y->S.Ncap) return x->S.Ncap < y->S.Ncap;
             if (x->S.B != y->S.B) return x->S.B < y->S.B;
             if (x->S.pool != y->S.pool) return x->S.pool < y->S.pool;
-            return (x->S.prior.lo == nullptr) < (y->S.prior.lo == nullptr);
+            if ((x->S.prior.lo == nullptr) != (y->S.prior.lo == nullptr)) return (x->S.prior.lo == nullptr) < (y->S.prior.lo == nullptr);
+            // (one launch, one kernel: the runs share the likelihood's kind, its source handle and the prior's kind -- those of one call always do)
+            if (x->S.like.kind != y->S.like.kind) return x->S.like.kind < y->S.like.kind;
+            if (x->S.src_id != y->S.src_id) return x->S.src_id < y->S.src_id;
+            return x->S.prior.kind < y->S.prior.kind;
         };
         std::stable_sort(ord.begin(), ord.end(), shape_less);
         for (size_t i = 0; i < n; ++i) { hs[i].S = ord[i]->S; std::memcpy(hs[i].p, ord[i]->p, sizeof(ord[i]->p)); std::memcpy(hs[i].ia, ord[i]->ia, sizeof(ord[i]->ia)); }
@@ -155,8 +162,11 @@ struct Cohort {
                     const int v = ord[x]->ia[row.folds[t].slot];
                     fold[t] = row.folds[t].how == FOLD_MAX ? std::max(fold[t], v) : (fold[t] | (v > 0));
                 }
-            if (row.many(f, dr + i, cnt, fold, q) == 0) n_fused += cnt;
-            else for (size_t x = i; x < j; ++x) { (void)row.one(*ord[x], q); n_single++; }
+            if (row.many(f, dr + i, cnt, fold, q) == 0) {
+                n_fused += cnt;
+                if (cnt > 1) for (size_t x = i; x < j; ++x) if (ord[x]->note) ord[x]->note->shared++;
+            }
+            else for (size_t x = i; x < j; ++x) { if (row.one(*ord[x], q) != 0 && ord[x]->note) ord[x]->note->failed = 1; n_single++; }
             if (k == CK_BASES_NEXT && st2) {
                 HIPCHK(hipEventRecord(ev_next, st2)); next_pending = true;
                 if (!seq_open) { seq_launched++; seq_open = true; }
@@ -196,6 +206,7 @@ inline Cohort::Rec rec_of(int kind, const PcState &S)
     for (void *&x : r.p) x = nullptr;
     for (long long &x : r.a) x = 0;
     for (int &x : r.ia) x = 0;
+    r.note = nullptr;
     return r;
 }
 // the phantom clean (an update by steps, the compaction of the pool) over the nph rows in use
@@ -251,10 +262,11 @@ inline Cohort::Rec rec_slice(const PcState &S, unsigned batch, int nchains, int 
     r.ia[PC_REC_I_BASES_SEQ] = bases_seq;
     return r;
 }
-inline Cohort::Rec rec_slice_g(const PcState &S, unsigned batch, int nchains, bool fused, int bases_seq)
+inline Cohort::Rec rec_slice_g(const PcState &S, unsigned batch, int nchains, bool fused, int bases_seq, Cohort::Note *note = nullptr)
 {
     Cohort::Rec r = rec_nursery(CK_SLICE_G, S, batch, nchains);
     r.a[PC_REC_A_FUSED] = fused ? 1 : 0; r.ia[PC_REC_I_BASES_SEQ] = bases_seq;
+    r.note = note;
     return r;
 }
 inline Cohort::Rec rec_sort(const PcState &S) { return rec_of(CK_SORT, S); }
@@ -309,7 +321,10 @@ inline const Cohort::Stage &Cohort::stage(int kind)
         { CK_SLICE_G, "slice_g",
           PC_ONE { return r.a[PC_REC_A_FUSED] ? pc_launch_slice_fused(&r.S, (unsigned)r.ia[PC_REC_I_BATCH], (int)r.a[PC_REC_A_NCHAINS], st)
                                               : pc_launch_slice(&r.S, (unsigned)r.ia[PC_REC_I_BATCH], (int)r.a[PC_REC_A_NCHAINS], st); },
-          PC_MANY { return pc_launch_slice_many(&f.S, d, cnt, (int)f.a[PC_REC_A_NCHAINS], (int)f.a[PC_REC_A_FUSED], st); }, {} },
+          // (the user's own problem -- a device prior, a source likelihood --: the launcher with the prior kind in its variants and the terms form's LDS)
+          PC_MANY { return (f.S.prior.kind >= 2 || f.S.like.kind == PC_LIKE_SOURCE)
+                               ? pc_launch_slice_step(&f.S, d, cnt, (int)f.a[PC_REC_A_NCHAINS], (int)f.a[PC_REC_A_FUSED], st)
+                               : pc_launch_slice_many(&f.S, d, cnt, (int)f.a[PC_REC_A_NCHAINS], (int)f.a[PC_REC_A_FUSED], st); }, {} },
         { CK_BASES_NEXT, "bases_next",
           PC_ONE { return pc_launch_nhats_part(&r.S, (unsigned)r.ia[PC_REC_I_BATCH], (int)r.a[PC_REC_A_NCHAINS], 1, st, 1); },
           PC_MANY { return pc_launch_bases_t_many(&f.S, d, cnt, 0u, (int)f.a[PC_REC_A_NCHAINS], st); }, {} },

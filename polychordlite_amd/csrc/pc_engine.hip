@@ -516,6 +516,7 @@ struct Engine {
     long nsplits = 0; int ncluster_peak = 1;
     bool src_terms = false;                    // a source likelihood in the terms form (pchip_source_create_terms)
     long path[PCHIP_PATH_COUNT] = {};          // launches per kernel variant (pchip_result.path): counted where the choice is made
+    Cohort::Note step_note;                    // in step: what Cohort::flush made of this run's sampling records (PCHIP_PATH_SLICE_STEP; a launch nobody took)
     Timing tm;
     KTimer kt;
     int B = 0, dev = 0;
@@ -1780,7 +1781,8 @@ struct Engine {
     // what the cohort's launches for any device likelihood take (else the run launches for itself in between)
     bool cohort_general_ok() const
     {
-        return !pc_env().cohort_general_off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK && S.prior.kind < PCHIP_PRIOR_TABLE;
+        // (a device prior and a source likelihood included: pc_launch_slice_step, pc_cohort.h)
+        return !pc_env().cohort_general_off && S.ngrade <= 1 && !S.seq_mode && S.like.kind != PC_LIKE_CORR_GAUSSIAN && S.like.kind != PC_LIKE_CALLBACK;
     }
     // what is known when a nursery is about to be sampled (the launchers' predicates: asked here, once a nursery)
     PcNurseryFacts nursery_facts(unsigned batch) const
@@ -1813,6 +1815,7 @@ struct Engine {
             hipEvent_t e0 = kt.begin(KT_NHATS);
             const PcNurseryChoice ch = pc_choose_nursery(plan, nursery_facts(batch));
             pc_count(path, ch);
+            pc_count_step(path, ch);
             int bases_seq = 0;                        // in step with other runs: the number of the launch that drew this nursery's bases (0: in line)
             switch (ch.bases) {
             case PC_BASES_READY: case PC_BASES_PART1: case PC_BASES_PART1_STEP: {
@@ -1844,9 +1847,9 @@ struct Engine {
                 slice_callback(batch);
                 if (stop.load(std::memory_order_relaxed)) { r_rc = 5; return false; }
                 break;
-            case PC_SAMPLER_LANE: (void)stage(rec_slice(S, batch, B, bases_seq)); break;
+            case PC_SAMPLER_LANE: { Cohort::Rec r = rec_slice(S, batch, B, bases_seq); r.note = co ? &step_note : nullptr; (void)stage(r); break; }
             // (not stage(): no run on its own comes here -- its launch is the case below, which counts other paths and reports a failure)
-            case PC_SAMPLER_WAVE_STEP: co->rec(rec_slice_g(S, batch, B, ch.fused, ch.fused ? bases_seq : 0)); break;
+            case PC_SAMPLER_WAVE_STEP: co->rec(rec_slice_g(S, batch, B, ch.fused, ch.fused ? bases_seq : 0, &step_note)); break;
             case PC_SAMPLER_WAVE:
                 if (co) { co->flush(); co->wait_next(); }
                 if (ch.fused ? pc_launch_slice_fused(&S, batch, B, st) : pc_launch_slice(&S, batch, B, st)) {
@@ -1951,6 +1954,10 @@ struct Engine {
         {
             if (h_ctl->status == PC_ST_DONE) return false;
             if (h_ctl->status == PC_ST_ERROR) { std::fprintf(stderr, "polychord_hip: device error %d\n", h_ctl->error); r_rc = 2; return false; }
+            if (step_note.failed) {      // (in step: the sampling launch of the round before was taken neither for the group nor for this run alone)
+                if (pc_rtc_wanted(&S) && pc_rtc_error()) { std::fprintf(stderr, "polychord_hip: %s\n", pc_rtc_error()); r_rc = 1; return false; }
+                std::fprintf(stderr, "polychord_hip: nDims unsupported\n"); r_rc = 3; return false;
+            }
             bool fresh_nursery = false;
             if (h_ctl->i_nursery == 0) {
                 fresh_nursery = true;
@@ -2146,6 +2153,7 @@ struct Engine {
         out->ndead = h_ctl->ndead; out->nlike = h_ctl->nlike; out->niter = h_ctl->niter;
         out->nlike_failed = h_ctl->nlike_failed; out->ncluster_peak = ncluster_peak; out->epoch_discard = S.epoch_discard;
         path[PCHIP_PATH_NN_FALLBACKS] = (long)h_ctl->nn_fallbacks; path[PCHIP_PATH_POOL_MODE] = S.pool; path[PCHIP_PATH_DEFER_UPDATE] = S.defer_update;
+        path[PCHIP_PATH_SLICE_STEP] = step_note.shared;
         for (int k = 0; k < PCHIP_PATH_COUNT; ++k) out->path[k] = path[k];
         grade_counts(out->nlike_grade);
         out->ncluster = nc_end; out->ncluster_dead = h_ctl->ncluster_dead; out->nbatches = tm.batches;

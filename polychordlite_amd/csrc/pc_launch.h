@@ -122,6 +122,10 @@ int pc_slice_fusable(const PcState *S);
 int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchains, hipStream_t st);
 // R runs of a device in step (grid.y = run, every run the same shape).  1: a shape only the one-run launchers take
 int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st);
+// ... where the problem is the user's own -- a source likelihood, a prior table, a source prior --: the general variants with the prior kind
+// as a template argument and the terms form's LDS (a table of its own behind pc_slice_launch).  1: no shared launch for this shape (nDims > 64
+// unfused, grades, the sequential stream, the correlated Gaussian): each run then launches its own k_slice
+int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st);
 // ... and their directions for the shapes that do not split: 24 < nDims <= 64
 int pc_launch_nhats_many(const PcState *S, const PcManyRec *dR, int R, int nchains, hipStream_t st);
 int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t st);

@@ -760,13 +760,27 @@ int pchip_run_repeats(const pchip_settings *s, const pchip_like *like, const pch
     return pchip_run_repeats_ex(s, like, prior, nseeds, seeds, ndevices, devices, max_in_flight, 1, results, merged);
 }
 
-int pchip_run_repeats_ex(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds,
-                         int ndevices, const int *devices, int max_in_flight, int want_rows, pchip_result *results, pchip_merged *merged)
+// One body for the two doors.  in_step = false: pchip_run_repeats[_ex], which refuses a source handle and takes the runs in step for the box
+// alone (a table: one thread per run) -- both pinned by its tests.  in_step = true: pchip_run_in_step, any problem that is wholly on the device.
+static int run_repeats_body(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds,
+                            int ndevices, const int *devices, int max_in_flight, int want_rows, pchip_result *results, pchip_merged *merged, bool in_step)
 {
     using clk = std::chrono::steady_clock;
     if (nseeds < 1) return 1;
-    if (like && (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & PC_ABL_RTC_BUILTINS))) {
-        // (the runs in step would take k_slice_many from the run-time module: not yet pinned to the solo runs)
+    if (in_step) {
+        // (before any device call: the refusal shows on a machine without a GPU)
+        if (!like || !prior) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step needs a likelihood and a prior\n"); return 1; }
+        if (like->kind == PCHIP_LIKE_CALLBACK) {
+            std::fprintf(stderr, "polychord_hip: pchip_run_in_step does not take a host callback likelihood: the runs in step share their kernel launches, and a callback belongs to its caller's thread -- pchip_run_repeats runs those one thread per run\n");
+            return 1;
+        }
+        if (prior->kind != 1 && prior->kind != PCHIP_PRIOR_TABLE && prior->kind != PCHIP_PRIOR_SOURCE) {
+            std::fprintf(stderr, "polychord_hip: pchip_run_in_step does not take a host prior (prior.kind = %d): the runs in step need the prior on the device -- the uniform box (1), a table (2) or the handle's own source prior (3)\n", prior->kind);
+            return 1;
+        }
+    }
+    else if (like && (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & PC_ABL_RTC_BUILTINS))) {
+        // (this door's refusal is pinned by its tests: a source handle goes in step through pchip_run_in_step)
         std::fprintf(stderr, "polychord_hip: pchip_run_repeats does not take a device source likelihood (or settings.ablate bit 15) yet: run the seeds one by one with pchip_run\n");
         return 1;
     }
@@ -780,7 +794,7 @@ int pchip_run_repeats_ex(const pchip_settings *s, const pchip_like *like, const 
     const int per_dev = std::max(1, max_in_flight);
     std::atomic<int> next{0}, worst{0};
     const auto t0 = clk::now();
-    const bool device_like = like->kind != PCHIP_LIKE_CALLBACK && prior->kind == 1;
+    const bool device_like = in_step || (like->kind != PCHIP_LIKE_CALLBACK && prior->kind == 1);
     // (the runs leave their lived records on the device for the merge below: no second trip over the host link)
     pchip_settings s_loc = *s;
     // (set here, freed here: a caller that did not ask for the device block must not find its results pinning ndead x (nTotal + 2) doubles
@@ -924,6 +938,18 @@ int pchip_run_repeats_ex(const pchip_settings *s, const pchip_like *like, const 
     }
     else { for (int k = 0; k < nseeds; ++k) pchip_result_free(&results[k]); }        // (nothing is left for the caller to free on failure)
     return rc;
+}
+
+int pchip_run_repeats_ex(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds,
+                         int ndevices, const int *devices, int max_in_flight, int want_rows, pchip_result *results, pchip_merged *merged)
+{
+    return run_repeats_body(s, like, prior, nseeds, seeds, ndevices, devices, max_in_flight, want_rows, results, merged, false);
+}
+
+int pchip_run_in_step(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds,
+                      int ndevices, const int *devices, int max_in_flight, int want_rows, pchip_result *results, pchip_merged *merged)
+{
+    return run_repeats_body(s, like, prior, nseeds, seeds, ndevices, devices, max_in_flight, want_rows, results, merged, true);
 }
 
 // ---- between processes (one per GPU): RCCL inside the library ---------------------------------------------------------

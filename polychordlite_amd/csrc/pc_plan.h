@@ -241,6 +241,13 @@ inline void pc_count(long *path, const PcNurseryChoice &c)
     case PC_SAMPLER_WAVE: path[PCHIP_PATH_SLICE_WAVE]++; pc_count(path, c.traits); break;
     }
 }
+// ... and what a launch for the runs in step adds now that it takes a source and a device prior (pchip_run_in_step): the other two traits.  (A function
+// of its own: pc_count above is what it was, tests/test_run_plan.py.)  Whether the launch was shared is known where it is made: Cohort::flush
+// counts PCHIP_PATH_SLICE_STEP.
+inline void pc_count_step(long *path, const PcNurseryChoice &c)
+{
+    if (c.sampler == PC_SAMPLER_WAVE_STEP) pc_count(path, PcLaunchTraits{false, c.traits.src_terms, c.traits.device_prior});
+}
 inline void pc_count(long *path, const PcContractChoice &c)
 {
     if (c.want_nn) path[PCHIP_PATH_NN_LISTS]++;

@@ -1683,14 +1683,15 @@ __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB * ((FW > 0 && (LEAN == 1 || 
 // several runs of a device in step (Cohort, pc_engine.hip): the same statements on each run's own state, blockIdx.y = run.  (Included, not
 // called: handing the state to a function by reference moved fused multiply-adds in the one-run kernel -- -ffp-contract=fast works on
 // whatever the optimiser has made of the code -- and the lane-per-chain kernel of pc_slice_t.hip is matched to that kernel's ISA.)
-template <int DPL, int NROWS, bool SPECIAL, int WPB = 1, int FW = 0, int LEAN = 0>
+// PT as in k_slice (a prior table, a source prior): the general variants only, launched by pc_launch_slice_step; the six-argument names are the
+// box's, as before
+template <int DPL, int NROWS, bool SPECIAL, int WPB = 1, int FW = 0, int LEAN = 0, int PT = 0>
 __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB) void k_slice_many(const PcManyRec *__restrict__ R, int phi_lds, int mat_lds)
 {
     // (pointers left generic here: with them made global -- pc_many_state -- the compiler fused other multiply-adds than in the one-run
     //  kernel, the same statements, and a run in step was no longer bit for bit the run alone)
     const PcState S = R[blockIdx.y].S;
     const unsigned batch = (unsigned)R[blockIdx.y].ia[PC_REC_I_BATCH];
-    constexpr int PT = 0;                         // (runs in step take the box only)
 #include "pc_slice_body.inc"
 }
 
@@ -1876,7 +1877,7 @@ static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R
     const size_t tb = sizeof(double) * (size_t)nr * (D + 1);
     size_t sh = sizeof(double) * ((size_t)D + nr) + 16 + (p.phi_lds ? tb : 0);
     if (fused) sh += sizeof(double) * ((size_t)p.fw * D + (size_t)nr * (D + 2));     // + L, directions, widths
-    if (!R) sh += pc_terms_lds(S);                              // (runs in step take no source: pchip_run_repeats refuses the handle)
+    if (!R) sh += pc_terms_lds(S);                              // (a source in step: pc_launch_slice_step below, not this plan)
     if (fused && sh > 150 * 1024) return p;
     // the functor variants (LEAN = 3 Rastrigin, 4 twin Gaussian, 5 the Gaussian when settings.ablate bit 0 asks for it as a functor): one grade,
     // keyed draws, the box (a prior table: the general variants); runs in step take the Gaussian functor as the general kernel
@@ -1963,6 +1964,59 @@ extern "C" int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchai
 // Several runs of a device in step: the sampling kernel of any device likelihood launched once for all of them (grid.y = run).
 // 1: a shape only the one-run launchers take.
 extern "C" int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st) { return pc_slice_launch(S, pc_slice_plan(S, nchains, fused, R), dR, 0u, st); }
+
+// ------------------------------------------------------------------------------------------
+// Runs in step whose problem is the user's own: a source likelihood (plain or terms form) and / or a device prior (a table, a source
+// prior).  pc_slice_plan and its tables above stay what they were (the box, the built-ins); the rules here are the plan's for R > 0 without
+// its refusal of a table, with the terms form's LDS, and never a functor variant: the general kernel, PT = 0 (a source under the box)
+// or 1.  DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT as above; the PT = 0 rows are the instantiations of PC_SLICE_MANY_VARIANTS' LEAN = 0 rows.
+// ------------------------------------------------------------------------------------------
+#define PC_SLICE_STEP_VARIANTS(X) \
+    X(1, 1, false, 1, 0, 0, 0) X(1, 2, false, 1, 0, 0, 0) X(1, 4, false, 1, 0, 0, 0) X(1, 1, false, 1, 8, 0, 0) X(1, 1, false, 1, 16, 0, 0) X(1, 2, false, 1, 24, 0, 0) \
+    X(1, 1, false, 1, 0, 0, 1) X(1, 2, false, 1, 0, 0, 1) X(1, 4, false, 1, 0, 0, 1) X(1, 1, false, 1, 8, 0, 1) X(1, 1, false, 1, 16, 0, 1) X(1, 2, false, 1, 24, 0, 1)
+
+// the plan for R runs in step, nchains chains each; ok = false: a shape without a shared launch (each run then launches its own k_slice, which
+// takes any shape: nDims 65 ... 256, grades, the sequential stream, the correlated Gaussian)
+static PcSlicePlan pc_slice_step_plan(const PcState *S, int nchains, int fused, int R)
+{
+    PcSlicePlan p{};
+    const int D = S->D, nr = S->nr;
+    if (R < 1 || nchains < 1 || D < 1) return p;
+    if (S->ngrade > 1 || S->seq_mode || S->like.kind == PC_LIKE_CORR_GAUSSIAN) return p;
+    if (fused ? !pc_slice_fusable(S) : D > 64) return p;
+    p.many = true;
+    p.dpl = 1;
+    p.nrows = D <= 16 ? 1 : ((D <= 32 || fused) ? 2 : 4);
+    p.special = false; p.wpb = 1; p.lean = 0; p.pt = S->prior.kind >= 2 ? 1 : 0;
+    p.fw = !fused ? 0 : (D <= 8 ? 8 : (D <= 16 ? 16 : 24));
+    p.grid = dim3(nchains, R); p.block = dim3(64);
+    // a chain's LDS as pc_slice_plan lays it out, and the second theta of the terms form behind it
+    p.phi_lds = pc_slice_phi_lds(S);
+    size_t sh = sizeof(double) * ((size_t)D + nr) + 16 + (p.phi_lds ? sizeof(double) * (size_t)nr * (D + 1) : 0);
+    if (fused) sh += sizeof(double) * ((size_t)p.fw * D + (size_t)nr * (D + 2));
+    sh += pc_terms_lds(S);
+    if (fused && sh > 150 * 1024) return p;
+    p.lds = sh; p.ok = true;
+    return p;
+}
+
+// 0: launched once for the R runs; 1: no shared launch for this shape, or the run-time module failed (pc_rtc_error)
+extern "C" int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st)
+{
+    const PcSlicePlan p = pc_slice_step_plan(S, nchains, fused, R);
+    if (!p.ok) return 1;
+#define PC_ROW(DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT) \
+    if (p.dpl == DPL && p.nrows == NROWS && p.special == SPECIAL && p.wpb == WPB && p.fw == FW && p.lean == LEAN && p.pt == PT) { \
+        if (p.lds > 48 * 1024) pc_need_dyn_lds((const void *)k_slice_many<DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT>, p.lds); \
+        PC_LAUNCH((k_slice_many<DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT>), p.grid, p.block, p.lds, st, dR, p.phi_lds, p.mat_lds); \
+        return 0; }
+    PC_SLICE_STEP_VARIANTS(PC_ROW)
+#undef PC_ROW
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "pc_launch_slice_step: no k_slice_many<%d, %d, %d, %d, %d, %d, %d> in the variant table", p.dpl, p.nrows, (int)p.special, p.wpb, p.fw, p.lean, p.pt);
+    pc_abi_set_last_error(msg);
+    return 1;
+}
 
 // pchip_prior_transform: the device transform of the table in S->prior at n points (device pointers)
 extern "C" int pc_launch_prior_transform(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st)

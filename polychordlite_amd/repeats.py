@@ -27,11 +27,25 @@ def run_repeats(settings, like, prior, seeds, max_in_flight=4, devices=None, wan
     agree (with comm): `agree(ok) -> bool`, a collective of the caller's (e.g. an all-reduce of a failure flag over torch.distributed) that
     EVERY rank calls exactly once between its local runs and the exchange.  A rank whose runs failed must not leave the others waiting in
     the all-gather: when any rank reports a failure every rank raises here, before the exchange, and the collectives stay matched."""
+    return _run("pchip_run_repeats_ex", settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree)
+
+
+def run_in_step(settings, like, prior, seeds, max_in_flight=4, devices=None, want_rows=False, write=None, comm=None, agree=None):
+    """`run_repeats` for any problem that is wholly on the device (pchip_run_in_step): a built-in or a device source likelihood, plain or
+    terms form, under the uniform box, a prior table or the handle's own source prior, and settings.ablate bit 15.  Up to `max_in_flight`
+    runs of a device go round by round together, every kernel launched once for all of them; each run is bit for bit `_ctypes_api.run` of
+    its seed (runs[k]["path"]["slice_step"] counts its nurseries whose sampling launch was shared).  A callback likelihood or a host prior
+    raises.  Arguments and return value as `run_repeats`."""
+    return _run("pchip_run_in_step", settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree)
+
+
+def _run(symbol, settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree):
+    """the body of both doors: `symbol` is pchip_run_repeats_ex or pchip_run_in_step, which share their arguments"""
     seeds = [int(s) for s in seeds]
     if not seeds:
         raise ValueError("run_repeats needs at least one seed")
     lib = mg._lib()
-    f = lib.pchip_run_repeats_ex
+    f = getattr(lib, symbol)
     f.restype = C.c_int
     f.argtypes = [C.POINTER(api.Settings), C.POINTER(api.Like), C.POINTER(api.Prior), C.c_int, C.POINTER(C.c_int), C.c_int,
                   C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(api.Result), C.POINTER(mg.Merged)]
@@ -56,7 +70,7 @@ def run_repeats(settings, like, prior, seeds, max_in_flight=4, devices=None, wan
                     lib.pchip_result_free(C.byref(res[k]))
             raise RuntimeError(f"run_repeats: the runs of at least one rank failed (this rank: code {rc}); the exchange was skipped on every rank")
     if rc != 0:
-        raise RuntimeError(f"pchip_run_repeats failed with code {rc}")
+        raise RuntimeError(f"{symbol[:-3] if symbol.endswith('_ex') else symbol} failed with code {rc}")
     t_runs = time.perf_counter() - t0
     runs = []
     for k in range(n):

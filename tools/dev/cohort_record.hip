@@ -136,6 +136,7 @@ int pc_launch_slice_t_many(const PcState *S, const PcManyRec *dR, int R, unsigne
 int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t st) { return rec::launch("slice", S, {batch, nchains}, st); }
 int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchains, hipStream_t st) { return rec::launch("slice_fused", S, {batch, nchains}, st); }
 int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st) { return rec::launch_many("slice_many", S, dR, R, {nchains, fused}, st); }
+int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st) { return rec::launch_many("slice_step", S, dR, R, {nchains, fused}, st); }
 int pc_launch_sort_live(const PcState *S, hipStream_t st) { return rec::launch("sort_live", S, {}, st); }
 int pc_launch_sort_live_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st) { return rec::launch_many("sort_live_many", S, dR, R, {}, st); }
 void pc_launch_nn_lists(const PcState *S, int nleft, int use_rank, hipStream_t st) { rec::launch("nn_lists", S, {nleft, use_rank}, st); }

@@ -250,6 +250,7 @@ int pc_launch_slice_t_many(const PcState *S, const PcManyRec *dR, int R, unsigne
 int pc_launch_slice(const PcState *S, unsigned, int, hipStream_t st) { return rec::launch("slice", S, nullptr, 0, st); }
 int pc_launch_slice_fused(const PcState *S, unsigned, int, hipStream_t st) { return rec::launch("slice_fused", S, nullptr, 0, st); }
 int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int, int, hipStream_t st) { return rec::launch("slice_many", S, dR, R, st); }
+int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R, int, int, hipStream_t st) { return rec::launch("slice_step", S, dR, R, st); }
 int pc_launch_sort_live(const PcState *S, hipStream_t st) { return rec::launch("sort_live", S, nullptr, 0, st); }
 int pc_launch_sort_live_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st) { return rec::launch("sort_live_many", S, dR, R, st); }
 void pc_launch_nn_lists(const PcState *S, int, int, hipStream_t st) { rec::launch("nn_lists", S, nullptr, 0, st); }
