@@ -2045,7 +2045,11 @@ struct Engine {
             if (h_ctl->status == PC_ST_UPDATE || (h_ctl->upd_pending && h_ctl->status == PC_ST_RUNNING)) {
                 do_update(h_ctl->status != PC_ST_UPDATE); h_ctl->status = PC_ST_RUNNING; h_ctl->upd_pending = 0;
                 // (every few updates: in step with other runs a copy request costs the one thread that drives them all ~10 us, and a run on its own
-                //  finds the k_slice next to a copy as much longer as the copy lasts -- four copies of a run's thirty-one: 11.40 -> 11.33 ms, three A/B pairs)
+                //  finds the k_slice next to a copy as much longer as the copy lasts -- four copies of a run's thirty-one: 11.40 -> 11.33 ms, three A/B pairs.
+                //  The copy is a kernel of the runtime's, and whatever runs beside it pays its whole length, not k_slice alone: with the event in front
+                //  of do_update() the copy ran beside the update, no k_slice was long any more (39 of 396 -> 0, 105 -> 51 us) and the updates beside a
+                //  copy took 111 us instead of 58 -- 10.68 -> 10.67 ms at this threshold, 10.60 -> 10.70 ms at 2 * nlive.  So it stays behind the
+                //  update: profiles/dead_rows.json)
                 if ((size_t)h_ctl->ndead >= h_dead_copied + 4 * (size_t)cfg.nlive) {
                 if (!ev_apply) ev_apply = hpool().get_sync_event();
                 HIPCHK(hipEventRecord(ev_apply, st));       // the dead rows of the rounds so far are in place behind this point
@@ -2084,6 +2088,17 @@ struct Engine {
         const int nT = S.nT;
         // (pinned buffers, copies in stream order in front of the kill-off: the host does not stop here)
         es.hlive = halloc<double>((size_t)S.Ncap * nT); es.hcl = halloc<int>(S.Ncap);
+        // A run on its own that ends through k_final_par: the loop's dead rows that have not left yet and the live rows go to the copy
+        // stream from here, beside the kill-off (which writes neither: S.live stays, everything below h_ctl->ndead is final), and not
+        // in front of it and behind the host's wait for it.  live_cluster stays in front: the kill-off rewrites it.
+        const bool tail_aside = !co && plan.par_ok && h_ctl->ncluster == 1 && st_copy && st_copy != st;
+        if (tail_aside) {
+            if (!ev_apply) ev_apply = hpool().get_sync_event();
+            HIPCHK(hipEventRecord(ev_apply, st));
+            HIPCHK(hipStreamWaitEvent(st_copy, ev_apply, 0));
+            stream_dead();
+            HIPCHK(hipMemcpyAsync(es.hlive, S.live, sizeof(double) * (size_t)S.Ncap * nT, hipMemcpyDeviceToHost, st_copy));
+        } else
         HIPCHK(hipMemcpyAsync(es.hlive, S.live, sizeof(double) * (size_t)S.Ncap * nT, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(es.hcl, S.live_cluster, sizeof(int) * S.Ncap, hipMemcpyDeviceToHost, st));
         es.nc_end = h_ctl->ncluster;
@@ -2094,7 +2109,8 @@ struct Engine {
             if (co && sort_valid) { co->rec(rec_final(S)); if (!fused_final) co->flush(); }      // (fused: the caller launches the kill-off of all runs that end now, then calls end_a2)
             else {
             if (!sort_valid) (void)pc_launch_sort_live(&S, st);
-            (void)pc_launch_final_par(&S, st);
+            if (co) (void)pc_launch_final_par(&S, st);
+            else (void)pc_launch_final_par_split(&S, st);      // (k_final_par without its row loop, k_final_rows behind it)
             }
         } else if (h_ctl->ncluster > 1 && pc_launch_killoff_cl(&S, h_ctl->ncluster, st) == 0) {      // (several clusters: the deaths in sorted order by one wavefront, pc_clus.hip)
             path[PCHIP_PATH_KILLOFF_CL]++;
@@ -2127,7 +2143,8 @@ struct Engine {
     int end(pchip_result *out) { end_a(); HIPCHK(hipStreamSynchronize(st)); end_wait_aside(); return end_b(out); }
     int end_b(pchip_result *out)
     {
-        struct HostBuf { EndState &e; ~HostBuf() { if (e.hlive) hfree(e.hlive); if (e.hcl) hfree(e.hcl); e.hlive = nullptr; e.hcl = nullptr; } } hb{es};
+        // (hlive may still be on its way on the copy stream when something below throws)
+        struct HostBuf { EndState &e; hipStream_t sc; bool waited = false; ~HostBuf() { if (!waited && sc) (void)hipStreamSynchronize(sc); if (e.hlive) hfree(e.hlive); if (e.hcl) hfree(e.hcl); e.hlive = nullptr; e.hcl = nullptr; } } hb{es, st_copy};
         double *hlive = es.hlive; int *hcl = es.hcl; double *d_pmax = es.d_pmax, *h_part = es.h_part, *h_zp = es.h_zp;
         const int nc_end = es.nc_end, ncd_max = es.ncd_max, pmD = es.pmD, pm_nb = es.pm_nb, pm_pw = es.pm_pw, nT = S.nT;
         const auto t0 = r_t0, t1 = r_t1; auto t2 = es.t2;
@@ -2182,7 +2199,7 @@ struct Engine {
         out->nlive_final = nl;
         out->live = (double *)std::malloc(sizeof(double) * (size_t)std::max(1, nl) * nT);
         out->live_cluster = (int *)std::malloc(sizeof(int) * (size_t)std::max(1, nl));
-        for (int s = 0, k = 0; s < S.Ncap; ++s) if (hcl[s] >= 0) { std::memcpy(out->live + (size_t)k * nT, hlive + (size_t)s * nT, sizeof(double) * nT); out->live_cluster[k] = hcl[s]; k++; }
+        for (int s = 0, k = 0; s < S.Ncap; ++s) if (hcl[s] >= 0) out->live_cluster[k++] = hcl[s];      // (the rows: behind the copy stream's wait below)
         const int ncd = std::min(h_ctl->ncluster_dead, S.maxc_dead);
         out->nZp = ncd;
         out->logZp = (double *)std::malloc(sizeof(double) * std::max(1, ncd));
@@ -2217,6 +2234,8 @@ struct Engine {
             out->d_records = blk_rec; out->records_cap = (long)cap; out->records_device = dev;
         }
         HIPCHK(hipStreamSynchronize(st_copy));
+        hb.waited = true;
+        for (int s = 0, k = 0; s < S.Ncap; ++s) if (hcl[s] >= 0) std::memcpy(out->live + (size_t)(k++) * nT, hlive + (size_t)s * nT, sizeof(double) * nT);      // (a run on its own: the live rows came by the copy stream, end_a)
         if (h_nrec) { out->n_records = (long)*h_nrec; hfree(h_nrec); }
         active_run.reset();
         return 0;

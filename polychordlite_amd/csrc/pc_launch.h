@@ -95,7 +95,9 @@ int pc_par_fits(const PcState *S);
 int pc_launch_consume_par(const PcState *S, hipStream_t st);
 // the same launch for R runs of one shape at once (blockIdx.y = run; dR: device array of their records)
 int pc_launch_consume_par_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st);
+// the one-cluster kill-off whole (the rows moved inside: runs in step) / split for a run on its own: k_final_par without its row loop, k_final_rows behind it
 int pc_launch_final_par(const PcState *S, hipStream_t st);
+int pc_launch_final_par_split(const PcState *S, hipStream_t st);
 int pc_launch_final_par_many(const PcManyRec *dR, int R, hipStream_t st);
 // ---- pc_rtc.hip --------------------------------------------------------------------------------------------
 // launched by PC_LAUNCH (pc_sample.hip) with the variant, grid, block, dynamic LDS and arguments the launcher chose for the static kernel.

@@ -773,7 +773,11 @@ __global__ __launch_bounds__(PAR_NT) void k_consume_par_many(const PcManyRec *R)
 // Kill-off (nested_sampling.F90:381-384): every remaining live point dies, lowest first.  Death i of
 // the sorted live set leaves n-i points behind, so volumes are prefix sums of log((n-i)/(n-i+1)) and the
 // evidence is the same pair scan as above, 1024 deaths per pass with the state carried between passes.
+// ROWS: the rows move to the dead array in here too, sixteen at a time behind each pass (runs in step).  A run on its own
+// leaves them to k_final_rows behind this kernel -- 2000 rows by one workgroup were most of its 128 us -- and finds the
+// first dead row and the count in ctl->fin_ndead0 / fin_n0 (ctl->ndead and cl_n[0] are rewritten at the end).
 // ------------------------------------------------------------------------------------------
+template <bool ROWS>
 __device__ __forceinline__ void final_par_body(const PcState &S)
 {
     __shared__ __attribute__((aligned(16))) double X0[PAR_NT], X1[PAR_NT], X2[PAR_NT], X3[PAR_NT];
@@ -839,7 +843,7 @@ __device__ __forceinline__ void final_par_body(const PcState &S)
         }
         __syncthreads();
         // rows: one wave per row, 16 rows at a time
-        for (int r = wv; r < m; r += PAR_NT / 64) {
+        if (ROWS) for (int r = wv; r < m; r += PAR_NT / 64) {
             const int sl = S.sort_slot[base + r];
             const double *row = S.live + (size_t)sl * nT;
             double *dst = S.dead + (size_t)(ndead0 + base + r) * nT;
@@ -853,10 +857,24 @@ __device__ __forceinline__ void final_par_body(const PcState &S)
         S.logZXp[0] = carry[5]; S.logZp2[0] = carry[6]; S.logZpXp[0] = carry[7]; S.death_thr[0] = carry[8]; S.cl_n[0] = 0;
         ctl->status = PC_ST_DONE; ctl->error = PC_ERR_NONE; ctl->ndead = ndead0 + n0; ctl->ncluster = 0; ctl->ncluster_dead = ncd + 1;
         ctl->logZ = carry[0]; ctl->logZ2 = carry[1]; ctl->cluster_deleted = 0;
+        ctl->fin_ndead0 = ndead0; ctl->fin_n0 = n0;
     }
 }
-__global__ __launch_bounds__(PAR_NT) void k_final_par(PcState S) { final_par_body(S); }
-__global__ __launch_bounds__(PAR_NT) void k_final_par_many(const PcManyRec *R) { final_par_body(pc_many_state(R, blockIdx.y)); }
+__global__ __launch_bounds__(PAR_NT) void k_final_par(PcState S) { final_par_body<false>(S); }
+__global__ __launch_bounds__(PAR_NT) void k_final_par_whole(PcState S) { final_par_body<true>(S); }
+__global__ __launch_bounds__(PAR_NT) void k_final_par_many(const PcManyRec *R) { final_par_body<true>(pc_many_state(R, blockIdx.y)); }
+// the rows of k_final_par's deaths, behind it on its stream: a wavefront a row, four a workgroup (like k_apply_pool); row i of
+// the sorted order becomes dead row fin_ndead0 + i.  Nothing where the kill-off found no room (PC_ST_ERROR: fin_* are not set).
+__global__ __launch_bounds__(256) void k_final_rows(PcState S)
+{
+    const PcCtl *ctl = S.ctl;
+    if (ctl->status == PC_ST_ERROR) return;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6), nT = S.nT;
+    if (i >= ctl->fin_n0) return;
+    const double *row = S.live + (size_t)S.sort_slot[i] * nT;
+    double *dst = S.dead + (size_t)(ctl->fin_ndead0 + i) * nT;
+    for (int e = lane; e < nT; e += 64) dst[e] = row[e];
+}
 
 
 static size_t par_lds(const PcState *S)
@@ -889,7 +907,13 @@ extern "C" int pc_launch_consume_par_many(const PcState *S, const PcManyRec *dR,
 
 extern "C" int pc_launch_final_par(const PcState *S, hipStream_t st)
 {
+    hipLaunchKernelGGL(k_final_par_whole, dim3(1), dim3(PAR_NT), 0, st, *S);
+    return 0;
+}
+extern "C" int pc_launch_final_par_split(const PcState *S, hipStream_t st)
+{
     hipLaunchKernelGGL(k_final_par, dim3(1), dim3(PAR_NT), 0, st, *S);
+    hipLaunchKernelGGL(k_final_rows, dim3((S->Ncap + 3) / 4), dim3(256), 0, st, *S);
     return 0;
 }
 extern "C" int pc_launch_final_par_many(const PcManyRec *dR, int R, hipStream_t st)

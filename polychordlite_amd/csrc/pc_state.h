@@ -70,9 +70,11 @@ struct PcCtl {                   // written by the consume kernel, read by the h
     int upd_tmark;                      // steps of the launch before the mark (the step that caused the triggering death included)
     int upd_T, upd_ts;                  // steps in the nursery at launch / consumed by the launch
     int upd_nph0;                       // phantom rows in use when the launch started (its regions begin there)
-    int upd_keep_thr, upd_pad;          // deaths after the mark: death_thr stays the last death's logL
+    int upd_keep_thr;                   // deaths after the mark: death_thr stays the last death's logL
+    int fin_ndead0;                     // k_final_par, for k_final_rows behind it: the kill-off's first dead row (ndead and cl_n[0] are rewritten at its end) ...
     double upd_thr;                     // logL of the death that triggered the mark (clean_phantoms' threshold)
-    int chol_suspect, chol_pad;         // the blocked factorisation met a pivot it does not trust: the reference-order kernel behind it decides
+    int chol_suspect;                   // the blocked factorisation met a pivot it does not trust: the reference-order kernel behind it decides
+    int fin_n0;                         // ... and the number of its rows
     long long wave_cyc[4];              // developer counters of k_consume_clp: cycles waves 1, 2, 3 spend in their loops over a pass's deaths, the phantom waves in theirs
 };
 
