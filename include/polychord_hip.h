@@ -315,7 +315,7 @@ typedef struct {
 /* The structs of this header grow at their END from release to release and carry no size member (their first members are what existing
  * bindings rely on).  A binding that mirrors them (ctypes, ISO_C_BINDING, cgo ...) checks itself against the library it loaded:
  * pchip_abi_version() == PCHIP_ABI_VERSION of the header it was written against, and pchip_sizeof("settings" | "result" | "merged" |
- * "like" | "prior" | "update") == the size of its own mirror (0 for an unknown name). */
+ * "like" | "prior" | "update" | "maximum") == the size of its own mirror (0 for an unknown name). */
 /* (still 9 with pchip_prior's two trailing members and PCHIP_PRIOR_TABLE: they are read only when kind == 2, which no earlier caller
  *  sets; pchip_sizeof("prior") tells a mirror of the older layout apart) */
 #define PCHIP_ABI_VERSION 9
@@ -381,6 +381,38 @@ void pchip_result_free(pchip_result *r);
    (<base_dir>/<file_root>.maximum).  Host code; live rows as in pchip_result.  0 on success. */
 int  pchip_maximise(polychord_loglike_fn loglikelihood, polychord_prior_fn prior, int nDims, int nDerived, double logzero,
                     const double *live, const int *live_cluster, int nlive, const double *post_mean, const char *path);
+/* The maximiser's result as values, and the maximiser for problems that live wholly on the DEVICE (a built-in or a source likelihood of either
+ * form under the uniform box, a prior table or the handle's own source prior: nothing that has a host function to polish through).
+ * Index [0] is the likelihood leg, [1] the posterior leg: status 0, or 1 "Could not construct simplex" (no cluster of the live set holds
+ * nDims + 1 rows above logzero: nothing is searched and nothing launched for that leg); cluster = the cluster the simplex came from;
+ * niter = Nelder-Mead iterations that moved the simplex, neval = likelihood calls of the search (a trial point outside the unit cube is
+ * logzero without one, calculate.f90:36-38).  A run whose likelihood leg has no simplex stops there: its posterior leg is status 1, cluster -1.
+ * Points are [theta | phi]; max_post = logl_at_post + dXdtheta(post point); mean_point = [mean theta | phi at the mean theta], as
+ * loglikelihood(mean) leaves it (maximiser.F90:77-80).  The point arrays are owned by the struct (pchip_maximum_free); a zeroed struct is a
+ * valid empty one, and every door that takes an `out` leaves each struct zeroed or filled on every return, refusals included, so
+ * pchip_maximum_free may follow unconditionally. */
+typedef struct { int status[2], cluster[2]; long niter[2], neval[2];     /* [0] likelihood leg, [1] posterior leg */
+                 double max_logl, *max_point;                              /* [nDims + nDerived] */
+                 double max_post, logl_at_post, *post_point;
+                 int has_mean; double logl_mean, *mean_point; } pchip_maximum;
+/* pchip_maximise without its file: the host path (host function pointers), the same searches in the same order.  0, or 1 when a leg has no
+ * simplex (status[] tells which). */
+int  pchip_maximise_values(polychord_loglike_fn loglikelihood, polychord_prior_fn prior, int nDims, int nDerived, double logzero,
+                           const double *live, const int *live_cluster, int nlive, const double *post_mean, pchip_maximum *out);
+/* The device maximiser: one wavefront per problem (a run's likelihood leg, its posterior leg), the simplex in LDS, the evaluation code of the
+ * sampling kernels (the bits of pchip_source_eval / pchip_prior_transform), nelder_mead.f90's rules with dl = 1e-5 and at most max_iter
+ * iterations (<= 0: 200000, the host's cap).  Of `s` nDims, nDerived, logzero, device and ablate are read; live rows as in pchip_result.
+ * nDims <= 64.  0; 1 with a message in polychord_hip_last_error() (a callback likelihood or a callback prior is refused before any device call;
+ * a leg without a simplex: status[], the other values stay); 2 no device / HIP error; 3 nDims > 64 (the host maximiser remains for host functions). */
+int  pchip_maximise_device(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, const double *live, const int *live_cluster,
+                           int nlive, const double *post_mean, long max_iter, pchip_maximum *out);
+/* ... for the final live sets of nruns runs of one problem (pchip_run_in_step's results): two launches for all runs -- the candidate values
+ * of every posterior leg, then every leg of every run.  out[r] is bit for bit pchip_maximise_device of run r alone. */
+int  pchip_maximise_device_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nruns, const pchip_result *runs,
+                                long max_iter, pchip_maximum *out /* [nruns] */);
+/* <root>.maximum of a pchip_maximum (write_max_file, read_write.F90:754-807): what pchip_maximise writes.  0; 1 a leg has no result; 2 the file */
+int  pchip_maximum_write(const pchip_maximum *m, int nDims, int nDerived, const char *path);
+void pchip_maximum_free(pchip_maximum *m);
 /* ---- repeat-sharded runs: independent runs of one problem, merged ------------------------------------
  * The reference's way to use more hardware is its MPI farm (nested_sampling.F90:262-301, mpi_utils.F90:376-463: workers'
  * babies gathered into one run).  Here every GPU carries a complete run of its own; the dead points of all runs are

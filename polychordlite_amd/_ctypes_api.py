@@ -77,6 +77,14 @@ class Result(C.Structure):
                 ("path", C.c_long * 24)]
 
 
+class Maximum(C.Structure):
+    """pchip_maximum: the maximiser's result as values; index 0 = the likelihood leg, 1 = the posterior leg"""
+    _fields_ = [("status", C.c_int * 2), ("cluster", C.c_int * 2), ("niter", C.c_long * 2), ("neval", C.c_long * 2),
+                ("max_logl", C.c_double), ("max_point", C.POINTER(C.c_double)),
+                ("max_post", C.c_double), ("logl_at_post", C.c_double), ("post_point", C.POINTER(C.c_double)),
+                ("has_mean", C.c_int), ("logl_mean", C.c_double), ("mean_point", C.POINTER(C.c_double))]
+
+
 # pchip_result.path[]: launches per kernel variant (include/polychord_hip.h PCHIP_PATH_*)
 PATH_NAMES = ("consume_par", "consume_cl", "consume_general", "consume_fast", "killoff_par", "killoff_cl", "killoff_general",
               "killoff_fast", "update_fused", "update_steps", "slice_wave", "slice_lane", "nn_lists", "nn_fallbacks", "pool_mode",
@@ -142,10 +150,20 @@ def load():
     pi = C.POINTER(C.c_int); pd = C.POINTER(C.c_double)
     lib.pchip_update_factors.argtypes = [C.POINTER(Settings), C.c_int, C.c_int, pd, pi, C.c_int, pd, pd, pi, pd, pd, C.c_int, pd, pd, pi, pd, pi]
     lib.pchip_update_factors.restype = C.c_int
+    lib.pchip_maximise_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, pd, pi, C.c_int, pd, C.POINTER(Maximum)]
+    lib.pchip_maximise_values.restype = C.c_int
+    lib.pchip_maximise_device.argtypes = [C.POINTER(Settings), C.POINTER(Like), C.POINTER(Prior), pd, pi, C.c_int, pd, C.c_long, C.POINTER(Maximum)]
+    lib.pchip_maximise_device.restype = C.c_int
+    lib.pchip_maximise_device_many.argtypes = [C.POINTER(Settings), C.POINTER(Like), C.POINTER(Prior), C.c_int, C.POINTER(Result), C.c_long, C.POINTER(Maximum)]
+    lib.pchip_maximise_device_many.restype = C.c_int
+    lib.pchip_maximum_write.argtypes = [C.POINTER(Maximum), C.c_int, C.c_int, C.c_char_p]
+    lib.pchip_maximum_write.restype = C.c_int
+    lib.pchip_maximum_free.argtypes = [C.POINTER(Maximum)]
+    lib.pchip_maximum_free.restype = None
     # this mirror against the library that was loaded (the structs grow at their end: include/polychord_hip.h PCHIP_ABI_VERSION)
     lib.pchip_sizeof.argtypes = [C.c_char_p]
     lib.pchip_sizeof.restype = C.c_ulong
-    for name, cls in (("settings", Settings), ("result", Result), ("like", Like), ("prior", Prior)):
+    for name, cls in (("settings", Settings), ("result", Result), ("like", Like), ("prior", Prior), ("maximum", Maximum)):
         if lib.pchip_sizeof(name.encode()) != C.sizeof(cls):
             raise ImportError(f"{LIB_PATH}: pchip_{name} is {lib.pchip_sizeof(name.encode())} bytes, this binding's mirror {C.sizeof(cls)} "
                               f"(library ABI version {lib.pchip_abi_version()}): rebuild with `python -m polychordlite_amd.build`")
@@ -281,6 +299,56 @@ def update_factors(live, live_cluster, phantom, ph_logL, ph_cluster, threshold, 
     return dict(cov=cov, chol=chol, count=count, shift=sho, chol_suspect=sus.value)
 
 
+def maximum_dict(m, nDims, nDerived):
+    """dict copy of a filled pchip_maximum (the struct stays the caller's to free): status, cluster, niter, neval per leg ([0] likelihood,
+    [1] posterior), max_logl / max_point, max_post / logl_at_post / post_point, logl_mean / mean_point (None without a mean)"""
+    n = nDims + nDerived
+    pt = lambda p: np.ctypeslib.as_array(p, shape=(n,)).copy() if p else None
+    return dict(status=[int(v) for v in m.status], cluster=[int(v) for v in m.cluster], niter=[int(v) for v in m.niter], neval=[int(v) for v in m.neval],
+                max_logl=m.max_logl, max_point=pt(m.max_point), max_post=m.max_post, logl_at_post=m.logl_at_post, post_point=pt(m.post_point),
+                logl_mean=m.logl_mean if m.has_mean else None, mean_point=pt(m.mean_point) if m.has_mean else None)
+
+
+def _maximum_out(lib, m, rc, who, nDims, nDerived, write):
+    """the dict of `m` (freed here); a leg without a simplex (code 1, status set) is a result, any other failure raises"""
+    try:
+        if rc != 0 and not (rc == 1 and m.max_point and (m.status[0] or m.status[1])):
+            msg = lib.polychord_hip_last_error()
+            raise RuntimeError(f"{who} failed with code {rc}" + (": " + msg.decode(errors="replace") if msg else ""))
+        if write is not None and lib.pchip_maximum_write(C.byref(m), nDims, nDerived, str(write).encode()) != 0:
+            raise RuntimeError(f"pchip_maximum_write({write}) failed")
+        return maximum_dict(m, nDims, nDerived)
+    finally:
+        lib.pchip_maximum_free(C.byref(m))
+
+
+def maximise_device(settings, like, prior, run, max_iter=0, write=None):
+    """pchip_maximise_device on the final live set of `run` (a dict of run(): live, live_cluster, post_mean): the maximum-likelihood and the
+    maximum-posterior point of a problem that lives wholly on the device, one wavefront per leg; dict of maximum_dict.  max_iter 0: the
+    host's cap of 200000 iterations; write: path of a <root>.maximum file to write as well"""
+    lib = load()
+    live = np.ascontiguousarray(run["live"], dtype=np.float64)
+    cl = np.ascontiguousarray(run["live_cluster"], dtype=np.int32)
+    mean = run.get("post_mean")
+    mean = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+    m = Maximum()
+    rc = lib.pchip_maximise_device(C.byref(settings), C.byref(like), C.byref(prior), dptr(live), cl.ctypes.data_as(C.POINTER(C.c_int)), live.shape[0],
+                                   dptr(mean) if mean is not None else None, int(max_iter), C.byref(m))
+    return _maximum_out(lib, m, rc, "pchip_maximise_device", settings.nDims, settings.nDerived, write)
+
+
+def maximise_values(loglike, prior_fn, nDims, nDerived, logzero, live, live_cluster, post_mean=None, write=None):
+    """pchip_maximise_values: the HOST maximiser through host function pointers (ctypes function objects or addresses); dict of maximum_dict"""
+    lib = load()
+    x = np.ascontiguousarray(live, dtype=np.float64)
+    cl = np.ascontiguousarray(live_cluster, dtype=np.int32)
+    mean = None if post_mean is None else np.ascontiguousarray(post_mean, dtype=np.float64)
+    m = Maximum()
+    rc = lib.pchip_maximise_values(C.cast(loglike, C.c_void_p), C.cast(prior_fn, C.c_void_p), nDims, nDerived, logzero, dptr(x),
+                                   cl.ctypes.data_as(C.POINTER(C.c_int)), x.shape[0], dptr(mean) if mean is not None else None, C.byref(m))
+    return _maximum_out(lib, m, rc, "pchip_maximise_values", nDims, nDerived, write)
+
+
 def make_problem(kind, nDims, nDerived=0, lo=None, hi=None, mu=0.5, sigma=0.1, invcov=None, mean=None, logdet=0.0, source=0,
                  prior_table=None, hyper=None, prior_source=False):
     """(Like, Prior, keepalive) for a built-in device likelihood, or a device source ("source", source=handle), and a uniform box prior
@@ -389,6 +457,8 @@ def result_dict(r, settings):
                logweights=_view(own, r.logweights, (nd,)),
                entry=_view(own, r.entry, (nd,)),
                live=_view(own, r.live, (r.nlive_final, nT)),
+               live_cluster=(np.ctypeslib.as_array(r.live_cluster, shape=(r.nlive_final,)).copy() if r.live_cluster and r.nlive_final > 0
+                             else np.zeros(max(r.nlive_final, 0), dtype=np.int32)),
                logZp=np.ctypeslib.as_array(r.logZp, shape=(max(r.nZp, 1),))[:r.nZp].copy(),
                post_mean=np.ctypeslib.as_array(r.post_mean, shape=(D + settings.nDerived,)).copy(),
                post_var=np.ctypeslib.as_array(r.post_var, shape=(D + settings.nDerived,)).copy(),

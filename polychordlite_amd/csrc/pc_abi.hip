@@ -509,6 +509,7 @@ unsigned long pchip_sizeof(const char *n)
     if (!std::strcmp(n, "like")) return sizeof(pchip_like);
     if (!std::strcmp(n, "prior")) return sizeof(pchip_prior);
     if (!std::strcmp(n, "update")) return sizeof(pchip_update);
+    if (!std::strcmp(n, "maximum")) return sizeof(pchip_maximum);
     return 0;
 }
 

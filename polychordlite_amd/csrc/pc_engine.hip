@@ -2638,4 +2638,137 @@ int pchip_source_eval(int handle, const double *thetas, long n, int nDims, int n
     return rc;
 }
 
+
+// ---- the device maximiser: `maximise = T` for problems that live wholly on the device (k_max_rank, k_maximise: pc_sample.hip) -----------
+// One engine state serves every run (the runs of pchip_run_in_step share their problem): its set-up gives the likelihood, the prior and the
+// source's data block as the sampling kernels take them.  Two launches whatever the number of runs: the candidate values of the posterior
+// legs over all live rows, then one wavefront per leg and run.  The choice of simplex and the result struct are pc_maximise.hip's.
+static int maximise_device_core(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nruns, const double *const *live,
+                                const int *const *cluster, const int *nlive, const double *const *mean, long max_iter, pchip_maximum *out)
+{
+    if (out && nruns >= 1) std::memset(out, 0, sizeof(pchip_maximum) * (size_t)nruns);     // every return leaves results that pchip_maximum_free takes
+    if (!s || !like || !prior || !out || nruns < 1) { pc_abi_set_last_error("pchip_maximise_device: settings, likelihood, prior, at least one run and a result for each"); return 1; }
+    if (like->kind == PC_LIKE_CALLBACK || prior->kind == PCHIP_PRIOR_CALLBACK) {
+        pc_abi_set_last_error("pchip_maximise_device: a host callback likelihood or a host prior (kind 0) has no device code -- pchip_maximise / pchip_maximise_values polish through the host functions");
+        return 1;
+    }
+    const int D = s->nDims, nDer = s->nDerived, nT = 2 * D + nDer + 2, nv = D + 1;
+    for (int r = 0; r < nruns; ++r)
+        if (!live[r] || !cluster[r] || nlive[r] < 1) { pc_abi_set_last_error("pchip_maximise_device: every run needs its live rows, their clusters and nlive >= 1"); return 1; }
+    if (D < 1 || nDer < 0) { pc_abi_set_last_error("pchip_maximise_device: nDims >= 1, nDerived >= 0"); return 1; }
+    if (D > 64) { pc_abi_set_last_error("pchip_maximise_device: nDims > 64 is not supported (one coordinate a lane); the host maximiser remains for host functions"); return 3; }
+    for (int r = 0; r < nruns; ++r) pc_maximum_alloc(&out[r], D, nDer);
+    const size_t nin = (size_t)nv * D + nv + D + nDer, nout = (size_t)2 * D + 2 * nDer + 4;
+    // the likelihood legs' simplexes need no device: a live set without one launches nothing
+    std::vector<double> in; std::vector<int> hdr, prob_run, prob_leg;
+    auto add_problem = [&](int r, int leg, const double *vals) {
+        std::vector<double> rec(nin, 0.0);
+        out[r].cluster[leg] = pc_max_choose_simplex(D, nT, s->logzero, live[r], cluster[r], nlive[r], vals, rec.data(), rec.data() + (size_t)nv * D);
+        if (out[r].cluster[leg] < 0) { out[r].status[leg] = 1; return; }
+        if (mean[r]) std::copy(mean[r], mean[r] + D + nDer, rec.begin() + (size_t)nv * D + nv);
+        in.insert(in.end(), rec.begin(), rec.end());
+        hdr.push_back(leg); hdr.push_back(mean[r] ? 1 : 0);
+        prob_run.push_back(r); prob_leg.push_back(leg);
+    };
+    std::vector<char> rank_run(nruns, 0);
+    long rows_total = 0;
+    for (int r = 0; r < nruns; ++r) {
+        add_problem(r, 0, nullptr);
+        // a run whose likelihood leg has no simplex stops there, as pchip_maximise_values does: its posterior leg is not tried
+        rank_run[r] = out[r].status[0] == 0;
+        if (rank_run[r]) rows_total += nlive[r]; else { out[r].status[1] = 1; out[r].cluster[1] = -1; }
+    }
+    int rc = 0;
+    if (rows_total > 0 || !prob_run.empty()) {
+        pchip_settings c;
+        pchip_settings_default(&c, D, nDer);
+        c.nlive = 8; c.nprior = 8; c.batch = 1; c.num_repeats = 1; c.do_clustering = 0; c.seed = 1; c.feedback = 0;
+        c.device = s->device; c.ablate = s->ablate; c.logzero = s->logzero;
+        Engine E;
+        double *d_rows = nullptr, *d_val = nullptr, *d_in = nullptr, *d_out = nullptr; int *d_hdr = nullptr; long long *d_outi = nullptr;
+        try {
+            E.setup(c, *like, *prior);
+            HIPCHK(hipStreamSynchronize(E.st));
+            const PcState &S = E.S;
+            if (rows_total > 0) {
+                std::vector<double> rows((size_t)rows_total * nT), val((size_t)rows_total);
+                size_t at = 0;
+                for (int r = 0; r < nruns; ++r) if (rank_run[r]) { std::copy(live[r], live[r] + (size_t)nlive[r] * nT, rows.begin() + at * nT); at += nlive[r]; }
+                HIPCHK(hipMalloc(&d_rows, sizeof(double) * rows.size())); HIPCHK(hipMalloc(&d_val, sizeof(double) * val.size()));
+                HIPCHK(hipMemcpy(d_rows, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+                if (pc_launch_max_rank(&S, (int)rows_total, d_rows, d_val, E.st)) {
+                    if (pc_rtc_error()) pc_abi_set_last_error(pc_rtc_error());
+                    engine_fail(PC_RC_SETTINGS, "pchip_maximise_device: k_max_rank could not be launched (%s)", polychord_hip_last_error() ? polychord_hip_last_error() : "no such kernel");
+                }
+                HIPCHK(hipStreamSynchronize(E.st));
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpy(val.data(), d_val, sizeof(double) * val.size(), hipMemcpyDeviceToHost));
+                at = 0;
+                for (int r = 0; r < nruns; ++r) if (rank_run[r]) { add_problem(r, 1, val.data() + at); at += nlive[r]; }
+            }
+            const int np = (int)prob_run.size();
+            if (np > 0) {
+                std::vector<double> res((size_t)np * nout); std::vector<long long> resi((size_t)np * 2);
+                HIPCHK(hipMalloc(&d_in, sizeof(double) * in.size())); HIPCHK(hipMalloc(&d_hdr, sizeof(int) * hdr.size()));
+                HIPCHK(hipMalloc(&d_out, sizeof(double) * res.size())); HIPCHK(hipMalloc(&d_outi, sizeof(long long) * resi.size()));
+                HIPCHK(hipMemcpy(d_in, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(d_hdr, hdr.data(), sizeof(int) * hdr.size(), hipMemcpyHostToDevice));
+                if (pc_launch_maximise(&S, np, d_in, d_hdr, max_iter > 0 ? (long long)max_iter : 200000LL, d_out, d_outi, E.st)) {
+                    if (pc_rtc_error()) pc_abi_set_last_error(pc_rtc_error());
+                    engine_fail(PC_RC_SETTINGS, "pchip_maximise_device: k_maximise could not be launched (%s)", polychord_hip_last_error() ? polychord_hip_last_error() : "no such kernel");
+                }
+                HIPCHK(hipStreamSynchronize(E.st));
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpy(res.data(), d_out, sizeof(double) * res.size(), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(resi.data(), d_outi, sizeof(long long) * resi.size(), hipMemcpyDeviceToHost));
+                for (int p = 0; p < np; ++p) {
+                    pchip_maximum &m = out[prob_run[p]];
+                    const int leg = prob_leg[p];
+                    const double *row = res.data() + (size_t)p * nout, *tail = row + 2 * D + nDer;
+                    m.niter[leg] = (long)resi[2 * (size_t)p]; m.neval[leg] = (long)resi[2 * (size_t)p + 1];
+                    if (leg == 0) {
+                        m.max_logl = tail[0];
+                        std::copy(row + D, row + 2 * D + nDer, m.max_point);
+                        if (mean[prob_run[p]]) {                     // [mean theta | phi(mean theta)], as loglikelihood(mean) leaves it (maximiser.F90:77-80)
+                            m.has_mean = 1; m.logl_mean = tail[2];
+                            std::copy(mean[prob_run[p]], mean[prob_run[p]] + D, m.mean_point);
+                            std::copy(tail + 4, tail + 4 + nDer, m.mean_point + D);
+                        }
+                    } else {
+                        m.logl_at_post = tail[0]; m.max_post = tail[0] + tail[1];
+                        std::copy(row + D, row + 2 * D + nDer, m.post_point);
+                    }
+                }
+            }
+        } catch (const EngineError &e) {
+            std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str());
+            pc_abi_set_last_error(e.msg.c_str());
+            (void)hipGetLastError();
+            rc = e.code ? e.code : PC_RC_DEVICE;
+        }
+        (void)hipFree(d_rows); (void)hipFree(d_val); (void)hipFree(d_in); (void)hipFree(d_hdr); (void)hipFree(d_out); (void)hipFree(d_outi);
+        E.destroy();
+    }
+    if (rc) { for (int r = 0; r < nruns; ++r) pchip_maximum_free(&out[r]); return rc; }
+    for (int r = 0; r < nruns; ++r)
+        if (out[r].status[0] || out[r].status[1]) { pc_abi_set_last_error("pchip_maximise_device: Could not construct simplex (no cluster of the live set holds nDims + 1 rows above logzero)"); rc = 1; }
+    return rc;
+}
+
+int pchip_maximise_device(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, const double *live, const int *live_cluster,
+                          int nlive, const double *post_mean, long max_iter, pchip_maximum *out)
+{
+    return maximise_device_core(s, like, prior, 1, &live, &live_cluster, &nlive, &post_mean, max_iter, out);
+}
+
+int pchip_maximise_device_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nruns, const pchip_result *runs,
+                               long max_iter, pchip_maximum *out)
+{
+    if (out && nruns >= 1) std::memset(out, 0, sizeof(pchip_maximum) * (size_t)nruns);
+    if (!runs || nruns < 1) { pc_abi_set_last_error("pchip_maximise_device_many: at least one run"); return 1; }
+    std::vector<const double *> live(nruns), mean(nruns); std::vector<const int *> cl(nruns); std::vector<int> nl(nruns);
+    for (int r = 0; r < nruns; ++r) { live[r] = runs[r].live; cl[r] = runs[r].live_cluster; nl[r] = runs[r].nlive_final; mean[r] = runs[r].post_mean; }
+    return maximise_device_core(s, like, prior, nruns, live.data(), cl.data(), nl.data(), mean.data(), max_iter, out);
+}
+
 }  // extern "C"

@@ -137,6 +137,20 @@ int pc_launch_prior_transform(const PcState *S, int n, const double *cubes, doub
 int pc_launch_source_eval(const PcState *S, int n, const double *thetas, double *logL, double *phi, hipStream_t st);
 // the prior of a source handle (prior.kind 3) at n points: k_prior_transform by name from the handle's module
 int pc_launch_source_prior_eval(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st);
+// the device maximiser (nDims <= 64; static kernels, or by name from the run-time module: a source handle, settings.ablate bit 15).
+// k_max_rank: val[i] = logL_i + dXdtheta(cube_i) of n live rows [n][nT].  k_maximise: nprob problems, one wavefront each -- in: nprob records
+// of (D + 1) D start cubes | D + 1 values | D + nDer posterior mean; hdr: leg (0 likelihood, 1 posterior) and has-mean per problem; out: nprob
+// records of 2 D + 2 nDer + 4 doubles [cube | theta | phi | logL | dXdtheta | logL(mean) | value | phi(mean)]; outi: iterations and likelihood calls
+int pc_launch_max_rank(const PcState *S, int n, const double *rows, double *val, hipStream_t st);
+int pc_launch_maximise(const PcState *S, int nprob, const double *in, const int *hdr, long long max_iter, double *out, long long *outi, hipStream_t st);
+// ---- pc_maximise.hip ---------------------------------------------------------------------------------------
+// do_maximisation's choice of simplex (maximiser.F90:92-161), the one copy both maximisers use: per cluster with at least D + 1 rows the D + 1
+// best by stable sort of `vals` (NULL: the rows' logL), the cluster whose best value is strictly highest, in index order, wins.  simplex
+// [(D + 1) D] and f [D + 1] are filled ascending; returns the cluster, or -1: no simplex can be built
+int pc_max_choose_simplex(int nDims, int nTotal, double logzero, const double *live, const int *cluster, int nlive, const double *vals,
+                          double *simplex, double *f);
+// the three point arrays of a pchip_maximum (zeroed first), for pchip_maximum_free
+void pc_maximum_alloc(pchip_maximum *m, int nDims, int nDerived);
 // ---- pc_slice_t.hip ----------------------------------------------------------------------------------------
 // lane = chain / lane = basis.  _ok: 1 where the kernels take the state; launchers: 0: launched; 1: not this way
 int pc_bases_t_ok(const PcState *S);

@@ -483,6 +483,251 @@ __global__ __launch_bounds__(64) void k_source_eval(PcState S, const double *the
 #endif
 
 // ------------------------------------------------------------------------------------------
+// The device maximiser (pchip_maximise_device): `maximise = T` for a problem that lives wholly on the device.  Restates dXdtheta
+// (maximiser.F90:179-207), nelder_mead (nelder_mead.f90:7-83) and calculate_point (calculate.f90:6-50) as pc_maximise.hip does on the
+// host, one wavefront a problem, lane = coordinate (nDims <= 64), through the evaluation code above: PC_PRIOR_THETA, like_eval.
+// Every decision is taken on a value read from lane 0, so control flow and the barriers inside the evaluation stay wave-uniform.
+// ------------------------------------------------------------------------------------------
+// LDS of k_maximise in doubles: ybuf [D], simplex [D + 1][D], values [D + 1], one D x D matrix, the order [D + 1] (ints)
+#define PC_MAX_LDS_DOUBLES(D) ((size_t)(D) + (size_t)((D) + 1) * (D) + ((D) + 1) + (size_t)(D) * (D) + ((D) + 2) / 2)
+
+template <int DPL>
+__device__ __forceinline__ void pc_max_lanes(const PcState &S, int lane, LaneDims<DPL> &ld, LaneTable<DPL> &lt, double *ybuf)
+{
+    static_assert(DPL == 1, "the maximiser holds one coordinate a lane: nDims <= 64");
+    const bool box = S.prior.kind < 2;
+    ld.on[0] = lane < S.D;
+    const double lo = (box && ld.on[0] && S.prior.lo) ? S.prior.lo[lane] : 0.0;
+    const double hi = (box && ld.on[0] && S.prior.hi) ? S.prior.hi[lane] : 1.0;
+    ld.lo[0] = lo; ld.span[0] = hi - lo;
+    ld.mean[0] = (ld.on[0] && S.like.mean) ? S.like.mean[lane] : 0.0;
+    if (!box) PC_PRIOR_LOAD(DPL, S, lane, lt);
+    else { lt.mask = 0u; lt.type[0] = 0; lt.pos[0] = 0; lt.len[0] = 0; lt.hyp[0] = 0; lt.p0[0] = 0.0; lt.p1[0] = 0.0; lt.p2[0] = 0.0; }
+}
+// cube -> theta: the table or the source prior of the sampling kernels, else the box as k_generate_live forms it
+template <int DPL>
+__device__ __forceinline__ void pc_max_theta(const PcState &S, const LaneDims<DPL> &ld, const LaneTable<DPL> &lt, const double (&cube)[DPL],
+                                             double (&th)[DPL], int lane, double *ybuf)
+{
+    if (S.prior.kind >= 2) PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf);
+    else th[0] = ld.lo[0] + ld.span[0] * cube[0];
+}
+// determinant of the column-major n x n matrix in LDS (destroyed): det_cm's elimination order (pc_maximise.hip, nelder_mead.f90:168-209), row
+// swaps on a zero pivot included; lane = row.  The caller's stores to M need no barrier of their own.
+__device__ inline double pc_max_det(double *M, int n, int lane)
+{
+    __syncthreads();
+    int sign = 1;
+    for (int k = 0; k < n - 1; ++k) {
+        double pkk = readlane_f64(M[k * n + k], 0);
+        if (pkk == 0.0) {
+            const unsigned long long nz = pc_lanes(lane > k && lane < n && M[k * n + lane] != 0.0);
+            if (nz == 0ull) return 0.0;
+            const int i = __builtin_ctzll(nz);
+            if (lane < n) { const double a = M[lane * n + i], b = M[lane * n + k]; M[lane * n + i] = b; M[lane * n + k] = a; }   // lane = column
+            sign = -sign;
+            __syncthreads();
+            pkk = readlane_f64(M[k * n + k], 0);
+        }
+        if (lane > k && lane < n) {
+            const double m = M[k * n + lane] / pkk;
+            int i = k + 1;
+            for (; i + 3 < n; i += 4) {                // (four columns a step, their loads in flight together: every element the same one operation)
+                double a[4], b[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { a[u] = M[(i + u) * n + lane]; b[u] = M[(i + u) * n + k]; }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) M[(i + u) * n + lane] = a[u] - m * b[u];
+            }
+            for (; i < n; ++i) M[i * n + lane] -= m * M[i * n + k];
+        }
+        __syncthreads();
+    }
+    double d = sign;
+    for (int i = 0; i < n; ++i) d *= M[i * n + i];
+    return readlane_f64(d, 0);
+}
+// log of the prior density in theta at `cube` up to the cube's own (maximiser.F90:179-207): the prior at cube and at D perturbed cubes
+// (dx = 1e-5; a step backwards and a flipped sign at the upper edge), the Jacobian in M, its determinant
+template <int DPL>
+__device__ inline double pc_max_dxdtheta(const PcState &S, const LaneDims<DPL> &ld, const LaneTable<DPL> &lt, const double (&cube)[DPL], int lane,
+                                         double *ybuf, double *M)
+{
+    const int D = S.D;
+    const double dx = 1e-5;
+    double t0[DPL], t1[DPL], c0[DPL];
+    pc_max_theta<DPL>(S, ld, lt, cube, t0, lane, ybuf);
+    int s = 1;
+    for (int i = 0; i < D; ++i) {
+        const bool back = readlane_f64(cube[0], i) + dx >= 1.0;
+        c0[0] = cube[0];
+        if (lane == i) c0[0] = back ? cube[0] - dx : cube[0] + dx;
+        if (back) s = -s;
+        pc_max_theta<DPL>(S, ld, lt, c0, t1, lane, ybuf);
+        if (lane < D) M[i * D + lane] = t1[0] - t0[0];
+    }
+    const double det = pc_max_det(M, D, lane);
+    return (double)D * log(dx) - log((double)s * det);
+}
+
+// candidate values of the posterior leg (maximiser.F90:92-161): logL_i + dXdtheta(cube_i), one wavefront a live row
+template <int DPL>
+__global__ __launch_bounds__(64) void k_max_rank(PcState S, const double *rows /* [n][nT] */, double *val /* [n] */)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double *ybuf = (double *)smem, *M = ybuf + S.D;
+    const int lane = threadIdx.x;
+    const double *row = rows + (size_t)blockIdx.x * S.nT;
+    LaneDims<DPL> ld; LaneTable<DPL> lt;
+    pc_max_lanes<DPL>(S, lane, ld, lt, ybuf);
+    double cube[DPL];
+    cube[0] = ld.on[0] ? row[lane] : 0.5;
+    const double dX = pc_max_dxdtheta<DPL>(S, ld, lt, cube, lane, ybuf, M);
+    if (lane == 0) val[blockIdx.x] = row[S.l0] + dX;
+}
+
+// maximisation_func (maximiser.F90:163-177) behind calculate_point: a point outside the unit cube is logzero without a likelihood call
+template <int DPL>
+__device__ inline double pc_max_func(const PcState &S, const LaneDims<DPL> &ld, const LaneTable<DPL> &lt, const double (&x)[DPL], int lane,
+                                     double *ybuf, double *M, int leg, long long &neval)
+{
+    if (pc_lanes(ld.on[0] && !(x[0] >= 0.0 && x[0] <= 1.0)) != 0ull) return S.logzero;
+    double th[DPL];
+    pc_max_theta<DPL>(S, ld, lt, x, th, lane, ybuf);
+    double v = readlane_f64(like_eval<DPL, 4>(S, th, ld, lane, ybuf), 0);
+    ++neval;
+    if (leg == 1 && v > S.logzero) v += pc_max_dxdtheta<DPL>(S, ld, lt, x, lane, ybuf, M);
+    return isfinite(v) ? v : S.logzero;          // a source may return NaN: the order of the vertices stays total (pc_max_sort)
+}
+// the likelihood call of calculate_point (calculate.f90:40-44): logL of theta (uniform over the wave) and, in phi[0 .. nDer), the derived
+// parameters by the form's own path, as k_generate_live writes a row
+template <int DPL>
+__device__ inline double pc_max_point(const PcState &S, const LaneDims<DPL> &ld, const double (&th)[DPL], int lane, double *ybuf, double *phi)
+{
+#ifdef PCHIP_USER_TERMS
+    double tsum = 0.0;
+    double logL = S.like.kind == PC_LIKE_SOURCE ? like_eval_terms<DPL>(S, th, ld, lane, ybuf, tsum) : like_eval<DPL, 4>(S, th, ld, lane, ybuf);
+#else
+    double logL = like_eval<DPL, 4>(S, th, ld, lane, ybuf);
+#endif
+    logL = readlane_f64(logL, 0);
+    double phi0, phi1;
+    like_phi<DPL, 4>(S, th, ld, lane, phi0, phi1);
+#ifdef PCHIP_USER_TERMS
+    if (S.like.kind == PC_LIKE_SOURCE && S.nDer > 0) like_phi_terms<DPL>(S, th, ld, lane, ybuf, tsum, phi);
+#elif defined(PCHIP_USER_SOURCE)
+    if (S.like.kind == PC_LIKE_SOURCE && S.nDer > 0) like_phi_source<DPL>(S, th, ld, lane, ybuf, phi);
+#endif
+    if (lane == 0 && S.like.kind != PC_LIKE_SOURCE) {
+        if (S.nDer >= 1) phi[0] = phi0;
+        if (S.nDer >= 2) phi[1] = phi1;
+    }
+    return logL;
+}
+// the order of the values: stable, ascending (idx[0] worst, idx[nv - 1] best), rank by counting
+__device__ __forceinline__ void pc_max_sort(const double *F, int *idx, int nv, int lane)
+{
+    __syncthreads();
+    for (int v = lane; v < nv; v += 64) {
+        const double fv = F[v];
+        int r = 0;
+        for (int u = 0; u < nv; ++u) { const double fu = F[u]; r += (fu < fv || (fu == fv && u < v)) ? 1 : 0; }
+        idx[r] = v;
+    }
+    __syncthreads();
+}
+
+// One workgroup of one wavefront per problem.  Problem p: in + p * nin, nin = (D + 1) D + (D + 1) + D + nDer doubles: the start cubes, their
+// values, the posterior mean (theta | phi); hdr[2p] = leg (0 likelihood, 1 posterior), hdr[2p + 1] = a mean is given.  Out, 2 D + 2 nDer + 4
+// doubles a problem: [cube | theta | phi | logL] of the best vertex, dXdtheta there (posterior leg), the likelihood at the mean (likelihood
+// leg), the vertex's value, phi at the mean (likelihood leg); outi[2p], outi[2p + 1] = iterations that moved the simplex, likelihood calls of the search.
+template <int DPL>
+__global__ __launch_bounds__(64) void k_maximise(PcState S, const double *in, const int *hdr, long long max_iter, double *out, long long *outi)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x, D = S.D, n = D, nv = D + 1, p = blockIdx.x;
+    double *ybuf = (double *)smem, *X = ybuf + D, *F = X + (size_t)nv * D, *M = F + nv;
+    int *idx = (int *)(M + (size_t)D * D);
+    const double *pin = in + (size_t)p * ((size_t)nv * D + nv + D + S.nDer);
+    const int leg = __builtin_amdgcn_readfirstlane(hdr[2 * p]), has_mean = __builtin_amdgcn_readfirstlane(hdr[2 * p + 1]);
+    LaneDims<DPL> ld; LaneTable<DPL> lt;
+    pc_max_lanes<DPL>(S, lane, ld, lt, ybuf);
+    for (int v = 0; v < nv; ++v) if (lane < D) X[v * D + lane] = pin[v * D + lane];
+    for (int v = lane; v < nv; v += 64) { const double f0 = pin[nv * D + v]; F[v] = isfinite(f0) ? f0 : S.logzero; idx[v] = v; }
+    const double dl = 1e-5;
+    double det0 = -1.0;
+    long long niter = 0, neval = 0;
+    double xo[DPL], xw[DPL], xr[DPL], xt[DPL];
+    for (long long iter = 0; iter < max_iter; ++iter) {
+        pc_max_sort(F, idx, nv, lane);
+        const int ib = __builtin_amdgcn_readfirstlane(idx[n]), iw = __builtin_amdgcn_readfirstlane(idx[0]), i2 = __builtin_amdgcn_readfirstlane(idx[1]);
+        for (int c = 0; c < n; ++c) if (lane < D) M[c * n + lane] = X[idx[c] * D + lane] - X[ib * D + lane];      // edges from the best vertex
+        const double det1 = fabs(pc_max_det(M, n, lane));
+        if (det0 < 0.0) det0 = det1;
+        const double fb = readlane_f64(F[ib], 0), fw = readlane_f64(F[iw], 0), f2 = readlane_f64(F[i2], 0);
+        if (fb - fw < dl || !(det0 > 0.0) || readlane_f64(pow(det1 / det0, 1.0 / (double)n), 0) < dl) break;
+        double s = 0.0;
+        for (int k = 1; k <= n; ++k) s += ld.on[0] ? X[idx[k] * D + lane] : 0.0;      // centroid of all but the worst, summed in the order of idx
+        xo[0] = ld.on[0] ? s / (double)n : 0.5;
+        xw[0] = ld.on[0] ? X[iw * D + lane] : 0.5;
+        xr[0] = xo[0] + (xo[0] - xw[0]);
+        const double fr = pc_max_func<DPL>(S, ld, lt, xr, lane, ybuf, M, leg, neval);
+        double fnew; bool shrink = false;
+        if (fr <= fb && f2 < fr) { fnew = fr; xt[0] = xr[0]; }
+        else if (fr > fb) {                                                // expansion
+            xt[0] = xo[0] + 2.0 * (xr[0] - xo[0]);
+            const double fe = pc_max_func<DPL>(S, ld, lt, xt, lane, ybuf, M, leg, neval);
+            if (fe > fr) fnew = fe; else { fnew = fr; xt[0] = xr[0]; }
+        } else {                                                           // contraction, else shrink towards the best
+            xt[0] = xo[0] + 0.5 * (xw[0] - xo[0]);
+            fnew = pc_max_func<DPL>(S, ld, lt, xt, lane, ybuf, M, leg, neval);
+            shrink = !(fnew > fw);
+        }
+        if (!shrink) {
+            if (lane < D) X[iw * D + lane] = xt[0];
+            if (lane == 0) F[iw] = fnew;
+        } else {
+            for (int j = 0; j < n; ++j) {
+                const int v = __builtin_amdgcn_readfirstlane(idx[j]);
+                const double xb = ld.on[0] ? X[ib * D + lane] : 0.5, xv = ld.on[0] ? X[v * D + lane] : 0.5;
+                xt[0] = xb + 0.5 * (xv - xb);
+                if (lane < D) X[v * D + lane] = xt[0];
+                const double fv = pc_max_func<DPL>(S, ld, lt, xt, lane, ybuf, M, leg, neval);
+                if (lane == 0) F[v] = fv;
+            }
+        }
+        ++niter;
+    }
+    pc_max_sort(F, idx, nv, lane);
+    // calculate_point at the best vertex: theta, logL, and phi by the form's own path (as k_generate_live writes a row)
+    const int ib = __builtin_amdgcn_readfirstlane(idx[n]);
+    double *row = out + (size_t)p * (2 * D + 2 * S.nDer + 4);
+    const int d0 = 2 * D, l0 = 2 * D + S.nDer;
+    double xb[DPL], th[DPL];
+    xb[0] = ld.on[0] ? X[ib * D + lane] : 0.5;
+    th[0] = 0.0;
+    double logL = S.logzero, dX = 0.0, lmean = 0.0;
+    const double fbest = readlane_f64(F[ib], 0);
+    const bool inside = pc_lanes(ld.on[0] && !(xb[0] >= 0.0 && xb[0] <= 1.0)) == 0ull;
+    if (lane == 0) for (int e = 0; e < S.nDer; ++e) { row[d0 + e] = 0.0; row[l0 + 4 + e] = 0.0; }
+    if (inside) {
+        pc_max_theta<DPL>(S, ld, lt, xb, th, lane, ybuf);
+        logL = pc_max_point<DPL>(S, ld, th, lane, ybuf, row + d0);
+        if (leg == 1) dX = pc_max_dxdtheta<DPL>(S, ld, lt, xb, lane, ybuf, M);
+    }
+    if (leg == 0 && has_mean) {                                            // maximiser.F90:77-80: loglikelihood(mean theta) and the phi it gives there
+        double tm[DPL];
+        tm[0] = ld.on[0] ? pin[nv * D + nv + lane] : 0.0;
+        lmean = pc_max_point<DPL>(S, ld, tm, lane, ybuf, row + l0 + 4);
+    }
+    if (lane < D) { row[lane] = xb[0]; row[D + lane] = th[0]; }
+    if (lane == 0) {
+        row[l0] = logL; row[l0 + 1] = dX; row[l0 + 2] = lmean; row[l0 + 3] = fbest;
+        outi[2 * p] = niter; outi[2 * p + 1] = neval;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // K0: seed choice + random orthonormal bases + whitening
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void select_seed(const PcState &S, unsigned batch, int chain, int &sel, int &slot)
@@ -2047,5 +2292,39 @@ extern "C" int pc_launch_source_prior_eval(const PcState *S, int n, const double
     if (S->like.kind != PC_LIKE_SOURCE || S->prior.kind != 3 || n < 1 || !dpl) return 1;
     const char *name = dpl == 1 ? "k_prior_transform<1>" : (dpl == 2 ? "k_prior_transform<2>" : "k_prior_transform<4>");
     return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D, st, *S, cubes, thetas);
+}
+
+// the device maximiser (pchip_maximise_device): nDims <= 64, any device likelihood under prior kinds 1, 2, 3; the LDS block is held against the
+// device's limit per workgroup (the message in polychord_hip_last_error)
+static int pc_max_lds_fits(const char *who, size_t sh)
+{
+    int dev = 0, lim = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || sh > (size_t)lim) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "%s: %zu bytes of LDS, the device has %d", who, sh, lim);
+        pc_abi_set_last_error(msg);
+        (void)hipGetLastError();
+        return 0;
+    }
+    return 1;
+}
+extern "C" int pc_launch_max_rank(const PcState *S, int n, const double *rows, double *val, hipStream_t st)
+{
+    if (S->D < 1 || S->D > 64 || n < 1) return 1;
+    const size_t sh = sizeof(double) * ((size_t)S->D + (size_t)S->D * S->D);
+    if (!pc_max_lds_fits("k_max_rank", sh)) return 1;
+    if (sh > 48 * 1024 && !pc_rtc_wanted(S)) pc_need_dyn_lds((const void *)k_max_rank<1>, sh);
+    PC_LAUNCH((k_max_rank<1>), dim3(n), dim3(64), sh, st, *S, rows, val);
+    return 0;
+}
+extern "C" int pc_launch_maximise(const PcState *S, int nprob, const double *in, const int *hdr, long long max_iter, double *out, long long *outi, hipStream_t st)
+{
+    if (S->D < 1 || S->D > 64 || nprob < 1) return 1;
+    const size_t sh = sizeof(double) * PC_MAX_LDS_DOUBLES(S->D);
+    if (!pc_max_lds_fits("k_maximise", sh)) return 1;
+    if (sh > 48 * 1024 && !pc_rtc_wanted(S)) pc_need_dyn_lds((const void *)k_maximise<1>, sh);
+    PC_LAUNCH((k_maximise<1>), dim3(nprob), dim3(64), sh, st, *S, in, hdr, max_iter, out, outi);
+    return 0;
 }
 #endif  // __HIPCC_RTC__

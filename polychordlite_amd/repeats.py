@@ -30,13 +30,33 @@ def run_repeats(settings, like, prior, seeds, max_in_flight=4, devices=None, wan
     return _run("pchip_run_repeats_ex", settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree)
 
 
-def run_in_step(settings, like, prior, seeds, max_in_flight=4, devices=None, want_rows=False, write=None, comm=None, agree=None):
+def run_in_step(settings, like, prior, seeds, max_in_flight=4, devices=None, want_rows=False, write=None, comm=None, agree=None, maximise=False):
     """`run_repeats` for any problem that is wholly on the device (pchip_run_in_step): a built-in or a device source likelihood, plain or
     terms form, under the uniform box, a prior table or the handle's own source prior, and settings.ablate bit 15.  Up to `max_in_flight`
     runs of a device go round by round together, every kernel launched once for all of them; each run is bit for bit `_ctypes_api.run` of
     its seed (runs[k]["path"]["slice_step"] counts its nurseries whose sampling launch was shared).  A callback likelihood or a host prior
-    raises.  Arguments and return value as `run_repeats`."""
-    return _run("pchip_run_in_step", settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree)
+    raises.  Arguments and return value as `run_repeats`.  maximise=True: every run's dict gains "maximum" (`_ctypes_api.maximum_dict`), the
+    maximum-likelihood and maximum-posterior points polished from its final live set on the device, two launches for all runs
+    (pchip_maximise_device_many); each is bit for bit `_ctypes_api.maximise_device` of that run alone."""
+    merged, runs = _run("pchip_run_in_step", settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree)
+    if maximise:
+        lib = mg._lib()
+        n = len(runs)
+        res = (api.Result * n)()
+        for k, r in enumerate(runs):
+            C.memmove(C.byref(res[k]), C.byref(r["_owner"].res), C.sizeof(api.Result))      # (borrowed: the dicts keep owning their blocks)
+        mx = (api.Maximum * n)()
+        rc = lib.pchip_maximise_device_many(C.byref(settings), C.byref(like), C.byref(prior), n, res, 0, mx)
+        try:
+            if rc != 0 and not (rc == 1 and all(bool(m.max_point) for m in mx)):
+                msg = lib.polychord_hip_last_error()
+                raise RuntimeError(f"pchip_maximise_device_many failed with code {rc}" + (": " + msg.decode(errors="replace") if msg else ""))
+            for r, m in zip(runs, mx):
+                r["maximum"] = api.maximum_dict(m, settings.nDims, settings.nDerived)
+        finally:
+            for m in mx:
+                lib.pchip_maximum_free(C.byref(m))
+    return merged, runs
 
 
 def _run(symbol, settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree):
