@@ -131,6 +131,9 @@ void pchip_set_capacity(int clusters, int phantom_rows);
  * to the driver -- e.g. after many runs in flight, before a run that sizes its buffers by the memory that is free.
  * polychord_hip_set_option("trim_cache", 0) does the same. */
 void pchip_trim_cache(void);
+/* How many device and pinned blocks the two caches have obtained from the driver and somebody holds now (a run in flight, a result
+ * that has not been freed, the merge's scratch): equal before and after a call that gave back everything it took.  Either may be NULL. */
+void pchip_blocks_in_use(long *device, long *pinned);
 
 typedef struct {
     int nDims, nDerived;

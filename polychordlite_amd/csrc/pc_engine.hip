@@ -67,104 +67,8 @@ extern "C" double polychord_hip_keyed_uniform(unsigned seed, unsigned dom, unsig
 
 namespace {
 
-// Process-wide cache of device blocks and pinned host blocks.  A run allocates ~70 buffers; hipMalloc /
-// hipFree cost O(100 us) each and hipFree synchronises the device, which is as long as the sampling
-// itself at the metric config.  Blocks are keyed by (device, rounded size) and handed back on free;
-// nothing relies on their contents (hipMalloc does not zero either).
 static std::atomic<long long> g_dbg_miss_n[2], g_dbg_miss_ns[2], g_dbg_mk_stream_n{0}, g_dbg_mk_stream_ns{0};      // (PC_DEBUG=5: trips to the driver -- device / pinned blocks, streams)
-struct BlockCache {
-    std::mutex m;
-    std::multimap<std::pair<int, size_t>, void *> free_;
-    std::unordered_map<void *, std::pair<int, size_t>> owner;
-    size_t cached = 0, limit;
-    bool host;
-    BlockCache(bool h, size_t lim) : limit(lim), host(h) {}
-    // eight sizes per octave above 4 KB (at most an eighth more than asked for): arrays sized by what a run found -- its dead
-    // points, its weights -- differ by a few rows from seed to seed, and every near miss was a trip to the driver (a pinned
-    // allocation is milliseconds there once another runtime, PyTorch's, lives in the process)
-    static size_t round_up(size_t b)
-    {
-        if (b < 4096) return (b + 255) & ~(size_t)255;
-        int top = 63 - __builtin_clzll((unsigned long long)b);
-        const size_t step = (size_t)1 << (top - 3);
-        return (b + step - 1) & ~(step - 1);
-    }
-    void *get(size_t bytes)
-    {
-        int dev = 0;
-        if (!host) (void)hipGetDevice(&dev);
-        const size_t sz = round_up(bytes ? bytes : 1);
-        if (!host && sz >= (256u << 10) && g_inject_fault.load() == 1) { g_inject_fault = 0; engine_fail(PC_RC_MEMORY, "out of device memory (%zu bytes): injected", sz); }
-        {
-            std::lock_guard<std::mutex> g(m);
-            auto it = free_.find({dev, sz});
-            if (it != free_.end()) { void *p = it->second; free_.erase(it); cached -= sz; return p; }
-        }
-        void *p = nullptr;
-        const auto q0 = std::chrono::steady_clock::now();
-        hipError_t e = host ? hipHostMalloc(&p, sz) : hipMalloc(&p, sz);
-        g_dbg_miss_n[host ? 1 : 0]++; g_dbg_miss_ns[host ? 1 : 0] += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - q0).count();
-        if (e != hipSuccess) {          // give the cached blocks back and retry once
-            trim();
-            e = host ? hipHostMalloc(&p, sz) : hipMalloc(&p, sz);
-        }
-        if (e != hipSuccess) { (void)hipGetLastError(); engine_fail(PC_RC_MEMORY, "out of %s memory (%zu bytes): %s", host ? "pinned host" : "device", sz, hipGetErrorString(e)); }
-        std::lock_guard<std::mutex> g(m);
-        owner[p] = {dev, sz};
-        return p;
-    }
-    bool put(void *p)                   // false: not one of ours
-    {
-        {
-            std::lock_guard<std::mutex> g(m);
-            auto it = owner.find(p);
-            if (it == owner.end()) return false;
-            if (cached + it->second.second <= limit) { free_.insert({it->second, p}); cached += it->second.second; return true; }
-            owner.erase(it);
-        }
-        if (host) (void)hipHostFree(p); else (void)hipFree(p);      // (over the limit: back to the driver, and not under the lock)
-        return true;
-    }
-    // a run's hundred-odd blocks at its end in one visit: eight threads tearing runs down at once spent most of that time queueing
-    // for the lock, block by block
-    void put_many(const std::vector<void *> &ps)
-    {
-        std::vector<void *> over;
-        {
-            std::lock_guard<std::mutex> g(m);
-            for (void *p : ps) {
-                auto it = owner.find(p);
-                if (it == owner.end()) continue;
-                if (cached + it->second.second <= limit) { free_.insert({it->second, p}); cached += it->second.second; }
-                else { owner.erase(it); over.push_back(p); }
-            }
-        }
-        for (void *p : over) { if (host) (void)hipHostFree(p); else (void)hipFree(p); }
-    }
-    void trim()
-    {
-        std::lock_guard<std::mutex> g(m);
-        for (auto &kv : free_) { if (host) (void)hipHostFree(kv.second); else (void)hipFree(kv.second); owner.erase(kv.second); }
-        free_.clear(); cached = 0;
-    }
-};
-// never destroyed: the HIP runtime may already be gone when static destructors run
-BlockCache &dcache() { static BlockCache *c = new BlockCache(false, (size_t)64 << 30); return *c; }
-BlockCache &hcache() { static BlockCache *c = new BlockCache(true, (size_t)12 << 30); return *c; }
-
-// PC_POISON=1 (tests): every device block is filled with 0x5A bytes when it is handed out -- ints become 1515870810,
-// doubles 2.6e127 -- so that a buffer some path forgets to initialise fails loudly instead of working by the luck of
-// what the previous run left in it
-template <class T> T *dalloc(size_t n)
-{
-    T *p = (T *)dcache().get(sizeof(T) * (n ? n : 1));
-    if (pc_env().poison) { (void)hipMemset((void *)p, 0x5A, sizeof(T) * (n ? n : 1)); (void)hipDeviceSynchronize(); }
-    return p;
-}
-static thread_local std::vector<void *> *tl_dfree_batch = nullptr;      // (Engine::destroy: the blocks are collected and given back together)
-template <class T> void dfree(T *&p) { if (p) { if (tl_dfree_batch) tl_dfree_batch->push_back((void *)p); else dcache().put((void *)p); } p = nullptr; }
-template <class T> T *halloc(size_t n) { return (T *)hcache().get(sizeof(T) * (n ? n : 1)); }
-void hfree(void *p) { if (p && !hcache().put(p)) std::free(p); }
+#include "pc_blocks.h"      // BlockCache and dalloc / dfree / halloc / hfree; RunBlocks: the ledger of the blocks a run holds
 
 // streams and events are pooled for the same reason (creation / destruction synchronise with the driver)
 struct HandlePool {
@@ -485,6 +389,7 @@ struct Engine {
     std::vector<unsigned> split_child, split_parent; std::vector<double> split_logfrac;
     std::vector<double> h_lo, h_hi;
     PcState S{};
+    RunBlocks blocks;                         // every device and pinned block the run holds: allocated through it, released from it (destroy)
     hipStream_t st = nullptr;
     hipStream_t st_copy = nullptr;            // dead rows leave for the host while the run goes on
     bool st_copy_shared = false;              // ... one of the cohort's two (not this run's to give back)
@@ -526,18 +431,16 @@ struct Engine {
 
     void alloc_phantom_side(int Pcap)
     {
-        ph2 = dalloc<double>((size_t)Pcap * S.nT); phL2 = dalloc<double>(Pcap); phC2 = dalloc<unsigned>(Pcap);
-        phU2 = dalloc<unsigned long long>(Pcap); keep = dalloc<unsigned char>(Pcap); blk = dalloc<int>((Pcap + 255) / 256 + 1);
+        ph2 = blocks.dev<double>((size_t)Pcap * S.nT); phL2 = blocks.dev<double>(Pcap); phC2 = blocks.dev<unsigned>(Pcap);
+        phU2 = blocks.dev<unsigned long long>(Pcap); keep = blocks.dev<unsigned char>(Pcap); blk = blocks.dev<int>((Pcap + 255) / 256 + 1);
     }
 
     // a small table of the set-up on its way to the device: through a pinned block of the cache, in stream order (a blocking copy
     // from pageable memory was 0.1 ms as a rule and 4 ... 11 ms now and then -- one run in eight or so -- while the driver pinned
     // the vector's pages); the blocks go back at the teardown
-    std::vector<void *> setup_staged;
     void upload(void *dst, const void *src, size_t bytes)
     {
-        void *h = halloc<char>(bytes);
-        setup_staged.push_back(h);
+        void *h = blocks.pin<char>(bytes);
         std::memcpy(h, src, bytes);
         HIPCHK(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, st));
     }
@@ -623,7 +526,7 @@ struct Engine {
         // dynamic nlive tables
         S.n_nlives = c.n_nlives;
         if (c.n_nlives > 0) {
-            d_dynL = dalloc<double>(c.n_nlives); d_dynN = dalloc<int>(c.n_nlives);
+            d_dynL = blocks.dev<double>(c.n_nlives); d_dynN = blocks.dev<int>(c.n_nlives);
             upload(d_dynL, c.loglikes, sizeof(double) * c.n_nlives);
             upload(d_dynN, c.nlives, sizeof(int) * c.n_nlives);
         }
@@ -645,7 +548,7 @@ struct Engine {
                 engine_fail(PC_RC_SETTINGS, "prior.kind = 3 (source prior): device source handle %d defines no pchip_prior_param -- make it with pchip_source_create_prior", like.source);
             S.src_id = like.source;
             src_terms = pc_rtc_source_terms(like.source) > 0;
-            if (n > 0) { d_src = dalloc<double>((size_t)n); upload(d_src, h, sizeof(double) * (size_t)n); S.src_data = d_src; S.src_ndata = n; }
+            if (n > 0) { d_src = blocks.dev<double>((size_t)n); upload(d_src, h, sizeof(double) * (size_t)n); S.src_data = d_src; S.src_ndata = n; }
         }
         // a source prior is the handle's own function, inside the sampling kernels: there is no host function for callback mode to call
         if (prior.kind == PCHIP_PRIOR_SOURCE && like.kind != PC_LIKE_SOURCE)
@@ -654,7 +557,7 @@ struct Engine {
         if (like.kind == PC_LIKE_CORR_GAUSSIAN) {
             std::vector<double> T((size_t)D * D);
             for (int a = 0; a < D; ++a) for (int b = 0; b < D; ++b) T[(size_t)b * D + a] = like.invcov[(size_t)a * D + b];
-            d_invcovT = dalloc<double>((size_t)D * D); d_mean = dalloc<double>(D);
+            d_invcovT = blocks.dev<double>((size_t)D * D); d_mean = blocks.dev<double>(D);
             upload(d_invcovT, T.data(), sizeof(double) * D * D);
             upload(d_mean, like.mean, sizeof(double) * D);
             S.like.invcov = d_invcovT; S.like.mean = d_mean;
@@ -684,66 +587,66 @@ struct Engine {
         }
         S.prior.kind = callback_mode ? (prior_kind == PCHIP_PRIOR_TABLE ? 0 : prior_kind) : prior_kind; S.prior.lo = nullptr; S.prior.hi = nullptr;
         if (prior_kind == 1 && p_lo && p_hi) {
-            d_lo = dalloc<double>(D); d_hi = dalloc<double>(D);
+            d_lo = blocks.dev<double>(D); d_hi = blocks.dev<double>(D);
             upload(d_lo, p_lo, sizeof(double) * D);
             upload(d_hi, p_hi, sizeof(double) * D);
             S.prior.lo = d_lo; S.prior.hi = d_hi;
         }
         if (S.prior.kind == PCHIP_PRIOR_TABLE) {
             const std::vector<double> tp = ptab.dev_par(); const std::vector<int> ti = ptab.dev_int();
-            d_lo = dalloc<double>(tp.size()); d_hi = dalloc<double>((ti.size() + 1) / 2);
+            d_lo = blocks.dev<double>(tp.size()); d_hi = blocks.dev<double>((ti.size() + 1) / 2);
             upload(d_lo, tp.data(), sizeof(double) * tp.size());
             upload(d_hi, ti.data(), sizeof(int) * ti.size());
             S.prior.lo = d_lo; S.prior.hi = d_hi; S.src_pad = (int)ptab.mask;
         }
         // state arrays
         const int Ncap = S.Ncap, maxc = S.maxc, nT = S.nT, nr = S.nr;
-        S.live = dalloc<double>((size_t)Ncap * nT); S.live_logL = dalloc<double>(Ncap);
-        S.live_cluster = dalloc<int>(Ncap); S.live_pos = dalloc<int>(Ncap); S.live_entry = dalloc<double>(Ncap);
-        S.cl_list = dalloc<int>((size_t)maxc * Ncap); S.cl_n = dalloc<int>(maxc);
-        S.logZp = dalloc<double>(maxc); S.logXp = dalloc<double>(maxc); S.logZXp = dalloc<double>(maxc);
-        S.logZp2 = dalloc<double>(maxc); S.logZpXp = dalloc<double>(maxc); S.logLp = dalloc<double>(maxc);
-        S.XpXq = dalloc<double>(2 * (size_t)maxc * maxc); S.imin_slot = dalloc<int>(maxc);      // (the second half: k_consume_clp's copy of the matrix in linear space, made anew by every pass)
-        S.lse_ref = dalloc<double>(maxc); S.lse_sum = dalloc<double>(maxc); S.death_thr = dalloc<double>(maxc);
-        S.cl_uid = dalloc<unsigned>(maxc);
-        S.chol = dalloc<double>((size_t)maxc * D * D); S.cov = dalloc<double>((size_t)maxc * D * D);
-        S.logZp_dead = dalloc<double>(S.maxc_dead); S.logZp2_dead = dalloc<double>(S.maxc_dead); S.cl_uid_dead = dalloc<unsigned>(S.maxc_dead);
-        S.phantom = dalloc<double>((size_t)S.Pcap * nT); S.ph_logL = dalloc<double>(S.Pcap);
-        S.ph_cuid = dalloc<unsigned>(S.Pcap); S.ph_uid = dalloc<unsigned long long>(S.Pcap);
+        S.live = blocks.dev<double>((size_t)Ncap * nT); S.live_logL = blocks.dev<double>(Ncap);
+        S.live_cluster = blocks.dev<int>(Ncap); S.live_pos = blocks.dev<int>(Ncap); S.live_entry = blocks.dev<double>(Ncap);
+        S.cl_list = blocks.dev<int>((size_t)maxc * Ncap); S.cl_n = blocks.dev<int>(maxc);
+        S.logZp = blocks.dev<double>(maxc); S.logXp = blocks.dev<double>(maxc); S.logZXp = blocks.dev<double>(maxc);
+        S.logZp2 = blocks.dev<double>(maxc); S.logZpXp = blocks.dev<double>(maxc); S.logLp = blocks.dev<double>(maxc);
+        S.XpXq = blocks.dev<double>(2 * (size_t)maxc * maxc); S.imin_slot = blocks.dev<int>(maxc);      // (the second half: k_consume_clp's copy of the matrix in linear space, made anew by every pass)
+        S.lse_ref = blocks.dev<double>(maxc); S.lse_sum = blocks.dev<double>(maxc); S.death_thr = blocks.dev<double>(maxc);
+        S.cl_uid = blocks.dev<unsigned>(maxc);
+        S.chol = blocks.dev<double>((size_t)maxc * D * D); S.cov = blocks.dev<double>((size_t)maxc * D * D);
+        S.logZp_dead = blocks.dev<double>(S.maxc_dead); S.logZp2_dead = blocks.dev<double>(S.maxc_dead); S.cl_uid_dead = blocks.dev<unsigned>(S.maxc_dead);
+        S.phantom = blocks.dev<double>((size_t)S.Pcap * nT); S.ph_logL = blocks.dev<double>(S.Pcap);
+        S.ph_cuid = blocks.dev<unsigned>(S.Pcap); S.ph_uid = blocks.dev<unsigned long long>(S.Pcap);
         alloc_phantom_side(S.Pcap);
-        S.dead = dalloc<double>((size_t)S.Dcap * nT); S.dead_logw = dalloc<double>(S.Dcap);
-        S.dead_postX = dalloc<double>(S.Dcap); S.dead_postZ = dalloc<double>(S.Dcap); S.dead_cuid = dalloc<unsigned>(S.Dcap);
-        S.dead_entry = dalloc<double>(S.Dcap);
-        S.babies = dalloc<double>((size_t)B * nr * nT); S.baby_logL = dalloc<double>((size_t)B * nr); S.baby_logL_T = dalloc<double>((size_t)B * nr);
-        S.ch_cluster = dalloc<int>(B); S.ch_epoch = dalloc<int>(B); S.ch_nlike = dalloc<int>(B); S.ch_seed_slot = dalloc<int>(B);
-        S.ch_contour = dalloc<double>(B);
-        if (S.ngrade > 1) { S.ch_nlike_g = dalloc<int>((size_t)B * PC_MAX_GRADE); h_nlike_g.assign((size_t)B * PC_MAX_GRADE, 0); }
+        S.dead = blocks.dev<double>((size_t)S.Dcap * nT); S.dead_logw = blocks.dev<double>(S.Dcap);
+        S.dead_postX = blocks.dev<double>(S.Dcap); S.dead_postZ = blocks.dev<double>(S.Dcap); S.dead_cuid = blocks.dev<unsigned>(S.Dcap);
+        S.dead_entry = blocks.dev<double>(S.Dcap);
+        S.babies = blocks.dev<double>((size_t)B * nr * nT); S.baby_logL = blocks.dev<double>((size_t)B * nr); S.baby_logL_T = blocks.dev<double>((size_t)B * nr);
+        S.ch_cluster = blocks.dev<int>(B); S.ch_epoch = blocks.dev<int>(B); S.ch_nlike = blocks.dev<int>(B); S.ch_seed_slot = blocks.dev<int>(B);
+        S.ch_contour = blocks.dev<double>(B);
+        if (S.ngrade > 1) { S.ch_nlike_g = blocks.dev<int>((size_t)B * PC_MAX_GRADE); h_nlike_g.assign((size_t)B * PC_MAX_GRADE, 0); }
         {   // log k for the evidence update of the serial kernel
             std::vector<double> ln((size_t)Ncap + 4);
             ln[0] = -PC_HUGE;
             for (int k = 1; k < Ncap + 4; ++k) ln[k] = std::log((double)k);
-            d_logn = dalloc<double>(ln.size());
+            d_logn = blocks.dev<double>(ln.size());
             upload(d_logn, ln.data(), sizeof(double) * ln.size());
             S.logn = d_logn;
         }
         S.nn_list = nullptr; S.nn_slot_owner = nullptr; S.nn_chain_slot = nullptr; S.nn_pts = nullptr; S.nn_code = nullptr; S.nn_valid = 0;
         if (c.do_clustering) {      // candidate lists of the nearest-cluster search (k_nn_lists)
-            S.nn_list = dalloc<int>((size_t)B * nr * PC_NN_K); S.nn_slot_owner = dalloc<int>(Ncap); S.nn_chain_slot = dalloc<int>(B);
-            S.nn_pts = dalloc<double>((size_t)(Ncap + B) * D); S.nn_code = dalloc<int>((size_t)2 * Ncap + B + 64);      // (codes of the candidates, then the ranks of the live points and their number: k_sort_live)
-            if (!sub_dims.empty()) { c_subdims = dalloc<int>(sub_dims.size()); upload(c_subdims, sub_dims.data(), sizeof(int) * sub_dims.size()); }
+            S.nn_list = blocks.dev<int>((size_t)B * nr * PC_NN_K); S.nn_slot_owner = blocks.dev<int>(Ncap); S.nn_chain_slot = blocks.dev<int>(B);
+            S.nn_pts = blocks.dev<double>((size_t)(Ncap + B) * D); S.nn_code = blocks.dev<int>((size_t)2 * Ncap + B + 64);      // (codes of the candidates, then the ranks of the live points and their number: k_sort_live)
+            if (!sub_dims.empty()) { c_subdims = blocks.dev<int>(sub_dims.size()); upload(c_subdims, sub_dims.data(), sizeof(int) * sub_dims.size()); }
         }
-        S.nhat = dalloc<double>((size_t)B * nr * D); S.nhat_w = dalloc<double>((size_t)B * nr);
+        S.nhat = blocks.dev<double>((size_t)B * nr * D); S.nhat_w = blocks.dev<double>((size_t)B * nr);
         const bool ms_pre = S.like.kind == PC_LIKE_CORR_GAUSSIAN && D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !(S.ablate & PC_ABL_FUNCTOR) && !pc_env().ms_pre_off && S.prior.kind < PCHIP_PRIOR_TABLE;
-        S.nhat_Ms = ms_pre ? dalloc<double>((size_t)B * nr * D) : nullptr;
-        S.ch_My = ms_pre ? dalloc<double>((size_t)B * D) : nullptr;
+        S.nhat_Ms = ms_pre ? blocks.dev<double>((size_t)B * nr * D) : nullptr;
+        S.ch_My = ms_pre ? blocks.dev<double>((size_t)B * D) : nullptr;
         const bool split_off = pc_env().nhats_split_off;
         // 64 < nDims <= 128, one grade: k_nhats_q<32, 1> leaves a basis register-major, 32 x 512 doubles
         const bool split_q = D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !split_off && !callback_mode;
         // 24 < nDims <= 64, one grade (round 5): k_nhats_q<8 / 16, 1> leaves a basis thread by thread, 16 HV^2 doubles
         const bool split_m = D > 24 && D <= 64 && S.ngrade <= 1 && !S.seq_mode && !split_off && !callback_mode;
         const size_t raw_n = split_q ? (size_t)B * S.nb_total * 32 * 512 : split_m ? (size_t)B * S.nb_total * (D <= 32 ? 1024 : 4096) : (size_t)B * S.nb_total * D * D + (size_t)B * 33 + 8;      // (+ the chains' deck records, 66 ints each: pc_deck_record, pc_sample.hip)
-        S.nhat_raw = ((D <= 24 && !S.seq_mode && !split_off) || split_q || split_m) ? dalloc<double>(raw_n)
-                   : (D > 128 ? dalloc<double>((size_t)B * S.nb_total * D * 256) : nullptr);   // k_nhats_big keeps its bases there
+        S.nhat_raw = ((D <= 24 && !S.seq_mode && !split_off) || split_q || split_m) ? blocks.dev<double>(raw_n)
+                   : (D > 128 ? blocks.dev<double>((size_t)B * S.nb_total * D * 256) : nullptr);   // k_nhats_big keeps its bases there
         // split launch: two buffers, so that the bases of nursery b + 1 can be drawn at any time while nursery b's are read
         // (nDims > 64: the bases cost more than the rest of a nursery's round -- they are drawn up to three nurseries ahead,
         //  through the updates as well)
@@ -752,21 +655,21 @@ struct Engine {
         //  contraction + row copies + the host's look at the stamp, which is why enqueueing k_slice ahead changed nothing)
         raw_depth = split_q ? RAW_RING : std::min((int)RAW_RING, pc_env().raw_depth);
         raw_buf[0] = S.nhat_raw;
-        for (int r = 1; r < raw_depth; ++r) raw_buf[r] = ((D <= 24 || split_q || split_m) && S.nhat_raw) ? dalloc<double>(raw_n) : nullptr;
-        S.plan = dalloc<PcPlan>(B); S.slot_src = dalloc<int>(Ncap); S.slot_step = dalloc<int>(Ncap); S.slot_dead = dalloc<int>(Ncap); HIPCHK(hipMemsetAsync(S.slot_dead, 0xFF, sizeof(int) * Ncap, st)); S.defer_update = 0; S.sort_slot = dalloc<int>(Ncap + 64); S.sort_key = dalloc<unsigned long long>(Ncap + 64);
-        S.ctl = dalloc<PcCtl>(1);
-        d_total = dalloc<int>(PC_UPD_CTR_INTS); HIPCHK(hipMemsetAsync(d_total, 0, sizeof(int) * PC_UPD_CTR_INTS, st));      // (the count, and the update chain's tickets: dalloc recycles memory as it is)
+        for (int r = 1; r < raw_depth; ++r) raw_buf[r] = ((D <= 24 || split_q || split_m) && S.nhat_raw) ? blocks.dev<double>(raw_n) : nullptr;
+        S.plan = blocks.dev<PcPlan>(B); S.slot_src = blocks.dev<int>(Ncap); S.slot_step = blocks.dev<int>(Ncap); S.slot_dead = blocks.dev<int>(Ncap); HIPCHK(hipMemsetAsync(S.slot_dead, 0xFF, sizeof(int) * Ncap, st)); S.defer_update = 0; S.sort_slot = blocks.dev<int>(Ncap + 64); S.sort_key = blocks.dev<unsigned long long>(Ncap + 64);
+        S.ctl = blocks.dev<PcCtl>(1);
+        d_total = blocks.dev<int>(PC_UPD_CTR_INTS); HIPCHK(hipMemsetAsync(d_total, 0, sizeof(int) * PC_UPD_CTR_INTS, st));      // (the count, and the update chain's tickets: dalloc recycles memory as it is)
         if (callback_mode) {
-            d_cs = (void *)dalloc<char>(pc_chain_state_size() * B); d_x0s = dalloc<double>((size_t)B * D); d_prop = dalloc<double>((size_t)B * D);
+            d_cs = (void *)blocks.dev<char>(pc_chain_state_size() * B); d_x0s = blocks.dev<double>((size_t)B * D); d_prop = blocks.dev<double>((size_t)B * D);
             const size_t nans = (size_t)B * (1 + D + std::max(1, nDer));
-            d_ans = dalloc<double>(nans);
-            d_decks = dalloc<int>((size_t)B * nr);
-            hp_prop = halloc<double>((size_t)B * D); hp_ans = halloc<double>(nans); hp_need = halloc<int>(B);
+            d_ans = blocks.dev<double>(nans);
+            d_decks = blocks.dev<int>((size_t)B * nr);
+            hp_prop = blocks.pin<double>((size_t)B * D); hp_ans = blocks.pin<double>(nans); hp_need = blocks.pin<int>(B);
             std::memset(hp_ans, 0, sizeof(double) * nans); std::memset(hp_need, 0, sizeof(int) * B);
             HIPCHK(hipMemset(d_cs, 0, pc_chain_state_size() * B));
         }
-        h_ctl = halloc<PcCtl>(1);
-        h_note = halloc<PcCtl>(1);                    // (hipHostMalloc memory is mapped and coherent: the device stores straight into it)
+        h_ctl = blocks.pin<PcCtl>(1);
+        h_note = blocks.pin<PcCtl>(1);                    // (hipHostMalloc memory is mapped and coherent: the device stores straight into it)
         std::memset(h_note, 0, sizeof(PcCtl)); note_seq = 0;
         { void *dp = nullptr; HIPCHK(hipHostGetDevicePointer(&dp, h_note, 0)); S.ctl_host = (PcCtl *)dp; }
         S.notify_seq = 0;
@@ -801,11 +704,8 @@ struct Engine {
     {
         if (fib) {
             fib->yield();
-            if (fib->cancel) {      // resumed to unwind: give back what this wait was for, then out through the frames of round_finish
-                for (const Fetch &f : fetching) hfree(f.h);
-                fetching.clear(); own_fetches.clear();
-                for (void *h : staged_up) hfree(h);
-                staged_up.clear();
+            if (fib->cancel) {      // resumed to unwind, out through the frames of round_finish: what this wait was for stays in the ledger, for destroy()
+                fetching.clear(); own_fetches.clear(); staged_up.clear();
                 throw FiberCancelled{};
             }
             return;
@@ -827,7 +727,7 @@ struct Engine {
     void fetch_raw(void *dst, const void *src, size_t bytes)
     {
         if (!bytes) return;
-        void *h = halloc<char>(bytes);
+        void *h = blocks.pin<char>(bytes);
         fetching.push_back({h, dst, bytes});
         hipStream_t q = st;
         if (co && batch_copies()) co->post_copies.push_back({(uintptr_t)h, (uintptr_t)src, (uintptr_t)bytes});
@@ -843,9 +743,9 @@ struct Engine {
     {
         if (!own_fetches.empty()) { std::vector<std::array<uintptr_t, 3>> c; c.swap(own_fetches); pc_copy_many(c, st); }
         sync_point();
-        for (const Fetch &f : fetching) { std::memcpy(f.dst, f.h, f.bytes); hfree(f.h); }
+        for (Fetch &f : fetching) { std::memcpy(f.dst, f.h, f.bytes); blocks.release(f.h); }
         fetching.clear();
-        for (void *h : staged_up) hfree(h);
+        for (void *&h : staged_up) blocks.release(h);
         staged_up.clear();
     }
     // host -> device, through a pinned block, in stream order (the block goes back at the next wait)
@@ -854,7 +754,7 @@ struct Engine {
     {
         if (!bytes) return;
         direct_op();
-        void *h = halloc<char>(bytes);
+        void *h = blocks.pin<char>(bytes);
         staged_up.push_back(h);
         std::memcpy(h, src, bytes);
         // (runs in step: with the other copies at the head of the next launch -- what was written down before this call has been launched
@@ -869,7 +769,7 @@ struct Engine {
     {
         if (!bytes) return;
         if (!co) { send_raw(dst, src, bytes); return; }
-        void *h = halloc<char>(bytes);
+        void *h = blocks.pin<char>(bytes);
         staged_up.push_back(h);
         std::memcpy(h, src, bytes);
         hipStream_t q = st;
@@ -938,18 +838,12 @@ struct Engine {
     {
         if (co) co->flush();      // (what the runs in step have written down is launched before an array moves)
         HIPCHK(hipStreamSynchronize(st_copy));        // rows still travelling from the old array
-        auto grow = [&](auto *&p, size_t per) {
-            using T = std::remove_reference_t<decltype(*p)>;
-            T *q = dalloc<T>((size_t)nd * per);
-            HIPCHK(hipMemcpyAsync(q, p, sizeof(T) * (size_t)h_ctl->ndead * per, hipMemcpyDeviceToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));
-            dfree(p); p = q;
-        };
+        auto grow = [&](auto *&p, size_t per) { blocks.regrow(p, (size_t)nd * per, (size_t)h_ctl->ndead * per, st); };
         grow(S.dead, S.nT); grow(S.dead_logw, 1); grow(S.dead_postX, 1); grow(S.dead_postZ, 1); grow(S.dead_cuid, 1); grow(S.dead_entry, 1);
         S.Dcap = nd;
         // the pinned mirror the rows are streamed into grows with the array (the same capacities in every run: the block comes
         // back from the cache; sized by the final count at the end it was a fresh multi-GB pinning and a second copy of every row)
-        if (h_dead && (size_t)nd > h_dead_cap) { hfree(h_dead); h_dead_cap = (size_t)nd; h_dead = halloc<double>(h_dead_cap * S.nT); h_dead_copied = 0; }
+        if (h_dead && (size_t)nd > h_dead_cap) { blocks.release(h_dead); h_dead_cap = (size_t)nd; h_dead = blocks.pin<double>(h_dead_cap * S.nT); h_dead_copied = 0; }
     }
 
     // The reference reallocates its phantom arrays whenever they fill up (run_time_info.f90:747-757 via
@@ -965,15 +859,9 @@ struct Engine {
         if (g_inject_fault.load() == 3) { g_inject_fault = 0; engine_fail(PC_RC_MEMORY, "out of device memory growing the phantom array to %lld rows (injected)", np); }
         const size_t used = (size_t)std::min<long long>(h_ctl->nphantom, S.Pcap);
         HIPCHK(hipStreamSynchronize(st));
-        auto grow = [&](auto *&p, size_t per) {
-            using T = std::remove_reference_t<decltype(*p)>;
-            T *q = dalloc<T>((size_t)np * per);
-            if (used) HIPCHK(hipMemcpyAsync(q, p, sizeof(T) * used * per, hipMemcpyDeviceToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));
-            dfree(p); p = q;
-        };
+        auto grow = [&](auto *&p, size_t per) { blocks.regrow(p, (size_t)np * per, used * per, st); };
         grow(S.phantom, S.nT); grow(S.ph_logL, 1); grow(S.ph_cuid, 1); grow(S.ph_uid, 1);
-        dfree(ph2); dfree(phL2); dfree(phC2); dfree(phU2); dfree(keep); dfree(blk);
+        blocks.release(ph2); blocks.release(phL2); blocks.release(phC2); blocks.release(phU2); blocks.release(keep); blocks.release(blk);
         alloc_phantom_side((int)np);
         S.Pcap = (int)np;
     }
@@ -981,7 +869,6 @@ struct Engine {
     // pool mode: the phantom array is full -- drop what the updates have invalidated (general clean: flags, scan, scatter into
     // the alternate buffers), grow if that is not enough.  Between nurseries only.
     long long pool_cursor = 0;
-    double *babies_own = nullptr;
     // the phantom array is full: the phantoms that are still wanted move to the front of the alternate buffers.  In step with other
     // runs the clean is launched for all of them at once and waited for once (compact_wanted / compact_record / compact_finish)
     bool compact_wanted() const { return S.pool && h_ctl->status == PC_ST_RUNNING && h_ctl->i_nursery == 0 && pool_cursor + (long long)B * S.nr > S.Pcap; }
@@ -1021,13 +908,7 @@ struct Engine {
         if (co) co->flush();      // (what the runs in step have written down is launched before an array moves)
         HIPCHK(hipStreamSynchronize(st));
         const size_t used = (size_t)std::min(h_ctl->ncluster_dead, S.maxc_dead);
-        auto grow = [&](auto *&p) {
-            using T = std::remove_reference_t<decltype(*p)>;
-            T *q = dalloc<T>((size_t)nd);
-            if (used) HIPCHK(hipMemcpy(q, p, sizeof(T) * used, hipMemcpyDeviceToDevice));
-            dfree(p); p = q;
-        };
-        grow(S.logZp_dead); grow(S.logZp2_dead); grow(S.cl_uid_dead);
+        blocks.regrow(S.logZp_dead, (size_t)nd, used, st); blocks.regrow(S.logZp2_dead, (size_t)nd, used, st); blocks.regrow(S.cl_uid_dead, (size_t)nd, used, st);
         S.maxc_dead = nd;
     }
 
@@ -1039,36 +920,31 @@ struct Engine {
         if (mn > 16384) engine_fail(PC_RC_LIMIT, "more than 16384 clusters");
         if (co) co->flush();
         HIPCHK(hipStreamSynchronize(st));
-        auto grow_d = [&](double *&p, double fill) {
-            std::vector<double> v = dl(p, (size_t)mo); v.resize(mn, fill);
-            dfree(p); p = dalloc<double>(mn); ul(p, v);
+        auto grow_d = [&](auto *&p, auto fill) {      // (through the host: the new entries get their initial values)
+            using T = std::remove_reference_t<decltype(*p)>;
+            std::vector<T> v = dl((const T *)p, (size_t)mo); v.resize(mn, (T)fill);
+            blocks.release(p); p = blocks.dev<T>(mn); ul(p, v);
         };
         grow_d(S.logZp, cfg.logzero); grow_d(S.logZXp, cfg.logzero); grow_d(S.logZp2, cfg.logzero); grow_d(S.logZpXp, cfg.logzero);
         grow_d(S.logLp, cfg.logzero); grow_d(S.logXp, 0.0); grow_d(S.lse_ref, 0.0); grow_d(S.lse_sum, 0.0); grow_d(S.death_thr, -PC_HUGE);
-        { std::vector<int> v = dl(S.cl_n, (size_t)mo); v.resize(mn, 0); dfree(S.cl_n); S.cl_n = dalloc<int>(mn); ul(S.cl_n, v); }
-        { std::vector<int> v = dl(S.imin_slot, (size_t)mo); v.resize(mn, 0); dfree(S.imin_slot); S.imin_slot = dalloc<int>(mn); ul(S.imin_slot, v); }
-        { std::vector<unsigned> v = dl(S.cl_uid, (size_t)mo); v.resize(mn, 0u); dfree(S.cl_uid); S.cl_uid = dalloc<unsigned>(mn); ul(S.cl_uid, v); }
+        grow_d(S.cl_n, 0); grow_d(S.imin_slot, 0); grow_d(S.cl_uid, 0u);
         {   // the cross-volume matrix changes its leading dimension
             std::vector<double> o = dl(S.XpXq, (size_t)mo * mo), v((size_t)mn * mn, 0.0);
             for (int a = 0; a < mo; ++a) std::copy(o.begin() + (size_t)a * mo, o.begin() + (size_t)(a + 1) * mo, v.begin() + (size_t)a * mn);
-            dfree(S.XpXq); S.XpXq = dalloc<double>(2 * (size_t)mn * mn); ul(S.XpXq, v);
+            blocks.release(S.XpXq); S.XpXq = blocks.dev<double>(2 * (size_t)mn * mn); ul(S.XpXq, v);
         }
-        {
-            int *q = dalloc<int>((size_t)mn * Ncap);
-            HIPCHK(hipMemcpy(q, S.cl_list, sizeof(int) * (size_t)mo * Ncap, hipMemcpyDeviceToDevice));
-            dfree(S.cl_list); S.cl_list = q;
-        }
+        blocks.regrow(S.cl_list, (size_t)mn * Ncap, (size_t)mo * Ncap, st);
         auto grow_mat = [&](double *&p) {
-            double *q = dalloc<double>((size_t)mn * DD);
+            double *q = blocks.dev<double>((size_t)mn * DD);
             HIPCHK(hipMemcpy(q, p, sizeof(double) * (size_t)mo * DD, hipMemcpyDeviceToDevice));
             std::vector<double> id((size_t)(mn - mo) * DD, 0.0);
             for (int c = 0; c < mn - mo; ++c) for (int a = 0; a < S.D; ++a) id[(size_t)c * DD + (size_t)a * S.D + a] = 1.0;
             HIPCHK(hipMemcpy(q + (size_t)mo * DD, id.data(), sizeof(double) * id.size(), hipMemcpyHostToDevice));
-            dfree(p); p = q;
+            blocks.release(p); p = q;
         };
         grow_mat(S.chol); grow_mat(S.cov);
         clus.regrow_counts(mn);
-        dfree(psum); dfree(pcnt); dfree(pcov); dfree(mean); dfree(count); cov_chunks_cap = 0;   // sized with maxc: covmats() reallocates
+        release_cov(); cov_chunks_cap = 0;   // sized with maxc: covmats() reallocates
         S.maxc = mn;
     }
 
@@ -1219,9 +1095,9 @@ struct Engine {
         pc_count(path, upd);
         if (upd.kind == PC_UPDATE_FUSED) {
             const size_t need = (size_t)pc_update_fused_blocks(&S, nph) * pc_update_fused_entries(&S);
-            if (need > upd_part_cap) { dfree(upd_part); upd_part_cap = 2 * need; upd_part = dalloc<double>(upd_part_cap); }
+            if (need > upd_part_cap) { blocks.release(upd_part); upd_part_cap = 2 * need; upd_part = blocks.dev<double>(upd_part_cap); }
             if (!upd_shift) {
-                upd_shift = dalloc<double>(S.D);
+                upd_shift = blocks.dev<double>(S.D);
                 std::vector<double> half(S.D, 0.5);               // first update: moments about the centre of the hypercube
                 HIPCHK(hipMemcpyAsync(upd_shift, half.data(), sizeof(double) * S.D, hipMemcpyHostToDevice, st));
                 HIPCHK(hipStreamSynchronize(st));
@@ -1302,15 +1178,16 @@ struct Engine {
     }
     template <class T> void ul(T *p, const std::vector<T> &v) { send_raw(p, v.data(), sizeof(T) * v.size()); }
 
+    void release_cov() { blocks.release(psum); blocks.release(pcnt); blocks.release(pcov); blocks.release(mean); blocks.release(count); }
     void covmats(int nph, int nc)
     {
         const size_t nchunk = pc_cov_nchunk(&S, nph);
         if (nchunk * nc > cov_chunks_cap) {
-            dfree(psum); dfree(pcnt); dfree(pcov); dfree(mean); dfree(count);
+            release_cov();
             cov_chunks_cap = nchunk * nc * 2;
-            psum = dalloc<double>(cov_chunks_cap * S.D); pcnt = dalloc<int>(cov_chunks_cap);
-            pcov = dalloc<double>(cov_chunks_cap * S.D * S.D);
-            mean = dalloc<double>((size_t)S.maxc * S.D); count = dalloc<int>(S.maxc);
+            psum = blocks.dev<double>(cov_chunks_cap * S.D); pcnt = blocks.dev<int>(cov_chunks_cap);
+            pcov = blocks.dev<double>(cov_chunks_cap * S.D * S.D);
+            mean = blocks.dev<double>((size_t)S.maxc * S.D); count = blocks.dev<int>(S.maxc);
         }
         direct_op();
         if (pc_launch_covmats(&S, nph, nc, psum, pcnt, mean, count, pcov, st)) {
@@ -1374,13 +1251,13 @@ struct Engine {
             attempt += (uint32_t)m;
             if (attempt > 1000u * (uint32_t)nprior + 100000u) engine_fail(PC_RC_SETTINGS, "could not generate live points (likelihood is logzero everywhere?)");
         }
-        double *drows = dalloc<double>((size_t)nprior * nT);
+        double *drows = blocks.dev<double>((size_t)nprior * nT);
         HIPCHK(hipMemcpy(drows, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
         pc_launch_install_live(&S, drows, nprior, st);
         h_ctl->nlike = nlike;
         HIPCHK(hipMemcpyAsync(&S.ctl->nlike, &h_ctl->nlike, sizeof(long long), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
-        dfree(drows);
+        blocks.release(drows);
         ndiscarded = (long)attempt - nprior;
         cb_eval_seconds = attempt ? t_eval / attempt : -1.0;
         call_dumper(2);
@@ -1428,7 +1305,7 @@ struct Engine {
     void generate_live()
     {   // GenerateLivePoints (generate.F90:150-183): keep the first nprior valid prior samples
         const int nprior = cfg.nprior <= 0 ? cfg.nlive : cfg.nprior, nT = S.nT;
-        double *rows = dalloc<double>((size_t)nprior * nT), *rl = dalloc<double>(nprior);
+        double *rows = blocks.dev<double>((size_t)nprior * nT), *rl = blocks.dev<double>(nprior);
         std::vector<double> keep_rows; keep_rows.reserve((size_t)nprior * nT);
         std::vector<double> hrows, hl(nprior);        // (hrows: only when a prior sample was not valid -- 736 KB zeroed for nothing was a third of a run's set-up)
         int have = 0, attempt0 = 0, last_attempt = -1;
@@ -1474,7 +1351,7 @@ struct Engine {
             h_ctl->seq = (unsigned long long)(a + (S.ngrade <= 1 ? 1 : 0)) * S.D;
             HIPCHK(hipMemcpy(&S.ctl->seq, &h_ctl->seq, sizeof(unsigned long long), hipMemcpyHostToDevice));
         }
-        dfree(rows); dfree(rl);
+        blocks.release(rows); blocks.release(rl);
         call_dumper(2);                // write_prior_file, nested_sampling.F90:197
         if (nprior > cfg.nlive) {      // nested_sampling.F90:201-205
             pc_count(path, PcTrimLive{}); pc_launch_consume(&S, 2, 0, st);
@@ -1724,7 +1601,7 @@ struct Engine {
     {
         active_run.reset(new ActiveRun(dev, &stop));
         r_t0 = clk::now();
-        h_dead_cap = (size_t)S.Dcap; h_dead = halloc<double>(h_dead_cap * S.nT); h_dead_copied = 0;
+        h_dead_cap = (size_t)S.Dcap; h_dead = blocks.pin<double>(h_dead_cap * S.nT); h_dead_copied = 0;
         bool resumed = false;
         if (cfg.resume_read) {                         // read_write.F90:384-476; a missing file means a fresh start
             if (FILE *probe = std::fopen(cfg.resume_read, "r")) {
@@ -1750,7 +1627,6 @@ struct Engine {
         S.defer_update = plan.defer ? 1 : 0; S.pool = plan.pool ? 1 : 0;
         if (S.pool) {
             pool_cursor = h_ctl->nphantom;
-            babies_own = S.babies;
             if (g_cap_phantoms.load() <= 0) {                                    // room for several updates between compactions,
                 size_t free_b = 0, total_b = 0;                                  // where the device has it to spare
                 (void)hipMemGetInfo(&free_b, &total_b);
@@ -2087,7 +1963,7 @@ struct Engine {
         // snapshot of the live set at termination, then nested_sampling.F90:381-384
         const int nT = S.nT;
         // (pinned buffers, copies in stream order in front of the kill-off: the host does not stop here)
-        es.hlive = halloc<double>((size_t)S.Ncap * nT); es.hcl = halloc<int>(S.Ncap);
+        es.hlive = blocks.pin<double>((size_t)S.Ncap * nT); es.hcl = blocks.pin<int>(S.Ncap);
         // A run on its own that ends through k_final_par: the loop's dead rows that have not left yet and the live rows go to the copy
         // stream from here, beside the kill-off (which writes neither: S.live stays, everything below h_ctl->ndead is final), and not
         // in front of it and behind the host's wait for it.  live_cluster stays in front: the kill-off rewrites it.
@@ -2129,8 +2005,8 @@ struct Engine {
         // (the partial sums go straight into pinned host memory, which the device addresses like its own: 180 KB over the
         //  link instead of a D2H copy request behind the kernel -- that request stalled its caller for 5-6 ms once per process,
         //  in the second or third run)
-        es.d_pmax = dalloc<double>(2 * (size_t)es.pm_nb); es.h_part = halloc<double>((size_t)es.pm_nb * es.pm_pw);
-        es.h_zp = halloc<double>(2 * (size_t)std::max(1, es.ncd_max));
+        es.d_pmax = blocks.dev<double>(2 * (size_t)es.pm_nb); es.h_part = blocks.pin<double>((size_t)es.pm_nb * es.pm_pw);
+        es.h_zp = blocks.pin<double>(2 * (size_t)std::max(1, es.ncd_max));
         pc_launch_post_moments(&S, -1, es.d_pmax, es.h_part, st);
         if (es.ncd_max > 0) {
             HIPCHK(hipMemcpyAsync(es.h_zp, S.logZp_dead, sizeof(double) * es.ncd_max, hipMemcpyDeviceToHost, st));
@@ -2143,9 +2019,9 @@ struct Engine {
     int end(pchip_result *out) { end_a(); HIPCHK(hipStreamSynchronize(st)); end_wait_aside(); return end_b(out); }
     int end_b(pchip_result *out)
     {
-        // (hlive may still be on its way on the copy stream when something below throws)
-        struct HostBuf { EndState &e; hipStream_t sc; bool waited = false; ~HostBuf() { if (!waited && sc) (void)hipStreamSynchronize(sc); if (e.hlive) hfree(e.hlive); if (e.hcl) hfree(e.hcl); e.hlive = nullptr; e.hcl = nullptr; } } hb{es, st_copy};
-        double *hlive = es.hlive; int *hcl = es.hcl; double *d_pmax = es.d_pmax, *h_part = es.h_part, *h_zp = es.h_zp;
+        // (when something below throws, the five blocks of the end stage stay in the ledger: destroy() waits for the copy stream, on which hlive
+        //  may still be on its way, before they go back)
+        double *hlive = es.hlive; int *hcl = es.hcl; double *h_part = es.h_part, *h_zp = es.h_zp;
         const int nc_end = es.nc_end, ncd_max = es.ncd_max, pmD = es.pmD, pm_nb = es.pm_nb, pm_pw = es.pm_pw, nT = S.nT;
         const auto t0 = r_t0, t1 = r_t1; auto t2 = es.t2;
         HIPCHK(hipGetLastError());                    // a kernel that could not be launched must not go unnoticed
@@ -2186,13 +2062,13 @@ struct Engine {
         if (dbg_lvl == 2) std::fprintf(stderr, "polychord_hip dbg: loop cycles %lld passB %lld (%lld flushes) accept-steps %lld (%lld) ins-rescan %lld (%lld) reject-steps cycles %lld\n", h_ctl->dbg[0], h_ctl->dbg[1], h_ctl->dbg[4], h_ctl->dbg[2], h_ctl->dbg[3], h_ctl->dbg[5], h_ctl->dbg[6], h_ctl->dbg[7]);
         if ((size_t)h_ctl->ndead > h_dead_cap) {          // the dead array grew beyond the first estimate
             HIPCHK(hipStreamSynchronize(st_copy));
-            hfree(h_dead); h_dead_cap = (size_t)h_ctl->ndead; h_dead = halloc<double>(h_dead_cap * nT); h_dead_copied = 0;
+            blocks.release(h_dead); h_dead_cap = (size_t)h_ctl->ndead; h_dead = blocks.pin<double>(h_dead_cap * nT); h_dead_copied = 0;
         }
         stream_dead();
-        out->dead = h_dead; h_dead = nullptr;
-        out->logweights = halloc<double>(std::max(1, h_ctl->ndead));
+        out->dead = blocks.hand_over(h_dead); h_dead = nullptr;      // (the result's three arrays are pchip_result_free's from here on)
+        out->logweights = blocks.hand_over(blocks.pin<double>(std::max(1, h_ctl->ndead)));
         HIPCHK(hipMemcpyAsync(out->logweights, S.dead_logw, sizeof(double) * h_ctl->ndead, hipMemcpyDeviceToHost, st_copy));
-        out->entry = halloc<double>(std::max(1, h_ctl->ndead));
+        out->entry = blocks.hand_over(blocks.pin<double>(std::max(1, h_ctl->ndead)));
         HIPCHK(hipMemcpyAsync(out->entry, S.dead_entry, sizeof(double) * h_ctl->ndead, hipMemcpyDeviceToHost, st_copy));
         int nl = 0;
         for (int s = 0; s < S.Ncap; ++s) nl += hcl[s] >= 0;
@@ -2206,7 +2082,7 @@ struct Engine {
         out->varlogZp = (double *)std::malloc(sizeof(double) * std::max(1, ncd));
         if (ncd > ncd_max) engine_fail(PC_RC_DEVICE, "more retired clusters (%d) than the final stage could have left (%d)", ncd, ncd_max);
         for (int i = 0; i < ncd; ++i) { const double zp = h_zp[i], zp2 = h_zp[ncd_max + i]; out->logZp[i] = 2 * zp - 0.5 * zp2; out->varlogZp[i] = zp2 - 2 * zp; }
-        hfree(h_zp);
+        blocks.release(es.h_zp);
         // posterior moments of theta from the dead points (requested above): sums about the pivot row p (k_post_moments),
         // mean = p + S1 / W, variance = S2 / W - (S1 / W)^2
         const int D = pmD, nb = pm_nb, pw = pm_pw;
@@ -2221,7 +2097,7 @@ struct Engine {
             out->post_mean[d] = h_part[2 * D + 1 + d] + dm;
             out->post_var[d] = std::max(0.0, out->post_var[d] / sw - dm * dm);
         }
-        dfree(d_pmax); hfree(h_part);
+        blocks.release(es.d_pmax); blocks.release(es.h_part);
         // settings.device_records: the lived records picked here, on the device that made them (what the exchange step of repeat-sharded
         // runs sends); their count comes back with the wait below
         long long *h_nrec = nullptr;
@@ -2229,14 +2105,14 @@ struct Engine {
             const long long cap = h_ctl->ndead;
             double *blk_rec = (double *)pc_cache_dev_alloc(pc_records_block_bytes(cap, nT));
             if (!blk_rec) engine_fail(PC_RC_MEMORY, "no device memory for the run's records (%lld rows)", cap);
-            h_nrec = halloc<long long>(1);
-            if (pc_pack_lived_device(S.dead, S.dead_logw, S.dead_entry, cap, nT, cfg.logzero, blk_rec, cap, h_nrec, st_copy) != 0) { pc_cache_dev_free(blk_rec); hfree(h_nrec); engine_fail(PC_RC_DEVICE, "packing the run's records"); }
+            h_nrec = blocks.pin<long long>(1);
+            if (pc_pack_lived_device(S.dead, S.dead_logw, S.dead_entry, cap, nT, cfg.logzero, blk_rec, cap, h_nrec, st_copy) != 0) { pc_cache_dev_free(blk_rec); engine_fail(PC_RC_DEVICE, "packing the run's records"); }
             out->d_records = blk_rec; out->records_cap = (long)cap; out->records_device = dev;
         }
         HIPCHK(hipStreamSynchronize(st_copy));
-        hb.waited = true;
         for (int s = 0, k = 0; s < S.Ncap; ++s) if (hcl[s] >= 0) std::memcpy(out->live + (size_t)(k++) * nT, hlive + (size_t)s * nT, sizeof(double) * nT);      // (a run on its own: the live rows came by the copy stream, end_a)
-        if (h_nrec) { out->n_records = (long)*h_nrec; hfree(h_nrec); }
+        if (h_nrec) { out->n_records = (long)*h_nrec; blocks.release(h_nrec); }
+        blocks.release(es.hlive); blocks.release(es.hcl);
         active_run.reset();
         return 0;
     }
@@ -2255,42 +2131,13 @@ struct Engine {
         if (st_side) (void)hipStreamSynchronize(st_side);
         }
         const auto dq0 = std::chrono::steady_clock::now();
-        std::vector<void *> blocks; blocks.reserve(160);
-        struct Batch { std::vector<void *> &b; Batch(std::vector<void *> &v) : b(v) { tl_dfree_batch = &b; } ~Batch() { tl_dfree_batch = nullptr; dcache().put_many(b); b.clear(); } };
-        {
-        Batch batch_guard(blocks);
-        if (raw_buf[0]) { S.nhat_raw = raw_buf[0]; for (int r = 1; r < RAW_RING; ++r) dfree(raw_buf[r]); raw_buf[0] = nullptr; }     // S.nhat_raw pointed at one of them
-        if (babies_own) { S.babies = babies_own; babies_own = nullptr; }      // (pool mode pointed it into the phantom array)
-        double **dd[] = { &S.live, &S.live_logL, &S.logZp, &S.logXp, &S.logZXp, &S.logZp2, &S.logZpXp, &S.logLp, &S.XpXq,
-                          &S.lse_ref, &S.lse_sum, &S.death_thr, &S.chol, &S.cov, &S.logZp_dead, &S.logZp2_dead, &S.phantom,
-                          &S.ph_logL, &S.dead, &S.dead_logw, &S.dead_postX, &S.dead_postZ, &S.babies, &S.baby_logL, &S.baby_logL_T,
-                          &S.ch_contour, &S.nhat, &S.nhat_w, &S.nhat_raw, &S.nhat_Ms, &S.ch_My, &S.live_entry, &S.dead_entry, &ph2, &phL2, &psum, &mean,
-                          &pcov, &d_lo, &d_hi, &d_invcovT, &d_mean, &d_dynL, &d_src };
-        for (auto p : dd) dfree(*p);
-        int **ii[] = { &S.live_cluster, &S.live_pos, &S.cl_list, &S.cl_n, &S.imin_slot, &S.ch_cluster, &S.ch_epoch, &S.ch_nlike,
-                       &S.ch_seed_slot, &S.slot_src, &S.slot_step, &S.slot_dead, &S.sort_slot, &blk, &d_total, &pcnt, &count, &d_dynN };
-        for (auto p : ii) dfree(*p);
-        { char *cs = (char *)d_cs; dfree(cs); d_cs = nullptr; }
-        dfree(d_x0s); dfree(d_prop); dfree(d_ans); dfree(d_decks);
-        if (hp_prop) { hfree(hp_prop); hp_prop = nullptr; } if (hp_ans) { hfree(hp_ans); hp_ans = nullptr; } if (hp_need) { hfree(hp_need); hp_need = nullptr; }
-        dfree(upd_part); dfree(upd_shift); upd_part_cap = 0;
-        clus.release(); dfree(c_subdims);   // (the clustering scratch used to stay behind: 12 MB per clustered run)
-        for (void *h : staged_up) hfree(h);
-        staged_up.clear();
-        for (const Fetch &f : fetching) hfree(f.h);
-        fetching.clear();
-        dfree(d_logn); dfree(S.ch_nlike_g); dfree(S.nn_list); dfree(S.nn_slot_owner); dfree(S.nn_chain_slot); dfree(S.nn_pts); dfree(S.nn_code);
-        unsigned **uu[] = { &S.cl_uid, &S.ph_cuid, &S.dead_cuid, &phC2, &S.cl_uid_dead };
-        for (auto p : uu) dfree(*p);
-        dfree(S.ph_uid); dfree(S.sort_key); dfree(S.plan); dfree(phU2); dfree(keep); dfree(S.ctl);
-        }
+        // every block the run still holds, whichever path allocated it and however the run ended (the staging blocks of a wait that never came,
+        // the end stage's of an end_b that threw): the ledger knows them, this function names none
+        blocks.release_all();
+        fetching.clear(); own_fetches.clear(); staged_up.clear();
+        h_dead = nullptr; h_ctl = nullptr; h_note = nullptr; es = EndState();
         const auto dq1 = std::chrono::steady_clock::now();
         kt.destroy();
-        if (h_dead) { hfree(h_dead); h_dead = nullptr; }
-        for (void *h : setup_staged) hfree(h);
-        setup_staged.clear();
-        if (h_ctl) hfree(h_ctl); h_ctl = nullptr;
-        if (h_note) hfree((void *)h_note); h_note = nullptr;
         if (ev_apply) { hpool().put_sync_event(ev_apply); ev_apply = nullptr; }
 
         if (st) { if (!streams_idle) (void)hipStreamSynchronize(st); if (!co) hpool().put_stream(st); } st = nullptr;
@@ -2324,6 +2171,7 @@ void *pc_cache_dev_alloc(size_t bytes) { try { return dcache().get(bytes); } cat
 void pc_cache_dev_free(void *p) { if (p && !dcache().put(p)) (void)hipFree(p); }
 void *pc_cache_host_alloc(size_t bytes) { try { return hcache().get(bytes); } catch (const EngineError &) { (void)hipGetLastError(); return nullptr; } }
 void pc_cache_host_free(void *p) { if (p && !hcache().put(p)) (void)hipHostFree(p); }
+void pchip_blocks_in_use(long *device, long *pinned) { if (device) *device = dcache().in_use(); if (pinned) *pinned = hcache().in_use(); }
 void pchip_trim_cache(void) { (void)hipDeviceSynchronize(); dcache().trim(); hcache().trim(); }      // the blocks finished runs left for the next ones go back to the driver
 // initial capacity of the per-cluster arrays (default 128) and of the phantom array in rows (0 = the engine's estimate);
 // both grow on demand, so these only matter to tests of the growth paths
@@ -2539,8 +2387,8 @@ int pchip_update_factors(const pchip_settings *s, int ncluster, int nlive, const
         if (path == 1) {
             S.pool = (s->ablate & PC_ABL_NO_POOL) ? 0 : 1;
             const size_t need = (size_t)pc_update_fused_blocks(&S, nph) * pc_update_fused_entries(&S);
-            E.upd_part_cap = need; E.upd_part = dalloc<double>(need);
-            E.upd_shift = dalloc<double>(D);
+            E.upd_part_cap = need; E.upd_part = E.blocks.dev<double>(need);
+            E.upd_shift = E.blocks.dev<double>(D);
             std::vector<double> sh(D, 0.5);
             if (shift) sh.assign(shift, shift + D);
             HIPCHK(hipMemcpy(E.upd_shift, sh.data(), sizeof(double) * D, hipMemcpyHostToDevice));

@@ -11,9 +11,9 @@
 //
 // The bottom half, ClusterUpdate<Eng>, owns the clustering scratch on the device and holds the orchestration: each method a short sequence of
 // "pure step, sends, launches or records, fetches, wait".  The including file provides, before an update is made: pc_state.h, pc_launch.h, the
-// cohort's rec_clus1 / rec_clusg, dalloc / dfree, engine_fail and the PC_RC_* codes, g_inject_fault; and
+// cohort's rec_clus1 / rec_clusg, RunBlocks (pc_blocks.h), engine_fail and the PC_RC_* codes, g_inject_fault; and
 //   of Engine, these members and no others:
-//     S, h_ctl, cfg.epoch_discard, co (rec), st
+//     S, h_ctl, cfg.epoch_discard, co (rec), st, blocks (the run's ledger: the scratch below is allocated through it and goes back with the run)
 //     nsplits, ncluster_peak, split_child, split_parent, split_logfrac
 //     send_raw, send_pre, fetch, fetch_raw, fetch_wait, direct_op
 //     grow_clusters          (which calls back regrow_counts)
@@ -205,8 +205,8 @@ inline void cluster_map_compose(std::vector<int> &map1, const std::vector<int> &
 // ---- the device's scratch and the traffic ---------------------------------------------------------------------------------------------
 
 template <class Eng> struct ClusterUpdate {
-    Eng &e;
-    explicit ClusterUpdate(Eng &engine) : e(engine) {}
+    Eng &e; RunBlocks &blocks;                 // (the run's ledger: the scratch is allocated through it and goes back with the run's other blocks)
+    explicit ClusterUpdate(Eng &engine) : e(engine), blocks(engine.blocks) {}
     // similarity blocks, neighbour lists and labels of the first pass (c_cap = the live slots they are sized for); the phantoms' counts per
     // cluster and the ids before a split (sized with S.maxc)
     double *c_Sm = nullptr; int *c_knn = nullptr, *c_lab = nullptr, *c_cnt = nullptr; unsigned *c_olduid = nullptr; int c_cap = 0;
@@ -215,22 +215,15 @@ template <class Eng> struct ClusterUpdate {
     int *c_map = nullptr; int c_map_cap = 0;                                                       // the cluster map for the nursery's chains
     ClusterMirror cmir;
 
-    void release()
-    {
-        dfree(c_Sm); dfree(c_knn); dfree(c_lab); dfree(c_cnt); dfree(c_olduid); c_cap = 0;
-        dfree(c_desc); dfree(c_bout); c_desc_cap = 0;
-        dfree(c_gdesc); dfree(c_gpool); dfree(c_glab); dfree(c_gout); c_g_cap = 0;
-        dfree(c_map); c_map_cap = 0;
-    }
     void ensure_scratch()
     {
         if (c_cap >= e.S.Ncap) return;
         c_cap = e.S.Ncap;
-        c_Sm = dalloc<double>((size_t)c_cap * c_cap); c_knn = dalloc<int>((size_t)c_cap * c_cap); c_lab = dalloc<int>(c_cap);
-        c_cnt = dalloc<int>(e.S.maxc); c_olduid = dalloc<unsigned>(e.S.maxc);
+        c_Sm = blocks.dev<double>((size_t)c_cap * c_cap); c_knn = blocks.dev<int>((size_t)c_cap * c_cap); c_lab = blocks.dev<int>(c_cap);
+        c_cnt = blocks.dev<int>(e.S.maxc); c_olduid = blocks.dev<unsigned>(e.S.maxc);
     }
     // (Engine::grow_clusters: the list of clusters has room for maxc now)
-    void regrow_counts(int maxc) { if (c_cnt) { dfree(c_cnt); dfree(c_olduid); c_cnt = dalloc<int>(maxc); c_olduid = dalloc<unsigned>(maxc); } }
+    void regrow_counts(int maxc) { if (c_cnt) { blocks.release(c_cnt); blocks.release(c_olduid); c_cnt = blocks.dev<int>(maxc); c_olduid = blocks.dev<unsigned>(maxc); } }
 
     void ask_mirror()
     {
@@ -287,9 +280,9 @@ template <class Eng> struct ClusterUpdate {
             // (the parts of a cluster are disjoint: their neighbour lists fit where the first pass' did)
             if (lev.koff > (long long)c_cap * c_cap) engine_fail(PC_RC_DEVICE, "clustering: the parts' neighbour lists (%lld entries) exceed the scratch of %d points", lev.koff, c_cap);
             if (c_g_cap < std::max(nb, npool)) {
-                dfree(c_gdesc); dfree(c_gpool); dfree(c_glab); dfree(c_gout);
+                blocks.release(c_gdesc); blocks.release(c_gpool); blocks.release(c_glab); blocks.release(c_gout);
                 c_g_cap = std::max(2 * std::max(nb, npool), e.S.Ncap);
-                c_gdesc = dalloc<int>((size_t)5 * c_g_cap); c_gpool = dalloc<int>(c_g_cap); c_glab = dalloc<int>(c_g_cap); c_gout = dalloc<int>(c_g_cap);
+                c_gdesc = blocks.dev<int>((size_t)5 * c_g_cap); c_gpool = blocks.dev<int>(c_g_cap); c_glab = blocks.dev<int>(c_g_cap); c_gout = blocks.dev<int>(c_g_cap);
             }
             e.send_pre(c_gdesc, lev.gdesc.data(), sizeof(int) * lev.gdesc.size());
             e.send_pre(c_gpool, lev.pool.data(), sizeof(int) * lev.pool.size());
@@ -315,7 +308,7 @@ template <class Eng> struct ClusterUpdate {
         cmir.valid = false;                              // (the contraction has moved volumes and evidences since the last update)
         struct MirrorEnds { ClusterMirror &m; ~MirrorEnds() { m.valid = false; } } mirror_ends{cmir};
         const int nold = e.h_ctl->ncluster;
-        if (c_desc_cap < nold) { dfree(c_desc); dfree(c_bout); c_desc_cap = std::max(2 * nold, 64); c_desc = dalloc<int>((size_t)4 * c_desc_cap); c_bout = dalloc<int>(c_desc_cap); }
+        if (c_desc_cap < nold) { blocks.release(c_desc); blocks.release(c_bout); c_desc_cap = std::max(2 * nold, 64); c_desc = blocks.dev<int>((size_t)4 * c_desc_cap); c_bout = blocks.dev<int>(c_desc_cap); }
         if ((int)cn.size() != nold) { e.fetch(cn, (const int *)e.S.cl_n, (size_t)nold); e.fetch_wait(); }
         std::vector<std::vector<int>> final_labels((size_t)nold); std::vector<int> final_num((size_t)nold, 1);
         const FirstPass fp = first_pass_descriptors(cn);
@@ -358,7 +351,7 @@ template <class Eng> struct ClusterUpdate {
     void remap_nursery(const std::vector<int> &cmap, int nold)
     {
         if (e.h_ctl->i_nursery <= 0) return;
-        if (c_map_cap < nold) { dfree(c_map); c_map_cap = std::max(2 * nold, 64); c_map = dalloc<int>(c_map_cap); }
+        if (c_map_cap < nold) { blocks.release(c_map); c_map_cap = std::max(2 * nold, 64); c_map = blocks.dev<int>(c_map_cap); }
         e.send_raw(c_map, cmap.data(), sizeof(int) * (size_t)nold);
         e.direct_op();
         pc_launch_remap_chains(&e.S, c_map, nold, e.h_ctl->i_nursery, e.st);

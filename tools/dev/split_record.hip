@@ -67,6 +67,12 @@ std::string tag(const void *p);                     // role + offset (behind Eng
 
 template <class T> T *dalloc(size_t n) { T *p = (T *)std::calloc(n ? n : 1, sizeof(T)); rec::blocks[(const char *)p] = (n ? n : 1) * sizeof(T); return p; }
 template <class T> void dfree(T *&p) { if (p) { rec::blocks.erase((const char *)p); std::free((void *)p); } p = nullptr; }
+// (the run's ledger over these: the clustering scratch is allocated through it; an update takes no pinned block)
+void dfree(const std::vector<void *> &ps) { for (void *p : ps) dfree(p); }
+template <class T> T *halloc(size_t n) { return (T *)std::calloc(n ? n : 1, sizeof(T)); }
+void hfree(void *p) { std::free(p); }
+#define PC_BLOCKS_OWN_PRIMITIVES
+#include "pc_blocks.h"
 
 // ---- the cohort of the runs in step, as far as an update sees it: records written down, launched at the next flush
 struct Cohort {
@@ -143,6 +149,7 @@ struct Settings { int epoch_discard = 0; };
 struct Engine {
     Cohort *co = nullptr;
     Settings cfg;
+    RunBlocks blocks;
     PcState S{}; PcCtl *h_ctl = nullptr; hipStream_t st = (hipStream_t)(uintptr_t)0x1000;
     long nsplits = 0; int ncluster_peak = 1;
     std::vector<unsigned> split_child, split_parent; std::vector<double> split_logfrac;
@@ -352,7 +359,7 @@ static void drive(const Scenario &sc, bool in_step)
     rec::line("device state " + rec::hex(h));
     g_inject_fault = 0;
 #ifndef SPLIT_PARENT
-    e.clus.release();
+    e.blocks.release_all();
 #endif
     for (auto &b : rec::blocks) std::free((void *)b.first);      // (the scenario's device: the state's arrays, and the parent's scratch)
     rec::blocks.clear();
