@@ -345,10 +345,30 @@ void pchip_source_destroy(int handle);
  * the lanes in lane order ((s0 + s1) + (s2 + s3) ... within rows of sixteen lanes, then (r0 + r1) + (r2 + r3)).  Contract: term is
  * pure, may read theta and data, must not synchronise; finish is pure and must not assume which lane calls it nor that all lanes see
  * the same theta (the derived parameters of a chain's points are written lane = point, from the sum kept when each was accepted: the
- * data are never walked a second time).  One sum per evaluation.  Same options rule, data block, handle space and
+ * data are never walked a second time).  One sum per evaluation (several: pchip_source_create_sums).  Same options rule, data block, handle space and
  * pchip_source_destroy as pchip_source_create; nterms >= 1.  pchip_like.kind stays PCHIP_LIKE_SOURCE: the handle knows its form;
  * pchip_result.path[PCHIP_PATH_SOURCE_TERMS] counts the launches that took it. */
 int  pchip_source_create_terms(const char *source, const char *options, const double *data, long ndata, long nterms);
+/* The terms form with SEVERAL SUMS per evaluation, for a likelihood whose finish needs more than one reduction of the same data (an
+ * amplitude or a baseline profiled out analytically: sum m, sum m^2, sum d m; two data sets with a chi-square each; a weighted mean and
+ * its variance).  The source defines
+ *     __device__ void   pchip_logl_terms(const double *theta, int nDims, const double *data, long ndata, long i, double *t);
+ *     __device__ double pchip_logl_finish_sums(const double *sums, const double *theta, double *phi, int nDims, int nDerived,
+ *                                              const double *data, long ndata);
+ * terms(i), 0 <= i < nterms, is called by ONE lane per i and writes the i-th term of every sum, t[0 .. nsums): one call per (point, i)
+ * serves all the sums.  finish_sums gets the finished sums[0 .. nsums), returns logL and writes all nDerived derived parameters -- cheap,
+ * no loop over the data.  Each sum k on its own is formed in the order defined for pchip_source_create_terms (lane l adds t_l[k],
+ * t_(l + 64)[k], ... to 0.0 by plain IEEE adds, then the balanced tree over the 64 lanes): its bits depend neither on nsums nor on
+ * whether the point was evaluated alone or as one end of a bracket.  The contract of term and finish holds for the two functions; an
+ * accepted point keeps all its sums, and its derived parameters are finish_sums of them -- the data are never walked a second time.
+ * nterms >= 1; 1 <= nsums <= PCHIP_SOURCE_MAX_SUMS (a compile-time constant of the handle's kernels: registers grow with it);
+ * with_prior != 0: the source defines pchip_prior_param as well and the handle may run with prior.kind = PCHIP_PRIOR_SOURCE (see
+ * pchip_source_create_prior).  Same options rule, data block, handle space, pchip_source_destroy and error reporting as
+ * pchip_source_create_terms (-1 with the log in polychord_hip_last_error(); a source that lacks one of its functions fails here, by name);
+ * launches count in path[PCHIP_PATH_SOURCE_TERMS] and path[PCHIP_PATH_SOURCE_KERNELS] as a one-sum handle's do. */
+#define PCHIP_SOURCE_MAX_SUMS 8
+int  pchip_source_create_sums(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums,
+                              int with_prior);
 /* The user's PRIOR in the same source and the same handle as the likelihood (pchip_prior.kind = PCHIP_PRIOR_SOURCE with pchip_like.kind =
  * PCHIP_LIKE_SOURCE, .source = the handle).  Besides the likelihood functions of its form -- nterms == 0: pchip_loglikelihood; nterms
  * >= 1: pchip_logl_term and pchip_logl_finish -- the source defines

@@ -128,6 +128,8 @@ def load():
     lib.pchip_source_create_terms.restype = C.c_int
     lib.pchip_source_create_prior.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long]
     lib.pchip_source_create_prior.restype = C.c_int
+    lib.pchip_source_create_sums.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long, C.c_int, C.c_int]
+    lib.pchip_source_create_sums.restype = C.c_int
     lib.pchip_source_prior_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_long, C.c_int, C.POINTER(C.c_double)]
     lib.pchip_source_prior_eval.restype = C.c_int
     lib.pchip_source_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_long, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -175,15 +177,20 @@ def dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def source_create(source, options=(), data=None, nterms=None, prior=False):
+def source_create(source, options=(), data=None, nterms=None, prior=False, nsums=None):
     """handle of a likelihood written as HIP device source (pchip_source_create); RuntimeError with the compiler's log if it does not compile.
     nterms given: the terms form (pchip_source_create_terms) -- the source defines pchip_logl_term and pchip_logl_finish, the sum has nterms terms.
-    prior=True: the source defines pchip_prior_param as well (pchip_source_create_prior), for runs with prior.kind = PRIOR_SOURCE"""
+    nsums given (with nterms): several sums per evaluation (pchip_source_create_sums) -- the source defines pchip_logl_terms and
+    pchip_logl_finish_sums, every sum has nterms terms; nsums=None: the calls above, unchanged.
+    prior=True: the source defines pchip_prior_param as well (pchip_source_create_prior; with nsums, pchip_source_create_sums' with_prior),
+    for runs with prior.kind = PRIOR_SOURCE"""
     lib = load()
     d = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
     opts = " ".join(options) if not isinstance(options, str) else options
     args = (source.encode(), opts.encode(), dptr(d) if d is not None and d.size else None, 0 if d is None else int(d.size))
-    if prior:
+    if nsums is not None:
+        h = lib.pchip_source_create_sums(*args, 0 if nterms is None else int(nterms), int(nsums), 1 if prior else 0)
+    elif prior:
         h = lib.pchip_source_create_prior(*args, 0 if nterms is None else int(nterms))
     else:
         h = lib.pchip_source_create(*args) if nterms is None else lib.pchip_source_create_terms(*args, int(nterms))

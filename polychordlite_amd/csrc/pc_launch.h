@@ -8,14 +8,19 @@
 #include "../../include/polychord_hip.h"
 #include <cstddef>
 
+// the number of sums of a handle made by pchip_source_create_sums; 0: any other handle, or none (pc_rtc.hip)
+extern "C" int pc_rtc_source_sums(int id);
+
 // k_slice keeps the theta rows of a chain's babies in LDS (its run-time flag phi_lds: derived parameters at the end of the chain, summed
 // in that order) when they fit under 48 KB next to the chain's block; pc_slice_t_ok takes only states where it does
 // (pc_slice_plan's rule, asked by pc_slice_t_ok in another file: inline here, the one definition in this header, so that the library's
-//  exported pc_* names stay what they were)
+//  exported pc_* names stay what they were).  A source with several sums keeps the sums of every baby beside the rows, [nr][nsums]: the
+// block counts here, and a shape it pushes over the limit writes its derived parameters inside the slice loop like any that does not fit
 static inline int pc_slice_phi_lds(const PcState *S)
 {
     const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16, tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
-    return (S->nDer > 0 && sh0 + tb <= 48 * 1024) ? 1 : 0;
+    const size_t sums = S->like.kind == PC_LIKE_SOURCE ? sizeof(double) * (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0;
+    return (S->nDer > 0 && sh0 + tb + sums <= 48 * 1024) ? 1 : 0;
 }
 
 extern "C" {

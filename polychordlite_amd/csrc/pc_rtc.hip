@@ -13,6 +13,10 @@
 // as #defines in front of the library's text in that handle's unit (PCHIP_USER_TERMS, PCHIP_SRC_NTERMS): pc_sample.hip's wave-cooperative
 // evaluation is compiled in their place only.
 //
+// Several sums per evaluation (pchip_source_create_sums): the source defines pchip_logl_terms (the i-th terms of all the sums, one lane per i)
+// and pchip_logl_finish_sums (logL and the derived parameters from the finished sums); such a handle's unit gets PCHIP_USER_SUMS and
+// PCHIP_SRC_NSUMS in front beside the two #defines of the terms form, and the same evaluation code is compiled for that many sums.
+//
 // A prior in the same source (pchip_source_create_prior): the text defines pchip_prior_param (theta[i] from the whole cube, one call per
 // parameter) next to the likelihood of either form; such a handle's unit gets PCHIP_USER_PRIOR in front, and a run with prior.kind =
 // PCHIP_PRIOR_SOURCE takes the table's kernel variants with that function behind the transform's one entry point (pc_sample.hip).
@@ -76,6 +80,7 @@ struct Source {
     std::string text;                      // the user's source, behind the #define lines of its options
     std::vector<double> data;
     long nterms = 0;                       // > 0: the terms form (pchip_logl_term / pchip_logl_finish), the sum's length
+    int nsums = 0;                         // > 0: several sums per evaluation (pchip_logl_terms / pchip_logl_finish_sums; pchip_source_create_sums)
     bool has_prior = false;                // the source defines pchip_prior_param as well (pchip_source_create_prior)
 };
 
@@ -164,12 +169,13 @@ int compile(const Source *s, const std::string &unit, const std::vector<std::str
 
 // the translation unit of the sampling kernels: the library's kernels (pc_sample.hip declares pchip_loglikelihood under PCHIP_USER_SOURCE),
 // then the user's text -- its macros and pragmas reach nothing of the library's.  A terms handle: its form and its loop bound in front;
-// a handle with a prior (pchip_source_create_prior): PCHIP_USER_PRIOR in front.
+// a handle with several sums: their number in front as well; a handle with a prior (pchip_source_create_prior): PCHIP_USER_PRIOR in front.
 std::string kernel_unit(const Source *s)
 {
     const std::string prior = s && s->has_prior ? "#define PCHIP_USER_PRIOR 1\n" : "";
+    const std::string sums = s && s->nsums > 0 ? "#define PCHIP_USER_SUMS 1\n#define PCHIP_SRC_NSUMS " + std::to_string(s->nsums) + "\n" : "";
     if (s && s->nterms > 0)
-        return prior + "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
+        return prior + sums + "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
     return s ? prior + "#define PCHIP_USER_SOURCE 1\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n"
              : std::string("#include \"pc_sample.hip\"\n");
 }
@@ -187,14 +193,21 @@ const char *const PROBE_UNIT_TERMS =
     "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
     "{ out[0] = pchip_logl_finish(pchip_logl_term(th, nDims, data, ndata, i), th, phi, nDims, nDerived, data, ndata); }\n"
     "#include \"pchip_user_source.h\"\n";
+// ... and of pchip_source_create_sums (behind a #define of PCHIP_SRC_NSUMS): one call of the terms, the finish of what it wrote
+const char *const PROBE_UNIT_SUMS =
+    "__device__ void pchip_logl_terms(const double *theta, int nDims, const double *data, long ndata, long i, double *t);\n"
+    "__device__ double pchip_logl_finish_sums(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
+    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
+    "{ double t[PCHIP_SRC_NSUMS]; pchip_logl_terms(th, nDims, data, ndata, i, t); out[0] = pchip_logl_finish_sums(t, th, phi, nDims, nDerived, data, ndata); }\n"
+    "#include \"pchip_user_source.h\"\n";
 
 // ... and of pchip_source_create_prior: the probe of the handle's form, then pchip_prior_param behind its declaration, called as well
 const char *const PROBE_PRIOR_DECL =
     "__device__ double pchip_prior_param(const double *cube, int i, int nDims, const double *data, long ndata);\n";
 const char *const PROBE_PRIOR_CALL = "out[0] += pchip_prior_param(th, 0, nDims, data, ndata); }\n";
-std::string probe_unit(long nterms, bool prior)
+std::string probe_unit(long nterms, int nsums, bool prior)
 {
-    std::string u = nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT;
+    std::string u = nsums > 0 ? "#define PCHIP_SRC_NSUMS " + std::to_string(nsums) + "\n" + PROBE_UNIT_SUMS : std::string(nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT);
     if (!prior) return u;
     const size_t close = u.rfind(" }\n");        // the end of pchip_probe's body: the call goes in front of it
     u.replace(close, 3, std::string(" ") + PROBE_PRIOR_CALL);
@@ -308,6 +321,15 @@ long pc_rtc_source_terms(int id)
     return it == G.src.end() ? 0 : it->second->nterms;
 }
 
+// the number of sums of a handle made by pchip_source_create_sums; 0: any other handle, or none
+int pc_rtc_source_sums(int id)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    auto it = G.src.find(id);
+    return it == G.src.end() ? 0 : it->second->nsums;
+}
+
 int pc_rtc_source_has_prior(int id)
 {
     Registry &G = reg();
@@ -316,9 +338,9 @@ int pc_rtc_source_has_prior(int id)
     return it != G.src.end() && it->second->has_prior ? 1 : 0;
 }
 
-// pchip_source_create[_terms | _prior]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
-// nterms > 0: the terms form.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
-int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, bool prior, std::string *log)
+// pchip_source_create[_terms | _sums | _prior]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
+// nterms > 0: the terms form, of nsums sums where nsums > 0.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
+int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums, bool prior, std::string *log)
 {
     if (!source) { *log = "pchip_source_create: no source"; return -1; }
     if (ndata < 0 || (ndata > 0 && !data)) { *log = "pchip_source_create: ndata > 0 needs a data block"; return -1; }
@@ -328,7 +350,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     auto s = std::make_shared<Source>();
     s->text = defs + "#line 1\n" + source;
     if (ndata > 0) s->data.assign(data, data + ndata);
-    s->nterms = nterms; s->has_prior = prior;
+    s->nterms = nterms; s->nsums = nsums; s->has_prior = prior;
     std::string arch = "gfx950";
     int dev = 0, ndev = 0;
     if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&dev) == hipSuccess) {
@@ -337,7 +359,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     }
     (void)hipGetLastError();
     std::vector<char> code; std::vector<std::string> lowered;
-    if (compile(s.get(), probe_unit(nterms, prior), { "pchip_probe" }, arch, code, lowered, *log)) return -1;
+    if (compile(s.get(), probe_unit(nterms, nsums, prior), { "pchip_probe" }, arch, code, lowered, *log)) return -1;
     Registry &G = reg();
     std::lock_guard<std::mutex> g(G.m);
     const int id = G.next++;
@@ -352,7 +374,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
 extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata)
 {
     std::string log;
-    const int id = pc_rtc_source_create(source, options, data, ndata, 0, false, &log);
+    const int id = pc_rtc_source_create(source, options, data, ndata, 0, 0, false, &log);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }
@@ -362,7 +384,7 @@ extern "C" int pchip_source_create_terms(const char *source, const char *options
     std::string log;
     int id = -1;
     if (nterms < 1) log = "pchip_source_create_terms: nterms = " + std::to_string(nterms) + " -- the sum needs at least one term (nterms >= 1)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, false, &log);
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, 0, false, &log);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }
@@ -373,7 +395,20 @@ extern "C" int pchip_source_create_prior(const char *source, const char *options
     std::string log;
     int id = -1;
     if (nterms < 0) log = "pchip_source_create_prior: nterms = " + std::to_string(nterms) + " -- 0 (the plain form) or the number of terms (nterms >= 1)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, true, &log);
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, 0, true, &log);
+    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
+    return id;
+}
+
+// the terms form with nsums sums per evaluation (pchip_logl_terms / pchip_logl_finish_sums); with_prior: pchip_prior_param in the same source
+extern "C" int pchip_source_create_sums(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums, int with_prior)
+{
+    std::string log;
+    int id = -1;
+    if (nterms < 1) log = "pchip_source_create_sums: nterms = " + std::to_string(nterms) + " -- the sums need at least one term (nterms >= 1)";
+    else if (nsums < 1 || nsums > PCHIP_SOURCE_MAX_SUMS)
+        log = "pchip_source_create_sums: nsums = " + std::to_string(nsums) + " -- 1 <= nsums <= " + std::to_string(PCHIP_SOURCE_MAX_SUMS) + " (PCHIP_SOURCE_MAX_SUMS)";
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, nsums, with_prior != 0, &log);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }

@@ -187,81 +187,136 @@ __device__ __forceinline__ double wsum(double v) { return (DPL > 1) ? wave_sum<4
 // has made of the code), and the add must not fuse with a multiply at the end of the user's inlined term.
 // Lane-consecutive i: a data block laid out as a structure of arrays is read with coalesced loads.  No LDS traffic and no barrier in
 // the loop (theta is read from the LDS copy behind the one barrier a source evaluation always had).
+//
+// Several sums per evaluation (pchip_source_create_sums; PCHIP_USER_SUMS and PCHIP_SRC_NSUMS in front as well): ONE call of the user's
+// pchip_logl_terms per (point, i) writes the i-th term of every sum, and each sum k on its own is formed exactly as above -- its bits do
+// not depend on how many sums travel beside it.  Everything below is written for PC_NSUMS sums; the one-sum form is its length-1 case
+// behind two adaptors around the user's pchip_logl_term / pchip_logl_finish.
+#ifdef PCHIP_USER_SUMS
+constexpr int PC_NSUMS = (int)(PCHIP_SRC_NSUMS);
+__device__ void   pchip_logl_terms(const double *theta, int nDims, const double *data, long ndata, long i, double *t);
+__device__ double pchip_logl_finish_sums(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
+__device__ __forceinline__ void pc_user_terms(const double *theta, int nDims, const double *data, long ndata, long i, double (&t)[PC_NSUMS])
+{
+    pchip_logl_terms(theta, nDims, data, ndata, i, t);
+}
+__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata)
+{
+    return pchip_logl_finish_sums(sums, theta, phi, nDims, nDerived, data, ndata);
+}
+#else
+constexpr int PC_NSUMS = 1;
 __device__ double pchip_logl_term(const double *theta, int nDims, const double *data, long ndata, long i);
 __device__ double pchip_logl_finish(double sum, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
+__device__ __forceinline__ void pc_user_terms(const double *theta, int nDims, const double *data, long ndata, long i, double (&t)[PC_NSUMS])
+{
+    t[0] = pchip_logl_term(theta, nDims, data, ndata, i);
+}
+__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata)
+{
+    return pchip_logl_finish(sums[0], theta, phi, nDims, nDerived, data, ndata);
+}
+#endif
+// terms a lane keeps in flight -- their loads travel together, a lane's wait for the data is what a short term costs --: four for one sum
+// (two a point in the pair pass), fewer as the sums multiply the values held (PC_NSUMS of them a term and point, beside as many accumulators)
+constexpr int PC_TERMS_FLIGHT = PC_NSUMS <= 1 ? 4 : (PC_NSUMS <= 4 ? 2 : 1);
+constexpr int PC_TERMS_FLIGHT2 = PC_NSUMS <= 1 ? 2 : 1;
 
-// (four terms a step where the lane has them -- their loads are in flight together, a lane's wait for the data is what a short term
-//  costs --, the adds one after the other in the order of i)
-__device__ __forceinline__ double pc_terms_sum(const PcState &S, const double *theta, int lane)
+// (the adds of a sum one after the other in the order of i)
+__device__ __forceinline__ void pc_terms_sum(const PcState &S, const double *theta, int lane, double (&sum)[PC_NSUMS])
 {
     constexpr long N = (long)(PCHIP_SRC_NTERMS);
-    double s = 0.0;
+    constexpr int U = PC_TERMS_FLIGHT;
+    double s[PC_NSUMS];
+#pragma unroll
+    for (int k = 0; k < PC_NSUMS; ++k) s[k] = 0.0;
     long i = lane;
-    for (; i + 192 < N; i += 256) {
-        double t[4];
+    if constexpr (U > 1) {
+        for (; i + 64 * (U - 1) < N; i += 64 * U) {
+            double t[U][PC_NSUMS];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) t[u] = pchip_logl_term(theta, S.D, S.src_data, (long)S.src_ndata, i + 64 * u);
+            for (int u = 0; u < U; ++u) pc_user_terms(theta, S.D, S.src_data, (long)S.src_ndata, i + 64 * u, t[u]);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) { asm volatile("" : "+v"(t[u])); s = s + t[u]; }
-    }
-    for (; i < N; i += 64) {
-        double t = pchip_logl_term(theta, S.D, S.src_data, (long)S.src_ndata, i);
-        asm volatile("" : "+v"(t));
-        s = s + t;
-    }
-    return wave_sum<4>(s);
-}
-// two points in ONE pass over the data, an accumulator each: every sum in the order above, so its bits do not depend on whether the point
-// was evaluated alone or in a pair
-__device__ __forceinline__ void pc_terms_sum2(const PcState &S, const double *thA, const double *thB, int lane, double &sA, double &sB)
-{
-    constexpr long N = (long)(PCHIP_SRC_NTERMS);
-    double a = 0.0, b = 0.0;
-    long i = lane;
-    for (; i + 64 < N; i += 128) {
-        double tA[2], tB[2];
+            for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            tA[u] = pchip_logl_term(thA, S.D, S.src_data, (long)S.src_ndata, i + 64 * u);
-            tB[u] = pchip_logl_term(thB, S.D, S.src_data, (long)S.src_ndata, i + 64 * u);
+                for (int k = 0; k < PC_NSUMS; ++k) { asm volatile("" : "+v"(t[u][k])); s[k] = s[k] + t[u][k]; }
         }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) { asm volatile("" : "+v"(tA[u])); asm volatile("" : "+v"(tB[u])); a = a + tA[u]; b = b + tB[u]; }
     }
     for (; i < N; i += 64) {
-        double tA = pchip_logl_term(thA, S.D, S.src_data, (long)S.src_ndata, i);
-        double tB = pchip_logl_term(thB, S.D, S.src_data, (long)S.src_ndata, i);
-        asm volatile("" : "+v"(tA));
-        asm volatile("" : "+v"(tB));
-        a = a + tA; b = b + tB;
+        double t[PC_NSUMS];
+        pc_user_terms(theta, S.D, S.src_data, (long)S.src_ndata, i, t);
+#pragma unroll
+        for (int k = 0; k < PC_NSUMS; ++k) { asm volatile("" : "+v"(t[k])); s[k] = s[k] + t[k]; }
     }
-    sA = wave_sum<4>(a); sB = wave_sum<4>(b);
+#pragma unroll
+    for (int k = 0; k < PC_NSUMS; ++k) sum[k] = wave_sum<4>(s[k]);
 }
-// logL of theta (uniform over the wave) and, in `sum`, the finished sum it came from: whoever accepts the point keeps it, and the
-// derived parameters are finish(sum, theta) again -- never a second walk over the data
+// two points in ONE pass over the data, PC_NSUMS accumulators each: every sum in the order above, so its bits do not depend on whether the
+// point was evaluated alone or in a pair
+__device__ __forceinline__ void pc_terms_sum2(const PcState &S, const double *thA, const double *thB, int lane, double (&sA)[PC_NSUMS],
+                                              double (&sB)[PC_NSUMS])
+{
+    constexpr long N = (long)(PCHIP_SRC_NTERMS);
+    constexpr int U = PC_TERMS_FLIGHT2;
+    double a[PC_NSUMS], b[PC_NSUMS];
+#pragma unroll
+    for (int k = 0; k < PC_NSUMS; ++k) { a[k] = 0.0; b[k] = 0.0; }
+    long i = lane;
+    if constexpr (U > 1) {
+        for (; i + 64 * (U - 1) < N; i += 64 * U) {
+            double tA[U][PC_NSUMS], tB[U][PC_NSUMS];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                pc_user_terms(thA, S.D, S.src_data, (long)S.src_ndata, i + 64 * u, tA[u]);
+                pc_user_terms(thB, S.D, S.src_data, (long)S.src_ndata, i + 64 * u, tB[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int k = 0; k < PC_NSUMS; ++k) {
+                    asm volatile("" : "+v"(tA[u][k])); asm volatile("" : "+v"(tB[u][k]));
+                    a[k] = a[k] + tA[u][k]; b[k] = b[k] + tB[u][k];
+                }
+        }
+    }
+    for (; i < N; i += 64) {
+        double tA[PC_NSUMS], tB[PC_NSUMS];
+        pc_user_terms(thA, S.D, S.src_data, (long)S.src_ndata, i, tA);
+        pc_user_terms(thB, S.D, S.src_data, (long)S.src_ndata, i, tB);
+#pragma unroll
+        for (int k = 0; k < PC_NSUMS; ++k) {
+            asm volatile("" : "+v"(tA[k])); asm volatile("" : "+v"(tB[k]));
+            a[k] = a[k] + tA[k]; b[k] = b[k] + tB[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PC_NSUMS; ++k) { sA[k] = wave_sum<4>(a[k]); sB[k] = wave_sum<4>(b[k]); }
+}
+// logL of theta (uniform over the wave) and, in `sum`, the finished sums it came from: whoever accepts the point keeps them, and the
+// derived parameters are finish(sums, theta) again -- never a second walk over the data
 template <int DPL>
 __device__ __forceinline__ double like_eval_terms(const PcState &S, const double (&th)[DPL], const LaneDims<DPL> &ld, int lane, double *ybuf,
-                                                  double &sum)
+                                                  double (&sum)[PC_NSUMS])
 {
 #pragma unroll
     for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
     __syncthreads();                              // one wave per workgroup: cheap
-    sum = pc_terms_sum(S, ybuf, lane);
+    pc_terms_sum(S, ybuf, lane, sum);
     double phi[PC_SRC_MAX_DERIVED];
-    const double l = pchip_logl_finish(sum, ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+    const double l = pc_user_finish(sum, ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
     __syncthreads();
     return l;
 }
-// all nDerived values of an accepted point from its sum (lane 0 writes them to out)
+// all nDerived values of an accepted point from its sums (lane 0 writes them to out)
 template <int DPL>
 __device__ __forceinline__ void like_phi_terms(const PcState &S, const double (&th)[DPL], const LaneDims<DPL> &ld, int lane, double *ybuf,
-                                               double sum, double *out)
+                                               const double (&sum)[PC_NSUMS], double *out)
 {
 #pragma unroll
     for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
     __syncthreads();
     double phi[PC_SRC_MAX_DERIVED];
-    (void)pchip_logl_finish(sum, ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+    (void)pc_user_finish(sum, ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
     if (lane == 0) for (int e = 0; e < S.nDer; ++e) out[e] = phi[e];
     __syncthreads();
 }
@@ -303,7 +358,7 @@ __device__ __forceinline__ double like_eval(const PcState &S, const double (&th)
         return pc_logaddexp(L.norm - s1 / 2.0, L.norm - s2 / 2.0) - 0.6931471805599453;
 #ifdef PCHIP_USER_TERMS
     } else if (kind == PC_LIKE_SOURCE) {          // the terms form: the wave shares the loop over the terms (like_eval_terms)
-        double sum;
+        double sum[PC_NSUMS];
         return like_eval_terms<DPL>(S, th, ld, lane, ybuf, sum);
 #elif defined(PCHIP_USER_SOURCE)
     } else if (kind == PC_LIKE_SOURCE) {          // the user's function (pc_rtc.hip): every lane evaluates it on the same LDS copy of theta,
@@ -405,7 +460,7 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
         PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf);
     }
 #ifdef PCHIP_USER_TERMS
-    double tsum = 0.0;
+    double tsum[PC_NSUMS] = {};
     const double logL = S.like.kind == PC_LIKE_SOURCE ? like_eval_terms<DPL>(S, th, ld, lane, ybuf, tsum) : like_eval<DPL, 4>(S, th, ld, lane, ybuf);
 #else
     const double logL = like_eval<DPL, 4>(S, th, ld, lane, ybuf);
@@ -471,7 +526,7 @@ __global__ __launch_bounds__(64) void k_source_eval(PcState S, const double *the
     }
     double *out = phi + (size_t)blockIdx.x * S.nDer;
 #ifdef PCHIP_USER_TERMS
-    double sum;
+    double sum[PC_NSUMS];
     const double l = like_eval_terms<DPL>(S, th, ld, lane, ybuf, sum);
     if (S.nDer > 0) like_phi_terms<DPL>(S, th, ld, lane, ybuf, sum, out);
 #else
@@ -605,7 +660,7 @@ template <int DPL>
 __device__ inline double pc_max_point(const PcState &S, const LaneDims<DPL> &ld, const double (&th)[DPL], int lane, double *ybuf, double *phi)
 {
 #ifdef PCHIP_USER_TERMS
-    double tsum = 0.0;
+    double tsum[PC_NSUMS] = {};
     double logL = S.like.kind == PC_LIKE_SOURCE ? like_eval_terms<DPL>(S, th, ld, lane, ybuf, tsum) : like_eval<DPL, 4>(S, th, ld, lane, ybuf);
 #else
     double logL = like_eval<DPL, 4>(S, th, ld, lane, ybuf);
@@ -1678,7 +1733,7 @@ struct ChainCtx {
     bool quad;
     double qa, qb, qc, qnorm;
 #ifdef PCHIP_USER_TERMS
-    double tsum;        // the terms form: the sum of the last point eval_at evaluated -- the accepted point's, when a slice ends
+    double tsum[PC_NSUMS];   // the terms form: the sums of the last point eval_at evaluated -- the accepted point's, when a slice ends
     double *ybuf2;      // ... and LDS for a second theta (eval_pair: both bracket ends in one pass over the data)
 #endif
 };
@@ -1695,7 +1750,7 @@ struct ChainCtx<DPL, NROWS, 1> {
     double qa, qb, qc, qnorm;
     LaneTable<DPL> tb;
 #ifdef PCHIP_USER_TERMS
-    double tsum;
+    double tsum[PC_NSUMS];
     double *ybuf2;
 #endif
 };
@@ -1709,16 +1764,16 @@ __device__ __forceinline__ void like_pair_terms(ChainCtx<DPL, NROWS, PT> &C, con
 {
     const PcState &S = C.S;
     lA = S.logzero; lB = S.logzero;
-    double sum;
+    double sum[PC_NSUMS];
     if (inA && inB) {
 #pragma unroll
         for (int k = 0; k < DPL; ++k) if (C.ld.on[k]) { C.ybuf[C.lane + 64 * k] = thA[k]; C.ybuf2[C.lane + 64 * k] = thB[k]; }
         __syncthreads();
-        double sA, sB;
+        double sA[PC_NSUMS], sB[PC_NSUMS];
         pc_terms_sum2(S, C.ybuf, C.ybuf2, C.lane, sA, sB);
         double phi[PC_SRC_MAX_DERIVED];
-        lA = pchip_logl_finish(sA, C.ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
-        lB = pchip_logl_finish(sB, C.ybuf2, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+        lA = pc_user_finish(sA, C.ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+        lB = pc_user_finish(sB, C.ybuf2, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
         __syncthreads();
     } else if (inA) lA = like_eval_terms<DPL>(S, thA, C.ld, C.lane, C.ybuf, sum);
     else if (inB) lB = like_eval_terms<DPL>(S, thB, C.ld, C.lane, C.ybuf, sum);
@@ -1957,10 +2012,13 @@ template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, d
 }
 #define PC_LAUNCH(K, G, B, SH, ST, ...) do { if (pc_rtc_wanted(S)) { if (pc_rtc_go(S, #K, G, B, SH, ST, __VA_ARGS__)) return 1; } \
                                              else hipLaunchKernelGGL(K, G, B, SH, ST, __VA_ARGS__); } while (0)
-// the terms form of a source evaluates the two ends of a bracket in one pass over the data: LDS for the second theta behind the chain's block
-static size_t pc_terms_lds(const PcState *S)
+// the terms form of a source evaluates the two ends of a bracket in one pass over the data: LDS for the second theta behind the chain's block;
+// a handle with several sums (pchip_source_create_sums) keeps the sums of every baby behind that, [nr][nsums], where the babies' theta rows
+// are in LDS (phi_lds: pc_slice_phi_lds has counted this block in its decision)
+static size_t pc_terms_lds(const PcState *S, int phi_lds)
 {
-    return (S->like.kind == PC_LIKE_SOURCE && pc_rtc_source_terms(S->src_id) > 0) ? sizeof(double) * (size_t)S->D : 0;
+    if (S->like.kind != PC_LIKE_SOURCE || pc_rtc_source_terms(S->src_id) <= 0) return 0;
+    return sizeof(double) * ((size_t)S->D + (phi_lds ? (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0));
 }
 // lane = coordinate: the coordinates a lane holds (template DPL) at nDims <= 64, 128, 256; 0 beyond (the launchers return 1)
 static int pc_dpl(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : (D <= 256 ? 4 : 0)); }
@@ -2122,7 +2180,7 @@ static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R
     const size_t tb = sizeof(double) * (size_t)nr * (D + 1);
     size_t sh = sizeof(double) * ((size_t)D + nr) + 16 + (p.phi_lds ? tb : 0);
     if (fused) sh += sizeof(double) * ((size_t)p.fw * D + (size_t)nr * (D + 2));     // + L, directions, widths
-    if (!R) sh += pc_terms_lds(S);                              // (a source in step: pc_launch_slice_step below, not this plan)
+    if (!R) sh += pc_terms_lds(S, p.phi_lds);                              // (a source in step: pc_launch_slice_step below, not this plan)
     if (fused && sh > 150 * 1024) return p;
     // the functor variants (LEAN = 3 Rastrigin, 4 twin Gaussian, 5 the Gaussian when settings.ablate bit 0 asks for it as a functor): one grade,
     // keyed draws, the box (a prior table: the general variants); runs in step take the Gaussian functor as the general kernel
@@ -2235,11 +2293,11 @@ static PcSlicePlan pc_slice_step_plan(const PcState *S, int nchains, int fused, 
     p.special = false; p.wpb = 1; p.lean = 0; p.pt = S->prior.kind >= 2 ? 1 : 0;
     p.fw = !fused ? 0 : (D <= 8 ? 8 : (D <= 16 ? 16 : 24));
     p.grid = dim3(nchains, R); p.block = dim3(64);
-    // a chain's LDS as pc_slice_plan lays it out, and the second theta of the terms form behind it
+    // a chain's LDS as pc_slice_plan lays it out, and the second theta of the terms form (and the babies' sums) behind it
     p.phi_lds = pc_slice_phi_lds(S);
     size_t sh = sizeof(double) * ((size_t)D + nr) + 16 + (p.phi_lds ? sizeof(double) * (size_t)nr * (D + 1) : 0);
     if (fused) sh += sizeof(double) * ((size_t)p.fw * D + (size_t)nr * (D + 2));
-    sh += pc_terms_lds(S);
+    sh += pc_terms_lds(S, p.phi_lds);
     if (fused && sh > 150 * 1024) return p;
     p.lds = sh; p.ok = true;
     return p;

@@ -209,8 +209,15 @@
     if constexpr (PT != 0) PC_PRIOR_LOAD(DPL, S, lane, C.tb);
 #ifdef PCHIP_USER_TERMS
     // the terms form of a source: the second theta of eval_pair behind the chain's block, where the launchers add nDims doubles for it
-    // (pc_terms_lds); the sum of every baby in the spare double of its tbuf row (the rows are D + 1 apart)
-    C.tsum = 0.0; C.ybuf2 = (double *)smem + (size_t)WPB * per_wave;
+    // (pc_terms_lds); the sum of every baby in the spare double of its tbuf row (the rows are D + 1 apart).  Several sums
+    // (PCHIP_USER_SUMS): a block of their own behind the second theta, [nr][PC_NSUMS], there when phi_lds is set (the launchers count it
+    // in that decision: pc_slice_phi_lds) -- the D + 1 stride of tbuf, of the bases and of the Cholesky staging stays what it is
+#pragma unroll
+    for (int k = 0; k < PC_NSUMS; ++k) C.tsum[k] = 0.0;
+    C.ybuf2 = (double *)smem + (size_t)WPB * per_wave;
+#ifdef PCHIP_USER_SUMS
+    double *sums_lds = C.ybuf2 + S.D;
+#endif
 #endif
     const bool corr = PT == 0 && (lean2 || (!lean && !leanf && S.like.kind == PC_LIKE_CORR_GAUSSIAN));
     C.quad = PT == 0 && !leanf && (lean_any || ((corr || S.like.kind == PC_LIKE_GAUSSIAN) && !(S.ablate & PC_ABL_FUNCTOR)));
@@ -621,7 +628,14 @@
 #pragma unroll
             for (int k = 0; k < DPL; ++k) if (ld.on[k]) tb_row[64 * k] = th[k];
 #ifdef PCHIP_USER_TERMS
-            if (LEAN == 0 && lane == 0) tb_row[D] = C.tsum;     // (lane 0: tb_row is the row's start)
+#ifdef PCHIP_USER_SUMS
+            if (LEAN == 0 && lane == 0 && S.like.kind == PC_LIKE_SOURCE) {
+#pragma unroll
+                for (int k = 0; k < PC_NSUMS; ++k) sums_lds[(size_t)s * PC_NSUMS + k] = C.tsum[k];
+            }
+#else
+            if (LEAN == 0 && lane == 0) tb_row[D] = C.tsum[0];     // (lane 0: tb_row is the row's start)
+#endif
 #endif
         } else if (!lean2 && nDer > 0) {
 #ifdef PCHIP_USER_TERMS
@@ -678,9 +692,13 @@
             double *row = S.babies + ((size_t)chain * nr + s) * nT;
             const double *tt = tbuf + (size_t)s * (D + 1);
 #ifdef PCHIP_USER_TERMS
-            if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) {   // finish(sum, theta) of the baby's kept sum, lane = baby: no walk over the data
+            if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) {   // finish(sums, theta) of the baby's kept sums, lane = baby: no walk over the data
                 double phi[PC_SRC_MAX_DERIVED];
-                (void)pchip_logl_finish(tt[D], tt, phi, D, S.nDer, S.src_data, (long)S.src_ndata);
+#ifdef PCHIP_USER_SUMS
+                (void)pc_user_finish(sums_lds + (size_t)s * PC_NSUMS, tt, phi, D, S.nDer, S.src_data, (long)S.src_ndata);
+#else
+                (void)pc_user_finish(tt + D, tt, phi, D, S.nDer, S.src_data, (long)S.src_ndata);
+#endif
                 for (int e = 0; e < S.nDer; ++e) row[S.d0 + e] = phi[e];
                 continue;
             }

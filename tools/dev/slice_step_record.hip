@@ -5,7 +5,8 @@
 // launcher is new): it holds every call against the launcher's rules written down a second time, here --
 //   declined (1)   nDims > 64 unfused; fused where pc_slice_fusable says no; more than one grade; the sequential stream; the correlated Gaussian
 //   accepted (0)   everything else: ONE launch of a row of PC_SLICE_STEP_VARIANTS, grid (chains, runs), 64 threads, the chain's LDS block plus
-//                  nDims doubles for a terms handle, pc_need_dyn_lds above 48 KB, LEAN = 0 whatever the likelihood, PT = 1 for prior kinds 2, 3
+//                  nDims doubles for a terms handle (and num_repeats x nsums for one with several sums, where the babies' theta rows are in LDS --
+//                  that block counts in the 48 KB decision), pc_need_dyn_lds above 48 KB, LEAN = 0 whatever the likelihood, PT = 1 for prior kinds 2, 3
 // Exit code 0 and a summary line when all calls agree; 1 and the first disagreements otherwise.  `--kernels`: the rows reached.
 // Built host-only with the address and undefined-behaviour sanitizers on the host code (make -C polychordlite_amd/csrc slice_step_record); tests/test_in_step_device.py runs it.
 #include <hip/hip_runtime.h>
@@ -41,7 +42,8 @@ void clear() { launches.clear(); attrs.clear(); error.clear(); }
 #include "pc_sample.hip"
 // what pc_sample.hip's host code calls in other files
 extern "C" int pc_rtc_launch(const PcState *, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t, void **) { rec::launch(expr, grid, block, sh); return 0; }
-extern "C" long pc_rtc_source_terms(int id) { return id == 2 ? 100 : 0; }
+extern "C" long pc_rtc_source_terms(int id) { return id == 2 || id == 3 ? 100 : 0; }
+extern "C" int pc_rtc_source_sums(int id) { return id == 3 ? 5 : 0; }
 extern "C" int pc_launch_bases_t(const PcState *S, unsigned, int, hipStream_t) { return S->D < 2; }
 extern "C" void pc_abi_set_last_error(const char *msg) { if (msg) rec::error = msg; }
 
@@ -58,15 +60,15 @@ int main(int argc, char **argv)
     auto fail = [&](const char *st, const std::string &what) { if (bad++ < 20) std::fprintf(stderr, "%s: %s\n", st, what.c_str()); };
     // nDims and num_repeats on both sides of every boundary the launcher tests (the fused widths 8 / 16 / 24, NROWS at 16 / 32, the unfused limit
     // 64; the babies' theta rows on both sides of 48 KB, the fused block on both sides of 150 KB), every likelihood kind (a source without and
-    // with the terms form), every prior kind, grades, the sequential stream, settings.ablate bits 0 and 15, bases in HBM or not
+    // with the terms form, of one sum and of five), every prior kind, grades, the sequential stream, settings.ablate bits 0 and 15, bases in HBM or not
     const int Ds[] = {1, 2, 8, 9, 16, 17, 20, 24, 25, 32, 33, 64, 65, 128, 256, 257};
     const int nrs[] = {1, 5, 40, 64, 65, 200, 255, 256, 1024, 1025};
-    const int kinds[] = {PC_LIKE_GAUSSIAN, PC_LIKE_RASTRIGIN, PC_LIKE_TWIN_GAUSSIAN, PC_LIKE_CORR_GAUSSIAN, PC_LIKE_SOURCE, -PC_LIKE_SOURCE};
+    const int kinds[] = {PC_LIKE_GAUSSIAN, PC_LIKE_RASTRIGIN, PC_LIKE_TWIN_GAUSSIAN, PC_LIKE_CORR_GAUSSIAN, PC_LIKE_SOURCE, -PC_LIKE_SOURCE, -100};
     char st[256];
     for (int D : Ds) for (int nr : nrs) for (int kind : kinds) for (int nDer = 0; nDer <= 2; nDer += 2) for (int pk = 1; pk <= 3; ++pk)
     for (int flags = 0; flags < 32; ++flags) for (int R : {1, 3, 16}) for (int nch : {30, 32}) for (int fused = 0; fused <= 1; ++fused) {
         PcState S{};
-        S.D = D; S.nr = nr; S.nDer = nDer; S.nT = 2 * D + nDer + 2; S.like.kind = kind < 0 ? -kind : kind; S.src_id = kind == PC_LIKE_SOURCE ? 1 : (kind < 0 ? 2 : 0);
+        S.D = D; S.nr = nr; S.nDer = nDer; S.nT = 2 * D + nDer + 2; S.like.kind = kind < 0 ? PC_LIKE_SOURCE : kind; S.src_id = kind == PC_LIKE_SOURCE ? 1 : (kind == -PC_LIKE_SOURCE ? 2 : (kind < 0 ? 3 : 0));
         S.prior.kind = pk; S.nb_total = 2;
         S.ngrade = (flags & 1) ? 2 : 1; S.seq_mode = (flags & 2) ? 1 : 0; S.ablate = ((flags & 4) ? PC_ABL_FUNCTOR : 0) | ((flags & 8) ? PC_ABL_RTC_BUILTINS : 0);
         S.nhat_raw = (flags & 16) ? nullptr : dummy;
@@ -78,10 +80,12 @@ int main(int argc, char **argv)
         const bool one_grade = S.ngrade <= 1 && !S.seq_mode, corr = S.like.kind == PC_LIKE_CORR_GAUSSIAN;
         bool want = one_grade && !corr && (fused ? pc_slice_fusable(&S) != 0 : D <= 64);
         const int fw = !fused ? 0 : (D <= 8 ? 8 : (D <= 16 ? 16 : 24)), nrows = D <= 16 ? 1 : ((D <= 32 || fused) ? 2 : 4);
-        const bool phi = nDer > 0 && sizeof(double) * ((size_t)D + nr) + 16 + sizeof(double) * (size_t)nr * (D + 1) <= 48 * 1024;
+        const size_t sums = S.src_id == 3 ? sizeof(double) * (size_t)nr * 5 : 0;
+        const bool phi = nDer > 0 && sizeof(double) * ((size_t)D + nr) + 16 + sizeof(double) * (size_t)nr * (D + 1) + sums <= 48 * 1024;
         size_t sh = sizeof(double) * ((size_t)D + nr) + 16 + (phi ? sizeof(double) * (size_t)nr * (D + 1) : 0);
         if (fused) sh += sizeof(double) * ((size_t)fw * D + (size_t)nr * (D + 2));
-        if (S.src_id == 2) sh += sizeof(double) * (size_t)D;
+        if (S.src_id >= 2) sh += sizeof(double) * (size_t)D;
+        if (phi) sh += sums;
         if (fused && sh > 150 * 1024) want = false;
         if (fused && want && (D > 24 || nr > 1024 || !S.nhat_raw)) fail(st, "pc_slice_fusable took a shape the fused kernel has no room for");
         if ((rc == 0) != want) { fail(st, std::string(rc == 0 ? "accepted" : "declined") + ", the rules say otherwise"); continue; }
