@@ -369,6 +369,31 @@ int  pchip_source_create_terms(const char *source, const char *options, const do
 #define PCHIP_SOURCE_MAX_SUMS 8
 int  pchip_source_create_sums(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums,
                               int with_prior);
+/* The QUADRATIC FORM: a Gaussian in data space with a dense covariance, logL = -1/2 r^T P r + const with r = d - m(theta) of length nres
+ * and P = C^-1 (binned power spectra, distance ladders, supernova compilations, correlated time series).  The source defines
+ *     __device__ double pchip_residual(const double *theta, int nDims, const double *data, long ndata, long i);
+ *     __device__ double pchip_logl_finish(double chi2, const double *theta, double *phi, int nDims, int nDerived,
+ *                                         const double *data, long ndata);
+ * residual(i), 0 <= i < nres, is called by ONE lane per i; finish is the terms form's own, of the finished chi2 = r^T P r, and writes
+ * all nDerived derived parameters (an accepted point keeps its chi2: the matrix is never walked a second time).  `precision` is P: host,
+ * nres x nres, row-major, copied at creation like the data; it is used EXACTLY as given -- not symmetrised, not factored: chi2 =
+ * sum_j r_j sum_i P[i * nres + j] r_i holds for any P.  The user's functions see data / ndata as given.  The defined order:
+ *   1. lane l calls residual(i) for i = l, l + 64, ...; the values are kept;
+ *   2. for every j:  q_j = 0.0;  for (i = 0; i < nres; ++i) q_j = fma(P[i * nres + j], r_i, q_j)  -- the fused multiply-add of IEEE 754,
+ *      rounded once: replay it on the host with fma();
+ *   3. t_j = r_j * q_j, one IEEE multiply (not fused with the add that follows);
+ *   4. chi2 = the sum of the t_j in the order defined for pchip_source_create_terms: lane l adds t_l, t_(l + 64), ... to 0.0 by plain
+ *      IEEE adds, then the balanced tree over the 64 lanes.
+ * A point's bits do not depend on whether it was evaluated alone or as one end of a bracket (both ends share ONE walk over P).
+ * Contract of residual: pure, may read theta and data, must not synchronise.  To the rest of the library the handle is a terms handle
+ * of nres terms and one sum: pchip_like.kind stays PCHIP_LIKE_SOURCE, launches count in path[PCHIP_PATH_SOURCE_TERMS] and
+ * path[PCHIP_PATH_SOURCE_KERNELS], pchip_source_eval, pchip_run_in_step and pchip_maximise_device take it as they take any terms handle.
+ * 1 <= nres <= PCHIP_SOURCE_MAX_RES (two blocks of residuals, 16 KB of LDS a chain at the limit; P at most 8 MB a run); precision !=
+ * NULL; with_prior as for pchip_source_create_sums.  -1 with the reason -- the range, the missing matrix, the compiler's log, the
+ * function the source lacks by name -- in polychord_hip_last_error(), before any device call. */
+#define PCHIP_SOURCE_MAX_RES 1024
+int  pchip_source_create_quad(const char *source, const char *options, const double *data, long ndata, long nres,
+                              const double *precision /* host, nres x nres, row-major */, int with_prior);
 /* The user's PRIOR in the same source and the same handle as the likelihood (pchip_prior.kind = PCHIP_PRIOR_SOURCE with pchip_like.kind =
  * PCHIP_LIKE_SOURCE, .source = the handle).  Besides the likelihood functions of its form -- nterms == 0: pchip_loglikelihood; nterms
  * >= 1: pchip_logl_term and pchip_logl_finish -- the source defines

@@ -548,7 +548,9 @@ struct Engine {
                 engine_fail(PC_RC_SETTINGS, "prior.kind = 3 (source prior): device source handle %d defines no pchip_prior_param -- make it with pchip_source_create_prior", like.source);
             S.src_id = like.source;
             src_terms = pc_rtc_source_terms(like.source) > 0;
-            if (n > 0) { d_src = blocks.dev<double>((size_t)n); upload(d_src, h, sizeof(double) * (size_t)n); S.src_data = d_src; S.src_ndata = n; }
+            // (a quadratic form: its precision matrix goes up behind the user's data, in the same block -- the kernels find it at src_data + src_ndata)
+            const long long nup = n + pc_rtc_source_tail(like.source);
+            if (nup > 0) { d_src = blocks.dev<double>((size_t)nup); upload(d_src, h, sizeof(double) * (size_t)nup); S.src_data = d_src; S.src_ndata = n; }
         }
         // a source prior is the handle's own function, inside the sampling kernels: there is no host function for callback mode to call
         if (prior.kind == PCHIP_PRIOR_SOURCE && like.kind != PC_LIKE_SOURCE)
@@ -2469,9 +2471,10 @@ int pchip_source_eval(int handle, const double *thetas, long n, int nDims, int n
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
     double *d_src = nullptr, *d_t = nullptr, *d_l = nullptr, *d_p = nullptr;
     const size_t nt = sizeof(double) * (size_t)n * nDims, np = sizeof(double) * (size_t)n * (nDerived > 0 ? nDerived : 1);
+    const long long nup = nd + pc_rtc_source_tail(handle);      // (a quadratic form: its precision matrix behind the user's data, as a run uploads it)
     int rc = 2;
     pc_abi_set_last_error(nullptr);
-    if ((nd == 0 || (hipMalloc(&d_src, sizeof(double) * (size_t)nd) == hipSuccess && hipMemcpy(d_src, h, sizeof(double) * (size_t)nd, hipMemcpyHostToDevice) == hipSuccess)) &&
+    if ((nup == 0 || (hipMalloc(&d_src, sizeof(double) * (size_t)nup) == hipSuccess && hipMemcpy(d_src, h, sizeof(double) * (size_t)nup, hipMemcpyHostToDevice) == hipSuccess)) &&
         hipMalloc(&d_t, nt) == hipSuccess && hipMalloc(&d_l, sizeof(double) * (size_t)n) == hipSuccess && hipMalloc(&d_p, np) == hipSuccess &&
         hipMemcpy(d_t, thetas, nt, hipMemcpyHostToDevice) == hipSuccess) {
         PcState S;

@@ -10,17 +10,30 @@
 
 // the number of sums of a handle made by pchip_source_create_sums; 0: any other handle, or none (pc_rtc.hip)
 extern "C" int pc_rtc_source_sums(int id);
+// the number of residuals of a handle made by pchip_source_create_quad; 0: any other handle, or none (pc_rtc.hip)
+extern "C" long pc_rtc_source_quad(int id);
+
+// A quadratic-form source keeps the residuals of the point -- of the two ends of a bracket -- in two blocks of nres doubles (an even
+// number each: 16-byte reads) at the FRONT of the dynamic LDS of every kernel that evaluates the likelihood (pc_sample.hip, PC_DYN_LDS):
+// their bytes, which every launcher of such a kernel adds to its own; 0 for any other state
+static inline size_t pc_quad_lds(const PcState *S)
+{
+    if (S->like.kind != PC_LIKE_SOURCE) return 0;
+    const long n = pc_rtc_source_quad(S->src_id);
+    return n > 0 ? sizeof(double) * 2 * (size_t)((n + 1) & ~1L) : 0;
+}
 
 // k_slice keeps the theta rows of a chain's babies in LDS (its run-time flag phi_lds: derived parameters at the end of the chain, summed
 // in that order) when they fit under 48 KB next to the chain's block; pc_slice_t_ok takes only states where it does
 // (pc_slice_plan's rule, asked by pc_slice_t_ok in another file: inline here, the one definition in this header, so that the library's
 //  exported pc_* names stay what they were).  A source with several sums keeps the sums of every baby beside the rows, [nr][nsums]: the
-// block counts here, and a shape it pushes over the limit writes its derived parameters inside the slice loop like any that does not fit
+// block counts here, and a shape it pushes over the limit writes its derived parameters inside the slice loop like any that does not fit.
+// The residual blocks of a quadratic form (pc_quad_lds) count in the same way.
 static inline int pc_slice_phi_lds(const PcState *S)
 {
     const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16, tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
     const size_t sums = S->like.kind == PC_LIKE_SOURCE ? sizeof(double) * (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0;
-    return (S->nDer > 0 && sh0 + tb + sums <= 48 * 1024) ? 1 : 0;
+    return (S->nDer > 0 && sh0 + tb + sums + pc_quad_lds(S) <= 48 * 1024) ? 1 : 0;
 }
 
 extern "C" {
@@ -109,8 +122,10 @@ int pc_launch_final_par_many(const PcManyRec *dR, int R, hipStream_t st);
 // 0: launched; 1: no such kernel (pc_rtc_error has the text)
 int pc_rtc_launch(const PcState *S, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t st, void **args);
 const char *pc_rtc_error(void);
-// 0: a source exists (and its data block, for the engine's upload)
+// 0: a source exists (and its data block, for the engine's upload: *n doubles of the user's, then pc_rtc_source_tail(id) of the handle's own)
 int pc_rtc_source_data(int id, const double **data, long long *n);
+// the doubles behind the user's data in that block (a quadratic form's precision matrix); 0: none, or no such handle
+long long pc_rtc_source_tail(int id);
 // the number of terms of a terms-form handle; 0: the plain form, or no such handle
 long pc_rtc_source_terms(int id);
 // 1: the handle's source defines pchip_prior_param as well (pchip_source_create_prior); 0: it does not, or no such handle

@@ -17,6 +17,13 @@
 // and pchip_logl_finish_sums (logL and the derived parameters from the finished sums); such a handle's unit gets PCHIP_USER_SUMS and
 // PCHIP_SRC_NSUMS in front beside the two #defines of the terms form, and the same evaluation code is compiled for that many sums.
 //
+// The quadratic form (pchip_source_create_quad): a Gaussian in data space with a dense precision matrix.  The source defines pchip_residual
+// (the i-th residual, one lane per i) and pchip_logl_finish (the terms form's own, of the finished chi2 = r^T P r); the matrix is copied
+// with the data and lies BEHIND the user's data in the handle's block (pc_rtc_source_tail doubles: a run uploads both in one piece, the
+// user's functions see data / ndata as given).  Such a handle is a terms handle of nres terms and one sum to everybody who asks, and its
+// unit gets PCHIP_USER_QUAD in front beside the two #defines of the terms form: pc_sample.hip's walk over the matrix is compiled in
+// their place only.
+//
 // A prior in the same source (pchip_source_create_prior): the text defines pchip_prior_param (theta[i] from the whole cube, one call per
 // parameter) next to the likelihood of either form; such a handle's unit gets PCHIP_USER_PRIOR in front, and a run with prior.kind =
 // PCHIP_PRIOR_SOURCE takes the table's kernel variants with that function behind the transform's one entry point (pc_sample.hip).
@@ -81,6 +88,9 @@ struct Source {
     std::vector<double> data;
     long nterms = 0;                       // > 0: the terms form (pchip_logl_term / pchip_logl_finish), the sum's length
     int nsums = 0;                         // > 0: several sums per evaluation (pchip_logl_terms / pchip_logl_finish_sums; pchip_source_create_sums)
+    long nquad = 0;                        // > 0: the quadratic form (pchip_residual / pchip_logl_finish; pchip_source_create_quad): nterms == nquad, and
+                                           //      the nquad x nquad precision matrix lies in `data` behind the user's ndata doubles
+    long long ndata = 0;                   // the user's data: the first ndata doubles of `data`
     bool has_prior = false;                // the source defines pchip_prior_param as well (pchip_source_create_prior)
 };
 
@@ -169,13 +179,14 @@ int compile(const Source *s, const std::string &unit, const std::vector<std::str
 
 // the translation unit of the sampling kernels: the library's kernels (pc_sample.hip declares pchip_loglikelihood under PCHIP_USER_SOURCE),
 // then the user's text -- its macros and pragmas reach nothing of the library's.  A terms handle: its form and its loop bound in front;
-// a handle with several sums: their number in front as well; a handle with a prior (pchip_source_create_prior): PCHIP_USER_PRIOR in front.
+// a handle with several sums: their number in front as well; a quadratic form: PCHIP_USER_QUAD in front as well; a handle with a prior (pchip_source_create_prior): PCHIP_USER_PRIOR in front.
 std::string kernel_unit(const Source *s)
 {
     const std::string prior = s && s->has_prior ? "#define PCHIP_USER_PRIOR 1\n" : "";
     const std::string sums = s && s->nsums > 0 ? "#define PCHIP_USER_SUMS 1\n#define PCHIP_SRC_NSUMS " + std::to_string(s->nsums) + "\n" : "";
+    const std::string quad = s && s->nquad > 0 ? "#define PCHIP_USER_QUAD 1\n" : "";
     if (s && s->nterms > 0)
-        return prior + sums + "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
+        return prior + sums + quad + "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
     return s ? prior + "#define PCHIP_USER_SOURCE 1\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n"
              : std::string("#include \"pc_sample.hip\"\n");
 }
@@ -200,14 +211,21 @@ const char *const PROBE_UNIT_SUMS =
     "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
     "{ double t[PCHIP_SRC_NSUMS]; pchip_logl_terms(th, nDims, data, ndata, i, t); out[0] = pchip_logl_finish_sums(t, th, phi, nDims, nDerived, data, ndata); }\n"
     "#include \"pchip_user_source.h\"\n";
+// ... and of pchip_source_create_quad: one residual, the finish of it
+const char *const PROBE_UNIT_QUAD =
+    "__device__ double pchip_residual(const double *theta, int nDims, const double *data, long ndata, long i);\n"
+    "__device__ double pchip_logl_finish(double chi2, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
+    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
+    "{ out[0] = pchip_logl_finish(pchip_residual(th, nDims, data, ndata, i), th, phi, nDims, nDerived, data, ndata); }\n"
+    "#include \"pchip_user_source.h\"\n";
 
 // ... and of pchip_source_create_prior: the probe of the handle's form, then pchip_prior_param behind its declaration, called as well
 const char *const PROBE_PRIOR_DECL =
     "__device__ double pchip_prior_param(const double *cube, int i, int nDims, const double *data, long ndata);\n";
 const char *const PROBE_PRIOR_CALL = "out[0] += pchip_prior_param(th, 0, nDims, data, ndata); }\n";
-std::string probe_unit(long nterms, int nsums, bool prior)
+std::string probe_unit(long nterms, int nsums, bool quad, bool prior)
 {
-    std::string u = nsums > 0 ? "#define PCHIP_SRC_NSUMS " + std::to_string(nsums) + "\n" + PROBE_UNIT_SUMS : std::string(nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT);
+    std::string u = quad ? std::string(PROBE_UNIT_QUAD) : nsums > 0 ? "#define PCHIP_SRC_NSUMS " + std::to_string(nsums) + "\n" + PROBE_UNIT_SUMS : std::string(nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT);
     if (!prior) return u;
     const size_t close = u.rfind(" }\n");        // the end of pchip_probe's body: the call goes in front of it
     u.replace(close, 3, std::string(" ") + PROBE_PRIOR_CALL);
@@ -300,7 +318,7 @@ int pc_rtc_launch(const PcState *S, const char *expr, dim3 grid, dim3 block, siz
 }
 const char *pc_rtc_error(void) { return t_err.empty() ? nullptr : t_err.c_str(); }
 
-// a source exists (and its data block, for the engine's upload)
+// a source exists (and its data block, for the engine's upload: *n of the user's doubles, pc_rtc_source_tail(id) of the handle's own behind them)
 int pc_rtc_source_data(int id, const double **data, long long *n)
 {
     Registry &G = reg();
@@ -308,8 +326,17 @@ int pc_rtc_source_data(int id, const double **data, long long *n)
     auto it = G.src.find(id);
     if (it == G.src.end()) return 1;
     *data = it->second->data.empty() ? nullptr : it->second->data.data();
-    *n = (long long)it->second->data.size();
+    *n = it->second->ndata;
     return 0;
+}
+
+// the doubles a handle keeps in its block BEHIND the user's data (a quadratic form: its precision matrix, nres x nres); 0: none, or no such handle
+long long pc_rtc_source_tail(int id)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    auto it = G.src.find(id);
+    return it == G.src.end() ? 0 : (long long)it->second->data.size() - it->second->ndata;
 }
 
 // the number of terms of a terms-form handle; 0: the plain form, or no such handle
@@ -330,6 +357,15 @@ int pc_rtc_source_sums(int id)
     return it == G.src.end() ? 0 : it->second->nsums;
 }
 
+// the number of residuals of a handle made by pchip_source_create_quad; 0: any other handle, or none
+long pc_rtc_source_quad(int id)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    auto it = G.src.find(id);
+    return it == G.src.end() ? 0 : it->second->nquad;
+}
+
 int pc_rtc_source_has_prior(int id)
 {
     Registry &G = reg();
@@ -338,9 +374,11 @@ int pc_rtc_source_has_prior(int id)
     return it != G.src.end() && it->second->has_prior ? 1 : 0;
 }
 
-// pchip_source_create[_terms | _sums | _prior]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
-// nterms > 0: the terms form, of nsums sums where nsums > 0.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
-int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums, bool prior, std::string *log)
+// pchip_source_create[_terms | _sums | _quad | _prior]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
+// nterms > 0: the terms form, of nsums sums where nsums > 0; precision != NULL: the quadratic form of nterms residuals, its matrix copied
+// behind the data.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
+int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums, bool prior, std::string *log,
+                         const double *precision)
 {
     if (!source) { *log = "pchip_source_create: no source"; return -1; }
     if (ndata < 0 || (ndata > 0 && !data)) { *log = "pchip_source_create: ndata > 0 needs a data block"; return -1; }
@@ -350,6 +388,8 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     auto s = std::make_shared<Source>();
     s->text = defs + "#line 1\n" + source;
     if (ndata > 0) s->data.assign(data, data + ndata);
+    s->ndata = ndata;
+    if (precision) { s->data.insert(s->data.end(), precision, precision + (size_t)nterms * (size_t)nterms); s->nquad = nterms; }
     s->nterms = nterms; s->nsums = nsums; s->has_prior = prior;
     std::string arch = "gfx950";
     int dev = 0, ndev = 0;
@@ -359,7 +399,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     }
     (void)hipGetLastError();
     std::vector<char> code; std::vector<std::string> lowered;
-    if (compile(s.get(), probe_unit(nterms, nsums, prior), { "pchip_probe" }, arch, code, lowered, *log)) return -1;
+    if (compile(s.get(), probe_unit(nterms, nsums, precision != nullptr, prior), { "pchip_probe" }, arch, code, lowered, *log)) return -1;
     Registry &G = reg();
     std::lock_guard<std::mutex> g(G.m);
     const int id = G.next++;
@@ -374,7 +414,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
 extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata)
 {
     std::string log;
-    const int id = pc_rtc_source_create(source, options, data, ndata, 0, 0, false, &log);
+    const int id = pc_rtc_source_create(source, options, data, ndata, 0, 0, false, &log, nullptr);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }
@@ -384,7 +424,7 @@ extern "C" int pchip_source_create_terms(const char *source, const char *options
     std::string log;
     int id = -1;
     if (nterms < 1) log = "pchip_source_create_terms: nterms = " + std::to_string(nterms) + " -- the sum needs at least one term (nterms >= 1)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, 0, false, &log);
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, 0, false, &log, nullptr);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }
@@ -395,7 +435,7 @@ extern "C" int pchip_source_create_prior(const char *source, const char *options
     std::string log;
     int id = -1;
     if (nterms < 0) log = "pchip_source_create_prior: nterms = " + std::to_string(nterms) + " -- 0 (the plain form) or the number of terms (nterms >= 1)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, 0, true, &log);
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, 0, true, &log, nullptr);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }
@@ -408,7 +448,21 @@ extern "C" int pchip_source_create_sums(const char *source, const char *options,
     if (nterms < 1) log = "pchip_source_create_sums: nterms = " + std::to_string(nterms) + " -- the sums need at least one term (nterms >= 1)";
     else if (nsums < 1 || nsums > PCHIP_SOURCE_MAX_SUMS)
         log = "pchip_source_create_sums: nsums = " + std::to_string(nsums) + " -- 1 <= nsums <= " + std::to_string(PCHIP_SOURCE_MAX_SUMS) + " (PCHIP_SOURCE_MAX_SUMS)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, nsums, with_prior != 0, &log);
+    else id = pc_rtc_source_create(source, options, data, ndata, nterms, nsums, with_prior != 0, &log, nullptr);
+    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
+    return id;
+}
+
+// the quadratic form: chi2 = r^T P r of nres residuals (pchip_residual / pchip_logl_finish), P copied here; with_prior as above
+extern "C" int pchip_source_create_quad(const char *source, const char *options, const double *data, long ndata, long nres, const double *precision,
+                                        int with_prior)
+{
+    std::string log;
+    int id = -1;
+    if (nres < 1 || nres > PCHIP_SOURCE_MAX_RES)
+        log = "pchip_source_create_quad: nres = " + std::to_string(nres) + " -- 1 <= nres <= " + std::to_string(PCHIP_SOURCE_MAX_RES) + " (PCHIP_SOURCE_MAX_RES)";
+    else if (!precision) log = "pchip_source_create_quad: precision == NULL -- the nres x nres matrix of the quadratic form (host, row-major)";
+    else id = pc_rtc_source_create(source, options, data, ndata, nres, 0, with_prior != 0, &log, precision);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }

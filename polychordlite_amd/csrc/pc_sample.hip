@@ -173,6 +173,14 @@ __device__ __forceinline__ void pc_prior_theta(const PcState &S, const LaneTable
 __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
 #endif
 
+// The dynamic LDS of a kernel that evaluates the likelihood, as `name`: the declaration every kernel had -- except in the unit of a
+// quadratic-form handle (PCHIP_USER_QUAD, below), where the kernel's own layout starts behind that form's residual blocks.
+#ifdef PCHIP_USER_QUAD
+#define PC_DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) char name##_all[]; char *const name = name##_all + PC_QUAD_LDS_BYTES
+#else
+#define PC_DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) char name[]
+#endif
+
 template <int DPL, int NROWS>
 __device__ __forceinline__ double wsum(double v) { return (DPL > 1) ? wave_sum<4>(v) : wave_sum<NROWS>(v); }
 
@@ -204,6 +212,29 @@ __device__ __forceinline__ double pc_user_finish(const double *sums, const doubl
 {
     return pchip_logl_finish_sums(sums, theta, phi, nDims, nDerived, data, ndata);
 }
+#elif defined(PCHIP_USER_QUAD)
+// The quadratic form (pchip_source_create_quad; PCHIP_USER_QUAD in front as well, PCHIP_SRC_NTERMS = nres): a Gaussian in data space with a
+// dense precision matrix, chi2 = r^T P r, where the user's pchip_residual supplies r_i and P (nres x nres, row-major, exactly as given)
+// lies behind the user's data in the run's block, at S.src_data + S.src_ndata.  To everything below it is a terms handle of one sum: the
+// finished chi2 is `the sum`.  Its one defined order (tests/test_source_quad.py rests on it):
+//   1. lane l: r_i = pchip_residual(i) for i = l, l + 64, ... into a block of nres doubles in LDS; one barrier
+//   2. lane l, every column j = l, l + 64, ...: q_j = 0.0; for (i = 0; i < nres; ++i) q_j = fma(P[i * nres + j], r_i, q_j)
+//      -- the fused multiply-add is explicit and correctly rounded; the 64 lanes read 64 consecutive doubles of row i, r_i is an LDS broadcast
+//   3. t_j = r_j * q_j, one IEEE multiply, kept from fusing with the add behind it by the empty asm of the terms form
+//   4. chi2 = the sum of the t_j in the terms form's order: lane l adds t_l, t_(l + 64), ... to 0.0, then wave_sum<4>
+// The residual blocks -- two, for the two ends of a bracket -- are the FIRST 2 x PC_QUAD_NP doubles of the workgroup's dynamic LDS: every
+// kernel that evaluates the likelihood starts its own layout behind them (PC_DYN_LDS below; the launchers add pc_quad_lds bytes), so that
+// the evaluation code finds them without a pointer handed down through every caller.  One wavefront a workgroup, as for every source.
+constexpr int PC_NSUMS = 1;
+constexpr long PC_QUAD_N = (long)(PCHIP_SRC_NTERMS);
+constexpr long PC_QUAD_NP = (PC_QUAD_N + 1) & ~1L;       // a block's length in doubles: even, both blocks on 16 bytes for the paired reads
+#define PC_QUAD_LDS_BYTES (sizeof(double) * 2 * (size_t)PC_QUAD_NP)
+__device__ double pchip_residual(const double *theta, int nDims, const double *data, long ndata, long i);
+__device__ double pchip_logl_finish(double chi2, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
+__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata)
+{
+    return pchip_logl_finish(sums[0], theta, phi, nDims, nDerived, data, ndata);
+}
 #else
 constexpr int PC_NSUMS = 1;
 __device__ double pchip_logl_term(const double *theta, int nDims, const double *data, long ndata, long i);
@@ -217,6 +248,112 @@ __device__ __forceinline__ double pc_user_finish(const double *sums, const doubl
     return pchip_logl_finish(sums[0], theta, phi, nDims, nDerived, data, ndata);
 }
 #endif
+#ifdef PCHIP_USER_QUAD
+// rows of P a lane keeps in flight for every column it holds, and the columns (strips of 64) it walks side by side: the fused multiply-adds
+// of one column are a dependent chain, the strips' chains are independent and share every r_i read.  Eight loads in flight a lane, two
+// chains for one point and four for a pair (with four strips, sixteen loads, the prior-table variants of k_slice spilled 28 vector
+// registers; with two none does)
+constexpr int PC_QUAD_FLIGHT = 4;
+constexpr int PC_QUAD_STRIPS = 2;
+__device__ __forceinline__ double *pc_quad_blocks()
+{
+    extern __shared__ __attribute__((aligned(16))) char pc_quad_res[];       // (the dynamic LDS from its start: every such declaration names it)
+    return (double *)pc_quad_res;
+}
+// G strips of columns from column j0 on, NP points: q of every (column, point) in the defined order, then the products and the lane's adds in
+// ascending j.  A lane whose column lies beyond nres walks column 0 (an address inside the matrix, no divergence) and adds nothing.
+template <int NP, int G>
+__device__ __forceinline__ void pc_quad_strips(const double *__restrict__ P, const double *r, long j0, int lane, double (&s)[NP])
+{
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    constexpr long N = PC_QUAD_N;
+    constexpr int U = PC_QUAD_FLIGHT;
+    double q[G][NP];
+    const double *col[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const long j = j0 + 64 * g + lane;
+        col[g] = P + (j < N ? j : 0);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) q[g][p] = 0.0;
+    }
+    long i = 0;
+    for (; i + U <= N; i += U) {                                  // (i a multiple of four: r + i on 16 bytes)
+        double m[U][G];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) m[u][g] = col[g][(size_t)(i + u) * N];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+#pragma unroll
+            for (int u = 0; u < U; u += 2) {
+                const v2d rr = *(const v2d *)(r + p * PC_QUAD_NP + i + u);
+#pragma unroll
+                for (int g = 0; g < G; ++g) q[g][p] = __builtin_fma(m[u][g], rr.x, q[g][p]);
+#pragma unroll
+                for (int g = 0; g < G; ++g) q[g][p] = __builtin_fma(m[u + 1][g], rr.y, q[g][p]);
+            }
+        }
+    }
+    for (; i < N; ++i) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const double m = col[g][(size_t)i * N];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) q[g][p] = __builtin_fma(m, r[p * PC_QUAD_NP + i], q[g][p]);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const long j = j0 + 64 * g + lane;
+        if (j < N) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double t = r[p * PC_QUAD_NP + j] * q[g][p];
+                asm volatile("" : "+v"(t));
+                s[p] = s[p] + t;
+            }
+        }
+    }
+}
+// chi2 of NP points (theta[p]: their LDS copies) in ONE walk over P, an accumulator per point and column: a point's bits do not depend on
+// whether it was evaluated alone or as one end of a bracket.  No barrier inside the walk.
+template <int NP>
+__device__ __forceinline__ void pc_quad_sum(const PcState &S, const double *const (&theta)[NP], int lane, double (&chi2)[NP])
+{
+    constexpr long N = PC_QUAD_N;
+    constexpr int G = PC_QUAD_STRIPS;
+    constexpr long K = (N + 63) / 64, KF = K / G;                 // strips; whole groups of G
+    constexpr int KR = (int)(K % G);                              // ... and the strips of the last group
+    double *r = pc_quad_blocks();
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+        for (long i = lane; i < N; i += 64) r[p * PC_QUAD_NP + i] = pchip_residual(theta[p], S.D, S.src_data, (long)S.src_ndata, i);
+    __syncthreads();                              // one wave per workgroup: cheap
+    const double *P = S.src_data + S.src_ndata;
+    double s[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) s[p] = 0.0;
+    for (long k = 0; k < KF; ++k) pc_quad_strips<NP, G>(P, r, 64 * G * k, lane, s);
+    if constexpr (KR > 0) pc_quad_strips<NP, (KR > 0 ? KR : 1)>(P, r, 64 * G * KF, lane, s);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) chi2[p] = wave_sum<4>(s[p]);
+}
+__device__ __forceinline__ void pc_terms_sum(const PcState &S, const double *theta, int lane, double (&sum)[PC_NSUMS])
+{
+    const double *const th[1] = { theta };
+    pc_quad_sum<1>(S, th, lane, sum);
+}
+__device__ __forceinline__ void pc_terms_sum2(const PcState &S, const double *thA, const double *thB, int lane, double (&sA)[PC_NSUMS],
+                                              double (&sB)[PC_NSUMS])
+{
+    const double *const th[2] = { thA, thB };
+    double c[2];
+    pc_quad_sum<2>(S, th, lane, c);
+    sA[0] = c[0]; sB[0] = c[1];
+}
+#else
 // terms a lane keeps in flight -- their loads travel together, a lane's wait for the data is what a short term costs --: four for one sum
 // (two a point in the pair pass), fewer as the sums multiply the values held (PC_NSUMS of them a term and point, beside as many accumulators)
 constexpr int PC_TERMS_FLIGHT = PC_NSUMS <= 1 ? 4 : (PC_NSUMS <= 4 ? 2 : 1);
@@ -292,6 +429,7 @@ __device__ __forceinline__ void pc_terms_sum2(const PcState &S, const double *th
 #pragma unroll
     for (int k = 0; k < PC_NSUMS; ++k) { sA[k] = wave_sum<4>(a[k]); sB[k] = wave_sum<4>(b[k]); }
 }
+#endif
 // logL of theta (uniform over the wave) and, in `sum`, the finished sums it came from: whoever accepts the point keeps them, and the
 // derived parameters are finish(sums, theta) again -- never a second walk over the data
 template <int DPL>
@@ -436,7 +574,7 @@ template <int DPL, int PT = 0>
 __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, double *rows /* [n][nT] */,
                                                      double *rows_logL)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    PC_DYN_LDS(smem);
     double *ybuf = (double *)smem;
     const int lane = threadIdx.x, a = blockIdx.x, attempt = attempt0 + a;
     const int D = S.D, nT = S.nT;
@@ -512,7 +650,7 @@ __global__ __launch_bounds__(64) void k_prior_transform(PcState S, const double 
 template <int DPL>
 __global__ __launch_bounds__(64) void k_source_eval(PcState S, const double *thetas /* [n][D] */, double *logL /* [n] */, double *phi /* [n][nDer] */)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    PC_DYN_LDS(smem);
     double *ybuf = (double *)smem;
     const int lane = threadIdx.x, D = S.D;
     const size_t base = (size_t)blockIdx.x * D;
@@ -699,7 +837,7 @@ __device__ __forceinline__ void pc_max_sort(const double *F, int *idx, int nv, i
 template <int DPL>
 __global__ __launch_bounds__(64) void k_maximise(PcState S, const double *in, const int *hdr, long long max_iter, double *out, long long *outi)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    PC_DYN_LDS(smem);
     const int lane = threadIdx.x, D = S.D, n = D, nv = D + 1, p = blockIdx.x;
     double *ybuf = (double *)smem, *X = ybuf + D, *F = X + (size_t)nv * D, *M = F + nv;
     int *idx = (int *)(M + (size_t)D * D);
@@ -2014,18 +2152,20 @@ template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, d
                                              else hipLaunchKernelGGL(K, G, B, SH, ST, __VA_ARGS__); } while (0)
 // the terms form of a source evaluates the two ends of a bracket in one pass over the data: LDS for the second theta behind the chain's block;
 // a handle with several sums (pchip_source_create_sums) keeps the sums of every baby behind that, [nr][nsums], where the babies' theta rows
-// are in LDS (phi_lds: pc_slice_phi_lds has counted this block in its decision)
+// are in LDS (phi_lds: pc_slice_phi_lds has counted this block in its decision); a quadratic form (pchip_source_create_quad) has its two
+// residual blocks, 2 x nres doubles a chain (nres rounded up to even), in front of the chain's block: pc_quad_lds, counted in that
+// decision as well
 static size_t pc_terms_lds(const PcState *S, int phi_lds)
 {
     if (S->like.kind != PC_LIKE_SOURCE || pc_rtc_source_terms(S->src_id) <= 0) return 0;
-    return sizeof(double) * ((size_t)S->D + (phi_lds ? (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0));
+    return sizeof(double) * ((size_t)S->D + (phi_lds ? (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0)) + pc_quad_lds(S);
 }
 // lane = coordinate: the coordinates a lane holds (template DPL) at nDims <= 64, 128, 256; 0 beyond (the launchers return 1)
 static int pc_dpl(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : (D <= 256 ? 4 : 0)); }
 extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL,
                                        hipStream_t st)
 {
-    const size_t sh = sizeof(double) * S->D;
+    const size_t sh = sizeof(double) * S->D + pc_quad_lds(S);
     const bool table = S->prior.kind >= 2;          // a prior table, or a source prior (kind 3: the same variants, from its handle's module)
     switch (pc_dpl(S->D) + (table ? 8 : 0)) {
     case 1: PC_LAUNCH((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
@@ -2340,7 +2480,7 @@ extern "C" int pc_launch_source_eval(const PcState *S, int n, const double *thet
     const int dpl = pc_dpl(S->D);
     if (S->like.kind != PC_LIKE_SOURCE || n < 1 || !dpl) return 1;
     const char *name = dpl == 1 ? "k_source_eval<1>" : (dpl == 2 ? "k_source_eval<2>" : "k_source_eval<4>");
-    return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D, st, *S, thetas, logL, phi);
+    return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D + pc_quad_lds(S), st, *S, thetas, logL, phi);
 }
 
 // pchip_source_prior_eval: the prior of a source handle at n points (device pointers) -- k_prior_transform of the handle's run-time module
@@ -2379,7 +2519,7 @@ extern "C" int pc_launch_max_rank(const PcState *S, int n, const double *rows, d
 extern "C" int pc_launch_maximise(const PcState *S, int nprob, const double *in, const int *hdr, long long max_iter, double *out, long long *outi, hipStream_t st)
 {
     if (S->D < 1 || S->D > 64 || nprob < 1) return 1;
-    const size_t sh = sizeof(double) * PC_MAX_LDS_DOUBLES(S->D);
+    const size_t sh = sizeof(double) * PC_MAX_LDS_DOUBLES(S->D) + pc_quad_lds(S);
     if (!pc_max_lds_fits("k_maximise", sh)) return 1;
     if (sh > 48 * 1024 && !pc_rtc_wanted(S)) pc_need_dyn_lds((const void *)k_maximise<1>, sh);
     PC_LAUNCH((k_maximise<1>), dim3(nprob), dim3(64), sh, st, *S, in, hdr, max_iter, out, outi);

@@ -1,6 +1,6 @@
 // pc_slice_body.inc -- the body of k_slice (pc_sample.hip), included by the one-run kernel and by k_slice_many (several runs in
 // step, blockIdx.y = run) so that both are the same statements on `S`, `batch`, `phi_lds`, `mat_lds`.  Not a header: no include guard.
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    PC_DYN_LDS(smem);                              // (a quadratic-form source: behind its residual blocks -- pc_sample.hip)
     __builtin_amdgcn_s_setprio(LEAN == 2 ? 0 : 3);  // a chain is one long dependent instruction stream: it goes first on its SIMD
 #if defined(SLICE_DBG) && SLICE_DBG == 2
     const long long kc0 = clock64(), kw0 = wall_clock64();
