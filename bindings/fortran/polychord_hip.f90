@@ -15,7 +15,9 @@ module polychord_hip
     public :: polychord_c_interface, polychord_hip_gaussian, polychord_hip_rastrigin, polychord_hip_twin_gaussian, &
               polychord_hip_uniform_prior, polychord_hip_set_gaussian, polychord_hip_set_uniform_prior, &
               polychord_hip_table_prior, polychord_hip_set_table_prior, pchip_prior_entry, &
-              polychord_hip_set_option, polychord_hip_set_sub_clustering, run_polychord_hip
+              polychord_hip_set_option, polychord_hip_set_sub_clustering, run_polychord_hip, &
+              polychord_hip_set_source, polychord_hip_source_loglike, polychord_hip_source_prior, &
+              pchip_source_create, pchip_source_destroy
 
     !> one parameter of a prior table (pchip_prior_entry of polychord_hip.h): the reference's type number 1 .. 10 (priors.f90:5-15),
     !! the prior block, the number of prior parameters and the parameters in the ini file's order
@@ -103,6 +105,40 @@ module polychord_hip
             import :: c_int
             integer(c_int), value :: n
             integer(c_int) :: dims(*)
+        end subroutine
+        !> The caller's own likelihood as HIP device source (polychord_hip.h: pchip_source_create), compiled at run time and evaluated
+        !! inside the sampling kernels: source and options NUL terminated (options: c_null_char alone for none), block(ndata) the data block
+        !! the source reads.  The handle (> 0), or -1 with the compiler's log in polychord_hip_last_error()
+        function pchip_source_create(source, options, block, ndata) result(handle) bind(c, name="pchip_source_create")
+            import :: c_char, c_double, c_long, c_int
+            character(kind=c_char) :: source(*), options(*)
+            real(c_double) :: block(*)
+            integer(c_long), value :: ndata
+            integer(c_int) :: handle
+        end function
+        subroutine pchip_source_destroy(handle) bind(c, name="pchip_source_destroy")
+            import :: c_int
+            integer(c_int), value :: handle
+        end subroutine
+        !> the handle the next polychord_c_interface calls use (0 clears it); 0, or non-zero for a handle that does not exist
+        function polychord_hip_set_source(handle) result(rc) bind(c, name="polychord_hip_set_source")
+            import :: c_int
+            integer(c_int), value :: handle
+            integer(c_int) :: rc
+        end function
+        !> pass it as `loglike`: the handle set above, inside the sampling kernels (called directly: one kernel launch a call)
+        function polychord_hip_source_loglike(theta, nDims, phi, nDerived) result(logL) &
+                bind(c, name="polychord_hip_source_loglike")
+            import :: c_double, c_int
+            real(c_double) :: theta(*), phi(*)
+            integer(c_int), value :: nDims, nDerived
+            real(c_double) :: logL
+        end function
+        !> pass it as `prior` with polychord_hip_source_loglike: the handle's own pchip_prior_param (pchip_source_create_prior)
+        subroutine polychord_hip_source_prior(cube, theta, nDims) bind(c, name="polychord_hip_source_prior")
+            import :: c_double, c_int
+            real(c_double) :: cube(*), theta(*)
+            integer(c_int), value :: nDims
         end subroutine
     end interface
 

@@ -85,6 +85,23 @@ typedef struct {
  * device.  polychord_hip_set_table_prior checks the table: 0, or non-zero with the message in polychord_hip_last_error(). */
 void polychord_hip_table_prior(double *cube, double *theta, int nDims);
 int  polychord_hip_set_table_prior(int nDims, const pchip_prior_entry *entries, const int *hyper);
+/* A likelihood (and prior) written as device source -- pchip_source_create and its kin in Part 2 below, any form -- behind the reference's
+ * callback signatures.  polychord_hip_set_source names the handle the next polychord_c_interface / _ini calls use (sticky and
+ * process-global like polychord_hip_set_gaussian; 0 clears it): 0, or non-zero with "... handle N does not exist" in
+ * polychord_hip_last_error().  The handle must be alive when the run starts.  Passed as `loglikelihood`, polychord_hip_source_loglike
+ * is recognised like a built-in: the handle is evaluated inside the sampling kernels under polychord_hip_uniform_prior, under
+ * polychord_hip_table_prior (so under any ini prior block) and under polychord_hip_source_prior, the handle's own pchip_prior_param
+ * (pchip_source_create_prior; only with polychord_hip_source_loglike as the likelihood); `maximise` then polishes on the device
+ * (pchip_maximise_device; nDims > 64 or no simplex: a message, no file).  Under any other prior function -- the caller's own -- the prior
+ * is called on the host, on the calling thread, and the parked proposals of a round are evaluated by ONE launch of the source (unless the
+ * caller registered a batch callback, which is then used as always).
+ * Both are also real host functions: pchip_source_eval / pchip_source_prior_eval at one point, the same bits -- ONE kernel launch a call,
+ * for single evaluations (a script calling its likelihood, cube_samples), not a sampling path.  Without a handle set, or for
+ * polychord_hip_source_prior with a handle that defines no prior, they end like a fatal condition of polychord_c_interface: message and
+ * `stop 1`, or in "halt_returns" mode the message in polychord_hip_last_error() and a return (logL then below any logzero). */
+int  polychord_hip_set_source(int handle);
+double polychord_hip_source_loglike(double *theta, int nDims, double *phi, int nDerived);
+void polychord_hip_source_prior(double *cube, double *theta, int nDims);
 /* Batched host evaluation.  In host-callback mode the engine parks the proposals of all chains of a nursery and hands them
  * to the host together; with a batch callback registered it makes ONE call per round instead of one loglikelihood call
  * per proposal: prior + likelihood for n hypercube points (row-major, host memory; logL[i] <= logzero marks an invalid
@@ -404,8 +421,9 @@ int  pchip_source_create_quad(const char *source, const char *options, const dou
  * deterministic, must not synchronise; only ever called for points inside the unit cube; the likelihood receives exactly the values
  * returned.  Same options rule, data block, handle space and pchip_source_destroy as pchip_source_create; a source that lacks one of
  * its functions fails here, by name.  The handle also runs under prior.kind 1 and 2, as one without a prior does.  A prior source for a
- * built-in or callback likelihood (a prior-only handle), pchip_run_repeats and the PolyChord-interface doors are not supported:
- * the run fails with a message (several seeds in step: pchip_run_in_step).  Launches are counted in path[PCHIP_PATH_DEVICE_PRIOR] and path[PCHIP_PATH_SOURCE_KERNELS]. */
+ * built-in or callback likelihood (a prior-only handle) and pchip_run_repeats are not supported: the run fails with a message (several
+ * seeds in step: pchip_run_in_step).  At the PolyChord-interface doors: polychord_hip_set_source, then polychord_hip_source_loglike and
+ * polychord_hip_source_prior as the callbacks (Part 2's first block).  Launches are counted in path[PCHIP_PATH_DEVICE_PRIOR] and path[PCHIP_PATH_SOURCE_KERNELS]. */
 int  pchip_source_create_prior(const char *source, const char *options, const double *data, long ndata, long nterms);
 /* The prior of such a handle at n hypercube points, cubes[n][nDims] -> thetas[n][nDims] (host arrays): one wavefront a point, through
  * the transform code of the sampling kernels.  Return codes as pchip_source_eval. */

@@ -138,6 +138,12 @@ def load():
     lib.pchip_source_eval.restype = C.c_int
     lib.pchip_source_destroy.argtypes = [C.c_int]
     lib.pchip_source_destroy.restype = None
+    lib.polychord_hip_set_source.argtypes = [C.c_int]
+    lib.polychord_hip_set_source.restype = C.c_int
+    lib.polychord_hip_source_loglike.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int]
+    lib.polychord_hip_source_loglike.restype = C.c_double
+    lib.polychord_hip_source_prior.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+    lib.polychord_hip_source_prior.restype = None
     lib.pchip_rtc_embedded_source.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     lib.pchip_rtc_embedded_source.restype = C.c_char_p
     lib.pchip_rtc_compile_check.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_double)]
@@ -208,6 +214,15 @@ def source_create(source, options=(), data=None, nterms=None, prior=False, nsums
         log = lib.polychord_hip_last_error()
         raise RuntimeError("device source does not compile:\n" + (log.decode(errors="replace") if log else "(no log)"))
     return h
+
+
+def set_source(handle):
+    """polychord_hip_set_source: the handle behind polychord_hip_source_loglike / polychord_hip_source_prior for the next calls of the
+    PolyChord-interface doors (0 clears it); RuntimeError with the library's message for a handle that does not exist"""
+    lib = load()
+    if lib.polychord_hip_set_source(int(handle)) != 0:
+        msg = lib.polychord_hip_last_error()
+        raise RuntimeError(msg.decode(errors="replace") if msg else f"polychord_hip_set_source({handle}) failed")
 
 
 def source_eval(handle, thetas, nDerived=0):

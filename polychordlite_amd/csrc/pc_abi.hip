@@ -33,6 +33,7 @@ struct Builtins {
     bool device_prior = true;                         // option "device_prior": a table goes to the device when the likelihood is there
     int batch = 0, device = -1, epoch_discard = 0;
     std::vector<int> sub_dims;                        // polychord_hip_set_sub_clustering: 0-based cube coordinates of the sub-dimension pass
+    int source = 0;                                   // polychord_hip_set_source: the device source handle behind polychord_hip_source_loglike / _prior (0: none)
     bool halt_returns = false;                        // fatal conditions return to the caller instead of `stop 1` (language bindings)
     std::string last_error;
 } G;
@@ -46,6 +47,22 @@ struct HaltRequest { std::string msg; };
     std::fprintf(stderr, "%s\n", msg);
     if (G.halt_returns) throw HaltRequest{msg};
     std::exit(1);
+}
+// ... for the host functions a caller may call directly, outside polychord_c_interface (no frame of ours to catch a HaltRequest): the
+// message and `stop 1`, or in "halt_returns" mode the message kept for polychord_hip_last_error() and a return to the function
+void halt_or_return(const std::string &msg)
+{
+    std::fprintf(stderr, "%s\n", msg.c_str());
+    if (!G.halt_returns) std::exit(1);
+    G.last_error = msg;
+}
+// the form of a device source handle, for the run header
+std::string source_form(int h)
+{
+    if (pc_rtc_source_quad(h) > 0) return "quadratic form, " + std::to_string(pc_rtc_source_quad(h)) + " residuals";
+    if (pc_rtc_source_sums(h) > 0) return "terms form, " + std::to_string(pc_rtc_source_terms(h)) + " terms, " + std::to_string(pc_rtc_source_sums(h)) + " sums";
+    if (pc_rtc_source_terms(h) > 0) return "terms form, " + std::to_string(pc_rtc_source_terms(h)) + " terms";
+    return "plain form";
 }
 
 // Fortran E24.15E3:  "  0.626931681801488E-001"
@@ -469,6 +486,38 @@ void polychord_hip_table_prior(double *cube, double *theta, int D)
     if (G.table.D != D) halt_program("polychord_hip: polychord_hip_set_table_prior was not called for this nDims");
     pc_prior_table_eval(G.table, cube, theta);
 }
+// A device source (pchip_source_create and its kin) behind the reference's callback signatures: polychord_hip_set_source names the handle,
+// polychord_c_interface recognises the two pointers below and evaluates the handle inside the sampling kernels.  Called as functions they
+// ARE pchip_source_eval / pchip_source_prior_eval at one point (the same bits): one launch a call, for single evaluations.
+int polychord_hip_set_source(int handle)
+{
+    const double *h = nullptr; long long n = 0;
+    if (handle != 0 && pc_rtc_source_data(handle, &h, &n)) {
+        G.last_error = "polychord_hip_set_source: device source handle " + std::to_string(handle) + " does not exist";
+        return 1;
+    }
+    G.source = handle;
+    G.last_error.clear();
+    return 0;
+}
+double polychord_hip_source_loglike(double *theta, int nDims, double *phi, int nDerived)
+{
+    const double invalid = -1.7976931348623157e308;       // (below any logzero: what a caller that goes on sees)
+    if (!G.source) { halt_or_return("polychord_hip: polychord_hip_set_source was not called"); return invalid; }
+    double logL = invalid;
+    const int rc = pchip_source_eval(G.source, theta, 1, nDims, nDerived, &logL, nDerived > 0 ? phi : nullptr);
+    if (rc != 0) {
+        halt_or_return("polychord_hip: polychord_hip_source_loglike failed (code " + std::to_string(rc) + ")" + (rc == 1 && !G.last_error.empty() ? ": " + G.last_error : std::string()));
+        return invalid;
+    }
+    return logL;
+}
+void polychord_hip_source_prior(double *cube, double *theta, int nDims)
+{
+    if (!G.source) { halt_or_return("polychord_hip: polychord_hip_set_source was not called"); return; }
+    const int rc = pchip_source_prior_eval(G.source, cube, 1, nDims, theta);
+    if (rc != 0) halt_or_return("polychord_hip: polychord_hip_source_prior failed (code " + std::to_string(rc) + ")" + (rc == 1 && !G.last_error.empty() ? ": " + G.last_error : std::string()));
+}
 int polychord_hip_set_table_prior(int D, const pchip_prior_entry *entries, const int *hyper)
 {
     PcPriorTable T;
@@ -601,7 +650,8 @@ static std::vector<double> time_speeds_host(polychord_loglike_fn like, polychord
 {
     std::vector<double> speed(nGrade, 1.0);
     const bool device_like = like == polychord_hip_gaussian || like == polychord_hip_rastrigin ||
-                             like == polychord_hip_twin_gaussian || like == polychord_hip_corr_gaussian;
+                             like == polychord_hip_twin_gaussian || like == polychord_hip_corr_gaussian ||
+                             like == polychord_hip_source_loglike;
     if (device_like) return speed;
     std::vector<double> cube(D), theta(D), phi(std::max(1, nDer));
     unsigned long long n = 0;
@@ -722,8 +772,22 @@ static void c_interface_impl(
     else if (loglikelihood == polychord_hip_corr_gaussian) {
         if (G.cg_D != nDims) halt_program("polychord_hip: polychord_hip_set_corr_gaussian was not called for this nDims");
         L.kind = PCHIP_LIKE_CORR_GAUSSIAN; L.invcov = G.cg_invcov.data(); L.mean = G.cg_mean.data(); L.logdetcov = G.cg_logdet;
+    } else if (loglikelihood == polychord_hip_source_loglike) {
+        // a device source behind the reference's signature: the handle knows its form (plain, terms, several sums, quadratic)
+        if (!G.source) halt_program("polychord_hip: polychord_hip_set_source was not called");
+        const double *h = nullptr; long long n = 0;
+        if (pc_rtc_source_data(G.source, &h, &n)) halt_program(("polychord_hip: device source handle " + std::to_string(G.source) + " does not exist").c_str());
+        L.kind = PCHIP_LIKE_SOURCE; L.source = G.source; L.fn = loglikelihood;
     } else { L.kind = PCHIP_LIKE_CALLBACK; L.fn = loglikelihood; }
-    if (prior == polychord_hip_uniform_prior) {
+    const int source_handle = L.kind == PCHIP_LIKE_SOURCE ? L.source : 0;
+    if (prior == polychord_hip_source_prior) {
+        // the handle's own pchip_prior_param, inside the sampling kernels (the engine's wording where the pair does not fit)
+        if (L.kind != PCHIP_LIKE_SOURCE)
+            halt_program("polychord_hip: prior.kind = 3 (source prior) needs a device source likelihood of the same handle: pass polychord_hip_source_loglike as the likelihood (a prior-only source is not supported)");
+        if (!pc_rtc_source_has_prior(L.source))
+            halt_program(("polychord_hip: prior.kind = 3 (source prior): device source handle " + std::to_string(L.source) + " defines no pchip_prior_param -- make it with pchip_source_create_prior").c_str());
+        P.kind = PCHIP_PRIOR_SOURCE; P.fn = prior;
+    } else if (prior == polychord_hip_uniform_prior) {
         P.kind = 1;
         if (G.up_D == nDims) { P.lo = G.up_lo.data(); P.hi = G.up_hi.data(); }
     } else if (prior == polychord_hip_table_prior && G.device_prior && L.kind != PCHIP_LIKE_CALLBACK) {
@@ -751,6 +815,22 @@ static void c_interface_impl(
         // a user prior with a built-in likelihood: evaluate both on the host (the device still proposes)
         L.kind = PCHIP_LIKE_CALLBACK; L.fn = loglikelihood;
     }
+    // ... a source likelihood among them: callback mode through polychord_hip_source_loglike, but -- unless the caller has a batch callback
+    // of their own, which wins -- the parked proposals of a round go through an evaluator registered for the length of this call: the host
+    // prior row by row on this thread, ONE launch of the source for all of them (pc_engine.hip, pc_source_batch_eval)
+    struct BatchGuard {
+        void *ev = nullptr; polychord_batch_fn fn0 = nullptr; void *user0 = nullptr;
+        ~BatchGuard() { if (ev) { polychord_hip_set_batch_callback(fn0, user0); pc_source_batch_close(ev); } }
+    } batch_guard;
+    if (source_handle && L.kind == PCHIP_LIKE_CALLBACK) {
+        pc_batch_callback_get(&batch_guard.fn0, &batch_guard.user0);
+        if (!batch_guard.fn0) {
+            if (!prior) halt_program("polychord_hip: a source likelihood under a host prior needs the prior function");
+            batch_guard.ev = pc_source_batch_open(source_handle, s.device, nDims, nDerived, prior);
+            if (!batch_guard.ev) halt_program(("polychord_hip: " + (G.last_error.empty() ? std::string("the batch evaluator of the source could not be opened") : G.last_error)).c_str());
+            polychord_hip_set_batch_callback(pc_source_batch_eval, batch_guard.ev);
+        }
+    }
     FileSink sink;
     sink.base = base; sink.root = root; sink.nDims = nDims; sink.nDer = nDerived;
     sink.write_stats = write_stats_f; sink.write_live = write_live; sink.write_dead = write_dead;
@@ -774,6 +854,12 @@ static void c_interface_impl(
             std::printf("chains in flight when the list of clusters changes: %s\n",
                         s.epoch_discard ? "all discarded (epoch_discard = 1: the reference farm's rule, nested_sampling.F90:313)"
                                         : "only those seeded in the cluster that ended are lost (epoch_discard = 0, this engine's default; option \"epoch_discard\" = 1: the reference farm's rule)");
+        if (L.kind == PCHIP_LIKE_SOURCE)
+            std::printf("likelihood: device source handle %d (%s) evaluated on the device, inside the sampling kernels\n", source_handle, source_form(source_handle).c_str());
+        else if (batch_guard.ev)
+            std::printf("likelihood: device source handle %d (%s)\nsource likelihood evaluated on the device in batches; prior on the host\n", source_handle, source_form(source_handle).c_str());
+        else if (source_handle)
+            std::printf("likelihood: device source handle %d (%s); evaluations through the caller's batch callback\n", source_handle, source_form(source_handle).c_str());
         if (table_on_device) std::printf("prior table evaluated on the device, inside the sampling kernels (option \"device_prior\" = 0: on the host)\n");
         if (write_resume || read_resume) std::printf("Resume file: %s/%s.resume\n", base.c_str(), root.c_str());
         std::printf("\nnum_repeats:");
@@ -787,7 +873,20 @@ static void c_interface_impl(
     if (maximise && r.nlive_final > 0) {
         // nested_sampling.F90:379: polish the best live points of the set at termination (host side, pc_maximise.hip)
         const std::string mpath = base + "/" + root + ".maximum";
-        if (pchip_maximise(loglikelihood, prior, nDims, nDerived, logzero, r.live, r.live_cluster, r.nlive_final,
+        if (L.kind == PCHIP_LIKE_SOURCE) {
+            // a recognised source under a device prior has no host function to polish through: the device maximiser, and its values to the file.
+            // nDims > 64 or a leg without a simplex: a message and no file, the run's results stand
+            pchip_maximum m{};
+            const int mrc = pchip_maximise_device(&s, &L, &P, r.live, r.live_cluster, r.nlive_final, posteriors ? r.post_mean : nullptr, 0, &m);
+            const int wrc = mrc == 0 ? pchip_maximum_write(&m, nDims, nDerived, mpath.c_str()) : 0;
+            pchip_maximum_free(&m);
+            if (mrc == 2) { pchip_result_free(&r); halt_program("polychord_hip: the device maximiser failed (HIP error, message above)"); }
+            if (mrc != 0) {
+                std::fprintf(stderr, "polychord_hip: maximise: %s -- %s is not written\n", G.last_error.empty() ? "the device maximiser gave no result" : G.last_error.c_str(), mpath.c_str());
+                G.last_error.clear();     // (not a fatal condition of the call: a binding must not raise for it)
+            }
+            if (wrc == 2) { pchip_result_free(&r); halt_program(("PolyChord Error: " + base + " does not exist").c_str()); }
+        } else if (pchip_maximise(loglikelihood, prior, nDims, nDerived, logzero, r.live, r.live_cluster, r.nlive_final,
                            posteriors ? r.post_mean : nullptr, mpath.c_str()) == 2)
             halt_program(("PolyChord Error: " + base + " does not exist").c_str());
     }

@@ -2489,6 +2489,98 @@ int pchip_source_eval(int handle, const double *thetas, long n, int nDims, int n
     return rc;
 }
 
+// ---- a source likelihood under a HOST prior, for the PolyChord-interface doors (pc_abi.hip) ------------------------------------------
+// pchip_run refuses that pair (a source has no host function of its own to run callback mode through); the doors run callback mode with
+// polychord_hip_source_loglike and register this evaluator as the batch callback for the length of their call: the parked proposals of a
+// round get the host prior one by one, on the calling thread, and ONE launch of k_source_eval for all of them -- the bits of
+// pchip_source_eval at each point (one wavefront a point, whatever n).  Opened once per run: the handle's data block (a quadratic form's
+// matrix behind it) stays on the device, the theta / logL / phi buffers grow on demand, the copies and the launch go through a stream of
+// its own and only that stream is waited for.
+struct PcSourceBatch {
+    int handle = 0, D = 0, nDer = 0;
+    polychord_prior_fn prior = nullptr;
+    hipStream_t st = nullptr;
+    double *d_src = nullptr; long long nd = 0;
+    double *d_buf = nullptr, *h_buf = nullptr;      // [cap] rows of theta (D) | logL (1) | phi (max(1, nDer)): device, and pinned host
+    long cap = 0;
+    bool failed = false;
+    size_t row() const { return (size_t)D + 1 + (size_t)(nDer > 0 ? nDer : 1); }
+    bool grow(long n)
+    {
+        if (n <= cap) return true;
+        const long want = std::max(n, 2 * cap);
+        (void)hipFree(d_buf); (void)hipHostFree(h_buf); d_buf = h_buf = nullptr; cap = 0;
+        if (hipMalloc(&d_buf, sizeof(double) * row() * (size_t)want) != hipSuccess || hipHostMalloc(&h_buf, sizeof(double) * row() * (size_t)want) != hipSuccess) return false;
+        cap = want;
+        return true;
+    }
+};
+
+void *pc_source_batch_open(int handle, int device, int nDims, int nDerived, polychord_prior_fn prior)
+{
+    const double *h = nullptr; long long nd = 0;
+    if (pc_rtc_source_data(handle, &h, &nd)) { pc_abi_set_last_error(("device source handle " + std::to_string(handle) + " does not exist").c_str()); return nullptr; }
+    if (!prior || nDims < 1 || nDims > 256 || nDerived < 0 || nDerived > PC_SRC_MAX_DERIVED) { pc_abi_set_last_error("a source likelihood under a host prior: a prior function, 1 <= nDims <= 256, 0 <= nDerived <= 32"); return nullptr; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); pc_abi_set_last_error("no HIP device available -- this engine has no CPU path"); return nullptr; }
+    PcSourceBatch *b = new PcSourceBatch;
+    b->handle = handle; b->D = nDims; b->nDer = nDerived; b->prior = prior; b->nd = nd;
+    const long long nup = nd + pc_rtc_source_tail(handle);
+    bool ok = hipSetDevice(device >= 0 ? device % ndev : 0) == hipSuccess && hipStreamCreate(&b->st) == hipSuccess;
+    if (ok && nup > 0)
+        ok = hipMalloc(&b->d_src, sizeof(double) * (size_t)nup) == hipSuccess &&
+             hipMemcpyAsync(b->d_src, h, sizeof(double) * (size_t)nup, hipMemcpyHostToDevice, b->st) == hipSuccess && hipStreamSynchronize(b->st) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); pc_abi_set_last_error("a source likelihood under a host prior: the stream or the data block could not be set up on the device"); pc_source_batch_close(b); return nullptr; }
+    return b;
+}
+
+void pc_source_batch_close(void *user)
+{
+    PcSourceBatch *b = (PcSourceBatch *)user;
+    if (!b) return;
+    if (b->st) { (void)hipStreamSynchronize(b->st); (void)hipStreamDestroy(b->st); }
+    (void)hipFree(b->d_src); (void)hipFree(b->d_buf); (void)hipHostFree(b->h_buf);
+    delete b;
+}
+
+// (a polychord_batch_fn: `user` is the evaluator)
+void pc_source_batch_eval(void *user, int n, int nDims, int nDerived, const double *cube, double *theta, double *phi, double *logL)
+{
+    PcSourceBatch *b = (PcSourceBatch *)user;
+    const int D = b->D, nDer = b->nDer, pd = nDer > 0 ? nDer : 1;
+    if (n < 1) return;
+    for (int i = 0; i < n; ++i) b->prior(const_cast<double *>(cube) + (size_t)i * D, theta + (size_t)i * D, D);
+    bool ok = !b->failed && nDims == D && nDerived == nDer && b->grow(n);
+    if (ok) {
+        double *h_t = b->h_buf, *h_l = h_t + (size_t)n * D, *h_p = h_l + n;
+        double *d_t = b->d_buf, *d_l = d_t + (size_t)n * D, *d_p = d_l + n;
+        std::memcpy(h_t, theta, sizeof(double) * (size_t)n * D);
+        PcState S;
+        std::memset(&S, 0, sizeof(S));
+        S.D = D; S.nDer = nDer; S.like.kind = PC_LIKE_SOURCE; S.src_id = b->handle; S.src_data = b->d_src; S.src_ndata = b->nd;
+        ok = hipMemcpyAsync(d_t, h_t, sizeof(double) * (size_t)n * D, hipMemcpyHostToDevice, b->st) == hipSuccess;
+        if (ok && pc_launch_source_eval(&S, n, d_t, d_l, d_p, b->st)) { ok = false; pc_abi_set_last_error(pc_rtc_error() ? pc_rtc_error() : "a source likelihood under a host prior: k_source_eval could not be launched"); }
+        else if (ok) {
+            ok = hipMemcpyAsync(h_l, d_l, sizeof(double) * ((size_t)n + (size_t)n * pd), hipMemcpyDeviceToHost, b->st) == hipSuccess && hipStreamSynchronize(b->st) == hipSuccess;
+            if (!ok) pc_abi_set_last_error((std::string("a source likelihood under a host prior: HIP error ") + hipGetErrorString(hipGetLastError())).c_str());
+        }
+        if (ok) {
+            std::memcpy(logL, h_l, sizeof(double) * (size_t)n);
+            if (nDer > 0) std::memcpy(phi, h_p, sizeof(double) * (size_t)n * nDer);
+        }
+    } else if (!b->failed) pc_abi_set_last_error("a source likelihood under a host prior: the buffers of a round could not be allocated");
+    if (!ok) {      // no value to give: every point invalid, and the run stops at this host boundary (the message stays in polychord_hip_last_error)
+        if (!b->failed && polychord_hip_last_error()) std::fprintf(stderr, "polychord_hip: %s\n", polychord_hip_last_error());
+        b->failed = true;
+        for (int i = 0; i < n; ++i) logL[i] = -1.7976931348623157e308;
+        for (size_t i = 0; i < (size_t)n * pd; ++i) phi[i] = 0.0;
+        polychord_hip_request_stop();
+    }
+}
+
+// the batch callback that is registered now (polychord_hip_set_batch_callback): the doors put theirs in only where the caller has none
+void pc_batch_callback_get(polychord_batch_fn *fn, void **user) { std::lock_guard<std::mutex> g(g_cb_mutex); if (fn) *fn = g_batch_fn; if (user) *user = g_batch_user; }
+
 
 // ---- the device maximiser: `maximise = T` for problems that live wholly on the device (k_max_rank, k_maximise: pc_sample.hip) -----------
 // One engine state serves every run (the runs of pchip_run_in_step share their problem): its set-up gives the likelihood, the prior and the

@@ -96,6 +96,14 @@ void *pc_cache_host_alloc(size_t bytes);
 void pc_cache_host_free(void *p);
 // several runs of one problem in step on a device.  Returns 0 or the first failing run's code.
 int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds, int device, int max_in_flight, pchip_result *results);
+// A source likelihood under a HOST prior (the PolyChord-interface doors): an evaluator opened once per run -- the handle's data block resident
+// on `device`, a stream and buffers of its own -- whose pc_source_batch_eval is a polychord_batch_fn (user = the evaluator): the host prior
+// row by row on the calling thread, then one launch of k_source_eval for all n rows.  open: NULL with the reason in polychord_hip_last_error()
+void *pc_source_batch_open(int handle, int device, int nDims, int nDerived, polychord_prior_fn prior);
+void pc_source_batch_eval(void *user, int n, int nDims, int nDerived, const double *cube, double *theta, double *phi, double *logL);
+void pc_source_batch_close(void *user);
+// the batch callback registered now (polychord_hip_set_batch_callback)
+void pc_batch_callback_get(polychord_batch_fn *fn, void **user);
 // ---- pc_fast.hip -------------------------------------------------------------------------------------------
 // _fits: 1 where the kernel's LDS block fits; launchers: 0: launched; 1: not this way
 int pc_fast_fits(const PcState *S);

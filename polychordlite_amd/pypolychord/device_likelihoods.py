@@ -75,6 +75,72 @@ class CorrelatedGaussian(_Builtin):
         api.load().polychord_hip_set_corr_gaussian(nDims, api.dptr(self.invcov), api.dptr(self.mean), self.logdetcov)
 
 
+class Source(_Builtin):
+    """The user's own likelihood as HIP device source (include/polychord_hip.h: pchip_source_create and its kin), compiled at run time and
+    evaluated inside the sampling kernels.  The arguments are those of `_ctypes_api.source_create`: `source` the text; `data` its data
+    block; `nterms` the terms form, `nsums` with it several sums per evaluation; `residuals` / `precision` the quadratic form;
+    `prior=True`: the text defines pchip_prior_param as well (pass `SourcePrior(this)` as the prior); `options`: -D / -U compiler options.
+    The handle is made on first use (RuntimeError with the compiler's log if the text does not compile).  Under `UniformPrior`,
+    `TablePrior` or `SourcePrior` the whole run stays on the device; under any other prior callable the prior is called on the host and
+    the likelihood is evaluated on the device, a round's proposals in one launch.  Called like a function it is the library's host function
+    (polychord_hip_source_loglike: one kernel launch a call, for single evaluations).  `close()` destroys the handle."""
+    symbol = "polychord_hip_source_loglike"
+
+    def __init__(self, source, nDerived=0, data=None, nterms=None, nsums=None, residuals=None, precision=None, prior=False, options=None):
+        self.source, self.nDerived, self.data, self.nterms, self.nsums = source, nDerived, data, nterms, nsums
+        self.residuals, self.precision, self.prior, self.options = residuals, precision, prior, options
+        self._handle = None
+
+    @property
+    def handle(self):
+        if self._handle is None:
+            self._handle = api.source_create(self.source, options=self.options or (), data=self.data, nterms=self.nterms, prior=self.prior,
+                                             nsums=self.nsums, residuals=self.residuals, precision=self.precision)
+        return self._handle
+
+    def configure(self, nDims):
+        api.set_source(self.handle)
+
+    def __call__(self, theta):
+        lib = api.load()
+        lib.polychord_hip_set_option(b"halt_returns", 1.0)      # a failure comes back as an exception, not as `stop 1`
+        out = super().__call__(theta)
+        msg = lib.polychord_hip_last_error()
+        if msg:
+            raise RuntimeError(msg.decode(errors="replace"))
+        return out
+
+    def close(self):
+        if self._handle is not None:
+            lib = api.load()
+            lib.pchip_source_destroy(self._handle)
+            self._handle = None
+
+
+class SourcePrior:
+    """The prior of a `Source(..., prior=True)`: the handle's own pchip_prior_param inside the sampling kernels; only with that Source as
+    the likelihood.  Called like a function it is the library's host function (polychord_hip_source_prior, one launch a call)."""
+    symbol = "polychord_hip_source_prior"
+
+    def __init__(self, source_obj):
+        self.source_obj = source_obj
+
+    def configure(self, nDims):
+        self.source_obj.configure(nDims)
+
+    def __call__(self, cube):
+        lib = api.load()
+        lib.polychord_hip_set_option(b"halt_returns", 1.0)
+        cube = np.ascontiguousarray(cube, dtype=np.float64)
+        self.configure(cube.size)
+        theta = np.empty_like(cube)
+        lib.polychord_hip_source_prior(api.dptr(cube), api.dptr(theta), int(cube.size))
+        msg = lib.polychord_hip_last_error()
+        if msg:
+            raise RuntimeError(msg.decode(errors="replace"))
+        return theta
+
+
 class UniformPrior:
     """priors.f90:40-55 uniform box; evaluated on the device when the likelihood is a built-in"""
     symbol = "polychord_hip_uniform_prior"
