@@ -188,7 +188,9 @@ typedef struct {
                            likelihoods launched from a module compiled at run time (pchip_source_create's path, PCHIP_PATH_SOURCE_KERNELS): the same numbers; bit 16 = the
                            one-cluster update as a chain of two launches whose last-arriving workgroups go on with the next stage (pc_update.hip)
                            instead of five launches (flag, index, gather, fold, final): the same rows in the same order and the same groups of
-                           sums, the same bits; slower at the metric configuration, kept as the independent second way the tests compare with */
+                           sums, the same bits; slower at the metric configuration, kept as the independent second way the tests compare with;
+                           bit 17 = a run on its own in pool mode: the update's flags by k_upd_flag in a launch of its own behind the row kernel
+                           instead of by workgroups of the row kernel's launch (k_apply_pool_flag): the same bits */
     const char *resume_write;  /* path of a .resume file (reference grammar, read_write.F90:219-288) rewritten at every
                                   update and at the end; NULL = off */
     int sequential_rng; /* tests: ONE Philox stream consumed in the reference's program order (forces batch = 1 and the

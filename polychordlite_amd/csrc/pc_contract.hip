@@ -13,6 +13,7 @@
 //               two-pass mean / centred SYRK with fixed-order reduction, calc_cholesky (utils.F90:621-649).
 #include "pc_state.h"
 #include "pc_launch.h"
+#include "pc_upd_flag.h"
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
@@ -1351,11 +1352,13 @@ __global__ __launch_bounds__(64 * PC_APPLY_WAVES) void k_apply_dead_ph_many(cons
 // new occupant moves in -- the one place where the order of the two copies matters.
 // (four wavefronts a workgroup, a chain or a slot each: with one wavefront a workgroup the launch was as long as the dispatcher
 //  took to hand 3000 workgroups out -- 192 k of them for sixty-four runs in step, 122 us)
-__device__ __forceinline__ void apply_pool_body(const PcState &S, unsigned batch, int nchains)
+// IDS = false (k_apply_pool_flag): the ids of the chains' rows are written by the flag workgroups of the same launch (pc_upd_flag.h).
+template <bool IDS>
+__device__ __forceinline__ void apply_pool_body(const PcState &S, unsigned batch, int nchains, int wg)
 {
     const PcCtl *ctl = S.ctl;
     const int lane = threadIdx.x & 63, nT = S.nT, nr = S.nr;
-    const int item = (int)blockIdx.x * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
+    const int item = wg * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);      // (wg: the workgroup's number among the row kernel's)
     if (item >= nchains + S.Ncap) return;
     if (item < nchains) {
         const int w = ctl->seg_lo + item;
@@ -1370,6 +1373,7 @@ __device__ __forceinline__ void apply_pool_body(const PcState &S, unsigned batch
                 S.dead_cuid[di] = S.plan[w].dead_cuid; S.dead_entry[di] = S.plan[-src - 1].contour;
             }
         }
+        if (!IDS) return;
         const int base = S.plan[w].ph_base;
         const unsigned cuid = S.plan[w].ph_cuid;
         const double Lg = S.plan[w].contour;
@@ -1405,8 +1409,16 @@ __device__ __forceinline__ void apply_pool_body(const PcState &S, unsigned batch
     // (a lane's copies are in program order, and the slot's records below are its wavefront's alone: no barrier)
     if (lane == 0) { S.slot_src[slot] = -1; S.slot_dead[slot] = -1; if (src >= 0) S.live_entry[slot] = S.plan[src].contour; }
 }
-__global__ __launch_bounds__(256) void k_apply_pool(PcState S, unsigned batch, int nchains) { apply_pool_body(S, batch, nchains); }
-__global__ __launch_bounds__(256) void k_apply_pool_many(const PcManyRec *R, int nchains) { apply_pool_body(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[PC_REC_I_BATCH], nchains); }
+__global__ __launch_bounds__(256) void k_apply_pool(PcState S, unsigned batch, int nchains) { apply_pool_body<true>(S, batch, nchains, (int)blockIdx.x); }
+__global__ __launch_bounds__(256) void k_apply_pool_many(const PcManyRec *R, int nchains) { apply_pool_body<true>(pc_many_state(R, blockIdx.y), (unsigned)R[blockIdx.y].ia[PC_REC_I_BATCH], nchains, (int)blockIdx.x); }
+// the row kernel and the update's flag pass in one launch: workgroups [0, nb_flag) take four blocks of 256 phantom rows each, like k_upd_flag's
+// (in front: theirs is the longer chain of dependent loads when an update is pending), the ones behind them are k_apply_pool's.  Nobody waits
+// for anybody: what the flag pass needs of this round's rows it forms itself.
+__global__ __launch_bounds__(256) void k_apply_pool_flag(PcState S, unsigned batch, int nchains, int nb_flag, int nph, unsigned char *keep, int *blk, int nblk)
+{
+    if ((int)blockIdx.x >= nb_flag) { apply_pool_body<false>(S, batch, nchains, (int)blockIdx.x - nb_flag); return; }
+    upd_flag_body<true>(S, nph, keep, blk, 1, nblk, (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), batch);
+}
 
 
 // new live rows: every slot now owned by a chain's last baby
@@ -2099,6 +2111,12 @@ extern "C" void pc_launch_apply(const PcState *S, unsigned batch, int nchains, h
     if (S->pool) { hipLaunchKernelGGL(k_apply_pool, dim3((nchains + S->Ncap + 3) / 4), dim3(256), 0, st, *S, batch, nchains); return; }
     hipLaunchKernelGGL(k_apply_dead_ph, dim3(nchains), dim3(64 * PC_APPLY_WAVES), 0, st, *S, batch);
     hipLaunchKernelGGL(k_apply_live, dim3(S->Ncap), dim3(64), 0, st, *S);
+}
+
+extern "C" void pc_launch_apply_flag(const PcState *S, unsigned batch, int nchains, int nph, unsigned char *keep, int *blk, hipStream_t st)
+{
+    const int nb_apply = (nchains + S->Ncap + 3) / 4, nblk = (nph + UPD_ROWS - 1) / UPD_ROWS, nb_flag = (nblk + 3) / 4;
+    hipLaunchKernelGGL(k_apply_pool_flag, dim3(nb_flag + nb_apply), dim3(256), 0, st, *S, batch, nchains, nb_flag, nph, keep, blk, nblk);
 }
 
 extern "C" int pc_launch_apply_many(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st)

@@ -401,6 +401,9 @@ struct Engine {
     RawSlot ring[RAW_RING];
     int raw_depth = 2;
     double *h_dead = nullptr; size_t h_dead_cap = 0, h_dead_copied = 0;
+    // a run on its own in pool mode: the row kernel's launch carries the update's flag pass (settings.ablate bit 17: not).  What the round in
+    // flight was launched with, for do_update:
+    bool r_flagged = false; int r_flag_nph = 0; unsigned char *r_flag_keep = nullptr; int *r_flag_blk = nullptr;
     PcCtl *h_ctl = nullptr;       // pinned mirror
     PcCtl *h_note = nullptr;      // pinned, device-visible: the contraction kernels publish the control block here (pc_publish_ctl)
     unsigned note_seq = 0;
@@ -1105,7 +1108,12 @@ struct Engine {
                 HIPCHK(hipStreamSynchronize(st));
             }
             hipEvent_t e0 = kt.begin(KT_CLEAN);
+            // (the flags of these rows came with the round's row kernel: round_enqueue)
+            if (!co && deferred && r_flagged && r_flag_nph == nph && r_flag_keep == keep && r_flag_blk == blk)
+                pc_launch_update_fused_at(&S, nph, keep, blk, d_total, ph2, phL2, phC2, phU2, upd_part, upd_shift, 1, 1, st);
+            else
             (void)stage(rec_update(S, keep, blk, d_total, ph2, phL2, phC2, phU2, upd_part, upd_shift, co ? pc_update_fused_grid(&S, nph, deferred ? 1 : 0) : 0, deferred, nph));
+            r_flagged = false;
             kt.end(KT_CLEAN, e0);
             if (upd.need_count) {
                 // (in step with other runs the update was only written down: the copy of its count comes behind its launch)
@@ -1627,6 +1635,7 @@ struct Engine {
         r_nursery_left = 0;
         make_plan();
         S.defer_update = plan.defer ? 1 : 0; S.pool = plan.pool ? 1 : 0;
+        r_flagged = false;
         if (S.pool) {
             pool_cursor = h_ctl->nphantom;
             if (g_cap_phantoms.load() <= 0) {                                    // room for several updates between compactions,
@@ -1888,6 +1897,14 @@ struct Engine {
             if (rc2) { std::fprintf(stderr, "polychord_hip: nlive too large for the LDS-resident contraction\n"); r_rc = 4; return false; }
             kt.end(KT_CONSUME, e2);
             hipEvent_t e3 = kt.begin(KT_APPLY);
+            // a run on its own in pool mode whose updates are deferred and fused: the flag pass of an update that this contraction may leave pending
+            // rides in the row kernel's launch (the device knows by then, the host does not yet); do_update starts behind it
+            r_flagged = !co && S.pool && S.defer_update && plan.fused_update && ch.kind == PC_CONTRACT_PAR && pool_cursor >= 1 && keep && blk &&
+                        !(S.ablate & (PC_ABL_FLAG_LAUNCH | PC_ABL_UPDATE_CHAIN));
+            if (r_flagged) {
+                r_flag_nph = (int)pool_cursor; r_flag_keep = keep; r_flag_blk = blk;
+                pc_launch_apply_flag(&S, batch - 1, B, r_flag_nph, keep, blk, st);
+            } else
             (void)stage(rec_apply(S, batch - 1, B));
             kt.end(KT_APPLY, e3);
             // the main stream's wait for the next nursery's bases is enqueued now, behind this round's kernels (long

@@ -70,6 +70,9 @@ void pc_launch_nn_lists(const PcState *S, int nleft, int use_rank, hipStream_t s
 int pc_launch_nn_lists_many(const PcState *S, const PcManyRec *dR, int R, int nleft_max, int use_rank, hipStream_t st);
 int pc_launch_consume(const PcState *S, int final_mode, int wide, hipStream_t st);
 void pc_launch_apply(const PcState *S, unsigned batch, int nchains, hipStream_t st);
+// pool mode, a run on its own, deferred update: the row kernel and, in the same launch, the workgroups of the update's flag pass over nph rows
+// (pc_upd_flag.h: keep [nph], blk [blocks of 256]), which also write the ids of the rows of the chains just consumed
+void pc_launch_apply_flag(const PcState *S, unsigned batch, int nchains, int nph, unsigned char *keep, int *blk, hipStream_t st);
 int pc_launch_apply_many(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st);
 // ... for R runs at once: every run its own row count (PcManyRec::ia[PC_REC_I_ROWS], blocks PC_REC_I_BLOCKS)
 int pc_launch_clean_many(const PcManyRec *dR, int R, int nblk_max, hipStream_t st);
@@ -198,6 +201,9 @@ int pc_update_fused_entries(const PcState *S);
 #define PC_UPD_CTR_INTS 2048
 void pc_launch_update_fused(const PcState *S, int nph, unsigned char *keep, int *blk, int *d_total, double *ph2, double *phL2, unsigned *phC2,
                             unsigned long long *phU2, double *part, double *shift, int deferred, hipStream_t st);
+// ... flagged: keep and blk were made for these nph rows by pc_launch_apply_flag in front (pool mode, deferred, not the chain): no k_upd_flag
+void pc_launch_update_fused_at(const PcState *S, int nph, unsigned char *keep, int *blk, int *d_total, double *ph2, double *phL2, unsigned *phC2,
+                               unsigned long long *phU2, double *part, double *shift, int deferred, int flagged, hipStream_t st);
 int pc_update_fused_grid(const PcState *S, int nph, int deferred);
 // ... for R runs, all of them the same number G of gathering workgroups (pc_update_fused_grid) and nblk_max >= their blocks.
 // 1: not this way (the caller launches them one by one)

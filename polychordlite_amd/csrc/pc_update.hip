@@ -32,12 +32,11 @@
 //  coordinate from the mean -- 5 u at half a standard deviation, a digit from about 1.5 on, three digits at thirty)
 #include "pc_state.h"
 #include "pc_launch.h"
+#include "pc_upd_flag.h"
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
-#define UPD_ROWS 256
-#define UPD_NT 256
 
 // the wave's rows selected by `mask` (row of bit b = src0 + b*nT), in order: optionally copied to consecutive rows at dst;
 // of those also in `mmask`, the first D elements minus the shift (and a one) go to consecutive tile rows, in order;
@@ -74,63 +73,9 @@ __device__ __forceinline__ void upd_stage_masked(const double *src0, unsigned lo
     }
 }
 
-// def (here and below): the update is made AFTER the launch of the parallel contraction that passed its trigger, for the
-// state at the mark the launch recorded (PcCtl::upd_*): the threshold of the clean is the logL of the death at the mark;
-// the moments leave out what came after it -- phantoms of later chains, live points accepted later -- and take in the
-// points that were alive then and have died since (their rows are in the dead array)
-// (a wavefront takes one block of the counts -- 256 rows, four consecutive rows per lane: 32-byte, 16-byte and 4-byte accesses in
-//  place of 8, 4 and 1 -- and a workgroup four of them; the survivors of a block are counted by ballots, no LDS)
-// a value another workgroup of the SAME launch reads behind a ticket (upd_ticket_last): stored write-through at agent scope, so that the
-// ticket needs no release fence (a release writes back the whole L2 of the XCD -- with the sampling kernel's rows still dirty there)
-template <typename T> __device__ __forceinline__ void upd_store_wt(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void upd_flag_body(const PcState &S, int nph, unsigned char *keep, int *blk_count, int def, int nblk)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int sb = blockIdx.x * 4 + wv;
-    if (sb >= nblk) return;
-    const unsigned uid0 = S.cl_uid[0];
-    const double thr = def ? S.ctl->upd_thr : S.death_thr[0];
-    const bool pool = S.pool;
-    // pool mode: a dropped phantom is dropped where it lies; the rows that count in the moments (the survivors that were
-    // phantoms at the mark -- rows of chains consumed later stay, but do not count) are listed by k_upd_index
-    const int tmark = (pool && def) ? S.ctl->upd_tmark : 0x7fffffff, nph0u = (pool && def) ? S.ctl->upd_nph0 : 0x7fffffff;
-    const int T = (pool && def) ? S.ctl->upd_T : 0, nr = S.nr;
-    const int j0 = sb * UPD_ROWS + 4 * lane;
-    const bool full = j0 + 3 < nph;
-    unsigned cu[4] = {PC_CUID_NONE, PC_CUID_NONE, PC_CUID_NONE, PC_CUID_NONE};
-    double ll[4] = {0.0, 0.0, 0.0, 0.0};
-    if (full) {
-        const uint4 c = *(const uint4 *)(S.ph_cuid + j0);
-        const double2 a = *(const double2 *)(S.ph_logL + j0), b2 = *(const double2 *)(S.ph_logL + j0 + 2);
-        cu[0] = c.x; cu[1] = c.y; cu[2] = c.z; cu[3] = c.w; ll[0] = a.x; ll[1] = a.y; ll[2] = b2.x; ll[3] = b2.y;
-    } else {
-        for (int u = 0; u < 4; ++u) if (j0 + u < nph) { cu[u] = S.ph_cuid[j0 + u]; ll[u] = S.ph_logL[j0 + u]; }
-    }
-    unsigned kb = 0; bool wr = false; int cnt = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int j = j0 + u;
-        bool k = false, km = false;
-        if (j < nph) {
-            k = (cu[u] == uid0) && !(ll[u] < thr);
-            if (pool) {
-                if (!k && cu[u] == uid0) { cu[u] = PC_CUID_NONE; wr = true; }
-                km = k && (j < nph0u || T - 1 - (j - nph0u) / nr < tmark);
-            }
-            kb |= (unsigned)((k ? 1 : 0) | (km ? 2 : 0)) << (8 * u);
-        }
-        cnt += __popcll(__ballot(pool ? km : k));
-    }
-    if (full) {
-        *(unsigned *)(keep + j0) = kb;
-        if (wr) *(uint4 *)(S.ph_cuid + j0) = make_uint4(cu[0], cu[1], cu[2], cu[3]);
-    } else {
-        for (int u = 0; u < 4; ++u) if (j0 + u < nph) { keep[j0 + u] = (unsigned char)((kb >> (8 * u)) & 0xFFu); if (wr) S.ph_cuid[j0 + u] = cu[u]; }
-    }
-    if (lane == 0) upd_store_wt(blk_count + sb, cnt);        // (write-through: the chain's last arriver reads it in this launch)
-}
-__global__ __launch_bounds__(UPD_NT) void k_upd_flag(PcState S, int nph, unsigned char *keep, int *blk_count, int def, int nblk) { upd_flag_body(S, nph, keep, blk_count, def, nblk); }
-__global__ __launch_bounds__(UPD_NT) void k_upd_flag_many(const PcManyRec *R, int def) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x * 4 >= r.ia[PC_REC_I_BLOCKS]) return; upd_flag_body(r.S, r.ia[PC_REC_I_ROWS], (unsigned char *)r.p[PC_REC_KEEP], (int *)r.p[PC_REC_BLK], def, r.ia[PC_REC_I_BLOCKS]); }
+// the flag pass itself (upd_flag_body, upd_store_wt): pc_upd_flag.h -- the row kernel of a run on its own carries it too
+__global__ __launch_bounds__(UPD_NT) void k_upd_flag(PcState S, int nph, unsigned char *keep, int *blk_count, int def, int nblk) { upd_flag_body<false>(S, nph, keep, blk_count, def, nblk, (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)); }
+__global__ __launch_bounds__(UPD_NT) void k_upd_flag_many(const PcManyRec *R, int def) { const PcManyView r = pc_many_view(R, blockIdx.y); if ((int)blockIdx.x * 4 >= r.ia[PC_REC_I_BLOCKS]) return; upd_flag_body<false>(r.S, r.ia[PC_REC_I_ROWS], (unsigned char *)r.p[PC_REC_KEEP], (int *)r.p[PC_REC_BLK], def, r.ia[PC_REC_I_BLOCKS], (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // tickets: what lets one launch do the work of several without any workgroup waiting for another.  A workgroup that has written
@@ -165,7 +110,7 @@ __device__ __forceinline__ bool upd_ticket_last(int *ctr, int n, int *last_s)
 __global__ __launch_bounds__(UPD_NT) void k_upd_flag_scan(PcState S, int nph, unsigned char *keep, int *blk, int def, int nblk, int *ctr)
 {
     __shared__ int last_s, wsum[4];
-    upd_flag_body(S, nph, keep, blk, def, nblk);
+    upd_flag_body<false>(S, nph, keep, blk, def, nblk, (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
     if (!upd_ticket_last(ctr + UPD_TICKET_FLAG, (int)gridDim.x, &last_s)) return;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i0 = 16 * tid;
     int c[16], s = 0;
@@ -778,6 +723,13 @@ extern "C" int pc_update_fused_entries(const PcState *S) { const int e = S->D * 
 extern "C" void pc_launch_update_fused(const PcState *S, int nph, unsigned char *keep, int *blk, int *d_total, double *ph2, double *phL2,
                                        unsigned *phC2, unsigned long long *phU2, double *part, double *shift, int deferred, hipStream_t st)
 {
+    pc_launch_update_fused_at(S, nph, keep, blk, d_total, ph2, phL2, phC2, phU2, part, shift, deferred, 0, st);
+}
+// flagged: keep and blk were made for these nph rows by the row kernel's launch in front (pc_launch_apply_flag: pool mode, deferred, not the
+// chain), and the update starts at k_upd_index_self
+extern "C" void pc_launch_update_fused_at(const PcState *S, int nph, unsigned char *keep, int *blk, int *d_total, double *ph2, double *phL2,
+                                          unsigned *phC2, unsigned long long *phU2, double *part, double *shift, int deferred, int flagged, hipStream_t st)
+{
     const int D = S->D, nblk = (nph + UPD_ROWS - 1) / UPD_ROWS, nlb = (S->Ncap + UPD_ROWS - 1) / UPD_ROWS, E = pc_update_fused_entries(S);
     const int ndb = deferred ? (S->B + UPD_ROWS - 1) / UPD_ROWS : 0;
     const int NTv = (D + 1 + 15) / 16, TSv = NTv <= 2 ? 16 * NTv + 1 : 16 * NTv + ((NTv & 1) ? 0 : 16), CAPv = NTv <= 2 ? 128 : 64;
@@ -799,7 +751,7 @@ extern "C" void pc_launch_update_fused(const PcState *S, int nph, unsigned char 
 #undef UPDC_LAUNCH
         if (D < 32) return;
     } else {
-        hipLaunchKernelGGL(k_upd_flag, dim3((nblk + 3) / 4), dim3(UPD_NT), 0, st, *S, nph, keep, blk, deferred, nblk);
+        if (!(flagged && S->pool && deferred)) hipLaunchKernelGGL(k_upd_flag, dim3((nblk + 3) / 4), dim3(UPD_NT), 0, st, *S, nph, keep, blk, deferred, nblk);
         if (!S->pool) pc_launch_scan_blocks(blk, nblk, d_total, &S->ctl->nphantom, st);
         else if (nblk <= UPD_SELF_BLOCKS && !std::getenv("PC_UPD_SCAN_LAUNCH"))
             hipLaunchKernelGGL(k_upd_index_self, dim3((nblk + 15) / 16), dim3(UPD_IDX_NT), 0, st, nph, (const unsigned char *)keep, (const int *)blk, nblk, (int *)phC2, d_total);

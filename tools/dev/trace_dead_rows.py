@@ -34,7 +34,8 @@ for cs, ce, _ in big:
     for n in ov: beside[n] = beside.get(n, 0) + 1
 out["d2h_over_40us"] = {"n": len(big), "us": stat([us(ce - cs) for cs, ce, *_ in big]), "copies_that_overlap_a_launch_of": beside, "each": rows}
 # the update's span: its first kernel's start to the next k_slice's start, with and without a big copy inside
-upd_first = [s for s, e, n in K if n.startswith("k_upd_flag")]
+# (an update starts at k_upd_flag, or at k_upd_index_self where the flags came with the row kernel's launch: k_apply_pool_flag)
+upd_first = [s for i, (s, e, n) in enumerate(K) if n.startswith("k_upd_flag") or (n.startswith("k_upd_index_self") and not (i and K[i - 1][2].startswith("k_upd_flag")))]
 spans = {"copy_beside": [], "no_copy": []}
 for u in upd_first:
     nxt = next((s for s, e in sl if s > u), None)
@@ -47,6 +48,14 @@ for u in upd_first:
     nx = next(((s, e) for s, e in sl if s > u), None)
     if nx: ks["copy_beside" if any(cs < nx[1] and ce > nx[0] for cs, ce, *_ in big) else "no_copy"].append(us(nx[1] - nx[0]))
 out["k_slice_behind_an_update_us"] = {k: stat(v) for k, v in ks.items()}
+# the row kernel (with or without the flag pass in its launch), and the update: launches from its first kernel up to the next k_slice
+out["row_kernel_us"] = {nm: stat([us(e - s) for s, e, n in K if n == nm]) for nm in sorted({n for s, e, n in K if n.startswith("k_apply_pool")})}
+per_upd = []
+for u in upd_first:
+    nxt = next((s for s, e in sl if s > u), None)
+    if nxt is not None: per_upd.append(sum(1 for s, e, n in K if u <= s < nxt))
+out["launches_per_update"] = stat(per_upd)
+out["d2h_over_40us_not_behind_a_killoff"] = sum(1 for cs, ce, _ in big if not any(fs <= cs < fs + 500000 for fs, fe, n in K if n.startswith("k_final_par")))
 for name in ("k_final_par", "k_final_par_whole", "k_final_rows"):
     out[name + "_us"] = stat([us(e - s) for s, e, n in K if n == name])
 # the tail: the kill-off's start to the end of the last copy of the chain of copies to the host behind it (rows, weights, birth contours: 8 us
