@@ -588,6 +588,22 @@ const char *pchip_comm_library(void);   /* the RCCL that was resolved (path or s
 int  pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior,
                         unsigned batch, int nchains, const double *seeds, const double *chol,
                         double contour, double *babies_out, double *nhats_out, int *nlike_out);
+/* kernel-level: the directions alone (Gaussian deviates, Gram-Schmidt, whitening with the Cholesky factor) by the launcher a run takes --
+ * accuracy tests against a long double reference (tests/test_directions.py).  Set up as pchip_slice_chains: one cluster, chain c seeded
+ * from seeds[c] (a row of nTotal doubles), chol [nDims][nDims] for all chains; no slice is sampled.
+ * path 0 = the whole kernels (what pchip_slice_chains launches); path 1 = the split launch of a run on its own, bases first, then seeds and
+ * whitening; path 2 = path 1 with the packed bases (one grade, nDims 2 ... 24).  A path that the state does not have (a shape that does
+ * not split, nDims > 256) returns PCHIP_NO_SUCH_PATH and launches nothing.
+ * Out (host memory): nhat [nchains][num_repeats][nDims] in generation order (not shuffled), nhat_w [nchains][num_repeats]; where the run
+ * would form them (correlated Gaussian, 64 < nDims <= 128: *has_Ms = 1) nhat_Ms [nchains][num_repeats][nDims] and ch_My [nchains][nDims]
+ * (either may be NULL); on paths 1 and 2 raw [nchains][bases][nDims][nDims], the orthonormal bases before whitening, basis after basis
+ * over all grades, vector after vector (of a grade that starts at parameter `off`, nDims - off vectors are written).  nrows, nbases: the
+ * directions per chain and the bases per chain that the caller's arrays were sized for; if the settings give other numbers: 1.
+ * 0, 1 (bad arguments, message in polychord_hip_last_error()), PCHIP_NO_SUCH_PATH, else a pchip_run code. */
+#define PCHIP_NO_SUCH_PATH 64
+int  pchip_directions(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, unsigned batch, int nchains,
+                      const double *seeds, const double *chol, int path, double *nhat_out, double *nhat_w_out,
+                      double *nhat_Ms_out, double *ch_My_out, int *has_Ms, double *raw_out, int nrows, int nbases);
 /* kernel-level: the DEVICE transform of a prior table (prior->kind == PCHIP_PRIOR_TABLE) at n hypercube points, cube [n][nDims] in,
  * theta [n][nDims] out (host memory) -- parity tests against polychord_hip_table_prior.  0, 1 (a bad table, message in
  * polychord_hip_last_error()), 2 (no device), 3 (nDims > 256). */

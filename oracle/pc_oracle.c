@@ -946,11 +946,15 @@ static void calculate_point(rti_t *R, double *pt, long *nlike)
 }
 
 /* ---- directions ------------------------------------------------------------ */
-static void generate_nhats(rti_t *R, uint32_t batch, uint32_t chain, double *nh /* [nr][D] */, int *speeds /* [nr] grade of each */)
+/* dev_out (or NULL): the Gaussian deviates in drawing order (of a vector that was drawn again, the last draw), cap doubles at most;
+ * *ndev (or NULL): how many were drawn; raw_out (or NULL): [nr][D], the directions before the shuffle */
+static void generate_nhats_ex(rti_t *R, uint32_t batch, uint32_t chain, double *nh /* [nr][D] */, int *speeds /* [nr] grade of each */,
+                              double *dev_out, long cap, long *ndev, double *raw_out)
 {   /* chordal_sampling.f90:94-145 (single grade) + random_utils.F90:381-437, 276-298, 505-532 */
     int D = R->D, nr = R->s->num_repeats;
     double *basis = (double *)malloc(sizeof(double) * (size_t)D * D);
     double *raw = (double *)calloc((size_t)nr * D, sizeof(double));
+    long nd = 0;
     uint32_t e = 0;                 /* running index inside the (batch, chain) stream of PC_DOM_NHAT */
     int col0 = 0;
     for (int g = 0; g < R->ngrade; ++g) {
@@ -967,9 +971,11 @@ static void generate_nhats(rti_t *R, uint32_t batch, uint32_t chain, double *nh 
                         n2 += v[d] * v[d];
                     }
                 } while (n2 <= 0.0);
+                if (dev_out && nd + Dg <= cap) memcpy(dev_out + nd, v, sizeof(double) * Dg);
+                nd += Dg;
                 double nrm = sqrt(n2);
                 for (int d = 0; d < Dg; ++d) v[d] = v[d] / nrm;
-                for (int j = 0; j < i; ++j) {   /* Gram-Schmidt against the finished vectors, in order */
+                for (int j = 0; j < (nh || raw_out ? i : 0); ++j) {   /* Gram-Schmidt against the finished vectors, in order (nobody wants the directions: the deviates alone) */
                     const double *q = basis + (size_t)j * Dg;
                     double dot = 0.0;
                     for (int d = 0; d < Dg; ++d) dot += v[d] * q[d];
@@ -998,11 +1004,17 @@ static void generate_nhats(rti_t *R, uint32_t batch, uint32_t chain, double *nh 
         if (j > i) j = i;
         int t = deck[i]; deck[i] = deck[j]; deck[j] = t;   /* deck(2:)(i) <-> deck(2:)(j) */
     }
-    for (int i = 0; i < nr; ++i) {
+    for (int i = 0; nh && i < nr; ++i) {
         memcpy(nh + (size_t)i * D, raw + (size_t)deck[i] * D, sizeof(double) * D);
         if (speeds) { int g = 0, c = R->g_nr[0]; while (deck[i] >= c) c += R->g_nr[++g]; speeds[i] = g; }
     }
+    if (raw_out) memcpy(raw_out, raw, sizeof(double) * (size_t)nr * D);
+    if (ndev) *ndev = nd;
     free(basis); free(raw); free(deck);
+}
+static void generate_nhats(rti_t *R, uint32_t batch, uint32_t chain, double *nh, int *speeds)
+{
+    generate_nhats_ex(R, batch, chain, nh, speeds, NULL, 0, NULL, NULL);
 }
 
 static void slice_sample(rti_t *R, uint32_t batch, uint32_t chain, int islice, double logLb,
@@ -1129,6 +1141,22 @@ long pc_slice_chain(const pc_settings *s, const pc_like *like, const pc_prior *p
     *rng = R.rng;
     cluster_free(&R.cl[0]); free(R.cl); free(R.XpXq);
     return n;
+}
+
+long pc_direction_inputs(const pc_settings *s, uint32_t key_seed, uint32_t batch, uint32_t chain, double *deviates, long cap, double *raw)
+{
+    rti_t R;
+    pc_like like; pc_prior prior;
+    memset(&like, 0, sizeof(like)); memset(&prior, 0, sizeof(prior));
+    rti_setup(&R, s, &like, &prior);
+    R.rng.key[0] = key_seed; R.rng.key[1] = 0x504F4C59u; R.rng.sequential = 0;
+    const int nr = R.s->num_repeats;
+    double *nh = raw ? (double *)malloc(sizeof(double) * (size_t)nr * R.D) : NULL;
+    long nd = 0;
+    generate_nhats_ex(&R, batch, chain, nh, NULL, deviates, cap, &nd, raw);
+    free(nh);
+    cluster_free(&R.cl[0]); free(R.cl); free(R.XpXq);
+    return nd;
 }
 
 void pc_settings_default(pc_settings *s, int nDims, int nDerived)

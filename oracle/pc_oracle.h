@@ -146,6 +146,11 @@ void pc_result_free(pc_result *r);
 long pc_slice_chain(const pc_settings *s, const pc_like *like, const pc_prior *prior, pc_rng *rng,
                     uint32_t batch, uint32_t chain, const double *seed_point, const double *chol,
                     double logL, double *babies /* [num_repeats][nTotal] */, double *nhats_out /* [nr][D] or NULL */);
+/* What generate_nhats draws and makes for chain (batch, chain) of key `key_seed` in keyed mode (chordal_sampling.f90:94-145,
+ * random_utils.F90:381-437): the Gaussian deviates in drawing order -- grade after grade, basis after basis, vector after vector, of a grade
+ * that starts at parameter off nDims - off per vector -- into deviates (at most cap doubles; NULL: none), and the directions before
+ * whitening and before the shuffle into raw [num_repeats][nDims] (NULL: not wanted, and no Gram-Schmidt is done).  Returns the number of deviates drawn. */
+long pc_direction_inputs(const pc_settings *s, uint32_t key_seed, uint32_t batch, uint32_t chain, double *deviates, long cap, double *raw);
 
 #ifdef __cplusplus
 }

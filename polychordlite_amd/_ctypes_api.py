@@ -114,6 +114,10 @@ def load():
                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.pchip_slice_chains.restype = C.c_int
+    lib.pchip_directions.argtypes = [C.POINTER(Settings), C.POINTER(Like), C.POINTER(Prior), C.c_uint, C.c_int, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.c_int]
+    lib.pchip_directions.restype = C.c_int
     lib.polychord_hip_set_gaussian.argtypes = [C.c_double, C.c_double]
     lib.polychord_hip_set_uniform_prior.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.polychord_hip_set_corr_gaussian.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double]
@@ -329,6 +333,40 @@ def update_factors(live, live_cluster, phantom, ph_logL, ph_cluster, threshold, 
         msg = lib.polychord_hip_last_error()
         raise RuntimeError(f"pchip_update_factors failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
     return dict(cov=cov, chol=chol, count=count, shift=sho, chol_suspect=sus.value)
+
+
+NO_SUCH_PATH = 64      # PCHIP_NO_SUCH_PATH
+
+
+def directions(settings, like, prior, batch, seeds, chol, path):
+    """pchip_directions: the directions of `len(seeds)` chains by the launcher a run takes (path 0: the whole kernels, 1: the split launch,
+    2: the split launch with the packed bases); seeds [nchains][nTotal], chol [nDims][nDims].  None where the state has no such path.
+    dict: nhat [nchains][nr][D] (generation order), nhat_w [nchains][nr], nhat_Ms / ch_My (None unless the run forms them), raw
+    [nchains][bases][D][D] (paths 1 and 2: the orthonormal bases before whitening; NaN where nothing was copied)"""
+    lib = load()
+    D = settings.nDims
+    sd = np.ascontiguousarray(np.atleast_2d(seeds), dtype=np.float64)
+    ch = np.ascontiguousarray(chol, dtype=np.float64)
+    assert ch.shape == (D, D) and sd.shape[1] == 2 * D + settings.nDerived + 2
+    nch = sd.shape[0]
+    if settings.nGrade > 1:
+        off = np.concatenate([[0], np.cumsum([settings.grade_dims[g] for g in range(settings.nGrade)])[:-1]])
+        reps = [settings.grade_repeats[g] for g in range(settings.nGrade)]
+    else:
+        off, reps = [0], [settings.num_repeats]
+    nr = int(sum(reps))
+    nb = int(sum(-(-r // (D - o)) for r, o in zip(reps, off)))
+    nhat = np.full((nch, nr, D), np.nan); w = np.full((nch, nr), np.nan)
+    Ms = np.full((nch, nr, D), np.nan); My = np.full((nch, D), np.nan); raw = np.full((nch, nb, D, D), np.nan)
+    has = C.c_int(0)
+    rc = lib.pchip_directions(C.byref(settings), C.byref(like), C.byref(prior), batch, nch, dptr(sd), dptr(ch), path, dptr(nhat), dptr(w),
+                              dptr(Ms), dptr(My), C.byref(has), dptr(raw), nr, nb)
+    if rc == NO_SUCH_PATH:
+        return None
+    if rc != 0:
+        msg = lib.polychord_hip_last_error()
+        raise RuntimeError(f"pchip_directions failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
+    return dict(nhat=nhat, nhat_w=w, nhat_Ms=Ms if has.value else None, ch_My=My if has.value else None, raw=raw if path else None)
 
 
 def maximum_dict(m, nDims, nDerived):

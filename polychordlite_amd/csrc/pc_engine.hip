@@ -2316,6 +2316,92 @@ int pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const pc
     return rc;
 }
 
+// kernel-level entry for the accuracy tests of the directions (tests/test_directions.py): K0 alone, set up as pchip_slice_chains sets it
+// up (one cluster, chain c seeded from row c, the caller's Cholesky factor), by the launcher a run would take:
+//   path 0: pc_launch_nhats, the whole kernels (what pchip_slice_chains launches);
+//   path 1: pc_launch_nhats_part(1) then (2) on the run's own nhat_raw, as Engine::enqueue_nursery does where pc_nhats_splittable holds;
+//   path 2: the same with packed = 1 -- the bases of pc_slice_t.hip (pc_bases_t_ok).
+// A path the state does not have: PCHIP_NO_SUCH_PATH, nothing launched.  raw_out (paths 1 and 2): the orthonormal bases part 1 left in
+// nhat_raw, brought from the layout of the kernel that wrote them to [chain][basis][vector][coordinate]; vectors no kernel wrote keep
+// whatever the block held.  k_slice is not run.
+int pchip_directions(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, unsigned batch, int nchains,
+                     const double *seeds, const double *chol, int path, double *nhat_out, double *nhat_w_out,
+                     double *nhat_Ms_out, double *ch_My_out, int *has_Ms, double *raw_out, int nrows, int nbases)
+{
+    if (!s || !like || !prior || nchains < 1 || !seeds || !chol || path < 0 || path > 2 || !nhat_out || !nhat_w_out || (path != 0 && !raw_out)) {
+        pc_abi_set_last_error("pchip_directions: settings, likelihood, prior, nchains >= 1 seed rows, a Cholesky factor, path 0, 1 or 2, arrays for nhat and nhat_w (and for the raw bases on paths 1 and 2)");
+        return 1;
+    }
+    if (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & PC_ABL_RTC_BUILTINS)) {
+        pc_abi_set_last_error("pchip_directions does not take a device source likelihood (or settings.ablate bit 15)");
+        return 1;
+    }
+    if (s->nDims > 256) return PCHIP_NO_SUCH_PATH;
+    pchip_settings c = *s;
+    c.nlive = nchains; c.nprior = nchains; c.batch = nchains; c.do_clustering = 0;
+    Engine E;
+    int rc = 0;
+    try {
+        E.setup(c, *like, *prior);
+        PcState &S = E.S;
+        const int nT = S.nT, D = S.D, nr = S.nr, nb = S.nb_total;
+        if (nrows != nr || nbases != nb) {
+            pc_abi_set_last_error("pchip_directions: the caller's arrays are for another number of directions or bases than the settings give");
+            rc = 1;
+        } else if ((path != 0 && !pc_nhats_splittable(&S)) || (path == 2 && !pc_bases_t_ok(&S))) rc = PCHIP_NO_SUCH_PATH;
+        if (has_Ms) *has_Ms = S.nhat_Ms != nullptr ? 1 : 0;
+        if (rc == 0) {
+            HIPCHK(hipMemcpy(S.live, seeds, sizeof(double) * (size_t)nchains * nT, hipMemcpyHostToDevice));
+            std::vector<double> ll(nchains); std::vector<int> idn(nchains), zero(nchains, 0);
+            for (int i = 0; i < nchains; ++i) { ll[i] = seeds[(size_t)i * nT + S.l0]; idn[i] = i; }
+            const double contour = *std::min_element(ll.begin(), ll.end());
+            HIPCHK(hipMemcpy(S.live_logL, ll.data(), sizeof(double) * nchains, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.live_cluster, zero.data(), sizeof(int) * nchains, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.live_pos, idn.data(), sizeof(int) * nchains, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.cl_list, idn.data(), sizeof(int) * nchains, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.cl_n, &nchains, sizeof(int), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.logLp, &contour, sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(S.chol, chol, sizeof(double) * D * D, hipMemcpyHostToDevice));
+            S.seed_override = 1;
+            if (path == 0) rc = pc_launch_nhats(&S, batch, nchains, E.st) ? PCHIP_NO_SUCH_PATH : 0;
+            else rc = (pc_launch_nhats_part(&S, batch, nchains, 1, E.st, path == 2 ? 1 : 0) || pc_launch_nhats_part(&S, batch, nchains, 2, E.st, 0)) ? PCHIP_NO_SUCH_PATH : 0;
+            HIPCHK(hipStreamSynchronize(E.st));
+            HIPCHK(hipGetLastError());
+        }
+        if (rc == 0) {
+            HIPCHK(hipMemcpy(nhat_out, S.nhat, sizeof(double) * (size_t)nchains * nr * D, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(nhat_w_out, S.nhat_w, sizeof(double) * (size_t)nchains * nr, hipMemcpyDeviceToHost));
+            if (S.nhat_Ms && nhat_Ms_out) HIPCHK(hipMemcpy(nhat_Ms_out, S.nhat_Ms, sizeof(double) * (size_t)nchains * nr * D, hipMemcpyDeviceToHost));
+            if (S.ch_My && ch_My_out) HIPCHK(hipMemcpy(ch_My_out, S.ch_My, sizeof(double) * (size_t)nchains * D, hipMemcpyDeviceToHost));
+        }
+        if (rc == 0 && path != 0) {
+            // a basis block as its kernel laid it out: k_nhats<., 64, 1> and the packed bases vector-major, D doubles a vector; k_nhats_q<8 | 16, 1>
+            // thread by thread, i.e. vector-major with rows of 32 | 64; k_basis in k_whiten's pair layout, 32 x 512 doubles
+            const size_t blk = D <= 24 ? (size_t)D * D : D <= 32 ? (size_t)1024 : D <= 64 ? (size_t)4096 : (size_t)32 * 512;
+            std::vector<double> raw((size_t)nchains * nb * blk);
+            HIPCHK(hipMemcpy(raw.data(), S.nhat_raw, sizeof(double) * raw.size(), hipMemcpyDeviceToHost));
+            for (size_t cb = 0; cb < (size_t)nchains * nb; ++cb) {
+                const double *in = raw.data() + cb * blk;
+                double *out = raw_out + cb * (size_t)D * D;
+                for (int v = 0; v < D; ++v)
+                    for (int d = 0; d < D; ++d) {
+                        size_t at;
+                        if (D <= 24) at = (size_t)v * D + d;
+                        else if (D <= 64) at = (size_t)v * (D <= 32 ? 32 : 64) + d;
+                        else { const int n = 2 * (d >> 3) + (d & 1), lk = (d & 7) >> 1; at = (size_t)n * 512 + 64 * (v >> 4) + 16 * lk + (v & 15); }
+                        out[(size_t)v * D + d] = in[at];
+                    }
+            }
+        }
+    } catch (const EngineError &e) {
+        std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str());
+        (void)hipGetLastError();
+        rc = e.code;
+    }
+    E.destroy();
+    return rc;
+}
+
 // kernel-level entry for the parity tests: the device transform of a prior table at n hypercube points
 int pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const double *cube, double *theta, int device)
 {

@@ -1423,11 +1423,19 @@ __global__ __launch_bounds__(PC_BIG_NT) void k_nhats_big(PcState S, unsigned bat
         }
     }
     if (active) {
-        double n0 = 0.0, n1 = 0.0;
-        int d = 0;
-        for (; d + 1 < D; d += 2) { const double a = mine[(size_t)d * PC_BIG_NT], b = mine[(size_t)(d + 1) * PC_BIG_NT]; n0 += a * a; n1 += b * b; }
-        if (d < D) { const double a = mine[(size_t)d * PC_BIG_NT]; n0 += a * a; }
-        const double w = sqrt(n0 + n1);                   // chordal_sampling.f90:80-82
+        // |t|^2 over up to 256 squares: a plain sum on two accumulators left the rows of unit norm to 4.2 u only (3 ... 4 u of it the sum's
+        // own rounding).  Compensated instead -- the product's error by FMA, the addition's by TwoSum (Ogita, Rump & Oishi, Dot2): the sum
+        // is exact to a rounding, what is left is the root, the reciprocal and the products (tests/test_directions.py holds 4 u)
+        double sn = 0.0, cn = 0.0;
+        for (int d = 0; d < D; ++d) {
+#pragma clang fp contract(off)
+            const double a = mine[(size_t)d * PC_BIG_NT];
+            const double p = a * a, pe = fma(a, a, -p);
+            const double t = sn + p, bp = t - sn;
+            cn += ((sn - (t - bp)) + (p - bp)) + pe;
+            sn = t;
+        }
+        const double w = sqrt(sn + cn);                   // chordal_sampling.f90:80-82
         iwv[i] = 1.0 / w;
         S.nhat_w[(size_t)chain * nr + col0 + basis * Dg + i] = w * 3.0;
     }

@@ -80,6 +80,8 @@ def load():
     lib.pc_slice_chain.argtypes = [C.POINTER(Settings), C.POINTER(Like), C.POINTER(Prior), C.POINTER(Rng), C.c_uint32,
                                    C.c_uint32, pd, pd, d, pd, pd]
     lib.pc_slice_chain.restype = C.c_long
+    lib.pc_direction_inputs.argtypes = [C.POINTER(Settings), C.c_uint32, C.c_uint32, C.c_uint32, pd, C.c_long, pd]
+    lib.pc_direction_inputs.restype = C.c_long
     lib.pc_random_invcov.argtypes = [C.c_uint32, C.c_int, d, pd, pd]
     lib.pc_like_eval.argtypes = [C.POINTER(Like), pd, C.c_int, pd, C.c_int]; lib.pc_like_eval.restype = d
     _lib = lib
@@ -155,3 +157,22 @@ def slice_chain(s, like, prior, key_seed, batch, chain, seed_point, chol, contou
     n = lib.pc_slice_chain(C.byref(s), C.byref(like), C.byref(prior), C.byref(rng), batch, chain, dptr(sp), dptr(ch),
                            contour, dptr(babies), dptr(nh))
     return babies, nh, n
+
+
+def direction_inputs(s, key_seed, batch, chain, want_raw=True):
+    """what the oracle's generate_nhats draws and makes for one chain in keyed mode -> (deviates in drawing order, the unshuffled fp64
+    directions before whitening [nr][D] or None)"""
+    lib = load()
+    D = s.nDims
+    if s.nGrade > 1:
+        reps = [int(s.grade_frac[g]) for g in range(s.nGrade)]
+        off = [sum(s.grade_dims[h] for h in range(g)) for g in range(s.nGrade)]
+    else:
+        reps, off = [s.num_repeats], [0]
+    nr = sum(reps)
+    n = sum(-(-r // (D - o)) * (D - o) ** 2 for r, o in zip(reps, off))
+    dev = np.zeros(n)
+    raw = np.zeros((nr, s.nDims)) if want_raw else None
+    got = lib.pc_direction_inputs(C.byref(s), key_seed & 0xFFFFFFFF, batch, chain, dptr(dev), n, dptr(raw) if want_raw else None)
+    assert got == n, (got, n)
+    return dev, raw

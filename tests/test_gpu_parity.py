@@ -17,7 +17,7 @@ from tests import oracle_api as orc
 
 pytestmark = pytest.mark.gpu
 
-BOX = {"gaussian": (None, None), "rastrigin": (-5.12, 5.12), "twin_gaussian": (-1.0, 1.0)}
+BOX = {"gaussian": (None, None), "rastrigin": (-5.12, 5.12), "twin_gaussian": (-1.0, 1.0), "corr_gaussian": (None, None)}
 
 
 def _settings(api, D, nDer, **kw):
@@ -31,15 +31,23 @@ def _settings(api, D, nDer, **kw):
 @pytest.mark.parametrize("kind,D,nDer,nr,nchains", [("gaussian", 20, 2, 40, 6), ("gaussian", 4, 1, 8, 3),
                                                    ("gaussian", 2, 0, 5, 3), ("rastrigin", 10, 0, 30, 4),
                                                    ("twin_gaussian", 30, 1, 40, 3), ("gaussian", 20, 2, 100, 2),
-                                                   ("gaussian", 33, 0, 40, 2)])
+                                                   ("gaussian", 33, 0, 40, 2),
+                                                   # above 64 dimensions: k_nhats_q<32> (with the M products of the correlated Gaussian), k_nhats_big
+                                                   ("gaussian", 100, 0, 103, 4), ("corr_gaussian", 100, 0, 103, 4), ("gaussian", 150, 0, 153, 4)])
 def test_slice_chains_match_oracle(engine, kind, D, nDer, nr, nchains):
     api = engine; lib = api.load(); olib = orc.load()
     lo, hi = BOX[kind]
     seed = 11
     s = _settings(api, D, nDer, num_repeats=nr, seed=seed)
-    L, P, keep = api.make_problem(kind, D, nDer, lo, hi)
     so = orc.settings(D, nDer, num_repeats=nr, seed=seed)
-    Lo, Po, keep2 = orc.make_problem(kind, D, lo, hi)
+    if kind == "corr_gaussian":
+        ic = np.zeros((D, D)); ld = C.c_double()
+        olib.pc_random_invcov(12345, D, C.c_double(0.1), orc.dptr(ic), C.byref(ld))
+        L, P, keep = api.make_problem(kind, D, nDer, invcov=ic, mean=np.full(D, 0.5), logdet=ld.value)
+        Lo, Po, keep2 = orc.make_problem(kind, D, invcov=ic, mean=np.full(D, 0.5), logdet=ld.value)
+    else:
+        L, P, keep = api.make_problem(kind, D, nDer, lo, hi)
+        Lo, Po, keep2 = orc.make_problem(kind, D, lo, hi)
     nT = 2 * D + nDer + 2
     rng = np.random.default_rng(D * 1000 + nr)
     lo_a = np.broadcast_to(0.0 if lo is None else lo, (D,)); hi_a = np.broadcast_to(1.0 if hi is None else hi, (D,))
