@@ -17,7 +17,7 @@ module polychord_hip
               polychord_hip_table_prior, polychord_hip_set_table_prior, pchip_prior_entry, &
               polychord_hip_set_option, polychord_hip_set_sub_clustering, run_polychord_hip, &
               polychord_hip_set_source, polychord_hip_source_loglike, polychord_hip_source_prior, &
-              pchip_source_create, pchip_source_destroy
+              pchip_source_create, pchip_source_create_shared, pchip_source_destroy
 
     !> one parameter of a prior table (pchip_prior_entry of polychord_hip.h): the reference's type number 1 .. 10 (priors.f90:5-15),
     !! the prior block, the number of prior parameters and the parameters in the ini file's order
@@ -114,6 +114,20 @@ module polychord_hip
             character(kind=c_char) :: source(*), options(*)
             real(c_double) :: block(*)
             integer(c_long), value :: ndata
+            integer(c_int) :: handle
+        end function
+        !> Shared values beside a wave-parallel form (polychord_hip.h: pchip_source_create_shared): the source defines pchip_shared_value and
+        !! its form's functions with `shared` behind theta.  nres > 0: the quadratic form, precision(nres * nres) row-major (nterms = 0,
+        !! nsums = 0); otherwise nterms >= 1 terms in one sum (nsums = 0) or in nsums sums; precision is not read when nres = 0 -- pass
+        !! c_null_ptr there.  The handle (> 0), or -1 with the reason in polychord_hip_last_error()
+        function pchip_source_create_shared(source, options, block, ndata, nshared, nterms, nsums, nres, precision, with_prior) &
+                result(handle) bind(c, name="pchip_source_create_shared")
+            import :: c_char, c_double, c_long, c_int, c_ptr
+            character(kind=c_char) :: source(*), options(*)
+            real(c_double) :: block(*)
+            integer(c_long), value :: ndata, nshared, nterms, nres
+            integer(c_int), value :: nsums, with_prior
+            type(c_ptr), value :: precision
             integer(c_int) :: handle
         end function
         subroutine pchip_source_destroy(handle) bind(c, name="pchip_source_destroy")

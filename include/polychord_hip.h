@@ -413,6 +413,39 @@ int  pchip_source_create_sums(const char *source, const char *options, const dou
 #define PCHIP_SOURCE_MAX_RES 1024
 int  pchip_source_create_quad(const char *source, const char *options, const double *data, long ndata, long nres,
                               const double *precision /* host, nres x nres, row-major */, int with_prior);
+/* SHARED VALUES: quantities that depend on theta but not on i -- a distance table on a redshift grid that every supernova interpolates,
+ * spline coefficients, a model spectrum on a k-grid, rotated parameters, normalisation integrals -- computed ONCE per evaluated point by
+ * the wavefront, one lane per value, instead of inside every term.  They go with each of the three wave-parallel forms above.  The source
+ * defines one more function,
+ *     __device__ double pchip_shared_value(const double *theta, int nDims, const double *data, long ndata, long k);
+ * the k-th shared value of the point, 0 <= k < nshared: called by ONE lane per k, once per evaluated point; pure, may read theta and data,
+ * must not synchronise, must not read other shared values (a cumulative table is a loop inside it).  The functions of the handle's form are
+ * C++ overloads of the names above with one more parameter, `const double *shared`, directly behind theta -- the finished block of
+ * nshared doubles:
+ *     __device__ double pchip_logl_term   (const double *theta, const double *shared, int nDims, const double *data, long ndata, long i);
+ *     __device__ void   pchip_logl_terms  (const double *theta, const double *shared, int nDims, const double *data, long ndata, long i, double *t);
+ *     __device__ double pchip_residual    (const double *theta, const double *shared, int nDims, const double *data, long ndata, long i);
+ *     __device__ double pchip_logl_finish (double sum_or_chi2, const double *theta, const double *shared, double *phi, int nDims, int nDerived,
+ *                                          const double *data, long ndata);
+ *     __device__ double pchip_logl_finish_sums(const double *sums, const double *theta, const double *shared, double *phi, int nDims,
+ *                                          int nDerived, const double *data, long ndata);
+ * Only the overloads of the handle's form are declared and called; the text may carry the others as well.  The form: nres > 0 the quadratic
+ * form (precision != NULL, nterms == 0, nsums == 0); otherwise nterms >= 1 with nsums == 0 one sum, with 1 <= nsums <=
+ * PCHIP_SOURCE_MAX_SUMS several.  A plain likelihood that wants shared values is nterms = 1.  The defined order:
+ *   1. theta goes to the wave's copy in LDS, behind a barrier;
+ *   2. lane l calls pchip_shared_value for k = l, l + 64, ... and stores each returned double, untouched, into the point's block; one barrier;
+ *   3. the form proceeds exactly as it does without shared values, `shared` pointing at that block: the order of every sum stays what it is.
+ * A point's bits do not depend on how it was evaluated: the two ends of a bracket have a block each, filled behind one barrier.  finish
+ * receives `shared`, so a derived parameter may be a shared value; an accepted point keeps only its sums, and the block is filled again
+ * (step 2) before finish writes its derived parameters.  To the rest of the library the handle is what its form is: path slots,
+ * pchip_source_eval, pchip_run_in_step, pchip_maximise_device and the doors take it unchanged.  1 <= nshared <= PCHIP_SOURCE_MAX_SHARED
+ * (two blocks of 4 KB of LDS a chain at the limit).  Not provided: values that read each other, shared values for pchip_loglikelihood's
+ * own entry point or for pchip_prior_param, values kept across the points of a chain.  -1 with the reason -- the range, the missing
+ * matrix, the mixed form, the compiler's log, the function the source lacks by name -- in polychord_hip_last_error(), before any device
+ * call. */
+#define PCHIP_SOURCE_MAX_SHARED 512
+int  pchip_source_create_shared(const char *source, const char *options, const double *data, long ndata,
+                                long nshared, long nterms, int nsums, long nres, const double *precision, int with_prior);
 /* The user's PRIOR in the same source and the same handle as the likelihood (pchip_prior.kind = PCHIP_PRIOR_SOURCE with pchip_like.kind =
  * PCHIP_LIKE_SOURCE, .source = the handle).  Besides the likelihood functions of its form -- nterms == 0: pchip_loglikelihood; nterms
  * >= 1: pchip_logl_term and pchip_logl_finish -- the source defines

@@ -10,7 +10,8 @@
 // Passing polychord_hip_gaussian / _rastrigin / _twin_gaussian / _corr_gaussian (and polychord_hip_uniform_prior, or
 // polychord_hip_table_prior after polychord_hip_set_table_prior: the reference's prior types, both declared in polychord_hip.h) as the
 // callbacks makes the engine evaluate them inside the sampling kernel.  The caller's OWN likelihood runs there too when it is written as
-// device source: pchip_source_create (or _terms, _sums, _quad, _prior), polychord_hip_set_source(handle), then
+// device source: pchip_source_create (or _terms, _sums, _quad, _prior; pchip_source_create_shared
+// for a source with shared values), polychord_hip_set_source(handle), then
 // polychord_hip_source_loglike as the likelihood -- and polychord_hip_source_prior as the prior for a handle that defines its prior
 // (all declared in polychord_hip.h; bindings/cpp/example_source.cpp).  There is no MPI in this engine: the MPI_Comm
 // overloads of the reference have no counterpart; one process drives one GPU.

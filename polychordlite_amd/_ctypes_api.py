@@ -136,6 +136,9 @@ def load():
     lib.pchip_source_create_sums.restype = C.c_int
     lib.pchip_source_create_quad.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long, C.POINTER(C.c_double), C.c_int]
     lib.pchip_source_create_quad.restype = C.c_int
+    lib.pchip_source_create_shared.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long, C.c_long, C.c_int, C.c_long,
+                                               C.POINTER(C.c_double), C.c_int]
+    lib.pchip_source_create_shared.restype = C.c_int
     lib.pchip_source_prior_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_long, C.c_int, C.POINTER(C.c_double)]
     lib.pchip_source_prior_eval.restype = C.c_int
     lib.pchip_source_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_long, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -189,24 +192,32 @@ def dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def source_create(source, options=(), data=None, nterms=None, prior=False, nsums=None, residuals=None, precision=None):
+def source_create(source, options=(), data=None, nterms=None, prior=False, nsums=None, residuals=None, precision=None, shared=None):
     """handle of a likelihood written as HIP device source (pchip_source_create); RuntimeError with the compiler's log if it does not compile.
     nterms given: the terms form (pchip_source_create_terms) -- the source defines pchip_logl_term and pchip_logl_finish, the sum has nterms terms.
     nsums given (with nterms): several sums per evaluation (pchip_source_create_sums) -- the source defines pchip_logl_terms and
     pchip_logl_finish_sums, every sum has nterms terms; nsums=None: the calls above, unchanged.
     residuals given: the quadratic form (pchip_source_create_quad) -- the source defines pchip_residual and pchip_logl_finish, chi2 = r^T P r
     of that many residuals; precision: P, a 2-D float64 array of shape (residuals, residuals), used exactly as given (ValueError on another shape).
+    shared given: that many shared values beside the form the other keywords name (pchip_source_create_shared) -- the source defines
+    pchip_shared_value and its form's functions with `const double *shared` behind theta; nterms alone one sum, nsums with it several,
+    residuals / precision the quadratic form.  shared=None: the calls above, unchanged.
     prior=True: the source defines pchip_prior_param as well (pchip_source_create_prior; with nsums, pchip_source_create_sums' with_prior),
     for runs with prior.kind = PRIOR_SOURCE"""
     lib = load()
     d = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
     opts = " ".join(options) if not isinstance(options, str) else options
     args = (source.encode(), opts.encode(), dptr(d) if d is not None and d.size else None, 0 if d is None else int(d.size))
+    p = None
     if residuals is not None:
         n = int(residuals)
         p = None if precision is None else np.ascontiguousarray(precision, dtype=np.float64)
         if p is not None and n >= 1 and p.shape != (n, n):
             raise ValueError(f"precision has shape {p.shape}: the quadratic form of {n} residuals takes a 2-D array of shape ({n}, {n})")
+    if shared is not None:
+        h = lib.pchip_source_create_shared(*args, int(shared), 0 if nterms is None else int(nterms), 0 if nsums is None else int(nsums),
+                                           0 if residuals is None else int(residuals), dptr(p) if p is not None and p.size else None, 1 if prior else 0)
+    elif residuals is not None:
         h = lib.pchip_source_create_quad(*args, n, dptr(p) if p is not None and p.size else None, 1 if prior else 0)
     elif nsums is not None:
         h = lib.pchip_source_create_sums(*args, 0 if nterms is None else int(nterms), int(nsums), 1 if prior else 0)

@@ -59,9 +59,10 @@ void halt_or_return(const std::string &msg)
 // the form of a device source handle, for the run header
 std::string source_form(int h)
 {
-    if (pc_rtc_source_quad(h) > 0) return "quadratic form, " + std::to_string(pc_rtc_source_quad(h)) + " residuals";
-    if (pc_rtc_source_sums(h) > 0) return "terms form, " + std::to_string(pc_rtc_source_terms(h)) + " terms, " + std::to_string(pc_rtc_source_sums(h)) + " sums";
-    if (pc_rtc_source_terms(h) > 0) return "terms form, " + std::to_string(pc_rtc_source_terms(h)) + " terms";
+    const std::string shared = pc_rtc_source_shared(h) > 0 ? ", " + std::to_string(pc_rtc_source_shared(h)) + " shared values" : "";
+    if (pc_rtc_source_quad(h) > 0) return "quadratic form, " + std::to_string(pc_rtc_source_quad(h)) + " residuals" + shared;
+    if (pc_rtc_source_sums(h) > 0) return "terms form, " + std::to_string(pc_rtc_source_terms(h)) + " terms, " + std::to_string(pc_rtc_source_sums(h)) + " sums" + shared;
+    if (pc_rtc_source_terms(h) > 0) return "terms form, " + std::to_string(pc_rtc_source_terms(h)) + " terms" + shared;
     return "plain form";
 }
 

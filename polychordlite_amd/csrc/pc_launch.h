@@ -13,9 +13,12 @@ extern "C" int pc_rtc_source_sums(int id);
 // the number of residuals of a handle made by pchip_source_create_quad; 0: any other handle, or none (pc_rtc.hip)
 extern "C" long pc_rtc_source_quad(int id);
 
+// the number of shared values of a handle made by pchip_source_create_shared; 0: any other handle, or none (pc_rtc.hip)
+extern "C" long pc_rtc_source_shared(int id);
+
 // A quadratic-form source keeps the residuals of the point -- of the two ends of a bracket -- in two blocks of nres doubles (an even
 // number each: 16-byte reads) at the FRONT of the dynamic LDS of every kernel that evaluates the likelihood (pc_sample.hip, PC_DYN_LDS):
-// their bytes, which every launcher of such a kernel adds to its own; 0 for any other state
+// their bytes; 0 for any other state
 static inline size_t pc_quad_lds(const PcState *S)
 {
     if (S->like.kind != PC_LIKE_SOURCE) return 0;
@@ -23,17 +26,30 @@ static inline size_t pc_quad_lds(const PcState *S)
     return n > 0 ? sizeof(double) * 2 * (size_t)((n + 1) & ~1L) : 0;
 }
 
+// The form's front block of that dynamic LDS: the quadratic form's two residual blocks, if any, then the two blocks of a handle with
+// shared values (pchip_source_create_shared: nshared doubles a point, rounded up to even, for the two ends of a bracket).  Its bytes,
+// which every launcher of a kernel that evaluates the likelihood adds to its own; 0 for any other state
+static inline size_t pc_front_lds(const PcState *S)
+{
+    if (S->like.kind != PC_LIKE_SOURCE) return 0;
+    const long n = pc_rtc_source_shared(S->src_id);
+    return pc_quad_lds(S) + (n > 0 ? sizeof(double) * 2 * (size_t)((n + 1) & ~1L) : 0);
+}
+
 // k_slice keeps the theta rows of a chain's babies in LDS (its run-time flag phi_lds: derived parameters at the end of the chain, summed
 // in that order) when they fit under 48 KB next to the chain's block; pc_slice_t_ok takes only states where it does
 // (pc_slice_plan's rule, asked by pc_slice_t_ok in another file: inline here, the one definition in this header, so that the library's
 //  exported pc_* names stay what they were).  A source with several sums keeps the sums of every baby beside the rows, [nr][nsums]: the
 // block counts here, and a shape it pushes over the limit writes its derived parameters inside the slice loop like any that does not fit.
-// The residual blocks of a quadratic form (pc_quad_lds) count in the same way.
+// The front block of a quadratic form (pc_front_lds) counts in the same way.  A handle with shared values never takes the end-of-chain
+// pass: there finish runs with lane = baby, and a lane has no shared block of its own -- its derived parameters are written inside the
+// slice loop (like_phi_terms fills the point's block again), and its unit does not compile the lane = baby branch.
 static inline int pc_slice_phi_lds(const PcState *S)
 {
     const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16, tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
     const size_t sums = S->like.kind == PC_LIKE_SOURCE ? sizeof(double) * (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0;
-    return (S->nDer > 0 && sh0 + tb + sums + pc_quad_lds(S) <= 48 * 1024) ? 1 : 0;
+    if (S->like.kind == PC_LIKE_SOURCE && pc_rtc_source_shared(S->src_id) > 0) return 0;
+    return (S->nDer > 0 && sh0 + tb + sums + pc_front_lds(S) <= 48 * 1024) ? 1 : 0;
 }
 
 extern "C" {

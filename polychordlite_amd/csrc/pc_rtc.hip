@@ -24,6 +24,11 @@
 // unit gets PCHIP_USER_QUAD in front beside the two #defines of the terms form: pc_sample.hip's walk over the matrix is compiled in
 // their place only.
 //
+// Shared values (pchip_source_create_shared): the source defines pchip_shared_value (the k-th of nshared values of theta that do not depend
+// on i, one lane per k, once per evaluated point) and the functions of its form -- terms, sums or quadratic -- as overloads with `const
+// double *shared` behind theta.  Such a handle is what its form is to everybody who asks, and its unit gets PCHIP_USER_SHARED and
+// PCHIP_SRC_NSHARED in front beside the form's own #defines.
+//
 // A prior in the same source (pchip_source_create_prior): the text defines pchip_prior_param (theta[i] from the whole cube, one call per
 // parameter) next to the likelihood of either form; such a handle's unit gets PCHIP_USER_PRIOR in front, and a run with prior.kind =
 // PCHIP_PRIOR_SOURCE takes the table's kernel variants with that function behind the transform's one entry point (pc_sample.hip).
@@ -90,6 +95,7 @@ struct Source {
     int nsums = 0;                         // > 0: several sums per evaluation (pchip_logl_terms / pchip_logl_finish_sums; pchip_source_create_sums)
     long nquad = 0;                        // > 0: the quadratic form (pchip_residual / pchip_logl_finish; pchip_source_create_quad): nterms == nquad, and
                                            //      the nquad x nquad precision matrix lies in `data` behind the user's ndata doubles
+    long nshared = 0;                      // > 0: shared values (pchip_shared_value; pchip_source_create_shared) beside the form above
     long long ndata = 0;                   // the user's data: the first ndata doubles of `data`
     bool has_prior = false;                // the source defines pchip_prior_param as well (pchip_source_create_prior)
 };
@@ -179,14 +185,15 @@ int compile(const Source *s, const std::string &unit, const std::vector<std::str
 
 // the translation unit of the sampling kernels: the library's kernels (pc_sample.hip declares pchip_loglikelihood under PCHIP_USER_SOURCE),
 // then the user's text -- its macros and pragmas reach nothing of the library's.  A terms handle: its form and its loop bound in front;
-// a handle with several sums: their number in front as well; a quadratic form: PCHIP_USER_QUAD in front as well; a handle with a prior (pchip_source_create_prior): PCHIP_USER_PRIOR in front.
+// a handle with several sums: their number in front as well; a quadratic form: PCHIP_USER_QUAD in front as well; shared values: PCHIP_USER_SHARED and their number in front as well; a handle with a prior (pchip_source_create_prior): PCHIP_USER_PRIOR in front.
 std::string kernel_unit(const Source *s)
 {
     const std::string prior = s && s->has_prior ? "#define PCHIP_USER_PRIOR 1\n" : "";
     const std::string sums = s && s->nsums > 0 ? "#define PCHIP_USER_SUMS 1\n#define PCHIP_SRC_NSUMS " + std::to_string(s->nsums) + "\n" : "";
     const std::string quad = s && s->nquad > 0 ? "#define PCHIP_USER_QUAD 1\n" : "";
+    const std::string shared = s && s->nshared > 0 ? "#define PCHIP_USER_SHARED 1\n#define PCHIP_SRC_NSHARED " + std::to_string(s->nshared) + "\n" : "";
     if (s && s->nterms > 0)
-        return prior + sums + quad + "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
+        return prior + sums + quad + shared + "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
     return s ? prior + "#define PCHIP_USER_SOURCE 1\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n"
              : std::string("#include \"pc_sample.hip\"\n");
 }
@@ -218,14 +225,42 @@ const char *const PROBE_UNIT_QUAD =
     "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
     "{ out[0] = pchip_logl_finish(pchip_residual(th, nDims, data, ndata, i), th, phi, nDims, nDerived, data, ndata); }\n"
     "#include \"pchip_user_source.h\"\n";
+// ... and of pchip_source_create_shared: the probe of the handle's form with one shared value computed and the block passed on -- the
+// overloads with `shared` behind theta are the only ones declared, so a source that has only the others fails at the link, by name
+const char *const PROBE_SHARED_DECL =
+    "__device__ double pchip_shared_value(const double *theta, int nDims, const double *data, long ndata, long k);\n";
+const char *const PROBE_SHARED_HEAD =
+    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
+    "{ double sh[2]; sh[0] = pchip_shared_value(th, nDims, data, ndata, i); ";
+const char *const PROBE_UNIT_TERMS_SHARED =
+    "__device__ double pchip_logl_term(const double *theta, const double *shared, int nDims, const double *data, long ndata, long i);\n"
+    "__device__ double pchip_logl_finish(double sum, const double *theta, const double *shared, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
+    "%HEAD%out[0] = pchip_logl_finish(pchip_logl_term(th, sh, nDims, data, ndata, i), th, sh, phi, nDims, nDerived, data, ndata); }\n"
+    "#include \"pchip_user_source.h\"\n";
+const char *const PROBE_UNIT_SUMS_SHARED =
+    "__device__ void pchip_logl_terms(const double *theta, const double *shared, int nDims, const double *data, long ndata, long i, double *t);\n"
+    "__device__ double pchip_logl_finish_sums(const double *sums, const double *theta, const double *shared, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
+    "%HEAD%double t[PCHIP_SRC_NSUMS]; pchip_logl_terms(th, sh, nDims, data, ndata, i, t); out[0] = pchip_logl_finish_sums(t, th, sh, phi, nDims, nDerived, data, ndata); }\n"
+    "#include \"pchip_user_source.h\"\n";
+const char *const PROBE_UNIT_QUAD_SHARED =
+    "__device__ double pchip_residual(const double *theta, const double *shared, int nDims, const double *data, long ndata, long i);\n"
+    "__device__ double pchip_logl_finish(double chi2, const double *theta, const double *shared, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
+    "%HEAD%out[0] = pchip_logl_finish(pchip_residual(th, sh, nDims, data, ndata, i), th, sh, phi, nDims, nDerived, data, ndata); }\n"
+    "#include \"pchip_user_source.h\"\n";
+std::string probe_unit_shared(int nsums, bool quad)
+{
+    std::string u = quad ? PROBE_UNIT_QUAD_SHARED : (nsums > 0 ? PROBE_UNIT_SUMS_SHARED : PROBE_UNIT_TERMS_SHARED);
+    u.replace(u.find("%HEAD%"), 6, PROBE_SHARED_HEAD);
+    return (nsums > 0 ? "#define PCHIP_SRC_NSUMS " + std::to_string(nsums) + "\n" : std::string()) + PROBE_SHARED_DECL + u;
+}
 
 // ... and of pchip_source_create_prior: the probe of the handle's form, then pchip_prior_param behind its declaration, called as well
 const char *const PROBE_PRIOR_DECL =
     "__device__ double pchip_prior_param(const double *cube, int i, int nDims, const double *data, long ndata);\n";
 const char *const PROBE_PRIOR_CALL = "out[0] += pchip_prior_param(th, 0, nDims, data, ndata); }\n";
-std::string probe_unit(long nterms, int nsums, bool quad, bool prior)
+std::string probe_unit(long nterms, int nsums, bool quad, bool prior, bool shared)
 {
-    std::string u = quad ? std::string(PROBE_UNIT_QUAD) : nsums > 0 ? "#define PCHIP_SRC_NSUMS " + std::to_string(nsums) + "\n" + PROBE_UNIT_SUMS : std::string(nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT);
+    std::string u = shared ? probe_unit_shared(nsums, quad) : quad ? std::string(PROBE_UNIT_QUAD) : nsums > 0 ? "#define PCHIP_SRC_NSUMS " + std::to_string(nsums) + "\n" + PROBE_UNIT_SUMS : std::string(nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT);
     if (!prior) return u;
     const size_t close = u.rfind(" }\n");        // the end of pchip_probe's body: the call goes in front of it
     u.replace(close, 3, std::string(" ") + PROBE_PRIOR_CALL);
@@ -366,6 +401,15 @@ long pc_rtc_source_quad(int id)
     return it == G.src.end() ? 0 : it->second->nquad;
 }
 
+// the number of shared values of a handle made by pchip_source_create_shared; 0: any other handle, or none
+long pc_rtc_source_shared(int id)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    auto it = G.src.find(id);
+    return it == G.src.end() ? 0 : it->second->nshared;
+}
+
 int pc_rtc_source_has_prior(int id)
 {
     Registry &G = reg();
@@ -374,11 +418,11 @@ int pc_rtc_source_has_prior(int id)
     return it != G.src.end() && it->second->has_prior ? 1 : 0;
 }
 
-// pchip_source_create[_terms | _sums | _quad | _prior]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
+// pchip_source_create[_terms | _sums | _quad | _prior | _shared]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
 // nterms > 0: the terms form, of nsums sums where nsums > 0; precision != NULL: the quadratic form of nterms residuals, its matrix copied
-// behind the data.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
+// behind the data; nshared > 0: shared values beside that form.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
 int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums, bool prior, std::string *log,
-                         const double *precision)
+                         const double *precision, long nshared = 0)
 {
     if (!source) { *log = "pchip_source_create: no source"; return -1; }
     if (ndata < 0 || (ndata > 0 && !data)) { *log = "pchip_source_create: ndata > 0 needs a data block"; return -1; }
@@ -390,7 +434,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     if (ndata > 0) s->data.assign(data, data + ndata);
     s->ndata = ndata;
     if (precision) { s->data.insert(s->data.end(), precision, precision + (size_t)nterms * (size_t)nterms); s->nquad = nterms; }
-    s->nterms = nterms; s->nsums = nsums; s->has_prior = prior;
+    s->nterms = nterms; s->nsums = nsums; s->has_prior = prior; s->nshared = nshared;
     std::string arch = "gfx950";
     int dev = 0, ndev = 0;
     if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&dev) == hipSuccess) {
@@ -399,7 +443,7 @@ int pc_rtc_source_create(const char *source, const char *options, const double *
     }
     (void)hipGetLastError();
     std::vector<char> code; std::vector<std::string> lowered;
-    if (compile(s.get(), probe_unit(nterms, nsums, precision != nullptr, prior), { "pchip_probe" }, arch, code, lowered, *log)) return -1;
+    if (compile(s.get(), probe_unit(nterms, nsums, precision != nullptr, prior, nshared > 0), { "pchip_probe" }, arch, code, lowered, *log)) return -1;
     Registry &G = reg();
     std::lock_guard<std::mutex> g(G.m);
     const int id = G.next++;
@@ -463,6 +507,32 @@ extern "C" int pchip_source_create_quad(const char *source, const char *options,
         log = "pchip_source_create_quad: nres = " + std::to_string(nres) + " -- 1 <= nres <= " + std::to_string(PCHIP_SOURCE_MAX_RES) + " (PCHIP_SOURCE_MAX_RES)";
     else if (!precision) log = "pchip_source_create_quad: precision == NULL -- the nres x nres matrix of the quadratic form (host, row-major)";
     else id = pc_rtc_source_create(source, options, data, ndata, nres, 0, with_prior != 0, &log, precision);
+    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
+    return id;
+}
+
+// shared values beside one of the three wave-parallel forms: nres > 0 the quadratic form, else nterms >= 1 terms in one sum (nsums == 0) or in
+// nsums sums; every refusal before any device call
+extern "C" int pchip_source_create_shared(const char *source, const char *options, const double *data, long ndata, long nshared, long nterms, int nsums,
+                                          long nres, const double *precision, int with_prior)
+{
+    const std::string me = "pchip_source_create_shared: ";
+    std::string log;
+    int id = -1;
+    if (nshared < 1 || nshared > PCHIP_SOURCE_MAX_SHARED)
+        log = me + "nshared = " + std::to_string(nshared) + " -- 1 <= nshared <= " + std::to_string(PCHIP_SOURCE_MAX_SHARED) + " (PCHIP_SOURCE_MAX_SHARED)";
+    else if (nres < 0 || nres > PCHIP_SOURCE_MAX_RES)
+        log = me + "nres = " + std::to_string(nres) + " -- 0, or the quadratic form with 1 <= nres <= " + std::to_string(PCHIP_SOURCE_MAX_RES) + " (PCHIP_SOURCE_MAX_RES)";
+    else if (nres > 0 && (nterms != 0 || nsums != 0))
+        log = me + "nres = " + std::to_string(nres) + " with nterms = " + std::to_string(nterms) + ", nsums = " + std::to_string(nsums) +
+              " -- one form a handle: the quadratic form (nres > 0) takes nterms == 0 and nsums == 0";
+    else if (nres > 0 && !precision) log = me + "precision == NULL -- the nres x nres matrix of the quadratic form (host, row-major)";
+    else if (nres == 0 && precision) log = me + "precision != NULL with nres = 0 -- the matrix belongs to the quadratic form (nres > 0)";
+    else if (nres == 0 && nterms < 1)
+        log = me + "nterms = " + std::to_string(nterms) + " -- the sum needs at least one term (nterms >= 1; a plain likelihood with shared values is nterms = 1)";
+    else if (nres == 0 && (nsums < 0 || nsums > PCHIP_SOURCE_MAX_SUMS))
+        log = me + "nsums = " + std::to_string(nsums) + " -- 0 (one sum), or 1 <= nsums <= " + std::to_string(PCHIP_SOURCE_MAX_SUMS) + " (PCHIP_SOURCE_MAX_SUMS)";
+    else id = pc_rtc_source_create(source, options, data, ndata, nres > 0 ? nres : nterms, nres > 0 ? 0 : nsums, with_prior != 0, &log, nres > 0 ? precision : nullptr, nshared);
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }

@@ -174,8 +174,11 @@ __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDim
 #endif
 
 // The dynamic LDS of a kernel that evaluates the likelihood, as `name`: the declaration every kernel had -- except in the unit of a
-// quadratic-form handle (PCHIP_USER_QUAD, below), where the kernel's own layout starts behind that form's residual blocks.
-#ifdef PCHIP_USER_QUAD
+// quadratic-form handle (PCHIP_USER_QUAD, below), where the kernel's own layout starts behind that form's residual blocks, and of a
+// handle with shared values (PCHIP_USER_SHARED, below), where it starts behind the form's whole front block.
+#ifdef PCHIP_USER_SHARED
+#define PC_DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) char name##_all[]; char *const name = name##_all + PC_FRONT_LDS_BYTES
+#elif defined(PCHIP_USER_QUAD)
 #define PC_DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) char name##_all[]; char *const name = name##_all + PC_QUAD_LDS_BYTES
 #else
 #define PC_DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) char name[]
@@ -183,6 +186,52 @@ __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDim
 
 template <int DPL, int NROWS>
 __device__ __forceinline__ double wsum(double v) { return (DPL > 1) ? wave_sum<4>(v) : wave_sum<NROWS>(v); }
+
+#ifdef PCHIP_USER_SHARED
+// Shared values (pchip_source_create_shared; PCHIP_USER_SHARED and PCHIP_SRC_NSHARED in front of the defines of the handle's form): what
+// the user's terms need of theta alone -- a table on a grid, spline coefficients, rotated parameters -- is computed ONCE per evaluated
+// point, one lane per value, and every function of the form gets the finished block as `shared` behind theta.  The defined order
+// (tests/test_source_shared.py rests on it):
+//   1. theta to the wave's LDS copy, behind the barrier a source evaluation always had
+//   2. lane l: shared[k] = pchip_shared_value(theta, k) for k = l, l + 64, ... -- the returned double stored as it is --; one barrier
+//   3. the form as it is without shared values: the strided term loop and wave_sum<4>, or the residual block and the walk over P; finish
+// The blocks -- two, for the two ends of a bracket; PC_SHARED_NP doubles each, even, so that they stay on 16 bytes -- lie in the form's
+// front block of the dynamic LDS, behind the residual blocks of a quadratic form: block 0 belongs to the theta in ybuf, block 1 to the
+// one in ybuf2.  PC_SH_PARAM / PC_SH_PASS / PC_SH_BLOCK(b) put the parameter, the argument and a block's address into the adaptors and
+// their calls below; without PCHIP_USER_SHARED they are empty and every token is what it was.
+constexpr long PC_SHARED_N = (long)(PCHIP_SRC_NSHARED);
+constexpr long PC_SHARED_NP = (PC_SHARED_N + 1) & ~1L;
+#ifdef PCHIP_USER_QUAD
+#define PC_SHARED_OFF_BYTES (sizeof(double) * 2 * (size_t)((((long)(PCHIP_SRC_NTERMS)) + 1) & ~1L))
+#else
+#define PC_SHARED_OFF_BYTES ((size_t)0)
+#endif
+#define PC_FRONT_LDS_BYTES (PC_SHARED_OFF_BYTES + sizeof(double) * 2 * (size_t)PC_SHARED_NP)
+__device__ double pchip_shared_value(const double *theta, int nDims, const double *data, long ndata, long k);
+__device__ __forceinline__ double *pc_shared_block(int b)
+{
+    extern __shared__ __attribute__((aligned(16))) char pc_front_all[];      // (the dynamic LDS from its start: every such declaration names it)
+    return (double *)(pc_front_all + PC_SHARED_OFF_BYTES) + (size_t)b * PC_SHARED_NP;
+}
+// step 2 for NP points (theta[p]: their LDS copies, already behind a barrier): block p is theta[p]'s
+template <int NP>
+__device__ __forceinline__ void pc_shared_fill(const PcState &S, const double *const (&theta)[NP], int lane)
+{
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        double *sh = pc_shared_block(p);
+        for (long k = lane; k < PC_SHARED_N; k += 64) sh[k] = pchip_shared_value(theta[p], S.D, S.src_data, (long)S.src_ndata, k);
+    }
+    __syncthreads();                              // one wave per workgroup: cheap
+}
+#define PC_SH_PARAM , const double *shared
+#define PC_SH_PASS , shared
+#define PC_SH_BLOCK(b) , pc_shared_block(b)
+#else
+#define PC_SH_PARAM
+#define PC_SH_PASS
+#define PC_SH_BLOCK(b)
+#endif
 
 #ifdef PCHIP_USER_TERMS
 // The terms form of a user source (pchip_source_create_terms; pc_rtc.hip defines PCHIP_USER_TERMS and PCHIP_SRC_NTERMS in front of this
@@ -202,15 +251,15 @@ __device__ __forceinline__ double wsum(double v) { return (DPL > 1) ? wave_sum<4
 // behind two adaptors around the user's pchip_logl_term / pchip_logl_finish.
 #ifdef PCHIP_USER_SUMS
 constexpr int PC_NSUMS = (int)(PCHIP_SRC_NSUMS);
-__device__ void   pchip_logl_terms(const double *theta, int nDims, const double *data, long ndata, long i, double *t);
-__device__ double pchip_logl_finish_sums(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
-__device__ __forceinline__ void pc_user_terms(const double *theta, int nDims, const double *data, long ndata, long i, double (&t)[PC_NSUMS])
+__device__ void   pchip_logl_terms(const double *theta PC_SH_PARAM, int nDims, const double *data, long ndata, long i, double *t);
+__device__ double pchip_logl_finish_sums(const double *sums, const double *theta PC_SH_PARAM, double *phi, int nDims, int nDerived, const double *data, long ndata);
+__device__ __forceinline__ void pc_user_terms(const double *theta PC_SH_PARAM, int nDims, const double *data, long ndata, long i, double (&t)[PC_NSUMS])
 {
-    pchip_logl_terms(theta, nDims, data, ndata, i, t);
+    pchip_logl_terms(theta PC_SH_PASS, nDims, data, ndata, i, t);
 }
-__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata)
+__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta PC_SH_PARAM, double *phi, int nDims, int nDerived, const double *data, long ndata)
 {
-    return pchip_logl_finish_sums(sums, theta, phi, nDims, nDerived, data, ndata);
+    return pchip_logl_finish_sums(sums, theta PC_SH_PASS, phi, nDims, nDerived, data, ndata);
 }
 #elif defined(PCHIP_USER_QUAD)
 // The quadratic form (pchip_source_create_quad; PCHIP_USER_QUAD in front as well, PCHIP_SRC_NTERMS = nres): a Gaussian in data space with a
@@ -223,29 +272,29 @@ __device__ __forceinline__ double pc_user_finish(const double *sums, const doubl
 //   3. t_j = r_j * q_j, one IEEE multiply, kept from fusing with the add behind it by the empty asm of the terms form
 //   4. chi2 = the sum of the t_j in the terms form's order: lane l adds t_l, t_(l + 64), ... to 0.0, then wave_sum<4>
 // The residual blocks -- two, for the two ends of a bracket -- are the FIRST 2 x PC_QUAD_NP doubles of the workgroup's dynamic LDS: every
-// kernel that evaluates the likelihood starts its own layout behind them (PC_DYN_LDS below; the launchers add pc_quad_lds bytes), so that
+// kernel that evaluates the likelihood starts its own layout behind them (PC_DYN_LDS above; the launchers add them: pc_quad_lds, inside pc_front_lds), so that
 // the evaluation code finds them without a pointer handed down through every caller.  One wavefront a workgroup, as for every source.
 constexpr int PC_NSUMS = 1;
 constexpr long PC_QUAD_N = (long)(PCHIP_SRC_NTERMS);
 constexpr long PC_QUAD_NP = (PC_QUAD_N + 1) & ~1L;       // a block's length in doubles: even, both blocks on 16 bytes for the paired reads
 #define PC_QUAD_LDS_BYTES (sizeof(double) * 2 * (size_t)PC_QUAD_NP)
-__device__ double pchip_residual(const double *theta, int nDims, const double *data, long ndata, long i);
-__device__ double pchip_logl_finish(double chi2, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
-__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata)
+__device__ double pchip_residual(const double *theta PC_SH_PARAM, int nDims, const double *data, long ndata, long i);
+__device__ double pchip_logl_finish(double chi2, const double *theta PC_SH_PARAM, double *phi, int nDims, int nDerived, const double *data, long ndata);
+__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta PC_SH_PARAM, double *phi, int nDims, int nDerived, const double *data, long ndata)
 {
-    return pchip_logl_finish(sums[0], theta, phi, nDims, nDerived, data, ndata);
+    return pchip_logl_finish(sums[0], theta PC_SH_PASS, phi, nDims, nDerived, data, ndata);
 }
 #else
 constexpr int PC_NSUMS = 1;
-__device__ double pchip_logl_term(const double *theta, int nDims, const double *data, long ndata, long i);
-__device__ double pchip_logl_finish(double sum, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
-__device__ __forceinline__ void pc_user_terms(const double *theta, int nDims, const double *data, long ndata, long i, double (&t)[PC_NSUMS])
+__device__ double pchip_logl_term(const double *theta PC_SH_PARAM, int nDims, const double *data, long ndata, long i);
+__device__ double pchip_logl_finish(double sum, const double *theta PC_SH_PARAM, double *phi, int nDims, int nDerived, const double *data, long ndata);
+__device__ __forceinline__ void pc_user_terms(const double *theta PC_SH_PARAM, int nDims, const double *data, long ndata, long i, double (&t)[PC_NSUMS])
 {
-    t[0] = pchip_logl_term(theta, nDims, data, ndata, i);
+    t[0] = pchip_logl_term(theta PC_SH_PASS, nDims, data, ndata, i);
 }
-__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata)
+__device__ __forceinline__ double pc_user_finish(const double *sums, const double *theta PC_SH_PARAM, double *phi, int nDims, int nDerived, const double *data, long ndata)
 {
-    return pchip_logl_finish(sums[0], theta, phi, nDims, nDerived, data, ndata);
+    return pchip_logl_finish(sums[0], theta PC_SH_PASS, phi, nDims, nDerived, data, ndata);
 }
 #endif
 #ifdef PCHIP_USER_QUAD
@@ -329,7 +378,7 @@ __device__ __forceinline__ void pc_quad_sum(const PcState &S, const double *cons
     double *r = pc_quad_blocks();
 #pragma unroll
     for (int p = 0; p < NP; ++p)
-        for (long i = lane; i < N; i += 64) r[p * PC_QUAD_NP + i] = pchip_residual(theta[p], S.D, S.src_data, (long)S.src_ndata, i);
+        for (long i = lane; i < N; i += 64) r[p * PC_QUAD_NP + i] = pchip_residual(theta[p] PC_SH_BLOCK(p), S.D, S.src_data, (long)S.src_ndata, i);
     __syncthreads();                              // one wave per workgroup: cheap
     const double *P = S.src_data + S.src_ndata;
     double s[NP];
@@ -372,7 +421,7 @@ __device__ __forceinline__ void pc_terms_sum(const PcState &S, const double *the
         for (; i + 64 * (U - 1) < N; i += 64 * U) {
             double t[U][PC_NSUMS];
 #pragma unroll
-            for (int u = 0; u < U; ++u) pc_user_terms(theta, S.D, S.src_data, (long)S.src_ndata, i + 64 * u, t[u]);
+            for (int u = 0; u < U; ++u) pc_user_terms(theta PC_SH_BLOCK(0), S.D, S.src_data, (long)S.src_ndata, i + 64 * u, t[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -381,7 +430,7 @@ __device__ __forceinline__ void pc_terms_sum(const PcState &S, const double *the
     }
     for (; i < N; i += 64) {
         double t[PC_NSUMS];
-        pc_user_terms(theta, S.D, S.src_data, (long)S.src_ndata, i, t);
+        pc_user_terms(theta PC_SH_BLOCK(0), S.D, S.src_data, (long)S.src_ndata, i, t);
 #pragma unroll
         for (int k = 0; k < PC_NSUMS; ++k) { asm volatile("" : "+v"(t[k])); s[k] = s[k] + t[k]; }
     }
@@ -404,8 +453,8 @@ __device__ __forceinline__ void pc_terms_sum2(const PcState &S, const double *th
             double tA[U][PC_NSUMS], tB[U][PC_NSUMS];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                pc_user_terms(thA, S.D, S.src_data, (long)S.src_ndata, i + 64 * u, tA[u]);
-                pc_user_terms(thB, S.D, S.src_data, (long)S.src_ndata, i + 64 * u, tB[u]);
+                pc_user_terms(thA PC_SH_BLOCK(0), S.D, S.src_data, (long)S.src_ndata, i + 64 * u, tA[u]);
+                pc_user_terms(thB PC_SH_BLOCK(1), S.D, S.src_data, (long)S.src_ndata, i + 64 * u, tB[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -418,8 +467,8 @@ __device__ __forceinline__ void pc_terms_sum2(const PcState &S, const double *th
     }
     for (; i < N; i += 64) {
         double tA[PC_NSUMS], tB[PC_NSUMS];
-        pc_user_terms(thA, S.D, S.src_data, (long)S.src_ndata, i, tA);
-        pc_user_terms(thB, S.D, S.src_data, (long)S.src_ndata, i, tB);
+        pc_user_terms(thA PC_SH_BLOCK(0), S.D, S.src_data, (long)S.src_ndata, i, tA);
+        pc_user_terms(thB PC_SH_BLOCK(1), S.D, S.src_data, (long)S.src_ndata, i, tB);
 #pragma unroll
         for (int k = 0; k < PC_NSUMS; ++k) {
             asm volatile("" : "+v"(tA[k])); asm volatile("" : "+v"(tB[k]));
@@ -439,9 +488,12 @@ __device__ __forceinline__ double like_eval_terms(const PcState &S, const double
 #pragma unroll
     for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
     __syncthreads();                              // one wave per workgroup: cheap
+#ifdef PCHIP_USER_SHARED
+    { const double *const one[1] = { ybuf }; pc_shared_fill<1>(S, one, lane); }
+#endif
     pc_terms_sum(S, ybuf, lane, sum);
     double phi[PC_SRC_MAX_DERIVED];
-    const double l = pc_user_finish(sum, ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+    const double l = pc_user_finish(sum, ybuf PC_SH_BLOCK(0), phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
     __syncthreads();
     return l;
 }
@@ -453,8 +505,11 @@ __device__ __forceinline__ void like_phi_terms(const PcState &S, const double (&
 #pragma unroll
     for (int k = 0; k < DPL; ++k) if (ld.on[k]) ybuf[lane + 64 * k] = th[k];
     __syncthreads();
+#ifdef PCHIP_USER_SHARED        // (an accepted point keeps its sums, not its shared values: step 2 again)
+    { const double *const one[1] = { ybuf }; pc_shared_fill<1>(S, one, lane); }
+#endif
     double phi[PC_SRC_MAX_DERIVED];
-    (void)pc_user_finish(sum, ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+    (void)pc_user_finish(sum, ybuf PC_SH_BLOCK(0), phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
     if (lane == 0) for (int e = 0; e < S.nDer; ++e) out[e] = phi[e];
     __syncthreads();
 }
@@ -1915,11 +1970,14 @@ __device__ __forceinline__ void like_pair_terms(ChainCtx<DPL, NROWS, PT> &C, con
 #pragma unroll
         for (int k = 0; k < DPL; ++k) if (C.ld.on[k]) { C.ybuf[C.lane + 64 * k] = thA[k]; C.ybuf2[C.lane + 64 * k] = thB[k]; }
         __syncthreads();
+#ifdef PCHIP_USER_SHARED        // (both blocks behind one barrier)
+        { const double *const two[2] = { C.ybuf, C.ybuf2 }; pc_shared_fill<2>(S, two, C.lane); }
+#endif
         double sA[PC_NSUMS], sB[PC_NSUMS];
         pc_terms_sum2(S, C.ybuf, C.ybuf2, C.lane, sA, sB);
         double phi[PC_SRC_MAX_DERIVED];
-        lA = pc_user_finish(sA, C.ybuf, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
-        lB = pc_user_finish(sB, C.ybuf2, phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+        lA = pc_user_finish(sA, C.ybuf PC_SH_BLOCK(0), phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+        lB = pc_user_finish(sB, C.ybuf2 PC_SH_BLOCK(1), phi, S.D, S.nDer, S.src_data, (long)S.src_ndata);
         __syncthreads();
     } else if (inA) lA = like_eval_terms<DPL>(S, thA, C.ld, C.lane, C.ybuf, sum);
     else if (inB) lB = like_eval_terms<DPL>(S, thB, C.ld, C.lane, C.ybuf, sum);
@@ -2161,19 +2219,20 @@ template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, d
 // the terms form of a source evaluates the two ends of a bracket in one pass over the data: LDS for the second theta behind the chain's block;
 // a handle with several sums (pchip_source_create_sums) keeps the sums of every baby behind that, [nr][nsums], where the babies' theta rows
 // are in LDS (phi_lds: pc_slice_phi_lds has counted this block in its decision); a quadratic form (pchip_source_create_quad) has its two
-// residual blocks, 2 x nres doubles a chain (nres rounded up to even), in front of the chain's block: pc_quad_lds, counted in that
+// residual blocks, 2 x nres doubles a chain (nres rounded up to even), in front of the chain's block, and a handle with shared values
+// (pchip_source_create_shared) its two blocks of nshared doubles behind them: the form's front block, pc_front_lds, counted in that
 // decision as well
 static size_t pc_terms_lds(const PcState *S, int phi_lds)
 {
     if (S->like.kind != PC_LIKE_SOURCE || pc_rtc_source_terms(S->src_id) <= 0) return 0;
-    return sizeof(double) * ((size_t)S->D + (phi_lds ? (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0)) + pc_quad_lds(S);
+    return sizeof(double) * ((size_t)S->D + (phi_lds ? (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0)) + pc_front_lds(S);
 }
 // lane = coordinate: the coordinates a lane holds (template DPL) at nDims <= 64, 128, 256; 0 beyond (the launchers return 1)
 static int pc_dpl(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : (D <= 256 ? 4 : 0)); }
 extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL,
                                        hipStream_t st)
 {
-    const size_t sh = sizeof(double) * S->D + pc_quad_lds(S);
+    const size_t sh = sizeof(double) * S->D + pc_front_lds(S);
     const bool table = S->prior.kind >= 2;          // a prior table, or a source prior (kind 3: the same variants, from its handle's module)
     switch (pc_dpl(S->D) + (table ? 8 : 0)) {
     case 1: PC_LAUNCH((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
@@ -2488,7 +2547,7 @@ extern "C" int pc_launch_source_eval(const PcState *S, int n, const double *thet
     const int dpl = pc_dpl(S->D);
     if (S->like.kind != PC_LIKE_SOURCE || n < 1 || !dpl) return 1;
     const char *name = dpl == 1 ? "k_source_eval<1>" : (dpl == 2 ? "k_source_eval<2>" : "k_source_eval<4>");
-    return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D + pc_quad_lds(S), st, *S, thetas, logL, phi);
+    return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D + pc_front_lds(S), st, *S, thetas, logL, phi);
 }
 
 // pchip_source_prior_eval: the prior of a source handle at n points (device pointers) -- k_prior_transform of the handle's run-time module
@@ -2527,7 +2586,7 @@ extern "C" int pc_launch_max_rank(const PcState *S, int n, const double *rows, d
 extern "C" int pc_launch_maximise(const PcState *S, int nprob, const double *in, const int *hdr, long long max_iter, double *out, long long *outi, hipStream_t st)
 {
     if (S->D < 1 || S->D > 64 || nprob < 1) return 1;
-    const size_t sh = sizeof(double) * PC_MAX_LDS_DOUBLES(S->D) + pc_quad_lds(S);
+    const size_t sh = sizeof(double) * PC_MAX_LDS_DOUBLES(S->D) + pc_front_lds(S);
     if (!pc_max_lds_fits("k_maximise", sh)) return 1;
     if (sh > 48 * 1024 && !pc_rtc_wanted(S)) pc_need_dyn_lds((const void *)k_maximise<1>, sh);
     PC_LAUNCH((k_maximise<1>), dim3(nprob), dim3(64), sh, st, *S, in, hdr, max_iter, out, outi);

@@ -1,6 +1,6 @@
 // pc_slice_body.inc -- the body of k_slice (pc_sample.hip), included by the one-run kernel and by k_slice_many (several runs in
 // step, blockIdx.y = run) so that both are the same statements on `S`, `batch`, `phi_lds`, `mat_lds`.  Not a header: no include guard.
-    PC_DYN_LDS(smem);                              // (a quadratic-form source: behind its residual blocks -- pc_sample.hip)
+    PC_DYN_LDS(smem);                              // (a quadratic-form source, shared values: behind the form's front block -- pc_sample.hip)
     __builtin_amdgcn_s_setprio(LEAN == 2 ? 0 : 3);  // a chain is one long dependent instruction stream: it goes first on its SIMD
 #if defined(SLICE_DBG) && SLICE_DBG == 2
     const long long kc0 = clock64(), kw0 = wall_clock64();
@@ -691,7 +691,10 @@
             if (s >= nr) continue;
             double *row = S.babies + ((size_t)chain * nr + s) * nT;
             const double *tt = tbuf + (size_t)s * (D + 1);
-#ifdef PCHIP_USER_TERMS
+#ifdef PCHIP_USER_SHARED
+            // (shared values: finish needs the point's shared block, and a lane = baby has none -- pc_slice_phi_lds never sets phi_lds for such a
+            //  handle, its derived parameters are written inside the slice loop, and no branch of the source is compiled here)
+#elif defined(PCHIP_USER_TERMS)
             if (LEAN == 0 && S.like.kind == PC_LIKE_SOURCE) {   // finish(sums, theta) of the baby's kept sums, lane = baby: no walk over the data
                 double phi[PC_SRC_MAX_DERIVED];
 #ifdef PCHIP_USER_SUMS

@@ -107,6 +107,7 @@ extern "C" int pc_launch_bases_t(const PcState *S, unsigned, int, hipStream_t) {
 #endif
 extern "C" int pc_rtc_source_sums(int) { return 0; }      // (pc_slice_phi_lds asks: no handle of the sweep has several sums)
 extern "C" long pc_rtc_source_quad(int) { return 0; }     // (pc_quad_lds asks: no handle of the sweep is a quadratic form)
+extern "C" long pc_rtc_source_shared(int) { return 0; }   // (pc_front_lds asks: no handle of the sweep has shared values)
 extern "C" void pc_abi_set_last_error(const char *msg) { if (msg) { rec::line += " | error: "; rec::line += msg; } }
 
 int main(int argc, char **argv)

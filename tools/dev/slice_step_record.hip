@@ -45,6 +45,7 @@ extern "C" int pc_rtc_launch(const PcState *, const char *expr, dim3 grid, dim3 
 extern "C" long pc_rtc_source_terms(int id) { return id == 2 || id == 3 ? 100 : 0; }
 extern "C" int pc_rtc_source_sums(int id) { return id == 3 ? 5 : 0; }
 extern "C" long pc_rtc_source_quad(int) { return 0; }     // (pc_quad_lds asks: no handle here is a quadratic form)
+extern "C" long pc_rtc_source_shared(int) { return 0; }   // (pc_front_lds asks: no handle here has shared values)
 extern "C" int pc_launch_bases_t(const PcState *S, unsigned, int, hipStream_t) { return S->D < 2; }
 extern "C" void pc_abi_set_last_error(const char *msg) { if (msg) rec::error = msg; }
 
