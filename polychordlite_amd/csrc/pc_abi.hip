@@ -57,14 +57,16 @@ void halt_or_return(const std::string &msg)
     G.last_error = msg;
 }
 // the form of a device source handle, for the run header
-std::string source_form(int h)
+std::string source_form(const PcSourceForm &f)
 {
-    const std::string shared = pc_rtc_source_shared(h) > 0 ? ", " + std::to_string(pc_rtc_source_shared(h)) + " shared values" : "";
-    if (pc_rtc_source_quad(h) > 0) return "quadratic form, " + std::to_string(pc_rtc_source_quad(h)) + " residuals" + shared;
-    if (pc_rtc_source_sums(h) > 0) return "terms form, " + std::to_string(pc_rtc_source_terms(h)) + " terms, " + std::to_string(pc_rtc_source_sums(h)) + " sums" + shared;
-    if (pc_rtc_source_terms(h) > 0) return "terms form, " + std::to_string(pc_rtc_source_terms(h)) + " terms" + shared;
+    const std::string shared = f.nshared > 0 ? ", " + std::to_string(f.nshared) + " shared values" : "";
+    if (f.nquad > 0) return "quadratic form, " + std::to_string(f.nquad) + " residuals" + shared;
+    if (f.nsums > 0) return "terms form, " + std::to_string(f.nterms) + " terms, " + std::to_string(f.nsums) + " sums" + shared;
+    if (f.nterms > 0) return "terms form, " + std::to_string(f.nterms) + " terms" + shared;
     return "plain form";
 }
+// a device source handle that exists and was not destroyed: its form in *f
+bool source_alive(int h, PcSourceForm *f) { return pc_rtc_source_form(h, f) == 0 && f->alive; }
 
 // Fortran E24.15E3:  "  0.626931681801488E-001"
 std::string fmt_e24(double v)
@@ -492,8 +494,8 @@ void polychord_hip_table_prior(double *cube, double *theta, int D)
 // ARE pchip_source_eval / pchip_source_prior_eval at one point (the same bits): one launch a call, for single evaluations.
 int polychord_hip_set_source(int handle)
 {
-    const double *h = nullptr; long long n = 0;
-    if (handle != 0 && pc_rtc_source_data(handle, &h, &n)) {
+    PcSourceForm f;
+    if (handle != 0 && !source_alive(handle, &f)) {
         G.last_error = "polychord_hip_set_source: device source handle " + std::to_string(handle) + " does not exist";
         return 1;
     }
@@ -767,6 +769,7 @@ static void c_interface_impl(
     if (write_resume) s.resume_write = resume_path.c_str();
     if (read_resume) s.resume_read = resume_path.c_str();
     pchip_like L{}; pchip_prior P{};
+    PcSourceForm src_form{};      // (a device source behind the likelihood: what its handle is, asked once)
     if (loglikelihood == polychord_hip_gaussian) { L.kind = PCHIP_LIKE_GAUSSIAN; L.mu = G.g_mu; L.sigma = G.g_sigma; }
     else if (loglikelihood == polychord_hip_rastrigin) L.kind = PCHIP_LIKE_RASTRIGIN;
     else if (loglikelihood == polychord_hip_twin_gaussian) { L.kind = PCHIP_LIKE_TWIN_GAUSSIAN; L.sigma = G.g_sigma; }
@@ -776,8 +779,7 @@ static void c_interface_impl(
     } else if (loglikelihood == polychord_hip_source_loglike) {
         // a device source behind the reference's signature: the handle knows its form (plain, terms, several sums, quadratic)
         if (!G.source) halt_program("polychord_hip: polychord_hip_set_source was not called");
-        const double *h = nullptr; long long n = 0;
-        if (pc_rtc_source_data(G.source, &h, &n)) halt_program(("polychord_hip: device source handle " + std::to_string(G.source) + " does not exist").c_str());
+        if (!source_alive(G.source, &src_form)) halt_program(("polychord_hip: device source handle " + std::to_string(G.source) + " does not exist").c_str());
         L.kind = PCHIP_LIKE_SOURCE; L.source = G.source; L.fn = loglikelihood;
     } else { L.kind = PCHIP_LIKE_CALLBACK; L.fn = loglikelihood; }
     const int source_handle = L.kind == PCHIP_LIKE_SOURCE ? L.source : 0;
@@ -785,7 +787,7 @@ static void c_interface_impl(
         // the handle's own pchip_prior_param, inside the sampling kernels (the engine's wording where the pair does not fit)
         if (L.kind != PCHIP_LIKE_SOURCE)
             halt_program("polychord_hip: prior.kind = 3 (source prior) needs a device source likelihood of the same handle: pass polychord_hip_source_loglike as the likelihood (a prior-only source is not supported)");
-        if (!pc_rtc_source_has_prior(L.source))
+        if (!src_form.has_prior)
             halt_program(("polychord_hip: prior.kind = 3 (source prior): device source handle " + std::to_string(L.source) + " defines no pchip_prior_param -- make it with pchip_source_create_prior").c_str());
         P.kind = PCHIP_PRIOR_SOURCE; P.fn = prior;
     } else if (prior == polychord_hip_uniform_prior) {
@@ -856,11 +858,11 @@ static void c_interface_impl(
                         s.epoch_discard ? "all discarded (epoch_discard = 1: the reference farm's rule, nested_sampling.F90:313)"
                                         : "only those seeded in the cluster that ended are lost (epoch_discard = 0, this engine's default; option \"epoch_discard\" = 1: the reference farm's rule)");
         if (L.kind == PCHIP_LIKE_SOURCE)
-            std::printf("likelihood: device source handle %d (%s) evaluated on the device, inside the sampling kernels\n", source_handle, source_form(source_handle).c_str());
+            std::printf("likelihood: device source handle %d (%s) evaluated on the device, inside the sampling kernels\n", source_handle, source_form(src_form).c_str());
         else if (batch_guard.ev)
-            std::printf("likelihood: device source handle %d (%s)\nsource likelihood evaluated on the device in batches; prior on the host\n", source_handle, source_form(source_handle).c_str());
+            std::printf("likelihood: device source handle %d (%s)\nsource likelihood evaluated on the device in batches; prior on the host\n", source_handle, source_form(src_form).c_str());
         else if (source_handle)
-            std::printf("likelihood: device source handle %d (%s); evaluations through the caller's batch callback\n", source_handle, source_form(source_handle).c_str());
+            std::printf("likelihood: device source handle %d (%s); evaluations through the caller's batch callback\n", source_handle, source_form(src_form).c_str());
         if (table_on_device) std::printf("prior table evaluated on the device, inside the sampling kernels (option \"device_prior\" = 0: on the host)\n");
         if (write_resume || read_resume) std::printf("Resume file: %s/%s.resume\n", base.c_str(), root.c_str());
         std::printf("\nnum_repeats:");

@@ -542,18 +542,18 @@ struct Engine {
         S.like.invcov = nullptr; S.like.mean = nullptr;
         S.src_id = 0; S.src_pad = 0; S.src_data = nullptr; S.src_ndata = 0;
         if (like.kind == PC_LIKE_SOURCE) {         // a user's device source (pc_rtc.hip): its data block goes up with the run
-            const double *h = nullptr; long long n = 0;
-            if (pc_rtc_source_data(like.source, &h, &n)) engine_fail(PC_RC_SETTINGS, "device source handle %d does not exist", like.source);
+            PcSourceForm f;
+            const auto hold = pc_rtc_source_hold(like.source, &f);      // (kept until the block is in the pinned staging buffer: upload)
+            if (!hold) engine_fail(PC_RC_SETTINGS, "device source handle %d does not exist", like.source);
             if (nDer > PC_SRC_MAX_DERIVED) engine_fail(PC_RC_SETTINGS, "a device source likelihood writes at most %d derived parameters, not %d", PC_SRC_MAX_DERIVED, nDer);
             if (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE && prior.kind != PCHIP_PRIOR_SOURCE)
                 engine_fail(PC_RC_SETTINGS, "a device source likelihood needs a device prior (the uniform box, a table or its own source prior: prior.kind 1, 2 or 3), not a host-callback prior");
-            if (prior.kind == PCHIP_PRIOR_SOURCE && !pc_rtc_source_has_prior(like.source))
+            if (prior.kind == PCHIP_PRIOR_SOURCE && !f.has_prior)
                 engine_fail(PC_RC_SETTINGS, "prior.kind = 3 (source prior): device source handle %d defines no pchip_prior_param -- make it with pchip_source_create_prior", like.source);
             S.src_id = like.source;
-            src_terms = pc_rtc_source_terms(like.source) > 0;
+            src_terms = f.nterms > 0;
             // (a quadratic form: its precision matrix goes up behind the user's data, in the same block -- the kernels find it at src_data + src_ndata)
-            const long long nup = n + pc_rtc_source_tail(like.source);
-            if (nup > 0) { d_src = blocks.dev<double>((size_t)nup); upload(d_src, h, sizeof(double) * (size_t)nup); S.src_data = d_src; S.src_ndata = n; }
+            if (!hold->empty()) { d_src = blocks.dev<double>(hold->size()); upload(d_src, hold->data(), sizeof(double) * hold->size()); S.src_data = d_src; S.src_ndata = f.ndata; }
         }
         // a source prior is the handle's own function, inside the sampling kernels: there is no host function for callback mode to call
         if (prior.kind == PCHIP_PRIOR_SOURCE && like.kind != PC_LIKE_SOURCE)
@@ -2531,154 +2531,6 @@ int pchip_update_factors(const pchip_settings *s, int ncluster, int nlive, const
     }
     E.destroy();
     return rc;
-}
-
-// the prior of a source handle alone at n hypercube points: the handle's run-time module, k_prior_transform, one wavefront a point
-int pchip_source_prior_eval(int handle, const double *cubes, long n, int nDims, double *thetas)
-{
-    const double *h = nullptr; long long nd = 0;
-    if (pc_rtc_source_data(handle, &h, &nd)) { pc_abi_set_last_error(("pchip_source_prior_eval: device source handle " + std::to_string(handle) + " does not exist").c_str()); return 1; }
-    if (!pc_rtc_source_has_prior(handle)) { pc_abi_set_last_error(("pchip_source_prior_eval: device source handle " + std::to_string(handle) + " defines no pchip_prior_param (pchip_source_create_prior makes one that does)").c_str()); return 1; }
-    if (!cubes || !thetas || n < 1 || n > 0x7fffffffL || nDims < 1) { pc_abi_set_last_error("pchip_source_prior_eval: n >= 1 points, nDims >= 1, arrays for cube and theta"); return 1; }
-    if (nDims > 256) return 3;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
-    double *d_src = nullptr, *d_c = nullptr, *d_t = nullptr;
-    const size_t nb = sizeof(double) * (size_t)n * nDims;
-    int rc = 2;
-    pc_abi_set_last_error(nullptr);
-    if ((nd == 0 || (hipMalloc(&d_src, sizeof(double) * (size_t)nd) == hipSuccess && hipMemcpy(d_src, h, sizeof(double) * (size_t)nd, hipMemcpyHostToDevice) == hipSuccess)) &&
-        hipMalloc(&d_c, nb) == hipSuccess && hipMalloc(&d_t, nb) == hipSuccess && hipMemcpy(d_c, cubes, nb, hipMemcpyHostToDevice) == hipSuccess) {
-        PcState S;
-        std::memset(&S, 0, sizeof(S));
-        S.D = nDims; S.like.kind = PC_LIKE_SOURCE; S.prior.kind = PCHIP_PRIOR_SOURCE; S.src_id = handle; S.src_data = d_src; S.src_ndata = nd;
-        if (pc_launch_source_prior_eval(&S, (int)n, d_c, d_t, nullptr)) { rc = 1; pc_abi_set_last_error(pc_rtc_error() ? pc_rtc_error() : "pchip_source_prior_eval: the launch failed"); }
-        else if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(thetas, d_t, nb, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
-    }
-    if (rc == 2) (void)hipGetLastError();
-    (void)hipFree(d_src); (void)hipFree(d_c); (void)hipFree(d_t);
-    return rc;
-}
-
-// a source likelihood alone at n points (either form of source): the handle's run-time module, k_source_eval, one wavefront a point
-int pchip_source_eval(int handle, const double *thetas, long n, int nDims, int nDerived, double *logL, double *phi)
-{
-    const double *h = nullptr; long long nd = 0;
-    if (pc_rtc_source_data(handle, &h, &nd)) { pc_abi_set_last_error(("pchip_source_eval: device source handle " + std::to_string(handle) + " does not exist").c_str()); return 1; }
-    if (!thetas || !logL || n < 1 || n > 0x7fffffffL || nDims < 1 || nDerived < 0 || (nDerived > 0 && !phi)) {
-        pc_abi_set_last_error("pchip_source_eval: n >= 1 points, nDims >= 1, arrays for theta, logL and (nDerived > 0) phi"); return 1;
-    }
-    if (nDerived > PC_SRC_MAX_DERIVED) { pc_abi_set_last_error(("pchip_source_eval: a device source likelihood writes at most " + std::to_string(PC_SRC_MAX_DERIVED) + " derived parameters").c_str()); return 1; }
-    if (nDims > 256) return 3;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
-    double *d_src = nullptr, *d_t = nullptr, *d_l = nullptr, *d_p = nullptr;
-    const size_t nt = sizeof(double) * (size_t)n * nDims, np = sizeof(double) * (size_t)n * (nDerived > 0 ? nDerived : 1);
-    const long long nup = nd + pc_rtc_source_tail(handle);      // (a quadratic form: its precision matrix behind the user's data, as a run uploads it)
-    int rc = 2;
-    pc_abi_set_last_error(nullptr);
-    if ((nup == 0 || (hipMalloc(&d_src, sizeof(double) * (size_t)nup) == hipSuccess && hipMemcpy(d_src, h, sizeof(double) * (size_t)nup, hipMemcpyHostToDevice) == hipSuccess)) &&
-        hipMalloc(&d_t, nt) == hipSuccess && hipMalloc(&d_l, sizeof(double) * (size_t)n) == hipSuccess && hipMalloc(&d_p, np) == hipSuccess &&
-        hipMemcpy(d_t, thetas, nt, hipMemcpyHostToDevice) == hipSuccess) {
-        PcState S;
-        std::memset(&S, 0, sizeof(S));
-        S.D = nDims; S.nDer = nDerived; S.like.kind = PC_LIKE_SOURCE; S.src_id = handle; S.src_data = d_src; S.src_ndata = nd;
-        if (pc_launch_source_eval(&S, (int)n, d_t, d_l, d_p, nullptr)) { rc = 1; pc_abi_set_last_error(pc_rtc_error() ? pc_rtc_error() : "pchip_source_eval: the launch failed"); }
-        else if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(logL, d_l, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
-                 (nDerived == 0 || hipMemcpy(phi, d_p, np, hipMemcpyDeviceToHost) == hipSuccess)) rc = 0;
-    }
-    if (rc == 2) (void)hipGetLastError();
-    (void)hipFree(d_src); (void)hipFree(d_t); (void)hipFree(d_l); (void)hipFree(d_p);
-    return rc;
-}
-
-// ---- a source likelihood under a HOST prior, for the PolyChord-interface doors (pc_abi.hip) ------------------------------------------
-// pchip_run refuses that pair (a source has no host function of its own to run callback mode through); the doors run callback mode with
-// polychord_hip_source_loglike and register this evaluator as the batch callback for the length of their call: the parked proposals of a
-// round get the host prior one by one, on the calling thread, and ONE launch of k_source_eval for all of them -- the bits of
-// pchip_source_eval at each point (one wavefront a point, whatever n).  Opened once per run: the handle's data block (a quadratic form's
-// matrix behind it) stays on the device, the theta / logL / phi buffers grow on demand, the copies and the launch go through a stream of
-// its own and only that stream is waited for.
-struct PcSourceBatch {
-    int handle = 0, D = 0, nDer = 0;
-    polychord_prior_fn prior = nullptr;
-    hipStream_t st = nullptr;
-    double *d_src = nullptr; long long nd = 0;
-    double *d_buf = nullptr, *h_buf = nullptr;      // [cap] rows of theta (D) | logL (1) | phi (max(1, nDer)): device, and pinned host
-    long cap = 0;
-    bool failed = false;
-    size_t row() const { return (size_t)D + 1 + (size_t)(nDer > 0 ? nDer : 1); }
-    bool grow(long n)
-    {
-        if (n <= cap) return true;
-        const long want = std::max(n, 2 * cap);
-        (void)hipFree(d_buf); (void)hipHostFree(h_buf); d_buf = h_buf = nullptr; cap = 0;
-        if (hipMalloc(&d_buf, sizeof(double) * row() * (size_t)want) != hipSuccess || hipHostMalloc(&h_buf, sizeof(double) * row() * (size_t)want) != hipSuccess) return false;
-        cap = want;
-        return true;
-    }
-};
-
-void *pc_source_batch_open(int handle, int device, int nDims, int nDerived, polychord_prior_fn prior)
-{
-    const double *h = nullptr; long long nd = 0;
-    if (pc_rtc_source_data(handle, &h, &nd)) { pc_abi_set_last_error(("device source handle " + std::to_string(handle) + " does not exist").c_str()); return nullptr; }
-    if (!prior || nDims < 1 || nDims > 256 || nDerived < 0 || nDerived > PC_SRC_MAX_DERIVED) { pc_abi_set_last_error("a source likelihood under a host prior: a prior function, 1 <= nDims <= 256, 0 <= nDerived <= 32"); return nullptr; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); pc_abi_set_last_error("no HIP device available -- this engine has no CPU path"); return nullptr; }
-    PcSourceBatch *b = new PcSourceBatch;
-    b->handle = handle; b->D = nDims; b->nDer = nDerived; b->prior = prior; b->nd = nd;
-    const long long nup = nd + pc_rtc_source_tail(handle);
-    bool ok = hipSetDevice(device >= 0 ? device % ndev : 0) == hipSuccess && hipStreamCreate(&b->st) == hipSuccess;
-    if (ok && nup > 0)
-        ok = hipMalloc(&b->d_src, sizeof(double) * (size_t)nup) == hipSuccess &&
-             hipMemcpyAsync(b->d_src, h, sizeof(double) * (size_t)nup, hipMemcpyHostToDevice, b->st) == hipSuccess && hipStreamSynchronize(b->st) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); pc_abi_set_last_error("a source likelihood under a host prior: the stream or the data block could not be set up on the device"); pc_source_batch_close(b); return nullptr; }
-    return b;
-}
-
-void pc_source_batch_close(void *user)
-{
-    PcSourceBatch *b = (PcSourceBatch *)user;
-    if (!b) return;
-    if (b->st) { (void)hipStreamSynchronize(b->st); (void)hipStreamDestroy(b->st); }
-    (void)hipFree(b->d_src); (void)hipFree(b->d_buf); (void)hipHostFree(b->h_buf);
-    delete b;
-}
-
-// (a polychord_batch_fn: `user` is the evaluator)
-void pc_source_batch_eval(void *user, int n, int nDims, int nDerived, const double *cube, double *theta, double *phi, double *logL)
-{
-    PcSourceBatch *b = (PcSourceBatch *)user;
-    const int D = b->D, nDer = b->nDer, pd = nDer > 0 ? nDer : 1;
-    if (n < 1) return;
-    for (int i = 0; i < n; ++i) b->prior(const_cast<double *>(cube) + (size_t)i * D, theta + (size_t)i * D, D);
-    bool ok = !b->failed && nDims == D && nDerived == nDer && b->grow(n);
-    if (ok) {
-        double *h_t = b->h_buf, *h_l = h_t + (size_t)n * D, *h_p = h_l + n;
-        double *d_t = b->d_buf, *d_l = d_t + (size_t)n * D, *d_p = d_l + n;
-        std::memcpy(h_t, theta, sizeof(double) * (size_t)n * D);
-        PcState S;
-        std::memset(&S, 0, sizeof(S));
-        S.D = D; S.nDer = nDer; S.like.kind = PC_LIKE_SOURCE; S.src_id = b->handle; S.src_data = b->d_src; S.src_ndata = b->nd;
-        ok = hipMemcpyAsync(d_t, h_t, sizeof(double) * (size_t)n * D, hipMemcpyHostToDevice, b->st) == hipSuccess;
-        if (ok && pc_launch_source_eval(&S, n, d_t, d_l, d_p, b->st)) { ok = false; pc_abi_set_last_error(pc_rtc_error() ? pc_rtc_error() : "a source likelihood under a host prior: k_source_eval could not be launched"); }
-        else if (ok) {
-            ok = hipMemcpyAsync(h_l, d_l, sizeof(double) * ((size_t)n + (size_t)n * pd), hipMemcpyDeviceToHost, b->st) == hipSuccess && hipStreamSynchronize(b->st) == hipSuccess;
-            if (!ok) pc_abi_set_last_error((std::string("a source likelihood under a host prior: HIP error ") + hipGetErrorString(hipGetLastError())).c_str());
-        }
-        if (ok) {
-            std::memcpy(logL, h_l, sizeof(double) * (size_t)n);
-            if (nDer > 0) std::memcpy(phi, h_p, sizeof(double) * (size_t)n * nDer);
-        }
-    } else if (!b->failed) pc_abi_set_last_error("a source likelihood under a host prior: the buffers of a round could not be allocated");
-    if (!ok) {      // no value to give: every point invalid, and the run stops at this host boundary (the message stays in polychord_hip_last_error)
-        if (!b->failed && polychord_hip_last_error()) std::fprintf(stderr, "polychord_hip: %s\n", polychord_hip_last_error());
-        b->failed = true;
-        for (int i = 0; i < n; ++i) logL[i] = -1.7976931348623157e308;
-        for (size_t i = 0; i < (size_t)n * pd; ++i) phi[i] = 0.0;
-        polychord_hip_request_stop();
-    }
 }
 
 // the batch callback that is registered now (polychord_hip_set_batch_callback): the doors put theirs in only where the caller has none

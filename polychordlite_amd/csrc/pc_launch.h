@@ -7,49 +7,46 @@
 #include "pc_state.h"
 #include "../../include/polychord_hip.h"
 #include <cstddef>
+#include <memory>
+#include <vector>
 
-// the number of sums of a handle made by pchip_source_create_sums; 0: any other handle, or none (pc_rtc.hip)
-extern "C" int pc_rtc_source_sums(int id);
-// the number of residuals of a handle made by pchip_source_create_quad; 0: any other handle, or none (pc_rtc.hip)
-extern "C" long pc_rtc_source_quad(int id);
-
-// the number of shared values of a handle made by pchip_source_create_shared; 0: any other handle, or none (pc_rtc.hip)
-extern "C" long pc_rtc_source_shared(int id);
+// What a device-source handle is (pc_rtc.hip keeps one per handle ever made, past pchip_source_destroy): the answer to every question the
+// launchers, the engine and the doors have about a handle, asked once with pc_rtc_source_form.  All zero: no source, the plain form.
+struct PcSourceForm {
+    long nterms;                           // > 0: the terms form, the sum's length (a quadratic form: its nres)
+    int nsums;                             // > 0: several sums per evaluation (pchip_source_create_sums)
+    long nquad;                            // > 0: the quadratic form of that many residuals (pchip_source_create_quad): nterms == nquad
+    long nshared;                          // > 0: shared values beside that form (pchip_source_create_shared)
+    int has_prior;                         // the source defines pchip_prior_param as well (pchip_source_create_prior)
+    long long ndata, ntail;                // the user's doubles, and the handle's own behind them in its block (a quadratic form's matrix)
+    int alive;                             // 0: destroyed -- the launch shapes below still hold for a run in flight, nothing new starts on it
+};
 
 // A quadratic-form source keeps the residuals of the point -- of the two ends of a bracket -- in two blocks of nres doubles (an even
 // number each: 16-byte reads) at the FRONT of the dynamic LDS of every kernel that evaluates the likelihood (pc_sample.hip, PC_DYN_LDS):
-// their bytes; 0 for any other state
-static inline size_t pc_quad_lds(const PcState *S)
-{
-    if (S->like.kind != PC_LIKE_SOURCE) return 0;
-    const long n = pc_rtc_source_quad(S->src_id);
-    return n > 0 ? sizeof(double) * 2 * (size_t)((n + 1) & ~1L) : 0;
-}
+// their bytes; 0 for any other form
+static inline size_t pc_quad_lds(const PcSourceForm &f) { return f.nquad > 0 ? sizeof(double) * 2 * (size_t)((f.nquad + 1) & ~1L) : 0; }
 
 // The form's front block of that dynamic LDS: the quadratic form's two residual blocks, if any, then the two blocks of a handle with
 // shared values (pchip_source_create_shared: nshared doubles a point, rounded up to even, for the two ends of a bracket).  Its bytes,
-// which every launcher of a kernel that evaluates the likelihood adds to its own; 0 for any other state
-static inline size_t pc_front_lds(const PcState *S)
-{
-    if (S->like.kind != PC_LIKE_SOURCE) return 0;
-    const long n = pc_rtc_source_shared(S->src_id);
-    return pc_quad_lds(S) + (n > 0 ? sizeof(double) * 2 * (size_t)((n + 1) & ~1L) : 0);
-}
+// which every launcher of a kernel that evaluates the likelihood adds to its own; 0 for any other form
+static inline size_t pc_front_lds(const PcSourceForm &f) { return pc_quad_lds(f) + (f.nshared > 0 ? sizeof(double) * 2 * (size_t)((f.nshared + 1) & ~1L) : 0); }
 
 // k_slice keeps the theta rows of a chain's babies in LDS (its run-time flag phi_lds: derived parameters at the end of the chain, summed
 // in that order) when they fit under 48 KB next to the chain's block; pc_slice_t_ok takes only states where it does
 // (pc_slice_plan's rule, asked by pc_slice_t_ok in another file: inline here, the one definition in this header, so that the library's
-//  exported pc_* names stay what they were).  A source with several sums keeps the sums of every baby beside the rows, [nr][nsums]: the
-// block counts here, and a shape it pushes over the limit writes its derived parameters inside the slice loop like any that does not fit.
+//  exported pc_* names stay what they were).  `f`: the form of the state's source, all zero for a state without one.  A source with several
+// sums keeps the sums of every baby beside the rows, [nr][nsums]: the block counts here, and a shape it pushes over the limit writes its
+// derived parameters inside the slice loop like any that does not fit.
 // The front block of a quadratic form (pc_front_lds) counts in the same way.  A handle with shared values never takes the end-of-chain
 // pass: there finish runs with lane = baby, and a lane has no shared block of its own -- its derived parameters are written inside the
 // slice loop (like_phi_terms fills the point's block again), and its unit does not compile the lane = baby branch.
-static inline int pc_slice_phi_lds(const PcState *S)
+static inline int pc_slice_phi_lds(const PcState *S, const PcSourceForm &f)
 {
     const size_t sh0 = sizeof(double) * ((size_t)S->D + S->nr) + 16, tb = sizeof(double) * (size_t)S->nr * (S->D + 1);
-    const size_t sums = S->like.kind == PC_LIKE_SOURCE ? sizeof(double) * (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0;
-    if (S->like.kind == PC_LIKE_SOURCE && pc_rtc_source_shared(S->src_id) > 0) return 0;
-    return (S->nDer > 0 && sh0 + tb + sums + pc_front_lds(S) <= 48 * 1024) ? 1 : 0;
+    const size_t sums = sizeof(double) * (size_t)S->nr * (size_t)f.nsums;
+    if (f.nshared > 0) return 0;
+    return (S->nDer > 0 && sh0 + tb + sums + pc_front_lds(f) <= 48 * 1024) ? 1 : 0;
 }
 
 extern "C" {
@@ -149,14 +146,9 @@ int pc_launch_final_par_many(const PcManyRec *dR, int R, hipStream_t st);
 // 0: launched; 1: no such kernel (pc_rtc_error has the text)
 int pc_rtc_launch(const PcState *S, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t st, void **args);
 const char *pc_rtc_error(void);
-// 0: a source exists (and its data block, for the engine's upload: *n doubles of the user's, then pc_rtc_source_tail(id) of the handle's own)
-int pc_rtc_source_data(int id, const double **data, long long *n);
-// the doubles behind the user's data in that block (a quadratic form's precision matrix); 0: none, or no such handle
-long long pc_rtc_source_tail(int id);
-// the number of terms of a terms-form handle; 0: the plain form, or no such handle
-long pc_rtc_source_terms(int id);
-// 1: the handle's source defines pchip_prior_param as well (pchip_source_create_prior); 0: it does not, or no such handle
-int pc_rtc_source_has_prior(int id);
+// the form of handle `id` in *f (zeroed first): one lock, one lookup.  0, or non-zero for an id that never existed; a destroyed handle
+// answers what it answered alive, with alive = 0
+int pc_rtc_source_form(int id, PcSourceForm *f);
 // ---- pc_sample.hip -----------------------------------------------------------------------------------------
 // Launchers: 0: launched; 1: not this way (no kernel for this shape, or the run-time module failed: pc_rtc_error).
 // the sampling kernels come from the run-time module (a source likelihood, settings.ablate bit 15)
@@ -226,3 +218,9 @@ int pc_update_fused_grid(const PcState *S, int nph, int deferred);
 int pc_launch_update_fused_many(const PcState *S, const PcManyRec *dR, int R, int nblk_max, int G, int deferred, hipStream_t st);
 
 }   // extern "C"
+
+// ---- pc_rtc.hip, C++ linkage ---------------------------------------------------------------------------------
+// A hold on the data block of a LIVE handle (the user's f->ndata doubles, then f->ntail of the handle's own; its form in *f where f is not
+// NULL), or nullptr: the handle does not exist, or was destroyed.  The block lives as long as any hold does, whatever happens to the
+// handle: a caller keeps its hold until its copy to pinned or device memory has been issued from it.
+std::shared_ptr<const std::vector<double>> pc_rtc_source_hold(int id, PcSourceForm *f);

@@ -19,7 +19,7 @@
 //
 // The quadratic form (pchip_source_create_quad): a Gaussian in data space with a dense precision matrix.  The source defines pchip_residual
 // (the i-th residual, one lane per i) and pchip_logl_finish (the terms form's own, of the finished chi2 = r^T P r); the matrix is copied
-// with the data and lies BEHIND the user's data in the handle's block (pc_rtc_source_tail doubles: a run uploads both in one piece, the
+// with the data and lies BEHIND the user's data in the handle's block (the form's ntail doubles: a run uploads both in one piece, the
 // user's functions see data / ndata as given).  Such a handle is a terms handle of nres terms and one sum to everybody who asks, and its
 // unit gets PCHIP_USER_QUAD in front beside the two #defines of the terms form: pc_sample.hip's walk over the matrix is compiled in
 // their place only.
@@ -32,6 +32,13 @@
 // A prior in the same source (pchip_source_create_prior): the text defines pchip_prior_param (theta[i] from the whole cube, one call per
 // parameter) next to the likelihood of either form; such a handle's unit gets PCHIP_USER_PRIOR in front, and a run with prior.kind =
 // PCHIP_PRIOR_SOURCE takes the table's kernel variants with that function behind the transform's one entry point (pc_sample.hip).
+//
+// What a handle is stands in ONE record, its PcSourceForm (pc_launch.h): the six pchip_source_create* doors fill it through one creation
+// path (pc_rtc_source_create; one ladder of refusals, spec_refusal), the unit of the kernels and the probe unit of the quick compile are
+// generated from it, and everybody else -- the launchers for their LDS, the engine, the doors -- reads it with pc_rtc_source_form, once.
+// pchip_source_destroy releases the text and the data and leaves the form, alive = 0: launch shapes stay right for a run in flight, and
+// whatever starts work (a run's set-up, the eval entry points, a compilation) refuses the handle as one that does not exist.  The data
+// block is handed out as a hold (pc_rtc_source_hold), never as a bare pointer into the registry.
 //
 // settings.ablate bit 15 sends the built-in kinds the same way (a module without a user source): the test that
 // this path is the static kernel.
@@ -88,16 +95,12 @@ struct Hiprtc {
     }
 };
 
+// a registered handle: never changed once it is in the registry (a compilation or an upload on another thread reads it without the lock).
+// pchip_source_destroy puts a record of the form alone in its place -- alive = 0, no text, no data
 struct Source {
+    PcSourceForm form{};                   // what the handle is (pc_launch.h)
     std::string text;                      // the user's source, behind the #define lines of its options
-    std::vector<double> data;
-    long nterms = 0;                       // > 0: the terms form (pchip_logl_term / pchip_logl_finish), the sum's length
-    int nsums = 0;                         // > 0: several sums per evaluation (pchip_logl_terms / pchip_logl_finish_sums; pchip_source_create_sums)
-    long nquad = 0;                        // > 0: the quadratic form (pchip_residual / pchip_logl_finish; pchip_source_create_quad): nterms == nquad, and
-                                           //      the nquad x nquad precision matrix lies in `data` behind the user's ndata doubles
-    long nshared = 0;                      // > 0: shared values (pchip_shared_value; pchip_source_create_shared) beside the form above
-    long long ndata = 0;                   // the user's data: the first ndata doubles of `data`
-    bool has_prior = false;                // the source defines pchip_prior_param as well (pchip_source_create_prior)
+    std::shared_ptr<const std::vector<double>> data;      // the user's form.ndata doubles, then form.ntail of the handle's own (pc_rtc_source_hold)
 };
 
 // a code object of one kernel variant for one architecture: compiled once, loaded on every device of that architecture
@@ -111,7 +114,9 @@ struct Registry {
     std::mutex m;                          // the maps below; never held across a compilation or a module load
     std::mutex cm;                         // hiprtc itself: one compilation at a time
     Hiprtc rtc;
-    std::map<int, std::shared_ptr<Source>> src;
+    // every handle ever made: a destroyed one keeps its form (a few dozen bytes a handle for the life of the process, the accepted cost of
+    // launch shapes that stay right for a run still in flight)
+    std::map<int, std::shared_ptr<const Source>> src;
     int next = 1;
     std::map<std::tuple<int, std::string, std::string>, std::shared_ptr<Code>> code;   // (source, arch, kernel name)
     // (source, device, kernel name) -> function; modules stay loaded for the life of the process (a run may hold the function)
@@ -184,87 +189,57 @@ int compile(const Source *s, const std::string &unit, const std::vector<std::str
 }
 
 // the translation unit of the sampling kernels: the library's kernels (pc_sample.hip declares pchip_loglikelihood under PCHIP_USER_SOURCE),
-// then the user's text -- its macros and pragmas reach nothing of the library's.  A terms handle: its form and its loop bound in front;
-// a handle with several sums: their number in front as well; a quadratic form: PCHIP_USER_QUAD in front as well; shared values: PCHIP_USER_SHARED and their number in front as well; a handle with a prior (pchip_source_create_prior): PCHIP_USER_PRIOR in front.
+// then the user's text -- its macros and pragmas reach nothing of the library's.  In front, what the handle's form says: a prior in the
+// source PCHIP_USER_PRIOR; the terms form PCHIP_USER_TERMS and its loop bound, and beside them the number of sums of a handle with several,
+// PCHIP_USER_QUAD of a quadratic form, PCHIP_USER_SHARED and their number of a handle with shared values
 std::string kernel_unit(const Source *s)
 {
-    const std::string prior = s && s->has_prior ? "#define PCHIP_USER_PRIOR 1\n" : "";
-    const std::string sums = s && s->nsums > 0 ? "#define PCHIP_USER_SUMS 1\n#define PCHIP_SRC_NSUMS " + std::to_string(s->nsums) + "\n" : "";
-    const std::string quad = s && s->nquad > 0 ? "#define PCHIP_USER_QUAD 1\n" : "";
-    const std::string shared = s && s->nshared > 0 ? "#define PCHIP_USER_SHARED 1\n#define PCHIP_SRC_NSHARED " + std::to_string(s->nshared) + "\n" : "";
-    if (s && s->nterms > 0)
-        return prior + sums + quad + shared + "#define PCHIP_USER_SOURCE 1\n#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(s->nterms) + "L\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
-    return s ? prior + "#define PCHIP_USER_SOURCE 1\n#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n"
-             : std::string("#include \"pc_sample.hip\"\n");
+    if (!s) return "#include \"pc_sample.hip\"\n";
+    const PcSourceForm &f = s->form;
+    std::string u = f.has_prior ? "#define PCHIP_USER_PRIOR 1\n" : "";
+    if (f.nterms > 0) {
+        if (f.nsums > 0) u += "#define PCHIP_USER_SUMS 1\n#define PCHIP_SRC_NSUMS " + std::to_string(f.nsums) + "\n";
+        if (f.nquad > 0) u += "#define PCHIP_USER_QUAD 1\n";
+        if (f.nshared > 0) u += "#define PCHIP_USER_SHARED 1\n#define PCHIP_SRC_NSHARED " + std::to_string(f.nshared) + "\n";
+    }
+    u += "#define PCHIP_USER_SOURCE 1\n";
+    if (f.nterms > 0) u += "#define PCHIP_USER_TERMS 1\n#define PCHIP_SRC_NTERMS " + std::to_string(f.nterms) + "L\n";
+    return u + "#include \"pc_sample.hip\"\n#include \"" + USER_NAME + "\"\n";
 }
 
-// the quick compile of pchip_source_create: the user's functions alone behind the same declaration, called from a small kernel
-const char *const PROBE_UNIT =
-    "__device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
-    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, double *out)\n"
-    "{ out[0] = pchip_loglikelihood(th, phi, nDims, nDerived, data, ndata); }\n"
-    "#include \"pchip_user_source.h\"\n";
-// ... and of pchip_source_create_terms: both functions of the terms form (a source that lacks one fails at the link of this unit, by name)
-const char *const PROBE_UNIT_TERMS =
-    "__device__ double pchip_logl_term(const double *theta, int nDims, const double *data, long ndata, long i);\n"
-    "__device__ double pchip_logl_finish(double sum, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
-    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
-    "{ out[0] = pchip_logl_finish(pchip_logl_term(th, nDims, data, ndata, i), th, phi, nDims, nDerived, data, ndata); }\n"
-    "#include \"pchip_user_source.h\"\n";
-// ... and of pchip_source_create_sums (behind a #define of PCHIP_SRC_NSUMS): one call of the terms, the finish of what it wrote
-const char *const PROBE_UNIT_SUMS =
-    "__device__ void pchip_logl_terms(const double *theta, int nDims, const double *data, long ndata, long i, double *t);\n"
-    "__device__ double pchip_logl_finish_sums(const double *sums, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
-    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
-    "{ double t[PCHIP_SRC_NSUMS]; pchip_logl_terms(th, nDims, data, ndata, i, t); out[0] = pchip_logl_finish_sums(t, th, phi, nDims, nDerived, data, ndata); }\n"
-    "#include \"pchip_user_source.h\"\n";
-// ... and of pchip_source_create_quad: one residual, the finish of it
-const char *const PROBE_UNIT_QUAD =
-    "__device__ double pchip_residual(const double *theta, int nDims, const double *data, long ndata, long i);\n"
-    "__device__ double pchip_logl_finish(double chi2, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
-    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
-    "{ out[0] = pchip_logl_finish(pchip_residual(th, nDims, data, ndata, i), th, phi, nDims, nDerived, data, ndata); }\n"
-    "#include \"pchip_user_source.h\"\n";
-// ... and of pchip_source_create_shared: the probe of the handle's form with one shared value computed and the block passed on -- the
-// overloads with `shared` behind theta are the only ones declared, so a source that has only the others fails at the link, by name
-const char *const PROBE_SHARED_DECL =
-    "__device__ double pchip_shared_value(const double *theta, int nDims, const double *data, long ndata, long k);\n";
-const char *const PROBE_SHARED_HEAD =
-    "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, const double *data, long ndata, long i, double *out)\n"
-    "{ double sh[2]; sh[0] = pchip_shared_value(th, nDims, data, ndata, i); ";
-const char *const PROBE_UNIT_TERMS_SHARED =
-    "__device__ double pchip_logl_term(const double *theta, const double *shared, int nDims, const double *data, long ndata, long i);\n"
-    "__device__ double pchip_logl_finish(double sum, const double *theta, const double *shared, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
-    "%HEAD%out[0] = pchip_logl_finish(pchip_logl_term(th, sh, nDims, data, ndata, i), th, sh, phi, nDims, nDerived, data, ndata); }\n"
-    "#include \"pchip_user_source.h\"\n";
-const char *const PROBE_UNIT_SUMS_SHARED =
-    "__device__ void pchip_logl_terms(const double *theta, const double *shared, int nDims, const double *data, long ndata, long i, double *t);\n"
-    "__device__ double pchip_logl_finish_sums(const double *sums, const double *theta, const double *shared, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
-    "%HEAD%double t[PCHIP_SRC_NSUMS]; pchip_logl_terms(th, sh, nDims, data, ndata, i, t); out[0] = pchip_logl_finish_sums(t, th, sh, phi, nDims, nDerived, data, ndata); }\n"
-    "#include \"pchip_user_source.h\"\n";
-const char *const PROBE_UNIT_QUAD_SHARED =
-    "__device__ double pchip_residual(const double *theta, const double *shared, int nDims, const double *data, long ndata, long i);\n"
-    "__device__ double pchip_logl_finish(double chi2, const double *theta, const double *shared, double *phi, int nDims, int nDerived, const double *data, long ndata);\n"
-    "%HEAD%out[0] = pchip_logl_finish(pchip_residual(th, sh, nDims, data, ndata, i), th, sh, phi, nDims, nDerived, data, ndata); }\n"
-    "#include \"pchip_user_source.h\"\n";
-std::string probe_unit_shared(int nsums, bool quad)
+// The quick compile of pchip_source_create and its kin: the user's functions alone, declared with the signatures of the handle's form and
+// called once each from a small kernel -- a source that lacks one fails at the link of this unit, by that function's name.  The per-item
+// function of the form (pchip_logl_term, pchip_logl_terms, pchip_residual) and its finish take `const double *shared` behind theta where the
+// handle has shared values: those overloads are then the only ones declared.  The user's text comes last, behind its own `#line 1`.
+std::string probe_unit(const PcSourceForm &f)
 {
-    std::string u = quad ? PROBE_UNIT_QUAD_SHARED : (nsums > 0 ? PROBE_UNIT_SUMS_SHARED : PROBE_UNIT_TERMS_SHARED);
-    u.replace(u.find("%HEAD%"), 6, PROBE_SHARED_HEAD);
-    return (nsums > 0 ? "#define PCHIP_SRC_NSUMS " + std::to_string(nsums) + "\n" : std::string()) + PROBE_SHARED_DECL + u;
-}
-
-// ... and of pchip_source_create_prior: the probe of the handle's form, then pchip_prior_param behind its declaration, called as well
-const char *const PROBE_PRIOR_DECL =
-    "__device__ double pchip_prior_param(const double *cube, int i, int nDims, const double *data, long ndata);\n";
-const char *const PROBE_PRIOR_CALL = "out[0] += pchip_prior_param(th, 0, nDims, data, ndata); }\n";
-std::string probe_unit(long nterms, int nsums, bool quad, bool prior, bool shared)
-{
-    std::string u = shared ? probe_unit_shared(nsums, quad) : quad ? std::string(PROBE_UNIT_QUAD) : nsums > 0 ? "#define PCHIP_SRC_NSUMS " + std::to_string(nsums) + "\n" + PROBE_UNIT_SUMS : std::string(nterms > 0 ? PROBE_UNIT_TERMS : PROBE_UNIT);
-    if (!prior) return u;
-    const size_t close = u.rfind(" }\n");        // the end of pchip_probe's body: the call goes in front of it
-    u.replace(close, 3, std::string(" ") + PROBE_PRIOR_CALL);
-    return PROBE_PRIOR_DECL + u;
+    const std::string D = "const double *data, long ndata", SH = f.nshared > 0 ? "const double *shared, " : "", sh = f.nshared > 0 ? "sh, " : "";
+    std::string decl, body;
+    if (f.nshared > 0) {
+        decl += "__device__ double pchip_shared_value(const double *theta, int nDims, " + D + ", long k);\n";
+        body += "double sh[2]; sh[0] = pchip_shared_value(th, nDims, data, ndata, i); ";
+    }
+    if (f.nterms <= 0) {
+        decl += "__device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, " + D + ");\n";
+        body += "out[0] = pchip_loglikelihood(th, phi, nDims, nDerived, data, ndata);";
+    } else if (f.nsums > 0) {
+        decl += "#define PCHIP_SRC_NSUMS " + std::to_string(f.nsums) + "\n"
+                "__device__ void pchip_logl_terms(const double *theta, " + SH + "int nDims, " + D + ", long i, double *t);\n"
+                "__device__ double pchip_logl_finish_sums(const double *sums, const double *theta, " + SH + "double *phi, int nDims, int nDerived, " + D + ");\n";
+        body += "double t[PCHIP_SRC_NSUMS]; pchip_logl_terms(th, " + sh + "nDims, data, ndata, i, t); "
+                "out[0] = pchip_logl_finish_sums(t, th, " + sh + "phi, nDims, nDerived, data, ndata);";
+    } else {
+        const std::string item = f.nquad > 0 ? "pchip_residual" : "pchip_logl_term";
+        decl += "__device__ double " + item + "(const double *theta, " + SH + "int nDims, " + D + ", long i);\n"
+                "__device__ double pchip_logl_finish(double " + (f.nquad > 0 ? "chi2" : "sum") + ", const double *theta, " + SH + "double *phi, int nDims, int nDerived, " + D + ");\n";
+        body += "out[0] = pchip_logl_finish(" + item + "(th, " + sh + "nDims, data, ndata, i), th, " + sh + "phi, nDims, nDerived, data, ndata);";
+    }
+    if (f.has_prior) {
+        decl += "__device__ double pchip_prior_param(const double *cube, int i, int nDims, " + D + ");\n";
+        body += " out[0] += pchip_prior_param(th, 0, nDims, data, ndata);";
+    }
+    return decl + "__global__ void pchip_probe(const double *th, double *phi, int nDims, int nDerived, " + D + ", long i, double *out)\n{ " + body + " }\n"
+           "#include \"" + USER_NAME + "\"\n";
 }
 
 std::string strip_parens(const char *expr)
@@ -274,23 +249,27 @@ std::string strip_parens(const char *expr)
     return e;
 }
 
+// the live handle `id` (under the registry's lock), or nullptr: never made, or destroyed -- what everything that starts work asks
+std::shared_ptr<const Source> live_source(Registry &G, int id)
+{
+    auto it = G.src.find(id);
+    return it != G.src.end() && it->second->form.alive ? it->second : nullptr;
+}
+std::string no_handle(int id) { return "device source handle " + std::to_string(id) + " does not exist"; }
+
 hipFunction_t get_function(int id, const std::string &expr, std::string &err)
 {
     Registry &G = reg();
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { err = "no HIP device"; return nullptr; }
     const auto key = std::make_tuple(id, dev, expr);
-    std::shared_ptr<Source> s;
+    std::shared_ptr<const Source> s;
     std::string arch;
     {
         std::lock_guard<std::mutex> g(G.m);
         auto it = G.fn.find(key);
-        if (it != G.fn.end()) return it->second;
-        if (id != 0) {
-            auto si = G.src.find(id);
-            if (si == G.src.end()) { err = "device source handle " + std::to_string(id) + " does not exist"; return nullptr; }
-            s = si->second;
-        }
+        if (it != G.fn.end()) return it->second;      // (a destroyed handle's too: a run in flight goes on with what it has)
+        if (id != 0 && !(s = live_source(G, id))) { err = no_handle(id); return nullptr; }
         auto ai = G.arch.find(dev);
         if (ai == G.arch.end()) {
             hipDeviceProp_t pr;
@@ -353,195 +332,149 @@ int pc_rtc_launch(const PcState *S, const char *expr, dim3 grid, dim3 block, siz
 }
 const char *pc_rtc_error(void) { return t_err.empty() ? nullptr : t_err.c_str(); }
 
-// a source exists (and its data block, for the engine's upload: *n of the user's doubles, pc_rtc_source_tail(id) of the handle's own behind them)
-int pc_rtc_source_data(int id, const double **data, long long *n)
+// the form of handle `id` in *f (zeroed first): one lock, one lookup.  0, or non-zero for an id that never existed; a destroyed handle
+// answers what it answered alive, with alive = 0
+int pc_rtc_source_form(int id, PcSourceForm *f)
 {
     Registry &G = reg();
     std::lock_guard<std::mutex> g(G.m);
     auto it = G.src.find(id);
-    if (it == G.src.end()) return 1;
-    *data = it->second->data.empty() ? nullptr : it->second->data.data();
-    *n = it->second->ndata;
-    return 0;
-}
-
-// the doubles a handle keeps in its block BEHIND the user's data (a quadratic form: its precision matrix, nres x nres); 0: none, or no such handle
-long long pc_rtc_source_tail(int id)
-{
-    Registry &G = reg();
-    std::lock_guard<std::mutex> g(G.m);
-    auto it = G.src.find(id);
-    return it == G.src.end() ? 0 : (long long)it->second->data.size() - it->second->ndata;
-}
-
-// the number of terms of a terms-form handle; 0: the plain form, or no such handle
-long pc_rtc_source_terms(int id)
-{
-    Registry &G = reg();
-    std::lock_guard<std::mutex> g(G.m);
-    auto it = G.src.find(id);
-    return it == G.src.end() ? 0 : it->second->nterms;
-}
-
-// the number of sums of a handle made by pchip_source_create_sums; 0: any other handle, or none
-int pc_rtc_source_sums(int id)
-{
-    Registry &G = reg();
-    std::lock_guard<std::mutex> g(G.m);
-    auto it = G.src.find(id);
-    return it == G.src.end() ? 0 : it->second->nsums;
-}
-
-// the number of residuals of a handle made by pchip_source_create_quad; 0: any other handle, or none
-long pc_rtc_source_quad(int id)
-{
-    Registry &G = reg();
-    std::lock_guard<std::mutex> g(G.m);
-    auto it = G.src.find(id);
-    return it == G.src.end() ? 0 : it->second->nquad;
-}
-
-// the number of shared values of a handle made by pchip_source_create_shared; 0: any other handle, or none
-long pc_rtc_source_shared(int id)
-{
-    Registry &G = reg();
-    std::lock_guard<std::mutex> g(G.m);
-    auto it = G.src.find(id);
-    return it == G.src.end() ? 0 : it->second->nshared;
-}
-
-int pc_rtc_source_has_prior(int id)
-{
-    Registry &G = reg();
-    std::lock_guard<std::mutex> g(G.m);
-    auto it = G.src.find(id);
-    return it != G.src.end() && it->second->has_prior ? 1 : 0;
-}
-
-// pchip_source_create[_terms | _sums | _quad | _prior | _shared]: registers the source and compiles the user's functions alone (a syntax error surfaces here, with the log).
-// nterms > 0: the terms form, of nsums sums where nsums > 0; precision != NULL: the quadratic form of nterms residuals, its matrix copied
-// behind the data; nshared > 0: shared values beside that form.  Returns the handle (> 0), or -1 with the compiler's log in `log`.
-int pc_rtc_source_create(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums, bool prior, std::string *log,
-                         const double *precision, long nshared = 0)
-{
-    if (!source) { *log = "pchip_source_create: no source"; return -1; }
-    if (ndata < 0 || (ndata > 0 && !data)) { *log = "pchip_source_create: ndata > 0 needs a data block"; return -1; }
-    std::string bad;
-    const std::string defs = options_to_defines(options, &bad);
-    if (!bad.empty()) { *log = "pchip_source_create: option " + bad + " -- only -DNAME[=VALUE] and -UNAME are passed on"; return -1; }
-    auto s = std::make_shared<Source>();
-    s->text = defs + "#line 1\n" + source;
-    if (ndata > 0) s->data.assign(data, data + ndata);
-    s->ndata = ndata;
-    if (precision) { s->data.insert(s->data.end(), precision, precision + (size_t)nterms * (size_t)nterms); s->nquad = nterms; }
-    s->nterms = nterms; s->nsums = nsums; s->has_prior = prior; s->nshared = nshared;
-    std::string arch = "gfx950";
-    int dev = 0, ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&dev) == hipSuccess) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) == hipSuccess) arch = pr.gcnArchName;
-    }
-    (void)hipGetLastError();
-    std::vector<char> code; std::vector<std::string> lowered;
-    if (compile(s.get(), probe_unit(nterms, nsums, precision != nullptr, prior, nshared > 0), { "pchip_probe" }, arch, code, lowered, *log)) return -1;
-    Registry &G = reg();
-    std::lock_guard<std::mutex> g(G.m);
-    const int id = G.next++;
-    G.src[id] = s;
-    return id;
+    *f = it == G.src.end() ? PcSourceForm{} : it->second->form;
+    return it == G.src.end();
 }
 
 }  // extern "C"
 
+// a hold on the data block of a live handle (pc_launch.h), or nullptr: no such handle, or destroyed
+std::shared_ptr<const std::vector<double>> pc_rtc_source_hold(int id, PcSourceForm *f)
+{
+    Registry &G = reg();
+    std::lock_guard<std::mutex> g(G.m);
+    const std::shared_ptr<const Source> s = live_source(G, id);
+    if (s && f) *f = s->form;
+    return s ? s->data : nullptr;
+}
+
 // ---- C engine API ---------------------------------------------------------------------------------------------------------------------
+namespace {
 
-extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata)
+// what one of the six pchip_source_create* doors was asked for: the door, the text, the data, and the fields of the form it takes
+struct PcSourceSpec {
+    enum Door { PLAIN, TERMS, PRIOR, SUMS, QUAD, SHARED } door;
+    const char *source, *options; const double *data; long ndata;
+    long nterms = 0; int nsums = 0; long nres = 0; const double *precision = nullptr; long nshared = 0; bool prior = false;
+};
+
+// why a spec is refused, in its door's name and words ("": it is not) -- every refusal before any device call; *defs: the options as #define lines
+std::string spec_refusal(const PcSourceSpec &c, std::string *defs)
 {
-    std::string log;
-    const int id = pc_rtc_source_create(source, options, data, ndata, 0, 0, false, &log, nullptr);
-    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
-    return id;
+    static const char *const names[] = { "pchip_source_create", "pchip_source_create_terms", "pchip_source_create_prior", "pchip_source_create_sums",
+                                         "pchip_source_create_quad", "pchip_source_create_shared" };
+    const std::string me = std::string(names[c.door]) + ": ";
+    auto says = [&](const char *field, long v, const std::string &rule) { return me + field + " = " + std::to_string(v) + " -- " + rule; };
+    const std::string sums_range = "1 <= nsums <= " + std::to_string(PCHIP_SOURCE_MAX_SUMS) + " (PCHIP_SOURCE_MAX_SUMS)";
+    const std::string res_range = "1 <= nres <= " + std::to_string(PCHIP_SOURCE_MAX_RES) + " (PCHIP_SOURCE_MAX_RES)";
+    const std::string no_matrix = me + "precision == NULL -- the nres x nres matrix of the quadratic form (host, row-major)";
+    const int d = c.door;
+    if (d == PcSourceSpec::TERMS && c.nterms < 1) return says("nterms", c.nterms, "the sum needs at least one term (nterms >= 1)");
+    if (d == PcSourceSpec::PRIOR && c.nterms < 0) return says("nterms", c.nterms, "0 (the plain form) or the number of terms (nterms >= 1)");
+    if (d == PcSourceSpec::SUMS && c.nterms < 1) return says("nterms", c.nterms, "the sums need at least one term (nterms >= 1)");
+    if (d == PcSourceSpec::SUMS && (c.nsums < 1 || c.nsums > PCHIP_SOURCE_MAX_SUMS)) return says("nsums", c.nsums, sums_range);
+    if (d == PcSourceSpec::QUAD && (c.nres < 1 || c.nres > PCHIP_SOURCE_MAX_RES)) return says("nres", c.nres, res_range);
+    if (d == PcSourceSpec::QUAD && !c.precision) return no_matrix;
+    if (d == PcSourceSpec::SHARED) {      // beside one of the three wave-parallel forms: nres > 0 the quadratic form, else nterms >= 1 terms in one sum (nsums == 0) or in nsums
+        if (c.nshared < 1 || c.nshared > PCHIP_SOURCE_MAX_SHARED)
+            return says("nshared", c.nshared, "1 <= nshared <= " + std::to_string(PCHIP_SOURCE_MAX_SHARED) + " (PCHIP_SOURCE_MAX_SHARED)");
+        if (c.nres < 0 || c.nres > PCHIP_SOURCE_MAX_RES) return says("nres", c.nres, "0, or the quadratic form with " + res_range);
+        if (c.nres > 0 && (c.nterms != 0 || c.nsums != 0))
+            return me + "nres = " + std::to_string(c.nres) + " with nterms = " + std::to_string(c.nterms) + ", nsums = " + std::to_string(c.nsums) +
+                   " -- one form a handle: the quadratic form (nres > 0) takes nterms == 0 and nsums == 0";
+        if (c.nres > 0 && !c.precision) return no_matrix;
+        if (c.nres == 0 && c.precision) return me + "precision != NULL with nres = 0 -- the matrix belongs to the quadratic form (nres > 0)";
+        if (c.nres == 0 && c.nterms < 1) return says("nterms", c.nterms, "the sum needs at least one term (nterms >= 1; a plain likelihood with shared values is nterms = 1)");
+        if (c.nres == 0 && (c.nsums < 0 || c.nsums > PCHIP_SOURCE_MAX_SUMS)) return says("nsums", c.nsums, "0 (one sum), or " + sums_range);
+    }
+    // what every door asks, in the first one's name
+    if (!c.source) return "pchip_source_create: no source";
+    if (c.ndata < 0 || (c.ndata > 0 && !c.data)) return "pchip_source_create: ndata > 0 needs a data block";
+    std::string bad;
+    *defs = options_to_defines(c.options, &bad);
+    if (!bad.empty()) return "pchip_source_create: option " + bad + " -- only -DNAME[=VALUE] and -UNAME are passed on";
+    return "";
 }
 
-extern "C" int pchip_source_create_terms(const char *source, const char *options, const double *data, long ndata, long nterms)
+// pchip_source_create[_terms | _prior | _sums | _quad | _shared]: checks the spec, compiles the user's functions alone (a syntax error surfaces
+// here, with the compiler's log) and registers the handle.  A quadratic form (nres > 0) is a terms handle of nres terms whose matrix is copied
+// behind the data.  Returns the handle (> 0), or -1 with the reason behind pchip_last_error.
+int pc_rtc_source_create(const PcSourceSpec &c)
 {
-    std::string log;
+    std::string defs, log = spec_refusal(c, &defs);
     int id = -1;
-    if (nterms < 1) log = "pchip_source_create_terms: nterms = " + std::to_string(nterms) + " -- the sum needs at least one term (nterms >= 1)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, 0, false, &log, nullptr);
+    if (log.empty()) {
+        auto s = std::make_shared<Source>();
+        PcSourceForm &f = s->form;
+        f.nterms = c.nres > 0 ? c.nres : c.nterms; f.nsums = c.nsums; f.nquad = c.nres; f.nshared = c.nshared; f.has_prior = c.prior;
+        f.ndata = c.ndata; f.ntail = (long long)c.nres * c.nres; f.alive = 1;
+        s->text = defs + "#line 1\n" + c.source;
+        std::vector<double> block;
+        if (c.ndata > 0) block.assign(c.data, c.data + c.ndata);
+        block.insert(block.end(), c.precision, c.precision + f.ntail);
+        s->data = std::make_shared<const std::vector<double>>(std::move(block));
+        std::string arch = "gfx950";
+        int dev = 0, ndev = 0;
+        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&dev) == hipSuccess) {
+            hipDeviceProp_t pr;
+            if (hipGetDeviceProperties(&pr, dev) == hipSuccess) arch = pr.gcnArchName;
+        }
+        (void)hipGetLastError();
+        std::vector<char> code; std::vector<std::string> lowered;
+        if (!compile(s.get(), probe_unit(f), { "pchip_probe" }, arch, code, lowered, log)) {
+            Registry &G = reg();
+            std::lock_guard<std::mutex> g(G.m);
+            id = G.next++; G.src[id] = s;
+        }
+    }
     pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
     return id;
 }
 
-// likelihood and prior in one source and one handle: nterms == 0 the plain form of likelihood, nterms >= 1 the terms form
+}  // namespace
+
+// the six doors (the spec's fields in order: door, source, options, data, ndata, nterms, nsums, nres, precision, nshared, prior).  _prior:
+// nterms == 0 the plain form of likelihood, nterms >= 1 the terms form; with_prior: pchip_prior_param in the same source
+extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata) { return pc_rtc_source_create({ PcSourceSpec::PLAIN, source, options, data, ndata }); }
+extern "C" int pchip_source_create_terms(const char *source, const char *options, const double *data, long ndata, long nterms) { return pc_rtc_source_create({ PcSourceSpec::TERMS, source, options, data, ndata, nterms }); }
 extern "C" int pchip_source_create_prior(const char *source, const char *options, const double *data, long ndata, long nterms)
 {
-    std::string log;
-    int id = -1;
-    if (nterms < 0) log = "pchip_source_create_prior: nterms = " + std::to_string(nterms) + " -- 0 (the plain form) or the number of terms (nterms >= 1)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, 0, true, &log, nullptr);
-    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
-    return id;
+    return pc_rtc_source_create({ PcSourceSpec::PRIOR, source, options, data, ndata, nterms, 0, 0, nullptr, 0, true });
 }
-
-// the terms form with nsums sums per evaluation (pchip_logl_terms / pchip_logl_finish_sums); with_prior: pchip_prior_param in the same source
 extern "C" int pchip_source_create_sums(const char *source, const char *options, const double *data, long ndata, long nterms, int nsums, int with_prior)
 {
-    std::string log;
-    int id = -1;
-    if (nterms < 1) log = "pchip_source_create_sums: nterms = " + std::to_string(nterms) + " -- the sums need at least one term (nterms >= 1)";
-    else if (nsums < 1 || nsums > PCHIP_SOURCE_MAX_SUMS)
-        log = "pchip_source_create_sums: nsums = " + std::to_string(nsums) + " -- 1 <= nsums <= " + std::to_string(PCHIP_SOURCE_MAX_SUMS) + " (PCHIP_SOURCE_MAX_SUMS)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nterms, nsums, with_prior != 0, &log, nullptr);
-    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
-    return id;
+    return pc_rtc_source_create({ PcSourceSpec::SUMS, source, options, data, ndata, nterms, nsums, 0, nullptr, 0, with_prior != 0 });
 }
-
-// the quadratic form: chi2 = r^T P r of nres residuals (pchip_residual / pchip_logl_finish), P copied here; with_prior as above
 extern "C" int pchip_source_create_quad(const char *source, const char *options, const double *data, long ndata, long nres, const double *precision,
                                         int with_prior)
 {
-    std::string log;
-    int id = -1;
-    if (nres < 1 || nres > PCHIP_SOURCE_MAX_RES)
-        log = "pchip_source_create_quad: nres = " + std::to_string(nres) + " -- 1 <= nres <= " + std::to_string(PCHIP_SOURCE_MAX_RES) + " (PCHIP_SOURCE_MAX_RES)";
-    else if (!precision) log = "pchip_source_create_quad: precision == NULL -- the nres x nres matrix of the quadratic form (host, row-major)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nres, 0, with_prior != 0, &log, precision);
-    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
-    return id;
+    return pc_rtc_source_create({ PcSourceSpec::QUAD, source, options, data, ndata, 0, 0, nres, precision, 0, with_prior != 0 });
 }
-
-// shared values beside one of the three wave-parallel forms: nres > 0 the quadratic form, else nterms >= 1 terms in one sum (nsums == 0) or in
-// nsums sums; every refusal before any device call
 extern "C" int pchip_source_create_shared(const char *source, const char *options, const double *data, long ndata, long nshared, long nterms, int nsums,
                                           long nres, const double *precision, int with_prior)
 {
-    const std::string me = "pchip_source_create_shared: ";
-    std::string log;
-    int id = -1;
-    if (nshared < 1 || nshared > PCHIP_SOURCE_MAX_SHARED)
-        log = me + "nshared = " + std::to_string(nshared) + " -- 1 <= nshared <= " + std::to_string(PCHIP_SOURCE_MAX_SHARED) + " (PCHIP_SOURCE_MAX_SHARED)";
-    else if (nres < 0 || nres > PCHIP_SOURCE_MAX_RES)
-        log = me + "nres = " + std::to_string(nres) + " -- 0, or the quadratic form with 1 <= nres <= " + std::to_string(PCHIP_SOURCE_MAX_RES) + " (PCHIP_SOURCE_MAX_RES)";
-    else if (nres > 0 && (nterms != 0 || nsums != 0))
-        log = me + "nres = " + std::to_string(nres) + " with nterms = " + std::to_string(nterms) + ", nsums = " + std::to_string(nsums) +
-              " -- one form a handle: the quadratic form (nres > 0) takes nterms == 0 and nsums == 0";
-    else if (nres > 0 && !precision) log = me + "precision == NULL -- the nres x nres matrix of the quadratic form (host, row-major)";
-    else if (nres == 0 && precision) log = me + "precision != NULL with nres = 0 -- the matrix belongs to the quadratic form (nres > 0)";
-    else if (nres == 0 && nterms < 1)
-        log = me + "nterms = " + std::to_string(nterms) + " -- the sum needs at least one term (nterms >= 1; a plain likelihood with shared values is nterms = 1)";
-    else if (nres == 0 && (nsums < 0 || nsums > PCHIP_SOURCE_MAX_SUMS))
-        log = me + "nsums = " + std::to_string(nsums) + " -- 0 (one sum), or 1 <= nsums <= " + std::to_string(PCHIP_SOURCE_MAX_SUMS) + " (PCHIP_SOURCE_MAX_SUMS)";
-    else id = pc_rtc_source_create(source, options, data, ndata, nres > 0 ? nres : nterms, nres > 0 ? 0 : nsums, with_prior != 0, &log, nres > 0 ? precision : nullptr, nshared);
-    pc_abi_set_last_error(id > 0 ? nullptr : log.c_str());
-    return id;
+    return pc_rtc_source_create({ PcSourceSpec::SHARED, source, options, data, ndata, nterms, nsums, nres, precision, nshared, with_prior != 0 });
 }
 
+// The text and the data go -- a hold taken before (pc_rtc_source_hold) keeps the block for as long as somebody copies from it --, the form
+// stays, alive = 0: a run on another thread may still launch the handle's compiled modules, which stay loaded, and its launchers size their
+// LDS from the form on every launch.  The price is the form's few dozen bytes for every handle ever made.
 extern "C" void pchip_source_destroy(int handle)
-{   // (compiled modules stay loaded: a run on another thread may still launch them)
+{
     Registry &G = reg();
     std::lock_guard<std::mutex> g(G.m);
-    G.src.erase(handle);
+    auto it = G.src.find(handle);
+    if (it == G.src.end() || !it->second->form.alive) return;
+    auto dead = std::make_shared<Source>();
+    dead->form = it->second->form; dead->form.alive = 0;
+    it->second = dead;
 }
 
 // the embedded text of kernel source `i` (its file name in *name), or NULL past the last: tests compare it with the files
@@ -556,11 +489,11 @@ extern "C" const char *pchip_rtc_embedded_source(int i, const char **name)
 // built-ins alone) -- what a run on such a device would compile, without a device.  0: ok; else the log in log[cap].
 extern "C" int pchip_rtc_compile_check(int handle, const char *arch, const char *names, char *log, int cap, double *seconds)
 {
-    std::shared_ptr<Source> s;
+    std::shared_ptr<const Source> s;
     {
         Registry &G = reg();
         std::lock_guard<std::mutex> g(G.m);
-        if (handle) { auto it = G.src.find(handle); if (it == G.src.end()) { if (log && cap > 0) std::snprintf(log, cap, "no source %d", handle); return 1; } s = it->second; }
+        if (handle && !(s = live_source(G, handle))) { if (log && cap > 0) std::snprintf(log, cap, "%s", no_handle(handle).c_str()); return 1; }
     }
     std::vector<std::string> exprs;
     std::string all(names ? names : ""), e;

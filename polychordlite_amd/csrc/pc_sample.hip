@@ -2222,17 +2222,26 @@ template <class... A> static int pc_rtc_go(const PcState *S, const char *expr, d
 // residual blocks, 2 x nres doubles a chain (nres rounded up to even), in front of the chain's block, and a handle with shared values
 // (pchip_source_create_shared) its two blocks of nshared doubles behind them: the form's front block, pc_front_lds, counted in that
 // decision as well
-static size_t pc_terms_lds(const PcState *S, int phi_lds)
+static size_t pc_terms_lds(const PcState *S, const PcSourceForm &f, int phi_lds)
 {
-    if (S->like.kind != PC_LIKE_SOURCE || pc_rtc_source_terms(S->src_id) <= 0) return 0;
-    return sizeof(double) * ((size_t)S->D + (phi_lds ? (size_t)S->nr * (size_t)pc_rtc_source_sums(S->src_id) : 0)) + pc_front_lds(S);
+    if (f.nterms <= 0) return 0;
+    return sizeof(double) * ((size_t)S->D + (phi_lds ? (size_t)S->nr * (size_t)f.nsums : 0)) + pc_front_lds(f);
+}
+// the form of a state's source, which every launcher of a kernel that evaluates the likelihood fetches once per call and hands to the
+// helpers above and in pc_launch.h: one locked lookup in pc_rtc.hip's registry for a source state, none for any other (all zero).  A
+// handle destroyed under a run in flight still answers (alive is not asked here): the cached kernel keeps its launch shape
+static PcSourceForm pc_state_form(const PcState *S)
+{
+    PcSourceForm f{};
+    if (S->like.kind == PC_LIKE_SOURCE) (void)pc_rtc_source_form(S->src_id, &f);
+    return f;
 }
 // lane = coordinate: the coordinates a lane holds (template DPL) at nDims <= 64, 128, 256; 0 beyond (the launchers return 1)
 static int pc_dpl(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : (D <= 256 ? 4 : 0)); }
 extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL,
                                        hipStream_t st)
 {
-    const size_t sh = sizeof(double) * S->D + pc_front_lds(S);
+    const size_t sh = sizeof(double) * S->D + pc_front_lds(pc_state_form(S));
     const bool table = S->prior.kind >= 2;          // a prior table, or a source prior (kind 3: the same variants, from its handle's module)
     switch (pc_dpl(S->D) + (table ? 8 : 0)) {
     case 1: PC_LAUNCH((k_generate_live<1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
@@ -2383,11 +2392,12 @@ static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R
     p.fw = !fused ? 0 : (D <= 8 ? 8 : (D <= 16 ? 16 : 24));
     p.grid = R ? dim3(nchains, R) : dim3(nchains); p.block = dim3(64);
     // a chain's LDS: ybuf + two int decks; theta of every baby (derived parameters at the end of the chain) when it fits
-    p.phi_lds = pc_slice_phi_lds(S);
+    const PcSourceForm f = pc_state_form(S);
+    p.phi_lds = pc_slice_phi_lds(S, f);
     const size_t tb = sizeof(double) * (size_t)nr * (D + 1);
     size_t sh = sizeof(double) * ((size_t)D + nr) + 16 + (p.phi_lds ? tb : 0);
     if (fused) sh += sizeof(double) * ((size_t)p.fw * D + (size_t)nr * (D + 2));     // + L, directions, widths
-    if (!R) sh += pc_terms_lds(S, p.phi_lds);                              // (a source in step: pc_launch_slice_step below, not this plan)
+    if (!R) sh += pc_terms_lds(S, f, p.phi_lds);                              // (a source in step: pc_launch_slice_step below, not this plan)
     if (fused && sh > 150 * 1024) return p;
     // the functor variants (LEAN = 3 Rastrigin, 4 twin Gaussian, 5 the Gaussian when settings.ablate bit 0 asks for it as a functor): one grade,
     // keyed draws, the box (a prior table: the general variants); runs in step take the Gaussian functor as the general kernel
@@ -2501,10 +2511,11 @@ static PcSlicePlan pc_slice_step_plan(const PcState *S, int nchains, int fused, 
     p.fw = !fused ? 0 : (D <= 8 ? 8 : (D <= 16 ? 16 : 24));
     p.grid = dim3(nchains, R); p.block = dim3(64);
     // a chain's LDS as pc_slice_plan lays it out, and the second theta of the terms form (and the babies' sums) behind it
-    p.phi_lds = pc_slice_phi_lds(S);
+    const PcSourceForm f = pc_state_form(S);
+    p.phi_lds = pc_slice_phi_lds(S, f);
     size_t sh = sizeof(double) * ((size_t)D + nr) + 16 + (p.phi_lds ? sizeof(double) * (size_t)nr * (D + 1) : 0);
     if (fused) sh += sizeof(double) * ((size_t)p.fw * D + (size_t)nr * (D + 2));
-    sh += pc_terms_lds(S, p.phi_lds);
+    sh += pc_terms_lds(S, f, p.phi_lds);
     if (fused && sh > 150 * 1024) return p;
     p.lds = sh; p.ok = true;
     return p;
@@ -2547,7 +2558,7 @@ extern "C" int pc_launch_source_eval(const PcState *S, int n, const double *thet
     const int dpl = pc_dpl(S->D);
     if (S->like.kind != PC_LIKE_SOURCE || n < 1 || !dpl) return 1;
     const char *name = dpl == 1 ? "k_source_eval<1>" : (dpl == 2 ? "k_source_eval<2>" : "k_source_eval<4>");
-    return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D + pc_front_lds(S), st, *S, thetas, logL, phi);
+    return pc_rtc_go(S, name, dim3(n), dim3(64), sizeof(double) * S->D + pc_front_lds(pc_state_form(S)), st, *S, thetas, logL, phi);
 }
 
 // pchip_source_prior_eval: the prior of a source handle at n points (device pointers) -- k_prior_transform of the handle's run-time module
@@ -2586,7 +2597,7 @@ extern "C" int pc_launch_max_rank(const PcState *S, int n, const double *rows, d
 extern "C" int pc_launch_maximise(const PcState *S, int nprob, const double *in, const int *hdr, long long max_iter, double *out, long long *outi, hipStream_t st)
 {
     if (S->D < 1 || S->D > 64 || nprob < 1) return 1;
-    const size_t sh = sizeof(double) * PC_MAX_LDS_DOUBLES(S->D) + pc_front_lds(S);
+    const size_t sh = sizeof(double) * PC_MAX_LDS_DOUBLES(S->D) + pc_front_lds(pc_state_form(S));
     if (!pc_max_lds_fits("k_maximise", sh)) return 1;
     if (sh > 48 * 1024 && !pc_rtc_wanted(S)) pc_need_dyn_lds((const void *)k_maximise<1>, sh);
     PC_LAUNCH((k_maximise<1>), dim3(nprob), dim3(64), sh, st, *S, in, hdr, max_iter, out, outi);

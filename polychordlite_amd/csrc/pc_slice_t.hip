@@ -716,7 +716,7 @@ extern "C" int pc_slice_t_ok(const PcState *S, int ncluster)
     if (off || ncluster != 1 || S->prior.kind >= 2) return 0;      // (a prior table or a source prior: k_slice's general variants)
     if (S->D > 24 || S->ngrade > 1 || S->seq_mode || S->nhat_raw == nullptr || S->nr > 255) return 0;
     if (S->like.kind != PC_LIKE_GAUSSIAN || (S->ablate & PC_ABL_FUNCTOR)) return 0;
-    if (S->nDer > 0 && !pc_slice_phi_lds(S)) return 0;      // (k_slice would take the derived parameters' other summation order)
+    if (S->nDer > 0 && !pc_slice_phi_lds(S, PcSourceForm{})) return 0;      // (k_slice would take the derived parameters' other summation order; the Gaussian: no source)
     return slice_t_lds(S) <= 64 * 1024;
 }
 

@@ -1,7 +1,9 @@
 """The sampling launchers choose the kernels, grids, blocks and LDS sizes they chose before they were rewritten around one plan
 (pc_slice_plan and the variant table of pc_sample.hip, launch_t of pc_slice_t.hip): tools/dev/launch_record.hip walks a grid of
 fabricated states through them on the CPU, under no developer switch and under each of seven, and the digest of every launcher's
-record is compared with the one taken from the commit before the rewrite (69220c3)."""
+record is compared with the one taken from the commit before the rewrite (69220c3).  A second sweep, `launch_record --forms`, walks the
+same launchers over the same grid for source handles of every form (several sums, quadratic, shared values): what pins the LDS sizes the
+launchers take from a handle's form record on the CPU, against the commit before that record (e2f1bd3)."""
 import os
 import subprocess
 
@@ -42,12 +44,27 @@ PARENT_UNDER = {'PC_SLICE_LEAN_OFF': {'slice': ('fdb1beeffeb0da6f', 716800),
  'PC_BASES_T_OFF': {'bases_t': ('0a131b6bc49e2f13', 358400), 'bases_t_many': ('730a16dd293b47e3', 1433600)},
  'PC_SLICE_T_OFF': {'slice_t_ok': ('1f32a1b3e67b3903', 179200)}}
 
+# launch_record --forms built against e2f1bd3's pc_sample.hip and pc_launch.h, with that commit's one accessor per field stubbed from the same
+# table of handles, no switch set: {launcher: (digest, calls)}
+PARENT_FORMS = {'slice': ('c5aa8f1ec4e4a77b', 921600),
+ 'slice_fused': ('6bf493219f1523eb', 921600),
+ 'slice_many0': ('1cf45aefe825d845', 921600),
+ 'slice_many1': ('af6b9727ea093f3f', 921600),
+ 'nhats': ('318a554bd2e1df53', 921600),
+ 'nhats_part1': ('b0857b6c5a881f33', 921600),
+ 'nhats_part2': ('6aa2ac09c37ab1c3', 921600),
+ 'nhats_part1_packed': ('9dccc37170a43143', 921600),
+ 'nhats_many': ('e8aced6c7605c633', 921600),
+ 'generate_live': ('ddb0789792c4a823', 921600),
+ 'prior_transform': ('9d8afbda98ddf71b', 921600),
+ 'source_eval': ('24cfff098d184613', 921600)}
 
-def record(binary, switch):
+
+def record(binary, switch, *args):
     env = {k: v for k, v in os.environ.items() if not k.startswith("PC_")}
     if switch:
         env[switch] = "1"
-    out = subprocess.run([binary], env=env, check=True, capture_output=True, text=True).stdout
+    out = subprocess.run([binary, *args], env=env, check=True, capture_output=True, text=True).stdout
     return {name: (digest, int(calls)) for name, digest, calls in (line.split() for line in out.splitlines())}
 
 
@@ -70,6 +87,15 @@ def test_launches_are_those_of_the_parent(recorders, switch):
         "launchers %s choose differently from 69220c3%s.  For the two texts: build tools/dev/launch_record.hip against both trees "
         "(make -C polychordlite_amd/csrc launch_record; in a checkout of 69220c3 the same two hipcc lines with -I set to its csrc), run "
         "each as `%slaunch_record --dump DIR` and diff DIR/<launcher>.txt" % (differ, " under " + switch if switch else "", switch + "=1 " if switch else ""))
+
+
+def test_launches_of_every_source_form_are_those_of_the_parent(recorders):
+    """the recorder itself exits 1 unless the handles with several sums and the quadratic form of 1024 residuals have states on both sides of
+    pc_slice_phi_lds's 48 KB limit"""
+    got = record(recorders[0], "", "--forms")
+    assert set(got) == set(PARENT_FORMS)
+    differ = sorted(n for n in PARENT_FORMS if got[n] != PARENT_FORMS[n])
+    assert not differ, "launchers %s choose differently from e2f1bd3 for a source handle of some form (`launch_record --forms --dump DIR` of both trees, as above)" % differ
 
 
 def test_every_sampling_kernel_is_reached(recorders):

@@ -8,6 +8,8 @@
 //   launch_record            one line per launcher: its name, the digest of its record, the number of calls
 //   launch_record --kernels  the distinct kernels reached (full template argument lists)
 //   launch_record --dump DIR the records themselves, DIR/<launcher>.txt (several hundred MB: for a diff of two builds)
+//   launch_record --forms    the second sweep instead of the first: the same launchers over the same grid for source handles of every form
+//                            (FORMS below), which is what pins the LDS sizes of pc_launch.h's helpers to the kernels' layout on the CPU
 // The developer switches are read once per process: run it once under each of them.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -102,19 +104,25 @@ struct Launcher {
 #include "pc_sample.hip"
 // what pc_sample.hip's host code calls in other files
 extern "C" int pc_rtc_launch(const PcState *, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t, void **) { rec::launch(expr, "", grid, block, sh); return 0; }
-extern "C" long pc_rtc_source_terms(int id) { return id == 2 ? 100 : 0; }
+// the handles of the two sweeps by src_id -- the first sweep knows 1 (the plain form) and 2 (100 terms) --: nterms, nsums, nquad, nshared
+static const PcSourceForm FORMS[] = { {}, {}, {100}, {100, 5}, {100, 8}, {5, 0, 5}, {1024, 0, 1024}, {100, 0, 0, 1}, {100, 0, 0, 512}, {65, 0, 65, 65}, {100, 5, 0, 65} };
+static const int NFORMS = sizeof FORMS / sizeof FORMS[0];
+extern "C" int pc_rtc_source_form(int id, PcSourceForm *f) { *f = id >= 0 && id < NFORMS ? FORMS[id] : PcSourceForm{}; return 0; }
 extern "C" int pc_launch_bases_t(const PcState *S, unsigned, int, hipStream_t) { rec::line += " | bases_t"; return S->D < 2; }
 #endif
-extern "C" int pc_rtc_source_sums(int) { return 0; }      // (pc_slice_phi_lds asks: no handle of the sweep has several sums)
-extern "C" long pc_rtc_source_quad(int) { return 0; }     // (pc_quad_lds asks: no handle of the sweep is a quadratic form)
-extern "C" long pc_rtc_source_shared(int) { return 0; }   // (pc_front_lds asks: no handle of the sweep has shared values)
 extern "C" void pc_abi_set_last_error(const char *msg) { if (msg) { rec::line += " | error: "; rec::line += msg; } }
 
 int main(int argc, char **argv)
 {
     static double dummy[4];
     static const PcManyRec *dR = (const PcManyRec *)dummy;      // (never read: the kernels are not launched)
-    const char *dump = (argc > 2 && !std::strcmp(argv[1], "--dump")) ? argv[2] : nullptr;
+    const char *dump = nullptr;
+    bool forms = false, list = false;
+    for (int a = 1; a < argc; ++a) {
+        if (!std::strcmp(argv[a], "--dump") && a + 1 < argc) dump = argv[++a];
+        else if (!std::strcmp(argv[a], "--forms")) forms = true;
+        else if (!std::strcmp(argv[a], "--kernels")) list = true;
+    }
 #ifdef RECORD_SLICE_T
     rec::Launcher L[] = { rec::Launcher("slice_t"), rec::Launcher("slice_t_many"), rec::Launcher("slice_t_ok"), rec::Launcher("bases_t"), rec::Launcher("bases_t_many") };
 #else
@@ -155,10 +163,24 @@ int main(int argc, char **argv)
     const int Ds[] = {1, 8, 9, 16, 17, 20, 24, 25, 32, 33, 64, 65, 80, 96, 112, 113, 128, 129, 256, 257};
     const int nrs[] = {1, 5, 40, 64, 65, 200, 255, 256, 1024, 1025};
     const int kinds[] = {PC_LIKE_CALLBACK, PC_LIKE_GAUSSIAN, PC_LIKE_RASTRIGIN, PC_LIKE_TWIN_GAUSSIAN, PC_LIKE_CORR_GAUSSIAN, PC_LIKE_SOURCE, -PC_LIKE_SOURCE};
-    for (int D : Ds) for (int nr : nrs) for (int kind : kinds) for (int nDer = 0; nDer <= 2; nDer += 2) for (int pk = 0; pk <= 2; pk += 2)
+    // --forms: a source of every handle of FORMS from 2 on instead of the kinds -- terms, 5 and 8 sums, nres 5 and 1024, nshared 1 and 512 beside
+    // terms, shared beside a quadratic form and beside sums.  For the handles whose own block counts in pc_slice_phi_lds's 48 KB decision (several
+    // sums, nres = 1024; not a shared handle, which never takes that pass) the sweep must hold states on both sides of the limit: `in`, the babies'
+    // rows fit beside the block; `over`, they would fit without it
+    std::vector<int> subjects;
+    if (forms) for (int h = 2; h < NFORMS; ++h) subjects.push_back(-h); else subjects.assign(kinds, kinds + sizeof kinds / sizeof kinds[0]);
+    long in[NFORMS] = {}, over[NFORMS] = {};
+    for (int D : Ds) for (int nr : nrs) for (int kind : subjects) for (int nDer = 0; nDer <= 2; nDer += 2) for (int pk = 0; pk <= 2; pk += 2)
     for (int flags = 0; flags < 64; ++flags) for (int nch : {30, 32}) {
         PcState S{};
-        S.D = D; S.nr = nr; S.nDer = nDer; S.nT = 2 * D + nDer + 2; S.like.kind = kind < 0 ? -kind : kind; S.src_id = kind == PC_LIKE_SOURCE ? 1 : (kind < 0 ? 2 : 0);
+        S.D = D; S.nr = nr; S.nDer = nDer; S.nT = 2 * D + nDer + 2; S.like.kind = kind < 0 ? PC_LIKE_SOURCE : kind;
+        S.src_id = forms ? -kind : (kind == PC_LIKE_SOURCE ? 1 : (kind < 0 ? 2 : 0));
+        if (forms && nDer > 0) {
+            const PcSourceForm &F = FORMS[S.src_id];
+            const size_t rows = sizeof(double) * ((size_t)D + nr) + 16 + sizeof(double) * (size_t)nr * (D + 1);
+            const size_t own = sizeof(double) * (size_t)nr * F.nsums + 2 * sizeof(double) * (size_t)((F.nquad + 1) & ~1L);
+            if (rows + own <= 48 * 1024) in[S.src_id]++; else if (rows <= 48 * 1024) over[S.src_id]++;
+        }
         S.prior.kind = pk; S.nb_total = 2;
         S.ngrade = (flags & 1) ? 2 : 1; S.seq_mode = (flags & 2) ? 1 : 0; S.ablate = ((flags & 4) ? 1 : 0) | ((flags & 8) ? 8192 : 0);
         S.nhat_raw = (flags & 16) ? nullptr : dummy; S.nhat_Ms = (flags & 32) ? dummy : nullptr;
@@ -176,8 +198,9 @@ int main(int argc, char **argv)
         L[10].done(st, pc_launch_prior_transform(&S, 50, nullptr, nullptr, nullptr));
         L[11].done(st, pc_launch_source_eval(&S, 50, nullptr, nullptr, nullptr, nullptr));
     }
+    for (int h : {3, 4, 6}) if (forms && !(in[h] && over[h])) { std::fprintf(stderr, "--forms: handle %d has no state on both sides of the 48 KB limit (%ld, %ld)\n", h, in[h], over[h]); return 1; }
 #endif
-    if (argc > 1 && !std::strcmp(argv[1], "--kernels")) { for (const auto &k : rec::kernels) std::printf("%s\n", k.c_str()); return 0; }
+    if (list) { for (const auto &k : rec::kernels) std::printf("%s\n", k.c_str()); return 0; }
     for (auto &l : L) { std::printf("%s %016llx %ld\n", l.name, l.h, l.calls); if (l.f) std::fclose(l.f); }
     return 0;
 }

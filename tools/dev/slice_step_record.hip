@@ -42,10 +42,8 @@ void clear() { launches.clear(); attrs.clear(); error.clear(); }
 #include "pc_sample.hip"
 // what pc_sample.hip's host code calls in other files
 extern "C" int pc_rtc_launch(const PcState *, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t, void **) { rec::launch(expr, grid, block, sh); return 0; }
-extern "C" long pc_rtc_source_terms(int id) { return id == 2 || id == 3 ? 100 : 0; }
-extern "C" int pc_rtc_source_sums(int id) { return id == 3 ? 5 : 0; }
-extern "C" long pc_rtc_source_quad(int) { return 0; }     // (pc_quad_lds asks: no handle here is a quadratic form)
-extern "C" long pc_rtc_source_shared(int) { return 0; }   // (pc_front_lds asks: no handle here has shared values)
+// (handle 1 the plain form, 2 a hundred terms, 3 a hundred terms in five sums; no quadratic form and no shared values here)
+extern "C" int pc_rtc_source_form(int id, PcSourceForm *f) { *f = PcSourceForm{}; f->nterms = id == 2 || id == 3 ? 100 : 0; f->nsums = id == 3 ? 5 : 0; return 0; }
 extern "C" int pc_launch_bases_t(const PcState *S, unsigned, int, hipStream_t) { return S->D < 2; }
 extern "C" void pc_abi_set_last_error(const char *msg) { if (msg) rec::error = msg; }
 
