@@ -19,8 +19,12 @@ module polychord_hip
               polychord_hip_set_source, polychord_hip_source_loglike, polychord_hip_source_prior, &
               pchip_source_create, pchip_source_create_shared, pchip_source_destroy
 
-    !> one parameter of a prior table (pchip_prior_entry of polychord_hip.h): the reference's type number 1 .. 10 (priors.f90:5-15),
-    !! the prior block, the number of prior parameters and the parameters in the ini file's order
+    !> one parameter of a prior table (pchip_prior_entry of polychord_hip.h): the reference's type number 1 .. 15 (priors.f90:5-20),
+    !! the prior block, the number of prior parameters and the parameters in the ini file's order.  The adaptive types 11 .. 15 are
+    !! blocks of consecutive parameters whose first is the count (polychord_hip.h has their rules); their numbers by name:
+    integer(c_int), parameter, public :: PCHIP_PT_ADAPTIVE_SORTED_UNIFORM = 11, PCHIP_PT_ADAPTIVE_SORTED_GAUSSIAN = 12, &
+        PCHIP_PT_ADAPTIVE_SORTED_HALF_GAUSSIAN = 13, PCHIP_PT_ADAPTIVE_SORTED_EXPONENTIAL = 14, &
+        PCHIP_PT_NN_ADAPTIVE_LAYER_GAUSSIAN = 15
     type, bind(c) :: pchip_prior_entry
         integer(c_int) :: ptype, pblock, npar
         real(c_double) :: par(3)

@@ -70,13 +70,25 @@ void polychord_hip_set_uniform_prior(int nDims, const double *lo, const double *
 /* The reference's prior types as a table, evaluated INSIDE the sampling kernels when the likelihood is a device likelihood: one entry
  * per PARAMETER -- the type number of priors.f90:5-15, the prior block, the prior parameters in the ini file's order -- and the
  * hypercube index of every parameter (priors.f90:708-737; NULL = identity).  sorted_ blocks are consecutive parameters of one type
- * and block (priors.f90:245-262).  The adaptive types (11-15) are not supported. */
+ * and block (priors.f90:245-262).
+ * The adaptive types 11-15 (priors.f90:363-488) are blocks of consecutive parameters of one type and block as well.  With x_1 .. x_n the
+ * block's cube coordinates:
+ *   adaptive_sorted_{uniform, gaussian, half_gaussian, exponential}, n >= 2: parameter 1 is the count, theta_1 = 0.5 + x_1 (n - 1), not
+ *     rounded.  nfunc = INT(theta_1 + 0.5); parameters 2 .. nfunc+1 are sorted among themselves like a sorted_ block of nfunc, parameters
+ *     nfunc+2 .. n keep y = x, and parameters 2 .. n go through the base transform, each with its own prior parameters.
+ *   nn_adaptive_layer_gaussian, n >= 3: parameter 1 is the layer number, theta_1 = 0.5 + 2 x_1; parameters 2 .. n are an adaptive block
+ *     of n - 1 (its count is parameter 2) whose base is half_gaussian where theta_1 < 1.5 and gaussian otherwise.
+ *   EVERY parameter of such a block, the count and the layer included, gives exactly the base type's number of prior parameters (2; 1 for
+ *     exponential): the reference skips the count's by position.  The count's and the layer's values are read and ignored.
+ *   One defined deviation: for x_1 = 1 - 2^-53 and n - 1 a power of two the reference's nfunc comes out as n and it sorts one element
+ *     past its array; here nfunc is clamped to 1 .. n-1, on the host and on the device. */
 enum { PCHIP_PT_UNIFORM = 1, PCHIP_PT_LOG_UNIFORM = 2, PCHIP_PT_POWER_UNIFORM = 3, PCHIP_PT_GAUSSIAN = 4, PCHIP_PT_HALF_GAUSSIAN = 5,
        PCHIP_PT_EXPONENTIAL = 6, PCHIP_PT_SORTED_UNIFORM = 7, PCHIP_PT_SORTED_GAUSSIAN = 8, PCHIP_PT_SORTED_HALF_GAUSSIAN = 9,
-       PCHIP_PT_SORTED_EXPONENTIAL = 10 };
+       PCHIP_PT_SORTED_EXPONENTIAL = 10, PCHIP_PT_ADAPTIVE_SORTED_UNIFORM = 11, PCHIP_PT_ADAPTIVE_SORTED_GAUSSIAN = 12,
+       PCHIP_PT_ADAPTIVE_SORTED_HALF_GAUSSIAN = 13, PCHIP_PT_ADAPTIVE_SORTED_EXPONENTIAL = 14, PCHIP_PT_NN_ADAPTIVE_LAYER_GAUSSIAN = 15 };
 typedef struct {
     int type;                      /* PCHIP_PT_* */
-    int block;                     /* prior block (the ini file's fifth column); only tells sorted_ blocks of one type apart */
+    int block;                     /* prior block (the ini file's fifth column); only tells sorted_ and adaptive blocks of one type apart */
     int npar;                      /* prior parameters given (uniform, log_uniform, gaussian, half_gaussian: 2; exponential: 1; power_uniform: 3) */
     double par[3];
 } pchip_prior_entry;

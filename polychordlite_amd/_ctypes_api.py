@@ -44,7 +44,7 @@ class Like(C.Structure):
 
 
 class PriorEntry(C.Structure):
-    """pchip_prior_entry: one parameter of a prior table (type number of PRIOR_TYPES, prior block, prior parameters)"""
+    """pchip_prior_entry: one parameter of a prior table (type number of PRIOR_TYPES / ADAPTIVE_PRIOR_TYPES, prior block, prior parameters)"""
     _fields_ = [("type", C.c_int), ("block", C.c_int), ("npar", C.c_int), ("par", C.c_double * 3)]
 
 
@@ -58,6 +58,9 @@ PRIOR_CALLBACK, PRIOR_BOX, PRIOR_TABLE, PRIOR_SOURCE = 0, 1, 2, 3
 # the reference's prior type numbers (priors.f90:5-15) a table takes
 PRIOR_TYPES = {"uniform": 1, "log_uniform": 2, "power_uniform": 3, "gaussian": 4, "half_gaussian": 5, "exponential": 6,
                "sorted_uniform": 7, "sorted_gaussian": 8, "sorted_half_gaussian": 9, "sorted_exponential": 10}
+# ... and its adaptive types (priors.f90:16-20): blocks whose first parameter decides, per point, how many of the others are sorted
+ADAPTIVE_PRIOR_TYPES = {"adaptive_sorted_uniform": 11, "adaptive_sorted_gaussian": 12, "adaptive_sorted_half_gaussian": 13,
+                        "adaptive_sorted_exponential": 14, "nn_adaptive_layer_gaussian": 15}
 
 
 class Result(C.Structure):
@@ -268,12 +271,12 @@ def source_prior_eval(handle, cubes):
 
 def prior_table(entries, hyper=None):
     """(PriorEntry array, hypercube-order array or None) of a prior table: entries = one (type, block, params) or (type, params) per
-    PARAMETER, type a name of PRIOR_TYPES or its number; hyper = hypercube index of every parameter (None: identity)"""
+    PARAMETER, type a name of PRIOR_TYPES or ADAPTIVE_PRIOR_TYPES or its number; hyper = hypercube index of every parameter (None: identity)"""
     arr = (PriorEntry * len(entries))()
     for i, e in enumerate(entries):
         t, block, pars = (e[0], 1, e[1]) if len(e) == 2 else e
         pars = [float(v) for v in np.atleast_1d(pars)]
-        arr[i].type = PRIOR_TYPES[t] if isinstance(t, str) else int(t)
+        arr[i].type = (PRIOR_TYPES[t] if t in PRIOR_TYPES else ADAPTIVE_PRIOR_TYPES[t]) if isinstance(t, str) else int(t)
         arr[i].block, arr[i].npar = int(block), len(pars)
         for k, v in enumerate(pars[:3]):
             arr[i].par[k] = v

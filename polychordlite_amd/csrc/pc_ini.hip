@@ -97,12 +97,17 @@ int base_prior_nparams(const std::string &t)
     if (t == "power_uniform") return 3;
     return -1;
 }
-std::string base_of(const std::string &prior) { return prior.rfind("sorted_", 0) == 0 ? prior.substr(7) : prior; }
+std::string base_of(const std::string &prior)
+{
+    if (prior == "nn_adaptive_layer_gaussian") return "gaussian";
+    if (prior.rfind("adaptive_sorted_", 0) == 0) return prior.substr(16);
+    return prior.rfind("sorted_", 0) == 0 ? prior.substr(7) : prior;
+}
 
-// type number of a prior name (priors.f90:5-15), 0 if unknown or unsupported (the adaptive types)
+// type number of a prior name (priors.f90:5-20), 0 if unknown
 int prior_type_of(const std::string &t)
 {
-    for (int k = 1; k <= 10; ++k) if (t == pc_prior_type_name(k)) return k;
+    for (int k = 1; k <= 15; ++k) if (t == pc_prior_type_name(k)) return k;
     return 0;
 }
 
@@ -115,6 +120,7 @@ std::vector<pchip_prior_entry> table_of(const std::vector<Param> &params)
         if (need < 0) halt_program("get_priors error: Unknown prior type for parameter " + params[i].name);
         if ((int)params[i].pp.size() < need) halt_program("ini error: parameter " + params[i].name + " needs " + std::to_string(need) + " prior parameters");
         e[i].type = prior_type_of(params[i].prior); e[i].block = params[i].block; e[i].npar = std::min<int>(3, (int)params[i].pp.size());
+        if (pc_prior_is_adaptive(e[i].type)) e[i].npar = (int)params[i].pp.size();      // an adaptive block takes exactly `need`: the true count goes on
         for (int k = 0; k < 3; ++k) e[i].par[k] = k < e[i].npar ? params[i].pp[k] : 0.0;
     }
     return e;
@@ -175,15 +181,9 @@ extern "C" int polychord_hip_ini_prior(const char *inifile, const double *cube, 
     const std::vector<int> hyper = hypercube_indices(ini.params);
     const std::vector<pchip_prior_entry> e = table_of(ini.params);
     PcPriorTable T;
-    T.D = nDims; T.e = e; T.hyper = hyper; T.pos.assign(nDims, 0); T.len.assign(nDims, 0);
-    for (int i = 0; i < nDims;) {
-        int j = i + 1;
-        if (e[i].type >= PCHIP_PT_SORTED_UNIFORM) {
-            while (j < nDims && e[j].type == e[i].type && e[j].block == e[i].block) ++j;
-            for (int k = i; k < j; ++k) { T.pos[k] = k - i + 1; T.len[k] = j - i; }
-        }
-        i = j;
-    }
+    T.D = nDims; T.e = e; T.hyper = hyper;
+    int stray, head;
+    (void)pc_prior_table_blocks(T.e, T.pos, T.len, T.cnt, T.lay, stray, head);
     pc_prior_table_eval(T, cube, theta);
     return nDims;
 }

@@ -31,19 +31,29 @@ struct LaneDims {
 // ------------------------------------------------------------------------------------------
 // prior table (PcPrior::kind == 2, the reference's prior types: priors.f90:40-290, hypercube_to_physical :494-556) on a wave, lane =
 // PARAMETER.  S.prior.lo carries the doubles [3][D] -- per base type: uniform lo, hi - lo; log_uniform lo, hi / lo; power_uniform
-// a = lo^(1/p), |a - hi^(1/p)|, p; gaussian / half_gaussian mu, sigma; exponential the rate -- S.prior.hi the integers [4][D] (base type
-// 1 .. 6, 1-based position in the sorted_ block and the block's length or 0, 0, hypercube index), S.src_pad the wave-uniform mask:
-// bit t = base type t is present, bit 16 = a sorted_ block, bit 17 = the hypercube order is no identity.  Read ONCE at the head of a chain.
+// a = lo^(1/p), |a - hi^(1/p)|, p; gaussian / half_gaussian mu, sigma; exponential the rate -- S.prior.hi the integers [6][D] (base type
+// 1 .. 6, 1-based position in the sorted_ block and the block's length or 0, 0, hypercube index, and for a member of an adaptive block --
+// priors.f90:363-488 -- the hypercube index of its count's and of its layer's coordinate, else -1), S.src_pad the wave-uniform mask:
+// bit t = base type t is present, bit 16 = a sorted_ or adaptive block, bit 17 = the hypercube order is no identity, bit 18 = an adaptive
+// block, bit 19 = a layer parameter (nn_adaptive_layer_gaussian).  Read ONCE at the head of a chain.
+// An adaptive block's count (and layer) parameter is a uniform entry here: lo 0.5, span = the number of members (2).  Its members carry
+// pos = 1-based position among the members and len = their number; how many of them are order statistics is the POINT's (pc_table_theta).
 // ------------------------------------------------------------------------------------------
 #define PC_PT_SORTED (1u << 16)
 #define PC_PT_PERMUTED (1u << 17)
+#define PC_PT_ADAPTIVE (1u << 18)
+#define PC_PT_LAYER (1u << 19)
 template <int DPL>
 struct LaneTable {
     int type[DPL], pos[DPL], len[DPL], hyp[DPL];
+    int cnt[DPL], lay[DPL];      // a member of an adaptive block: hypercube index of its count's and of its layer's coordinate, else -1
     double p0[DPL], p1[DPL], p2[DPL];
     unsigned mask;
 };
-template <int DPL>
+// AD (here and in pc_table_theta): the text knows adaptive blocks.  k_slice / k_slice_many carry it as PT = 2, a template value of its own, so
+// that the PT = 1 kernels of every other table are instruction for instruction what they were (with the adaptive text inside, the sorted
+// table's k_slice took 4 % longer a launch: profiles/adaptive_priors.json); the kernels off the hot path have the one text, AD = true.
+template <int DPL, bool AD>
 __device__ __forceinline__ void pc_table_load(const PcState &S, int lane, LaneTable<DPL> &lt)
 {
     const int D = S.D;
@@ -56,33 +66,74 @@ __device__ __forceinline__ void pc_table_load(const PcState &S, int lane, LaneTa
         const bool on = dim < D;
         lt.type[k] = on ? ti[dim] : 0; lt.pos[k] = on ? ti[D + dim] : 0; lt.len[k] = on ? ti[2 * D + dim] : 0; lt.hyp[k] = on ? ti[3 * D + dim] : 0;
         lt.p0[k] = on ? tp[dim] : 0.0; lt.p1[k] = on ? tp[D + dim] : 0.0; lt.p2[k] = on ? tp[2 * D + dim] : 0.0;
+        if constexpr (AD) {
+            lt.cnt[k] = -1; lt.lay[k] = -1;
+            if (lt.mask & PC_PT_ADAPTIVE) {               // (wave-uniform: a run without such a block reads nothing more)
+                lt.cnt[k] = on ? ti[4 * D + dim] : -1; lt.lay[k] = on ? ti[5 * D + dim] : -1;
+            }
+        }
     }
+}
+// nfunc of an adaptive block with n1 members at its count coordinate x (priors.f90:378-380): INT((0.5 + x n1) + 0.5), each operation
+// rounded on its own as on the host (pc_adaptive_nfunc, pc_prior_table.h: no fma, or a point one ulp beside a bin edge sorts another number
+// of members than the host does), clamped to 1 .. n1 as there
+__device__ __forceinline__ int pc_table_nfunc(double x, int n1)
+{
+    const int nf = (int)__dadd_rn(__dadd_rn(0.5, __dmul_rn(x, (double)n1)), 0.5);
+    return nf < 1 ? 1 : (nf > n1 ? n1 : nf);
+}
+// a member of an adaptive block at one point: nfn = the length of the sorted part it belongs to (0: it keeps y = x), and whether its
+// layer coordinate asks for the half_gaussian base (theta_1 = 0.5 + 2 x < 1.5, priors.f90:480-486; 2 x is exact).  cube_h: the staged cube
+template <int DPL>
+__device__ __forceinline__ void pc_table_adapt(const LaneTable<DPL> &lt, const double *cube_h, int (&nfn)[DPL], bool (&half)[DPL])
+{
+#pragma unroll
+    for (int k = 0; k < DPL; ++k)
+        if (lt.cnt[k] >= 0) {
+            const int nf = pc_table_nfunc(cube_h[lt.cnt[k]], lt.len[k]);
+            nfn[k] = lt.pos[k] <= nf ? nf : 0;
+            if (lt.mask & PC_PT_LAYER) { if (lt.lay[k] >= 0) half[k] = __dadd_rn(0.5, cube_h[lt.lay[k]] * 2.0) < 1.5; }
+        }
 }
 // cube (hypercube order) -> theta (parameter order).  ybuf: the wave's LDS scratch of >= D doubles (one wave per workgroup: the barriers
 // are cheap and every lane reaches them -- the mask is a kernel argument).  A wave pays each type PRESENT in the run once per call:
 //   * y = cube[hyper[dim]]: a gather through LDS unless the order is the identity;
+//   * adaptive blocks: every member reads its block's count coordinate (and its layer's) from the staged cube -- staged for the gather
+//     already, else here -- and forms nfunc; the first nfunc members are a sorted_ block whose last member is count + nfunc, the others
+//     keep y = x;
 //   * sorted_ blocks (priors.f90:245-262): every member forms x_j^(1/j) (one pow a lane), then the running product from the block's LAST member down to
 //     its own, in the reference's order of multiplication (y_n = x_n^(1/n), y_k = y_{k+1} x_k^(1/k)): a short serial chain a lane over
 //     LDS, all members in parallel; a block may lie across the lane-63 / lane-0 boundary;
 //   * the separable transform of the lane's type; the types that are absent from the run are skipped by a scalar branch.
-template <int DPL>
+template <int DPL, bool AD>
 __device__ __forceinline__ void pc_table_theta(const LaneTable<DPL> &lt, const double (&cube)[DPL], double (&th)[DPL], int lane, double *ybuf)
 {
     double y[DPL];
 #pragma unroll
     for (int k = 0; k < DPL; ++k) y[k] = cube[k];
+    int nfn[DPL];               // length of the sorted part this lane's coordinate is a member of: the block's, or the point's nfunc
+    bool half[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; ++k) { nfn[k] = lt.len[k]; half[k] = false; }
     if (lt.mask & PC_PT_PERMUTED) {
 #pragma unroll
         for (int k = 0; k < DPL; ++k) if (lt.type[k]) ybuf[lane + 64 * k] = cube[k];
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < DPL; ++k) if (lt.type[k]) y[k] = ybuf[lt.hyp[k]];
+        if constexpr (AD) { if (lt.mask & PC_PT_ADAPTIVE) pc_table_adapt<DPL>(lt, ybuf, nfn, half); }
+        __syncthreads();
+    } else if (AD && (lt.mask & PC_PT_ADAPTIVE)) {
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) if (lt.type[k]) ybuf[lane + 64 * k] = cube[k];
+        __syncthreads();
+        pc_table_adapt<DPL>(lt, ybuf, nfn, half);
         __syncthreads();
     }
     if (lt.mask & PC_PT_SORTED) {
 #pragma unroll
         for (int k = 0; k < DPL; ++k) {
-            if (lt.len[k] > 0) {
+            if (nfn[k] > 0) {
                 const int j = lt.pos[k];
                 double t = pow(y[k], 1.0 / (double)j);
                 // (within 2^-33 of 1 the root is formed exactly, as on the host -- pc_sorted_root, pc_prior_table.h: the last bit of pow
@@ -98,8 +149,8 @@ __device__ __forceinline__ void pc_table_theta(const LaneTable<DPL> &lt, const d
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < DPL; ++k)
-            if (lt.len[k] > 0) {
-                const int dim = lane + 64 * k, last = dim - lt.pos[k] + lt.len[k];
+            if (nfn[k] > 0) {
+                const int dim = lane + 64 * k, last = dim - lt.pos[k] + nfn[k];
                 double r = ybuf[last];
                 for (int i = last - 1; i >= dim; --i) r = r * ybuf[i];
                 y[k] = r;
@@ -108,7 +159,8 @@ __device__ __forceinline__ void pc_table_theta(const LaneTable<DPL> &lt, const d
     }
 #pragma unroll
     for (int k = 0; k < DPL; ++k) {
-        const int t = lt.type[k];
+        int t = lt.type[k];
+        if constexpr (AD) { if (lt.mask & PC_PT_LAYER) { if (half[k]) t = 5; } }
         double v = 0.0;
         if (lt.mask & (1u << 1)) { if (t == 1) v = lt.p0[k] + lt.p1[k] * y[k]; }                          // priors.f90:40-55
         if (lt.mask & (1u << 2)) { if (t == 2) v = lt.p0[k] * pow(lt.p1[k], y[k]); }                      // :114-128
@@ -145,27 +197,27 @@ __device__ __forceinline__ void pc_source_theta(const PcState &S, const double (
 }
 // S.prior.kind is a kernel argument: the branch is wave-uniform, and a table (kind 2) run of such a handle takes pc_table_theta as ever.
 // A source prior has no table: S.prior.lo / .hi are null and nothing is loaded.
-template <int DPL>
+template <int DPL, bool AD>
 __device__ __forceinline__ void pc_prior_load(const PcState &S, int lane, LaneTable<DPL> &lt)
 {
     if (S.prior.kind == 3) {
         lt.mask = 0u;
 #pragma unroll
-        for (int k = 0; k < DPL; ++k) { lt.type[k] = 0; lt.pos[k] = 0; lt.len[k] = 0; lt.hyp[k] = 0; lt.p0[k] = 0.0; lt.p1[k] = 0.0; lt.p2[k] = 0.0; }
-    } else pc_table_load<DPL>(S, lane, lt);
+        for (int k = 0; k < DPL; ++k) { lt.type[k] = 0; lt.pos[k] = 0; lt.len[k] = 0; lt.hyp[k] = 0; lt.cnt[k] = -1; lt.lay[k] = -1; lt.p0[k] = 0.0; lt.p1[k] = 0.0; lt.p2[k] = 0.0; }
+    } else pc_table_load<DPL, AD>(S, lane, lt);
 }
-template <int DPL>
+template <int DPL, bool AD>
 __device__ __forceinline__ void pc_prior_theta(const PcState &S, const LaneTable<DPL> &lt, const double (&cube)[DPL], double (&th)[DPL], int lane,
                                                double *ybuf)
 {
     if (S.prior.kind == 3) pc_source_theta<DPL>(S, cube, th, lane, ybuf);
-    else pc_table_theta<DPL>(lt, cube, th, lane, ybuf);
+    else pc_table_theta<DPL, AD>(lt, cube, th, lane, ybuf);
 }
-#define PC_PRIOR_LOAD(DPL, S, lane, lt) pc_prior_load<DPL>(S, lane, lt)
-#define PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf) pc_prior_theta<DPL>(S, lt, cube, th, lane, ybuf)
+#define PC_PRIOR_LOAD(DPL, AD, S, lane, lt) pc_prior_load<DPL, AD>(S, lane, lt)
+#define PC_PRIOR_THETA(DPL, AD, S, lt, cube, th, lane, ybuf) pc_prior_theta<DPL, AD>(S, lt, cube, th, lane, ybuf)
 #else
-#define PC_PRIOR_LOAD(DPL, S, lane, lt) pc_table_load<DPL>(S, lane, lt)
-#define PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf) pc_table_theta<DPL>(lt, cube, th, lane, ybuf)
+#define PC_PRIOR_LOAD(DPL, AD, S, lane, lt) pc_table_load<DPL, AD>(S, lane, lt)
+#define PC_PRIOR_THETA(DPL, AD, S, lt, cube, th, lane, ybuf) pc_table_theta<DPL, AD>(lt, cube, th, lane, ybuf)
 #endif
 
 #ifdef PCHIP_USER_SOURCE
@@ -649,8 +701,8 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
     }
     if constexpr (PT != 0) {
         LaneTable<DPL> lt;
-        PC_PRIOR_LOAD(DPL, S, lane, lt);
-        PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf);
+        PC_PRIOR_LOAD(DPL, true, S, lane, lt);
+        PC_PRIOR_THETA(DPL, true, S, lt, cube, th, lane, ybuf);
     }
 #ifdef PCHIP_USER_TERMS
     double tsum[PC_NSUMS] = {};
@@ -690,11 +742,11 @@ __global__ __launch_bounds__(64) void k_prior_transform(PcState S, const double 
     const int lane = threadIdx.x, D = S.D;
     const size_t base = (size_t)blockIdx.x * D;
     LaneTable<DPL> lt;
-    PC_PRIOR_LOAD(DPL, S, lane, lt);
+    PC_PRIOR_LOAD(DPL, true, S, lane, lt);
     double cube[DPL], th[DPL];
 #pragma unroll
     for (int k = 0; k < DPL; ++k) cube[k] = (lane + 64 * k < D) ? cubes[base + lane + 64 * k] : 0.5;
-    PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf);
+    PC_PRIOR_THETA(DPL, true, S, lt, cube, th, lane, ybuf);
 #pragma unroll
     for (int k = 0; k < DPL; ++k) if (lane + 64 * k < D) thetas[base + lane + 64 * k] = th[k];
 }
@@ -749,15 +801,15 @@ __device__ __forceinline__ void pc_max_lanes(const PcState &S, int lane, LaneDim
     const double hi = (box && ld.on[0] && S.prior.hi) ? S.prior.hi[lane] : 1.0;
     ld.lo[0] = lo; ld.span[0] = hi - lo;
     ld.mean[0] = (ld.on[0] && S.like.mean) ? S.like.mean[lane] : 0.0;
-    if (!box) PC_PRIOR_LOAD(DPL, S, lane, lt);
-    else { lt.mask = 0u; lt.type[0] = 0; lt.pos[0] = 0; lt.len[0] = 0; lt.hyp[0] = 0; lt.p0[0] = 0.0; lt.p1[0] = 0.0; lt.p2[0] = 0.0; }
+    if (!box) PC_PRIOR_LOAD(DPL, true, S, lane, lt);
+    else { lt.mask = 0u; lt.type[0] = 0; lt.pos[0] = 0; lt.len[0] = 0; lt.hyp[0] = 0; lt.cnt[0] = -1; lt.lay[0] = -1; lt.p0[0] = 0.0; lt.p1[0] = 0.0; lt.p2[0] = 0.0; }
 }
 // cube -> theta: the table or the source prior of the sampling kernels, else the box as k_generate_live forms it
 template <int DPL>
 __device__ __forceinline__ void pc_max_theta(const PcState &S, const LaneDims<DPL> &ld, const LaneTable<DPL> &lt, const double (&cube)[DPL],
                                              double (&th)[DPL], int lane, double *ybuf)
 {
-    if (S.prior.kind >= 2) PC_PRIOR_THETA(DPL, S, lt, cube, th, lane, ybuf);
+    if (S.prior.kind >= 2) PC_PRIOR_THETA(DPL, true, S, lt, cube, th, lane, ybuf);
     else th[0] = ld.lo[0] + ld.span[0] * cube[0];
 }
 // determinant of the column-major n x n matrix in LDS (destroyed): det_cm's elimination order (pc_maximise.hip, nelder_mead.f90:168-209), row
@@ -1955,6 +2007,22 @@ struct ChainCtx<DPL, NROWS, 1> {
     double *ybuf2;
 #endif
 };
+// PT = 2 (a table with an adaptive block): the same members
+template <int DPL, int NROWS>
+struct ChainCtx<DPL, NROWS, 2> {
+    const PcState &S;
+    const LaneDims<DPL> &ld;
+    int lane;
+    double *ybuf;
+    int nlike;
+    bool quad;
+    double qa, qb, qc, qnorm;
+    LaneTable<DPL> tb;
+#ifdef PCHIP_USER_TERMS
+    double tsum[PC_NSUMS];
+    double *ybuf2;
+#endif
+};
 
 #ifdef PCHIP_USER_TERMS
 // the two ends of a bracket (thA / thB: theta of the ends that are inside the cube, inA / inB wave-uniform): both in one pass over the
@@ -2018,7 +2086,7 @@ __device__ __forceinline__ double eval_at(ChainCtx<DPL, NROWS, PT> &C, const dou
         for (int k = 0; k < DPL; ++k) th[k] = 0.0;
         return C.S.logzero;
     }
-    if constexpr (PT != 0) PC_PRIOR_THETA(DPL, C.S, C.tb, cube, th, C.lane, C.ybuf);
+    if constexpr (PT != 0) PC_PRIOR_THETA(DPL, PT == 2, C.S, C.tb, cube, th, C.lane, C.ybuf);
     else {
 #pragma unroll
     for (int k = 0; k < DPL; ++k) th[k] = C.ld.lo[k] + C.ld.span[k] * cube[k];
@@ -2055,20 +2123,20 @@ __device__ __forceinline__ void eval_pair(ChainCtx<DPL, NROWS, PT> &C, const dou
         const bool oa = __ballot(outA) != 0ull, ob = __ballot(outB) != 0ull;
 #ifdef PCHIP_USER_TERMS
         if (kind == PC_LIKE_SOURCE) {
-            if (!oa) PC_PRIOR_THETA(DPL, C.S, C.tb, cA, thA, C.lane, C.ybuf);
-            if (!ob) PC_PRIOR_THETA(DPL, C.S, C.tb, cB, thB, C.lane, C.ybuf);
+            if (!oa) PC_PRIOR_THETA(DPL, PT == 2, C.S, C.tb, cA, thA, C.lane, C.ybuf);
+            if (!ob) PC_PRIOR_THETA(DPL, PT == 2, C.S, C.tb, cB, thB, C.lane, C.ybuf);
             like_pair_terms<DPL, NROWS, PT>(C, thA, thB, !oa, !ob, lA, lB);
             return;
         }
 #endif
         lA = C.S.logzero; lB = C.S.logzero;
         if (!oa) {
-            PC_PRIOR_THETA(DPL, C.S, C.tb, cA, thA, C.lane, C.ybuf);
+            PC_PRIOR_THETA(DPL, PT == 2, C.S, C.tb, cA, thA, C.lane, C.ybuf);
             lA = like_eval<DPL, NROWS, KIND>(C.S, thA, C.ld, C.lane, C.ybuf);
             if (lA > C.S.logzero) C.nlike++;
         }
         if (!ob) {
-            PC_PRIOR_THETA(DPL, C.S, C.tb, cB, thB, C.lane, C.ybuf);
+            PC_PRIOR_THETA(DPL, PT == 2, C.S, C.tb, cB, thB, C.lane, C.ybuf);
             lB = like_eval<DPL, NROWS, KIND>(C.S, thB, C.ld, C.lane, C.ybuf);
             if (lB > C.S.logzero) C.nlike++;
         }
@@ -2177,7 +2245,8 @@ constexpr int pc_step_spec = PC_STEP_SPEC;
 #else
 #define PC_SLICE_ATTR
 #endif
-// PT = 1: the prior is a table (pc_table_theta) -- the general variants only (LEAN = 0, WPB = 1): no closed form along the chord
+// PT = 1: the prior is a table (pc_table_theta) -- the general variants only (LEAN = 0, WPB = 1): no closed form along the chord;
+// PT = 2: a table with an adaptive block (pc_table_theta<DPL, true>: the block structure is the point's), chosen by pc_table_pt
 template <int DPL, int NROWS, bool SPECIAL, int WPB = 1, int FW = 0, int LEAN = 0, int PT = 0>
 __global__ PC_SLICE_ATTR __launch_bounds__(64 * WPB * ((FW > 0 && (LEAN == 1 || LEAN == 3 || LEAN == 5) && WPB == 4) ? 2 : 1)) void k_slice(PcState S, unsigned batch, int phi_lds, int mat_lds)
 {
@@ -2364,6 +2433,8 @@ extern "C" int pc_slice_fusable(const PcState *S)
 // PC_SLICE_VARIANTS lists the variants that exist, pc_slice_launch sends a plan to its row.  A new variant: a rule in the
 // plan and a row in the table.
 // ------------------------------------------------------------------------------------------
+// PT of a run behind a prior table or a source prior: 2 = the table has an adaptive block (its mask says so), 1 = any other
+static int pc_table_pt(const PcState *S) { return S->prior.kind == 2 && ((unsigned)S->src_pad & PC_PT_ADAPTIVE) ? 2 : 1; }
 struct PcSlicePlan {
     bool ok, many;                                // ok = false: no such launch (the launchers return 1);  many: k_slice_many, grid.y = run
     int dpl, nrows; bool special; int wpb, fw, lean, pt;      // the template arguments (see k_slice)
@@ -2388,7 +2459,7 @@ static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R
     p.many = R > 0;
     p.dpl = pc_dpl(D);
     p.nrows = D <= 16 ? 1 : ((D <= 32 || fused) ? 2 : 4);
-    p.special = special; p.wpb = 1; p.pt = table ? 1 : 0;
+    p.special = special; p.wpb = 1; p.pt = table ? pc_table_pt(S) : 0;
     p.fw = !fused ? 0 : (D <= 8 ? 8 : (D <= 16 ? 16 : 24));
     p.grid = R ? dim3(nchains, R) : dim3(nchains); p.block = dim3(64);
     // a chain's LDS: ybuf + two int decks; theta of every baby (derived parameters at the end of the chain) when it fits
@@ -2433,8 +2504,15 @@ static PcSlicePlan pc_slice_plan(const PcState *S, int nchains, int fused, int R
     return p;
 }
 
+// Tables with an adaptive block (PT = 2, pc_table_pt): the twin of every PT = 1 row of the tables below -- of PC_SLICE_VARIANTS for k_slice, of
+// PC_SLICE_STEP_VARIANTS for k_slice_many -- in tables of their own behind them: those two list what every other run takes, as before.
+#define PC_SLICE_ADAPT_VARIANTS(X) \
+    X(1, 1, false, 1, 0, 0, 2) X(1, 1, true, 1, 0, 0, 2) X(1, 2, false, 1, 0, 0, 2) X(1, 2, true, 1, 0, 0, 2) X(1, 4, false, 1, 0, 0, 2) X(1, 4, true, 1, 0, 0, 2) X(2, 4, false, 1, 0, 0, 2) X(2, 4, true, 1, 0, 0, 2) X(4, 4, false, 1, 0, 0, 2) X(4, 4, true, 1, 0, 0, 2) X(1, 1, false, 1, 8, 0, 2) X(1, 1, false, 1, 16, 0, 2) X(1, 2, false, 1, 24, 0, 2)
+#define PC_SLICE_STEP_ADAPT_VARIANTS(X) \
+    X(1, 1, false, 1, 0, 0, 2) X(1, 2, false, 1, 0, 0, 2) X(1, 4, false, 1, 0, 0, 2) X(1, 1, false, 1, 8, 0, 2) X(1, 1, false, 1, 16, 0, 2) X(1, 2, false, 1, 24, 0, 2)
+
 // the instantiations of k_slice: DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT  (a prior table: the rows k_slice<DPL, NROWS, GR, 1, 0, 0, 1> and, fused,
-// k_slice<1, NROWS, false, 1, FW, 0, 1>)
+// k_slice<1, NROWS, false, 1, FW, 0, 1>; their twins PT = 2: PC_SLICE_ADAPT_VARIANTS above)
 #define PC_SLICE_VARIANTS(X) \
     /* behind k_nhats*: nDims <= 16, 32, 64, 128, 256; general (box / table prior, without / with the rare modes) and functors */ \
     X(1, 1, false, 1, 0, 0, 0) X(1, 1, true, 1, 0, 0, 0) X(1, 1, false, 1, 0, 0, 1) X(1, 1, true, 1, 0, 0, 1) X(1, 1, false, 1, 0, 3, 0) X(1, 1, false, 1, 0, 4, 0) X(1, 1, false, 1, 0, 5, 0) \
@@ -2464,6 +2542,7 @@ static int pc_slice_launch(const PcState *S, const PcSlicePlan &p, const PcManyR
         PC_LAUNCH((k_slice<DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT>), p.grid, p.block, p.lds, st, *S, batch, p.phi_lds, p.mat_lds); \
         return 0; }
     PC_SLICE_VARIANTS(PC_ROW)
+    PC_SLICE_ADAPT_VARIANTS(PC_ROW)
 #undef PC_ROW
 #define PC_ROW(DPL, NROWS, SPECIAL, WPB, FW, LEAN) \
     if (p.many && p.dpl == DPL && p.nrows == NROWS && p.special == SPECIAL && p.wpb == WPB && p.fw == FW && p.lean == LEAN && p.pt == 0) { \
@@ -2489,7 +2568,7 @@ extern "C" int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R
 // Runs in step whose problem is the user's own: a source likelihood (plain or terms form) and / or a device prior (a table, a source
 // prior).  pc_slice_plan and its tables above stay what they were (the box, the built-ins); the rules here are the plan's for R > 0 without
 // its refusal of a table, with the terms form's LDS, and never a functor variant: the general kernel, PT = 0 (a source under the box)
-// or 1.  DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT as above; the PT = 0 rows are the instantiations of PC_SLICE_MANY_VARIANTS' LEAN = 0 rows.
+// or 1 (2: a table with an adaptive block).  DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT as above; the PT = 0 rows are the instantiations of PC_SLICE_MANY_VARIANTS' LEAN = 0 rows.
 // ------------------------------------------------------------------------------------------
 #define PC_SLICE_STEP_VARIANTS(X) \
     X(1, 1, false, 1, 0, 0, 0) X(1, 2, false, 1, 0, 0, 0) X(1, 4, false, 1, 0, 0, 0) X(1, 1, false, 1, 8, 0, 0) X(1, 1, false, 1, 16, 0, 0) X(1, 2, false, 1, 24, 0, 0) \
@@ -2507,7 +2586,7 @@ static PcSlicePlan pc_slice_step_plan(const PcState *S, int nchains, int fused, 
     p.many = true;
     p.dpl = 1;
     p.nrows = D <= 16 ? 1 : ((D <= 32 || fused) ? 2 : 4);
-    p.special = false; p.wpb = 1; p.lean = 0; p.pt = S->prior.kind >= 2 ? 1 : 0;
+    p.special = false; p.wpb = 1; p.lean = 0; p.pt = S->prior.kind >= 2 ? pc_table_pt(S) : 0;
     p.fw = !fused ? 0 : (D <= 8 ? 8 : (D <= 16 ? 16 : 24));
     p.grid = dim3(nchains, R); p.block = dim3(64);
     // a chain's LDS as pc_slice_plan lays it out, and the second theta of the terms form (and the babies' sums) behind it
@@ -2532,6 +2611,7 @@ extern "C" int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R
         PC_LAUNCH((k_slice_many<DPL, NROWS, SPECIAL, WPB, FW, LEAN, PT>), p.grid, p.block, p.lds, st, dR, p.phi_lds, p.mat_lds); \
         return 0; }
     PC_SLICE_STEP_VARIANTS(PC_ROW)
+    PC_SLICE_STEP_ADAPT_VARIANTS(PC_ROW)
 #undef PC_ROW
     char msg[160];
     std::snprintf(msg, sizeof msg, "pc_launch_slice_step: no k_slice_many<%d, %d, %d, %d, %d, %d, %d> in the variant table", p.dpl, p.nrows, (int)p.special, p.wpb, p.fw, p.lean, p.pt);

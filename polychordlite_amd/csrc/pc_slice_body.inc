@@ -206,7 +206,7 @@
     // PT: the chain's prior table, its constants read once (pc_table_load); every trial is then cube -> theta by pc_table_theta and a
     // likelihood call -- no closed form along the chord, no carried products of the correlated Gaussian
     ChainCtx<DPL, NROWS, PT> C{S, ld, lane, ybuf, 0, false, 0.0, 0.0, 0.0, 0.0};
-    if constexpr (PT != 0) PC_PRIOR_LOAD(DPL, S, lane, C.tb);
+    if constexpr (PT != 0) PC_PRIOR_LOAD(DPL, PT == 2, S, lane, C.tb);
 #ifdef PCHIP_USER_TERMS
     // the terms form of a source: the second theta of eval_pair behind the chain's block, where the launchers add nDims doubles for it
     // (pc_terms_lds); the sum of every baby in the spare double of its tbuf row (the rows are D + 1 apart).  Several sums

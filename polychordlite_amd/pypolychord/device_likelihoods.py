@@ -164,7 +164,11 @@ class TablePrior:
     """The reference's prior types (priors.f90: uniform, log_uniform, power_uniform, gaussian, half_gaussian, exponential and the
     sorted_ forms of uniform / gaussian / half_gaussian / exponential) as a table, one entry per parameter: (type, params) or
     (type, block, params), e.g. [("gaussian", [0.5, 1.0])] * 4 + [("sorted_uniform", 1, [0, 1])] * 2.  `hyper`: the hypercube index
-    of every parameter (None: identity).  Evaluated inside the sampling kernels when the likelihood is a built-in; called like a
+    of every parameter (None: identity).  The adaptive types -- adaptive_sorted_uniform, adaptive_sorted_gaussian,
+    adaptive_sorted_half_gaussian, adaptive_sorted_exponential, nn_adaptive_layer_gaussian -- are blocks of consecutive entries of one
+    type and block: the first entry is the count (behind the layer number, for nn_adaptive_layer_gaussian) and decides per point how
+    many of the following members are sorted; every entry of the block, the count included, gives exactly the base type's number of
+    prior parameters, e.g. [("adaptive_sorted_uniform", 1, [0, 1])] * 5.  Evaluated inside the sampling kernels when the likelihood is a built-in; called like a
     function it is the library's host function (polychord_hip_table_prior).  ValueError if the library refuses the table."""
     symbol = "polychord_hip_table_prior"
 
