@@ -665,6 +665,47 @@ int  pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const dou
 int  pchip_update_factors(const pchip_settings *s, int ncluster, int nlive, const double *live, const int *live_cluster,
                           int nph, const double *phantom, const double *ph_logL, const int *ph_cluster, const double *threshold,
                           const double *shift, int path, double *cov, double *chol, int *count, double *shift_out, int *chol_suspect);
+/* kernel-level: the clustering of an update (do_clustering + add_cluster, the kNN kernels of pc_cluster.hip and the host's recursion) on
+ * given point sets, by the run's own launchers -- tests against the reference's answers on ties, duplicates and tile edges
+ * (tests/test_clustering_kernels.py).  Of a set's settings nDims, device, ablate, n_sub_cluster and sub_cluster_dims are read.
+ * In, per set: ncluster clusters; nlive live slots, slot i with cube coordinates live[i][nDims], live_logL[i] and live_cluster[i] (0-based;
+ * -1: the slot is dead) -- a point's list position is its rank among the rows of its cluster; nph phantom rows with cube coordinates, logL
+ * and cluster (-1: the row holds no phantom).  The clusters get the ids 0 ... ncluster - 1 and fixed distinct volumes and evidences,
+ * logXp[c] = log((c + 1) / sum) among them; out->init hands them back.
+ * path 0 (one set): the state is installed as a run holds it at the start of an update and ClusterUpdate::do_clustering is called as
+ * Engine::do_update calls it (with sub-dimensions: the sub pass, then the full pass) -- the one-run launchers.
+ * Out, per set (host memory, sized by the caller: maxc clusters, nsplit_cap genealogy entries; every pointer but the scratch is needed):
+ * the state after the update.  cl_list holds the clusters' slots one cluster behind the other in list order (cl_n[c] each).  ph_cluster is
+ * the phantoms' cluster index (-1: gone); ph_count k_ph_count's counts of the last split (-1 each if nothing split).  XpXq has the leading
+ * dimension maxc.  init: [5][ncluster] logXp, logZp, logZXp, logZp2, logZpXp as installed, then XpXq [ncluster][ncluster].
+ * scratch_Sm / scratch_knn [scratch_cap^2] and scratch_lab [scratch_cap], all three or none: the first pass's similarity block, neighbour
+ * lists and first-level labels (1-based) of the first cluster the pass looks at, scratch_n its points (with sub-dimensions: of the sub pass).
+ * path 1 (nsets >= 1 sets at once, which may differ in size, in clusters and in sub-dimensions): the launchers of the runs in step -- the first
+ * pass of all sets in one launch, every level of their recursions in one launch each, from records laid down by the cohort's own code; one
+ * pass per set (a set with sub-dimensions: its sub pass), and no split is made.  Out: live_cluster as given, live_pos[i] the part (1-based,
+ * numbered by first appearance in list order) of slot i within its cluster, cl_n[c] the parts of cluster c, ncluster as given, levels, and
+ * the scratch where asked for; the other arrays are not written.
+ * A path that does not exist: PCHIP_NO_SUCH_PATH, nothing launched.
+ * 0, 1 (bad arguments, message in polychord_hip_last_error()), PCHIP_NO_SUCH_PATH, else a pchip_run code (4: a cluster too large for the
+ * LDS kNN sort -- nothing of the clustering is launched then). */
+typedef struct {
+    int ncluster, nlive, nph;
+    const double *live, *live_logL; const int *live_cluster;
+    const double *phantom, *ph_logL; const int *ph_cluster;
+} pchip_cluster_in;
+typedef struct {
+    int maxc, nsplit_cap, scratch_cap;                     /* in: what the arrays below have room for */
+    int ncluster, nsplit, levels, scratch_n;               /* out: clusters after the update, genealogy entries, levels of the recursion launched */
+    int *live_cluster, *live_pos, *cl_list;                /* [nlive] */
+    int *cl_n, *imin_slot, *ph_count; unsigned *cl_uid;    /* [maxc] */
+    double *logLp, *lse_ref, *lse_sum, *logXp, *logZp, *logZXp, *logZp2, *logZpXp;      /* [maxc] */
+    double *XpXq;                                          /* [maxc][maxc] */
+    int *ph_cluster;                                       /* [nph] */
+    unsigned *split_child, *split_parent; double *split_logfrac;      /* [nsplit_cap] */
+    double *init;                                          /* [5 * ncluster + ncluster^2] */
+    double *scratch_Sm; int *scratch_knn, *scratch_lab;    /* optional */
+} pchip_cluster_out;
+int  pchip_cluster_update(const pchip_settings *s, int nsets, const pchip_cluster_in *in, pchip_cluster_out *out, int path);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,9 @@ only; needs /root/reference and amdflang).  Fixtures are numbers only (inputs + 
                      targets (logZ within sigma) and the CPU baseline timing of this container
   ref_replay.json    (logL, birth) columns of one reference dead-birth file + its .stats evidence:
                      pins the evidence recursion (SURVEY 8c "deterministic evidence replay")
+  ref_clustering.json  labels, number of clusters and (small sets) neighbour lists of the reference's NN_clustering / compute_knn
+                     (oracle/ref_clustering.f90) on the point sets of tests/test_clustering_kernels.py, with a checksum of each
+                     set's coordinates (`gen_golden.py clustering` writes this file alone)
 """
 import json
 import os
@@ -194,7 +197,42 @@ def farm_cases():
     return out
 
 
+def clustering_cases():
+    """the reference's own clustering of the point sets tests/test_clustering_kernels.py generates from fixed seeds: the sets go to
+    oracle/_ref/ref_clustering as a byte stream (int32 count; per set int32 n, D and the coordinates), its answers come back as JSON.
+    Per set: n, D, the checksum of the coordinates, the number of clusters, the labels, and for sets of at most 64 points the lists of
+    compute_knn with k = min(n, 20) (1-based, point after point).  One set per line."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from tests.test_clustering_kernels import FORTRAN_MAX_N, checksum, point_sets
+    sets = {k: x for k, x in point_sets().items() if x.shape[0] <= FORTRAN_MAX_N}
+    os.makedirs(TMP, exist_ok=True)
+    path = os.path.join(TMP, "clustering_sets.bin")
+    with open(path, "wb") as f:
+        f.write(np.int32(len(sets)).tobytes())
+        for x in sets.values():
+            f.write(np.array(x.shape, dtype="<i4").tobytes()); f.write(np.ascontiguousarray(x, dtype="<f8").tobytes())
+    subprocess.check_call(["make", "-C", HERE, "_ref/ref_clustering"])
+    out = sh(os.path.join(HERE, "_ref", "ref_clustering") + " " + path)
+    if out.returncode != 0:
+        raise RuntimeError(out.stdout[-2000:] + out.stderr[-2000:])
+    ans = json.loads(out.stdout)["sets"]
+    lines = []
+    for (name, x), a in zip(sets.items(), ans):
+        assert (a["n"], a["D"]) == x.shape, (name, a["n"], a["D"], x.shape)
+        rec = dict(n=a["n"], D=a["D"], checksum=checksum(x), ncl=a["ncl"], labels=a["labels"])
+        if "knn" in a:
+            rec.update(k=a["k"], knn=a["knn"])
+        lines.append(json.dumps(name) + ":" + json.dumps(rec, separators=(",", ":")))
+        print("clustering", name, a["n"], a["D"], a["ncl"])
+    with open(os.path.join(GOLD, "ref_clustering.json"), "w") as f:
+        f.write("{\n" + ",\n".join(lines) + "\n}\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "clustering":      # only tests/golden/ref_clustering.json
+        clustering_cases()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "farm":       # only tests/golden/ref_farm.json
         os.makedirs(TMP, exist_ok=True)
         json.dump(farm_cases(), open(os.path.join(GOLD, "ref_farm.json"), "w"), indent=1)
@@ -253,6 +291,7 @@ def main():
     # prior transforms of the reference's priors_module (oracle/ref_priors.f90)
     priors = json.loads(subprocess.check_output([os.path.join(HERE, "_ref", "ref_priors")], text=True))
     json.dump(priors, open(os.path.join(GOLD, "ref_priors.json"), "w"), indent=1)
+    clustering_cases()
 
     inj = os.path.join(HERE, "_ref", "ref_driver_inject")
     nat = os.path.join(HERE, "_ref", "ref_driver")

@@ -170,6 +170,8 @@ def load():
     pi = C.POINTER(C.c_int); pd = C.POINTER(C.c_double)
     lib.pchip_update_factors.argtypes = [C.POINTER(Settings), C.c_int, C.c_int, pd, pi, C.c_int, pd, pd, pi, pd, pd, C.c_int, pd, pd, pi, pd, pi]
     lib.pchip_update_factors.restype = C.c_int
+    lib.pchip_cluster_update.argtypes = [C.POINTER(Settings), C.c_int, C.POINTER(ClusterIn), C.POINTER(ClusterOut), C.c_int]
+    lib.pchip_cluster_update.restype = C.c_int
     lib.pchip_maximise_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, pd, pi, C.c_int, pd, C.POINTER(Maximum)]
     lib.pchip_maximise_values.restype = C.c_int
     lib.pchip_maximise_device.argtypes = [C.POINTER(Settings), C.POINTER(Like), C.POINTER(Prior), pd, pi, C.c_int, pd, C.c_long, C.POINTER(Maximum)]
@@ -350,6 +352,108 @@ def update_factors(live, live_cluster, phantom, ph_logL, ph_cluster, threshold, 
 
 
 NO_SUCH_PATH = 64      # PCHIP_NO_SUCH_PATH
+
+
+class ClusterIn(C.Structure):
+    """pchip_cluster_in"""
+    _fields_ = [("ncluster", C.c_int), ("nlive", C.c_int), ("nph", C.c_int),
+                ("live", C.POINTER(C.c_double)), ("live_logL", C.POINTER(C.c_double)), ("live_cluster", C.POINTER(C.c_int)),
+                ("phantom", C.POINTER(C.c_double)), ("ph_logL", C.POINTER(C.c_double)), ("ph_cluster", C.POINTER(C.c_int))]
+
+
+class ClusterOut(C.Structure):
+    """pchip_cluster_out"""
+    _fields_ = ([(k, C.c_int) for k in ("maxc", "nsplit_cap", "scratch_cap", "ncluster", "nsplit", "levels", "scratch_n")]
+                + [(k, C.POINTER(C.c_int)) for k in ("live_cluster", "live_pos", "cl_list", "cl_n", "imin_slot", "ph_count")]
+                + [("cl_uid", C.POINTER(C.c_uint))]
+                + [(k, C.POINTER(C.c_double)) for k in ("logLp", "lse_ref", "lse_sum", "logXp", "logZp", "logZXp", "logZp2", "logZpXp", "XpXq")]
+                + [("ph_cluster", C.POINTER(C.c_int)), ("split_child", C.POINTER(C.c_uint)), ("split_parent", C.POINTER(C.c_uint)),
+                   ("split_logfrac", C.POINTER(C.c_double)), ("init", C.POINTER(C.c_double)),
+                   ("scratch_Sm", C.POINTER(C.c_double)), ("scratch_knn", C.POINTER(C.c_int)), ("scratch_lab", C.POINTER(C.c_int))])
+
+
+class ClusterUpdateError(RuntimeError):
+    def __init__(self, code, msg):
+        super().__init__(msg)
+        self.code = code
+
+
+def cluster_update(sets, path=0, device=-1):
+    """pchip_cluster_update: the clustering of an update on given point sets, by the run's own launchers.  sets: dicts with live [nlive][nDims],
+    cluster [nlive] (0-based, -1: a dead slot) and optionally logL [nlive], ncluster, phantom [nph][nDims], ph_logL, ph_cluster, sub_dims,
+    scratch (points the first cluster's scratch is asked for; 0: not).  None where the path does not exist; ClusterUpdateError (code) on
+    failure; else one dict per set: the state after the update (include/polychord_hip.h), the per-cluster arrays cut to ncluster entries.
+    path 0: one set, the one-run launchers.  path 1: the sets at once by the launchers of the runs in step; of a set's dict then live_cluster
+    (as given), live_pos (a slot's part within its cluster, 1-based), cl_n (the parts of each cluster), levels and the scratch are meaningful."""
+    lib = load()
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint))
+    R = len(sets)
+    S = (Settings * R)(); I = (ClusterIn * R)(); O = (ClusterOut * R)()
+    keep, outs = [], []
+    for r, st in enumerate(sets):
+        x = np.ascontiguousarray(np.atleast_2d(st["live"]), dtype=np.float64)
+        n, D = x.shape
+        lc = np.ascontiguousarray(st["cluster"], dtype=np.int32)
+        ll = np.ascontiguousarray(st.get("logL", np.zeros(n)), dtype=np.float64)
+        ph = np.ascontiguousarray(np.reshape(st.get("phantom", np.zeros((0, D))), (-1, D)), dtype=np.float64)
+        nph = ph.shape[0]
+        pl = np.ascontiguousarray(st.get("ph_logL", np.zeros(nph)), dtype=np.float64)
+        pc = np.ascontiguousarray(st.get("ph_cluster", np.zeros(nph)), dtype=np.int32)
+        assert lc.shape == (n,) and ll.shape == (n,) and pl.shape == (nph,) and pc.shape == (nph,)
+        nc = int(st.get("ncluster", lc.max() + 1))
+        lib.pchip_settings_default(C.byref(S[r]), D, 0)
+        S[r].device = device
+        sd = np.ascontiguousarray(st.get("sub_dims", ()), dtype=np.int32)
+        if sd.size:
+            S[r].n_sub_cluster, S[r].sub_cluster_dims = int(sd.size), ip(sd)
+        I[r].ncluster, I[r].nlive, I[r].nph = nc, n, nph
+        I[r].live, I[r].live_logL, I[r].live_cluster = dptr(x), dptr(ll), ip(lc)
+        if nph:
+            I[r].phantom, I[r].ph_logL, I[r].ph_cluster = dptr(ph), dptr(pl), ip(pc)
+        maxc, cap = min(nc + n, max(nc, int(st.get("maxc", 2048)))), int(st.get("scratch", 0))      # (room for that many clusters after the update)
+        o = dict(live_cluster=np.full(n, -9, np.int32), live_pos=np.full(n, -9, np.int32), cl_list=np.full(n, -9, np.int32),
+                 cl_n=np.full(maxc, -9, np.int32), imin_slot=np.full(maxc, -9, np.int32), ph_count=np.full(maxc, -9, np.int32),
+                 cl_uid=np.zeros(maxc, np.uint32), XpXq=np.full((maxc, maxc), np.nan),
+                 ph_cluster=np.full(max(nph, 1), -9, np.int32), split_child=np.zeros(maxc, np.uint32), split_parent=np.zeros(maxc, np.uint32),
+                 split_logfrac=np.full(maxc, np.nan), init=np.full(5 * nc + nc * nc, np.nan))
+        for k in ("logLp", "lse_ref", "lse_sum", "logXp", "logZp", "logZXp", "logZp2", "logZpXp"):
+            o[k] = np.full(maxc, np.nan)
+        if cap:
+            o.update(Sm=np.full((cap, cap), np.nan), knn=np.full((cap, cap), -9, np.int32), lab=np.full(cap, -9, np.int32))
+            O[r].scratch_Sm, O[r].scratch_knn, O[r].scratch_lab, O[r].scratch_cap = dptr(o["Sm"]), ip(o["knn"]), ip(o["lab"]), cap
+        O[r].maxc, O[r].nsplit_cap = maxc, maxc
+        for k in ("live_cluster", "live_pos", "cl_list", "cl_n", "imin_slot", "ph_count", "ph_cluster"):
+            setattr(O[r], k, ip(o[k]))
+        for k in ("cl_uid", "split_child", "split_parent"):
+            setattr(O[r], k, up(o[k]))
+        for k in ("logLp", "lse_ref", "lse_sum", "logXp", "logZp", "logZXp", "logZp2", "logZpXp", "XpXq", "split_logfrac", "init"):
+            setattr(O[r], k, dptr(o[k]))
+        keep.append((x, lc, ll, ph, pl, pc, sd))
+        outs.append((o, n, nc, nph, cap, maxc))
+    rc = lib.pchip_cluster_update(S, R, I, O, path)
+    if rc == NO_SUCH_PATH:
+        return None
+    if rc != 0:
+        msg = lib.polychord_hip_last_error()
+        raise ClusterUpdateError(rc, f"pchip_cluster_update failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
+    res = []
+    for r, (o, n, nc0, nph, cap, maxc) in enumerate(outs):
+        nc, nsp = O[r].ncluster, O[r].nsplit
+        d = dict(ncluster=nc, nsplit=nsp, levels=O[r].levels, live_cluster=o["live_cluster"], live_pos=o["live_pos"],
+                 ph_cluster=o["ph_cluster"][:nph], XpXq=o["XpXq"][:nc, :nc].copy(), init=o["init"][:5 * nc0].reshape(5, nc0),
+                 XpXq0=o["init"][5 * nc0:].reshape(nc0, nc0))
+        for k in ("cl_n", "imin_slot", "ph_count", "cl_uid", "logLp", "lse_ref", "lse_sum", "logXp", "logZp", "logZXp", "logZp2", "logZpXp"):
+            d[k] = o[k][:nc]
+        for k in ("split_child", "split_parent", "split_logfrac"):
+            d[k] = o[k][:nsp]
+        ends = np.cumsum(d["cl_n"])
+        d["cl_list"] = [o["cl_list"][e - m:e] for e, m in zip(ends, d["cl_n"])]
+        if cap:
+            m = O[r].scratch_n
+            d.update(scratch_n=m, Sm=o["Sm"].ravel()[:m * m].reshape(m, m), knn=o["knn"].ravel()[:m * m].reshape(m, m), lab=o["lab"][:m])
+        res.append(d)
+    return res
 
 
 def directions(settings, like, prior, batch, seeds, chol, path):

@@ -30,17 +30,20 @@
 #include "pc_launch.h"
 #include <cstdlib>
 
+// (Un-fused by the pragma, not by __dmul_rn / __dadd_rn: those are a plain * and + in the HIP headers, which the compiler contracts to
+//  v_fmac_f64 once they are inlined -- the kernel did until tests/test_clustering_kernels.py held the block against the oracle's bit for bit.)
 __device__ __forceinline__ void similarity_body(const PcState &S, const int *pts /* slots in list order */, int n, double *Sm, int ybase, int ystride)
 {
+#pragma clang fp contract(off)
     const int a = blockIdx.x, D = S.D;
     const double *xa = S.live + (size_t)pts[a] * S.nT;
     double ra = 0.0;
-    for (int d = 0; d < D; ++d) ra = __dadd_rn(ra, __dmul_rn(xa[d], xa[d]));
+    for (int d = 0; d < D; ++d) ra = ra + xa[d] * xa[d];
     for (int b = ybase + threadIdx.x; b < n; b += ystride) {
         const double *xb = S.live + (size_t)pts[b] * S.nT;
         double rb = 0.0, s = 0.0;
-        for (int d = 0; d < D; ++d) { rb = __dadd_rn(rb, __dmul_rn(xb[d], xb[d])); s = __dadd_rn(s, __dmul_rn(xa[d], xb[d])); }
-        Sm[(size_t)a * n + b] = __dadd_rn(__dadd_rn(ra, rb), -__dmul_rn(2.0, s));
+        for (int d = 0; d < D; ++d) { rb = rb + xb[d] * xb[d]; s = s + xa[d] * xb[d]; }
+        Sm[(size_t)a * n + b] = (ra + rb) - 2.0 * s;
     }
 }
 
@@ -50,18 +53,19 @@ __device__ __forceinline__ void similarity_body(const PcState &S, const int *pts
 // run owns (uniform over the grid: scalar loads); a pass is as many launches as a full one.
 __device__ __forceinline__ void similarity_sub_body(const PcState &S, const int *dims, int nd, const int *pts, int n, double *Sm, int ybase, int ystride)
 {
+#pragma clang fp contract(off)
     const int a = blockIdx.x;
     const double *xa = S.live + (size_t)pts[a] * S.nT;
     double ra = 0.0;
-    for (int k = 0; k < nd; ++k) { const double v = xa[dims[k]]; ra = __dadd_rn(ra, __dmul_rn(v, v)); }
+    for (int k = 0; k < nd; ++k) { const double v = xa[dims[k]]; ra = ra + v * v; }
     for (int b = ybase + threadIdx.x; b < n; b += ystride) {
         const double *xb = S.live + (size_t)pts[b] * S.nT;
         double rb = 0.0, s = 0.0;
         for (int k = 0; k < nd; ++k) {
             const int d = dims[k];
-            rb = __dadd_rn(rb, __dmul_rn(xb[d], xb[d])); s = __dadd_rn(s, __dmul_rn(xa[d], xb[d]));
+            rb = rb + xb[d] * xb[d]; s = s + xa[d] * xb[d];
         }
-        Sm[(size_t)a * n + b] = __dadd_rn(__dadd_rn(ra, rb), -__dmul_rn(2.0, s));
+        Sm[(size_t)a * n + b] = (ra + rb) - 2.0 * s;
     }
 }
 

@@ -80,6 +80,18 @@ struct Cohort {
     // ... and copies to the device that what is written down reads: made at the start of flush()
     std::vector<std::function<void()>> pre;
     void rec(const Rec &r) { pend.push_back(r); }
+    // a record as the _many kernels read it; and what a stage's launch for the records [first, last) wants folded of their integers
+    // (flush below, and the kernel-level door pchip_cluster_update, which launches the clustering stages for given point sets)
+    static void lay(PcManyRec &d, const Rec &r) { d.S = r.S; std::memcpy(d.p, r.p, sizeof(r.p)); std::memcpy(d.ia, r.ia, sizeof(r.ia)); }
+    static void folds_of(const Stage &row, const Rec *const *first, const Rec *const *last, int fold[3])
+    {
+        fold[0] = fold[1] = fold[2] = 0;
+        for (int t = 0; t < 3 && row.folds[t].how != FOLD_END; ++t)
+            for (const Rec *const *x = first; x != last; ++x) {
+                const int v = (*x)->ia[row.folds[t].slot];
+                fold[t] = row.folds[t].how == FOLD_MAX ? std::max(fold[t], v) : (fold[t] | (v > 0));
+            }
+    }
     // ... the copies among them as (destination, source, bytes): one kernel for all of them (k_copy_batch), not a hipMemcpyAsync each
     std::vector<std::array<uintptr_t, 3>> post_copies, pre_copies;
     // everything written down and asked for is forgotten, nothing of it launched (the flush it waited for will not come)
@@ -134,7 +146,7 @@ struct Cohort {
             return x->S.prior.kind < y->S.prior.kind;
         };
         std::stable_sort(ord.begin(), ord.end(), shape_less);
-        for (size_t i = 0; i < n; ++i) { hs[i].S = ord[i]->S; std::memcpy(hs[i].p, ord[i]->p, sizeof(ord[i]->p)); std::memcpy(hs[i].ia, ord[i]->ia, sizeof(ord[i]->ia)); }
+        for (size_t i = 0; i < n; ++i) lay(hs[i], *ord[i]);
         HIPCHK(hipMemcpyAsync(dr, hs, sizeof(PcManyRec) * n, hipMemcpyHostToDevice, st));
         bool up_marked = false, used_st2 = false;
         for (size_t i = 0; i < n;) {
@@ -156,12 +168,8 @@ struct Cohort {
                     if ((unsigned long long)need > seq_waited) { HIPCHK(hipStreamWaitEvent(st, ev_seq[need & 3], 0)); seq_waited = (unsigned long long)need; }
                 } else wait_next();
             }
-            int fold[3] = {0, 0, 0};
-            for (int t = 0; t < 3 && row.folds[t].how != FOLD_END; ++t)
-                for (size_t x = i; x < j; ++x) {
-                    const int v = ord[x]->ia[row.folds[t].slot];
-                    fold[t] = row.folds[t].how == FOLD_MAX ? std::max(fold[t], v) : (fold[t] | (v > 0));
-                }
+            int fold[3];
+            folds_of(row, ord.data() + i, ord.data() + j, fold);
             if (row.many(f, dr + i, cnt, fold, q) == 0) {
                 n_fused += cnt;
                 if (cnt > 1) for (size_t x = i; x < j; ++x) if (ord[x]->note) ord[x]->note->shared++;

@@ -2533,6 +2533,284 @@ int pchip_update_factors(const pchip_settings *s, int ncluster, int nlive, const
     return rc;
 }
 
+// ... its set-up: an engine for nlive slots that clusters, and the point set installed in it as a run holds it at the start of an update
+static pchip_settings cluster_door_settings(const pchip_settings &s, int nlive)
+{
+    pchip_settings c;
+    pchip_settings_default(&c, s.nDims, 0);
+    c.nlive = nlive; c.nprior = nlive; c.batch = 1; c.num_repeats = 1; c.do_clustering = 1; c.seed = 1; c.feedback = 0; c.device = s.device; c.ablate = s.ablate;
+    c.n_sub_cluster = s.n_sub_cluster; c.sub_cluster_dims = s.sub_cluster_dims;
+    return c;
+}
+static void cluster_door_install(Engine &E, const pchip_cluster_in &I, double *init_out, std::vector<int> &cn)
+{
+    const int nc0 = I.ncluster, nlive = I.nlive, nph = I.nph;
+    HIPCHK(hipStreamSynchronize(E.st));                      // (the set-up's own launch writes the per-cluster arrays and the control block)
+    if (nc0 > E.S.maxc) E.grow_clusters(nc0);
+    if (nph > E.S.Pcap) E.grow_phantoms(nph);
+    PcState &S = E.S;
+    const int nT = S.nT, D = S.D, Ncap = S.Ncap, maxc = S.maxc;
+    // the live slots: rows, values, (cluster, position) labels, and the clusters' lists and sizes made of them
+    std::vector<double> rows((size_t)Ncap * nT, 0.0);
+    std::vector<int> lpos(Ncap, 0), list((size_t)nc0 * Ncap, 0);
+    cn.assign(nc0, 0);
+    for (int i = 0; i < nlive; ++i) {
+        std::memcpy(rows.data() + (size_t)i * nT, I.live + (size_t)i * D, sizeof(double) * D);
+        rows[(size_t)i * nT + S.l0] = I.live_logL[i];
+        const int cl = I.live_cluster[i];
+        if (cl >= 0) { lpos[i] = cn[cl]; list[(size_t)cl * Ncap + cn[cl]] = i; cn[cl]++; }
+    }
+    HIPCHK(hipMemcpy(S.live, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.live_logL, I.live_logL, sizeof(double) * nlive, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.live_cluster, I.live_cluster, sizeof(int) * nlive, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.live_pos, lpos.data(), sizeof(int) * nlive, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.cl_list, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.cl_n, cn.data(), sizeof(int) * nc0, hipMemcpyHostToDevice));
+    if (nph > 0) {
+        rows.assign((size_t)nph * nT, 0.0);
+        std::vector<unsigned> cu(nph); std::vector<unsigned long long> uid(nph);
+        for (int j = 0; j < nph; ++j) {
+            std::memcpy(rows.data() + (size_t)j * nT, I.phantom + (size_t)j * D, sizeof(double) * D);
+            rows[(size_t)j * nT + S.l0] = I.ph_logL[j];
+            cu[j] = I.ph_cluster[j] < 0 ? PC_CUID_NONE : (unsigned)I.ph_cluster[j]; uid[j] = (unsigned long long)j;
+        }
+        HIPCHK(hipMemcpy(S.phantom, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(S.ph_logL, I.ph_logL, sizeof(double) * nph, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(S.ph_cuid, cu.data(), sizeof(unsigned) * nph, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(S.ph_uid, uid.data(), sizeof(unsigned long long) * nph, hipMemcpyHostToDevice));
+    }
+    // the clusters' ids, volumes and evidences: fixed and distinct
+    std::vector<unsigned> cuid(nc0);
+    std::vector<double> init((size_t)5 * nc0 + (size_t)nc0 * nc0), XQ((size_t)nc0 * maxc, 0.0);
+    const double sum = 0.5 * nc0 * (nc0 + 1.0);
+    for (int k = 0; k < nc0; ++k) {
+        cuid[k] = (unsigned)k;
+        init[k] = std::log((k + 1.0) / sum); init[nc0 + k] = -1.0 - 0.25 * k; init[2 * nc0 + k] = -2.0 - 0.125 * k;
+        init[3 * nc0 + k] = -3.0 - 0.5 * k; init[4 * nc0 + k] = -4.0 - 0.375 * k;
+    }
+    for (int a = 0; a < nc0; ++a)
+        for (int b = 0; b < nc0; ++b) {
+            const double v = init[a] + init[b] + (a == b ? std::log(1.5) : 0.0);
+            init[(size_t)5 * nc0 + (size_t)a * nc0 + b] = v; XQ[(size_t)a * maxc + b] = v;
+        }
+    std::memcpy(init_out, init.data(), sizeof(double) * init.size());
+    HIPCHK(hipMemcpy(S.cl_uid, cuid.data(), sizeof(unsigned) * nc0, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.logXp, init.data(), sizeof(double) * nc0, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.logZp, init.data() + nc0, sizeof(double) * nc0, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.logZXp, init.data() + 2 * nc0, sizeof(double) * nc0, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.logZp2, init.data() + 3 * nc0, sizeof(double) * nc0, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.logZpXp, init.data() + 4 * nc0, sizeof(double) * nc0, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.XpXq, XQ.data(), sizeof(double) * XQ.size(), hipMemcpyHostToDevice));
+    E.h_ctl->ncluster = nc0; E.h_ctl->nphantom = nph; E.h_ctl->next_cluster_uid = (unsigned)nc0;
+    HIPCHK(hipMemcpy(S.ctl, E.h_ctl, sizeof(PcCtl), hipMemcpyHostToDevice));
+}
+
+// kernel-level entry for the tests of the clustering kernels (tests/test_clustering_kernels.py): a given point set with its clusters, list
+// positions and phantoms, installed as a run holds them at the start of an update; then the update's clustering as Engine::do_update makes
+// it -- no hooks, no resume file, nothing launched that a run does not launch.
+//   path 0: ClusterUpdate::do_clustering by the one-run launchers (with sub-dimensions: the sub pass, then the full pass).
+//   path 1: the launchers of the runs in step, without fibers: the first pass of all sets in one pc_launch_knn_cluster_batch_many, every
+//           level of all sets' recursions in one pc_launch_knn_cluster_sub_many -- the records made by rec_clus1 / rec_clusg, laid down and
+//           folded by the cohort's own code (Cohort::lay, Cohort::folds_of) and launched through its table of stages; the host side is
+//           first_pass_descriptors and PartRefiner.  One pass per set (a set with sub-dimensions: the sub pass), no add_cluster.
+// The first pass's scratch of its first cluster leaves through ClusterTap (pc_split.h) where the caller asks for it.
+static int cluster_door_many(const pchip_settings *s, int R, const pchip_cluster_in *in, pchip_cluster_out *out)
+{
+    pchip_like like; std::memset(&like, 0, sizeof(like)); like.kind = PC_LIKE_GAUSSIAN; like.mu = 0.5; like.sigma = 1.0;
+    pchip_prior prior; std::memset(&prior, 0, sizeof(prior)); prior.kind = 1;
+    std::vector<std::unique_ptr<Engine>> E;
+    PcManyRec *d_recs = nullptr;
+    int rc = 0;
+    try {
+        std::vector<std::vector<int>> cn((size_t)R);
+        for (int r = 0; r < R; ++r) {
+            E.emplace_back(new Engine);
+            E[r]->setup(cluster_door_settings(s[r], in[r].nlive), like, prior);
+            cluster_door_install(*E[r], in[r], out[r].init, cn[r]);
+            E[r]->clus.ensure_scratch();
+        }
+        hipStream_t st = E[0]->st;                           // (every set's own stream is idle: the installs were blocking copies)
+        HIPCHK(hipMalloc(&d_recs, sizeof(PcManyRec) * (size_t)R));
+        // one stage for the records of several sets: laid down, folded and launched as Cohort::flush does for the runs of a round
+        auto launch = [&](std::vector<Cohort::Rec> &recs) {
+            if (recs.empty()) return;
+            std::vector<PcManyRec> hs(recs.size());
+            std::vector<const Cohort::Rec *> ord;
+            for (size_t i = 0; i < recs.size(); ++i) { Cohort::lay(hs[i], recs[i]); ord.push_back(&recs[i]); }
+            HIPCHK(hipMemcpy(d_recs, hs.data(), sizeof(PcManyRec) * hs.size(), hipMemcpyHostToDevice));
+            const Cohort::Stage &row = Cohort::stage(recs[0].kind);
+            int fold[3];
+            Cohort::folds_of(row, ord.data(), ord.data() + ord.size(), fold);
+            if (row.many(recs[0], d_recs, (int)recs.size(), fold, st)) engine_fail(PC_RC_LDS, "a cluster too large for the LDS kNN sort");
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+        };
+        auto down = [&](std::vector<int> &v, const int *src, size_t n) { v.resize(n); if (n) HIPCHK(hipMemcpy(v.data(), src, sizeof(int) * n, hipMemcpyDeviceToHost)); };
+        auto up = [&](int *dst, const std::vector<int> &v) { if (!v.empty()) HIPCHK(hipMemcpy(dst, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice)); };
+        // the first pass
+        std::vector<FirstPass> fp((size_t)R);
+        std::vector<PartRefiner> parts((size_t)R);
+        std::vector<Cohort::Rec> recs;
+        for (int r = 0; r < R; ++r) {
+            Engine &e = *E[r]; auto &cu = e.clus;
+            fp[r] = first_pass_descriptors(cn[r]);
+            if (fp[r].nd() == 0) continue;
+            if (fp[r].o2 > (long long)cu.c_cap * cu.c_cap) engine_fail(PC_RC_DEVICE, "clustering: the clusters' similarity blocks (%lld entries) exceed the scratch of %d points", fp[r].o2, cu.c_cap);
+            cu.c_desc_cap = std::max(2 * in[r].ncluster, 64);
+            cu.c_desc = e.blocks.dev<int>((size_t)4 * cu.c_desc_cap); cu.c_bout = e.blocks.dev<int>(cu.c_desc_cap);
+            cu.c_g_cap = e.S.Ncap;
+            cu.c_gdesc = e.blocks.dev<int>((size_t)5 * cu.c_g_cap); cu.c_gpool = e.blocks.dev<int>(cu.c_g_cap); cu.c_glab = e.blocks.dev<int>(cu.c_g_cap); cu.c_gout = e.blocks.dev<int>(cu.c_g_cap);
+            up(cu.c_desc, fp[r].desc);
+            recs.push_back(rec_clus1(e.S, cu.c_desc, cu.c_Sm, cu.c_knn, cu.c_lab, cu.c_bout, e.sub_dims.empty() ? nullptr : e.c_subdims, fp[r].nd(), fp[r].nmax, (int)e.sub_dims.size()));
+        }
+        launch(recs);
+        for (int r = 0; r < R; ++r) {
+            out[r].levels = 0; out[r].scratch_n = 0;
+            if (fp[r].nd() == 0) continue;
+            auto &cu = E[r]->clus;
+            std::vector<int> verdict, lab0;
+            down(verdict, cu.c_bout, (size_t)fp[r].nd()); down(lab0, cu.c_lab, (size_t)fp[r].o1);
+            if (out[r].scratch_Sm) {
+                const size_t n = (size_t)fp[r].desc[1];
+                if ((int)n > out[r].scratch_cap) engine_fail(PC_RC_LIMIT, "the first cluster's scratch was asked for with room for %d points; it has %d", out[r].scratch_cap, (int)n);
+                out[r].scratch_n = (int)n;
+                HIPCHK(hipMemcpy(out[r].scratch_Sm, cu.c_Sm, sizeof(double) * n * n, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(out[r].scratch_knn, cu.c_knn, sizeof(int) * n * n, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(out[r].scratch_lab, cu.c_lab, sizeof(int) * n, hipMemcpyDeviceToHost));
+            }
+            parts[r].open(fp[r], verdict, lab0);
+        }
+        // the recursion, level by level: the open parts of every set in one launch
+        while (true) {
+            recs.clear();
+            std::vector<int> who;
+            for (int r = 0; r < R; ++r) {
+                if (fp[r].nd() == 0 || !parts[r].work_left()) continue;
+                Engine &e = *E[r]; auto &cu = e.clus;
+                const PartRefiner::Level &lev = parts[r].next_level();
+                if (lev.koff > (long long)cu.c_cap * cu.c_cap || std::max(lev.nb, (int)lev.pool.size()) > cu.c_g_cap)
+                    engine_fail(PC_RC_DEVICE, "clustering: the parts of a level (%d, %lld list entries) exceed the scratch of %d points", lev.nb, lev.koff, cu.c_cap);
+                up(cu.c_gdesc, lev.gdesc); up(cu.c_gpool, lev.pool);
+                recs.push_back(rec_clusg(e.S, cu.c_gdesc, cu.c_Sm, cu.c_gpool, cu.c_knn, cu.c_glab, cu.c_gout, lev.nb, lev.mmax));
+                who.push_back(r);
+            }
+            if (recs.empty()) break;
+            launch(recs);
+            for (int r : who) {
+                auto &cu = E[r]->clus;
+                std::vector<int> labs, nums;
+                down(labs, cu.c_glab, parts[r].lev.pool.size()); down(nums, cu.c_gout, (size_t)parts[r].lev.nb);
+                parts[r].take(labs, nums);
+                out[r].levels++;
+            }
+        }
+        // every set's final labels: live_pos = a slot's part (1-based) within its cluster, cl_n = the parts of each cluster
+        for (int r = 0; r < R; ++r) {
+            const pchip_cluster_in &I = in[r]; pchip_cluster_out &O = out[r];
+            std::vector<std::vector<int>> final_labels((size_t)I.ncluster); std::vector<int> final_num((size_t)I.ncluster, 1);
+            if (fp[r].nd() > 0) parts[r].finish(final_labels, final_num);
+            std::vector<int> at((size_t)I.ncluster, 0);
+            for (int i = 0; i < I.nlive; ++i) {
+                const int c = I.live_cluster[i];
+                O.live_cluster[i] = c; O.live_pos[i] = 0;
+                if (c >= 0) { O.live_pos[i] = final_num[c] > 1 ? final_labels[c][(size_t)at[c]] : 1; at[c]++; }
+            }
+            O.ncluster = I.ncluster; O.nsplit = 0;
+            for (int c = 0; c < I.ncluster; ++c) O.cl_n[c] = final_num[c];
+        }
+    } catch (const EngineError &e) {
+        std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str());
+        (void)hipGetLastError();
+        rc = e.code;
+    }
+    if (d_recs) (void)hipFree(d_recs);
+    for (auto &e : E) e->destroy();
+    return rc;
+}
+int pchip_cluster_update(const pchip_settings *s, int nsets, const pchip_cluster_in *in, pchip_cluster_out *out, int path)
+{
+    if (!s || !in || !out || nsets < 1) { pc_abi_set_last_error("pchip_cluster_update: settings, point sets and results for nsets >= 1 sets"); return 1; }
+    for (int r = 0; r < nsets; ++r) {
+        const pchip_cluster_in &I = in[r]; const pchip_cluster_out &O = out[r];
+        if (s[r].nDims < 1 || I.ncluster < 1 || I.nlive < 1 || !I.live || !I.live_logL || !I.live_cluster || I.nph < 0 || (I.nph > 0 && (!I.phantom || !I.ph_logL || !I.ph_cluster))) {
+            pc_abi_set_last_error("pchip_cluster_update: nDims >= 1, ncluster >= 1, nlive >= 1 slots with coordinates, logL and cluster, nph >= 0 rows with coordinates, logL and cluster");
+            return 1;
+        }
+        if (O.maxc < I.ncluster || O.nsplit_cap < 0 || !O.live_cluster || !O.live_pos || !O.cl_list || !O.cl_n || !O.imin_slot || !O.ph_count || !O.cl_uid || !O.logLp || !O.lse_ref ||
+            !O.lse_sum || !O.logXp || !O.logZp || !O.logZXp || !O.logZp2 || !O.logZpXp || !O.XpXq || (I.nph > 0 && !O.ph_cluster) ||
+            (O.nsplit_cap > 0 && (!O.split_child || !O.split_parent || !O.split_logfrac)) || !O.init) {
+            pc_abi_set_last_error("pchip_cluster_update: every array of the result but the scratch is needed, with room for maxc >= ncluster clusters");
+            return 1;
+        }
+        const int nscr = (O.scratch_Sm != nullptr) + (O.scratch_knn != nullptr) + (O.scratch_lab != nullptr);
+        if ((nscr != 0 && nscr != 3) || (nscr == 3 && O.scratch_cap < 1)) { pc_abi_set_last_error("pchip_cluster_update: the scratch is asked for with all three arrays and scratch_cap >= 1, or not at all"); return 1; }
+        for (int i = 0; i < I.nlive; ++i) if (I.live_cluster[i] < -1 || I.live_cluster[i] >= I.ncluster) { pc_abi_set_last_error("pchip_cluster_update: a live slot's cluster is -1 (dead) or 0 ... ncluster - 1"); return 1; }
+        for (int j = 0; j < I.nph; ++j) if (I.ph_cluster[j] < -1 || I.ph_cluster[j] >= I.ncluster) { pc_abi_set_last_error("pchip_cluster_update: a phantom row's cluster is -1 (no phantom) or 0 ... ncluster - 1"); return 1; }
+        if (s[r].nDims > 256) return 3;
+    }
+    if (path == 1) return cluster_door_many(s, nsets, in, out);
+    if (path != 0 || nsets != 1) return PCHIP_NO_SUCH_PATH;
+    const pchip_cluster_in &I = in[0]; pchip_cluster_out &O = out[0];
+    const int nc0 = I.ncluster, nlive = I.nlive, nph = I.nph;
+    const pchip_settings c = cluster_door_settings(*s, nlive);
+    pchip_like like; std::memset(&like, 0, sizeof(like)); like.kind = PC_LIKE_GAUSSIAN; like.mu = 0.5; like.sigma = 1.0;
+    pchip_prior prior; std::memset(&prior, 0, sizeof(prior)); prior.kind = 1;
+    Engine E;
+    int rc = 0;
+    try {
+        E.setup(c, like, prior);
+        std::vector<int> cn;
+        cluster_door_install(E, I, O.init, cn);
+        const int Ncap = E.S.Ncap;
+        // the update's clustering, as Engine::do_update makes it
+        ClusterTap tap{O.scratch_Sm, O.scratch_knn, O.scratch_lab, O.scratch_cap, 0};
+        ClusterTap *tp = O.scratch_Sm ? &tap : nullptr;
+        if (E.sub_dims.empty()) E.clus.do_clustering(cn, nullptr, 0, nullptr, tp);
+        else {
+            std::vector<int> map1, map2;
+            bool found = E.clus.do_clustering(cn, E.c_subdims, (int)E.sub_dims.size(), &map1, tp);
+            if (found) cn.clear();
+            found = E.clus.do_clustering(cn, nullptr, 0, &map2) || found;
+            cluster_map_compose(map1, map2);
+            if (found && !E.cfg.epoch_discard) E.clus.remap_nursery(map1, nc0);
+        }
+        HIPCHK(hipStreamSynchronize(E.st));
+        HIPCHK(hipGetLastError());
+        // the state after it (E.S: a split may have moved the per-cluster arrays)
+        const int nc = E.h_ctl->ncluster, mc = E.S.maxc, nsp = (int)E.split_child.size();
+        O.ncluster = nc; O.nsplit = nsp; O.levels = (int)E.clus.levels; O.scratch_n = tap.n;
+        if (nc > O.maxc || nsp > O.nsplit_cap) engine_fail(PC_RC_LIMIT, "pchip_cluster_update: %d clusters and %d genealogy entries after the update, the caller's arrays hold %d and %d", nc, nsp, O.maxc, O.nsplit_cap);
+        auto down = [&](auto *dst, const auto *src, size_t n) { if (n) HIPCHK(hipMemcpy(dst, src, sizeof(*dst) * n, hipMemcpyDeviceToHost)); };
+        down(O.live_cluster, E.S.live_cluster, (size_t)nlive); down(O.live_pos, E.S.live_pos, (size_t)nlive);
+        down(O.cl_n, E.S.cl_n, (size_t)nc); down(O.imin_slot, E.S.imin_slot, (size_t)nc); down(O.cl_uid, E.S.cl_uid, (size_t)nc);
+        down(O.logLp, E.S.logLp, (size_t)nc); down(O.lse_ref, E.S.lse_ref, (size_t)nc); down(O.lse_sum, E.S.lse_sum, (size_t)nc);
+        down(O.logXp, E.S.logXp, (size_t)nc); down(O.logZp, E.S.logZp, (size_t)nc); down(O.logZXp, E.S.logZXp, (size_t)nc);
+        down(O.logZp2, E.S.logZp2, (size_t)nc); down(O.logZpXp, E.S.logZpXp, (size_t)nc);
+        for (int a = 0; a < nc; ++a) down(O.XpXq + (size_t)a * O.maxc, E.S.XpXq + (size_t)a * mc, (size_t)nc);
+        for (int k = 0, at = 0; k < nc; ++k) {
+            if (O.cl_n[k] < 0 || at + O.cl_n[k] > nlive) engine_fail(PC_RC_DEVICE, "pchip_cluster_update: the clusters' sizes after the update do not add up to the live slots");
+            down(O.cl_list + at, E.S.cl_list + (size_t)k * Ncap, (size_t)O.cl_n[k]); at += O.cl_n[k];
+        }
+        for (int k = 0; k < nc; ++k) O.ph_count[k] = -1;
+        if (E.nsplits > 0) down(O.ph_count, E.clus.c_cnt, (size_t)nc);
+        if (nph > 0) {
+            std::vector<unsigned> cu(nph);
+            down(cu.data(), E.S.ph_cuid, (size_t)nph);
+            for (int j = 0; j < nph; ++j) {
+                O.ph_cluster[j] = -1;
+                for (int k = 0; k < nc; ++k) if (cu[j] == O.cl_uid[k]) O.ph_cluster[j] = k;
+            }
+        }
+        for (int k = 0; k < nsp; ++k) { O.split_child[k] = E.split_child[k]; O.split_parent[k] = E.split_parent[k]; O.split_logfrac[k] = E.split_logfrac[k]; }
+    } catch (const EngineError &e) {
+        std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str());
+        (void)hipGetLastError();
+        rc = e.code;
+    }
+    E.destroy();
+    return rc;
+}
+
 // the batch callback that is registered now (polychord_hip_set_batch_callback): the doors put theirs in only where the caller has none
 void pc_batch_callback_get(polychord_batch_fn *fn, void **user) { std::lock_guard<std::mutex> g(g_cb_mutex); if (fn) *fn = g_batch_fn; if (user) *user = g_batch_user; }
 

@@ -202,6 +202,10 @@ inline void cluster_map_split_at(std::vector<int> &cmap, int p) { for (int &m : 
 // two passes in one update: map1 through the first, map2 from the list after it through the second
 inline void cluster_map_compose(std::vector<int> &map1, const std::vector<int> &map2) { for (int &m : map1) m = m >= 0 ? map2[(size_t)m] : -1; }
 
+// What a caller may ask of a pass (the kernel-level door pchip_cluster_update, for its tests): host arrays for the first pass's similarity block,
+// neighbour lists (cap x cap each) and first-level labels (cap) of the first cluster the pass looks at; n: its points, set by the pass
+struct ClusterTap { double *Sm; int *knn, *lab; int cap, n; };
+
 // ---- the device's scratch and the traffic ---------------------------------------------------------------------------------------------
 
 template <class Eng> struct ClusterUpdate {
@@ -214,6 +218,7 @@ template <class Eng> struct ClusterUpdate {
     int *c_gdesc = nullptr, *c_gpool = nullptr, *c_glab = nullptr, *c_gout = nullptr; int c_g_cap = 0;      // a level of the recursion
     int *c_map = nullptr; int c_map_cap = 0;                                                       // the cluster map for the nursery's chains
     ClusterMirror cmir;
+    long levels = 0;                                                                               // levels of the recursion launched so far
 
     void ensure_scratch()
     {
@@ -277,6 +282,7 @@ template <class Eng> struct ClusterUpdate {
         while (parts.work_left()) {
             const PartRefiner::Level &lev = parts.next_level();
             const int nb = lev.nb, npool = (int)lev.pool.size();
+            levels++;
             // (the parts of a cluster are disjoint: their neighbour lists fit where the first pass' did)
             if (lev.koff > (long long)c_cap * c_cap) engine_fail(PC_RC_DEVICE, "clustering: the parts' neighbour lists (%lld entries) exceed the scratch of %d points", lev.koff, c_cap);
             if (c_g_cap < std::max(nb, npool)) {
@@ -300,8 +306,9 @@ template <class Eng> struct ClusterUpdate {
     // and the verdicts back: two host waits per update); the clusters in which it finds more than one group are refined level by level
     // and split by add_cluster, in the reference's order.  cn: the clusters' sizes (asked for here when they are not the list's).
     // dims / nd_sub: the coordinates of the sub-dimension pass (nd_sub = 0: all).  cmap_out: the pass leaves the map of the list's clusters
-    // through it there and does not move the nursery's chains itself (two passes in one update: the caller composes the two maps)
-    bool do_clustering(std::vector<int> cn = std::vector<int>(), const int *dims = nullptr, int nd_sub = 0, std::vector<int> *cmap_out = nullptr)
+    // through it there and does not move the nursery's chains itself (two passes in one update: the caller composes the two maps).
+    // tap: the first pass's scratch of its first cluster goes to the caller's arrays, in a wait of its own before a level overwrites the lists
+    bool do_clustering(std::vector<int> cn = std::vector<int>(), const int *dims = nullptr, int nd_sub = 0, std::vector<int> *cmap_out = nullptr, ClusterTap *tap = nullptr)
     {
         ensure_scratch();
         bool found = false;
@@ -326,6 +333,13 @@ template <class Eng> struct ClusterUpdate {
             ask_mirror();                                            // (and what a split will read, should the pass find one)
             e.fetch_wait();
             cmir.valid = true;
+            if (tap) {
+                const size_t n = (size_t)fp.desc[1];
+                if ((int)n > tap->cap) engine_fail(PC_RC_LIMIT, "the first cluster's scratch was asked for with room for %d points; it has %d", tap->cap, (int)n);
+                tap->n = (int)n;
+                e.fetch_raw(tap->Sm, c_Sm, sizeof(double) * n * n); e.fetch_raw(tap->knn, c_knn, sizeof(int) * n * n); e.fetch_raw(tap->lab, c_lab, sizeof(int) * n);
+                e.fetch_wait();
+            }
             PartRefiner parts;
             parts.open(fp, out, lab0);
             refine(parts);

@@ -22,7 +22,8 @@ def test_library_exports_declared_symbols():
     from polychordlite_amd import _ctypes_api as api
     lib = api.load()
     names = _declared()
-    assert {"polychord_c_interface", "polychord_c_interface_ini", "pchip_run", "pchip_slice_chains", "pchip_directions"} <= names
+    assert {"polychord_c_interface", "polychord_c_interface_ini", "pchip_run", "pchip_slice_chains", "pchip_directions",
+            "pchip_update_factors", "pchip_cluster_update"} <= names
     for n in sorted(names):
         assert hasattr(lib, n), f"{n} declared in include/ but not exported"
 
