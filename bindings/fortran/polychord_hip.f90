@@ -17,6 +17,7 @@ module polychord_hip
               polychord_hip_table_prior, polychord_hip_set_table_prior, pchip_prior_entry, &
               polychord_hip_set_option, polychord_hip_set_sub_clustering, run_polychord_hip, &
               polychord_hip_set_source, polychord_hip_source_loglike, polychord_hip_source_prior, &
+              polychord_hip_set_device_batch_callback, &
               pchip_source_create, pchip_source_create_shared, pchip_source_destroy
 
     !> one parameter of a prior table (pchip_prior_entry of polychord_hip.h): the reference's type number 1 .. 15 (priors.f90:5-20),
@@ -109,6 +110,15 @@ module polychord_hip
             import :: c_int
             integer(c_int), value :: n
             integer(c_int) :: dims(*)
+        end subroutine
+        !> A likelihood that already lives on the GPU (polychord_hip.h: polychord_device_batch_fn): fn is the c_funloc of a
+        !! bind(c) function(user, n, nDims, nDerived, d_cube, d_theta, d_phi, d_logL, flags, stream) result(rc) -- integer(c_int) by value,
+        !! type(c_ptr) by value for user, the four DEVICE pointers and the engine's stream -- called once per round with the parked
+        !! proposals as one dense block in device memory; rc /= 0 ends the run.  Sticky; c_null_funptr removes it
+        subroutine polychord_hip_set_device_batch_callback(fn, user) bind(c, name="polychord_hip_set_device_batch_callback")
+            import :: c_funptr, c_ptr
+            type(c_funptr), value :: fn
+            type(c_ptr), value :: user
         end subroutine
         !> The caller's own likelihood as HIP device source (polychord_hip.h: pchip_source_create), compiled at run time and evaluated
         !! inside the sampling kernels: source and options NUL terminated (options: c_null_char alone for none), block(ndata) the data block

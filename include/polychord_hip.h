@@ -124,6 +124,27 @@ void polychord_hip_source_prior(double *cube, double *theta, int nDims);
 typedef void (*polychord_batch_fn)(void *user, int n, int nDims, int nDerived, const double *cube, double *theta, double *phi,
                                    double *logL);
 void polychord_hip_set_batch_callback(polychord_batch_fn fn, void *user);
+/* The batch callback for likelihoods that already live on the GPU (a tensor program, a pipeline of library calls): the parked proposals
+ * of a round are packed into one dense block in DEVICE memory, in ascending chain order, and the answers are read where the callback
+ * wrote them -- no row visits the host; the host reads one int per round.
+ * flags bit 0: d_theta already holds the prior transform of d_cube (the run's prior is the box or a table: evaluated by the engine
+   on the device); otherwise the callback writes d_theta from d_cube, as the host batch callback does.
+   All pointers are device memory of the run's device, row-major, dense: cube, theta [n][nDims], phi [n][max(1,nDerived)], logL [n].
+   stream: the engine's hipStream_t.  On return the callback's work is either complete or enqueued on `stream` (work on another
+   stream: make `stream` wait for it, or synchronise, before returning).  logL[i] <= logzero marks an invalid point.
+   The blocks are valid in the order of `stream` as well: what fills them (the live points' draws, the engine's prior) may still be
+   running when the callback is entered, so work that is NOT enqueued on `stream` -- a blocking hipMemcpy included -- first waits for it.
+   Returns 0; non-zero ends the run like polychord_hip_request_stop.
+ * Process-global and sticky like the host batch callback, read when a run starts; NULL removes it.  Only in callback mode
+ * (like.kind == PCHIP_LIKE_CALLBACK) of pchip_run / pchip_run_hooks and the doors on top of them; with both batch callbacks registered this
+ * one wins.  The scalar callbacks must still be valid (the maximiser, cube_samples, single evaluations).  prior.kind 0 (a host function):
+ * the callback owns the prior, flags 0; prior.kind 1 / 2: the engine's transform, the bits of the sampling kernels' box and of
+ * pchip_prior_transform, flags 1 (nDims <= 256); prior.kind 3 stays refused with a callback likelihood.  The live points are drawn on the
+ * device from the Philox coordinates of the host path, so a run is the host batch callback's run of the same functions.
+ * pchip_result.path[PCHIP_PATH_DEVICE_BATCH] counts the calls. */
+typedef int (*polychord_device_batch_fn)(void *user, int n, int nDims, int nDerived, const double *d_cube, double *d_theta,
+                                         double *d_phi, double *d_logL, int flags, void *stream);
+void polychord_hip_set_device_batch_callback(polychord_device_batch_fn fn, void *user);
 /* asks a running engine to stop at the next host callback boundary (used by language bindings when a
  * user callback raised: the reference throws through the Fortran frames, _pypolychord.cpp:219-224) */
 void polychord_hip_request_stop(void);
@@ -306,6 +327,7 @@ enum { PCHIP_PATH_CONSUME_PAR = 0,      /* one cluster: the parallel contraction
        PCHIP_PATH_SOURCE_TERMS = 21,        /* ... of those of slot 19, the launches whose kernels took the terms form of a source (pchip_source_create_terms) */
        PCHIP_PATH_SLICE_STEP = 22,          /* runs in step: nurseries whose sampling kernel was launched ONCE for several runs (whichever kernel: k_slice_many,
                                                k_slice_t_many); 0 for a run on its own, a group of one, a shape each run launches for itself */
+       PCHIP_PATH_DEVICE_BATCH = 23,        /* calls of the device batch callback (polychord_hip_set_device_batch_callback); 0 on every other run */
        PCHIP_PATH_COUNT = 24 };
 
 /* snapshot handed to the update hook: what the reference's file writers see at every update
@@ -706,6 +728,12 @@ typedef struct {
     double *scratch_Sm; int *scratch_knn, *scratch_lab;    /* optional */
 } pchip_cluster_out;
 int  pchip_cluster_update(const pchip_settings *s, int nsets, const pchip_cluster_in *in, pchip_cluster_out *out, int path);
+
+/* The pack of the device batch callback alone (tests/test_park_pack.py), host arrays in and out, the product's two kernels in between:
+ * need [nchains] (a chain waits for an answer: non-zero), prop [nchains][nDims]  ->  rank [nchains] (the ascending enumeration of the chains
+ * with need, -1 for the others), *count, and cube [>= count][nDims]: row rank[c] = prop[c].  Rows of `cube` from count on are not written.
+ * 0, or 1 (arguments) / 2 (device). */
+int  pchip_park_pack(int nchains, int nDims, const int *need, const double *prop, int *rank, int *count, double *cube, int device);
 
 #ifdef __cplusplus
 }

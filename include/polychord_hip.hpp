@@ -45,6 +45,12 @@ struct Settings {
         : nDims(_nDims), nDerived(_nDerived), num_repeats(_nDims * 5), grade_frac{1.0}, grade_dims{_nDims} {}
 };
 
+// A likelihood that already lives on the GPU (a tensor program, hipBLAS / rocFFT calls): registered here, the parked proposals of every
+// round of the next run_polychord calls reach it as ONE dense block in device memory, with the engine's stream, and its answers are read
+// where it wrote them (polychord_hip.h: polychord_device_batch_fn has the contract -- flags bit 0, the stream rule, the return value).
+// Sticky and process-global; nullptr removes it.  The scalar loglikelihood passed to run_polychord must still be valid.
+inline void set_device_batch_callback(polychord_device_batch_fn fn, void *user = nullptr) { polychord_hip_set_device_batch_callback(fn, user); }
+
 inline double default_loglikelihood(double *, int, double *, int) { return 0.0; }
 inline void default_prior(double *cube, double *theta, int nDims) { for (int i = 0; i < nDims; ++i) theta[i] = cube[i]; }
 inline void default_dumper(int, int, int, double *, double *, double *, double, double) {}

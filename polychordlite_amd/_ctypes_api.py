@@ -92,6 +92,63 @@ class Maximum(C.Structure):
 PATH_NAMES = ("consume_par", "consume_cl", "consume_general", "consume_fast", "killoff_par", "killoff_cl", "killoff_general",
               "killoff_fast", "update_fused", "update_steps", "slice_wave", "slice_lane", "nn_lists", "nn_fallbacks", "pool_mode",
               "defer_update", "consume_cl_serial", "subcluster_passes", "subcluster_splits", "source_kernels", "device_prior", "source_terms", "slice_step")
+# ... and the counter behind them, kept beside the tuple (tests pin the tuple's length to the kernel variants): calls of the device batch
+# callback, PCHIP_PATH_DEVICE_BATCH; result_dict puts it into the same `path` dict as "device_batch"
+PATH_DEVICE_BATCH = 23
+
+# polychord_device_batch_fn (include/polychord_hip.h): user, n, nDims, nDerived, d_cube, d_theta, d_phi, d_logL, flags, stream -> 0 / stop.
+# The pointers are DEVICE memory: plain addresses here.
+DEVICE_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
+_device_batch_cb = None
+
+
+def set_device_batch_callback(fn):
+    """polychord_hip_set_device_batch_callback: fn(user, n, nDims, nDerived, d_cube, d_theta, d_phi, d_logL, flags, stream) -> int, called
+    with device addresses (see DeviceBlock) once per round of a callback-likelihood run; None removes it.  Process-global and sticky; the
+    ctypes thunk is kept alive here until the next call.  A DEVICE_BATCH_FN is taken as it is."""
+    global _device_batch_cb
+    lib = load()
+    cb = None if fn is None else (fn if isinstance(fn, DEVICE_BATCH_FN) else DEVICE_BATCH_FN(fn))
+    lib.polychord_hip_set_device_batch_callback.argtypes = [C.c_void_p, C.c_void_p]
+    lib.polychord_hip_set_device_batch_callback.restype = None
+    lib.polychord_hip_set_device_batch_callback(C.cast(cb, C.c_void_p) if cb is not None else None, None)
+    _device_batch_cb = cb
+    return cb
+
+
+class DeviceBlock:
+    """A dense row-major float64 block of device memory the library handed out, for consumers of `__cuda_array_interface__` (version 3:
+    torch.as_tensor, cupy.asarray -- zero copy).  ptr: the device address; shape: a tuple of ints; stream: the hipStream_t the block is valid
+    on (None or 0: no `stream` entry, the consumer synchronises nothing)."""
+
+    def __init__(self, ptr, shape, stream=None, readonly=False):
+        self.ptr, self.shape, self.stream, self.readonly = int(ptr or 0), tuple(int(v) for v in shape), (int(stream) if stream else None), readonly
+
+    @property
+    def __cuda_array_interface__(self):
+        d = {"shape": self.shape, "typestr": "<f8", "data": (self.ptr, bool(self.readonly)), "version": 3, "strides": None}
+        if self.stream:
+            d["stream"] = self.stream
+        return d
+
+
+def park_pack(need, prop, cube=None, device=-1):
+    """pchip_park_pack: the pack of the device batch callback alone.  need [nchains] ints, prop [nchains][nDims]; cube: the block the rows are
+    written into ([nchains][nDims], changed in place; None: zeros).  Returns rank [nchains], count, cube."""
+    lib = load()
+    nd = np.ascontiguousarray(need, dtype=np.int32)
+    pr = np.ascontiguousarray(prop, dtype=np.float64)
+    out = np.zeros_like(pr) if cube is None else cube
+    assert out.flags.c_contiguous and out.dtype == np.float64 and out.shape == pr.shape
+    rank = np.empty(nd.size, dtype=np.int32)
+    cnt = C.c_int(-1)
+    ip = C.POINTER(C.c_int)
+    lib.pchip_park_pack.argtypes = [C.c_int, C.c_int, ip, C.POINTER(C.c_double), ip, ip, C.POINTER(C.c_double), C.c_int]
+    lib.pchip_park_pack.restype = C.c_int
+    rc = lib.pchip_park_pack(pr.shape[0], pr.shape[1], nd.ctypes.data_as(ip), dptr(pr), rank.ctypes.data_as(ip), C.byref(cnt), dptr(out), device)
+    if rc:
+        raise RuntimeError(f"pchip_park_pack failed with code {rc}")
+    return rank, cnt.value, out
 
 
 _lib = None
@@ -651,7 +708,7 @@ def result_dict(r, settings):
                post_mean=np.ctypeslib.as_array(r.post_mean, shape=(D + settings.nDerived,)).copy(),
                post_var=np.ctypeslib.as_array(r.post_var, shape=(D + settings.nDerived,)).copy(),
                nlike_grade=[int(v) for v in r.nlike_grade], nlike_failed=r.nlike_failed, ncluster_peak=r.ncluster_peak, epoch_discard=r.epoch_discard, n_records=int(r.n_records) if r.d_records else None,
-               path={n: int(r.path[i]) for i, n in enumerate(PATH_NAMES)},
+               path=dict({n: int(r.path[i]) for i, n in enumerate(PATH_NAMES)}, device_batch=int(r.path[PATH_DEVICE_BATCH])),
                varlogZp=np.ctypeslib.as_array(r.varlogZp, shape=(max(r.nZp, 1),))[:r.nZp].copy(),
                logzero=settings.logzero,
                _owner=own)          # the pchip_result itself (merge.comm_merge hands it back to the library)

@@ -793,12 +793,13 @@ static void c_interface_impl(
     } else if (prior == polychord_hip_uniform_prior) {
         P.kind = 1;
         if (G.up_D == nDims) { P.lo = G.up_lo.data(); P.hi = G.up_hi.data(); }
-    } else if (prior == polychord_hip_table_prior && G.device_prior && L.kind != PCHIP_LIKE_CALLBACK) {
-        // a prior table with a built-in likelihood: both on the device (a table that is a box runs as the box: Engine::setup)
+    } else if (prior == polychord_hip_table_prior && G.device_prior && (L.kind != PCHIP_LIKE_CALLBACK || pc_device_batch_registered())) {
+        // a prior table with a built-in likelihood: both on the device (a table that is a box runs as the box: Engine::setup); with a
+        // callback likelihood behind a device batch callback: the engine transforms the packed blocks (flags bit 0)
         if (G.table.D != nDims) halt_program("polychord_hip: polychord_hip_set_table_prior was not called for this nDims");
         P.kind = PCHIP_PRIOR_TABLE; P.table = G.table.e.data(); P.hyper = G.table.hyper.data(); P.fn = prior;
     } else { P.kind = 0; P.fn = prior; }
-    const bool table_on_device = P.kind == PCHIP_PRIOR_TABLE && !G.table.is_box;
+    const bool table_on_device = P.kind == PCHIP_PRIOR_TABLE && !G.table.is_box && L.kind != PCHIP_LIKE_CALLBACK;
     const std::string base = base_dir ? base_dir : "chains", root = file_root ? file_root : "test";
     if (write_stats_f || write_dead || write_live || posteriors || equals || write_prior || write_resume) {
         struct stat sb;

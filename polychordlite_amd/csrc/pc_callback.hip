@@ -22,14 +22,18 @@ struct PcChain {
 // One wavefront per chain, lane = cube coordinate (d, d + 64, ...): a proposal, an acceptance or a row store touches all
 // coordinates in one round trip (one thread per chain walked them one global access at a time: 68 us per tick at 20-D).
 // Everything that steers the state machine is wave-uniform.
+// DEV (the device batch callback, pc_park.hip): nothing is stored to the host -- the proposals stay in `prop`, the need flag in PcChain::need --
+// and the answers are dense blocks in the order of the last pack: chain c's row is rank[c] (prop_host / need_host are null, rank is not).
+template <bool DEV>
 __global__ __launch_bounds__(64) void k_slice_tick(PcState S, unsigned batch, int nchains, PcChain *cs, double *x0s /* [B][D] */,
                                                   int *decks /* [B][nr] */, double *prop /* [B][D] */,
                                                   const double *ev_logL, const double *ev_theta, const double *ev_phi,
-                                                  int first, double *prop_host, int *need_host)
+                                                  int first, double *prop_host, int *need_host, const int *rank)
 {   // prop_host / need_host: pinned host memory; the proposals and the need flags are stored there directly (posted
     // writes over PCIe), so that the host finds them after one stream synchronisation, without copies
     const int chain = blockIdx.x, lane = threadIdx.x;
     if (chain >= nchains) return;
+    const int arow = DEV ? rank[chain] : chain;          // this chain's row in the answers (DEV: read only behind need or ok_theta, when it is a rank)
     const int D = S.D, nr = S.nr, nT = S.nT;
     PcChain c = cs[chain];
     double *x0 = x0s + (size_t)chain * D;
@@ -55,7 +59,7 @@ __global__ __launch_bounds__(64) void k_slice_tick(PcState S, unsigned batch, in
     double logL = 0.0;
     bool have = false;
     if (c.need) {                                        // the host answered the parked proposal
-        logL = ev_logL[chain];
+        logL = ev_logL[arow];
         if (logL > S.logzero) {
             c.nlike++;
             if (S.ngrade > 1 && lane == 0) S.ch_nlike_g[(size_t)chain * PC_MAX_GRADE + pc_grade_of(S, deck[c.s])]++;   // chordal_sampling.f90:84
@@ -68,8 +72,12 @@ __global__ __launch_bounds__(64) void k_slice_tick(PcState S, unsigned batch, in
     auto propose = [&](double t) {
         c.t = t;
         bool outside = false;
+        if constexpr (DEV) {
+            for (int d = lane; d < D; d += 64) { const double v = x0[d] + t * nh[d]; pc[d] = v; outside |= (v < 0.0) | (v > 1.0); }
+        } else {
         double *ph = prop_host + (size_t)chain * D;
         for (int d = lane; d < D; d += 64) { const double v = x0[d] + t * nh[d]; pc[d] = v; ph[d] = v; outside |= (v < 0.0) | (v > 1.0); }
+        }
         if (__ballot(outside) != 0ull) { logL = S.logzero; have = true; c.ok_theta = 0; return false; }   // calculate.f90:36-38
         c.need = 1; have = false;
         return true;
@@ -133,9 +141,9 @@ __global__ __launch_bounds__(64) void k_slice_tick(PcState S, unsigned batch, in
             double *row = S.babies + ((size_t)chain * nr + c.s) * nT;
             for (int d = lane; d < D; d += 64) {
                 const double v = pc[d];
-                x0[d] = v; row[d] = v; row[S.p0 + d] = c.ok_theta ? ev_theta[(size_t)chain * D + d] : 0.0;
+                x0[d] = v; row[d] = v; row[S.p0 + d] = c.ok_theta ? ev_theta[(size_t)arow * D + d] : 0.0;
             }
-            for (int e = lane; e < S.nDer; e += 64) row[S.d0 + e] = c.ok_theta ? ev_phi[(size_t)chain * S.nDer + e] : 0.0;
+            for (int e = lane; e < S.nDer; e += 64) row[S.d0 + e] = c.ok_theta ? ev_phi[(size_t)arow * S.nDer + e] : 0.0;
             if (lane == 0) {
                 row[S.b0] = c.contour; row[S.l0] = c.lnew;
                 S.baby_logL[(size_t)chain * nr + c.s] = c.lnew; S.baby_logL_T[(size_t)c.s * S.B + chain] = c.lnew;
@@ -148,7 +156,7 @@ __global__ __launch_bounds__(64) void k_slice_tick(PcState S, unsigned batch, in
     }
     if (lane == 0) {
         if (c.phase == CB_DONE) S.ch_nlike[chain] = c.nlike;
-        need_host[chain] = c.need;
+        if constexpr (!DEV) need_host[chain] = c.need;
         cs[chain] = c;
     }
 }
@@ -157,8 +165,18 @@ extern "C" void pc_launch_slice_tick(const PcState *S, unsigned batch, int nchai
                                      const double *ev_logL, const double *ev_theta, const double *ev_phi, int first, double *prop_host,
                                      int *need_host, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_slice_tick, dim3(nchains), dim3(64), 0, st, *S, batch, nchains, (PcChain *)cs, x0s, decks, prop,
-                       ev_logL, ev_theta, ev_phi, first, prop_host, need_host);
+    hipLaunchKernelGGL(k_slice_tick<false>, dim3(nchains), dim3(64), 0, st, *S, batch, nchains, (PcChain *)cs, x0s, decks, prop,
+                       ev_logL, ev_theta, ev_phi, first, prop_host, need_host, (const int *)nullptr);
 }
+// the tick of the device batch callback: the answers of the last round at their ranks, nothing to the host (pc_park.hip packs what it parks)
+extern "C" void pc_launch_slice_tick_dev(const PcState *S, unsigned batch, int nchains, void *cs, double *x0s, int *decks, double *prop,
+                                         const double *ev_logL, const double *ev_theta, const double *ev_phi, int first, const int *rank,
+                                         hipStream_t st)
+{
+    hipLaunchKernelGGL(k_slice_tick<true>, dim3(nchains), dim3(64), 0, st, *S, batch, nchains, (PcChain *)cs, x0s, decks, prop,
+                       ev_logL, ev_theta, ev_phi, first, (double *)nullptr, (int *)nullptr, rank);
+}
+// where a chain's need flag lies in its state record, in ints (the pack's index kernel reads it there)
+extern "C" void pc_chain_need_layout(int *stride, int *offset) { *stride = (int)(sizeof(PcChain) / sizeof(int)); *offset = (int)(offsetof(PcChain, need) / sizeof(int)); }
 
 extern "C" size_t pc_chain_state_size(void) { return sizeof(PcChain); }

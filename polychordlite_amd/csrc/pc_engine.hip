@@ -61,6 +61,8 @@ static std::atomic<int> g_inject_fault{0};           // polychord_hip_set_option
 static std::mutex g_cb_mutex;
 static polychord_batch_fn g_batch_fn = nullptr;     // polychord_hip_set_batch_callback
 static void *g_batch_user = nullptr;
+static polychord_device_batch_fn g_dbatch_fn = nullptr;     // polychord_hip_set_device_batch_callback
+static void *g_dbatch_user = nullptr;
 static std::mutex g_run_mutex;
 static std::vector<std::atomic<int> *> g_run_stop;  // stop flags of the runs in flight
 extern "C" double polychord_hip_keyed_uniform(unsigned seed, unsigned dom, unsigned shi, unsigned slo, unsigned idx);
@@ -374,6 +376,13 @@ struct Engine {
     // answers (logL | theta | phi of every chain, one block) go back in one copy
     double *hp_prop = nullptr, *hp_ans = nullptr, *d_ans = nullptr; int *hp_need = nullptr;
     long long cb_evals = 0; long cb_ticks = 0;
+    // the device batch callback registered when the run was set up (it wins over batch_fn): the parked proposals of a round packed into
+    // dense device blocks, the answers read at the chains' ranks (pc_park.hip) -- the host reads *hp_count a round and nothing else
+    polychord_device_batch_fn dbatch_fn = nullptr; void *dbatch_user = nullptr;
+    bool dev_batch = false; int db_flags = 0;              // db_flags bit 0: the engine evaluates the prior (box or table) on the blocks
+    PcState S_pri{};                                       // ... the state k_prior_transform reads for it (nDims, the prior, the table's mask)
+    double *db_cube = nullptr, *db_theta = nullptr, *db_phi = nullptr, *db_logL = nullptr;
+    int *db_rank = nullptr, *db_count = nullptr, *hp_count = nullptr, *hp_count_dev = nullptr;
     std::vector<int> cb_idx; std::vector<double> cb_c, cb_t, cb_p, cb_l;   // batch callback scratch
     // host mirror of the dead points for the dumper hook (nested_sampling.F90:546-590)
     polychord_dumper_fn dumper = nullptr;
@@ -450,7 +459,7 @@ struct Engine {
     void setup(const pchip_settings &c, const pchip_like &like, const pchip_prior &prior)
     {
         cfg = c;
-        { std::lock_guard<std::mutex> g(g_cb_mutex); batch_fn = g_batch_fn; batch_user = g_batch_user; }
+        { std::lock_guard<std::mutex> g(g_cb_mutex); batch_fn = g_batch_fn; batch_user = g_batch_user; dbatch_fn = g_dbatch_fn; dbatch_user = g_dbatch_user; }
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
             engine_fail(PC_RC_DEVICE, "no HIP device available -- this engine has no CPU path");
@@ -604,6 +613,27 @@ struct Engine {
             upload(d_hi, ti.data(), sizeof(int) * ti.size());
             S.prior.lo = d_lo; S.prior.hi = d_hi; S.src_pad = (int)ptab.mask;
         }
+        // The device batch callback: a callback likelihood only.  Under the box or a table the engine transforms the packed cubes itself
+        // (flags bit 0), by k_prior_transform on a state of its own -- the sampling state of callback mode carries no table.
+        dev_batch = dbatch_fn != nullptr && like.kind == PC_LIKE_CALLBACK;
+        db_flags = 0;
+        if (dev_batch) {
+            std::memset(&S_pri, 0, sizeof(S_pri));
+            S_pri.D = D;
+            if (prior_kind == 1) { S_pri.prior.kind = 1; S_pri.prior.lo = d_lo; S_pri.prior.hi = d_hi; db_flags = 1; }
+            else if (prior_kind == PCHIP_PRIOR_TABLE) {
+                const std::vector<double> tp = ptab.dev_par(); const std::vector<int> ti = ptab.dev_int();
+                d_lo = blocks.dev<double>(tp.size()); d_hi = blocks.dev<double>((ti.size() + 1) / 2);
+                upload(d_lo, tp.data(), sizeof(double) * tp.size());
+                upload(d_hi, ti.data(), sizeof(int) * ti.size());
+                S_pri.prior.kind = PCHIP_PRIOR_TABLE; S_pri.prior.lo = d_lo; S_pri.prior.hi = d_hi; S_pri.src_pad = (int)ptab.mask; db_flags = 1;
+            }
+            if (db_flags && D > 256) engine_fail(PC_RC_NDIMS, "the device batch callback under a device prior (box or table): nDims <= 256, not %d", D);
+            if (c.feedback >= 1) {
+                std::printf("likelihood evaluated on the device in batches through the caller's device callback; prior %s\n", db_flags ? "on the device" : "by the callback");
+                std::fflush(stdout);
+            }
+        }
         // state arrays
         const int Ncap = S.Ncap, maxc = S.maxc, nT = S.nT, nr = S.nr;
         S.live = blocks.dev<double>((size_t)Ncap * nT); S.live_logL = blocks.dev<double>(Ncap);
@@ -667,10 +697,21 @@ struct Engine {
         if (callback_mode) {
             d_cs = (void *)blocks.dev<char>(pc_chain_state_size() * B); d_x0s = blocks.dev<double>((size_t)B * D); d_prop = blocks.dev<double>((size_t)B * D);
             const size_t nans = (size_t)B * (1 + D + std::max(1, nDer));
+            if (dev_batch) {      // dense blocks for a nursery's round or the prior samples of the live points, whichever is more rows
+                const size_t cap = (size_t)std::max(B, nprior);
+                db_cube = blocks.dev<double>(cap * D); db_theta = blocks.dev<double>(cap * D); db_phi = blocks.dev<double>(cap * std::max(1, nDer));
+                db_logL = blocks.dev<double>(cap); db_rank = blocks.dev<int>(B); db_count = blocks.dev<int>(1);
+                hp_count = blocks.pin<int>(1); *hp_count = 0;
+                { void *dp = nullptr; HIPCHK(hipHostGetDevicePointer(&dp, hp_count, 0)); hp_count_dev = (int *)dp; }
+                HIPCHK(hipMemsetAsync(db_rank, 0xFF, sizeof(int) * B, st));
+                HIPCHK(hipMemsetAsync(db_phi, 0, sizeof(double) * cap * std::max(1, nDer), st));
+                d_decks = blocks.dev<int>((size_t)B * nr);
+            } else {
             d_ans = blocks.dev<double>(nans);
             d_decks = blocks.dev<int>((size_t)B * nr);
             hp_prop = blocks.pin<double>((size_t)B * D); hp_ans = blocks.pin<double>(nans); hp_need = blocks.pin<int>(B);
             std::memset(hp_ans, 0, sizeof(double) * nans); std::memset(hp_need, 0, sizeof(int) * B);
+            }
             HIPCHK(hipMemset(d_cs, 0, pc_chain_state_size() * B));
         }
         h_ctl = blocks.pin<PcCtl>(1);
@@ -1312,6 +1353,76 @@ struct Engine {
         }
     }
 
+    // ---- the device batch callback (polychord_hip_set_device_batch_callback): the blocks stay on the device ----
+    // prior (box or table: the engine's, on the block) + the caller's function for the n cubes in db_cube; everything is enqueued on the
+    // run's stream, nothing is waited for here
+    void device_eval_batch(int n)
+    {
+        if (db_flags && pc_launch_prior_transform(&S_pri, n, db_cube, db_theta, st)) engine_fail(PC_RC_NDIMS, "the device prior of the batch callback could not be launched (nDims = %d)", S.D);
+        path[PCHIP_PATH_DEVICE_BATCH]++;
+        cb_evals += n;
+        if (dbatch_fn(dbatch_user, n, S.D, S.nDer, db_cube, db_theta, db_phi, db_logL, db_flags, (void *)st) != 0) stop.store(1);
+    }
+
+    void generate_live_device()
+    {   // generate_live_callback without the host: the same attempts and Philox coordinates, drawn by k_live_cubes; only the logL values come
+        // down, to choose the valid rows, which k_live_gather puts together for k_install_live
+        const int nprior = cfg.nprior <= 0 ? cfg.nlive : cfg.nprior, nT = S.nT;
+        double *drows = blocks.dev<double>((size_t)nprior * nT), *h_l = blocks.pin<double>(nprior);
+        int *d_idx = blocks.dev<int>(nprior), *h_idx = blocks.pin<int>(nprior);
+        int have = 0; uint32_t attempt = 0; long long nlike = 0;
+        double t_eval = 0.0;
+        while (have < nprior) {
+            const int m = nprior - have;
+            pc_launch_live_cubes(&S, attempt, m, db_cube, st);
+            const auto te0 = std::chrono::steady_clock::now();
+            device_eval_batch(m);
+            if (stop.load(std::memory_order_relaxed)) return;      // (the blocks go back with the ledger)
+            HIPCHK(hipMemcpyAsync(h_l, db_logL, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            t_eval += std::chrono::duration<double>(std::chrono::steady_clock::now() - te0).count();
+            if (stop.load(std::memory_order_relaxed)) return;
+            int nv = 0;
+            for (int i = 0; i < m; ++i) if (h_l[i] > cfg.logzero) h_idx[nv++] = i;
+            if (nv > 0) {
+                HIPCHK(hipMemcpyAsync(d_idx, h_idx, sizeof(int) * nv, hipMemcpyHostToDevice, st));
+                pc_launch_live_gather(&S, nv, d_idx, db_cube, db_theta, db_phi, db_logL, drows + (size_t)have * nT, st);
+                HIPCHK(hipStreamSynchronize(st));                   // (h_idx and the blocks are written again by the next attempt)
+            }
+            have += nv; nlike += nv;
+            attempt += (uint32_t)m;
+            if (attempt > 1000u * (uint32_t)nprior + 100000u) engine_fail(PC_RC_SETTINGS, "could not generate live points (likelihood is logzero everywhere?)");
+        }
+        pc_launch_install_live(&S, drows, nprior, st);
+        h_ctl->nlike = nlike;
+        HIPCHK(hipMemcpyAsync(&S.ctl->nlike, &h_ctl->nlike, sizeof(long long), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        blocks.release(drows); blocks.release(h_l); blocks.release(d_idx); blocks.release(h_idx);
+        ndiscarded = (long)attempt - nprior;
+        cb_eval_seconds = attempt ? t_eval / attempt : -1.0;
+        call_dumper(2);
+        if (nprior > cfg.nlive) { pc_count(path, PcTrimLive{}); pc_launch_consume(&S, 2, 0, st); read_ctl(); }
+    }
+
+    // one nursery batch through the device callback.  A round: the tick (answers at the ranks of the last pack), the pack (index kernel,
+    // row kernel), ONE wait for the count, the prior on the block if it is the engine's, the caller's function
+    void slice_device(unsigned batch)
+    {
+        int first = 1, stride = 1, off = 0;
+        pc_chain_need_layout(&stride, &off);
+        while (true) {
+            pc_launch_slice_tick_dev(&S, batch, B, d_cs, d_x0s, d_decks, d_prop, db_logL, db_theta, db_phi, first, db_rank, st);
+            first = 0; cb_ticks++;
+            pc_launch_park_pack(B, S.D, (const int *)d_cs + off, stride, d_prop, db_rank, db_count, hp_count_dev, db_cube, st);
+            HIPCHK(hipStreamSynchronize(st));
+            if (stop.load(std::memory_order_relaxed)) return;
+            const int n = *(volatile int *)hp_count;
+            if (n == 0) break;
+            device_eval_batch(n);
+            if (stop.load(std::memory_order_relaxed)) return;
+        }
+    }
+
     void generate_live()
     {   // GenerateLivePoints (generate.F90:150-183): keep the first nprior valid prior samples
         const int nprior = cfg.nprior <= 0 ? cfg.nlive : cfg.nprior, nT = S.nT;
@@ -1626,7 +1737,7 @@ struct Engine {
                 resume_batch0 = (unsigned)rs.ndead;
             }
         }
-        if (!resumed) { if (callback_mode) generate_live_callback(); else generate_live(); }
+        if (!resumed) { if (dev_batch) generate_live_device(); else if (callback_mode) generate_live_callback(); else generate_live(); }
         if (stop.load(std::memory_order_relaxed)) return 5;
         if (cb_auto_batch && !(cb_eval_seconds >= 0.0 && cb_eval_seconds < 2e-6)) { B = B_small; S.B = B; }   // expensive (or unmeasured) callback
         r_t1 = clk::now();
@@ -1731,7 +1842,7 @@ struct Engine {
             switch (ch.sampler) {
             case PC_SAMPLER_CALLBACK:
                 if (co) co->flush();
-                slice_callback(batch);
+                if (dev_batch) slice_device(batch); else slice_callback(batch);
                 if (stop.load(std::memory_order_relaxed)) { r_rc = 5; return false; }
                 break;
             case PC_SAMPLER_LANE: { Cohort::Rec r = rec_slice(S, batch, B, bases_seq); r.note = co ? &step_note : nullptr; (void)stage(r); break; }
@@ -2196,6 +2307,7 @@ void pchip_trim_cache(void) { (void)hipDeviceSynchronize(); dcache().trim(); hca
 // both grow on demand, so these only matter to tests of the growth paths
 void pchip_set_capacity(int clusters, int phantom_rows) { if (clusters > 0) g_cap_clusters = clusters; if (phantom_rows >= 0) g_cap_phantoms = phantom_rows; }   // negative: leave as is
 void polychord_hip_set_batch_callback(polychord_batch_fn fn, void *user) { std::lock_guard<std::mutex> g(g_cb_mutex); g_batch_fn = fn; g_batch_user = user; }
+void polychord_hip_set_device_batch_callback(polychord_device_batch_fn fn, void *user) { std::lock_guard<std::mutex> g(g_cb_mutex); g_dbatch_fn = fn; g_dbatch_user = user; }
 
 double polychord_hip_keyed_uniform(unsigned seed, unsigned dom, unsigned shi, unsigned slo, unsigned idx)
 {   // the engine's counter RNG on the host (same numbers as pc_dev.h pc_uniform)
@@ -2430,6 +2542,39 @@ int pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const doub
     }
     if (rc) (void)hipGetLastError();
     (void)hipFree(d_tp); (void)hipFree(d_ti); (void)hipFree(d_c); (void)hipFree(d_t);
+    return rc;
+}
+
+// kernel-level entry for tests/test_park_pack.py: the pack of the device batch callback (k_park_index, k_park_rows) on host arrays
+int pchip_park_pack(int nchains, int nDims, const int *need, const double *prop, int *rank, int *count, double *cube, int device)
+{
+    if (nchains < 1 || nDims < 1 || !need || !prop || !rank || !count || !cube) { pc_abi_set_last_error("pchip_park_pack: nchains >= 1 flags and rows of nDims >= 1, and room for the ranks, the count and the rows"); return 1; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
+    if (hipSetDevice(device >= 0 ? device % ndev : 0) != hipSuccess) return 2;
+    const size_t nb = sizeof(double) * (size_t)nchains * nDims, ni = sizeof(int) * (size_t)nchains;
+    int *d_need = nullptr, *d_rank = nullptr, *d_count = nullptr, *h_count = nullptr; double *d_prop = nullptr, *d_cube = nullptr;
+    int rc = 2;
+    // (the caller's `cube` goes up first: the rows from count on come back as they were)
+    if (hipMalloc(&d_need, ni) == hipSuccess && hipMalloc(&d_rank, ni) == hipSuccess && hipMalloc(&d_count, sizeof(int)) == hipSuccess &&
+        hipMalloc(&d_prop, nb) == hipSuccess && hipMalloc(&d_cube, nb) == hipSuccess && hipHostMalloc(&h_count, sizeof(int)) == hipSuccess &&
+        hipMemcpy(d_need, need, ni, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_prop, prop, nb, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_cube, cube, nb, hipMemcpyHostToDevice) == hipSuccess) {
+        void *dp = nullptr;
+        *h_count = -1;
+        if (hipHostGetDevicePointer(&dp, h_count, 0) == hipSuccess) {
+            pc_launch_park_pack(nchains, nDims, d_need, 1, d_prop, d_rank, d_count, (int *)dp, d_cube, nullptr);
+            int dc = -2;
+            if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(rank, d_rank, ni, hipMemcpyDeviceToHost) == hipSuccess &&
+                hipMemcpy(&dc, d_count, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(cube, d_cube, nb, hipMemcpyDeviceToHost) == hipSuccess) {
+                *count = *(volatile int *)h_count;
+                rc = dc == *count ? 0 : 2;         // the device word and the pinned word are one number
+            }
+        }
+    }
+    if (rc) (void)hipGetLastError();
+    (void)hipFree(d_need); (void)hipFree(d_rank); (void)hipFree(d_count); (void)hipFree(d_prop); (void)hipFree(d_cube);
+    if (h_count) (void)hipHostFree(h_count);
     return rc;
 }
 
@@ -2813,6 +2958,8 @@ int pchip_cluster_update(const pchip_settings *s, int nsets, const pchip_cluster
 
 // the batch callback that is registered now (polychord_hip_set_batch_callback): the doors put theirs in only where the caller has none
 void pc_batch_callback_get(polychord_batch_fn *fn, void **user) { std::lock_guard<std::mutex> g(g_cb_mutex); if (fn) *fn = g_batch_fn; if (user) *user = g_batch_user; }
+// a device batch callback is registered now (polychord_hip_set_device_batch_callback): a callback likelihood's table prior then stays a table
+int pc_device_batch_registered(void) { std::lock_guard<std::mutex> g(g_cb_mutex); return g_dbatch_fn != nullptr; }
 
 
 // ---- the device maximiser: `maximise = T` for problems that live wholly on the device (k_max_rank, k_maximise: pc_sample.hip) -----------

@@ -58,6 +58,18 @@ void pc_abi_set_last_error(const char *msg);
 void pc_launch_slice_tick(const PcState *S, unsigned batch, int nchains, void *cs, double *x0s, int *decks, double *prop, const double *ev_logL,
                           const double *ev_theta, const double *ev_phi, int first, double *prop_host, int *need_host, hipStream_t st);
 size_t pc_chain_state_size(void);
+// the device batch callback's tick: answers read at rank[chain] of the dense blocks, nothing stored to the host
+void pc_launch_slice_tick_dev(const PcState *S, unsigned batch, int nchains, void *cs, double *x0s, int *decks, double *prop, const double *ev_logL,
+                              const double *ev_theta, const double *ev_phi, int first, const int *rank, hipStream_t st);
+void pc_chain_need_layout(int *stride, int *offset);
+// ---- pc_park.hip -------------------------------------------------------------------------------------------
+// rank [nchains] (ascending enumeration of the chains with a flag, -1 without), their number to *count and *count_host (device-visible
+// pinned word, or null), their cubes as rows of `cube` ([count][D]); flag of chain c at need[c * stride]
+void pc_launch_park_pack(int nchains, int D, const int *need, int stride, const double *prop, int *rank, int *count, int *count_host,
+                         double *cube, hipStream_t st);
+void pc_launch_live_cubes(const PcState *S, unsigned attempt0, int m, double *cube, hipStream_t st);
+void pc_launch_live_gather(const PcState *S, int n, const int *idx, const double *cube, const double *theta, const double *phi,
+                           const double *logL, double *rows, hipStream_t st);
 // ---- pc_clus.hip -------------------------------------------------------------------------------------------
 // 0: launched; 1: not this way (the caller takes the general kernel)
 int pc_launch_killoff_cl(const PcState *S, int nc, hipStream_t st);
@@ -120,6 +132,7 @@ void pc_source_batch_eval(void *user, int n, int nDims, int nDerived, const doub
 void pc_source_batch_close(void *user);
 // the batch callback registered now (polychord_hip_set_batch_callback)
 void pc_batch_callback_get(polychord_batch_fn *fn, void **user);
+int pc_device_batch_registered(void);
 // ---- pc_fast.hip -------------------------------------------------------------------------------------------
 // _fits: 1 where the kernel's LDS block fits; launchers: 0: launched; 1: not this way
 int pc_fast_fits(const PcState *S);
@@ -170,7 +183,8 @@ int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R, int nchai
 // ... and their directions for the shapes that do not split: 24 < nDims <= 64
 int pc_launch_nhats_many(const PcState *S, const PcManyRec *dR, int R, int nchains, hipStream_t st);
 int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t st);
-// pchip_prior_transform: the device transform of the table in S->prior at n points (device pointers)
+// pchip_prior_transform: the device transform of the table in S->prior at n points (device pointers); the device batch callback's prior:
+// a table, or the uniform box (S->prior.kind 1, lo / hi or null) as k_generate_live forms it
 int pc_launch_prior_transform(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st);
 // pchip_source_eval: a source likelihood at n points (device pointers), by the handle's run-time module
 int pc_launch_source_eval(const PcState *S, int n, const double *thetas, double *logL, double *phi, hipStream_t st);

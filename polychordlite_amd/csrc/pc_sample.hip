@@ -39,6 +39,10 @@ struct LaneDims {
 // An adaptive block's count (and layer) parameter is a uniform entry here: lo 0.5, span = the number of members (2).  Its members carry
 // pos = 1-based position among the members and len = their number; how many of them are order statistics is the POINT's (pc_table_theta).
 // ------------------------------------------------------------------------------------------
+// the uniform box at one coordinate, span = hi - lo: ONE expression for every kernel that forms it outside the chord (the live points, the
+// maximiser, the blocks of the device batch callback), so that they agree to the bit -- the compiler contracts it to an fma, as it does the
+// uniform entry of a table below
+__device__ __forceinline__ double pc_box_theta(double lo, double span, double cube) { return lo + span * cube; }
 #define PC_PT_SORTED (1u << 16)
 #define PC_PT_PERMUTED (1u << 17)
 #define PC_PT_ADAPTIVE (1u << 18)
@@ -697,7 +701,7 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
         ld.mean[k] = (ld.on[k] && S.like.mean) ? S.like.mean[dim] : 0.0;
         cube[k] = !ld.on[k] ? 0.5 : (S.seq_mode ? pc_seq_uniform(S, (unsigned long long)attempt * D + dim)
                                                  : pc_uniform(S.k0, S.k1, PC_DOM_LIVEGEN, 0u, (uint32_t)attempt, (uint32_t)dim));
-        th[k] = ld.lo[k] + ld.span[k] * cube[k];
+        th[k] = pc_box_theta(ld.lo[k], ld.span[k], cube[k]);
     }
     if constexpr (PT != 0) {
         LaneTable<DPL> lt;
@@ -733,7 +737,8 @@ __global__ __launch_bounds__(64) void k_generate_live(PcState S, int attempt0, d
     }
 }
 
-// the device transform of a prior table alone (pchip_prior_transform: parity tests against the host function): one wave a point
+// the device transform of a prior table alone (pchip_prior_transform: parity tests against the host function): one wave a point.
+// The device batch callback's prior as well (pc_park.hip's blocks): a table, or the uniform box (S.prior.kind == 1, wave-uniform).
 template <int DPL>
 __global__ __launch_bounds__(64) void k_prior_transform(PcState S, const double *cubes /* [n][D] */, double *thetas /* [n][D] */)
 {
@@ -741,6 +746,16 @@ __global__ __launch_bounds__(64) void k_prior_transform(PcState S, const double 
     double *ybuf = (double *)smem;
     const int lane = threadIdx.x, D = S.D;
     const size_t base = (size_t)blockIdx.x * D;
+    if (S.prior.kind == 1) {
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) {
+            const int dim = lane + 64 * k;
+            if (dim >= D) continue;
+            const double lo = S.prior.lo ? S.prior.lo[dim] : 0.0, hi = S.prior.hi ? S.prior.hi[dim] : 1.0;
+            thetas[base + dim] = pc_box_theta(lo, hi - lo, cubes[base + dim]);
+        }
+        return;
+    }
     LaneTable<DPL> lt;
     PC_PRIOR_LOAD(DPL, true, S, lane, lt);
     double cube[DPL], th[DPL];
@@ -810,7 +825,7 @@ __device__ __forceinline__ void pc_max_theta(const PcState &S, const LaneDims<DP
                                              double (&th)[DPL], int lane, double *ybuf)
 {
     if (S.prior.kind >= 2) PC_PRIOR_THETA(DPL, true, S, lt, cube, th, lane, ybuf);
-    else th[0] = ld.lo[0] + ld.span[0] * cube[0];
+    else th[0] = pc_box_theta(ld.lo[0], ld.span[0], cube[0]);
 }
 // determinant of the column-major n x n matrix in LDS (destroyed): det_cm's elimination order (pc_maximise.hip, nelder_mead.f90:168-209), row
 // swaps on a zero pivot included; lane = row.  The caller's stores to M need no barrier of their own.
@@ -2622,7 +2637,7 @@ extern "C" int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R
 // pchip_prior_transform: the device transform of the table in S->prior at n points (device pointers)
 extern "C" int pc_launch_prior_transform(const PcState *S, int n, const double *cubes, double *thetas, hipStream_t st)
 {
-    if (S->prior.kind != 2 || n < 1) return 1;
+    if ((S->prior.kind != 2 && S->prior.kind != 1) || n < 1) return 1;
     const size_t sh = sizeof(double) * S->D;
     switch (pc_dpl(S->D)) {
     case 1: hipLaunchKernelGGL((k_prior_transform<1>), dim3(n), dim3(64), sh, st, *S, cubes, thetas); return 0;

@@ -1,5 +1,6 @@
 """`run` / `run_polychord` -- same signatures, defaults and errors as reference
 pypolychord/polychord.py (run_polychord :16-215, run :221-646)."""
+import ctypes
 import warnings
 from pathlib import Path
 
@@ -120,6 +121,128 @@ class _BatchEvaluator:
         self._cb = None
 
 
+_ENGINE_PRIORS = ("polychord_hip_uniform_prior", "polychord_hip_table_prior")      # device_likelihoods.UniformPrior / TablePrior
+
+
+def _device_batch_pair(loglikelihood, prior):
+    """True for a likelihood marked `device_batch` under one of the two priors that go with it; ValueError for any other pairing.
+    Looks at attributes only: nothing is loaded."""
+    dev_like = bool(getattr(loglikelihood, "device_batch", False))
+    dev_prior = bool(getattr(prior, "device_batch", False))
+    engine_prior = getattr(prior, "symbol", None) in _ENGINE_PRIORS
+    if dev_like and not (dev_prior or engine_prior):
+        raise ValueError("a likelihood marked device_batch takes its theta on the device, so its prior is one of two: UniformPrior / "
+                         "TablePrior of device_likelihoods (the engine evaluates it on the packed block) or a callable marked "
+                         "prior.device_batch = True (cube tensor -> theta tensor); a host prior does not go with it")
+    if dev_prior and not dev_like:
+        raise ValueError("a prior marked device_batch maps a cube tensor on the device: it goes with a likelihood marked "
+                         "loglikelihood.device_batch = True only")
+    return dev_like
+
+
+class _HipPointerAttribute(ctypes.Structure):
+    """hipPointerAttribute_t (ROCm 6 and later)"""
+    _fields_ = [("type", ctypes.c_int), ("device", ctypes.c_int), ("devicePointer", ctypes.c_void_p), ("hostPointer", ctypes.c_void_p),
+                ("isManaged", ctypes.c_int), ("allocationFlags", ctypes.c_uint)]
+
+
+class _DeviceBatchEvaluator:
+    """Evaluation of the parked proposals of a round where they are: on the device (polychord_hip_set_device_batch_callback).
+
+    `loglikelihood.device_batch = True`: the callable takes a torch tensor theta of shape (n, nDims), float64, on the run's device --
+    the library's own block, wrapped without a copy -- and returns logL of shape (n,), or (logL, phi) with phi of shape (n, nDerived),
+    tensors on that device.  The prior is UniformPrior / TablePrior of device_likelihoods (the engine fills theta on the device: flags
+    bit 0) or a callable marked `prior.device_batch = True`, cube tensor -> theta tensor.  The callables run under the engine's stream
+    (torch.cuda.ExternalStream), so their work is ordered behind the pack and in front of the next tick without a synchronisation.
+    Under mpirun it is active on rank 0 only: the rows are not farmed."""
+
+    def __init__(self, loglikelihood, prior, nDims, nDerived, logzero):
+        self.like, self.prior, self.nDims, self.nDerived, self.logzero = loglikelihood, prior, nDims, nDerived, logzero
+        self.own_prior = bool(getattr(prior, "device_batch", False))
+        self.error = None
+        self.calls = 0
+        self._cb = self._torch = self._device = self._hip = None
+
+    def _pointer_device(self, ptr):
+        """the device ordinal of a device pointer the library's HIP runtime knows, else None"""
+        import ctypes as C
+        a = _HipPointerAttribute()
+        self._hip.hipPointerGetAttributes.argtypes = [C.POINTER(_HipPointerAttribute), C.c_void_p]
+        self._hip.hipPointerGetAttributes.restype = C.c_int
+        rc = self._hip.hipPointerGetAttributes(C.byref(a), C.c_void_p(ptr))
+        if rc != 0:
+            self._hip.hipGetLastError()
+            return None
+        return int(a.device) if a.type in (2, 3) else None       # hipMemoryTypeDevice, hipMemoryTypeManaged
+
+    def _first_call(self, ptr):
+        """torch, the run's device, and the check that torch's allocations and the library's live in ONE HIP runtime (the torch wheel
+        brings a libamdhip64.so of its own; whichever was loaded first serves both -- on another box it may be two)"""
+        import torch
+        from .. import merge
+        self._hip = merge.hip_runtime()
+        dev = self._pointer_device(ptr)
+        probe_dev = None
+        if dev is not None:
+            probe = torch.empty(1, dtype=torch.float64, device=torch.device("cuda", dev))
+            probe_dev = self._pointer_device(probe.data_ptr())
+        if dev is None or probe_dev != dev:
+            raise RuntimeError("torch and libpolychord_hip do not share a HIP runtime (the library's runtime places a torch tensor on "
+                               f"device {probe_dev}, the run's blocks are on device {dev}): load both against one libamdhip64.so")
+        self._torch, self._device = torch, torch.device("cuda", dev)
+
+    def wrap(self, ptr, shape, stream):
+        """a block of the library's as a tensor, zero copy"""
+        from .. import _ctypes_api as api
+        return self._torch.as_tensor(api.DeviceBlock(ptr, shape, stream), device=self._device)
+
+    def evaluate(self, n, nd, nder, cube_p, theta_p, phi_p, logL_p, flags, stream):
+        if self._device is None:
+            self._first_call(cube_p)
+        torch = self._torch
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self._device)):
+            theta = self.wrap(theta_p, (n, nd), stream)
+            if not flags & 1:
+                if not self.own_prior:
+                    raise RuntimeError("the engine did not evaluate the prior of a device_batch likelihood (option device_prior = 0?)")
+                theta.copy_(torch.as_tensor(self.prior(self.wrap(cube_p, (n, nd), stream)), dtype=torch.float64, device=self._device).reshape(n, nd))
+            out = self.like(theta)
+            if isinstance(out, tuple):
+                out, phi = out
+                if nder > 0:
+                    self.wrap(phi_p, (n, nder), stream).copy_(torch.as_tensor(phi, dtype=torch.float64, device=self._device).reshape(n, nder))
+            self.wrap(logL_p, (n,), stream).copy_(torch.as_tensor(out, dtype=torch.float64, device=self._device).reshape(n))
+
+    def register(self):
+        import ctypes as C
+        from .. import _ctypes_api as api
+        lib = api.load()
+
+        def cb(_user, n, nd, nder, cube_p, theta_p, phi_p, logL_p, flags, stream):
+            try:
+                if self.error is not None:
+                    raise self.error
+                self.calls += 1
+                self.evaluate(n, nd, nder, cube_p, theta_p, phi_p, logL_p, flags, stream)
+            except BaseException as e:   # noqa: BLE001 - re-raised by run() once the engine has wound down
+                if self.error is None:
+                    self.error = e
+                try:                     # logzero everywhere, by the library's runtime (a blocking copy: torch may be what failed)
+                    from .. import merge
+                    fill = np.full(n, self.logzero)
+                    merge.hip_runtime().hipMemcpy(C.c_void_p(logL_p), fill.ctypes.data_as(C.c_void_p), fill.nbytes, 1)
+                finally:
+                    lib.polychord_hip_request_stop()
+            return 0
+        self._cb = api.set_device_batch_callback(cb)
+        return lib
+
+    def unregister(self, lib):
+        from .. import _ctypes_api as api
+        api.set_device_batch_callback(None)
+        self._cb = None
+
+
 class _SubClustering:
     """sub-dimension clustering for the length of one call: the library's sticky setting (polychord_hip_set_sub_clustering)
     set before it and cleared after it, however it ends -- the call format of `_pypolychord.run` stays the reference's"""
@@ -151,32 +274,37 @@ def _engine_run(loglikelihood, prior, *args, sub_clustering_dimensions=()):
 
 
 def _engine_run_call(loglikelihood, prior, *args):
+    device = _device_batch_pair(loglikelihood, prior)
     wl, wp = _wrap(loglikelihood, prior)
     comm = _mpi_comm()
     batch = _BatchEvaluator(loglikelihood, prior, args[1], args[2], comm, args[10])
+    if device:                          # the rows stay on rank 0's device: no host batch callback, nothing farmed
+        batch.active = False
+    ev = _DeviceBatchEvaluator(loglikelihood, prior, args[1], args[2], args[10]) if device else (batch if batch.active else None)
     if comm is None:
-        if not batch.active:
+        if ev is None:
             return _pypolychord.run(wl, wp, *args)
-        lib = batch.register()
+        lib = ev.register()
         try:
             _pypolychord.run(wl, wp, *args)
         finally:
-            batch.unregister(lib)
-        if batch.error is not None:
-            raise batch.error
+            ev.unregister(lib)
+        if ev.error is not None:
+            raise ev.error
         return None
     err = None
     if comm.Get_rank() == 0:
-        lib = batch.register() if batch.active else None
+        lib = ev.register() if ev is not None else None
         try:
             _pypolychord.run(wl, wp, *args)
         except BaseException as e:      # noqa: BLE001 - re-raised below
             err = e
         finally:
             if lib is not None:
-                batch.unregister(lib)
-                comm.bcast("done", root=0)
-        err = err or batch.error
+                ev.unregister(lib)
+                if batch.active:
+                    comm.bcast("done", root=0)
+        err = err or (ev.error if ev is not None else None)
     elif batch.active:
         batch.serve()
     comm.Barrier()
@@ -205,7 +333,15 @@ def _call_prior(prior, cube):
     """theta of one hypercube point, also from a prior written for blocks of rows (`prior.vectorised`)"""
     if getattr(prior, "vectorised", False):
         return np.asarray(prior(np.asarray(cube, dtype=float)[None, :]), dtype=float)[0]
+    if getattr(prior, "device_batch", False):      # the one row goes to the device and comes back
+        return prior(_device_row(cube)).reshape(1, -1)[0].cpu().numpy()
     return prior(cube)
+
+
+def _device_row(v):
+    """one point as a (1, n) float64 tensor on the current HIP device, for the scalar calls of a `device_batch` callable"""
+    import torch
+    return torch.as_tensor(np.asarray(v, dtype=float)[None, :], device="cuda")
 
 
 def _call_like(loglikelihood, theta):
@@ -215,6 +351,11 @@ def _call_like(loglikelihood, theta):
         if isinstance(out, tuple):
             return float(np.asarray(out[0]).reshape(-1)[0]), np.asarray(out[1], dtype=float).reshape(1, -1)[0]
         return float(np.asarray(out).reshape(-1)[0])
+    if getattr(loglikelihood, "device_batch", False):
+        out = loglikelihood(_device_row(theta))
+        if isinstance(out, tuple):
+            return float(out[0].reshape(-1)[0]), out[1].reshape(1, -1)[0].cpu().numpy()
+        return float(out.reshape(-1)[0])
     return loglikelihood(theta)
 
 
@@ -319,6 +460,7 @@ def _legacy_make_resume_file(settings, loglikelihood, prior):
 
 def run_polychord(loglikelihood, nDims, nDerived, settings, prior=default_prior, dumper=default_dumper):
     """legacy interface (polychord.py:16-215)"""
+    _device_batch_pair(loglikelihood, prior)
     comm = _mpi_comm()
     root = comm is None or comm.Get_rank() == 0
     if root:
@@ -359,6 +501,7 @@ def run(loglikelihood, nDims, **kwargs):
         raise TypeError(f"{__name__} got unknown keyword arguments: {kwargs.keys() - default_kwargs.keys()}")
     default_kwargs.update(kwargs)
     kwargs = default_kwargs
+    _device_batch_pair(loglikelihood, kwargs["prior"])
     comm = _mpi_comm()
     root = comm is None or comm.Get_rank() == 0                # polychord.py:566-572 of the reference: rank 0 makes the directories
     if root:
