@@ -141,7 +141,14 @@ void polychord_hip_set_batch_callback(polychord_batch_fn fn, void *user);
  * the callback owns the prior, flags 0; prior.kind 1 / 2: the engine's transform, the bits of the sampling kernels' box and of
  * pchip_prior_transform, flags 1 (nDims <= 256); prior.kind 3 stays refused with a callback likelihood.  The live points are drawn on the
  * device from the Philox coordinates of the host path, so a run is the host batch callback's run of the same functions.
- * pchip_result.path[PCHIP_PATH_DEVICE_BATCH] counts the calls. */
+ * pchip_result.path[PCHIP_PATH_DEVICE_BATCH] counts the calls.
+ * Several seeds in step (pchip_run_in_step with like.kind == PCHIP_LIKE_CALLBACK while this callback is registered): ONE call a tick for the
+ * parked proposals of all runs of a group.  The rows are ordered by run (the order of `seeds` within the group) and inside a run by
+ * ascending chain: the solo order, concatenated; the callee is not told where one run's rows end.  flags, the stream rule, the return code
+ * and logzero are as above; a non-zero return stops every run of the group (code 5).  The callee is always called on the thread that called
+ * pchip_run_in_step.  Each run is bit for bit its solo pchip_run through the same callback PROVIDED the callee's answer for a row depends
+ * neither on the row's position in the block nor on n -- a batched product that rounds by row position (see pc_park.hip) gives runs that
+ * differ from the solo ones in the last bits, and whatever follows from those. */
 typedef int (*polychord_device_batch_fn)(void *user, int n, int nDims, int nDerived, const double *d_cube, double *d_theta,
                                          double *d_phi, double *d_logL, int flags, void *stream);
 void polychord_hip_set_device_batch_callback(polychord_device_batch_fn fn, void *user);
@@ -614,7 +621,14 @@ int  pchip_run_repeats_ex(const pchip_settings *s, const pchip_like *like, const
  * launch (nDims > 64 behind the bases kernels, parameter grades, the sequential stream, the correlated Gaussian) still goes round by round
  * with the others and launches its own k_slice.  A host callback likelihood or a host prior (kind 0) is refused with code 1 and a message,
  * before any device call; prior.kind 3 with a handle that defines no prior fails as pchip_run does.  (pchip_run_repeats keeps refusing a
- * source handle and runs a table one thread per run.) */
+ * source handle and runs a table one thread per run.)
+ * A callback likelihood (like.kind == PCHIP_LIKE_CALLBACK, like.fn not NULL) is taken while a DEVICE batch callback is registered at the time
+ * of the call (polychord_hip_set_device_batch_callback, which has the contract): the runs of a group tick together, their parked proposals
+ * are packed into one block, and the caller's function is called once a tick for all of them, on the calling thread.  One device (ndevices
+ * > 1 is refused with code 1 and a message) and one group at a time, without scheduler threads whatever do_clustering says.  prior.kind 1 / 2:
+ * the engine's transform on the whole block (flags bit 0); prior.kind 0: the callee makes the prior itself (flags 0) -- no host prior function
+ * is called by a run in step; prior.kind 3 is refused.  The live points are made run by run during set-up (nprior rows a call).
+ * path[PCHIP_PATH_DEVICE_BATCH] of a run counts the calls that carried rows of that run: the solo run's count. */
 int  pchip_run_in_step(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds,
                        int ndevices, const int *devices, int max_in_flight, int want_rows, pchip_result *results, pchip_merged *merged);
 
@@ -734,6 +748,11 @@ int  pchip_cluster_update(const pchip_settings *s, int nsets, const pchip_cluste
  * with need, -1 for the others), *count, and cube [>= count][nDims]: row rank[c] = prop[c].  Rows of `cube` from count on are not written.
  * 0, or 1 (arguments) / 2 (device). */
 int  pchip_park_pack(int nchains, int nDims, const int *need, const double *prop, int *rank, int *count, double *cube, int device);
+/* ... of a group of 1 <= nruns <= 64 runs in step (tests/test_park_pack_many.py): run r has nchains[r] >= 1 chains; need, prop and rank hold
+ * the runs one behind the other.  rank: the row in the ONE block -- the counts of the runs before + the run's own ascending enumeration, -1
+ * without need --, counts [nruns], *total, and cube [>= total][nDims]; rows of `cube` from the total on are not written.  0, 1 or 2 as above. */
+int  pchip_park_pack_many(int nruns, const int *nchains, int nDims, const int *need, const double *prop, int *rank, int *counts, int *total,
+                          double *cube, int device);
 
 #ifdef __cplusplus
 }

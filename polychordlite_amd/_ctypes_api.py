@@ -151,6 +151,30 @@ def park_pack(need, prop, cube=None, device=-1):
     return rank, cnt.value, out
 
 
+def park_pack_many(nchains, need, prop, cube=None, device=-1):
+    """pchip_park_pack_many: the pack of a group of runs in step alone.  nchains [nruns] ints; need [sum nchains] ints and prop
+    [sum nchains][nDims], the runs one behind the other; cube: the ONE block the rows are written into ([sum nchains][nDims], changed in
+    place; None: zeros).  Returns rank [sum nchains] (rows of the block), counts [nruns], total, cube."""
+    lib = load()
+    nc = np.ascontiguousarray(nchains, dtype=np.int32)
+    nd = np.ascontiguousarray(need, dtype=np.int32)
+    pr = np.ascontiguousarray(prop, dtype=np.float64)
+    out = np.zeros_like(pr) if cube is None else cube
+    assert out.flags.c_contiguous and out.dtype == np.float64 and out.shape == pr.shape
+    assert nc.ndim == 1 and pr.ndim == 2 and nd.size == pr.shape[0] == int(nc.sum())
+    rank = np.empty(nd.size, dtype=np.int32)
+    counts = np.full(nc.size, -1, dtype=np.int32)
+    tot = C.c_int(-1)
+    ip = C.POINTER(C.c_int)
+    lib.pchip_park_pack_many.argtypes = [C.c_int, ip, C.c_int, ip, C.POINTER(C.c_double), ip, ip, ip, C.POINTER(C.c_double), C.c_int]
+    lib.pchip_park_pack_many.restype = C.c_int
+    rc = lib.pchip_park_pack_many(nc.size, nc.ctypes.data_as(ip), pr.shape[1], nd.ctypes.data_as(ip), dptr(pr), rank.ctypes.data_as(ip),
+                                  counts.ctypes.data_as(ip), C.byref(tot), dptr(out), device)
+    if rc:
+        raise RuntimeError(f"pchip_park_pack_many failed with code {rc}")
+    return rank, counts, tot.value, out
+
+
 _lib = None
 
 

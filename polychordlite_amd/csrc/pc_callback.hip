@@ -24,15 +24,15 @@ struct PcChain {
 // Everything that steers the state machine is wave-uniform.
 // DEV (the device batch callback, pc_park.hip): nothing is stored to the host -- the proposals stay in `prop`, the need flag in PcChain::need --
 // and the answers are dense blocks in the order of the last pack: chain c's row is rank[c] (prop_host / need_host are null, rank is not).
+// The tick of one chain, by its wavefront: the body of k_slice_tick (a run on its own) and of k_slice_tick_many (the runs of a group in step,
+// each with its own state and buffers from its record).
 template <bool DEV>
-__global__ __launch_bounds__(64) void k_slice_tick(PcState S, unsigned batch, int nchains, PcChain *cs, double *x0s /* [B][D] */,
-                                                  int *decks /* [B][nr] */, double *prop /* [B][D] */,
-                                                  const double *ev_logL, const double *ev_theta, const double *ev_phi,
-                                                  int first, double *prop_host, int *need_host, const int *rank)
+__device__ __forceinline__ void slice_tick_chain(const PcState &S, unsigned batch, int chain, int lane, PcChain *cs, double *x0s /* [B][D] */,
+                                                 int *decks /* [B][nr] */, double *prop /* [B][D] */,
+                                                 const double *ev_logL, const double *ev_theta, const double *ev_phi,
+                                                 int first, double *prop_host, int *need_host, const int *rank)
 {   // prop_host / need_host: pinned host memory; the proposals and the need flags are stored there directly (posted
     // writes over PCIe), so that the host finds them after one stream synchronisation, without copies
-    const int chain = blockIdx.x, lane = threadIdx.x;
-    if (chain >= nchains) return;
     const int arow = DEV ? rank[chain] : chain;          // this chain's row in the answers (DEV: read only behind need or ok_theta, when it is a rank)
     const int D = S.D, nr = S.nr, nT = S.nT;
     PcChain c = cs[chain];
@@ -161,6 +161,30 @@ __global__ __launch_bounds__(64) void k_slice_tick(PcState S, unsigned batch, in
     }
 }
 
+template <bool DEV>
+__global__ __launch_bounds__(64) void k_slice_tick(PcState S, unsigned batch, int nchains, PcChain *cs, double *x0s, int *decks, double *prop,
+                                                  const double *ev_logL, const double *ev_theta, const double *ev_phi,
+                                                  int first, double *prop_host, int *need_host, const int *rank)
+{
+    const int chain = blockIdx.x, lane = threadIdx.x;
+    if (chain >= nchains) return;
+    slice_tick_chain<DEV>(S, batch, chain, lane, cs, x0s, decks, prop, ev_logL, ev_theta, ev_phi, first, prop_host, need_host, rank);
+}
+
+// The tick of the device batch callback for the runs of a group in step: blockIdx.y = run, blockIdx.x = chain, one wavefront a chain as in
+// k_slice_tick<true>; every run's state, nursery number, buffers and first-tick flag come from its record (PC_REC_T_*, PC_REC_I_FIRST).
+// The answers of all runs lie in ONE block (the group's), which each record's LOGL / THETA / PHI point at; a run's ranks are rows of it.
+__global__ __launch_bounds__(64) void k_slice_tick_many(const PcManyRec *__restrict__ R, int nchains)
+{
+    const int chain = blockIdx.x, lane = threadIdx.x, run = blockIdx.y;
+    if (chain >= nchains) return;
+    const PcManyView v = pc_many_view(R, run);
+    slice_tick_chain<true>(v.S, (unsigned)v.ia[PC_REC_I_BATCH], chain, lane, (PcChain *)v.p[PC_REC_T_CS], (double *)v.p[PC_REC_T_X0],
+                           (int *)v.p[PC_REC_T_DECK], (double *)v.p[PC_REC_T_PROP], (const double *)v.p[PC_REC_T_LOGL],
+                           (const double *)v.p[PC_REC_T_THETA], (const double *)v.p[PC_REC_T_PHI], v.ia[PC_REC_I_FIRST],
+                           (double *)nullptr, (int *)nullptr, (const int *)v.p[PC_REC_T_RANK]);
+}
+
 extern "C" void pc_launch_slice_tick(const PcState *S, unsigned batch, int nchains, void *cs, double *x0s, int *decks, double *prop,
                                      const double *ev_logL, const double *ev_theta, const double *ev_phi, int first, double *prop_host,
                                      int *need_host, hipStream_t st)
@@ -175,6 +199,13 @@ extern "C" void pc_launch_slice_tick_dev(const PcState *S, unsigned batch, int n
 {
     hipLaunchKernelGGL(k_slice_tick<true>, dim3(nchains), dim3(64), 0, st, *S, batch, nchains, (PcChain *)cs, x0s, decks, prop,
                        ev_logL, ev_theta, ev_phi, first, (double *)nullptr, (int *)nullptr, rank);
+}
+// ... for R runs of a group in step, nchains chains each (dR: device array of their records)
+extern "C" int pc_launch_slice_tick_many(const PcManyRec *dR, int R, int nchains, hipStream_t st)
+{
+    if (R < 1 || R > 65535 || nchains < 1) return 1;
+    hipLaunchKernelGGL(k_slice_tick_many, dim3(nchains, R), dim3(64), 0, st, dR, nchains);
+    return 0;
 }
 // where a chain's need flag lies in its state record, in ints (the pack's index kernel reads it there)
 extern "C" void pc_chain_need_layout(int *stride, int *offset) { *stride = (int)(sizeof(PcChain) / sizeof(int)); *offset = (int)(offsetof(PcChain, need) / sizeof(int)); }

@@ -23,8 +23,9 @@
 #include <cstring>
 #include <cstdint>
 
-enum { CK_COMPACT = 0, CK_RESET, CK_CLUS1, CK_CLUSG, CK_BASES, CK_NHATS_G, CK_SLICE, CK_SLICE_G, CK_BASES_NEXT, CK_SORT, CK_NN, CK_CONSUME, CK_CONSUME_CL, CK_APPLY, CK_UPDATE, CK_FINAL, CK_N };      // (in the order they are launched)
-// (_G: any device likelihood, the wavefront-per-chain kernels of a run on its own with the run in the grid; NN / CONSUME_CL: runs with several clusters)
+enum { CK_COMPACT = 0, CK_RESET, CK_CLUS1, CK_CLUSG, CK_BASES, CK_NHATS_G, CK_SLICE, CK_SLICE_G, CK_TICK, CK_BASES_NEXT, CK_SORT, CK_NN, CK_CONSUME, CK_CONSUME_CL, CK_APPLY, CK_UPDATE, CK_FINAL, CK_N };      // (in the order they are launched)
+// (_G: any device likelihood, the wavefront-per-chain kernels of a run on its own with the run in the grid; TICK: the device batch callback, one tick of
+//  the chains that wait for an answer -- several a nursery, each in a flush of its own (pc_step.h); NN / CONSUME_CL: runs with several clusters)
 
 // Rec::a, what the runs of one launch must share: the chains of the nursery (directions, sampling, apply) and whether k_slice makes seeds +
 // whitening itself (CK_SLICE_G); the fused update's grid and its deferred flag; more than 64 clusters (CK_CONSUME_CL)
@@ -277,6 +278,17 @@ inline Cohort::Rec rec_slice_g(const PcState &S, unsigned batch, int nchains, bo
     r.note = note;
     return r;
 }
+// one tick of a nursery through the device batch callback: the chains' records, start points, decks and parked proposals, the answers of the
+// last call (the group's one block) and the ranks of the last pack (rows of that block); first: the nursery's first tick
+inline Cohort::Rec rec_tick(const PcState &S, unsigned batch, int nchains, void *cs, double *x0s, int *decks, double *prop, const double *ev_logL,
+                            const double *ev_theta, const double *ev_phi, const int *rank, bool first)
+{
+    Cohort::Rec r = rec_nursery(CK_TICK, S, batch, nchains);
+    r.p[PC_REC_T_CS] = cs; r.p[PC_REC_T_X0] = x0s; r.p[PC_REC_T_DECK] = decks; r.p[PC_REC_T_PROP] = prop;
+    r.p[PC_REC_T_LOGL] = (void *)ev_logL; r.p[PC_REC_T_THETA] = (void *)ev_theta; r.p[PC_REC_T_PHI] = (void *)ev_phi; r.p[PC_REC_T_RANK] = (void *)rank;
+    r.ia[PC_REC_I_FIRST] = first ? 1 : 0;
+    return r;
+}
 inline Cohort::Rec rec_sort(const PcState &S) { return rec_of(CK_SORT, S); }
 inline Cohort::Rec rec_nn(const PcState &S, int nursery_left)
 {
@@ -333,6 +345,11 @@ inline const Cohort::Stage &Cohort::stage(int kind)
           PC_MANY { return (f.S.prior.kind >= 2 || f.S.like.kind == PC_LIKE_SOURCE)
                                ? pc_launch_slice_step(&f.S, d, cnt, (int)f.a[PC_REC_A_NCHAINS], (int)f.a[PC_REC_A_FUSED], st)
                                : pc_launch_slice_many(&f.S, d, cnt, (int)f.a[PC_REC_A_NCHAINS], (int)f.a[PC_REC_A_FUSED], st); }, {} },
+        { CK_TICK, "tick",
+          PC_ONE { pc_launch_slice_tick_dev(&r.S, (unsigned)r.ia[PC_REC_I_BATCH], (int)r.a[PC_REC_A_NCHAINS], r.p[PC_REC_T_CS], (double *)r.p[PC_REC_T_X0], (int *)r.p[PC_REC_T_DECK],
+                                            (double *)r.p[PC_REC_T_PROP], (const double *)r.p[PC_REC_T_LOGL], (const double *)r.p[PC_REC_T_THETA], (const double *)r.p[PC_REC_T_PHI],
+                                            r.ia[PC_REC_I_FIRST], (const int *)r.p[PC_REC_T_RANK], st); return 0; },
+          PC_MANY { return pc_launch_slice_tick_many(d, cnt, (int)f.a[PC_REC_A_NCHAINS], st); }, {} },
         { CK_BASES_NEXT, "bases_next",
           PC_ONE { return pc_launch_nhats_part(&r.S, (unsigned)r.ia[PC_REC_I_BATCH], (int)r.a[PC_REC_A_NCHAINS], 1, st, 1); },
           PC_MANY { return pc_launch_bases_t_many(&f.S, d, cnt, 0u, (int)f.a[PC_REC_A_NCHAINS], st); }, {} },

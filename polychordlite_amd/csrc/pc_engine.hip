@@ -383,6 +383,9 @@ struct Engine {
     PcState S_pri{};                                       // ... the state k_prior_transform reads for it (nDims, the prior, the table's mask)
     double *db_cube = nullptr, *db_theta = nullptr, *db_phi = nullptr, *db_logL = nullptr;
     int *db_rank = nullptr, *db_count = nullptr, *hp_count = nullptr, *hp_count_dev = nullptr;
+    // ... in step with other runs (TickGroup, pc_tick.h): the four blocks are the group's ONE block, a tick is written down and the run yields;
+    // tick_want says where its flags, proposals and ranks are, tick_count comes back with the rows the pack found for it
+    bool tick_shared = false, tick_asked = false; PcParkRun tick_want{}; int tick_count = 0;
     std::vector<int> cb_idx; std::vector<double> cb_c, cb_t, cb_p, cb_l;   // batch callback scratch
     // host mirror of the dead points for the dumper hook (nested_sampling.F90:546-590)
     polychord_dumper_fn dumper = nullptr;
@@ -1358,10 +1361,22 @@ struct Engine {
     // run's stream, nothing is waited for here
     void device_eval_batch(int n)
     {
+        tick_answered(n);
+        device_call(n);
+    }
+    // ... the two halves of it.  In step the group makes ONE call for the rows of all its runs, through the first of them that ticked
+    // (device_call with the group's total), and every run that had rows in it counts the call and its own rows (tick_answered)
+    void device_call(int n)
+    {
         if (db_flags && pc_launch_prior_transform(&S_pri, n, db_cube, db_theta, st)) engine_fail(PC_RC_NDIMS, "the device prior of the batch callback could not be launched (nDims = %d)", S.D);
-        path[PCHIP_PATH_DEVICE_BATCH]++;
-        cb_evals += n;
         if (dbatch_fn(dbatch_user, n, S.D, S.nDer, db_cube, db_theta, db_phi, db_logL, db_flags, (void *)st) != 0) stop.store(1);
+    }
+    void tick_answered(int n) { path[PCHIP_PATH_DEVICE_BATCH]++; cb_evals += n; }
+    // the group's block in place of the run's own four (which served the live points, and go back now: the stream is idle behind begin())
+    void tick_bind(double *cube, double *theta, double *phi, double *logL)
+    {
+        blocks.release(db_cube); blocks.release(db_theta); blocks.release(db_phi); blocks.release(db_logL);
+        db_cube = cube; db_theta = theta; db_phi = phi; db_logL = logL; tick_shared = true;
     }
 
     void generate_live_device()
@@ -1410,6 +1425,22 @@ struct Engine {
     {
         int first = 1, stride = 1, off = 0;
         pc_chain_need_layout(&stride, &off);
+        if (co) {
+            // In step: the tick is written down, the group is told where the flags, the proposals and the ranks are, and the run yields.  The
+            // driver launches the ticks of all runs that wait once, packs their proposals into the one block, waits once and calls the
+            // caller's function once (pc_step.h, enqueue_as_fibers); the run's own count says whether it is done.
+            if (!fib || !tick_shared) engine_fail(PC_RC_DEVICE, "a device batch callback in step outside its group's tick phase");
+            while (true) {
+                co->rec(rec_tick(S, batch, B, d_cs, d_x0s, d_decks, d_prop, db_logL, db_theta, db_phi, db_rank, first != 0));
+                first = 0; cb_ticks++;
+                tick_want = PcParkRun{(const int *)d_cs + off, d_prop, db_rank, B, stride}; tick_asked = true;
+                fib->yield();
+                if (fib->cancel) throw FiberCancelled{};      // (resumed to unwind: another run failed)
+                if (stop.load(std::memory_order_relaxed)) return;
+                if (tick_count == 0) break;
+            }
+            return;
+        }
         while (true) {
             pc_launch_slice_tick_dev(&S, batch, B, d_cs, d_x0s, d_decks, d_prop, db_logL, db_theta, db_phi, first, db_rank, st);
             first = 0; cb_ticks++;
@@ -2286,6 +2317,7 @@ struct Engine {
 
 }  // namespace
 
+#include "pc_tick.h"        // TickGroup: what the runs of a group share when their likelihood is the caller's device batch callback
 #include "pc_step.h"        // pc_run_many: the driver of the runs in step, a group at a time, as named phases (StepGroup)
 
 extern "C" {
@@ -2575,6 +2607,55 @@ int pchip_park_pack(int nchains, int nDims, const int *need, const double *prop,
     if (rc) (void)hipGetLastError();
     (void)hipFree(d_need); (void)hipFree(d_rank); (void)hipFree(d_count); (void)hipFree(d_prop); (void)hipFree(d_cube);
     if (h_count) (void)hipHostFree(h_count);
+    return rc;
+}
+
+// kernel-level entry for tests/test_park_pack_many.py: the pack of a group of runs (k_park_index_many, k_park_rows_many) on host arrays, the
+// runs' flags, proposals and ranks one run behind the other
+int pchip_park_pack_many(int nruns, const int *nchains, int nDims, const int *need, const double *prop, int *rank, int *counts, int *total,
+                         double *cube, int device)
+{
+    if (nruns < 1 || nruns > PC_PARK_MAX_RUNS || nDims < 1 || !nchains || !need || !prop || !rank || !counts || !total || !cube) {
+        pc_abi_set_last_error("pchip_park_pack_many: 1 <= nruns <= 64 runs of nchains[r] >= 1 flags and rows of nDims >= 1, and room for the ranks, the counts, the total and the rows");
+        return 1;
+    }
+    size_t all = 0; int max_chains = 0;
+    for (int r = 0; r < nruns; ++r) {
+        if (nchains[r] < 1) { pc_abi_set_last_error("pchip_park_pack_many: every run has at least one chain"); return 1; }
+        all += (size_t)nchains[r]; max_chains = std::max(max_chains, nchains[r]);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
+    if (hipSetDevice(device >= 0 ? device % ndev : 0) != hipSuccess) return 2;
+    const size_t nb = sizeof(double) * all * nDims, ni = sizeof(int) * all;
+    int *d_need = nullptr, *d_rank = nullptr, *d_count = nullptr, *h_count = nullptr; double *d_prop = nullptr, *d_cube = nullptr; PcParkRun *h_runs = nullptr;
+    int rc = 2;
+    // (the caller's `cube` goes up first: the rows from the total on come back as they were)
+    if (hipMalloc(&d_need, ni) == hipSuccess && hipMalloc(&d_rank, ni) == hipSuccess && hipMalloc(&d_count, sizeof(int) * PC_PARK_MAX_RUNS) == hipSuccess &&
+        hipMalloc(&d_prop, nb) == hipSuccess && hipMalloc(&d_cube, nb) == hipSuccess && hipHostMalloc(&h_count, sizeof(int) * (PC_PARK_MAX_RUNS + 1)) == hipSuccess &&
+        hipHostMalloc(&h_runs, sizeof(PcParkRun) * PC_PARK_MAX_RUNS) == hipSuccess &&
+        hipMemcpy(d_need, need, ni, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_prop, prop, nb, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_cube, cube, nb, hipMemcpyHostToDevice) == hipSuccess) {
+        size_t o = 0;
+        for (int r = 0; r < nruns; ++r) { h_runs[r] = PcParkRun{d_need + o, d_prop + o * nDims, d_rank + o, nchains[r], 1}; o += (size_t)nchains[r]; }
+        for (int r = 0; r <= nruns; ++r) h_count[r] = -1;
+        void *dp = nullptr, *dr = nullptr;
+        if (hipHostGetDevicePointer(&dp, h_count, 0) == hipSuccess && hipHostGetDevicePointer(&dr, h_runs, 0) == hipSuccess &&
+            pc_launch_park_pack_many(nruns, (const PcParkRun *)dr, max_chains, nDims, d_count, (int *)dp, d_cube, nullptr) == 0) {
+            std::vector<int> dc((size_t)nruns, -2);
+            if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(rank, d_rank, ni, hipMemcpyDeviceToHost) == hipSuccess &&
+                hipMemcpy(dc.data(), d_count, sizeof(int) * nruns, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(cube, d_cube, nb, hipMemcpyDeviceToHost) == hipSuccess) {
+                long sum = 0; rc = 0;
+                for (int r = 0; r < nruns; ++r) { counts[r] = ((volatile int *)h_count)[r]; sum += counts[r]; if (dc[(size_t)r] != counts[r]) rc = 2; }      // the device words and the pinned words are the same numbers
+                *total = ((volatile int *)h_count)[nruns];
+                if (sum != *total) rc = 2;
+            }
+        }
+    }
+    if (rc) (void)hipGetLastError();
+    (void)hipFree(d_need); (void)hipFree(d_rank); (void)hipFree(d_count); (void)hipFree(d_prop); (void)hipFree(d_cube);
+    if (h_count) (void)hipHostFree(h_count);
+    if (h_runs) (void)hipHostFree(h_runs);
     return rc;
 }
 

@@ -61,12 +61,19 @@ size_t pc_chain_state_size(void);
 // the device batch callback's tick: answers read at rank[chain] of the dense blocks, nothing stored to the host
 void pc_launch_slice_tick_dev(const PcState *S, unsigned batch, int nchains, void *cs, double *x0s, int *decks, double *prop, const double *ev_logL,
                               const double *ev_theta, const double *ev_phi, int first, const int *rank, hipStream_t st);
+// ... for R runs of a group in step at once (grid.y = run; records with PC_REC_T_*, PC_REC_I_BATCH, PC_REC_I_FIRST).  1: not this way
+int pc_launch_slice_tick_many(const PcManyRec *dR, int R, int nchains, hipStream_t st);
 void pc_chain_need_layout(int *stride, int *offset);
 // ---- pc_park.hip -------------------------------------------------------------------------------------------
 // rank [nchains] (ascending enumeration of the chains with a flag, -1 without), their number to *count and *count_host (device-visible
 // pinned word, or null), their cubes as rows of `cube` ([count][D]); flag of chain c at need[c * stride]
 void pc_launch_park_pack(int nchains, int D, const int *need, int stride, const double *prop, int *rank, int *count, int *count_host,
                          double *cube, hipStream_t st);
+// the pack of a group of nruns <= PC_PARK_MAX_RUNS runs into ONE block: runs[r] (device-visible) names run r's flags, proposals and rank array;
+// rank: the GLOBAL row (the counts of the runs before + the run's own ascending enumeration, -1 without a flag); count [nruns] on the device;
+// count_host [nruns + 1] (device-visible pinned words): each run's count, then the total; the cubes as rows of `cube` ([total][D]), run after
+// run.  max_chains: the largest nchains among the runs.  1: not launched (nruns out of range)
+int pc_launch_park_pack_many(int nruns, const PcParkRun *runs, int max_chains, int D, int *count, int *count_host, double *cube, hipStream_t st);
 void pc_launch_live_cubes(const PcState *S, unsigned attempt0, int m, double *cube, hipStream_t st);
 void pc_launch_live_gather(const PcState *S, int n, const int *idx, const double *cube, const double *theta, const double *phi,
                            const double *logL, double *rows, hipStream_t st);

@@ -761,20 +761,31 @@ int pchip_run_repeats(const pchip_settings *s, const pchip_like *like, const pch
 }
 
 // One body for the two doors.  in_step = false: pchip_run_repeats[_ex], which refuses a source handle and takes the runs in step for the box
-// alone (a table: one thread per run) -- both pinned by its tests.  in_step = true: pchip_run_in_step, any problem that is wholly on the device.
+// alone (a table: one thread per run) -- both pinned by its tests.  in_step = true: pchip_run_in_step, any problem that is wholly on the device
+// -- a callback likelihood too while a device batch callback is registered (one device, one group at a time, no scheduler threads).
 static int run_repeats_body(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds,
                             int ndevices, const int *devices, int max_in_flight, int want_rows, pchip_result *results, pchip_merged *merged, bool in_step)
 {
     using clk = std::chrono::steady_clock;
     if (nseeds < 1) return 1;
+    bool device_cb = false;
     if (in_step) {
         // (before any device call: the refusal shows on a machine without a GPU)
         if (!like || !prior) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step needs a likelihood and a prior\n"); return 1; }
-        if (like->kind == PCHIP_LIKE_CALLBACK) {
+        // a callback likelihood goes in step through the caller's DEVICE batch callback alone (polychord_hip_set_device_batch_callback,
+        // registered now): one call a tick for the rows of all runs of a group, on this thread
+        device_cb = like->kind == PCHIP_LIKE_CALLBACK && pc_device_batch_registered() != 0;
+        if (like->kind == PCHIP_LIKE_CALLBACK && !device_cb) {
             std::fprintf(stderr, "polychord_hip: pchip_run_in_step does not take a host callback likelihood: the runs in step share their kernel launches, and a callback belongs to its caller's thread -- pchip_run_repeats runs those one thread per run\n");
             return 1;
         }
-        if (prior->kind != 1 && prior->kind != PCHIP_PRIOR_TABLE && prior->kind != PCHIP_PRIOR_SOURCE) {
+        if (device_cb) {
+            if (!like->fn) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step: a callback likelihood needs like.fn even where the device batch callback evaluates it\n"); return 1; }
+            if (ndevices > 1) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step takes a device batch callback on one device only (ndevices = %d): the caller's function is called on the calling thread, one group at a time\n", ndevices); return 1; }
+            if (prior->kind == PCHIP_PRIOR_SOURCE) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step: prior.kind = 3 (source prior) needs a device source likelihood of the same handle, not a callback\n"); return 1; }
+        }
+        // (under the device batch callback a callback prior is the callee's own work on the device: no host function is called by a run in step)
+        else if (prior->kind != 1 && prior->kind != PCHIP_PRIOR_TABLE && prior->kind != PCHIP_PRIOR_SOURCE) {
             std::fprintf(stderr, "polychord_hip: pchip_run_in_step does not take a host prior (prior.kind = %d): the runs in step need the prior on the device -- the uniform box (1), a table (2) or the handle's own source prior (3)\n", prior->kind);
             return 1;
         }
@@ -812,7 +823,7 @@ static int run_repeats_body(const pchip_settings *s, const pchip_like *like, con
         //  (CohortStreams, pc_engine.hip); sixteen runs of configs[2] / [3]: 495 / 386 ms with two groups, 430 / 340 with four; with six or
         //  eight groups main streams share queues again and the call takes twice as long.  And four groups whatever they hold: four runs
         //  as four groups of one 172 ms against 274 in one group, eight as four groups of two 264 against 325 in two)
-        const int sched = std::getenv("PC_REPEATS_SCHED") ? std::max(1, std::atoi(std::getenv("PC_REPEATS_SCHED"))) : ((s->do_clustering && per_dev >= 2) ? std::min(4, per_dev) : 1);
+        const int sched = device_cb ? 1 : std::getenv("PC_REPEATS_SCHED") ? std::max(1, std::atoi(std::getenv("PC_REPEATS_SCHED"))) : ((s->do_clustering && per_dev >= 2) ? std::min(4, per_dev) : 1);      // (a device batch callback: one group at a time on the calling thread, nobody else calls the caller's function)
         const int nd = (int)devs.size();
         // (several groups on a device: streams of known hardware-queue classes for all of them, classed now, while the device is idle)
         if (sched > 1) for (int d : devs) pc_prepare_streams(d, 4 * sched);

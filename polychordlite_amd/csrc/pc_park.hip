@@ -4,6 +4,8 @@
 //   k_park_index   one workgroup: rank[c] = how many chains below c wait for an answer (-1 for a chain that does not), and their number
 //                  to a device word and to ONE pinned host word -- all the host reads of a round;
 //   k_park_rows    one wavefront a chain, lane = coordinate: the chain's parked cube to row rank[c] of the block;
+//   k_park_index_many / k_park_rows_many   the same for a group of runs in step: the runs' rows one behind the other in ONE block, in the
+//                  order of the runs, the ranks global, every run's count and the total to pinned words;
 //   k_live_cubes   the prior samples of the live points, the Philox coordinates of generate_live_callback (PC_DOM_LIVEGEN, 0, attempt, d);
 //   k_live_gather  the valid ones of them as rows [cube | theta | phi | logzero | logL] for pc_launch_install_live.
 //
@@ -16,7 +18,7 @@
 // need: the chains' flags, flag of chain c at need[c * stride] (PcChain::need inside the chain records: pc_chain_need_layout; a plain
 // array: stride 1).  Chunks of PC_PARK_THREADS chains: within a wavefront the rank is the population count of the ballot below the lane,
 // across the wavefronts of a chunk the sum of their counts through LDS, across chunks a carry every thread keeps for itself.
-__global__ __launch_bounds__(PC_PARK_THREADS) void k_park_index(int nchains, const int *need, int stride, int *rank, int *count, int *count_host)
+__device__ __forceinline__ int park_ranks(int nchains, const int *need, int stride, int *rank)
 {
     __shared__ int wave_n[PC_PARK_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -35,7 +37,22 @@ __global__ __launch_bounds__(PC_PARK_THREADS) void k_park_index(int nchains, con
         carry += total;
         __syncthreads();                                // wave_n is written again by the next chunk
     }
-    if (tid == 0) { *count = carry; if (count_host) *count_host = carry; }
+    return carry;
+}
+
+__global__ __launch_bounds__(PC_PARK_THREADS) void k_park_index(int nchains, const int *need, int stride, int *rank, int *count, int *count_host)
+{
+    const int carry = park_ranks(nchains, need, stride, rank);
+    if (threadIdx.x == 0) { *count = carry; if (count_host) *count_host = carry; }
+}
+
+// The pack of a group of runs in step (pc_step.h): one workgroup a run, the scheme above for the run's LOCAL ranks, the run's number of parked
+// chains to count[run] and to the pinned word count_host[run] (what the run reads to know whether it is done).
+__global__ __launch_bounds__(PC_PARK_THREADS) void k_park_index_many(const PcParkRun *__restrict__ runs, int *count, int *count_host)
+{
+    const int run = blockIdx.x;
+    const int carry = park_ranks(runs[run].nchains, pc_as_global(runs[run].need, runs), runs[run].stride, pc_as_global(runs[run].rank, runs));
+    if (threadIdx.x == 0) { count[run] = carry; count_host[run] = carry; }
 }
 
 __global__ __launch_bounds__(64) void k_park_rows(int nchains, int D, const int *rank, const double *prop /* [nchains][D] */, double *cube /* [n][D] */)
@@ -47,6 +64,28 @@ __global__ __launch_bounds__(64) void k_park_rows(int nchains, int D, const int 
     const double *src = prop + (size_t)chain * D;
     double *dst = cube + (size_t)r * D;
     for (int d = lane; d < D; d += 64) dst[d] = src[d];
+}
+
+// ... one wavefront per (run, chain), lane = coordinate.  The run's base is the sum of the counts of the runs before it (at most 64 runs: one
+// wave reduction); the rank becomes the GLOBAL row base + local, which the next tick reads the answers at, and the cube goes there.  Every
+// run's rank array is touched by its own wavefronts only, each its own entry.  The first workgroup leaves the total in count_host[nruns].
+__global__ __launch_bounds__(64) void k_park_rows_many(const PcParkRun *__restrict__ runs, int nruns, int D, const int *count, int *count_host, double *cube /* [total][D] */)
+{
+    const int chain = blockIdx.x, run = blockIdx.y, lane = threadIdx.x;
+    const int n_l = lane < nruns ? count[lane] : 0;
+    int base = lane < run ? n_l : 0, total = n_l;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { base += __shfl_xor(base, o); total += __shfl_xor(total, o); }
+    if (chain == 0 && run == 0 && lane == 0) count_host[nruns] = total;
+    if (run >= nruns || chain >= runs[run].nchains) return;
+    int *rank = pc_as_global(runs[run].rank, runs);
+    const int local = rank[chain];
+    if (local < 0) return;
+    const int r = base + local;
+    const double *src = pc_as_global(runs[run].prop, runs) + (size_t)chain * D;
+    double *dst = cube + (size_t)r * D;
+    for (int d = lane; d < D; d += 64) dst[d] = src[d];
+    if (lane == 0) rank[chain] = r;
 }
 
 __global__ __launch_bounds__(64) void k_live_cubes(uint32_t k0, uint32_t k1, uint32_t attempt0, int m, int D, double *cube /* [m][D] */)
@@ -74,6 +113,14 @@ extern "C" void pc_launch_park_pack(int nchains, int D, const int *need, int str
 {
     hipLaunchKernelGGL(k_park_index, dim3(1), dim3(PC_PARK_THREADS), 0, st, nchains, need, stride, rank, count, count_host);
     hipLaunchKernelGGL(k_park_rows, dim3(nchains), dim3(64), 0, st, nchains, D, (const int *)rank, prop, cube);
+}
+
+extern "C" int pc_launch_park_pack_many(int nruns, const PcParkRun *runs, int max_chains, int D, int *count, int *count_host, double *cube, hipStream_t st)
+{
+    if (nruns < 1 || nruns > PC_PARK_MAX_RUNS || max_chains < 1) return 1;
+    hipLaunchKernelGGL(k_park_index_many, dim3(nruns), dim3(PC_PARK_THREADS), 0, st, runs, count, count_host);
+    hipLaunchKernelGGL(k_park_rows_many, dim3(max_chains, nruns), dim3(64), 0, st, runs, nruns, D, (const int *)count, count_host, cube);
+    return 0;
 }
 
 extern "C" void pc_launch_live_cubes(const PcState *S, unsigned attempt0, int m, double *cube, hipStream_t st)

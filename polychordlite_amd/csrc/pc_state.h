@@ -222,6 +222,15 @@ enum { PC_REC_I_ND = 1, PC_REC_I_NMAX = 2, PC_REC_I_ND_SUB = 3 };
 // clustering, the passes over parts of clusters: part descriptors, similarities, the parts' points, kNN lists, labels, verdicts; parts, the largest
 enum { PC_REC_G_DESC = 0, PC_REC_G_SM = 1, PC_REC_G_POOL = 2, PC_REC_G_KNN = 3, PC_REC_G_LAB = 4, PC_REC_G_OUT = 5 };
 enum { PC_REC_I_NB = 1, PC_REC_I_MMAX = 2 };
+// the tick of the device batch callback: chain records, start points, decks, parked proposals, the answers of the last call (logL, theta, phi)
+// and the ranks of the last pack; whether this is the nursery's first tick
+enum { PC_REC_T_CS = 0, PC_REC_T_X0 = 1, PC_REC_T_DECK = 2, PC_REC_T_PROP = 3, PC_REC_T_LOGL = 4, PC_REC_T_THETA = 5, PC_REC_T_PHI = 6, PC_REC_T_RANK = 7 };
+enum { PC_REC_I_FIRST = 1 };
+
+// One run's share of the pack for a group of runs (pc_park.hip, k_park_index_many / k_park_rows_many): the flag of chain c at need[c * stride],
+// the parked proposals [nchains][D], and where the run's ranks go [nchains]
+struct PcParkRun { const int *need; const double *prop; int *rank; int nchains, stride; };
+#define PC_PARK_MAX_RUNS 64      // (a group's runs: the bases are one wave reduction)
 
 #ifdef __HIPCC__
 // ---- kernels that take their state from a record in memory (the runs of a device in step, blockIdx.y = run) --------------------------

@@ -9,6 +9,7 @@
 //     setup, begin, compact_wanted, compact_record, compact_finish
 //     round_enqueue, round_ready, finish_may_wait, round_finish
 //     end_a, end_a2, end_wait_aside, end_b, destroy
+//   TickGroup (pc_tick.h: what runs through the caller's device batch callback share): on, set_up, pack, answer, leave, drop, release
 //   these services:
 //     hpool()                      get_stream, put_stream, take_stream_if, get_sync_event, put_sync_event
 //     sclasses()                   known, classify: a stream's hardware-queue class
@@ -71,6 +72,10 @@ struct StepGroup {
     struct EndBatch { std::vector<int> fin, rcs; hipEvent_t ev = nullptr, ev2 = nullptr; int dev = 0; std::thread th; };
     std::vector<std::unique_ptr<EndBatch>> endings;
     int *h_totals = nullptr; size_t totals_cap = 0;      // compact_full's rows in use, one pinned word per run
+    // the likelihood is the caller's device batch callback: the runs' ticks go together (enqueue_as_fibers), their answers share one block (tg),
+    // and the caller's function is called on this thread alone
+    const bool ticking = like && like->kind == PCHIP_LIKE_CALLBACK;
+    TickGroup tg;
     const bool fibers_on = !pc_env().cohort_fibers_off, prof = pc_env().debug == 5;
     StepTimes t;
 
@@ -151,7 +156,7 @@ struct StepGroup {
             std::atomic<int> nextk{1};
             auto worker = [&] { (void)hipSetDevice(devnow); for (int k; !failed && (k = nextk.fetch_add(1)) < n;) setup_one(k); };
             std::vector<std::thread> th;
-            for (int w = 1; w < std::min(setup_threads, n - 1) && n >= 8; ++w) th.emplace_back(worker);
+            for (int w = 1; w < std::min(setup_threads, n - 1) && n >= 8 && !ticking; ++w) th.emplace_back(worker);      // (ticking: the live points are the caller's function at work, on this thread)
             worker();
             for (auto &w : th) w.join();
         }
@@ -175,6 +180,7 @@ struct StepGroup {
             }
             live[k] = 1; nlive++;
         }
+        if (ticking && nlive > 0) tg.set_up(E, live, n);
     }
 
     // Assumes the live runs between two rounds.  Leaves the phantom arrays that were full compacted, together, with one wait for all.
@@ -202,9 +208,63 @@ struct StepGroup {
     void enqueue_round()
     {
         const auto a0 = t.now();
-        for (int k = 0; k < n; ++k) enq[k] = (live[k] && E[k]->round_enqueue()) ? 1 : 0;
+        if (tg.on) enqueue_as_fibers();
+        else for (int k = 0; k < n; ++k) enq[k] = (live[k] && E[k]->round_enqueue()) ? 1 : 0;
         const auto a1 = t.now(); t.enq += t.sec(a0, a1);
         co.flush(); t.fl += t.sec(a1, t.now());
+    }
+    // ... round_enqueue of the live runs, each as a fiber, where a fresh nursery is sampled through the caller's device batch callback.
+    // Assumes tg set up (every run's answers in the group's one block).  A run at a fresh nursery writes a tick down, says where its flags,
+    // proposals and ranks are, and yields; a run in the middle of a nursery writes its round down and is done at once.  Between two resumes,
+    // for all runs that wait: one launch of their ticks (and of whatever else was written down), one pack of their parked proposals into the
+    // one block, one wait, the prior and ONE call of the caller's function on this thread if the pack found rows at all.  A run whose count
+    // comes back zero is through with its nursery: it leaves the ticks, writes the rest of its round down and waits for the phase's end.
+    // Leaves enq[k] as enqueue_round says, the last records written down and not launched.  When a run throws, or the pack or the call
+    // does, the others are unwound as in finish_as_fibers and it is rethrown.
+    void enqueue_as_fibers()
+    {
+        std::vector<int> wk;
+        for (int k = 0; k < n; ++k) { enq[k] = 0; if (live[k]) wk.push_back(k); }
+        if (fibs.size() < wk.size()) fibs.resize(wk.size());
+        std::vector<char> ok(wk.size(), 0);
+        for (size_t a = 0; a < wk.size(); ++a) {
+            Fiber &f = fibs[a];
+            f.make_stack();
+            f.started = false; f.done = false; f.cancel = false; f.err = nullptr;
+            Engine *e = E[wk[a]]; char *okp = &ok[a];
+            f.fn = [e, okp] { *okp = e->round_enqueue() ? 1 : 0; };
+            e->fib = &f;
+        }
+        std::exception_ptr first_err;
+        for (;;) {
+            bool waiting = false;
+            for (size_t a = 0; a < wk.size(); ++a) {
+                Fiber &f = fibs[a];
+                if (f.done) continue;
+                f.resume();
+                if (f.err && !first_err) first_err = f.err;
+                if (!f.done) waiting = true;
+            }
+            if (first_err || !waiting) break;
+            const auto w0 = t.now();
+            try {
+                co.flush();
+                tg.pack(co.st);
+                pc_wait_stream(co.st);
+                tg.answer();
+            } catch (...) { first_err = std::current_exception(); break; }
+            t.fwait += t.sec(w0, t.now()); t.n_fwait++;
+        }
+        if (first_err) {
+            co.drop_pending(); tg.drop();
+            for (size_t a = 0; a < wk.size(); ++a) {
+                Fiber &f = fibs[a];
+                if (f.started && !f.done) { f.cancel = true; f.resume(); }
+            }
+            co.drop_pending(); tg.drop();
+        }
+        for (size_t a = 0; a < wk.size(); ++a) { E[wk[a]]->fib = nullptr; enq[wk[a]] = ok[a]; }
+        if (first_err) std::rethrow_exception(first_err);
     }
 
     // Assumes the round launched.  Leaves every run with a round under way told by the device what the round did.
@@ -296,7 +356,7 @@ struct StepGroup {
         eb->dev = E[eb->fin[0]]->dev;
         eb->ev = hpool().get_sync_event(); HIPCHK(hipEventRecord(eb->ev, co.st));
         if (co.st2) { eb->ev2 = hpool().get_sync_event(); HIPCHK(hipEventRecord(eb->ev2, co.st2)); }      // (bases drawn ahead for a run that is over: not into freed memory)
-        for (int k : eb->fin) { live[k] = 0; nlive--; if (E[k]->r_rc && !worst) worst = E[k]->r_rc; }
+        for (int k : eb->fin) { live[k] = 0; nlive--; tg.leave(k); if (E[k]->r_rc && !worst) worst = E[k]->r_rc; }
         eb->th = std::thread([this, eb] { end_batch(*eb); });
         t.end_dev += t.sec(e0, t.now());
     }
@@ -353,7 +413,7 @@ struct StepGroup {
     }
 
     // Assumes no ending under way.  Leaves nothing held: the runs still there (a failed call's) destroyed and their results freed, the
-    // fibers' stacks, the cohort's blocks and events, h_totals, the lease and the streams given back, each stream idle when it goes.
+    // fibers' stacks, the cohort's blocks and events, h_totals, the tick group's block, the lease and the streams given back, each stream idle when it goes.
     // The PC_DEBUG=5 report is made in between, once the side stream is idle and the last engine destroyed: its wall time and its teardown
     // figures take those in, and nothing of them is left for the next group's report.
     void release()
@@ -365,6 +425,7 @@ struct StepGroup {
         co.destroy();
         if (h_totals) { hfree(h_totals); h_totals = nullptr; }
         if (co.st) (void)hipStreamSynchronize(co.st);
+        tg.release();
         lease.release();
         if (co.st) { hpool().put_stream(co.st); co.st = nullptr; }
         if (co.st2) { (void)hipStreamSynchronize(co.st2); hpool().put_stream(co.st2); co.st2 = nullptr; }
@@ -376,7 +437,8 @@ struct StepGroup {
 }  // namespace
 
 // The runs of `seeds` on `device`, driven by the calling thread, up to max_in_flight of them in step on one stream, group after group.
-// Built-in device likelihoods only: a host callback belongs to its caller's thread.  Returns 0 or the first failing run's code.
+// Device likelihoods: the built-in ones, a source handle, or the caller's DEVICE batch callback, whose function is called on this thread for
+// the rows of the whole group (tg); a host callback belongs to its caller's thread.  Returns 0 or the first failing run's code.
 extern "C" int pc_run_many(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, int nseeds, const int *seeds, int device,
                            int max_in_flight, pchip_result *results)
 {

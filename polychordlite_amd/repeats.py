@@ -34,8 +34,9 @@ def run_in_step(settings, like, prior, seeds, max_in_flight=4, devices=None, wan
     """`run_repeats` for any problem that is wholly on the device (pchip_run_in_step): a built-in or a device source likelihood, plain or
     terms form, under the uniform box, a prior table or the handle's own source prior, and settings.ablate bit 15.  Up to `max_in_flight`
     runs of a device go round by round together, every kernel launched once for all of them; each run is bit for bit `_ctypes_api.run` of
-    its seed (runs[k]["path"]["slice_step"] counts its nurseries whose sampling launch was shared).  A callback likelihood or a host prior
-    raises.  Arguments and return value as `run_repeats`.  maximise=True: every run's dict gains "maximum" (`_ctypes_api.maximum_dict`), the
+    its seed (runs[k]["path"]["slice_step"] counts its nurseries whose sampling launch was shared).  A callback likelihood is taken while
+    `_ctypes_api.set_device_batch_callback` holds a function (one call a tick for the rows of all runs of a group, on this thread; one
+    device; `run_in_step_callable` does this for a torch callable); otherwise it raises, as a host prior does.  Arguments and return value as `run_repeats`.  maximise=True: every run's dict gains "maximum" (`_ctypes_api.maximum_dict`), the
     maximum-likelihood and maximum-posterior points polished from its final live set on the device, two launches for all runs
     (pchip_maximise_device_many); each is bit for bit `_ctypes_api.maximise_device` of that run alone."""
     merged, runs = _run("pchip_run_in_step", settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree)
@@ -57,6 +58,70 @@ def run_in_step(settings, like, prior, seeds, max_in_flight=4, devices=None, wan
             for m in mx:
                 lib.pchip_maximum_free(C.byref(m))
     return merged, runs
+
+
+def callable_problem(loglikelihood, prior, settings):
+    """(like, prior, evaluator, keep) for a torch callable marked `device_batch` and its prior, as `run_in_step_callable` hands them to the
+    library: an `_ctypes_api.Like` of kind callback, the `_ctypes_api.Prior` of UniformPrior / TablePrior (box / table: the engine's transform
+    on the block) or of kind 0 for a callable marked `prior.device_batch`, the `_DeviceBatchEvaluator` to register around the runs, and the
+    objects the structs point at.  With the evaluator registered, `_ctypes_api.run(settings, like, prior)` is the solo run of one seed."""
+    from .pypolychord import polychord as pc
+    if not pc._device_batch_pair(loglikelihood, prior):
+        raise ValueError("a likelihood marked loglikelihood.device_batch = True is needed")
+    nd, nder = int(settings.nDims), int(settings.nDerived)
+
+    def scalar(theta_p, n, phi_p, m):      # (like.fn must be a function; no run in step calls it)
+        out = pc._call_like(loglikelihood, np.ctypeslib.as_array(theta_p, shape=(n,)).copy())
+        if isinstance(out, tuple):
+            if m > 0:
+                np.ctypeslib.as_array(phi_p, shape=(m,))[:] = out[1]
+            out = out[0]
+        return float(out)
+    fl = api.LOGLIKE_FN(scalar)
+    like = api.Like(); like.kind = api.LIKE_CALLBACK; like.fn = C.cast(fl, C.c_void_p)
+    pr = api.Prior()
+    keep = [fl]
+    symbol = getattr(prior, "symbol", None)
+    if symbol == "polychord_hip_uniform_prior":
+        lo = np.ascontiguousarray(np.broadcast_to(prior.lo, (nd,)), dtype=np.float64)
+        hi = np.ascontiguousarray(np.broadcast_to(prior.hi, (nd,)), dtype=np.float64)
+        pr.kind, pr.lo, pr.hi = api.PRIOR_BOX, api.dptr(lo), api.dptr(hi)
+        keep += [lo, hi]
+    elif symbol == "polychord_hip_table_prior":
+        if nd != len(prior.entries):
+            raise ValueError(f"TablePrior has {len(prior.entries)} entries, the run {nd} parameters")
+        arr, hy = api.prior_table(prior.entries, prior.hyper)
+        pr.kind, pr.table = api.PRIOR_TABLE, arr
+        if hy is not None:
+            pr.hyper = hy.ctypes.data_as(C.POINTER(C.c_int))
+        keep += [arr, hy]
+    else:
+        pr.kind = api.PRIOR_CALLBACK          # the callable's own prior, on the device: the evaluator calls it on the cube block
+    return like, pr, pc._DeviceBatchEvaluator(loglikelihood, prior, nd, nder, settings.logzero), keep
+
+
+def run_in_step_callable(loglikelihood, prior, settings, seeds, max_in_flight=4, want_rows=False, write=None):
+    """`run_in_step` for a likelihood that is a torch callable on the device: `loglikelihood.device_batch = True`, theta tensor (n, nDims)
+    -> logL (n,) or (logL, phi), as `pypolychord.run` takes it.  prior: `UniformPrior` / `TablePrior` of pypolychord.device_likelihoods (the
+    engine evaluates it on the whole block) or a callable marked `prior.device_batch = True` (cube tensor -> theta tensor).  settings: an
+    `_ctypes_api.Settings`.  The seeds go in step, up to `max_in_flight` of them a group, and the callable is called ONCE a tick with the
+    parked proposals of all runs of the group, run after run in the order of `seeds` -- each run is its solo run if the callable's answer
+    for a row depends neither on the row's place in the block nor on n.  Returns (merged, runs) like `run_in_step`; what the callable raises
+    is raised here once the runs have wound down."""
+    like, pr, ev, keep = callable_problem(loglikelihood, prior, settings)
+    lib = ev.register()
+    try:
+        out = run_in_step(settings, like, pr, seeds, max_in_flight=max_in_flight, want_rows=want_rows, write=write)
+    except RuntimeError:
+        if ev.error is not None:
+            raise ev.error
+        raise
+    finally:
+        ev.unregister(lib)
+    if ev.error is not None:
+        raise ev.error
+    del keep
+    return out
 
 
 def _run(symbol, settings, like, prior, seeds, max_in_flight, devices, want_rows, write, comm, agree):

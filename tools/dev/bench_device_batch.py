@@ -10,6 +10,12 @@ transfers should not matter.  The runs alternate a, b, a, b ... in ONE process o
 ndead, nlike, log Z), so ticks/s and evaluations/s compare like with like.  Needs a GPU: there is no other path.
 
     python tools/dev/bench_device_batch.py --out profiles/device_batch.json
+
+--in-step: the other leg.  R = 4 and 16 seeds of that problem through pchip_run_in_step (one call a tick for the rows of all runs of the
+group) against the same seeds one after another through the solo device-batch pchip_run, alternating in one process, at both ends; every
+run in step is checked against its solo run (ndead, nlike, log Z).
+
+    python tools/dev/bench_device_batch.py --in-step --out profiles/device_batch_in_step.json
 """
 import argparse
 import ctypes as C
@@ -48,6 +54,9 @@ def main():
     ap.add_argument("--max-ndead-dear", type=int, default=2000, help="... at the dear end (a millisecond a call: the window is long anyway)")
     ap.add_argument("--inner-dear", type=int, default=200, help="passes of the dear end's kernel (about a millisecond a call)")
     ap.add_argument("--runs", type=int, default=5, help="timed runs per path and end, alternating")
+    ap.add_argument("--in-step", action="store_true", help="the in-step leg instead: R seeds through pchip_run_in_step against R solo runs")
+    ap.add_argument("--seeds", type=int, nargs="*", default=[4, 16], help="--in-step: the numbers of seeds R")
+    ap.add_argument("--legs", nargs="*", default=["solo", "in_step"], help="--in-step: the legs to run (one alone: for a kernel trace)")
     ap.add_argument("--so", default=None, help="a prebuilt libdbgauss.so")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -83,6 +92,79 @@ def main():
             lib.polychord_hip_set_device_batch_callback(None, None)
         return dict(seconds=dt, calls=int(ctx.calls), nlike=int(r["nlike"]), ndead=int(r["ndead"]), logZ=float(r["logZ"]),
                     t_loop=float(r["t_loop"]), t_generate=float(r["t_generate"]), device_batch=int(r["path"]["device_batch"]))
+
+    def solo_seeds(seeds, inner):
+        """the seeds one after another through the solo device-batch pchip_run"""
+        ctx = GaussCtx(0.5, 0.1, c0, inner, 0)
+        lib.polychord_hip_set_device_batch_callback(C.cast(g.gauss_device_batch, C.c_void_p), C.byref(ctx))
+        try:
+            t0 = time.perf_counter()
+            rs = []
+            for sd in seeds:
+                s.seed = sd
+                r = api.run(s, L, P)
+                rs.append((int(r["ndead"]), int(r["nlike"]), float(r["logZ"]), int(r["path"]["device_batch"])))
+                del r
+            dt = time.perf_counter() - t0
+        finally:
+            lib.polychord_hip_set_device_batch_callback(None, None)
+        return dict(seconds=dt, calls=int(ctx.calls), nlike=sum(x[1] for x in rs), runs=rs)
+
+    def step_seeds(seeds, inner):
+        """... and in step: one group of len(seeds) runs, one call a tick"""
+        from polychordlite_amd import repeats
+        ctx = GaussCtx(0.5, 0.1, c0, inner, 0)
+        lib.polychord_hip_set_device_batch_callback(C.cast(g.gauss_device_batch, C.c_void_p), C.byref(ctx))
+        try:
+            s.seed = seeds[0]
+            t0 = time.perf_counter()
+            merged, runs = repeats.run_in_step(s, L, P, seeds, max_in_flight=len(seeds))
+            dt = time.perf_counter() - t0
+            rs = [(int(r["ndead"]), int(r["nlike"]), float(r["logZ"]), int(r["path"]["device_batch"])) for r in runs]
+            t_runs = float(merged["t_runs_s"])
+            del merged, runs
+        finally:
+            lib.polychord_hip_set_device_batch_callback(None, None)
+        return dict(seconds=dt, runs_seconds=t_runs, calls=int(ctx.calls), nlike=sum(x[1] for x in rs), runs=rs)
+
+    if a.in_step:
+        report = dict(shape=dict(nDims=D, nlive=a.nlive, num_repeats=a.repeats, batch=a.batch), ends={})
+        for end, inner, max_ndead in (("cheap", 0, a.max_ndead), ("dear", a.inner_dear, a.max_ndead_dear)):
+            s.max_ndead = max_ndead
+            report["ends"][end] = {}
+            for R in a.seeds:
+                seeds = list(range(11, 11 + R))
+                legs = {k: f for k, f in (("solo", solo_seeds), ("in_step", step_seeds)) if k in a.legs}
+                for f in legs.values():             # warm-up: code objects, the block caches, the streams
+                    f(seeds, inner)
+                runs = {k: [] for k in legs}
+                for _ in range(a.runs):
+                    for k, f in legs.items():
+                        runs[k].append(f(seeds, inner))
+                same = len(legs) < 2 or runs["solo"][0]["runs"] == runs["in_step"][0]["runs"]
+                e = dict(inner=inner, max_ndead=max_ndead, seeds=R, same_runs=same)
+                for k in legs:
+                    sec = [x["seconds"] for x in runs[k]]
+                    med = statistics.median(sec)
+                    x0 = runs[k][0]
+                    e[k] = dict(seconds=sec, median_s=med, min_s=min(sec), max_s=max(sec), calls=x0["calls"], evaluations=x0["nlike"],
+                                rows_per_call=x0["nlike"] / x0["calls"], evals_per_s=x0["nlike"] / med, us_per_call=1e6 * med / x0["calls"])
+                    if k == "in_step":
+                        e[k]["runs_median_s"] = statistics.median(x["runs_seconds"] for x in runs[k])      # (without the merge of the runs)
+                if len(legs) == 2:
+                    e["solo_over_in_step"] = e["solo"]["median_s"] / e["in_step"]["median_s"]
+                report["ends"][end][str(R)] = e
+                print(f"{end:5s} inner {inner:5d}, {R:2d} seeds: same runs: {same}")
+                for k in legs:
+                    print(f"   {k:8s}: {e[k]['median_s']:.3f} s (min {e[k]['min_s']:.3f}, max {e[k]['max_s']:.3f})  {e[k]['calls']} calls, "
+                          f"{e[k]['rows_per_call']:.1f} rows a call, {e[k]['evals_per_s']:.0f} evaluations/s, {e[k]['us_per_call']:.1f} us a call")
+        g.gauss_release()
+        print(json.dumps(report))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(report, f, indent=1)
+                f.write("\n")
+        return
 
     report = dict(shape=dict(nDims=D, nlive=a.nlive, num_repeats=a.repeats, batch=a.batch), ends={})
     for end, inner, max_ndead in (("cheap", 0, a.max_ndead), ("dear", a.inner_dear, a.max_ndead_dear)):

@@ -137,6 +137,9 @@ int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t s
 int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchains, hipStream_t st) { return rec::launch("slice_fused", S, {batch, nchains}, st); }
 int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st) { return rec::launch_many("slice_many", S, dR, R, {nchains, fused}, st); }
 int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st) { return rec::launch_many("slice_step", S, dR, R, {nchains, fused}, st); }
+// (the tick stage of the device batch callback, CK_TICK: named by the table, in no scenario here -- the parent has no such stage)
+void pc_launch_slice_tick_dev(const PcState *S, unsigned batch, int nchains, void *, double *, int *, double *, const double *, const double *, const double *, int first, const int *, hipStream_t st) { rec::launch("slice_tick_dev", S, {batch, nchains, first}, st); }
+int pc_launch_slice_tick_many(const PcManyRec *dR, int R, int nchains, hipStream_t st) { return rec::launch_many("slice_tick_many", nullptr, dR, R, {nchains}, st); }
 int pc_launch_sort_live(const PcState *S, hipStream_t st) { return rec::launch("sort_live", S, {}, st); }
 int pc_launch_sort_live_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st) { return rec::launch_many("sort_live_many", S, dR, R, {}, st); }
 void pc_launch_nn_lists(const PcState *S, int nleft, int use_rank, hipStream_t st) { rec::launch("nn_lists", S, {nleft, use_rank}, st); }

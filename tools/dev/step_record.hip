@@ -251,6 +251,9 @@ int pc_launch_slice(const PcState *S, unsigned, int, hipStream_t st) { return re
 int pc_launch_slice_fused(const PcState *S, unsigned, int, hipStream_t st) { return rec::launch("slice_fused", S, nullptr, 0, st); }
 int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int, int, hipStream_t st) { return rec::launch("slice_many", S, dR, R, st); }
 int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R, int, int, hipStream_t st) { return rec::launch("slice_step", S, dR, R, st); }
+// (the tick stage of the device batch callback, CK_TICK: named by the cohort's table, in no scenario here)
+void pc_launch_slice_tick_dev(const PcState *S, unsigned, int, void *, double *, int *, double *, const double *, const double *, const double *, int, const int *, hipStream_t st) { rec::launch("slice_tick_dev", S, nullptr, 0, st); }
+int pc_launch_slice_tick_many(const PcManyRec *dR, int R, int, hipStream_t st) { return rec::launch("slice_tick_many", nullptr, dR, R, st); }
 int pc_launch_sort_live(const PcState *S, hipStream_t st) { return rec::launch("sort_live", S, nullptr, 0, st); }
 int pc_launch_sort_live_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st) { return rec::launch("sort_live_many", S, dR, R, st); }
 void pc_launch_nn_lists(const PcState *S, int, int, hipStream_t st) { rec::launch("nn_lists", S, nullptr, 0, st); }
@@ -361,6 +364,17 @@ struct Engine {
         say(std::string("destroyed") + (streams_idle ? " (streams idle)" : "") +
             (rec::driving() ? "; written down: " + rec::num((long long)co->pend.size()) + " records, " + rec::num((long long)(co->pre.size() + co->post.size())) + " closures, " + rec::num((long long)(co->pre_copies.size() + co->post_copies.size())) + " copies" : std::string()));
     }
+};
+
+// (what runs through the caller's device batch callback share, pc_tick.h: the scripted runs have no callback, the group's stays switched off)
+struct TickGroup {
+    bool on = false;
+    void set_up(const std::vector<Engine *> &, const std::vector<char> &, int) {}
+    void pack(hipStream_t) {}
+    void answer() {}
+    void leave(int) {}
+    void drop() {}
+    void release() {}
 };
 
 #ifdef STEP_PARENT
