@@ -230,7 +230,9 @@ typedef struct {
                            instead of five launches (flag, index, gather, fold, final): the same rows in the same order and the same groups of
                            sums, the same bits; slower at the metric configuration, kept as the independent second way the tests compare with;
                            bit 17 = a run on its own in pool mode: the update's flags by k_upd_flag in a launch of its own behind the row kernel
-                           instead of by workgroups of the row kernel's launch (k_apply_pool_flag): the same bits */
+                           instead of by workgroups of the row kernel's launch (k_apply_pool_flag): the same bits; bit 18 = the parallel
+                           contraction's acceptance as the serial recurrence, sixty-four steps at a time on one wavefront, instead of one dominance
+                           count a step for all steps at once (pc_par.hip): the same bits */
     const char *resume_write;  /* path of a .resume file (reference grammar, read_write.F90:219-288) rewritten at every
                                   update and at the end; NULL = off */
     int sequential_rng; /* tests: ONE Philox stream consumed in the reference's program order (forces batch = 1 and the
@@ -753,6 +755,14 @@ int  pchip_park_pack(int nchains, int nDims, const int *need, const double *prop
  * without need --, counts [nruns], *total, and cube [>= total][nDims]; rows of `cube` from the total on are not written.  0, 1 or 2 as above. */
 int  pchip_park_pack_many(int nruns, const int *nchains, int nDims, const int *need, const double *prop, int *rank, int *counts, int *total,
                           double *cube, int device);
+
+/* The acceptance of the one-cluster parallel contraction alone (tests/test_par_accept.py), host arrays in and out, the contraction's own
+ * device functions for its binary search, ranks and acceptance in between, one workgroup of 1024 threads on the keys of the logL given:
+ * snapshot_logL [n] ascending (1 <= n <= 8192), cand_logL [T] by step (1 <= T <= 1024), valid [T] (non-zero: a step of the current epoch)
+ * ->  accept [T] (1: the candidate of step t replaces the lowest live point).  serial != 0: by the serial recurrence (settings.ablate bit 18).
+ * 0, or 1 (arguments) / 2 (device). */
+int  pchip_par_accept(int n, const double *snapshot_logL, int T, const double *cand_logL, const unsigned char *valid, int serial,
+                      unsigned char *accept, int device);
 
 #ifdef __cplusplus
 }

@@ -175,6 +175,25 @@ def park_pack_many(nchains, need, prop, cube=None, device=-1):
     return rank, counts, tot.value, out
 
 
+def par_accept(snapshot_logL, cand_logL, valid=None, serial=False, device=-1):
+    """pchip_par_accept: the acceptance of the one-cluster parallel contraction alone.  snapshot_logL [n] ascending, cand_logL [T] by step,
+    valid [T] (None: every step); serial: by the serial recurrence (settings.ablate bit 18).  Returns accept [T] as bools."""
+    lib = load()
+    sn = np.ascontiguousarray(snapshot_logL, dtype=np.float64)
+    cd = np.ascontiguousarray(cand_logL, dtype=np.float64)
+    vl = np.ones(cd.size, dtype=np.uint8) if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    assert sn.ndim == 1 and cd.ndim == 1 and vl.shape == cd.shape
+    acc = np.full(cd.size, 0xEE, dtype=np.uint8)
+    bp = C.POINTER(C.c_ubyte)
+    lib.pchip_par_accept.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), bp, C.c_int, bp, C.c_int]
+    lib.pchip_par_accept.restype = C.c_int
+    rc = lib.pchip_par_accept(sn.size, dptr(sn), cd.size, dptr(cd), vl.ctypes.data_as(bp), 1 if serial else 0, acc.ctypes.data_as(bp), device)
+    if rc:
+        raise RuntimeError(f"pchip_par_accept failed with code {rc}")
+    assert np.all(acc <= 1)
+    return acc.astype(bool)
+
+
 _lib = None
 
 

@@ -2610,6 +2610,34 @@ int pchip_park_pack(int nchains, int nDims, const int *need, const double *prop,
     return rc;
 }
 
+// kernel-level entry for tests/test_par_accept.py: the acceptance of the parallel contraction (k_par_accept: par_search, par_rank, par_accept of
+// pc_par.hip) on host arrays
+int pchip_par_accept(int n, const double *snapshot_logL, int T, const double *cand_logL, const unsigned char *valid, int serial,
+                     unsigned char *accept, int device)
+{
+    if (n < 1 || n > 8192 || T < 1 || T > 1024 || !snapshot_logL || !cand_logL || !valid || !accept) {
+        pc_abi_set_last_error("pchip_par_accept: 1 <= n <= 8192 ascending snapshot values, 1 <= T <= 1024 candidates with their flags, and room for T answers");
+        return 1;
+    }
+    for (int i = 1; i < n; ++i) if (!(snapshot_logL[i - 1] <= snapshot_logL[i])) { pc_abi_set_last_error("pchip_par_accept: the snapshot is not ascending"); return 1; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); std::fprintf(stderr, "polychord_hip: no HIP device available -- this engine has no CPU path\n"); return 2; }
+    if (hipSetDevice(device >= 0 ? device % ndev : 0) != hipSuccess) return 2;
+    double *d_snap = nullptr, *d_cand = nullptr; unsigned char *d_valid = nullptr, *d_acc = nullptr;
+    int rc = 2;
+    if (hipMalloc(&d_snap, sizeof(double) * (size_t)n) == hipSuccess && hipMalloc(&d_cand, sizeof(double) * (size_t)T) == hipSuccess &&
+        hipMalloc(&d_valid, (size_t)T) == hipSuccess && hipMalloc(&d_acc, (size_t)T) == hipSuccess &&
+        hipMemcpy(d_snap, snapshot_logL, sizeof(double) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_cand, cand_logL, sizeof(double) * (size_t)T, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_valid, valid, (size_t)T, hipMemcpyHostToDevice) == hipSuccess && hipMemset(d_acc, 0xEE, (size_t)T) == hipSuccess) {
+        if (pc_launch_par_accept(n, d_snap, T, d_cand, d_valid, serial, d_acc, nullptr) == 0 && hipDeviceSynchronize() == hipSuccess &&
+            hipMemcpy(accept, d_acc, (size_t)T, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    }
+    if (rc) (void)hipGetLastError();
+    (void)hipFree(d_snap); (void)hipFree(d_cand); (void)hipFree(d_valid); (void)hipFree(d_acc);
+    return rc;
+}
+
 // kernel-level entry for tests/test_park_pack_many.py: the pack of a group of runs (k_park_index_many, k_park_rows_many) on host arrays, the
 // runs' flags, proposals and ranks one run behind the other
 int pchip_park_pack_many(int nruns, const int *nchains, int nDims, const int *need, const double *prop, int *rank, int *counts, int *total,

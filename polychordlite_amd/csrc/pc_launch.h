@@ -157,6 +157,10 @@ int pc_par_fits(const PcState *S);
 int pc_launch_consume_par(const PcState *S, hipStream_t st);
 // the same launch for R runs of one shape at once (blockIdx.y = run; dR: device array of their records)
 int pc_launch_consume_par_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st);
+// the contraction's binary search, ranks and acceptance alone, on the keys of given logL (device arrays: snap [n] ascending, cand [T] by step,
+// valid [T] -> accept [T]; serial: the acceptance of settings.ablate bit 18).  0: launched; 1: not these sizes (n <= 8192, T <= 1024)
+int pc_launch_par_accept(int n, const double *snap, int T, const double *cand, const unsigned char *valid, int serial, unsigned char *accept,
+                         hipStream_t st);
 // the one-cluster kill-off whole (the rows moved inside: runs in step) / split for a run on its own: k_final_par without its row loop, k_final_rows behind it
 int pc_launch_final_par(const PcState *S, hipStream_t st);
 int pc_launch_final_par_split(const PcState *S, hipStream_t st);

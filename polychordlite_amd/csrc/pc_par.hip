@@ -11,8 +11,10 @@
 //     before step t are the k_t smallest of S u A_t, and g_t is the (k_t+1)-th smallest;
 //   * hence  accept_t  <=>  #{e in S: e < c_t} > #{s < t accepted: c_s >= c_t}: acceptance depends on
 //     RANKS only.  The left side is a binary search, the right side a popcount over a bitmap of
-//     accepted ranks.  Steps are resolved 64 at a time (one wavefront, a fixpoint iteration over the
-//     in-chunk dependencies that settles in 2-3 rounds);
+//     accepted ranks.  A rejected candidate lay below a contour that only rises, so every later, smaller
+//     candidate is rejected whether it is counted or not: the right side may count every VALID earlier
+//     step of larger rank, and acceptance is a dominance count with no dependence between the steps
+//     (par_accept below; DESIGN section 5 has the proof);
 //   * points accepted later are larger than g_t, so g_t = u[k_t] with u = sorted(S u A_final): the
 //     j-th death of the launch is u[j], and the slot a candidate inherits is found by pointer
 //     jumping over "who died for whom";
@@ -235,6 +237,194 @@ __device__ __forceinline__ double block_scan_add(double v, int lane, int wv, dou
     return v + p;
 }
 
+// ---- phases 1-3 of the contraction: snapshot counts, ranks and acceptance of a nursery's candidates.  Functions of their own because the
+//      kernel-level door k_par_accept (pchip_par_accept, tests/test_par_accept.py) runs them on given keys, the same statements as a run.
+// The LDS tables they work on (every thread holds the same pointers)
+struct ParAcc {
+    const u64 *sSortK;   // [>= n] snapshot keys, ascending
+    const u64 *cK;       // [1024] candidate keys by step (KEY_HUGE at and behind T)
+    int *hist;           // [n + 2 and more] zeroed; candidates per snapshot gap, then gap offsets
+    int *srtT;           // [1024] steps by gap
+    int *accStep;        // [1024] scratch (sixteen words of it)
+    int *rnk, *rlo;      // [1024] rank among the candidates, snapshot points below the candidate
+    u64 *Gm;             // [1024] in-chunk "earlier and larger" masks (the serial resolution reads them)
+    u64 *accR, *amask;   // [16] zeroed; accepted candidates by rank, by step
+    const u64 *vmask;    // [16] steps of the current epoch
+    u64 *cmap;           // [16][16] zeroed; chunk c (64 steps), word w: the ranks of chunk c's valid steps
+    u64 *ccum;           // [16][16] the same of all chunks before c
+    int *ccnt;           // [16][16] bits of ccum[c] in the words before w; then [16] bits of ccum[c]
+    u64 *smap;           // [64][16] zeroed; row s (16 steps), word w: the ranks of row s's valid steps
+    u64 *scum;           // [64][16] the same of the rows before s in s's chunk
+    int *scnt;           // [64][16] bits of scum[s] in the words before w; then [64] bits of scum[s]
+    int *cumA, *cumV, *cumR;   // [17] exclusive per-word bit counts of amask, vmask, accR, then their totals
+};
+
+// phase 1: snapshot points strictly below (rl) / not above (rp) the candidate
+__device__ __forceinline__ void par_search(const u64 *sSortK, int n, u64 ck, bool inT, int &rl, int &rp)
+{
+    if (inT) {
+        int lo = 0, hi = n;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (sSortK[mid] < ck) lo = mid + 1; else hi = mid; }
+        rl = lo; rp = lo;
+        while (rp < n && sSortK[rp] == ck) rp++;
+    }
+}
+
+// phase 2: rank of every candidate among the candidates (equal keys: earlier step = larger).
+//      Candidates are already bucketed by the snapshot gap they fall in (rl): rank = candidates in
+//      lower gaps + candidates of the same gap that compare lower.
+__device__ __forceinline__ int par_rank(const ParAcc &A, int n, u64 ck, bool inT, int rl, int tid, int lane, int wv)
+{
+    const u64 *cK = A.cK; int *hist = A.hist, *srtT = A.srtT, *accStep = A.accStep;
+    int myoff = 0;
+    if (inT) myoff = atomicAdd(&hist[rl], 1);            // arrival order inside a gap: placement only
+    __syncthreads();
+    {
+        const int nb = n + 2;                             // gaps 0..n, plus one sentinel that receives T
+        const int per = (nb + PAR_NT - 1) / PAR_NT, b0 = tid * per;
+        int sum = 0;
+        for (int x = 0; x < per; ++x) if (b0 + x < nb) sum += hist[b0 + x];
+        int inc = sum;
+        inc = wave_scan_i32(inc, lane);
+        if (lane == 63) accStep[wv] = inc;
+        __syncthreads();
+        int run = inc - sum;
+        for (int x = 0; x < wv; ++x) run += accStep[x];
+        for (int x = 0; x < per; ++x) if (b0 + x < nb) { const int cnt = hist[b0 + x]; hist[b0 + x] = run; run += cnt; }
+    }
+    __syncthreads();
+    if (inT) srtT[hist[rl] + myoff] = tid;
+    __syncthreads();
+    int rho = tid;
+    if (inT) {
+        const int g0 = hist[rl], g1 = hist[rl + 1];
+        int below = 0;
+        for (int x = g0; x < g1; ++x) {
+            const int o = srtT[x];
+            const u64 ko = cK[o];
+            below += (ko < ck) || (ko == ck && o > tid);
+        }
+        rho = g0 + below;
+    }
+    return rho;
+}
+
+// phase 3: acceptance,  a_t = v_t and r_t > #{ s < t : v_s and rho_s > rho_t }  -- every VALID earlier candidate of larger rank counts,
+//      accepted or not: a 2-D dominance count with no dependence between the steps, taken at three widths.  Earlier
+//      chunks of 64 steps: from per-chunk rank bitmaps, cmap[c] = ranks of chunk c's valid steps, ccum[c] = those of all chunks before c,
+//      ccnt its exclusive per-word bit counts.  Earlier rows of 16 steps in my chunk: the same from per-row bitmaps (smap, scum, scnt).
+//      Earlier steps of my row: fifteen DPP row shifts of the rank, compared.
+//      serial (settings.ablate bit 18, the form of the recurrence  ... : a_s and ...): in-chunk "earlier and larger" masks by every wave,
+//      then wave 0 resolves the chunks in step order against the bitmap of accepted ranks.
+//      Leaves amask, accR, cumA / cumV / cumR behind a barrier.
+#define PAR_ROW_STEP(K) { const int o = __builtin_amdgcn_update_dpp(-1, rhoV, 0x110 + K, 0xF, 0xF, false); inrow += o > rho; }
+__device__ __forceinline__ void par_accept(const ParAcc &A, int T, bool serial, bool valid, int rl, int rho, int tid, int lane, int wv)
+{
+    int *rnk = A.rnk, *rlo = A.rlo, *accStep = A.accStep, *cumA = A.cumA, *cumV = A.cumV, *cumR = A.cumR;
+    u64 *Gm = A.Gm, *accR = A.accR, *amask = A.amask; const u64 *vmask = A.vmask;
+    int inrow = 0;                                        // valid earlier steps of my row with a larger rank
+    if (serial) {
+        u64 G = 0ull;
+        #pragma unroll
+        for (int j = 0; j < 64; ++j) {
+            const int rj = __builtin_amdgcn_readlane(rho, j);
+            if (j < lane && rj > rho) G |= 1ull << j;
+        }
+        Gm[tid] = G;
+    } else {
+        if (valid) {
+            atomicOr(&A.cmap[wv * PAR_W + (rho >> 6)], 1ull << (rho & 63));
+            atomicOr(&A.smap[(tid >> 4) * PAR_W + (rho >> 6)], 1ull << (rho & 63));
+        }
+        const int rhoV = valid ? rho : -1;                // (row_shr: a lane without a source keeps -1, which is larger than no rank)
+        PAR_ROW_STEP(1) PAR_ROW_STEP(2) PAR_ROW_STEP(3) PAR_ROW_STEP(4) PAR_ROW_STEP(5) PAR_ROW_STEP(6) PAR_ROW_STEP(7) PAR_ROW_STEP(8)
+        PAR_ROW_STEP(9) PAR_ROW_STEP(10) PAR_ROW_STEP(11) PAR_ROW_STEP(12) PAR_ROW_STEP(13) PAR_ROW_STEP(14) PAR_ROW_STEP(15)
+    }
+    __syncthreads();
+    if (!serial) {
+        {                                                 // thread = (row s, word w): a row's sixteen words are one DPP row
+            const int s = tid >> 4;
+            u64 o = 0ull;
+            for (int x = s & ~3; x < s; ++x) o |= A.smap[x * PAR_W + (tid & 15)];
+            A.scum[tid] = o;
+            const int cw = __popcll(o); int inc = cw;
+            inc += dpp_i32<0x111>(inc); inc += dpp_i32<0x112>(inc); inc += dpp_i32<0x114>(inc); inc += dpp_i32<0x118>(inc);
+            A.scnt[tid] = inc - cw;
+            if ((tid & 15) == PAR_W - 1) A.scnt[PAR_NT + s] = inc;
+        }
+        if (tid < PAR_W * PAR_W) {                        // thread = (chunk c, word w)
+            const int c = tid >> 4;
+            u64 o = 0ull;
+            for (int x = 0; x < c; ++x) o |= A.cmap[x * PAR_W + (tid & 15)];
+            A.ccum[tid] = o;
+            const int cw = __popcll(o); int inc = cw;
+            inc += dpp_i32<0x111>(inc); inc += dpp_i32<0x112>(inc); inc += dpp_i32<0x114>(inc); inc += dpp_i32<0x118>(inc);
+            A.ccnt[tid] = inc - cw;
+            if ((tid & 15) == PAR_W - 1) A.ccnt[PAR_W * PAR_W + c] = inc;
+        }
+        __syncthreads();
+        const int wq = rho >> 6, bq = rho & 63, s = tid >> 4;
+        const u64 le = ((1ull << bq) << 1) - 1ull;
+        // valid before my chunk / before my row in it with a larger rank = all of them minus those at or below my rank; then my own row's
+        const int P = A.ccnt[PAR_W * PAR_W + wv] - A.ccnt[wv * PAR_W + wq] - __popcll(A.ccum[wv * PAR_W + wq] & le)
+                      + A.scnt[PAR_NT + s] - A.scnt[s * PAR_W + wq] - __popcll(A.scum[s * PAR_W + wq] & le) + inrow;
+        const bool a = valid && rl > P;
+        const u64 am = __ballot(a);
+        if (lane == 0) amask[wv] = am;
+        if (a) atomicOr(&accR[wq], 1ull << bq);
+        __syncthreads();
+    }
+    if (wv == 0) {
+        if (serial) {
+            const int nch = (T + 63) >> 6;
+            int *cum = accStep;                               // [16] accepted candidates in the bitmap words before x
+            if (lane < PAR_W) cum[lane] = 0;
+            __threadfence_block();
+            int rho_t = rnk[lane], r = rlo[lane], tot = 0;
+            u64 Gt = Gm[lane];
+            for (int c = 0; c < nch; ++c) {
+                // operands of the next chunk travel while this one is resolved
+                const int tn = (c + 1 < nch) ? (c + 1) * 64 + lane : lane;
+                const int nrho = rnk[tn], nr2 = rlo[tn];
+                const u64 nG = Gm[tn];
+                const bool v = (vmask[c] >> lane) & 1ull;
+                const int wq = rho_t >> 6, bq = rho_t & 63;
+                // accepted in earlier chunks with a larger rank = all of them minus those at or below my rank
+                const int P = tot - cum[wq] - __popcll(accR[wq] & (((1ull << bq) << 1) - 1ull));
+                u64 am = __ballot(v && r > P);
+                for (int it = 0; it < 66; ++it) {
+                    const bool a = v && r > P + __popcll(Gt & am);
+                    const u64 nm = __ballot(a);
+                    if (nm == am) break;
+                    am = nm;
+                }
+                if ((am >> lane) & 1ull) atomicOr(&accR[wq], 1ull << bq);
+                if (lane == 0) amask[c] = am;
+                tot += __popcll(am);
+                PAR_WAVE_ORDER();                             // (LDS operations of one wave execute in issue order: nothing to wait for)
+                {   // refresh the per-word offsets
+                    int cw = (lane < PAR_W) ? __popcll(accR[lane]) : 0, inc = cw;      // (sixteen words = one DPP row: row shifts, no LDS crossbar)
+                    inc += dpp_i32<0x111>(inc); inc += dpp_i32<0x112>(inc); inc += dpp_i32<0x114>(inc); inc += dpp_i32<0x118>(inc);
+                    if (lane < PAR_W) cum[lane] = inc - cw;
+                }
+                PAR_WAVE_ORDER();
+                rho_t = nrho; r = nr2; Gt = nG;
+            }
+        }
+        {   // the offsets every thread counts from in the phases below
+            const int ca = (lane < PAR_W) ? __popcll(amask[lane]) : 0, cv = (lane < PAR_W) ? __popcll(vmask[lane]) : 0,
+                      cr = (lane < PAR_W) ? __popcll(accR[lane]) : 0;
+            int ia = ca, iv = cv, ir = cr;
+            ia += dpp_i32<0x111>(ia); ia += dpp_i32<0x112>(ia); ia += dpp_i32<0x114>(ia); ia += dpp_i32<0x118>(ia);
+            iv += dpp_i32<0x111>(iv); iv += dpp_i32<0x112>(iv); iv += dpp_i32<0x114>(iv); iv += dpp_i32<0x118>(iv);
+            ir += dpp_i32<0x111>(ir); ir += dpp_i32<0x112>(ir); ir += dpp_i32<0x114>(ir); ir += dpp_i32<0x118>(ir);
+            if (lane < PAR_W) { cumA[lane] = ia - ca; cumV[lane] = iv - cv; cumR[lane] = ir - cr; }
+            if (lane == PAR_W - 1) { cumA[PAR_W] = ia; cumV[PAR_W] = iv; cumR[PAR_W] = ir; }
+        }
+    }
+    __syncthreads();
+}
+
 __device__ __forceinline__ void consume_par_body(const PcState &S)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -272,6 +462,10 @@ __device__ __forceinline__ void consume_par_body(const PcState &S)
     int *hist = ish + 16;                    // [NS + 64] candidates per snapshot gap, then gap offsets
     double *X5 = (double *)(hist + NS + 64); // [1024] scan scratch (third sequence)
     double *sLse = (double *)Gm;
+    // phase 3 only, in tables that are written from phase 4 on: the rank bitmaps of the chunks, the chunks before them and their counts (uKey,
+    // uSrc), of the rows of sixteen steps (srtK), the rows before them in their chunk (sZi) and their counts (slotA, parA)
+    u64 *cmap = uKey, *smap = srtK, *scum = (u64 *)sZi;
+    const bool acc_serial = (S.ablate & PC_ABL_ACCEPT_SERIAL) != 0;   // (bit 18: the acceptance as the serial recurrence -- tests compare the two on the same run)
 
     const int epoch = ctl->admin_epoch;
     const int ndead0 = ctl->ndead, fail0 = ctl->failures, nph0 = ctl->nphantom;
@@ -304,116 +498,26 @@ __device__ __forceinline__ void consume_par_body(const PcState &S)
         const u64 vm = __ballot(valid);
         if (lane == 0) { vmask[wv] = vm; accR[wv] = 0ull; amask[wv] = 0ull; }
     }
+    if (tid < PAR_W * PAR_W) cmap[tid] = 0ull;
+    smap[tid] = 0ull;
     if (tid == 0) { ish[0] = (T << 2) | 3; ish[1] = 0; ish[3] = 0; }
     __syncthreads();
     const double l0 = ulog[0], l1 = ulog[1], l2 = ulog[2], d01 = l0 - l1, d02 = l0 - l2;
 
     // ---- phase 1: snapshot points strictly below / not above the candidate
     int rl = 0, rp = 0;
-    if (inT) {
-        int lo = 0, hi = n;
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (sSortK[mid] < ck) lo = mid + 1; else hi = mid; }
-        rl = lo; rp = lo;
-        while (rp < n && sSortK[rp] == ck) rp++;
-    }
+    par_search(sSortK, n, ck, inT, rl, rp);
     rlo[tid] = rl;
 
     cyc[ncy++] = clock64();
-    // ---- phase 2: rank of every candidate among the candidates (equal keys: earlier step = larger).
-    //      Candidates are already bucketed by the snapshot gap they fall in (rl): rank = candidates in
-    //      lower gaps + candidates of the same gap that compare lower.
-    int myoff = 0;
-    if (inT) myoff = atomicAdd(&hist[rl], 1);            // arrival order inside a gap: placement only
-    __syncthreads();
-    {
-        const int nb = n + 2;                             // gaps 0..n, plus one sentinel that receives T
-        const int per = (nb + PAR_NT - 1) / PAR_NT, b0 = tid * per;
-        int sum = 0;
-        for (int x = 0; x < per; ++x) if (b0 + x < nb) sum += hist[b0 + x];
-        int inc = sum;
-        inc = wave_scan_i32(inc, lane);
-        if (lane == 63) accStep[wv] = inc;
-        __syncthreads();
-        int run = inc - sum;
-        for (int x = 0; x < wv; ++x) run += accStep[x];
-        for (int x = 0; x < per; ++x) if (b0 + x < nb) { const int cnt = hist[b0 + x]; hist[b0 + x] = run; run += cnt; }
-    }
-    __syncthreads();
-    if (inT) srtT[hist[rl] + myoff] = tid;
-    __syncthreads();
-    int rho = tid;
-    if (inT) {
-        const int g0 = hist[rl], g1 = hist[rl + 1];
-        int below = 0;
-        for (int x = g0; x < g1; ++x) {
-            const int o = srtT[x];
-            const u64 ko = cK[o];
-            below += (ko < ck) || (ko == ck && o > tid);
-        }
-        rho = g0 + below;
-    }
+    // ---- phase 2: rank of every candidate among the candidates (equal keys: earlier step = larger)
+    const ParAcc A = { sSortK, cK, hist, srtT, accStep, rnk, rlo, Gm, accR, amask, vmask, cmap, cmap + PAR_W * PAR_W, uSrc, smap, scum, slotA, cumA, cumV, cumR };
+    const int rho = par_rank(A, n, ck, inT, rl, tid, lane, wv);
     rnk[tid] = rho;
 
     cyc[ncy++] = clock64();
-    // ---- phase 3: acceptance.  In-chunk dependency masks by every wave, then wave 0 resolves the
-    //      chunks in step order against the bitmap of accepted ranks.
-    {
-        u64 G = 0ull;
-        #pragma unroll
-        for (int j = 0; j < 64; ++j) {
-            const int rj = __builtin_amdgcn_readlane(rho, j);
-            if (j < lane && rj > rho) G |= 1ull << j;
-        }
-        Gm[tid] = G;
-    }
-    __syncthreads();
-    if (wv == 0) {
-        const int nch = (T + 63) >> 6;
-        int *cum = accStep;                               // [16] accepted candidates in the bitmap words before x
-        if (lane < PAR_W) cum[lane] = 0;
-        __threadfence_block();
-        int rho_t = rnk[lane], r = rlo[lane], tot = 0;
-        u64 Gt = Gm[lane];
-        for (int c = 0; c < nch; ++c) {
-            // operands of the next chunk travel while this one is resolved
-            const int tn = (c + 1 < nch) ? (c + 1) * 64 + lane : lane;
-            const int nrho = rnk[tn], nr2 = rlo[tn];
-            const u64 nG = Gm[tn];
-            const bool v = (vmask[c] >> lane) & 1ull;
-            const int wq = rho_t >> 6, bq = rho_t & 63;
-            // accepted in earlier chunks with a larger rank = all of them minus those at or below my rank
-            const int P = tot - cum[wq] - __popcll(accR[wq] & (((1ull << bq) << 1) - 1ull));
-            u64 am = __ballot(v && r > P);
-            for (int it = 0; it < 66; ++it) {
-                const bool a = v && r > P + __popcll(Gt & am);
-                const u64 nm = __ballot(a);
-                if (nm == am) break;
-                am = nm;
-            }
-            if ((am >> lane) & 1ull) atomicOr(&accR[wq], 1ull << bq);
-            if (lane == 0) amask[c] = am;
-            tot += __popcll(am);
-            PAR_WAVE_ORDER();                             // (LDS operations of one wave execute in issue order: nothing to wait for)
-            {   // refresh the per-word offsets
-                int cw = (lane < PAR_W) ? __popcll(accR[lane]) : 0, inc = cw;      // (sixteen words = one DPP row: row shifts, no LDS crossbar)
-                inc += dpp_i32<0x111>(inc); inc += dpp_i32<0x112>(inc); inc += dpp_i32<0x114>(inc); inc += dpp_i32<0x118>(inc);
-                if (lane < PAR_W) cum[lane] = inc - cw;
-            }
-            PAR_WAVE_ORDER();
-            rho_t = nrho; r = nr2; Gt = nG;
-        }
-        {   // the offsets every thread counts from in the phases below
-            const int ca = (lane < PAR_W) ? __popcll(amask[lane]) : 0, cv = (lane < PAR_W) ? __popcll(vmask[lane]) : 0,
-                      cr = (lane < PAR_W) ? __popcll(accR[lane]) : 0;
-            int ia = ca, iv = cv, ir = cr;
-            ia += dpp_i32<0x111>(ia); ia += dpp_i32<0x112>(ia); ia += dpp_i32<0x114>(ia); ia += dpp_i32<0x118>(ia);
-            iv += dpp_i32<0x111>(iv); iv += dpp_i32<0x112>(iv); iv += dpp_i32<0x114>(iv); iv += dpp_i32<0x118>(iv);
-            ir += dpp_i32<0x111>(ir); ir += dpp_i32<0x112>(ir); ir += dpp_i32<0x114>(ir); ir += dpp_i32<0x118>(ir);
-            if (lane < PAR_W) { cumA[lane] = ia - ca; cumV[lane] = iv - cv; cumR[lane] = ir - cr; }
-            if (lane == PAR_W - 1) { cumA[PAR_W] = ia; cumV[PAR_W] = iv; cumR[PAR_W] = ir; }
-        }
-    }
-    __syncthreads();
+    // ---- phase 3: acceptance: one dominance count a step, all steps at once (bit 18: wave 0 resolves the chunks in step order)
+    par_accept(A, T, acc_serial, valid, rl, rho, tid, lane, wv);
 
     cyc[ncy++] = clock64();
     // ---- phase 4: counts
@@ -767,6 +871,69 @@ __device__ __forceinline__ void consume_par_body(const PcState &S)
 }
 __global__ __launch_bounds__(PAR_NT) void k_consume_par(PcState S) { consume_par_body(S); }
 __global__ __launch_bounds__(PAR_NT) void k_consume_par_many(const PcManyRec *R) { consume_par_body(pc_many_state(R, blockIdx.y)); }
+
+// Kernel-level door (pchip_par_accept, tests/test_par_accept.py): phases 1-3 alone -- par_search, par_rank, par_accept as the contraction
+// calls them -- on the keys of given logL: snap [n] ascending, cand [T] by step, valid_in [T]  ->  accept [T].  One workgroup.
+__global__ __launch_bounds__(PAR_NT) void k_par_accept(int n, const double *snap, int T, const double *cand, const unsigned char *valid_in,
+                                                       int serial, unsigned char *accept)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int NS = (n + 63) & ~63;
+    u64 *sSortK = (u64 *)smem;               // [NS]
+    u64 *cK = sSortK + NS;                   // [1024]
+    u64 *Gm = cK + PAR_NT;                   // [1024]
+    u64 *cmap = Gm + PAR_NT;                 // [2][16][16]
+    u64 *smap = cmap + 2 * PAR_W * PAR_W;    // [2][64][16]
+    u64 *accR = smap + 2 * PAR_NT;           // [16]
+    u64 *amask = accR + PAR_W;               // [16]
+    u64 *vmask = amask + PAR_W;              // [16]
+    int *srtT = (int *)(vmask + PAR_W);      // [1024]
+    int *rnk = srtT + PAR_NT;                // [1024]
+    int *rlo = rnk + PAR_NT;                 // [1024]
+    int *accStep = rlo + PAR_NT;             // [1024]
+    int *ccnt = accStep + PAR_NT;            // [16][16] + [16]
+    int *scnt = ccnt + PAR_W * PAR_W + PAR_W;   // [64][16] + [64]
+    int *hist = scnt + PAR_NT + 64;          // [NS + 64]
+    __shared__ int cumA[PAR_W + 1], cumV[PAR_W + 1], cumR[PAR_W + 1];
+    for (int i = tid; i < NS; i += PAR_NT) sSortK[i] = (i < n) ? d2key(snap[i]) : KEY_HUGE;
+    const bool inT = tid < T;
+    u64 ck = KEY_HUGE; bool valid = false;
+    if (inT) { ck = d2key(cand[tid]); valid = valid_in[tid] != 0; }
+    cK[tid] = ck;
+    for (int i = tid; i < NS + 64; i += PAR_NT) hist[i] = 0;
+    {
+        const u64 vm = __ballot(valid);
+        if (lane == 0) { vmask[wv] = vm; accR[wv] = 0ull; amask[wv] = 0ull; }
+    }
+    if (tid < PAR_W * PAR_W) cmap[tid] = 0ull;
+    smap[tid] = 0ull;
+    __syncthreads();
+    int rl = 0, rp = 0;
+    par_search(sSortK, n, ck, inT, rl, rp);
+    rlo[tid] = rl;
+    const ParAcc A = { sSortK, cK, hist, srtT, accStep, rnk, rlo, Gm, accR, amask, vmask, cmap, cmap + PAR_W * PAR_W, ccnt, smap, smap + PAR_NT, scnt, cumA, cumV, cumR };
+    const int rho = par_rank(A, n, ck, inT, rl, tid, lane, wv);
+    rnk[tid] = rho;
+    par_accept(A, T, serial != 0, valid, rl, rho, tid, lane, wv);
+    if (inT) accept[tid] = (unsigned char)((amask[wv] >> lane) & 1ull);
+}
+#define PAR_DOOR_NMAX 8192
+static size_t par_door_lds(int n)
+{
+    const size_t NS = ((size_t)n + 63) & ~(size_t)63;
+    return 8 * (NS + 4 * PAR_NT + 2 * PAR_W * PAR_W + 3 * PAR_W) + 4 * (5 * PAR_NT + 64 + PAR_W * PAR_W + PAR_W + NS + 64);
+}
+// 0: launched; 1: not these sizes (1 <= n <= 8192 snapshot points, 1 <= T <= 1024 steps).  Device arrays.
+extern "C" int pc_launch_par_accept(int n, const double *snap, int T, const double *cand, const unsigned char *valid, int serial,
+                                    unsigned char *accept, hipStream_t st)
+{
+    if (n < 1 || n > PAR_DOOR_NMAX || T < 1 || T > PAR_NT) return 1;
+    const size_t sh = par_door_lds(n);
+    pc_need_dyn_lds((const void *)k_par_accept, sh);
+    hipLaunchKernelGGL(k_par_accept, dim3(1), dim3(PAR_NT), sh, st, n, snap, T, cand, valid, serial, accept);
+    return 0;
+}
 
 
 // ------------------------------------------------------------------------------------------
