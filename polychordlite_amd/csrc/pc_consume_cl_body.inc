@@ -792,9 +792,10 @@
             // the cross-volume matrix of 70 clusters, a hundred times per run)
             {
                 const int m1 = nc - 1;
-                double v[64];
+                constexpr int NV = (CL_MAXC * CL_MAXC + CL_NT - 1) / CL_NT;      // (a thread's share of the largest matrix; as in pc_consume_clp_body.inc)
+                double v[NV];
 #pragma unroll
-                for (int u = 0; u < 64; ++u) {
+                for (int u = 0; u < NV; ++u) {
                     const int e = tid + u * CL_NT;
                     if (e < m1 * m1) { const int na = e / m1, nb = e % m1; v[u] = S.XpXq[(size_t)(na + (na >= p)) * maxc + nb + (nb >= p)]; }
                 }
@@ -806,7 +807,7 @@
                 }
                 __syncthreads();
 #pragma unroll
-                for (int u = 0; u < 64; ++u) {
+                for (int u = 0; u < NV; ++u) {
                     const int e = tid + u * CL_NT;
                     if (e < m1 * m1) S.XpXq[(size_t)(e / m1) * maxc + e % m1] = v[u];
                 }
