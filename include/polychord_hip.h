@@ -232,7 +232,9 @@ typedef struct {
                            bit 17 = a run on its own in pool mode: the update's flags by k_upd_flag in a launch of its own behind the row kernel
                            instead of by workgroups of the row kernel's launch (k_apply_pool_flag): the same bits; bit 18 = the parallel
                            contraction's acceptance as the serial recurrence, sixty-four steps at a time on one wavefront, instead of one dominance
-                           count a step for all steps at once (pc_par.hip): the same bits */
+                           count a step for all steps at once (pc_par.hip): the same bits; bit 19 = a run on its own, nDims <= 24, one grade:
+                           the orthonormal bases by the kernel with a wavefront a basis (k_nhats) instead of 64 / nDims bases a wavefront
+                           (k_nhats_w, pc_sample.hip): the same bits */
     const char *resume_write;  /* path of a .resume file (reference grammar, read_write.F90:219-288) rewritten at every
                                   update and at the end; NULL = off */
     int sequential_rng; /* tests: ONE Philox stream consumed in the reference's program order (forces batch = 1 and the
@@ -687,7 +689,16 @@ int  pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const p
 int  pchip_directions(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, unsigned batch, int nchains,
                       const double *seeds, const double *chol, int path, double *nhat_out, double *nhat_w_out,
                       double *nhat_Ms_out, double *ch_My_out, int *has_Ms, double *raw_out, int nrows, int nbases);
-/* kernel-level: the DEVICE transform of a prior table (prior->kind == PCHIP_PRIOR_TABLE) at n hypercube points, cube [n][nDims] in,
+/* kernel-level: the deck records that the first half of the split launch leaves behind the bases of a nursery (nDims <= 24, one grade, keyed
+ * draws, num_repeats <= 64): per chain 66 ints, [tag low word, tag high word, deck[64]] -- deck[p] is the direction slice p of the chain
+ * takes (the first stays, the others are shuffled), the tag a function of (seed keys, batch, chain, num_repeats) under which the sampling
+ * kernel recognises the record.  Set up as pchip_directions, bases only, by the kernel a run on its own takes (settings.ablate bit 19: the
+ * kernel with a wavefront a basis).  records [nchains][66] (host memory) is IN and OUT: it is placed behind the bases before the launch, so
+ * where no record is written (num_repeats > 64) it comes back as it was.
+ * 0, 1 (bad arguments, message in polychord_hip_last_error()), PCHIP_NO_SUCH_PATH (nDims > 24, grades, the sequential stream), else a
+ * pchip_run code. */
+int  pchip_deck_records(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, unsigned batch, int nchains, int *records);
+/* kernel-level: the DEVICE transform of a prior table(prior->kind == PCHIP_PRIOR_TABLE) at n hypercube points, cube [n][nDims] in,
  * theta [n][nDims] out (host memory) -- parity tests against polychord_hip_table_prior.  0, 1 (a bad table, message in
  * polychord_hip_last_error()), 2 (no device), 3 (nDims > 256). */
 int  pchip_prior_transform(const pchip_prior *prior, int nDims, int n, const double *cube, double *theta, int device);

@@ -587,6 +587,24 @@ def directions(settings, like, prior, batch, seeds, chol, path):
     return dict(nhat=nhat, nhat_w=w, nhat_Ms=Ms if has.value else None, ch_My=My if has.value else None, raw=raw if path else None)
 
 
+def deck_records(settings, like, prior, batch, nchains, fill=-1):
+    """pchip_deck_records: the deck records the first half of the split launch leaves behind the bases of `nchains` chains, int32
+    [nchains][66] = [tag lo, tag hi, deck[64]] exactly as they lie there; every int is `fill` where the kernel wrote nothing.  None where
+    the state has no such path."""
+    lib = load()
+    # (bound here, not in load(): PCHIP_LIB may name an older build that has no such door)
+    lib.pchip_deck_records.argtypes = [C.POINTER(Settings), C.POINTER(Like), C.POINTER(Prior), C.c_uint, C.c_int, C.POINTER(C.c_int)]
+    lib.pchip_deck_records.restype = C.c_int
+    rec = np.full((nchains, 66), fill, dtype=np.int32)
+    rc = lib.pchip_deck_records(C.byref(settings), C.byref(like), C.byref(prior), batch, nchains, rec.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc == NO_SUCH_PATH:
+        return None
+    if rc != 0:
+        msg = lib.polychord_hip_last_error()
+        raise RuntimeError(f"pchip_deck_records failed with code {rc}" + (": " + msg.decode(errors="replace") if rc == 1 and msg else ""))
+    return rec
+
+
 def maximum_dict(m, nDims, nDerived):
     """dict copy of a filled pchip_maximum (the struct stays the caller's to free): status, cluster, niter, neval per leg ([0] likelihood,
     [1] posterior), max_logl / max_point, max_post / logl_at_post / post_point, logl_mean / mean_point (None without a mean)"""

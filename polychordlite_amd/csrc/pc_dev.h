@@ -158,6 +158,73 @@ __device__ inline double pc_inv_normal_tail(double p)
     return (q < 0.0) ? -v : v;
 }
 
+// ---------------------------------------------------------------- Gram-Schmidt, thread = vector, 64 / nDims bases a wavefront
+// The normalisation and Gram-Schmidt of k_nhats<DMAX, 64, 1> (pc_sample.hip) for the kernels that pack several bases into a wavefront --
+// k_bases_packed (pc_slice_t.hip: deviates already in HBM) and k_nhats_w (pc_sample.hip: deviates made in place) -- ONE text, PC_GS_PACKED: k_nhats'
+// arithmetic operation for operation, dot products on four partial sums (and the way the compiler fuses `0 + a0 a0 + a4 a4` there), the
+// projection as one fused multiply-add per coordinate.
+// a.a as k_nhats' PC_DOT4(x, a, a) comes out of the compiler: four partial sums over coordinates d = k, k + 4, ...; each starts as
+// 0 + a_k a_k + a_{k+4} a_{k+4}, of which ONE product is rounded and the other fused into the addition -- which one is the
+// compiler's choice per site (read from the ISA of libpolychord_hip.so: the pivot's q.q fuses a_k everywhere; the norm of a raw
+// vector fuses a_4, not a_0, in the kernels compiled for nDims <= 16).  tests/test_gpu_parity.py holds the kernels together.
+template <int D, bool FIRST_RIGHT>
+__device__ __forceinline__ double dot4_same(const double (&a)[D])
+{
+#pragma clang fp contract(off)
+    double pp[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k >= D) pp[k] = 0.0;
+        else if (k + 4 >= D) pp[k] = fma(a[k], a[k], 0.0);
+        else if (FIRST_RIGHT && k == 0) pp[k] = fma(a[k + 4 < D ? k + 4 : 0], a[k + 4 < D ? k + 4 : 0], a[k] * a[k]);
+        else pp[k] = fma(a[k], a[k], a[k + 4 < D ? k + 4 : 0] * a[k + 4 < D ? k + 4 : 0]);
+    }
+#pragma unroll
+    for (int d = 8; d < D; ++d) pp[d & 3] = fma(a[d], a[d], pp[d & 3]);
+    return (pp[0] + pp[1]) + (pp[2] + pp[3]);
+}
+template <int D>
+__device__ __forceinline__ double dot4(const double (&a)[D], const double (&b)[D])
+{
+#pragma clang fp contract(off)
+    double pp[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int d = 0; d < D; ++d) pp[d & 3] = fma(a[d], b[d], pp[d & 3]);
+    return (pp[0] + pp[1]) + (pp[2] + pp[3]);
+}
+// The normalisation and the steps as text, not as a function: inlined from a function the same statements reach the register allocator in
+// another order, and k_bases_packed would no longer be the instructions it was (tools/dev/isa_diff.py) -- the kernels hold their bits
+// together by what the compiler makes of this text, so both take the text itself.  Under `#pragma clang fp contract(off)` in the caller.
+// v: this thread's raw vector (vector i of its basis, zero padded to DMAX; zeros in a thread without a vector, active = false); Q: [2][DMAX]
+// of LDS, the pivot of this thread's basis, double buffered.  Every thread of the workgroup comes here: a barrier per Gram-Schmidt step.
+#define PC_GS_PACKED(DMAX, v, Q, D, i, active) \
+    {   /* random_direction (random_utils.F90:276-298) */ \
+        const double inrm = 1.0 / sqrt(dot4_same<DMAX, (DMAX <= 16)>(v)); \
+        _Pragma("unroll") for (int d = 0; d < DMAX; ++d) v[d] = v[d] * inrm; \
+    } \
+    if (i == 0 && active) { \
+        _Pragma("unroll") for (int d = 0; d < DMAX; ++d) Q[d] = v[d]; \
+    } \
+    __syncthreads(); \
+    for (int j = 0; j < D; ++j) {                                               /* Gram-Schmidt (random_utils.F90:391-399), k_nhats' steps */ \
+        const double *q = Q + (size_t)(j & 1) * DMAX; \
+        double qv[DMAX]; \
+        _Pragma("unroll") for (int d = 0; d < DMAX; ++d) qv[d] = active ? q[d] : 0.0; \
+        const double qq = dot4_same<DMAX, false>(qv), dv = dot4<DMAX>(qv, v); \
+        if (i == j) { \
+            const double inrm = 1.0 / sqrt(qq); \
+            _Pragma("unroll") for (int d = 0; d < DMAX; ++d) v[d] = v[d] * inrm; \
+        } else if (active && i > j) { \
+            const double cproj = dv / qq; \
+            _Pragma("unroll") for (int d = 0; d < DMAX; ++d) v[d] = fma(-cproj, qv[d], v[d]); \
+            if (i == j + 1) { \
+                double *qn = Q + (size_t)((j + 1) & 1) * DMAX; \
+                _Pragma("unroll") for (int d = 0; d < DMAX; ++d) qn[d] = v[d]; \
+            } \
+        } \
+        __syncthreads(); \
+    }
+
 // ---------------------------------------------------------------- log-space sums
 __device__ __forceinline__ double pc_logaddexp(double a, double b)
 {   // utils.F90:377-389:  (a > b) ? a + log(exp(b - a) + 1) : b + log(exp(a - b) + 1)

@@ -1855,7 +1855,7 @@ struct Engine {
                     if (rs.valid) HIPCHK(hipStreamWaitEvent(st, rs.ready, 0));       // (a stale job may still be writing there)
                     // (not stage(): a run on its own passes its packed flag, the row's one-run launch 1)
                     if (ch.bases == PC_BASES_PART1_STEP) co->rec(rec_bases(S, batch, B));
-                    else (void)pc_launch_nhats_part(&S, batch, B, 1, st, ch.packed ? 1 : 0);
+                    else (void)pc_launch_nhats_part(&S, batch, B, 1, st, pc_part1_kind(ch.packed, cfg.ablate));
                 }
                 rs.valid = false;
                 if (ch.part2) { if (co) { co->flush(); co->wait_next(); } (void)pc_launch_nhats_part(&S, batch, B, 2, st, 0); }
@@ -1957,7 +1957,7 @@ struct Engine {
             if (rs.used) HIPCHK(hipStreamWaitEvent(st_side, rs.consumed, 0));
             PcState S1 = S; S1.nhat_raw = raw_buf[x % raw_depth];
             hipEvent_t es = kt.begin_on(KT_SIDE, st_side);
-            (void)pc_launch_nhats_part(&S1, x, B, 1, st_side, (cfg.ablate & PC_ABL_BASES_PACKED) ? 1 : 0);
+            (void)pc_launch_nhats_part(&S1, x, B, 1, st_side, pc_part1_kind((cfg.ablate & PC_ABL_BASES_PACKED) != 0, cfg.ablate));
             kt.end_on(KT_SIDE, es, st_side);
             HIPCHK(hipEventRecord(rs.ready, st_side));
             rs.valid = true; rs.batch = x; rs.B = B; rs.waited = false;
@@ -2508,7 +2508,7 @@ int pchip_directions(const pchip_settings *s, const pchip_like *like, const pchi
             HIPCHK(hipMemcpy(S.chol, chol, sizeof(double) * D * D, hipMemcpyHostToDevice));
             S.seed_override = 1;
             if (path == 0) rc = pc_launch_nhats(&S, batch, nchains, E.st) ? PCHIP_NO_SUCH_PATH : 0;
-            else rc = (pc_launch_nhats_part(&S, batch, nchains, 1, E.st, path == 2 ? 1 : 0) || pc_launch_nhats_part(&S, batch, nchains, 2, E.st, 0)) ? PCHIP_NO_SUCH_PATH : 0;
+            else rc = (pc_launch_nhats_part(&S, batch, nchains, 1, E.st, pc_part1_kind(path == 2, c.ablate)) || pc_launch_nhats_part(&S, batch, nchains, 2, E.st, 0)) ? PCHIP_NO_SUCH_PATH : 0;
             HIPCHK(hipStreamSynchronize(E.st));
             HIPCHK(hipGetLastError());
         }
@@ -2536,6 +2536,46 @@ int pchip_directions(const pchip_settings *s, const pchip_like *like, const pchi
                         out[(size_t)v * D + d] = in[at];
                     }
             }
+        }
+    } catch (const EngineError &e) {
+        std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str());
+        (void)hipGetLastError();
+        rc = e.code;
+    }
+    E.destroy();
+    return rc;
+}
+
+// kernel-level entry beside pchip_directions (tests/test_bases_wave.py): the deck records part 1 of the split launch leaves behind the bases of
+// a nursery (pc_deck_record, pc_sample.hip), 66 ints a chain exactly as they lie there.  Set up as pchip_directions; part 1 only, by the kernel
+// a run on its own takes (settings.ablate bit 19: k_nhats<.., 64, 1>).  The caller's array goes into the block first: what comes back where
+// the kernel writes no record (num_repeats > 64) is what the caller put there.
+int pchip_deck_records(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, unsigned batch, int nchains, int *records_out)
+{
+    if (!s || !like || !prior || nchains < 1 || !records_out) {
+        pc_abi_set_last_error("pchip_deck_records: settings, likelihood, prior, nchains >= 1 and an array of 66 ints a chain");
+        return 1;
+    }
+    if (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & PC_ABL_RTC_BUILTINS)) {
+        pc_abi_set_last_error("pchip_deck_records does not take a device source likelihood (or settings.ablate bit 15)");
+        return 1;
+    }
+    if (s->nDims > 24) return PCHIP_NO_SUCH_PATH;      // (no records behind the bases of the larger kernels)
+    pchip_settings c = *s;
+    c.nlive = nchains; c.nprior = nchains; c.batch = nchains; c.do_clustering = 0;
+    Engine E;
+    int rc = 0;
+    try {
+        E.setup(c, *like, *prior);
+        PcState &S = E.S;
+        if (!pc_nhats_splittable(&S) || S.ngrade > 1) rc = PCHIP_NO_SUCH_PATH;
+        else {
+            int *rec = (int *)(S.nhat_raw + (size_t)S.B * S.nb_total * S.D * S.D);      // pc_deck_record(S, 0)
+            HIPCHK(hipMemcpy(rec, records_out, sizeof(int) * (size_t)nchains * 66, hipMemcpyHostToDevice));
+            rc = pc_launch_nhats_part(&S, batch, nchains, 1, E.st, pc_part1_kind(false, c.ablate)) ? PCHIP_NO_SUCH_PATH : 0;
+            HIPCHK(hipStreamSynchronize(E.st));
+            HIPCHK(hipGetLastError());
+            if (rc == 0) HIPCHK(hipMemcpy(records_out, rec, sizeof(int) * (size_t)nchains * 66, hipMemcpyDeviceToHost));
         }
     } catch (const EngineError &e) {
         std::fprintf(stderr, "polychord_hip: %s\n", e.msg.c_str());

@@ -180,6 +180,12 @@ int pc_rtc_wanted(const PcState *S);
 int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL, hipStream_t st);
 // the split launch (see k_nhats): part 1 = bases, part 2 = seeds + whitening; 1 where it exists (else only the whole kernel: pc_launch_nhats)
 int pc_nhats_splittable(const PcState *S);
+// packed (part 1, nDims <= 24; where its kernel does not take the state, k_nhats<.., 1>): which kernel draws the bases -- the same bits from each
+enum { PC_PART1_BASIS = 0,      // k_nhats<.., 64, 1>: a wavefront a basis (graded runs; settings.ablate bit 19)
+       PC_PART1_PACKED = 1,     // k_deviates_t + k_bases_packed of pc_slice_t.hip (runs in step; settings.ablate bit 7), no deck records
+       PC_PART1_WAVE = 2 };     // k_nhats_w: 64 / nDims bases a wavefront, one launch, deck records (a run on its own, one grade)
+// (the one place that says which: `packed` is pc_plan.h's decision for the nursery, or bit 7 on the side stream)
+static inline int pc_part1_kind(bool packed, int ablate) { return packed ? PC_PART1_PACKED : ((ablate & PC_ABL_BASES_WAVE) ? PC_PART1_BASIS : PC_PART1_WAVE); }
 int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchains, int part, hipStream_t st, int packed);
 int pc_launch_nhats(const PcState *S, unsigned batch, int nchains, hipStream_t st);
 // 1: k_slice can do seeds + whitening itself (pc_launch_slice_fused; pc_launch_slice_many with fused = 1)

@@ -1380,6 +1380,87 @@ __global__ __launch_bounds__(NT) void k_nhats(PcState S, unsigned batch)
 }
 
 // ------------------------------------------------------------------------------------------
+// Part 1 of the split launch for nDims <= 24, one grade, keyed draws, with 64 / nDims bases a wavefront: k_nhats<DMAX, 64, 1> keeps nDims of
+// its 64 lanes busy through nDims Gram-Schmidt steps (a barrier, an LDS pass, two dot products, a division or a square root each) -- here
+// thread = (basis sub, vector i), the same steps for per = 64 / nDims bases at once (PC_GS_PACKED, pc_dev.h: one text with k_bases_packed of
+// pc_slice_t.hip).  Bases are numbered flat, g = blockIdx.x * per + sub = chain * nb_total + basis in the chain: nhat_raw is linear in g, and
+// a wavefront may hold the end of one chain and the start of the next.  Lanes past per * nDims and bases past the last do nothing but the barriers.
+//   The deviates: the wavefront's per * ceil(nDims^2 / 2) stream calls (PC_DOM_NHAT, stream (batch, chain): element e of a basis is
+// pc_inv_normal_cdf of the uniform k_nhats takes) dealt to 64 lanes, into LDS vector-major as k_nhats lays them down.  (By instruction count:
+// a thread making its own vector's elements needs ceil(nDims / 2) calls or one more and leaves the lanes past per * nDims idle -- equal at
+// nDims 10 and 20, 9 - 10 against 7 rounds at nDims 17, 12 against 9 at 24.)  AS241 as k_deviates_t does it: the central branch in line,
+// the tail arguments left in place in LDS with their positions queued (ballot + prefix count) and finished together.
+//   The decks: every chain whose first basis lies in this wavefront gets its record [tag, deck] behind the bases, as k_nhats<.., 1> leaves it.
+//   LDS (pc_nhats_w_lds): per * nDims^2 doubles of deviates, per * 2 * DMAX of pivots, per * nDims^2 ints of queue.
+// ------------------------------------------------------------------------------------------
+template <int DMAX>
+__global__ __launch_bounds__(64) void k_nhats_w(PcState S, unsigned batch, int nbases)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int D = S.D, DD = D * D, nb = S.nb_total, nr = S.nr, per = 64 / D, NC = (DD + 1) / 2;
+    const int tid = threadIdx.x, sub = tid / D, i = tid - sub * D;
+    const int g0 = blockIdx.x * per, g = g0 + sub;
+    const int nbw = nbases - g0 < per ? nbases - g0 : per;                      // bases of this wavefront
+    const bool active = sub < per && g < nbases;
+    double *G = (double *)smem;                                                 // [per][D * D] deviates, vector-major
+    double *Qw = G + (size_t)per * DD;                                          // [per][2][DMAX] pivots
+    int *qA = (int *)(Qw + (size_t)per * 2 * DMAX);                             // [per * D * D] positions in G that hold a tail argument
+    // drawn ahead with the bases: the decks (k_slice's dependent swaps, off its wavefront); all 64 lanes, whichever basis they work on
+    if (nr <= 64) {
+        for (int s = 0; s < nbw; ++s) {
+            const int chain = (g0 + s) / nb;
+            if (g0 + s != chain * nb) continue;
+            const int dk = pc_deck_keyed(S, batch, chain, tid, nr);
+            int *rec = pc_deck_record(S, chain);
+            rec[2 + tid] = dk;
+            const unsigned long long tg = pc_deck_tag(S, batch, chain, nr);
+            if (tid == 0) { rec[0] = (int)(unsigned)tg; rec[1] = (int)(unsigned)(tg >> 32); }
+        }
+    }
+    // gaussian deviates (random_utils.F90:251-263): running index of stream (batch, chain) in PC_DOM_NHAT, basis after basis, vector after vector
+    int qn = 0;                                                                 // (wave-uniform) tail arguments queued so far
+    auto put = [&](bool want, double u, int dst) {
+        bool t = false;
+        double x = 0.0;
+        if (want) x = pc_inv_normal_central(u, t);
+        if (want) G[dst] = t ? u : x;
+        const unsigned long long m = __ballot(want && t);
+        if (want && t) qA[qn + __popcll(m & ((1ull << tid) - 1ull))] = dst;
+        qn += __popcll(m);
+    };
+    for (int t0 = 0; t0 < nbw * NC; t0 += 64) {
+        const int t = t0 + tid;
+        const bool in = t < nbw * NC;
+        const int s = in ? t / NC : 0, m = in ? t - s * NC : 0;
+        const int chain = (g0 + s) / nb, basis = (g0 + s) - chain * nb;
+        const uint32_t e0 = (uint32_t)pc_sel(S.g_e0, 0) + (uint32_t)basis * DD, e1 = e0 + (uint32_t)DD;
+        const uint32_t call = (e0 >> 1) + (uint32_t)m;
+        double ua = 0.5, ub = 0.5;
+        if (in) pc_uniform2(S.k0, S.k1, PC_DOM_NHAT, batch, (uint32_t)chain, call, ua, ub);
+        const uint32_t ia = 2 * call, ib = ia + 1;
+        put(in && ia >= e0 && ia < e1, ua, s * DD + (int)(ia - e0));
+        put(in && ib >= e0 && ib < e1, ub, s * DD + (int)(ib - e0));
+    }
+    __syncthreads();
+    for (int k = tid; k < qn; k += 64) { const int at = qA[k]; G[at] = pc_inv_normal_tail(G[at]); }
+    __syncthreads();
+    double v[DMAX];
+    const double *mine = G + (size_t)(active ? sub : 0) * DD + (size_t)i * D;
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) v[d] = (active && d < D) ? mine[d] : 0.0;
+    double *Q = Qw + (size_t)(sub < per ? sub : 0) * 2 * DMAX;
+    {
+#pragma clang fp contract(off)
+        PC_GS_PACKED(DMAX, v, Q, D, i, active)
+    }
+    if (active) {
+        double *raw = S.nhat_raw + ((size_t)g * D + i) * D;                     // [chain][basis][vector][D], linear in the basis number
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) if (d < D) raw[d] = v[d];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // K0 for 128 < nDims <= 256: a basis no longer fits in a CU's LDS (256 x 256 fp64 = 512 KB).  One workgroup of 256 threads per
 // (chain, basis), thread i owns vector i; the basis lives in a global scratch block, coordinate-major (V[d][i]: the
 // threads of a wave touch consecutive addresses, the pivot column is a broadcast read served by the L1/L2).  Same
@@ -2350,6 +2431,9 @@ extern "C" int pc_nhats_splittable(const PcState *S)
 static size_t pc_nhats_q_lds(int HV) { return sizeof(double) * (size_t)(2 + HV) * 4 * (HV + 2); }
 // ... and of k_nhats_q<32>: basis + sixteen rows of L (two tile buffers up to nDims 112; beyond that one, with a barrier more per tile: 160 KB of LDS)
 static size_t pc_nhats_q32_lds(int D) { const int NR = ((D + 15) / 16) * 16; return sizeof(double) * (2 * 4 * 34 + (size_t)(NR + (NR <= 112 ? 32 : 16)) * 129); }
+// ... and of k_nhats_w<DMAX> (nDims <= 24): per = 64 / nDims bases a workgroup, each nDims^2 doubles of deviates, a double-buffered pivot of
+// DMAX doubles and nDims^2 ints of tail queue (every deviate may be a tail argument): at most 64 nDims (8 + 4) + 64 x 16 x 3 bytes = 21.5 KB
+static size_t pc_nhats_w_lds(int D, int DMAX) { return (size_t)(64 / D) * (sizeof(double) * ((size_t)D * D + 2 * DMAX) + sizeof(int) * (size_t)D * D); }
 extern "C" int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchains, int part, hipStream_t st, int packed)
 {
     if (!pc_nhats_splittable(S)) return 1;
@@ -2383,8 +2467,17 @@ extern "C" int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchain
         return 0;
     }
     const size_t sh = sizeof(double) * ((size_t)(D + 8) * (D + 8) + 2 * 128) + 16;
-    // several runs on the device (packed != 0): the same bases, lane = basis (pc_slice_t.hip)
-    if (part == 1 && packed && pc_launch_bases_t(S, batch, nchains, st) == 0) return 0;
+    // several runs on the device (packed == PC_PART1_PACKED): the same bases, lane = basis (pc_slice_t.hip)
+    if (part == 1 && packed == PC_PART1_PACKED && pc_launch_bases_t(S, batch, nchains, st) == 0) return 0;
+    // a run on its own (packed == PC_PART1_WAVE): one grade, keyed draws -- 64 / nDims bases a wavefront, in one launch, decks included
+    if (part == 1 && packed == PC_PART1_WAVE && S->ngrade <= 1) {
+        const int nbases = nchains * S->nb_total, per = 64 / D;
+        const dim3 gw((nbases + per - 1) / per);
+        if (D <= 8) hipLaunchKernelGGL((k_nhats_w<8>), gw, dim3(64), pc_nhats_w_lds(D, 8), st, *S, batch, nbases);
+        else if (D <= 16) hipLaunchKernelGGL((k_nhats_w<16>), gw, dim3(64), pc_nhats_w_lds(D, 16), st, *S, batch, nbases);
+        else hipLaunchKernelGGL((k_nhats_w<24>), gw, dim3(64), pc_nhats_w_lds(D, 24), st, *S, batch, nbases);
+        return 0;
+    }
     if (part == 1) {
         if (D <= 8) hipLaunchKernelGGL((k_nhats<8, 64, 1>), grid, dim3(64), sh, st, *S, batch);
         else if (D <= 16) hipLaunchKernelGGL((k_nhats<16, 64, 1>), grid, dim3(64), sh, st, *S, batch);

@@ -534,35 +534,8 @@ namespace {
 // sums (and the way the compiler fuses `0 + a0 a0 + a4 a4` there), the projection as one fused multiply-add per coordinate.
 // (Tried and dropped: a basis per lane in LDS -- 3.2 KB a basis, a CU holds fifty: the runs queue for LDS.)
 // ------------------------------------------------------------------------------------------
-// a.a as k_nhats' PC_DOT4(x, a, a) comes out of the compiler: four partial sums over coordinates d = k, k + 4, ...; each starts as
-// 0 + a_k a_k + a_{k+4} a_{k+4}, of which ONE product is rounded and the other fused into the addition -- which one is the
-// compiler's choice per site (read from the ISA of libpolychord_hip.so: the pivot's q.q fuses a_k everywhere; the norm of a raw
-// vector fuses a_4, not a_0, in the kernels compiled for nDims <= 16).  tests/test_gpu_parity.py holds the two kernels together.
-template <int D, bool FIRST_RIGHT>
-__device__ __forceinline__ double dot4_same(const double (&a)[D])
-{
-#pragma clang fp contract(off)
-    double pp[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k >= D) pp[k] = 0.0;
-        else if (k + 4 >= D) pp[k] = fma(a[k], a[k], 0.0);
-        else if (FIRST_RIGHT && k == 0) pp[k] = fma(a[k + 4 < D ? k + 4 : 0], a[k + 4 < D ? k + 4 : 0], a[k] * a[k]);
-        else pp[k] = fma(a[k], a[k], a[k + 4 < D ? k + 4 : 0] * a[k + 4 < D ? k + 4 : 0]);
-    }
-#pragma unroll
-    for (int d = 8; d < D; ++d) pp[d & 3] = fma(a[d], a[d], pp[d & 3]);
-    return (pp[0] + pp[1]) + (pp[2] + pp[3]);
-}
-template <int D>
-__device__ __forceinline__ double dot4(const double (&a)[D], const double (&b)[D])
-{
-#pragma clang fp contract(off)
-    double pp[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int d = 0; d < D; ++d) pp[d & 3] = fma(a[d], b[d], pp[d & 3]);
-    return (pp[0] + pp[1]) + (pp[2] + pp[3]);
-}
+// (the normalisation and the Gram-Schmidt step, dot4_same / dot4 and the fusing rules they restate: PC_GS_PACKED of pc_dev.h, one text with
+//  k_nhats_w of pc_sample.hip)
 
 // step 2: thread = vector, as in k_nhats, but 64 / nDims bases to a wavefront (a basis keeps nDims of a wave's lanes busy) and
 // the deviates already made: every thread keeps its vector in registers, the pivot goes round through a few hundred bytes of
@@ -581,38 +554,7 @@ __device__ __forceinline__ void bases_packed_body(const PcState &S, int nbases)
     double *raw = S.nhat_raw + ((size_t)(active ? g : 0) * D + i) * D;          // [chain][basis][vector][D], linear in the basis number
 #pragma unroll
     for (int d = 0; d < DMAX; ++d) v[d] = (active && d < D) ? raw[d] : 0.0;
-    {   // random_direction (random_utils.F90:276-298)
-        const double inrm = 1.0 / sqrt(dot4_same<DMAX, (DMAX <= 16)>(v));
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) v[d] = v[d] * inrm;
-    }
-    if (i == 0 && active) {
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) Q[d] = v[d];
-    }
-    __syncthreads();
-    for (int j = 0; j < D; ++j) {                                               // Gram-Schmidt (random_utils.F90:391-399), k_nhats' steps
-        const double *q = Q + (size_t)(j & 1) * DMAX;
-        double qv[DMAX];
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) qv[d] = active ? q[d] : 0.0;
-        const double qq = dot4_same<DMAX, false>(qv), dv = dot4<DMAX>(qv, v);
-        if (i == j) {
-            const double inrm = 1.0 / sqrt(qq);
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) v[d] = v[d] * inrm;
-        } else if (active && i > j) {
-            const double cproj = dv / qq;
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) v[d] = fma(-cproj, qv[d], v[d]);
-            if (i == j + 1) {
-                double *qn = Q + (size_t)((j + 1) & 1) * DMAX;
-#pragma unroll
-                for (int d = 0; d < DMAX; ++d) qn[d] = v[d];
-            }
-        }
-        __syncthreads();
-    }
+    PC_GS_PACKED(DMAX, v, Q, D, i, active)
     if (active) {
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) if (d < D) raw[d] = v[d];
