@@ -1392,43 +1392,85 @@ __global__ __launch_bounds__(NT) void k_nhats(PcState S, unsigned batch)
 // the tail arguments left in place in LDS with their positions queued (ballot + prefix count) and finished together.
 //   The decks: every chain whose first basis lies in this wavefront gets its record [tag, deck] behind the bases, as k_nhats<.., 1> leaves it.
 //   LDS (pc_nhats_w_lds): per * nDims^2 doubles of deviates, per * 2 * DMAX of pivots, per * nDims^2 ints of queue.
+//   NW wavefronts a workgroup (4; 1 under settings.ablate bit 20, PC_ABL_BASES_WAVE1: the kernel as it was) for the same per bases, the same
+// numbering, carve and records.  What a launch lasts is wavefront 0's serial path, so the others take from it what any lane can do: all
+// 64 NW threads deal the stream calls (a deviate is a function of its stream position and lands in G[dst] whichever lane makes it; the queue
+// of tail arguments fills in any order through one LDS counter, each entry finished on its own), and the decks are made by wavefronts
+// 1 ... NW - 1 -- the s-th chain start of the workgroup by wavefront 1 + s % (NW - 1) -- behind the deviates, while wavefront 0 orthogonalises.
+// Wavefront 0 alone loads v[] and runs PC_GS_PACKED, statement for statement as with NW = 1; its stores (NW > 1) go through G, which lies as
+// the workgroup's stretch of nhat_raw lies, and leave 512 contiguous bytes an instruction: the counters have the stores' acknowledgement at a
+// third of a workgroup's time summed over a launch, and the step time follows them (profiles/bases_wave4.json).  The others END in front of the macro's
+// first barrier, as k_slice's helper wavefronts end ahead of their workgroup's later barriers (a barrier counts the wavefronts that still
+// run): going through nDims + 1 barriers with `active` false would keep three wavefronts and their registers on the CU for the whole of
+// Gram-Schmidt, which is what the launch is there to get off the chip before the next k_slice wants it whole.
+//   -DNHATS_W_DBG=1 | 2: clock64 at the section boundaries into PcCtl::dbg (1: workgroup 0, 2: summed over the workgroups) -- 0 decks (NW = 1:
+// wavefront 0; NW > 1: wavefront 1), wavefront 0's 1 deviates loop, 2 tail pass, 3 loading v[], 4 PC_GS_PACKED, 5 stores, 6 start to end;
+// 7 the workgroups counted.  With a PAR_NO_DBG build of pc_par.hip (the contraction's counters share the block): Makefile, basesdbg.
 // ------------------------------------------------------------------------------------------
-template <int DMAX>
-__global__ __launch_bounds__(64) void k_nhats_w(PcState S, unsigned batch, int nbases)
+template <int DMAX, int NW>
+__global__ __launch_bounds__(64 * NW) void k_nhats_w(PcState S, unsigned batch, int nbases)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int D = S.D, DD = D * D, nb = S.nb_total, nr = S.nr, per = 64 / D, NC = (DD + 1) / 2;
-    const int tid = threadIdx.x, sub = tid / D, i = tid - sub * D;
+    const int tid = threadIdx.x, lane = NW == 1 ? tid : (tid & 63), wv = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int sub = lane / D, i = lane - sub * D;                               // (wavefront 0's: thread = (basis, vector))
     const int g0 = blockIdx.x * per, g = g0 + sub;
-    const int nbw = nbases - g0 < per ? nbases - g0 : per;                      // bases of this wavefront
+    const int nbw = nbases - g0 < per ? nbases - g0 : per;                      // bases of this workgroup
     const bool active = sub < per && g < nbases;
     double *G = (double *)smem;                                                 // [per][D * D] deviates, vector-major
     double *Qw = G + (size_t)per * DD;                                          // [per][2][DMAX] pivots
     int *qA = (int *)(Qw + (size_t)per * 2 * DMAX);                             // [per * D * D] positions in G that hold a tail argument
+#ifdef NHATS_W_DBG
+    long long wcy[8];
+    wcy[0] = wcy[1] = clock64();
+#define NHATS_W_MARK(k) wcy[k] = clock64();
+#else
+#define NHATS_W_MARK(k)
+#endif
     // drawn ahead with the bases: the decks (k_slice's dependent swaps, off its wavefront); all 64 lanes, whichever basis they work on
-    if (nr <= 64) {
+    auto decks = [&]() {
+        if (nr > 64) return;
+        int ns = 0;                                                             // chain starts of the workgroup so far
         for (int s = 0; s < nbw; ++s) {
             const int chain = (g0 + s) / nb;
             if (g0 + s != chain * nb) continue;
-            const int dk = pc_deck_keyed(S, batch, chain, tid, nr);
-            int *rec = pc_deck_record(S, chain);
-            rec[2 + tid] = dk;
-            const unsigned long long tg = pc_deck_tag(S, batch, chain, nr);
-            if (tid == 0) { rec[0] = (int)(unsigned)tg; rec[1] = (int)(unsigned)(tg >> 32); }
+            if (NW == 1 || wv == 1 + ns % (NW > 1 ? NW - 1 : 1)) {
+                const int dk = pc_deck_keyed(S, batch, chain, lane, nr);
+                int *rec = pc_deck_record(S, chain);
+                rec[2 + lane] = dk;
+                const unsigned long long tg = pc_deck_tag(S, batch, chain, nr);
+                if (lane == 0) { rec[0] = (int)(unsigned)tg; rec[1] = (int)(unsigned)(tg >> 32); }
+            }
+            ++ns;
         }
-    }
+    };
+    if constexpr (NW == 1) { decks(); NHATS_W_MARK(1) }
     // gaussian deviates (random_utils.F90:251-263): running index of stream (batch, chain) in PC_DOM_NHAT, basis after basis, vector after vector
     int qn = 0;                                                                 // (wave-uniform) tail arguments queued so far
+    int *qcnt = nullptr;                                                        // NW > 1: ... by the whole workgroup
+    if constexpr (NW > 1) {
+        __shared__ int qcnt_s;
+        qcnt = &qcnt_s;
+        if (tid == 0) qcnt_s = 0;
+        __syncthreads();
+    }
     auto put = [&](bool want, double u, int dst) {
         bool t = false;
         double x = 0.0;
         if (want) x = pc_inv_normal_central(u, t);
         if (want) G[dst] = t ? u : x;
         const unsigned long long m = __ballot(want && t);
-        if (want && t) qA[qn + __popcll(m & ((1ull << tid) - 1ull))] = dst;
-        qn += __popcll(m);
+        if constexpr (NW == 1) {
+            if (want && t) qA[qn + __popcll(m & ((1ull << tid) - 1ull))] = dst;
+            qn += __popcll(m);
+        } else if (m) {                                                         // a segment of the queue for this wavefront's entries of this call
+            int at = 0;
+            if (lane == 0) at = atomicAdd(qcnt, __popcll(m));
+            at = __builtin_amdgcn_readfirstlane(at);
+            if (want && t) qA[at + __popcll(m & ((1ull << lane) - 1ull))] = dst;
+        }
     };
-    for (int t0 = 0; t0 < nbw * NC; t0 += 64) {
+    for (int t0 = 0; t0 < nbw * NC; t0 += 64 * NW) {
         const int t = t0 + tid;
         const bool in = t < nbw * NC;
         const int s = in ? t / NC : 0, m = in ? t - s * NC : 0;
@@ -1442,22 +1484,65 @@ __global__ __launch_bounds__(64) void k_nhats_w(PcState S, unsigned batch, int n
         put(in && ib >= e0 && ib < e1, ub, s * DD + (int)(ib - e0));
     }
     __syncthreads();
-    for (int k = tid; k < qn; k += 64) { const int at = qA[k]; G[at] = pc_inv_normal_tail(G[at]); }
+    NHATS_W_MARK(2)
+    if constexpr (NW > 1) qn = *qcnt;
+    for (int k = tid; k < qn; k += 64 * NW) { const int at = qA[k]; G[at] = pc_inv_normal_tail(G[at]); }
     __syncthreads();
+    NHATS_W_MARK(3)
+    if constexpr (NW > 1) {
+        if (wv != 0) {                                                          // the deviates are whole: the decks, and the end (head comment)
+            decks();
+#ifdef NHATS_W_DBG
+            if (wv == 1 && lane == 0 && (NHATS_W_DBG == 2 || blockIdx.x == 0)) atomicAdd((unsigned long long *)&S.ctl->dbg[0], (unsigned long long)(clock64() - wcy[3]));
+#endif
+            return;
+        }
+    }
     double v[DMAX];
     const double *mine = G + (size_t)(active ? sub : 0) * DD + (size_t)i * D;
 #pragma unroll
     for (int d = 0; d < DMAX; ++d) v[d] = (active && d < D) ? mine[d] : 0.0;
     double *Q = Qw + (size_t)(sub < per ? sub : 0) * 2 * DMAX;
+#ifdef NHATS_W_DBG
+    {   // (the loads must have come back where the section ends: a sum over v[] that the stamp waits for, kept alive through an empty asm)
+        double sv = 0.0;
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) sv += v[d];
+        asm volatile("" :: "v"(sv));
+    }
+#endif
+    NHATS_W_MARK(4)
     {
 #pragma clang fp contract(off)
         PC_GS_PACKED(DMAX, v, Q, D, i, active)
     }
-    if (active) {
+    NHATS_W_MARK(5)
+    if constexpr (NW > 1) {
+        // the bases leave as they lie in nhat_raw: G is free since v[] was loaded and [sub][i][d] IS the workgroup's stretch of nhat_raw, so the
+        // rows go back to it and out 512 contiguous bytes a store instruction, not nDims instructions of 64 rows' eight bytes each
+        double *row = G + (size_t)(active ? sub : 0) * DD + (size_t)i * D;
+        if (active) {
+#pragma unroll
+            for (int d = 0; d < DMAX; ++d) if (d < D) row[d] = v[d];
+        }
+        __syncthreads();
+        double *raw0 = S.nhat_raw + (size_t)g0 * DD;
+        for (int e = lane; e < nbw * DD; e += 64) raw0[e] = G[e];
+    } else if (active) {
         double *raw = S.nhat_raw + ((size_t)g * D + i) * D;                     // [chain][basis][vector][D], linear in the basis number
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) if (d < D) raw[d] = v[d];
     }
+#ifdef NHATS_W_DBG
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                            // (the stores acknowledged)
+    NHATS_W_MARK(6)
+    if (lane == 0 && (NHATS_W_DBG == 2 || blockIdx.x == 0)) {
+        for (int x = (NW == 1 ? 0 : 1); x < 6; ++x) atomicAdd((unsigned long long *)&S.ctl->dbg[x], (unsigned long long)(wcy[x + 1] - wcy[x]));
+        atomicAdd((unsigned long long *)&S.ctl->dbg[6], (unsigned long long)(wcy[6] - wcy[0]));
+        atomicAdd((unsigned long long *)&S.ctl->dbg[7], 1ull);
+    }
+#endif
+#undef NHATS_W_MARK
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2473,9 +2558,15 @@ extern "C" int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchain
     if (part == 1 && packed == PC_PART1_WAVE && S->ngrade <= 1) {
         const int nbases = nchains * S->nb_total, per = 64 / D;
         const dim3 gw((nbases + per - 1) / per);
-        if (D <= 8) hipLaunchKernelGGL((k_nhats_w<8>), gw, dim3(64), pc_nhats_w_lds(D, 8), st, *S, batch, nbases);
-        else if (D <= 16) hipLaunchKernelGGL((k_nhats_w<16>), gw, dim3(64), pc_nhats_w_lds(D, 16), st, *S, batch, nbases);
-        else hipLaunchKernelGGL((k_nhats_w<24>), gw, dim3(64), pc_nhats_w_lds(D, 24), st, *S, batch, nbases);
+        if (S->ablate & PC_ABL_BASES_WAVE1) {        // one wavefront a workgroup, as it was: the same bits
+            if (D <= 8) hipLaunchKernelGGL((k_nhats_w<8, 1>), gw, dim3(64), pc_nhats_w_lds(D, 8), st, *S, batch, nbases);
+            else if (D <= 16) hipLaunchKernelGGL((k_nhats_w<16, 1>), gw, dim3(64), pc_nhats_w_lds(D, 16), st, *S, batch, nbases);
+            else hipLaunchKernelGGL((k_nhats_w<24, 1>), gw, dim3(64), pc_nhats_w_lds(D, 24), st, *S, batch, nbases);
+            return 0;
+        }
+        if (D <= 8) hipLaunchKernelGGL((k_nhats_w<8, 4>), gw, dim3(256), pc_nhats_w_lds(D, 8), st, *S, batch, nbases);
+        else if (D <= 16) hipLaunchKernelGGL((k_nhats_w<16, 4>), gw, dim3(256), pc_nhats_w_lds(D, 16), st, *S, batch, nbases);
+        else hipLaunchKernelGGL((k_nhats_w<24, 4>), gw, dim3(256), pc_nhats_w_lds(D, 24), st, *S, batch, nbases);
         return 0;
     }
     if (part == 1) {

@@ -37,12 +37,13 @@ enum { PC_ERR_NONE = 0, PC_ERR_PHANTOM_CAP = 1, PC_ERR_DEAD_CAP = 2, PC_ERR_CLUS
 //                                   after chunk on one wavefront, not as one dominance count a step
 //   19   PC_ABL_BASES_WAVE          a run on its own, nDims <= 24, one grade: the bases a wavefront each     pc_engine.hip
 //                                   (k_nhats<.., 64, 1>), not 64 / nDims a wavefront (k_nhats_w)
+//   20   PC_ABL_BASES_WAVE1         ... k_nhats_w with one wavefront a workgroup (k_nhats_w<.., 1>), not four  pc_sample.hip
 //   30   PC_ABL_TRACE_CHOL          trace of Cholesky fallbacks                                              pc_contract.hip
 enum { PC_ABL_FUNCTOR = 1 << 0, PC_ABL_NO_POOL = 1 << 1, PC_ABL_NO_DEFER = 1 << 2, PC_ABL_NO_FUSED_UPDATE = 1 << 3, PC_ABL_PAIR_SCANS = 1 << 4,
        PC_ABL_CONSUME_GENERAL = 1 << 5, PC_ABL_SLICE_LANE = 1 << 6, PC_ABL_BASES_PACKED = 1 << 7, PC_ABL_CL_END_AT_DEATH = 1 << 8,
        PC_ABL_KILLOFF_GENERAL = 1 << 9, PC_ABL_CONSUME_CL_SERIAL = 1 << 10, PC_ABL_RETIRED_11 = 1 << 11, PC_ABL_RETIRED_12 = 1 << 12,
        PC_ABL_NO_HELPER = 1 << 13, PC_ABL_QC_BY_CHAIN = 1 << 14, PC_ABL_RTC_BUILTINS = 1 << 15, PC_ABL_UPDATE_CHAIN = 1 << 16, PC_ABL_FLAG_LAUNCH = 1 << 17,
-       PC_ABL_ACCEPT_SERIAL = 1 << 18, PC_ABL_BASES_WAVE = 1 << 19, PC_ABL_TRACE_CHOL = 1 << 30 };
+       PC_ABL_ACCEPT_SERIAL = 1 << 18, PC_ABL_BASES_WAVE = 1 << 19, PC_ABL_BASES_WAVE1 = 1 << 20, PC_ABL_TRACE_CHOL = 1 << 30 };
 
 #define PC_MASK_WORDS 16         /* phantom mask words per chain: num_repeats <= 1024 */
 
