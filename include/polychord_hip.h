@@ -234,7 +234,7 @@ typedef struct {
                            contraction's acceptance as the serial recurrence, sixty-four steps at a time on one wavefront, instead of one dominance
                            count a step for all steps at once (pc_par.hip): the same bits; bit 19 = a run on its own, nDims <= 24, one grade:
                            the orthonormal bases by the kernel with a wavefront a basis (k_nhats) instead of 64 / nDims bases a wavefront
-                           (k_nhats_w, pc_sample.hip): the same bits; bit 20 = ... k_nhats_w with one wavefront a workgroup instead of four
+                           (k_nhats_w, pc_bases.hip): the same bits; bit 20 = ... k_nhats_w with one wavefront a workgroup instead of four
                            (three more that share the deviates and make the decks): the same bits */
     const char *resume_write;  /* path of a .resume file (reference grammar, read_write.F90:219-288) rewritten at every
                                   update and at the end; NULL = off */

@@ -159,8 +159,8 @@ __device__ inline double pc_inv_normal_tail(double p)
 }
 
 // ---------------------------------------------------------------- Gram-Schmidt, thread = vector, 64 / nDims bases a wavefront
-// The normalisation and Gram-Schmidt of k_nhats<DMAX, 64, 1> (pc_sample.hip) for the kernels that pack several bases into a wavefront --
-// k_bases_packed (pc_slice_t.hip: deviates already in HBM) and k_nhats_w (pc_sample.hip: deviates made in place) -- ONE text, PC_GS_PACKED: k_nhats'
+// The normalisation and Gram-Schmidt of k_nhats<DMAX, 64, 1> (pc_bases.hip) for the kernels that pack several bases into a wavefront --
+// k_bases_packed (pc_slice_t.hip: deviates already in HBM) and k_nhats_w (pc_bases.hip: deviates made in place) -- ONE text, PC_GS_PACKED: k_nhats'
 // arithmetic operation for operation, dot products on four partial sums (and the way the compiler fuses `0 + a0 a0 + a4 a4` there), the
 // projection as one fused multiply-add per coordinate.
 // a.a as k_nhats' PC_DOT4(x, a, a) comes out of the compiler: four partial sums over coordinates d = k, k + 4, ...; each starts as

@@ -682,7 +682,7 @@ struct Engine {
         const bool split_q = D > 64 && D <= 128 && S.ngrade <= 1 && !S.seq_mode && !split_off && !callback_mode;
         // 24 < nDims <= 64, one grade (round 5): k_nhats_q<8 / 16, 1> leaves a basis thread by thread, 16 HV^2 doubles
         const bool split_m = D > 24 && D <= 64 && S.ngrade <= 1 && !S.seq_mode && !split_off && !callback_mode;
-        const size_t raw_n = split_q ? (size_t)B * S.nb_total * 32 * 512 : split_m ? (size_t)B * S.nb_total * (D <= 32 ? 1024 : 4096) : (size_t)B * S.nb_total * D * D + (size_t)B * 33 + 8;      // (+ the chains' deck records, 66 ints each: pc_deck_record, pc_sample.hip)
+        const size_t raw_n = split_q ? (size_t)B * S.nb_total * 32 * 512 : split_m ? (size_t)B * S.nb_total * (D <= 32 ? 1024 : 4096) : (size_t)B * S.nb_total * D * D + (size_t)B * 33 + 8;      // (+ the chains' deck records, 66 ints each: pc_deck_record, pc_seed.h)
         S.nhat_raw = ((D <= 24 && !S.seq_mode && !split_off) || split_q || split_m) ? blocks.dev<double>(raw_n)
                    : (D > 128 ? blocks.dev<double>((size_t)B * S.nb_total * D * 256) : nullptr);   // k_nhats_big keeps its bases there
         // split launch: two buffers, so that the bases of nursery b + 1 can be drawn at any time while nursery b's are read
@@ -2547,7 +2547,7 @@ int pchip_directions(const pchip_settings *s, const pchip_like *like, const pchi
 }
 
 // kernel-level entry beside pchip_directions (tests/test_bases_wave.py): the deck records part 1 of the split launch leaves behind the bases of
-// a nursery (pc_deck_record, pc_sample.hip), 66 ints a chain exactly as they lie there.  Set up as pchip_directions; part 1 only, by the kernel
+// a nursery (pc_deck_record, pc_seed.h), 66 ints a chain exactly as they lie there.  Set up as pchip_directions; part 1 only, by the kernel
 // a run on its own takes (settings.ablate bit 19: k_nhats<.., 64, 1>).  The caller's array goes into the block first: what comes back where
 // the kernel writes no record (num_repeats > 64) is what the caller put there.
 int pchip_deck_records(const pchip_settings *s, const pchip_like *like, const pchip_prior *prior, unsigned batch, int nchains, int *records_out)

@@ -173,11 +173,8 @@ const char *pc_rtc_error(void);
 // the form of handle `id` in *f (zeroed first): one lock, one lookup.  0, or non-zero for an id that never existed; a destroyed handle
 // answers what it answered alive, with alive = 0
 int pc_rtc_source_form(int id, PcSourceForm *f);
-// ---- pc_sample.hip -----------------------------------------------------------------------------------------
-// Launchers: 0: launched; 1: not this way (no kernel for this shape, or the run-time module failed: pc_rtc_error).
-// the sampling kernels come from the run-time module (a source likelihood, settings.ablate bit 15)
-int pc_rtc_wanted(const PcState *S);
-int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL, hipStream_t st);
+// ---- pc_bases.hip ------------------------------------------------------------------------------------------
+// The launchers of the direction kernels (static kernels only): 0: launched; 1: not this way (no kernel for this shape).
 // the split launch (see k_nhats): part 1 = bases, part 2 = seeds + whitening; 1 where it exists (else only the whole kernel: pc_launch_nhats)
 int pc_nhats_splittable(const PcState *S);
 // packed (part 1, nDims <= 24; where its kernel does not take the state, k_nhats<.., 1>): which kernel draws the bases -- the same bits from each
@@ -188,6 +185,13 @@ enum { PC_PART1_BASIS = 0,      // k_nhats<.., 64, 1>: a wavefront a basis (grad
 static inline int pc_part1_kind(bool packed, int ablate) { return packed ? PC_PART1_PACKED : ((ablate & PC_ABL_BASES_WAVE) ? PC_PART1_BASIS : PC_PART1_WAVE); }
 int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchains, int part, hipStream_t st, int packed);
 int pc_launch_nhats(const PcState *S, unsigned batch, int nchains, hipStream_t st);
+// ... and for R runs of a device in step (grid.z = run) the shapes that do not split: 24 < nDims <= 64
+int pc_launch_nhats_many(const PcState *S, const PcManyRec *dR, int R, int nchains, hipStream_t st);
+// ---- pc_sample.hip -----------------------------------------------------------------------------------------
+// Launchers: 0: launched; 1: not this way (no kernel for this shape, or the run-time module failed: pc_rtc_error).
+// the sampling kernels come from the run-time module (a source likelihood, settings.ablate bit 15)
+int pc_rtc_wanted(const PcState *S);
+int pc_launch_generate_live(const PcState *S, int attempt0, int n, double *rows, double *rows_logL, hipStream_t st);
 // 1: k_slice can do seeds + whitening itself (pc_launch_slice_fused; pc_launch_slice_many with fused = 1)
 int pc_slice_fusable(const PcState *S);
 int pc_launch_slice_fused(const PcState *S, unsigned batch, int nchains, hipStream_t st);
@@ -197,8 +201,6 @@ int pc_launch_slice_many(const PcState *S, const PcManyRec *dR, int R, int nchai
 // as a template argument and the terms form's LDS (a table of its own behind pc_slice_launch).  1: no shared launch for this shape (nDims > 64
 // unfused, grades, the sequential stream, the correlated Gaussian): each run then launches its own k_slice
 int pc_launch_slice_step(const PcState *S, const PcManyRec *dR, int R, int nchains, int fused, hipStream_t st);
-// ... and their directions for the shapes that do not split: 24 < nDims <= 64
-int pc_launch_nhats_many(const PcState *S, const PcManyRec *dR, int R, int nchains, hipStream_t st);
 int pc_launch_slice(const PcState *S, unsigned batch, int nchains, hipStream_t st);
 // pchip_prior_transform: the device transform of the table in S->prior at n points (device pointers); the device batch callback's prior:
 // a table, or the uniform box (S->prior.kind 1, lo / hi or null) as k_generate_live forms it

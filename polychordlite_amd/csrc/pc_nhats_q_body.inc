@@ -1,4 +1,4 @@
-// pc_nhats_q_body.inc -- the body of k_nhats_q (pc_sample.hip), included by the one-run kernel and by k_nhats_q_many (several runs in
+// pc_nhats_q_body.inc -- the body of k_nhats_q (pc_bases.hip), included by the one-run kernel and by k_nhats_q_many (several runs in
 // step, blockIdx.z = run): the same statements on `S` and `batch`.  Not a header: no include guard.
     constexpr int DP = 4 * HV, NTQ = 16 * HV;
     // LDS rows are stored as four coordinate blocks of HV + 2 doubles: the four threads of a vector read their blocks

@@ -2,8 +2,9 @@
 //
 // A source (pchip_source_create) is a string that defines
 //     __device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
-// The library compiles it with hiprtc, together with the exact text of its own sampling kernels (pc_dev.h, pc_state.h, pc_sample.hip and
-// the bodies it includes, embedded when the library is built: pc_rtc_sources.inc), for the device a run is on.  The launchers of
+// The library compiles it with hiprtc, together with the exact text of its own sampling kernels (pc_dev.h, pc_state.h, pc_seed.h,
+// pc_sample.hip and pc_slice_body.inc, embedded when the library is built: pc_rtc_sources.inc), for the device a run is on -- the kernels
+// that evaluate the user's problem and nothing else: the direction kernels (pc_bases.hip) exist in the library alone.  The launchers of
 // pc_sample.hip choose a kernel variant and its launch shape as they do for the built-ins, and hand the variant's name to pc_rtc_launch,
 // which instantiates it (hiprtcAddNameExpression), loads the code object once per device and launches it with the same arguments and
 // the same dynamic LDS.

@@ -1,19 +1,20 @@
-// pc_sample.hip -- the parallel half of the engine: prior sampling of the initial live set,
-// random whitened directions (K0) and the batched slice-sampling chains (K1).
+// pc_sample.hip -- the kernels that evaluate the user's problem: the prior transform, the likelihood on a wave,
+// prior sampling of the initial live set, the maximiser and the batched slice-sampling chains (K1).
+// pc_rtc.hip compiles this very text a second time at run time (with pc_dev.h, pc_state.h, pc_seed.h and
+// pc_slice_body.inc) for a device-source handle; every launcher below goes through PC_LAUNCH.
 //
 // One nursery batch = B independent chains, all seeded from one snapshot of the live set:
 // exactly the reference's synchronous farm with nprocs-1 = B
 // (src/polychord/nested_sampling.F90:262-286), but the "workers" are wavefronts.
 //
-//   K0 k_nhats   one workgroup per (chain, basis); thread i owns basis vector i in registers.
-//                Restates generate_nhats (chordal_sampling.f90:94-145), random_orthonormal_basis
-//                (random_utils.F90:381-403, row-oriented but arithmetically identical Gram-Schmidt),
-//                GenerateSeed (generate.F90:19-55) and the whitening nhats = L.nhats
-//                (chordal_sampling.f90:73-82).
+//   K0           the chains' random whitened directions: pc_bases.hip, a translation unit of its own
+//                (nothing there depends on the user's problem); the seed choice and the deck that both
+//                sides need are pc_seed.h.
 //   K1 k_slice   one wavefront per chain; lane d owns cube coordinate d (+64k).  Restates
 //                SliceSampling / slice_sample (chordal_sampling.f90:7-92, 163-273) and
 //                calculate_point (calculate.f90:6-50); likelihood sums are DPP butterflies.
 #include "pc_state.h"
+#include "pc_seed.h"
 #ifndef __HIPCC_RTC__
 #include <cstdlib>
 #endif
@@ -1043,1112 +1044,6 @@ __global__ __launch_bounds__(64) void k_maximise(PcState S, const double *in, co
 }
 
 // ------------------------------------------------------------------------------------------
-// K0: seed choice + random orthonormal bases + whitening
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void select_seed(const PcState &S, unsigned batch, int chain, int &sel, int &slot)
-{   // GenerateSeed, generate.F90:42-53; random_integer_P random_utils.F90:548-576
-    const int nc = S.ctl->ncluster;
-    if (nc == 1) {       // one cluster: the volume-weighted draw (generate.F90:36-41) can only return it
-        sel = 0;
-        const double u2s = S.seq_mode ? pc_seq_uniform(S, S.ctl->seq + 1) : pc_uniform(S.k0, S.k1, PC_DOM_SEED, batch, (uint32_t)chain, 1u);
-        const int ns = S.cl_n[0];
-        int is = (int)ceil(u2s * ns);
-        is = is < 1 ? 1 : (is > ns ? ns : is);
-        slot = S.cl_list[is - 1];
-        if (S.seed_override) slot = chain;
-        return;
-    }
-    double m = S.logXp[0];
-    for (int c = 1; c < nc; ++c) m = fmax(m, S.logXp[c]);
-    double sum = 0.0;
-    for (int c = 0; c < nc; ++c) sum += exp(S.logXp[c] - m);
-    const double lse = m + log(sum);
-    double norm = 0.0;
-    for (int c = 0; c < nc; ++c) norm += exp(S.logXp[c] - lse);
-    const double u = S.seq_mode ? pc_seq_uniform(S, S.ctl->seq) : pc_uniform(S.k0, S.k1, PC_DOM_SEED, batch, (uint32_t)chain, 0u);
-    double cdf = 0.0;
-    sel = nc - 1;
-    for (int c = 0; c < nc; ++c) { cdf += exp(S.logXp[c] - lse) / norm; if (u < cdf) { sel = c; break; } }
-    const double u2 = S.seq_mode ? pc_seq_uniform(S, S.ctl->seq + 1) : pc_uniform(S.k0, S.k1, PC_DOM_SEED, batch, (uint32_t)chain, 1u);
-    const int n = S.cl_n[sel];
-    int idx = (int)ceil(u2 * n);
-    idx = idx < 1 ? 1 : (idx > n ? n : idx);
-    slot = S.cl_list[(size_t)sel * S.Ncap + idx - 1];
-    if (S.seed_override) slot = chain;
-}
-
-// The deck of a chain (chordal_sampling.f90:135-142, random_utils.F90:505-532: the first direction stays, the others are Fisher-Yates shuffled),
-// keyed draws, num_repeats <= 64: the value for position p lives in lane p.  A pure function of (keys, nursery, chain): k_slice makes it, or finds
-// it behind the bases where k_nhats<.., 1> left it on the side stream (round 6) under a tag of those four numbers -- a matching tag IS the right deck,
-// whatever older run wrote it.
-__device__ __forceinline__ int pc_deck_keyed(const PcState &S, unsigned batch, int chain, int lane, int nr)
-{
-    int dk = lane, jv = 0;
-    if (lane >= 1 && lane < nr) {
-        const double u = pc_uniform(S.k0, S.k1, PC_DOM_SHUFFLE, batch, (uint32_t)chain, (uint32_t)lane);
-        int j = (int)ceil(u * lane);
-        jv = j < 1 ? 1 : (j > lane ? lane : j);
-    }
-    for (int i = nr - 1; i >= 1; --i) {
-        const int j = __builtin_amdgcn_readlane(jv, i);
-        const int di = __builtin_amdgcn_readlane(dk, i), dj = __builtin_amdgcn_readlane(dk, j);
-        dk = (lane == i) ? dj : ((lane == j) ? di : dk);
-    }
-    return dk;
-}
-// (everything the deck is a function of; a record that carries this tag carries that deck, whichever run, shape or buffer layout wrote it)
-__device__ __forceinline__ unsigned long long pc_deck_tag(const PcState &S, unsigned batch, int chain, int nr)
-{
-    return ((((unsigned long long)S.k0 << 32) | (unsigned long long)S.k1) ^ ((unsigned long long)batch * 0x9E3779B97F4A7C15ull)
-            ^ ((unsigned long long)(unsigned)chain * 0xC2B2AE3D27D4EB4Full) ^ ((unsigned long long)(unsigned)nr << 56)) | 1ull;
-}
-// behind the bases of a nursery (nDims <= 24: the engine allocates the tail): one record of 66 ints a chain, [tag lo, tag hi, deck[64]]
-__device__ __forceinline__ int *pc_deck_record(const PcState &S, int chain) { return (int *)(S.nhat_raw + (size_t)S.B * S.nb_total * S.D * S.D) + (size_t)chain * 66; }
-
-// select_seed by a whole wavefront (several clusters): the same numbers -- every exponential and quotient has the operands of the loops above and
-// every sum their order -- with the clusters' volumes loaded and exponentiated a lane each and only the additions in sequence (v_readlane): one
-// thread's three loops of a dependent global load + exponential per cluster were ~30 k cycles in front of every chain at two dozen clusters.
-__device__ __forceinline__ void select_seed_wave(const PcState &S, unsigned batch, int chain, int lane, int &sel, int &slot)
-{
-    const int nc = S.ctl->ncluster;
-    if (nc == 1 || S.seq_mode) {
-        int a = 0, b = 0;
-        if (lane == 0) select_seed(S, batch, chain, a, b);
-        sel = __builtin_amdgcn_readfirstlane(a); slot = __builtin_amdgcn_readfirstlane(b);
-        return;
-    }
-    double m = -PC_HUGE;
-    for (int c0 = 0; c0 < nc; c0 += 64) { const int c = c0 + lane; m = fmax(m, c < nc ? S.logXp[c] : -PC_HUGE); }
-    m = wave_max(m);
-    double sum = 0.0;
-    for (int c0 = 0; c0 < nc; c0 += 64) {
-        const int c = c0 + lane;
-        const double e = c < nc ? exp(S.logXp[c] - m) : 0.0;
-        const int n = nc - c0 < 64 ? nc - c0 : 64;
-        for (int q = 0; q < n; ++q) sum += readlane_f64(e, q);
-    }
-    const double lse = m + log(sum);
-    double norm = 0.0;
-    for (int c0 = 0; c0 < nc; c0 += 64) {
-        const int c = c0 + lane;
-        const double t = c < nc ? exp(S.logXp[c] - lse) : 0.0;
-        const int n = nc - c0 < 64 ? nc - c0 : 64;
-        for (int q = 0; q < n; ++q) norm += readlane_f64(t, q);
-    }
-    const double u = pc_uniform(S.k0, S.k1, PC_DOM_SEED, batch, (uint32_t)chain, 0u);
-    double cdf = 0.0;
-    sel = nc - 1;
-    bool found = false;
-    for (int c0 = 0; c0 < nc && !found; c0 += 64) {
-        const int c = c0 + lane;
-        const double r = c < nc ? exp(S.logXp[c] - lse) / norm : 0.0;
-        const int n = nc - c0 < 64 ? nc - c0 : 64;
-        for (int q = 0; q < n; ++q) { cdf += readlane_f64(r, q); if (u < cdf) { sel = c0 + q; found = true; break; } }
-    }
-    const double u2 = pc_uniform(S.k0, S.k1, PC_DOM_SEED, batch, (uint32_t)chain, 1u);
-    const int n = S.cl_n[sel];
-    int idx = (int)ceil(u2 * n);
-    idx = idx < 1 ? 1 : (idx > n ? n : idx);
-    slot = S.cl_list[(size_t)sel * S.Ncap + idx - 1];
-    if (S.seed_override) slot = chain;
-}
-
-// PART 0: the whole kernel.  PART 1 / 2: the two halves of a split launch -- the orthonormal bases depend on nothing
-// but the keys and the batch number (1: they go to S.nhat_raw, on a side stream while the previous nursery is being
-// consumed), seed selection and whitening need the live set and the covariance of the moment (2).
-template <int DMAX, int NT, int PART = 0>
-__global__ __launch_bounds__(NT) void k_nhats(PcState S, unsigned batch)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int D = S.D, nr = S.nr;
-    double *G = (double *)smem;          // [D*D] deviates, vector-major
-    double *Q = G + (size_t)(D + 8) * (D + 8);   // [2][DMAX] broadcast of the current vector (double buffered)
-    int *sh = (int *)(Q + 2 * DMAX);     // [2] chosen cluster, seed slot
-#ifdef NHATS_DBG
-    long long ncyc[8]; ncyc[0] = clock64();
-#endif
-    const int tid = threadIdx.x, chain = blockIdx.y;
-    // grade of this block and its basis within the grade (chordal_sampling.f90:119-130): the basis spans the
-    // parameters off..D-1, its vectors carry zeros in front; one grade: off = 0, Dg = D
-    int grade, basis;
-    pc_grade_of_basis(S, blockIdx.x, grade, basis);
-    const int off = pc_sel(S.g_off, grade), Dg = D - off, nrg = pc_sel(S.g_nr, grade), col0 = pc_sel(S.g_col0, grade);
-    if (PART != 1 && tid == 0) {
-        int sel, slot;
-        select_seed(S, batch, chain, sel, slot);
-        sh[0] = sel; sh[1] = slot;
-        if (blockIdx.x == 0) {
-            S.ch_cluster[chain] = sel; S.ch_seed_slot[chain] = slot;
-            S.ch_contour[chain] = S.logLp[sel];          // nested_sampling.F90:270
-            S.ch_epoch[chain] = S.ctl->admin_epoch;
-            if (chain == 0) { S.ctl->i_nursery = gridDim.y; S.ctl->batch_id = batch; }
-        }
-    }
-#ifdef NHATS_DBG
-    ncyc[1] = clock64();
-#endif
-    if constexpr (PART == 1 && NT == 64) {
-        // drawn ahead with the bases: the chain's deck (k_slice's 39 dependent swaps, off its wavefront)
-        if (blockIdx.x == 0 && S.D <= 24 && S.ngrade <= 1 && !S.seq_mode && nr <= 64) {
-            const int dk = pc_deck_keyed(S, batch, chain, tid, nr);
-            int *rec = pc_deck_record(S, chain);
-            rec[2 + tid] = dk;
-            const unsigned long long tg = pc_deck_tag(S, batch, chain, nr);
-            if (tid == 0) { rec[0] = (int)(unsigned)tg; rec[1] = (int)(unsigned)(tg >> 32); }
-        }
-    }
-    const int i = tid;
-    const bool active = i < Dg;
-    double v[DMAX];
-    double *raw = S.nhat_raw + (((size_t)chain * gridDim.x + blockIdx.x) * D + (i < D ? i : 0)) * D;   // [chain][basis][vector][D]
-    if constexpr (PART == 2) {
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) v[d] = (active && d < D) ? raw[d] : 0.0;
-        __syncthreads();
-    } else {
-    // gaussian deviates: running index of stream (batch, chain) in PC_DOM_NHAT, grade after grade, basis after basis,
-    // vector after vector (seq_mode: after the two seed draws: generate_nhats inside SliceSampling)
-    const uint32_t eoff = S.seq_mode ? (uint32_t)S.ctl->seq + 2u : 0u;
-    const uint32_t e0 = eoff + (uint32_t)pc_sel(S.g_e0, grade) + (uint32_t)basis * Dg * Dg, e1 = e0 + (uint32_t)Dg * Dg;
-    if (off > 0) {
-        for (int e = tid; e < Dg * D; e += NT) G[e] = 0.0;
-        __syncthreads();
-    }
-    for (uint32_t call = (e0 >> 1) + tid; call <= ((e1 - 1) >> 1); call += NT) {
-        double ua, ub;
-        if (S.seq_mode) pc_uniform2(S.k0, S.k1, PC_DOM_SEQ, 0u, 0u, call, ua, ub);
-        else pc_uniform2(S.k0, S.k1, PC_DOM_NHAT, batch, (uint32_t)chain, call, ua, ub);
-        const uint32_t ia = 2 * call, ib = 2 * call + 1;
-        // element x of the basis = coordinate off + x % Dg of vector x / Dg
-        if (ia >= e0 && ia < e1) { const uint32_t x = ia - e0; G[off == 0 ? x : (x / Dg) * D + off + x % Dg] = pc_inv_normal_cdf(ua); }
-        if (ib >= e0 && ib < e1) { const uint32_t x = ib - e0; G[off == 0 ? x : (x / Dg) * D + off + x % Dg] = pc_inv_normal_cdf(ub); }
-    }
-    __syncthreads();
-#ifdef NHATS_DBG
-    ncyc[2] = clock64();
-#endif
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) v[d] = (active && d < D) ? G[(size_t)i * D + d] : 0.0;
-    // dot products run on four partial sums (the summation order every other kernel of these bases reproduces)
-#define PC_DOT4(RES, A, B) { double p0_ = 0.0, p1_ = 0.0, p2_ = 0.0, p3_ = 0.0; \
-        _Pragma("unroll") for (int d = 0; d < DMAX; d += 4) { \
-            p0_ += (A)[d] * (B)[d]; p1_ += (A)[d + 1] * (B)[d + 1]; p2_ += (A)[d + 2] * (B)[d + 2]; p3_ += (A)[d + 3] * (B)[d + 3]; } \
-        RES = (p0_ + p1_) + (p2_ + p3_); }
-    // (register vectors are zero padded up to DMAX, LDS rows up to D + 8: no per-element bounds tests, which
-    //  cost a scalar compare-and-branch each)
-    // random_direction (random_utils.F90:276-298): normalise the raw deviates
-    {
-        double n2;
-        PC_DOT4(n2, v, v)
-        const double inrm = 1.0 / sqrt(n2);
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) v[d] = v[d] * inrm;
-    }
-#ifdef NHATS_DBG
-    ncyc[3] = clock64();
-#endif
-    // Gram-Schmidt, row oriented (the projections of random_utils.F90:391-399 in the same order): at step j
-    // the vector v_j -- already orthogonal to its predecessors, not yet normalised -- is broadcast
-    // through LDS; every later vector removes its component along it, (v.q / q.q) q, while thread j
-    // normalises.  One barrier per step; q.q is recomputed by everybody instead of being broadcast.
-    double *Qb = Q;                                   // [2][QS] double buffer
-    const int QS = DMAX;
-    if (i == 0) {
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) Qb[d] = v[d];
-    }
-    __syncthreads();
-#define PC_GS_STEP(QV) { \
-        double qq, dv; \
-        PC_DOT4(qq, QV, QV) \
-        PC_DOT4(dv, QV, v) \
-        if (i == j) { \
-            const double inrm = 1.0 / sqrt(qq); \
-            _Pragma("unroll") for (int d = 0; d < DMAX; ++d) v[d] = v[d] * inrm; \
-        } else if (active && i > j) { \
-            const double cproj = dv / qq; \
-            _Pragma("unroll") for (int d = 0; d < DMAX; ++d) v[d] = v[d] - cproj * (QV)[d]; \
-            if (i == j + 1) { \
-                double *qn = Qb + (size_t)((j + 1) & 1) * QS; \
-                _Pragma("unroll") for (int d = 0; d < DMAX; ++d) qn[d] = v[d]; \
-            } \
-        } }
-    for (int j = 0; j < Dg; ++j) {
-        const double *q = Qb + (size_t)(j & 1) * QS;
-        if constexpr (DMAX <= 32) {
-            double qv[DMAX];                          // registers: one LDS pass per step
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) qv[d] = q[d];
-            PC_GS_STEP(qv)
-        } else {
-            PC_GS_STEP(q)                             // large nDims: stream q from LDS, v alone fills the registers
-        }
-        __syncthreads();
-    }
-#undef PC_GS_STEP
-    if constexpr (PART == 1) {
-        if (active) {
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) if (d < D) raw[d] = v[d];
-        }
-        return;
-    }
-    }   // PART != 2
-#ifdef NHATS_DBG
-    ncyc[4] = clock64();
-#endif
-    // whitening  w = L.n  (chordal_sampling.f90:73)
-    const int col = col0 + basis * Dg + i;
-    const bool wanted = basis * Dg + i < nrg;         // the last basis of a grade is truncated
-    if constexpr (DMAX <= 32) {
-        // the deviate buffer is free: it receives the Cholesky factor, every thread multiplies its own
-        // vector from registers; the D row sums are independent chains (row a adds b = 0..a in order)
-        const double *Lg = S.chol + (size_t)sh[0] * D * D;
-        for (int e = tid; e < D * D; e += NT) G[e] = Lg[e];
-        __syncthreads();
-        if (active && wanted) {
-            double t[DMAX];
-#pragma unroll
-            for (int a = 0; a < DMAX; ++a) t[a] = 0.0;
-#pragma unroll
-            for (int b = 0; b < DMAX; ++b)
-#pragma unroll
-                for (int a = b; a < DMAX; ++a) t[a] += G[(size_t)a * D + b] * v[b];
-#pragma unroll
-            for (int a = 0; a < DMAX; ++a) if (a >= D) t[a] = 0.0;     // rows past D read padding
-            double n2;
-            PC_DOT4(n2, t, t)
-            const double w = sqrt(n2), iw = 1.0 / w;           // chordal_sampling.f90:80-82
-            double *out = S.nhat + ((size_t)chain * nr + col) * D;
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) if (d < D) out[d] = t[d] * iw;
-            S.nhat_w[(size_t)chain * nr + col] = w * 3.0;
-        }
-    } else {
-        // large nDims: the finished vectors go back to LDS (odd row stride: no bank conflicts when every thread
-        // walks its own row) and the Cholesky factor streams through a tile of rows in the padding of the buffer,
-        // loaded cooperatively -- the product used to read every L(a,b) from global memory inside a dependent loop
-        const int DS = D + 1, TR = 12;
-        double *Lt = G + (size_t)D * DS;             // [TR][D]
-        __syncthreads();
-        if (active) {
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) if (d < D) G[(size_t)i * DS + d] = v[d];
-        }
-        const double *Lc = S.chol + (size_t)sh[0] * D * D;
-        double *mine = G + (size_t)i * DS;
-        for (int a_hi = D - 1; a_hi >= 0; a_hi -= TR) {     // in place: row a only needs n[0..a], rows go downwards
-            const int a_lo = max(0, a_hi - TR + 1), nrow = a_hi - a_lo + 1;
-            __syncthreads();
-            for (int e = tid; e < nrow * D; e += NT) Lt[e] = Lc[(size_t)a_lo * D + e];
-            __syncthreads();
-            if (active && wanted) {
-                for (int a = a_hi; a >= a_lo; --a) {
-                    const double *Lr = Lt + (size_t)(a - a_lo) * D;
-                    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-                    int bb = 0;
-                    for (; bb + 3 <= a; bb += 4) {
-                        t0 += Lr[bb] * mine[bb]; t1 += Lr[bb + 1] * mine[bb + 1]; t2 += Lr[bb + 2] * mine[bb + 2]; t3 += Lr[bb + 3] * mine[bb + 3];
-                    }
-                    for (; bb <= a; ++bb) t0 += Lr[bb] * mine[bb];
-                    mine[a] = (t0 + t1) + (t2 + t3);
-                }
-            }
-        }
-        if (active && wanted) {
-            double n0 = 0.0, n1 = 0.0;
-            int d = 0;
-            for (; d + 1 < D; d += 2) { n0 += mine[d] * mine[d]; n1 += mine[d + 1] * mine[d + 1]; }
-            if (d < D) n0 += mine[d] * mine[d];
-            const double w = sqrt(n0 + n1);                   // chordal_sampling.f90:80-82
-            Q[i] = 1.0 / w;
-            S.nhat_w[(size_t)chain * nr + col] = w * 3.0;
-        }
-        __syncthreads();
-        // rows leave coalesced
-        for (int r = 0; r < Dg && basis * Dg + r < nrg; ++r) {
-            double *out = S.nhat + ((size_t)chain * nr + col0 + basis * Dg + r) * D;
-            const double iw = Q[r];
-            for (int d = tid; d < D; d += NT) out[d] = G[(size_t)r * DS + d] * iw;
-        }
-    }
-#ifdef NHATS_DBG
-    ncyc[5] = clock64();
-    if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) for (int x = 0; x < 5; ++x) S.ctl->dbg[x] += ncyc[x + 1] - ncyc[x];
-#endif
-#undef PC_DOT4
-}
-
-// ------------------------------------------------------------------------------------------
-// Part 1 of the split launch for nDims <= 24, one grade, keyed draws, with 64 / nDims bases a wavefront: k_nhats<DMAX, 64, 1> keeps nDims of
-// its 64 lanes busy through nDims Gram-Schmidt steps (a barrier, an LDS pass, two dot products, a division or a square root each) -- here
-// thread = (basis sub, vector i), the same steps for per = 64 / nDims bases at once (PC_GS_PACKED, pc_dev.h: one text with k_bases_packed of
-// pc_slice_t.hip).  Bases are numbered flat, g = blockIdx.x * per + sub = chain * nb_total + basis in the chain: nhat_raw is linear in g, and
-// a wavefront may hold the end of one chain and the start of the next.  Lanes past per * nDims and bases past the last do nothing but the barriers.
-//   The deviates: the wavefront's per * ceil(nDims^2 / 2) stream calls (PC_DOM_NHAT, stream (batch, chain): element e of a basis is
-// pc_inv_normal_cdf of the uniform k_nhats takes) dealt to 64 lanes, into LDS vector-major as k_nhats lays them down.  (By instruction count:
-// a thread making its own vector's elements needs ceil(nDims / 2) calls or one more and leaves the lanes past per * nDims idle -- equal at
-// nDims 10 and 20, 9 - 10 against 7 rounds at nDims 17, 12 against 9 at 24.)  AS241 as k_deviates_t does it: the central branch in line,
-// the tail arguments left in place in LDS with their positions queued (ballot + prefix count) and finished together.
-//   The decks: every chain whose first basis lies in this wavefront gets its record [tag, deck] behind the bases, as k_nhats<.., 1> leaves it.
-//   LDS (pc_nhats_w_lds): per * nDims^2 doubles of deviates, per * 2 * DMAX of pivots, per * nDims^2 ints of queue.
-//   NW wavefronts a workgroup (4; 1 under settings.ablate bit 20, PC_ABL_BASES_WAVE1: the kernel as it was) for the same per bases, the same
-// numbering, carve and records.  What a launch lasts is wavefront 0's serial path, so the others take from it what any lane can do: all
-// 64 NW threads deal the stream calls (a deviate is a function of its stream position and lands in G[dst] whichever lane makes it; the queue
-// of tail arguments fills in any order through one LDS counter, each entry finished on its own), and the decks are made by wavefronts
-// 1 ... NW - 1 -- the s-th chain start of the workgroup by wavefront 1 + s % (NW - 1) -- behind the deviates, while wavefront 0 orthogonalises.
-// Wavefront 0 alone loads v[] and runs PC_GS_PACKED, statement for statement as with NW = 1; its stores (NW > 1) go through G, which lies as
-// the workgroup's stretch of nhat_raw lies, and leave 512 contiguous bytes an instruction: the counters have the stores' acknowledgement at a
-// third of a workgroup's time summed over a launch, and the step time follows them (profiles/bases_wave4.json).  The others END in front of the macro's
-// first barrier, as k_slice's helper wavefronts end ahead of their workgroup's later barriers (a barrier counts the wavefronts that still
-// run): going through nDims + 1 barriers with `active` false would keep three wavefronts and their registers on the CU for the whole of
-// Gram-Schmidt, which is what the launch is there to get off the chip before the next k_slice wants it whole.
-//   -DNHATS_W_DBG=1 | 2: clock64 at the section boundaries into PcCtl::dbg (1: workgroup 0, 2: summed over the workgroups) -- 0 decks (NW = 1:
-// wavefront 0; NW > 1: wavefront 1), wavefront 0's 1 deviates loop, 2 tail pass, 3 loading v[], 4 PC_GS_PACKED, 5 stores, 6 start to end;
-// 7 the workgroups counted.  With a PAR_NO_DBG build of pc_par.hip (the contraction's counters share the block): Makefile, basesdbg.
-// ------------------------------------------------------------------------------------------
-template <int DMAX, int NW>
-__global__ __launch_bounds__(64 * NW) void k_nhats_w(PcState S, unsigned batch, int nbases)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int D = S.D, DD = D * D, nb = S.nb_total, nr = S.nr, per = 64 / D, NC = (DD + 1) / 2;
-    const int tid = threadIdx.x, lane = NW == 1 ? tid : (tid & 63), wv = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int sub = lane / D, i = lane - sub * D;                               // (wavefront 0's: thread = (basis, vector))
-    const int g0 = blockIdx.x * per, g = g0 + sub;
-    const int nbw = nbases - g0 < per ? nbases - g0 : per;                      // bases of this workgroup
-    const bool active = sub < per && g < nbases;
-    double *G = (double *)smem;                                                 // [per][D * D] deviates, vector-major
-    double *Qw = G + (size_t)per * DD;                                          // [per][2][DMAX] pivots
-    int *qA = (int *)(Qw + (size_t)per * 2 * DMAX);                             // [per * D * D] positions in G that hold a tail argument
-#ifdef NHATS_W_DBG
-    long long wcy[8];
-    wcy[0] = wcy[1] = clock64();
-#define NHATS_W_MARK(k) wcy[k] = clock64();
-#else
-#define NHATS_W_MARK(k)
-#endif
-    // drawn ahead with the bases: the decks (k_slice's dependent swaps, off its wavefront); all 64 lanes, whichever basis they work on
-    auto decks = [&]() {
-        if (nr > 64) return;
-        int ns = 0;                                                             // chain starts of the workgroup so far
-        for (int s = 0; s < nbw; ++s) {
-            const int chain = (g0 + s) / nb;
-            if (g0 + s != chain * nb) continue;
-            if (NW == 1 || wv == 1 + ns % (NW > 1 ? NW - 1 : 1)) {
-                const int dk = pc_deck_keyed(S, batch, chain, lane, nr);
-                int *rec = pc_deck_record(S, chain);
-                rec[2 + lane] = dk;
-                const unsigned long long tg = pc_deck_tag(S, batch, chain, nr);
-                if (lane == 0) { rec[0] = (int)(unsigned)tg; rec[1] = (int)(unsigned)(tg >> 32); }
-            }
-            ++ns;
-        }
-    };
-    if constexpr (NW == 1) { decks(); NHATS_W_MARK(1) }
-    // gaussian deviates (random_utils.F90:251-263): running index of stream (batch, chain) in PC_DOM_NHAT, basis after basis, vector after vector
-    int qn = 0;                                                                 // (wave-uniform) tail arguments queued so far
-    int *qcnt = nullptr;                                                        // NW > 1: ... by the whole workgroup
-    if constexpr (NW > 1) {
-        __shared__ int qcnt_s;
-        qcnt = &qcnt_s;
-        if (tid == 0) qcnt_s = 0;
-        __syncthreads();
-    }
-    auto put = [&](bool want, double u, int dst) {
-        bool t = false;
-        double x = 0.0;
-        if (want) x = pc_inv_normal_central(u, t);
-        if (want) G[dst] = t ? u : x;
-        const unsigned long long m = __ballot(want && t);
-        if constexpr (NW == 1) {
-            if (want && t) qA[qn + __popcll(m & ((1ull << tid) - 1ull))] = dst;
-            qn += __popcll(m);
-        } else if (m) {                                                         // a segment of the queue for this wavefront's entries of this call
-            int at = 0;
-            if (lane == 0) at = atomicAdd(qcnt, __popcll(m));
-            at = __builtin_amdgcn_readfirstlane(at);
-            if (want && t) qA[at + __popcll(m & ((1ull << lane) - 1ull))] = dst;
-        }
-    };
-    for (int t0 = 0; t0 < nbw * NC; t0 += 64 * NW) {
-        const int t = t0 + tid;
-        const bool in = t < nbw * NC;
-        const int s = in ? t / NC : 0, m = in ? t - s * NC : 0;
-        const int chain = (g0 + s) / nb, basis = (g0 + s) - chain * nb;
-        const uint32_t e0 = (uint32_t)pc_sel(S.g_e0, 0) + (uint32_t)basis * DD, e1 = e0 + (uint32_t)DD;
-        const uint32_t call = (e0 >> 1) + (uint32_t)m;
-        double ua = 0.5, ub = 0.5;
-        if (in) pc_uniform2(S.k0, S.k1, PC_DOM_NHAT, batch, (uint32_t)chain, call, ua, ub);
-        const uint32_t ia = 2 * call, ib = ia + 1;
-        put(in && ia >= e0 && ia < e1, ua, s * DD + (int)(ia - e0));
-        put(in && ib >= e0 && ib < e1, ub, s * DD + (int)(ib - e0));
-    }
-    __syncthreads();
-    NHATS_W_MARK(2)
-    if constexpr (NW > 1) qn = *qcnt;
-    for (int k = tid; k < qn; k += 64 * NW) { const int at = qA[k]; G[at] = pc_inv_normal_tail(G[at]); }
-    __syncthreads();
-    NHATS_W_MARK(3)
-    if constexpr (NW > 1) {
-        if (wv != 0) {                                                          // the deviates are whole: the decks, and the end (head comment)
-            decks();
-#ifdef NHATS_W_DBG
-            if (wv == 1 && lane == 0 && (NHATS_W_DBG == 2 || blockIdx.x == 0)) atomicAdd((unsigned long long *)&S.ctl->dbg[0], (unsigned long long)(clock64() - wcy[3]));
-#endif
-            return;
-        }
-    }
-    double v[DMAX];
-    const double *mine = G + (size_t)(active ? sub : 0) * DD + (size_t)i * D;
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) v[d] = (active && d < D) ? mine[d] : 0.0;
-    double *Q = Qw + (size_t)(sub < per ? sub : 0) * 2 * DMAX;
-#ifdef NHATS_W_DBG
-    {   // (the loads must have come back where the section ends: a sum over v[] that the stamp waits for, kept alive through an empty asm)
-        double sv = 0.0;
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) sv += v[d];
-        asm volatile("" :: "v"(sv));
-    }
-#endif
-    NHATS_W_MARK(4)
-    {
-#pragma clang fp contract(off)
-        PC_GS_PACKED(DMAX, v, Q, D, i, active)
-    }
-    NHATS_W_MARK(5)
-    if constexpr (NW > 1) {
-        // the bases leave as they lie in nhat_raw: G is free since v[] was loaded and [sub][i][d] IS the workgroup's stretch of nhat_raw, so the
-        // rows go back to it and out 512 contiguous bytes a store instruction, not nDims instructions of 64 rows' eight bytes each
-        double *row = G + (size_t)(active ? sub : 0) * DD + (size_t)i * D;
-        if (active) {
-#pragma unroll
-            for (int d = 0; d < DMAX; ++d) if (d < D) row[d] = v[d];
-        }
-        __syncthreads();
-        double *raw0 = S.nhat_raw + (size_t)g0 * DD;
-        for (int e = lane; e < nbw * DD; e += 64) raw0[e] = G[e];
-    } else if (active) {
-        double *raw = S.nhat_raw + ((size_t)g * D + i) * D;                     // [chain][basis][vector][D], linear in the basis number
-#pragma unroll
-        for (int d = 0; d < DMAX; ++d) if (d < D) raw[d] = v[d];
-    }
-#ifdef NHATS_W_DBG
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                            // (the stores acknowledged)
-    NHATS_W_MARK(6)
-    if (lane == 0 && (NHATS_W_DBG == 2 || blockIdx.x == 0)) {
-        for (int x = (NW == 1 ? 0 : 1); x < 6; ++x) atomicAdd((unsigned long long *)&S.ctl->dbg[x], (unsigned long long)(wcy[x + 1] - wcy[x]));
-        atomicAdd((unsigned long long *)&S.ctl->dbg[6], (unsigned long long)(wcy[6] - wcy[0]));
-        atomicAdd((unsigned long long *)&S.ctl->dbg[7], 1ull);
-    }
-#endif
-#undef NHATS_W_MARK
-}
-
-// ------------------------------------------------------------------------------------------
-// K0 for 128 < nDims <= 256: a basis no longer fits in a CU's LDS (256 x 256 fp64 = 512 KB).  One workgroup of 256 threads per
-// (chain, basis), thread i owns vector i; the basis lives in a global scratch block, coordinate-major (V[d][i]: the
-// threads of a wave touch consecutive addresses, the pivot column is a broadcast read served by the L1/L2).  Same
-// arithmetic as k_nhats: row-oriented Gram-Schmidt against the not yet normalised pivot, dot products on four partial
-// sums, whitening in place from the last row upwards.
-// ------------------------------------------------------------------------------------------
-#define PC_BIG_NT 256
-#define PC_BIG_P 16
-__global__ __launch_bounds__(PC_BIG_NT) void k_nhats_big(PcState S, unsigned batch)
-{
-    __shared__ int sh[2];
-    __shared__ double iwv[PC_BIG_NT];
-    __shared__ double Pq[PC_BIG_P * PC_BIG_NT];        // pivot panel, [pivot][coordinate]
-    __shared__ double pqq[PC_BIG_P];
-    const int D = S.D, nr = S.nr, tid = threadIdx.x, chain = blockIdx.y, i = tid;
-    int grade, basis;
-    pc_grade_of_basis(S, blockIdx.x, grade, basis);
-    const int off = pc_sel(S.g_off, grade), Dg = D - off, nrg = pc_sel(S.g_nr, grade), col0 = pc_sel(S.g_col0, grade);
-    if (tid == 0) {
-        int sel, slot;
-        select_seed(S, batch, chain, sel, slot);
-        sh[0] = sel; sh[1] = slot;
-        if (blockIdx.x == 0) {
-            S.ch_cluster[chain] = sel; S.ch_seed_slot[chain] = slot;
-            S.ch_contour[chain] = S.logLp[sel];          // nested_sampling.F90:270
-            S.ch_epoch[chain] = S.ctl->admin_epoch;
-            if (chain == 0) { S.ctl->i_nursery = gridDim.y; S.ctl->batch_id = batch; }
-        }
-    }
-    double *V = S.nhat_raw + ((size_t)chain * gridDim.x + blockIdx.x) * D * PC_BIG_NT;   // [D][256]
-    // vectors past the truncated end of a grade's last basis are never used and nothing depends on them
-    const int nvec = min(Dg, nrg - basis * Dg);
-    const bool active = i < nvec;
-    const uint32_t eoff = S.seq_mode ? (uint32_t)S.ctl->seq + 2u : 0u;
-    const uint32_t e0 = eoff + (uint32_t)pc_sel(S.g_e0, grade) + (uint32_t)basis * Dg * Dg, e1 = e0 + (uint32_t)Dg * Dg;
-    for (int e = tid; e < off * PC_BIG_NT; e += PC_BIG_NT) V[e] = 0.0;
-    for (uint32_t call = (e0 >> 1) + tid; call <= ((e1 - 1) >> 1); call += PC_BIG_NT) {
-        double ua, ub;
-        if (S.seq_mode) pc_uniform2(S.k0, S.k1, PC_DOM_SEQ, 0u, 0u, call, ua, ub);
-        else pc_uniform2(S.k0, S.k1, PC_DOM_NHAT, batch, (uint32_t)chain, call, ua, ub);
-        const uint32_t ia = 2 * call, ib = 2 * call + 1;
-        if (ia >= e0 && ia < e1) { const uint32_t x = ia - e0; V[(size_t)(off + x % Dg) * PC_BIG_NT + x / Dg] = pc_inv_normal_cdf(ua); }
-        if (ib >= e0 && ib < e1) { const uint32_t x = ib - e0; V[(size_t)(off + x % Dg) * PC_BIG_NT + x / Dg] = pc_inv_normal_cdf(ub); }
-    }
-    __syncthreads();
-    double *mine = V + i;
-    auto dot_own = [&](const double *q) {              // q . mine (q == mine: the squared norm), four partial sums
-        double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-        int d = off;
-        for (; d + 3 < D; d += 4) {
-            p0 += q[(size_t)d * PC_BIG_NT] * mine[(size_t)d * PC_BIG_NT]; p1 += q[(size_t)(d + 1) * PC_BIG_NT] * mine[(size_t)(d + 1) * PC_BIG_NT];
-            p2 += q[(size_t)(d + 2) * PC_BIG_NT] * mine[(size_t)(d + 2) * PC_BIG_NT]; p3 += q[(size_t)(d + 3) * PC_BIG_NT] * mine[(size_t)(d + 3) * PC_BIG_NT];
-        }
-        for (; d < D; ++d) p0 += q[(size_t)d * PC_BIG_NT] * mine[(size_t)d * PC_BIG_NT];
-        return (p0 + p1) + (p2 + p3);
-    };
-    auto norm2 = [&](const double *q) {                // q . q in the same four-way order
-        double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-        int d = off;
-        for (; d + 3 < D; d += 4) {
-            const double a = q[(size_t)d * PC_BIG_NT], b = q[(size_t)(d + 1) * PC_BIG_NT], c = q[(size_t)(d + 2) * PC_BIG_NT], e = q[(size_t)(d + 3) * PC_BIG_NT];
-            p0 += a * a; p1 += b * b; p2 += c * c; p3 += e * e;
-        }
-        for (; d < D; ++d) { const double a = q[(size_t)d * PC_BIG_NT]; p0 += a * a; }
-        return (p0 + p1) + (p2 + p3);
-    };
-    if (active) {                                      // random_direction (random_utils.F90:276-298)
-        const double inrm = 1.0 / sqrt(dot_own(mine));
-        for (int d = off; d < D; ++d) mine[(size_t)d * PC_BIG_NT] *= inrm;
-    }
-    __syncthreads();
-    // Gram-Schmidt (random_utils.F90:391-399) in panels of sixteen pivots.  A panel is staged in LDS and orthogonalised
-    // there (modified Gram-Schmidt, one wave per later vector of the panel, lanes over the coordinates); every vector
-    // behind the panel then takes its sixteen projections in one pass over its coordinates and removes them in a
-    // second: three global accesses per coordinate and panel instead of five per coordinate and pivot.  (Within a
-    // panel the pivots are mutually orthogonal, so projecting on all of them at once differs from one after the other
-    // by round-off only.)  Pivots stay unnormalised: (v.q / q.q) q; every owner normalises after the loop.
-    {
-        const int wv = tid >> 6, lane = tid & 63;
-        for (int j0 = 0; j0 < nvec; j0 += PC_BIG_P) {
-            const int np = min(PC_BIG_P, nvec - j0);
-            for (int e = tid; e < np * D; e += PC_BIG_NT) {           // vector index fastest: 128-B runs of the scratch
-                const int pp = e % np, d = e / np;
-                Pq[pp * PC_BIG_NT + d] = V[(size_t)d * PC_BIG_NT + j0 + pp];
-            }
-            for (int e = np * PC_BIG_NT + tid; e < PC_BIG_P * PC_BIG_NT; e += PC_BIG_NT) Pq[e] = 0.0;
-            __syncthreads();
-            for (int pp = 0; pp + 1 < np; ++pp) {
-                const double *qp = Pq + pp * PC_BIG_NT;
-                for (int q = pp + 1 + wv; q < np; q += 4) {
-                    double *vq = Pq + q * PC_BIG_NT;
-                    double dq = 0.0, dd = 0.0;
-                    for (int d = off + lane; d < D; d += 64) { const double a = qp[d], b2 = vq[d]; dq += a * b2; dd += a * a; }
-                    dq = wave_sum<4>(dq); dd = wave_sum<4>(dd);
-                    const double c = dq / dd;
-                    for (int d = off + lane; d < D; d += 64) vq[d] -= c * qp[d];
-                }
-                __syncthreads();
-            }
-            for (int pp = wv; pp < np; pp += 4) {
-                const double *qp = Pq + pp * PC_BIG_NT;
-                double dd = 0.0;
-                for (int d = off + lane; d < D; d += 64) dd += qp[d] * qp[d];
-                dd = wave_sum<4>(dd);
-                if (lane == 0) pqq[pp] = dd;
-            }
-            for (int e = tid; e < np * D; e += PC_BIG_NT) {
-                const int pp = e % np, d = e / np;
-                V[(size_t)d * PC_BIG_NT + j0 + pp] = Pq[pp * PC_BIG_NT + d];
-            }
-            __syncthreads();
-            if (active && i >= j0 + np) {
-                double c[PC_BIG_P];
-#pragma unroll
-                for (int pp = 0; pp < PC_BIG_P; ++pp) c[pp] = 0.0;
-                for (int d = off; d < D; ++d) {
-                    const double x = mine[(size_t)d * PC_BIG_NT];
-#pragma unroll
-                    for (int pp = 0; pp < PC_BIG_P; ++pp) c[pp] += x * Pq[pp * PC_BIG_NT + d];
-                }
-#pragma unroll
-                for (int pp = 0; pp < PC_BIG_P; ++pp) c[pp] = pp < np ? c[pp] / pqq[pp] : 0.0;
-                for (int d = off; d < D; ++d) {
-                    double x = mine[(size_t)d * PC_BIG_NT];
-#pragma unroll
-                    for (int pp = 0; pp < PC_BIG_P; ++pp) x -= c[pp] * Pq[pp * PC_BIG_NT + d];
-                    mine[(size_t)d * PC_BIG_NT] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (active) {
-        const double inrm = 1.0 / sqrt(dot_own(mine));
-        for (int d = off; d < D; ++d) mine[(size_t)d * PC_BIG_NT] *= inrm;
-    }
-    // whitening  w = L.n  (chordal_sampling.f90:73), in place, sixteen rows of L at a time from the last row upwards
-    // (row a only needs n[0..a]): the rows wait in LDS, a thread reads each of its coordinates once per tile and
-    // feeds sixteen independent sums in ascending column order (one row at a time re-read the vector nDims/2 times:
-    // 20 GB per launch at nDims = 200)
-    {
-        const double *Lc = S.chol + (size_t)sh[0] * D * D;
-        for (int a_hi = D - 1; a_hi >= 0; a_hi -= PC_BIG_P) {
-            const int a_lo = max(0, a_hi - PC_BIG_P + 1), nrow = a_hi - a_lo + 1;
-            __syncthreads();                              // the previous tile (or the last pivot panel) is no longer read
-            for (int e = tid; e < PC_BIG_P * PC_BIG_NT; e += PC_BIG_NT) {
-                const int r = e / PC_BIG_NT, b2 = e % PC_BIG_NT;
-                Pq[e] = (r < nrow && b2 <= a_hi) ? Lc[(size_t)(a_lo + r) * D + b2] : 0.0;
-            }
-            __syncthreads();
-            if (active) {
-                double acc[PC_BIG_P];
-#pragma unroll
-                for (int r = 0; r < PC_BIG_P; ++r) acc[r] = 0.0;
-                for (int b2 = 0; b2 <= a_hi; ++b2) {
-                    const double x = mine[(size_t)b2 * PC_BIG_NT];
-#pragma unroll
-                    for (int r = 0; r < PC_BIG_P; ++r) acc[r] += Pq[r * PC_BIG_NT + b2] * x;
-                }
-#pragma unroll
-                for (int r = 0; r < PC_BIG_P; ++r) if (r < nrow) mine[(size_t)(a_lo + r) * PC_BIG_NT] = acc[r];
-            }
-        }
-    }
-    if (active) {
-        // |t|^2 over up to 256 squares: a plain sum on two accumulators left the rows of unit norm to 4.2 u only (3 ... 4 u of it the sum's
-        // own rounding).  Compensated instead -- the product's error by FMA, the addition's by TwoSum (Ogita, Rump & Oishi, Dot2): the sum
-        // is exact to a rounding, what is left is the root, the reciprocal and the products (tests/test_directions.py holds 4 u)
-        double sn = 0.0, cn = 0.0;
-        for (int d = 0; d < D; ++d) {
-#pragma clang fp contract(off)
-            const double a = mine[(size_t)d * PC_BIG_NT];
-            const double p = a * a, pe = fma(a, a, -p);
-            const double t = sn + p, bp = t - sn;
-            cn += ((sn - (t - bp)) + (p - bp)) + pe;
-            sn = t;
-        }
-        const double w = sqrt(sn + cn);                   // chordal_sampling.f90:80-82
-        iwv[i] = 1.0 / w;
-        S.nhat_w[(size_t)chain * nr + col0 + basis * Dg + i] = w * 3.0;
-    }
-    __syncthreads();
-    for (int r = 0; r < nvec; ++r) {
-        double *out = S.nhat + ((size_t)chain * nr + col0 + basis * Dg + r) * D;
-        const double iw = iwv[r];
-        for (int d = tid; d < D; d += PC_BIG_NT) out[d] = V[(size_t)d * PC_BIG_NT + r] * iw;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// K0 for 64 < nDims <= 128: FOUR threads per basis vector (32 coordinates each, all in registers), 512 threads per
-// basis.  Dot products are 8 deep instead of 32, the four partial sums meet through DPP quad permutes, the pivot
-// travels through 2 KB of LDS, and the whitening streams the Cholesky factor through 32-row LDS tiles whose rows
-// line up with the four coordinate blocks.  (One thread per vector needed 128 fp64 registers and spilled; vectors
-// kept in LDS made every Gram-Schmidt step an LDS round trip per coordinate: 1.5 ms per launch at nDims = 100.)
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double quad_sum(double v)
-{
-    v += dpp_f64<PC_DPP_XOR1>(v);
-    v += dpp_f64<PC_DPP_XOR2>(v);
-    return v;
-}
-// HV = coordinates per thread: 8 (nDims <= 32), 16 (<= 64), 32 (<= 128); 4*HV vectors of 4*HV padded coordinates
-// PART (HV = 32, one grade): 0 = the whole kernel; 1 = deviates + Gram-Schmidt only, the orthonormal basis goes to nhat_raw
-// in the operand layout of k_whiten, which does the rest.  Part 1 touches nothing the contraction changes: it is drawn on
-// the side stream while earlier nurseries are sampled and consumed.  (The production first half is k_basis -- Gram-Schmidt
-// in panels; this one, pivot by pivot, stays as the reference-order variant behind PC_BASIS_PANEL_OFF.)
-template <int HV, int PART = 0>
-__global__ __launch_bounds__(16 * HV) void k_nhats_q(PcState S, unsigned batch)
-{
-    // (fused where ONE expression says a * b + c and nowhere else: the body is compiled as the whole kernel, as its two halves and with
-    //  the run in the grid, and what the optimiser fuses across statements differed between those -- a run in step must be the run alone)
-#pragma clang fp contract(on)
-#include "pc_nhats_q_body.inc"
-}
-template <int HV, int PART = 0>
-__global__ __launch_bounds__(16 * HV) void k_nhats_q_many(const PcManyRec *__restrict__ R)
-{
-    // (pointers left generic here: with them made global -- pc_many_state -- the compiler fused other multiply-adds than in the one-run
-    //  kernel, the same statements, and a run in step was no longer bit for bit the run alone)
-    const PcState S = R[blockIdx.z].S;
-    const unsigned batch = (unsigned)R[blockIdx.z].ia[PC_REC_I_BATCH];
-    {
-#pragma clang fp contract(on)
-#include "pc_nhats_q_body.inc"
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// First half of K0 for 64 < nDims <= 128, one grade (split launch): the orthonormal bases (random_utils.F90:381-437),
-// Gram-Schmidt in PANELS of sixteen vectors with the trailing update on the fp64 matrix cores.
-//
-// Eight waves per basis, wave g owns vectors 16 g .. 16 g + 15 in the pair layout of k_whiten (which reads them back as
-// its B operand).  Panel p: wave p orthogonalises its sixteen vectors among themselves -- the reference's loop, pivot by
-// pivot, the pivot travelling through LDS inside ONE wave (no block barrier, the other waves are parked) -- and leaves
-// them, normalised, in LDS; then every later wave projects its sixteen vectors on the whole panel at once:
-//     C = Q V^T   (16 x 16, contraction over the coordinates),    V <- V - C^T Q,
-// two products whose operands are the registers the vectors live in (V is the B operand of the first and the accumulator
-// of the second; C comes out of the first in the layout the second wants it in) and rows of the panel read from LDS.
-// That is the reference's arithmetic inside a panel and block classical Gram-Schmidt across panels: the coefficients
-// of a panel's pivots are taken from the vector as it was BEFORE the panel, not after each pivot -- the same numbers up to
-// rounding of the order of the basis' condition number times epsilon (what k_nhats_big does beyond 128 dimensions).
-// One barrier per panel instead of one per pivot, 56 matrix instructions per wave and panel instead of sixteen rounds of
-// 32 LDS loads + 96 FMAs: the one-pivot-at-a-time kernel spent 110 us per basis here.
-// sum over the four lanes 16 apart (the four coordinate classes of a vector in the pair layout), every lane ends with the
-// total: gfx950's row / half swaps (v_permlane16_swap, v_permlane32_swap) instead of two trips through the LDS crossbar
-__device__ __forceinline__ double lk_sum4(double x)
-{
-    {
-        const auto a = __builtin_amdgcn_permlane16_swap(__double2loint(x), __double2loint(x), false, false);
-        const auto b = __builtin_amdgcn_permlane16_swap(__double2hiint(x), __double2hiint(x), false, false);
-        x = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    }
-    {
-        const auto a = __builtin_amdgcn_permlane32_swap(__double2loint(x), __double2loint(x), false, false);
-        const auto b = __builtin_amdgcn_permlane32_swap(__double2hiint(x), __double2hiint(x), false, false);
-        x = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    }
-    return x;
-}
-// one pivot of the in-panel Gram-Schmidt (random_utils.F90:391-399): the pivot is vector J of the wave, i.e. lane J of every
-// row of sixteen lanes -- its coordinates reach the other lanes of the row by DPP row broadcast, no LDS round trip
-template <int J, int NM>
-__device__ __forceinline__ void gs_pivot(double (&v)[NM], int li)
-{
-    double q[NM];
-#pragma unroll
-    for (int n = 0; n < NM; ++n)
-        q[n] = __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v[n]), 0x150 + J, 0xF, 0xF, false),
-                                __builtin_amdgcn_update_dpp(0, __double2loint(v[n]), 0x150 + J, 0xF, 0xF, false));
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
-#pragma unroll
-    for (int n = 0; n < NM; n += 4) {
-        a0 += q[n] * q[n]; a1 += q[n + 1] * q[n + 1]; a2 += q[n + 2] * q[n + 2]; a3 += q[n + 3] * q[n + 3];
-        c0 += q[n] * v[n]; c1 += q[n + 1] * v[n + 1]; c2 += q[n + 2] * v[n + 2]; c3 += q[n + 3] * v[n + 3];
-    }
-    const double qq = lk_sum4((a0 + a1) + (a2 + a3)), dv = lk_sum4((c0 + c1) + (c2 + c3));
-    // 1 / qq by Newton from the hardware estimate (two steps: full precision)
-    double rq = __builtin_amdgcn_rcp(qq);
-    rq = fma(rq, fma(-qq, rq, 1.0), rq);
-    rq = fma(rq, fma(-qq, rq, 1.0), rq);
-    const double cproj = (li > J) ? dv * rq : 0.0;                      // (the pivot itself and the vectors before it stay)
-#pragma unroll
-    for (int n = 0; n < NM; ++n) v[n] -= cproj * q[n];
-}
-
-template <int NT>
-__global__ __launch_bounds__(512) void k_basis(PcState S, unsigned batch)
-{
-    typedef double v4d __attribute__((ext_vector_type(4)));
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    constexpr int NM = 4 * NT, NS = 130, RAWB = 32 * 512;
-    __shared__ __attribute__((aligned(16))) double Qp[2][16 * NS];
-    __builtin_amdgcn_s_setprio(3);                 // (the side stream's kernel is the one the run waits for: section 5d)
-    const int D = S.D;
-    const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6, li = lane & 15, lk = lane >> 4;
-    const int chain = blockIdx.y, basis = blockIdx.x;
-    const int ivec = 16 * g + li, np = (D + 15) >> 4;
-    const bool vact = ivec < D;
-    // gaussian deviates: element (basis D + i) D + d of stream (batch, chain) in PC_DOM_NHAT, two per Philox call
-#ifdef BASIS_DBG
-    const long long t_start = clock64();
-#endif
-    double v[NM];
-#pragma unroll
-    for (int n = 0; n < NM; ++n) v[n] = 0.0;
-    {
-        // AS241 in two halves (pc_dev.h): the central branch inline; the arguments that fall in a tail (15 %) wait in an LDS
-        // queue and are finished together, so a wave runs the log / sqrt branch about ten times instead of 4 NT times
-        constexpr int TQ = 16;                                           // queue slots a lane (beyond: the whole function inline)
-        __shared__ double tailq[TQ * 512];
-        unsigned tmask = 0u; int tcount = 0;
-        auto deviate = [&](double u, int n) __attribute__((always_inline)) {
-            bool t;
-            double x = pc_inv_normal_central(u, t);
-            if (t) { if (tcount < TQ) { tailq[tcount * 512 + tid] = u; tmask |= 1u << n; tcount++; } else x = pc_inv_normal_cdf(u); }
-            return x;
-        };
-        if (vact) {
-            const long long e0 = (long long)pc_sel(S.g_e0, 0) + ((long long)basis * D + ivec) * D;
-#pragma unroll
-            for (int n = 0; n < NM; n += 2) {
-                const int d = 8 * (n >> 1) + 2 * lk;
-                if (d < D) {
-                    const long long e = e0 + d;
-                    double ua, ub;
-                    pc_uniform2(S.k0, S.k1, PC_DOM_NHAT, batch, (uint32_t)chain, (uint32_t)(e >> 1), ua, ub);
-                    if ((e & 1ll) == 0) { v[n] = deviate(ua, n); if (d + 1 < D) v[n + 1] = deviate(ub, n + 1); }
-                    else {
-                        v[n] = deviate(ub, n);
-                        if (d + 1 < D) { pc_uniform2(S.k0, S.k1, PC_DOM_NHAT, batch, (uint32_t)chain, (uint32_t)(e >> 1) + 1u, ua, ub); v[n + 1] = deviate(ua, n + 1); }
-                    }
-                }
-            }
-        }
-        for (int k = 0; __any(k < tcount); ++k)
-            if (k < tcount) tailq[k * 512 + tid] = pc_inv_normal_tail(tailq[k * 512 + tid]);
-        int c = 0;
-#pragma unroll
-        for (int n = 0; n < NM; ++n) if ((tmask >> n) & 1u) { v[n] = tailq[c * 512 + tid]; c++; }
-    }
-    {   // random_direction (random_utils.F90:276-298)
-        double p0 = 0.0, p1 = 0.0;
-#pragma unroll
-        for (int n = 0; n < NM; n += 2) { p0 += v[n] * v[n]; p1 += v[n + 1] * v[n + 1]; }
-        const double n2 = lk_sum4(p0 + p1), inrm = vact ? 1.0 / sqrt(n2) : 0.0;
-#pragma unroll
-        for (int n = 0; n < NM; ++n) v[n] *= inrm;
-    }
-    const int arow_l = 8 * (li >> 3) + 2 * (li & 3) + ((li >> 2) & 1);   // row of an output tile that sits in my A-operand slot
-    double *rawb = S.nhat_raw + ((size_t)chain * S.nb_total + basis) * (size_t)RAWB + (size_t)g * 64 + lane;
-#ifdef BASIS_DBG
-    const bool dbg = blockIdx.x == 0 && blockIdx.y == 0 && lane == 0;
-    const long long t_rng = clock64();
-    if (dbg && g == 0) atomicAdd((unsigned long long *)&S.ctl->gen_cyc[0], (unsigned long long)(t_rng - t_start));
-#endif
-    for (int p = 0; p < np; ++p) {
-        double *Q = Qp[p & 1];
-#ifdef BASIS_DBG
-        const long long t_a = clock64();
-#endif
-        if (g == p) {
-            // ---- my panel: Gram-Schmidt pivot by pivot (random_utils.F90:391-399), the pivot unnormalised as there
-            const int cnt = min(16, D - 16 * p);
-#define PC_GS(J) if (J < cnt) gs_pivot<J, NM>(v, li);
-            PC_GS(0) PC_GS(1) PC_GS(2) PC_GS(3) PC_GS(4) PC_GS(5) PC_GS(6) PC_GS(7)
-            PC_GS(8) PC_GS(9) PC_GS(10) PC_GS(11) PC_GS(12) PC_GS(13) PC_GS(14) PC_GS(15)
-#undef PC_GS
-            {   // the panel's vectors are final: normalise (the reference does it when a vector becomes the pivot: same vector)
-                double p0 = 0.0, p1 = 0.0;
-#pragma unroll
-                for (int n = 0; n < NM; n += 2) { p0 += v[n] * v[n]; p1 += v[n + 1] * v[n + 1]; }
-                const double n2 = lk_sum4(p0 + p1), inrm = (li < cnt) ? 1.0 / sqrt(n2) : 0.0;
-#pragma unroll
-                for (int n = 0; n < NM; ++n) v[n] *= inrm;
-            }
-            // the finished panel, normalised, for the waves behind; and out to HBM
-#pragma unroll
-            for (int n = 0; n < NM; n += 2) *(v2d *)&Q[li * NS + 4 * n + 2 * lk] = v2d{v[n], v[n + 1]};
-#pragma unroll
-            for (int n = 0; n < NM; ++n) rawb[(size_t)n * 512] = v[n];
-#ifdef BASIS_DBG
-            if (dbg) atomicAdd((unsigned long long *)&S.ctl->gen_cyc[1], (unsigned long long)(clock64() - t_a));
-#endif
-        }
-        __syncthreads();
-#ifdef BASIS_DBG
-        const long long t_b = clock64();
-#endif
-        if (g > p && 16 * g < D) {
-            // ---- a later wave: C = Q V^T, V <- V - C^T Q
-            v4d c4 = v4d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int n = 0; n < NM; n += 2) {
-                const v2d a2 = *(const v2d *)&Q[li * NS + 4 * n + 2 * lk];
-                c4 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2.x, v[n], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2.y, v[n + 1], c4, 0, 0, 0);
-            }
-#pragma unroll
-            for (int ti = 0; ti < NT; ++ti) {
-                v4d a4 = v4d{v[4 * ti], v[4 * ti + 1], v[4 * ti + 2], v[4 * ti + 3]};
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks)
-                    a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(Q[(4 * ks + lk) * NS + 16 * ti + arow_l], -c4[ks], a4, 0, 0, 0);
-                v[4 * ti] = a4[0]; v[4 * ti + 1] = a4[1]; v[4 * ti + 2] = a4[2]; v[4 * ti + 3] = a4[3];
-            }
-#ifdef BASIS_DBG
-            if (dbg && g == p + 1) atomicAdd((unsigned long long *)&S.ctl->gen_cyc[2], (unsigned long long)(clock64() - t_b));
-#endif
-        }
-    }
-#ifdef BASIS_DBG
-    if (dbg && g == 0) { atomicAdd((unsigned long long *)&S.ctl->gen_cyc[3], (unsigned long long)(clock64() - t_start)); atomicAdd((unsigned long long *)&S.ctl->nn_walks, 1ull); }
-#endif
-}
-
-// ------------------------------------------------------------------------------------------
-// Second half of K0 for 64 < nDims <= 128, one grade (split launch, see k_nhats_q<32, 1>): seeds, whitening W = L.N and, for
-// the correlated Gaussian, the products M.(span o n^) -- everything on the fp64 matrix cores, sixteen vectors per wave.
-//
-// Register layout ("pair layout"): lane (li = lane & 15, lk = lane >> 4) of the wave that owns vectors 16 g .. 16 g + 15
-// holds, of vector 16 g + li, the coordinates  dim(n, lk) = 8 (n >> 1) + 2 lk + (n & 1),  n = 0 .. 4 NT - 1  -- pairs of
-// neighbours, so that a row leaves in 16-byte pieces.  That IS the B operand of v_mfma_f64_16x16x4_f64 for contraction
-// step n (B[k = lk][j = li]) once the A operand uses the same numbering of the contracted index, and it is also the D
-// layout of an output tile whose sixteen rows are numbered  row(ti, i) = 16 ti + 8 (i >> 3) + 2 (i & 3) + ((i >> 2) & 1):
-// register r of tile ti of lane lk is row i = lk + 4 r, i.e. dim(4 ti + r, lk).  So the basis read from HBM is the B operand
-// of L.N, its normalised result is the B operand of M.s, and both results leave from the registers they were summed in:
-// no basis in LDS, no transposes.  LDS holds two tiles of sixteen matrix rows (the one in use, the one arriving).
-// A block is four waves = 64 vectors, two blocks per basis; each streams the tiles of L and M itself.
-template <int NT>
-__global__ __launch_bounds__(256) void k_whiten(PcState S, unsigned batch)
-{
-    typedef double v4d __attribute__((ext_vector_type(4)));
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    constexpr int NM = 4 * NT, NR = 16 * NT, NS = 130, RAWB = 32 * 512;
-    __shared__ __attribute__((aligned(16))) double tiles[2][16 * NS];
-    __shared__ double spn[128], y0s[128];
-    __shared__ int sh[2];
-    const int D = S.D, nr = S.nr;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4;
-    const int chain = blockIdx.y, basis = blockIdx.x >> 1, half = blockIdx.x & 1, g = 4 * half + wv;
-    const bool wact = 16 * g < D;                                       // my sixteen vectors exist (at least one of them)
-    const bool ms = S.nhat_Ms != nullptr;
-    if (tid == 0) {
-        int sel, slot;
-        select_seed(S, batch, chain, sel, slot);
-        sh[0] = sel; sh[1] = slot;
-        if (blockIdx.x == 0) {
-            S.ch_cluster[chain] = sel; S.ch_seed_slot[chain] = slot;
-            S.ch_contour[chain] = S.logLp[sel];          // nested_sampling.F90:270
-            S.ch_epoch[chain] = S.ctl->admin_epoch;
-            if (chain == 0) { S.ctl->i_nursery = gridDim.y; S.ctl->batch_id = batch; }
-        }
-    }
-    // the basis, straight into the operand registers
-    double b[NM];
-    {
-        const double *rawb = S.nhat_raw + ((size_t)chain * S.nb_total + basis) * (size_t)RAWB + (size_t)g * 64 + lane;
-#pragma unroll
-        for (int n = 0; n < NM; ++n) b[n] = wact ? rawb[(size_t)n * 512] : 0.0;
-    }
-    __syncthreads();
-    const double *Lc = S.chol + (size_t)sh[0] * D * D;
-    if (ms && tid < 128) {
-        const bool on = tid < D;
-        const double lo = (on && S.prior.lo) ? S.prior.lo[tid] : 0.0, hi = (on && S.prior.hi) ? S.prior.hi[tid] : 1.0;
-        spn[tid] = on ? hi - lo : 0.0;
-        const double c0 = on ? S.live[(size_t)sh[1] * S.nT + tid] : 0.0;
-        y0s[tid] = on ? (lo + (hi - lo) * c0) - (S.like.mean ? S.like.mean[tid] : 0.0) : 0.0;
-    }
-    // tiles travel global -> registers -> LDS one tile ahead of the matrix cores: one barrier per tile
-    double pre[8];
-    auto load_L = [&](int ti) __attribute__((always_inline)) {
-        const int kmax = min(NR, 16 * (ti + 1));                        // L(a, b) = 0 for b > a
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int x = tid + q * 256, r = x / kmax, bcol = x - r * kmax, arow = 16 * ti + r;
-            pre[q] = (x < 16 * kmax && arow < D && bcol < D) ? Lc[(size_t)arow * D + bcol] : 0.0;
-        }
-    };
-    auto store_L = [&](int ti) __attribute__((always_inline)) {
-        const int kmax = min(NR, 16 * (ti + 1));
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int x = tid + q * 256, r = x / kmax, bcol = x - r * kmax;
-            if (x < 16 * kmax) tiles[ti & 1][r * NS + bcol] = pre[q];
-        }
-    };
-    const double *Mt = S.like.invcov;                                   // Mt[b * D + a] = M(a, b)
-    auto load_M = [&](int ti) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int x = tid + q * 256, r = x & 15, bcol = x >> 4, arow = 16 * ti + r;
-            pre[q] = (x < 16 * NR && arow < D && bcol < D) ? Mt[(size_t)bcol * D + arow] : 0.0;
-        }
-    };
-    auto store_M = [&](int ti) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int x = tid + q * 256, r = x & 15, bcol = x >> 4;
-            if (x < 16 * NR) tiles[ti & 1][r * NS + bcol] = pre[q];
-        }
-    };
-    // my row of a tile as A operand (row(ti, li) - 16 ti), and where contraction steps n, n + 1 (n even) sit in it
-    const int arow_l = 8 * (li >> 3) + 2 * (li & 3) + ((li >> 2) & 1);
-    const int aoff = arow_l * NS + 2 * lk;
-    v4d acc[NT];
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti) acc[ti] = v4d{0.0, 0.0, 0.0, 0.0};
-    load_L(0);
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti) {
-        store_L(ti);
-        if (ti + 1 < NT) load_L(ti + 1);
-        __syncthreads();
-        if (wact) {
-            const double *pa = &tiles[ti & 1][aoff];
-            v4d a4 = v4d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int n = 0; n < 4 * (ti + 1); n += 2) {
-                const v2d a2 = *(const v2d *)(pa + 4 * n);              // dims 8 (n >> 1) + 2 lk, + 1
-                a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2.x, b[n], a4, 0, 0, 0);
-                a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2.y, b[n + 1], a4, 0, 0, 0);
-            }
-            acc[ti] = a4;
-        }
-    }
-    if (ms) load_M(0);
-    // |w| of my vector (chordal_sampling.f90:80-82): my registers, then the other three lane groups
-    double n2 = 0.0;
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) n2 += acc[ti][r] * acc[ti][r];
-    n2 += __shfl_xor(n2, 16); n2 += __shfl_xor(n2, 32);
-    const double wn = sqrt(n2), iw = 1.0 / wn;
-    const int ivec = 16 * g + li;
-    const bool wanted = wact && ivec < D && basis * D + ivec < nr;
-    const size_t orow = ((size_t)chain * nr + (size_t)basis * D + ivec) * D;
-    const bool al16 = (D & 1) == 0;
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) b[4 * ti + r] = acc[ti][r] * iw;   // n^ in pair layout
-    auto put_rows = [&](double *base) __attribute__((always_inline)) {
-        if (!wanted) return;
-        double *out = base + orow;
-#pragma unroll
-        for (int n = 0; n < NM; n += 2) {
-            const int d = 8 * (n >> 1) + 2 * lk;
-            if (d + 1 < D && al16) *(v2d *)(out + d) = v2d{b[n], b[n + 1]};
-            else { if (d < D) out[d] = b[n]; if (d + 1 < D) out[d + 1] = b[n + 1]; }
-        }
-    };
-    put_rows(S.nhat);
-    if (wanted && lk == 0) S.nhat_w[(size_t)chain * nr + (size_t)basis * D + ivec] = wn * 3.0;
-    if (!ms) return;
-    // ---- correlated Gaussian (random_gaussian.f90:17-30): along a chord the exponent is quadratic (see ChainCtx) and all a
-    //      slice needs of the matrix is M.s, s = span o n^; every direction of the chain is known here.  One wave of the
-    //      chain's first basis also forms M.(theta_seed - mean), the product the chain needs for its start point.
-#pragma unroll
-    for (int n = 0; n < NM; ++n) b[n] *= spn[8 * (n >> 1) + 2 * lk + (n & 1)];
-    const bool do_y0 = basis == 0 && half == 1 && wv == 3;
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti) acc[ti] = v4d{0.0, 0.0, 0.0, 0.0};
-    __syncthreads();                                                    // the last tile of L has been consumed
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti) {
-        store_M(ti);
-        if (ti + 1 < NT) load_M(ti + 1);
-        __syncthreads();
-        const double *pa = &tiles[ti & 1][aoff];
-        if (wact) {
-            v4d a4 = v4d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int n = 0; n < NM; n += 2) {
-                const v2d a2 = *(const v2d *)(pa + 4 * n);
-                a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2.x, b[n], a4, 0, 0, 0);
-                a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2.y, b[n + 1], a4, 0, 0, 0);
-            }
-            acc[ti] = a4;
-        }
-        if (do_y0) {
-            double t = 0.0;
-#pragma unroll
-            for (int n = 0; n < NM; n += 2) {
-                const v2d a2 = *(const v2d *)(pa + 4 * n);
-                const int d = 8 * (n >> 1) + 2 * lk;
-                t += a2.x * y0s[d] + a2.y * y0s[d + 1];
-            }
-            t += __shfl_xor(t, 16); t += __shfl_xor(t, 32);
-            const int a = 16 * ti + arow_l;
-            if (lk == 0 && a < D) S.ch_My[(size_t)chain * D + a] = t;
-        }
-    }
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) b[4 * ti + r] = acc[ti][r];
-    put_rows(S.nhat_Ms);
-}
-
-// ------------------------------------------------------------------------------------------
 // K1: one slice-sampling chain per wavefront
 // ------------------------------------------------------------------------------------------
 template <int DPL, int NROWS, int PT = 0>
@@ -2502,123 +1397,6 @@ extern "C" int pc_launch_generate_live(const PcState *S, int attempt0, int n, do
     case 12: PC_LAUNCH((k_generate_live<4, 1>), dim3(n), dim3(64), sh, st, *S, attempt0, rows, rows_logL); return 0;
     }
     return 1;
-}
-
-// the split launch (see k_nhats): part 1 = bases, part 2 = seeds + whitening; returns 1 where only the whole kernel exists
-extern "C" int pc_nhats_splittable(const PcState *S)
-{
-    const char *e = std::getenv("PC_NHATS_QUAD_MIN");
-    if (S->D > 64 && S->D <= 128) return S->ngrade <= 1 && !S->seq_mode && S->nhat_raw != nullptr;    // k_nhats_q<32, 1 / 2>
-    if (S->D > 24 && S->D <= 64) return S->ngrade <= 1 && !S->seq_mode && S->nhat_raw != nullptr && (!e || std::atoi(e) <= 25);      // k_nhats_q<8 / 16, 1 / 2> (round 5)
-    return S->D <= 24 && S->D < (e ? std::atoi(e) : 25) && !S->seq_mode && S->nhat_raw != nullptr;
-}
-// dynamic LDS of k_nhats_q<HV> (HV = 8, 16): pivot buffer + Cholesky tile (HV rows of 4 (HV + 2) doubles) ...
-static size_t pc_nhats_q_lds(int HV) { return sizeof(double) * (size_t)(2 + HV) * 4 * (HV + 2); }
-// ... and of k_nhats_q<32>: basis + sixteen rows of L (two tile buffers up to nDims 112; beyond that one, with a barrier more per tile: 160 KB of LDS)
-static size_t pc_nhats_q32_lds(int D) { const int NR = ((D + 15) / 16) * 16; return sizeof(double) * (2 * 4 * 34 + (size_t)(NR + (NR <= 112 ? 32 : 16)) * 129); }
-// ... and of k_nhats_w<DMAX> (nDims <= 24): per = 64 / nDims bases a workgroup, each nDims^2 doubles of deviates, a double-buffered pivot of
-// DMAX doubles and nDims^2 ints of tail queue (every deviate may be a tail argument): at most 64 nDims (8 + 4) + 64 x 16 x 3 bytes = 21.5 KB
-static size_t pc_nhats_w_lds(int D, int DMAX) { return (size_t)(64 / D) * (sizeof(double) * ((size_t)D * D + 2 * DMAX) + sizeof(int) * (size_t)D * D); }
-extern "C" int pc_launch_nhats_part(const PcState *S, unsigned batch, int nchains, int part, hipStream_t st, int packed)
-{
-    if (!pc_nhats_splittable(S)) return 1;
-    const int D = S->D;
-    dim3 grid(S->nb_total, nchains);
-    if (D > 64) {
-        if (part == 1) {
-            static const bool panel_off = std::getenv("PC_BASIS_PANEL_OFF") != nullptr;
-            const int nt1 = (D + 15) / 16;
-            if (panel_off) hipLaunchKernelGGL((k_nhats_q<32, 1>), grid, dim3(512), sizeof(double) * 2 * 4 * 34, st, *S, batch);
-            else if (nt1 <= 5) hipLaunchKernelGGL((k_basis<5>), grid, dim3(512), 0, st, *S, batch);
-            else if (nt1 == 6) hipLaunchKernelGGL((k_basis<6>), grid, dim3(512), 0, st, *S, batch);
-            else if (nt1 == 7) hipLaunchKernelGGL((k_basis<7>), grid, dim3(512), 0, st, *S, batch);
-            else hipLaunchKernelGGL((k_basis<8>), grid, dim3(512), 0, st, *S, batch);
-        }
-        else {
-            dim3 g2(S->nb_total * 2, nchains);
-            const int nt = (D + 15) / 16;
-            if (nt <= 5) hipLaunchKernelGGL((k_whiten<5>), g2, dim3(256), 0, st, *S, batch);
-            else if (nt == 6) hipLaunchKernelGGL((k_whiten<6>), g2, dim3(256), 0, st, *S, batch);
-            else if (nt == 7) hipLaunchKernelGGL((k_whiten<7>), g2, dim3(256), 0, st, *S, batch);
-            else hipLaunchKernelGGL((k_whiten<8>), g2, dim3(256), 0, st, *S, batch);
-        }
-        return 0;
-    }
-    if (D > 24) {
-        // nDims 25 ... 64: the four-threads-per-vector kernel in two halves -- deviates + Gram-Schmidt (nothing the contraction changes:
-        // drawn ahead on the side stream), then seeds + whitening in front of k_slice
-        if (D <= 32) { if (part == 1) hipLaunchKernelGGL((k_nhats_q<8, 1>), grid, dim3(128), pc_nhats_q_lds(8), st, *S, batch); else hipLaunchKernelGGL((k_nhats_q<8, 2>), grid, dim3(128), pc_nhats_q_lds(8), st, *S, batch); }
-        else { if (part == 1) hipLaunchKernelGGL((k_nhats_q<16, 1>), grid, dim3(256), pc_nhats_q_lds(16), st, *S, batch); else hipLaunchKernelGGL((k_nhats_q<16, 2>), grid, dim3(256), pc_nhats_q_lds(16), st, *S, batch); }
-        return 0;
-    }
-    const size_t sh = sizeof(double) * ((size_t)(D + 8) * (D + 8) + 2 * 128) + 16;
-    // several runs on the device (packed == PC_PART1_PACKED): the same bases, lane = basis (pc_slice_t.hip)
-    if (part == 1 && packed == PC_PART1_PACKED && pc_launch_bases_t(S, batch, nchains, st) == 0) return 0;
-    // a run on its own (packed == PC_PART1_WAVE): one grade, keyed draws -- 64 / nDims bases a wavefront, in one launch, decks included
-    if (part == 1 && packed == PC_PART1_WAVE && S->ngrade <= 1) {
-        const int nbases = nchains * S->nb_total, per = 64 / D;
-        const dim3 gw((nbases + per - 1) / per);
-        if (S->ablate & PC_ABL_BASES_WAVE1) {        // one wavefront a workgroup, as it was: the same bits
-            if (D <= 8) hipLaunchKernelGGL((k_nhats_w<8, 1>), gw, dim3(64), pc_nhats_w_lds(D, 8), st, *S, batch, nbases);
-            else if (D <= 16) hipLaunchKernelGGL((k_nhats_w<16, 1>), gw, dim3(64), pc_nhats_w_lds(D, 16), st, *S, batch, nbases);
-            else hipLaunchKernelGGL((k_nhats_w<24, 1>), gw, dim3(64), pc_nhats_w_lds(D, 24), st, *S, batch, nbases);
-            return 0;
-        }
-        if (D <= 8) hipLaunchKernelGGL((k_nhats_w<8, 4>), gw, dim3(256), pc_nhats_w_lds(D, 8), st, *S, batch, nbases);
-        else if (D <= 16) hipLaunchKernelGGL((k_nhats_w<16, 4>), gw, dim3(256), pc_nhats_w_lds(D, 16), st, *S, batch, nbases);
-        else hipLaunchKernelGGL((k_nhats_w<24, 4>), gw, dim3(256), pc_nhats_w_lds(D, 24), st, *S, batch, nbases);
-        return 0;
-    }
-    if (part == 1) {
-        if (D <= 8) hipLaunchKernelGGL((k_nhats<8, 64, 1>), grid, dim3(64), sh, st, *S, batch);
-        else if (D <= 16) hipLaunchKernelGGL((k_nhats<16, 64, 1>), grid, dim3(64), sh, st, *S, batch);
-        else hipLaunchKernelGGL((k_nhats<24, 64, 1>), grid, dim3(64), sh, st, *S, batch);
-    } else {
-        if (D <= 8) hipLaunchKernelGGL((k_nhats<8, 64, 2>), grid, dim3(64), sh, st, *S, batch);
-        else if (D <= 16) hipLaunchKernelGGL((k_nhats<16, 64, 2>), grid, dim3(64), sh, st, *S, batch);
-        else hipLaunchKernelGGL((k_nhats<24, 64, 2>), grid, dim3(64), sh, st, *S, batch);
-    }
-    return 0;
-}
-
-extern "C" int pc_launch_nhats(const PcState *S, unsigned batch, int nchains, hipStream_t st)
-{
-    const int D = S->D, nb = S->nb_total;
-    dim3 grid(nb, nchains);
-    static int quad_min = -1;                       // smallest nDims that takes the four-threads-per-vector kernel
-    if (quad_min < 0) { const char *e = std::getenv("PC_NHATS_QUAD_MIN"); quad_min = e ? std::atoi(e) : 25; }   // measured: 20-D 52 vs 39 us (old kernel better), 28-D 43 vs 47, 40-D 95 vs 133, 64-D 129 vs 240
-    if (D >= quad_min) {
-        if (D <= 32) hipLaunchKernelGGL((k_nhats_q<8>), grid, dim3(128), pc_nhats_q_lds(8), st, *S, batch);
-        else if (D <= 64) hipLaunchKernelGGL((k_nhats_q<16>), grid, dim3(256), pc_nhats_q_lds(16), st, *S, batch);
-        else if (D <= 128) {
-            const size_t shq = pc_nhats_q32_lds(D);
-            pc_need_dyn_lds((const void *)k_nhats_q<32>, shq);
-            hipLaunchKernelGGL((k_nhats_q<32>), grid, dim3(512), shq, st, *S, batch);
-        }
-        else if (D <= 256 && S->nhat_raw) hipLaunchKernelGGL(k_nhats_big, grid, dim3(PC_BIG_NT), 0, st, *S, batch);
-        else return 1;
-        return 0;
-    }
-    // deviates / Cholesky factor with padded rows, then the double-buffered pivot (2 x DMAX <= 2 x 128)
-    const size_t sh = sizeof(double) * ((size_t)(D + 8) * (D + 8) + 2 * 128) + 16;
-    if (D <= 8) hipLaunchKernelGGL((k_nhats<8, 64>), grid, dim3(64), sh, st, *S, batch);
-    else if (D <= 16) hipLaunchKernelGGL((k_nhats<16, 64>), grid, dim3(64), sh, st, *S, batch);
-    else if (D <= 24) hipLaunchKernelGGL((k_nhats<24, 64>), grid, dim3(64), sh, st, *S, batch);
-    else if (D <= 32) hipLaunchKernelGGL((k_nhats<32, 64>), grid, dim3(64), sh, st, *S, batch);
-    else if (D <= 64) hipLaunchKernelGGL((k_nhats<64, 64>), grid, dim3(64), sh, st, *S, batch);
-    else return 1;
-    return 0;
-}
-
-// ... and for several runs of a device in step (grid.z = run) the shapes that do not split: 24 < nDims <= 64
-extern "C" int pc_launch_nhats_many(const PcState *S, const PcManyRec *dR, int R, int nchains, hipStream_t st)
-{
-    const int D = S->D, nb = S->nb_total;
-    if (D < 25 || D > 64 || S->seq_mode || std::getenv("PC_NHATS_QUAD_MIN")) return 1;
-    dim3 grid(nb, nchains, R);
-    if (D <= 32) hipLaunchKernelGGL((k_nhats_q_many<8>), grid, dim3(128), pc_nhats_q_lds(8), st, dR);
-    else hipLaunchKernelGGL((k_nhats_q_many<16>), grid, dim3(256), pc_nhats_q_lds(16), st, dR);
-    return 0;
 }
 
 extern "C" int pc_slice_fusable(const PcState *S)

@@ -71,18 +71,7 @@
                 if (__builtin_amdgcn_readfirstlane((int)(rec[0] == (int)(unsigned)tg && rec[1] == (int)(unsigned)(tg >> 32)))) return dk;
             }
         }
-        int dk = lane, jv = 0;
-        if (lane >= 1 && lane < nr) {
-            const double u = seq_mode ? pc_seq_uniform(S, seq_g0 + (unsigned long long)(nr - 1 - lane))
-                                        : pc_uniform(S.k0, S.k1, PC_DOM_SHUFFLE, batch, (uint32_t)chain, (uint32_t)lane);
-            int j = (int)ceil(u * lane);
-            jv = j < 1 ? 1 : (j > lane ? lane : j);
-        }
-        for (int i = nr - 1; i >= 1; --i) {
-            const int j = __builtin_amdgcn_readlane(jv, i);
-            const int di = __builtin_amdgcn_readlane(dk, i), dj = __builtin_amdgcn_readlane(dk, j);
-            dk = (lane == i) ? dj : ((lane == j) ? di : dk);
-        }
+        PC_DECK_SHUFFLE(dk, S, batch, chain, lane, nr, seq_mode, seq_g0)       // (pc_seed.h: one text with the records' writers)
         return dk;
     };
     // (one wavefront's LDS traffic: ordered by issue; the workgroup barrier where the chain has no helper -- as it always was -- and a

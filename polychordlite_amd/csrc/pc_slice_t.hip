@@ -96,7 +96,7 @@ __device__ __forceinline__ void slice_t_body(const PcState &S, unsigned batch, i
         const double hi = (on && S.prior.hi) ? S.prior.hi[tid] : 1.0;
         sLo[tid] = lo; sSpan[tid] = hi - lo;
     }
-    // ---- GenerateSeed (generate.F90:19-55), one cluster: a live point drawn evenly (select_seed of pc_sample.hip)
+    // ---- GenerateSeed (generate.F90:19-55), one cluster: a live point drawn evenly (select_seed of pc_seed.h)
     int slot = 0;
     const bool chain_wave = !HELP || wv == 0;             // the wavefront that walks the chains (HELP: the other one makes directions and uniforms)
     if (chain_wave) {
@@ -527,7 +527,7 @@ static void launch_t(const PcState *S, const PcManyRec *dR, int R, unsigned batc
 namespace {
 
 // ------------------------------------------------------------------------------------------
-// The orthonormal bases of k_nhats<.., 1> (pc_sample.hip: one grade, keyed draws, nDims <= 24) in two kernels that leave the chip
+// The orthonormal bases of k_nhats<.., 1> (pc_bases.hip: one grade, keyed draws, nDims <= 24) in two kernels that leave the chip
 // to the runs next door: the deviates of all bases by a thread per stream call (k_deviates_t: no LDS, as wide as the nursery:
 // random_utils.F90:251-263), then normalisation and Gram-Schmidt (random_utils.F90:276-298, 391-399) with thread = vector and
 // 64 / nDims bases to a wavefront (k_bases_packed) -- k_nhats' arithmetic operation for operation: dot products on four partial
@@ -535,7 +535,7 @@ namespace {
 // (Tried and dropped: a basis per lane in LDS -- 3.2 KB a basis, a CU holds fifty: the runs queue for LDS.)
 // ------------------------------------------------------------------------------------------
 // (the normalisation and the Gram-Schmidt step, dot4_same / dot4 and the fusing rules they restate: PC_GS_PACKED of pc_dev.h, one text with
-//  k_nhats_w of pc_sample.hip)
+//  k_nhats_w of pc_bases.hip)
 
 // step 2: thread = vector, as in k_nhats, but 64 / nDims bases to a wavefront (a basis keeps nDims of a wave's lanes busy) and
 // the deviates already made: every thread keeps its vector in registers, the pivot goes round through a few hundred bytes of

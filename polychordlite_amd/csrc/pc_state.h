@@ -35,9 +35,9 @@ enum { PC_ERR_NONE = 0, PC_ERR_PHANTOM_CAP = 1, PC_ERR_DEAD_CAP = 2, PC_ERR_CLUS
 //                                   of its own, not by workgroups of the row kernel's launch
 //   18   PC_ABL_ACCEPT_SERIAL       the parallel contraction's acceptance as the serial recurrence, chunk    pc_par.hip
 //                                   after chunk on one wavefront, not as one dominance count a step
-//   19   PC_ABL_BASES_WAVE          a run on its own, nDims <= 24, one grade: the bases a wavefront each     pc_engine.hip
-//                                   (k_nhats<.., 64, 1>), not 64 / nDims a wavefront (k_nhats_w)
-//   20   PC_ABL_BASES_WAVE1         ... k_nhats_w with one wavefront a workgroup (k_nhats_w<.., 1>), not four  pc_sample.hip
+//   19   PC_ABL_BASES_WAVE          a run on its own, nDims <= 24, one grade: the bases a wavefront each     pc_launch.h for pc_engine.hip
+//                                   (k_nhats<.., 64, 1>), not 64 / nDims a wavefront (k_nhats_w)             (the kernels: pc_bases.hip)
+//   20   PC_ABL_BASES_WAVE1         ... k_nhats_w with one wavefront a workgroup (k_nhats_w<.., 1>), not four  pc_bases.hip
 //   30   PC_ABL_TRACE_CHOL          trace of Cholesky fallbacks                                              pc_contract.hip
 enum { PC_ABL_FUNCTOR = 1 << 0, PC_ABL_NO_POOL = 1 << 1, PC_ABL_NO_DEFER = 1 << 2, PC_ABL_NO_FUSED_UPDATE = 1 << 3, PC_ABL_PAIR_SCANS = 1 << 4,
        PC_ABL_CONSUME_GENERAL = 1 << 5, PC_ABL_SLICE_LANE = 1 << 6, PC_ABL_BASES_PACKED = 1 << 7, PC_ABL_CL_END_AT_DEATH = 1 << 8,

@@ -1,4 +1,4 @@
-"""k_nhats_w (pc_sample.hip): part 1 of the split launch of a run on its own at nDims <= 24, one grade -- 64 / nDims bases a wavefront, bases
+"""k_nhats_w (pc_bases.hip): part 1 of the split launch of a run on its own at nDims <= 24, one grade -- 64 / nDims bases a wavefront, bases
 numbered flat over the nursery, the deviates made in place, the chains' deck records written by the wavefront that holds a chain's first basis
 -- against k_nhats<.., 64, 1> (settings.ablate bit 19: a wavefront a basis), which it replaces, and against the packed bases of the runs in
 step (path 2 of pchip_directions, bit 7 of a run).  Everything BYTE FOR BYTE: per vector the operations and their order are k_nhats'.

@@ -1,4 +1,4 @@
-"""k_nhats_w<DMAX, NW> (pc_sample.hip): part 1 of the split launch of a run on its own at nDims <= 24, one grade, by a workgroup of NW = 4
+"""k_nhats_w<DMAX, NW> (pc_bases.hip): part 1 of the split launch of a run on its own at nDims <= 24, one grade, by a workgroup of NW = 4
 wavefronts for the same 64 / nDims bases -- all 256 threads deal the workgroup's stream calls, wavefronts 1 ... 3 make the decks of the chains
 that start in the workgroup (the s-th start by wavefront 1 + s % 3) and end, wavefront 0 orthogonalises and stores -- against NW = 1
 (settings.ablate bit 20: one wavefront does all of it, the kernel as it was) and against k_nhats<.., 64, 1> (bit 19: a wavefront a basis).

@@ -60,7 +60,7 @@ def test_embedded_kernel_text_is_the_files():
             assert t == fh.read(), fn
         seen.append(fn)
         i += 1
-    assert set(seen) == {"pc_dev.h", "pc_state.h", "pc_sample.hip", "pc_slice_body.inc", "pc_nhats_q_body.inc"}
+    assert set(seen) == {"pc_dev.h", "pc_state.h", "pc_seed.h", "pc_sample.hip", "pc_slice_body.inc"}
 
 
 def test_source_symbols_are_exported():

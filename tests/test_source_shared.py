@@ -339,7 +339,7 @@ def test_the_other_forms_still_compile_beside_shared_handles_and_the_text_is_fiv
             break
         seen.append(name.value.decode())
         i += 1
-    assert sorted(seen) == sorted(["pc_dev.h", "pc_state.h", "pc_sample.hip", "pc_slice_body.inc", "pc_nhats_q_body.inc"])
+    assert sorted(seen) == sorted(["pc_dev.h", "pc_state.h", "pc_seed.h", "pc_sample.hip", "pc_slice_body.inc"])
     shared = [_create_form(api, form, 16, 16) for form in ("terms", "sums", "quad")]
     hq = api.source_create(QUAD, options=("-DNRES=16",), data=_quad_line_data(16), residuals=16, precision=_precision("rand", 16))
     hs = api.source_create(EIGHT, data=_eight_data(16), nterms=16, nsums=8)

@@ -322,7 +322,7 @@ def test_the_other_forms_still_compile_beside_a_sums_handle_and_the_text_is_five
             break
         seen.append(name.value.decode())
         i += 1
-    assert sorted(seen) == sorted(["pc_dev.h", "pc_state.h", "pc_sample.hip", "pc_slice_body.inc", "pc_nhats_q_body.inc"])
+    assert sorted(seen) == sorted(["pc_dev.h", "pc_state.h", "pc_seed.h", "pc_sample.hip", "pc_slice_body.inc"])
     hs = _create_sums(api, EIGHT, data=_eight_data(16), nterms=16, nsums=8)
     ht = api.source_create(LINE_TERMS, nterms=16)
     hp = api.source_create(line_replay(LINE_TERMS), options=("-DNTERMS=16",))

@@ -194,7 +194,7 @@ def test_a_plain_handle_still_compiles_the_plain_list_and_the_text_is_five_files
             break
         seen.append(name.value.decode())
         i += 1
-    assert sorted(seen) == sorted(["pc_dev.h", "pc_state.h", "pc_sample.hip", "pc_slice_body.inc", "pc_nhats_q_body.inc"])
+    assert sorted(seen) == sorted(["pc_dev.h", "pc_state.h", "pc_seed.h", "pc_sample.hip", "pc_slice_body.inc"])
     ht = api.source_create(LINE_TERMS, nterms=16)
     hp = api.source_create(replay_of(LINE_TERMS), options=("-DNTERMS=16",))
     names = ["k_generate_live<1>", "k_slice<1, 1, false>", "k_slice<1, 1, true>", "k_slice<1, 1, false, 1, 8>", "k_slice<2, 4, false>",

@@ -1,6 +1,6 @@
 """dev: one run of the metric configuration on the NHATS_W_DBG build (PCHIP_LIB = libpolychord_hip_basesdbg.so, `make -C polychordlite_amd/csrc
 ../libpolychord_hip_basesdbg.so [BASES_DBG=1]`), the section counters of k_nhats_w read from the engine's PC_DEBUG=4 lines -> JSON on stdout.
-Argument: settings.ablate (0: four wavefronts a workgroup, 1048576 = bit 20: one).  Sections (pc_sample.hip, k_nhats_w): 0 decks (one
+Argument: settings.ablate (0: four wavefronts a workgroup, 1048576 = bit 20: one).  Sections (pc_bases.hip, k_nhats_w): 0 decks (one
 wavefront a workgroup: wavefront 0, in front of everything; four: wavefront 1, behind the deviates), then wavefront 0's 1 deviates loop up to
 its barrier, 2 tail pass, 3 loading v[], 4 PC_GS_PACKED, 5 stores; 6 wavefront 0 from start to end; 7 the workgroups counted (BASES_DBG=1:
 workgroup 0 of every launch; 2: all of them)."""

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Compare the gfx950 instruction text of the kernels two builds of an object file have in common.
 
-    python3 tools/dev/isa_diff.py OLD.o NEW.o [--arch gfx950] [--drop-trailing-zero NAME ...]
+    python3 tools/dev/isa_diff.py OLD.o NEW.o [NEW2.o ...] [--arch gfx950] [--drop-trailing-zero NAME ...]
 
-Unbundles the device code object of both files, disassembles them, and compares kernel by kernel (demangled names) the instruction
-text with addresses and encodings removed.  A template that gained a defaulted trailing parameter keeps its instruction stream but not
+Unbundles the device code object of the files, disassembles them, and compares kernel by kernel (demangled names) the instruction
+text with addresses and encodings removed.  Several NEW objects -- a translation unit that was split -- count as the union of their
+kernels, so that "only in OLD" means a kernel was lost, not that it moved; a name that occurs in two of them is an error.
+A template that gained a defaulted trailing parameter keeps its instruction stream but not
 its name: `--drop-trailing-zero k_slice` compares NEW's `k_slice<..., 0>` with OLD's `k_slice<...>`.  Prints one line per kernel that
 differs or exists on one side only, then a summary; exit status 1 if a common kernel differs.
 """
@@ -43,13 +45,19 @@ def disassemble(obj, arch, tmp):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("old"); ap.add_argument("new")
+    ap.add_argument("old"); ap.add_argument("new", nargs="+")
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("--drop-trailing-zero", nargs="*", default=[])
     ap.add_argument("--show", type=int, default=0, help="print up to this many lines of the diff of every kernel that differs")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
-        old, new = disassemble(a.old, a.arch, tmp), disassemble(a.new, a.arch, tmp)
+        old, new = disassemble(a.old, a.arch, tmp), {}
+        for obj in a.new:
+            funcs = disassemble(obj, a.arch, tmp)
+            twice = sorted(set(funcs) & set(new))
+            if twice:
+                sys.exit("in two NEW objects (the second: %s): %s" % (obj, ", ".join(twice)))
+            new.update(funcs)
     renamed = {}
     for n, body in new.items():
         k = n
@@ -58,10 +66,11 @@ def main():
             if m and (m.group(1) + ">" + m.group(2)) in old:
                 k = m.group(1) + ">" + m.group(2)
         renamed[k] = body
-    same = diff = 0
+    same = diff = lost = 0
     for n in sorted(old):
         if n not in renamed:
             print("only in OLD:", n)
+            lost += 1
             continue
         if old[n] == renamed[n]:
             same += 1
@@ -76,7 +85,7 @@ def main():
     only_new = [n for n in sorted(renamed) if n not in old]
     for n in only_new:
         print("only in NEW:", n)
-    print("%d kernels / functions identical, %d differ, %d only in NEW" % (same, diff, len(only_new)))
+    print("%d kernels / functions identical, %d differ, %d only in OLD, %d only in NEW" % (same, diff, lost, len(only_new)))
     return 1 if diff else 0
 
 

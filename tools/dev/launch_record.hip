@@ -1,6 +1,6 @@
 // launch_record.hip -- which kernel the sampling launchers choose, and with what launch shape, recorded on the CPU.
 //
-// Includes pc_sample.hip (or, with -DRECORD_SLICE_T, pc_slice_t.hip) with hipLaunchKernelGGL and pc_need_dyn_lds turned into
+// Includes pc_sample.hip and pc_bases.hip (or, with -DRECORD_SLICE_T, pc_slice_t.hip) with hipLaunchKernelGGL and pc_need_dyn_lds turned into
 // recorders, and walks a grid of fabricated states through the launchers: no device, no kernel runs.  Built host-only
 // (make -C polychordlite_amd/csrc launch_record); tests/test_launch_plan.py compares the digests below with those of the
 // commit before the launchers were rewritten around one plan.
@@ -102,7 +102,8 @@ struct Launcher {
 #include "pc_slice_t.hip"
 #else
 #include "pc_sample.hip"
-// what pc_sample.hip's host code calls in other files
+#include "pc_bases.hip"
+// what their host code calls in other files
 extern "C" int pc_rtc_launch(const PcState *, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t, void **) { rec::launch(expr, "", grid, block, sh); return 0; }
 // the handles of the two sweeps by src_id -- the first sweep knows 1 (the plain form) and 2 (100 terms) --: nterms, nsums, nquad, nshared
 static const PcSourceForm FORMS[] = { {}, {}, {100}, {100, 5}, {100, 8}, {5, 0, 5}, {1024, 0, 1024}, {100, 0, 0, 1}, {100, 0, 0, 512}, {65, 0, 65, 65}, {100, 5, 0, 65} };

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Registers of the run-time kernels of a device source, without a device: composes the unit pc_rtc.hip's kernel_unit() composes for a
-handle (the form's #defines, pc_sample.hip from the library's embedded text, the user's text behind its -D options), compiles it with
+handle (the form's #defines, pc_sample.hip with pc_seed.h and pc_slice_body.inc from the library's embedded text -- the evaluation kernels;
+the direction kernels of pc_bases.hip are no part of it --, the user's text behind its -D options), compiles it with
 hiprtc for gfx950 and prints, per kernel, what the code object's metadata note says: VGPRs, AGPRs, spilled vector and scalar registers,
 scratch bytes a lane.
 

@@ -1,6 +1,6 @@
 // slice_step_record.hip -- what pc_launch_slice_step (pc_sample.hip) accepts, declines and launches, checked on the CPU.
 //
-// Includes pc_sample.hip with hipLaunchKernelGGL and pc_need_dyn_lds turned into recorders, as launch_record.hip does, and walks a grid of
+// Includes pc_sample.hip (and pc_bases.hip, whose pc_nhats_splittable pc_slice_fusable asks) with hipLaunchKernelGGL and pc_need_dyn_lds turned into recorders, as launch_record.hip does, and walks a grid of
 // fabricated states through the launcher: no device, no kernel runs.  Unlike launch_record it compares with nothing recorded earlier (the
 // launcher is new): it holds every call against the launcher's rules written down a second time, here --
 //   declined (1)   nDims > 64 unfused; fused where pc_slice_fusable says no; more than one grade; the sequential stream; the correlated Gaussian
@@ -40,7 +40,8 @@ void clear() { launches.clear(); attrs.clear(); error.clear(); }
 #define pc_need_dyn_lds(...) rec::lds(#__VA_ARGS__, __VA_ARGS__)
 
 #include "pc_sample.hip"
-// what pc_sample.hip's host code calls in other files
+#include "pc_bases.hip"
+// what their host code calls in other files
 extern "C" int pc_rtc_launch(const PcState *, const char *expr, dim3 grid, dim3 block, size_t sh, hipStream_t, void **) { rec::launch(expr, grid, block, sh); return 0; }
 // (handle 1 the plain form, 2 a hundred terms, 3 a hundred terms in five sums; no quadratic form and no shared values here)
 extern "C" int pc_rtc_source_form(int id, PcSourceForm *f) { *f = PcSourceForm{}; f->nterms = id == 2 || id == 3 ? 100 : 0; f->nsums = id == 3 ? 5 : 0; return 0; }
