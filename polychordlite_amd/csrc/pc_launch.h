@@ -101,16 +101,19 @@ void pc_launch_ph_rehome(const PcState *S, int nph, int nc, const unsigned *old_
 void pc_launch_nn_lists(const PcState *S, int nleft, int use_rank, hipStream_t st);
 int pc_launch_nn_lists_many(const PcState *S, const PcManyRec *dR, int R, int nleft_max, int use_rank, hipStream_t st);
 int pc_launch_consume(const PcState *S, int final_mode, int wide, hipStream_t st);
+void pc_launch_init_state(const PcState *S, double logzero, hipStream_t st);
+// ---- pc_rows.hip -------------------------------------------------------------------------------------------
 void pc_launch_apply(const PcState *S, unsigned batch, int nchains, hipStream_t st);
 // pool mode, a run on its own, deferred update: the row kernel and, in the same launch, the workgroups of the update's flag pass over nph rows
 // (pc_upd_flag.h: keep [nph], blk [blocks of 256]), which also write the ids of the rows of the chains just consumed
 void pc_launch_apply_flag(const PcState *S, unsigned batch, int nchains, int nph, unsigned char *keep, int *blk, hipStream_t st);
 int pc_launch_apply_many(const PcState *S, const PcManyRec *dR, int R, unsigned batch, int nchains, hipStream_t st);
-// ... for R runs at once: every run its own row count (PcManyRec::ia[PC_REC_I_ROWS], blocks PC_REC_I_BLOCKS)
-int pc_launch_clean_many(const PcManyRec *dR, int R, int nblk_max, hipStream_t st);
 void pc_launch_install_live(const PcState *S, const double *rows, int n, hipStream_t st);
+// ---- pc_update_steps.hip -----------------------------------------------------------------------------------
 // phantom clean: returns nothing; *d_total (device int) receives the surviving count
 void pc_launch_clean(const PcState *S, int nph, unsigned char *keep, int *blk, int *d_total, double *ph2, double *phL2, unsigned *phC2, unsigned long long *phU2, int *dst_index, hipStream_t st);
+// ... for R runs at once: every run its own row count (PcManyRec::ia[PC_REC_I_ROWS], blocks PC_REC_I_BLOCKS)
+int pc_launch_clean_many(const PcManyRec *dR, int R, int nblk_max, hipStream_t st);
 void pc_launch_reset_thresholds(const PcState *S, hipStream_t st);
 int pc_launch_reset_thresholds_many(const PcState *S, const PcManyRec *dR, int R, hipStream_t st);
 int pc_cov_nchunk(const PcState *S, int nph);
@@ -118,7 +121,6 @@ int pc_launch_covmats(const PcState *S, int nph, int nc, double *psum, int *pcnt
 // pieces of the general update path used by the fused update of pc_update.hip
 void pc_launch_scan_blocks(int *blk, int nblk, int *total, int *total2, hipStream_t st);
 void pc_launch_chol_only(const PcState *S, const double *ncov, const int *count, hipStream_t st);
-void pc_launch_init_state(const PcState *S, double logzero, hipStream_t st);
 int pc_post_blocks(void);
 void pc_launch_post_moments(const PcState *S, int nd, double *pmax, double *part, hipStream_t st);
 // ---- pc_engine.hip -----------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ enum { PC_ERR_NONE = 0, PC_ERR_PHANTOM_CAP = 1, PC_ERR_DEAD_CAP = 2, PC_ERR_CLUS
 //   19   PC_ABL_BASES_WAVE          a run on its own, nDims <= 24, one grade: the bases a wavefront each     pc_launch.h for pc_engine.hip
 //                                   (k_nhats<.., 64, 1>), not 64 / nDims a wavefront (k_nhats_w)             (the kernels: pc_bases.hip)
 //   20   PC_ABL_BASES_WAVE1         ... k_nhats_w with one wavefront a workgroup (k_nhats_w<.., 1>), not four  pc_bases.hip
-//   30   PC_ABL_TRACE_CHOL          trace of Cholesky fallbacks                                              pc_contract.hip
+//   30   PC_ABL_TRACE_CHOL          trace of Cholesky fallbacks                                              pc_update_steps.hip
 enum { PC_ABL_FUNCTOR = 1 << 0, PC_ABL_NO_POOL = 1 << 1, PC_ABL_NO_DEFER = 1 << 2, PC_ABL_NO_FUSED_UPDATE = 1 << 3, PC_ABL_PAIR_SCANS = 1 << 4,
        PC_ABL_CONSUME_GENERAL = 1 << 5, PC_ABL_SLICE_LANE = 1 << 6, PC_ABL_BASES_PACKED = 1 << 7, PC_ABL_CL_END_AT_DEATH = 1 << 8,
        PC_ABL_KILLOFF_GENERAL = 1 << 9, PC_ABL_CONSUME_CL_SERIAL = 1 << 10, PC_ABL_RETIRED_11 = 1 << 11, PC_ABL_RETIRED_12 = 1 << 12,

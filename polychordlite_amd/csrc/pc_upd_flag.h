@@ -1,6 +1,6 @@
 // pc_upd_flag.h -- the first stage of the one-cluster update: which phantom rows survive, survivors per block of 256 rows.  Device code, shared
 // by the update's own launch (pc_update.hip: k_upd_flag, k_upd_flag_many, k_upd_flag_scan) and by the row kernel of a run on its own in pool mode
-// (pc_contract.hip: k_apply_pool_flag), whose launch carries the workgroups of this pass in front of its own.
+// (pc_rows.hip: k_apply_pool_flag), whose launch carries the workgroups of this pass in front of its own.
 #pragma once
 #include "pc_state.h"
 

@@ -5,7 +5,7 @@
 //   calculate_covmats (:601-641): mean and population covariance of live + phantom cube coordinates;
 //   calc_cholesky (utils.F90:621-649), with the scaled-identity fallback of :633-638.
 //
-// The general path (pc_contract.hip: k_clean_flag / k_scan_blocks / k_clean_scatter / k_reset_thresholds /
+// The general path (pc_update_steps.hip: k_clean_flag / k_scan_blocks / k_clean_scatter / k_reset_thresholds /
 // k_cov_mean_partial / k_fold_partials / k_cov_partial / k_fold_partials / k_cov_final_chol) is nine launches of 4 - 25 us
 // with the host's launch rate between them: ~140 us per update, 31 updates per run at the metric configuration = a fifth
 // of the run.  Here:

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): a run on its own in pool mode whose row kernel's launch carries the update's flag pass (k_apply_pool_flag, pc_contract.hip,
+"""GPU (-m gpu): a run on its own in pool mode whose row kernel's launch carries the update's flag pass (k_apply_pool_flag, pc_rows.hip,
 pc_upd_flag.h), held against the parent's path: settings.ablate bit 17, the flags by k_upd_flag in a launch of its own behind k_apply_pool.
 Only who writes the ids of a round's rows and the update's keep bytes, and in which launch, differs, so every array and counter a run returns
 is the same, byte for byte.  (The other half of the same proposal -- k_apply_pool storing the dead rows into the host's pinned mirror --

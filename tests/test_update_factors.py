@@ -4,7 +4,7 @@ Engine::do_update's non-deferred branch on given rows:
   path 1  the fused update (pc_update.hip): one-pass moments about a shift on the fp64 matrix cores (k_upd_gather<NT>, pool and compacting
           mode; k_upd_chain<NT> under settings.ablate bit 16), k_upd_fold, then upd_final_stage<8|16|24|32> below 32 dimensions,
           k_upd_final_w + k_chol_blocked<2..8> (+ k_cov_final_chol when it says chol_suspect) from 32 on;
-  path 0  the general steps (pc_contract.hip): clean, k_cov_mean_partial / k_cov_partial (plain below 32 dimensions, matrix cores from 32),
+  path 0  the general steps (pc_update_steps.hip): clean, k_cov_mean_partial / k_cov_partial (plain below 32 dimensions, matrix cores from 32),
           k_fold_partials, k_cov_final_chol in its three memory layouts (both matrices in LDS up to 101, L alone 102...143, in HBM from 144).
 
 THE REFERENCE is written out here: per cluster the mean and the centred products divided by n (population normalisation,
@@ -276,7 +276,7 @@ def test_cpu_fallbacks(D):
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
 def cov_rows(D):
-    """rows per chunk of the general covariance kernels (pc_contract.hip cov_rows: the centred tile [rows][stride] within 120 KB of LDS)"""
+    """rows per chunk of the general covariance kernels (pc_update_steps.hip cov_rows: the centred tile [rows][stride] within 120 KB of LDS)"""
     ts = ((D + 15) & ~15) + 1 if D >= 32 else D + 1
     r = 256
     while r > 8 and 8 * r * ts + 4 * r > 120 * 1024:

@@ -9,6 +9,13 @@ kernels, so that "only in OLD" means a kernel was lost, not that it moved; a nam
 A template that gained a defaulted trailing parameter keeps its instruction stream but not
 its name: `--drop-trailing-zero k_slice` compares NEW's `k_slice<..., 0>` with OLD's `k_slice<...>`.  Prints one line per kernel that
 differs or exists on one side only, then a summary; exit status 1 if a common kernel differs.
+
+Two things that change when a function gets other neighbours in its object are layout, not instructions, and are taken out of both sides
+before the comparison (normalise_layout):
+  * the run of `s_nop`s behind a function's LAST `s_endpgm` (with no `s_endpgm`, the trailing run): padding up to the alignment of whatever
+    follows.  An `s_nop` inside the body, or behind an `s_endpgm` that is not the last, is an instruction and stays.
+  * the literal of an `s_add_u32` (and of the `s_addc_u32` behind it) that directly follows an `s_getpc_b64` naming the same register pair:
+    the pc-relative distance to a constant or a function, which is where the linker put it.  Any other literal stays.
 """
 import argparse
 import os
@@ -40,7 +47,35 @@ def disassemble(obj, arch, tmp):
         ins = re.sub(r"<[^>]*>", "<sym>", ins)          # branch targets are printed as <symbol+offset>
         if ins and ins != "...":
             funcs[name].append(ins)
-    return funcs
+    return {n: normalise_layout(body) for n, body in funcs.items()}
+
+
+def normalise_layout(lines):
+    """The instruction lines of one function without what only its place in the object decides (see the module's docstring)."""
+    lines = list(lines)
+    op = [l.split()[0] for l in lines]
+    if "s_endpgm" in op:
+        first = len(op) - op[::-1].index("s_endpgm")          # behind the last s_endpgm
+        last = first
+        while last < len(op) and op[last] == "s_nop":
+            last += 1
+    else:
+        first = last = len(op)
+        while first > 0 and op[first - 1] == "s_nop":
+            first -= 1
+    del lines[first:last]
+    for i, l in enumerate(lines):
+        m = re.match(r"^s_getpc_b64 s\[(\d+):(\d+)\]$", l)
+        if not m or i + 1 >= len(lines):
+            continue
+        lo, hi = "s" + m.group(1), "s" + m.group(2)
+        a = re.match(r"^s_add_u32 %s, %s, (\S+)$" % (lo, lo), lines[i + 1])
+        if not a:
+            continue
+        lines[i + 1] = "s_add_u32 %s, %s, <pcrel>" % (lo, lo)
+        if i + 2 < len(lines) and re.match(r"^s_addc_u32 %s, %s, (\S+)$" % (hi, hi), lines[i + 2]):
+            lines[i + 2] = "s_addc_u32 %s, %s, <pcrel>" % (hi, hi)
+    return lines
 
 
 def main():
