@@ -459,6 +459,32 @@ int  pchip_source_create_sums(const char *source, const char *options, const dou
 #define PCHIP_SOURCE_MAX_RES 1024
 int  pchip_source_create_quad(const char *source, const char *options, const double *data, long ndata, long nres,
                               const double *precision /* host, nres x nres, row-major */, int with_prior);
+/* The BATCHED QUADRATIC FORM: the same Gaussian with up to PCHIP_SOURCE_MAX_RES_BATCH residuals (Pantheon+ 1701, DES-SN5YR about 1800, a
+ * joint spectrum 2000 - 3000; P is 128 MB a run at the limit), evaluated for MANY points at once on the fp64 matrix cores instead of inside
+ * the sampling kernels.  The source defines the two functions of pchip_source_create_quad, pchip_residual and pchip_logl_finish, under the
+ * same contract; `precision` is copied behind the data as there and used EXACTLY as given (not symmetrised, not transposed).  A run takes
+ * the device batch path (the one behind polychord_hip_set_device_batch_callback) with the library's own evaluator: every round the parked
+ * proposals are packed into one block on the device, the box or the prior table is evaluated on the block, and three launches answer it --
+ *   1. k_quad_residuals: R[row][i] = residual(theta_row, i), one thread per (row, i), the returned double stored as it is;
+ *   2. k_quad_chi2_mm:   Q = R P in 16 x 16 tiles by v_mfma_f64_16x16x4_f64 over i = 0, 4, 8, ...; t_j = Q[row][j] * R[row][j], one IEEE
+ *                        multiply; the sixteen t_j of a tile by a fixed butterfly; a wavefront's two tiles in ascending order: one partial
+ *                        per row and strip of 32 columns;
+ *   3. k_quad_finish:    chi2 = the row's partials added to 0.0 in ascending order, logL = finish(chi2, theta_row, phi, ...), one thread a row.
+ * A ROW'S BITS DEPEND ON THAT ROW'S RESIDUALS, ON P AND ON nres ONLY: not on the number of rows, the row's place in the block or the other
+ * rows (the split of the columns is a function of nres alone, ragged edges are zero operands, no atomics on doubles).  So pchip_source_eval
+ * of a dead point's theta gives the bits the run found, and runs in step (pchip_run_in_step: ONE evaluation a tick for the rows of all
+ * runs of a group, one device) are bit for bit their solo runs.  The order is NOT the in-kernel form's: the two agree within their
+ * rounding bounds, |chi2 - r^T P r| <= (2 nres + 4) 2^-53 sum_ij |r_i| |P_ij| |r_j| here.
+ * Runs: pchip_run / pchip_run_hooks / pchip_run_in_step with like.kind = PCHIP_LIKE_SOURCE under prior.kind 1 (the box) or 2 (a table);
+ * a host prior (kind 0) and PCHIP_PRIOR_SOURCE are refused with code 1 and a message before any device call.  path[PCHIP_PATH_DEVICE_BATCH]
+ * counts the evaluations, path[PCHIP_PATH_SOURCE_KERNELS] the launches of the two run-time kernels.  Chains per nursery default to
+ * nlive / 2 as for a device likelihood.  Not covered: pchip_maximise_device, pchip_run_repeats and pchip_slice_chains refuse the handle
+ * with a message; no handle's own prior, no shared values.  1 <= nres <= PCHIP_SOURCE_MAX_RES_BATCH, precision != NULL: -1 with the
+ * reason -- the range, the missing matrix, the compiler's log, the function the source lacks by name -- in polychord_hip_last_error(),
+ * before any device call.  pchip_source_create_quad is unchanged: its range, its defined fma order and its bits. */
+#define PCHIP_SOURCE_MAX_RES_BATCH 4096
+int  pchip_source_create_quad_batch(const char *source, const char *options, const double *data, long ndata, long nres,
+                                    const double *precision /* host, nres x nres, row-major */);
 /* SHARED VALUES: quantities that depend on theta but not on i -- a distance table on a redshift grid that every supernova interpolates,
  * spline coefficients, a model spectrum on a k-grid, rotated parameters, normalisation integrals -- computed ONCE per evaluated point by
  * the wavefront, one lane per value, instead of inside every term.  They go with each of the three wave-parallel forms above.  The source
@@ -511,7 +537,8 @@ int  pchip_source_create_prior(const char *source, const char *options, const do
 int  pchip_source_prior_eval(int handle, const double *cubes, long n, int nDims, double *thetas);
 /* A source likelihood (either form) at n points, thetas[n][nDims] -> logL[n], phi[n][nDerived] (host arrays; phi may be NULL when
  * nDerived is 0): one wavefront a point, through the evaluation code of the sampling kernels.  For tests, and for users checking their
- * source against a host version.  0, or 1 with a message in polychord_hip_last_error(), 2 no device / HIP error, 3 nDims > 256. */
+ * source against a host version.  (A batched quadratic form, pchip_source_create_quad_batch: the three launches of its runs for all n
+ * rows, the same bits as inside a run.)  0, or 1 with a message in polychord_hip_last_error(), 2 no device / HIP error, 3 nDims > 256. */
 int  pchip_source_eval(int handle, const double *thetas, long n, int nDims, int nDerived, double *logL, double *phi);
 unsigned long pchip_sizeof(const char *struct_name);
 void pchip_settings_default(pchip_settings *s, int nDims, int nDerived);

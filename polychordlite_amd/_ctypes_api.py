@@ -239,6 +239,8 @@ def load():
     lib.pchip_source_create_sums.restype = C.c_int
     lib.pchip_source_create_quad.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long, C.POINTER(C.c_double), C.c_int]
     lib.pchip_source_create_quad.restype = C.c_int
+    lib.pchip_source_create_quad_batch.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long, C.POINTER(C.c_double)]
+    lib.pchip_source_create_quad_batch.restype = C.c_int
     lib.pchip_source_create_shared.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_long, C.c_long, C.c_long, C.c_int, C.c_long,
                                                C.POINTER(C.c_double), C.c_int]
     lib.pchip_source_create_shared.restype = C.c_int
@@ -297,7 +299,7 @@ def dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def source_create(source, options=(), data=None, nterms=None, prior=False, nsums=None, residuals=None, precision=None, shared=None):
+def source_create(source, options=(), data=None, nterms=None, prior=False, nsums=None, residuals=None, precision=None, shared=None, batched=False):
     """handle of a likelihood written as HIP device source (pchip_source_create); RuntimeError with the compiler's log if it does not compile.
     nterms given: the terms form (pchip_source_create_terms) -- the source defines pchip_logl_term and pchip_logl_finish, the sum has nterms terms.
     nsums given (with nterms): several sums per evaluation (pchip_source_create_sums) -- the source defines pchip_logl_terms and
@@ -307,8 +309,15 @@ def source_create(source, options=(), data=None, nterms=None, prior=False, nsums
     shared given: that many shared values beside the form the other keywords name (pchip_source_create_shared) -- the source defines
     pchip_shared_value and its form's functions with `const double *shared` behind theta; nterms alone one sum, nsums with it several,
     residuals / precision the quadratic form.  shared=None: the calls above, unchanged.
+    batched=True (with residuals / precision): the batched quadratic form (pchip_source_create_quad_batch) -- the same two functions, up to 4096
+    residuals, evaluated for all parked proposals of a round at once on the matrix cores; no prior of its own, no shared values (ValueError
+    without residuals, or with prior / shared / nterms / nsums).  batched=False: the calls above, unchanged.
     prior=True: the source defines pchip_prior_param as well (pchip_source_create_prior; with nsums, pchip_source_create_sums' with_prior),
     for runs with prior.kind = PRIOR_SOURCE"""
+    if batched and residuals is None:
+        raise ValueError("batched=True is the batched quadratic form: it needs residuals (and precision)")
+    if batched and (prior or shared is not None or nterms is not None or nsums is not None):
+        raise ValueError("batched=True takes residuals and precision alone: no prior of its own, no shared values, no terms or sums")
     lib = load()
     d = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
     opts = " ".join(options) if not isinstance(options, str) else options
@@ -319,7 +328,9 @@ def source_create(source, options=(), data=None, nterms=None, prior=False, nsums
         p = None if precision is None else np.ascontiguousarray(precision, dtype=np.float64)
         if p is not None and n >= 1 and p.shape != (n, n):
             raise ValueError(f"precision has shape {p.shape}: the quadratic form of {n} residuals takes a 2-D array of shape ({n}, {n})")
-    if shared is not None:
+    if batched:
+        h = lib.pchip_source_create_quad_batch(*args, n, dptr(p) if p is not None and p.size else None)
+    elif shared is not None:
         h = lib.pchip_source_create_shared(*args, int(shared), 0 if nterms is None else int(nterms), 0 if nsums is None else int(nsums),
                                            0 if residuals is None else int(residuals), dptr(p) if p is not None and p.size else None, 1 if prior else 0)
     elif residuals is not None:

@@ -60,6 +60,7 @@ void halt_or_return(const std::string &msg)
 std::string source_form(const PcSourceForm &f)
 {
     const std::string shared = f.nshared > 0 ? ", " + std::to_string(f.nshared) + " shared values" : "";
+    if (f.nbatch > 0) return "batched quadratic form, " + std::to_string(f.nbatch) + " residuals";
     if (f.nquad > 0) return "quadratic form, " + std::to_string(f.nquad) + " residuals" + shared;
     if (f.nsums > 0) return "terms form, " + std::to_string(f.nterms) + " terms, " + std::to_string(f.nsums) + " sums" + shared;
     if (f.nterms > 0) return "terms form, " + std::to_string(f.nterms) + " terms" + shared;
@@ -815,6 +816,10 @@ static void c_interface_impl(
         f = std::fopen((base + "/" + root + ".properties.ini").c_str(), "w");
         if (f) { std::fprintf(f, "sampler=nested\nlabel=%s\n", root.c_str()); std::fclose(f); }
     }
+    // (a batched quadratic form keeps its blocks on the device: the box or a device table, nothing else)
+    if (src_form.nbatch > 0 && P.kind != 1 && P.kind != PCHIP_PRIOR_TABLE)
+        halt_program(("polychord_hip: device source handle " + std::to_string(source_handle) + " is a batched quadratic form (pchip_source_create_quad_batch): a host prior is refused -- "
+                      "polychord_hip_uniform_prior, or polychord_hip_table_prior with option \"device_prior\" = 1").c_str());
     if (P.kind == 0 && L.kind != PCHIP_LIKE_CALLBACK) {
         // a user prior with a built-in likelihood: evaluate both on the host (the device still proposes)
         L.kind = PCHIP_LIKE_CALLBACK; L.fn = loglikelihood;
@@ -858,7 +863,9 @@ static void c_interface_impl(
             std::printf("chains in flight when the list of clusters changes: %s\n",
                         s.epoch_discard ? "all discarded (epoch_discard = 1: the reference farm's rule, nested_sampling.F90:313)"
                                         : "only those seeded in the cluster that ended are lost (epoch_discard = 0, this engine's default; option \"epoch_discard\" = 1: the reference farm's rule)");
-        if (L.kind == PCHIP_LIKE_SOURCE)
+        if (L.kind == PCHIP_LIKE_SOURCE && src_form.nbatch > 0)
+            std::printf("likelihood: device source handle %d (%s) evaluated on the device in batches on the matrix cores\n", source_handle, source_form(src_form).c_str());
+        else if (L.kind == PCHIP_LIKE_SOURCE)
             std::printf("likelihood: device source handle %d (%s) evaluated on the device, inside the sampling kernels\n", source_handle, source_form(src_form).c_str());
         else if (batch_guard.ev)
             std::printf("likelihood: device source handle %d (%s)\nsource likelihood evaluated on the device in batches; prior on the host\n", source_handle, source_form(src_form).c_str());
@@ -877,7 +884,10 @@ static void c_interface_impl(
     if (maximise && r.nlive_final > 0) {
         // nested_sampling.F90:379: polish the best live points of the set at termination (host side, pc_maximise.hip)
         const std::string mpath = base + "/" + root + ".maximum";
-        if (L.kind == PCHIP_LIKE_SOURCE) {
+        if (L.kind == PCHIP_LIKE_SOURCE && src_form.nbatch > 0) {
+            // (not covered: the device maximiser has no in-kernel evaluation of a batched quadratic form to call; the run's results stand)
+            std::printf("polychord_hip: maximise: not covered for a batched quadratic form (pchip_source_create_quad_batch) -- %s is not written\n", mpath.c_str());
+        } else if (L.kind == PCHIP_LIKE_SOURCE) {
             // a recognised source under a device prior has no host function to polish through: the device maximiser, and its values to the file.
             // nDims > 64 or a leg without a simplex: a message and no file, the run's results stand
             pchip_maximum m{};

@@ -381,6 +381,23 @@ struct Engine {
     polychord_device_batch_fn dbatch_fn = nullptr; void *dbatch_user = nullptr;
     bool dev_batch = false; int db_flags = 0;              // db_flags bit 0: the engine evaluates the prior (box or table) on the blocks
     PcState S_pri{};                                       // ... the state k_prior_transform reads for it (nDims, the prior, the table's mask)
+    // A batched quadratic form behind the likelihood (pchip_source_create_quad_batch): the run is a device-batch run whose callback is the
+    // library's own evaluator, quad_batch_call -- three launches for the rows of a tick (pc_launch_quad_batch).  qb_nres > 0 says so; S_qb is
+    // the source state the two run-time kernels are launched with (the handle, its block on this device), qb_R / qb_part the scratch for
+    // qb_rows rows: a longer block is evaluated slab by slab (a row's bits do not depend on the cut)
+    int qb_nres = 0; PcState S_qb{}; double *qb_R = nullptr, *qb_part = nullptr; long qb_rows = 0;
+    static double quad_batch_no_host(double *, int, double *, int) { return -1.7976931348623157e308; }      // (callback mode's scalar function: never reached on the device batch path)
+    static int quad_batch_call(void *user, int n, int, int, const double *, double *theta, double *phi, double *logL, int, void *stream)
+    {
+        Engine *e = (Engine *)user;
+        const int nDer = e->S_qb.nDer;
+        for (long at = 0; at < n; at += e->qb_rows) {
+            const int m = (int)std::min<long>(e->qb_rows, n - at);
+            if (pc_launch_quad_batch(&e->S_qb, e->qb_nres, m, theta + (size_t)at * e->S_qb.D, logL + at, phi + (size_t)at * nDer, e->qb_R, e->qb_part, (hipStream_t)stream))
+                engine_fail(PC_RC_SETTINGS, "the batched quadratic form could not be evaluated: %.400s", pc_rtc_error() ? pc_rtc_error() : "no such launch");
+        }
+        return 0;
+    }
     double *db_cube = nullptr, *db_theta = nullptr, *db_phi = nullptr, *db_logL = nullptr;
     int *db_rank = nullptr, *db_count = nullptr, *hp_count = nullptr, *hp_count_dev = nullptr;
     // ... in step with other runs (TickGroup, pc_tick.h): the four blocks are the group's ONE block, a tick is written down and the run yields;
@@ -459,10 +476,15 @@ struct Engine {
         std::memcpy(h, src, bytes);
         HIPCHK(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, st));
     }
-    void setup(const pchip_settings &c, const pchip_like &like, const pchip_prior &prior)
+    void setup(const pchip_settings &c, const pchip_like &like_in, const pchip_prior &prior)
     {
         cfg = c;
         { std::lock_guard<std::mutex> g(g_cb_mutex); batch_fn = g_batch_fn; batch_user = g_batch_user; dbatch_fn = g_dbatch_fn; dbatch_user = g_dbatch_user; }
+        // a batched quadratic form: to everything below a callback likelihood behind a device batch callback -- the library's own, whatever
+        // the caller has registered
+        pchip_like like = like_in;
+        if (const char *why = pc_quad_batch_refusal("pchip_run", &like_in, &prior, &qb_nres)) { pc_abi_set_last_error(why); engine_fail(PC_RC_SETTINGS, "%s", why); }
+        if (qb_nres > 0) { like.kind = PC_LIKE_CALLBACK; like.fn = quad_batch_no_host; batch_fn = nullptr; batch_user = nullptr; dbatch_fn = quad_batch_call; dbatch_user = this; }
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
             engine_fail(PC_RC_DEVICE, "no HIP device available -- this engine has no CPU path");
@@ -522,7 +544,7 @@ struct Engine {
         // are spent on spawns that fail -- cheap for a compiled likelihood (then the round trips per nursery dominate and
         // many chains per nursery pay: nlive / 2), dear for an expensive one (nlive / 4, at most 64).  Which one this is
         // is measured while the live points are generated; buffers are sized for the larger choice.
-        cb_auto_batch = c.batch <= 0 && !c.sequential_rng && (like.kind == PC_LIKE_CALLBACK || (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE && prior.kind != PCHIP_PRIOR_SOURCE));
+        cb_auto_batch = c.batch <= 0 && !c.sequential_rng && qb_nres == 0 && (like.kind == PC_LIKE_CALLBACK || (prior.kind != 1 && prior.kind != PCHIP_PRIOR_TABLE && prior.kind != PCHIP_PRIOR_SOURCE));
         if (cb_auto_batch) B_small = std::max(1, std::min(64, c.nlive / 4));
         S.B = B;
         S.maxc = c.do_clustering ? std::max(2, g_cap_clusters.load()) : 4;
@@ -566,6 +588,15 @@ struct Engine {
             src_terms = f.nterms > 0;
             // (a quadratic form: its precision matrix goes up behind the user's data, in the same block -- the kernels find it at src_data + src_ndata)
             if (!hold->empty()) { d_src = blocks.dev<double>(hold->size()); upload(d_src, hold->data(), sizeof(double) * hold->size()); S.src_data = d_src; S.src_ndata = f.ndata; }
+        }
+        if (qb_nres > 0) {      // the batched quadratic form: its block (the matrix behind the user's data) goes up like any handle's, for the evaluator's state
+            PcSourceForm f;
+            const auto hold = pc_rtc_source_hold(like_in.source, &f);
+            if (!hold) engine_fail(PC_RC_SETTINGS, "device source handle %d does not exist", like_in.source);
+            if (nDer > PC_SRC_MAX_DERIVED) engine_fail(PC_RC_SETTINGS, "a device source likelihood writes at most %d derived parameters, not %d", PC_SRC_MAX_DERIVED, nDer);
+            d_src = blocks.dev<double>(hold->size()); upload(d_src, hold->data(), sizeof(double) * hold->size());
+            std::memset(&S_qb, 0, sizeof(S_qb));
+            S_qb.D = D; S_qb.nDer = nDer; S_qb.like.kind = PC_LIKE_SOURCE; S_qb.src_id = like_in.source; S_qb.src_data = d_src; S_qb.src_ndata = f.ndata;
         }
         // a source prior is the handle's own function, inside the sampling kernels: there is no host function for callback mode to call
         if (prior.kind == PCHIP_PRIOR_SOURCE && like.kind != PC_LIKE_SOURCE)
@@ -632,8 +663,10 @@ struct Engine {
                 S_pri.prior.kind = PCHIP_PRIOR_TABLE; S_pri.prior.lo = d_lo; S_pri.prior.hi = d_hi; S_pri.src_pad = (int)ptab.mask; db_flags = 1;
             }
             if (db_flags && D > 256) engine_fail(PC_RC_NDIMS, "the device batch callback under a device prior (box or table): nDims <= 256, not %d", D);
+            if (qb_nres > 0 && !db_flags) engine_fail(PC_RC_SETTINGS, "a batched quadratic form needs the uniform box or a prior table (prior.kind 1 or 2), not prior.kind = %d", prior.kind);
             if (c.feedback >= 1) {
-                std::printf("likelihood evaluated on the device in batches through the caller's device callback; prior %s\n", db_flags ? "on the device" : "by the callback");
+                if (qb_nres > 0) std::printf("likelihood: batched quadratic form of %d residuals (device source handle %d), evaluated in batches on the matrix cores, three launches a round; prior on the device\n", qb_nres, like_in.source);
+                else std::printf("likelihood evaluated on the device in batches through the caller's device callback; prior %s\n", db_flags ? "on the device" : "by the callback");
                 std::fflush(stdout);
             }
         }
@@ -704,6 +737,10 @@ struct Engine {
                 const size_t cap = (size_t)std::max(B, nprior);
                 db_cube = blocks.dev<double>(cap * D); db_theta = blocks.dev<double>(cap * D); db_phi = blocks.dev<double>(cap * std::max(1, nDer));
                 db_logL = blocks.dev<double>(cap); db_rank = blocks.dev<int>(B); db_count = blocks.dev<int>(1);
+                if (qb_nres > 0) {      // the evaluator's scratch: residuals [rows][ldr], partial sums [rows][ncb]
+                    qb_rows = pc_quad_mm_rows((long)std::min<size_t>(cap, PC_QUAD_BATCH_SLAB));
+                    qb_R = blocks.dev<double>((size_t)qb_rows * pc_quad_mm_ldr(qb_nres)); qb_part = blocks.dev<double>((size_t)qb_rows * pc_quad_mm_ncb(qb_nres));
+                }
                 hp_count = blocks.pin<int>(1); *hp_count = 0;
                 { void *dp = nullptr; HIPCHK(hipHostGetDevicePointer(&dp, hp_count, 0)); hp_count_dev = (int *)dp; }
                 HIPCHK(hipMemsetAsync(db_rank, 0xFF, sizeof(int) * B, st));
@@ -1371,7 +1408,11 @@ struct Engine {
         if (db_flags && pc_launch_prior_transform(&S_pri, n, db_cube, db_theta, st)) engine_fail(PC_RC_NDIMS, "the device prior of the batch callback could not be launched (nDims = %d)", S.D);
         if (dbatch_fn(dbatch_user, n, S.D, S.nDer, db_cube, db_theta, db_phi, db_logL, db_flags, (void *)st) != 0) stop.store(1);
     }
-    void tick_answered(int n) { path[PCHIP_PATH_DEVICE_BATCH]++; cb_evals += n; }
+    void tick_answered(int n)
+    {
+        path[PCHIP_PATH_DEVICE_BATCH]++; cb_evals += n;
+        if (qb_nres > 0) path[PCHIP_PATH_SOURCE_KERNELS] += 2 * (long)((n + qb_rows - 1) / qb_rows);      // (k_quad_residuals and k_quad_finish of every slab)
+    }
     // the group's block in place of the run's own four (which served the live points, and go back now: the stream is idle behind begin())
     void tick_bind(double *cube, double *theta, double *phi, double *logL)
     {
@@ -2371,6 +2412,8 @@ int pchip_run_hooks(const pchip_settings *s, const pchip_like *like, const pchip
     if (s->num_repeats < 1) { std::fprintf(stderr, "polychord_hip: You need to set num_repeats. Suggestion: 5*nDims\n"); return 1; } // settings.f90:216
     if (s->num_repeats > 64 * PC_MASK_WORDS) { std::fprintf(stderr, "polychord_hip: num_repeats > %d unsupported\n", 64 * PC_MASK_WORDS); return 1; }
     if (like->kind == PC_LIKE_CALLBACK && !like->fn) { std::fprintf(stderr, "polychord_hip: callback likelihood without a function pointer\n"); return 1; }
+    // (a batched quadratic form under a host prior or a source prior: refused before any device call)
+    if (const char *why = pc_quad_batch_refusal("pchip_run", like, prior, nullptr)) { std::fprintf(stderr, "polychord_hip: %s\n", why); pc_abi_set_last_error(why); std::memset(out, 0, sizeof(*out)); return 1; }
     using clk = std::chrono::steady_clock;
     auto t0 = clk::now();
     std::memset(out, 0, sizeof(*out));
@@ -2425,6 +2468,7 @@ int pchip_slice_chains(const pchip_settings *s, const pchip_like *like, const pc
 {
     if (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & PC_ABL_RTC_BUILTINS)) {
         std::fprintf(stderr, "polychord_hip: pchip_slice_chains does not take a device source likelihood (or settings.ablate bit 15)\n");
+        if (const char *why = pc_quad_batch_refusal("pchip_slice_chains", like, prior, nullptr)) pc_abi_set_last_error(why);
         return 1;
     }
     pchip_settings c = *s;
@@ -3124,6 +3168,8 @@ static int maximise_device_core(const pchip_settings *s, const pchip_like *like,
         pc_abi_set_last_error("pchip_maximise_device: a host callback likelihood or a host prior (kind 0) has no device code -- pchip_maximise / pchip_maximise_values polish through the host functions");
         return 1;
     }
+    // (a batched quadratic form has no in-kernel evaluation for k_maximise to call: not covered)
+    if (const char *why = pc_quad_batch_refusal("pchip_maximise_device", like, prior, nullptr)) { pc_abi_set_last_error(why); return 1; }
     const int D = s->nDims, nDer = s->nDerived, nT = 2 * D + nDer + 2, nv = D + 1;
     for (int r = 0; r < nruns; ++r)
         if (!live[r] || !cluster[r] || nlive[r] < 1) { pc_abi_set_last_error("pchip_maximise_device: every run needs its live rows, their clusters and nlive >= 1"); return 1; }

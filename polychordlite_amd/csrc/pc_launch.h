@@ -20,6 +20,8 @@ struct PcSourceForm {
     int has_prior;                         // the source defines pchip_prior_param as well (pchip_source_create_prior)
     long long ndata, ntail;                // the user's doubles, and the handle's own behind them in its block (a quadratic form's matrix)
     int alive;                             // 0: destroyed -- the launch shapes below still hold for a run in flight, nothing new starts on it
+    int nbatch;                            // > 0: the BATCHED quadratic form of that many residuals (pchip_source_create_quad_batch, pc_quad_mm.hip): no
+                                           // in-kernel evaluation -- nterms == nquad == 0, the LDS helpers below answer 0 --, its matrix in ntail as well
 };
 
 // A quadratic-form source keeps the residuals of the point -- of the two ends of a bracket -- in two blocks of nres doubles (an even
@@ -175,6 +177,27 @@ const char *pc_rtc_error(void);
 // the form of handle `id` in *f (zeroed first): one lock, one lookup.  0, or non-zero for an id that never existed; a destroyed handle
 // answers what it answered alive, with alive = 0
 int pc_rtc_source_form(int id, PcSourceForm *f);
+// ---- pc_quad_mm.hip ----------------------------------------------------------------------------------------
+// The batched quadratic form (pchip_source_create_quad_batch): chi2 of n rows at once on the matrix cores, between the two run-time kernels
+// that call the user's functions (k_quad_residuals, k_quad_finish: pc_sample.hip under PCHIP_USER_QUAD_BATCH).  All sizes are functions of
+// nres alone: ldr, the leading dimension of the residual block (nres rounded up to 16); ncb, the partial sums a row (one per wavefront's
+// strip of 32 columns).  Rows come in blocks of PC_QUAD_MM_ROWS: the scratch holds pc_quad_mm_rows(n) of them, padding rows zero.
+#define PC_QUAD_MM_ROWS 64
+static inline int pc_quad_mm_ldr(int nres) { return (nres + 15) & ~15; }
+static inline int pc_quad_mm_ncb(int nres) { return 4 * ((nres + 127) / 128); }
+static inline long pc_quad_mm_rows(long n) { return (n + PC_QUAD_MM_ROWS - 1) / PC_QUAD_MM_ROWS * PC_QUAD_MM_ROWS; }
+// the most rows one evaluation takes (the callers cut longer blocks into slabs: a row's bits do not depend on the cut); R is 256 MB at the
+// largest nres then
+#define PC_QUAD_BATCH_SLAB 8192
+// k_quad_chi2_mm: R [pc_quad_mm_rows(n)][ldr] (device), P [nres][nres] row-major exactly as given, part [pc_quad_mm_rows(n)][ncb].  1: not launched
+int pc_launch_quad_chi2_mm(int n, int nres, const double *R, const double *P, double *part, hipStream_t st);
+// the whole evaluation of n rows (device pointers; S: a source state of the handle -- like.kind, src_id, src_data, src_ndata, D, nDer):
+// residuals, chi2, finish, three launches on `st`; R / part: scratch for pc_quad_mm_rows(n) rows.  1: not launched (pc_rtc_error, or the
+// text behind pchip_last_error)
+int pc_launch_quad_batch(const PcState *S, int nres, int n, const double *thetas, double *logL, double *phi, double *R, double *part, hipStream_t st);
+// why a likelihood / prior pair is refused where a batched handle is involved (NULL: it is not, or the likelihood is no batched handle);
+// `who`: the entry point's name.  *nres (may be NULL): the handle's residuals, 0 for any other likelihood.  Before any device call
+const char *pc_quad_batch_refusal(const char *who, const pchip_like *like, const pchip_prior *prior, int *nres);
 // ---- pc_bases.hip ------------------------------------------------------------------------------------------
 // The launchers of the direction kernels (static kernels only): 0: launched; 1: not this way (no kernel for this shape).
 // the split launch (see k_nhats): part 1 = bases, part 2 = seeds + whitening; 1 where it exists (else only the whole kernel: pc_launch_nhats)

@@ -774,15 +774,19 @@ static int run_repeats_body(const pchip_settings *s, const pchip_like *like, con
         if (!like || !prior) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step needs a likelihood and a prior\n"); return 1; }
         // a callback likelihood goes in step through the caller's DEVICE batch callback alone (polychord_hip_set_device_batch_callback,
         // registered now): one call a tick for the rows of all runs of a group, on this thread
-        device_cb = like->kind == PCHIP_LIKE_CALLBACK && pc_device_batch_registered() != 0;
+        // ... and so does a batched quadratic form (pchip_source_create_quad_batch), through the library's own evaluator: one evaluation a tick
+        int qb_nres = 0;
+        if (const char *why = pc_quad_batch_refusal("pchip_run_in_step", like, prior, &qb_nres)) { std::fprintf(stderr, "polychord_hip: %s\n", why); pc_abi_set_last_error(why); return 1; }
+        const bool batched = qb_nres > 0;
+        device_cb = batched || (like->kind == PCHIP_LIKE_CALLBACK && pc_device_batch_registered() != 0);
         if (like->kind == PCHIP_LIKE_CALLBACK && !device_cb) {
             std::fprintf(stderr, "polychord_hip: pchip_run_in_step does not take a host callback likelihood: the runs in step share their kernel launches, and a callback belongs to its caller's thread -- pchip_run_repeats runs those one thread per run\n");
             return 1;
         }
         if (device_cb) {
-            if (!like->fn) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step: a callback likelihood needs like.fn even where the device batch callback evaluates it\n"); return 1; }
-            if (ndevices > 1) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step takes a device batch callback on one device only (ndevices = %d): the caller's function is called on the calling thread, one group at a time\n", ndevices); return 1; }
-            if (prior->kind == PCHIP_PRIOR_SOURCE) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step: prior.kind = 3 (source prior) needs a device source likelihood of the same handle, not a callback\n"); return 1; }
+            if (!batched && !like->fn) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step: a callback likelihood needs like.fn even where the device batch callback evaluates it\n"); return 1; }
+            if (ndevices > 1) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step takes a device batch callback, or a batched quadratic form, on one device only (ndevices = %d): the evaluation is called on the calling thread, one group at a time\n", ndevices); return 1; }
+            if (!batched && prior->kind == PCHIP_PRIOR_SOURCE) { std::fprintf(stderr, "polychord_hip: pchip_run_in_step: prior.kind = 3 (source prior) needs a device source likelihood of the same handle, not a callback\n"); return 1; }
         }
         // (under the device batch callback a callback prior is the callee's own work on the device: no host function is called by a run in step)
         else if (prior->kind != 1 && prior->kind != PCHIP_PRIOR_TABLE && prior->kind != PCHIP_PRIOR_SOURCE) {
@@ -793,6 +797,7 @@ static int run_repeats_body(const pchip_settings *s, const pchip_like *like, con
     else if (like && (like->kind == PCHIP_LIKE_SOURCE || (s->ablate & PC_ABL_RTC_BUILTINS))) {
         // (this door's refusal is pinned by its tests: a source handle goes in step through pchip_run_in_step)
         std::fprintf(stderr, "polychord_hip: pchip_run_repeats does not take a device source likelihood (or settings.ablate bit 15) yet: run the seeds one by one with pchip_run\n");
+        if (const char *why = pc_quad_batch_refusal("pchip_run_repeats", like, prior, nullptr)) pc_abi_set_last_error(why);
         return 1;
     }
     int ndev_all = 0;

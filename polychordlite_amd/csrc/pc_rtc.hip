@@ -25,6 +25,11 @@
 // unit gets PCHIP_USER_QUAD in front beside the two #defines of the terms form: pc_sample.hip's walk over the matrix is compiled in
 // their place only.
 //
+// The BATCHED quadratic form (pchip_source_create_quad_batch): the same two functions and the same block (the matrix behind the data), up to
+// PCHIP_SOURCE_MAX_RES_BATCH residuals, and NO in-kernel evaluation: a round's parked proposals are evaluated together, three launches a
+// tick, chi2 on the matrix cores (pc_quad_mm.hip).  Its form has nterms == nquad == 0 and nbatch = nres; its unit gets PCHIP_USER_QUAD_BATCH and
+// PCHIP_SRC_NRES in front, under which pc_sample.hip compiles k_quad_residuals and k_quad_finish -- the only kernels its module is asked for.
+//
 // Shared values (pchip_source_create_shared): the source defines pchip_shared_value (the k-th of nshared values of theta that do not depend
 // on i, one lane per k, once per evaluated point) and the functions of its form -- terms, sums or quadratic -- as overloads with `const
 // double *shared` behind theta.  Such a handle is what its form is to everybody who asks, and its unit gets PCHIP_USER_SHARED and
@@ -34,7 +39,7 @@
 // parameter) next to the likelihood of either form; such a handle's unit gets PCHIP_USER_PRIOR in front, and a run with prior.kind =
 // PCHIP_PRIOR_SOURCE takes the table's kernel variants with that function behind the transform's one entry point (pc_sample.hip).
 //
-// What a handle is stands in ONE record, its PcSourceForm (pc_launch.h): the six pchip_source_create* doors fill it through one creation
+// What a handle is stands in ONE record, its PcSourceForm (pc_launch.h): the seven pchip_source_create* doors fill it through one creation
 // path (pc_rtc_source_create; one ladder of refusals, spec_refusal), the unit of the kernels and the probe unit of the quick compile are
 // generated from it, and everybody else -- the launchers for their LDS, the engine, the doors -- reads it with pc_rtc_source_form, once.
 // pchip_source_destroy releases the text and the data and leaves the form, alive = 0: launch shapes stay right for a run in flight, and
@@ -198,6 +203,7 @@ std::string kernel_unit(const Source *s)
     if (!s) return "#include \"pc_sample.hip\"\n";
     const PcSourceForm &f = s->form;
     std::string u = f.has_prior ? "#define PCHIP_USER_PRIOR 1\n" : "";
+    if (f.nbatch > 0) u += "#define PCHIP_USER_QUAD_BATCH 1\n#define PCHIP_SRC_NRES " + std::to_string(f.nbatch) + "L\n";
     if (f.nterms > 0) {
         if (f.nsums > 0) u += "#define PCHIP_USER_SUMS 1\n#define PCHIP_SRC_NSUMS " + std::to_string(f.nsums) + "\n";
         if (f.nquad > 0) u += "#define PCHIP_USER_QUAD 1\n";
@@ -220,7 +226,11 @@ std::string probe_unit(const PcSourceForm &f)
         decl += "__device__ double pchip_shared_value(const double *theta, int nDims, " + D + ", long k);\n";
         body += "double sh[2]; sh[0] = pchip_shared_value(th, nDims, data, ndata, i); ";
     }
-    if (f.nterms <= 0) {
+    if (f.nbatch > 0) {                          // (the batched quadratic form: the quadratic form's two functions, never with shared values)
+        decl += "__device__ double pchip_residual(const double *theta, int nDims, " + D + ", long i);\n"
+                "__device__ double pchip_logl_finish(double chi2, const double *theta, double *phi, int nDims, int nDerived, " + D + ");\n";
+        body += "out[0] = pchip_logl_finish(pchip_residual(th, nDims, data, ndata, i), th, phi, nDims, nDerived, data, ndata);";
+    } else if (f.nterms <= 0) {
         decl += "__device__ double pchip_loglikelihood(const double *theta, double *phi, int nDims, int nDerived, " + D + ");\n";
         body += "out[0] = pchip_loglikelihood(th, phi, nDims, nDerived, data, ndata);";
     } else if (f.nsums > 0) {
@@ -359,9 +369,9 @@ std::shared_ptr<const std::vector<double>> pc_rtc_source_hold(int id, PcSourceFo
 // ---- C engine API ---------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// what one of the six pchip_source_create* doors was asked for: the door, the text, the data, and the fields of the form it takes
+// what one of the seven pchip_source_create* doors was asked for: the door, the text, the data, and the fields of the form it takes
 struct PcSourceSpec {
-    enum Door { PLAIN, TERMS, PRIOR, SUMS, QUAD, SHARED } door;
+    enum Door { PLAIN, TERMS, PRIOR, SUMS, QUAD, SHARED, QUAD_BATCH } door;
     const char *source, *options; const double *data; long ndata;
     long nterms = 0; int nsums = 0; long nres = 0; const double *precision = nullptr; long nshared = 0; bool prior = false;
 };
@@ -370,7 +380,7 @@ struct PcSourceSpec {
 std::string spec_refusal(const PcSourceSpec &c, std::string *defs)
 {
     static const char *const names[] = { "pchip_source_create", "pchip_source_create_terms", "pchip_source_create_prior", "pchip_source_create_sums",
-                                         "pchip_source_create_quad", "pchip_source_create_shared" };
+                                         "pchip_source_create_quad", "pchip_source_create_shared", "pchip_source_create_quad_batch" };
     const std::string me = std::string(names[c.door]) + ": ";
     auto says = [&](const char *field, long v, const std::string &rule) { return me + field + " = " + std::to_string(v) + " -- " + rule; };
     const std::string sums_range = "1 <= nsums <= " + std::to_string(PCHIP_SOURCE_MAX_SUMS) + " (PCHIP_SOURCE_MAX_SUMS)";
@@ -383,6 +393,9 @@ std::string spec_refusal(const PcSourceSpec &c, std::string *defs)
     if (d == PcSourceSpec::SUMS && (c.nsums < 1 || c.nsums > PCHIP_SOURCE_MAX_SUMS)) return says("nsums", c.nsums, sums_range);
     if (d == PcSourceSpec::QUAD && (c.nres < 1 || c.nres > PCHIP_SOURCE_MAX_RES)) return says("nres", c.nres, res_range);
     if (d == PcSourceSpec::QUAD && !c.precision) return no_matrix;
+    if (d == PcSourceSpec::QUAD_BATCH && (c.nres < 1 || c.nres > PCHIP_SOURCE_MAX_RES_BATCH))
+        return says("nres", c.nres, "1 <= nres <= " + std::to_string(PCHIP_SOURCE_MAX_RES_BATCH) + " (PCHIP_SOURCE_MAX_RES_BATCH)");
+    if (d == PcSourceSpec::QUAD_BATCH && !c.precision) return no_matrix;
     if (d == PcSourceSpec::SHARED) {      // beside one of the three wave-parallel forms: nres > 0 the quadratic form, else nterms >= 1 terms in one sum (nsums == 0) or in nsums
         if (c.nshared < 1 || c.nshared > PCHIP_SOURCE_MAX_SHARED)
             return says("nshared", c.nshared, "1 <= nshared <= " + std::to_string(PCHIP_SOURCE_MAX_SHARED) + " (PCHIP_SOURCE_MAX_SHARED)");
@@ -404,9 +417,9 @@ std::string spec_refusal(const PcSourceSpec &c, std::string *defs)
     return "";
 }
 
-// pchip_source_create[_terms | _prior | _sums | _quad | _shared]: checks the spec, compiles the user's functions alone (a syntax error surfaces
+// pchip_source_create[_terms | _prior | _sums | _quad | _shared | _quad_batch]: checks the spec, compiles the user's functions alone (a syntax error surfaces
 // here, with the compiler's log) and registers the handle.  A quadratic form (nres > 0) is a terms handle of nres terms whose matrix is copied
-// behind the data.  Returns the handle (> 0), or -1 with the reason behind pchip_last_error.
+// behind the data; the batched quadratic form keeps the matrix in the same place and is no terms handle.  Returns the handle (> 0), or -1 with the reason behind pchip_last_error.
 int pc_rtc_source_create(const PcSourceSpec &c)
 {
     std::string defs, log = spec_refusal(c, &defs);
@@ -414,7 +427,9 @@ int pc_rtc_source_create(const PcSourceSpec &c)
     if (log.empty()) {
         auto s = std::make_shared<Source>();
         PcSourceForm &f = s->form;
-        f.nterms = c.nres > 0 ? c.nres : c.nterms; f.nsums = c.nsums; f.nquad = c.nres; f.nshared = c.nshared; f.has_prior = c.prior;
+        const bool batched = c.door == PcSourceSpec::QUAD_BATCH;
+        f.nterms = batched ? 0 : (c.nres > 0 ? c.nres : c.nterms); f.nsums = c.nsums; f.nquad = batched ? 0 : c.nres; f.nshared = c.nshared; f.has_prior = c.prior;
+        f.nbatch = batched ? (int)c.nres : 0;
         f.ndata = c.ndata; f.ntail = (long long)c.nres * c.nres; f.alive = 1;
         s->text = defs + "#line 1\n" + c.source;
         std::vector<double> block;
@@ -441,7 +456,7 @@ int pc_rtc_source_create(const PcSourceSpec &c)
 
 }  // namespace
 
-// the six doors (the spec's fields in order: door, source, options, data, ndata, nterms, nsums, nres, precision, nshared, prior).  _prior:
+// the seven doors (the spec's fields in order: door, source, options, data, ndata, nterms, nsums, nres, precision, nshared, prior).  _prior:
 // nterms == 0 the plain form of likelihood, nterms >= 1 the terms form; with_prior: pchip_prior_param in the same source
 extern "C" int pchip_source_create(const char *source, const char *options, const double *data, long ndata) { return pc_rtc_source_create({ PcSourceSpec::PLAIN, source, options, data, ndata }); }
 extern "C" int pchip_source_create_terms(const char *source, const char *options, const double *data, long ndata, long nterms) { return pc_rtc_source_create({ PcSourceSpec::TERMS, source, options, data, ndata, nterms }); }
@@ -457,6 +472,10 @@ extern "C" int pchip_source_create_quad(const char *source, const char *options,
                                         int with_prior)
 {
     return pc_rtc_source_create({ PcSourceSpec::QUAD, source, options, data, ndata, 0, 0, nres, precision, 0, with_prior != 0 });
+}
+extern "C" int pchip_source_create_quad_batch(const char *source, const char *options, const double *data, long ndata, long nres, const double *precision)
+{
+    return pc_rtc_source_create({ PcSourceSpec::QUAD_BATCH, source, options, data, ndata, 0, 0, nres, precision, 0, false });
 }
 extern "C" int pchip_source_create_shared(const char *source, const char *options, const double *data, long ndata, long nshared, long nterms, int nsums,
                                           long nres, const double *precision, int with_prior)

@@ -798,6 +798,40 @@ __global__ __launch_bounds__(64) void k_source_eval(PcState S, const double *the
 }
 #endif
 
+#ifdef PCHIP_USER_QUAD_BATCH
+// The batched quadratic form (pchip_source_create_quad_batch; pc_rtc.hip puts PCHIP_USER_QUAD_BATCH and PCHIP_SRC_NRES in front of this text
+// in such a handle's unit, beside PCHIP_USER_SOURCE and nothing else): the handle has NO in-kernel evaluation -- no sampling kernel is ever
+// instantiated from its unit -- and the two kernels below are all its module is asked for.  They stand around pc_quad_mm.hip's
+// k_quad_chi2_mm, which forms chi2 = r^T P r of all rows of a block on the matrix cores (the contract and the order: there).
+__device__ double pchip_residual(const double *theta, int nDims, const double *data, long ndata, long i);
+__device__ double pchip_logl_finish(double chi2, const double *theta, double *phi, int nDims, int nDerived, const double *data, long ndata);
+// one thread per (row, i), i fastest: R[row][i] = pchip_residual(theta_row, i), the returned double as it is, into a block of leading
+// dimension ldr = nres rounded up to 16 and of n rounded up to 64 rows; zeros in the padding columns and the padding rows
+__global__ __launch_bounds__(256) void k_quad_residuals(PcState S, int n, const double *thetas /* [n][D] */, double *R /* [rows][ldr] */)
+{
+    constexpr long N = (long)(PCHIP_SRC_NRES), LDR = (N + 15) & ~15L;
+    const long rows = ((long)n + 63) / 64 * 64;
+    const long cell = (long)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= rows * LDR) return;
+    const long row = cell / LDR, i = cell - row * LDR;
+    R[cell] = (row < n && i < N) ? pchip_residual(thetas + (size_t)row * S.D, S.D, S.src_data, (long)S.src_ndata, i) : 0.0;
+}
+// one thread per row: chi2 = the row's ncb partials added to 0.0 in ascending order, logL = pchip_logl_finish(chi2, theta_row, ...), the
+// derived parameters it wrote to phi[row][nDer]
+__global__ __launch_bounds__(64) void k_quad_finish(PcState S, int n, const double *thetas /* [n][D] */, const double *part /* [rows][ncb] */, int ncb,
+                                                    double *logL /* [n] */, double *phi /* [n][nDer] */)
+{
+    const long row = (long)blockIdx.x * 64 + threadIdx.x;
+    if (row >= n) return;
+    double chi2 = 0.0;
+    for (int c = 0; c < ncb; ++c) chi2 = chi2 + part[(size_t)row * ncb + c];
+    double ph[PC_SRC_MAX_DERIVED];
+    const double l = pchip_logl_finish(chi2, thetas + (size_t)row * S.D, ph, S.D, S.nDer, S.src_data, (long)S.src_ndata);
+    for (int e = 0; e < S.nDer; ++e) phi[(size_t)row * S.nDer + e] = ph[e];
+    logL[row] = l;
+}
+#endif
+
 // ------------------------------------------------------------------------------------------
 // The device maximiser (pchip_maximise_device): `maximise = T` for a problem that lives wholly on the device.  Restates dXdtheta
 // (maximiser.F90:179-207), nelder_mead (nelder_mead.f90:7-83) and calculate_point (calculate.f90:6-50) as pc_maximise.hip does on the

@@ -89,20 +89,47 @@ int pchip_source_eval(int handle, const double *thetas, long n, int nDims, int n
     if (nDerived > PC_SRC_MAX_DERIVED) { pc_abi_set_last_error(("pchip_source_eval: a device source likelihood writes at most " + std::to_string(PC_SRC_MAX_DERIVED) + " derived parameters").c_str()); return 1; }
     if (nDims > 256) return 3;
     if (no_device()) return 2;
-    double *d_t = nullptr, *d_l = nullptr, *d_p = nullptr;
+    double *d_t = nullptr, *d_l = nullptr, *d_p = nullptr, *d_R = nullptr, *d_part = nullptr;
     const size_t nt = sizeof(double) * (size_t)n * nDims, np = sizeof(double) * (size_t)n * (nDerived > 0 ? nDerived : 1);
     int rc = 2;
     pc_abi_set_last_error(nullptr);
-    if (B.upload(nullptr) && hipMalloc(&d_t, nt) == hipSuccess && hipMalloc(&d_l, sizeof(double) * (size_t)n) == hipSuccess && hipMalloc(&d_p, np) == hipSuccess &&
+    // (the batched quadratic form: the evaluator of its runs, slab by slab -- scratch for the residuals and the partial sums of a slab)
+    const int nres = B.form.nbatch;
+    const long slab = std::min<long>(n, PC_QUAD_BATCH_SLAB), srows = pc_quad_mm_rows(slab);
+    const bool scratch = nres <= 0 || (hipMalloc(&d_R, sizeof(double) * (size_t)srows * pc_quad_mm_ldr(nres)) == hipSuccess &&
+                                       hipMalloc(&d_part, sizeof(double) * (size_t)srows * pc_quad_mm_ncb(nres)) == hipSuccess);
+    if (scratch && B.upload(nullptr) && hipMalloc(&d_t, nt) == hipSuccess && hipMalloc(&d_l, sizeof(double) * (size_t)n) == hipSuccess && hipMalloc(&d_p, np) == hipSuccess &&
         hipMemcpy(d_t, thetas, nt, hipMemcpyHostToDevice) == hipSuccess) {
         const PcState S = B.state(handle, nDims, nDerived);
-        if (pc_launch_source_eval(&S, (int)n, d_t, d_l, d_p, nullptr)) { rc = 1; pc_abi_set_last_error(pc_rtc_error() ? pc_rtc_error() : "pchip_source_eval: the launch failed"); }
+        int failed = 0;
+        if (nres > 0) {
+            for (long at = 0; at < n && !failed; at += slab)
+                failed = pc_launch_quad_batch(&S, nres, (int)std::min(slab, n - at), d_t + (size_t)at * nDims, d_l + at, d_p + (size_t)at * nDerived, d_R, d_part, nullptr);
+        } else failed = pc_launch_source_eval(&S, (int)n, d_t, d_l, d_p, nullptr);
+        if (failed) { rc = 1; pc_abi_set_last_error(pc_rtc_error() ? pc_rtc_error() : "pchip_source_eval: the launch failed"); }
         else if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(logL, d_l, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
                  (nDerived == 0 || hipMemcpy(phi, d_p, np, hipMemcpyDeviceToHost) == hipSuccess)) rc = 0;
     }
     if (rc == 2) (void)hipGetLastError();
-    (void)hipFree(d_t); (void)hipFree(d_l); (void)hipFree(d_p);
+    (void)hipFree(d_t); (void)hipFree(d_l); (void)hipFree(d_p); (void)hipFree(d_R); (void)hipFree(d_part);
     return rc;
+}
+
+// The batched quadratic form at the doors that start work on a likelihood / prior pair: what it cannot do, said before any device call.
+// who: the entry point (pchip_run, pchip_run_in_step: a device prior is all they need; any other name: the handle is not taken at all)
+const char *pc_quad_batch_refusal(const char *who, const pchip_like *like, const pchip_prior *prior, int *nres)
+{
+    thread_local std::string msg;
+    if (nres) *nres = 0;
+    PcSourceForm f;
+    if (!like || like->kind != PCHIP_LIKE_SOURCE || pc_rtc_source_form(like->source, &f) != 0 || f.nbatch <= 0) return nullptr;
+    if (nres) *nres = f.nbatch;
+    const std::string me = std::string(who) + ": device source handle " + std::to_string(like->source) + " is a batched quadratic form (pchip_source_create_quad_batch)";
+    const bool runs = std::strcmp(who, "pchip_run") == 0 || std::strcmp(who, "pchip_run_in_step") == 0;
+    if (!runs) { msg = me + " -- not covered: it is evaluated in batches on the matrix cores, by pchip_run, pchip_run_in_step and pchip_source_eval alone"; return msg.c_str(); }
+    if (prior && prior->kind == PCHIP_PRIOR_SOURCE) { msg = me + " and has no prior of its own -- prior.kind = 3 (source prior) is refused: the uniform box (1) or a table (2)"; return msg.c_str(); }
+    if (prior && prior->kind != 1 && prior->kind != PCHIP_PRIOR_TABLE) { msg = me + " -- its blocks stay on the device: a host prior (prior.kind = " + std::to_string(prior->kind) + ") is refused, the uniform box (1) or a table (2)"; return msg.c_str(); }
+    return nullptr;
 }
 
 // ---- a source likelihood under a HOST prior, for the PolyChord-interface doors (pc_abi.hip) ------------------------------------------
@@ -137,6 +164,7 @@ void *pc_source_batch_open(int handle, int device, int nDims, int nDerived, poly
     PcSourceBatch *b = new PcSourceBatch;
     auto refuse = [b](const std::string &msg) { pc_abi_set_last_error(msg.c_str()); pc_source_batch_close(b); return (void *)nullptr; };
     if (!b->src.find(handle)) return refuse(no_handle("", handle));
+    if (b->src.form.nbatch > 0) return refuse("device source handle " + std::to_string(handle) + " is a batched quadratic form (pchip_source_create_quad_batch): a host prior is refused, the uniform box or a prior table");
     if (!prior || nDims < 1 || nDims > 256 || nDerived < 0 || nDerived > PC_SRC_MAX_DERIVED) return refuse("a source likelihood under a host prior: a prior function, 1 <= nDims <= 256, 0 <= nDerived <= 32");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return refuse("no HIP device available -- this engine has no CPU path"); }

@@ -9,7 +9,7 @@
 //     setup, begin, compact_wanted, compact_record, compact_finish
 //     round_enqueue, round_ready, finish_may_wait, round_finish
 //     end_a, end_a2, end_wait_aside, end_b, destroy
-//   TickGroup (pc_tick.h: what runs through the caller's device batch callback share): on, set_up, pack, answer, leave, drop, release
+//   TickGroup (pc_tick.h: what runs through the caller's device batch callback share): ticks, on, set_up, pack, answer, leave, drop, release
 //   these services:
 //     hpool()                      get_stream, put_stream, take_stream_if, get_sync_event, put_sync_event
 //     sclasses()                   known, classify: a stream's hardware-queue class
@@ -74,7 +74,8 @@ struct StepGroup {
     int *h_totals = nullptr; size_t totals_cap = 0;      // compact_full's rows in use, one pinned word per run
     // the likelihood is the caller's device batch callback: the runs' ticks go together (enqueue_as_fibers), their answers share one block (tg),
     // and the caller's function is called on this thread alone
-    const bool ticking = like && like->kind == PCHIP_LIKE_CALLBACK;
+    // (or the library's own evaluator of a batched quadratic form, which goes the same way: TickGroup::ticks says which likelihoods do)
+    const bool ticking = TickGroup::ticks(like);
     TickGroup tg;
     const bool fibers_on = !pc_env().cohort_fibers_off, prof = pc_env().debug == 5;
     StepTimes t;

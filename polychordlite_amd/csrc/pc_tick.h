@@ -5,6 +5,9 @@
 // its members B, S, st, stop, dev_batch, tick_asked, tick_want, tick_count, tick_bind, device_call, tick_answered --, RunBlocks (pc_blocks.h),
 // pc_launch.h and HIPCHK.
 //
+// The library's own evaluator of a batched quadratic form (pchip_source_create_quad_batch, Engine::quad_batch_call) takes the caller's place
+// unchanged: the group's first run that ticked evaluates the rows of all of them, from its own copy of the handle's block.
+//
 // One block of answers for all runs, sized for the sum of their chains a nursery; every run's db_cube / db_theta / db_phi / db_logL point at
 // it, so a run's tick finds its answers at the GLOBAL ranks the pack leaves in the run's rank array, with no change to the tick's indexing.
 // A tick of the group is: the ticks of the runs that wait (Cohort::flush, CK_TICK: one launch), pack(), ONE stream wait, answer().
@@ -22,6 +25,11 @@ struct TickGroup {
     int *d_count = nullptr, *hp_count = nullptr, *hp_count_dev = nullptr;      // counts [64] on the device; pinned: each run's count, then the total
     int who[PC_PARK_MAX_RUNS]; int nask = 0;
     bool on = false;
+
+    // the likelihoods whose runs tick: a callback (behind the caller's device batch callback: pc_run_many's caller has checked that one is
+    // registered) and a batched quadratic form (pchip_source_create_quad_batch), whose evaluator is the library's own
+    static int quad_batch_nres(const pchip_like *like) { int nres = 0; (void)pc_quad_batch_refusal("pchip_run_in_step", like, nullptr, &nres); return nres; }
+    static bool ticks(const pchip_like *like) { return like && (like->kind == PCHIP_LIKE_CALLBACK || quad_batch_nres(like) > 0); }
 
     // Assumes the runs set up and begun (their live points made, each by calls of its own: nprior rows a run), the stream idle.  Leaves the
     // one block allocated and every run bound to it.

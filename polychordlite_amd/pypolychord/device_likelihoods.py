@@ -80,6 +80,8 @@ class Source(_Builtin):
     evaluated inside the sampling kernels.  The arguments are those of `_ctypes_api.source_create`: `source` the text; `data` its data
     block; `nterms` the terms form, `nsums` with it several sums per evaluation; `residuals` / `precision` the quadratic form;
     `shared` that many shared values beside any of these three (pchip_source_create_shared: the text defines pchip_shared_value);
+    `batched=True` with `residuals` / `precision`: the batched quadratic form (pchip_source_create_quad_batch), up to 4096 residuals, a
+    round's proposals evaluated at once on the matrix cores -- under `UniformPrior` or `TablePrior` only, and `maximise=True` is skipped with a message;
     `prior=True`: the text defines pchip_prior_param as well (pass `SourcePrior(this)` as the prior); `options`: -D / -U compiler options.
     The handle is made on first use (RuntimeError with the compiler's log if the text does not compile).  Under `UniformPrior`,
     `TablePrior` or `SourcePrior` the whole run stays on the device; under any other prior callable the prior is called on the host and
@@ -87,7 +89,11 @@ class Source(_Builtin):
     (polychord_hip_source_loglike: one kernel launch a call, for single evaluations).  `close()` destroys the handle."""
     symbol = "polychord_hip_source_loglike"
 
-    def __init__(self, source, nDerived=0, data=None, nterms=None, nsums=None, residuals=None, precision=None, prior=False, options=None, shared=None):
+    def __init__(self, source, nDerived=0, data=None, nterms=None, nsums=None, residuals=None, precision=None, prior=False, options=None, shared=None,
+                 batched=False):
+        if batched and residuals is None:
+            raise ValueError("batched=True is the batched quadratic form: it needs residuals (and precision)")
+        self.batched = bool(batched)
         self.source, self.nDerived, self.data, self.nterms, self.nsums = source, nDerived, data, nterms, nsums
         self.residuals, self.precision, self.prior, self.options = residuals, precision, prior, options
         self.shared = shared
@@ -97,7 +103,8 @@ class Source(_Builtin):
     def handle(self):
         if self._handle is None:
             self._handle = api.source_create(self.source, options=self.options or (), data=self.data, nterms=self.nterms, prior=self.prior,
-                                             nsums=self.nsums, residuals=self.residuals, precision=self.precision, shared=self.shared)
+                                             nsums=self.nsums, residuals=self.residuals, precision=self.precision, shared=self.shared,
+                                             **({"batched": True} if self.batched else {}))
         return self._handle
 
     def configure(self, nDims):

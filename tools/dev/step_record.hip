@@ -369,6 +369,7 @@ struct Engine {
 // (what runs through the caller's device batch callback share, pc_tick.h: the scripted runs have no callback, the group's stays switched off)
 struct TickGroup {
     bool on = false;
+    static bool ticks(const pchip_like *like) { return like && like->kind == PCHIP_LIKE_CALLBACK; }
     void set_up(const std::vector<Engine *> &, const std::vector<char> &, int) {}
     void pack(hipStream_t) {}
     void answer() {}
