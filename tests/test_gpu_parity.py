@@ -646,7 +646,8 @@ def test_clustered_contraction_kernels_agree(engine, kind, D, nDer, nlive, nr, b
     assert b["path"]["consume_general"] > 0 and b["path"]["consume_cl"] == 0
     assert a["ncluster_peak"] >= 2 and a["ncluster_dead"] >= 2          # clusters were found, and clusters died on the way
     # (more than 64 clusters alive at once -- two clusters per lane in the LDS-resident kernels -- needs a live set those kernels' LDS does not take:
-    #  2400 points reach it, through the general kernel; the largest live set that fits holds 40 clusters at its peak)
+    #  2400 points reach it, through the general kernel; of THESE shapes the largest that fits holds 40 clusters at its peak.  Ten and eight dimensions at
+    #  nlive 1000 with a nursery of 128 do fit and pass 64: tests/test_wide_clusters.py runs the `<2>` kernels there, against the oracle and each other)
     if nlive == 2400: assert a["ncluster_peak"] > 64, a["ncluster_peak"]
     if nlive == 1000: assert a["ncluster_peak"] > 32, a["ncluster_peak"]
     for b in (c, b):
