@@ -125,7 +125,8 @@ void pc_launch_scan_blocks(int *blk, int nblk, int *total, int *total2, hipStrea
 void pc_launch_chol_only(const PcState *S, const double *ncov, const int *count, hipStream_t st);
 int pc_post_blocks(void);
 void pc_launch_post_moments(const PcState *S, int nd, double *pmax, double *part, hipStream_t st);
-// ---- pc_engine.hip -----------------------------------------------------------------------------------------
+// ---- pc_engine.hip: Engine, pchip_run[_hooks], the option and cache entry points, the device maximiser (the kernel-level doors of the
+//      tests, declared in polychord_hip.h, are pc_doors.h, which it includes) -----------------------------------------------------------
 // called before several scheduler groups start on a device, while it is idle: the pool gets at least `want` streams
 void pc_prepare_streams(int dev, int want);
 // scratch blocks kept between calls (the driver works frees off for 10 ... 30 ms)

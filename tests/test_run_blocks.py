@@ -4,7 +4,8 @@ CPU: tools/dev/blocks_record -- the ledger's rules over malloc-backed primitives
 address and undefined-behaviour sanitizers.
 GPU (-m gpu): pchip_blocks_in_use counts the blocks the two caches have obtained from the driver and somebody holds.  After a first run
 of a scenario (and pchip_result_free) that count is the baseline; whatever the scenario does afterwards -- the same run again, a run that
-fails at an injected host fault, a host likelihood that raises, runs in step that fail -- must leave it where it was."""
+fails at an injected host fault, a host likelihood that raises, runs in step that fail -- must leave it where it was.  The same for the
+kernel-level doors of the tests (pc_doors.h) and the device maximiser: each twice, and two of them failing at an injected fault."""
 import ctypes as C
 import gc
 import os
@@ -97,6 +98,117 @@ def test_a_run_gives_back_what_it_took(engine, lib, what):
     for _ in range(2):
         once()
         assert _counts(lib) == base
+
+
+# the kernel-level doors (pc_doors.h) and the device maximiser: an engine's ledger or a ledger of their own, given back by the one guard
+def _chains(api, lib, D, nchains, nr):
+    """pchip_slice_chains for nchains chains seeded near the peak of the built-in Gaussian: (code, babies)"""
+    nT = 2 * D + 2
+    L, P, keep = api.make_problem("gaussian", D, 0)
+    seeds = _live_rows(D, nchains)
+    chol = np.ascontiguousarray(0.02 * np.eye(D))
+    babies = np.zeros((nchains, nr, nT))
+    s = _settings(api, D, 0, num_repeats=nr, seed=11)
+    rc = lib.pchip_slice_chains(C.byref(s), C.byref(L), C.byref(P), 5, nchains, api.dptr(seeds), api.dptr(chol), float(seeds[:, -1].min()) - 4.0,
+                                api.dptr(babies), None, None)
+    return rc, babies
+
+
+def _live_rows(D, n):
+    """n rows [cube | theta | birth | logL] of the built-in Gaussian (mu 0.5, sigma 0.1) in the unit box, one cluster"""
+    rows = np.zeros((n, 2 * D + 2))
+    cubes = 0.5 + 0.04 * np.random.default_rng(10 * D + n).standard_normal((n, D))
+    rows[:, :D], rows[:, D:2 * D], rows[:, -2] = cubes, cubes, -1e30
+    rows[:, -1] = -D * (np.log(0.1) + 0.5 * np.log(2 * np.pi)) - 0.5 * np.sum(((cubes - 0.5) / 0.1) ** 2, axis=1)
+    return rows
+
+
+def _maximise(api, D, n, raw=False):
+    """pchip_maximise_device on n rows of the built-in Gaussian: the wrapper's dict, or (raw) the code alone"""
+    L, P, keep = api.make_problem("gaussian", D, 0)
+    s = _settings(api, D, 0, logzero=-1e30)
+    live, cl = _live_rows(D, n), np.zeros(n, dtype=np.int32)
+    if not raw:
+        return api.maximise_device(s, L, P, dict(live=live, live_cluster=cl, post_mean=None))
+    lib, m = api.load(), api.Maximum()
+    rc = lib.pchip_maximise_device(C.byref(s), C.byref(L), C.byref(P), api.dptr(live), cl.ctypes.data_as(C.POINTER(C.c_int)), n, None, 0, C.byref(m))
+    lib.pchip_maximum_free(C.byref(m))
+    return rc
+
+
+def _doors(api, lib):
+    """every door once at a small shape, by name: nDims 2 ... 4, 4 ... 8 chains or rows, one or two clusters"""
+    D, n = 3, 6
+    L, P, keep = api.make_problem("gaussian", D, 0)
+    rows = _live_rows(D, n)
+    chol = np.tril(np.full((D, D), 0.01)) + 0.05 * np.eye(D)
+    s = lambda: _settings(api, D, 0, num_repeats=2 * D, seed=5)
+    rng = np.random.default_rng(3)
+    x = rng.uniform(0.2, 0.8, (8, D)); ph = rng.uniform(0.2, 0.8, (4, D))
+    two = np.vstack([0.2 + 0.01 * rng.standard_normal((4, 2)), 0.8 + 0.01 * rng.standard_normal((4, 2))])
+    need, prop = np.array([1, 0, 1, 1, 0], dtype=np.int32), rng.uniform(size=(5, D))
+
+    def chains():
+        rc, babies = _chains(api, lib, D, n, 2 * D)
+        assert rc == 0
+
+    return {
+        "slice_chains": chains,
+        "directions path 0": lambda: api.directions(s(), L, P, 5, rows, chol, 0),
+        "directions path 1": lambda: api.directions(s(), L, P, 5, rows, chol, 1),
+        "deck_records": lambda: api.deck_records(s(), L, P, 5, n),
+        "prior_transform": lambda: api.prior_transform([("uniform", (0, 1)), ("uniform", (10, 20))], rng.uniform(size=(4, 2))),
+        "park_pack": lambda: api.park_pack(need, prop),
+        "park_pack_many": lambda: api.park_pack_many([3, 2], need, prop),
+        "par_accept": lambda: api.par_accept(np.arange(6.0), np.array([0.5, 2.5, 7.0, 1.5])),
+        "update_factors path 0": lambda: api.update_factors(x, np.array([0, 1] * 4), ph, np.zeros(4), np.array([0, 1, 0, 1]), [-1.0, -1.0], 0),
+        "update_factors path 1": lambda: api.update_factors(x, np.zeros(8, dtype=np.int32), ph, np.zeros(4), np.zeros(4, dtype=np.int32), [-1.0], 1),
+        "cluster_update path 0": lambda: api.cluster_update([dict(live=two, cluster=np.zeros(8, dtype=np.int32))], path=0),
+        "cluster_update path 1": lambda: api.cluster_update([dict(live=two, cluster=np.zeros(8, dtype=np.int32))] * 2, path=1),
+        "maximise_device": lambda: _maximise(api, D, 2 * (D + 1)),
+    }
+
+
+@pytest.mark.gpu
+def test_each_door_gives_back_what_it_took(engine, lib):
+    """every kernel-level door and the device maximiser twice: the caches' counts after the second call are those after the first"""
+    for name, door in _doors(engine, lib).items():
+        door()
+        base = _counts(lib)
+        door()
+        assert _counts(lib) == base, name
+
+
+@pytest.mark.gpu
+def test_a_failed_door_gives_back_what_it_took(engine, lib):
+    """pchip_inject_fault(1) -- the next device block of at least 256 KB is refused: a host exception before any launch -- under
+    pchip_slice_chains and under pchip_maximise_device: each returns 7 (an injection nobody consumed would return 0 and fail here), leaves
+    the counts at the baseline, and the good call after it gives the first good call's output bit for bit.  nDims = 10 is the smallest at
+    which both set-ups ask for such a block whatever the caches round to: the dead points' array, (64 nlive + 4 batch + 1024) rows of
+    2 nDims + 2 doubles, is 1568 x 22 x 8 = 275 968 bytes for eight chains and 1540 x 22 x 8 = 271 040 for the maximiser's engine."""
+    api, D = engine, 10
+    rc, good = _chains(api, lib, D, 8, 4)
+    assert rc == 0
+    base = _counts(lib)
+    lib.pchip_inject_fault(1)
+    rc, _ = _chains(api, lib, D, 8, 4)
+    assert rc == 7
+    assert _counts(lib) == base
+    rc, again = _chains(api, lib, D, 8, 4)
+    assert rc == 0 and again.tobytes() == good.tobytes()
+    assert _counts(lib) == base
+
+    good = _maximise(api, D, 2 * (D + 1))
+    assert good["status"] == [0, 0]
+    base = _counts(lib)
+    lib.pchip_inject_fault(1)
+    assert _maximise(api, D, 2 * (D + 1), raw=True) == 7
+    assert _counts(lib) == base
+    again = _maximise(api, D, 2 * (D + 1))
+    assert _counts(lib) == base
+    assert good.keys() == again.keys()
+    for k, v in good.items():
+        assert (v is None and again[k] is None) or np.asarray(v).tobytes() == np.asarray(again[k]).tobytes(), k
 
 
 @pytest.mark.gpu
